@@ -2,7 +2,12 @@
 """bench.py - images/sec of the fused CamCalib + SPEC + SMPL forward at batch 256 per GPU
 (BASELINE.json config 3; config 4 = the same per-GPU work on N GPUs + one RCCL all-gather).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; ``--dump-outputs DIR`` also writes what the last
+timed step returned as ``DIR/<name>.npy``.  Every other measurement and check (sustained region, per-stage roofline, C2,
+small batches, host hand-over, real-input and demo lines, bf16 piece products, CPU baseline, the N > 1 probe and ``comm``
+block) runs only with ``--full``.
 
 ``--gpus N`` with N > 1 launches the N ranks itself (re-exec under ``torch.distributed.run``, one process per
 GPU, rendezvous on 127.0.0.1) unless it already runs under a launcher (WORLD_SIZE set); it REFUSES to run
@@ -134,6 +139,22 @@ def build_models(device, conv_precision=0):
     hm.to(device).eval().commit(device, freeze=True)
     log(f'[bench] models built + packed in {time.time() - t0:.1f}s')
     return cc, hm, cs, hs
+
+
+def dump_outputs(outdir, out, budget=64 << 20):
+    """The arrays one step handed to its caller as ``outdir/<name>.npy`` (float64 stays float64, all else float32).  Above
+    ``budget`` bytes in all, every array keeps the same fixed, seeded sample of its rows (leading dimension)."""
+    arrays = out if isinstance(out, dict) else {'record': out}
+    host = {k: v.detach().to('cpu', torch.float64 if v.dtype == torch.float64 else torch.float32).numpy()
+            for k, v in arrays.items() if torch.is_tensor(v)}
+    frac = min(1.0, budget / max(1, sum(a.nbytes for a in host.values())))
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in host.items():
+        if frac < 1.0 and a.ndim:
+            keep = max(1, int(a.shape[0] * frac))
+            a = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(outdir, k + '.npy'), a)
+    log(f'[bench] wrote {len(host)} output arrays to {outdir}' + ('' if frac >= 1.0 else f' (seeded {frac:.3f} row sample)'))
 
 
 def make_inputs(B, device, seed):
@@ -501,11 +522,21 @@ def main():
     ap.add_argument('--cpu-baseline-seconds', type=float, default=22.0, help='budget of the CPU oracle timing on rank 0')
     ap.add_argument('--subbatch', type=int, default=-1, help='trunk sub-batch for the early stages (0 = off, -1 = library default)')
     ap.add_argument('--subbatch-layers', type=int, default=-1)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in all)')
+    ap.add_argument('--full', action='store_true', help='also run every secondary measurement and check (see the module docstring); '
+                                                        'the --no-* options switch single ones off again')
     args = ap.parse_args()
 
     if args.gpus < 1:
         log('[bench] ERROR: --gpus must be >= 1')
         sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        log('[bench] ERROR: --steps must be >= 1 and --warmup >= 0')
+        sys.exit(2)
+    if not args.full:    # a plain run does only what the headline needs
+        args.no_profile = args.no_c2 = args.no_small_batch = args.no_e2e = args.no_split_bf16 = True
+        args.no_sustained = args.no_cpu_baseline = True
     fake = args.fake_forward
     if (args.backend == 'gloo') != fake:
         log('[bench] ERROR: --backend gloo and --fake-forward go together (the dry run of the N > 1 control flow); the measured path is nccl = RCCL')
@@ -618,6 +649,8 @@ def main():
             return gather.submit(out, inplace=True)
         return out
 
+    last = {}      # what the latest timed step returned (--dump-outputs)
+
     def timed(nsteps, collect=True):
         sync()
         if use_dist:
@@ -625,7 +658,7 @@ def main():
         sync()
         t0 = time.perf_counter()
         for _ in range(nsteps):
-            step(collect)
+            last['out'] = step(collect)
         if gather is not None:
             gather.drain()
         sync()
@@ -638,7 +671,7 @@ def main():
     # all-gather - the gathered records must equal the unsharded forward of all 16 images bit for bit (plan pinned: an
     # image's bits are batch-invariant within a plan)
     probe_ok = None
-    if use_dist:
+    if use_dist and args.full:
         from spec_amd.pipeline import shard_range
         px, psc, pce, piw, pih = make_inputs(16, device, 424242)          # same seed on every rank
         for m in (cc, hm):
@@ -679,6 +712,8 @@ def main():
         per_rank = [round(B * args.steps / float(v), 1) for v in allt.tolist()]
     ms_per_step = elapsed / args.steps * 1e3
     value = B * n_gpus * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last['out'])
 
     # ---- sustained region: the same step for >= 5 s (clock / thermal steady state) -------------------------
     sustained = None
@@ -694,7 +729,7 @@ def main():
 
     # ---- N > 1: the collective alone ------------------------------------------------------------------------
     comm = None
-    if use_dist:
+    if use_dist and args.full:
         out = pipe(x, scale, center, img_w, img_h)
         sync()
         dist.barrier()

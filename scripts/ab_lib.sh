@@ -2,7 +2,7 @@
 # A/B of two builds of libspecmi.so on one box, alternating: scripts/ab_lib.sh <alternative .so> [reps]
 ALT=$1; REPS=${2:-3}
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
-S="--no-cpu-baseline --no-split-bf16 --no-c2 --no-small-batch --no-sustained --no-e2e --steps 20"
+S="--full --no-cpu-baseline --no-split-bf16 --no-c2 --no-small-batch --no-sustained --no-e2e --steps 20"
 pe() { python -c "
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

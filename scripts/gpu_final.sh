@@ -10,6 +10,6 @@ timeout 600 python tests/parity_report.py > $OUT/${TAG}_parity_report.txt 2>&1; 
 timeout 600 python scripts/gpu_pretrained_like_report.py > $OUT/${TAG}_parity_report_pretrained_like.txt 2>/dev/null; tail -8 $OUT/${TAG}_parity_report_pretrained_like.txt | cut -c1-200
 bash scripts/gpu_prof.sh $TAG all > $OUT/${TAG}_prof.log 2>&1; tail -6 $OUT/${TAG}_prof.log
 cd $R
-timeout 600 python bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; tail -c 900 $OUT/${TAG}_bench.json; echo
+timeout 600 python bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err; tail -c 900 $OUT/${TAG}_bench.json; echo
 cp $OUT/bench_profile.json $OUT/${TAG}_layers.json 2>/dev/null
 bash scripts/gpu_small_batch_evidence.sh $TAG > $OUT/${TAG}_evidence.log 2>&1; grep "^# kernels" $OUT/${TAG}_evidence.log

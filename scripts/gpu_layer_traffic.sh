@@ -8,7 +8,7 @@ OUT=$R/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd $R
-python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-sustained --no-c2 --no-e2e --no-small-batch --no-split-bf16 > /tmp/lt_bench.json 2>/dev/null
+python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-sustained --no-c2 --no-e2e --no-small-batch --no-split-bf16 > /tmp/lt_bench.json 2>/dev/null
 cp $OUT/bench_profile.json /tmp/lt_layers.json
 cd /tmp
 BENCH="python $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-profile --no-overlap --no-graph --no-sustained --no-c2 --no-e2e --no-small-batch --no-split-bf16"

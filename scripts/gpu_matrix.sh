@@ -6,7 +6,7 @@ OUT=$R/gpurun_out; mkdir -p $OUT; cd $R
 i=0
 for flags in "$@"; do
   i=$((i+1))
-  timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline $flags > $OUT/mx_${TAG}_$i.json 2> $OUT/mx_${TAG}_$i.err
+  timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline $flags > $OUT/mx_${TAG}_$i.json 2> $OUT/mx_${TAG}_$i.err
   python - "$OUT/mx_${TAG}_$i.json" "$flags" <<'PY'
 import json,sys
 try:

@@ -16,7 +16,7 @@ if [ "$MODE" = "tests" ]; then
   fi
   tail -30 $OUT/test_$TAG.log
 fi
-timeout 600 python bench.py --steps 20 --warmup 3 > $OUT/bench_${TAG}.json 2> $OUT/bench_${TAG}.err
+timeout 600 python bench.py --full --steps 20 --warmup 3 > $OUT/bench_${TAG}.json 2> $OUT/bench_${TAG}.err
 cp $OUT/bench_profile.json $OUT/bench_${TAG}_layers.json 2>/dev/null
 python - "$OUT/bench_${TAG}.json" <<'PY'
 import json,sys

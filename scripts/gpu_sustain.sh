@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $R
 ( while true; do echo "--- $(date +%s.%N)"; rocm-smi --showclocks --showpower --showtemp --showuse 2>/dev/null | grep -E "sclk|mclk|Power|Temperature|GPU use" ; sleep 2; done ) > $OUT/${TAG}_smi_samples.txt 2>&1 &
 SMI=$!
-timeout 900 python bench.py --steps 20 --warmup 3 --sustained-seconds $SECS --no-cpu-baseline --no-c2 --no-small-batch > $OUT/${TAG}_sustained_bench.json 2> $OUT/${TAG}_sustained_bench.err
+timeout 900 python bench.py --full --steps 20 --warmup 3 --sustained-seconds $SECS --no-cpu-baseline --no-c2 --no-small-batch > $OUT/${TAG}_sustained_bench.json 2> $OUT/${TAG}_sustained_bench.err
 kill $SMI 2>/dev/null
 python - "$OUT/${TAG}_sustained_bench.json" "$OUT/${TAG}_smi_samples.txt" <<'PY'
 import json,sys,re

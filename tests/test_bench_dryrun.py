@@ -8,16 +8,19 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(world, extra=()):
+def _run(world, extra=(), full=True):
     env = dict(os.environ, OMP_NUM_THREADS='2', HIP_VISIBLE_DEVICES='', CUDA_VISIBLE_DEVICES='')
     env.pop('WORLD_SIZE', None); env.pop('RANK', None); env.pop('LOCAL_RANK', None); env.pop('MASTER_PORT', None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(world), '--backend', 'gloo', '--fake-forward', '--steps', '4',
            '--warmup', '1', '--batch', '6', '--sustained-seconds', '0.2', '--cpu-baseline-seconds', '1.5', *extra]
+    if full:                                           # the comm block, the sustained region and the CPU baseline are --full
+        cmd.append('--full')
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -57,6 +60,27 @@ def test_bench_joints_payload_and_eager_steps():
     assert line['comm']['payload'] == 'joints' and line['comm']['sent_bytes_per_image'] == 2496
     assert line['config']['launch'] == 'eager launches' and line['cpu_baseline'] is None
     assert line['comm']['probe_gathered_16_images_equal_unsharded'] is True
+
+
+@pytest.mark.timeout(600)
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full: the headline steps and nothing else; --dump-outputs writes what the last timed step returned, and two runs with
+    the same arguments write the same arrays."""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f'run{i}'
+        line, _ = _run(2, ('--steps', '3', '--dump-outputs', str(d)), full=False)
+        assert line['steps'] == 3 and line['ms_per_step'] > 0 and line['value'] > 0
+        for k in ('metric', 'unit', 'higher_is_better', 'dtype'):
+            assert k in line
+        for k in ('sustained', 'cpu_baseline', 'comm', 'roofline', 'stages', 'c2', 'small_batch', 'e2e_frames', 'e2e_demo', 'split_bf16', 'pcie'):
+            assert line[k] is None, k
+        files = sorted(p.name for p in d.iterdir())
+        assert files == ['record.npy']                        # N > 1: the gathered records, as the caller of the step receives them
+        rec = np.load(d / 'record.npy')
+        assert rec.dtype == np.float32 and rec.shape == (2 * 6, 21294)
+        dumps.append(rec)
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 def test_bench_refuses_mixed_modes():

@@ -306,7 +306,7 @@ def test_bench_dist_path_single_rank(payload):
     persistent receive buffers, comm block with the with / without-collective step times) on one rank."""
     import json
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--dist', '--steps', '3', '--warmup', '1',
-                        '--batch', '32', '--no-cpu-baseline', '--no-profile', '--no-c2', '--sustained-seconds', '0.2', '--gather', payload],
+                        '--batch', '32', '--full', '--no-cpu-baseline', '--no-profile', '--no-c2', '--sustained-seconds', '0.2', '--gather', payload],
                        capture_output=True, text=True, timeout=850, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY='0'))
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
