@@ -31,8 +31,10 @@
  *   - one handle per model instance; a handle is not thread-safe (the reference is
  *     single-threaded) and is driven from ONE stream at a time (its workspaces, split-K slabs and hand-off counters are per
  *     handle: two streams in the same handle at once would share them); distinct handles are independent.
- *   - all arithmetic is IEEE fp32 (reference inference never enables AMP:
- *     spec/config.py:138, spec/tester.py:109-110); index tables are int32.
+ *   - all arithmetic is IEEE fp32 by default; index tables are int32.  The reference's evaluation entry point runs under
+ *     Lightning precision=16 when its config sets TRAINING.USE_AMP (scripts/spec_eval.py:63-70, spec/config.py:138, default
+ *     false): specmi_set_precision(h, SPECMI_PRECISION_FP16) selects the matching reduced-precision ResNet trunk (fp16
+ *     activations and weights, fp32 accumulation; "precision" section below).  Heads, decode and SMPL stay fp32 either way.
  */
 #ifndef SPECMI_H
 #define SPECMI_H
@@ -184,6 +186,23 @@ int specmi_set_tensor_i32(specmi_handle* h, const char* name, const int32_t* hos
 /* Validate, fold BN, pack and upload to HBM.  May be called again after further set_* calls. */
 int specmi_commit(specmi_handle* h);
 
+/* ---- precision (the reference's TRAINING.USE_AMP switch) ----------------------------------------------------------------
+ * Model state that specmi_commit reads, not an option.  SPECMI_PRECISION_FP32 (default): every path as documented above.
+ * SPECMI_PRECISION_FP16: the ResNet trunk (every convolution and the max-pool) runs on fp16 activations with the BatchNorm
+ * scale folded into fp16 weights, fp16 x fp16 products accumulated in fp32 on the fp16 matrix cores, an fp32 epilogue
+ * (shift, fp16 residual, ReLU) rounded to nearest even into fp16; the last convolution of layer4 stores fp32, and the
+ * avg-pool, heads, decode, SMPL and projection run unchanged in fp32 (numeric contract: DESIGN.md, "fp16 trunk").
+ *   - the fp16 weights are packed at specmi_commit; a forward on a handle whose precision changed since its last successful
+ *     commit returns SPECMI_ERR_STATE.  Commit returns SPECMI_ERR_ARG, naming the layer, when a folded weight lies outside
+ *     the finite fp16 range (never silently inf), and for the HRNet backbones (not built at fp16).
+ *   - one kernel family at every batch size and resolution: options "plan", "winograd", "persist", "wsplit", the latency_* /
+ *     trunk_subbatch tuning and "conv_precision" do not apply to the fp16 trunk; an image's bits do not depend on B.
+ *   - specmi_trunk_forward_pair with either handle at fp16 runs as two specmi_trunk_forward calls on the stream (same bits). */
+enum { SPECMI_PRECISION_FP32 = 0, SPECMI_PRECISION_FP16 = 1 };
+int specmi_set_precision(specmi_handle* h, int precision);
+/* the precision last set (what the next commit packs) */
+int specmi_get_precision(specmi_handle* h, int* precision);
+
 /* ---- forward: CamCalib ----------------------------------------------------------------- */
 
 /* (The execution plan - option "plan" above - is chosen from the FIRST handle's options and B, H, W for both trunks.)
@@ -305,6 +324,18 @@ int specmi_conv2d(specmi_handle* h, const float* x, int B, int H, int W, int Cin
                   const float* w_oihw_host, const float* scale_host, const float* shift_host,
                   int Cout, int KH, int KW, int stride, int pad, const float* residual,
                   int relu, float* out, void* stream);
+
+/* One fused layer of the fp16 trunk (conv_f16.hip), as specmi_conv2d is for the fp32 one.  x (B,H,W,Cp) fp16 NHWC device,
+ * Cp = Cin rounded up to a multiple of 8 (channels past Cin zero); w (Cout,Cin,KH,KW) OIHW fp32 HOST and scale / shift (Cout)
+ * fp32 HOST are folded exactly as specmi_commit folds them: weights fp16_rne(w * scale) from the fp64 product (SPECMI_ERR_ARG
+ * if one overflows fp16), shift added in fp32.  residual (B,OH,OW,Cout) fp16 NHWC device or NULL; out (B,OH,OW,Cout) NHWC
+ * device, fp16 (out_f32 = 0) or fp32 (out_f32 = 1).  Cout % 4 == 0; device pointers 16-byte aligned.  Optional second A source
+ * (the folded downsample): x2 (B,H2,W2,Cin2) fp16 NHWC read at pixel (oy*stride2, ox*stride2) and concatenated after x along
+ * K; w is then (Cout, Cin+Cin2, 1, 1), the layer 1x1 / stride 1 and Cin, Cin2 multiples of 32.  Synchronises the stream. */
+int specmi_conv2d_f16(specmi_handle* h, const void* x, int B, int H, int W, int Cin,
+                      const float* w_oihw_host, const float* scale_host, const float* shift_host,
+                      int Cout, int KH, int KW, int stride, int pad, const void* residual, int relu,
+                      void* out, int out_f32, const void* x2, int H2, int W2, int Cin2, int stride2, void* stream);
 
 /* MaxPool2d(3,2,1) and global average pool on NHWC device tensors (trunk building blocks). */
 int specmi_maxpool3x3s2(specmi_handle* h, const float* x, int B, int H, int W, int C,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Throughput of the non-headline model variants of the path, one JSON line each:
-HMR on the HRNet-W32 / W48 trunks (spec/models/hmr.py:44-51) and CamCalib on ResNet-34 (camcalib/config.py:81).
-Not the BASELINE.json metric (bench.py measures that); numbers quoted in DESIGN.md section 7."""
+HMR on the HRNet-W32 / W48 trunks (spec/models/hmr.py:44-51) and CamCalib on ResNet-34 (camcalib/config.py:81); ``--fp16``:
+the C3 step (CamCalib + SPEC + SMPL) with the fp16 trunk (TRAINING.USE_AMP) against fp32, timed alternately in one process,
+with a parity block.  Not the BASELINE.json metric (bench.py measures that); numbers quoted in DESIGN.md section 7."""
 import argparse
 import json
 import os
@@ -33,6 +34,9 @@ def main():
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--only', default='', help='comma-separated backbones (default: all)')
     ap.add_argument('--labels', type=int, default=0, help='also print the N most expensive (kernel, layer group) rows')
+    ap.add_argument('--fp16', action='store_true', help='only the fp16-trunk C3 step against fp32 (one JSON line)')
+    ap.add_argument('--rounds', type=int, default=3, help='--fp16: alternating fp32 / fp16 timing rounds')
+    ap.add_argument('--layers', action='store_true', help='--fp16: also print every fp16 trunk launch against its binding roof')
     args = ap.parse_args()
     from spec_amd import assets, synth
     from spec_amd.cam_utils import cam_params_from_angles
@@ -45,6 +49,8 @@ def main():
     x = t(synth.images(3, 16)).to(dev).repeat(B // 16 + 1, 1, 1, 1)[:B].contiguous()
     sc, ce, iw, ih = [t(a).to(dev) for a in synth.bbox_inputs(3, B, 224., 224., jitter=False)]
     R, K = cam_params_from_angles(np.full(B, 0.1, np.float32), np.full(B, -0.05, np.float32), np.full(B, 300., np.float32), iw, ih)
+    if args.fp16:
+        return fp16_step(args, dev, t, x, sc, ce, iw, ih)
     for backbone in ('hrnet_w32-conv', 'hrnet_w32-interp', 'hrnet_w48-conv', 'resnet50'):
         if args.only and backbone not in args.only.split(','):
             continue
@@ -84,6 +90,73 @@ def main():
     ms = timed(lambda: cc(x), args.steps)
     print(json.dumps({'variant': 'CameraRegressorNetwork(resnet34) forward', 'batch': B, 'ms_per_step': round(ms, 3),
                       'images_per_s': round(B * 1e3 / ms, 1)}), flush=True)
+
+
+def fp16_step(args, dev, t, x, sc, ce, iw, ih):
+    """The C3 step (SpecPipeline: CamCalib -> decode -> SPEC -> SMPL -> projection) at fp32 and with the fp16 trunk on both
+    networks, synthetic weights and crops, timed alternately (args.rounds rounds of >= 20 steps each after warming up every
+    shape), plus a parity block of fp16 against fp32 on the same inputs."""
+    from spec_amd import synth
+    from spec_amd.modules import HMR, CameraRegressorNetwork
+    from spec_amd.pipeline import SpecPipeline
+    B = x.shape[0]
+    pipes = {}
+    for prec in ('fp32', 'fp16'):
+        cc = CameraRegressorNetwork()
+        cc.load_state_dict({k: t(v) for k, v in synth.camcalib_state(1001).items()})
+        hm = HMR(use_cam=True, use_cam_feats=True)
+        hm.load_state_dict({k: t(v) for k, v in synth.hmr_state(1002, True).items()}, strict=False)
+        for m in (cc, hm):
+            m.set_precision(prec)
+            m.to(dev).eval().commit(dev, freeze=True)
+        pipes[prec] = SpecPipeline(cc, hm)
+    steps = max(20, args.steps)
+    ms = {'fp32': [], 'fp16': []}
+    for _ in range(args.rounds):
+        for prec in ('fp32', 'fp16'):
+            ms[prec].append(timed(lambda: pipes[prec](x, sc, ce, iw, ih), steps))
+    o32 = {k: v.clone() for k, v in pipes['fp32'](x, sc, ce, iw, ih).items()}
+    o16 = pipes['fp16'](x, sc, ce, iw, ih)
+    torch.cuda.synchronize()
+    v32, v16 = o32['smpl_vertices'].double(), o16['smpl_vertices'].double()
+    mpjpe = (o16['smpl_joints3d'].double() - o32['smpl_joints3d'].double()).norm(dim=-1).mean(dim=-1) * 1000.0
+    ang = {k: float(((o16['cam_' + k].double() - o32['cam_' + k].double()).abs().max()) * 180.0 / np.pi) for k in ('vfov', 'pitch', 'roll')}
+    med = {p: float(np.median(v)) for p, v in ms.items()}
+    print(json.dumps({'variant': 'C3 step fp16 trunk (TRAINING.USE_AMP) vs fp32', 'batch': B, 'steps_per_round': steps,
+                      'rounds_ms_fp32': [round(v, 3) for v in ms['fp32']], 'rounds_ms_fp16': [round(v, 3) for v in ms['fp16']],
+                      'ms_per_step_fp32': round(med['fp32'], 3), 'ms_per_step_fp16': round(med['fp16'], 3),
+                      'images_per_s_fp32': round(B * 1e3 / med['fp32'], 1), 'images_per_s_fp16': round(B * 1e3 / med['fp16'], 1),
+                      'ratio_fp16_over_fp32': round(med['fp16'] / med['fp32'], 4),
+                      'parity': {'max_rel_vertex_err': float((v16 - v32).abs().max() / v32.abs().max()),
+                                 'mpjpe_mm_mean': float(mpjpe.mean()), 'mpjpe_mm_max': float(mpjpe.max()),
+                                 'camcalib_angle_deg_max': ang}}), flush=True)
+    if args.layers:
+        layer_roofs(pipes['fp16'].hmr.engine(dev), x)
+
+
+# binding roofs of MI355X (MI355X_MICROARCH.md): dense fp16 MFMA ~2.5 PF, HBM3E 8.0 TB/s peak
+PEAK_F16_FLOPS, PEAK_HBM_BYTES = 2.5e15, 8.0e12
+
+
+def layer_roofs(eng, x):
+    """Every launch of one fp16 trunk forward (built-in profiler: algorithmic FLOPs, and bytes at 2 B per fp16 element) against its
+    binding roof: roof time = max(FLOPs / fp16 MFMA peak, bytes / HBM peak), share = roof time / measured time."""
+    eng.trunk(x)
+    torch.cuda.synchronize()
+    eng.profile(True)
+    eng.trunk(x)
+    torch.cuda.synchronize()
+    prof = eng.profile_read()
+    eng.profile(False)
+    tot = sum(e['ms'] for e in prof)
+    print(f'{"layer":<40s} {"kernel":<28s} {"ms":>8s} {"TF/s":>8s} {"TB/s":>7s} {"bound":>6s} {"share of roof":>13s}')
+    for e in prof:
+        t_f, t_b = e['flops'] / PEAK_F16_FLOPS * 1e3, e['bytes'] / PEAK_HBM_BYTES * 1e3
+        print(f'{e["label"]:<40s} {e["kernel"]:<28s} {e["ms"]:8.3f} {e["flops"] / e["ms"] / 1e9:8.1f} {e["bytes"] / e["ms"] / 1e9:7.2f} '
+              f'{"mfma" if t_f >= t_b else "hbm":>6s} {max(t_f, t_b) / e["ms"]:13.3f}')
+    fl = sum(e['flops'] for e in prof)
+    print(f'trunk B={x.shape[0]}: {tot:.3f} ms, {fl / 1e12:.3f} TFLOP, {fl / tot / 1e9:.1f} TF/s = {fl / tot * 1e3 / PEAK_F16_FLOPS:.3f} of the fp16 MFMA peak',
+          flush=True)
 
 
 if __name__ == '__main__':

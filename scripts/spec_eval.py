@@ -101,7 +101,8 @@ def main():
     if args.report:
         import json
         rep = {'config': cfg, 'checkpoint': ckpt or hp['TRAINING']['PRETRAINED_LIT'], 'data_root': os.path.abspath(root),
-               'standin_tree': bool(args.standin), 'limit': args.limit, 'target_abs_delta_wmpjpe_mm': 0.1, 'datasets': {}}
+               'standin_tree': bool(args.standin), 'limit': args.limit, 'target_abs_delta_wmpjpe_mm': 0.1,
+               'precision': evaluation.eval_precision(hp), 'datasets': {}}
         ok = True
         for name, res in results.items():
             m, ref = res['mean'], evaluation.README_TABLE.get(name)

@@ -30,6 +30,7 @@ def source_hash() -> str:
 
 
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_MISSING = 0, 1, 2, 3, 4
+PRECISION_FP32, PRECISION_FP16 = 0, 1       # SPECMI_PRECISION_* (include/specmi.h)
 MODEL_CAMCALIB, MODEL_HMR, MODEL_SMPL = 0, 1, 2
 
 c_float_p = C.POINTER(C.c_float)
@@ -99,6 +100,12 @@ PROTOTYPES = {
     'specmi_conv2d': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'specmi_conv2d_f16': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                    C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    'specmi_set_precision': (C.c_int, [C.c_void_p, C.c_int]),
+    'specmi_get_precision': (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     'specmi_maxpool3x3s2': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_void_p]),
     'specmi_avgpool': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

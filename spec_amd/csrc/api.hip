@@ -486,7 +486,7 @@ static void plan_trunk(specmi_handle* h, int H, int W, bool to_caller, TrunkPlan
         add(bk.c1, xi, t1, -1, ch, cw, ch, cw, 1, ".conv1");
         add(bk.c2, t1, t2, -1, ch, cw, oh, ow, 1, ".conv2");
         int identity = xi;
-        const bool fuse = bk.has_ds && bk.f_w && opt_i(h, "fuse_downsample", 1);
+        const bool fuse = bk.has_ds && (bk.f_w || bk.f_w16) && opt_i(h, "fuse_downsample", 1);
         if (bk.has_ds && !fuse) {
             add(bk.ds, xi, idb, -1, ch, cw, oh, ow, 0, ".downsample");
             identity = idb;
@@ -621,6 +621,52 @@ static int launch_ops(specmi_handle* ha, specmi_handle* hb, const TrunkPlan& Pa,
     return SPECMI_OK;
 }
 
+// The fp16 trunk (precision SPECMI_PRECISION_FP16, conv_f16.hip): the same op list and ping-pong buffers as the fp32 trunk,
+// holding fp16 NHWC activations (half the bytes of the fp32 workspace the same warm-up rule sizes: nothing is allocated under
+// graph capture).  The image is converted into act[1] (free until the max-pool writes it), every convolution - the stem
+// included - is one conv_f16 launch, and the last one stores fp32 for the heads.  One kernel family at every batch size:
+// plan, Winograd, persistent / wave-split / sub-batch options do not apply.
+static int run_trunk_f16(specmi_handle* h, const float* images, int B, int H, int W, float* feat_out, const float** feat,
+                         int* fh, int* fw, hipStream_t s) {
+    TrunkPlan P;
+    plan_trunk(h, H, W, feat_out != nullptr, P);
+    auto buf = [&](int idx) -> void* { return idx == -2 ? static_cast<void*>(feat_out) : static_cast<void*>(h->act[idx]); };
+    const size_t n = P.ops.size();
+    for (size_t i = 0; i < n; ++i) {
+        const TrunkOp& op = P.ops[i];
+        LaunchCtx ctx{s, &h->prof, op.label.c_str()};
+        if (op.kind == 1) {
+            LAUNCHCHK(h, launch_maxpool_f16(buf(op.in_buf), buf(op.out_buf), B, op.H, op.W, 64, op.OH, op.OW, ctx), "maxpool_f16");
+            continue;
+        }
+        ConvF16Args a;
+        const ConvW& c = op.kind == 0 ? h->stem : *op.c;
+        if (op.kind == 0) {
+            LaunchCtx cctx{s, &h->prof, "backbone.input_f16"};
+            LAUNCHCHK(h, launch_to_nhwc_f16(images, h->act[1], B, 3, H, W, cctx), "to_nhwc_f16");
+            a.x = h->act[1]; a.ldx = 8;
+        } else {
+            a.x = buf(op.in_buf); a.ldx = c.cin;
+        }
+        a.w = c.w16; a.shift = c.shift; a.Kp = c.Kp16; a.Npad = c.Npad;
+        a.res = op.res_buf == -1 ? nullptr : buf(op.res_buf);
+        a.out = buf(op.out_buf);
+        a.B = B; a.H = op.H; a.W = op.W; a.Cin = c.cin; a.OH = op.OH; a.OW = op.OW; a.Cout = c.cout; a.ldo = c.cout;
+        a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad; a.relu = op.relu;
+        a.out_f32 = i + 1 == n;
+        if (op.fused) {
+            const Bneck& bk = *op.fused;
+            a.w = bk.f_w16; a.shift = bk.f_shift; a.Npad = bk.f_Npad; a.Kp = c.cin + bk.ds.cin;
+            a.x2 = buf(op.in2_buf); a.H2 = op.H2; a.W2 = op.W2; a.ldx2 = bk.ds.cin; a.Cin2 = bk.ds.cin; a.stride2 = bk.ds.stride;
+        }
+        if (!a.w) return fail(h, SPECMI_ERR_STATE, "%s: no fp16 weights (commit at SPECMI_PRECISION_FP16 first)", op.label.c_str());
+        LAUNCHCHK(h, launch_conv_f16(a, ctx), op.label.c_str());
+    }
+    *feat = P.final_buf == -2 ? feat_out : h->act[P.final_buf];
+    *fh = P.fh; *fw = P.fw;
+    return SPECMI_OK;
+}
+
 // images NCHW -> layer4 map NHWC in *feat (a workspace buffer unless feat_out given).
 // Option "trunk_subbatch" = S > 0: the stem, the max-pool and the first "trunk_subbatch_layers"
 // ResNet stages are run S images at a time (activations of a slice are <= 103 MB at S = 32 and stay
@@ -635,6 +681,7 @@ static int run_trunk(specmi_handle* h, const float* images, int B, int H, int W,
         *feat = feat_out ? feat_out : hrnet_feat_ws(h);
         return SPECMI_OK;
     }
+    if (h->committed_precision == SPECMI_PRECISION_FP16) return run_trunk_f16(h, images, B, H, W, feat_out, feat, fh, fw, s);
     TrunkPlan P;
     plan_trunk(h, H, W, feat_out != nullptr, P);
     const std::vector<TrunkOp>& ops = P.ops;
@@ -667,6 +714,13 @@ static int run_trunk_pair(specmi_handle* ha, specmi_handle* hb, const float* img
                           float* feat_a, float* feat_b, hipStream_t s) {
     int rc;
     if (H < 32 || W < 32) return fail(ha, SPECMI_ERR_ARG, "image size %dx%d too small", H, W);
+    if (ha->committed_precision == SPECMI_PRECISION_FP16 || hb->committed_precision == SPECMI_PRECISION_FP16) {
+        // the fp16 trunk has no grouped launches: two single-trunk calls on the stream (the same bits as two calls, by definition)
+        const float* f; int fh, fw;
+        if ((rc = run_trunk(ha, img_a, B, H, W, feat_a, &f, &fh, &fw, s))) return rc;
+        if ((rc = run_trunk(hb, img_b, B, H, W, feat_b, &f, &fh, &fw, s))) { ha->err = hb->err; return rc; }
+        return SPECMI_OK;
+    }
     if ((rc = ensure_ws(ha, B, H, W))) return rc;
     if ((rc = ensure_ws(hb, B, H, W))) { ha->err = hb->err; return rc; }
     TrunkPlan Pa, Pb;
@@ -894,6 +948,7 @@ int specmi_commit(specmi_handle* h) {
         free_pool(h->ws_allocs);
         h->act_elems = 0; h->ws_B = 0;
         h->committed = true;
+        h->committed_precision = h->precision;
         return SPECMI_OK;
     }
     const std::string bp = "backbone.";
@@ -902,6 +957,8 @@ int specmi_commit(specmi_handle* h) {
         return fail(h, SPECMI_ERR_ARG, "backbone %d: resnet18 / 34 / 50 / 101 / 152, hrnet_w32 (32) and hrnet_w48 (48) are built", depth);
     if ((depth == 32 || depth == 48) && h->kind != SPECMI_MODEL_HMR)
         return fail(h, SPECMI_ERR_ARG, "the HRNet trunks belong to HMR (camcalib/model.py:33 builds resnet trunks only)");
+    if ((depth == 32 || depth == 48) && h->precision != SPECMI_PRECISION_FP32)
+        return fail(h, SPECMI_ERR_ARG, "the HRNet backbones are built at SPECMI_PRECISION_FP32 only");
     if (h->hrnet) { hrnet_free(h->hrnet); h->hrnet = nullptr; }
     if (depth == 32 || depth == 48) {
         h->blocks.clear();
@@ -960,6 +1017,7 @@ int specmi_commit(specmi_handle* h) {
         h->act_elems = 0; h->ws_B = 0;
     }
     h->committed = true;
+    h->committed_precision = h->precision;
     return SPECMI_OK;
 }
 
@@ -969,7 +1027,9 @@ int specmi_commit(specmi_handle* h) {
     HIPCHK(h, dev_guard__.enter((h)->device));
 
 #define NEED_COMMIT(h) \
-    if (!(h)->committed) return fail(h, SPECMI_ERR_STATE, "specmi_commit has not succeeded on this handle");
+    if (!(h)->committed) return fail(h, SPECMI_ERR_STATE, "specmi_commit has not succeeded on this handle"); \
+    if ((h)->precision != (h)->committed_precision) \
+        return fail(h, SPECMI_ERR_STATE, "the precision changed since the last specmi_commit: commit again");
 
 int specmi_trunk_forward(specmi_handle* h, const float* images, int B, int H, int W, float* feat, void* stream) {
     ENTER(h); NEED_COMMIT(h);
@@ -985,6 +1045,8 @@ int specmi_trunk_forward_pair(specmi_handle* ha, specmi_handle* hb, const float*
     ENTER(ha); NEED_COMMIT(ha);
     if (!hb) return fail(ha, SPECMI_ERR_ARG, "second handle is NULL");
     if (!hb->committed) return fail(ha, SPECMI_ERR_STATE, "second handle not committed");
+    if (hb->precision != hb->committed_precision)
+        return fail(ha, SPECMI_ERR_STATE, "the precision of the second handle changed since its last specmi_commit: commit again");
     if (hb->device != ha->device) return fail(ha, SPECMI_ERR_ARG, "the two handles live on different devices");
     if (!images_a || !images_b || !feat_a || !feat_b || B <= 0) return fail(ha, SPECMI_ERR_ARG, "bad argument");
     if (ha->hrnet || hb->hrnet || ha->blocks.size() != hb->blocks.size() || ha->blocks.empty() ||
@@ -1319,6 +1381,62 @@ int specmi_conv2d(specmi_handle* h, const float* x, int B, int H, int W, int Cin
     free_pool(tmp);
     if (lrc) return fail(h, SPECMI_ERR_HIP, "conv2d launch failed: %s", hipGetErrorString((hipError_t)lrc));
     if (se != hipSuccess) return fail(h, SPECMI_ERR_HIP, "conv2d failed: %s", hipGetErrorString(se));
+    return SPECMI_OK;
+}
+
+int specmi_set_precision(specmi_handle* h, int precision) {
+    if (!h) return SPECMI_ERR_ARG;
+    if (precision != SPECMI_PRECISION_FP32 && precision != SPECMI_PRECISION_FP16)
+        return fail(h, SPECMI_ERR_ARG, "precision %d: SPECMI_PRECISION_FP32 (0) or SPECMI_PRECISION_FP16 (1)", precision);
+    h->precision = precision;
+    return SPECMI_OK;
+}
+
+int specmi_get_precision(specmi_handle* h, int* precision) {
+    if (!h || !precision) return h ? fail(h, SPECMI_ERR_ARG, "precision is NULL") : SPECMI_ERR_ARG;
+    *precision = h->precision;
+    return SPECMI_OK;
+}
+
+int specmi_conv2d_f16(specmi_handle* h, const void* x, int B, int H, int W, int Cin, const float* w_host, const float* scale_host,
+                      const float* shift_host, int Cout, int KH, int KW, int stride, int pad, const void* residual, int relu,
+                      void* out, int out_f32, const void* x2, int H2, int W2, int Cin2, int stride2, void* stream) {
+    ENTER(h);
+    if (!x || !w_host || !scale_host || !shift_host || !out || B <= 0 || Cin <= 0 || Cout <= 0 || KH != KW || KH < 1 || stride < 1 ||
+        pad < 0 || (x2 && (Cin2 <= 0 || stride2 < 1)))
+        return fail(h, SPECMI_ERR_ARG, "bad argument");
+    const int OH = conv_out(H, KH, stride, pad), OW = conv_out(W, KW, stride, pad);
+    if (OH < 1 || OW < 1) return fail(h, SPECMI_ERR_ARG, "empty output");
+    const int Npad = round_up(Cout, 64), cin_p = round_up(Cin, 8);
+    const int Ktot = x2 ? Cin + Cin2 : Cin;        // input channels of w
+    std::vector<double> wk;
+    fold_f16_oihw(w_host, scale_host, Cout, Ktot, x2 ? Ktot : cin_p, KH, KW, wk);
+    const int K = x2 ? Ktot : cin_p * KH * KW, Kp = x2 ? K : round_up(K, 32);
+    std::vector<unsigned short> w16;
+    const long bad = pack_f16_weights(wk, Cout, K, Kp, Npad, w16);
+    if (bad >= 0) return fail(h, SPECMI_ERR_ARG, "folded weight %g (output channel %ld) is outside the finite fp16 range", wk[(size_t)bad], bad / K);
+    std::vector<float> sh(Npad, 0.f);
+    std::memcpy(sh.data(), shift_host, (size_t)Cout * 4);
+    std::vector<void*> tmp;
+    void *dw = nullptr, *dsh = nullptr;
+    int rc;
+    if ((rc = dev_upload(h, w16.data(), w16.size() * 2, &dw, tmp)) || (rc = dev_upload(h, sh.data(), sh.size() * 4, &dsh, tmp))) {
+        free_pool(tmp);
+        return rc;
+    }
+    ConvF16Args a;
+    a.x = x; a.w = dw; a.shift = static_cast<const float*>(dsh); a.res = residual; a.out = out;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldx = x2 ? Cin : cin_p; a.OH = OH; a.OW = OW; a.Cout = Cout; a.Npad = Npad; a.ldo = Cout;
+    a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.relu = relu; a.out_f32 = out_f32 ? 1 : 0; a.Kp = Kp;
+    a.x2 = x2; a.H2 = H2; a.W2 = W2; a.ldx2 = Cin2; a.Cin2 = Cin2; a.stride2 = stride2;
+    hipStream_t s = (hipStream_t)stream;
+    LaunchCtx ctx{s, &h->prof, "conv2d_f16"};
+    const int lrc = launch_conv_f16(a, ctx);
+    hipError_t se = hipStreamSynchronize(s);
+    free_pool(tmp);
+    if (lrc == (int)hipErrorInvalidValue) return fail(h, SPECMI_ERR_ARG, "conv2d_f16: shape or alignment not supported");
+    if (lrc) return fail(h, SPECMI_ERR_HIP, "conv2d_f16 launch failed: %s", hipGetErrorString((hipError_t)lrc));
+    if (se != hipSuccess) return fail(h, SPECMI_ERR_HIP, "conv2d_f16 failed: %s", hipGetErrorString(se));
     return SPECMI_OK;
 }
 

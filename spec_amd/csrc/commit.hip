@@ -97,21 +97,39 @@ int commit_conv(specmi_handle* h, const std::string& prefix, ConvW& c) {
         pack_gemm_weights(wsrc, cout, cin, c.k, c.k, c.Kp, c.Npad, packed);
     }
     fold_bn(g->f.data(), b->f.data(), m->f.data(), v->f.data(), c.cout, 1e-5f, c.Npad > cout ? c.Npad : cout, scale, shift);
-    if ((rc = dev_upload(h, packed.data(), packed.size() * 4, (void**)&c.w, h->param_allocs))) return rc;
+    // at SPECMI_PRECISION_FP16 the trunk reads only the fp16 weights and the fp32 shift: the fp32 weight forms are not uploaded
+    const bool fp32_forms = h->precision != SPECMI_PRECISION_FP16;
+    c.w = nullptr;
+    if (fp32_forms && (rc = dev_upload(h, packed.data(), packed.size() * 4, (void**)&c.w, h->param_allocs))) return rc;
     if ((rc = dev_upload(h, scale.data(), scale.size() * 4, (void**)&c.scale, h->param_allocs))) return rc;
     if ((rc = dev_upload(h, shift.data(), shift.size() * 4, (void**)&c.shift, h->param_allocs))) return rc;
     c.wino = nullptr;
-    if (c.k == 3 && c.stride == 1 && c.pad == 1 && cin % 16 == 0 && (cout % 64 == 0 || (cout % 32 == 0 && cout > 64))) {
+    if (fp32_forms && c.k == 3 && c.stride == 1 && c.pad == 1 && cin % 16 == 0 && (cout % 64 == 0 || (cout % 32 == 0 && cout > 64))) {
         std::vector<float> u;
         pack_wino_weights(wsrc, cout, cin, u);
         if ((rc = dev_upload(h, u.data(), u.size() * 4, (void**)&c.wino, h->param_allocs))) return rc;
     }
     // optional split-bf16 path (conv_bf16s.hip): the weights of the plain 1x1 / stride-1 layers as three bf16 pieces
     c.wsplit = nullptr;
-    if (opt_i(h, "conv_precision", 0) != 0 && (c.k == 1 || c.k == 3) && cin % 16 == 0 && cout % 4 == 0) {
+    if (fp32_forms && opt_i(h, "conv_precision", 0) != 0 && (c.k == 1 || c.k == 3) && cin % 16 == 0 && cout % 4 == 0) {
         std::vector<unsigned short> pieces;
         pack_bf16_split_weights_oihw(wsrc, cout, cin, c.k, c.k, c.Npad, pieces);
         if ((rc = dev_upload(h, pieces.data(), pieces.size() * 2, &c.wsplit, h->param_allocs))) return rc;
+    }
+    // fp16 trunk path (conv_f16.hip): fp16_rne(w * scale), the products in fp64, channels padded to a multiple of 8
+    c.w16 = nullptr;
+    c.Kp16 = 0;
+    if (h->precision == SPECMI_PRECISION_FP16) {
+        const int cin_p = round_up(cin, 8), K = cin_p * c.k * c.k;
+        std::vector<double> wk;
+        std::vector<unsigned short> w16;
+        fold_f16_oihw(wsrc, scale.data(), cout, cin, cin_p, c.k, c.k, wk);
+        c.Kp16 = round_up(K, 32);
+        const long bad = pack_f16_weights(wk, cout, K, c.Kp16, c.Npad, w16);
+        if (bad >= 0)
+            return fail(h, SPECMI_ERR_ARG, "layer '%s%s': folded weight %g (output channel %ld) is outside the finite fp16 range",
+                        prefix.c_str(), c.name.c_str(), wk[(size_t)bad], bad / K);
+        if ((rc = dev_upload(h, w16.data(), w16.size() * 2, &c.w16, h->param_allocs))) return rc;
     }
     return SPECMI_OK;
 }
@@ -141,16 +159,32 @@ int commit_fused_ds(specmi_handle* h, const std::string& prefix, Bneck& b) {
         for (int k = 0; k < K2; ++k) wcat[(size_t)n * K + K1 + k] = (float)((double)wd->f[(size_t)n * K2 + k] * (double)sd[n]);
         shift[n] = h3[n] + hd[n];
     }
-    pack_gemm_weights(wcat.data(), N, K, 1, 1, K, Npad, packed);
+    const bool fp32_forms = h->precision != SPECMI_PRECISION_FP16;   // fp16: only f_w16 and f_shift are read
+    if (fp32_forms) pack_gemm_weights(wcat.data(), N, K, 1, 1, K, Npad, packed);
     b.f_Npad = Npad;
     b.f_wsplit = nullptr;
-    if (opt_i(h, "conv_precision", 0) != 0 && K1 % 16 == 0 && K2 % 16 == 0 && N % 4 == 0) {
+    b.f_w = b.f_scale = nullptr;
+    if (fp32_forms && opt_i(h, "conv_precision", 0) != 0 && K1 % 16 == 0 && K2 % 16 == 0 && N % 4 == 0) {
         std::vector<unsigned short> pieces;
         pack_bf16_split_weights(wcat.data(), N, K, Npad, pieces);
         if ((rc = dev_upload(h, pieces.data(), pieces.size() * 2, &b.f_wsplit, h->param_allocs))) return rc;
     }
-    if ((rc = dev_upload(h, packed.data(), packed.size() * 4, (void**)&b.f_w, h->param_allocs))) return rc;
-    if ((rc = dev_upload(h, ones.data(), ones.size() * 4, (void**)&b.f_scale, h->param_allocs))) return rc;
+    b.f_w16 = nullptr;
+    if (h->precision == SPECMI_PRECISION_FP16) {   // the same fold, rounded once to fp16 from the fp64 products
+        std::vector<double> wk((size_t)N * K);
+        for (int n = 0; n < N; ++n) {
+            for (int k = 0; k < K1; ++k) wk[(size_t)n * K + k] = (double)w3->f[(size_t)n * K1 + k] * (double)s3[n];
+            for (int k = 0; k < K2; ++k) wk[(size_t)n * K + K1 + k] = (double)wd->f[(size_t)n * K2 + k] * (double)sd[n];
+        }
+        std::vector<unsigned short> w16;
+        const long bad = pack_f16_weights(wk, N, K, K, Npad, w16);
+        if (bad >= 0)
+            return fail(h, SPECMI_ERR_ARG, "layer '%s%s': folded weight %g (output channel %ld) is outside the finite fp16 range",
+                        prefix.c_str(), (bad % K < K1 ? c3.name : ds.name).c_str(), wk[(size_t)bad], bad / K);
+        if ((rc = dev_upload(h, w16.data(), w16.size() * 2, &b.f_w16, h->param_allocs))) return rc;
+    }
+    if (fp32_forms && (rc = dev_upload(h, packed.data(), packed.size() * 4, (void**)&b.f_w, h->param_allocs))) return rc;
+    if (fp32_forms && (rc = dev_upload(h, ones.data(), ones.size() * 4, (void**)&b.f_scale, h->param_allocs))) return rc;
     if ((rc = dev_upload(h, shift.data(), shift.size() * 4, (void**)&b.f_shift, h->param_allocs))) return rc;
     return SPECMI_OK;
 }

@@ -30,6 +30,8 @@ struct ConvW {
     float *w = nullptr, *scale = nullptr, *shift = nullptr;  // device
     float* wino = nullptr;  // device: Winograd-domain filters (3x3 stride-1 layers only)
     void* wsplit = nullptr; // device: bf16 pieces of the weights (1x1 stride-1 layers, only when option conv_precision != 0)
+    void* w16 = nullptr;    // device: fp16_rne(w * bn scale) [Kp16/8][Npad][8] (precision SPECMI_PRECISION_FP16 only)
+    int Kp16 = 0;
 };
 
 struct Bneck {
@@ -40,6 +42,7 @@ struct Bneck {
     // weights pre-multiplied by the BN scales (fp64), shift = shift3 + shift_ds, scale = 1
     float *f_w = nullptr, *f_scale = nullptr, *f_shift = nullptr;
     void* f_wsplit = nullptr;   // bf16 pieces of the same folded matrix (option conv_precision != 0)
+    void* f_w16 = nullptr;      // fp16 image of the same folded matrix (precision SPECMI_PRECISION_FP16)
     int f_Npad = 0;
 };
 
@@ -58,6 +61,8 @@ struct specmi_handle {
     std::map<std::string, int> opt_i;
     std::map<std::string, float> opt_f;
     bool committed = false;
+    // SPECMI_PRECISION_*: what specmi_set_precision asked for, and what the last successful commit packed
+    int precision = 0, committed_precision = 0;
     std::string err;
 
     // packed parameters (device)

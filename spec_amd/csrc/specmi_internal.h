@@ -174,6 +174,32 @@ bool conv_bf16s_supported(const ConvArgs& a);
 int launch_conv_bf16s(const ConvArgs& a, const void* wsplit, int terms, const LaunchCtx& ctx);
 
 // ----------------------------------------------------------------------------------------
+// fp16 trunk path: implicit-GEMM convolution on the fp16 matrix cores, image conversion, max-pool  (conv_f16.hip)
+// ----------------------------------------------------------------------------------------
+struct ConvF16Args {
+    const void* x = nullptr;       // fp16 NHWC, pixel stride ldx (multiple of 8, >= Cin; channels past Cin are zero)
+    const void* w = nullptr;       // fp16 [Kp/8][Npad][8]: fp16_rne(w * bn_scale), k = (ky*KW + kx)*ldx + ci, zero padded
+    const float* shift = nullptr;  // fp32 [Npad]
+    const void* res = nullptr;     // optional fp16 residual, indexed like out
+    void* out = nullptr;           // fp16 (out_f32 = 0) or fp32 [M][ldo]
+    int B = 0, H = 0, W = 0, Cin = 0, ldx = 0;
+    int OH = 0, OW = 0, Cout = 0, Npad = 0, ldo = 0;
+    int KH = 1, KW = 1, stride = 1, pad = 0, relu = 0, out_f32 = 0;
+    int Kp = 0;                    // round_up(KH*KW*ldx, 32), or Cin + Cin2 with x2
+    // optional second A source of a 1x1 / stride-1 layer (the folded downsample): K = [x | x2 at (oy*stride2, ox*stride2)]
+    const void* x2 = nullptr;
+    int H2 = 0, W2 = 0, ldx2 = 0, Cin2 = 0, stride2 = 1;
+};
+// (cout, K) fp64 products -> fp16 [Kp/8][Npad][8]; returns the index n*K + k of the first product that overflows fp16, or -1
+long pack_f16_weights(const std::vector<double>& wk, int cout, int K, int Kp, int Npad, std::vector<unsigned short>& out);
+// OIHW weights x per-channel BN scale in fp64, K ordered (ky, kx, ci) over cin_p channels
+void fold_f16_oihw(const float* w, const float* scale, int cout, int cin, int cin_p, int kh, int kw, std::vector<double>& wk);
+int launch_conv_f16(const ConvF16Args& a, const LaunchCtx& ctx);
+// NCHW fp32 (C <= 8) -> NHWC fp16 with 8 channels (zero padded)
+int launch_to_nhwc_f16(const float* x, void* out, int B, int C, int H, int W, const LaunchCtx& ctx);
+int launch_maxpool_f16(const void* x, void* out, int B, int H, int W, int C, int OH, int OW, const LaunchCtx& ctx);
+
+// ----------------------------------------------------------------------------------------
 // stem + pooling  (stem.hip)
 // ----------------------------------------------------------------------------------------
 // x NCHW (B,3,H,W); w = pack_stem_weights() output; out NHWC (B,OH,OW,64), BN+ReLU.

@@ -70,6 +70,22 @@ class Engine:
         _lib.check(self.h, self.lib.specmi_get_option_i32(self.h, name.encode(), C.byref(v)))
         return int(v.value)
 
+    # Precision of the ResNet trunk (include/specmi.h, "precision"): model state read by the next commit, not an option.
+    PRECISIONS = {'fp32': _lib.PRECISION_FP32, 'fp16': _lib.PRECISION_FP16}
+
+    def set_precision(self, precision: str):
+        """'fp32' (default) or 'fp16' (the reference's TRAINING.USE_AMP trunk); takes effect at the next commit (load)."""
+        if precision not in self.PRECISIONS:
+            raise ValueError(f"precision must be one of {tuple(self.PRECISIONS)}")
+        _lib.check(self.h, self.lib.specmi_set_precision(self.h, self.PRECISIONS[precision]))
+        return self
+
+    @property
+    def precision(self) -> str:
+        v = C.c_int(0)
+        _lib.check(self.h, self.lib.specmi_get_precision(self.h, C.byref(v)))
+        return {code: name for name, code in self.PRECISIONS.items()}[int(v.value)]
+
     def experimental(self, on: bool = True):
         """Let this handle accept the experimental option names (include/specmi.h): tuning thresholds, debug pins, opt-ins."""
         self.set_option('experimental', int(bool(on)))
@@ -431,6 +447,34 @@ class Engine:
             self.h, _ptr(x), B, H, W, cin, w.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
             sh.ctypes.data_as(C.c_void_p), cout, kh, kw, stride, pad, _ptr(res), int(relu), _ptr(out),
             self._stream()))
+        return out
+
+    def conv2d_f16(self, x, w_oihw, scale, shift, stride, pad, residual=None, relu=True, out_f32=False,
+                   x2=None, w2_oihw=None, stride2=1):
+        """Single fused layer of the fp16 trunk (tests).  x (B,H,W,Cp) fp16 NHWC device tensor, Cp = Cin rounded up to 8
+        (zero padded); w (Cout,Cin,KH,KW) the unfolded weights, scale / shift the BN fold.  x2 / w2_oihw: the folded
+        downsample's second A source (B,H2,W2,Cin2) and its 1x1 weights (Cout,Cin2,1,1), concatenated after w along K."""
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.float16 and x.is_cuda):
+            raise TypeError('x must be a float16 cuda tensor')
+        x = x.contiguous()
+        w = np.asarray(w_oihw, dtype=np.float32)
+        cout, cin, kh, kw = w.shape
+        B, H, W, _ = x.shape
+        cin2, H2, W2 = 0, 0, 0
+        if x2 is not None:
+            x2 = x2.contiguous()
+            _, H2, W2, cin2 = x2.shape
+            w = np.concatenate([w, np.asarray(w2_oihw, dtype=np.float32)], axis=1)
+        w = np.ascontiguousarray(w)
+        sc = np.ascontiguousarray(np.asarray(scale, dtype=np.float32))
+        sh = np.ascontiguousarray(np.asarray(shift, dtype=np.float32))
+        oh, ow = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
+        out = torch.empty(B, oh, ow, cout, device=self.device, dtype=torch.float32 if out_f32 else torch.float16)
+        res = None if residual is None else residual.contiguous()
+        _lib.check(self.h, self.lib.specmi_conv2d_f16(
+            self.h, _ptr(x), B, H, W, cin, w.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
+            sh.ctypes.data_as(C.c_void_p), cout, kh, kw, stride, pad, _ptr(res), int(relu), _ptr(out), int(bool(out_f32)),
+            _ptr(x2), H2, W2, cin2, int(stride2), self._stream()))
         return out
 
     def maxpool(self, x):

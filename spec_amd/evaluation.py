@@ -40,7 +40,7 @@ README_TABLE = {'spec-mtp': (124.3, 71.8, 147.1), 'spec-syn': (74.9, 54.5, 90.5)
 DEFAULTS = {   # the hparams of spec/config.py the evaluation reads
     'LOG_DIR': 'logs/experiments', 'METHOD': 'hmr_cam',
     'DATASET': {'BATCH_SIZE': 64, 'VAL_DS': 'spec-syn_spec-mtp_3dpw-test-cam', 'IMG_RES': 224},
-    'TRAINING': {'PRETRAINED_LIT': None},
+    'TRAINING': {'PRETRAINED_LIT': None, 'USE_AMP': False},
     'TESTING': {'USE_GT_CAM': False, 'SAVE_RESULTS': True},
     'HMR': {'BACKBONE': 'resnet50', 'USE_CAM_FEATS': False},
 }
@@ -71,6 +71,12 @@ def load_config(cfg_path: Optional[str], opts: Optional[List[str]] = None) -> di
             node = node.setdefault(p, {})
         node[parts[-1]] = yaml.safe_load(v) if isinstance(v, str) else v
     return hp
+
+
+def eval_precision(hparams: dict) -> str:
+    """The trunk precision the evaluation runs at: 'fp16' when ``TRAINING.USE_AMP`` is true - the reference then evaluates
+    under Lightning ``precision=16`` (scripts/spec_eval.py:63-70) - else 'fp32'."""
+    return 'fp16' if bool((hparams.get('TRAINING') or {}).get('USE_AMP', False)) else 'fp32'
 
 
 def read_image_rgb(path: str) -> np.ndarray:
@@ -144,6 +150,10 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         Jh36m = np.load('data/J_regressor_h36m.npy')
     finally:
         os.chdir(cwd)
+    precision = eval_precision(hparams)
+    if precision == 'fp16':
+        log('Using native 16bit precision (TRAINING.USE_AMP): the ResNet trunk runs in fp16, heads and SMPL in fp32')
+    hm.set_precision(precision)           # (no engine yet: recorded, packed by the commit below)
     hm.to(dev).eval().commit(dev, freeze=True)
     body = metrics.BodyModel(assets.smpl_model(), device=dev)
     bs = int(hparams['DATASET']['BATCH_SIZE'])
@@ -181,6 +191,7 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
             log(f'{name}: delta vs README  W-MPJPE {d[0]:+.2f} mm  PA-MPJPE {d[1]:+.2f} mm  W-PVE {d[2]:+.2f} mm  '
                 f'(target |delta W-MPJPE| <= 0.1 mm: {"met" if abs(d[0]) <= 0.1 else "NOT met"})')
             res['readme_delta_mm'] = {'wmpjpe': d[0], 'pampjpe': d[1], 'wpve': d[2]}
+        res['precision'] = precision
         results[name] = res
     return results
 

@@ -330,6 +330,38 @@ class _EngineModule(nn.Module):
             self._sig = ('stale',)
         return self
 
+    # Precision of the ResNet trunk (include/specmi.h, "precision"): 'fp32' (default, what the benchmark's headline measures) or
+    # 'fp16' - the reference's TRAINING.USE_AMP switch (Lightning precision=16, scripts/spec_eval.py:63-70): fp16 activations and
+    # BN-folded fp16 weights, fp32 accumulation; heads and SMPL stay fp32 ("fp16 trunk").  torch.autocast contexts
+    # are not consulted.  Same invalidate-and-recommit pattern as set_conv_precision; when the commit raises (a folded weight
+    # outside fp16's range) the previous precision is committed again and the module keeps working at it.
+    precision = 'fp32'
+
+    def _fp16_supported(self) -> bool:
+        return True
+
+    def set_precision(self, precision: str):
+        if precision not in Engine.PRECISIONS:
+            raise ValueError(f"precision must be one of {tuple(Engine.PRECISIONS)}")
+        if precision != 'fp32' and not self._fp16_supported():
+            raise NotImplementedError('the fp16 trunk is built for the ResNet backbones only')
+        old = self.precision
+        self.precision = precision
+        self._invalidate()
+        if self._engine is None:
+            self._sig = ('stale',)
+            return self
+        try:
+            self.commit(self._engine.device, freeze=self._frozen)
+        except Exception:
+            self.precision = old
+            try:
+                self.commit(self._engine.device, freeze=self._frozen)
+            except Exception:
+                self._sig = ('stale',)
+            raise
+        return self
+
     # Execution plan of the trunk (include/specmi.h, option "plan"): 'throughput' = the kernels the batch-256 headline runs
     # (Winograd + 64x64 / 128x128 implicit GEMM); 'latency' = every convolution cut into K slices that fill the chip at batch
     # 1-8 (one canonical summation tree per layer); 'single' (round 5) = the latency plan with every 3x3 convolution on the sliced
@@ -366,6 +398,7 @@ class _EngineModule(nn.Module):
         sd = {k: v for k, v in self.state_dict().items()
               if not k.startswith('smpl.') and v.dtype.is_floating_point}
         sd = self._engine_state(sd)
+        self._engine.set_precision(self.precision)
         self._engine.load(sd, smpl=self._smpl_model(), conv_precision=int(self.conv_precision), plan=self.PLANS[self.plan],
                           **self._options())
         self._tracked = None
@@ -477,6 +510,9 @@ class HMR(_EngineModule):
                 self.load_pretrained_spin(pretrained)
             else:
                 self.load_pretrained(pretrained)
+
+    def _fp16_supported(self) -> bool:
+        return self._backbone_id not in (32, 48)
 
     def _options(self):
         return {'use_cam': int(self.use_cam), 'use_cam_feats': int(self.use_cam_feats),
