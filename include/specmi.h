@@ -155,16 +155,7 @@ const char* specmi_version(void);
  *     "latency_min_chunks" (4), "latency_wino_min_tiles" (128), "latency_fill_wgs" (240) / "latency_fill_wgs_large" (400),
  *     "latency_unit_model" (0; 1 = pick the unit by a round model with "latency_unit_slots" 256: measured equal or worse);
  *   wave-split unit of the latency / single plans (spec_amd/csrc/conv_wsplit.hip): "wsplit" (1; 0 = never, 2 / 3 = always with one
- *     group / all groups per workgroup), "wsplit_max_units" (1400, trunk pair), "wsplit_max_units_single" (500), "wsplit_slots" (256);
- *   "persist" (0, opt-in): every run of implicit-GEMM layers of the latency / single plan as ONE persistent launch
- *     (spec_amd/csrc/conv_persist.hip).  Bit-identical to the per-layer launches and measured SLOWER on MI355X (0.68 vs 0.55 ms,
- *     profiles/r05_a_persist_ab.jsonl); at most two such forwards may be in flight per device.  "persist_wgs" (0 = 512 pair / 256
- *     single), "persist_fill_wgs" (0 = the latency fill), "persist_l2_prefetch" (0), "persist_spin_limit" (400000), "persist_min_run"
- *     (2), "persist_max_run" (64; 1 = every layer its own walker launch: resident workgroups walk the layer's tiles, no in-launch
- *     waits - the round-6 tile-walking ablation, profiles/r06_*_walk_ablation.*), "persist_allow_full" (0); specmi_sync_status
- *     reports a spin that gave up;
- *   "tail_fuse" (0, opt-in): at small batches each network's tail as ONE launch (spec_amd/csrc/head.hip) - same bits, four graph
- *     nodes less per step and NOT faster on MI355X (profiles/r05_f_tail_check.jsonl). */
+ *     group / all groups per workgroup), "wsplit_max_units" (1400, trunk pair), "wsplit_max_units_single" (500), "wsplit_slots" (256). */
 int specmi_set_option_i32(specmi_handle* h, const char* name, int value);
 int specmi_set_option_f32(specmi_handle* h, const char* name, float value);
 /* The effective value of an integer option on this handle: what was set, else the default of the table. */
@@ -195,7 +186,7 @@ int specmi_commit(specmi_handle* h);
  *   - the fp16 weights are packed at specmi_commit; a forward on a handle whose precision changed since its last successful
  *     commit returns SPECMI_ERR_STATE.  Commit returns SPECMI_ERR_ARG, naming the layer, when a folded weight lies outside
  *     the finite fp16 range (never silently inf), and for the HRNet backbones (not built at fp16).
- *   - one kernel family at every batch size and resolution: options "plan", "winograd", "persist", "wsplit", the latency_* /
+ *   - one kernel family at every batch size and resolution: options "plan", "winograd", "wsplit", the latency_* /
  *     trunk_subbatch tuning and "conv_precision" do not apply to the fp16 trunk; an image's bits do not depend on B.
  *   - specmi_trunk_forward_pair with either handle at fp16 runs as two specmi_trunk_forward calls on the stream (same bits). */
 enum { SPECMI_PRECISION_FP32 = 0, SPECMI_PRECISION_FP16 = 1 };
@@ -219,9 +210,7 @@ int specmi_trunk_forward_pair(specmi_handle* ha, specmi_handle* hb, const float*
 int specmi_camcalib_head_forward(specmi_handle* h, const float* feat_nhwc, int B, int fh, int fw, float* logits_vfov,
                                  float* logits_pitch, float* logits_roll, void* stream);
 
-/* specmi_camcalib_head_forward + specmi_camcalib_decode in one call (round 5); with option "tail_fuse" = 1 and at small batches
- * (the GEMV path of the latency / single plans, one Linear layer per head) the avg-pool, the three heads and the decode run as ONE
- * launch (spec_amd/csrc/head.hip: tail_gemv_kernel - the code of the three kernels, same bits); otherwise the separate kernels.
+/* specmi_camcalib_head_forward + specmi_camcalib_decode in one call (round 5).
  * Replaces camcalib/model.py:74-80 + camcalib/cam_utils.py:110-133 + scripts/camcalib_demo.py:129 + spec/utils/cam_params.py:37-46.
  * Outputs as in the two calls (any of vfov .. K may be NULL); "angle_ld" applies to vfov / pitch / roll. */
 int specmi_camcalib_head_decode(specmi_handle* h, const float* feat_nhwc, int B, int fh, int fw, float* logits_vfov,
@@ -413,15 +402,14 @@ int specmi_rotate_points(specmi_handle* h, const float* R, const float* points, 
 int specmi_trunk_plan(specmi_handle* h, int B, int H, int W, int pair, int32_t* mode);
 
 /* ---- in-launch hand-off state (round 5) ---------------------------------------------------
- * The latency / single plans hand data between workgroups INSIDE a launch (split-K tile tickets, the completion counters of the
- * persistent multi-layer walker: spec_amd/csrc/conv_persist.hip).  Those protocols keep a few device counters that every launch
- * leaves at zero.  They have no counterpart in the reference (spec/tester.py:109-151 runs stock torch ops). */
+ * The sliced (split-K) layers of the latency / single plans and the FC GEMMs hand partial tiles between the workgroups of ONE
+ * launch: every K slice takes a ticket from its tile's arrival counter and the last to arrive folds the slices and re-zeroes the
+ * counter (spec_amd/csrc/conv_igemm.hip, conv_wsplit.hip).  These counters are zero between launches.  They have no counterpart
+ * in the reference (spec/tester.py:109-151 runs stock torch ops). */
 
-/* Synchronises the device.  *persist_err: 0 = the handle's persistent launches all completed their hand-offs; 1 = a bounded spin
- * gave up (the results of that launch are garbage: a protocol error or a grid that was not co-resident - more than two persistent
- * forwards in flight on one device); 3 = the bounded wait inside a fused tail (option "tail_fuse") gave up; < 0 = a control block
- * was not left clean (-1 / -2 the walker's, -3 the fused tails'). */
-int specmi_sync_status(specmi_handle* h, int32_t* persist_err);
+/* Synchronises the device.  *status: 0 = every split-K arrival counter of the handle is zero (the hand-off state is clean);
+ * -2 = a counter was not left at zero (a launch died mid-flight, or a protocol error; specmi_sync_reset clears it). */
+int specmi_sync_status(specmi_handle* h, int32_t* status);
 /* Zeroes the hand-off counters on `stream`.  The library does this itself at specmi_commit and after any forward that returned
  * an error; a caller that destroyed a captured graph mid-replay (or killed a launch some other way) calls it before the next forward. */
 int specmi_sync_reset(specmi_handle* h, void* stream);

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B builds of libspecmi.so with compile-time knobs of the persistent walker (experiments only):
+# A/B builds of libspecmi.so with compile-time knobs (experiments only, e.g. the wave-split ablation of scripts/gpu_ws_ablate.py):
 #   scripts/build_variants.sh name "-DFOO=1 -DBAR=2" ...   ->  spec_amd/lib/variants/libspecmi_<name>.so  (select with SPECMI_LIB)
 set -e
 cd "$(dirname "$0")/.."

@@ -15,7 +15,7 @@ ap.add_argument('--batch', type=int, default=1)
 ap.add_argument('--reps', type=int, default=20)
 ap.add_argument('--plan', default='auto')
 ap.add_argument('--grouped', default='auto', help="'auto' (what a caller gets), 1 or 0")
-ap.add_argument('--opt', action='append', default=[], help='library option name=value for both models (e.g. persist=1, tail_fuse=1)')
+ap.add_argument('--opt', action='append', default=[], help='library option name=value for both models (e.g. wsplit=0, head_fuse=0)')
 args = ap.parse_args()
 torch.set_grad_enabled(False)
 dev = torch.device('cuda:0')

@@ -82,13 +82,11 @@ static int sync_for_growth(specmi_handle* h, const char* what) {
     return fail(h, SPECMI_ERR_HIP, "hipDeviceSynchronize failed while growing %s: %s", what, hipGetErrorString(e));
 }
 
-// The in-launch hand-offs (split-K tile tickets, the persistent walker's completion counters) rely on counters that every
-// launch leaves at zero.  A launch that dies mid-flight does not: zero them whenever that may have happened (after any failed
-// forward), at specmi_commit and on demand (specmi_sync_reset).  Enqueued on `s`.
+// The in-launch hand-offs (split-K tile tickets) rely on arrival counters that every launch leaves at zero.  A launch that dies
+// mid-flight does not: zero them whenever that may have happened (after any failed forward), at specmi_commit and on demand
+// (specmi_sync_reset).  Enqueued on `s`.
 static void reset_sync_state(specmi_handle* h, hipStream_t s) {
     if (h->sk.cnt) (void)hipMemsetAsync(h->sk.cnt, 0, (size_t)h->sk.ncnt * 4, s);
-    if (h->pctl) (void)hipMemsetAsync(h->pctl, 0, sizeof(PersistCtl), s);
-    if (h->tail_ctl) (void)hipMemsetAsync(h->tail_ctl, 0, (size_t)specmi_handle::kTailCtlWords * 4, s);
     (void)hipGetLastError();
 }
 
@@ -138,10 +136,6 @@ static int ensure_ws(specmi_handle* h, int B, int H, int W) {
     if ((rc = dev_alloc(h, (size_t)Bp32 * SMPL_KQ * 8 * 4, (void**)&h->pf_ws, h->ws_allocs))) return rc;
     if ((rc = dev_alloc(h, (size_t)Bp32 * 288 * 4, (void**)&h->A_ws, h->ws_allocs))) return rc;
     if ((rc = dev_alloc(h, (size_t)Bp * 72 * 4, (void**)&h->pj_ws, h->ws_allocs))) return rc;
-    if (!h->tail_ctl) {   // (once: captured graphs keep naming it)
-        HIPCHK(h, hipMalloc((void**)&h->tail_ctl, (size_t)specmi_handle::kTailCtlWords * 4));
-        HIPCHK(h, hipMemset(h->tail_ctl, 0, (size_t)specmi_handle::kTailCtlWords * 4));
-    }
     HIPCHK(h, hipMemset(h->pf_ws, 0, (size_t)Bp32 * SMPL_KQ * 8 * 4));   // rows 218..223 of the feature operand stay zero
     HIPCHK(h, hipMemset(h->A_ws, 0, (size_t)Bp32 * 288 * 4));
     h->ws_B = Bw;
@@ -308,11 +302,11 @@ static OpLaunch prepare_op(specmi_handle* h, const TrunkOp& op, const float* ima
 // plan: 0 auto, 1 throughput, 2 latency, 3 single.  Returns the trunk mode of this call: 0 throughput kernels, 1 latency (sliced
 // direct kernels on layer3 / layer4, Winograd where an image fills its rows), 2 single (round 5: batch 1-2, the reference's demo
 // granularity, scripts/camcalib_demo.py:95-102 - every 3x3 convolution on the sliced direct kernel, which is faster there by
-// 21 / 12 us at batch 1 / 2 (profiles/r04_b_latency_layers.txt) and leaves the whole trunk behind the max-pool as one run of
-// implicit-GEMM layers for the persistent walker).  auto = single up to "single_max_batch" (2) images' worth of pixels, latency up
-// to N = "latency_max_batch" (10) for the trunk PAIR / "latency_max_batch_single" (16) for one trunk - measured per batch size
-// (profiles/r04_l_plan_crossover.jsonl: pair 1.67 vs 1.78 ms at 10 images, 2.18 vs 2.15 at 12; one trunk after the other 3.08 vs
-// 3.32 ms still at 16; a single CamCalib frame at 600 x 1066 = 12.7 crops' worth of rows: 2.10 vs 2.27 ms for the demo's one-frame step)
+// 21 / 12 us at batch 1 / 2, profiles/r04_b_latency_layers.txt).  auto = single up to "single_max_batch" (2) images' worth of
+// pixels, latency up to N = "latency_max_batch" (10) for the trunk PAIR / "latency_max_batch_single" (16) for one trunk - measured
+// per batch size (profiles/r04_l_plan_crossover.jsonl: pair 1.67 vs 1.78 ms at 10 images, 2.18 vs 2.15 at 12; one trunk after the
+// other 3.08 vs 3.32 ms still at 16; a single CamCalib frame at 600 x 1066 = 12.7 crops' worth of rows: 2.10 vs 2.27 ms for the
+// demo's one-frame step)
 static int trunk_mode(specmi_handle* h, int B, int H, int W, bool pair = false) {
     const int plan = opt_i(h, "plan", 0);
     if (plan == 1) return 0;
@@ -504,77 +498,8 @@ static void plan_trunk(specmi_handle* h, int H, int W, bool to_caller, TrunkPlan
     P.final_buf = final_buf; P.fh = ch; P.fw = cw;
 }
 
-// ---- persistent runs (conv_persist.hip) ----------------------------------------------------------------------------------
-// Ops [i0, i1) of a trunk (Lb == nullptr) or of a trunk pair - all implicit-GEMM convolutions of the latency / single plan - as
-// ONE launch.  Returns SPECMI_OK, an error, or -1: "not for the walker" (a shape it does not take: the caller launches the
-// layers one by one).
-static int persist_run(specmi_handle* h, const std::vector<OpLaunch>& La, const std::vector<OpLaunch>* Lb, const std::vector<TrunkOp>& ops,
-                       size_t i0, size_t i1, float* feat_a, float* feat_b, hipStream_t s) {
-    const int nl = (int)(i1 - i0);
-    const int groups = Lb ? 2 : 1;
-    std::vector<PersistLayerHost> lay((size_t)nl);
-    float *out0 = nullptr, *out1 = nullptr;
-    const int fill = opt_i(h, "persist_fill_wgs", 0) > 0 ? opt_i(h, "persist_fill_wgs", 0) : sk_fill(h);      // 0 = the latency fill
-    const int fu = opt_i(h, "latency_force_unit", 0);
-    for (int l = 0; l < nl; ++l) {
-        PersistLayerHost& P = lay[(size_t)l];
-        P.a = La[i0 + l].a;
-        P.pair = Lb != nullptr;
-        if (Lb) P.b = (*Lb)[i0 + l].a;
-        P.pl = conv_igemm_sk_plan(P.a, groups, opt_i(h, "latency_target_wgs", 256), opt_i(h, "latency_min_chunks", 4), fill);
-        if (fu) P.pl.unit = fu == 1 ? 1 : (fu == 2 ? P.pl.G : P.pl.leaves);
-        if (ops[i0 + l].out_buf == -2) {
-            // the caller's feature buffer changes from call to call (and between the warm-up and the capture of a graph): it is a
-            // launch argument, the table holds a placeholder
-            if ((reinterpret_cast<uintptr_t>(feat_a) & 15) || (Lb && (reinterpret_cast<uintptr_t>(feat_b) & 15))) return -1;
-            P.out_arg = 1;
-            out0 = feat_a; out1 = feat_b;
-            P.a.out = nullptr;
-            if (Lb) P.b.out = nullptr;
-        }
-    }
-    const int nwg = opt_i(h, "persist_wgs", 0) > 0 ? opt_i(h, "persist_wgs", 0) : (Lb ? 512 : 256);           // 0 = by context
-    const int l2pf = opt_i(h, "persist_l2_prefetch", 0);
-    size_t ws_need = 0;
-    int cnt_need = 0;
-    if (persist_fill_table(lay.data(), nl, SkWs{}, nwg, l2pf, nullptr, &ws_need, &cnt_need)) return -1;
-    int rc;
-    if ((rc = ensure_sk(h, ws_need ? ws_need : 1, cnt_need))) return rc;
-    std::vector<unsigned char> img(persist_table_bytes(nl));
-    if (persist_fill_table(lay.data(), nl, h->sk, nwg, l2pf, img.data(), &ws_need, &cnt_need)) return -1;
-    const specmi_handle::PersistTable* tab = nullptr;
-    for (const auto& t : h->persist_tables)
-        if (t.nl == nl && t.img.size() == img.size() && memcmp(t.img.data(), img.data(), img.size()) == 0) { tab = &t; break; }
-    if (!tab || !h->pctl) {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); st = hipStreamCaptureStatusNone; }
-        if (st != hipStreamCaptureStatusNone)
-            return fail(h, SPECMI_ERR_STATE, "the layer table of this batch / resolution is not on the device yet, which is not possible while "
-                        "a stream is being captured: run one eager forward of this shape first (the capture is invalid now)");
-        if (!h->pctl) {
-            HIPCHK(h, hipMalloc((void**)&h->pctl, sizeof(PersistCtl)));
-            HIPCHK(h, hipMemset(h->pctl, 0, sizeof(PersistCtl)));
-        }
-        if (!tab) {
-            specmi_handle::PersistTable t;
-            t.nl = nl;
-            HIPCHK(h, hipMalloc(&t.dev, img.size()));
-            HIPCHK(h, hipMemcpy(t.dev, img.data(), img.size(), hipMemcpyHostToDevice));
-            t.img = std::move(img);
-            h->persist_tables.push_back(std::move(t));
-            tab = &h->persist_tables.back();
-        }
-    }
-    LaunchCtx ctx{s, &h->prof, ops[i0].label.c_str()};
-    LAUNCHCHK(h, launch_persist(tab->dev, nl, h->pctl, out0, out1, nwg, (unsigned)opt_i(h, "persist_spin_limit", 400000), ctx, 0.0, 0.0,
-                                opt_i(h, "persist_allow_full", 0) != 0),
-              "persistent trunk run");
-    return SPECMI_OK;
-}
-
-// Launch ops [first, n) of a trunk (hb == nullptr) or of a trunk pair.  mode != 0 and option "persist" (default 0: opt-in): maximal runs of
-// implicit-GEMM convolutions go to the persistent walker (one launch per run of up to 64 layers), everything else - the stem,
-// the max-pool, Winograd layers, the optional split-bf16 path - is launched op by op as before.
+// Launch ops [first, n) of a trunk (hb == nullptr) or of a trunk pair, one op at a time.  Every op is prepared (and, for a pair,
+// checked against its twin) before the first launch.
 static int launch_ops(specmi_handle* ha, specmi_handle* hb, const TrunkPlan& Pa, const TrunkPlan* Pb, const float* img_a, const float* img_b,
                       int B, int H, int W, float* feat_a, float* feat_b, size_t first, int mode, hipStream_t s) {
     const size_t n = Pa.ops.size();
@@ -597,27 +522,8 @@ static int launch_ops(specmi_handle* ha, specmi_handle* hb, const TrunkPlan& Pa,
             return fail(ha, SPECMI_ERR_ARG, "op %zu (%s) differs between the two trunks: grouped launches need identical layer shapes",
                         i, oa.label.c_str());
     }
-    // (the built-in launch profiler wants one record per layer: it sees the per-layer launches)
-    const bool persist = mode != 0 && opt_i(ha, "persist", 0) && !ha->prof.on;   // opt-in: measured slower than the per-layer launches (profiles/r05_a_*)
-    const size_t min_run = (size_t)opt_i(ha, "persist_min_run", 2);
-    size_t max_run = (size_t)opt_i(ha, "persist_max_run", 64);     // 1: every layer its own walker launch (tiles walked, no in-launch waits)
-    if (max_run < 1 || max_run > (size_t)kPersistMaxLayers) max_run = (size_t)kPersistMaxLayers;
-    auto eligible = [&](size_t i) { return La[i].kind == 2 && La[i].family == 0 && !La[i].a.force_variant; };
-    int rc;
-    size_t i = first;
-    while (i < n) {
-        if (persist && eligible(i)) {
-            size_t j = i;
-            while (j < n && eligible(j) && j - i < max_run) ++j;
-            if (j - i >= min_run) {
-                rc = persist_run(ha, La, hb ? &Lb : nullptr, Pa.ops, i, j, feat_a, feat_b, s);
-                if (rc == SPECMI_OK) { i = j; continue; }
-                if (rc != -1) return rc;
-            }
-        }
-        if ((rc = launch_op(ha, Pa.ops[i], La[i], hb ? &Lb[i] : nullptr, B, H, W, s))) return rc;
-        ++i;
-    }
+    for (size_t i = first; i < n; ++i)
+        if (int rc = launch_op(ha, Pa.ops[i], La[i], hb ? &Lb[i] : nullptr, B, H, W, s)) return rc;
     return SPECMI_OK;
 }
 
@@ -625,7 +531,7 @@ static int launch_ops(specmi_handle* ha, specmi_handle* hb, const TrunkPlan& Pa,
 // holding fp16 NHWC activations (half the bytes of the fp32 workspace the same warm-up rule sizes: nothing is allocated under
 // graph capture).  The image is converted into act[1] (free until the max-pool writes it), every convolution - the stem
 // included - is one conv_f16 launch, and the last one stores fp32 for the heads.  One kernel family at every batch size:
-// plan, Winograd, persistent / wave-split / sub-batch options do not apply.
+// plan, Winograd, wave-split / sub-batch options do not apply.
 static int run_trunk_f16(specmi_handle* h, const float* images, int B, int H, int W, float* feat_out, const float** feat,
                          int* fh, int* fw, hipStream_t s) {
     TrunkPlan P;
@@ -746,47 +652,24 @@ static OutLd out_ld(specmi_handle* h) {
 // defer != nullptr: head_final is not launched; *defer describes it for the SMPL pose kernel, which does its work (run_smpl)
 static int run_head(specmi_handle* h, const float* feat, int B, int fh, int fw, const float* R, const float* K,
                     const float* img_h, float* pred_pose, float* pred_shape, float* pred_cam, float* pred_pose_6d,
-                    const OutLd& old, hipStream_t s, HeadFinal* defer = nullptr, bool* pose_done = nullptr) {
+                    const OutLd& old, hipStream_t s, HeadFinal* defer = nullptr) {
     int rc;
     const int ucf = opt_i(h, "use_cam_feats", 0);
     const int F = h->feat_ch, LD = h->xc_ld;
     if (ucf && (!R || !K || !img_h))
         return fail(h, SPECMI_ERR_ARG, "use_cam_feats needs cam_rotmat, cam_intrinsics and img_h");
-    if (pose_done) *pose_done = false;
-    // Small batches (round 5, option "tail_fuse", default 0): avg-pool + state init -> composed regressor map -> pose chains as ONE
-    // launch (head.hip: tail_gemv_kernel; the code of the three kernels, same bits).  Needs the collapsed head, the GEMV path,
-    // head_final deferred into the pose chain and a map that pools in one part.  Opt-in: measured 15.2 us against 16.3 us for the
-    // three kernels at batch 1 and the whole step 0-1 % SLOWER at batch 1-10 (profiles/r05_f_tail_check.jsonl) - an in-launch hop
-    // costs what a kernel boundary costs on this part.
-    if (defer && pose_done && !h->has_var && opt_i(h, "tail_fuse", 0) && use_latency_heads(h, B) && h->has_head_c && opt_i(h, "head_collapse", 1) &&
-        h->head_c.w_rm && fh * fw < 64 && (B + 1) / 2 + 3 <= specmi_handle::kTailCtlWords && h->tail_ctl && !h->prof.on) {
-        const HeadInit hi{h->xc, h->init_pose, h->init_shape, h->init_cam, R, K, img_h, ucf, F, LD};
-        defer->state = h->h1; defer->ld_state = 1024;
-        defer->pred_pose = pred_pose; defer->pred_shape = pred_shape; defer->pred_cam = pred_cam; defer->pred_pose_6d = pred_pose_6d;
-        defer->ld_pose = old.pose; defer->ld_shape = old.shape; defer->ld_cam = old.cam; defer->ld_p6d = old.p6d;
-        defer->rot_ws = h->rot_ws; defer->betas_ws = h->betas_ws; defer->cam_ws = h->cam_ws;
-        const FcGemv hd{h->xc, h->head_c.w_rm, h->head_c.shift, nullptr, h->h1};
-        LaunchCtx ctx{s, &h->prof, "head.tail"};
-        const int lrc = launch_tail_hmr(hd, h->head_c.nout, h->head_c.Kp, LD, 1024, B, feat, h->xc, fh * fw, F, hi, h->tail_ctl,
-                                        specmi_handle::kTailCtlWords, h->smpl, h->pf_ws, h->A_ws, h->pj_ws, *defer, ctx);
-        if (lrc == 0) { *pose_done = true; return SPECMI_OK; }
-        if (lrc != (int)hipErrorInvalidValue) LAUNCHCHK(h, lrc, "hmr tail");
-        (void)hipGetLastError();
-    }
+    // the IEF state columns are written by extra workgroups of the pooling launch (option "head_fuse" bit 0, default on; large
+    // maps pool in parts and keep head_init as its own launch)
+    const HeadInit hi{h->xc, h->init_pose, h->init_shape, h->init_cam, R, K, img_h, ucf, F, LD};
+    bool init_done = false;
     {
-        // the IEF state columns are written by extra workgroups of the pooling launch (option "head_fuse" bit 0, default on; large
-        // maps pool in parts and keep head_init as its own launch)
-        const HeadInit hi{h->xc, h->init_pose, h->init_shape, h->init_cam, R, K, img_h, ucf, F, LD};
-        bool init_done = false;
-        {
-            LaunchCtx ctx{s, &h->prof, "head.avgpool"};
-            LAUNCHCHK(h, launch_avgpool(feat, h->xc, B, fh * fw, F, LD, ctx, (opt_i(h, "head_fuse", 3) & 1) ? &hi : nullptr, &init_done), "avgpool");
-        }
-        if (!init_done) {
-            LaunchCtx ctx{s, &h->prof, "head.init"};
-            LAUNCHCHK(h, launch_head_init(h->xc, h->init_pose, h->init_shape, h->init_cam, R, K, img_h, ucf, B, F, LD, ctx),
-                      "head_init");
-        }
+        LaunchCtx ctx{s, &h->prof, "head.avgpool"};
+        LAUNCHCHK(h, launch_avgpool(feat, h->xc, B, fh * fw, F, LD, ctx, (opt_i(h, "head_fuse", 3) & 1) ? &hi : nullptr, &init_done), "avgpool");
+    }
+    if (!init_done) {
+        LaunchCtx ctx{s, &h->prof, "head.init"};
+        LAUNCHCHK(h, launch_head_init(h->xc, h->init_pose, h->init_shape, h->init_cam, R, K, img_h, ucf, B, F, LD, ctx),
+                  "head_init");
     }
     const float* state = h->xc + F;
     long ld_state = LD;
@@ -838,7 +721,7 @@ static int run_head(specmi_handle* h, const float* feat, int B, int fh, int fw, 
 static int run_smpl(specmi_handle* h, const float* rotmat, const float* betas, const float* cam, int B, const float* R,
                     const float* K, const float* bbox_scale, const float* bbox_center, const float* img_w,
                     const float* img_h, float* vertices, float* joints3d, float* joints2d, float* cam_t,
-                    const OutLd& old, hipStream_t s, const HeadFinal* final_ = nullptr, bool pose_done = false) {
+                    const OutLd& old, hipStream_t s, const HeadFinal* final_ = nullptr) {
     const int use_cam = opt_i(h, "use_cam", 0);
     if (use_cam && (!R || !K || !bbox_scale || !bbox_center || !img_w || !img_h))
         return fail(h, SPECMI_ERR_ARG, "use_cam needs cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h");
@@ -857,7 +740,6 @@ static int run_smpl(specmi_handle* h, const float* rotmat, const float* betas, c
     a.normalize_joints2d = use_cam ? 0 : 1;  // spec/models/hmr.py:111 vs :119
     a.skin_split = opt_i(h, "smpl_skin_split", -1);
     a.final_ = final_;
-    a.pose_done = pose_done;
     LaunchCtx ctx{s, &h->prof, "smpl"};
     LAUNCHCHK(h, launch_smpl(h->smpl, a, ctx), "smpl");
     return SPECMI_OK;
@@ -899,9 +781,6 @@ int specmi_destroy(specmi_handle* h) {
     if (h->sk.cnt) (void)hipFree(h->sk.cnt);
     free_pool(h->sk_retired);
     free_pool(h->ws_retired);
-    for (auto& t : h->persist_tables) if (t.dev) (void)hipFree(t.dev);
-    if (h->pctl) (void)hipFree(h->pctl);
-    if (h->tail_ctl) (void)hipFree(h->tail_ctl);
     if (h->resize_tab) (void)hipFree(h->resize_tab);
     hrnet_free(h->hrnet);
     delete h;
@@ -1137,21 +1016,6 @@ int specmi_camcalib_head_decode(specmi_handle* h, const float* feat, int B, int 
     int rc;
     if ((rc = ensure_ws(h, B, 32, 32))) return rc;
     const long ld_ang = opt_i(h, "angle_ld", 0) > 0 ? opt_i(h, "angle_ld", 0) : 1;
-    const FcW& f0 = h->fc_cam[0][0];
-    // small batches (round 5, option "tail_fuse", opt-in): avg-pool -> the three heads -> decode as ONE launch (head.hip: tail_gemv_kernel)
-    if (opt_i(h, "tail_fuse", 0) && use_latency_heads(h, B) && h->fc_layers == 1 && f0.w_rm && fh * fw < 64 && f0.Kp == h->feat_ch &&
-        h->fc_cam[1][0].nout == f0.nout && h->fc_cam[2][0].nout == f0.nout && h->fc_cam[1][0].Kp == f0.Kp && h->fc_cam[2][0].Kp == f0.Kp &&
-        (B + 1) / 2 + 3 <= specmi_handle::kTailCtlWords && h->tail_ctl && !h->prof.on) {
-        float* outs[3] = {lv, lp, lr};
-        FcGemv hd[3];
-        for (int i = 0; i < 3; ++i) hd[i] = FcGemv{h->xf, h->fc_cam[i][0].w_rm, h->fc_cam[i][0].shift, nullptr, outs[i]};
-        LaunchCtx ctx{s, &h->prof, "camcalib.tail"};
-        const int lrc = launch_tail_camcalib(hd, f0.nout, f0.Kp, B, feat, h->xf, fh * fw, h->feat_ch, h->tail_ctl, specmi_handle::kTailCtlWords,
-                                             img_h, img_w, vfov, pitch, roll, f_pix, R, K, ld_ang, ctx);
-        if (lrc == 0) return SPECMI_OK;
-        if (lrc != (int)hipErrorInvalidValue) LAUNCHCHK(h, lrc, "camcalib tail");
-        (void)hipGetLastError();
-    }
     if ((rc = run_camcalib_head(h, feat, B, fh, fw, lv, lp, lr, s))) { reset_sync_state(h, s); return rc; }
     LaunchCtx ctx{s, &h->prof, "camcalib.decode"};
     // the bins are the LAST Linear of a head's chain (num_fc_layers > 1: the first one is num_fc_channels wide, camcalib/model.py:59-70)
@@ -1254,11 +1118,10 @@ int specmi_hmr_forward(specmi_handle* h, const float* images, int B, int H, int 
     const OutLd old = out_ld(h);
     HeadFinal fin;
     const bool fuse = (opt_i(h, "head_fuse", 3) & 2) != 0;     // head_final's work inside the SMPL pose kernel (same bits, one node less)
-    bool pose_done = false;
     if ((rc = run_head(h, f, B, fh, fw, R, K, img_h, out->pred_pose, out->pred_shape, out->pred_cam, out->pred_pose_6d, old, s,
-                       fuse ? &fin : nullptr, fuse ? &pose_done : nullptr)) ||
+                       fuse ? &fin : nullptr)) ||
         (rc = run_smpl(h, h->rot_ws, h->betas_ws, h->cam_ws, B, R, K, bbox_scale, bbox_center, img_w, img_h,
-                       out->smpl_vertices, out->smpl_joints3d, out->smpl_joints2d, out->pred_cam_t, old, s, fuse ? &fin : nullptr, pose_done)))
+                       out->smpl_vertices, out->smpl_joints3d, out->smpl_joints2d, out->pred_cam_t, old, s, fuse ? &fin : nullptr)))
         reset_sync_state(h, s);      // include/specmi.h: the hand-off counters are reset after any forward that returned an error
     return rc;
 }
@@ -1275,11 +1138,10 @@ int specmi_hmr_regress(specmi_handle* h, const float* feat, int B, int fh, int f
     const OutLd old = out_ld(h);
     HeadFinal fin;
     const bool fuse = (opt_i(h, "head_fuse", 3) & 2) != 0;     // head_final's work inside the SMPL pose kernel (same bits, one node less)
-    bool pose_done = false;
     if ((rc = run_head(h, feat, B, fh, fw, R, K, img_h, out->pred_pose, out->pred_shape, out->pred_cam, out->pred_pose_6d, old, s,
-                       fuse ? &fin : nullptr, fuse ? &pose_done : nullptr)) ||
+                       fuse ? &fin : nullptr)) ||
         (rc = run_smpl(h, h->rot_ws, h->betas_ws, h->cam_ws, B, R, K, bbox_scale, bbox_center, img_w, img_h,
-                       out->smpl_vertices, out->smpl_joints3d, out->smpl_joints2d, out->pred_cam_t, old, s, fuse ? &fin : nullptr, pose_done)))
+                       out->smpl_vertices, out->smpl_joints3d, out->smpl_joints2d, out->pred_cam_t, old, s, fuse ? &fin : nullptr)))
         reset_sync_state(h, s);
     return rc;
 }
@@ -1566,28 +1428,16 @@ int specmi_trunk_plan(specmi_handle* h, int B, int H, int W, int pair, int32_t* 
     return SPECMI_OK;
 }
 
-int specmi_sync_status(specmi_handle* h, int32_t* persist_err) {
+int specmi_sync_status(specmi_handle* h, int32_t* status) {
     ENTER(h);
-    if (!persist_err) return fail(h, SPECMI_ERR_ARG, "null argument");
+    if (!status) return fail(h, SPECMI_ERR_ARG, "null argument");
     HIPCHK(h, hipDeviceSynchronize());
-    *persist_err = 0;
-    if (h->pctl) {
-        PersistCtl c;
-        HIPCHK(h, hipMemcpy(&c, h->pctl, sizeof(c), hipMemcpyDeviceToHost));
-        *persist_err = (int32_t)c.err;
-        if (!c.err) {   // a finished launch leaves the control block clean: anything else is a protocol error too
-            if (c.exit) *persist_err = -1;
-            for (int i = 0; i < 2 * kPersistMaxLayers; ++i)
-                if (c.done[i]) *persist_err = -2;
-        }
-    }
-    if (h->tail_ctl && !*persist_err) {   // the fused tails (option "tail_fuse"): error word last, every counter zero between launches
-        unsigned v[specmi_handle::kTailCtlWords];
-        HIPCHK(h, hipMemcpy(v, h->tail_ctl, sizeof(v), hipMemcpyDeviceToHost));
-        if (v[specmi_handle::kTailCtlWords - 1]) *persist_err = 3;
-        else
-            for (int i = 0; i < specmi_handle::kTailCtlWords - 1; ++i)
-                if (v[i]) *persist_err = -3;
+    *status = 0;
+    if (h->sk.cnt) {   // the last arriver of every sliced tile re-zeroes its counter: anything else is a protocol error
+        std::vector<unsigned> v((size_t)h->sk.ncnt);
+        HIPCHK(h, hipMemcpy(v.data(), h->sk.cnt, v.size() * 4, hipMemcpyDeviceToHost));
+        for (unsigned c : v)
+            if (c) *status = -2;
     }
     return SPECMI_OK;
 }
@@ -1604,16 +1454,6 @@ int specmi_debug_poison_sync(specmi_handle* h, uint32_t value) {
     if (h->sk.cnt) {
         std::vector<unsigned> v((size_t)h->sk.ncnt, value);
         HIPCHK(h, hipMemcpy(h->sk.cnt, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    }
-    if (h->tail_ctl) {
-        std::vector<unsigned> v((size_t)specmi_handle::kTailCtlWords, value);
-        HIPCHK(h, hipMemcpy(h->tail_ctl, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    }
-    if (h->pctl) {
-        PersistCtl c;
-        for (int i = 0; i < 2 * kPersistMaxLayers; ++i) c.done[i] = value;
-        c.exit = value; c.err = 0;
-        HIPCHK(h, hipMemcpy(h->pctl, &c, sizeof(c), hipMemcpyHostToDevice));
     }
     return SPECMI_OK;
 }

@@ -227,7 +227,7 @@ __global__ void __launch_bounds__(256, 4) conv_wsplit_f32_kernel(const KArgs p) 
     // Waves without a leaf (groups of 2 or 3) only keep the barriers company.  Two separate loops, not `if (active)` around the
     // chunks: hipcc's wait-count pass is path-insensitive - with the chunk under an `if` it assumes the other register set's
     // eight loads are not in flight and waits for vmcnt(6) instead of vmcnt(14) at the top of every chunk (the two-chunk
-    // distance collapses to one; seen in the disassembly).  Whole (even, odd) pairs for the same reason (conv_igemm_body.inc);
+    // distance collapses to one; seen in the disassembly).  Whole (even, odd) pairs for the same reason (conv_igemm.hip);
     // the last two or three chunks are peeled: they fetch nothing (or one chunk), so the loop body has no "past the end" test.
     const std::true_type pf{};
     const std::false_type nopf{};
@@ -267,7 +267,7 @@ __global__ void __launch_bounds__(256, 4) conv_wsplit_f32_kernel(const KArgs p) 
 
     if (S > 1) {
         // group slab -> workspace (16 bytes per thread, consecutive threads consecutive: coalesced) with write-through stores,
-        // drain, ticket; the last arriver folds the S groups in order (conv_igemm_body.inc: same hand-off)
+        // drain, ticket; the last arriver folds the S groups in order (conv_igemm.hip: same hand-off)
         const size_t tile = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
         float* const tile_ws = p.sk_ws + tile * S * (size_t)1024;
         const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(tile_ws, 0, (unsigned)S * 4096u, 0x00020000);

@@ -14,7 +14,7 @@ using namespace specmi;
 // (include/specmi.h).  Experimental names - tuning thresholds, debug pins, measured-slower opt-ins, the narrower-arithmetic
 // secondary mode - are refused unless the process sets SPECMI_EXPERIMENTAL=1 or the handle's (stable) option "experimental" is 1;
 // setting one to its default is always a no-op and allowed.  tests/test_abi.py checks the defaults here against the opt_i(...) call
-// sites and against the header.  (0 = "by context" for persist_wgs / persist_fill_wgs.)
+// sites and against the header.
 namespace {
 struct OptSpec { const char* name; int def; bool stable; };
 const OptSpec kOptions[] = {
@@ -34,9 +34,6 @@ const OptSpec kOptions[] = {
     {"latency_unit_slots", 256, false}, {"latency_force_unit", 0, false},
     {"wsplit", 1, false}, {"wsplit_max_units", 1400, false}, {"wsplit_max_units_single", 500, false}, {"wsplit_slots", 256, false},
     {"conv2d_sk", 0, false}, {"conv2d_wsplit", 0, false},
-    {"persist", 0, false}, {"persist_min_run", 2, false}, {"persist_max_run", 64, false}, {"persist_wgs", 0, false}, {"persist_fill_wgs", 0, false},
-    {"persist_l2_prefetch", 0, false}, {"persist_spin_limit", 400000, false}, {"persist_allow_full", 0, false},
-    {"tail_fuse", 0, false},
 };
 const OptSpec* find_option(const char* name) {
     for (const OptSpec& o : kOptions)

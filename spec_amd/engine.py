@@ -100,7 +100,7 @@ class Engine:
         return self.PLAN_NAMES[int(mode.value)]
 
     def sync_status(self) -> int:
-        """Synchronises; 0 = every in-launch hand-off of this handle's persistent launches completed (include/specmi.h)."""
+        """Synchronises; 0 = every split-K arrival counter of this handle is back at zero, -2 = one is not (include/specmi.h)."""
         err = C.c_int32(0)
         _lib.check(self.h, self.lib.specmi_sync_status(self.h, C.byref(err)))
         return int(err.value)

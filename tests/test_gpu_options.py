@@ -52,18 +52,18 @@ def test_unknown_and_experimental_names_are_refused(no_env):
     eng.close()
 
 
-def test_opt_in_by_handle_and_by_environment(no_env, monkeypatch):
+def test_experimental_opt_in_by_handle_and_by_environment(no_env, monkeypatch):
     a, b = Engine('hmr', DEV), Engine('hmr', DEV)
     a.experimental()
-    a.set_option('tail_fuse', 1)
-    assert a.get_option('tail_fuse') == 1
+    a.set_option('trunk_subbatch_layers', 3)
+    assert a.get_option('trunk_subbatch_layers') == 3
     with pytest.raises(_lib.SpecmiError):
-        b.set_option('tail_fuse', 1)                     # per handle: b did not opt in
+        b.set_option('trunk_subbatch_layers', 3)         # per handle: b did not opt in
     a.experimental(False)
     with pytest.raises(_lib.SpecmiError):
         a.set_option('wsplit', 0)
     monkeypatch.setenv('SPECMI_EXPERIMENTAL', '1')
-    b.set_option('tail_fuse', 1)
+    b.set_option('trunk_subbatch_layers', 3)
     monkeypatch.setenv('SPECMI_EXPERIMENTAL', '0')
     with pytest.raises(_lib.SpecmiError):
         b.set_option('wsplit', 0)

@@ -1,5 +1,5 @@
-"""Round 5: the wave-split unit of the canonical k-sum tree (conv_wsplit.hip), the 'single' plan (batch 1-2), the persistent
-multi-layer walker (conv_persist.hip, opt-in) and the hand-off state hardening.  Reference operating point:
+"""Round 5: the wave-split unit of the canonical k-sum tree (conv_wsplit.hip), the 'single' plan (batch 1-2) and the hand-off
+state hardening.  Reference operating point:
 spec/tester.py:109-151 (batch = #detections of a frame), scripts/camcalib_demo.py:95-102 (batch 1)."""
 import numpy as np
 import pytest
@@ -139,47 +139,9 @@ def test_single_plan_meets_oracle_and_is_batch_invariant(models):
                 assert torch.equal(out[k], want[k][:n]), (n, k)
 
 
-@pytest.mark.parametrize('plan,B', [('single', 1), ('single', 2), ('latency', 3), ('latency', 8)])
-def test_persistent_walker_is_bit_identical(models, plan, B):
-    """Option persist = 1: every run of implicit-GEMM layers as ONE launch of resident workgroups (completion counters between
-    layers, write-through hand-offs).  Same tile body, same tree: the bits of the per-layer launches - pair and single trunk,
-    eager and replayed - and a clean control block afterwards."""
-    from spec_amd.pipeline import SpecPipeline, GraphedPipeline
-    cc, hm = models
-    ce, he = cc.engine(torch.device(DEV)), hm.engine(torch.device(DEV))
-    ins = _inputs(61, B)
-    with pinned_plan(plan, cc, hm):
-        try:
-            res = {}
-            for persist in (0, 1):
-                for e in (ce, he):
-                    e.set_option('persist', persist)
-                    e.set_option('wsplit', 0 if persist else 1)     # the walker runs the 64x64 body; its reference may use either unit
-                fa, fb = ce.trunk_pair(he, ins[0], ins[0])
-                f1 = he.trunk(ins[0])
-                out = SpecPipeline(cc, hm, grouped=True)(*ins)
-                torch.cuda.synchronize()
-                res[persist] = [fa.clone(), fb.clone(), f1.clone()] + [out[k].clone() for k in KEYS]
-            for a, b in zip(res[0], res[1]):
-                assert torch.equal(a, b)
-            assert torch.equal(res[1][1], res[1][2])                 # pair == single trunk
-            assert ce.sync_status() == 0 and he.sync_status() == 0
-            gp = GraphedPipeline(SpecPipeline(cc, hm, grouped=True), *ins)
-            for _ in range(20):
-                out = gp(*ins)
-                for i, k in enumerate(KEYS):
-                    assert torch.equal(out[k], res[0][3 + i]), k
-            assert ce.sync_status() == 0 and he.sync_status() == 0
-        finally:
-            for e in (ce, he):
-                e.set_option('persist', 0)
-                e.set_option('wsplit', 1)
-
-
-def test_poisoned_hand_off_counters_are_reset(models):
-    """The split-K tickets and the walker's completion counters must be zero between launches.  A launch that died mid-flight
-    leaves them dirty: specmi_sync_reset, specmi_commit and the error path of a forward all zero them - the next forward gives
-    the same bits as before."""
+def test_poisoned_split_k_counters_are_reset(models):
+    """The split-K tickets must be zero between launches.  A launch that died mid-flight leaves them dirty: specmi_sync_reset,
+    specmi_commit and the error path of a forward all zero them - the next forward gives the same bits as before."""
     from spec_amd.pipeline import SpecPipeline
     from spec_amd._lib import SpecmiError
     cc, hm = models
@@ -187,30 +149,23 @@ def test_poisoned_hand_off_counters_are_reset(models):
     ins = _inputs(67, 2)
     with pinned_plan('latency', cc, hm):
         pipe = SpecPipeline(cc, hm, grouped=True)
-        for persist in (0, 1):
-            for e in (ce, he):
-                e.set_option('persist', persist)
-            try:
-                ref = {k: v.clone() for k, v in pipe(*ins).items() if k in KEYS}
-                # 1. explicit reset
-                for e in (ce, he):
-                    e.debug_poison_sync(0xDEADBEEF)
-                    e.sync_reset()
-                out = pipe(*ins)
-                for k in KEYS:
-                    assert torch.equal(out[k], ref[k]), ('reset', persist, k)
-                # 2. a forward that fails (image too small: refused before any launch) cleans up behind itself
-                for e in (ce, he):
-                    e.debug_poison_sync(7)
-                    with pytest.raises(SpecmiError):
-                        e.trunk(torch.zeros(1, 3, 16, 16, device=DEV))
-                out = pipe(*ins)
-                for k in KEYS:
-                    assert torch.equal(out[k], ref[k]), ('error path', persist, k)
-                assert ce.sync_status() == 0 and he.sync_status() == 0
-            finally:
-                for e in (ce, he):
-                    e.set_option('persist', 0)
+        ref = {k: v.clone() for k, v in pipe(*ins).items() if k in KEYS}
+        # 1. explicit reset
+        for e in (ce, he):
+            e.debug_poison_sync(0xDEADBEEF)
+            e.sync_reset()
+        out = pipe(*ins)
+        for k in KEYS:
+            assert torch.equal(out[k], ref[k]), ('reset', k)
+        # 2. a forward that fails (image too small: refused before any launch) cleans up behind itself
+        for e in (ce, he):
+            e.debug_poison_sync(7)
+            with pytest.raises(SpecmiError):
+                e.trunk(torch.zeros(1, 3, 16, 16, device=DEV))
+        out = pipe(*ins)
+        for k in KEYS:
+            assert torch.equal(out[k], ref[k]), ('error path', k)
+        assert ce.sync_status() == 0 and he.sync_status() == 0
     # 3. re-commit
     he.debug_poison_sync(3)
     ce.debug_poison_sync(3)
@@ -220,39 +175,6 @@ def test_poisoned_hand_off_counters_are_reset(models):
         out = SpecPipeline(cc, hm, grouped=True)(*ins)
         for k in KEYS:
             assert torch.equal(out[k], ref[k]), ('commit', k)
-
-
-@pytest.mark.parametrize('B', [1, 2, 3, 7, 10])
-def test_fused_tails_are_bit_identical(models, B):
-    """Option tail_fuse (opt-in): at small batches each network's tail is ONE launch - CamCalib avg-pool -> three heads -> decode,
-    HMR avg-pool + state init -> regressor map -> pose chains - with an in-launch completion counter and a last-arriver epilogue
-    (head.hip: tail_gemv_kernel).  Same code as the separate kernels: every output bit, eager and replayed, grouped and two streams."""
-    from spec_amd.pipeline import SpecPipeline, GraphedPipeline
-    cc, hm = models
-    ce, he = cc.engine(torch.device(DEV)), hm.engine(torch.device(DEV))
-    ins = _inputs(71 + B, B)
-    keys = KEYS + ('pred_pose', 'pred_shape', 'pred_cam', 'cam_roll', 'cam_f_pix', 'cam_rotmat', 'cam_intrinsics')
-    try:
-        res = {}
-        for fuse in (0, 1):
-            for e in (ce, he):
-                e.set_option('tail_fuse', fuse)
-            res[fuse] = {}
-            for tag, pp in (('grouped', SpecPipeline(cc, hm, grouped=True)), ('two_streams', SpecPipeline(cc, hm, overlap=True, grouped=False))):
-                out = pp(*ins)
-                torch.cuda.synchronize()
-                res[fuse][tag] = {k: out[k].clone() for k in keys}
-        for tag in ('grouped', 'two_streams'):
-            for k in keys:
-                assert torch.equal(res[0][tag][k], res[1][tag][k]), (tag, k)
-        gp = GraphedPipeline(SpecPipeline(cc, hm), *ins)
-        for _ in range(20):
-            out = gp(*ins)
-            for k in keys:
-                assert torch.equal(out[k], res[0]['grouped'][k]), k
-    finally:
-        for e in (ce, he):
-            e.set_option('tail_fuse', 0)
 
 
 def test_bins_lookup_on_the_device_matches_the_numpy_api():
@@ -289,9 +211,9 @@ def test_trunk_plan_reports_what_a_forward_takes(models):
         assert st['grouped'] and st['plan'] == 'single'
 
 
-def test_camcalib_head_decode_equals_the_two_calls(models):
-    """specmi_camcalib_head_decode (separate kernels and the fused tail) == specmi_camcalib_head_forward + specmi_camcalib_decode,
-    dense and with the angles as strided columns of a record, optional outputs absent."""
+def test_camcalib_head_decode_matches_the_two_calls(models):
+    """specmi_camcalib_head_decode == specmi_camcalib_head_forward + specmi_camcalib_decode, dense and with the angles as strided
+    columns of a record, optional outputs absent."""
     cc, _ = models
     e = cc.engine(torch.device(DEV))
     for B in (1, 5):
@@ -301,21 +223,16 @@ def test_camcalib_head_decode_equals_the_two_calls(models):
             feat = e.trunk(x)
             logits = e.camcalib_head(feat)
             ref = e.camcalib_decode(logits[0], logits[1], logits[2], ih, iw)
-            for fuse in (0, 1):
-                e.set_option('tail_fuse', fuse)
-                try:
-                    lg, cam = e.camcalib_head_decode(feat, ih, iw)
-                    for a, b in zip(lg, logits):
-                        assert torch.equal(a, b)
-                    for k in ('vfov', 'pitch', 'roll', 'f_pix', 'cam_rotmat', 'cam_intrinsics'):
-                        assert torch.equal(cam[k], ref[k]), (B, fuse, k)
-                    rec = torch.zeros(B, 7, device=DEV)
-                    lg2, cam2 = e.camcalib_head_decode(feat, None, None, angles_out=(rec[:, 1], rec[:, 3], rec[:, 5]))
-                    assert cam2['f_pix'] is None and cam2['cam_intrinsics'] is None
-                    assert torch.equal(rec[:, 1], ref['vfov']) and torch.equal(rec[:, 3], ref['pitch']) and torch.equal(rec[:, 5], ref['roll'])
-                    assert torch.equal(cam2['cam_rotmat'], ref['cam_rotmat']) and float(rec[:, [0, 2, 4, 6]].abs().max()) == 0.0
-                finally:
-                    e.set_option('tail_fuse', 0)
+            lg, cam = e.camcalib_head_decode(feat, ih, iw)
+            for a, b in zip(lg, logits):
+                assert torch.equal(a, b)
+            for k in ('vfov', 'pitch', 'roll', 'f_pix', 'cam_rotmat', 'cam_intrinsics'):
+                assert torch.equal(cam[k], ref[k]), (B, k)
+            rec = torch.zeros(B, 7, device=DEV)
+            lg2, cam2 = e.camcalib_head_decode(feat, None, None, angles_out=(rec[:, 1], rec[:, 3], rec[:, 5]))
+            assert cam2['f_pix'] is None and cam2['cam_intrinsics'] is None
+            assert torch.equal(rec[:, 1], ref['vfov']) and torch.equal(rec[:, 3], ref['pitch']) and torch.equal(rec[:, 5], ref['roll'])
+            assert torch.equal(cam2['cam_rotmat'], ref['cam_rotmat']) and float(rec[:, [0, 2, 4, 6]].abs().max()) == 0.0
 
 
 @pytest.mark.parametrize('num_fc_layers,B', [(2, 1), (2, 5), (3, 2), (2, 40)])

@@ -57,7 +57,7 @@ def test_launch_structure_rule_lives_in_one_place():
     assert 'launch_structure' in src and not re.search(r'1[17]\s*<=\s*b\s*<=\s*(16|20)', src)
 
 
-def test_round5_entry_points_are_declared_and_bound():
+def test_round5_entry_points_and_options_are_declared():
     from spec_amd import _lib
     hdr = open(os.path.join(ROOT, 'include', 'specmi.h')).read()
     for name in ('specmi_trunk_plan', 'specmi_sync_status', 'specmi_sync_reset', 'specmi_debug_poison_sync', 'specmi_camcalib_head_decode'):
@@ -67,5 +67,5 @@ def test_round5_entry_points_are_declared_and_bound():
     for name in _lib.PROTOTYPES:
         assert hasattr(lib, name), name
     # the options a caller can reach are documented where the ABI is
-    for opt in ('"wsplit"', '"persist"', '"tail_fuse"', '"single_max_batch"', '3 = single'):
+    for opt in ('"wsplit"', '"single_max_batch"', '3 = single'):
         assert opt in hdr, opt
