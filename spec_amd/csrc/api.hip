@@ -378,7 +378,7 @@ static int launch_op(specmi_handle* h, const TrunkOp& op, const OpLaunch& L, con
             SkPlan pw = pl;
             const long t32 = conv_wsplit_tiles(L.a, groups);
             const long ng = pl.leaves / (pl.G > 0 ? pl.G : 1);
-            const int nch = L.a.KH * L.a.KW * (L.a.Cin / 32) + (L.a.x2 ? L.a.Cin2 / 32 : 0);
+            const int nch = conv_k_chunks(L.a);
             const double t_leaf = 0.45 * (double)(nch / pl.leaves);
             const long slots = opt_i(h, "wsplit_slots", 256);
             const double cost_all = (double)((t32 + slots - 1) / slots) * (double)ng * t_leaf;

@@ -25,16 +25,13 @@
 //     residual, ReLU, 16-byte row-contiguous stores.
 #include <cstring>
 
-#include "specmi_internal.h"
+#include "conv_igemm_tile.h"
 
 namespace specmi {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct SArgs {
     const float* x;
@@ -53,8 +50,6 @@ struct SArgs {
     // TAPS: a KH x KW convolution as an implicit GEMM, K ordered (ky, kx, ci): stage s = (filter tap s / cpt, channels 16 (s % cpt)..)
     int H, W, KH, KW, stride, pad, cpt;
 };
-
-constexpr unsigned kOOB16 = 0x80000000u;
 
 // fp32 pair -> (leading bf16 pair, exact fp32 residual pair)
 __device__ __forceinline__ unsigned split_pair(float& a, float& b) {
@@ -80,10 +75,7 @@ __global__ void __launch_bounds__(256) conv1x1_bf16s_kernel(const SArgs p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, hh = lane >> 5;
 
-    // XCD-aware tile order (as conv_igemm.hip): the 8 XCDs get contiguous runs of tiles, n fastest
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nblk >> 3, r8 = nblk & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int L = xcd_tile_order(blockIdx.x, gridDim.x);
     const int tile_m = L / p.nbn, tile_n = L - tile_m * p.nbn;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -98,7 +90,7 @@ __global__ void __launch_bounds__(256) conv1x1_bf16s_kernel(const SArgs p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int m = m0 + a_r + 64 * i;
-        a_voff[i] = m < p.M ? (unsigned)(m * p.ldx * 4 + a_kq * 16) : kOOB16;
+        a_voff[i] = m < p.M ? (unsigned)(m * p.ldx * 4 + a_kq * 16) : kOutOfRange;
         if (TAPS) {   // the row's output pixel -> offset of its tap (0, 0) (may wrap for padded rows: only used on valid taps)
             const int mm = m < p.M ? m : 0;
             const int b_ = mm / p.OHW, rem = mm - b_ * p.OHW, oy = rem / p.OW, ox = rem - oy * p.OW;
@@ -117,13 +109,13 @@ __global__ void __launch_bounds__(256) conv1x1_bf16s_kernel(const SArgs p) {
                 const int b2 = mm / p.OHW, rem = mm - b2 * p.OHW, oy = rem / p.OW, ox = rem - oy * p.OW;
                 pix2 = (b2 * p.H2 + oy * p.stride2) * p.W2 + ox * p.stride2;
             }
-            a_voff2[i] = m < p.M ? (unsigned)(pix2 * p.ldx2 * 4 + a_kq * 16) : kOOB16;
+            a_voff2[i] = m < p.M ? (unsigned)(pix2 * p.ldx2 * 4 + a_kq * 16) : kOutOfRange;
         }
     }
     const unsigned a_lds = (unsigned)((a_kq >> 1) * (BM * 16) + a_r * 16 + (a_kq & 1) * 8);   // + 64 rows: + 1024
     const bool b_active = BN == 128 || tid < 2 * BN;
     const int b_oct = tid / BN, b_n = tid % BN;
-    const unsigned b_voff = b_active ? (unsigned)((b_oct * p.Npad + n0 + b_n) * 16) : kOOB16;
+    const unsigned b_voff = b_active ? (unsigned)((b_oct * p.Npad + n0 + b_n) * 16) : kOutOfRange;
 
     f32x4 ra[2];
     u32x4 rb[NP];
@@ -136,7 +128,7 @@ __global__ void __launch_bounds__(256) conv1x1_bf16s_kernel(const SArgs p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
                 ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                    xrs, ((a_mask[TAPS ? i : 0] >> tap) & 1u) ? a_voff[i] + tap_bytes : kOOB16, (unsigned)(c0 * 64), 0));
+                    xrs, ((a_mask[TAPS ? i : 0] >> tap) & 1u) ? a_voff[i] + tap_bytes : kOutOfRange, (unsigned)(c0 * 64), 0));
         } else {
 #pragma unroll
         for (int i = 0; i < 2; ++i)

@@ -27,15 +27,12 @@
 #include <cmath>
 #include <cstring>
 
-#include "specmi_internal.h"
+#include "conv_igemm_tile.h"
 
 namespace specmi {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct HArgs {
     const void* x;          // fp16 NHWC, pixel stride ldx (multiple of 8)
@@ -53,8 +50,6 @@ struct HArgs {
     int nsteps1, ldx2, H2, W2, stride2;
 };
 
-constexpr unsigned kOOBh = 0x80000000u;
-
 template <int BN, bool DUAL, bool OUT32>
 __global__ void __launch_bounds__(256) conv_f16_kernel(const HArgs p) {
     static_assert(BN == 128 || BN == 64, "");
@@ -68,10 +63,7 @@ __global__ void __launch_bounds__(256) conv_f16_kernel(const HArgs p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, hh = lane >> 5;
 
-    // XCD-aware tile order (as conv_igemm.hip): the 8 XCDs get contiguous runs of tiles, n fastest
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nblk >> 3, r8 = nblk & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int L = xcd_tile_order(blockIdx.x, gridDim.x);
     const int tile_m = L / p.nbn, tile_n = L - tile_m * p.nbn;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -94,7 +86,7 @@ __global__ void __launch_bounds__(256) conv_f16_kernel(const HArgs p) {
         a_base[i] = ((b_ * p.H + iy0) * p.W + ix0) * p.ldx * 2;   // bytes of tap (0, 0) (may be negative: only valid taps add up)
         if (DUAL) {
             const int pix2 = (b_ * p.H2 + oy * p.stride2) * p.W2 + ox * p.stride2;
-            a_voff2[i] = m < p.M ? (unsigned)(pix2 * p.ldx2 * 2) : kOOBh;
+            a_voff2[i] = m < p.M ? (unsigned)(pix2 * p.ldx2 * 2) : kOutOfRange;
         }
     }
     const unsigned a_lds = (unsigned)(a_q * APL + a_r * 16);      // + 64 rows: + 1024
@@ -107,7 +99,7 @@ __global__ void __launch_bounds__(256) conv_f16_kernel(const HArgs p) {
             const unsigned c = (unsigned)(((s - p.nsteps1) * 4 + a_q) * 16);
 #pragma unroll
             for (int i = 0; i < 2; ++i)
-                ra[i] = __builtin_amdgcn_raw_buffer_load_b128(x2rs, a_voff2[DUAL ? i : 0] == kOOBh ? kOOBh : a_voff2[DUAL ? i : 0] + c, 0, 0);
+                ra[i] = __builtin_amdgcn_raw_buffer_load_b128(x2rs, a_voff2[DUAL ? i : 0] == kOutOfRange ? kOutOfRange : a_voff2[DUAL ? i : 0] + c, 0, 0);
         } else {
             const int o = s * 4 + a_q;
             const int tap = o / p.cpo, c8 = o - tap * p.cpo;
@@ -116,7 +108,7 @@ __global__ void __launch_bounds__(256) conv_f16_kernel(const HArgs p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const bool ok = tap < p.ntaps && (unsigned)(a_iy[i] + ky) < (unsigned)p.H && (unsigned)(a_ix[i] + kx) < (unsigned)p.W;
-                ra[i] = __builtin_amdgcn_raw_buffer_load_b128(xrs, ok ? (unsigned)(a_base[i] + toff) : kOOBh, 0, 0);
+                ra[i] = __builtin_amdgcn_raw_buffer_load_b128(xrs, ok ? (unsigned)(a_base[i] + toff) : kOutOfRange, 0, 0);
             }
         }
 #pragma unroll

@@ -78,23 +78,15 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_f32_kernel(const KA
     float* Bs = smem + 2 * A_STAGE;
 
     const int tid = threadIdx.x;
-    const bool grp = blockIdx.z != 0;   // wave-uniform: scalar selects
-    const float* const px = grp ? p.g1.x : p.x;
-    const float* const pw = grp ? p.g1.w : p.w;
-    const float* const pscale = grp ? p.g1.scale : p.scale;
-    const float* const pshift = grp ? p.g1.shift : p.shift;
-    const float* const pres = grp ? p.g1.res : p.res;
-    const float* const px2 = grp ? p.g1.x2 : p.x2;
-    float* const pout = grp ? p.g1.out : p.out;
+    const NetOperands net = net_operands(p);
+    const float* const pres = net.res;
 #ifdef SPECMI_TUNE
     const long long t_start = __builtin_amdgcn_s_memtime();
     long long tp[4] = {0, 0, 0, 0};
     (void)tp;
 #endif
 
-    // ---- XCD-aware tile order (bijective for any grid size) ------------------------------
-    const int xcd = bid & 7, q8 = nblk >> 3, r8 = nblk & 7;
-    const int L = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int L = xcd_tile_order(bid, nblk);
     int tile_m = L / p.nbn, tile_n = L - tile_m * p.nbn;
     if (p.xcd_cols) {
         // Weight panel larger than an XCD's 4 MiB L2 and many tile columns (layer4 conv3: 512 / 3072 x 2048 = 4 / 12 MiB, 32
@@ -102,62 +94,23 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_f32_kernel(const KA
         // of L2 misses per launch against 0.24 / 0.19 GB algorithmic, profiles/r03_v_layer_traffic.txt).  Here an XCD owns a
         // fixed eighth of the columns - its slice of the panel stays in its L2 - and walks all tile rows; the (smaller) A
         // operand is then read by all eight XCDs instead.  nbn % 8 == 0, so the grid splits evenly.
-        tile_n = xcd * p.xcd_cols + (bid >> 3) % p.xcd_cols;
+        tile_n = (bid & 7) * p.xcd_cols + (bid >> 3) % p.xcd_cols;
         tile_m = (bid >> 3) / p.xcd_cols;
     }
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
     // ---- buffer descriptors (wave-uniform) and per-thread row offsets -----------------------
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(px), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pw), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t x2rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DUAL ? px2 : px), 0, DUAL ? p.x2_bytes : p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(net.x), 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(net.w), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t x2rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DUAL ? net.x2 : net.x), 0, DUAL ? p.x2_bytes : p.x_bytes, 0x00020000);
     const int a_kq = tid % KQ, a_r = tid / KQ;
-    unsigned a_voff[AI];   // byte offset of (row's tap-(0,0) pixel, quad a_kq); out-of-range when the row is past M (1x1)
-    unsigned a_mask[AI];   // 3x3: bit t = filter tap t lies inside the image for this row
-    unsigned a_voff2[DUAL ? AI : 1];   // DUAL: the row's pixel in the second source (its own size / stride / channel count)
-    // The tile prologue sits on every workgroup's critical path, so the pixel decode avoids the
-    // ~40-instruction integer divide: 1x1/stride-1 rows address the input with m itself, other
-    // shapes divide by OH*OW and OW with host-computed magic multipliers.
+    unsigned a_voff[AI], a_mask[AI], a_voff2[DUAL ? AI : 1];   // RowAddr of the thread's rows
 #pragma unroll
     for (int i = 0; i < AI; ++i) {
-        const int m = m0 + a_r + ARS * i;
-        const bool ok = m < p.M;
-        const int mm = ok ? m : 0;
-        if (DUAL) {
-            if (p.stride2 == 1) {
-                a_voff2[i] = ok ? (unsigned)(mm * p.ldx2 * 4 + a_kq * 16) : kOutOfRange;
-            } else {
-                const int b2 = p.OHW == 1 ? mm : (int)(__umulhi((unsigned)mm, p.mg_ohw) >> p.sh_ohw);
-                const int rem2 = mm - b2 * p.OHW;
-                const int oy2 = p.OW == 1 ? rem2 : (int)(__umulhi((unsigned)rem2, p.mg_ow) >> p.sh_ow);
-                const int ox2 = rem2 - oy2 * p.OW;
-                const int pix2 = (b2 * p.H2 + oy2 * p.stride2) * p.W2 + ox2 * p.stride2;
-                a_voff2[i] = ok ? (unsigned)(pix2 * p.ldx2 * 4 + a_kq * 16) : kOutOfRange;
-            }
-        }
-        if (IS1X1 && p.stride == 1) {
-            a_voff[i] = ok ? (unsigned)(mm * p.ldx * 4 + a_kq * 16) : kOutOfRange;
-            a_mask[i] = 0;
-            continue;
-        }
-        const int b = p.OHW == 1 ? mm : (int)(__umulhi((unsigned)mm, p.mg_ohw) >> p.sh_ohw);
-        const int rem = mm - b * p.OHW;
-        const int oy = p.OW == 1 ? rem : (int)(__umulhi((unsigned)rem, p.mg_ow) >> p.sh_ow);
-        const int ox = rem - oy * p.OW;
-        const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-        const int pix0 = (b * p.H + iy0) * p.W + ix0;
-        const unsigned off = (unsigned)(pix0 * p.ldx * 4 + a_kq * 16);   // wraps for padded rows; only used on valid taps
-        if (IS1X1) {
-            a_voff[i] = ok ? off : kOutOfRange;
-            a_mask[i] = 0;
-        } else {
-            a_voff[i] = off;
-            unsigned colbits = 0, mk = 0;   // tap (ky,kx) is inside the image iff row ky and column kx are
-            for (int kx = 0; kx < p.KW; ++kx) colbits |= ((unsigned)(ix0 + kx) < (unsigned)p.W ? 1u : 0u) << kx;
-            for (int ky = 0; ky < p.KH; ++ky)
-                if ((unsigned)(iy0 + ky) < (unsigned)p.H) mk |= colbits << (ky * p.KW);
-            a_mask[i] = ok ? mk : 0u;
-        }
+        const RowAddr r = conv_row_addr(p, IS1X1, DUAL, m0 + a_r + ARS * i, a_kq * 16);
+        a_voff[i] = r.voff;
+        a_mask[i] = r.mask;
+        if (DUAL) a_voff2[i] = r.voff2;
     }
     unsigned b_voff[BI];
 #pragma unroll
@@ -479,14 +432,9 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_f32_kernel(const KA
     // 4-byte stores at a row stride; after the transpose every lane moves 16 contiguous bytes.
     // All waves have passed the barrier above, so the A/B stages are free to reuse.
     float* Cs = smem;
-    float* const outp = pout;
     if (SPLITK && nslices > 1) {
-        // Partial tile -> workspace in accumulator order (16 bytes per lane, consecutive lanes consecutive: coalesced), then
-        // the arrival ticket.  Per-XCD L2s are not kept consistent with each other and a CU's L1 is never refreshed by another CU's
-        // stores, so the hand-off is the write-through form (MI355X_MICROARCH.md, inter-workgroup visibility): sc1 stores
-        // leave the XCD's L2 for memory, every wave drains its stores (vmcnt 0), ONE lane takes the ticket with a relaxed
-        // agent-scope atomic, and the last arriver reads all slabs with sc1 loads (no L1, fresh from the fabric) - no
-        // cache-wide write-back / invalidate (a __threadfence() per workgroup measured 35 us per launch here).
+        // Partial tile -> workspace in accumulator order (16 bytes per lane, consecutive lanes consecutive: coalesced) with
+        // write-through stores, then the arrival ticket (sk_last_arriver)
         const unsigned S = (unsigned)nslices;
         const size_t tile = blockIdx.z * gridDim.x + blockIdx.x;
         constexpr unsigned SLAB = BM * BN * 4;   // bytes
@@ -506,18 +454,8 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_f32_kernel(const KA
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), srs,
                                                            (unsigned)((((i * TN + j) * 4 + r4) * NT + tid) * 16), soff, /*sc1*/ 16);
                 }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's slab stores have left for memory
-        __syncthreads();
-        int* const flag = reinterpret_cast<int*>(smem);     // (the one LDS array: the stages are free after the loop's last barrier)
-        if (tid == 0) {
-            const unsigned ticket = __hip_atomic_fetch_add(p.sk_cnt + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = ticket == S - 1;
-            // every slice has arrived: the counter is free again for the next launch / graph replay
-            if (last) __hip_atomic_store(p.sk_cnt + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = last;
-        }
-        __syncthreads();
-        if (!*flag) return;
+        // (the flag takes the one LDS array: the stages are free after the loop's last barrier)
+        if (!sk_last_arriver(p.sk_cnt + tile, S, reinterpret_cast<int*>(smem))) return;
         __syncthreads();   // (the flag word is about to be overwritten by the transpose)
         // the rest of the canonical tree, whichever slice arrived last: leaf slabs fold G at a time into groups and the
         // groups into the result; group slabs fold into the result.  All slabs of a group (<= 4 x NQD loads) are in flight at once.
@@ -613,43 +551,24 @@ __global__ void __launch_bounds__(64 * WGM * WGN) conv_igemm_f32_kernel(const KA
             }
     __syncthreads();
 
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(pscale + n);
-    const f32x4 sh = *reinterpret_cast<const f32x4*>(pshift + n);
+    const f32x4 sc = *reinterpret_cast<const f32x4*>(net.scale + n);
+    const f32x4 sh = *reinterpret_cast<const f32x4*>(net.shift + n);
     if (full) {
         // the residual rows were fetched under the last chunk's MFMAs (rr)
 #pragma unroll
         for (int ps = 0; ps < NP; ++ps) {
             const int row = r0 + ps * RPP;
             const int m = m0 + row;
-            const f32x4 a = *reinterpret_cast<const f32x4*>(Cs + row * LDC + cq * 4);
-            f32x4 v;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaf(a[e], sc[e], sh[e]);
-            if (pres) {
-                if (SPLITK) rr[ps] = *reinterpret_cast<const f32x4*>(pres + ((m < p.M) ? (size_t)m * p.ldo + n : (size_t)n));
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += rr[ps][e];
-            }
-            if (p.relu) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-            }
-            if (m < p.M && !TUNE_ABLATE(4)) *reinterpret_cast<f32x4*>(outp + (size_t)m * p.ldo + n) = v;
+            if (SPLITK && pres) rr[ps] = *reinterpret_cast<const f32x4*>(pres + ((m < p.M) ? (size_t)m * p.ldo + n : (size_t)n));
+            const f32x4 v = epilogue_quad(*reinterpret_cast<const f32x4*>(Cs + row * LDC + cq * 4), sc, sh, pres != nullptr, rr[ps], p.relu);
+            if (m < p.M && !TUNE_ABLATE(4)) *reinterpret_cast<f32x4*>(net.out + (size_t)m * p.ldo + n) = v;
         }
     } else {
         for (int ps = 0; ps < NP; ++ps) {
             const int row = r0 + ps * RPP;
             const int m = m0 + row;
             if (m >= p.M) break;
-            const size_t o = (size_t)m * p.ldo + n;
-            for (int e = 0; e < 4; ++e) {
-                if (n + e < p.Cout) {
-                    float t = fmaf(Cs[row * LDC + cq * 4 + e], sc[e], sh[e]);
-                    if (pres) t += pres[o + e];
-                    if (p.relu) t = fmaxf(t, 0.f);
-                    outp[o + e] = t;
-                }
-            }
+            epilogue_tail(Cs + row * LDC + cq * 4, sc, sh, pres, p.relu, net.out, (size_t)m * p.ldo + n, p.Cout - n);
         }
     }
 #ifdef SPECMI_TUNE
@@ -730,7 +649,7 @@ static int pick_variant(int M, int Npad, bool is1x1, int K, int force, int Cout)
 }
 
 const char* conv_igemm_variant(const ConvArgs& a) {
-    return kVariantNames[pick_variant(a.B * a.OH * a.OW, a.Npad, a.KH == 1 && a.KW == 1 && a.pad == 0, a.Cin + a.Cin2, a.force_variant, a.Cout)];
+    return kVariantNames[pick_variant(a.B * a.OH * a.OW, a.Npad, conv_is_1x1(a), a.Cin + a.Cin2, a.force_variant, a.Cout)];
 }
 
 static int dispatch_dual(int v, const KArgs& k, int M, const LaunchCtx& ctx, double flops, double bytes) {
@@ -759,17 +678,6 @@ static int dispatch(int v, const KArgs& k, int M, const LaunchCtx& ctx, double f
     }
 }
 
-// floor(n / d) == umulhi(n, mg) >> sh for every n < 2^31 and 2 <= d < 2^31:
-// L = 31 + ceil(log2 d), mg = floor(2^L / d) + 1 (< 2^32), sh = L - 32.  d == 1 is handled in the kernel.
-static void magic_u32(unsigned d, unsigned* mg, unsigned* sh) {
-    if (d < 2) { *mg = 0; *sh = 0; return; }
-    unsigned s = 0;
-    while ((1ull << s) < d) ++s;
-    const unsigned L = 31 + s;
-    *mg = (unsigned)((1ull << L) / d + 1ull);
-    *sh = L - 32;
-}
-
 static void make_kargs(const ConvArgs& a, const ConvArgs* b, KArgs& k, double* flops, double* bytes) {
     k.x = a.x; k.w = a.w; k.scale = a.scale; k.shift = a.shift; k.res = a.res; k.out = a.out;
     k.g1.x = nullptr; k.g1.w = nullptr; k.g1.scale = nullptr; k.g1.shift = nullptr; k.g1.res = nullptr; k.g1.x2 = nullptr; k.g1.out = nullptr;
@@ -781,7 +689,7 @@ static void make_kargs(const ConvArgs& a, const ConvArgs* b, KArgs& k, double* f
     k.M = M;
     const bool dual = a.x2 != nullptr;
     k.cpc = a.Cin / 32;
-    k.nchunks = a.KH * a.KW * k.cpc + (dual ? a.Cin2 / 32 : 0);
+    k.nchunks = conv_k_chunks(a);
     k.x2 = a.x2; k.H2 = a.H2; k.W2 = a.W2; k.ldx2 = a.ldx2; k.stride2 = a.stride2; k.cpc1 = k.cpc;
     k.x2_bytes = dual ? (unsigned)((size_t)a.B * a.H2 * a.W2 * a.ldx2 * 4) : 0u;
     k.nbn = 0;
@@ -798,10 +706,7 @@ static void make_kargs(const ConvArgs& a, const ConvArgs* b, KArgs& k, double* f
     k.vec_ok = (a.ldo % 4 == 0) && ((reinterpret_cast<uintptr_t>(a.out) & 15) == 0) &&
                (!a.res || (reinterpret_cast<uintptr_t>(a.res) & 15) == 0) &&
                (!b || (((reinterpret_cast<uintptr_t>(b->out) & 15) == 0) && (!b->res || (reinterpret_cast<uintptr_t>(b->res) & 15) == 0)));
-    const double Kd = (double)a.KH * a.KW * a.Cin + (dual ? a.Cin2 : 0);
-    *flops = 2.0 * (double)M * a.Cout * Kd;
-    *bytes = 4.0 * ((double)a.B * a.H * a.W * a.Cin + (dual ? (double)M * a.Cin2 : 0.0) +
-                    (double)M * a.Cout * (a.res ? 2.0 : 1.0) + Kd * a.Cout);
+    conv_flops_bytes(a, flops, bytes);
 }
 
 static int launch_one(const ConvArgs& a, const LaunchCtx& ctx, const ConvArgs* b = nullptr) {
@@ -810,7 +715,7 @@ static int launch_one(const ConvArgs& a, const LaunchCtx& ctx, const ConvArgs* b
     make_kargs(a, b, k, &flops, &bytes);
     const int M = k.M;
     const bool dual = a.x2 != nullptr;
-    const bool is1x1 = (a.KH == 1 && a.KW == 1 && a.pad == 0);
+    const bool is1x1 = conv_is_1x1(a);
     const int v = pick_variant(M, a.Npad, is1x1, a.Cin + (dual ? a.Cin2 : 0), a.force_variant, a.Cout);
     if (dual) return dispatch_dual(v, k, M, ctx, flops, bytes);
     return is1x1 ? dispatch<true>(v, k, M, ctx, flops, bytes) : dispatch<false>(v, k, M, ctx, flops, bytes);
@@ -820,7 +725,7 @@ static int launch_one(const ConvArgs& a, const LaunchCtx& ctx, const ConvArgs* b
 // K slices of the FC GEMMs (CamCalib heads, HMR regressor; M = batch rows <= 1024): the rule every plan has used since
 // round 1, so the headline's FC results keep their bits
 int conv_igemm_splitk_plan(const ConvArgs& a) {
-    const bool is1x1 = (a.KH == 1 && a.KW == 1 && a.pad == 0 && a.stride == 1);
+    const bool is1x1 = conv_is_1x1(a) && a.stride == 1;
     const int M = a.B * a.OH * a.OW;
     if (!is1x1 || a.x2 || M > 1024 || a.force_variant) return 1;
     const int nch = a.Cin / 32;
@@ -836,7 +741,7 @@ int conv_igemm_splitk_plan(const ConvArgs& a) {
 // count that gives the pair of trunks at batch 1 (2 x tiles) `target_wgs` workgroups, else the largest allowed.
 int conv_igemm_sk_slices(const ConvArgs& a, int target_wgs, int min_chunks) {
     if (a.Npad % 64 != 0 || a.Cin % 32 != 0 || a.force_variant) return 1;
-    const int nch = a.KH * a.KW * (a.Cin / 32) + (a.x2 ? a.Cin2 / 32 : 0);
+    const int nch = conv_k_chunks(a);
     // K < 512: the unsplit kernel wins at every batch size (measured per layer, profiles/r04_b_latency_layers.txt: a second
     // slab round trip costs more than walking 8-12 chunks)
     if (nch < 16) return 1;
@@ -866,7 +771,7 @@ SkPlan conv_igemm_sk_plan(const ConvArgs& a, int groups, int target_wgs, int min
         // are the three units; ties go to the larger one (fewer slabs).  It reproduces what the threshold sweeps found batch by
         // batch - group at 10 images, leaves at 12, where 240 / 400 workgroups were each right once (profiles/r05_n_*).
         const long slots = fill_wgs < 0 ? -fill_wgs : 256;
-        const int nch = a.KH * a.KW * (a.Cin / 32) + (a.x2 ? a.Cin2 / 32 : 0);
+        const int nch = conv_k_chunks(a);
         const int cand[3] = {pl.leaves, pl.G, 1};
         double best = 0.0;
         pl.unit = pl.leaves;
@@ -887,16 +792,11 @@ SkPlan conv_igemm_sk_plan(const ConvArgs& a, int groups, int target_wgs, int min
     return pl;
 }
 
-size_t conv_igemm_sk_ws_floats(const ConvArgs& a, int S, int groups) {
-    const size_t tiles = (size_t)((a.B * a.OH * a.OW + 63) / 64) * (a.Npad / 64);
-    return S > 1 ? tiles * S * groups * 64 * 64 : 0;
-}
 int conv_igemm_sk_tiles(const ConvArgs& a, int groups) { return ((a.B * a.OH * a.OW + 63) / 64) * (a.Npad / 64) * groups; }
+size_t conv_igemm_sk_ws_floats(const ConvArgs& a, int S, int groups) { return S > 1 ? (size_t)conv_igemm_sk_tiles(a, groups) * S * 64 * 64 : 0; }
 
-int conv_igemm_sk_check(const ConvArgs& a, const SkPlan& pl, const ConvArgs* b) {
-    const int nch = a.KH * a.KW * (a.Cin / 32) + (a.x2 ? a.Cin2 / 32 : 0);
-    if (pl.leaves < 1 || nch % pl.leaves != 0 || pl.G < 1 || pl.leaves % pl.G != 0 || (pl.unit != 1 && pl.unit != pl.G && pl.unit != pl.leaves) ||
-        a.Cin % 32 != 0 || a.Npad % 64 != 0 || a.ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(a.x) & 15))
+int conv_igemm_check(const ConvArgs& a, const ConvArgs* b) {
+    if (a.Cin % 32 != 0 || a.Npad % 64 != 0 || a.ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(a.x) & 15))
         return (int)hipErrorInvalidValue;
     if (a.x2 && (a.KH != 1 || a.KW != 1 || a.pad != 0 || a.Cin2 % 32 != 0 || a.ldx2 % 4 != 0 || (reinterpret_cast<uintptr_t>(a.x2) & 15)))
         return (int)hipErrorInvalidValue;
@@ -906,6 +806,14 @@ int conv_igemm_sk_check(const ConvArgs& a, const SkPlan& pl, const ConvArgs* b) 
               b->H2 != a.H2 || b->W2 != a.W2 || b->ldx2 != a.ldx2 || b->Cin2 != a.Cin2 || b->stride2 != a.stride2 ||
               (reinterpret_cast<uintptr_t>(b->x) & 15) || (b->x2 && (reinterpret_cast<uintptr_t>(b->x2) & 15))))
         return (int)hipErrorInvalidValue;
+    return 0;
+}
+
+int conv_igemm_sk_check(const ConvArgs& a, const SkPlan& pl, const ConvArgs* b) {
+    const int nch = conv_k_chunks(a);
+    if (pl.leaves < 1 || nch % pl.leaves != 0 || pl.G < 1 || pl.leaves % pl.G != 0 || (pl.unit != 1 && pl.unit != pl.G && pl.unit != pl.leaves))
+        return (int)hipErrorInvalidValue;
+    if (int rc = conv_igemm_check(a, b)) return rc;
     size_t img_bytes = (size_t)a.H * a.W * a.ldx * 4;
     if (a.x2 && (size_t)a.H2 * a.W2 * a.ldx2 * 4 > img_bytes) img_bytes = (size_t)a.H2 * a.W2 * a.ldx2 * 4;
     const size_t limit = (size_t)1 << 31;
@@ -914,10 +822,9 @@ int conv_igemm_sk_check(const ConvArgs& a, const SkPlan& pl, const ConvArgs* b) 
 }
 
 void conv_igemm_make_sk_kargs(const ConvArgs& a, const SkPlan& pl, const ConvArgs* b, KArgs& k) {
-    const int nch = a.KH * a.KW * (a.Cin / 32) + (a.x2 ? a.Cin2 / 32 : 0);
     double flops, bytes;
     make_kargs(a, b, k, &flops, &bytes);
-    k.sk_leaf = nch / pl.leaves; k.sk_G = pl.G; k.sk_unit = pl.unit;
+    k.sk_leaf = k.nchunks / pl.leaves; k.sk_G = pl.G; k.sk_unit = pl.unit;
     k.nchunks = k.sk_leaf * pl.unit;
     k.nbn = a.Npad / 64;
     k.xcd_cols = 0;
@@ -932,13 +839,11 @@ int launch_conv_igemm_sk(const ConvArgs& a, const SkPlan& pl, const SkWs& sk, co
     if (S > 1 && (!sk.ws || !sk.cnt || conv_igemm_sk_ws_floats(a, S, groups) > sk.floats || conv_igemm_sk_tiles(a, groups) > sk.ncnt))
         return (int)hipErrorInvalidValue;
     KArgs k;
-    double flops, bytes;
-    make_kargs(a, b, k, &flops, &bytes);
-    const int nch = a.KH * a.KW * (a.Cin / 32) + (a.x2 ? a.Cin2 / 32 : 0);
-    k.sk_leaf = nch / pl.leaves; k.sk_G = pl.G; k.sk_unit = pl.unit;
-    k.nchunks = k.sk_leaf * pl.unit;
+    conv_igemm_make_sk_kargs(a, pl, b, k);
     k.sk_ws = sk.ws; k.sk_cnt = sk.cnt;
-    const bool is1x1 = (a.KH == 1 && a.KW == 1 && a.pad == 0);
+    double flops, bytes;
+    conv_flops_bytes(a, &flops, &bytes);
+    const bool is1x1 = conv_is_1x1(a);
     if (a.x2) return launch_variant<64, 64, 2, 2, true, 32, true, true, true>(k, k.M, ctx, "conv_igemm_f32<64x64,2x2,2src,splitK>", flops, bytes, S);
     if (is1x1) return launch_variant<64, 64, 2, 2, true, 32, false, true, true>(k, k.M, ctx, "conv_igemm_f32<64x64,2x2,splitK>", flops, bytes, S);
     return launch_variant<64, 64, 2, 2, false, 32, false, true, true>(k, k.M, ctx, "conv_igemm_f32<64x64,2x2,splitK>", flops, bytes, S);
@@ -946,17 +851,7 @@ int launch_conv_igemm_sk(const ConvArgs& a, const SkPlan& pl, const SkWs& sk, co
 
 // b != nullptr: the same layer shape of a second network (its own x / w / scale / shift / res / x2 / out) in the same launch
 int launch_conv_igemm(const ConvArgs& a, const LaunchCtx& ctx, const ConvArgs* b) {
-    if (a.Cin % 32 != 0 || a.Npad % 64 != 0 || a.ldx % 4 != 0 || (reinterpret_cast<uintptr_t>(a.x) & 15))
-        return (int)hipErrorInvalidValue;
-    if (b && (b->B != a.B || b->H != a.H || b->W != a.W || b->Cin != a.Cin || b->ldx != a.ldx || b->OH != a.OH || b->OW != a.OW ||
-              b->Cout != a.Cout || b->Npad != a.Npad || b->ldo != a.ldo || b->KH != a.KH || b->KW != a.KW || b->stride != a.stride ||
-              b->pad != a.pad || b->relu != a.relu || (b->res != nullptr) != (a.res != nullptr) || (b->x2 != nullptr) != (a.x2 != nullptr) ||
-              b->H2 != a.H2 || b->W2 != a.W2 || b->ldx2 != a.ldx2 || b->Cin2 != a.Cin2 || b->stride2 != a.stride2 ||
-              (reinterpret_cast<uintptr_t>(b->x) & 15) || (b->x2 && (reinterpret_cast<uintptr_t>(b->x2) & 15))))
-        return (int)hipErrorInvalidValue;
-    if (a.x2 && (a.KH != 1 || a.KW != 1 || a.pad != 0 || a.Cin2 % 32 != 0 || a.ldx2 % 4 != 0 ||
-                 (reinterpret_cast<uintptr_t>(a.x2) & 15)))
-        return (int)hipErrorInvalidValue;
+    if (int rc = conv_igemm_check(a, b)) return rc;
     // buffer addressing is 32-bit: split the batch when the activation tensor reaches 2 GiB
     size_t img_bytes = (size_t)a.H * a.W * a.ldx * 4;
     if (a.x2 && (size_t)a.H2 * a.W2 * a.ldx2 * 4 > img_bytes) img_bytes = (size_t)a.H2 * a.W2 * a.ldx2 * 4;

@@ -86,10 +86,6 @@ __device__ __forceinline__ int wino_lane_now() {
     return l;
 }
 
-__device__ __forceinline__ int wino_div(int n, int d, unsigned mg, unsigned sh) {
-    return d == 1 ? n : (int)(__umulhi((unsigned)n, mg) >> sh);
-}
-
 // NF = frequencies per wave.
 //   NF == 16: workgroup = 32 tiles x 128 co, wave w = co block w, all frequencies (256 accumulator
 //             registers, one wave per SIMD), V triple buffered.
@@ -186,9 +182,9 @@ __global__ void __launch_bounds__(256, NF == 16 ? 1 : 2) conv_wino_f32_kernel(co
         const int t = tm * 32 + tl;
         const bool ok = t < p.Mt;
         const int tt = ok ? t : 0;
-        const int b = wino_div(tt, p.THW, p.mg_thw, p.sh_thw);
+        const int b = magic_div(tt, p.THW, p.mg_thw, p.sh_thw);
         const int rem = tt - b * p.THW;
-        const int ty = wino_div(rem, p.TW, p.mg_tw, p.sh_tw);
+        const int ty = magic_div(rem, p.TW, p.mg_tw, p.sh_tw);
         const int tx = rem - ty * p.TW;
         const int iy0 = 2 * ty - 1, ix0 = 2 * tx - 1;
         // per-thread base + wave-uniform (dy, dx) term: the uniform part stays in SGPRs
@@ -539,15 +535,6 @@ __global__ void __launch_bounds__(256, NF == 16 ? 1 : 2) conv_wino_f32_kernel(co
 #endif
 }
 
-static void wino_magic(unsigned d, unsigned* mg, unsigned* sh) {
-    if (d < 2) { *mg = 0; *sh = 0; return; }
-    unsigned s = 0;
-    while ((1ull << s) < d) ++s;
-    const unsigned L = 31 + s;
-    *mg = (unsigned)((1ull << L) / d + 1ull);
-    *sh = L - 32;
-}
-
 bool conv_wino_supported(const ConvArgs& a) {
     // Cout % 64 == 32 runs the 64-channel layout with half of its last co column idle: worth it from 96 channels
     // (<= 25 % idle MFMAs against the direct kernel's 2.25x flops), not for 32
@@ -655,8 +642,8 @@ static int wino_launch_one(const ConvArgs& a, const LaunchCtx& ctx, const ConvAr
     k.nbn = 0;
     k.nstage = a.Cin / 16;
     k.relu = a.relu;
-    wino_magic((unsigned)k.THW, &k.mg_thw, &k.sh_thw);
-    wino_magic((unsigned)k.TW, &k.mg_tw, &k.sh_tw);
+    magic_u32((unsigned)k.THW, &k.mg_thw, &k.sh_thw);
+    magic_u32((unsigned)k.TW, &k.mg_tw, &k.sh_tw);
     k.x_bytes = (unsigned)((size_t)a.B * a.H * a.W * a.ldx * 4);
     k.u_bytes = (unsigned)((size_t)16 * a.Cin * a.Cout * 4);
     k.out_bytes = (unsigned)((size_t)a.B * a.H * a.W * a.ldo * 4);

@@ -21,7 +21,7 @@
 //     runs the epilogue) - 16 KB instead of 256 KB for layer4's 3x3 layers at batch 1;
 //   * BatchNorm scale / shift, residual and ReLU in the epilogue with 16-byte row-contiguous stores; im2col padding and the
 //     M tail through the buffer range check; second A source (folded downsample branch) and grouped launches (blockIdx.z =
-//     network) as in the 64x64 kernel.
+//     network) through the helpers it shares with the 64x64 kernel (conv_igemm_tile.h).
 // Operand traffic per MFMA is 8 KB per wave-chunk against the 64x64 kernel's 6 (no sharing between waves), and an A fragment
 // load touches 32 cache lines: fine while a CU holds one or two workgroups (batch 1-3; layer4 up to batch 4), slower than the
 // 64x64 kernel beyond (measured per layer and batch: profiles/r05_c_wsplit_layers.txt; a variant that stages A as whole rows
@@ -43,70 +43,22 @@ __global__ void __launch_bounds__(256, 4) conv_wsplit_f32_kernel(const KArgs p) 
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform BY CONSTRUCTION: tell the compiler (scalar chunk offsets)
     const int l31 = lane & 31, hh = lane >> 5;
-    const bool grp = blockIdx.z != 0;
-    const float* const px = grp ? p.g1.x : p.x;
-    const float* const pw = grp ? p.g1.w : p.w;
-    const float* const pscale = grp ? p.g1.scale : p.scale;
-    const float* const pshift = grp ? p.g1.shift : p.shift;
-    const float* const pres = grp ? p.g1.res : p.res;
-    const float* const px2 = grp ? p.g1.x2 : p.x2;
-    float* const pout = grp ? p.g1.out : p.out;
-
-    // ---- tile: XCD-aware order as in the 64x64 kernel (tiles sharing an A row panel on one XCD) -------------------------
-    const int nblk = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nblk >> 3, r8 = nblk & 7;
-    const int Lt = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const NetOperands net = net_operands(p);
+    const int Lt = xcd_tile_order(blockIdx.x, gridDim.x);
     const int tile_m = Lt / p.nbn, tile_n = Lt - tile_m * p.nbn;   // nbn = Npad / 32
     const int m0 = tile_m * 32, n0 = tile_n * 32;
 
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(px), 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(pw), 0, p.w_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t x2rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DUAL ? px2 : px), 0, DUAL ? p.x2_bytes : p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(net.x), 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(net.w), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t x2rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(DUAL ? net.x2 : net.x), 0, DUAL ? p.x2_bytes : p.x_bytes, 0x00020000);
 
     // ---- this lane's A row: byte offset of (tap (0,0) pixel, channel 4 * hh) -----------------------------------------------
-    unsigned a_voff, a_voff2 = 0, a_mask = 0;
-    {
 #ifdef WS_ABLATE_A      // timing experiment (wrong results): every tile reads the SAME 32 activation rows
-        const int m = l31;
+    const RowAddr row = conv_row_addr(p, IS1X1, DUAL, l31, hh * 16);
 #else
-        const int m = m0 + l31;
+    const RowAddr row = conv_row_addr(p, IS1X1, DUAL, m0 + l31, hh * 16);
 #endif
-        const bool ok = m < p.M;
-        const int mm = ok ? m : 0;
-        if (DUAL) {
-            if (p.stride2 == 1) {
-                a_voff2 = ok ? (unsigned)(mm * p.ldx2 * 4 + hh * 16) : kOutOfRange;
-            } else {
-                const int b2 = p.OHW == 1 ? mm : (int)(__umulhi((unsigned)mm, p.mg_ohw) >> p.sh_ohw);
-                const int rem2 = mm - b2 * p.OHW;
-                const int oy2 = p.OW == 1 ? rem2 : (int)(__umulhi((unsigned)rem2, p.mg_ow) >> p.sh_ow);
-                const int ox2 = rem2 - oy2 * p.OW;
-                const int pix2 = (b2 * p.H2 + oy2 * p.stride2) * p.W2 + ox2 * p.stride2;
-                a_voff2 = ok ? (unsigned)(pix2 * p.ldx2 * 4 + hh * 16) : kOutOfRange;
-            }
-        }
-        if (IS1X1 && p.stride == 1) {
-            a_voff = ok ? (unsigned)(mm * p.ldx * 4 + hh * 16) : kOutOfRange;
-        } else {
-            const int b = p.OHW == 1 ? mm : (int)(__umulhi((unsigned)mm, p.mg_ohw) >> p.sh_ohw);
-            const int rem = mm - b * p.OHW;
-            const int oy = p.OW == 1 ? rem : (int)(__umulhi((unsigned)rem, p.mg_ow) >> p.sh_ow);
-            const int ox = rem - oy * p.OW;
-            const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-            const int pix0 = (b * p.H + iy0) * p.W + ix0;
-            const unsigned off = (unsigned)(pix0 * p.ldx * 4 + hh * 16);   // wraps for padded rows; only used on valid taps
-            if (IS1X1) {
-                a_voff = ok ? off : kOutOfRange;
-            } else {
-                a_voff = off;
-                unsigned colbits = 0, mk = 0;
-                for (int kx = 0; kx < p.KW; ++kx) colbits |= ((unsigned)(ix0 + kx) < (unsigned)p.W ? 1u : 0u) << kx;
-                for (int ky = 0; ky < p.KH; ++ky)
-                    if ((unsigned)(iy0 + ky) < (unsigned)p.H) mk |= colbits << (ky * p.KW);
-                a_mask = ok ? mk : 0u;
-            }
-        }
-    }
+    const unsigned a_voff = row.voff, a_voff2 = row.voff2, a_mask = row.mask;
 #ifdef WS_ABLATE_B      // timing experiment (wrong results): every tile reads the SAME weight columns -> B traffic becomes L1 / L2 hits
     const unsigned b_voff = (unsigned)((hh * p.Npad + l31) * 16);
 #else
@@ -267,21 +219,12 @@ __global__ void __launch_bounds__(256, 4) conv_wsplit_f32_kernel(const KArgs p) 
 
     if (S > 1) {
         // group slab -> workspace (16 bytes per thread, consecutive threads consecutive: coalesced) with write-through stores,
-        // drain, ticket; the last arriver folds the S groups in order (conv_igemm.hip: same hand-off)
+        // ticket (sk_last_arriver: the hand-off of the 64x64 kernel); the last arriver folds the S groups in order
         const size_t tile = (size_t)blockIdx.z * gridDim.x + blockIdx.x;
         float* const tile_ws = p.sk_ws + tile * S * (size_t)1024;
         const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(tile_ws, 0, (unsigned)S * 4096u, 0x00020000);
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, result), srs, (unsigned)(tid * 16), (unsigned)blockIdx.y * 4096u, /*sc1*/ 16);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            const unsigned ticket = __hip_atomic_fetch_add(p.sk_cnt + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int last = ticket == (unsigned)S - 1;
-            if (last) __hip_atomic_store(p.sk_cnt + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            flag = last;
-        }
-        __syncthreads();
-        if (!flag) return;
+        if (!sk_last_arriver(p.sk_cnt + tile, (unsigned)S, &flag)) return;
 #pragma unroll
         for (int e = 0; e < 4; ++e) result[e] = 0.f;
         int z = 0;
@@ -305,31 +248,15 @@ __global__ void __launch_bounds__(256, 4) conv_wsplit_f32_kernel(const KArgs p) 
     // ---- epilogue: BN scale / shift, residual, ReLU; one row x four columns per thread ------------------------------------------
     const int m = m0 + frow, n = n0 + fcol;
     if (m >= p.M || n >= p.Cout) return;
-    const f32x4 sc = *reinterpret_cast<const f32x4*>(pscale + n);
-    const f32x4 sh = *reinterpret_cast<const f32x4*>(pshift + n);
+    const f32x4 sc = *reinterpret_cast<const f32x4*>(net.scale + n);
+    const f32x4 sh = *reinterpret_cast<const f32x4*>(net.shift + n);
     const size_t o = (size_t)m * p.ldo + n;
-    f32x4 o4;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o4[e] = fmaf(result[e], sc[e], sh[e]);
     if (n + 3 < p.Cout && p.vec_ok) {
-        if (pres) {
-            const f32x4 rr = *reinterpret_cast<const f32x4*>(pres + o);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o4[e] += rr[e];
-        }
-        if (p.relu) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o4[e] = fmaxf(o4[e], 0.f);
-        }
-        *reinterpret_cast<f32x4*>(pout + o) = o4;
+        f32x4 rr = {0.f, 0.f, 0.f, 0.f};
+        if (net.res) rr = *reinterpret_cast<const f32x4*>(net.res + o);
+        *reinterpret_cast<f32x4*>(net.out + o) = epilogue_quad(result, sc, sh, net.res != nullptr, rr, p.relu);
     } else {
-        for (int e = 0; e < 4; ++e) {
-            if (n + e >= p.Cout) break;
-            float t = o4[e];
-            if (pres) t += pres[o + e];
-            if (p.relu) t = fmaxf(t, 0.f);
-            pout[o + e] = t;
-        }
+        epilogue_tail(reinterpret_cast<const float*>(&result), sc, sh, net.res, p.relu, net.out, o, p.Cout - n);
     }
 }
 
@@ -339,7 +266,7 @@ size_t conv_wsplit_ws_floats(const ConvArgs& a, int S, int groups) { return S > 
 
 // the canonical tree must have 2..4 leaves per group (one per wave); unit = leaves (no slabs) or G (one group per workgroup)
 bool conv_wsplit_supported(const ConvArgs& a, const SkPlan& pl) {
-    const int nch = a.KH * a.KW * (a.Cin / 32) + (a.x2 ? a.Cin2 / 32 : 0);
+    const int nch = conv_k_chunks(a);
     return pl.leaves >= 2 && pl.G >= 2 && pl.G <= 4 && pl.leaves % pl.G == 0 && (pl.unit == pl.leaves || pl.unit == pl.G) && !a.force_variant &&
            a.KH * a.KW <= 32 &&                            // (the padding mask of a pixel holds one bit per filter tap)
            nch % pl.leaves == 0 && nch / pl.leaves >= 2;   // (the K loop keeps two chunks in flight)
@@ -356,17 +283,14 @@ int launch_conv_wsplit(const ConvArgs& a, const SkPlan& pl, const SkWs& sk, cons
     conv_igemm_make_sk_kargs(a, pl, b, k);
     k.nbn = (a.Cout + 31) / 32;   // 32-wide tiles skip the all-padding half of a 64-padded panel
     k.sk_ws = sk.ws; k.sk_cnt = sk.cnt;
-    const int M = k.M;
-    const int grid = ((M + 31) / 32) * k.nbn;
-    const double Kd = (double)a.KH * a.KW * a.Cin + (a.x2 ? a.Cin2 : 0);
-    const double flops = 2.0 * (double)M * a.Cout * Kd;
-    const double bytes = 4.0 * ((double)a.B * a.H * a.W * a.Cin + (a.x2 ? (double)M * a.Cin2 : 0.0) + (double)M * a.Cout * (a.res ? 2.0 : 1.0) + Kd * a.Cout);
-    const bool is1x1 = (a.KH == 1 && a.KW == 1 && a.pad == 0);
+    const int grid = ((k.M + 31) / 32) * k.nbn;
+    double flops, bytes;
+    conv_flops_bytes(a, &flops, &bytes);
     const char* name = a.x2 ? "conv_wsplit_f32<32x32,4 leaves,2src>" : "conv_wsplit_f32<32x32,4 leaves>";
     ProfScope ps(ctx, name, flops * groups, bytes * groups);
     const dim3 g(grid, S, groups), blk(256);
     if (a.x2) hipLaunchKernelGGL((conv_wsplit_f32_kernel<true, true>), g, blk, 0, ctx.stream, k);
-    else if (is1x1) hipLaunchKernelGGL((conv_wsplit_f32_kernel<true, false>), g, blk, 0, ctx.stream, k);
+    else if (conv_is_1x1(a)) hipLaunchKernelGGL((conv_wsplit_f32_kernel<true, false>), g, blk, 0, ctx.stream, k);
     else hipLaunchKernelGGL((conv_wsplit_f32_kernel<false, false>), g, blk, 0, ctx.stream, k);
     return (int)hipGetLastError();
 }

@@ -95,6 +95,30 @@ struct ConvArgs {
     int force_variant = 0;   // conv_igemm tile (1: 128x128/4 waves, 2: 128x64/4, 3: 64x64/4, 4: 128x128/8 waves)
     int wino_variant = 0;    // conv_wino frequencies per wave (16 / 8)
 };
+// 32-channel K chunks of the layer: one per (filter tap, 32 channels of x), then those of the second source
+inline int conv_k_chunks(const ConvArgs& a) { return a.KH * a.KW * (a.Cin / 32) + (a.x2 ? a.Cin2 / 32 : 0); }
+// no im2col: every output pixel reads one input pixel (any stride)
+inline bool conv_is_1x1(const ConvArgs& a) { return a.KH == 1 && a.KW == 1 && a.pad == 0; }
+// what the launch profiler records for the layer: algorithmic flops and the bytes of x (+ x2), w, out (+ res) moved once
+inline void conv_flops_bytes(const ConvArgs& a, double* flops, double* bytes) {
+    const double M = (double)a.B * a.OH * a.OW;
+    const double Kd = (double)a.KH * a.KW * a.Cin + (a.x2 ? a.Cin2 : 0);
+    *flops = 2.0 * M * a.Cout * Kd;
+    *bytes = 4.0 * ((double)a.B * a.H * a.W * a.Cin + (a.x2 ? M * a.Cin2 : 0.0) + M * a.Cout * (a.res ? 2.0 : 1.0) + Kd * a.Cout);
+}
+// floor(n / d) == umulhi(n, mg) >> sh for every n < 2^31 and 2 <= d < 2^31:
+// L = 31 + ceil(log2 d), mg = floor(2^L / d) + 1 (< 2^32), sh = L - 32.  d == 1 is magic_div's own case.
+inline void magic_u32(unsigned d, unsigned* mg, unsigned* sh) {
+    if (d < 2) { *mg = 0; *sh = 0; return; }
+    unsigned s = 0;
+    while ((1ull << s) < d) ++s;
+    const unsigned L = 31 + s;
+    *mg = (unsigned)((1ull << L) / d + 1ull);
+    *sh = L - 32;
+}
+__device__ __forceinline__ int magic_div(int n, int d, unsigned mg, unsigned sh) {
+    return d == 1 ? n : (int)(__umulhi((unsigned)n, mg) >> sh);
+}
 // Cin % 32 == 0, Npad % 64 == 0.  Returns hipError as int.
 // b != nullptr: the same layer shape of a SECOND network (own tensors) in the same launch (gridDim.z = 2)
 int launch_conv_igemm(const ConvArgs& a, const LaunchCtx& ctx, const ConvArgs* b = nullptr);
