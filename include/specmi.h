@@ -242,6 +242,28 @@ int specmi_camcalib_decode(specmi_handle* h, const float* logits_vfov, const flo
 int specmi_camcalib_bins(specmi_handle* h, const float* logits, int rows, int nbins, int32_t* argmax_idx,
                          float* soft_idx, void* stream);
 
+/* CamCalib's test step after the network (camcalib/trainer.py:84-116): CameraRegressorLoss (camcalib/loss.py:24-125: the four
+ * loss types, three weights applied as :109-116 - 'softargmax_biased_l2' uses the biased criterion for vfov only),
+ * convert_preds_to_angles' soft-argmax branch and |pred - gt|, on three (B, nbins) device logit tensors.
+ *   target_*  : (B,) int32 bin index (np.digitize, pano_dataset.py:135-138) for SPECMI_LOSS_CE / _KL, (B,) fp32 soft index in
+ *               [-1, 1] (pano_dataset.py:139-142) for the soft-argmax losses;  gt_* : (B,) fp32 angles in radians.
+ * Per image and head, each a (3, B) array in the order vfov, pitch, roll (all five required):
+ *   loss_term (unweighted; ce = kl = -log_softmax(x)[t]: against a one-hot target F.kl_div keeps exactly that term),
+ *   argmax_idx (first maximum; the 'ce' / 'kl' decode gathers the host float64 bin-centre tables with it, as
+ *   specmi_camcalib_bins' callers do), soft_idx in [-1, 1], angle (radians, soft-argmax branch), abs_err = |angle - gt|.
+ * means (7 floats, may be NULL): [loss, vfov_loss, pitch_loss, roll_loss] with the weights applied, then
+ *   [vfov_acc, pitch_acc, roll_acc] = mean abs_err in degrees; summed in an order that depends on B alone (bit-reproducible).
+ * A per-image value never depends on the other rows of the batch. */
+#define SPECMI_LOSS_CE 0
+#define SPECMI_LOSS_KL 1
+#define SPECMI_LOSS_SOFTARGMAX_L2 2
+#define SPECMI_LOSS_SOFTARGMAX_BIASED_L2 3
+int specmi_camcalib_eval(specmi_handle* h, const float* logits_vfov, const float* logits_pitch, const float* logits_roll,
+                         int B, int nbins, int loss_type, const void* target_vfov, const void* target_pitch,
+                         const void* target_roll, const float* gt_vfov, const float* gt_pitch, const float* gt_roll,
+                         float weight_vfov, float weight_pitch, float weight_roll, float* loss_term, int32_t* argmax_idx,
+                         float* soft_idx, float* angle, float* abs_err, float* means, void* stream);
+
 /* read_cam_params (spec/utils/cam_params.py:24-50) for angles that were decoded earlier, e.g.
  * read back from the CamCalib result pickle: (pitch, roll, f_pix, img_w, img_h) (B,) device ->
  * cam_rotmat (B,3,3), cam_intrinsics (B,3,3) (K[2,2] = 0).  Either output may be NULL. */
@@ -370,6 +392,16 @@ int specmi_crop_resize_normalize(specmi_handle* h, const uint8_t* frame_rgb_hwc,
  * (shorter side 600, longer int(600*long/short)).  Optional raw_hwc: the resized uint8 image (OH,OW,3). */
 int specmi_resize_normalize(specmi_handle* h, const uint8_t* frame_rgb_hwc, int H, int W, int OH, int OW,
                             float* out_chw, uint8_t* raw_hwc, void* stream);
+
+/* A CamCalib validation batch (camcalib/pano_dataset.py:184-220 Resize(min_size, max_size) per frame, :223-306 collator /
+ * to_image_list): n uint8 RGB HWC frames of DIFFERENT sizes in one device slab -> out (n, 3, Hmax, Wmax) fp32 NCHW.  Frame f
+ * (at byte offsets[f], geom[4f .. 4f+3] = H, W, OH, OW; offsets and geom are HOST arrays) is resampled to (OH, OW) with the
+ * arithmetic of specmi_resize_normalize, bit for bit, into out[f, :, :OH, :OW]; every other element is exactly 0.0f (zeros in
+ * normalised space).  A frame with (OH, OW) == (H, W) is converted without resampling.  The caller picks the target sizes
+ * (spec_amd.camcalib_eval.resize_size) and Hmax >= max OH, Wmax >= max OW.  Two launches whatever n is; every output element
+ * is written once (no memset).  Refused: n > 65535, a slab of 4 GiB or more, an output plane of 2^31 elements or more. */
+int specmi_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames_rgb_hwc, size_t slab_bytes, const int64_t* offsets,
+                                   const int32_t* geom, int n, int Hmax, int Wmax, float* out_nchw, void* stream);
 
 /* ---- evaluation metrics on the path's outputs ---------------------------------- */
 

@@ -8,6 +8,7 @@ launch stream around each kernel), averaged over ``--iters`` launches after a wa
 section 3 states).  All of them are byte / gather work: none is reshaped into a GEMM.
 
     python scripts/bench_aux.py [--iters 20] [--out gpurun_out/aux_bench.json]
+    python scripts/bench_aux.py --only camcalib_eval      # the two kernels of CamCalib's test step -> profiles/camcalib_eval_aux.json
 """
 import argparse
 import json
@@ -39,8 +40,78 @@ def timed(eng, fn, iters):
     return {k: (v[0] / v[3], v[1] / v[3], v[2] / v[3], v[3] // iters) for k, v in rows.items() if v[3]}
 
 
+def camcalib_eval_section(eng, a, add, g):
+    """The two kernels of CamCalib's test step (spec_amd/camcalib_eval.py).  The ragged resize is also compared, wall clock and
+    alternated in this process, with the composition that existed before it: one ``specmi_resize_normalize`` per frame into a
+    scratch tensor + one zero-fill of the batch + one slice copy per frame."""
+    import time
+    from spec_amd import _lib
+    from spec_amd.camcalib_eval import resize_size
+    from spec_amd.engine import _ptr
+    dev = eng.device
+    n = 64
+    shapes = [(1920, 1080), (1080, 1920), (800, 600), (1000, 1000), (1280, 720), (640, 480), (1600, 1200), (600, 900)]   # (w, h)
+    geom, offs, off = [], [], 0
+    for i in range(n):
+        w, h = shapes[i % len(shapes)]
+        oh, ow = resize_size(w, h, 600, 1000)
+        geom.append((h, w, oh, ow)); offs.append(off); off += h * w * 3
+    slab = torch.randint(0, 256, (off,), generator=g, dtype=torch.uint8).to(dev)
+    Hmax, Wmax = max(q[2] for q in geom), max(q[3] for q in geom)
+    out = torch.empty(n, 3, Hmax, Wmax, device=dev)
+    work = f'{n} uint8 frames of 8 sizes (480p .. 1080p, {off / 1e6:.0f} MB) -> Resize(600, 1000) -> ({n},3,{Hmax},{Wmax}) fp32 zero padded'
+    ragged = lambda: eng.resize_normalize_ragged(slab, offs, geom, out=out)
+    add('camcalib_eval.pad_batch (specmi_resize_normalize_ragged)', work, timed(eng, ragged, a.iters), ('frames_per_s', n))
+    frames = [slab[o:o + h * w * 3] for o, (h, w, _, _) in zip(offs, geom)]
+    scratch = [torch.empty(3, oh, ow, device=dev) for _, _, oh, ow in geom]
+    out2 = torch.empty_like(out)
+
+    def composed():
+        out2.zero_()
+        for f, (h, w, oh, ow) in enumerate(geom):
+            _lib.check(eng.h, eng.lib.specmi_resize_normalize(eng.h, _ptr(frames[f]), h, w, oh, ow, _ptr(scratch[f]), None, eng._stream()))
+            out2[f, :, :oh, :ow].copy_(scratch[f])
+    ragged(); composed()
+    torch.cuda.synchronize()
+    same = bool(torch.equal(out, out2))
+    wall = {'ragged': [], 'composed': []}
+    for _ in range(max(5, a.iters // 2)):                       # alternated: both see the same clocks and the same neighbours
+        for name, fn in (('ragged', ragged), ('composed', composed)):
+            torch.cuda.synchronize(); t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+            wall[name].append((time.perf_counter() - t0) * 1e3)
+    med = {k: float(np.median(v)) for k, v in wall.items()}
+    out_bytes = out.numel() * 4 + off
+    cmp_ = {'workload': work, 'bit_identical': same, 'wall_ms_median': {k: round(v, 3) for k, v in med.items()},
+            'ratio_composed_over_ragged': round(med['composed'] / med['ragged'], 2),
+            'ragged_wall_GBps': round(out_bytes / (med['ragged'] * 1e-3) / 1e9, 1),
+            'ragged_frac_of_hbm_peak_wall': round(out_bytes / (med['ragged'] * 1e-3) / HBM_PEAK, 4),
+            'note': 'wall clock of one call, host work included: the ragged call builds 64 Pillow coefficient tables on the host '
+                    '(identical tables are not uploaded again); the composition rebuilds one table and synchronises the device per frame'}
+    print(f"pad_batch: ragged {med['ragged']:.3f} ms  per-frame composition {med['composed']:.3f} ms  ratio {cmp_['ratio_composed_over_ragged']}  "
+          f"bit-identical {same}")
+    B = a.batch
+    lg = [torch.randn(B, 256, generator=g).to(dev) * 3 for _ in range(3)]
+    tgt = [torch.randint(0, 256, (B,), generator=g) for _ in range(3)]
+    gt = [torch.rand(B, generator=g) for _ in range(3)]
+    add('Engine.camcalib_eval (loss + decode + error + batch means)', f'3 x {B} rows x 256 bins, ce',
+        timed(eng, lambda: eng.camcalib_eval(*lg, tgt, gt, 'ce'), a.iters), ('rows_per_s', 3 * B))
+    return cmp_
+
+
+def finish(a, table, extra=None):
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(dict({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'batch': a.batch, 'timing': 'per-launch HIP events on the launch stream '
+                        '(library profiler)', 'rows': table}, **(extra or {})), f, indent=1)
+    w = max(len(r['call']) for r in table)
+    for r in table:
+        print(f"{r['call']:<{w}}  {r['kernel']:<22} {r['ms_per_launch'] * 1e3:9.1f} us  {r['algorithmic_MB']:9.2f} MB  "
+              f"{r['achieved_GBps']:8.1f} GB/s  frac {r['frac_of_hbm_peak']:.3f}   {r['workload']}")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--only', choices=['camcalib_eval'], default=None, help='run one section only')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--out', default='gpurun_out/aux_bench.json')
@@ -65,6 +136,11 @@ def main():
             if per_unit:
                 row[per_unit[0]] = round(per_unit[1] / (ms * 1e-3), 1)
             table.append(row)
+
+    if a.only == 'camcalib_eval':
+        from spec_amd import _lib
+        cmp_ = camcalib_eval_section(eng, a, add, g)
+        return finish(a, table, {'pad_batch_vs_per_frame_composition': cmp_, 'source_hash': _lib.source_hash()})
 
     # ---- 8f-1: crops from one 1080p frame ---------------------------------------------------------------------------
     frame = torch.randint(0, 256, (1080, 1920, 3), generator=g, dtype=torch.uint8).to(dev)
@@ -119,14 +195,8 @@ def main():
     add('cam_utils bins (arg-max + soft-argmax)', f'{3 * B} rows x 256 bins',
         timed(eng, lambda: eng.camcalib_bins(logits, argmax=True, soft=True), a.iters), ('rows_per_s', 3 * B))
 
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, 'w') as f:
-        json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'batch': B, 'timing': 'per-launch HIP events on the launch stream '
-                   '(library profiler)', 'rows': table}, f, indent=1)
-    w = max(len(r['call']) for r in table)
-    for r in table:
-        print(f"{r['call']:<{w}}  {r['kernel']:<22} {r['ms_per_launch'] * 1e3:9.1f} us  {r['algorithmic_MB']:9.2f} MB  "
-              f"{r['achieved_GBps']:8.1f} GB/s  frac {r['frac_of_hbm_peak']:.3f}   {r['workload']}")
+    cmp_ = camcalib_eval_section(eng, a, add, g)
+    finish(a, table, {'pad_batch_vs_per_frame_composition': cmp_})
 
 
 if __name__ == '__main__':

@@ -32,6 +32,7 @@ def source_hash() -> str:
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_MISSING = 0, 1, 2, 3, 4
 PRECISION_FP32, PRECISION_FP16 = 0, 1       # SPECMI_PRECISION_* (include/specmi.h)
 MODEL_CAMCALIB, MODEL_HMR, MODEL_SMPL = 0, 1, 2
+LOSS_TYPES = {'ce': 0, 'kl': 1, 'softargmax_l2': 2, 'softargmax_biased_l2': 3}     # SPECMI_LOSS_* (include/specmi.h)
 
 c_float_p = C.POINTER(C.c_float)
 c_int32_p = C.POINTER(C.c_int32)
@@ -122,6 +123,11 @@ PROTOTYPES = {
                                                C.c_void_p]),
     'specmi_resize_normalize': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    'specmi_resize_normalize_ragged': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, c_int32_p, C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p]),
+    'specmi_camcalib_eval': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'specmi_eval_mesh': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'specmi_eval_joints': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,

@@ -782,6 +782,8 @@ int specmi_destroy(specmi_handle* h) {
     free_pool(h->sk_retired);
     free_pool(h->ws_retired);
     if (h->resize_tab) (void)hipFree(h->resize_tab);
+    if (h->ragged_tab) (void)hipFree(h->ragged_tab);
+    if (h->ragged_tmp) (void)hipFree(h->ragged_tmp);
     hrnet_free(h->hrnet);
     delete h;
     return SPECMI_OK;
@@ -1043,6 +1045,30 @@ int specmi_camcalib_bins(specmi_handle* h, const float* logits, int rows, int nb
     if (!logits || rows <= 0 || nbins < 2 || (!argmax_idx && !soft_idx)) return fail(h, SPECMI_ERR_ARG, "bad argument");
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, "camcalib.bins"};
     LAUNCHCHK(h, launch_bins_reduce(logits, rows, nbins, argmax_idx, soft_idx, ctx), "bins_reduce");
+    return SPECMI_OK;
+}
+
+int specmi_camcalib_eval(specmi_handle* h, const float* lv, const float* lp, const float* lr, int B, int nbins, int loss_type,
+                         const void* target_vfov, const void* target_pitch, const void* target_roll, const float* gt_vfov,
+                         const float* gt_pitch, const float* gt_roll, float w_vfov, float w_pitch, float w_roll, float* loss_term,
+                         int32_t* argmax_idx, float* soft_idx, float* angle, float* abs_err, float* means, void* stream) {
+    ENTER(h);
+    if (!lv || !lp || !lr || B <= 0 || nbins < 2) return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if (loss_type < SPECMI_LOSS_CE || loss_type > SPECMI_LOSS_SOFTARGMAX_BIASED_L2)
+        return fail(h, SPECMI_ERR_ARG, "loss_type %d is not defined (camcalib/loss.py:75-85: ce, kl, softargmax_l2, softargmax_biased_l2)", loss_type);
+    if (!target_vfov || !target_pitch || !target_roll || !gt_vfov || !gt_pitch || !gt_roll)
+        return fail(h, SPECMI_ERR_ARG, "targets and ground-truth angles of all three heads are needed");
+    if (!loss_term || !argmax_idx || !soft_idx || !angle || !abs_err) return fail(h, SPECMI_ERR_ARG, "the five per-image outputs are needed");
+    if ((double)B * nbins >= 2147483648.0) return fail(h, SPECMI_ERR_ARG, "B * nbins does not fit 31 bits");
+    CamEvalArgs a;
+    a.logits[0] = lv; a.logits[1] = lp; a.logits[2] = lr;
+    a.target[0] = target_vfov; a.target[1] = target_pitch; a.target[2] = target_roll;
+    a.gt[0] = gt_vfov; a.gt[1] = gt_pitch; a.gt[2] = gt_roll;
+    a.B = B; a.nbins = nbins; a.loss_type = loss_type;
+    a.weight[0] = w_vfov; a.weight[1] = w_pitch; a.weight[2] = w_roll;
+    a.loss_term = loss_term; a.argmax = argmax_idx; a.soft = soft_idx; a.angle = angle; a.err = abs_err; a.means = means;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "camcalib.eval"};
+    LAUNCHCHK(h, launch_camcalib_eval(a, ctx), "camcalib_eval");
     return SPECMI_OK;
 }
 
@@ -1348,6 +1374,74 @@ int specmi_resize_normalize(specmi_handle* h, const uint8_t* frame, int H, int W
     LaunchCtx ctx{s, &h->prof, "resize_normalize"};
     LAUNCHCHK(h, launch_resize_normalize(frame, H, W, OH, OW, h->resize_tab, h->resize_tab + o_hk, ksh, h->resize_tab + o_vb,
                                          h->resize_tab + o_vk, ksv, out, raw, ctx), "resize_normalize");
+    return SPECMI_OK;
+}
+
+// a device buffer of the ragged resize that must hold `need` bytes: kept, or replaced by one at least 1.5x the old size while the
+// outgrown one joins ws_retired (the rule of ensure_ws: work enqueued earlier may still name it)
+static int grow_ragged(specmi_handle* h, void** buf, size_t* have, size_t need, const char* what) {
+    if (need <= *have) return SPECMI_OK;
+    if (int rc0 = sync_for_growth(h, what)) return rc0;
+    if (*have && need < *have + *have / 2) need = *have + *have / 2;
+    if (*buf) h->ws_retired.push_back(*buf);
+    *buf = nullptr; *have = 0;
+    HIPCHK(h, hipMalloc(buf, need));
+    *have = need;
+    return SPECMI_OK;
+}
+
+int specmi_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets,
+                                   const int32_t* geom, int n, int Hmax, int Wmax, float* out, void* stream) {
+    ENTER(h);
+    if (!frames || !offsets || !geom || !out || n <= 0 || Hmax <= 0 || Wmax <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if (n > 65535) return fail(h, SPECMI_ERR_ARG, "at most 65535 frames per call (grid dimension), got %d", n);
+    if (slab_bytes >= 4294967296.0 || (double)Hmax * Wmax >= 2147483648.0)
+        return fail(h, SPECMI_ERR_ARG, "a frame slab of %zu bytes / a %d x %d output plane is beyond the kernels' 32-bit offsets", slab_bytes, Hmax, Wmax);
+    hipStream_t s = (hipStream_t)stream;
+    // [n records | per resampled frame: hb (2 OW) | hk (OW ksh) | vb (2 OH) | vk (OH ksv)]
+    std::vector<int> tab((size_t)n * kRaggedRec, 0), hb, hk, vb, vk;
+    size_t tmp_bytes = 0;
+    int max_hpass = 0;
+    for (int f = 0; f < n; ++f) {
+        const int H = geom[4 * f], W = geom[4 * f + 1], OH = geom[4 * f + 2], OW = geom[4 * f + 3];
+        if (H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || OH > Hmax || OW > Wmax)
+            return fail(h, SPECMI_ERR_ARG, "frame %d: size %d x %d -> %d x %d does not fit the %d x %d batch", f, H, W, OH, OW, Hmax, Wmax);
+        if (offsets[f] < 0 || (double)offsets[f] + (double)H * W * 3 > (double)slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "frame %d: %d x %d x 3 bytes at offset %lld leave the slab of %zu bytes", f, H, W, (long long)offsets[f], slab_bytes);
+        RaggedFrame fr{};
+        fr.src_off = (unsigned)offsets[f]; fr.H = H; fr.W = W; fr.OH = OH; fr.OW = OW;
+        fr.resample = (OH != H || OW != W) ? 1 : 0;
+        if (fr.resample) {
+            if ((double)H * OW >= 2147483648.0 / 3 || (double)tmp_bytes + (double)H * OW * 3 >= 4294967296.0)
+                return fail(h, SPECMI_ERR_ARG, "frame %d: the uint8 rows between the passes are beyond 32-bit offsets", f);
+            fr.ksh = pillow_coeffs(W, OW, hb, hk);
+            fr.ksv = pillow_coeffs(H, OH, vb, vk);
+            if ((double)tab.size() + hb.size() + hk.size() + vb.size() + vk.size() >= 2147483648.0)
+                return fail(h, SPECMI_ERR_ARG, "the coefficient tables are beyond 31-bit offsets");
+            fr.hb = (int)tab.size(); tab.insert(tab.end(), hb.begin(), hb.end());
+            fr.hk = (int)tab.size(); tab.insert(tab.end(), hk.begin(), hk.end());
+            fr.vb = (int)tab.size(); tab.insert(tab.end(), vb.begin(), vb.end());
+            fr.vk = (int)tab.size(); tab.insert(tab.end(), vk.begin(), vk.end());
+            fr.tmp_off = (unsigned)tmp_bytes;
+            tmp_bytes += (size_t)H * OW * 3;
+            if (H * OW > max_hpass) max_hpass = H * OW;
+        }
+        std::memcpy(tab.data() + (size_t)f * kRaggedRec, &fr, sizeof(fr));
+    }
+    int rc;
+    if ((rc = grow_ragged(h, (void**)&h->ragged_tmp, &h->ragged_tmp_bytes, tmp_bytes, "the ragged-resize row workspace"))) return rc;
+    const bool regrown = tab.size() * 4 > h->ragged_tab_bytes;
+    if ((rc = grow_ragged(h, (void**)&h->ragged_tab, &h->ragged_tab_bytes, tab.size() * 4, "the ragged-resize tables"))) return rc;
+    if (regrown || tab != h->ragged_host) {
+        // a batch enqueued earlier on ANY stream may still read the old tables (specmi_resize_normalize has the same rule)
+        if (!regrown && (rc = sync_for_growth(h, "the ragged-resize tables"))) return rc;
+        h->ragged_host.swap(tab);
+        HIPCHK(h, hipMemcpyAsync(h->ragged_tab, h->ragged_host.data(), h->ragged_host.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    LaunchCtx ctx{s, &h->prof, "preprocess.resize_ragged"};
+    LAUNCHCHK(h, launch_resize_normalize_ragged(frames, h->ragged_tab, h->ragged_tmp, n, max_hpass, Hmax, Wmax, (double)slab_bytes, (double)tmp_bytes,
+                                                out, ctx),
+              "resize_normalize_ragged");
     return SPECMI_OK;
 }
 

@@ -101,6 +101,13 @@ struct specmi_handle {
     size_t resize_tab_ints = 0;
     std::vector<int> resize_host;       // host image of the same (kept alive for the async copy)
     int resize_geom[4] = {0, 0, 0, 0};  // H, W, OH, OW the tables were built for
+    // ragged batch resize (specmi_resize_normalize_ragged): per-frame records + coefficient tables, and the uint8 rows between
+    // the two passes.  Both grow geometrically; an outgrown buffer joins ws_retired
+    int* ragged_tab = nullptr;
+    size_t ragged_tab_bytes = 0;
+    unsigned char* ragged_tmp = nullptr;
+    size_t ragged_tmp_bytes = 0;
+    std::vector<int> ragged_host;       // host image of ragged_tab as last uploaded
     SkWs sk;                            // split-K partial tiles + arrival counters (ensure_sk; never allocated under graph capture:
                                         // the warm-up call of a shape sizes it)
     std::vector<void*> sk_retired;      // outgrown split-K buffers, kept until destroy (captured graphs may still name them)

@@ -233,6 +233,14 @@ int launch_fc_gemv(const FcGemv* heads, int nheads, int N, int Kp, int ldx, int 
     return (int)hipGetLastError();
 }
 
+// soft_idx_to_angle of head 0 / 1 / 2 = vfov / pitch / roll (camcalib/cam_utils.py:94-107,128-133): (max - min) is a python double
+// rounded to fp32 when it meets the tensor
+__device__ __forceinline__ float soft_idx_to_angle(float s, int head) {
+    const float span = head == 0 ? (float)(2.1 - 0.2617) : (float)(0.6 - (-0.6));
+    const float lo = head == 0 ? (float)0.2617 : (float)-0.6;
+    return span * ((s + 1.0f) / 2.0f) + lo;
+}
+
 // soft-argmax decode of image b: waves 0..2 = vfov / pitch / roll (a fourth wave idles), `ang` = 3 floats of LDS
 struct DecodeArgs {
     const float *lv, *lp, *lr; int nbins; const float *img_h, *img_w;
@@ -258,10 +266,7 @@ __device__ __forceinline__ void camcalib_decode_image(const DecodeArgs& a, int b
         sp = wave_sum(sp);
         if (lane == 0) {
             const float s = sp / (float)(a.nbins - 1) * 2.0f - 1.0f;                  // softargmax1d normalisation
-            // soft_idx_to_angle: (max - min) is a python double rounded to fp32 when it meets the tensor
-            const float span = wave == 0 ? (float)(2.1 - 0.2617) : (float)(0.6 - (-0.6));
-            const float lo = wave == 0 ? (float)0.2617 : (float)-0.6;
-            ang[wave] = span * ((s + 1.0f) / 2.0f) + lo;
+            ang[wave] = soft_idx_to_angle(s, wave);
         }
     }
     __syncthreads();
@@ -296,12 +301,9 @@ int launch_camcalib_decode(const float* lv, const float* lp, const float* lr, in
 //   idx[row]  = np.argmax(row)            (bins2vfov / bins2pitch / bins2roll / bins2horizon, cam_utils.py:66-91):
 //               FIRST index of the maximum, a NaN counts as the maximum (NumPy semantics) - index work, bit-exact;
 //   soft[row] = softargmax1d(row, normalize_keypoints=True) in [-1, 1] (get_softargmax, cam_utils.py:110-118).
-__global__ void __launch_bounds__(256) bins_reduce_kernel(const float* __restrict__ x, int rows, int nbins,
-                                                           int* __restrict__ idx, float* __restrict__ soft) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= rows) return;
-    const float* r = x + (size_t)row * nbins;
-    float mx = -INFINITY;
+// np.argmax of a row by one wave -> index (every lane); mx = the largest non-NaN value (-inf for an all-NaN row)
+__device__ __forceinline__ int wave_argmax_row(const float* __restrict__ r, int nbins, int lane, float& mx) {
+    mx = -INFINITY;
     int mi = 0x7fffffff, nan_i = 0x7fffffff;
     for (int i = lane; i < nbins; i += 64) {
         const float v = r[i];
@@ -315,20 +317,101 @@ __global__ void __launch_bounds__(256) bins_reduce_kernel(const float* __restric
         nan_i = min(nan_i, __shfl_xor(nan_i, o, 64));
         if (omx > mx || (omx == mx && omi < mi)) { mx = omx; mi = omi; }
     }
-    if (idx && lane == 0) idx[row] = nan_i != 0x7fffffff ? nan_i : (mi == 0x7fffffff ? 0 : mi);
+    return nan_i != 0x7fffffff ? nan_i : (mi == 0x7fffffff ? 0 : mi);
+}
+// softargmax1d(normalize_keypoints=True) of a row by one wave, given its maximum -> [-1, 1] (every lane); se = sum exp(x - mx)
+__device__ __forceinline__ float wave_softargmax_row(const float* __restrict__ r, int nbins, int lane, float mx, float& se) {
+    float sp = 0.f;
+    se = 0.f;
+    for (int i = lane; i < nbins; i += 64) se += expf(r[i] - mx);
+    se = wave_sum(se);
+    for (int i = lane; i < nbins; i += 64) sp += expf(r[i] - mx) / se * (float)i;
+    sp = wave_sum(sp);
+    return sp / (float)(nbins - 1) * 2.0f - 1.0f;
+}
+
+__global__ void __launch_bounds__(256) bins_reduce_kernel(const float* __restrict__ x, int rows, int nbins,
+                                                           int* __restrict__ idx, float* __restrict__ soft) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    const float* r = x + (size_t)row * nbins;
+    float mx, se;
+    const int mi = wave_argmax_row(r, nbins, lane, mx);
+    if (idx && lane == 0) idx[row] = mi;
     if (soft) {
-        float se = 0.f, sp = 0.f;
-        for (int i = lane; i < nbins; i += 64) se += expf(r[i] - mx);
-        se = wave_sum(se);
-        for (int i = lane; i < nbins; i += 64) sp += expf(r[i] - mx) / se * (float)i;
-        sp = wave_sum(sp);
-        if (lane == 0) soft[row] = sp / (float)(nbins - 1) * 2.0f - 1.0f;
+        const float sf = wave_softargmax_row(r, nbins, lane, mx, se);
+        if (lane == 0) soft[row] = sf;
     }
 }
 
 int launch_bins_reduce(const float* x, int rows, int nbins, int* idx, float* soft, const LaunchCtx& ctx) {
     ProfScope ps(ctx, "bins_reduce", 0.0, 4.0 * rows * (nbins + 2.0));
     hipLaunchKernelGGL(bins_reduce_kernel, dim3((rows + 3) / 4), dim3(256), 0, ctx.stream, x, rows, nbins, idx, soft);
+    return (int)hipGetLastError();
+}
+
+// ---- CamCalib test step -------------------------------------------------------------------------------------------------
+// camcalib/trainer.py:84-116 after the network: CameraRegressorLoss (camcalib/loss.py:24-125) + convert_preds_to_angles +
+// |pred - gt|.  One wave per (image, head), the reductions of bins_reduce_kernel; per image and head:
+//   loss_term : 'ce' / 'kl' (loss_type 0 / 1): -log_softmax(x)[t] = log(sum exp(x - max)) - (x[t] - max), max-subtracted so that
+//               logits of 1e4 stay finite (F.kl_div against a one-hot target keeps exactly this term of every row);
+//               'softargmax_l2' (2): (t - s)^2; 'softargmax_biased_l2' (3): vfov s > t ? l2 : l2 / (l2 + 1), pitch / roll plain l2
+//   argmax, soft (s), angle = soft_idx_to_angle(s), err = |angle - gt| (radians).
+// A per-image value depends on its own row only.
+__global__ void __launch_bounds__(192) camcalib_eval_kernel(const CamEvalArgs a) {
+    const int b = blockIdx.x, head = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float* r = a.logits[head] + (size_t)b * a.nbins;
+    float mx, se;
+    const int mi = wave_argmax_row(r, a.nbins, lane, mx);
+    const float s = wave_softargmax_row(r, a.nbins, lane, mx, se);
+    if (lane != 0) return;
+    float term;
+    if (a.loss_type <= 1) {
+        const int t = min(max(static_cast<const int*>(a.target[head])[b], 0), a.nbins - 1);
+        term = logf(se) - (r[t] - mx);
+    } else {
+        const float t = static_cast<const float*>(a.target[head])[b];
+        const float d = t - s, l2 = d * d;
+        term = (a.loss_type == 3 && head == 0 && !(s > t)) ? l2 / (l2 + 1.0f) : l2;
+    }
+    const float ang = soft_idx_to_angle(s, head);
+    const size_t o = (size_t)head * a.B + b;
+    a.loss_term[o] = term;
+    a.argmax[o] = mi;
+    a.soft[o] = s;
+    a.angle[o] = ang;
+    a.err[o] = fabsf(ang - a.gt[head][b]);
+}
+
+// The batch means the reference logs, from the per-image arrays: waves 0..2 = mean loss term of a head times its weight
+// (loss.py:109-114), waves 3..5 = mean |error| of a head in degrees (trainer.py:111-113), then loss = vfov + pitch + roll
+// (loss.py:116).  A lane adds images lane, lane + 64, ... in ascending order and the wave folds the 64 partial sums in the
+// xor-shuffle tree: the order is a function of B alone, so two runs give the same bits.
+// means = [loss, vfov_loss, pitch_loss, roll_loss, vfov_acc, pitch_acc, roll_acc]
+__global__ void __launch_bounds__(384) camcalib_eval_mean_kernel(const CamEvalArgs a) {
+    __shared__ float head_loss[3];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, head = wave % 3;
+    const float* v = (wave < 3 ? a.loss_term : a.err) + (size_t)head * a.B;
+    float acc = 0.f;
+    for (int i = lane; i < a.B; i += 64) acc += v[i];
+    acc = wave_sum(acc) / (float)a.B;
+    if (lane == 0) {
+        if (wave < 3) a.means[1 + head] = head_loss[head] = a.weight[head] * acc;
+        else a.means[4 + head] = acc * (float)(180.0 / 3.14159265358979323846);     // Tensor.rad2deg
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) a.means[0] = head_loss[0] + head_loss[1] + head_loss[2];
+}
+
+int launch_camcalib_eval(const CamEvalArgs& a, const LaunchCtx& ctx) {
+    {
+        ProfScope ps(ctx, "camcalib_eval", 0.0, 4.0 * a.B * 3 * (a.nbins + 7.0));
+        hipLaunchKernelGGL(camcalib_eval_kernel, dim3(a.B), dim3(192), 0, ctx.stream, a);
+        if (const int rc = (int)hipGetLastError()) return rc;
+    }
+    if (!a.means) return 0;
+    ProfScope ps(ctx, "camcalib_eval_mean", 0.0, 4.0 * (6.0 * a.B + 7));
+    hipLaunchKernelGGL(camcalib_eval_mean_kernel, dim3(1), dim3(384), 0, ctx.stream, a);
     return (int)hipGetLastError();
 }
 

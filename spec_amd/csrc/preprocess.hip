@@ -343,6 +343,28 @@ int pillow_coeffs(int in_size, int out_size, std::vector<int>& bounds, std::vect
     return ksize;
 }
 
+// The pieces of the resample that resize_normalize_kernel and the ragged batch kernels below share (one statement of the filter):
+// a pass's accumulator -> the uint8 value Pillow stores (clip8)
+__device__ __forceinline__ int pil_clip8(int acc) {
+    const int v = acc >> PIL_BITS;
+    return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+// horizontal pass of ONE pixel: `row` = the source row at the first tap, k = the xcnt fixed-point weights -> uint8 RGB
+__device__ __forceinline__ void pil_hpass(const unsigned char* __restrict__ row, int xcnt, const int* __restrict__ k, int (&v)[3]) {
+    int h[3] = {1 << (PIL_BITS - 1), 1 << (PIL_BITS - 1), 1 << (PIL_BITS - 1)};
+    for (int x = 0; x < xcnt; ++x) {
+        const int w = k[x];
+        h[0] += row[3 * x + 0] * w; h[1] += row[3 * x + 1] * w; h[2] += row[3 * x + 2] * w;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = pil_clip8(h[c]);                 // the uint8 image between the two passes
+}
+// ToTensor + ImageNet Normalize of a uint8 value of colour plane c
+__device__ __forceinline__ float to_tensor_normalize(int v, int c) {
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    return ((float)v / 255.0f - mean[c]) / stdv[c];
+}
+
 __global__ void __launch_bounds__(256) resize_normalize_kernel(const unsigned char* __restrict__ frame, int H, int W, int OH,
                                                                 int OW, const int* __restrict__ hb, const int* __restrict__ hk,
                                                                 int ksh, const int* __restrict__ vb,
@@ -354,27 +376,17 @@ __global__ void __launch_bounds__(256) resize_normalize_kernel(const unsigned ch
     const int xmin = hb[2 * ox], xcnt = hb[2 * ox + 1], ymin = vb[2 * oy], ycnt = vb[2 * oy + 1];
     int acc[3] = {1 << (PIL_BITS - 1), 1 << (PIL_BITS - 1), 1 << (PIL_BITS - 1)};
     for (int y = 0; y < ycnt; ++y) {
-        const unsigned char* row = frame + ((size_t)(ymin + y) * W + xmin) * 3;
-        int h[3] = {1 << (PIL_BITS - 1), 1 << (PIL_BITS - 1), 1 << (PIL_BITS - 1)};
-        for (int x = 0; x < xcnt; ++x) {
-            const int w = hk[(size_t)ox * ksh + x];
-            h[0] += row[3 * x + 0] * w; h[1] += row[3 * x + 1] * w; h[2] += row[3 * x + 2] * w;
-        }
+        int v[3];
+        pil_hpass(frame + ((size_t)(ymin + y) * W + xmin) * 3, xcnt, hk + (size_t)ox * ksh, v);
         const int wv = vk[(size_t)oy * ksv + y];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            int v = h[c] >> PIL_BITS;                     // the uint8 image between the two passes
-            v = v < 0 ? 0 : (v > 255 ? 255 : v);
-            acc[c] += v * wv;
-        }
+        for (int c = 0; c < 3; ++c) acc[c] += v[c] * wv;
     }
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        int v = acc[c] >> PIL_BITS;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
+        const int v = pil_clip8(acc[c]);
         if (raw) raw[(size_t)idx * 3 + c] = (unsigned char)v;
-        out[((size_t)c * OH + oy) * OW + ox] = ((float)v / 255.0f - mean[c]) / stdv[c];
+        out[((size_t)c * OH + oy) * OW + ox] = to_tensor_normalize(v, c);
     }
 }
 
@@ -383,6 +395,80 @@ int launch_resize_normalize(const unsigned char* frame, int H, int W, int OH, in
     ProfScope ps(ctx, "resize_normalize", 0.0, (double)H * W * 3 + (double)OH * OW * (12.0 + (raw ? 3.0 : 0.0)));
     hipLaunchKernelGGL(resize_normalize_kernel, dim3((OH * OW + 255) / 256), dim3(256), 0, ctx.stream, frame, H, W, OH, OW, hb,
                        hk, ksh, vb, vk, ksv, out, raw);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// CamCalib validation batch (camcalib/pano_dataset.py:184-220 Resize(min_size, max_size) per frame, :223-306 collator /
+// to_image_list): n frames of DIFFERENT sizes -> one (n, 3, Hmax, Wmax) tensor, frame f resampled to (OH_f, OW_f) in the
+// top-left corner, exact zeros elsewhere.  Two launches whatever n is: the horizontal pass of every frame into a uint8
+// workspace (H_f x OW_f x 3: what Pillow holds between its passes), then ONE sweep over the whole output that runs the
+// vertical pass + ToTensor + Normalize inside a frame's region and stores 0.0f outside it - every output element is
+// written exactly once.  A frame whose target size is its own size is converted, not resampled (torchvision's resize
+// returns the image unchanged).  Same device functions, hence the same bits, as resize_normalize_kernel.
+// `tab` holds the per-frame records (RaggedFrame, kRaggedRec ints each) followed by the coefficient tables they index.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) ragged_hpass_kernel(const unsigned char* __restrict__ frames, const int* __restrict__ tab,
+                                                            unsigned char* __restrict__ tmp) {
+    const RaggedFrame& fr = reinterpret_cast<const RaggedFrame*>(tab)[blockIdx.y];
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (!fr.resample || idx >= fr.H * fr.OW) return;
+    const int y = idx / fr.OW, ox = idx - y * fr.OW;
+    const int* hb = tab + fr.hb;
+    const int xmin = hb[2 * ox], xcnt = hb[2 * ox + 1];
+    int v[3];
+    pil_hpass(frames + fr.src_off + ((size_t)y * fr.W + xmin) * 3, xcnt, tab + fr.hk + (size_t)ox * fr.ksh, v);
+    unsigned char* q = tmp + fr.tmp_off + (size_t)idx * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) q[c] = (unsigned char)v[c];
+}
+
+__global__ void __launch_bounds__(256) ragged_vpass_pad_kernel(const unsigned char* __restrict__ frames, const int* __restrict__ tab,
+                                                                const unsigned char* __restrict__ tmp, int Hmax, int Wmax,
+                                                                float* __restrict__ out) {
+    const RaggedFrame& fr = reinterpret_cast<const RaggedFrame*>(tab)[blockIdx.y];
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= Hmax * Wmax) return;
+    const int oy = idx / Wmax, ox = idx - oy * Wmax;
+    float r[3] = {0.0f, 0.0f, 0.0f};                                     // to_image_list: zeros in normalised space
+    if (oy < fr.OH && ox < fr.OW) {
+        int v[3];
+        if (fr.resample) {
+            const int ymin = tab[fr.vb + 2 * oy], ycnt = tab[fr.vb + 2 * oy + 1];
+            const int* vk = tab + fr.vk + (size_t)oy * fr.ksv;
+            int acc[3] = {1 << (PIL_BITS - 1), 1 << (PIL_BITS - 1), 1 << (PIL_BITS - 1)};
+            const unsigned char* col = tmp + fr.tmp_off + ((size_t)ymin * fr.OW + ox) * 3;
+            for (int y = 0; y < ycnt; ++y) {
+                const int wv = vk[y];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c] += col[(size_t)y * fr.OW * 3 + c] * wv;
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = pil_clip8(acc[c]);
+        } else {
+            const unsigned char* q = frames + fr.src_off + ((size_t)oy * fr.W + ox) * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c] = q[c];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r[c] = to_tensor_normalize(v[c], c);
+    }
+    const size_t plane = (size_t)Hmax * Wmax;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[((size_t)blockIdx.y * 3 + c) * plane + idx] = r[c];
+}
+
+int launch_resize_normalize_ragged(const unsigned char* frames, const int* tab, unsigned char* tmp, int n, int max_hpass_px,
+                                   int Hmax, int Wmax, double src_bytes, double tmp_bytes, float* out, const LaunchCtx& ctx) {
+    // algorithmic HBM bytes: every frame once, the uint8 rows between the passes written and read once, every output element once
+    if (max_hpass_px > 0) {
+        ProfScope ps(ctx, "ragged_hpass", 0.0, src_bytes + tmp_bytes);
+        hipLaunchKernelGGL(ragged_hpass_kernel, dim3((max_hpass_px + 255) / 256, n), dim3(256), 0, ctx.stream, frames, tab, tmp);
+        if (const int rc = (int)hipGetLastError()) return rc;
+    }
+    ProfScope ps(ctx, "ragged_vpass_pad", 0.0, 12.0 * n * Hmax * Wmax + tmp_bytes);
+    hipLaunchKernelGGL(ragged_vpass_pad_kernel, dim3((Hmax * Wmax + 255) / 256, n), dim3(256), 0, ctx.stream, frames, tab, tmp, Hmax,
+                       Wmax, out);
     return (int)hipGetLastError();
 }
 

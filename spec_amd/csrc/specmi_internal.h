@@ -292,6 +292,18 @@ int launch_fc_gemv(const FcGemv* heads, int nheads, int N, int Kp, int ldx, int 
 int launch_cam_params(const float* pitch, const float* roll, const float* f_pix, const float* img_w, const float* img_h,
                       int B, float* R, float* K, const LaunchCtx& ctx);
 
+// CamCalib test step (camcalib/loss.py:24-125 + camcalib/trainer.py:104-116) on three (B, nbins) logit tensors.  Every per-image
+// array is (3, B), heads in the order vfov, pitch, roll; means = 7 floats (include/specmi.h: specmi_camcalib_eval)
+struct CamEvalArgs {
+    const float* logits[3];
+    const void* target[3];        // int32 bin index (loss_type 0 / 1) or fp32 soft index (2 / 3)
+    const float* gt[3];           // ground-truth angles, radians
+    int B, nbins, loss_type;
+    float weight[3];
+    float* loss_term; int* argmax; float* soft; float* angle; float* err; float* means;
+};
+int launch_camcalib_eval(const CamEvalArgs& a, const LaunchCtx& ctx);
+
 // ----------------------------------------------------------------------------------------
 // SMPL  (smpl.hip)
 // ----------------------------------------------------------------------------------------
@@ -377,5 +389,14 @@ int launch_crop_resize_normalize(const unsigned char* frame, int H, int W, const
 int pillow_coeffs(int in_size, int out_size, std::vector<int>& bounds, std::vector<int>& kk);
 int launch_resize_normalize(const unsigned char* frame, int H, int W, int OH, int OW, const int* hb, const int* hk, int ksh,
                             const int* vb, const int* vk, int ksv, float* out, unsigned char* raw, const LaunchCtx& ctx);
+
+// One frame of a ragged batch as the device reads it (kRaggedRec ints at the head of the table buffer): byte offset of the
+// frame in the slab, source and target size, int offsets of its coefficient tables (pillow_coeffs layout) in the same buffer,
+// byte offset of its H x OW x 3 intermediate in the uint8 workspace; resample = 0: target size == size, convert only
+struct RaggedFrame { unsigned src_off; int H, W, OH, OW, hb, hk, ksh, vb, vk, ksv; unsigned tmp_off; int resample, pad_[3]; };
+constexpr int kRaggedRec = sizeof(RaggedFrame) / 4;
+// max_hpass_px = max over the resampled frames of H * OW (0: no frame is resampled, the horizontal launch is skipped)
+int launch_resize_normalize_ragged(const unsigned char* frames, const int* tab, unsigned char* tmp, int n, int max_hpass_px,
+                                   int Hmax, int Wmax, double src_bytes, double tmp_bytes, float* out, const LaunchCtx& ctx);
 
 }  // namespace specmi

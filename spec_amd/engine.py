@@ -308,6 +308,54 @@ class Engine:
         _lib.check(self.h, self.lib.specmi_camcalib_bins(self.h, _ptr(x), rows, nb, _ptr(idx), _ptr(sf), self._stream()))
         return idx, sf
 
+    def camcalib_eval(self, lv, lp, lr, targets, gts, loss_type, weights=(1.0, 1.0, 1.0)):
+        """``specmi_camcalib_eval``: the loss terms, decode and angle errors of CamCalib's test step on three (B, nbins) logit
+        tensors.  ``targets``: three (B,) arrays - integer bin indices for 'ce' / 'kl', fp32 soft indices for the soft-argmax losses;
+        ``gts``: three (B,) angles in radians.  -> dict(loss_term, argmax, soft, angle, err: (3, B) device tensors in the order
+        vfov, pitch, roll; means: (7,) = loss, vfov_loss, pitch_loss, roll_loss, vfov_acc, pitch_acc, roll_acc [degrees])."""
+        if loss_type not in _lib.LOSS_TYPES:
+            raise ValueError(f'{loss_type} is not defined..')
+        lv, lp, lr = (_dev_f32(t, self.device) for t in (lv, lp, lr))
+        B, nb = lv.shape
+        if lp.shape != (B, nb) or lr.shape != (B, nb):
+            raise ValueError('the three logit tensors must have one shape')
+        tdt = torch.int32 if loss_type in ('ce', 'kl') else torch.float32
+        tg = [torch.as_tensor(np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t)).to(device=self.device, dtype=tdt).contiguous()
+              for t in targets]
+        gt = [_dev_f32(g, self.device, (B,)) for g in gts]
+        if any(t.shape != (B,) for t in tg):
+            raise ValueError('targets: three (B,) arrays')
+        mk = lambda dt=torch.float32: torch.empty(3, B, device=self.device, dtype=dt)
+        res = {'loss_term': mk(), 'argmax': mk(torch.int32), 'soft': mk(), 'angle': mk(), 'err': mk(),
+               'means': torch.empty(7, device=self.device, dtype=torch.float32)}
+        if B > 0:
+            _lib.check(self.h, self.lib.specmi_camcalib_eval(
+                self.h, _ptr(lv), _ptr(lp), _ptr(lr), B, nb, _lib.LOSS_TYPES[loss_type], _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]),
+                _ptr(gt[0]), _ptr(gt[1]), _ptr(gt[2]), float(weights[0]), float(weights[1]), float(weights[2]), _ptr(res['loss_term']),
+                _ptr(res['argmax']), _ptr(res['soft']), _ptr(res['angle']), _ptr(res['err']), _ptr(res['means']), self._stream()))
+        return res
+
+    def resize_normalize_ragged(self, slab, offsets, geom, out=None):
+        """``specmi_resize_normalize_ragged``: ``slab`` = 1-D uint8 device tensor holding n RGB HWC frames, ``offsets`` (n,) byte
+        offsets, ``geom`` (n, 4) [H, W, OH, OW] (both on the host) -> (n, 3, max OH, max OW) fp32, frame f in the top-left
+        corner of its image, exact zeros elsewhere."""
+        if not isinstance(slab, torch.Tensor) or slab.device.type != 'cuda' or slab.dtype != torch.uint8 or slab.dim() != 1:
+            raise ValueError('slab must be a 1-D uint8 device tensor')
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        geom = np.ascontiguousarray(geom, dtype=np.int32).reshape(-1, 4)
+        n = geom.shape[0]
+        if n < 1 or offsets.shape[0] != n:
+            raise ValueError('one offset and one [H, W, OH, OW] row per frame (at least one frame)')
+        Hmax, Wmax = int(geom[:, 2].max()), int(geom[:, 3].max())
+        if out is None:
+            out = torch.empty(n, 3, Hmax, Wmax, device=self.device, dtype=torch.float32)
+        elif tuple(out.shape) != (n, 3, Hmax, Wmax) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f'out must be a contiguous ({n},3,{Hmax},{Wmax}) fp32 device tensor')
+        _lib.check(self.h, self.lib.specmi_resize_normalize_ragged(
+            self.h, _ptr(slab.contiguous()), slab.numel(), offsets.ctypes.data_as(_lib.c_int64_p), geom.ctypes.data_as(_lib.c_int32_p),
+            n, Hmax, Wmax, _ptr(out), self._stream()))
+        return out
+
     def _cam_args(self, B, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h):
         d = self.device
         return (_dev_f32(cam_rotmat, d, (B, 3, 3)), _dev_f32(cam_intrinsics, d, (B, 3, 3)),

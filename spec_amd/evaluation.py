@@ -46,11 +46,12 @@ DEFAULTS = {   # the hparams of spec/config.py the evaluation reads
 }
 
 
-def load_config(cfg_path: Optional[str], opts: Optional[List[str]] = None) -> dict:
-    """YAML config (yacs dump) merged over the defaults, then ``--opts KEY.SUB value ...`` overrides."""
+def load_config(cfg_path: Optional[str], opts: Optional[List[str]] = None, defaults: Optional[dict] = None) -> dict:
+    """YAML config (yacs dump) merged over the defaults, then ``--opts KEY.SUB value ...`` overrides.  ``defaults``: another
+    default tree than this flow's (``spec_amd.camcalib_eval`` merges its own the same way)."""
     import copy
     import yaml
-    hp = copy.deepcopy(DEFAULTS)
+    hp = copy.deepcopy(DEFAULTS if defaults is None else defaults)
 
     def merge(dst, src):
         for k, v in (src or {}).items():
