@@ -354,6 +354,15 @@ int specmi_maxpool3x3s2(specmi_handle* h, const float* x, int B, int H, int W, i
 int specmi_avgpool(specmi_handle* h, const float* x, int B, int HW, int C, float* out,
                    void* stream);
 
+/* The two small kernels of the fp16 trunk (conv_f16.hip), trunk building blocks as the two above are.  Max-pool: x (B,H,W,C)
+ * and out (B,OH,OW,C) fp16 NHWC device, C % 8 == 0, exact (the result is one of the inputs).  Image conversion: x (B,C,H,W) fp32
+ * NCHW device, 1 <= C <= 8, out (B,H,W,8) fp16 NHWC device, values rounded to nearest even (|v| >= 65520 becomes inf), channels
+ * past C are +0.  Device pointers 16-byte aligned. */
+int specmi_maxpool3x3s2_f16(specmi_handle* h, const void* x, int B, int H, int W, int C,
+                            void* out, void* stream);
+int specmi_to_nhwc_f16(specmi_handle* h, const float* x, int B, int C, int H, int W, void* out,
+                       void* stream);
+
 /* ---- crop + normalise in front of the path ------------------------------------ */
 
 /* The detection loop of spec/tester.py:116-128: for each bbox (cx, cy, w, h) [device, (n,4)]

@@ -1336,6 +1336,22 @@ int specmi_maxpool3x3s2(specmi_handle* h, const float* x, int B, int H, int W, i
     return SPECMI_OK;
 }
 
+int specmi_maxpool3x3s2_f16(specmi_handle* h, const void* x, int B, int H, int W, int C, void* out, void* stream) {
+    ENTER(h);
+    if (!x || !out || B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8) return fail(h, SPECMI_ERR_ARG, "bad argument (C % 8 == 0)");
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "maxpool_f16"};
+    LAUNCHCHK(h, launch_maxpool_f16(x, out, B, H, W, C, conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1), ctx), "maxpool_f16");
+    return SPECMI_OK;
+}
+
+int specmi_to_nhwc_f16(specmi_handle* h, const float* x, int B, int C, int H, int W, void* out, void* stream) {
+    ENTER(h);
+    if (!x || !out || B <= 0 || H <= 0 || W <= 0 || C < 1 || C > 8) return fail(h, SPECMI_ERR_ARG, "bad argument (1 <= C <= 8)");
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "to_nhwc_f16"};
+    LAUNCHCHK(h, launch_to_nhwc_f16(x, out, B, C, H, W, ctx), "to_nhwc_f16");
+    return SPECMI_OK;
+}
+
 int specmi_avgpool(specmi_handle* h, const float* x, int B, int HW, int C, float* out, void* stream) {
     ENTER(h);
     if (!x || !out || B <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");

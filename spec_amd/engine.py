@@ -532,6 +532,24 @@ class Engine:
         _lib.check(self.h, self.lib.specmi_maxpool3x3s2(self.h, _ptr(x), B, H, W, Cc, _ptr(out), self._stream()))
         return out
 
+    def maxpool_f16(self, x):
+        """MaxPool2d(3, 2, 1) of the fp16 trunk (tests).  x (B,H,W,C) fp16 NHWC device tensor, C % 8 == 0."""
+        if not (isinstance(x, torch.Tensor) and x.dtype == torch.float16 and x.is_cuda):
+            raise TypeError('x must be a float16 cuda tensor')
+        x = x.contiguous()
+        B, H, W, Cc = x.shape
+        out = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc, device=self.device, dtype=torch.float16)
+        _lib.check(self.h, self.lib.specmi_maxpool3x3s2_f16(self.h, _ptr(x), B, H, W, Cc, _ptr(out), self._stream()))
+        return out
+
+    def to_nhwc_f16(self, x):
+        """The fp16 trunk's image conversion (tests).  x (B,C,H,W) fp32 NCHW, C <= 8 -> (B,H,W,8) fp16 NHWC, pad channels zero."""
+        x = _dev_f32(x, self.device)
+        B, Cc, H, W = x.shape
+        out = torch.empty(B, H, W, 8, device=self.device, dtype=torch.float16)
+        _lib.check(self.h, self.lib.specmi_to_nhwc_f16(self.h, _ptr(x), B, Cc, H, W, _ptr(out), self._stream()))
+        return out
+
     def avgpool(self, x):
         x = _dev_f32(x, self.device)
         B, H, W, Cc = x.shape

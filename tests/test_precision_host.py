@@ -8,7 +8,7 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ('specmi_set_precision', 'specmi_get_precision', 'specmi_conv2d_f16')
+NEW = ('specmi_set_precision', 'specmi_get_precision', 'specmi_conv2d_f16', 'specmi_maxpool3x3s2_f16', 'specmi_to_nhwc_f16')
 
 
 @pytest.fixture(scope='module')
