@@ -412,6 +412,27 @@ int specmi_resize_normalize(specmi_handle* h, const uint8_t* frame_rgb_hwc, int 
 int specmi_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames_rgb_hwc, size_t slab_bytes, const int64_t* offsets,
                                    const int32_t* geom, int n, int Hmax, int Wmax, float* out_nchw, void* stream);
 
+/* Labelled perspective views out of an equirectangular panorama - the per-pixel work of the reference's dataset generator,
+ * extractImage's mode="image" branch (camcalib/datagen/image_extraction.py:129-159, called by makeAndSaveImg,
+ * camcalib/datagen/generateCalibrationDataset.py:122-126): n views of DIFFERENT sizes cut from ONE uint8 RGB HWC panorama in
+ * device memory in one launch.  views (HOST, n x 5 doubles): elevation, azimuth, roll in radians, vfov in degrees, ratio =
+ * width / height; out_hw (HOST, n x 2): height and width of view f, the width being round(height / (1 / ratio)) with
+ * Python's round (a mismatch is refused); view f is written as uint8 HWC at out_slab + offsets[f] (HOST offsets, the slab
+ * and offsets convention of specmi_resize_normalize_ragged, whose input this is).  Bytes of the slab between views are not
+ * touched.  Per pixel, in fp64: numpy.linspace grid, roll in the image plane, inverse gnomonic projection with the
+ * reference's rho + 1e-10, the two +-2 pi wraps, the reference's pixel maps, then
+ * scipy.ndimage.map_coordinates(order=1, prefilter=False, mode="wrap") as scipy computes it (period N - 1) and scipy's
+ * uint8 store.  Differs from the reference only where the last ulp of the device's asin / atan2 moves a value across a
+ * rounding tie.  Refused (SPECMI_ERR_ARG): a null pointer, n <= 0 or > 65535, a size below 1, a non-finite view parameter,
+ * vfov outside (0, 180), ratio <= 0, a view that leaves the slab.
+ * The per-view records live in one device table owned by the handle.  A call whose views or sizes differ from the previous
+ * call's rewrites that table and therefore first SYNCHRONISES THE WHOLE DEVICE (an extraction enqueued earlier, on any stream,
+ * may still read it) - in practice once per panorama; the same rule as specmi_resize_normalize_ragged's tables.  Such a call
+ * cannot be made while a stream is being captured (SPECMI_ERR_STATE); a call that repeats the previous views does neither. */
+int specmi_pano_extract_views(specmi_handle* h, const uint8_t* pano_rgb_hwc, int PH, int PW, const double* views,
+                              const int32_t* out_hw, const int64_t* offsets, size_t slab_bytes, uint8_t* out_slab, int n,
+                              void* stream);
+
 /* ---- evaluation metrics on the path's outputs ---------------------------------- */
 
 /* eval_single (spec/utils/compute_error.py:52-86, spec/trainer.py:272-316): joints =

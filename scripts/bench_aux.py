@@ -9,6 +9,8 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
 
     python scripts/bench_aux.py [--iters 20] [--out gpurun_out/aux_bench.json]
     python scripts/bench_aux.py --only camcalib_eval      # the two kernels of CamCalib's test step -> profiles/camcalib_eval_aux.json
+    python scripts/bench_aux.py --only pano_views         # the panorama view extractor -> profiles/pano_views_aux.json
+    python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
 import argparse
 import json
@@ -98,6 +100,112 @@ def camcalib_eval_section(eng, a, add, g):
     return cmp_
 
 
+PANO_HW, PANO_SEED, PANO_VIEWS = (4096, 8192), 12, 12
+
+
+def pano_workload():
+    """The extractor's workload: a seeded 8192 x 4096 uint8 panorama (smooth content + noise) and 12 cameras of ``sample_cameras``."""
+    from spec_amd import panorama
+    rng = np.random.default_rng(PANO_SEED)
+    H, W = PANO_HW
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    pano = np.stack([127 + 100 * np.sin(xx / (300.0 + 40 * c)) * np.cos(yy / (250.0 + 30 * c)) for c in range(3)], -1)
+    pano = np.clip(pano + rng.normal(0, 8, pano.shape).astype(np.float32), 0, 255).astype(np.uint8)
+    cams = panorama.sample_cameras(PANO_VIEWS, rng)
+    views, heights = panorama.camera_views(cams)
+    return pano, views, heights, [panorama.view_size(h, r) for h, r in zip(heights, views[:, 4])]
+
+
+def scipy_wrap(c, n):
+    """The fold the kernel applies (scipy's historical mode="wrap"): only a coordinate OUTSIDE [0, n - 1] moves, by multiples of n - 1."""
+    c = np.where(c < 0, c + (n - 1) * (np.trunc(-c / (n - 1)) + 1), c)
+    return np.where(c > n - 1, c - (n - 1) * np.trunc(c / (n - 1)), c)
+
+
+def texels_touched(views, sizes, PH, PW):
+    """Distinct panorama texels the four taps of every output pixel read, per view summed (a host float64 evaluation of the
+    kernel's coordinates; a tap that lands one texel off at a rounding tie does not change the count materially)."""
+    total = 0
+    for (el, az, roll, vfov, ratio), (h, w) in zip(views, sizes):
+        fy = np.tan(np.radians(vfov) / 2.0); fxx = fy / (1.0 / ratio)
+        x, y = np.meshgrid(np.linspace(-fxx, fxx, w), np.linspace(-fy, fy, h), indexing='xy')
+        x, y = x * np.cos(roll) + y * np.sin(roll), -x * np.sin(roll) + y * np.cos(roll)
+        rho = np.sqrt(x * x + y * y); c = np.arctan(rho)
+        lat = np.arcsin(np.clip(np.cos(c) * np.sin(el) + y * np.sin(c) * np.cos(el) / (rho + 1e-10), -1, 1))
+        lon = az + np.arctan2(x * np.sin(c), rho * np.cos(el) * np.cos(c) - y * np.sin(el) * np.sin(c))
+        lon = np.where(lon > np.pi, lon - 2 * np.pi, lon); lon = np.where(lon < -np.pi, lon + 2 * np.pi, lon)
+        col = scipy_wrap(lon / np.pi * PW / 2 + PW / 2, PW); row = scipy_wrap(lat / (np.pi / 2) * PH / 2 + PH / 2, PH)
+        r0, c0 = np.floor(row).astype(np.int64), np.floor(col).astype(np.int64)
+        r1, c1 = np.minimum(r0 + 1, PH - 1), np.minimum(c0 + 1, PW - 1)
+        total += np.unique(np.concatenate([(r * PW + cc).ravel() for r in (r0, r1) for cc in (c0, c1)])).size
+    return int(total)
+
+
+def pano_views_section(eng, a):
+    """The extractor on an 8192 x 4096 panorama, 12 views: HIP-event time against the HBM roof with bytes = output bytes + distinct
+    texels touched x 3, and - wall clock, same run, same batch - beside the two steps it feeds: the ragged resize and CamCalib's forward."""
+    import tempfile
+    import time
+    from spec_amd import camcalib_eval as ce
+    pano_np, views, heights, sizes = pano_workload()
+    pano = torch.from_numpy(pano_np).to(eng.device)
+    out_bytes = sum(h * w * 3 for h, w in sizes)
+    touched = texels_touched(views, sizes, *PANO_HW) * 3
+    slab, offsets = eng.pano_extract_views(pano, views, sizes)
+    extract = lambda: eng.pano_extract_views(pano, views, sizes, offsets=offsets, out=slab)
+    ms = timed(eng, extract, a.iters)['pano_extract'][0]
+    geom = [(h, w) + ce.resize_size(w, h, 600, 1000) for h, w in sizes]
+    batch = eng.resize_normalize_ragged(slab, offsets, geom)
+    with tempfile.TemporaryDirectory() as tmp:
+        ce.write_standin_tree(tmp, n_images=1)
+        model = ce.build_model(ce.load_config(os.path.join(tmp, ce.STANDIN_CFG)), None, tmp, eng.device)
+    meng = model.engine(eng.device)
+    steps = {'pano_extract_views': extract, 'resize_normalize_ragged': lambda: meng.resize_normalize_ragged(slab, offsets, geom, out=batch),
+             'camcalib_forward_resnet34': lambda: ce.forward_padded(model, batch)}
+    wall = {k: [] for k in steps}
+    for k, fn in steps.items():
+        fn()
+    for _ in range(max(5, a.iters // 2)):
+        for k, fn in steps.items():
+            torch.cuda.synchronize(); t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+            wall[k].append((time.perf_counter() - t0) * 1e3)
+    med = {k: round(float(np.median(v)), 3) for k, v in wall.items()}
+    row = {'workload': f'{len(sizes)} views of sample_cameras (seed {PANO_SEED}; sizes {sorted(set(sizes))}) out of one {PANO_HW[1]} x {PANO_HW[0]} uint8 panorama',
+           'kernel': 'pano_extract', 'ms_per_launch': round(ms, 5), 'output_MB': round(out_bytes / 1e6, 3), 'texels_touched_MB': round(touched / 1e6, 3),
+           'achieved_GBps': round((out_bytes + touched) / (ms * 1e-3) / 1e9, 1), 'frac_of_hbm_peak': round((out_bytes + touched) / (ms * 1e-3) / HBM_PEAK, 4),
+           'Mpixels_per_s': round(out_bytes / 3 / (ms * 1e-3) / 1e6, 1),
+           'wall_ms_median_same_batch': med, 'padded_batch': list(batch.shape),
+           'extract_share_of_step': round(med['pano_extract_views'] / sum(med.values()), 4),
+           'note': 'wall clock includes host work per call (view table, Pillow coefficient tables); the extractor call synchronises the '
+                   'device when its view table changes, which a fresh panorama always does'}
+    print(json.dumps(row, indent=1))
+    return row
+
+
+def pano_views_host(a):
+    """The reference's own extractImage on THIS host's CPU for the same panorama and views (context for pano_views; no GPU)."""
+    import time
+    import warnings
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden'))
+    from make_panorama_fixture import import_extract_image
+    ie = import_extract_image(a.reference)
+    pano, views, heights, sizes = pano_workload()
+    per = []
+    with warnings.catch_warnings():
+        warnings.simplefilter('ignore')
+        for (el, az, roll, vfov, ratio), h in zip(views, heights):
+            t0 = time.perf_counter()
+            im = ie.extractImage(pano, [el, az, roll], h, vfov=vfov, ratio=ratio)
+            per.append((time.perf_counter() - t0) * 1e3)
+            assert im.shape[:2] == sizes[len(per) - 1]
+    row = {'workload': f'{len(sizes)} views, the workload of --only pano_views', 'reference_extractImage_ms_per_view': [round(t, 1) for t in per],
+           'reference_extractImage_ms_total': round(sum(per), 1), 'host': f'{os.cpu_count()} logical CPUs, numpy {np.__version__}; one process, as the reference runs it'}
+    print(json.dumps(row, indent=1))
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        json.dump(row, f, indent=1)
+
+
 def finish(a, table, extra=None):
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, 'w') as f:
@@ -111,11 +219,14 @@ def finish(a, table, extra=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['camcalib_eval'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['camcalib_eval', 'pano_views', 'pano_views_host'], default=None, help='run one section only')
+    ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--out', default='gpurun_out/aux_bench.json')
     a = ap.parse_args()
+    if a.only == 'pano_views_host':
+        return pano_views_host(a)
     from spec_amd import assets, preprocess, metrics
     from spec_amd.cam_utils import _engine
     assets.use_synthetic_assets(1003)
@@ -141,6 +252,15 @@ def main():
         from spec_amd import _lib
         cmp_ = camcalib_eval_section(eng, a, add, g)
         return finish(a, table, {'pad_batch_vs_per_frame_composition': cmp_, 'source_hash': _lib.source_hash()})
+
+    if a.only == 'pano_views':
+        from spec_amd import _lib
+        row = pano_views_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'per-launch HIP events (library profiler); wall clock where named',
+                       'pano_views': row, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
 
     # ---- 8f-1: crops from one 1080p frame ---------------------------------------------------------------------------
     frame = torch.randint(0, 256, (1080, 1920, 3), generator=g, dtype=torch.uint8).to(dev)

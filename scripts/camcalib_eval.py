@@ -12,6 +12,12 @@ the reference logs at epoch end: val loss, vfov / pitch / roll mean absolute err
 ``--standin DIR`` first writes a small synthetic tree in the REAL formats under DIR (frames of mixed sizes, JSON labels,
 ``val_images.pkl``, a Lightning-layout checkpoint, the YAML config) and evaluates that: a dry run of the whole flow, the
 numbers are meaningless.  ``--report FILE`` writes the result (without the logits) as JSON.
+
+``--panoramas DIR`` evaluates on views generated from the equirectangular panoramas under DIR instead of a stored validation
+set - the reference's dataset generator (camcalib/datagen/generateCalibrationDataset.py) on the GPU: ``--views-per-pano``
+cameras per panorama drawn from its distribution with ``--seed``, cut out on the device and fed to the network without
+leaving it.  ``--write-tree OUT`` also stores these views as a 'pano_scalenet' tree under OUT (JPEG quality 95 + JSON labels +
+``val_images.pkl``), which ``--data-root OUT --opts DATASET.VAL_DS pano_scalenet`` (and the reference's loader) reads.
 """
 import argparse
 import json
@@ -30,6 +36,10 @@ def main():
     ap.add_argument('--data-root', type=str, default='.', help='directory that holds data/')
     ap.add_argument('--standin', type=str, default=None, help='write a synthetic tree in the real formats here and evaluate it')
     ap.add_argument('--report', type=str, default=None, metavar='eval.json')
+    ap.add_argument('--panoramas', type=str, default=None, metavar='DIR', help='evaluate on views generated from the panoramas in DIR')
+    ap.add_argument('--views-per-pano', type=int, default=12)
+    ap.add_argument('--seed', type=int, default=0, help='seed of the camera sampler (--panoramas)')
+    ap.add_argument('--write-tree', type=str, default=None, metavar='OUT', help='with --panoramas: also write the views as a pano_scalenet tree')
     args = ap.parse_args()
     import torch
     torch.set_grad_enabled(False)
@@ -40,7 +50,15 @@ def main():
         root = args.standin
         cfg = cfg or os.path.join(root, ce.STANDIN_CFG)
     hp = ce.load_config(cfg, args.opts)
-    res = ce.run_evaluation(hp, data_root=root, ckpt=args.ckpt)
+    dataset = None
+    if args.write_tree and not args.panoramas:
+        ap.error('--write-tree needs --panoramas')
+    if args.panoramas:
+        from spec_amd import panorama
+        dataset = panorama.PanoViewDataset(panorama.list_panoramas(args.panoramas), args.views_per_pano, args.seed)
+        if args.write_tree:
+            panorama.write_tree(dataset, args.write_tree, while_evaluating=True)     # every view is generated once
+    res = ce.run_evaluation(hp, data_root=root, ckpt=args.ckpt, dataset=dataset)
     if args.report:
         rep = {k: (v.tolist() if hasattr(v, 'tolist') else v) for k, v in res.items() if k != 'logits'}
         with open(args.report, 'w') as f:

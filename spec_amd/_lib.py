@@ -37,6 +37,7 @@ LOSS_TYPES = {'ce': 0, 'kl': 1, 'softargmax_l2': 2, 'softargmax_biased_l2': 3}  
 c_float_p = C.POINTER(C.c_float)
 c_int32_p = C.POINTER(C.c_int32)
 c_int64_p = C.POINTER(C.c_int64)
+c_double_p = C.POINTER(C.c_double)
 
 
 class HmrOutputs(C.Structure):
@@ -129,6 +130,8 @@ PROTOTYPES = {
                                           C.c_void_p]),
     'specmi_resize_normalize_ragged': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, c_int32_p, C.c_int, C.c_int, C.c_int,
                                                  C.c_void_p, C.c_void_p]),
+    'specmi_pano_extract_views': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_double_p, c_int32_p, c_int64_p, C.c_size_t,
+                                            C.c_void_p, C.c_int, C.c_void_p]),
     'specmi_camcalib_eval': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -130,10 +130,14 @@ class PanoValDataset:
         return evaluation.read_image_rgb(self.imgname(i))
 
 
-def pad_batch(frames: List[np.ndarray], min_size: int, max_size: Optional[int], device, engine=None) -> torch.Tensor:
+def pad_batch(frames, min_size: int, max_size: Optional[int], device, engine=None) -> torch.Tensor:
     """Steps 1-2 for one batch: (H_f, W_f, 3) uint8 host frames -> (n, 3, Hmax, Wmax) fp32 on the device (one upload, two
-    launches)."""
+    launches).  ``frames`` may also be ``(slab, offsets, [(H, W)])`` - frames that already lie in a 1-D uint8 device slab
+    (``spec_amd.panorama.PanoViewDataset.device_batch``): nothing is uploaded."""
     eng = engine or cam_utils._engine(torch.device(device))
+    if isinstance(frames, tuple):
+        slab, offsets, sizes = frames
+        return eng.resize_normalize_ragged(slab, offsets, [(H, W) + resize_size(W, H, min_size, max_size) for H, W in sizes])
     geom, offsets, off = [], [], 0
     for fr in frames:
         if fr.dtype != np.uint8 or fr.ndim != 3 or fr.shape[2] != 3:
@@ -189,8 +193,9 @@ def build_model(hparams: dict, ckpt: Optional[str], data_root: str = '.', device
 
 @torch.no_grad()
 def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = None, log=print, device='cuda', model=None,
-                   sub_batch: Optional[int] = None) -> dict:
-    """CamCalib's test epoch over ``DATASET.VAL_DS``: consecutive batches of ``DATASET.BATCH_SIZE`` frames in file order, each
+                   sub_batch: Optional[int] = None, dataset=None) -> dict:
+    """CamCalib's test epoch over ``DATASET.VAL_DS`` - or over ``dataset``, an object with ``PanoValDataset``'s interface such as
+    ``spec_amd.panorama.PanoViewDataset``, whose ``device_batch`` hands frames over without a host round trip: consecutive batches of ``DATASET.BATCH_SIZE`` frames in file order, each
     padded to ITS OWN largest height and width, forwarded, scored.  Returns the four epoch figures the reference logs
     (``val_loss``, ``vfov_acc``, ``pitch_acc``, ``roll_acc``: mean of the per-batch means), the per-batch dicts and, per image,
     the logits, decoded angles and absolute errors (radians).
@@ -205,7 +210,7 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     loss_type = m['LOSS_TYPE']
     if loss_type not in LOSS_TYPES:
         raise ValueError(f'{loss_type} is not defined..')
-    ds = PanoValDataset(val_dataset_name(hparams), data_root)
+    ds = dataset if dataset is not None else PanoValDataset(val_dataset_name(hparams), data_root)
     log(f'Val dataset len: {len(ds)}')
     if model is None:
         model = build_model(hparams, ckpt, data_root, dev)
@@ -218,7 +223,9 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     outputs, per = [], {k: [] for k in ('logits', 'pred', 'err', 'gt', 'img_sizes')}
     for b0 in range(0, len(ds), bs):
         idx = range(b0, min(len(ds), b0 + bs))
-        frames = [ds.frame(i) for i in idx]
+        on_device = hasattr(ds, 'device_batch')
+        frames = ds.device_batch(idx) if on_device else [ds.frame(i) for i in idx]
+        sizes_hw = frames[2] if on_device else [f.shape[:2] for f in frames]
         gt = np.asarray([ds.labels(i) for i in idx], dtype=np.float64).T              # (3, n): vfov, pitch, roll
         gt32 = gt.astype(np.float32)                                                   # torch.tensor(python float)
         images = pad_batch(frames, min_res, max_res, dev, eng)
@@ -226,7 +233,7 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         ev = eng.camcalib_eval(*logits, encode_targets(*gt, loss_type), gt32, loss_type, weights)
         means = ev['means'].cpu().numpy()
         out = {'loss': float(means[0]), 'vfov_loss': float(means[1]), 'pitch_loss': float(means[2]), 'roll_loss': float(means[3]),
-               'n': len(frames), 'padded_hw': tuple(images.shape[2:])}
+               'n': len(idx), 'padded_hw': tuple(images.shape[2:])}
         if loss_type in ('ce', 'kl'):
             am = ev['argmax'].cpu().numpy()
             pred = np.stack([centers[k][am[k]] for k in range(3)])                     # float64 bin centres
@@ -241,7 +248,7 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         outputs.append(out)
         per['logits'].append(torch.stack(logits, 0).cpu().numpy())
         per['pred'].append(pred); per['err'].append(err); per['gt'].append(gt)
-        per['img_sizes'] += [resize_size(f.shape[1], f.shape[0], min_res, max_res) for f in frames]
+        per['img_sizes'] += [resize_size(w, h, min_res, max_res) for h, w in sizes_hw]
     if eng.sync_status() != 0:
         raise RuntimeError('a split-K arrival counter was left non-zero')
     res = epoch_end(outputs)

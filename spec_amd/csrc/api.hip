@@ -784,6 +784,7 @@ int specmi_destroy(specmi_handle* h) {
     if (h->resize_tab) (void)hipFree(h->resize_tab);
     if (h->ragged_tab) (void)hipFree(h->ragged_tab);
     if (h->ragged_tmp) (void)hipFree(h->ragged_tmp);
+    if (h->pano_tab) (void)hipFree(h->pano_tab);
     hrnet_free(h->hrnet);
     delete h;
     return SPECMI_OK;
@@ -1458,6 +1459,47 @@ int specmi_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames, size
     LAUNCHCHK(h, launch_resize_normalize_ragged(frames, h->ragged_tab, h->ragged_tmp, n, max_hpass, Hmax, Wmax, (double)slab_bytes, (double)tmp_bytes,
                                                 out, ctx),
               "resize_normalize_ragged");
+    return SPECMI_OK;
+}
+
+int specmi_pano_extract_views(specmi_handle* h, const uint8_t* pano, int PH, int PW, const double* views, const int32_t* out_hw,
+                              const int64_t* offsets, size_t slab_bytes, uint8_t* out_slab, int n, void* stream) {
+    ENTER(h);
+    if (!pano || !views || !out_hw || !offsets || !out_slab) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (n <= 0) return fail(h, SPECMI_ERR_ARG, "at least one view per call, got %d", n);
+    if (n > 65535) return fail(h, SPECMI_ERR_ARG, "at most 65535 views per call (grid dimension), got %d", n);
+    if (PH < 1 || PW < 1) return fail(h, SPECMI_ERR_ARG, "a %d x %d panorama", PH, PW);
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<PanoView> tab((size_t)n);
+    int max_tiles = 0;
+    double out_bytes = 0.0;
+    for (int f = 0; f < n; ++f) {
+        const double* v = views + 5 * (size_t)f;
+        const int H = out_hw[2 * f], W = out_hw[2 * f + 1];
+        for (int k = 0; k < 5; ++k)
+            if (!std::isfinite(v[k])) return fail(h, SPECMI_ERR_ARG, "view %d: parameter %d is not finite", f, k);
+        if (!(v[3] > 0.0 && v[3] < 180.0) || !(v[4] > 0.0))
+            return fail(h, SPECMI_ERR_ARG, "view %d: vfov %g degrees (0 < vfov < 180) / ratio %g (> 0)", f, v[3], v[4]);
+        if (H < 1 || W < 1) return fail(h, SPECMI_ERR_ARG, "view %d: size %d x %d", f, H, W);
+        if ((double)H * W >= 2147483648.0 / 3) return fail(h, SPECMI_ERR_ARG, "view %d: %d x %d pixels are beyond 31-bit offsets", f, H, W);
+        if (offsets[f] < 0 || (double)offsets[f] + (double)H * W * 3 > (double)slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "view %d: %d x %d x 3 bytes at offset %lld leave the slab of %zu bytes", f, H, W, (long long)offsets[f], slab_bytes);
+        if (!make_pano_view(v, H, W, (long long)offsets[f], tab[f]))
+            return fail(h, SPECMI_ERR_ARG, "view %d: a height of %d at ratio %g gives a width of round(h * ratio), not %d", f, H, v[4], W);
+        max_tiles = std::max(max_tiles, pano_view_tiles(H, W));
+        out_bytes += (double)H * W * 3;
+    }
+    int rc;
+    const bool regrown = tab.size() * sizeof(PanoView) > h->pano_tab_bytes;
+    if ((rc = grow_ragged(h, (void**)&h->pano_tab, &h->pano_tab_bytes, tab.size() * sizeof(PanoView), "the panorama view table"))) return rc;
+    if (regrown || tab.size() != h->pano_host.size() || std::memcmp(tab.data(), h->pano_host.data(), tab.size() * sizeof(PanoView))) {
+        // an extraction enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
+        if (!regrown && (rc = sync_for_growth(h, "the panorama view table"))) return rc;
+        h->pano_host.swap(tab);
+        HIPCHK(h, hipMemcpyAsync(h->pano_tab, h->pano_host.data(), h->pano_host.size() * sizeof(PanoView), hipMemcpyHostToDevice, s));
+    }
+    LaunchCtx ctx{s, &h->prof, "preprocess.pano_views"};
+    LAUNCHCHK(h, launch_pano_extract(pano, PH, PW, h->pano_tab, n, max_tiles, out_bytes, out_slab, ctx), "pano_extract_views");
     return SPECMI_OK;
 }
 

@@ -108,6 +108,10 @@ struct specmi_handle {
     unsigned char* ragged_tmp = nullptr;
     size_t ragged_tmp_bytes = 0;
     std::vector<int> ragged_host;       // host image of ragged_tab as last uploaded
+    // panorama views (specmi_pano_extract_views): the per-view records, same growth and upload rules as ragged_tab
+    PanoView* pano_tab = nullptr;
+    size_t pano_tab_bytes = 0;
+    std::vector<PanoView> pano_host;    // host image of pano_tab as last uploaded
     SkWs sk;                            // split-K partial tiles + arrival counters (ensure_sk; never allocated under graph capture:
                                         // the warm-up call of a shape sizes it)
     std::vector<void*> sk_retired;      // outgrown split-K buffers, kept until destroy (captured graphs may still name them)

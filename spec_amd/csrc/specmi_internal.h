@@ -399,4 +399,20 @@ constexpr int kRaggedRec = sizeof(RaggedFrame) / 4;
 int launch_resize_normalize_ragged(const unsigned char* frames, const int* tab, unsigned char* tmp, int n, int max_hpass_px,
                                    int Hmax, int Wmax, double src_bytes, double tmp_bytes, float* out, const LaunchCtx& ctx);
 
+// ----------------------------------------------------------------------------------------
+// perspective views out of an equirectangular panorama  (panorama.hip)
+// ----------------------------------------------------------------------------------------
+// What one view fixes, as the device reads it: sin / cos of elevation and roll, numpy.linspace's start / stop / step per
+// axis, the view's byte offset in the output slab and its size
+struct PanoView {
+    double sin_el, cos_el, azimuth, cos_roll, sin_roll, neg_sin_roll, x_start, x_stop, x_step, y_start, y_stop, y_step;
+    long long out_off;
+    int H, W;
+};
+// view = [elevation, azimuth, roll (rad), vfov (deg), ratio]; false: (H, W) is not (H, round(H / (1 / ratio)))
+bool make_pano_view(const double* view, int H, int W, long long out_off, PanoView& pv);
+int pano_view_tiles(int H, int W);      // workgroups a view of this size takes
+int launch_pano_extract(const unsigned char* pano, int PH, int PW, const PanoView* views, int n, int max_tiles, double out_bytes,
+                        unsigned char* out, const LaunchCtx& ctx);
+
 }  // namespace specmi

@@ -356,6 +356,33 @@ class Engine:
             n, Hmax, Wmax, _ptr(out), self._stream()))
         return out
 
+    def pano_extract_views(self, pano, views, out_hw, offsets=None, out=None):
+        """``specmi_pano_extract_views``: ``pano`` = (PH, PW, 3) uint8 device tensor, ``views`` (n, 5) float64 [elevation, azimuth,
+        roll (rad), vfov (deg), ratio], ``out_hw`` (n, 2) - both on the host -> (1-D uint8 device slab, (n,) byte offsets): view f
+        is the (H_f, W_f, 3) block at ``offsets[f]``.  Default offsets pack the views back to back; ``out`` supplies the slab."""
+        if (not isinstance(pano, torch.Tensor) or pano.device != self.device or pano.dtype != torch.uint8 or pano.dim() != 3
+                or pano.shape[2] != 3 or not pano.is_contiguous()):
+            raise ValueError('pano must be a contiguous (PH, PW, 3) uint8 tensor on the engine device')
+        views = np.ascontiguousarray(views, dtype=np.float64).reshape(-1, 5)
+        out_hw = np.ascontiguousarray(out_hw, dtype=np.int32).reshape(-1, 2)
+        n = views.shape[0]
+        if out_hw.shape[0] != n:
+            raise ValueError('one [H, W] row per view')
+        nbytes = out_hw.astype(np.int64).prod(axis=1) * 3
+        if offsets is None:
+            offsets = np.concatenate([[0], np.cumsum(nbytes)[:-1]]) if n else np.zeros(0)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+        if offsets.shape[0] != n:
+            raise ValueError('one offset per view')
+        if out is None:
+            out = torch.empty(int((offsets + nbytes).max()) if n else 0, device=self.device, dtype=torch.uint8)
+        elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError('out must be a contiguous 1-D uint8 device tensor')
+        _lib.check(self.h, self.lib.specmi_pano_extract_views(
+            self.h, _ptr(pano), int(pano.shape[0]), int(pano.shape[1]), views.ctypes.data_as(_lib.c_double_p),
+            out_hw.ctypes.data_as(_lib.c_int32_p), offsets.ctypes.data_as(_lib.c_int64_p), out.numel(), _ptr(out), n, self._stream()))
+        return out, offsets
+
     def _cam_args(self, B, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h):
         d = self.device
         return (_dev_f32(cam_rotmat, d, (B, 3, 3)), _dev_f32(cam_intrinsics, d, (B, 3, 3)),
