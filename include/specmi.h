@@ -194,6 +194,22 @@ int specmi_set_precision(specmi_handle* h, int precision);
 /* the precision last set (what the next commit packs) */
 int specmi_get_precision(specmi_handle* h, int* precision);
 
+/* ---- NHWC8 fp16: the image layout of the fp16 trunk's entrance ------------------------------------------------------------
+ * (B, H, W, 8) fp16, pixel-major, 16 bytes per pixel, device pointer 16-byte aligned.  Channels 0-2 hold fp16_rne(v), v being
+ * the fp32 normalised value the fp32 producer of the same name stores (one rounding to nearest even, nothing else differs);
+ * channels 3-7 hold +0 (bits 0x0000).  Bit for bit what specmi_to_nhwc_f16(x, B, 3, H, W) makes of the fp32 NCHW image, and
+ * what the Cin = 8 stem of the fp16 trunk reads.
+ *   producers: specmi_crop_normalize_batch_f16, specmi_crop_resize_normalize_f16, specmi_resize_normalize_f16,
+ *              specmi_resize_normalize_ragged_f16 - each takes the arguments of its fp32 twin with `void* out_nhwc8` in place of
+ *              the fp32 image; the lane that owns a pixel writes it as one 16-byte vector.  Refused beyond the twin's refusals
+ *              (SPECMI_ERR_ARG): an output that is not 16-byte aligned.
+ *   consumers: specmi_trunk_forward_f16in, specmi_camcalib_forward_f16in, specmi_hmr_forward_f16in - each takes the arguments
+ *              of its twin with `const void* images_nhwc8`: the stem reads the caller's buffer where it lies, no fp32 image
+ *              exists and the conversion launch (to_nhwc_f16) is skipped; everything after the stem is the twin's code, so the
+ *              outputs equal, bit for bit, the twin's on the fp32 producer's image.  Refused, nothing launched, the handle
+ *              serves the next call: SPECMI_ERR_STATE - the handle is not committed at SPECMI_PRECISION_FP16, or has an HRNet
+ *              trunk; SPECMI_ERR_ARG - images_nhwc8 is not 16-byte aligned, H or W below 32. */
+
 /* ---- forward: CamCalib ----------------------------------------------------------------- */
 
 /* (The execution plan - option "plan" above - is chosen from the FIRST handle's options and B, H, W for both trunks.)
@@ -222,6 +238,11 @@ int specmi_camcalib_head_decode(specmi_handle* h, const float* feat_nhwc, int B,
 int specmi_camcalib_forward(specmi_handle* h, const float* images_nchw, int B, int H, int W,
                             float* logits_vfov, float* logits_pitch, float* logits_roll,
                             void* stream);
+/* specmi_camcalib_forward from NHWC8 fp16 images (B,H,W,8) ("NHWC8 fp16" above): replaces the fp32 image + its conversion in
+ * front of the fp16 trunk.  Refuses a handle not committed at SPECMI_PRECISION_FP16 (SPECMI_ERR_STATE), a misaligned
+ * pointer and H / W < 32 (SPECMI_ERR_ARG). */
+int specmi_camcalib_forward_f16in(specmi_handle* h, const void* images_nhwc8, int B, int H, int W,
+                                  float* logits_vfov, float* logits_pitch, float* logits_roll, void* stream);
 
 /* convert_preds_to_angles soft-argmax branch (camcalib/cam_utils.py:114-133), focal length
  * (scripts/camcalib_demo.py:129) and the CamCalib->SPEC hand-off read_cam_params
@@ -279,6 +300,13 @@ int specmi_hmr_forward(specmi_handle* h, const float* images_nchw, int B, int H,
                        const float* cam_rotmat, const float* cam_intrinsics,
                        const float* bbox_scale, const float* bbox_center, const float* img_w,
                        const float* img_h, const specmi_hmr_outputs* out, void* stream);
+/* specmi_hmr_forward from NHWC8 fp16 images (B,H,W,8) ("NHWC8 fp16" above): replaces the fp32 crops + their conversion in
+ * front of the fp16 trunk.  Refuses a handle not committed at SPECMI_PRECISION_FP16 or with an HRNet trunk
+ * (SPECMI_ERR_STATE), a misaligned pointer and H / W < 32 (SPECMI_ERR_ARG). */
+int specmi_hmr_forward_f16in(specmi_handle* h, const void* images_nhwc8, int B, int H, int W,
+                             const float* cam_rotmat, const float* cam_intrinsics,
+                             const float* bbox_scale, const float* bbox_center, const float* img_w,
+                             const float* img_h, const specmi_hmr_outputs* out, void* stream);
 
 /* The two extra outputs of HMR.forward when the model was built with estimate_var = True (spec/models/hmr.py:35-38,57-64; consumed
  * by spec/losses.py:61-62): pred_pose_var (B, 288) = [pred_pose_6d | var_pose], pred_shape_var (B, 20) = [pred_shape | var_shape],
@@ -301,6 +329,12 @@ int specmi_hmr_regress(specmi_handle* h, const float* feat_nhwc, int B, int fh, 
  * layer4 map in NHWC: (B, H/32, W/32, 2048). */
 int specmi_trunk_forward(specmi_handle* h, const float* images_nchw, int B, int H, int W,
                          float* feat_nhwc, void* stream);
+/* specmi_trunk_forward from NHWC8 fp16 images (B,H,W,8) ("NHWC8 fp16" above): the stem reads images_nhwc8 itself, the
+ * to_nhwc_f16 launch and the fp32 image it read are gone.  A batch whose image passes 2 GiB is still cut into launches of
+ * whole images.  Refuses a handle not committed at SPECMI_PRECISION_FP16 or with an HRNet trunk (SPECMI_ERR_STATE), a
+ * misaligned pointer and H / W < 32 (SPECMI_ERR_ARG). */
+int specmi_trunk_forward_f16in(specmi_handle* h, const void* images_nhwc8, int B, int H, int W,
+                               float* feat_nhwc, void* stream);
 
 /* HMRHead.forward on an NHWC feature map (hmr.py:96/98): avg-pool + 3 IEF iterations +
  * rot6d->rotmat.  Outputs any-NULL. */
@@ -385,6 +419,13 @@ int specmi_crop_normalize(specmi_handle* h, const uint8_t* frame_rgb_hwc, int H,
 int specmi_crop_normalize_batch(specmi_handle* h, const uint8_t* frames_rgb_hwc, int nframes, int H, int W,
                                 const int32_t* frame_index, const float* bboxes, int n, float scale, int crop_size,
                                 float* out_nchw, uint8_t* raw_hwc, float* bbox_scale, float* bbox_center, void* stream);
+/* specmi_crop_normalize_batch with the crops stored as NHWC8 fp16 (n,S,S,8) ("NHWC8 fp16" above) instead of (n,3,S,S) fp32:
+ * replaces specmi_crop_normalize[_batch] + specmi_to_nhwc_f16 (the single-frame crop is this call with nframes = 1 and
+ * frame_index = NULL, or an all-zero index; a NULL index with nframes > 1 is refused).  raw_hwc, bbox_scale, bbox_center as in the twin.  Refuses what the twin refuses and an out_nhwc8
+ * that is not 16-byte aligned (SPECMI_ERR_ARG). */
+int specmi_crop_normalize_batch_f16(specmi_handle* h, const uint8_t* frames_rgb_hwc, int nframes, int H, int W,
+                                    const int32_t* frame_index, const float* bboxes, int n, float scale, int crop_size,
+                                    void* out_nhwc8, uint8_t* raw_hwc, float* bbox_scale, float* bbox_center, void* stream);
 
 /* The evaluation dataset's image path (spec/dataset/cam_dataset.py:253-287 rgb_processing with flip 0 / rot 0 / pn 1, :367-377):
  * pare `crop(img, center, scale, [res, res])` = copy of the integer box [ul, br) (zero outside the frame) scaled to res x res
@@ -393,6 +434,10 @@ int specmi_crop_normalize_batch(specmi_handle* h, const uint8_t* frames_rgb_hwc,
  * the host: spec_amd.preprocess.pare_crop_boxes); frame uint8 RGB HWC device; out (n,3,S,S) fp32 NCHW. */
 int specmi_crop_resize_normalize(specmi_handle* h, const uint8_t* frame_rgb_hwc, int H, int W, const int32_t* boxes, int n,
                                  int crop_size, float* out_nchw, void* stream);
+/* specmi_crop_resize_normalize with the crops stored as NHWC8 fp16 (n,S,S,8): replaces it + specmi_to_nhwc_f16.  Refuses
+ * what the twin refuses and an out_nhwc8 that is not 16-byte aligned (SPECMI_ERR_ARG). */
+int specmi_crop_resize_normalize_f16(specmi_handle* h, const uint8_t* frame_rgb_hwc, int H, int W, const int32_t* boxes, int n,
+                                     int crop_size, void* out_nhwc8, void* stream);
 
 /* The CamCalib frame transform (camcalib/pano_dataset.py:156-162, scripts/camcalib_demo.py:100): torchvision
  * Resize(600) on a PIL image = Pillow's antialiased bilinear resample (Image.resize((OW, OH), BILINEAR): separable
@@ -401,6 +446,10 @@ int specmi_crop_resize_normalize(specmi_handle* h, const uint8_t* frame_rgb_hwc,
  * (shorter side 600, longer int(600*long/short)).  Optional raw_hwc: the resized uint8 image (OH,OW,3). */
 int specmi_resize_normalize(specmi_handle* h, const uint8_t* frame_rgb_hwc, int H, int W, int OH, int OW,
                             float* out_chw, uint8_t* raw_hwc, void* stream);
+/* specmi_resize_normalize with the frame stored as NHWC8 fp16 (OH,OW,8): replaces it + specmi_to_nhwc_f16.  Refuses what the
+ * twin refuses and an out_nhwc8 that is not 16-byte aligned (SPECMI_ERR_ARG). */
+int specmi_resize_normalize_f16(specmi_handle* h, const uint8_t* frame_rgb_hwc, int H, int W, int OH, int OW,
+                                void* out_nhwc8, uint8_t* raw_hwc, void* stream);
 
 /* A CamCalib validation batch (camcalib/pano_dataset.py:184-220 Resize(min_size, max_size) per frame, :223-306 collator /
  * to_image_list): n uint8 RGB HWC frames of DIFFERENT sizes in one device slab -> out (n, 3, Hmax, Wmax) fp32 NCHW.  Frame f
@@ -411,6 +460,11 @@ int specmi_resize_normalize(specmi_handle* h, const uint8_t* frame_rgb_hwc, int 
  * is written once (no memset).  Refused: n > 65535, a slab of 4 GiB or more, an output plane of 2^31 elements or more. */
 int specmi_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames_rgb_hwc, size_t slab_bytes, const int64_t* offsets,
                                    const int32_t* geom, int n, int Hmax, int Wmax, float* out_nchw, void* stream);
+/* specmi_resize_normalize_ragged with the batch stored as NHWC8 fp16 (n,Hmax,Wmax,8): replaces it + specmi_to_nhwc_f16.  A
+ * pixel outside its frame's (OH, OW) region is 16 bytes of zero (+0 halves: padding stays zero in normalised space); every
+ * pixel is written once.  Refuses what the twin refuses and an out_nhwc8 that is not 16-byte aligned (SPECMI_ERR_ARG). */
+int specmi_resize_normalize_ragged_f16(specmi_handle* h, const uint8_t* frames_rgb_hwc, size_t slab_bytes, const int64_t* offsets,
+                                       const int32_t* geom, int n, int Hmax, int Wmax, void* out_nhwc8, void* stream);
 
 /* Labelled perspective views out of an equirectangular panorama - the per-pixel work of the reference's dataset generator,
  * extractImage's mode="image" branch (camcalib/datagen/image_extraction.py:129-159, called by makeAndSaveImg,

@@ -64,6 +64,12 @@ def camcalib_eval_section(eng, a, add, g):
     work = f'{n} uint8 frames of 8 sizes (480p .. 1080p, {off / 1e6:.0f} MB) -> Resize(600, 1000) -> ({n},3,{Hmax},{Wmax}) fp32 zero padded'
     ragged = lambda: eng.resize_normalize_ragged(slab, offs, geom, out=out)
     add('camcalib_eval.pad_batch (specmi_resize_normalize_ragged)', work, timed(eng, ragged, a.iters), ('frames_per_s', n))
+    # the same batch stored as NHWC8 fp16 (16 B per pixel in one vector store) - what an fp16 trunk reads without a conversion
+    out16 = torch.empty(n, Hmax, Wmax, 8, device=dev, dtype=torch.float16)
+    ragged16 = lambda: eng.resize_normalize_ragged(slab, offs, geom, out=out16, dtype=torch.float16)
+    add('camcalib_eval.pad_batch (specmi_resize_normalize_ragged_f16)', work.replace(f'({n},3,{Hmax},{Wmax}) fp32', f'({n},{Hmax},{Wmax},8) NHWC8 fp16'),
+        timed(eng, ragged16, a.iters), ('frames_per_s', n))
+    del out16
     frames = [slab[o:o + h * w * 3] for o, (h, w, _, _) in zip(offs, geom)]
     scratch = [torch.empty(3, oh, ow, device=dev) for _, _, oh, ow in geom]
     out2 = torch.empty_like(out)

@@ -2,7 +2,8 @@
 """Throughput of the non-headline model variants of the path, one JSON line each:
 HMR on the HRNet-W32 / W48 trunks (spec/models/hmr.py:44-51) and CamCalib on ResNet-34 (camcalib/config.py:81); ``--fp16``:
 the C3 step (CamCalib + SPEC + SMPL) with the fp16 trunk (TRAINING.USE_AMP) against fp32, timed alternately in one process,
-with a parity block.  Not the BASELINE.json metric (bench.py measures that); numbers quoted in DESIGN.md section 7."""
+with a parity block; ``--f16-input``: the fp16 C3 step from device-resident uint8 frames and boxes, fp32 crops + conversion
+against NHWC8 fp16 crops read by the stem ("Input").  Not the BASELINE.json metric (bench.py measures that); numbers quoted in DESIGN.md section 7."""
 import argparse
 import json
 import os
@@ -36,6 +37,7 @@ def main():
     ap.add_argument('--labels', type=int, default=0, help='also print the N most expensive (kernel, layer group) rows')
     ap.add_argument('--fp16', action='store_true', help='only the fp16-trunk C3 step against fp32 (one JSON line)')
     ap.add_argument('--rounds', type=int, default=3, help='--fp16: alternating fp32 / fp16 timing rounds')
+    ap.add_argument('--f16-input', action='store_true', help='only the fp16 C3 step from uint8 frames: fp32 crops + conversion vs NHWC8 fp16 crops')
     ap.add_argument('--layers', action='store_true', help='--fp16: also print every fp16 trunk launch against its binding roof')
     args = ap.parse_args()
     from spec_amd import assets, synth
@@ -51,6 +53,8 @@ def main():
     R, K = cam_params_from_angles(np.full(B, 0.1, np.float32), np.full(B, -0.05, np.float32), np.full(B, 300., np.float32), iw, ih)
     if args.fp16:
         return fp16_step(args, dev, t, x, sc, ce, iw, ih)
+    if args.f16_input:
+        return f16_input_step(args, dev, t)
     for backbone in ('hrnet_w32-conv', 'hrnet_w32-interp', 'hrnet_w48-conv', 'resnet50'):
         if args.only and backbone not in args.only.split(','):
             continue
@@ -132,6 +136,86 @@ def fp16_step(args, dev, t, x, sc, ce, iw, ih):
                                  'camcalib_angle_deg_max': ang}}), flush=True)
     if args.layers:
         layer_roofs(pipes['fp16'].hmr.engine(dev), x)
+
+
+def f16_input_step(args, dev, t):
+    """The fp16 C3 step STARTING FROM uint8 frames and boxes in HBM (what every caller of the library has): (a) the crops as
+    fp32 NCHW, converted inside each trunk (to_nhwc_f16) - the route before the fp16 entrance existed; (b) the crops as NHWC8 fp16,
+    read by both stems where they lie.  Same models, same frames, alternated in one process (args.rounds rounds of >= 20 steps);
+    the two routes must give the same bits.  (With NHWC8 input SpecPipeline never groups the two trunks into one launch per layer,
+    which it does with fp32 input at B <= 3 and 17-20: run the leg with --batch 2 / 17 to see that difference.)  Also the device
+    memory a 64-frame CamCalib validation batch (ragged producer + forward) holds on both routes, each on a fresh model:
+    growth of the device's used memory (hipMemGetInfo: the library's hipMalloc workspaces and the caller's tensors), not torch's
+    allocator statistics, which do not see the workspaces."""
+    from spec_amd import synth
+    from spec_amd import camcalib_eval as ce
+    from spec_amd.modules import HMR, CameraRegressorNetwork
+    from spec_amd.pipeline import SpecPipeline
+    from spec_amd.preprocess import crop_detections_batch
+    B, F, H, W = args.batch, 32, 720, 1280
+    cc = CameraRegressorNetwork()
+    cc.load_state_dict({k: t(v) for k, v in synth.camcalib_state(1001).items()})
+    hm = HMR(use_cam=True, use_cam_feats=True)
+    hm.load_state_dict({k: t(v) for k, v in synth.hmr_state(1002, True).items()}, strict=False)
+    for m in (cc, hm):
+        m.set_precision('fp16')
+        m.to(dev).eval().commit(dev, freeze=True)
+    pipe = SpecPipeline(cc, hm)
+    g = torch.Generator().manual_seed(7)
+    frames = torch.randint(0, 256, (F, H, W, 3), dtype=torch.uint8, generator=g).to(dev)
+    fidx = (torch.arange(B, dtype=torch.int32) % F).to(dev)
+    u = torch.rand(B, 4, generator=g)
+    boxes = torch.stack([200 + u[:, 0] * (W - 400), 150 + u[:, 1] * (H - 300), 120 + u[:, 2] * 200, 200 + u[:, 3] * 300], 1).to(dev)
+    iw, ih = torch.full((B,), float(W), device=dev), torch.full((B,), float(H), device=dev)
+    bufs = {dt: {'inp_images': (torch.empty(B, 224, 224, 8, device=dev, dtype=dt) if dt == torch.float16 else torch.empty(B, 3, 224, 224, device=dev)),
+                 'bbox_scale': torch.empty(B, device=dev), 'bbox_center': torch.empty(B, 2, device=dev)} for dt in (torch.float32, torch.float16)}
+
+    def step(dt):
+        c = crop_detections_batch(frames, fidx, boxes, crop_size=224, out=bufs[dt], dtype=dt)
+        return pipe(c['inp_images'], c['bbox_scale'], c['bbox_center'], iw, ih)
+
+    steps = max(20, args.steps)
+    routes = {'fp32_crops': torch.float32, 'f16_crops': torch.float16}
+    ms = {k: [] for k in routes}
+    for _ in range(args.rounds):
+        for k, dt in routes.items():
+            ms[k].append(timed(lambda: step(dt), steps))
+    oa = {k: v.clone() for k, v in step(torch.float32).items() if v is not None}
+    ob = step(torch.float16)
+    torch.cuda.synchronize()
+    same = all(torch.equal(oa[k].view(torch.int32), ob[k].view(torch.int32)) for k in oa)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    spread_a = max(ms['fp32_crops']) - min(ms['fp32_crops'])
+    # 64 ragged frames of a CamCalib validation batch (the sizes of profiles/camcalib_eval_aux.json: 600 x 1000 targets)
+    rng = np.random.default_rng(0)
+    val = [rng.integers(0, 256, (720 + 8 * (i % 5), 1200 + 16 * (i % 7), 3), dtype=np.uint8) for i in range(64)]
+    del pipe, hm, cc, frames, bufs, oa, ob
+    used = lambda: (lambda free, total: total - free)(*torch.cuda.mem_get_info(dev))
+    peak = {}
+    for k, dt in routes.items():
+        m = CameraRegressorNetwork()                     # a fresh handle per route: its workspaces start empty
+        m.load_state_dict({kk: t(v) for kk, v in synth.camcalib_state(1001).items()})
+        m.set_precision('fp16'); m.set_plan('throughput')
+        m.to(dev).eval().commit(dev, freeze=True)
+        torch.cuda.synchronize(); torch.cuda.empty_cache()
+        base = used()
+        x = ce.pad_batch(val, 600, 1000, dev, m.engine(dev), dtype=dt)
+        after_producer = used()
+        logits = ce.forward_padded(m, x)
+        torch.cuda.synchronize()
+        peak[k] = {'image_tensor_MB': round(x.numel() * x.element_size() / 1e6, 1), 'padded_shape': list(x.shape),
+                   'device_used_after_producer_MB': round((after_producer - base) / 1e6, 1),
+                   'device_used_after_forward_MB': round((used() - base) / 1e6, 1)}
+        del x, logits
+        m._engine.close(); del m
+        torch.cuda.synchronize(); torch.cuda.empty_cache()
+    print(json.dumps({'variant': 'fp16 C3 step from uint8 frames: fp32 crops + to_nhwc_f16 (a) vs NHWC8 fp16 crops (b)', 'batch': B,
+                      'frames': [F, H, W], 'steps_per_round': steps,
+                      'rounds_ms_a_fp32_crops': [round(v, 3) for v in ms['fp32_crops']], 'rounds_ms_b_f16_crops': [round(v, 3) for v in ms['f16_crops']],
+                      'ms_per_step_a': round(med['fp32_crops'], 3), 'ms_per_step_b': round(med['f16_crops'], 3),
+                      'ratio_b_over_a': round(med['f16_crops'] / med['fp32_crops'], 4), 'round_spread_ms_a': round(spread_a, 3),
+                      'b_not_slower_beyond_spread_of_a': bool(med['f16_crops'] <= med['fp32_crops'] + spread_a),
+                      'outputs_bit_identical': bool(same), 'camcalib_val_batch_64': peak}), flush=True)
 
 
 # binding roofs of MI355X (MI355X_MICROARCH.md): dense fp16 MFMA ~2.5 PF, HBM3E 8.0 TB/s peak

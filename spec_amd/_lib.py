@@ -130,6 +130,21 @@ PROTOTYPES = {
                                           C.c_void_p]),
     'specmi_resize_normalize_ragged': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, c_int32_p, C.c_int, C.c_int, C.c_int,
                                                  C.c_void_p, C.c_void_p]),
+    # NHWC8 fp16 producers / consumers: the prototypes of their fp32 twins (every pointer is a void*)
+    'specmi_crop_normalize_batch_f16': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                                  C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'specmi_crop_resize_normalize_f16': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                   C.c_void_p]),
+    'specmi_resize_normalize_f16': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    'specmi_resize_normalize_ragged_f16': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, c_int32_p, C.c_int, C.c_int, C.c_int,
+                                                     C.c_void_p, C.c_void_p]),
+    'specmi_trunk_forward_f16in': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'specmi_camcalib_forward_f16in': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'specmi_hmr_forward_f16in': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(HmrOutputs), C.c_void_p]),
     'specmi_pano_extract_views': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_double_p, c_int32_p, c_int64_p, C.c_size_t,
                                             C.c_void_p, C.c_int, C.c_void_p]),
     'specmi_camcalib_eval': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,

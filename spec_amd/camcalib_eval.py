@@ -29,6 +29,7 @@ import torch
 
 from . import cam_utils, evaluation
 from .checkpoint import load_pretrained_model, read_checkpoint
+from .engine import flow_image_dtype
 
 # camcalib/config.py:36-87 (the keys the test step reads)
 DEFAULTS = {
@@ -130,14 +131,18 @@ class PanoValDataset:
         return evaluation.read_image_rgb(self.imgname(i))
 
 
-def pad_batch(frames, min_size: int, max_size: Optional[int], device, engine=None) -> torch.Tensor:
+def pad_batch(frames, min_size: int, max_size: Optional[int], device, engine=None, dtype=torch.float32) -> torch.Tensor:
     """Steps 1-2 for one batch: (H_f, W_f, 3) uint8 host frames -> (n, 3, Hmax, Wmax) fp32 on the device (one upload, two
     launches).  ``frames`` may also be ``(slab, offsets, [(H, W)])`` - frames that already lie in a 1-D uint8 device slab
-    (``spec_amd.panorama.PanoViewDataset.device_batch``): nothing is uploaded."""
+    (``spec_amd.panorama.PanoViewDataset.device_batch``): nothing is uploaded.  ``dtype=torch.float16``: the batch in the fp16
+    trunk's NHWC8 layout (n, Hmax, Wmax, 8), padding +0: 16 B per pixel held by the caller instead of 12 B (the library's workspaces are the same on both routes); what it
+    saves is the conversion pass over the batch."""
+    from .engine import out_dtype
+    out_dtype(dtype)                       # ValueError for anything but fp32 / fp16, before the engine is touched
     eng = engine or cam_utils._engine(torch.device(device))
     if isinstance(frames, tuple):
         slab, offsets, sizes = frames
-        return eng.resize_normalize_ragged(slab, offsets, [(H, W) + resize_size(W, H, min_size, max_size) for H, W in sizes])
+        return eng.resize_normalize_ragged(slab, offsets, [(H, W) + resize_size(W, H, min_size, max_size) for H, W in sizes], dtype=dtype)
     geom, offsets, off = [], [], 0
     for fr in frames:
         if fr.dtype != np.uint8 or fr.ndim != 3 or fr.shape[2] != 3:
@@ -148,7 +153,7 @@ def pad_batch(frames, min_size: int, max_size: Optional[int], device, engine=Non
         offsets.append(off)
         off += H * W * 3
     slab = torch.from_numpy(np.concatenate([np.ascontiguousarray(fr).reshape(-1) for fr in frames])).to(eng.device)
-    return eng.resize_normalize_ragged(slab, offsets, geom)
+    return eng.resize_normalize_ragged(slab, offsets, geom, dtype=dtype)
 
 
 def forward_limit(H: int, W: int) -> int:
@@ -161,7 +166,10 @@ def forward_limit(H: int, W: int) -> int:
 def forward_padded(model, images: torch.Tensor, sub_batch: Optional[int] = None):
     """The network on one padded batch, whole images in sub-batches of ``sub_batch`` (default: ``forward_limit``) -> three
     (n, nbins) logit tensors; with the plan pinned the sub-batch size does not change a bit."""
-    n, _, H, W = images.shape
+    if images.dtype == torch.float16:      # NHWC8 (n, H, W, 8): a slice of whole images is contiguous and 16-byte aligned
+        n, H, W, _ = images.shape
+    else:
+        n, _, H, W = images.shape
     step = min(int(sub_batch), forward_limit(H, W)) if sub_batch else forward_limit(H, W)
     if step >= n:
         return [t.clone() for t in model(images)]
@@ -193,7 +201,7 @@ def build_model(hparams: dict, ckpt: Optional[str], data_root: str = '.', device
 
 @torch.no_grad()
 def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = None, log=print, device='cuda', model=None,
-                   sub_batch: Optional[int] = None, dataset=None) -> dict:
+                   sub_batch: Optional[int] = None, dataset=None, _fp32_images: Optional[bool] = None) -> dict:
     """CamCalib's test epoch over ``DATASET.VAL_DS`` - or over ``dataset``, an object with ``PanoValDataset``'s interface such as
     ``spec_amd.panorama.PanoViewDataset``, whose ``device_batch`` hands frames over without a host round trip: consecutive batches of ``DATASET.BATCH_SIZE`` frames in file order, each
     padded to ITS OWN largest height and width, forwarded, scored.  Returns the four epoch figures the reference logs
@@ -204,7 +212,10 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     but not on ``sub_batch`` (how many padded images one trunk call takes).
 
     The kernel takes the ground-truth angles as fp32; for 'ce' / 'kl' the predictions are the float64 bin centres gathered on
-    the host with the kernel's arg-max indices and the accuracies are float64, as in the reference."""
+    the host with the kernel's arg-max indices and the accuracies are float64, as in the reference.
+
+    ``_fp32_images=False``: a model at precision 'fp16' is fed NHWC8 fp16 batches (``pad_batch(dtype=torch.float16)``); True: the
+    fp32 batch + in-trunk conversion (same bits); None = ``engine.F16_CROPS_DEFAULT``."""
     dev = torch.device(device)
     m = hparams['MODEL']
     loss_type = m['LOSS_TYPE']
@@ -228,12 +239,13 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         sizes_hw = frames[2] if on_device else [f.shape[:2] for f in frames]
         gt = np.asarray([ds.labels(i) for i in idx], dtype=np.float64).T              # (3, n): vfov, pitch, roll
         gt32 = gt.astype(np.float32)                                                   # torch.tensor(python float)
-        images = pad_batch(frames, min_res, max_res, dev, eng)
+        images = pad_batch(frames, min_res, max_res, dev, eng, dtype=flow_image_dtype(model, _fp32_images))
         logits = forward_padded(model, images, sub_batch)
+        padded_hw = tuple(images.shape[1:3]) if images.dtype == torch.float16 else tuple(images.shape[2:])
         ev = eng.camcalib_eval(*logits, encode_targets(*gt, loss_type), gt32, loss_type, weights)
         means = ev['means'].cpu().numpy()
         out = {'loss': float(means[0]), 'vfov_loss': float(means[1]), 'pitch_loss': float(means[2]), 'roll_loss': float(means[3]),
-               'n': len(idx), 'padded_hw': tuple(images.shape[2:])}
+               'n': len(idx), 'padded_hw': padded_hw}
         if loss_type in ('ce', 'kl'):
             am = ev['argmax'].cpu().numpy()
             pred = np.stack([centers[k][am[k]] for k in range(3)])                     # float64 bin centres

@@ -532,8 +532,10 @@ static int launch_ops(specmi_handle* ha, specmi_handle* hb, const TrunkPlan& Pa,
 // graph capture).  The image is converted into act[1] (free until the max-pool writes it), every convolution - the stem
 // included - is one conv_f16 launch, and the last one stores fp32 for the heads.  One kernel family at every batch size:
 // plan, Winograd, wave-split / sub-batch options do not apply.
-static int run_trunk_f16(specmi_handle* h, const float* images, int B, int H, int W, float* feat_out, const float** feat,
-                         int* fh, int* fw, hipStream_t s) {
+// images16 != nullptr (the *_f16in entry points): the caller's NHWC8 fp16 image is the stem's input where it lies and the
+// conversion launch is skipped; launch_conv_f16 cuts a batch past 2 GiB into whole images of whichever buffer it is given.
+static int run_trunk_f16(specmi_handle* h, const float* images, const void* images16, int B, int H, int W, float* feat_out,
+                         const float** feat, int* fh, int* fw, hipStream_t s) {
     TrunkPlan P;
     plan_trunk(h, H, W, feat_out != nullptr, P);
     auto buf = [&](int idx) -> void* { return idx == -2 ? static_cast<void*>(feat_out) : static_cast<void*>(h->act[idx]); };
@@ -547,7 +549,9 @@ static int run_trunk_f16(specmi_handle* h, const float* images, int B, int H, in
         }
         ConvF16Args a;
         const ConvW& c = op.kind == 0 ? h->stem : *op.c;
-        if (op.kind == 0) {
+        if (op.kind == 0 && images16) {
+            a.x = images16; a.ldx = 8;
+        } else if (op.kind == 0) {
             LaunchCtx cctx{s, &h->prof, "backbone.input_f16"};
             LAUNCHCHK(h, launch_to_nhwc_f16(images, h->act[1], B, 3, H, W, cctx), "to_nhwc_f16");
             a.x = h->act[1]; a.ldx = 8;
@@ -577,9 +581,16 @@ static int run_trunk_f16(specmi_handle* h, const float* images, int B, int H, in
 // Option "trunk_subbatch" = S > 0: the stem, the max-pool and the first "trunk_subbatch_layers"
 // ResNet stages are run S images at a time (activations of a slice are <= 103 MB at S = 32 and stay
 // resident in the 256 MiB Infinity Cache between layers); later stages see the whole batch.
+// images16 (NHWC8 fp16, include/specmi.h) in place of images: the fp16 ResNet trunk only; refused before anything is allocated or launched.
 static int run_trunk(specmi_handle* h, const float* images, int B, int H, int W, float* feat_out, const float** feat,
-                     int* fh, int* fw, hipStream_t s) {
+                     int* fh, int* fw, hipStream_t s, const void* images16 = nullptr) {
     int rc;
+    if (images16) {
+        if (h->hrnet) return fail(h, SPECMI_ERR_STATE, "fp16 NHWC8 images feed the fp16 ResNet trunk: this handle has an HRNet trunk");
+        if (h->committed_precision != SPECMI_PRECISION_FP16)
+            return fail(h, SPECMI_ERR_STATE, "fp16 NHWC8 images feed the fp16 trunk: commit at SPECMI_PRECISION_FP16 first");
+        if (reinterpret_cast<uintptr_t>(images16) & 15) return fail(h, SPECMI_ERR_ARG, "images_nhwc8 is not 16-byte aligned");
+    }
     if (H < 32 || W < 32) return fail(h, SPECMI_ERR_ARG, "image size %dx%d too small", H, W);
     if ((rc = ensure_ws(h, B, H, W))) return rc;
     if (h->hrnet) {
@@ -587,7 +598,7 @@ static int run_trunk(specmi_handle* h, const float* images, int B, int H, int W,
         *feat = feat_out ? feat_out : hrnet_feat_ws(h);
         return SPECMI_OK;
     }
-    if (h->committed_precision == SPECMI_PRECISION_FP16) return run_trunk_f16(h, images, B, H, W, feat_out, feat, fh, fw, s);
+    if (h->committed_precision == SPECMI_PRECISION_FP16) return run_trunk_f16(h, images, images16, B, H, W, feat_out, feat, fh, fw, s);
     TrunkPlan P;
     plan_trunk(h, H, W, feat_out != nullptr, P);
     const std::vector<TrunkOp>& ops = P.ops;
@@ -913,13 +924,22 @@ int specmi_commit(specmi_handle* h) {
     if ((h)->precision != (h)->committed_precision) \
         return fail(h, SPECMI_ERR_STATE, "the precision changed since the last specmi_commit: commit again");
 
-int specmi_trunk_forward(specmi_handle* h, const float* images, int B, int H, int W, float* feat, void* stream) {
+// specmi_trunk_forward and specmi_trunk_forward_f16in: exactly one of images / images16 is given
+static int trunk_forward(specmi_handle* h, const float* images, const void* images16, int B, int H, int W, float* feat, void* stream) {
     ENTER(h); NEED_COMMIT(h);
-    if (!images || !feat || B <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if ((!images && !images16) || !feat || B <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
     const float* f; int fh, fw;
-    const int rc = run_trunk(h, images, B, H, W, feat, &f, &fh, &fw, (hipStream_t)stream);
+    const int rc = run_trunk(h, images, B, H, W, feat, &f, &fh, &fw, (hipStream_t)stream, images16);
     if (rc) reset_sync_state(h, (hipStream_t)stream);
     return rc;
+}
+
+int specmi_trunk_forward(specmi_handle* h, const float* images, int B, int H, int W, float* feat, void* stream) {
+    return trunk_forward(h, images, nullptr, B, H, W, feat, stream);
+}
+
+int specmi_trunk_forward_f16in(specmi_handle* h, const void* images_nhwc8, int B, int H, int W, float* feat, void* stream) {
+    return trunk_forward(h, nullptr, images_nhwc8, B, H, W, feat, stream);
 }
 
 int specmi_trunk_forward_pair(specmi_handle* ha, specmi_handle* hb, const float* images_a, const float* images_b, int B, int H,
@@ -951,16 +971,26 @@ int specmi_camcalib_head_forward(specmi_handle* h, const float* feat, int B, int
     return run_camcalib_head(h, feat, B, fh, fw, lv, lp, lr, (hipStream_t)stream);
 }
 
-int specmi_camcalib_forward(specmi_handle* h, const float* images, int B, int H, int W, float* lv, float* lp, float* lr,
-                            void* stream) {
+static int camcalib_forward(specmi_handle* h, const float* images, const void* images16, int B, int H, int W, float* lv, float* lp,
+                            float* lr, void* stream) {
     ENTER(h); NEED_COMMIT(h);
     if (h->kind != SPECMI_MODEL_CAMCALIB) return fail(h, SPECMI_ERR_STATE, "handle is not a CamCalib model");
-    if (!images || !lv || !lp || !lr || B <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if ((!images && !images16) || !lv || !lp || !lr || B <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
     hipStream_t s = (hipStream_t)stream;
     const float* f; int fh, fw, rc;
-    if ((rc = run_trunk(h, images, B, H, W, nullptr, &f, &fh, &fw, s)) || (rc = run_camcalib_head(h, f, B, fh, fw, lv, lp, lr, s)))
+    if ((rc = run_trunk(h, images, B, H, W, nullptr, &f, &fh, &fw, s, images16)) || (rc = run_camcalib_head(h, f, B, fh, fw, lv, lp, lr, s)))
         reset_sync_state(h, s);
     return rc;
+}
+
+int specmi_camcalib_forward(specmi_handle* h, const float* images, int B, int H, int W, float* lv, float* lp, float* lr,
+                            void* stream) {
+    return camcalib_forward(h, images, nullptr, B, H, W, lv, lp, lr, stream);
+}
+
+int specmi_camcalib_forward_f16in(specmi_handle* h, const void* images_nhwc8, int B, int H, int W, float* lv, float* lp, float* lr,
+                                  void* stream) {
+    return camcalib_forward(h, nullptr, images_nhwc8, B, H, W, lv, lp, lr, stream);
 }
 
 static int run_camcalib_head(specmi_handle* h, const float* f, int B, int fh, int fw, float* lv, float* lp, float* lr, hipStream_t s) {
@@ -1133,15 +1163,15 @@ int specmi_smpl_native(specmi_handle* h, const float* pose, int pose_is_axis_ang
     return SPECMI_OK;
 }
 
-int specmi_hmr_forward(specmi_handle* h, const float* images, int B, int H, int W, const float* R, const float* K,
+static int hmr_forward(specmi_handle* h, const float* images, const void* images16, int B, int H, int W, const float* R, const float* K,
                        const float* bbox_scale, const float* bbox_center, const float* img_w, const float* img_h,
                        const specmi_hmr_outputs* out, void* stream) {
     ENTER(h); NEED_COMMIT(h);
     if (h->kind != SPECMI_MODEL_HMR) return fail(h, SPECMI_ERR_STATE, "handle is not an HMR model");
-    if (!images || !out || B <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if ((!images && !images16) || !out || B <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
     hipStream_t s = (hipStream_t)stream;
     const float* f; int fh, fw, rc;
-    if ((rc = run_trunk(h, images, B, H, W, nullptr, &f, &fh, &fw, s))) { reset_sync_state(h, s); return rc; }
+    if ((rc = run_trunk(h, images, B, H, W, nullptr, &f, &fh, &fw, s, images16))) { reset_sync_state(h, s); return rc; }
     const OutLd old = out_ld(h);
     HeadFinal fin;
     const bool fuse = (opt_i(h, "head_fuse", 3) & 2) != 0;     // head_final's work inside the SMPL pose kernel (same bits, one node less)
@@ -1151,6 +1181,18 @@ int specmi_hmr_forward(specmi_handle* h, const float* images, int B, int H, int 
                        out->smpl_vertices, out->smpl_joints3d, out->smpl_joints2d, out->pred_cam_t, old, s, fuse ? &fin : nullptr)))
         reset_sync_state(h, s);      // include/specmi.h: the hand-off counters are reset after any forward that returned an error
     return rc;
+}
+
+int specmi_hmr_forward(specmi_handle* h, const float* images, int B, int H, int W, const float* R, const float* K,
+                       const float* bbox_scale, const float* bbox_center, const float* img_w, const float* img_h,
+                       const specmi_hmr_outputs* out, void* stream) {
+    return hmr_forward(h, images, nullptr, B, H, W, R, K, bbox_scale, bbox_center, img_w, img_h, out, stream);
+}
+
+int specmi_hmr_forward_f16in(specmi_handle* h, const void* images_nhwc8, int B, int H, int W, const float* R, const float* K,
+                             const float* bbox_scale, const float* bbox_center, const float* img_w, const float* img_h,
+                             const specmi_hmr_outputs* out, void* stream) {
+    return hmr_forward(h, nullptr, images_nhwc8, B, H, W, R, K, bbox_scale, bbox_center, img_w, img_h, out, stream);
 }
 
 int specmi_hmr_regress(specmi_handle* h, const float* feat, int B, int fh, int fw, const float* R, const float* K,
@@ -1361,10 +1403,15 @@ int specmi_avgpool(specmi_handle* h, const float* x, int B, int HW, int C, float
     return SPECMI_OK;
 }
 
-int specmi_resize_normalize(specmi_handle* h, const uint8_t* frame, int H, int W, int OH, int OW, float* out, uint8_t* raw,
+// every *_f16 producer: the output is NHWC8 fp16 (include/specmi.h), one 16-byte vector per pixel
+#define NEED_ALIGNED16(h, p) \
+    if (reinterpret_cast<uintptr_t>(p) & 15) return fail(h, SPECMI_ERR_ARG, "the NHWC8 fp16 output is not 16-byte aligned");
+
+static int resize_normalize(specmi_handle* h, const uint8_t* frame, int H, int W, int OH, int OW, void* out, bool f16, uint8_t* raw,
                             void* stream) {
     ENTER(h);
     if (!frame || !out || H <= 0 || W <= 0 || OH <= 0 || OW <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if (f16) NEED_ALIGNED16(h, out);
     hipStream_t s = (hipStream_t)stream;
     // tables: [hb (2 OW) | hk (OW ksh) | vb (2 OH) | vk (OH ksv)], rebuilt only when the geometry changes
     std::vector<int> hb, hk, vb, vk;
@@ -1390,8 +1437,18 @@ int specmi_resize_normalize(specmi_handle* h, const uint8_t* frame, int H, int W
     }
     LaunchCtx ctx{s, &h->prof, "resize_normalize"};
     LAUNCHCHK(h, launch_resize_normalize(frame, H, W, OH, OW, h->resize_tab, h->resize_tab + o_hk, ksh, h->resize_tab + o_vb,
-                                         h->resize_tab + o_vk, ksv, out, raw, ctx), "resize_normalize");
+                                         h->resize_tab + o_vk, ksv, out, raw, ctx, f16), "resize_normalize");
     return SPECMI_OK;
+}
+
+int specmi_resize_normalize(specmi_handle* h, const uint8_t* frame, int H, int W, int OH, int OW, float* out, uint8_t* raw,
+                            void* stream) {
+    return resize_normalize(h, frame, H, W, OH, OW, out, false, raw, stream);
+}
+
+int specmi_resize_normalize_f16(specmi_handle* h, const uint8_t* frame, int H, int W, int OH, int OW, void* out_nhwc8, uint8_t* raw,
+                                void* stream) {
+    return resize_normalize(h, frame, H, W, OH, OW, out_nhwc8, true, raw, stream);
 }
 
 // a device buffer of the ragged resize that must hold `need` bytes: kept, or replaced by one at least 1.5x the old size while the
@@ -1407,10 +1464,11 @@ static int grow_ragged(specmi_handle* h, void** buf, size_t* have, size_t need, 
     return SPECMI_OK;
 }
 
-int specmi_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets,
-                                   const int32_t* geom, int n, int Hmax, int Wmax, float* out, void* stream) {
+static int resize_normalize_ragged(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets,
+                                   const int32_t* geom, int n, int Hmax, int Wmax, void* out, bool f16, void* stream) {
     ENTER(h);
     if (!frames || !offsets || !geom || !out || n <= 0 || Hmax <= 0 || Wmax <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if (f16) NEED_ALIGNED16(h, out);
     if (n > 65535) return fail(h, SPECMI_ERR_ARG, "at most 65535 frames per call (grid dimension), got %d", n);
     if (slab_bytes >= 4294967296.0 || (double)Hmax * Wmax >= 2147483648.0)
         return fail(h, SPECMI_ERR_ARG, "a frame slab of %zu bytes / a %d x %d output plane is beyond the kernels' 32-bit offsets", slab_bytes, Hmax, Wmax);
@@ -1457,9 +1515,19 @@ int specmi_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames, size
     }
     LaunchCtx ctx{s, &h->prof, "preprocess.resize_ragged"};
     LAUNCHCHK(h, launch_resize_normalize_ragged(frames, h->ragged_tab, h->ragged_tmp, n, max_hpass, Hmax, Wmax, (double)slab_bytes, (double)tmp_bytes,
-                                                out, ctx),
+                                                out, ctx, f16),
               "resize_normalize_ragged");
     return SPECMI_OK;
+}
+
+int specmi_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets,
+                                   const int32_t* geom, int n, int Hmax, int Wmax, float* out, void* stream) {
+    return resize_normalize_ragged(h, frames, slab_bytes, offsets, geom, n, Hmax, Wmax, out, false, stream);
+}
+
+int specmi_resize_normalize_ragged_f16(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets,
+                                       const int32_t* geom, int n, int Hmax, int Wmax, void* out_nhwc8, void* stream) {
+    return resize_normalize_ragged(h, frames, slab_bytes, offsets, geom, n, Hmax, Wmax, out_nhwc8, true, stream);
 }
 
 int specmi_pano_extract_views(specmi_handle* h, const uint8_t* pano, int PH, int PW, const double* views, const int32_t* out_hw,
@@ -1514,26 +1582,54 @@ int specmi_crop_normalize(specmi_handle* h, const uint8_t* frame, int H, int W, 
     return SPECMI_OK;
 }
 
+static int crop_normalize_batch(specmi_handle* h, const uint8_t* frames, int nframes, int H, int W, const int32_t* frame_index,
+                                const float* bboxes, int n, float scale, int crop_size, void* out, bool f16, uint8_t* raw,
+                                float* bbox_scale, float* bbox_center, void* stream) {
+    ENTER(h);
+    // the fp16 form is also the single-frame crop: frame_index == NULL with nframes == 1 means "every crop from frame 0"
+    const bool single = f16 && !frame_index && nframes == 1;
+    if (!frames || (!frame_index && !single) || !bboxes || !out || nframes <= 0 || H <= 0 || W <= 0 || n <= 0 || crop_size <= 0 || !(scale > 0.f))
+        return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if (f16) NEED_ALIGNED16(h, out);
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "preprocess.crop_batch"};
+    LAUNCHCHK(h, launch_crop_normalize(frames, H, W, bboxes, n, scale, crop_size, out, raw, bbox_scale, bbox_center, ctx,
+                                       frame_index, nframes, f16),
+              "crop_normalize_batch");
+    return SPECMI_OK;
+}
+
 int specmi_crop_normalize_batch(specmi_handle* h, const uint8_t* frames, int nframes, int H, int W, const int32_t* frame_index,
                                 const float* bboxes, int n, float scale, int crop_size, float* out, uint8_t* raw,
                                 float* bbox_scale, float* bbox_center, void* stream) {
+    return crop_normalize_batch(h, frames, nframes, H, W, frame_index, bboxes, n, scale, crop_size, out, false, raw, bbox_scale,
+                                bbox_center, stream);
+}
+
+int specmi_crop_normalize_batch_f16(specmi_handle* h, const uint8_t* frames, int nframes, int H, int W, const int32_t* frame_index,
+                                    const float* bboxes, int n, float scale, int crop_size, void* out_nhwc8, uint8_t* raw,
+                                    float* bbox_scale, float* bbox_center, void* stream) {
+    return crop_normalize_batch(h, frames, nframes, H, W, frame_index, bboxes, n, scale, crop_size, out_nhwc8, true, raw, bbox_scale,
+                                bbox_center, stream);
+}
+
+static int crop_resize_normalize(specmi_handle* h, const uint8_t* frame, int H, int W, const int32_t* boxes, int n, int crop_size,
+                                 void* out, bool f16, void* stream) {
     ENTER(h);
-    if (!frames || !frame_index || !bboxes || !out || nframes <= 0 || H <= 0 || W <= 0 || n <= 0 || crop_size <= 0 || !(scale > 0.f))
-        return fail(h, SPECMI_ERR_ARG, "bad argument");
-    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "preprocess.crop_batch"};
-    LAUNCHCHK(h, launch_crop_normalize(frames, H, W, bboxes, n, scale, crop_size, out, raw, bbox_scale, bbox_center, ctx,
-                                       frame_index, nframes),
-              "crop_normalize_batch");
+    if (!frame || !boxes || !out || H <= 0 || W <= 0 || n <= 0 || crop_size <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if (f16) NEED_ALIGNED16(h, out);
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "preprocess.dataset_crop"};
+    LAUNCHCHK(h, launch_crop_resize_normalize(frame, H, W, boxes, n, crop_size, out, ctx, f16), "crop_resize_normalize");
     return SPECMI_OK;
 }
 
 int specmi_crop_resize_normalize(specmi_handle* h, const uint8_t* frame, int H, int W, const int32_t* boxes, int n,
                                  int crop_size, float* out, void* stream) {
-    ENTER(h);
-    if (!frame || !boxes || !out || H <= 0 || W <= 0 || n <= 0 || crop_size <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
-    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "preprocess.dataset_crop"};
-    LAUNCHCHK(h, launch_crop_resize_normalize(frame, H, W, boxes, n, crop_size, out, ctx), "crop_resize_normalize");
-    return SPECMI_OK;
+    return crop_resize_normalize(h, frame, H, W, boxes, n, crop_size, out, false, stream);
+}
+
+int specmi_crop_resize_normalize_f16(specmi_handle* h, const uint8_t* frame, int H, int W, const int32_t* boxes, int n,
+                                     int crop_size, void* out_nhwc8, void* stream) {
+    return crop_resize_normalize(h, frame, H, W, boxes, n, crop_size, out_nhwc8, true, stream);
 }
 
 int specmi_eval_mesh(specmi_handle* h, const float* pred, const float* gt, int B, int V, const float* Jr, int J,

@@ -27,6 +27,18 @@ namespace specmi {
 // memory latency.  The two horizontally adjacent taps of a row (6 contiguous bytes) come from ONE unaligned 8-byte load.
 constexpr int kPX = 4;
 
+// The fp16 output form of every producer below (template parameter F16; specmi.h "NHWC8 fp16"): the same fp32 value v per
+// channel, rounded once to nearest even, stored as pixel-major (n, H, W, 8) halves - channels 0-2 = fp16(v), 3-7 = +0 - which
+// is what to_nhwc_f16_kernel (conv_f16.hip) makes of the fp32 image and what the Cin = 8 stem reads.  The lane that owns a pixel
+// writes it as ONE 16-byte vector; lanes own consecutive pixels in every kernel here, so a wave stores 1 KiB contiguous
+// (the fp32 form: three 256-byte runs in three colour planes).
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void store_nhwc8(void* __restrict__ out, size_t pixel, const float (&v)[3]) {
+    const f16x8 p = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f,
+                     (_Float16)0.f};
+    reinterpret_cast<f16x8*>(out)[pixel] = p;
+}
+
 // RGB of the pixels c0 and c1 (0 <= c0 <= c1 <= c0 + 1 <= W - 1) of frame row cy.  WIDE needs W >= 2 and total >= 8 bytes.
 template <bool WIDE>
 __device__ __forceinline__ void load_tap_pair(const unsigned char* __restrict__ frame, size_t total, int W, int cy, int c0,
@@ -88,16 +100,17 @@ constexpr int kTabY = 256 * kPX * kNB + 2;     // rows a workgroup's pixels can 
 // once per workgroup with exactly those divisions.  The separable source coordinates (fp64 -> 1/1024 px fixed point) are
 // tabulated too: S columns + the few rows of this workgroup instead of 4 fp64->int64 conversions per pixel.  The
 // per-pixel path is integer arithmetic + three LDS reads + two 8-byte loads.
-template <bool WIDE, bool TABLE>
+template <bool WIDE, bool TABLE, bool F16>
 __global__ void __launch_bounds__(256) crop_normalize_kernel(const unsigned char* __restrict__ frame, int H, int W,
                                                               const float* __restrict__ bboxes, float scale, int S,
-                                                              float* __restrict__ out, unsigned char* __restrict__ raw,
+                                                              void* __restrict__ out_, unsigned char* __restrict__ raw,
                                                               float* __restrict__ bbox_scale,
                                                               float* __restrict__ bbox_center,
                                                               const int* __restrict__ frame_of, size_t frame_stride, int nframes) {
     __shared__ float lut[3][256];
     __shared__ int2 tabx[TABLE ? kTabX : 1], taby[TABLE ? kTabY : 1];
     const int d = blockIdx.y, t = threadIdx.x;
+    float* __restrict__ out = static_cast<float*>(out_);
     // batched: crop d is cut from frame frame_of[d] of a slab of equal-sized frames.  The index comes from caller memory the host
     // side cannot check without a synchronisation: a stale / negative / too large value is clamped into the slab (a wrong crop,
     // never an out-of-bounds read); spec_amd.preprocess.crop_detections_batch rejects it while the index is still on the host
@@ -150,37 +163,43 @@ __global__ void __launch_bounds__(256) crop_normalize_kernel(const unsigned char
         for (int k = 0; k < kPX; ++k) {
             const int idx = idx0 + k * 256;
             if (idx < npix) {
+                float r[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     int v = (__mul24(tap[k][0][c], wgt[k][0]) + __mul24(tap[k][1][c], wgt[k][1]) + __mul24(tap[k][2][c], wgt[k][2]) +
                              __mul24(tap[k][3][c], wgt[k][3]) + (1 << 14)) >> 15;   // taps < 2^8, weights <= 2^15
                     v = v < 0 ? 0 : (v > 255 ? 255 : v);
                     if (raw) raw[((size_t)d * npix + idx) * 3 + c] = (unsigned char)v;
-                    out[(size_t)(d * 3 + c) * npix + idx] = lut[c][v];
+                    r[c] = lut[c][v];
+                    if (!F16) out[(size_t)(d * 3 + c) * npix + idx] = r[c];
                 }
+                if (F16) store_nhwc8(out_, (size_t)d * npix + idx, r);
             }
         }
     }
 }
 
-template <bool WIDE, bool TABLE>
+template <bool WIDE, bool TABLE, bool F16>
 static void crop_normalize_go(dim3 grid, hipStream_t st, const unsigned char* frame, int H, int W, const float* bboxes, float scale,
-                              int S, float* out, unsigned char* raw, float* bbox_scale, float* bbox_center, const int* frame_of,
+                              int S, void* out, unsigned char* raw, float* bbox_scale, float* bbox_center, const int* frame_of,
                               size_t frame_stride, int nframes) {
-    hipLaunchKernelGGL((crop_normalize_kernel<WIDE, TABLE>), grid, dim3(256), 0, st, frame, H, W, bboxes, scale, S, out, raw, bbox_scale,
+    hipLaunchKernelGGL((crop_normalize_kernel<WIDE, TABLE, F16>), grid, dim3(256), 0, st, frame, H, W, bboxes, scale, S, out, raw, bbox_scale,
                        bbox_center, frame_of, frame_stride, nframes);
 }
 
 int launch_crop_normalize(const unsigned char* frame, int H, int W, const float* bboxes, int n, float scale, int S,
-                          float* out, unsigned char* raw, float* bbox_scale, float* bbox_center, const LaunchCtx& ctx,
-                          const int* frame_of, int nframes) {
+                          void* out, unsigned char* raw, float* bbox_scale, float* bbox_center, const LaunchCtx& ctx,
+                          const int* frame_of, int nframes, bool f16) {
     // algorithmic HBM bytes: every frame once + every output once (the 4 taps x 3 channels of a pixel come through L2)
-    ProfScope ps(ctx, "crop_normalize", 0.0, (double)H * W * 3 * (frame_of ? nframes : 1) + (double)n * S * S * (12.0 + (raw ? 3.0 : 0.0)));
+    ProfScope ps(ctx, f16 ? "crop_normalize_f16" : "crop_normalize", 0.0,
+                 (double)H * W * 3 * (frame_of ? nframes : 1) + (double)n * S * S * ((f16 ? 16.0 : 12.0) + (raw ? 3.0 : 0.0)));
     if (H >= (1 << 24) || W >= (1 << 24) || (double)H * W * 3 >= 4294967296.0) return (int)hipErrorInvalidValue;   // 32-bit offsets
     const dim3 grid((S * S + 256 * kPX * kNB - 1) / (256 * kPX * kNB), n);
     const bool wide = W >= 2 && (size_t)H * W * 3 >= 8, table = S <= kTabX;
-    auto go = wide ? (table ? crop_normalize_go<true, true> : crop_normalize_go<true, false>)
-                   : (table ? crop_normalize_go<false, true> : crop_normalize_go<false, false>);
+    auto go = f16 ? (wide ? (table ? crop_normalize_go<true, true, true> : crop_normalize_go<true, false, true>)
+                          : (table ? crop_normalize_go<false, true, true> : crop_normalize_go<false, false, true>))
+                  : (wide ? (table ? crop_normalize_go<true, true, false> : crop_normalize_go<true, false, false>)
+                          : (table ? crop_normalize_go<false, true, false> : crop_normalize_go<false, false, false>));
     if (frame_of && nframes < 1) return (int)hipErrorInvalidValue;
     go(grid, ctx.stream, frame, H, W, bboxes, scale, S, out, raw, bbox_scale, bbox_center, frame_of, (size_t)H * W * 3, nframes);
     return (int)hipGetLastError();
@@ -202,10 +221,11 @@ __device__ __forceinline__ void resize_coord(int i, double scale, int n, int& s0
     if (s0 >= n - 1) { f = 0.f; s0 = n - 1; }
 }
 
-template <bool WIDE, bool TABLE>
+template <bool WIDE, bool TABLE, bool F16>
 __global__ void __launch_bounds__(256) crop_resize_normalize_kernel(const unsigned char* __restrict__ frame, int H, int W,
                                                                      const int* __restrict__ boxes, int S,
-                                                                     float* __restrict__ out) {
+                                                                     void* __restrict__ out_) {
+    float* __restrict__ out = static_cast<float*>(out_);
     __shared__ int txs[TABLE ? kTabX : 1], tys[TABLE ? kTabY : 1];
     __shared__ float txf[TABLE ? kTabX : 1], tyf[TABLE ? kTabY : 1];
     const int d = blockIdx.y, t = threadIdx.x;
@@ -215,8 +235,13 @@ __global__ void __launch_bounds__(256) crop_resize_normalize_kernel(const unsign
     const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
     if (bw <= 0 || bh <= 0) {
         for (int i = pix0 + t; i < min(pix0 + 256 * kPX * kNB, npix); i += 256) {
+            float r[3];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) out[(size_t)(d * 3 + c) * npix + i] = (0.0f - mean[c]) / stdv[c];
+            for (int c = 0; c < 3; ++c) {
+                r[c] = (0.0f - mean[c]) / stdv[c];
+                if (!F16) out[(size_t)(d * 3 + c) * npix + i] = r[c];
+            }
+            if (F16) store_nhwc8(out_, (size_t)d * npix + i, r);
         }
         return;
     }
@@ -263,6 +288,7 @@ __global__ void __launch_bounds__(256) crop_resize_normalize_kernel(const unsign
             const int idx = idx0 + k * 256;
             if (idx < npix) {
                 const double a0 = (double)(1.f - cf[k][0]), a1 = (double)cf[k][0], b0 = (double)(1.f - cf[k][1]), b1 = (double)cf[k][1];
+                float r[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
                     const double p00 = in[k][0] ? (double)tap[k][0][c] : 0.0, p01 = in[k][1] ? (double)tap[k][1][c] : 0.0;
@@ -273,26 +299,31 @@ __global__ void __launch_bounds__(256) crop_resize_normalize_kernel(const unsign
                     double v = __dadd_rn(__dmul_rn(r0, b0), __dmul_rn(r1, b1));             // vertical pass
                     v = fmin(255.0, fmax(0.0, v));                                          // rgb_processing: pn = 1, clip
                     const float tt = (float)v / 255.0f;                                     // astype('float32') / 255.0
-                    out[(size_t)(d * 3 + c) * npix + idx] = (tt - mean[c]) / stdv[c];
+                    r[c] = (tt - mean[c]) / stdv[c];
+                    if (!F16) out[(size_t)(d * 3 + c) * npix + idx] = r[c];
                 }
+                if (F16) store_nhwc8(out_, (size_t)d * npix + idx, r);
             }
         }
     }
 }
 
-template <bool WIDE, bool TABLE>
-static void crop_resize_go(dim3 grid, hipStream_t st, const unsigned char* frame, int H, int W, const int* boxes, int S, float* out) {
-    hipLaunchKernelGGL((crop_resize_normalize_kernel<WIDE, TABLE>), grid, dim3(256), 0, st, frame, H, W, boxes, S, out);
+template <bool WIDE, bool TABLE, bool F16>
+static void crop_resize_go(dim3 grid, hipStream_t st, const unsigned char* frame, int H, int W, const int* boxes, int S, void* out) {
+    hipLaunchKernelGGL((crop_resize_normalize_kernel<WIDE, TABLE, F16>), grid, dim3(256), 0, st, frame, H, W, boxes, S, out);
 }
 
-int launch_crop_resize_normalize(const unsigned char* frame, int H, int W, const int* boxes, int n, int S, float* out,
-                                 const LaunchCtx& ctx) {
-    ProfScope ps(ctx, "crop_resize_normalize", 0.0, (double)H * W * 3 + (double)n * S * S * 12.0);
+int launch_crop_resize_normalize(const unsigned char* frame, int H, int W, const int* boxes, int n, int S, void* out,
+                                 const LaunchCtx& ctx, bool f16) {
+    ProfScope ps(ctx, f16 ? "crop_resize_normalize_f16" : "crop_resize_normalize", 0.0,
+                 (double)H * W * 3 + (double)n * S * S * (f16 ? 16.0 : 12.0));
     if (H >= (1 << 24) || W >= (1 << 24) || (double)H * W * 3 >= 4294967296.0) return (int)hipErrorInvalidValue;   // 32-bit offsets
     const dim3 grid((S * S + 256 * kPX * kNB - 1) / (256 * kPX * kNB), n);
     const bool wide = W >= 2 && (size_t)H * W * 3 >= 8, table = S <= kTabX;
-    auto go = wide ? (table ? crop_resize_go<true, true> : crop_resize_go<true, false>)
-                   : (table ? crop_resize_go<false, true> : crop_resize_go<false, false>);
+    auto go = f16 ? (wide ? (table ? crop_resize_go<true, true, true> : crop_resize_go<true, false, true>)
+                          : (table ? crop_resize_go<false, true, true> : crop_resize_go<false, false, true>))
+                  : (wide ? (table ? crop_resize_go<true, true, false> : crop_resize_go<true, false, false>)
+                          : (table ? crop_resize_go<false, true, false> : crop_resize_go<false, false, false>));
     go(grid, ctx.stream, frame, H, W, boxes, S, out);
     return (int)hipGetLastError();
 }
@@ -365,11 +396,13 @@ __device__ __forceinline__ float to_tensor_normalize(int v, int c) {
     return ((float)v / 255.0f - mean[c]) / stdv[c];
 }
 
+template <bool F16>
 __global__ void __launch_bounds__(256) resize_normalize_kernel(const unsigned char* __restrict__ frame, int H, int W, int OH,
                                                                 int OW, const int* __restrict__ hb, const int* __restrict__ hk,
                                                                 int ksh, const int* __restrict__ vb,
                                                                 const int* __restrict__ vk, int ksv,
-                                                                float* __restrict__ out, unsigned char* __restrict__ raw) {
+                                                                void* __restrict__ out_, unsigned char* __restrict__ raw) {
+    float* __restrict__ out = static_cast<float*>(out_);
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= OH * OW) return;
     const int oy = idx / OW, ox = idx - oy * OW;
@@ -382,19 +415,23 @@ __global__ void __launch_bounds__(256) resize_normalize_kernel(const unsigned ch
 #pragma unroll
         for (int c = 0; c < 3; ++c) acc[c] += v[c] * wv;
     }
+    float r[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int v = pil_clip8(acc[c]);
         if (raw) raw[(size_t)idx * 3 + c] = (unsigned char)v;
-        out[((size_t)c * OH + oy) * OW + ox] = to_tensor_normalize(v, c);
+        r[c] = to_tensor_normalize(v, c);
+        if (!F16) out[((size_t)c * OH + oy) * OW + ox] = r[c];
     }
+    if (F16) store_nhwc8(out_, (size_t)idx, r);
 }
 
 int launch_resize_normalize(const unsigned char* frame, int H, int W, int OH, int OW, const int* hb, const int* hk, int ksh,
-                            const int* vb, const int* vk, int ksv, float* out, unsigned char* raw, const LaunchCtx& ctx) {
-    ProfScope ps(ctx, "resize_normalize", 0.0, (double)H * W * 3 + (double)OH * OW * (12.0 + (raw ? 3.0 : 0.0)));
-    hipLaunchKernelGGL(resize_normalize_kernel, dim3((OH * OW + 255) / 256), dim3(256), 0, ctx.stream, frame, H, W, OH, OW, hb,
-                       hk, ksh, vb, vk, ksv, out, raw);
+                            const int* vb, const int* vk, int ksv, void* out, unsigned char* raw, const LaunchCtx& ctx, bool f16) {
+    ProfScope ps(ctx, f16 ? "resize_normalize_f16" : "resize_normalize", 0.0,
+                 (double)H * W * 3 + (double)OH * OW * ((f16 ? 16.0 : 12.0) + (raw ? 3.0 : 0.0)));
+    hipLaunchKernelGGL(f16 ? resize_normalize_kernel<true> : resize_normalize_kernel<false>, dim3((OH * OW + 255) / 256), dim3(256), 0,
+                       ctx.stream, frame, H, W, OH, OW, hb, hk, ksh, vb, vk, ksv, out, raw);
     return (int)hipGetLastError();
 }
 
@@ -423,9 +460,10 @@ __global__ void __launch_bounds__(256) ragged_hpass_kernel(const unsigned char* 
     for (int c = 0; c < 3; ++c) q[c] = (unsigned char)v[c];
 }
 
+template <bool F16>
 __global__ void __launch_bounds__(256) ragged_vpass_pad_kernel(const unsigned char* __restrict__ frames, const int* __restrict__ tab,
                                                                 const unsigned char* __restrict__ tmp, int Hmax, int Wmax,
-                                                                float* __restrict__ out) {
+                                                                void* __restrict__ out_) {
     const RaggedFrame& fr = reinterpret_cast<const RaggedFrame*>(tab)[blockIdx.y];
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= Hmax * Wmax) return;
@@ -454,21 +492,26 @@ __global__ void __launch_bounds__(256) ragged_vpass_pad_kernel(const unsigned ch
         for (int c = 0; c < 3; ++c) r[c] = to_tensor_normalize(v[c], c);
     }
     const size_t plane = (size_t)Hmax * Wmax;
+    if (F16) {                                                           // padding: 16 bytes of zero (+0 halves)
+        store_nhwc8(out_, (size_t)blockIdx.y * plane + idx, r);
+    } else {
+        float* __restrict__ out = static_cast<float*>(out_);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) out[((size_t)blockIdx.y * 3 + c) * plane + idx] = r[c];
+        for (int c = 0; c < 3; ++c) out[((size_t)blockIdx.y * 3 + c) * plane + idx] = r[c];
+    }
 }
 
 int launch_resize_normalize_ragged(const unsigned char* frames, const int* tab, unsigned char* tmp, int n, int max_hpass_px,
-                                   int Hmax, int Wmax, double src_bytes, double tmp_bytes, float* out, const LaunchCtx& ctx) {
+                                   int Hmax, int Wmax, double src_bytes, double tmp_bytes, void* out, const LaunchCtx& ctx, bool f16) {
     // algorithmic HBM bytes: every frame once, the uint8 rows between the passes written and read once, every output element once
     if (max_hpass_px > 0) {
         ProfScope ps(ctx, "ragged_hpass", 0.0, src_bytes + tmp_bytes);
         hipLaunchKernelGGL(ragged_hpass_kernel, dim3((max_hpass_px + 255) / 256, n), dim3(256), 0, ctx.stream, frames, tab, tmp);
         if (const int rc = (int)hipGetLastError()) return rc;
     }
-    ProfScope ps(ctx, "ragged_vpass_pad", 0.0, 12.0 * n * Hmax * Wmax + tmp_bytes);
-    hipLaunchKernelGGL(ragged_vpass_pad_kernel, dim3((Hmax * Wmax + 255) / 256, n), dim3(256), 0, ctx.stream, frames, tab, tmp, Hmax,
-                       Wmax, out);
+    ProfScope ps(ctx, f16 ? "ragged_vpass_pad_f16" : "ragged_vpass_pad", 0.0, (f16 ? 16.0 : 12.0) * n * Hmax * Wmax + tmp_bytes);
+    hipLaunchKernelGGL(f16 ? ragged_vpass_pad_kernel<true> : ragged_vpass_pad_kernel<false>, dim3((Hmax * Wmax + 255) / 256, n), dim3(256),
+                       0, ctx.stream, frames, tab, tmp, Hmax, Wmax, out);
     return (int)hipGetLastError();
 }
 

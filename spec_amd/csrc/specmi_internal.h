@@ -376,19 +376,20 @@ int launch_rotate_points(const float* R, const float* x, int B, int N, float* ou
 // ----------------------------------------------------------------------------------------
 // crop + normalise  (preprocess.hip)
 // ----------------------------------------------------------------------------------------
+// Every producer: f16 = false -> `out` is the fp32 NCHW image; f16 = true -> `out` is NHWC8 fp16 (include/specmi.h), 16-byte aligned
 // frame_of != nullptr: `frame` is a slab of nframes equal-sized frames and crop d is cut from frame frame_of[d] (device, (n) int32)
 int launch_crop_normalize(const unsigned char* frame, int H, int W, const float* bboxes, int n, float scale, int S,
-                          float* out, unsigned char* raw, float* bbox_scale, float* bbox_center, const LaunchCtx& ctx,
-                          const int* frame_of = nullptr, int nframes = 1);
+                          void* out, unsigned char* raw, float* bbox_scale, float* bbox_center, const LaunchCtx& ctx,
+                          const int* frame_of = nullptr, int nframes = 1, bool f16 = false);
 
 // dataset crop: integer boxes (n,4) [ulx, uly, brx, bry] -> cv2.resize-style bilinear to S x S + ToTensor + Normalize
-int launch_crop_resize_normalize(const unsigned char* frame, int H, int W, const int* boxes, int n, int S, float* out,
-                                 const LaunchCtx& ctx);
+int launch_crop_resize_normalize(const unsigned char* frame, int H, int W, const int* boxes, int n, int S, void* out,
+                                 const LaunchCtx& ctx, bool f16 = false);
 
 // Pillow-exact bilinear resize + ToTensor + Normalize (CamCalib frame transform)
 int pillow_coeffs(int in_size, int out_size, std::vector<int>& bounds, std::vector<int>& kk);
 int launch_resize_normalize(const unsigned char* frame, int H, int W, int OH, int OW, const int* hb, const int* hk, int ksh,
-                            const int* vb, const int* vk, int ksv, float* out, unsigned char* raw, const LaunchCtx& ctx);
+                            const int* vb, const int* vk, int ksv, void* out, unsigned char* raw, const LaunchCtx& ctx, bool f16 = false);
 
 // One frame of a ragged batch as the device reads it (kRaggedRec ints at the head of the table buffer): byte offset of the
 // frame in the slab, source and target size, int offsets of its coefficient tables (pillow_coeffs layout) in the same buffer,
@@ -397,7 +398,8 @@ struct RaggedFrame { unsigned src_off; int H, W, OH, OW, hb, hk, ksh, vb, vk, ks
 constexpr int kRaggedRec = sizeof(RaggedFrame) / 4;
 // max_hpass_px = max over the resampled frames of H * OW (0: no frame is resampled, the horizontal launch is skipped)
 int launch_resize_normalize_ragged(const unsigned char* frames, const int* tab, unsigned char* tmp, int n, int max_hpass_px,
-                                   int Hmax, int Wmax, double src_bytes, double tmp_bytes, float* out, const LaunchCtx& ctx);
+                                   int Hmax, int Wmax, double src_bytes, double tmp_bytes, void* out, const LaunchCtx& ctx,
+                                   bool f16 = false);
 
 // ----------------------------------------------------------------------------------------
 // perspective views out of an equirectangular panorama  (panorama.hip)

@@ -29,6 +29,45 @@ def _dev_f32(t, device, shape=None):
     return t
 
 
+def nhwc8_input(images, precision: str) -> bool:
+    """Is ``images`` the fp16 entrance of the fp16 trunk - a ``torch.float16`` tensor in the NHWC8 layout (B, H, W, 8) of
+    include/specmi.h?  Validation only, no device call: an fp16 tensor of another shape, or one handed to a model whose
+    precision is not 'fp16', raises ``ValueError`` (nothing is converted silently, in either direction)."""
+    if not isinstance(images, torch.Tensor) or images.dtype != torch.float16:
+        return False
+    if images.dim() != 4 or images.shape[3] != 8:
+        raise ValueError(f'fp16 images must be NHWC8, shape (B,H,W,8) (spec_amd.preprocess, dtype=torch.float16), got {tuple(images.shape)}')
+    if precision != 'fp16':
+        raise ValueError("fp16 NHWC8 images feed the fp16 trunk only: call set_precision('fp16') on the model first "
+                         f"(its precision is {precision!r}), or produce fp32 crops")
+    return True
+
+
+# Which route the flows that own their crop buffers (FrameStream, DemoPipeline, SPECTester, the two evaluation flows) take for a
+# model at precision 'fp16': False = fp32 images converted inside the trunk (route (a), DESIGN.md 7b "Input"), True = NHWC8 fp16
+# images read by the stem (route (b)).  Same bits either way; the default follows the measurement quoted there.
+F16_CROPS_DEFAULT = False
+
+
+def flow_image_dtype(module, fp32_crops=None):
+    """The dtype such a flow asks the producers for: ``fp32_crops`` (the flow's private switch) decides, None = the default."""
+    if fp32_crops is None:
+        fp32_crops = not F16_CROPS_DEFAULT
+    return torch.float32 if fp32_crops else getattr(module, 'image_dtype', torch.float32)
+
+
+def out_dtype(dtype):
+    """The ``dtype=`` keyword of the producers: torch.float32 -> the (n,3,H,W) fp32 image, torch.float16 -> NHWC8 fp16."""
+    if dtype not in (torch.float32, torch.float16):
+        raise ValueError(f'dtype must be torch.float32 ((n,3,H,W) images) or torch.float16 (NHWC8 (n,H,W,8) images), got {dtype}')
+    return dtype == torch.float16
+
+
+def image_tensor(n, H, W, device, f16: bool):
+    return (torch.empty(n, H, W, 8, device=device, dtype=torch.float16) if f16 else
+            torch.empty(n, 3, H, W, device=device, dtype=torch.float32))
+
+
 class Engine:
     def __init__(self, kind: str, device: torch.device):
         if device.type != 'cuda':
@@ -180,13 +219,25 @@ class Engine:
     def _images(self, images):
         if not isinstance(images, torch.Tensor) or images.device.type != 'cuda':
             raise RuntimeError('images must be a device tensor (no CPU path in spec_amd)')
+        if images.dtype == torch.float16:
+            raise ValueError('this call takes fp32 (B,3,H,W) images; fp16 NHWC8 images go to trunk / camcalib_forward / hmr_forward')
         if images.dim() != 4 or images.shape[1] != 3:
             raise ValueError(f'images must be (B,3,H,W), got {tuple(images.shape)}')
         return images.to(device=self.device, dtype=torch.float32).contiguous()
 
-    def trunk(self, images):
+    def _images_in(self, images):
+        """-> (contiguous device tensor, B, H, W, f16): fp32 (B,3,H,W), or the fp16 trunk's NHWC8 (B,H,W,8) entrance (f16 = True:
+        the call goes to the ``_f16in`` entry point)."""
+        if isinstance(images, torch.Tensor) and images.dtype == torch.float16 and nhwc8_input(images, self.precision):
+            if images.device.type != 'cuda':
+                raise RuntimeError('images must be a device tensor (no CPU path in spec_amd)')
+            x = images.to(device=self.device).contiguous()
+            return x, x.shape[0], x.shape[1], x.shape[2], True
         x = self._images(images)
-        B, _, H, W = x.shape
+        return x, x.shape[0], x.shape[2], x.shape[3], False
+
+    def trunk(self, images):
+        x, B, H, W, f16 = self._images_in(images)
 
         def o(n, k, s, p):
             return (n + 2 * p - k) // s + 1
@@ -198,7 +249,8 @@ class Engine:
         feat = torch.empty(B, fh, fw, self.feat_channels, device=self.device, dtype=torch.float32)
         if B == 0:
             return feat
-        _lib.check(self.h, self.lib.specmi_trunk_forward(self.h, _ptr(x), B, H, W, _ptr(feat), self._stream()))
+        fn = self.lib.specmi_trunk_forward_f16in if f16 else self.lib.specmi_trunk_forward
+        _lib.check(self.h, fn(self.h, _ptr(x), B, H, W, _ptr(feat), self._stream()))
         return feat
 
     def _feat_shape(self, H, W):
@@ -237,12 +289,12 @@ class Engine:
         return [out[0], out[1], out[2]]
 
     def camcalib_forward(self, images):
-        x = self._images(images)
-        B, _, H, W = x.shape
+        x, B, H, W, f16 = self._images_in(images)
         out = torch.empty(3, B, self.nbins, device=self.device, dtype=torch.float32)
         if B == 0:                      # an empty batch gives empty outputs, as the reference's torch modules do
             return [out[0], out[1], out[2]]
-        _lib.check(self.h, self.lib.specmi_camcalib_forward(
+        fn = self.lib.specmi_camcalib_forward_f16in if f16 else self.lib.specmi_camcalib_forward
+        _lib.check(self.h, fn(
             self.h, _ptr(x), B, H, W, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), self._stream()))
         return [out[0], out[1], out[2]]
 
@@ -335,10 +387,12 @@ class Engine:
                 _ptr(res['argmax']), _ptr(res['soft']), _ptr(res['angle']), _ptr(res['err']), _ptr(res['means']), self._stream()))
         return res
 
-    def resize_normalize_ragged(self, slab, offsets, geom, out=None):
+    def resize_normalize_ragged(self, slab, offsets, geom, out=None, dtype=torch.float32):
         """``specmi_resize_normalize_ragged``: ``slab`` = 1-D uint8 device tensor holding n RGB HWC frames, ``offsets`` (n,) byte
         offsets, ``geom`` (n, 4) [H, W, OH, OW] (both on the host) -> (n, 3, max OH, max OW) fp32, frame f in the top-left
-        corner of its image, exact zeros elsewhere."""
+        corner of its image, exact zeros elsewhere.  ``dtype=torch.float16``: (n, max OH, max OW, 8) NHWC8 fp16
+        (``specmi_resize_normalize_ragged_f16``), the same values rounded once."""
+        f16 = out_dtype(dtype)
         if not isinstance(slab, torch.Tensor) or slab.device.type != 'cuda' or slab.dtype != torch.uint8 or slab.dim() != 1:
             raise ValueError('slab must be a 1-D uint8 device tensor')
         offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
@@ -347,11 +401,13 @@ class Engine:
         if n < 1 or offsets.shape[0] != n:
             raise ValueError('one offset and one [H, W, OH, OW] row per frame (at least one frame)')
         Hmax, Wmax = int(geom[:, 2].max()), int(geom[:, 3].max())
+        shape = (n, Hmax, Wmax, 8) if f16 else (n, 3, Hmax, Wmax)
         if out is None:
-            out = torch.empty(n, 3, Hmax, Wmax, device=self.device, dtype=torch.float32)
-        elif tuple(out.shape) != (n, 3, Hmax, Wmax) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f'out must be a contiguous ({n},3,{Hmax},{Wmax}) fp32 device tensor')
-        _lib.check(self.h, self.lib.specmi_resize_normalize_ragged(
+            out = image_tensor(n, Hmax, Wmax, self.device, f16)
+        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f'out must be a contiguous {shape} {dtype} device tensor')
+        fn = self.lib.specmi_resize_normalize_ragged_f16 if f16 else self.lib.specmi_resize_normalize_ragged
+        _lib.check(self.h, fn(
             self.h, _ptr(slab.contiguous()), slab.numel(), offsets.ctypes.data_as(_lib.c_int64_p), geom.ctypes.data_as(_lib.c_int32_p),
             n, Hmax, Wmax, _ptr(out), self._stream()))
         return out
@@ -410,15 +466,15 @@ class Engine:
     def hmr_forward(self, images, cam_rotmat=None, cam_intrinsics=None, bbox_scale=None,
                     bbox_center=None, img_w=None, img_h=None, out: Optional[Dict[str, torch.Tensor]] = None,
                     record: Optional[torch.Tensor] = None):
-        x = self._images(images)
-        B, _, H, W = x.shape
+        x, B, H, W, f16 = self._images_in(images)
         R, K, sc, ce, iw, ih = self._cam_args(B, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h)
         views = self._out_for(B, record)
         out = views if views is not None else (out if out is not None else self._hmr_outputs(B))
         if B == 0:
             return out
         o = _lib.HmrOutputs(**{k: out[k].data_ptr() for k, _ in _lib.HmrOutputs._fields_})
-        _lib.check(self.h, self.lib.specmi_hmr_forward(
+        fn = self.lib.specmi_hmr_forward_f16in if f16 else self.lib.specmi_hmr_forward
+        _lib.check(self.h, fn(
             self.h, _ptr(x), B, H, W, _ptr(R), _ptr(K), _ptr(sc), _ptr(ce), _ptr(iw), _ptr(ih),
             C.byref(o), self._stream()))
         return out

@@ -27,6 +27,7 @@ import torch
 from . import assets, io_formats, metrics
 from .cam_utils import cam_params_from_angles
 from .checkpoint import load_pretrained_model, read_checkpoint
+from .engine import flow_image_dtype
 from .preprocess import dataset_crops
 
 # spec/config.py:34-56
@@ -101,13 +102,14 @@ class EvalDataset:
     def __len__(self):
         return self.n
 
-    def batch(self, idx, device, img_res=224, use_gt_cam=False) -> Dict[str, torch.Tensor]:
+    def batch(self, idx, device, img_res=224, use_gt_cam=False, dtype=torch.float32) -> Dict[str, torch.Tensor]:
+        """``dtype``: what the crops are stored as (``spec_amd.preprocess``: fp32 (n,3,S,S), or NHWC8 fp16 for an fp16 model)."""
         d = self.data
         crops, shapes = [], []
         for i in idx:
             frame = torch.from_numpy(read_image_rgb(os.path.join(self.img_dir, str(self.imgname[i])))).to(device)
             H, W = frame.shape[:2]
-            crops.append(dataset_crops(frame, d['center'][i:i + 1], d['scale'][i:i + 1], img_res))   # cam_dataset.py:367-377
+            crops.append(dataset_crops(frame, d['center'][i:i + 1], d['scale'][i:i + 1], img_res, dtype=dtype))   # cam_dataset.py:367-377
             shapes.append((H, W))
         shapes = np.asarray(shapes, np.float32)
         f = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32).to(device)
@@ -166,7 +168,7 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         dump = io_formats.EvalDump()
         for b0 in range(0, n, bs):
             idx = np.arange(b0, min(n, b0 + bs))
-            b = ds.batch(idx, dev, hparams['DATASET']['IMG_RES'], bool(hparams['TESTING']['USE_GT_CAM']))
+            b = ds.batch(idx, dev, hparams['DATASET']['IMG_RES'], bool(hparams['TESTING']['USE_GT_CAM']), dtype=flow_image_dtype(hm))
             # positional call of spec/trainer.py:139
             pred = hm(b['img'], b['cam_rotmat'], b['cam_int'], b['scale'], b['center'], b['img_w'], b['img_h'])
             dump.add(pred, imgnames=b['imgname'], dataset_name=name)

@@ -19,15 +19,19 @@ from typing import Callable, Optional
 
 import torch
 
+from .engine import flow_image_dtype, image_tensor
 from .preprocess import crop_detections_batch
 
 
 class FrameStream:
     def __init__(self, step: Callable, device, frame_hw, frames_per_step: int, crops_per_step: int, crop_size: int = 224,
-                 slots: int = 2, scale: float = 1.0, copy_stream: Optional[torch.cuda.Stream] = None):
+                 slots: int = 2, scale: float = 1.0, copy_stream: Optional[torch.cuda.Stream] = None, _fp32_crops: Optional[bool] = None):
         """``step(images, bbox_scale, bbox_center, img_w, img_h)`` is a ``SpecPipeline`` or ``GraphedPipeline``.  When it
         has ``static_in`` (a captured graph) the crops are written directly into those buffers.  ``copy_stream``: the
-        stream of the uploads; by default one is chosen by measurement (``_pick_copy_stream``)."""
+        stream of the uploads; by default one is chosen by measurement (``_pick_copy_stream``).
+        The crops are cut in the layout the step reads: that of a captured step's static buffers, else ``step.image_dtype``
+        (``SpecPipeline``: NHWC8 fp16 when both models run at fp16 - no fp32 crop tensor exists then) with ``_fp32_crops=False``,
+        fp32 crops + in-trunk conversion with True (same bits); None = ``engine.F16_CROPS_DEFAULT``."""
         self.step, self.device = step, torch.device(device)
         self.H, self.W = int(frame_hw[0]), int(frame_hw[1])
         self.F, self.N, self.S, self.scale = int(frames_per_step), int(crops_per_step), int(crop_size), float(scale)
@@ -37,12 +41,14 @@ class FrameStream:
         self.fidx = [torch.empty(self.N, dtype=torch.int32, device=dev) for _ in range(slots)]
         static = getattr(step, 'static_in', None)
         if static is not None:
-            if static[0].shape != (self.N, 3, self.S, self.S):
-                raise ValueError(f'the captured step takes {tuple(static[0].shape)} crops, FrameStream was asked for '
-                                 f'{(self.N, 3, self.S, self.S)}')
+            self.dtype = static[0].dtype
+            want = (self.N, self.S, self.S, 8) if self.dtype == torch.float16 else (self.N, 3, self.S, self.S)
+            if static[0].shape != want:
+                raise ValueError(f'the captured step takes {tuple(static[0].shape)} crops, FrameStream was asked for {want}')
             self.x, self.sc, self.ce, self.img_w, self.img_h = static
         else:
-            self.x = torch.empty(self.N, 3, self.S, self.S, dtype=torch.float32, device=dev)
+            self.dtype = flow_image_dtype(step, _fp32_crops)
+            self.x = image_tensor(self.N, self.S, self.S, dev, self.dtype == torch.float16)
             self.sc = torch.empty(self.N, dtype=torch.float32, device=dev)
             self.ce = torch.empty(self.N, 2, dtype=torch.float32, device=dev)
             self.img_w = torch.empty(self.N, dtype=torch.float32, device=dev)
@@ -93,7 +99,7 @@ class FrameStream:
             self.ready[i].record(self.copy_stream)
         self.h2d_bytes += frames_host.numel() + boxes_host.numel() * 4 + fidx_host.numel() * 4
         main.wait_event(self.ready[i])
-        crop_detections_batch(self.slabs[i], self.fidx[i], self.boxes[i], scale=self.scale, crop_size=self.S,
+        crop_detections_batch(self.slabs[i], self.fidx[i], self.boxes[i], scale=self.scale, crop_size=self.S, dtype=self.dtype,
                               out={'inp_images': self.x, 'bbox_scale': self.sc, 'bbox_center': self.ce})
         ev = torch.cuda.Event()
         ev.record(main)

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import assets
-from .engine import Engine
+from .engine import Engine, nhwc8_input
 
 
 # --------------------------------------------------------------------------------------------
@@ -382,6 +382,19 @@ class _EngineModule(nn.Module):
     def _smpl_model(self):
         return None
 
+    # The fp16 trunk's own entrance: ``forward`` also takes a torch.float16 tensor in the NHWC8 layout (B, H, W, 8) that
+    # spec_amd.preprocess writes with dtype=torch.float16 - the stem reads it where it lies (include/specmi.h, the ``_f16in`` entry
+    # points), same bits as the fp32 image of the same producer.  Checked here, before any device call: an fp16 tensor on a module
+    # whose precision is 'fp32', or of another shape, raises ValueError (no silent conversion in either direction).
+    def _check_images(self, images):
+        nhwc8_input(images, self.precision)
+
+    @property
+    def image_dtype(self):
+        """The dtype the producers of spec_amd.preprocess should write for this module: torch.float16 (NHWC8) when its trunk
+        runs at fp16, else torch.float32."""
+        return torch.float16 if self.precision == 'fp16' else torch.float32
+
     def commit(self, device=None, freeze=False):
         """(Re)build the packed HBM copy of the parameters.  ``freeze=True`` skips the
         per-forward change check afterwards (serving / benchmark loops)."""
@@ -463,6 +476,7 @@ class CameraRegressorNetwork(_EngineModule):
 
     @torch.no_grad()
     def forward(self, images):
+        self._check_images(images)
         return self.engine(images.device).camcalib_forward(images)
 
 
@@ -535,6 +549,7 @@ class HMR(_EngineModule):
     @torch.no_grad()
     def forward(self, images, cam_rotmat=None, cam_intrinsics=None, bbox_scale=None, bbox_center=None,
                 img_w=None, img_h=None):
+        self._check_images(images)
         eng = self.engine(images.device)
         if self.use_cam:
             out = eng.hmr_forward(images, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h)

@@ -53,6 +53,14 @@ class SpecPipeline:
         self.grouped = grouped
         self._side = {}
 
+    @property
+    def image_dtype(self):
+        """What a caller that cuts the crops for this step should ask the producers for (``spec_amd.preprocess``, ``dtype=``):
+        torch.float16 - NHWC8 (B,S,S,8), read by both fp16 trunks where it lies - when both models run at precision 'fp16',
+        else torch.float32 (B,3,S,S)."""
+        both = (self.camcalib, self.hmr)
+        return torch.float16 if all(getattr(m, 'precision', 'fp32') == 'fp16' for m in both) else torch.float32
+
     @staticmethod
     def auto_groups(nb: int) -> bool:
         """grouped='auto': both trunks per layer as one grouped launch at this batch size?"""
@@ -100,7 +108,9 @@ class SpecPipeline:
                  record: torch.Tensor = None) -> Dict[str, torch.Tensor]:
         """``images``: (B,3,224,224) crops for SPEC.  ``camcalib_images``: what CamCalib sees
         (the full frame in the reference demo; defaults to the same crops, as in the benchmark).
-        ``record``: optional caller-owned (B, record_floats) fp32 tensor to write the packed outputs into."""
+        ``record``: optional caller-owned (B, record_floats) fp32 tensor to write the packed outputs into.
+        With both models at precision 'fp16', ``images`` / ``camcalib_images`` may be NHWC8 fp16 (B,H,W,8) tensors
+        (``image_dtype``): each trunk then reads them directly (its own launches: grouped launches take fp32 images; same bits)."""
         cam_in = images if camcalib_images is None else camcalib_images
         device = images.device
         eng = self.hmr.engine(device)
@@ -110,7 +120,10 @@ class SpecPipeline:
         if record is not None:
             v = eng.record_views(record)
             angles = (v['cam_vfov'], v['cam_pitch'], v['cam_roll'])
-        can_group = self._can_group(tuple(images.shape), tuple(cam_in.shape))
+        nhwc8 = images.dtype == torch.float16
+        if (cam_in.dtype == torch.float16) != nhwc8:
+            raise ValueError('images and camcalib_images must use one layout: both fp32 (B,3,H,W) or both NHWC8 fp16 (B,H,W,8)')
+        can_group = not nhwc8 and self._can_group(tuple(images.shape), tuple(cam_in.shape))
         if can_group:
             ceng = self.camcalib.engine(device)
             cfeat, feat = ceng.trunk_pair(eng, cam_in, images)
@@ -160,7 +173,8 @@ class GraphedPipeline:
         """``buffers`` > 1 captures that many graphs, each writing its own static output set, replayed round-robin:
         a consumer (e.g. the asynchronous all-gather of step s) may still read buffer s % buffers while step s+1
         runs."""
-        self.static_in = [t.clone() for t in (images, bbox_scale, bbox_center, img_w, img_h)]
+        self.static_in = [t.clone() for t in (images, bbox_scale, bbox_center, img_w, img_h)]     # images: fp32 NCHW or NHWC8 fp16, as given
+        self.image_dtype = self.static_in[0].dtype
         for _ in range(warmup):                      # allocates workspaces, sets kernel attributes
             pipeline(*self.static_in)
         torch.cuda.synchronize()
@@ -204,6 +218,9 @@ class DemoPipeline:
     def __init__(self, camcalib, hmr, min_size: int = 600, crop_size: int = 224, overlap: bool = True):
         self.camcalib, self.hmr, self.min_size, self.crop_size, self.overlap = camcalib, hmr, int(min_size), int(crop_size), overlap
         self._side = {}
+        # the step owns its frame and crop tensors: False = a model at precision 'fp16' gets them as NHWC8 fp16 (no fp32 image, no
+        # conversion launch), True = fp32 images + in-trunk conversion (same bits), None = engine.F16_CROPS_DEFAULT
+        self._fp32_crops = None
 
     @torch.no_grad()
     def __call__(self, frames_u8, boxes, frame_index, record: torch.Tensor = None) -> Dict[str, torch.Tensor]:
@@ -216,9 +233,12 @@ class DemoPipeline:
         angles = None
         fh = torch.full((F,), float(H), device=device)
         fw = torch.full((F,), float(W), device=device)
+        from .engine import flow_image_dtype
+        cam_dtype = flow_image_dtype(self.camcalib, self._fp32_crops)
+        crop_dtype = flow_image_dtype(self.hmr, self._fp32_crops)
 
         def cam_side():
-            cam_in = camcalib_transform_batch(frames_u8, self.min_size)
+            cam_in = camcalib_transform_batch(frames_u8, self.min_size, dtype=cam_dtype)
             logits = self.camcalib(cam_in)
             return cam_utils.decode_camera(logits[0], logits[1], logits[2], img_h=fh, img_w=fw)
 
@@ -230,7 +250,7 @@ class DemoPipeline:
             side.wait_stream(main)
             with torch.cuda.stream(side):
                 cam = cam_side()
-        crops = crop_detections_batch(frames_u8, frame_index, boxes, scale=1.0, crop_size=self.crop_size)
+        crops = crop_detections_batch(frames_u8, frame_index, boxes, scale=1.0, crop_size=self.crop_size, dtype=crop_dtype)
         feat = eng.trunk(crops['inp_images'])
         if self.overlap:
             main.wait_stream(side)

@@ -2,22 +2,29 @@
 
 Crop + normalise: the detection loop of ``spec/tester.py:116-128``
 (``get_single_image_crop_demo`` per bbox, ``bbox_scale = bbox[2]/200``, ``bbox_center``) as one
-HIP launch (``specmi_crop_normalize``) from a uint8 RGB frame that already sits in HBM."""
+HIP launch (``specmi_crop_normalize``) from a uint8 RGB frame that already sits in HBM.
+
+Every producer takes ``dtype=torch.float32`` (the (n,3,H,W) image the reference builds) or ``dtype=torch.float16``: the same
+values rounded once to fp16 in the NHWC8 layout (n,H,W,8) the fp16 trunk reads (include/specmi.h, the ``_f16`` exports) - bit
+for bit what the fp32 image becomes inside an fp16 forward, without the fp32 image.  Any other dtype raises ``ValueError``."""
 from __future__ import annotations
 
 import torch
 
 from . import _lib
 from .cam_utils import _engine
-from .engine import _dev_f32, _ptr
+from .engine import _dev_f32, _ptr, image_tensor, out_dtype
 
 
 @torch.no_grad()
-def crop_detections(frame_rgb_u8, dets, scale: float = 1.0, crop_size: int = 224, return_raw: bool = False, out=None):
+def crop_detections(frame_rgb_u8, dets, scale: float = 1.0, crop_size: int = 224, return_raw: bool = False, out=None,
+                    dtype=torch.float32):
     """frame (H,W,3) uint8 device tensor, dets (n,4) [cx, cy, w, h] ->
     dict(inp_images (n,3,S,S) fp32, bbox_scale (n,), bbox_center (n,2)[, raw (n,S,S,3) uint8]).
     ``out``: optional dict of preallocated contiguous tensors (``inp_images``, ``bbox_scale``, ``bbox_center`` - e.g. slices
-    of a larger batch buffer) to write into instead of allocating."""
+    of a larger batch buffer) to write into instead of allocating.  ``dtype=torch.float16``: ``inp_images`` is (n,S,S,8) NHWC8
+    fp16 (the batch call with one frame)."""
+    f16 = out_dtype(dtype)
     if not isinstance(frame_rgb_u8, torch.Tensor) or frame_rgb_u8.device.type != 'cuda':
         raise RuntimeError('crop_detections needs a device tensor (no CPU path in spec_amd)')
     if frame_rgb_u8.dtype != torch.uint8 or frame_rgb_u8.dim() != 3 or frame_rgb_u8.shape[2] != 3:
@@ -29,9 +36,12 @@ def crop_detections(frame_rgb_u8, dets, scale: float = 1.0, crop_size: int = 224
     if boxes.dim() != 2 or boxes.shape[1] != 4:
         raise ValueError('dets must be (n,4) [cx, cy, w, h]')
     n, (H, W) = boxes.shape[0], frame.shape[:2]
-    img, sc, ce = _crop_outputs(out, n, crop_size, dev)
+    img, sc, ce = _crop_outputs(out, n, crop_size, dev, f16)
     raw = torch.empty(n, crop_size, crop_size, 3, device=dev, dtype=torch.uint8) if return_raw else None
-    if n > 0:
+    if n > 0 and f16:       # one frame, no index (NULL = every crop from frame 0)
+        _lib.check(eng.h, eng.lib.specmi_crop_normalize_batch_f16(eng.h, _ptr(frame), 1, H, W, None, _ptr(boxes), n, float(scale),
+                                                                  crop_size, _ptr(img), _ptr(raw), _ptr(sc), _ptr(ce), eng._stream()))
+    elif n > 0:
         _lib.check(eng.h, eng.lib.specmi_crop_normalize(eng.h, _ptr(frame), H, W, _ptr(boxes), n, float(scale), crop_size,
                                                         _ptr(img), _ptr(raw), _ptr(sc), _ptr(ce), eng._stream()))
     res = {'inp_images': img, 'bbox_scale': sc, 'bbox_center': ce}
@@ -40,22 +50,25 @@ def crop_detections(frame_rgb_u8, dets, scale: float = 1.0, crop_size: int = 224
     return res
 
 
-def _crop_outputs(out, n, crop_size, dev):
+def _crop_outputs(out, n, crop_size, dev, f16=False):
     if out is None:
-        return (torch.empty(n, 3, crop_size, crop_size, device=dev, dtype=torch.float32),
+        return (image_tensor(n, crop_size, crop_size, dev, f16),
                 torch.empty(n, device=dev, dtype=torch.float32), torch.empty(n, 2, device=dev, dtype=torch.float32))
     img, sc, ce = out['inp_images'], out['bbox_scale'], out['bbox_center']
-    for t_, shp in ((img, (n, 3, crop_size, crop_size)), (sc, (n,)), (ce, (n, 2))):
-        if tuple(t_.shape) != shp or t_.dtype != torch.float32 or not t_.is_contiguous() or t_.device != dev:
-            raise ValueError(f'out tensor must be a contiguous fp32 device tensor of shape {shp}, got {tuple(t_.shape)} {t_.dtype}')
+    img_shape = (n, crop_size, crop_size, 8) if f16 else (n, 3, crop_size, crop_size)
+    for t_, shp, dt in ((img, img_shape, torch.float16 if f16 else torch.float32), (sc, (n,), torch.float32), (ce, (n, 2), torch.float32)):
+        if tuple(t_.shape) != shp or t_.dtype != dt or not t_.is_contiguous() or t_.device != dev:
+            raise ValueError(f'out tensor must be a contiguous {dt} device tensor of shape {shp}, got {tuple(t_.shape)} {t_.dtype}')
     return img, sc, ce
 
 
 @torch.no_grad()
-def crop_detections_batch(frames_u8, frame_index, dets, scale: float = 1.0, crop_size: int = 224, out=None):
+def crop_detections_batch(frames_u8, frame_index, dets, scale: float = 1.0, crop_size: int = 224, out=None, dtype=torch.float32):
     """The detections of MANY equal-sized frames in one launch (``specmi_crop_normalize_batch``): ``frames_u8`` (F,H,W,3) uint8
     device slab, ``frame_index`` (n,) int32 (which frame each detection belongs to), ``dets`` (n,4) [cx, cy, w, h] -> the same
-    dict as ``crop_detections`` for all n crops, bit-identical to cutting them frame by frame."""
+    dict as ``crop_detections`` for all n crops, bit-identical to cutting them frame by frame.  ``dtype=torch.float16``:
+    ``inp_images`` is (n,S,S,8) NHWC8 fp16 (``specmi_crop_normalize_batch_f16``)."""
+    f16 = out_dtype(dtype)
     if not isinstance(frames_u8, torch.Tensor) or frames_u8.device.type != 'cuda':
         raise RuntimeError('crop_detections_batch needs a device tensor (no CPU path in spec_amd)')
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
@@ -77,11 +90,11 @@ def crop_detections_batch(frames_u8, frame_index, dets, scale: float = 1.0, crop
     fidx = fidx.to(device=dev, dtype=torch.int32).contiguous()
     if fidx.shape != (n,):
         raise ValueError('frame_index must have one entry per detection')
-    img, sc, ce = _crop_outputs(out, n, crop_size, dev)
+    img, sc, ce = _crop_outputs(out, n, crop_size, dev, f16)
     if n > 0:
-        _lib.check(eng.h, eng.lib.specmi_crop_normalize_batch(eng.h, _ptr(frames_u8), F, H, W, _ptr(fidx), _ptr(boxes), n,
-                                                              float(scale), crop_size, _ptr(img), None, _ptr(sc), _ptr(ce),
-                                                              eng._stream()))
+        fn = eng.lib.specmi_crop_normalize_batch_f16 if f16 else eng.lib.specmi_crop_normalize_batch
+        _lib.check(eng.h, fn(eng.h, _ptr(frames_u8), F, H, W, _ptr(fidx), _ptr(boxes), n, float(scale), crop_size, _ptr(img), None, _ptr(sc),
+                             _ptr(ce), eng._stream()))
     return {'inp_images': img, 'bbox_scale': sc, 'bbox_center': ce}
 
 
@@ -112,10 +125,11 @@ def pare_crop_boxes(centers, scales, res: int = 224):
 
 
 @torch.no_grad()
-def dataset_crops(frame_rgb_u8, centers, scales, crop_size: int = 224):
+def dataset_crops(frame_rgb_u8, centers, scales, crop_size: int = 224, dtype=torch.float32):
     """The evaluation dataset's image path on the device (spec/dataset/cam_dataset.py:253-287,367-377): pare ``crop`` (integer
     box copy + cv2.resize bilinear) + clip + ``/ 255`` + ImageNet Normalize.  frame (H,W,3) uint8 device tensor, centers (n,2),
-    scales (n,) (bbox height / 200) -> (n,3,S,S) fp32."""
+    scales (n,) (bbox height / 200) -> (n,3,S,S) fp32, or (n,S,S,8) NHWC8 fp16 with ``dtype=torch.float16``."""
+    f16 = out_dtype(dtype)
     if not isinstance(frame_rgb_u8, torch.Tensor) or frame_rgb_u8.device.type != 'cuda':
         raise RuntimeError('dataset_crops needs a device tensor (no CPU path in spec_amd)')
     if frame_rgb_u8.dtype != torch.uint8 or frame_rgb_u8.dim() != 3 or frame_rgb_u8.shape[2] != 3:
@@ -124,9 +138,9 @@ def dataset_crops(frame_rgb_u8, centers, scales, crop_size: int = 224):
     frame = frame_rgb_u8.contiguous()
     boxes = torch.from_numpy(pare_crop_boxes(centers, scales, crop_size)).to(eng.device)
     n, (H, W) = boxes.shape[0], frame.shape[:2]
-    out = torch.empty(n, 3, crop_size, crop_size, device=eng.device, dtype=torch.float32)
-    _lib.check(eng.h, eng.lib.specmi_crop_resize_normalize(eng.h, _ptr(frame), H, W, _ptr(boxes), n, crop_size, _ptr(out),
-                                                           eng._stream()))
+    out = image_tensor(n, crop_size, crop_size, eng.device, f16)
+    fn = eng.lib.specmi_crop_resize_normalize_f16 if f16 else eng.lib.specmi_crop_resize_normalize
+    _lib.check(eng.h, fn(eng.h, _ptr(frame), H, W, _ptr(boxes), n, crop_size, _ptr(out), eng._stream()))
     return out
 
 
@@ -139,11 +153,12 @@ def resize_output_size(w: int, h: int, min_size: int = 600):
 
 
 @torch.no_grad()
-def camcalib_transform(frame_rgb_u8, min_size: int = 600, return_raw: bool = False):
+def camcalib_transform(frame_rgb_u8, min_size: int = 600, return_raw: bool = False, dtype=torch.float32):
     """The CamCalib demo's ``ImageFolder`` transform (``camcalib/pano_dataset.py:156-162``): Resize(600) of
     the PIL image (Pillow's antialiased bilinear), ToTensor, ImageNet Normalize - one HIP launch
     (``specmi_resize_normalize``), bit-identical to Pillow + torchvision.  frame (H,W,3) uint8 device tensor ->
-    (1,3,oh,ow) fp32 [, (oh,ow,3) uint8]."""
+    (1,3,oh,ow) fp32 [, (oh,ow,3) uint8]; ``dtype=torch.float16``: (1,oh,ow,8) NHWC8 fp16 (``specmi_resize_normalize_f16``)."""
+    f16 = out_dtype(dtype)
     if not isinstance(frame_rgb_u8, torch.Tensor) or frame_rgb_u8.device.type != 'cuda':
         raise RuntimeError('camcalib_transform needs a device tensor (no CPU path in spec_amd)')
     if frame_rgb_u8.dtype != torch.uint8 or frame_rgb_u8.dim() != 3 or frame_rgb_u8.shape[2] != 3:
@@ -152,17 +167,20 @@ def camcalib_transform(frame_rgb_u8, min_size: int = 600, return_raw: bool = Fal
     frame = frame_rgb_u8.contiguous()
     H, W = frame.shape[:2]
     ow, oh = resize_output_size(W, H, min_size)
-    out = torch.empty(1, 3, oh, ow, device=eng.device, dtype=torch.float32)
+    out = image_tensor(1, oh, ow, eng.device, f16)
     raw = torch.empty(oh, ow, 3, device=eng.device, dtype=torch.uint8) if return_raw else None
-    _lib.check(eng.h, eng.lib.specmi_resize_normalize(eng.h, _ptr(frame), H, W, oh, ow, _ptr(out), _ptr(raw), eng._stream()))
+    fn = eng.lib.specmi_resize_normalize_f16 if f16 else eng.lib.specmi_resize_normalize
+    _lib.check(eng.h, fn(eng.h, _ptr(frame), H, W, oh, ow, _ptr(out), _ptr(raw), eng._stream()))
     return (out, raw) if return_raw else out
 
 
 @torch.no_grad()
-def camcalib_transform_batch(frames_u8, min_size: int = 600, out=None):
+def camcalib_transform_batch(frames_u8, min_size: int = 600, out=None, dtype=torch.float32):
     """``camcalib_transform`` for a slab of F equal-sized frames: (F,H,W,3) uint8 device -> (F,3,oh,ow) fp32, one
     ``specmi_resize_normalize`` launch per frame into ONE batch tensor (CamCalib then runs once on all F frames instead of once
-    per frame, ``scripts/camcalib_demo.py:95-102``); each frame's pixels are bit-identical to the single-frame call."""
+    per frame, ``scripts/camcalib_demo.py:95-102``); each frame's pixels are bit-identical to the single-frame call.
+    ``dtype=torch.float16``: (F,oh,ow,8) NHWC8 fp16."""
+    f16 = out_dtype(dtype)
     if not isinstance(frames_u8, torch.Tensor) or frames_u8.device.type != 'cuda':
         raise RuntimeError('camcalib_transform_batch needs a device tensor (no CPU path in spec_amd)')
     if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
@@ -170,10 +188,12 @@ def camcalib_transform_batch(frames_u8, min_size: int = 600, out=None):
     eng = _engine(frames_u8.device)
     F, H, W = frames_u8.shape[:3]
     ow, oh = resize_output_size(W, H, min_size)
+    shape = (F, oh, ow, 8) if f16 else (F, 3, oh, ow)
     if out is None:
-        out = torch.empty(F, 3, oh, ow, device=eng.device, dtype=torch.float32)
-    elif tuple(out.shape) != (F, 3, oh, ow) or out.dtype != torch.float32 or not out.is_contiguous():
-        raise ValueError(f'out must be a contiguous (F,3,{oh},{ow}) fp32 tensor')
+        out = image_tensor(F, oh, ow, eng.device, f16)
+    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
+        raise ValueError(f'out must be a contiguous {shape} {dtype} tensor')
+    fn = eng.lib.specmi_resize_normalize_f16 if f16 else eng.lib.specmi_resize_normalize
     for f in range(F):
-        _lib.check(eng.h, eng.lib.specmi_resize_normalize(eng.h, _ptr(frames_u8[f]), H, W, oh, ow, _ptr(out[f]), None, eng._stream()))
+        _lib.check(eng.h, fn(eng.h, _ptr(frames_u8[f]), H, W, oh, ow, _ptr(out[f]), None, eng._stream()))
     return out

@@ -20,6 +20,7 @@ import torch
 from . import assets, cam_utils, io_formats
 from .checkpoint import load_pretrained_model, read_checkpoint
 from .modules import HMR, CameraRegressorNetwork
+from .engine import flow_image_dtype, image_tensor
 from .preprocess import camcalib_transform, crop_detections
 
 CAMCALIB_CKPT = 'data/camcalib/checkpoints/camcalib_sa_biased_l2.ckpt'     # scripts/camcalib_demo.py:39
@@ -71,7 +72,7 @@ def run_camcalib_folder(img_folder, out_folder, ckpt=CAMCALIB_CKPT, loss_type='s
     for img_fname in [f for f in list_images(img_folder) if not os.path.basename(f).startswith('.')]:
         frame = torch.from_numpy(_read_rgb(img_fname)).to(dev)
         orig_h = frame.shape[0]
-        preds = model(camcalib_transform(frame, 600))
+        preds = model(camcalib_transform(frame, 600, dtype=flow_image_dtype(model)))
         if loss_type in ('kl', 'ce'):
             vfov, pitch, roll = (np.asarray(a).squeeze() for a in cam_utils.convert_preds_to_angles(*preds, loss_type=loss_type, return_type='np'))
         else:
@@ -95,6 +96,7 @@ class SPECTester:
         self._load_pretrained_model()
         self.model.eval()
         self._camcalib = getattr(args, 'camcalib_model', None)
+        self._fp32_crops = None       # False: NHWC8 fp16 crops for a model at fp16; True: fp32 crops + in-trunk conversion (same bits)
 
     def _build_model(self):
         c = self.model_cfg
@@ -160,7 +162,8 @@ class SPECTester:
         if not todo:
             return 0
         cap = max(cap, max(len(detections[i]) for i, _ in todo))       # a frame's detections stay in one batch
-        buf = {'inp_images': torch.empty(cap, 3, res, res, device=dev), 'bbox_scale': torch.empty(cap, device=dev),
+        crop_dtype = flow_image_dtype(self.model, self._fp32_crops)
+        buf = {'inp_images': image_tensor(cap, res, res, dev, crop_dtype == torch.float16), 'bbox_scale': torch.empty(cap, device=dev),
                'bbox_center': torch.empty(cap, 2, device=dev)}
         img_w, img_h = torch.empty(cap, device=dev), torch.empty(cap, device=dev)
         R, K = torch.empty(cap, 3, 3, device=dev), torch.empty(cap, 3, 3, device=dev)
@@ -206,7 +209,7 @@ class SPECTester:
                     flush()
                 frame = torch.from_numpy(rgb).pin_memory().to(dev, non_blocking=True)
                 orig_height, orig_width = frame.shape[:2]
-                crop_detections(frame, dets, scale=1.0, crop_size=res,                              # tester.py:116-128
+                crop_detections(frame, dets, scale=1.0, crop_size=res, dtype=crop_dtype,           # tester.py:116-128
                                 out={key: v[k:k + n] for key, v in buf.items()})
                 img_h[k:k + n] = float(orig_height)
                 img_w[k:k + n] = float(orig_width)
