@@ -189,9 +189,9 @@ static int run_fc(specmi_handle* h, const FcW& fc, const float* x, int ldx, int 
         a.B = nb; a.H = 1; a.W = 1; a.Cin = fc.Kp; a.ldx = ldx;
         a.OH = 1; a.OW = 1; a.Cout = fc.nout; a.Npad = fc.Npad; a.ldo = ldo;
         a.KH = 1; a.KW = 1; a.stride = 1; a.pad = 0; a.relu = 0;
-        a.force_variant = opt_i(h, "force_conv_variant", 0);
+        a.force_variant = opt(h, OPT_force_conv_variant);
         LaunchCtx ctx{s, &h->prof, label};
-        const int S = opt_i(h, "fc_splitk", 1) ? conv_igemm_splitk_plan(a) : 1;
+        const int S = opt(h, OPT_fc_splitk) ? conv_igemm_splitk_plan(a) : 1;
         if (S > 1) {
             int rc;
             if ((rc = ensure_sk(h, conv_igemm_sk_ws_floats(a, S, 1), conv_igemm_sk_tiles(a, 1)))) return rc;
@@ -235,6 +235,9 @@ struct OpLaunch {
     float* out = nullptr;
 };
 
+// the canonical tree of a sliced layer and the unit of this launch (px = pixels of the trunk call, see sk_fill), from the options
+static SkPlan sk_plan(const specmi_handle* h, const ConvArgs& a, int groups, long px = 0);
+
 static OpLaunch prepare_op(specmi_handle* h, const TrunkOp& op, const float* images, float* feat_out, int b0, int nb,
                            int Himg, int Wimg, int mode = 0) {
     const bool latency = mode != 0;
@@ -260,8 +263,8 @@ static OpLaunch prepare_op(specmi_handle* h, const TrunkOp& op, const float* ima
     a.B = nb; a.H = op.H; a.W = op.W; a.Cin = c.cin; a.ldx = c.cin;
     a.OH = op.OH; a.OW = op.OW; a.Cout = c.cout; a.Npad = c.Npad; a.ldo = c.cout;
     a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad; a.relu = op.relu;
-    a.force_variant = opt_i(h, "force_conv_variant", 0);
-    a.wino_variant = opt_i(h, "force_wino_variant", 0);
+    a.force_variant = opt(h, OPT_force_conv_variant);
+    a.wino_variant = opt(h, OPT_force_wino_variant);
     if (op.fused) {
         const Bneck& bk = *op.fused;
         a.w = bk.f_w; a.scale = bk.f_scale; a.shift = bk.f_shift; a.Npad = bk.f_Npad; a.res = nullptr;
@@ -269,17 +272,17 @@ static OpLaunch prepare_op(specmi_handle* h, const TrunkOp& op, const float* ima
         a.H2 = op.H2; a.W2 = op.W2; a.ldx2 = bk.ds.cin; a.Cin2 = bk.ds.cin; a.stride2 = bk.ds.stride;
     }
     if (const void* wsplit = op.fused ? op.fused->f_wsplit : c.wsplit) {
-        const int terms = opt_i(h, "conv_precision", 0);
+        const int terms = opt(h, OPT_conv_precision);
         // 3x3 layers: the bf16 implicit GEMM spends 9 taps x terms / 16 of an fp32 MFMA cycle per MAC, the fp32 Winograd kernel
         // 16 / 36: with three terms the bf16 path wins on every 3x3 layer, with six only where Winograd does not apply (stride 2)
-        const bool wino_ok = c.wino && opt_i(h, "winograd", 1) && conv_wino_supported(a);
-        const bool take = c.k == 1 || terms == 3 || !wino_ok || opt_i(h, "conv_precision_3x3", 0);
+        const bool wino_ok = c.wino && opt(h, OPT_winograd) && conv_wino_supported(a);
+        const bool take = c.k == 1 || terms == 3 || !wino_ok || opt(h, OPT_conv_precision_3x3);
         if ((terms == 3 || terms == 6) && take && conv_bf16s_supported(a)) {
             L.family = 2; L.wsplit = wsplit; L.terms = terms;
             return L;
         }
     }
-    bool wino = c.wino && opt_i(h, "winograd", 1) && conv_wino_supported(a);
+    bool wino = c.wino && opt(h, OPT_winograd) && conv_wino_supported(a);
     if (latency && !a.force_variant) {
         // Latency plan (batch <= 10 by default).  Every choice below is a function of the layer's per-image shape, never of the batch:
         // an image's bits are the same at batch 1 and 16.  Winograd only where an image alone brings enough 2x2 tiles to
@@ -287,10 +290,10 @@ static OpLaunch prepare_op(specmi_handle* h, const TrunkOp& op, const float* ima
         // weight bytes) run the direct kernel over K slices.
         // (wide layers need proportionally more tiles: layer4 of a 600 x 1066 frame has 170 tiles per image = 48 Winograd workgroups
         // walking Cin = 512 for 75 us, the sliced direct kernel takes 45)
-        const int min_tiles = opt_i(h, "latency_wino_min_tiles", 128);
+        const int min_tiles = opt(h, OPT_latency_wino_min_tiles);
         if (wino && ((a.OH + 1) / 2) * ((a.OW + 1) / 2) < (min_tiles > a.Cin || min_tiles == 0 || min_tiles >= 100000 ? min_tiles : a.Cin)) wino = false;
         if (mode == 2) wino = false;   // 'single': batch 1-2, the direct kernel wins on layer1 / layer2 too
-        if (!wino) L.sk = conv_igemm_sk_slices(a, opt_i(h, "latency_target_wgs", 256), opt_i(h, "latency_min_chunks", 4));
+        if (!wino) L.sk = sk_plan(h, a, 1).leaves;
     }
     if (wino) {
         a.w = c.wino;
@@ -308,13 +311,13 @@ static OpLaunch prepare_op(specmi_handle* h, const TrunkOp& op, const float* ima
 // other 3.08 vs 3.32 ms still at 16; a single CamCalib frame at 600 x 1066 = 12.7 crops' worth of rows: 2.10 vs 2.27 ms for the
 // demo's one-frame step)
 static int trunk_mode(specmi_handle* h, int B, int H, int W, bool pair = false) {
-    const int plan = opt_i(h, "plan", 0);
+    const int plan = opt(h, OPT_plan);
     if (plan == 1) return 0;
     if (plan == 2) return 1;
     if (plan == 3) return 2;
     const long px = (long)B * H * W, crop = 224L * 224;
-    if (px <= (long)opt_i(h, "single_max_batch", 2) * crop) return 2;
-    const int nmax = pair ? opt_i(h, "latency_max_batch", 10) : opt_i(h, "latency_max_batch_single", 16);
+    if (px <= (long)opt(h, OPT_single_max_batch) * crop) return 2;
+    const int nmax = pair ? opt(h, OPT_latency_max_batch) : opt(h, OPT_latency_max_batch_single);
     return px <= (long)nmax * crop ? 1 : 0;
 }
 // the FC layers behind the trunk see batch rows only: the small-batch GEMV kernel (head.hip) up to "latency_max_batch" rows
@@ -323,14 +326,17 @@ static int trunk_mode(specmi_handle* h, int B, int H, int W, bool pair = false) 
 // px = pixels of the trunk call (B x H x W): beyond ten 224 x 224 crops' worth - a single trunk keeps the latency plan up to 16 - the
 // threshold is "latency_fill_wgs_large" (400): measured per batch under the auto structure (profiles/r05_n_unit_rule_sweep.jsonl:
 // 1.99 -> 1.80 ms at batch 11, 2.13 -> 1.91 at 12, 2.20 -> 2.10 at 14; at batch <= 10 240 stays ahead: 1.55 vs 2.06 ms at 10)
-static int sk_fill(specmi_handle* h, long px = 0) {
-    if (opt_i(h, "latency_unit_model", 0)) return -opt_i(h, "latency_unit_slots", 256);
-    return px > 10L * 224 * 224 ? opt_i(h, "latency_fill_wgs_large", 400) : opt_i(h, "latency_fill_wgs", 240);
+static int sk_fill(const specmi_handle* h, long px = 0) {
+    if (opt(h, OPT_latency_unit_model)) return -opt(h, OPT_latency_unit_slots);
+    return px > 10L * 224 * 224 ? opt(h, OPT_latency_fill_wgs_large) : opt(h, OPT_latency_fill_wgs);
+}
+static SkPlan sk_plan(const specmi_handle* h, const ConvArgs& a, int groups, long px) {
+    return conv_igemm_sk_plan(a, groups, opt(h, OPT_latency_target_wgs), opt(h, OPT_latency_min_chunks), sk_fill(h, px));
 }
 
 static bool use_latency_heads(specmi_handle* h, int B) {
-    const int plan = opt_i(h, "plan", 0);
-    return opt_i(h, "fc_gemv", 1) && (plan == 2 || plan == 3 || (plan == 0 && B <= opt_i(h, "latency_max_batch", 10)));
+    const int plan = opt(h, OPT_plan);
+    return opt(h, OPT_fc_gemv) && (plan == 2 || plan == 3 || (plan == 0 && B <= opt(h, OPT_latency_max_batch)));
 }
 
 // partner != nullptr: the same op of a second network, launched together (one grouped launch); the caller has checked
@@ -357,9 +363,8 @@ static int launch_op(specmi_handle* h, const TrunkOp& op, const OpLaunch& L, con
     if (L.sk > 1) {
         const int groups = partner ? 2 : 1;
         int rc;
-        SkPlan pl = conv_igemm_sk_plan(L.a, groups, opt_i(h, "latency_target_wgs", 256), opt_i(h, "latency_min_chunks", 4),
-                                       sk_fill(h, (long)nb * Himg * Wimg));
-        const int fu = opt_i(h, "latency_force_unit", 0);   // tests: 1 leaf / 2 group / 3 whole K per workgroup, whatever the batch
+        SkPlan pl = sk_plan(h, L.a, groups, (long)nb * Himg * Wimg);
+        const int fu = opt(h, OPT_latency_force_unit);   // tests: 1 leaf / 2 group / 3 whole K per workgroup, whatever the batch
         if (fu) pl.unit = fu == 1 ? 1 : (fu == 2 ? pl.G : pl.leaves);
         // The wave-split unit (conv_wsplit.hip, round 5): a 32x32 tile per workgroup, the G leaves of a group on its waves side by
         // side - four times the tiles, slabs of 4 KB per GROUP or none.  Same canonical tree, same bits: a pure speed choice, made
@@ -373,14 +378,14 @@ static int launch_op(specmi_handle* h, const TrunkOp& op, const OpLaunch& L, con
         //     a round costing one leaf (L chunks of ~0.45 us) and the slab hand-off ~1 us - the rule that reproduces every row of
         //     the tables (batch 1-4, layer2-4).
         // "wsplit": 0 never, 1 (default) by this rule, 2 / 3 always with one group / all groups per workgroup (tests, tables).
-        const int wsplit = opt_i(h, "wsplit", 1);
+        const int wsplit = opt(h, OPT_wsplit);
         if (wsplit && !fu) {
             SkPlan pw = pl;
             const long t32 = conv_wsplit_tiles(L.a, groups);
             const long ng = pl.leaves / (pl.G > 0 ? pl.G : 1);
             const int nch = conv_k_chunks(L.a);
             const double t_leaf = 0.45 * (double)(nch / pl.leaves);
-            const long slots = opt_i(h, "wsplit_slots", 256);
+            const long slots = opt(h, OPT_wsplit_slots);
             const double cost_all = (double)((t32 + slots - 1) / slots) * (double)ng * t_leaf;
             const double cost_group = (double)((t32 * ng + slots - 1) / slots) * t_leaf + 1.0;
             pw.unit = (wsplit == 3 || (wsplit == 1 && cost_all <= cost_group)) ? pl.leaves : pl.G;
@@ -388,7 +393,7 @@ static int launch_op(specmi_handle* h, const TrunkOp& op, const OpLaunch& L, con
             // 4-10 - want the cap at 500 units, 1.245 vs 1.285 ms at batch 6, 1.441 vs 1.487 at 8; the pair's grouped launches between 1300 and 1500:
             // 0.884 vs 0.913 ms at batch 3 and 1.312 vs 1.421 at 6 with layer3 / layer4 on the unit (<= 1280 units), 1.546 vs 1.573 at
             // batch 8 without it (1568 / 1664 units))
-            const long max_units = groups == 2 ? opt_i(h, "wsplit_max_units", 1400) : opt_i(h, "wsplit_max_units_single", 500);
+            const long max_units = groups == 2 ? opt(h, OPT_wsplit_max_units) : opt(h, OPT_wsplit_max_units_single);
             const bool take = wsplit > 1 || (pl.unit != pl.leaves && !L.a.x2 && t32 * ng <= max_units);
             if (take && conv_wsplit_supported(L.a, pw)) {
                 if ((rc = ensure_sk(h, conv_wsplit_ws_floats(L.a, pw.leaves / pw.unit, groups), conv_wsplit_tiles(L.a, groups)))) return rc;
@@ -480,7 +485,7 @@ static void plan_trunk(specmi_handle* h, int H, int W, bool to_caller, TrunkPlan
         add(bk.c1, xi, t1, -1, ch, cw, ch, cw, 1, ".conv1");
         add(bk.c2, t1, t2, -1, ch, cw, oh, ow, 1, ".conv2");
         int identity = xi;
-        const bool fuse = bk.has_ds && (bk.f_w || bk.f_w16) && opt_i(h, "fuse_downsample", 1);
+        const bool fuse = bk.has_ds && (bk.f_w || bk.f_w16) && opt(h, OPT_fuse_downsample);
         if (bk.has_ds && !fuse) {
             add(bk.ds, xi, idb, -1, ch, cw, oh, ow, 0, ".downsample");
             identity = idb;
@@ -604,8 +609,8 @@ static int run_trunk(specmi_handle* h, const float* images, int B, int H, int W,
     const std::vector<TrunkOp>& ops = P.ops;
     const std::vector<int>& stage_of = P.stage_of;
     const int final_buf = P.final_buf, ch = P.fh, cw = P.fw;
-    const int S = opt_i(h, "trunk_subbatch", 0);
-    const int Lsplit = opt_i(h, "trunk_subbatch_layers", 2);
+    const int S = opt(h, OPT_trunk_subbatch);
+    const int Lsplit = opt(h, OPT_trunk_subbatch_layers);
     const int mode = trunk_mode(h, B, H, W);
     size_t first_full = 0;
     if (S > 0 && S < B) {
@@ -655,7 +660,7 @@ struct OutLd {
 };
 static OutLd out_ld(specmi_handle* h) {
     OutLd o;
-    const long ld = opt_i(h, "output_ld", 0);
+    const long ld = opt(h, OPT_output_ld);
     if (ld > 0) o.pose = o.shape = o.cam = o.p6d = o.verts = o.j3d = o.j2d = o.camt = ld;
     return o;
 }
@@ -665,7 +670,7 @@ static int run_head(specmi_handle* h, const float* feat, int B, int fh, int fw, 
                     const float* img_h, float* pred_pose, float* pred_shape, float* pred_cam, float* pred_pose_6d,
                     const OutLd& old, hipStream_t s, HeadFinal* defer = nullptr) {
     int rc;
-    const int ucf = opt_i(h, "use_cam_feats", 0);
+    const int ucf = opt(h, OPT_use_cam_feats);
     const int F = h->feat_ch, LD = h->xc_ld;
     if (ucf && (!R || !K || !img_h))
         return fail(h, SPECMI_ERR_ARG, "use_cam_feats needs cam_rotmat, cam_intrinsics and img_h");
@@ -675,7 +680,7 @@ static int run_head(specmi_handle* h, const float* feat, int B, int fh, int fw, 
     bool init_done = false;
     {
         LaunchCtx ctx{s, &h->prof, "head.avgpool"};
-        LAUNCHCHK(h, launch_avgpool(feat, h->xc, B, fh * fw, F, LD, ctx, (opt_i(h, "head_fuse", 3) & 1) ? &hi : nullptr, &init_done), "avgpool");
+        LAUNCHCHK(h, launch_avgpool(feat, h->xc, B, fh * fw, F, LD, ctx, (opt(h, OPT_head_fuse) & 1) ? &hi : nullptr, &init_done), "avgpool");
     }
     if (!init_done) {
         LaunchCtx ctx{s, &h->prof, "head.init"};
@@ -694,7 +699,7 @@ static int run_head(specmi_handle* h, const float* feat, int B, int fh, int fw, 
         }
         return run_fc(h, w, x, ldx, B, res, out, ldo, s, label);
     };
-    if (h->has_head_c && opt_i(h, "head_collapse", 1)) {
+    if (h->has_head_c && opt(h, OPT_head_collapse)) {
         // the three IEF iterations as one composed affine map (commit_head_collapsed)
         if ((rc = fc(h->head_c, h->xc, LD, nullptr, h->h1, 1024, "head.ief_collapsed"))) return rc;
         state = h->h1;
@@ -733,7 +738,7 @@ static int run_smpl(specmi_handle* h, const float* rotmat, const float* betas, c
                     const float* K, const float* bbox_scale, const float* bbox_center, const float* img_w,
                     const float* img_h, float* vertices, float* joints3d, float* joints2d, float* cam_t,
                     const OutLd& old, hipStream_t s, const HeadFinal* final_ = nullptr) {
-    const int use_cam = opt_i(h, "use_cam", 0);
+    const int use_cam = opt(h, OPT_use_cam);
     if (use_cam && (!R || !K || !bbox_scale || !bbox_center || !img_w || !img_h))
         return fail(h, SPECMI_ERR_ARG, "use_cam needs cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h");
     SmplArgs a;
@@ -746,10 +751,10 @@ static int run_smpl(specmi_handle* h, const float* rotmat, const float* betas, c
     a.pose_feat = h->pf_ws; a.A = h->A_ws; a.posed_j = h->pj_ws;
     a.B = B;
     a.mode = use_cam ? 0 : 1;
-    a.focal_length = opt_f(h, "focal_length", 5000.f);
-    a.img_res = (float)opt_i(h, "img_res", 224);
+    a.focal_length = h->focal_length;
+    a.img_res = (float)opt(h, OPT_img_res);
     a.normalize_joints2d = use_cam ? 0 : 1;  // spec/models/hmr.py:111 vs :119
-    a.skin_split = opt_i(h, "smpl_skin_split", -1);
+    a.skin_split = opt(h, OPT_smpl_skin_split);
     a.final_ = final_;
     LaunchCtx ctx{s, &h->prof, "smpl"};
     LAUNCHCHK(h, launch_smpl(h->smpl, a, ctx), "smpl");
@@ -845,7 +850,7 @@ int specmi_commit(specmi_handle* h) {
         return SPECMI_OK;
     }
     const std::string bp = "backbone.";
-    const int depth = opt_i(h, "backbone", 50);
+    const int depth = opt(h, OPT_backbone);
     if (depth != 50 && depth != 34 && depth != 18 && depth != 101 && depth != 152 && depth != 32 && depth != 48)
         return fail(h, SPECMI_ERR_ARG, "backbone %d: resnet18 / 34 / 50 / 101 / 152, hrnet_w32 (32) and hrnet_w48 (48) are built", depth);
     if ((depth == 32 || depth == 48) && h->kind != SPECMI_MODEL_HMR)
@@ -855,7 +860,7 @@ int specmi_commit(specmi_handle* h) {
     if (h->hrnet) { hrnet_free(h->hrnet); h->hrnet = nullptr; }
     if (depth == 32 || depth == 48) {
         h->blocks.clear();
-        if ((rc = hrnet_commit(h, bp, depth, opt_i(h, "hrnet_use_conv", 1)))) return rc;
+        if ((rc = hrnet_commit(h, bp, depth, opt(h, OPT_hrnet_use_conv)))) return rc;
     } else {
         build_resnet(h, depth);
         if ((rc = commit_conv(h, bp, h->stem))) return rc;
@@ -870,7 +875,7 @@ int specmi_commit(specmi_handle* h) {
     if (h->kind == SPECMI_MODEL_CAMCALIB) {
         // camcalib/model.py:39-57: one Linear per angle, or Sequential(Linear x num_fc_layers) WITHOUT activations
         const char* names[3] = {"fc_vfov", "fc_pitch", "fc_roll"};
-        const int L = opt_i(h, "num_fc_layers", 1), hc = opt_i(h, "num_fc_channels", 1024);
+        const int L = opt(h, OPT_num_fc_layers), hc = opt(h, OPT_num_fc_channels);
         if (L < 1 || L > 3 || hc < 1 || hc > 1024) return fail(h, SPECMI_ERR_ARG, "num_fc_layers in 1..3 and num_fc_channels <= 1024 are built");
         h->fc_layers = L;
         const std::string lastw = L == 1 ? std::string("fc_vfov.weight") : "fc_vfov." + std::to_string(L - 1) + ".weight";
@@ -878,7 +883,6 @@ int specmi_commit(specmi_handle* h) {
         if (!w0) return fail(h, SPECMI_ERR_MISSING, "missing tensor '%s'", lastw.c_str());
         const int last_in = L == 1 ? h->feat_ch : hc;
         const int nb = (int)(w0->numel() / last_in);
-        h->opt_i["nbins"] = nb;
         for (int i = 0; i < 3; ++i)
             for (int l = 0; l < L; ++l) {
                 const std::string nm = L == 1 ? std::string(names[i]) : std::string(names[i]) + "." + std::to_string(l);
@@ -886,14 +890,14 @@ int specmi_commit(specmi_handle* h) {
                 if ((rc = commit_fc(h, {nm}, {nout}, nin, h->fc_cam[i][l]))) return rc;
             }
     } else {
-        const int ucf = opt_i(h, "use_cam_feats", 0);
+        const int ucf = opt(h, OPT_use_cam_feats);
         const int nin = h->feat_ch + 144 + 13 + (ucf ? 7 : 0);
         h->xc_ld = round_up(h->feat_ch + 164, 32);
         h->has_head_c = false;
         if ((rc = commit_fc(h, {"head.fc1"}, {1024}, nin, h->fc1))) return rc;
         if ((rc = commit_fc(h, {"head.fc2"}, {1024}, 1024, h->fc2))) return rc;
         if ((rc = commit_fc(h, {"head.decpose", "head.decshape", "head.deccam"}, {144, 10, 3}, 1024, h->dec))) return rc;
-        h->has_var = opt_i(h, "estimate_var", 0) != 0;
+        h->has_var = opt(h, OPT_estimate_var) != 0;
         if (h->has_var && (rc = commit_fc(h, {"head.decpose_var", "head.decshape_var"}, {144, 10}, 1024, h->head_var))) return rc;
         h->last_state = h->last_var = nullptr; h->last_B = 0;
         const HostTensor *ip, *is, *ic;
@@ -903,7 +907,7 @@ int specmi_commit(specmi_handle* h) {
         if ((rc = dev_upload(h, ip->f.data(), 144 * 4, (void**)&h->init_pose, h->param_allocs))) return rc;
         if ((rc = dev_upload(h, is->f.data(), 10 * 4, (void**)&h->init_shape, h->param_allocs))) return rc;
         if ((rc = dev_upload(h, ic->f.data(), 3 * 4, (void**)&h->init_cam, h->param_allocs))) return rc;
-        if (opt_i(h, "head_collapse", 1) && (rc = commit_head_collapsed(h, h->feat_ch, ucf))) return rc;
+        if (opt(h, OPT_head_collapse) && (rc = commit_head_collapsed(h, h->feat_ch, ucf))) return rc;
         if ((rc = commit_smpl(h))) return rc;
         // the SMPL vertex count sizes the workspace
         free_pool(h->ws_allocs);
@@ -1048,7 +1052,7 @@ int specmi_camcalib_head_decode(specmi_handle* h, const float* feat, int B, int 
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if ((rc = ensure_ws(h, B, 32, 32))) return rc;
-    const long ld_ang = opt_i(h, "angle_ld", 0) > 0 ? opt_i(h, "angle_ld", 0) : 1;
+    const long ld_ang = opt(h, OPT_angle_ld) > 0 ? opt(h, OPT_angle_ld) : 1;
     if ((rc = run_camcalib_head(h, feat, B, fh, fw, lv, lp, lr, s))) { reset_sync_state(h, s); return rc; }
     LaunchCtx ctx{s, &h->prof, "camcalib.decode"};
     // the bins are the LAST Linear of a head's chain (num_fc_layers > 1: the first one is num_fc_channels wide, camcalib/model.py:59-70)
@@ -1066,7 +1070,7 @@ int specmi_camcalib_decode(specmi_handle* h, const float* lv, const float* lp, c
     if (K && !img_w) return fail(h, SPECMI_ERR_ARG, "K needs img_w");
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, "camcalib.decode"};
     LAUNCHCHK(h, launch_camcalib_decode(lv, lp, lr, B, nbins, img_h, img_w, vfov, pitch, roll, f_pix, R, K,
-                                        (long)(opt_i(h, "angle_ld", 0) > 0 ? opt_i(h, "angle_ld", 0) : 1), ctx), "decode");
+                                        (long)(opt(h, OPT_angle_ld) > 0 ? opt(h, OPT_angle_ld) : 1), ctx), "decode");
     return SPECMI_OK;
 }
 
@@ -1157,7 +1161,7 @@ int specmi_smpl_native(specmi_handle* h, const float* pose, int pose_is_axis_ang
     a.vertices = vertices; a.joints3d = a.joints2d = a.cam_t = nullptr;
     a.pose_feat = h->pf_ws; a.A = h->A_ws; a.posed_j = h->pj_ws;
     a.B = B; a.mode = 1; a.focal_length = 0.f; a.img_res = 0.f; a.normalize_joints2d = 0;
-    a.skin_split = opt_i(h, "smpl_skin_split", -1);
+    a.skin_split = opt(h, OPT_smpl_skin_split);
     LaunchCtx ctx{s, &h->prof, "smpl.native"};
     LAUNCHCHK(h, launch_smpl_native(h->smpl, a, joints24, ctx), "smpl_native");
     return SPECMI_OK;
@@ -1174,7 +1178,7 @@ static int hmr_forward(specmi_handle* h, const float* images, const void* images
     if ((rc = run_trunk(h, images, B, H, W, nullptr, &f, &fh, &fw, s, images16))) { reset_sync_state(h, s); return rc; }
     const OutLd old = out_ld(h);
     HeadFinal fin;
-    const bool fuse = (opt_i(h, "head_fuse", 3) & 2) != 0;     // head_final's work inside the SMPL pose kernel (same bits, one node less)
+    const bool fuse = (opt(h, OPT_head_fuse) & 2) != 0;     // head_final's work inside the SMPL pose kernel (same bits, one node less)
     if ((rc = run_head(h, f, B, fh, fw, R, K, img_h, out->pred_pose, out->pred_shape, out->pred_cam, out->pred_pose_6d, old, s,
                        fuse ? &fin : nullptr)) ||
         (rc = run_smpl(h, h->rot_ws, h->betas_ws, h->cam_ws, B, R, K, bbox_scale, bbox_center, img_w, img_h,
@@ -1206,7 +1210,7 @@ int specmi_hmr_regress(specmi_handle* h, const float* feat, int B, int fh, int f
     if ((rc = ensure_ws(h, B, 32, 32))) return rc;
     const OutLd old = out_ld(h);
     HeadFinal fin;
-    const bool fuse = (opt_i(h, "head_fuse", 3) & 2) != 0;     // head_final's work inside the SMPL pose kernel (same bits, one node less)
+    const bool fuse = (opt(h, OPT_head_fuse) & 2) != 0;     // head_final's work inside the SMPL pose kernel (same bits, one node less)
     if ((rc = run_head(h, feat, B, fh, fw, R, K, img_h, out->pred_pose, out->pred_shape, out->pred_cam, out->pred_pose_6d, old, s,
                        fuse ? &fin : nullptr)) ||
         (rc = run_smpl(h, h->rot_ws, h->betas_ws, h->cam_ws, B, R, K, bbox_scale, bbox_center, img_w, img_h,
@@ -1224,7 +1228,7 @@ int specmi_hmr_uncertainty(specmi_handle* h, int B, float* pred_pose_var, float*
         return fail(h, SPECMI_ERR_STATE, "specmi_hmr_uncertainty follows a head forward of the same batch (%d) on the same stream; the last one had %d",
                     B, h->last_B);
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, "head.var"};
-    LAUNCHCHK(h, launch_head_var(h->last_state, h->last_ld_state, h->last_var, h->last_ld_var, opt_i(h, "uncertainty_activation", 0), pred_pose_var,
+    LAUNCHCHK(h, launch_head_var(h->last_state, h->last_ld_state, h->last_var, h->last_ld_var, opt(h, OPT_uncertainty_activation), pred_pose_var,
                                  pred_shape_var, B, ctx), "head_var");
     return SPECMI_OK;
 }
@@ -1246,9 +1250,9 @@ int specmi_conv2d(specmi_handle* h, const float* x, int B, int H, int W, int Cin
     std::memcpy(sc.data(), scale_host, (size_t)Cout * 4);
     std::memcpy(sh.data(), shift_host, (size_t)Cout * 4);
     // option "winograd": 1 (default) = F(2x2,3x3) where the shape allows it, 0 = always the direct implicit GEMM
-    const bool wino = !stem && opt_i(h, "winograd", 1) && KH == 3 && stride == 1 && pad == 1 && Cin % 16 == 0 &&
+    const bool wino = !stem && opt(h, OPT_winograd) && KH == 3 && stride == 1 && pad == 1 && Cin % 16 == 0 &&
                       (Cout % 64 == 0 || (Cout % 32 == 0 && Cout > 64));
-    const int terms = opt_i(h, "conv_precision", 0);
+    const int terms = opt(h, OPT_conv_precision);
     const bool split = !stem && (terms == 3 || terms == 6) && Cin % 16 == 0 && Cout % 4 == 0;
     std::vector<unsigned short> pieces;
     void* dsplit = nullptr;
@@ -1278,25 +1282,24 @@ int specmi_conv2d(specmi_handle* h, const float* x, int B, int H, int W, int Cin
         a.x = x; a.w = dw; a.scale = dsc; a.shift = dsh; a.res = residual; a.out = out;
         a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldx = Cin; a.OH = OH; a.OW = OW; a.Cout = Cout; a.Npad = Npad;
         a.ldo = Cout; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.relu = relu;
-        a.force_variant = opt_i(h, "force_conv_variant", 0);
-        a.wino_variant = opt_i(h, "force_wino_variant", 0);
+        a.force_variant = opt(h, OPT_force_conv_variant);
+        a.wino_variant = opt(h, OPT_force_wino_variant);
         // option "conv2d_sk" (tests): > 1 = that many leaves, -1 = the latency plan's own rule, 0 = the throughput kernel;
         // "latency_force_unit": 0 = by batch, 1 / 2 / 3 = a leaf / a group / the whole K per workgroup
-        int S = wino ? 0 : opt_i(h, "conv2d_sk", 0);
+        int S = wino ? 0 : opt(h, OPT_conv2d_sk);
         if (split && conv_bf16s_supported(a)) lrc = launch_conv_bf16s(a, dsplit, terms, ctx);
         else if (S != 0) {
-            SkPlan pl = conv_igemm_sk_plan(a, 1, opt_i(h, "latency_target_wgs", 256), opt_i(h, "latency_min_chunks", 4),
-                                           sk_fill(h));
+            SkPlan pl = sk_plan(h, a, 1);
             if (S > 0) {
                 pl.leaves = S; pl.G = 1;
                 for (int g = 2; g <= 4; ++g)
                     if (S % g == 0) pl.G = g;
                 pl.unit = 1;
             }
-            const int fu = opt_i(h, "latency_force_unit", 0);
+            const int fu = opt(h, OPT_latency_force_unit);
             if (fu) pl.unit = fu == 1 ? 1 : (fu == 2 ? pl.G : pl.leaves);
             // "conv2d_wsplit" (tests): 2 / 3 = the wave-split unit of the same tree, one group / all groups per workgroup
-            const int ws = opt_i(h, "conv2d_wsplit", 0);
+            const int ws = opt(h, OPT_conv2d_wsplit);
             SkPlan pw = pl;
             pw.unit = ws == 3 ? pl.leaves : pl.G;
             if (ws >= 2 && conv_wsplit_supported(a, pw)) {

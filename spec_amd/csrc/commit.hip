@@ -111,7 +111,7 @@ int commit_conv(specmi_handle* h, const std::string& prefix, ConvW& c) {
     }
     // optional split-bf16 path (conv_bf16s.hip): the weights of the plain 1x1 / stride-1 layers as three bf16 pieces
     c.wsplit = nullptr;
-    if (fp32_forms && opt_i(h, "conv_precision", 0) != 0 && (c.k == 1 || c.k == 3) && cin % 16 == 0 && cout % 4 == 0) {
+    if (fp32_forms && opt(h, OPT_conv_precision) != 0 && (c.k == 1 || c.k == 3) && cin % 16 == 0 && cout % 4 == 0) {
         std::vector<unsigned short> pieces;
         pack_bf16_split_weights_oihw(wsrc, cout, cin, c.k, c.k, c.Npad, pieces);
         if ((rc = dev_upload(h, pieces.data(), pieces.size() * 2, &c.wsplit, h->param_allocs))) return rc;
@@ -164,7 +164,7 @@ int commit_fused_ds(specmi_handle* h, const std::string& prefix, Bneck& b) {
     b.f_Npad = Npad;
     b.f_wsplit = nullptr;
     b.f_w = b.f_scale = nullptr;
-    if (fp32_forms && opt_i(h, "conv_precision", 0) != 0 && K1 % 16 == 0 && K2 % 16 == 0 && N % 4 == 0) {
+    if (fp32_forms && opt(h, OPT_conv_precision) != 0 && K1 % 16 == 0 && K2 % 16 == 0 && N % 4 == 0) {
         std::vector<unsigned short> pieces;
         pack_bf16_split_weights(wcat.data(), N, K, Npad, pieces);
         if ((rc = dev_upload(h, pieces.data(), pieces.size() * 2, &b.f_wsplit, h->param_allocs))) return rc;

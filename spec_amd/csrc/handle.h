@@ -54,12 +54,68 @@ struct FcW {  // Linear layers as H=W=1 convolutions
 
 struct HrNet;
 
+// ---- the option list: every integer name specmi_set_option_i32 accepts, its default and whether it is part of the STABLE surface
+// (include/specmi.h).  The only place a name and its default are written: enum Opt below and the table specmi_option_info reports
+// (options.hip) are the two expansions of it, in this order.
+#define SPECMI_OPTIONS(SPECMI_OPT) \
+    /* stable: model shape (before commit) */                                                                             \
+    SPECMI_OPT(backbone, 50, true)                                                                                        \
+    SPECMI_OPT(num_fc_layers, 1, true)                                                                                    \
+    SPECMI_OPT(num_fc_channels, 1024, true)                                                                               \
+    SPECMI_OPT(use_cam, 0, true)                                                                                          \
+    SPECMI_OPT(use_cam_feats, 0, true)                                                                                    \
+    SPECMI_OPT(img_res, 224, true)                                                                                        \
+    SPECMI_OPT(hrnet_use_conv, 1, true)                                                                                   \
+    SPECMI_OPT(estimate_var, 0, true)                                                                                     \
+    SPECMI_OPT(uncertainty_activation, 0, true)                                                                           \
+    /* stable: execution (any time) */                                                                                    \
+    SPECMI_OPT(plan, 0, true)                                                                                             \
+    SPECMI_OPT(winograd, 1, true)                                                                                         \
+    SPECMI_OPT(fuse_downsample, 1, true)                                                                                  \
+    SPECMI_OPT(head_collapse, 1, true)                                                                                    \
+    SPECMI_OPT(output_ld, 0, true)                                                                                        \
+    SPECMI_OPT(angle_ld, 0, true)                                                                                         \
+    SPECMI_OPT(experimental, 0, true)                                                                                     \
+    /* experimental: secondary arithmetic, debug pins, tuning thresholds, measured-slower or measured-neutral opt-ins */  \
+    SPECMI_OPT(conv_precision, 0, false)                                                                                  \
+    SPECMI_OPT(conv_precision_3x3, 0, false)                                                                              \
+    SPECMI_OPT(force_conv_variant, 0, false)                                                                              \
+    SPECMI_OPT(force_wino_variant, 0, false)                                                                              \
+    SPECMI_OPT(fc_splitk, 1, false)                                                                                       \
+    SPECMI_OPT(fc_gemv, 1, false)                                                                                         \
+    SPECMI_OPT(head_fuse, 3, false)                                                                                       \
+    SPECMI_OPT(smpl_skin_split, -1, false)                                                                                \
+    SPECMI_OPT(trunk_subbatch, 0, false)                                                                                  \
+    SPECMI_OPT(trunk_subbatch_layers, 2, false)                                                                           \
+    SPECMI_OPT(single_max_batch, 2, false)                                                                                \
+    SPECMI_OPT(latency_max_batch, 10, false)                                                                              \
+    SPECMI_OPT(latency_max_batch_single, 16, false)                                                                       \
+    SPECMI_OPT(latency_target_wgs, 256, false)                                                                            \
+    SPECMI_OPT(latency_min_chunks, 4, false)                                                                              \
+    SPECMI_OPT(latency_wino_min_tiles, 128, false)                                                                        \
+    SPECMI_OPT(latency_fill_wgs, 240, false)                                                                              \
+    SPECMI_OPT(latency_fill_wgs_large, 400, false)                                                                        \
+    SPECMI_OPT(latency_unit_model, 0, false)                                                                              \
+    SPECMI_OPT(latency_unit_slots, 256, false)                                                                            \
+    SPECMI_OPT(latency_force_unit, 0, false)                                                                              \
+    SPECMI_OPT(wsplit, 1, false)                                                                                          \
+    SPECMI_OPT(wsplit_max_units, 1400, false)                                                                             \
+    SPECMI_OPT(wsplit_max_units_single, 500, false)                                                                       \
+    SPECMI_OPT(wsplit_slots, 256, false)                                                                                  \
+    SPECMI_OPT(conv2d_sk, 0, false)                                                                                       \
+    SPECMI_OPT(conv2d_wsplit, 0, false)
+
+#define SPECMI_OPT(name, def, stable) OPT_##name,
+enum Opt { SPECMI_OPTIONS(SPECMI_OPT) OPT_COUNT };
+#undef SPECMI_OPT
+
 struct specmi_handle {
+    specmi_handle();                // options.hip: every option at its default
     int device = 0;
     int kind = 0;
     std::map<std::string, HostTensor> staged;
-    std::map<std::string, int> opt_i;
-    std::map<std::string, float> opt_f;
+    int opt[OPT_COUNT];             // one slot per integer option
+    float focal_length = 5000.f;    // the one float option (specmi_set_option_f32)
     bool committed = false;
     // SPECMI_PRECISION_*: what specmi_set_precision asked for, and what the last successful commit packed
     int precision = 0, committed_precision = 0;
@@ -138,7 +194,7 @@ int fail(specmi_handle* h, int code, const char* fmt, ...);
     } while (0)
 
 
-// ---- shared host helpers (api.hip; find / need: commit.hip; opt_i / opt_f: options.hip) -------------------------------------------------------------------------
+// ---- shared host helpers (api.hip; find / need: commit.hip) -------------------------------------------------------------------------
 int round_up(int x, int m);
 int conv_out(int x, int k, int s, int p);
 int dev_upload(specmi_handle* h, const void* src, size_t bytes, void** out, std::vector<void*>& pool);
@@ -146,8 +202,7 @@ int dev_alloc(specmi_handle* h, size_t bytes, void** out, std::vector<void*>& po
 void free_pool(std::vector<void*>& pool);
 const HostTensor* find(specmi_handle* h, const std::string& name);
 int need(specmi_handle* h, const std::string& name, std::initializer_list<int64_t> shape, bool is_int, const HostTensor** out);
-int opt_i(specmi_handle* h, const char* name, int dflt);
-float opt_f(specmi_handle* h, const char* name, float dflt);
+inline int opt(const specmi_handle* h, Opt o) { return h->opt[o]; }
 // ---- commit.hip: packing, BatchNorm folding, the composed regressor, layer tables, SMPL constants ----------
 // conv weight + eval-mode BatchNorm under state-dict names prefix + c.name / c.bn_name -> packed device tensors
 int commit_conv(specmi_handle* h, const std::string& prefix, ConvW& c);

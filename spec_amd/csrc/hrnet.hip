@@ -335,11 +335,11 @@ struct Runner {
         a.OH = conv_out(ih, c.k, c.stride, c.pad); a.OW = conv_out(iw, c.k, c.stride, c.pad);
         a.Cout = out_c; a.Npad = c.Npad; a.ldo = out_ld;
         a.KH = c.k; a.KW = c.k; a.stride = c.stride; a.pad = c.pad; a.relu = relu;
-        a.force_variant = opt_i(h, "force_conv_variant", 0);
-        a.wino_variant = opt_i(h, "force_wino_variant", 0);
+        a.force_variant = opt(h, OPT_force_conv_variant);
+        a.wino_variant = opt(h, OPT_force_wino_variant);
         LaunchCtx ctx{s, &h->prof, label};
         int rc;
-        if (c.wino && opt_i(h, "winograd", 1) && conv_wino_supported(a)) {
+        if (c.wino && opt(h, OPT_winograd) && conv_wino_supported(a)) {
             a.w = c.wino;
             rc = launch_conv_wino(a, ctx);
         } else {

@@ -80,10 +80,11 @@ STABLE = {'backbone': 50, 'num_fc_layers': 1, 'num_fc_channels': 1024, 'use_cam'
           'plan': 0, 'winograd': 1, 'fuse_downsample': 1, 'head_collapse': 1, 'output_ld': 0, 'angle_ld': 0, 'experimental': 0}
 
 
-def test_option_table_matches_header_and_call_sites(lib):
+def test_option_table_matches_header_and_readers(lib):
     """The library's option table is the single list: its stable part is exactly the frozen set with the documented defaults, every
-    name (and nothing else) is documented in include/specmi.h under the right heading, and the default of every ``opt_i(h, "name", N)``
-    call site in the sources equals the table's."""
+    name (and nothing else) is documented in include/specmi.h under the right heading, every option but ``experimental`` (the gate
+    itself) has a reader ``OPT_<name>`` in the sources, and no reader names an option by a string any more.
+    Default agreement needs no test: a reader is ``opt(h, OPT_<name>)`` and states no default; the list in handle.h is the only copy."""
     table = _option_table(lib)
     assert {k: v[0] for k, v in table.items() if v[1]} == STABLE
     hdr = open(os.path.join(ROOT, 'include', 'specmi.h')).read()
@@ -95,13 +96,15 @@ def test_option_table_matches_header_and_call_sites(lib):
     assert quoted(stable_doc) - {'focal_length'} <= {k for k, v in table.items() if v[1]}, quoted(stable_doc) - set(table)
     assert quoted(exp_doc) - {'experimental'} <= {k for k, v in table.items() if not v[1]}, quoted(exp_doc) - set(table)
     csrc = os.path.join(ROOT, 'spec_amd', 'csrc')
+    src = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith(('.hip', '.h', '.inc'))}
+    # the list itself spells SPECMI_OPT(name, ...), never OPT_name: every OPT_<name> token in the sources is a reader
     seen = set()
-    for f in sorted(os.listdir(csrc)):
-        if not f.endswith(('.hip', '.h', '.inc')):
-            continue
-        for name, dflt in re.findall(r'opt_i\(h[ab]?, "([a-z_0-9]+)", ([^)]*)\)', open(os.path.join(csrc, f)).read()):
-            assert name in table, f'{f}: opt_i reads an option the table does not list: {name}'
+    for f, text in src.items():
+        for name in re.findall(r'\bOPT_([a-z_0-9]+)\b', text):
+            assert name in table, f'{f}: OPT_{name} is not in the table'
             seen.add(name)
-            if re.fullmatch(r'-?\d+', dflt.strip()):
-                assert int(dflt) == table[name][0], f'{f}: call-site default of {name} is {dflt}, the table says {table[name][0]}'
-    assert seen == set(table) - {'experimental'}, set(table) ^ seen
+    assert seen - {'experimental'} == set(table) - {'experimental'}, set(table) ^ seen
+    for f, text in src.items():
+        assert not re.search(r'\bopt_[if]\s*\(', text), f'{f}: a by-name opt_i( / opt_f( read remains'
+        for args in re.findall(r'\bopt\s*\(([^()]*)\)', text):
+            assert not quoted(args) & set(table), f'{f}: opt( is given an option name as a string: {args}'

@@ -70,6 +70,34 @@ def test_experimental_opt_in_by_handle_and_by_environment(no_env, monkeypatch):
     a.close(); b.close()
 
 
+def test_each_option_has_its_own_slot_on_its_own_handle(no_env):
+    """Options are stored one slot per name on each handle: setting one changes that name on that handle and nothing else.
+    No kernel is launched."""
+    table = _option_table(_lib.load())
+    a, b = Engine('hmr', DEV), Engine('hmr', DEV)
+    a.experimental()
+    expect = {name: dflt for name, (dflt, _stable) in table.items()}
+    expect['experimental'] = 1
+    for name, (dflt, _stable) in table.items():
+        if name == 'experimental':
+            continue
+        a.set_option(name, dflt + 1)
+        expect[name] = dflt + 1
+        assert a.get_option(name) == dflt + 1, name
+        assert b.get_option(name) == dflt, name
+        assert {k: a.get_option(k) for k in table} == expect, name
+    assert {k: b.get_option(k) for k in table} == {k: v[0] for k, v in table.items()}
+    a.set_option('focal_length', 1234.0)
+    assert {k: a.get_option(k) for k in table} == expect                 # the float has a slot of its own too
+    with pytest.raises(_lib.SpecmiError) as e:
+        a.set_option('no_such_float', 1.0)
+    assert e.value.code == _lib.ERR_ARG and 'unknown float option' in str(e.value)
+    with pytest.raises(_lib.SpecmiError) as e:
+        a.get_option('focal_length')                                     # not in the integer table
+    assert e.value.code == _lib.ERR_ARG and 'unknown option' in str(e.value)
+    a.close(); b.close()
+
+
 def test_default_path_needs_no_experimental_option(no_env):
     """With SPECMI_EXPERIMENTAL unset (tests/conftest.py sets it for the tests that pin variants and flip opt-ins): fresh modules,
     commit, the whole pipeline under every stable plan, and the reference-composed fixture - the stable surface is all the drop-in
