@@ -3,6 +3,8 @@ device tensors (torch is plumbing here: HBM allocations + the current HIP stream
 from __future__ import annotations
 
 import ctypes as C
+import functools
+import math
 from typing import Dict, Mapping, Optional
 
 import numpy as np
@@ -11,6 +13,37 @@ import torch
 from . import _lib
 
 KIND = {'camcalib': _lib.MODEL_CAMCALIB, 'hmr': _lib.MODEL_HMR, 'smpl': _lib.MODEL_SMPL}
+
+# The packed per-image record, stated once: (key, per-image shape) in packing order, None = (num_verts, 3).
+# 85,164 B of SPEC outputs + 12 B of camera angles.  Every offset, every dense output shape and the all-gather payloads
+# (spec_amd.pipeline, which re-exports this table) derive from it through ``record_layout``.
+PACKED_KEYS = (
+    ('smpl_vertices', None), ('smpl_joints3d', (49, 3)), ('smpl_joints2d', (49, 2)),
+    ('pred_cam_t', (3,)), ('pred_pose', (24, 3, 3)), ('pred_cam', (3,)), ('pred_shape', (10,)),
+    ('pred_pose_6d', (144,)), ('cam_vfov', ()), ('cam_pitch', ()), ('cam_roll', ()),
+)
+# the vertices come first and are the only size that depends on the body model: everything after them is the joints payload
+assert PACKED_KEYS[0] == ('smpl_vertices', None) and all(shp is not None for _, shp in PACKED_KEYS[1:])
+_HMR_KEYS = tuple(k for k, _ in _lib.HmrOutputs._fields_)     # what the head + SMPL calls write: the record without the angles
+assert _HMR_KEYS == tuple(k for k, _ in PACKED_KEYS[:len(_HMR_KEYS)])
+_ROTMATS = dict(PACKED_KEYS)['pred_pose']                     # one rotation matrix per joint: also what smpl / smpl_native take
+
+
+@functools.lru_cache(maxsize=None)
+def record_layout(num_verts: int):
+    """((key, offset, per-image shape), ...) of the packed record in packing order, and its length in floats: 21,294 for
+    V = 6890.  Pure and cached per ``num_verts``: do not modify the result."""
+    lay, off = [], 0
+    for k, shp in PACKED_KEYS:
+        shp = (num_verts, 3) if shp is None else shp
+        lay.append((k, off, shp))
+        off += math.prod(shp)
+    return tuple(lay), off
+
+
+@functools.lru_cache(maxsize=None)
+def _record_shapes(num_verts: int):
+    return {k: shp for k, _, shp in record_layout(num_verts)[0]}
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -66,6 +99,17 @@ def out_dtype(dtype):
 def image_tensor(n, H, W, device, f16: bool):
     return (torch.empty(n, H, W, 8, device=device, dtype=torch.float16) if f16 else
             torch.empty(n, 3, H, W, device=device, dtype=torch.float32))
+
+
+def _image_out(out, n, H, W, f16: bool, device):
+    """The image a producer writes: a fresh ``image_tensor``, or the caller's ``out=`` checked for shape, dtype, contiguity and
+    device (a tensor on another device would hand the kernel a foreign pointer)."""
+    if out is None:
+        return image_tensor(n, H, W, device, f16)
+    shape, dtype = ((n, H, W, 8), torch.float16) if f16 else ((n, 3, H, W), torch.float32)
+    if tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != device:
+        raise ValueError(f'out must be a contiguous {shape} {dtype} device tensor')
+    return out
 
 
 class Engine:
@@ -194,27 +238,34 @@ class Engine:
     def record_layout(self):
         """[(key, offset, per-image shape)] of the packed record the kernels can write directly:
         85,164 B of SPEC outputs + 12 B of camera angles = 21,294 floats for V = 6890."""
-        lay, off = [], 0
-        for k, shp in (('smpl_vertices', (self.num_verts, 3)), ('smpl_joints3d', (49, 3)), ('smpl_joints2d', (49, 2)),
-                       ('pred_cam_t', (3,)), ('pred_pose', (24, 3, 3)), ('pred_cam', (3,)), ('pred_shape', (10,)),
-                       ('pred_pose_6d', (144,)), ('cam_vfov', ()), ('cam_pitch', ()), ('cam_roll', ())):
-            n = int(np.prod(shp)) if shp else 1
-            lay.append((k, off, shp))
-            off += n
-        return lay, off
+        lay, total = record_layout(self.num_verts)
+        return list(lay), total
 
     def record_views(self, record: torch.Tensor) -> Dict[str, torch.Tensor]:
         """Views of a (B, record_floats) record as the output dict (no copy)."""
-        lay, total = self.record_layout()
+        lay, total = record_layout(self.num_verts)
         if record.dim() != 2 or record.shape[1] != total or record.dtype != torch.float32 or record.stride(1) != 1:
             raise ValueError(f'record must be a (B, {total}) fp32 tensor with unit column stride')
         B = record.shape[0]
-        return {k: record[:, off:off + (int(np.prod(shp)) if shp else 1)].view(B, *shp) if shp
-                else record[:, off] for k, off, shp in lay}
+        return {k: record[:, off:off + math.prod(shp)].view(B, *shp) if shp else record[:, off] for k, off, shp in lay}
 
     # ---- forward ---------------------------------------------------------------------------
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _empty(self, *shape, dtype=torch.float32):
+        return torch.empty(*shape, device=self.device, dtype=dtype)
+
+    def _outputs(self, B, keys, views=None) -> Dict[str, torch.Tensor]:
+        """The output dict of a call that writes ``keys`` of the record: those views of the caller's record, else fresh dense
+        tensors of the table's shapes."""
+        if views is not None:
+            return {k: views[k] for k in keys}
+        shapes = _record_shapes(self.num_verts)
+        return {k: self._empty(B, *shapes[k]) for k in keys}
+
+    def _hmr_outputs(self, B) -> Dict[str, torch.Tensor]:
+        return self._outputs(B, _HMR_KEYS)
 
     def _images(self, images):
         if not isinstance(images, torch.Tensor) or images.device.type != 'cuda':
@@ -238,24 +289,18 @@ class Engine:
 
     def trunk(self, images):
         x, B, H, W, f16 = self._images_in(images)
-
-        def o(n, k, s, p):
-            return (n + 2 * p - k) // s + 1
-        fh, fw = H, W
-        fh, fw = o(fh, 7, 2, 3), o(fw, 7, 2, 3)
-        fh, fw = o(fh, 3, 2, 1), o(fw, 3, 2, 1)
-        for _ in range(3):
-            fh, fw = o(fh, 3, 2, 1), o(fw, 3, 2, 1)
-        feat = torch.empty(B, fh, fw, self.feat_channels, device=self.device, dtype=torch.float32)
+        feat = self._empty(B, *self._feat_shape(H, W), self.feat_channels)
         if B == 0:
             return feat
         fn = self.lib.specmi_trunk_forward_f16in if f16 else self.lib.specmi_trunk_forward
         _lib.check(self.h, fn(self.h, _ptr(x), B, H, W, _ptr(feat), self._stream()))
         return feat
 
-    def _feat_shape(self, H, W):
-        def o(n, k, s_, p):
-            return (n + 2 * p - k) // s_ + 1
+    @staticmethod
+    def _feat_shape(H, W):
+        """(fh, fw) of the trunk's feature map: the 7x7 stride-2 stem, then the max-pool and three stride-2 stages (3x3, pad 1)."""
+        def o(n, k, s, p):
+            return (n + 2 * p - k) // s + 1
         fh, fw = o(H, 7, 2, 3), o(W, 7, 2, 3)
         for _ in range(4):
             fh, fw = o(fh, 3, 2, 1), o(fw, 3, 2, 1)
@@ -269,8 +314,7 @@ class Engine:
             raise ValueError(f'grouped trunk launches need equal input shapes, got {tuple(xa.shape)} and {tuple(xb.shape)}')
         B, _, H, W = xa.shape
         fh, fw = self._feat_shape(H, W)
-        fa = torch.empty(B, fh, fw, self.feat_channels, device=self.device, dtype=torch.float32)
-        fb = torch.empty(B, fh, fw, other.feat_channels, device=self.device, dtype=torch.float32)
+        fa, fb = self._empty(B, fh, fw, self.feat_channels), self._empty(B, fh, fw, other.feat_channels)
         if B == 0:
             return fa, fb
         _lib.check(self.h, self.lib.specmi_trunk_forward_pair(self.h, other.h, _ptr(xa), _ptr(xb), B, H, W, _ptr(fa), _ptr(fb),
@@ -281,7 +325,7 @@ class Engine:
         """avg-pool + the three Linear chains of CameraRegressorNetwork.forward from a trunk feature map."""
         f = _dev_f32(feat_nhwc, self.device)
         B, fh, fw, _ = f.shape
-        out = torch.empty(3, B, self.nbins, device=self.device, dtype=torch.float32)
+        out = self._empty(3, B, self.nbins)
         if B == 0:
             return [out[0], out[1], out[2]]
         _lib.check(self.h, self.lib.specmi_camcalib_head_forward(self.h, _ptr(f), B, fh, fw, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
@@ -290,7 +334,7 @@ class Engine:
 
     def camcalib_forward(self, images):
         x, B, H, W, f16 = self._images_in(images)
-        out = torch.empty(3, B, self.nbins, device=self.device, dtype=torch.float32)
+        out = self._empty(3, B, self.nbins)
         if B == 0:                      # an empty batch gives empty outputs, as the reference's torch modules do
             return [out[0], out[1], out[2]]
         fn = self.lib.specmi_camcalib_forward_f16in if f16 else self.lib.specmi_camcalib_forward
@@ -303,10 +347,19 @@ class Engine:
         ([logits_vfov, logits_pitch, logits_roll], dict(vfov, pitch, roll, f_pix, cam_rotmat, cam_intrinsics))."""
         f = _dev_f32(feat_nhwc, self.device)
         B, fh, fw, _ = f.shape
-        out = torch.empty(3, B, self.nbins, device=self.device, dtype=torch.float32)
+        out = self._empty(3, B, self.nbins)
         img_h = _dev_f32(img_h, self.device, (B,))
         img_w = _dev_f32(img_w, self.device, (B,))
-        mk = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
+        cam = self._camera_outputs(B, img_h, img_w, angles_out)
+        if B > 0:
+            _lib.check(self.h, self.lib.specmi_camcalib_head_decode(
+                self.h, _ptr(f), B, fh, fw, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(img_h), _ptr(img_w),
+                *(_ptr(t) for t in cam.values()), self._stream()))
+        return [out[0], out[1], out[2]], cam
+
+    def _camera_outputs(self, B, img_h, img_w, angles_out) -> Dict[str, Optional[torch.Tensor]]:
+        """What a decode call writes, in the order of its pointer arguments; sets the handle's angle stride ("angle_ld") for
+        ``angles_out`` (see ``camcalib_decode``)."""
         if angles_out is not None:
             vf, pt, rl = angles_out
             ld = vf.stride(0) if B > 1 else 1
@@ -314,16 +367,11 @@ class Engine:
                 raise ValueError('angles_out: three (B,) fp32 tensors with one common stride')
             self._set_ld('angle_ld', ld if ld != 1 else 0)
         else:
-            vf, pt, rl = mk(B), mk(B), mk(B)
+            vf, pt, rl = self._empty(B), self._empty(B), self._empty(B)
             self._set_ld('angle_ld', 0)
-        fp = mk(B) if img_h is not None else None
-        R = mk(B, 3, 3)
-        K = mk(B, 3, 3) if (img_h is not None and img_w is not None) else None
-        if B > 0:
-            _lib.check(self.h, self.lib.specmi_camcalib_head_decode(
-                self.h, _ptr(f), B, fh, fw, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(img_h), _ptr(img_w), _ptr(vf), _ptr(pt),
-                _ptr(rl), _ptr(fp), _ptr(R), _ptr(K), self._stream()))
-        return [out[0], out[1], out[2]], {'vfov': vf, 'pitch': pt, 'roll': rl, 'f_pix': fp, 'cam_rotmat': R, 'cam_intrinsics': K}
+        return {'vfov': vf, 'pitch': pt, 'roll': rl, 'f_pix': self._empty(B) if img_h is not None else None,
+                'cam_rotmat': self._empty(B, 3, 3),
+                'cam_intrinsics': self._empty(B, 3, 3) if (img_h is not None and img_w is not None) else None}
 
     def camcalib_decode(self, lv, lp, lr, img_h=None, img_w=None, angles_out=None):
         """``angles_out``: optional (vfov, pitch, roll) tensors of shape (B,) with a common element stride
@@ -332,23 +380,10 @@ class Engine:
         B, nb = lv.shape
         img_h = _dev_f32(img_h, self.device, (B,))
         img_w = _dev_f32(img_w, self.device, (B,))
-        mk = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
-        if angles_out is not None:
-            vf, pt, rl = angles_out
-            ld = vf.stride(0) if B > 1 else 1
-            if any(t.shape != (B,) or t.dtype != torch.float32 or (B > 1 and t.stride(0) != ld) for t in (vf, pt, rl)):
-                raise ValueError('angles_out: three (B,) fp32 tensors with one common stride')
-            self._set_ld('angle_ld', ld if ld != 1 else 0)
-        else:
-            vf, pt, rl = mk(B), mk(B), mk(B)
-            self._set_ld('angle_ld', 0)
-        f = mk(B) if img_h is not None else None
-        R = mk(B, 3, 3)
-        K = mk(B, 3, 3) if (img_h is not None and img_w is not None) else None
+        cam = self._camera_outputs(B, img_h, img_w, angles_out)
         _lib.check(self.h, self.lib.specmi_camcalib_decode(
-            self.h, _ptr(lv), _ptr(lp), _ptr(lr), B, nb, _ptr(img_h), _ptr(img_w), _ptr(vf), _ptr(pt),
-            _ptr(rl), _ptr(f), _ptr(R), _ptr(K), self._stream()))
-        return {'vfov': vf, 'pitch': pt, 'roll': rl, 'f_pix': f, 'cam_rotmat': R, 'cam_intrinsics': K}
+            self.h, _ptr(lv), _ptr(lp), _ptr(lr), B, nb, _ptr(img_h), _ptr(img_w), *(_ptr(t) for t in cam.values()), self._stream()))
+        return cam
 
     def camcalib_bins(self, logits, argmax=True, soft=False):
         """Per-row argmax (int32) and / or normalised soft-argmax of (..., nbins) device logits."""
@@ -377,9 +412,8 @@ class Engine:
         gt = [_dev_f32(g, self.device, (B,)) for g in gts]
         if any(t.shape != (B,) for t in tg):
             raise ValueError('targets: three (B,) arrays')
-        mk = lambda dt=torch.float32: torch.empty(3, B, device=self.device, dtype=dt)
-        res = {'loss_term': mk(), 'argmax': mk(torch.int32), 'soft': mk(), 'angle': mk(), 'err': mk(),
-               'means': torch.empty(7, device=self.device, dtype=torch.float32)}
+        res = {'loss_term': self._empty(3, B), 'argmax': self._empty(3, B, dtype=torch.int32), 'soft': self._empty(3, B),
+               'angle': self._empty(3, B), 'err': self._empty(3, B), 'means': self._empty(7)}
         if B > 0:
             _lib.check(self.h, self.lib.specmi_camcalib_eval(
                 self.h, _ptr(lv), _ptr(lp), _ptr(lr), B, nb, _lib.LOSS_TYPES[loss_type], _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]),
@@ -401,11 +435,7 @@ class Engine:
         if n < 1 or offsets.shape[0] != n:
             raise ValueError('one offset and one [H, W, OH, OW] row per frame (at least one frame)')
         Hmax, Wmax = int(geom[:, 2].max()), int(geom[:, 3].max())
-        shape = (n, Hmax, Wmax, 8) if f16 else (n, 3, Hmax, Wmax)
-        if out is None:
-            out = image_tensor(n, Hmax, Wmax, self.device, f16)
-        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f'out must be a contiguous {shape} {dtype} device tensor')
+        out = _image_out(out, n, Hmax, Wmax, f16, self.device)
         fn = self.lib.specmi_resize_normalize_ragged_f16 if f16 else self.lib.specmi_resize_normalize_ragged
         _lib.check(self.h, fn(
             self.h, _ptr(slab.contiguous()), slab.numel(), offsets.ctypes.data_as(_lib.c_int64_p), geom.ctypes.data_as(_lib.c_int32_p),
@@ -445,12 +475,6 @@ class Engine:
                 _dev_f32(bbox_scale, d, (B,)), _dev_f32(bbox_center, d, (B, 2)),
                 _dev_f32(img_w, d, (B,)), _dev_f32(img_h, d, (B,)))
 
-    def _hmr_outputs(self, B) -> Dict[str, torch.Tensor]:
-        mk = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
-        return {'smpl_vertices': mk(B, self.num_verts, 3), 'smpl_joints3d': mk(B, 49, 3),
-                'smpl_joints2d': mk(B, 49, 2), 'pred_cam_t': mk(B, 3), 'pred_pose': mk(B, 24, 3, 3),
-                'pred_cam': mk(B, 3), 'pred_shape': mk(B, 10), 'pred_pose_6d': mk(B, 144)}
-
     def _out_for(self, B, record):
         """Output dict + the handle's output stride: dense tensors, or views of a (B, record_floats) record the
         kernels write in place."""
@@ -472,7 +496,7 @@ class Engine:
         out = views if views is not None else (out if out is not None else self._hmr_outputs(B))
         if B == 0:
             return out
-        o = _lib.HmrOutputs(**{k: out[k].data_ptr() for k, _ in _lib.HmrOutputs._fields_})
+        o = _lib.HmrOutputs(**{k: out[k].data_ptr() for k in _HMR_KEYS})
         fn = self.lib.specmi_hmr_forward_f16in if f16 else self.lib.specmi_hmr_forward
         _lib.check(self.h, fn(
             self.h, _ptr(x), B, H, W, _ptr(R), _ptr(K), _ptr(sc), _ptr(ce), _ptr(iw), _ptr(ih),
@@ -489,7 +513,7 @@ class Engine:
         out = views if views is not None else self._hmr_outputs(B)
         if B == 0:                      # empty batch: empty outputs, like hmr_forward / trunk
             return out
-        o = _lib.HmrOutputs(**{k: out[k].data_ptr() for k, _ in _lib.HmrOutputs._fields_})
+        o = _lib.HmrOutputs(**{k: out[k].data_ptr() for k in _HMR_KEYS})
         _lib.check(self.h, self.lib.specmi_hmr_regress(
             self.h, _ptr(f), B, fh, fw, _ptr(R), _ptr(K), _ptr(sc), _ptr(ce), _ptr(iw), _ptr(ih),
             C.byref(o), self._stream()))
@@ -498,8 +522,7 @@ class Engine:
     def hmr_uncertainty(self, B: int):
         """(pred_pose_var (B, 288), pred_shape_var (B, 20)) of a model committed with ``estimate_var``: call right after the head
         forward of the same batch on the same stream (``specmi_hmr_uncertainty``)."""
-        pv = torch.empty(B, 288, device=self.device, dtype=torch.float32)
-        sv = torch.empty(B, 20, device=self.device, dtype=torch.float32)
+        pv, sv = self._empty(B, 288), self._empty(B, 20)
         if B > 0:
             _lib.check(self.h, self.lib.specmi_hmr_uncertainty(self.h, int(B), _ptr(pv), _ptr(sv), self._stream()))
         return pv, sv
@@ -510,10 +533,7 @@ class Engine:
         R = _dev_f32(cam_rotmat, self.device, (B, 3, 3))
         K = _dev_f32(cam_intrinsics, self.device, (B, 3, 3))
         ih = _dev_f32(img_h, self.device, (B,))
-        mk = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
-        views = self._out_for(B, record)
-        out = ({k: views[k] for k in ('pred_pose', 'pred_shape', 'pred_cam', 'pred_pose_6d')} if views is not None else
-               {'pred_pose': mk(B, 24, 3, 3), 'pred_shape': mk(B, 10), 'pred_cam': mk(B, 3), 'pred_pose_6d': mk(B, 144)})
+        out = self._outputs(B, ('pred_pose', 'pred_shape', 'pred_cam', 'pred_pose_6d'), self._out_for(B, record))
         if B == 0:
             return out
         _lib.check(self.h, self.lib.specmi_hmr_head_forward(
@@ -525,16 +545,11 @@ class Engine:
              bbox_center=None, img_w=None, img_h=None, record=None):
         rot = _dev_f32(rotmat, self.device)
         B = rot.shape[0]
-        rot = rot.reshape(B, 24, 3, 3).contiguous()
+        rot = rot.reshape(B, *_ROTMATS).contiguous()
         be = _dev_f32(betas, self.device, (B, 10))
         cm = _dev_f32(cam, self.device, (B, 3))
         R, K, sc, ce, iw, ih = self._cam_args(B, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h)
-        mk = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
-        views = self._out_for(B, record)
-        out = ({k: views[k] for k in ('smpl_vertices', 'smpl_joints3d', 'smpl_joints2d', 'pred_cam_t')}
-               if views is not None else
-               {'smpl_vertices': mk(B, self.num_verts, 3), 'smpl_joints3d': mk(B, 49, 3),
-                'smpl_joints2d': mk(B, 49, 2), 'pred_cam_t': mk(B, 3)})
+        out = self._outputs(B, ('smpl_vertices', 'smpl_joints3d', 'smpl_joints2d', 'pred_cam_t'), self._out_for(B, record))
         if B == 0:
             return out
         _lib.check(self.h, self.lib.specmi_smpl_forward(
@@ -549,12 +564,11 @@ class Engine:
         p = _dev_f32(pose, self.device)
         B = p.shape[0]
         aa = p.dim() == 2
-        if aa and p.shape[1] != 72 or not aa and tuple(p.shape[1:]) != (24, 3, 3):
+        if aa and p.shape[1] != 72 or not aa and tuple(p.shape[1:]) != _ROTMATS:
             raise ValueError(f'pose must be (B,72) axis-angle or (B,24,3,3) rotation matrices, got {tuple(p.shape)}')
         be = _dev_f32(betas, self.device, (B, 10))
-        mk = lambda *s: torch.empty(*s, device=self.device, dtype=torch.float32)
-        v = mk(B, self.num_verts, 3) if vertices else None
-        j = mk(B, 24, 3) if joints24 else None
+        v = self._empty(B, self.num_verts, 3) if vertices else None
+        j = self._empty(B, 24, 3) if joints24 else None
         self._set_ld('output_ld', 0)
         _lib.check(self.h, self.lib.specmi_smpl_native(self.h, _ptr(p), int(aa), _ptr(be), B, _ptr(v), _ptr(j),
                                                        self._stream()))

@@ -10,18 +10,31 @@ and a single RCCL all-gather over xGMI collects them.
 """
 from __future__ import annotations
 
+import contextlib
+import math
 from typing import Dict
 
 import torch
 
 from . import cam_utils
+from .engine import PACKED_KEYS, record_layout    # the packed record's one table and layout (re-exported here)
 
-# (key, per-image shape) in packing order: 85,164 B of SPEC outputs + 12 B of camera angles
-PACKED_KEYS = (
-    ('smpl_vertices', None), ('smpl_joints3d', (49, 3)), ('smpl_joints2d', (49, 2)),
-    ('pred_cam_t', (3,)), ('pred_pose', (24, 3, 3)), ('pred_cam', (3,)), ('pred_shape', (10,)),
-    ('pred_pose_6d', (144,)), ('cam_vfov', ()), ('cam_pitch', ()), ('cam_roll', ()),
-)
+
+@contextlib.contextmanager
+def _forked(side):
+    """Run the body on the stream ``side``, after everything the current stream has enqueued so far (the body's inputs)."""
+    side.wait_stream(torch.cuda.current_stream(side.device))
+    with torch.cuda.stream(side):
+        yield
+
+
+def _join(side, tensors):
+    """The current stream waits for ``side`` and takes over the tensors (a dict, None entries allowed) produced there."""
+    main = torch.cuda.current_stream(side.device)
+    main.wait_stream(side)
+    for v in tensors.values():
+        if v is not None:
+            v.record_stream(main)
 
 
 class SpecPipeline:
@@ -116,7 +129,7 @@ class SpecPipeline:
         eng = self.hmr.engine(device)
         angles = None
         if record is None and self.packed and self.hmr.use_cam:
-            record = torch.empty(images.shape[0], eng.record_layout()[1], device=device, dtype=torch.float32)
+            record = torch.empty(images.shape[0], record_layout(eng.num_verts)[1], device=device, dtype=torch.float32)
         if record is not None:
             v = eng.record_views(record)
             angles = (v['cam_vfov'], v['cam_pitch'], v['cam_roll'])
@@ -140,17 +153,12 @@ class SpecPipeline:
                 out = self.hmr(images, cam_rotmat=cam['cam_rotmat'], cam_intrinsics=cam['cam_intrinsics'],
                                bbox_scale=bbox_scale, bbox_center=bbox_center, img_w=img_w, img_h=img_h)
         else:
-            main = torch.cuda.current_stream(device)
             side = self._side_stream(device, lambda: eng.trunk(images))
-            side.wait_stream(main)                      # inputs were produced on the main stream
-            with torch.cuda.stream(side):
+            with _forked(side):
                 ceng = self.camcalib.engine(device)
                 logits, cam = ceng.camcalib_head_decode(ceng.trunk(cam_in), img_h=img_h, img_w=img_w, angles_out=angles)
             feat = eng.trunk(images)                    # SPEC trunk on the main stream, concurrently
-            main.wait_stream(side)                      # the head needs (R, K)
-            for v in cam.values():
-                if v is not None:
-                    v.record_stream(main)
+            _join(side, cam)                            # the head needs (R, K)
             out = eng.hmr_regress(feat, cam['cam_rotmat'], cam['cam_intrinsics'], bbox_scale, bbox_center, img_w, img_h,
                                   record=record)
         out = dict(out)
@@ -162,45 +170,55 @@ class SpecPipeline:
         return out
 
 
-class GraphedPipeline:
-    """The whole step captured once into a hipGraph (via torch.cuda.CUDAGraph) and replayed: for
-    small batches the ~130 kernel launches of a step are launch-bound, a replay costs one
-    submission.  Inputs are copied into static buffers; outputs are the static output tensors
-    (valid until the next call)."""
+class GraphedStep:
+    """Any no-host-sync step ``fn(*tensors) -> dict`` captured once into a hipGraph (via torch.cuda.CUDAGraph) and replayed;
+    inputs are copied into static buffers unless they already are those buffers (``static_in``), outputs are the static output
+    tensors (valid until the next call)."""
 
-    def __init__(self, pipeline: SpecPipeline, images, bbox_scale, bbox_center, img_w, img_h, warmup: int = 2,
-                 buffers: int = 1):
+    def __init__(self, fn, *inputs, warmup: int = 2, buffers: int = 1):
         """``buffers`` > 1 captures that many graphs, each writing its own static output set, replayed round-robin:
         a consumer (e.g. the asynchronous all-gather of step s) may still read buffer s % buffers while step s+1
         runs."""
-        self.static_in = [t.clone() for t in (images, bbox_scale, bbox_center, img_w, img_h)]     # images: fp32 NCHW or NHWC8 fp16, as given
-        self.image_dtype = self.static_in[0].dtype
+        self.static_in = [t.clone() for t in inputs]
         for _ in range(warmup):                      # allocates workspaces, sets kernel attributes
-            pipeline(*self.static_in)
+            fn(*self.static_in)
         torch.cuda.synchronize()
         self.graphs, self.static_outs, self.turn = [], [], 0
-        for i in range(max(1, buffers)):
+        for _ in range(max(1, buffers)):
             g = torch.cuda.CUDAGraph()
             # thread-local error mode: another thread's runtime calls (e.g. the RCCL watchdog's event queries in a
             # multi-GPU job) must not invalidate this capture
             kw = {'pool': self.graphs[0].pool()} if self.graphs else {}
             with torch.cuda.graph(g, capture_error_mode='thread_local', **kw):
-                out = pipeline(*self.static_in)
+                self.static_outs.append(fn(*self.static_in))
             self.graphs.append(g)
-            if isinstance(out, dict) and out.get('record') is not None:
-                out['record'].specmi_static_buffers = max(1, buffers)   # replay overwrites this record: AsyncGather must not send it blindly
-            self.static_outs.append(out)
         self.graph, self.static_out = self.graphs[0], self.static_outs[0]
 
     @torch.no_grad()
-    def __call__(self, images, bbox_scale, bbox_center, img_w, img_h):
-        for dst, src in zip(self.static_in, (images, bbox_scale, bbox_center, img_w, img_h)):
+    def __call__(self, *inputs):
+        for dst, src in zip(self.static_in, inputs):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
         i = self.turn
         self.turn = (i + 1) % len(self.graphs)
         self.graphs[i].replay()
         return self.static_outs[i]
+
+
+class GraphedPipeline(GraphedStep):
+    """The whole ``SpecPipeline`` step as a ``GraphedStep``: for small batches the ~130 kernel launches of a step are
+    launch-bound, a replay costs one submission.  ``images``: fp32 NCHW or NHWC8 fp16, as given (``image_dtype``)."""
+
+    def __init__(self, pipeline: SpecPipeline, images, bbox_scale, bbox_center, img_w, img_h, warmup: int = 2,
+                 buffers: int = 1):
+        super().__init__(pipeline, images, bbox_scale, bbox_center, img_w, img_h, warmup=warmup, buffers=buffers)
+        self.image_dtype = self.static_in[0].dtype
+        for out in self.static_outs:
+            if isinstance(out, dict) and out.get('record') is not None:
+                out['record'].specmi_static_buffers = len(self.graphs)   # replay overwrites this record: AsyncGather must not send it blindly
+
+    def __call__(self, images, bbox_scale, bbox_center, img_w, img_h):
+        return super().__call__(images, bbox_scale, bbox_center, img_w, img_h)
 
 
 class DemoPipeline:
@@ -242,21 +260,16 @@ class DemoPipeline:
             logits = self.camcalib(cam_in)
             return cam_utils.decode_camera(logits[0], logits[1], logits[2], img_h=fh, img_w=fw)
 
-        main = torch.cuda.current_stream(device)
         if self.overlap:
             if device not in self._side:
                 self._side[device] = torch.cuda.Stream(device=device)
             side = self._side[device]
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
+            with _forked(side):
                 cam = cam_side()
         crops = crop_detections_batch(frames_u8, frame_index, boxes, scale=1.0, crop_size=self.crop_size, dtype=crop_dtype)
         feat = eng.trunk(crops['inp_images'])
         if self.overlap:
-            main.wait_stream(side)
-            for v in cam.values():
-                if v is not None:
-                    v.record_stream(main)
+            _join(side, cam)
         else:
             cam = cam_side()
         fi = frame_index.long()
@@ -268,28 +281,6 @@ class DemoPipeline:
                     'cam_rotmat': cam['cam_rotmat'], 'cam_intrinsics': cam['cam_intrinsics'], 'bbox_scale': crops['bbox_scale'],
                     'bbox_center': crops['bbox_center']})
         return out
-
-
-class GraphedStep:
-    """Any no-host-sync step ``fn(*tensors) -> dict`` captured once into a hipGraph and replayed; inputs are copied into static
-    buffers unless they already are those buffers (``static_in``), outputs are the static output tensors."""
-
-    def __init__(self, fn, *inputs, warmup: int = 2):
-        self.static_in = [t.clone() for t in inputs]
-        for _ in range(warmup):
-            fn(*self.static_in)
-        torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
-            self.static_out = fn(*self.static_in)
-
-    @torch.no_grad()
-    def __call__(self, *inputs):
-        for dst, src in zip(self.static_in, inputs):
-            if dst.data_ptr() != src.data_ptr():
-                dst.copy_(src)
-        self.graph.replay()
-        return self.static_out
 
 
 def shard_range(total: int, rank: int, world: int):
@@ -312,18 +303,18 @@ def pack_outputs(out: Dict[str, torch.Tensor]) -> torch.Tensor:
 
 def unpack_outputs(packed: torch.Tensor, num_verts: int) -> Dict[str, torch.Tensor]:
     B = packed.shape[0]
-    res, off = {}, 0
-    for k, shp in PACKED_KEYS:
-        shp = (num_verts, 3) if shp is None else shp
-        n = 1
-        for s in shp:
-            n *= s
-        res[k] = packed[:, off:off + n].reshape(B, *shp)
-        off += n
-    return res
+    return {k: packed[:, off:off + math.prod(shp)].reshape(B, *shp) for k, off, shp in record_layout(num_verts)[0]}
 
 
-JOINT_KEYS = tuple(k for k, _ in PACKED_KEYS if k != 'smpl_vertices')
+JOINT_KEYS = tuple(k for k, _ in PACKED_KEYS[1:])      # the record without its vertices, which come first (asserted beside the table)
+
+
+def _joint_columns(width: int):
+    """[start, stop) of the joint columns in a record of ``width`` floats per image: the run after ``smpl_vertices``."""
+    lay, total = record_layout((width - record_layout(0)[1]) // 3)
+    if total != width:
+        raise ValueError(f'{width} floats per image is not a packed record of any vertex count')
+    return lay[1][1], total
 
 
 def joints_payload(out: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -331,24 +322,16 @@ def joints_payload(out: Dict[str, torch.Tensor]) -> torch.Tensor:
     camera angles = 624 floats = 2,496 B per image) as a fresh contiguous (B, 624) tensor: 0.64 MB per rank at B = 256
     instead of 21.8 MB.  Always a copy (the columns are a strided slice of the record)."""
     rec = out.get('record')
-    B = out['pred_cam'].shape[0]
     if rec is not None:
-        nj = sum(out[k].reshape(B, -1).shape[1] for k in JOINT_KEYS)
-        return rec[:, rec.shape[1] - nj:].contiguous()
+        start, stop = _joint_columns(rec.shape[1])
+        return rec[:, start:stop].contiguous()
+    B = out['pred_cam'].shape[0]
     return torch.cat([out[k].reshape(B, -1) for k in JOINT_KEYS], dim=1).contiguous()
 
 
 def unpack_joints(packed: torch.Tensor) -> Dict[str, torch.Tensor]:
-    B = packed.shape[0]
-    res, off = {}, 0
-    for k, shp in PACKED_KEYS:
-        if shp is None:
-            continue
-        n = 1
-        for s_ in shp:
-            n *= s_
-        res[k] = packed[:, off:off + n].reshape(B, *shp)
-        off += n
+    res = unpack_outputs(packed, 0)        # a record of a body without vertices is exactly the joints payload
+    del res['smpl_vertices']
     return res
 
 

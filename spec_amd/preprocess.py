@@ -13,7 +13,32 @@ import torch
 
 from . import _lib
 from .cam_utils import _engine
-from .engine import _dev_f32, _ptr, image_tensor, out_dtype
+from .engine import _dev_f32, _image_out, _ptr, image_tensor, out_dtype
+
+
+def _frame_arg(name, t):
+    """One frame for the producer ``name``: an (H,W,3) uint8 device tensor -> contiguous."""
+    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+        raise RuntimeError(f'{name} needs a device tensor (no CPU path in spec_amd)')
+    if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3:
+        raise ValueError(f'{name}: frame must be (H,W,3) uint8 RGB')
+    return t.contiguous()
+
+
+def _slab_arg(name, t):
+    """A slab of equal-sized frames for the producer ``name``: a contiguous (F,H,W,3) uint8 device tensor."""
+    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda':
+        raise RuntimeError(f'{name} needs a device tensor (no CPU path in spec_amd)')
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3 or not t.is_contiguous():
+        raise ValueError(f'{name}: frames must be a contiguous (F,H,W,3) uint8 RGB slab')
+    return t
+
+
+def _boxes_arg(dets, dev):
+    boxes = _dev_f32(dets, dev)
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise ValueError('dets must be (n,4) [cx, cy, w, h]')
+    return boxes
 
 
 @torch.no_grad()
@@ -25,16 +50,10 @@ def crop_detections(frame_rgb_u8, dets, scale: float = 1.0, crop_size: int = 224
     of a larger batch buffer) to write into instead of allocating.  ``dtype=torch.float16``: ``inp_images`` is (n,S,S,8) NHWC8
     fp16 (the batch call with one frame)."""
     f16 = out_dtype(dtype)
-    if not isinstance(frame_rgb_u8, torch.Tensor) or frame_rgb_u8.device.type != 'cuda':
-        raise RuntimeError('crop_detections needs a device tensor (no CPU path in spec_amd)')
-    if frame_rgb_u8.dtype != torch.uint8 or frame_rgb_u8.dim() != 3 or frame_rgb_u8.shape[2] != 3:
-        raise ValueError('frame must be (H,W,3) uint8 RGB')
-    eng = _engine(frame_rgb_u8.device)
+    frame = _frame_arg('crop_detections', frame_rgb_u8)
+    eng = _engine(frame.device)
     dev = eng.device
-    frame = frame_rgb_u8.contiguous()
-    boxes = _dev_f32(dets, dev)
-    if boxes.dim() != 2 or boxes.shape[1] != 4:
-        raise ValueError('dets must be (n,4) [cx, cy, w, h]')
+    boxes = _boxes_arg(dets, dev)
     n, (H, W) = boxes.shape[0], frame.shape[:2]
     img, sc, ce = _crop_outputs(out, n, crop_size, dev, f16)
     raw = torch.empty(n, crop_size, crop_size, 3, device=dev, dtype=torch.uint8) if return_raw else None
@@ -54,9 +73,8 @@ def _crop_outputs(out, n, crop_size, dev, f16=False):
     if out is None:
         return (image_tensor(n, crop_size, crop_size, dev, f16),
                 torch.empty(n, device=dev, dtype=torch.float32), torch.empty(n, 2, device=dev, dtype=torch.float32))
-    img, sc, ce = out['inp_images'], out['bbox_scale'], out['bbox_center']
-    img_shape = (n, crop_size, crop_size, 8) if f16 else (n, 3, crop_size, crop_size)
-    for t_, shp, dt in ((img, img_shape, torch.float16 if f16 else torch.float32), (sc, (n,), torch.float32), (ce, (n, 2), torch.float32)):
+    img, sc, ce = _image_out(out['inp_images'], n, crop_size, crop_size, f16, dev), out['bbox_scale'], out['bbox_center']
+    for t_, shp, dt in ((sc, (n,), torch.float32), (ce, (n, 2), torch.float32)):
         if tuple(t_.shape) != shp or t_.dtype != dt or not t_.is_contiguous() or t_.device != dev:
             raise ValueError(f'out tensor must be a contiguous {dt} device tensor of shape {shp}, got {tuple(t_.shape)} {t_.dtype}')
     return img, sc, ce
@@ -69,15 +87,10 @@ def crop_detections_batch(frames_u8, frame_index, dets, scale: float = 1.0, crop
     dict as ``crop_detections`` for all n crops, bit-identical to cutting them frame by frame.  ``dtype=torch.float16``:
     ``inp_images`` is (n,S,S,8) NHWC8 fp16 (``specmi_crop_normalize_batch_f16``)."""
     f16 = out_dtype(dtype)
-    if not isinstance(frames_u8, torch.Tensor) or frames_u8.device.type != 'cuda':
-        raise RuntimeError('crop_detections_batch needs a device tensor (no CPU path in spec_amd)')
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
-        raise ValueError('frames must be a contiguous (F,H,W,3) uint8 RGB slab')
+    frames_u8 = _slab_arg('crop_detections_batch', frames_u8)
     eng = _engine(frames_u8.device)
     dev = eng.device
-    boxes = _dev_f32(dets, dev)
-    if boxes.dim() != 2 or boxes.shape[1] != 4:
-        raise ValueError('dets must be (n,4) [cx, cy, w, h]')
+    boxes = _boxes_arg(dets, dev)
     n = boxes.shape[0]
     fidx = frame_index if isinstance(frame_index, torch.Tensor) else torch.as_tensor(frame_index)
     F, H, W = frames_u8.shape[:3]
@@ -130,12 +143,8 @@ def dataset_crops(frame_rgb_u8, centers, scales, crop_size: int = 224, dtype=tor
     box copy + cv2.resize bilinear) + clip + ``/ 255`` + ImageNet Normalize.  frame (H,W,3) uint8 device tensor, centers (n,2),
     scales (n,) (bbox height / 200) -> (n,3,S,S) fp32, or (n,S,S,8) NHWC8 fp16 with ``dtype=torch.float16``."""
     f16 = out_dtype(dtype)
-    if not isinstance(frame_rgb_u8, torch.Tensor) or frame_rgb_u8.device.type != 'cuda':
-        raise RuntimeError('dataset_crops needs a device tensor (no CPU path in spec_amd)')
-    if frame_rgb_u8.dtype != torch.uint8 or frame_rgb_u8.dim() != 3 or frame_rgb_u8.shape[2] != 3:
-        raise ValueError('frame must be (H,W,3) uint8 RGB')
-    eng = _engine(frame_rgb_u8.device)
-    frame = frame_rgb_u8.contiguous()
+    frame = _frame_arg('dataset_crops', frame_rgb_u8)
+    eng = _engine(frame.device)
     boxes = torch.from_numpy(pare_crop_boxes(centers, scales, crop_size)).to(eng.device)
     n, (H, W) = boxes.shape[0], frame.shape[:2]
     out = image_tensor(n, crop_size, crop_size, eng.device, f16)
@@ -159,12 +168,8 @@ def camcalib_transform(frame_rgb_u8, min_size: int = 600, return_raw: bool = Fal
     (``specmi_resize_normalize``), bit-identical to Pillow + torchvision.  frame (H,W,3) uint8 device tensor ->
     (1,3,oh,ow) fp32 [, (oh,ow,3) uint8]; ``dtype=torch.float16``: (1,oh,ow,8) NHWC8 fp16 (``specmi_resize_normalize_f16``)."""
     f16 = out_dtype(dtype)
-    if not isinstance(frame_rgb_u8, torch.Tensor) or frame_rgb_u8.device.type != 'cuda':
-        raise RuntimeError('camcalib_transform needs a device tensor (no CPU path in spec_amd)')
-    if frame_rgb_u8.dtype != torch.uint8 or frame_rgb_u8.dim() != 3 or frame_rgb_u8.shape[2] != 3:
-        raise ValueError('frame must be (H,W,3) uint8 RGB')
-    eng = _engine(frame_rgb_u8.device)
-    frame = frame_rgb_u8.contiguous()
+    frame = _frame_arg('camcalib_transform', frame_rgb_u8)
+    eng = _engine(frame.device)
     H, W = frame.shape[:2]
     ow, oh = resize_output_size(W, H, min_size)
     out = image_tensor(1, oh, ow, eng.device, f16)
@@ -181,18 +186,11 @@ def camcalib_transform_batch(frames_u8, min_size: int = 600, out=None, dtype=tor
     per frame, ``scripts/camcalib_demo.py:95-102``); each frame's pixels are bit-identical to the single-frame call.
     ``dtype=torch.float16``: (F,oh,ow,8) NHWC8 fp16."""
     f16 = out_dtype(dtype)
-    if not isinstance(frames_u8, torch.Tensor) or frames_u8.device.type != 'cuda':
-        raise RuntimeError('camcalib_transform_batch needs a device tensor (no CPU path in spec_amd)')
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
-        raise ValueError('frames must be a contiguous (F,H,W,3) uint8 RGB slab')
+    frames_u8 = _slab_arg('camcalib_transform_batch', frames_u8)
     eng = _engine(frames_u8.device)
     F, H, W = frames_u8.shape[:3]
     ow, oh = resize_output_size(W, H, min_size)
-    shape = (F, oh, ow, 8) if f16 else (F, 3, oh, ow)
-    if out is None:
-        out = image_tensor(F, oh, ow, eng.device, f16)
-    elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous():
-        raise ValueError(f'out must be a contiguous {shape} {dtype} tensor')
+    out = _image_out(out, F, oh, ow, f16, eng.device)
     fn = eng.lib.specmi_resize_normalize_f16 if f16 else eng.lib.specmi_resize_normalize
     for f in range(F):
         _lib.check(eng.h, fn(eng.h, _ptr(frames_u8[f]), H, W, oh, ow, _ptr(out[f]), None, eng._stream()))
