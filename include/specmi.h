@@ -200,7 +200,7 @@ int specmi_get_precision(specmi_handle* h, int* precision);
  * channels 3-7 hold +0 (bits 0x0000).  Bit for bit what specmi_to_nhwc_f16(x, B, 3, H, W) makes of the fp32 NCHW image, and
  * what the Cin = 8 stem of the fp16 trunk reads.
  *   producers: specmi_crop_normalize_batch_f16, specmi_crop_resize_normalize_f16, specmi_resize_normalize_f16,
- *              specmi_resize_normalize_ragged_f16 - each takes the arguments of its fp32 twin with `void* out_nhwc8` in place of
+ *              specmi_resize_normalize_ragged_f16, specmi_crop_normalize_f16_ragged, specmi_crop_resize_normalize_f16_ragged - each takes the arguments of its fp32 twin with `void* out_nhwc8` in place of
  *              the fp32 image; the lane that owns a pixel writes it as one 16-byte vector.  Refused beyond the twin's refusals
  *              (SPECMI_ERR_ARG): an output that is not 16-byte aligned.
  *   consumers: specmi_trunk_forward_f16in, specmi_camcalib_forward_f16in, specmi_hmr_forward_f16in - each takes the arguments
@@ -438,6 +438,46 @@ int specmi_crop_resize_normalize(specmi_handle* h, const uint8_t* frame_rgb_hwc,
  * what the twin refuses and an out_nhwc8 that is not 16-byte aligned (SPECMI_ERR_ARG). */
 int specmi_crop_resize_normalize_f16(specmi_handle* h, const uint8_t* frame_rgb_hwc, int H, int W, const int32_t* boxes, int n,
                                      int crop_size, void* out_nhwc8, void* stream);
+
+/* The crops of specmi_crop_normalize for the detections of MANY frames of DIFFERENT sizes in one launch - what a folder of
+ * photographs needs where specmi_crop_normalize_batch (equal-sized frames: video) does not apply; replaces one
+ * specmi_crop_normalize launch per frame (spec/tester.py:109-128).  The frames lie in one uint8 RGB HWC device slab of
+ * slab_bytes bytes, the slab and offsets convention of specmi_resize_normalize_ragged: frame f starts at byte offsets[f]
+ * (HOST, nframes int64; any byte offset, gaps allowed) and is geom[2f] x geom[2f+1] = H x W pixels (HOST, nframes x 2 int32).
+ * Crop d is cut from frame frame_index[d] (DEVICE, (n) int32; an out-of-range value is CLAMPED into [0, nframes) as in
+ * specmi_crop_normalize_batch - a wrong crop, never an out-of-bounds read; validate on the host where the index is produced)
+ * with bbox d (DEVICE, (n,4) float).  Outputs as in specmi_crop_normalize, bit-identical per crop to that call on the crop's frame.
+ * Refused (SPECMI_ERR_ARG), launching nothing: a null required pointer (raw_hwc, bbox_scale, bbox_center are optional),
+ * n <= 0 or n > 65535, nframes <= 0, H or W below 1 or from 2^24 up, a frame that leaves the slab (negative offset or
+ * offset + H*W*3 > slab_bytes), a slab of 4 GiB or more, crop_size < 1, scale <= 0.
+ * The per-frame records (offset, H, W) live in one device table owned by the handle and shared by the four ragged crop calls.
+ * A call whose records differ from the previous call's rewrites that table and therefore first SYNCHRONISES THE WHOLE DEVICE
+ * (crops enqueued earlier, on any stream, may still read it) - the same rule as specmi_resize_normalize_ragged's and
+ * specmi_pano_extract_views' tables.  Such a call cannot be made while a stream is being captured (SPECMI_ERR_STATE); a call
+ * whose records equal the previous call's does neither. */
+int specmi_crop_normalize_ragged(specmi_handle* h, const uint8_t* frames_rgb_hwc, size_t slab_bytes, const int64_t* offsets,
+                                 const int32_t* geom, int nframes, const int32_t* frame_index, const float* bboxes, int n,
+                                 float scale, int crop_size, float* out_nchw, uint8_t* raw_hwc, float* bbox_scale,
+                                 float* bbox_center, void* stream);
+/* specmi_crop_normalize_ragged with the crops stored as NHWC8 fp16 (n,S,S,8): replaces it + specmi_to_nhwc_f16.  Refuses what
+ * the twin refuses and an out_nhwc8 that is not 16-byte aligned (SPECMI_ERR_ARG). */
+int specmi_crop_normalize_f16_ragged(specmi_handle* h, const uint8_t* frames_rgb_hwc, size_t slab_bytes, const int64_t* offsets,
+                                     const int32_t* geom, int nframes, const int32_t* frame_index, const float* bboxes, int n,
+                                     float scale, int crop_size, void* out_nhwc8, uint8_t* raw_hwc, float* bbox_scale,
+                                     float* bbox_center, void* stream);
+/* The crops of specmi_crop_resize_normalize for the samples of an evaluation batch whose images differ in size, in one launch:
+ * replaces one upload, one specmi_crop_resize_normalize launch of a single crop and one allocation per sample plus the
+ * concatenation of the batch (spec/dataset/cam_dataset.py:367-377 under a DataLoader).  Slab, offsets, geom, frame_index, the
+ * clamp, the refusals and the table rule as in specmi_crop_normalize_ragged; boxes (DEVICE, (n,4) int32) and out as in
+ * specmi_crop_resize_normalize, bit-identical per crop to that call on the crop's frame. */
+int specmi_crop_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames_rgb_hwc, size_t slab_bytes, const int64_t* offsets,
+                                        const int32_t* geom, int nframes, const int32_t* frame_index, const int32_t* boxes, int n,
+                                        int crop_size, float* out_nchw, void* stream);
+/* specmi_crop_resize_normalize_ragged with the crops stored as NHWC8 fp16 (n,S,S,8): replaces it + specmi_to_nhwc_f16.  Refuses
+ * what the twin refuses and an out_nhwc8 that is not 16-byte aligned (SPECMI_ERR_ARG). */
+int specmi_crop_resize_normalize_f16_ragged(specmi_handle* h, const uint8_t* frames_rgb_hwc, size_t slab_bytes, const int64_t* offsets,
+                                            const int32_t* geom, int nframes, const int32_t* frame_index, const int32_t* boxes, int n,
+                                            int crop_size, void* out_nhwc8, void* stream);
 
 /* The CamCalib frame transform (camcalib/pano_dataset.py:156-162, scripts/camcalib_demo.py:100): torchvision
  * Resize(600) on a PIL image = Pillow's antialiased bilinear resample (Image.resize((OW, OH), BILINEAR): separable

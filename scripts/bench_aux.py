@@ -10,6 +10,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py [--iters 20] [--out gpurun_out/aux_bench.json]
     python scripts/bench_aux.py --only camcalib_eval      # the two kernels of CamCalib's test step -> profiles/camcalib_eval_aux.json
     python scripts/bench_aux.py --only pano_views         # the panorama view extractor -> profiles/pano_views_aux.json
+    python scripts/bench_aux.py --only ragged_crops       # crops from frames of different sizes, per-frame route against the ragged one -> profiles/ragged_crops_aux.json
     python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
 import argparse
@@ -212,6 +213,101 @@ def pano_views_host(a):
         json.dump(row, f, indent=1)
 
 
+def ragged_crops_section(eng, a):
+    """Crops from host frames of DIFFERENT sizes, (a) the per-frame route - one upload and one crop launch per frame, plus the
+    concatenation for the dataset crop - against (b) the ragged route - one slab, one upload, one launch -, wall clock from host
+    frames to crops on the device, alternated in this process in 3 rounds; and the ragged launch alone, HIP-event time against
+    the HBM roof.  Decoding the images is outside both routes."""
+    import time
+    from spec_amd import preprocess as pp
+    dev = eng.device
+    rng = np.random.default_rng(0)
+    shapes = [(1920, 1080), (1080, 1920), (800, 600), (1000, 1000), (1280, 720), (640, 480), (1600, 1200), (600, 900)]   # (w, h)
+
+    def frames_of(n):
+        return [rng.integers(0, 256, (shapes[i % len(shapes)][1], shapes[i % len(shapes)][0], 3), dtype=np.uint8) for i in range(n)]
+
+    def compare(route_a, route_b, reps):
+        ra, rb = route_a(), route_b()
+        torch.cuda.synchronize()
+        same = bool(torch.equal(ra, rb))
+        del ra, rb
+        rounds = {'per_frame': [], 'ragged': []}
+        for _ in range(3):                                              # alternated: both see the same clocks and the same neighbours
+            wall = {'per_frame': [], 'ragged': []}
+            for _ in range(reps):
+                for name, fn in (('per_frame', route_a), ('ragged', route_b)):
+                    torch.cuda.synchronize(); t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+                    wall[name].append((time.perf_counter() - t0) * 1e3)
+            for k, v in wall.items():
+                rounds[k].append(float(np.median(v)))
+        med = {k: float(np.median(v)) for k, v in rounds.items()}
+        spread = max(rounds['per_frame']) - min(rounds['per_frame'])
+        return {'bit_identical': same, 'wall_ms_round_medians': {k: [round(x, 3) for x in v] for k, v in rounds.items()},
+                'wall_ms_median': {k: round(v, 3) for k, v in med.items()}, 'per_frame_spread_between_rounds_ms': round(spread, 3),
+                'ratio_per_frame_over_ragged': round(med['per_frame'] / med['ragged'], 2),
+                'ragged_not_slower_beyond_the_spread': bool(med['ragged'] <= med['per_frame'] + spread)}
+
+    def kernel_row(fn, name):
+        ms, by, _, _ = timed(eng, fn, a.iters)[name]
+        return {'kernel': name, 'ms_per_launch': round(ms, 5), 'algorithmic_MB': round(by / 1e6, 3), 'achieved_GBps': round(by / (ms * 1e-3) / 1e9, 1),
+                'frac_of_hbm_peak': round(by / (ms * 1e-3) / HBM_PEAK, 4)}
+    reps = max(3, a.iters // 4)
+    out = {}
+    # ---- a 64-sample evaluation batch (EvalDataset.batch) -----------------------------------------------------------
+    n = 64
+    frames = frames_of(n)
+    centers = np.stack([[rng.uniform(0.3, 0.7) * f.shape[1], rng.uniform(0.3, 0.7) * f.shape[0]] for f in frames])
+    scales = np.asarray([rng.uniform(0.5, 0.9) * f.shape[0] / 200 for f in frames])
+    index = np.arange(n, dtype=np.int32)
+
+    def eval_a():
+        return torch.cat([pp.dataset_crops(torch.from_numpy(f).to(dev), centers[i:i + 1], scales[i:i + 1], 224) for i, f in enumerate(frames)])
+
+    def eval_b():
+        slab, offsets, sizes = pp.pack_frames(frames, dev)
+        return pp.dataset_crops_ragged(slab, offsets, sizes, index, centers, scales, 224)
+    row = compare(eval_a, eval_b, reps)
+    slab, offsets, sizes = pp.pack_frames(frames, dev)
+    batch = torch.empty(n, 3, 224, 224, device=dev)
+    row.update(workload=f'{n} host frames of 8 sizes (480p .. 1080p, {slab.numel() / 1e6:.0f} MB), one dataset crop each -> ({n},3,224,224) fp32',
+               h2d_MB=round(slab.numel() / 1e6, 1), launches={'per_frame': n, 'ragged': 1}, uploads={'per_frame': n, 'ragged': 1},
+               ragged_launch=kernel_row(lambda: pp.dataset_crops_ragged(slab, offsets, sizes, index, centers, scales, 224, out=batch),
+                                        'crop_resize_normalize_ragged'))
+    out['eval_batch'] = row
+    print(json.dumps(row, indent=1))
+    del slab, batch
+    # ---- a 32-frame folder flush, 8 detections per frame (SPECTester.run_on_image_folder) ---------------------------
+    F, per = 32, 8
+    frames = frames_of(F)
+    dets = [np.stack([rng.uniform(0, f.shape[1], per), rng.uniform(0, f.shape[0], per), rng.uniform(100, 500, per), rng.uniform(150, 650, per)],
+                     1).astype(np.float32) for f in frames]
+    all_dets, fidx = np.concatenate(dets), np.repeat(np.arange(F, dtype=np.int32), per)
+    buf = {'inp_images': torch.empty(F * per, 3, 224, 224, device=dev), 'bbox_scale': torch.empty(F * per, device=dev),
+           'bbox_center': torch.empty(F * per, 2, device=dev)}
+
+    def flush_a():
+        for i, f in enumerate(frames):
+            frame = torch.from_numpy(f).pin_memory().to(dev, non_blocking=True)
+            pp.crop_detections(frame, dets[i], out={k: v[i * per:(i + 1) * per] for k, v in buf.items()})
+        return buf['inp_images'].clone()
+
+    def flush_b():
+        slab, offsets, sizes = pp.pack_frames(frames, dev)
+        pp.crop_detections_ragged(slab, offsets, sizes, fidx, all_dets, out=buf)
+        return buf['inp_images'].clone()
+    row = compare(flush_a, flush_b, reps)
+    slab, offsets, sizes = pp.pack_frames(frames, dev)
+    row.update(workload=f'{F} host frames of 8 sizes (480p .. 1080p, {slab.numel() / 1e6:.0f} MB), {per} detections each -> ({F * per},3,224,224) fp32',
+               h2d_MB=round(slab.numel() / 1e6, 1), launches={'per_frame': F, 'ragged': 1}, uploads={'per_frame': F, 'ragged': 1},
+               ragged_launch=kernel_row(lambda: pp.crop_detections_ragged(slab, offsets, sizes, fidx, all_dets, out=buf), 'crop_normalize_ragged'),
+               note='both routes end with one clone of the crop buffer (the comparison needs a result of its own); the per-frame route '
+                    'pins each frame as the folder demo does; the demo\'s per-frame img_h / img_w / R / K assignments are outside both')
+    out['folder_flush'] = row
+    print(json.dumps(row, indent=1))
+    return out
+
+
 def finish(a, table, extra=None):
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, 'w') as f:
@@ -225,7 +321,7 @@ def finish(a, table, extra=None):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['camcalib_eval', 'pano_views', 'pano_views_host'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops'], default=None, help='run one section only')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -266,6 +362,16 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'per-launch HIP events (library profiler); wall clock where named',
                        'pano_views': row, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'ragged_crops':
+        from spec_amd import _lib
+        rows = ragged_crops_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'wall clock, host frames -> crops on the device, 3 alternated '
+                       'rounds; ragged_launch: per-launch HIP events (library profiler)', 'ragged_crops': rows, 'source_hash': _lib.source_hash()},
+                      f, indent=1)
         return
 
     # ---- 8f-1: crops from one 1080p frame ---------------------------------------------------------------------------

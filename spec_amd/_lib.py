@@ -139,6 +139,15 @@ PROTOTYPES = {
                                               C.c_void_p]),
     'specmi_resize_normalize_ragged_f16': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, c_int32_p, C.c_int, C.c_int, C.c_int,
                                                      C.c_void_p, C.c_void_p]),
+    # ragged crops: (h, slab, slab_bytes, offsets, geom, nframes, frame_index, boxes, n, ...)
+    'specmi_crop_normalize_ragged': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, c_int32_p, C.c_int, C.c_void_p, C.c_void_p,
+                                               C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'specmi_crop_normalize_f16_ragged': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, c_int32_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                   C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'specmi_crop_resize_normalize_ragged': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, c_int32_p, C.c_int, C.c_void_p,
+                                                      C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    'specmi_crop_resize_normalize_f16_ragged': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, c_int32_p, C.c_int, C.c_void_p,
+                                                          C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'specmi_trunk_forward_f16in': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'specmi_camcalib_forward_f16in': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

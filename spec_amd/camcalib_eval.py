@@ -143,17 +143,9 @@ def pad_batch(frames, min_size: int, max_size: Optional[int], device, engine=Non
     if isinstance(frames, tuple):
         slab, offsets, sizes = frames
         return eng.resize_normalize_ragged(slab, offsets, [(H, W) + resize_size(W, H, min_size, max_size) for H, W in sizes], dtype=dtype)
-    geom, offsets, off = [], [], 0
-    for fr in frames:
-        if fr.dtype != np.uint8 or fr.ndim != 3 or fr.shape[2] != 3:
-            raise ValueError('frames must be (H,W,3) uint8 RGB')
-        H, W = fr.shape[:2]
-        oh, ow = resize_size(W, H, min_size, max_size)
-        geom.append((H, W, oh, ow))
-        offsets.append(off)
-        off += H * W * 3
-    slab = torch.from_numpy(np.concatenate([np.ascontiguousarray(fr).reshape(-1) for fr in frames])).to(eng.device)
-    return eng.resize_normalize_ragged(slab, offsets, geom, dtype=dtype)
+    from .preprocess import pack_frames
+    slab, offsets, sizes = pack_frames(frames, eng.device)
+    return eng.resize_normalize_ragged(slab, offsets, [(H, W) + resize_size(W, H, min_size, max_size) for H, W in sizes], dtype=dtype)
 
 
 def forward_limit(H: int, W: int) -> int:

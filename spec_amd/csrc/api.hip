@@ -801,6 +801,7 @@ int specmi_destroy(specmi_handle* h) {
     if (h->ragged_tab) (void)hipFree(h->ragged_tab);
     if (h->ragged_tmp) (void)hipFree(h->ragged_tmp);
     if (h->pano_tab) (void)hipFree(h->pano_tab);
+    if (h->crop_tab) (void)hipFree(h->crop_tab);
     hrnet_free(h->hrnet);
     delete h;
     return SPECMI_OK;
@@ -1633,6 +1634,88 @@ int specmi_crop_resize_normalize(specmi_handle* h, const uint8_t* frame, int H, 
 int specmi_crop_resize_normalize_f16(specmi_handle* h, const uint8_t* frame, int H, int W, const int32_t* boxes, int n,
                                      int crop_size, void* out_nhwc8, void* stream) {
     return crop_resize_normalize(h, frame, H, W, boxes, n, crop_size, out_nhwc8, true, stream);
+}
+
+// the checks and the record table the two ragged crops share; everything is checked before the table is touched
+static int crop_ragged_table(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets, const int32_t* geom,
+                             int nframes, const int32_t* frame_index, const void* boxes, int n, int crop_size, const void* out, bool f16,
+                             hipStream_t s) {
+    if (!frames || !offsets || !geom || !frame_index || !boxes || !out) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (n <= 0 || n > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 crops per call (grid dimension), got %d", n);
+    if (nframes <= 0) return fail(h, SPECMI_ERR_ARG, "at least one frame per call, got %d", nframes);
+    if (crop_size < 1) return fail(h, SPECMI_ERR_ARG, "a crop size of %d", crop_size);
+    if (f16) NEED_ALIGNED16(h, out);
+    if (slab_bytes >= 4294967296.0) return fail(h, SPECMI_ERR_ARG, "a frame slab of %zu bytes is beyond the kernels' 32-bit offsets", slab_bytes);
+    std::vector<CropFrame> tab((size_t)nframes);
+    for (int f = 0; f < nframes; ++f) {
+        const int H = geom[2 * f], W = geom[2 * f + 1];
+        if (H < 1 || W < 1 || H >= (1 << 24) || W >= (1 << 24)) return fail(h, SPECMI_ERR_ARG, "frame %d: size %d x %d (1 <= side < 2^24)", f, H, W);
+        if (offsets[f] < 0 || (double)offsets[f] + (double)H * W * 3 > (double)slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "frame %d: %d x %d x 3 bytes at offset %lld leave the slab of %zu bytes", f, H, W, (long long)offsets[f], slab_bytes);
+        tab[f] = CropFrame{(unsigned)offsets[f], H, W, 0};
+    }
+    int rc;
+    const bool regrown = tab.size() * sizeof(CropFrame) > h->crop_tab_bytes;
+    if ((rc = grow_ragged(h, (void**)&h->crop_tab, &h->crop_tab_bytes, tab.size() * sizeof(CropFrame), "the ragged-crop frame table"))) return rc;
+    if (regrown || tab.size() != h->crop_host.size() || std::memcmp(tab.data(), h->crop_host.data(), tab.size() * sizeof(CropFrame))) {
+        // crops enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
+        if (!regrown && (rc = sync_for_growth(h, "the ragged-crop frame table"))) return rc;
+        h->crop_host.swap(tab);
+        HIPCHK(h, hipMemcpyAsync(h->crop_tab, h->crop_host.data(), h->crop_host.size() * sizeof(CropFrame), hipMemcpyHostToDevice, s));
+    }
+    return SPECMI_OK;
+}
+
+static int crop_normalize_ragged(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets, const int32_t* geom,
+                                 int nframes, const int32_t* frame_index, const float* bboxes, int n, float scale, int crop_size,
+                                 void* out, bool f16, uint8_t* raw, float* bbox_scale, float* bbox_center, void* stream) {
+    ENTER(h);
+    if (!(scale > 0.f)) return fail(h, SPECMI_ERR_ARG, "a scale of %g", (double)scale);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = crop_ragged_table(h, frames, slab_bytes, offsets, geom, nframes, frame_index, bboxes, n, crop_size, out, f16, s)) return rc;
+    LaunchCtx ctx{s, &h->prof, "preprocess.crop_ragged"};
+    LAUNCHCHK(h, launch_crop_normalize_ragged(frames, h->crop_tab, nframes, (double)slab_bytes, frame_index, bboxes, n, scale, crop_size, out,
+                                              raw, bbox_scale, bbox_center, ctx, f16),
+              "crop_normalize_ragged");
+    return SPECMI_OK;
+}
+
+int specmi_crop_normalize_ragged(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets, const int32_t* geom,
+                                 int nframes, const int32_t* frame_index, const float* bboxes, int n, float scale, int crop_size,
+                                 float* out, uint8_t* raw, float* bbox_scale, float* bbox_center, void* stream) {
+    return crop_normalize_ragged(h, frames, slab_bytes, offsets, geom, nframes, frame_index, bboxes, n, scale, crop_size, out, false, raw,
+                                 bbox_scale, bbox_center, stream);
+}
+
+int specmi_crop_normalize_f16_ragged(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets, const int32_t* geom,
+                                     int nframes, const int32_t* frame_index, const float* bboxes, int n, float scale, int crop_size,
+                                     void* out_nhwc8, uint8_t* raw, float* bbox_scale, float* bbox_center, void* stream) {
+    return crop_normalize_ragged(h, frames, slab_bytes, offsets, geom, nframes, frame_index, bboxes, n, scale, crop_size, out_nhwc8, true, raw,
+                                 bbox_scale, bbox_center, stream);
+}
+
+static int crop_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets,
+                                        const int32_t* geom, int nframes, const int32_t* frame_index, const int32_t* boxes, int n,
+                                        int crop_size, void* out, bool f16, void* stream) {
+    ENTER(h);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = crop_ragged_table(h, frames, slab_bytes, offsets, geom, nframes, frame_index, boxes, n, crop_size, out, f16, s)) return rc;
+    LaunchCtx ctx{s, &h->prof, "preprocess.dataset_crop_ragged"};
+    LAUNCHCHK(h, launch_crop_resize_normalize_ragged(frames, h->crop_tab, nframes, (double)slab_bytes, frame_index, boxes, n, crop_size, out, ctx, f16),
+              "crop_resize_normalize_ragged");
+    return SPECMI_OK;
+}
+
+int specmi_crop_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets,
+                                        const int32_t* geom, int nframes, const int32_t* frame_index, const int32_t* boxes, int n,
+                                        int crop_size, float* out, void* stream) {
+    return crop_resize_normalize_ragged(h, frames, slab_bytes, offsets, geom, nframes, frame_index, boxes, n, crop_size, out, false, stream);
+}
+
+int specmi_crop_resize_normalize_f16_ragged(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets,
+                                            const int32_t* geom, int nframes, const int32_t* frame_index, const int32_t* boxes, int n,
+                                            int crop_size, void* out_nhwc8, void* stream) {
+    return crop_resize_normalize_ragged(h, frames, slab_bytes, offsets, geom, nframes, frame_index, boxes, n, crop_size, out_nhwc8, true, stream);
 }
 
 int specmi_eval_mesh(specmi_handle* h, const float* pred, const float* gt, int B, int V, const float* Jr, int J,

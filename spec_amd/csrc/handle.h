@@ -168,6 +168,10 @@ struct specmi_handle {
     PanoView* pano_tab = nullptr;
     size_t pano_tab_bytes = 0;
     std::vector<PanoView> pano_host;    // host image of pano_tab as last uploaded
+    // ragged crops (specmi_crop_normalize_ragged, specmi_crop_resize_normalize_ragged): the per-frame records, same rules again
+    CropFrame* crop_tab = nullptr;
+    size_t crop_tab_bytes = 0;
+    std::vector<CropFrame> crop_host;   // host image of crop_tab as last uploaded
     SkWs sk;                            // split-K partial tiles + arrival counters (ensure_sk; never allocated under graph capture:
                                         // the warm-up call of a shape sizes it)
     std::vector<void*> sk_retired;      // outgrown split-K buffers, kept until destroy (captured graphs may still name them)

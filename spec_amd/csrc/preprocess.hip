@@ -329,6 +329,232 @@ int launch_crop_resize_normalize(const unsigned char* frame, int H, int W, const
 }
 
 // ------------------------------------------------------------------------------------------------
+// The two crops from frames of DIFFERENT sizes in one launch (the per-sample loop of EvalDataset.batch, the per-frame loop of
+// SPECTester.run_on_image_folder): the frames lie in one uint8 slab, crop d (blockIdx.y) reads frame_of[d] - clamped into
+// [0, nframes) like the equal-size batch - and from that its frame's record (CropFrame: byte offset, H, W) out of a device
+// table, then runs the per-pixel path of the kernels above on frames + offset with that H and W: the same device functions in
+// the same order, hence the same bits.  Same work mapping, tables and stores.  WIDE is decided per crop (a slab mixes a 1 x 1
+// frame with a 1080p one); a workgroup serves one crop, so the branch is wave-uniform and each side keeps its taps back to
+// back.  The 8-byte tap load clamps against its own frame's `total`, so it never leaves the frame, hence never the slab;
+// frames start at any byte offset (the load is an unaligned memcpy).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ CropFrame ragged_frame(const CropFrame* __restrict__ tab, const int* __restrict__ frame_of, int d, int nframes) {
+    return tab[min((unsigned)max(frame_of[d], 0), (unsigned)(nframes - 1))];
+}
+
+template <bool WIDE, bool TABLE, bool F16>
+__device__ __forceinline__ void crop_normalize_pixels(const unsigned char* __restrict__ frame, int H, int W, const CropAffine& A, int S,
+                                                      int d, int pix0, int yfirst, const float (&lut)[3][256], const int2* tabx,
+                                                      const int2* taby, void* __restrict__ out_, unsigned char* __restrict__ raw) {
+    float* __restrict__ out = static_cast<float*>(out_);
+    const int t = threadIdx.x, npix = S * S;
+    const size_t total = (size_t)H * W * 3;
+#pragma unroll 1
+    for (int kb = 0; kb < kNB; ++kb) {
+        const int idx0 = pix0 + kb * (256 * kPX) + t;
+        if (idx0 - t >= npix) break;
+        int tap[kPX][4][3], wgt[kPX][4];
+#pragma unroll
+        for (int k = 0; k < kPX; ++k) {
+            const int idx = min(idx0 + k * 256, npix - 1);
+            const int y = idx / S, x = idx - y * S;
+            const int2 cxf = TABLE ? tabx[x] : A.col(x, W), cyf = TABLE ? taby[y - yfirst] : A.row(y, H);
+            const int sx = cxf.x, fx = cxf.y, sy = cyf.x, fy = cyf.y;
+            const bool y0 = sy >= 0 && sy < H, y1 = sy + 1 >= 0 && sy + 1 < H;
+            const bool x0 = sx >= 0 && sx < W, x1 = sx + 1 >= 0 && sx + 1 < W;
+            wgt[k][0] = (y0 && x0) ? __mul24(32 - fx, 32 - fy) * 32 : 0;
+            wgt[k][1] = (y0 && x1) ? __mul24(fx, 32 - fy) * 32 : 0;
+            wgt[k][2] = (y1 && x0) ? __mul24(32 - fx, fy) * 32 : 0;
+            wgt[k][3] = (y1 && x1) ? __mul24(fx, fy) * 32 : 0;
+            const int cy0 = min(max(sy, 0), H - 1), cy1 = min(max(sy + 1, 0), H - 1);
+            const int cx0 = min(max(sx, 0), W - 1), cx1 = min(max(sx + 1, 0), W - 1);
+            load_tap_pair<WIDE>(frame, total, W, cy0, cx0, cx1, tap[k][0], tap[k][1]);
+            load_tap_pair<WIDE>(frame, total, W, cy1, cx0, cx1, tap[k][2], tap[k][3]);
+        }
+#pragma unroll
+        for (int k = 0; k < kPX; ++k) {
+            const int idx = idx0 + k * 256;
+            if (idx < npix) {
+                float r[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    int v = (__mul24(tap[k][0][c], wgt[k][0]) + __mul24(tap[k][1][c], wgt[k][1]) + __mul24(tap[k][2][c], wgt[k][2]) +
+                             __mul24(tap[k][3][c], wgt[k][3]) + (1 << 14)) >> 15;
+                    v = v < 0 ? 0 : (v > 255 ? 255 : v);
+                    if (raw) raw[((size_t)d * npix + idx) * 3 + c] = (unsigned char)v;
+                    r[c] = lut[c][v];
+                    if (!F16) out[(size_t)(d * 3 + c) * npix + idx] = r[c];
+                }
+                if (F16) store_nhwc8(out_, (size_t)d * npix + idx, r);
+            }
+        }
+    }
+}
+
+template <bool TABLE, bool F16>
+__global__ void __launch_bounds__(256) crop_normalize_ragged_kernel(const unsigned char* __restrict__ frames,
+                                                                     const CropFrame* __restrict__ tab, int nframes,
+                                                                     const int* __restrict__ frame_of,
+                                                                     const float* __restrict__ bboxes, float scale, int S,
+                                                                     void* __restrict__ out_, unsigned char* __restrict__ raw,
+                                                                     float* __restrict__ bbox_scale, float* __restrict__ bbox_center) {
+    __shared__ float lut[3][256];
+    __shared__ int2 tabx[TABLE ? kTabX : 1], taby[TABLE ? kTabY : 1];
+    const int d = blockIdx.y, t = threadIdx.x;
+    const CropFrame fr = ragged_frame(tab, frame_of, d, nframes);
+    const unsigned char* __restrict__ frame = frames + fr.off;
+    const int H = fr.H, W = fr.W;
+    {
+        const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) lut[c][t] = ((float)t / 255.0f - mean[c]) / stdv[c];
+    }
+    const float cx = bboxes[d * 4 + 0], cy = bboxes[d * 4 + 1], bw = bboxes[d * 4 + 2], bh = bboxes[d * 4 + 3];
+    if (blockIdx.x == 0 && t == 0) {
+        if (bbox_scale) bbox_scale[d] = bw / 200.0f;
+        if (bbox_center) { bbox_center[d * 2 + 0] = cx; bbox_center[d * 2 + 1] = cy; }
+    }
+    const CropAffine A(cx, cy, bw, bh, scale, S);
+    const int npix = S * S, pix0 = blockIdx.x * (256 * kPX * kNB);
+    const int yfirst = pix0 / S;
+    if (TABLE) {
+        const int ylast = min(pix0 + 256 * kPX * kNB - 1, npix - 1) / S;
+        for (int i = t; i < S; i += 256) tabx[i] = A.col(i, W);
+        for (int i = t; i <= ylast - yfirst; i += 256) taby[i] = A.row(yfirst + i, H);
+    }
+    __syncthreads();
+    if (W >= 2 && (size_t)H * W * 3 >= 8)      // launch_crop_normalize's WIDE rule, per crop
+        crop_normalize_pixels<true, TABLE, F16>(frame, H, W, A, S, d, pix0, yfirst, lut, tabx, taby, out_, raw);
+    else
+        crop_normalize_pixels<false, TABLE, F16>(frame, H, W, A, S, d, pix0, yfirst, lut, tabx, taby, out_, raw);
+}
+
+int launch_crop_normalize_ragged(const unsigned char* frames, const CropFrame* tab, int nframes, double slab_bytes, const int* frame_of,
+                                 const float* bboxes, int n, float scale, int S, void* out, unsigned char* raw, float* bbox_scale,
+                                 float* bbox_center, const LaunchCtx& ctx, bool f16) {
+    // algorithmic HBM bytes: the slab once + every output once
+    ProfScope ps(ctx, f16 ? "crop_normalize_ragged_f16" : "crop_normalize_ragged", 0.0,
+                 slab_bytes + (double)n * S * S * ((f16 ? 16.0 : 12.0) + (raw ? 3.0 : 0.0)));
+    const dim3 grid((S * S + 256 * kPX * kNB - 1) / (256 * kPX * kNB), n);
+    const bool table = S <= kTabX;
+    auto k = f16 ? (table ? crop_normalize_ragged_kernel<true, true> : crop_normalize_ragged_kernel<false, true>)
+                 : (table ? crop_normalize_ragged_kernel<true, false> : crop_normalize_ragged_kernel<false, false>);
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, ctx.stream, frames, tab, nframes, frame_of, bboxes, scale, S, out, raw, bbox_scale, bbox_center);
+    return (int)hipGetLastError();
+}
+
+template <bool WIDE, bool TABLE, bool F16>
+__device__ __forceinline__ void crop_resize_pixels(const unsigned char* __restrict__ frame, int H, int W, int ulx, int uly, int bw, int bh,
+                                                   double scale_x, double scale_y, int S, int d, int pix0, int yfirst, const int* txs,
+                                                   const int* tys, const float* txf, const float* tyf, void* __restrict__ out_) {
+    float* __restrict__ out = static_cast<float*>(out_);
+    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+    const int t = threadIdx.x, npix = S * S;
+    const size_t total = (size_t)H * W * 3;
+#pragma unroll 1
+    for (int kb = 0; kb < kNB; ++kb) {
+        const int idx0 = pix0 + kb * (256 * kPX) + t;
+        if (idx0 - t >= npix) break;
+        int tap[kPX][4][3];
+        bool in[kPX][4];
+        float cf[kPX][2];
+#pragma unroll
+        for (int k = 0; k < kPX; ++k) {
+            const int idx = min(idx0 + k * 256, npix - 1);
+            const int dy = idx / S, dx = idx - dy * S;
+            int sx, sy;
+            float fx, fy;
+            if (TABLE) { sx = txs[dx]; fx = txf[dx]; sy = tys[dy - yfirst]; fy = tyf[dy - yfirst]; }
+            else { resize_coord(dx, scale_x, bw, sx, fx); resize_coord(dy, scale_y, bh, sy, fy); }
+            const int sx1 = sx + 1 < bw ? sx + 1 : sx, sy1 = sy + 1 < bh ? sy + 1 : sy;
+            cf[k][0] = fx; cf[k][1] = fy;
+            const int iy0 = uly + sy, iy1 = uly + sy1, ix0 = ulx + sx, ix1 = ulx + sx1;
+            const bool vy0 = (unsigned)iy0 < (unsigned)H, vy1 = (unsigned)iy1 < (unsigned)H;
+            const bool vx0 = (unsigned)ix0 < (unsigned)W, vx1 = (unsigned)ix1 < (unsigned)W;
+            in[k][0] = vy0 && vx0; in[k][1] = vy0 && vx1; in[k][2] = vy1 && vx0; in[k][3] = vy1 && vx1;
+            const int cx0 = min(max(ix0, 0), W - 1), cx1 = min(max(ix1, 0), W - 1);
+            load_tap_pair<WIDE>(frame, total, W, min(max(iy0, 0), H - 1), cx0, cx1, tap[k][0], tap[k][1]);
+            load_tap_pair<WIDE>(frame, total, W, min(max(iy1, 0), H - 1), cx0, cx1, tap[k][2], tap[k][3]);
+        }
+#pragma unroll
+        for (int k = 0; k < kPX; ++k) {
+            const int idx = idx0 + k * 256;
+            if (idx < npix) {
+                const double a0 = (double)(1.f - cf[k][0]), a1 = (double)cf[k][0], b0 = (double)(1.f - cf[k][1]), b1 = (double)cf[k][1];
+                float r[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const double p00 = in[k][0] ? (double)tap[k][0][c] : 0.0, p01 = in[k][1] ? (double)tap[k][1][c] : 0.0;
+                    const double p10 = in[k][2] ? (double)tap[k][2][c] : 0.0, p11 = in[k][3] ? (double)tap[k][3][c] : 0.0;
+                    const double r0 = __dadd_rn(__dmul_rn(p00, a0), __dmul_rn(p01, a1));     // no fma contraction, as above
+                    const double r1 = __dadd_rn(__dmul_rn(p10, a0), __dmul_rn(p11, a1));
+                    double v = __dadd_rn(__dmul_rn(r0, b0), __dmul_rn(r1, b1));
+                    v = fmin(255.0, fmax(0.0, v));
+                    const float tt = (float)v / 255.0f;
+                    r[c] = (tt - mean[c]) / stdv[c];
+                    if (!F16) out[(size_t)(d * 3 + c) * npix + idx] = r[c];
+                }
+                if (F16) store_nhwc8(out_, (size_t)d * npix + idx, r);
+            }
+        }
+    }
+}
+
+template <bool TABLE, bool F16>
+__global__ void __launch_bounds__(256) crop_resize_normalize_ragged_kernel(const unsigned char* __restrict__ frames,
+                                                                            const CropFrame* __restrict__ tab, int nframes,
+                                                                            const int* __restrict__ frame_of,
+                                                                            const int* __restrict__ boxes, int S, void* __restrict__ out_) {
+    float* __restrict__ out = static_cast<float*>(out_);
+    __shared__ int txs[TABLE ? kTabX : 1], tys[TABLE ? kTabY : 1];
+    __shared__ float txf[TABLE ? kTabX : 1], tyf[TABLE ? kTabY : 1];
+    const int d = blockIdx.y, t = threadIdx.x;
+    const int npix = S * S, pix0 = blockIdx.x * (256 * kPX * kNB);
+    const int ulx = boxes[d * 4 + 0], uly = boxes[d * 4 + 1], brx = boxes[d * 4 + 2], bry = boxes[d * 4 + 3];
+    const int bw = brx - ulx, bh = bry - uly;
+    if (bw <= 0 || bh <= 0) {
+        const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
+        for (int i = pix0 + t; i < min(pix0 + 256 * kPX * kNB, npix); i += 256) {
+            float r[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                r[c] = (0.0f - mean[c]) / stdv[c];
+                if (!F16) out[(size_t)(d * 3 + c) * npix + i] = r[c];
+            }
+            if (F16) store_nhwc8(out_, (size_t)d * npix + i, r);
+        }
+        return;
+    }
+    const CropFrame fr = ragged_frame(tab, frame_of, d, nframes);
+    const unsigned char* __restrict__ frame = frames + fr.off;
+    const int H = fr.H, W = fr.W;
+    const double scale_x = (double)bw / (double)S, scale_y = (double)bh / (double)S;
+    const int yfirst = pix0 / S;
+    if (TABLE) {
+        const int ylast = min(pix0 + 256 * kPX * kNB - 1, npix - 1) / S;
+        for (int i = t; i < S; i += 256) resize_coord(i, scale_x, bw, txs[i], txf[i]);
+        for (int i = t; i <= ylast - yfirst; i += 256) resize_coord(yfirst + i, scale_y, bh, tys[i], tyf[i]);
+        __syncthreads();
+    }
+    if (W >= 2 && (size_t)H * W * 3 >= 8)      // launch_crop_resize_normalize's WIDE rule, per crop
+        crop_resize_pixels<true, TABLE, F16>(frame, H, W, ulx, uly, bw, bh, scale_x, scale_y, S, d, pix0, yfirst, txs, tys, txf, tyf, out_);
+    else
+        crop_resize_pixels<false, TABLE, F16>(frame, H, W, ulx, uly, bw, bh, scale_x, scale_y, S, d, pix0, yfirst, txs, tys, txf, tyf, out_);
+}
+
+int launch_crop_resize_normalize_ragged(const unsigned char* frames, const CropFrame* tab, int nframes, double slab_bytes,
+                                        const int* frame_of, const int* boxes, int n, int S, void* out, const LaunchCtx& ctx, bool f16) {
+    ProfScope ps(ctx, f16 ? "crop_resize_normalize_ragged_f16" : "crop_resize_normalize_ragged", 0.0,
+                 slab_bytes + (double)n * S * S * (f16 ? 16.0 : 12.0));
+    const dim3 grid((S * S + 256 * kPX * kNB - 1) / (256 * kPX * kNB), n);
+    const bool table = S <= kTabX;
+    auto k = f16 ? (table ? crop_resize_normalize_ragged_kernel<true, true> : crop_resize_normalize_ragged_kernel<false, true>)
+                 : (table ? crop_resize_normalize_ragged_kernel<true, false> : crop_resize_normalize_ragged_kernel<false, false>);
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, ctx.stream, frames, tab, nframes, frame_of, boxes, S, out);
+    return (int)hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
 // CamCalib frame transform (camcalib/pano_dataset.py:156-162): torchvision Resize(600) on a PIL image =
 // Pillow's separable triangle-filter resample (support grows with the down-scale factor, 22-bit fixed-point
 // coefficients, horizontal pass -> uint8 -> vertical pass -> uint8), then ToTensor + Normalize.

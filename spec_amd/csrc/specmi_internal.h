@@ -386,6 +386,17 @@ int launch_crop_normalize(const unsigned char* frame, int H, int W, const float*
 int launch_crop_resize_normalize(const unsigned char* frame, int H, int W, const int* boxes, int n, int S, void* out,
                                  const LaunchCtx& ctx, bool f16 = false);
 
+// The two crops from frames of DIFFERENT sizes: `frames` is a uint8 slab, `tab` (device) one CropFrame per frame - byte offset
+// in the slab, H, W -, crop d is cut from frame frame_of[d] (device, (n) int32, clamped into [0, nframes)).  The caller
+// guarantees H, W < 2^24 and a slab below 4 GiB (32-bit offsets); slab_bytes only feeds the profiler's byte count
+struct CropFrame { unsigned off; int H, W, pad_; };
+int launch_crop_normalize_ragged(const unsigned char* frames, const CropFrame* tab, int nframes, double slab_bytes, const int* frame_of,
+                                 const float* bboxes, int n, float scale, int S, void* out, unsigned char* raw, float* bbox_scale,
+                                 float* bbox_center, const LaunchCtx& ctx, bool f16 = false);
+int launch_crop_resize_normalize_ragged(const unsigned char* frames, const CropFrame* tab, int nframes, double slab_bytes,
+                                        const int* frame_of, const int* boxes, int n, int S, void* out, const LaunchCtx& ctx,
+                                        bool f16 = false);
+
 // Pillow-exact bilinear resize + ToTensor + Normalize (CamCalib frame transform)
 int pillow_coeffs(int in_size, int out_size, std::vector<int>& bounds, std::vector<int>& kk);
 int launch_resize_normalize(const unsigned char* frame, int H, int W, int OH, int OW, const int* hb, const int* hk, int ksh,

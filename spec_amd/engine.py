@@ -89,6 +89,19 @@ def flow_image_dtype(module, fp32_crops=None):
     return torch.float32 if fp32_crops else getattr(module, 'image_dtype', torch.float32)
 
 
+# Which route the flows whose frames differ in size (EvalDataset.batch, SPECTester.run_on_image_folder) take for their crops:
+# False = one upload and one crop launch per frame (route (a)), True = one slab, one upload, one ragged launch per batch (route
+# (b)).  Same bits either way; the default follows F16_CROPS_DEFAULT's rule: (b) where it is not slower than
+# (a) beyond (a)'s own spread between rounds - and from host frames it is 3.5 x slower (profiles/ragged_crops_aux.json: the host-side
+# packing pass and a pageable upload outweigh the launches saved).
+RAGGED_CROPS_DEFAULT = False
+
+
+def flow_ragged_crops(ragged_crops=None) -> bool:
+    """``ragged_crops`` (the flow's private switch) decides, None = the default."""
+    return RAGGED_CROPS_DEFAULT if ragged_crops is None else bool(ragged_crops)
+
+
 def out_dtype(dtype):
     """The ``dtype=`` keyword of the producers: torch.float32 -> the (n,3,H,W) fp32 image, torch.float16 -> NHWC8 fp16."""
     if dtype not in (torch.float32, torch.float16):

@@ -27,8 +27,8 @@ import torch
 from . import assets, io_formats, metrics
 from .cam_utils import cam_params_from_angles
 from .checkpoint import load_pretrained_model, read_checkpoint
-from .engine import flow_image_dtype
-from .preprocess import dataset_crops
+from .engine import flow_image_dtype, flow_ragged_crops
+from .preprocess import dataset_crops, dataset_crops_ragged, pack_frames
 
 # spec/config.py:34-56
 DATASET_FOLDERS = {'spec-mtp': 'data/dataset_folders/spec-mtp', 'spec-syn': 'data/dataset_folders/spec-syn',
@@ -98,6 +98,7 @@ class EvalDataset:
         self.data = dict(np.load(dataset_file or os.path.join(data_root, DATASET_FILES[name])))
         self.imgname = self.data['imgname']
         self.n = len(self.imgname)
+        self._ragged_crops = None     # True: one slab, one upload, one ragged crop launch per batch; False: one of each per sample (same bits)
 
     def __len__(self):
         return self.n
@@ -105,12 +106,18 @@ class EvalDataset:
     def batch(self, idx, device, img_res=224, use_gt_cam=False, dtype=torch.float32) -> Dict[str, torch.Tensor]:
         """``dtype``: what the crops are stored as (``spec_amd.preprocess``: fp32 (n,3,S,S), or NHWC8 fp16 for an fp16 model)."""
         d = self.data
-        crops, shapes = [], []
-        for i in idx:
-            frame = torch.from_numpy(read_image_rgb(os.path.join(self.img_dir, str(self.imgname[i])))).to(device)
-            H, W = frame.shape[:2]
-            crops.append(dataset_crops(frame, d['center'][i:i + 1], d['scale'][i:i + 1], img_res, dtype=dtype))   # cam_dataset.py:367-377
-            shapes.append((H, W))
+        paths = [os.path.join(self.img_dir, str(self.imgname[i])) for i in idx]
+        if flow_ragged_crops(self._ragged_crops):     # the batch's images in one slab, one upload, one launch into the batch tensor
+            slab, offsets, shapes = pack_frames([read_image_rgb(p) for p in paths], device)
+            img = dataset_crops_ragged(slab, offsets, shapes, np.arange(len(paths), dtype=np.int32), d['center'][idx], d['scale'][idx],
+                                       img_res, dtype=dtype)                                                    # cam_dataset.py:367-377
+        else:
+            crops, shapes = [], []
+            for i, p in zip(idx, paths):
+                frame = torch.from_numpy(read_image_rgb(p)).to(device)
+                crops.append(dataset_crops(frame, d['center'][i:i + 1], d['scale'][i:i + 1], img_res, dtype=dtype))   # cam_dataset.py:367-377
+                shapes.append(tuple(frame.shape[:2]))
+            img = torch.cat(crops)
         shapes = np.asarray(shapes, np.float32)
         f = lambda a: torch.as_tensor(np.asarray(a), dtype=torch.float32).to(device)
         img_h, img_w = f(shapes[:, 0]), f(shapes[:, 1])
@@ -126,9 +133,9 @@ class EvalDataset:
         else:                                         # cam_dataset.py:617-653: precomputed CamCalib predictions
             R, K = cam_params_from_angles(d['camcalib_pitch'][idx], d['camcalib_roll'][idx], d['camcalib_f_pix'][idx],
                                           shapes[:, 1], shapes[:, 0], device=device)
-        return {'img': torch.cat(crops), 'cam_rotmat': R, 'cam_int': K, 'scale': f(d['scale'][idx]),
+        return {'img': img, 'cam_rotmat': R, 'cam_int': K, 'scale': f(d['scale'][idx]),
                 'center': f(d['center'][idx]), 'img_h': img_h, 'img_w': img_w,
-                'imgname': [os.path.join(self.img_dir, str(self.imgname[i])) for i in idx]}
+                'imgname': paths}
 
 
 @torch.no_grad()

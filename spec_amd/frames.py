@@ -31,7 +31,10 @@ class FrameStream:
         stream of the uploads; by default one is chosen by measurement (``_pick_copy_stream``).
         The crops are cut in the layout the step reads: that of a captured step's static buffers, else ``step.image_dtype``
         (``SpecPipeline``: NHWC8 fp16 when both models run at fp16 - no fp32 crop tensor exists then) with ``_fp32_crops=False``,
-        fp32 crops + in-trunk conversion with True (same bits); None = ``engine.F16_CROPS_DEFAULT``."""
+        fp32 crops + in-trunk conversion with True (same bits); None = ``engine.F16_CROPS_DEFAULT``.
+        The frames of a stream are equal-sized, so it stays on ``crop_detections_batch``; ``crop_detections_ragged`` serves frames
+        of different sizes and may rewrite its frame table and synchronise the device, which does not belong next to a captured
+        step."""
         self.step, self.device = step, torch.device(device)
         self.H, self.W = int(frame_hw[0]), int(frame_hw[1])
         self.F, self.N, self.S, self.scale = int(frames_per_step), int(crops_per_step), int(crop_size), float(scale)

@@ -111,6 +111,95 @@ def crop_detections_batch(frames_u8, frame_index, dets, scale: float = 1.0, crop
     return {'inp_images': img, 'bbox_scale': sc, 'bbox_center': ce}
 
 
+def pack_frames(frames, device=None):
+    """Host frames of different sizes -> one slab, the input convention of the ragged calls (``specmi_resize_normalize_ragged``,
+    ``specmi_crop_normalize_ragged``, ``specmi_crop_resize_normalize_ragged``): a list of (H,W,3) uint8 arrays ->
+    (1-D uint8 slab holding them back to back, (n,) int64 byte offsets, [(H, W)]).  ``device=None``: the slab stays a host
+    array; else it is uploaded in ONE copy and returned as a tensor on ``device``."""
+    import numpy as np
+    frames = list(frames)
+    if not frames:
+        raise ValueError('at least one frame')
+    sizes, offsets, off = [], [], 0
+    for fr in frames:
+        if not isinstance(fr, np.ndarray) or fr.dtype != np.uint8 or fr.ndim != 3 or fr.shape[2] != 3:
+            raise ValueError('frames must be (H,W,3) uint8 RGB')
+        H, W = fr.shape[:2]
+        sizes.append((int(H), int(W)))
+        offsets.append(off)
+        off += H * W * 3
+    slab = np.concatenate([np.ascontiguousarray(fr).reshape(-1) for fr in frames])
+    if device is not None:
+        slab = torch.from_numpy(slab).to(device)
+    return slab, np.asarray(offsets, dtype=np.int64), sizes
+
+
+def _ragged_args(name, slab, offsets, sizes, frame_index, n):
+    """The frame side of the ragged crop ``name``, checked in this order: the host tables (one offset and one (H, W) per
+    frame), ``frame_index`` against the number of frames while it is still on the host - ``crop_detections_batch``'s check -,
+    then the slab (1-D uint8 device tensor).  -> (engine, slab, offsets int64, geom (F,2) int32, frame_index on the device)."""
+    import numpy as np
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    geom = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1, 2)
+    F = geom.shape[0]
+    if F < 1 or offsets.shape[0] != F:
+        raise ValueError(f'{name}: one offset and one (H, W) per frame (at least one frame)')
+    fidx = frame_index if isinstance(frame_index, torch.Tensor) else torch.as_tensor(np.asarray(frame_index))
+    if fidx.device.type == 'cpu' and fidx.numel():
+        lo, hi = int(fidx.min()), int(fidx.max())
+        if lo < 0 or hi >= F:
+            raise ValueError(f'frame_index values must lie in [0, {F}), got [{lo}, {hi}]')
+    if tuple(fidx.shape) != (n,):
+        raise ValueError(f'{name}: frame_index must have one entry per crop')
+    if not isinstance(slab, torch.Tensor) or slab.device.type != 'cuda':
+        raise RuntimeError(f'{name} needs a device tensor (no CPU path in spec_amd)')
+    if slab.dtype != torch.uint8 or slab.dim() != 1 or not slab.is_contiguous():
+        raise ValueError(f'{name}: slab must be a contiguous 1-D uint8 tensor')
+    eng = _engine(slab.device)
+    return eng, slab, offsets, geom, fidx.to(device=eng.device, dtype=torch.int32).contiguous()
+
+
+@torch.no_grad()
+def crop_detections_ragged(slab, offsets, sizes, frame_index, dets, scale: float = 1.0, crop_size: int = 224, out=None,
+                           dtype=torch.float32):
+    """The detections of MANY frames of DIFFERENT sizes in one launch (``specmi_crop_normalize_ragged``): ``slab`` 1-D uint8
+    device tensor holding the (H,W,3) frames, ``offsets`` (F,) byte offsets and ``sizes`` [(H, W)] on the host (``pack_frames``
+    makes all three), ``frame_index`` (n,) int32, ``dets`` (n,4) [cx, cy, w, h] -> the same dict as ``crop_detections_batch``,
+    bit-identical to ``crop_detections`` frame by frame.  ``dtype=torch.float16``: NHWC8 fp16 crops.  A call whose offsets or
+    sizes differ from the previous call's synchronises the device (include/specmi.h): not for use under graph capture."""
+    f16 = out_dtype(dtype)
+    n = len(dets)
+    eng, slab, offsets, geom, fidx = _ragged_args('crop_detections_ragged', slab, offsets, sizes, frame_index, n)
+    dev = eng.device
+    boxes = _boxes_arg(dets, dev)
+    img, sc, ce = _crop_outputs(out, n, crop_size, dev, f16)
+    if n > 0:
+        fn = eng.lib.specmi_crop_normalize_f16_ragged if f16 else eng.lib.specmi_crop_normalize_ragged
+        _lib.check(eng.h, fn(eng.h, _ptr(slab), slab.numel(), offsets.ctypes.data_as(_lib.c_int64_p), geom.ctypes.data_as(_lib.c_int32_p),
+                             geom.shape[0], _ptr(fidx), _ptr(boxes), n, float(scale), crop_size, _ptr(img), None, _ptr(sc), _ptr(ce),
+                             eng._stream()))
+    return {'inp_images': img, 'bbox_scale': sc, 'bbox_center': ce}
+
+
+@torch.no_grad()
+def dataset_crops_ragged(slab, offsets, sizes, frame_index, centers, scales, crop_size: int = 224, dtype=torch.float32, out=None):
+    """``dataset_crops`` for the samples of a batch whose images differ in size, in one launch
+    (``specmi_crop_resize_normalize_ragged``): slab / offsets / sizes / frame_index as in ``crop_detections_ragged``, centers
+    (n,2), scales (n,) -> (n,3,S,S) fp32 or (n,S,S,8) NHWC8 fp16, bit-identical to ``dataset_crops`` sample by sample.  The
+    boxes still come from ``pare_crop_boxes`` on the host.  ``out``: the batch tensor to write into."""
+    f16 = out_dtype(dtype)
+    host_boxes = pare_crop_boxes(centers, scales, crop_size)
+    n = host_boxes.shape[0]
+    eng, slab, offsets, geom, fidx = _ragged_args('dataset_crops_ragged', slab, offsets, sizes, frame_index, n)
+    boxes = torch.from_numpy(host_boxes).to(eng.device)
+    out = _image_out(out, n, crop_size, crop_size, f16, eng.device)
+    if n > 0:
+        fn = eng.lib.specmi_crop_resize_normalize_f16_ragged if f16 else eng.lib.specmi_crop_resize_normalize_ragged
+        _lib.check(eng.h, fn(eng.h, _ptr(slab), slab.numel(), offsets.ctypes.data_as(_lib.c_int64_p), geom.ctypes.data_as(_lib.c_int32_p),
+                             geom.shape[0], _ptr(fidx), _ptr(boxes), n, crop_size, _ptr(out), eng._stream()))
+    return out
+
+
 def pare_crop_boxes(centers, scales, res: int = 224):
     """Integer crop boxes of pare's ``crop(img, center, scale, [res, res])`` (SPIN / PARE image_utils): ``ul = transform([1, 1],
     ..., invert=1) - 1``, ``br = transform([res + 1, res + 1], ..., invert=1) - 1`` with ``transform`` = 3x3 float64 matrix

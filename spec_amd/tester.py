@@ -20,8 +20,8 @@ import torch
 from . import assets, cam_utils, io_formats
 from .checkpoint import load_pretrained_model, read_checkpoint
 from .modules import HMR, CameraRegressorNetwork
-from .engine import flow_image_dtype, image_tensor
-from .preprocess import camcalib_transform, crop_detections
+from .engine import flow_image_dtype, flow_ragged_crops, image_tensor
+from .preprocess import camcalib_transform, crop_detections, crop_detections_ragged, pack_frames
 
 CAMCALIB_CKPT = 'data/camcalib/checkpoints/camcalib_sa_biased_l2.ckpt'     # scripts/camcalib_demo.py:39
 IMG_EXT = ('.png', '.jpg', '.jpeg')
@@ -97,6 +97,7 @@ class SPECTester:
         self.model.eval()
         self._camcalib = getattr(args, 'camcalib_model', None)
         self._fp32_crops = None       # False: NHWC8 fp16 crops for a model at fp16; True: fp32 crops + in-trunk conversion (same bits)
+        self._ragged_crops = None     # True: a flush's frames in one slab, one upload, one ragged crop launch; False: one of each per frame (same bits)
 
     def _build_model(self):
         c = self.model_cfg
@@ -125,6 +126,23 @@ class SPECTester:
             return [np.asarray(boxes.get(os.path.basename(f), boxes.get(f, [])), np.float32).reshape(-1, 4) for f in list_images(image_folder)]
         return [np.asarray(b, np.float32).reshape(-1, 4) for b in boxes]
 
+    def _crop_held(self, held, pending, buf, img_h, img_w, R, K, output_path, res, crop_dtype):
+        """The ragged route of ``run_on_image_folder`` for one flush: ``held`` [(RGB array, detections)] and ``pending``
+        [(image, first crop, crops)] name the same frames in the same order."""
+        import joblib
+        k = pending[-1][1] + pending[-1][2]
+        slab, offsets, sizes = pack_frames([rgb for rgb, _ in held], self.device)
+        counts = [n for _, _, n in pending]
+        crop_detections_ragged(slab, offsets, sizes, np.repeat(np.arange(len(held), dtype=np.int32), counts),
+                               np.concatenate([dets for _, dets in held]), scale=1.0, crop_size=res, dtype=crop_dtype,
+                               out={key: v[:k] for key, v in buf.items()})                           # tester.py:116-128
+        recs = [joblib.load(io_formats.camcalib_result_path(output_path, f)) for f, _, _ in pending]     # io_formats.read_cam_params
+        per_crop = lambda vals: np.repeat(np.asarray(vals, np.float32), counts)
+        h, w = per_crop([s[0] for s in sizes]), per_crop([s[1] for s in sizes])
+        img_h[:k], img_w[:k] = torch.from_numpy(h).to(self.device), torch.from_numpy(w).to(self.device)
+        R[:k], K[:k] = cam_utils.cam_params_from_angles(per_crop([r['pitch'].item() for r in recs]), per_crop([r['roll'].item() for r in recs]),
+                                                        per_crop([float(r['f_pix']) for r in recs]), w, h, device=self.device)
+
     def run_camcalib(self, image_folder, output_folder):
         return run_camcalib_folder(image_folder, f'{output_folder}/camcalib', ckpt=getattr(self.args, 'camcalib_ckpt', None) or CAMCALIB_CKPT,
                                    model=self._camcalib, device=self.device)
@@ -142,7 +160,11 @@ class SPECTester:
         choice is logged.  ``--plan auto`` buys the lowest per-frame latency (single / latency plan by detection count) at the
         price of last bits that depend on the batch (contract: 1e-4).
         Decode-ahead is bounded: at most 2 x ``args.decode_threads`` decoded frames wait in host memory (the reference holds
-        one frame at a time; an unbounded queue would keep a whole video folder in RAM when decoding outruns the GPU)."""
+        one frame at a time; an unbounded queue would keep a whole video folder in RAM when decoding outruns the GPU).
+        ``self._ragged_crops`` (None = ``engine.RAGGED_CROPS_DEFAULT``): the decoded frames of one flush are held on the host -
+        at most ``frame_batch`` of them, on top of the decode window -, packed into one slab, uploaded once and cut by ONE
+        ``crop_detections_ragged`` call; ``img_h``, ``img_w`` and the angles behind ``R`` / ``K`` are gathered on the host and go
+        up once per flush.  Same crops, same files, bit for bit."""
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         image_file_names = list_images(image_folder)
@@ -167,6 +189,8 @@ class SPECTester:
                'bbox_center': torch.empty(cap, 2, device=dev)}
         img_w, img_h = torch.empty(cap, device=dev), torch.empty(cap, device=dev)
         R, K = torch.empty(cap, 3, 3, device=dev), torch.empty(cap, 3, 3, device=dev)
+        ragged = flow_ragged_crops(self._ragged_crops)
+        held = []                     # ragged route: (RGB array, detections) of the frames waiting for this flush
         pending, k, n_done = [], 0, 0
         save = not getattr(self.args, 'no_save', False)
         if save:
@@ -176,6 +200,9 @@ class SPECTester:
             nonlocal k, pending
             if k == 0:
                 return
+            if ragged:
+                self._crop_held(held, pending, buf, img_h, img_w, R, K, output_path, res, crop_dtype)
+                held.clear()
             output = self.model(buf['inp_images'][:k], cam_rotmat=R[:k], cam_intrinsics=K[:k], bbox_scale=buf['bbox_scale'][:k],
                                 bbox_center=buf['bbox_center'][:k], img_w=img_w[:k], img_h=img_h[:k])
             output = {key: v.cpu().numpy() for key, v in output.items()}          # ONE device->host hand-over per batch
@@ -207,16 +234,19 @@ class SPECTester:
                 n = len(dets)
                 if k + n > cap:
                     flush()
-                frame = torch.from_numpy(rgb).pin_memory().to(dev, non_blocking=True)
-                orig_height, orig_width = frame.shape[:2]
-                crop_detections(frame, dets, scale=1.0, crop_size=res, dtype=crop_dtype,           # tester.py:116-128
-                                out={key: v[k:k + n] for key, v in buf.items()})
-                img_h[k:k + n] = float(orig_height)
-                img_w[k:k + n] = float(orig_width)
-                cam_rotmat, cam_intrinsics, *_ = io_formats.read_cam_params(output_path, img_fname, (orig_height, orig_width),
-                                                                            device=dev)
-                R[k:k + n] = cam_rotmat
-                K[k:k + n] = cam_intrinsics
+                if ragged:                                # cropped at the flush (_crop_held)
+                    held.append((rgb, dets))
+                else:
+                    frame = torch.from_numpy(rgb).pin_memory().to(dev, non_blocking=True)
+                    orig_height, orig_width = frame.shape[:2]
+                    crop_detections(frame, dets, scale=1.0, crop_size=res, dtype=crop_dtype,           # tester.py:116-128
+                                    out={key: v[k:k + n] for key, v in buf.items()})
+                    img_h[k:k + n] = float(orig_height)
+                    img_w[k:k + n] = float(orig_width)
+                    cam_rotmat, cam_intrinsics, *_ = io_formats.read_cam_params(output_path, img_fname, (orig_height, orig_width),
+                                                                                device=dev)
+                    R[k:k + n] = cam_rotmat
+                    K[k:k + n] = cam_intrinsics
                 pending.append((img_fname, k, n))
                 k += n
                 if per_frame:
