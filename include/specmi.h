@@ -527,6 +527,39 @@ int specmi_pano_extract_views(specmi_handle* h, const uint8_t* pano_rgb_hwc, int
                               const int32_t* out_hw, const int64_t* offsets, size_t slab_bytes, uint8_t* out_slab, int n,
                               void* stream);
 
+/* ---- the demo's pictures ------------------------------------------------------------------------ */
+
+#define SPECMI_RENDER_SIDE_VIEW 1           /* the 270 degree turn about y, black background (renderer_cam.py:82-85,197,207) */
+#define SPECMI_RENDER_GROUND_PLANE 2        /* side view only: the checker plane through the lowest vertex (:98-107) */
+#define SPECMI_RENDER_CULL 4                /* draw only the faces an outward-wound closed mesh shows */
+#define SPECMI_RENDER_THREAD_PER_TRIANGLE 8 /* one thread instead of one wavefront per triangle: the same bits (measurement) */
+
+/* The mesh overlay / side view of the M detections of ONE frame, rasterised on the device: replaces one pyrender / OpenGL
+ * OffscreenRenderer.render per detection and panel (spec/utils/renderer_cam.py:44-144 render_overlay_image, called by
+ * render_image_group :181-208 from spec/tester.py:191-201) and the device-to-host copy of the vertices that precedes it.
+ * Works on a handle of any model kind, committed or not.  DEVICE pointers: vertices (M,V,3) fp32, faces (F,3) int32, cam_t
+ * (M,3) fp32 (pred_cam_t), R (3,3) fp32 row-major (the render rotation of tester.py:169-171), frame and out (H,W,3) uint8 RGB,
+ * and the optional outputs id_map (H,W) int32 = m*F+f of the visible face, -1 where nothing is drawn, -2 on the ground
+ * plane; depth (H,W) fp32 = camera-space z, 0 where nothing is drawn (renderer_cam.py:141 tests rend_depth > 0); screen
+ * (M,V,3) 4-byte words = the vertex stage's snapped x and y as int32 in 1/256 pixel (INT32_MIN for a dropped vertex) and z as
+ * fp32.  HOST: rgb, 3 floats in [0, 1] (clamped).  frame may be NULL in side view (it is not read); out may be frame.
+ * The camera is pyrender's IntrinsicsCamera(fx, fy, cx, cy): x_s = cx + fx X / Z, pixel (i, j) centred at (j + 0.5, i + 0.5).
+ * The rasterisation contract - vertex stage, 1/256-pixel snapping, int64 edge functions with the top-left rule, culling,
+ * perspective-correct fp32 depth resolved by one 64-bit atomicMin per covered pixel (order-free; ties to the lower id), integer
+ * normal sums, this project's own shading min(1, 0.3 + 0.7 max(0, n.l)) and its own analytic ground plane - is stated at the
+ * head of spec_amd/csrc/render.hip and restated on the CPU in tests/render_ref.py.  A triangle with a vertex at Z <= 0.05 or
+ * at 2^20 pixels or more from the origin is dropped whole: THERE IS NO CLIPPING.  A face index outside [0, V) drops the face.
+ * Refused (SPECMI_ERR_ARG), launching nothing: a null required pointer (frame is required without SIDE_VIEW), an unknown
+ * flag, GROUND_PLANE without SIDE_VIEW, M, V or F below 1, M*F or 3*M*V of 2^31 or more, H or W outside [1, 32768], a focal
+ * length that is not positive and finite, a centre or colour that is not finite.
+ * The depth keys (8 bytes per pixel), snapped vertices and normal sums (12 bytes per vertex each) live in one workspace owned
+ * by the handle: calls on one handle are ordered on one stream at a time, and a call that needs a larger workspace first
+ * SYNCHRONISES THE WHOLE DEVICE and cannot be made while a stream is being captured (SPECMI_ERR_STATE). */
+int specmi_render_meshes(specmi_handle* h, const float* vertices, int M, int V, const int32_t* faces, int F, const float* cam_t,
+                         const float* R, float fx, float fy, float cx, float cy, const uint8_t* frame_rgb_hwc, int H, int W,
+                         const float* rgb, int flags, uint8_t* out_rgb_hwc, int32_t* id_map, float* depth, void* screen,
+                         void* stream);
+
 /* ---- evaluation metrics on the path's outputs ---------------------------------- */
 
 /* eval_single (spec/utils/compute_error.py:52-86, spec/trainer.py:272-316): joints =

@@ -11,6 +11,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only camcalib_eval      # the two kernels of CamCalib's test step -> profiles/camcalib_eval_aux.json
     python scripts/bench_aux.py --only pano_views         # the panorama view extractor -> profiles/pano_views_aux.json
     python scripts/bench_aux.py --only ragged_crops       # crops from frames of different sizes, per-frame route against the ragged one -> profiles/ragged_crops_aux.json
+    python scripts/bench_aux.py --only render             # mesh overlay + side view, 8 meshes on a 1080p frame, both raster launch shapes -> profiles/render_aux.json
     python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
 import argparse
@@ -319,9 +320,41 @@ def finish(a, table, extra=None):
               f"{r['achieved_GBps']:8.1f} GB/s  frac {r['frac_of_hbm_peak']:.3f}   {r['workload']}")
 
 
+def render_workload(M=8, H=1080, W=1920):
+    """8 person-sized closed meshes of SMPL's face count order (icospheres of 5120 faces stretched to 0.5 x 1.7 x 0.3 m) spread
+    over a 1080p frame at 3 .. 6 m from a camera of f = 1200 px."""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from tests.render_ref import icosphere
+    v, f = icosphere(4)
+    v = v * np.array([0.25, 0.85, 0.15], np.float32)
+    t = np.array([[-2.4 + 0.7 * m, 0.1 * (m % 3 - 1), 3.0 + 0.43 * m] for m in range(M)], np.float32)
+    return np.ascontiguousarray(np.broadcast_to(v, (M,) + v.shape)), f, t, (1200., 1200.), (W / 2, H / 2), (H, W)
+
+
+def render_section(eng, a):
+    """The mesh overlay and the side view (specmi_render_meshes) of 8 meshes on a 1080p frame: per-launch HIP events of the three
+    kernels in both launch shapes of the raster kernel, next to the bytes they must touch."""
+    from spec_amd import _lib
+    v, f, t, focal, center, (H, W) = render_workload()
+    dev = eng.device
+    frame = torch.randint(0, 256, (H, W, 3), dtype=torch.uint8).to(dev)
+    args = [torch.from_numpy(x).to(dev) for x in (v, f, t, np.eye(3, dtype=np.float32))]
+    rows = {}
+    for name, flags in (('overlay', _lib.RENDER_CULL), ('side_view', _lib.RENDER_CULL | _lib.RENDER_SIDE_VIEW | _lib.RENDER_GROUND_PLANE)):
+        for shape, bit in (('wave_per_triangle', 0), ('thread_per_triangle', _lib.RENDER_THREAD_PER_TRIANGLE)):
+            call = lambda: eng.render_meshes(args[0], args[1], args[2], args[3], focal, center, frame=frame, flags=flags | bit)
+            res = timed(eng, call, a.iters)
+            covered = int((eng.render_meshes(args[0], args[1], args[2], args[3], focal, center, frame=frame, flags=flags | bit, maps=True)['id_map'] >= 0).sum())
+            rows[f'{name}.{shape}'] = {'kernels_ms': {k: round(ms, 5) for k, (ms, _, _, _) in res.items()}, 'total_ms': round(sum(ms for ms, _, _, _ in res.values()), 5),
+                                       'algorithmic_MB': {k: round(by / 1e6, 3) for k, (_, by, _, _) in res.items()}, 'mesh_pixels': covered}
+    return {'workload': f'{v.shape[0]} meshes of {v.shape[1]} vertices / {f.shape[0]} faces on a {W} x {H} frame, f = {focal[0]:.0f} px', 'calls': rows,
+            'must_touch_MB': {'keys_memset_and_resolve': round(H * W * 16 / 1e6, 3), 'frame_in_out': round(H * W * 6 / 1e6, 3),
+                              'vertices_faces': round((v.size * 4 * 3 + v.shape[0] * f.size * 4) / 1e6, 3)}}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render'], default=None, help='run one section only')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -362,6 +395,16 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'per-launch HIP events (library profiler); wall clock where named',
                        'pano_views': row, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'render':
+        from spec_amd import _lib
+        row = render_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'per-launch HIP events (library profiler)', 'render': row,
+                       'source_hash': _lib.source_hash()}, f, indent=1)
+        print(json.dumps(row))
         return
 
     if a.only == 'ragged_crops':

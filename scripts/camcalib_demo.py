@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """Drop-in for the reference's ``scripts/camcalib_demo.py`` (same flags: --img_folder --out_folder --loss --ckpt --show
 --no_save) on MI355X: CamCalib on every image of a folder, one ``<image name>.pkl`` with ``{'vfov','f_pix','pitch','roll'}``
-per image in ``--out_folder`` (what ``spec/utils/cam_params.py:28-35`` reads back).  The horizon-line visualisations
-(--show / saved images, matplotlib + skimage in the reference) are outside the path: ``--no_save`` is implied."""
+per image in ``--out_folder`` (what ``spec/utils/cam_params.py:28-35`` reads back) and, without ``--no_save``, the image with
+the predicted horizon line and caption next to it under the image's own name (scripts/camcalib_demo.py:154-155,217-218 of the
+reference: ``show_horizon_line(..., debug=True, color=(255, 0, 0), width=3)``, drawn on the host with Pillow).  The logit
+plots of ``--show`` (matplotlib) are not produced."""
 import argparse
 import os
 import sys
@@ -19,9 +21,17 @@ def main(args):
     torch.set_grad_enabled(False)
     if args.img_folder in (None, '-'):
         sys.exit('only --img_folder input is built (the dataset modes need the Pano360 / SPEC datasets)')
-    if args.show or not args.no_save:
-        print('[camcalib_demo] visualisation output is not produced by this build (pickles only)', file=sys.stderr)
+    if args.show:
+        print('[camcalib_demo] the logit plots of --show are not produced by this build', file=sys.stderr)
     res = run_camcalib_folder(args.img_folder, args.out_folder, ckpt=args.ckpt or CKPT, loss_type=args.loss)
+    if not args.no_save:
+        from PIL import Image
+        from spec_amd.render import show_horizon_line
+        from spec_amd.tester import _read_rgb
+        for img_fname, rec in res.items():
+            img, _ = show_horizon_line(_read_rgb(img_fname), float(rec['vfov']), float(rec['pitch']), float(rec['roll']),
+                                       focal_length=float(rec['f_pix']), debug=True, color=(255, 0, 0), width=3, GT=False)
+            Image.fromarray(img).save(os.path.join(args.out_folder, os.path.basename(img_fname)))
     print(f'CamCalib: {len(res)} images -> {args.out_folder}')
 
 

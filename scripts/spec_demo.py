@@ -8,8 +8,9 @@
     frame -> CamCalib (vfov, pitch, roll) -> <out>/camcalib/<name>.pkl -> (R, K) -> crops on the device ->
     SPEC (HMR regressor + SMPL + projection) -> <out>/spec_results/<stem>.pkl
 
-Differences by design (see spec_amd/tester.py): CamCalib runs in-process, crops are cut on the device, the person detector and
-the renderer are outside the path - boxes come from ``--detections`` (joblib: list per image or {image name: (n,4) [cx, cy, w,
+Differences by design (see spec_amd/tester.py): CamCalib runs in-process, crops are cut on the device, the pictures are drawn by
+this project's own device rasteriser (spec_amd/render.py: the reference's geometry, its own shading) and the person detector is
+outside the path - boxes come from ``--detections`` (joblib: list per image or {image name: (n,4) [cx, cy, w,
 h]}); without it one centred square box per frame is used.  ``--synthetic N`` runs the same flow on N random frames with random
 weights (no licensed assets needed)."""
 import argparse
@@ -113,7 +114,7 @@ if __name__ == '__main__':
                              "bit-identical for any batching); 'auto' = lowest latency per forward, last bits depend on the batch")
     parser.add_argument('--display', action='store_true')
     parser.add_argument('--smooth', action='store_true')
-    parser.add_argument('--no_render', action='store_true', help='(rendering is never done by this build)')
+    parser.add_argument('--no_render', action='store_true', help='write no pictures (frame with horizon line | mesh overlay | side view, drawn by the device rasteriser)')
     parser.add_argument('--no_save', action='store_true', help='disable final save of output results.')
     parser.add_argument('--save_obj', action='store_true')
     parser.add_argument('--sideview', action='store_true')

@@ -32,6 +32,7 @@ def source_hash() -> str:
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_MISSING = 0, 1, 2, 3, 4
 PRECISION_FP32, PRECISION_FP16 = 0, 1       # SPECMI_PRECISION_* (include/specmi.h)
 MODEL_CAMCALIB, MODEL_HMR, MODEL_SMPL = 0, 1, 2
+RENDER_SIDE_VIEW, RENDER_GROUND_PLANE, RENDER_CULL, RENDER_THREAD_PER_TRIANGLE = 1, 2, 4, 8     # SPECMI_RENDER_* (include/specmi.h)
 LOSS_TYPES = {'ce': 0, 'kl': 1, 'softargmax_l2': 2, 'softargmax_biased_l2': 3}     # SPECMI_LOSS_* (include/specmi.h)
 
 c_float_p = C.POINTER(C.c_float)
@@ -156,6 +157,10 @@ PROTOTYPES = {
                                            C.POINTER(HmrOutputs), C.c_void_p]),
     'specmi_pano_extract_views': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, c_double_p, c_int32_p, c_int64_p, C.c_size_t,
                                             C.c_void_p, C.c_int, C.c_void_p]),
+    # (h, vertices, M, V, faces, F, cam_t, R, fx, fy, cx, cy, frame, H, W, rgb, flags, out, id_map, depth, screen, stream)
+    'specmi_render_meshes': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_int,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'specmi_camcalib_eval': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import constants as C
 
-_STATE: Dict[str, Optional[dict]] = {'smpl': None, 'mean': None}
+_STATE: Dict[str, Optional[dict]] = {'smpl': None, 'mean': None, 'faces': None, 'smpl_path': None}
 
 DEFAULT_SMPL_DIR = 'data/body_models/smpl'
 DEFAULT_MEAN_PARAMS = 'data/smpl_mean_params.npz'
@@ -33,6 +33,7 @@ def use_synthetic_assets(seed: int = 1003, mean_params: Optional[dict] = None):
     _STATE['mean'] = mean_params or {
         'pose': np.tile(np.array([1, 0, 0, 1, 0, 0], np.float32), 24),
         'shape': np.zeros(10, np.float32), 'cam': np.array([0.9, 0., 0.], np.float32)}
+    _STATE['faces'], _STATE['smpl_path'] = None, None               # the face table is made when a picture is first drawn
     return _STATE['smpl']
 
 
@@ -66,8 +67,8 @@ def _dense(a):
     return np.asarray(a)
 
 
-def load_smpl_file(path: str, j_regressor_extra: Optional[np.ndarray] = None) -> dict:
-    """SMPL .pkl / .npz -> the tensor dict libspecmi expects (smplx.SMPL buffer layouts)."""
+def _read_smpl_raw(path: str) -> dict:
+    """The members of an SMPL .pkl / .npz file (or of the model file in a directory) as stored."""
     if os.path.isdir(path):
         for cand in ('SMPL_NEUTRAL.pkl', 'SMPL_NEUTRAL.npz', 'basicModel_neutral_lbs_10_207_0_v1.0.0.pkl'):
             if os.path.exists(os.path.join(path, cand)):
@@ -82,6 +83,18 @@ def load_smpl_file(path: str, j_regressor_extra: Optional[np.ndarray] = None) ->
     else:
         with open(path, 'rb') as f:
             raw = _RestrictedUnpickler(f, encoding='latin1').load()
+    return raw
+
+
+def load_smpl_faces(path: str) -> np.ndarray:
+    """The ``f`` table of an SMPL file: (13776, 3) int32 vertex indices, outward-wound (what smplx.SMPL calls ``faces``,
+    spec/utils/renderer_cam.py:58-65)."""
+    return np.ascontiguousarray(_dense(_read_smpl_raw(path)['f']).astype(np.int32).reshape(-1, 3))
+
+
+def load_smpl_file(path: str, j_regressor_extra: Optional[np.ndarray] = None) -> dict:
+    """SMPL .pkl / .npz -> the tensor dict libspecmi expects (smplx.SMPL buffer layouts)."""
+    raw = _read_smpl_raw(path)
     v_template = _dense(raw['v_template']).astype(np.float32)
     nv = v_template.shape[0]
     shapedirs = _dense(raw['shapedirs']).astype(np.float32)[:, :, :C.NUM_BETAS]
@@ -109,6 +122,7 @@ def load_assets(smpl_path: str = DEFAULT_SMPL_DIR, mean_params_path: str = DEFAU
                 j_regressor_extra_path: str = DEFAULT_J_EXTRA):
     jx = np.load(j_regressor_extra_path)
     _STATE['smpl'] = load_smpl_file(smpl_path, jx)
+    _STATE['faces'], _STATE['smpl_path'] = None, smpl_path          # the face table is read when a picture is first drawn
     mp = np.load(mean_params_path)
     _STATE['mean'] = {'pose': mp['pose'].astype(np.float32), 'shape': mp['shape'].astype(np.float32),
                       'cam': mp['cam'].astype(np.float32)}
@@ -134,3 +148,15 @@ def smpl_model() -> dict:
 def mean_params() -> dict:
     _ensure()
     return _STATE['mean']
+
+
+def faces() -> np.ndarray:
+    """The body model's triangles, (F, 3) int32: the ``f`` table of the SMPL file, or the synthetic model's own table."""
+    _ensure()
+    if _STATE['faces'] is None:
+        if _STATE['smpl_path'] is None:
+            from . import synth
+            _STATE['faces'] = synth.smpl_faces(_STATE['smpl']['v_template'])
+        else:
+            _STATE['faces'] = load_smpl_faces(_STATE['smpl_path'])
+    return _STATE['faces']

@@ -802,6 +802,7 @@ int specmi_destroy(specmi_handle* h) {
     if (h->ragged_tmp) (void)hipFree(h->ragged_tmp);
     if (h->pano_tab) (void)hipFree(h->pano_tab);
     if (h->crop_tab) (void)hipFree(h->crop_tab);
+    if (h->render_ws) (void)hipFree(h->render_ws);
     hrnet_free(h->hrnet);
     delete h;
     return SPECMI_OK;
@@ -1572,6 +1573,41 @@ int specmi_pano_extract_views(specmi_handle* h, const uint8_t* pano, int PH, int
     }
     LaunchCtx ctx{s, &h->prof, "preprocess.pano_views"};
     LAUNCHCHK(h, launch_pano_extract(pano, PH, PW, h->pano_tab, n, max_tiles, out_bytes, out_slab, ctx), "pano_extract_views");
+    return SPECMI_OK;
+}
+
+int specmi_render_meshes(specmi_handle* h, const float* vertices, int M, int V, const int32_t* faces, int F, const float* cam_t,
+                         const float* R, float fx, float fy, float cx, float cy, const uint8_t* frame, int H, int W, const float* rgb,
+                         int flags, uint8_t* out, int32_t* id_map, float* depth, void* screen, void* stream) {
+    ENTER(h);
+    const bool side = flags & SPECMI_RENDER_SIDE_VIEW, ground = flags & SPECMI_RENDER_GROUND_PLANE;
+    if (!vertices || !faces || !cam_t || !R || !rgb || !out) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (flags & ~(SPECMI_RENDER_SIDE_VIEW | SPECMI_RENDER_GROUND_PLANE | SPECMI_RENDER_CULL | SPECMI_RENDER_THREAD_PER_TRIANGLE))
+        return fail(h, SPECMI_ERR_ARG, "unknown render flag in 0x%x", flags);
+    if (!side && !frame) return fail(h, SPECMI_ERR_ARG, "an overlay needs the frame it is drawn over (null pointer)");
+    if (ground && !side) return fail(h, SPECMI_ERR_ARG, "the ground plane belongs to the side view");
+    if (M < 1 || V < 1 || F < 1) return fail(h, SPECMI_ERR_ARG, "%d meshes of %d vertices and %d faces", M, V, F);
+    if ((double)M * F >= 2147483648.0 || (double)M * V * 3 >= 2147483648.0)
+        return fail(h, SPECMI_ERR_ARG, "%d meshes of %d vertices and %d faces are beyond 31-bit ids", M, V, F);
+    if (H < 1 || W < 1 || H > 32768 || W > 32768) return fail(h, SPECMI_ERR_ARG, "a %d x %d frame (1 .. 32768 per side)", H, W);
+    if (!(fx > 0.f) || !(fy > 0.f) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy))
+        return fail(h, SPECMI_ERR_ARG, "focal length (%g, %g) (> 0, finite) / centre (%g, %g) (finite)", (double)fx, (double)fy, (double)cx, (double)cy);
+    RenderArgs a{};
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(rgb[k])) return fail(h, SPECMI_ERR_ARG, "base colour component %d is not finite", k);
+        a.rgb[k] = std::fmin(std::fmax(rgb[k], 0.f), 1.f);
+    }
+    size_t off[4];
+    const size_t need = render_ws_layout(M, V, H, W, off);
+    if (int rc = grow_ragged(h, &h->render_ws, &h->render_ws_bytes, need, "the render workspace")) return rc;
+    char* ws = (char*)h->render_ws;
+    a.vertices = vertices; a.faces = faces; a.cam_t = cam_t; a.R = R; a.frame = frame;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
+    a.M = M; a.V = V; a.F = F; a.H = H; a.W = W; a.side = side; a.ground = ground; a.cull = (flags & SPECMI_RENDER_CULL) ? 1 : 0;
+    a.keys = (unsigned long long*)(ws + off[0]); a.sws = (int*)(ws + off[1]); a.normals = (int*)(ws + off[2]); a.lowest = (int*)(ws + off[3]);
+    a.out = out; a.id_map = id_map; a.depth = depth; a.screen = (int*)screen;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, side ? "render.side_view" : "render.overlay"};
+    LAUNCHCHK(h, launch_render(a, (flags & SPECMI_RENDER_THREAD_PER_TRIANGLE) != 0, ctx), "render_meshes");
     return SPECMI_OK;
 }
 

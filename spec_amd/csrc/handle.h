@@ -172,6 +172,9 @@ struct specmi_handle {
     CropFrame* crop_tab = nullptr;
     size_t crop_tab_bytes = 0;
     std::vector<CropFrame> crop_host;   // host image of crop_tab as last uploaded
+    // mesh rasteriser (specmi_render_meshes): depth keys, snapped vertices, normal sums; grows like ragged_tmp
+    void* render_ws = nullptr;
+    size_t render_ws_bytes = 0;
     SkWs sk;                            // split-K partial tiles + arrival counters (ensure_sk; never allocated under graph capture:
                                         // the warm-up call of a shape sizes it)
     std::vector<void*> sk_retired;      // outgrown split-K buffers, kept until destroy (captured graphs may still name them)

@@ -428,4 +428,30 @@ int pano_view_tiles(int H, int W);      // workgroups a view of this size takes
 int launch_pano_extract(const unsigned char* pano, int PH, int PW, const PanoView* views, int n, int max_tiles, double out_bytes,
                         unsigned char* out, const LaunchCtx& ctx);
 
+// ----------------------------------------------------------------------------------------
+// mesh overlay / side view rasteriser  (render.hip)
+// ----------------------------------------------------------------------------------------
+// One specmi_render_meshes call as the three kernels read it.  keys / sws / normals / lowest are the four parts of the
+// handle's render workspace (render_ws_layout); screen, id_map, depth are the caller's optional outputs.
+struct RenderArgs {
+    const float* vertices;      // (M, V, 3)
+    const int* faces;           // (F, 3)
+    const float* cam_t;         // (M, 3)
+    const float* R;             // (3, 3)
+    const unsigned char* frame; // (H, W, 3); unused in side view
+    float fx, fy, cx, cy, rgb[3];
+    int M, V, F, H, W, side, ground, cull;
+    unsigned long long* keys;   // (H, W): float_bits(z) << 32 | id, all ones = nothing drawn
+    int* sws;                   // (M, V, 3): snapped x, y and the bits of z
+    int* normals;               // (M, V, 3): fixed-point sums of the incident face normals
+    int* lowest;                // the lowest y of the scene as an ordered int (ground plane)
+    unsigned char* out;         // (H, W, 3)
+    int* id_map;                // (H, W) or null
+    float* depth;               // (H, W) or null
+    int* screen;                // (M, V, 3) or null: the caller's copy of sws
+};
+// byte offsets of keys, sws, normals, lowest in the workspace -> its size
+size_t render_ws_layout(int M, int V, int H, int W, size_t off[4]);
+int launch_render(const RenderArgs& a, bool thread_per_triangle, const LaunchCtx& ctx);
+
 }  // namespace specmi

@@ -482,6 +482,53 @@ class Engine:
             out_hw.ctypes.data_as(_lib.c_int32_p), offsets.ctypes.data_as(_lib.c_int64_p), out.numel(), _ptr(out), n, self._stream()))
         return out, offsets
 
+    def render_meshes(self, vertices, faces, cam_t, R, focal, center, frame=None, size=None, rgb=(1., 1., 1.), flags=0, maps=False):
+        """``specmi_render_meshes``: ``vertices`` (M, V, 3) / ``cam_t`` (M, 3) / ``R`` (3, 3) fp32 and ``faces`` (F, 3) int32 on the
+        engine device, ``focal`` = (fx, fy), ``center`` = (cx, cy), ``frame`` (H, W, 3) uint8 (may be None in side view, then
+        ``size`` = (H, W)), ``flags`` of ``_lib.RENDER_*``.  -> the (H, W, 3) uint8 image; with ``maps`` a dict that also holds
+        ``id_map`` (H, W) int32, ``depth`` (H, W) fp32, ``screen_xy`` (M, V, 2) int32 and ``screen_z`` (M, V) fp32.
+        Everything is checked here, before the library is called."""
+        d = self.device
+        for name, x, dt in (('vertices', vertices, torch.float32), ('cam_t', cam_t, torch.float32), ('R', R, torch.float32), ('faces', faces, torch.int32)):
+            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != dt or not x.is_contiguous():
+                raise ValueError(f'{name} must be a contiguous {dt} tensor on the engine device')
+        if vertices.dim() != 3 or vertices.shape[2] != 3 or min(vertices.shape[:2]) < 1:
+            raise ValueError('vertices must be (M, V, 3) with M, V >= 1')
+        M, V = int(vertices.shape[0]), int(vertices.shape[1])
+        if tuple(cam_t.shape) != (M, 3) or tuple(R.shape) != (3, 3):
+            raise ValueError('cam_t must be (M, 3) and R (3, 3)')
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+            raise ValueError('faces must be (F, 3) with F >= 1')
+        side = bool(flags & _lib.RENDER_SIDE_VIEW)
+        if flags & ~15 or (flags & _lib.RENDER_GROUND_PLANE and not side):
+            raise ValueError('flags: RENDER_SIDE_VIEW | RENDER_GROUND_PLANE (side view only) | RENDER_CULL | RENDER_THREAD_PER_TRIANGLE')
+        if frame is not None:
+            if (not isinstance(frame, torch.Tensor) or frame.device != d or frame.dtype != torch.uint8 or frame.dim() != 3
+                    or frame.shape[2] != 3 or not frame.is_contiguous()):
+                raise ValueError('frame must be a contiguous (H, W, 3) uint8 tensor on the engine device')
+            size = tuple(frame.shape[:2])
+        elif not side or size is None:
+            raise ValueError('an overlay needs its frame; a side view its frame or size=(H, W)')
+        H, W = int(size[0]), int(size[1])
+        if not (1 <= H <= 32768 and 1 <= W <= 32768):
+            raise ValueError('a frame of 1 .. 32768 pixels per side')
+        cam = [float(focal[0]), float(focal[1]), float(center[0]), float(center[1])]
+        if not (all(np.isfinite(cam)) and cam[0] > 0 and cam[1] > 0):
+            raise ValueError('focal lengths must be positive and finite, the centre finite')
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32).reshape(-1)
+        if rgb.shape[0] != 3 or not np.isfinite(rgb).all():
+            raise ValueError('rgb: three finite floats in [0, 1]')
+        out = torch.empty(H, W, 3, device=d, dtype=torch.uint8)
+        id_map = torch.empty(H, W, device=d, dtype=torch.int32) if maps else None
+        depth = torch.empty(H, W, device=d, dtype=torch.float32) if maps else None
+        screen = torch.empty(M, V, 3, device=d, dtype=torch.int32) if maps else None
+        _lib.check(self.h, self.lib.specmi_render_meshes(
+            self.h, _ptr(vertices), M, V, _ptr(faces), int(faces.shape[0]), _ptr(cam_t), _ptr(R), *cam, _ptr(frame), H, W,
+            rgb.ctypes.data_as(_lib.c_float_p), int(flags), _ptr(out), _ptr(id_map), _ptr(depth), _ptr(screen), self._stream()))
+        if not maps:
+            return out
+        return {'image': out, 'id_map': id_map, 'depth': depth, 'screen_xy': screen[..., :2], 'screen_z': screen[..., 2].contiguous().view(torch.float32)}
+
     def _cam_args(self, B, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h):
         d = self.device
         return (_dev_f32(cam_rotmat, d, (B, 3, 3)), _dev_f32(cam_intrinsics, d, (B, 3, 3)),

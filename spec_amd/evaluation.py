@@ -253,7 +253,7 @@ def write_standin_data_tree(root: str, n_images: int = 6, seed: int = 7, dataset
             'posedirs': Ch(model['posedirs'].T.reshape(V, 3, 207).astype(np.float64)),
             'J_regressor': sp.csc_matrix(model['J_regressor'].astype(np.float64)),
             'weights': Ch(model['lbs_weights'].astype(np.float64)),
-            'kintree_table': kintree, 'f': np.zeros((13776, 3), np.uint32),
+            'kintree_table': kintree, 'f': synth.smpl_faces(model['v_template']).astype(np.uint32),
             'bs_type': 'lrotmin', 'bs_style': 'lbs',
         }
         with open(j('data/body_models/smpl/SMPL_NEUTRAL.pkl'), 'wb') as f:

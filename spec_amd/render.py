@@ -1,0 +1,180 @@
+"""The demo's pictures: the mesh overlay and the side view rasterised on the device (``specmi_render_meshes``,
+spec_amd/csrc/render.hip) and the three-panel image the reference writes per detection
+(``spec/utils/renderer_cam.py:147-218 render_image_group``, called from ``spec/tester.py:191-201`` and ``spec/trainer.py:366-``).
+
+What is exact and what is this project's own: the geometry (the x flip of the translation, the 180 / 270 degree turns, the camera
+pose and pyrender's intrinsics) is the reference's, and coverage and visibility follow a contract that is reproducible bit for
+bit (tests/render_ref.py).  The look is NOT pyrender's: shading is ``rgb * min(1, 0.3 + 0.7 max(0, n.l))``, the side view's
+ground plane is an analytic two-grey checker of 0.5 m tiles (the reference's ``get_checkerboard_plane`` lives in the un-vendored
+``pare``), the colour table below is a stand-in for ``pare``'s ``get_colors`` and there is no alpha blending.  Triangles that
+reach behind the near plane (z <= 0.05) are dropped, not clipped.  The horizon line and its caption are drawn on the host with
+Pillow exactly as ``camcalib/vis_utils.py:63-110`` does."""
+from __future__ import annotations
+
+import os
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+
+# stand-ins for pare.utils.vis_utils.get_colors() (RGB, 0 .. 255)
+COLORS = {'pinkish': (204, 128, 153), 'pink': (230, 153, 179), 'gray': (166, 166, 166), 'grey': (166, 166, 166), 'white': (255, 255, 255),
+          'light_blue': (166, 191, 230), 'green': (128, 204, 128)}
+
+
+def _rgb(color):
+    c = COLORS[color] if isinstance(color, str) else color
+    c = np.asarray(c, np.float32).reshape(3)
+    return c / 255.0 if c.max() > 1.0 else c
+
+
+_faces_cache = {}
+
+
+def device_faces(faces, device) -> torch.Tensor:
+    """``faces`` (None = the body model's table, ``assets.faces()``) as an (F, 3) int32 tensor on ``device``; the model's table is
+    uploaded once per device."""
+    if isinstance(faces, torch.Tensor):
+        return faces.to(device=device, dtype=torch.int32).contiguous()
+    if faces is not None:
+        return torch.from_numpy(np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)).to(device)
+    from . import assets
+    table = assets.faces()
+    key = (id(table), str(device))
+    if key not in _faces_cache:
+        _faces_cache.clear()
+        _faces_cache[key] = (table, torch.from_numpy(table).to(device))
+    return _faces_cache[key][1]
+
+
+def render_overlay(frame_u8, vertices, cam_t, R, focal, center, faces=None, color='pinkish', side_view=False, ground_plane=False,
+                   cull=True, engine=None, maps=False):
+    """The meshes ``vertices`` (M, V, 3) - or one mesh (V, 3) - with translations ``cam_t`` (M, 3) drawn over ``frame_u8``
+    (H, W, 3) uint8 as ``render_overlay_image`` places them (renderer_cam.py:74-117): camera rotation ``R`` (3, 3), ``focal`` =
+    (fx, fy), ``center`` = (cx, cy).  ``side_view``: the 270 degree turn about y on a black background, ``ground_plane`` adds the
+    checker plane to it.  Everything stays on the device: -> (H, W, 3) uint8 tensor (``maps``: the dict of
+    ``Engine.render_meshes``).  There is no host path."""
+    from . import cam_utils
+    if not isinstance(frame_u8, torch.Tensor) or frame_u8.device.type != 'cuda':
+        raise ValueError('frame_u8 must be a device tensor: the renderer has no host path')
+    dev = frame_u8.device
+    eng = engine or cam_utils._engine(dev)
+    as_f32 = lambda x: torch.as_tensor(x).to(device=eng.device, dtype=torch.float32).contiguous()
+    vertices, cam_t, R = as_f32(vertices), as_f32(cam_t), as_f32(R)
+    if vertices.dim() == 2:
+        vertices, cam_t = vertices[None], cam_t.reshape(1, 3)
+    flags = ((_lib.RENDER_SIDE_VIEW if side_view else 0) | (_lib.RENDER_GROUND_PLANE if ground_plane else 0) | (_lib.RENDER_CULL if cull else 0))
+    return eng.render_meshes(vertices, device_faces(faces, eng.device), cam_t, R, focal, center, frame=frame_u8.contiguous(),
+                             rgb=_rgb(color), flags=flags, maps=maps)
+
+
+def show_horizon_line(image, vfov, pitch, roll, focal_length=-1, color=(0, 255, 0), width=5, debug=False, GT=False, text_size=16):
+    """``camcalib/vis_utils.py:63-110`` on the host with Pillow: the horizon of a camera with (vfov, pitch, roll) in radians as a
+    line across ``image`` (H, W, 3), with ``debug`` a black caption strip of ``text_size`` rows (top, or bottom for ``GT``) and
+    the angles in degrees in Pillow's default font.  -> (uint8 image, horizon height as a fraction of H)."""
+    from PIL import Image, ImageDraw
+    image = np.array(image)
+    h, w = image.shape[:2]
+    if image.dtype in (np.float32, np.float64):
+        image = image.astype('uint8')
+    if debug:
+        strip = slice(h - text_size, h) if GT else slice(0, text_size)
+        image[strip, :, :] = 0
+    im = Image.fromarray(image)
+    draw = ImageDraw.Draw(im)
+    ctr = h * (0.5 - 0.5 * np.tan(pitch) / np.tan(vfov / 2))
+    left, right = ctr - w * np.tan(roll) / 2, ctr + w * np.tan(roll) / 2
+    if debug:
+        caption = 'vfov:{0:.1f}, pitch:{1:.1f}, roll:{2:.1f}, f_pix:{3:.1f}'.format(np.degrees(vfov), np.degrees(pitch), np.degrees(roll), focal_length)
+        draw.text((0, h - text_size) if GT else (0, 0), ('GT: ' if GT else '') + caption, (255, 255, 255))
+    draw.line((0, left, w, right), fill=color, width=width)
+    return np.array(im), ctr / h
+
+
+def write_obj(path: str, vertices, faces) -> str:
+    """A Wavefront .obj with ``v`` and 1-based ``f`` records (17 significant digits are not needed: ``%.9g`` round-trips fp32)."""
+    v, f = np.asarray(vertices, np.float32).reshape(-1, 3), np.asarray(faces, np.int64).reshape(-1, 3)
+    with open(path, 'w') as fh:
+        fh.writelines('v %.9g %.9g %.9g\n' % tuple(p) for p in v.tolist())
+        fh.writelines('f %d %d %d\n' % tuple(t) for t in (f + 1).tolist())
+    return path
+
+
+def read_obj(path: str):
+    """-> (vertices (V, 3) float32, faces (F, 3) int32, 0-based) of a file ``write_obj`` wrote (``f`` records may carry /vt/vn)."""
+    v, f = [], []
+    with open(path) as fh:
+        for line in fh:
+            p = line.split()
+            if p and p[0] == 'v':
+                v.append([float(x) for x in p[1:4]])
+            elif p and p[0] == 'f':
+                f.append([int(x.split('/')[0]) - 1 for x in p[1:4]])
+    return np.asarray(v, np.float32).reshape(-1, 3), np.asarray(f, np.int32).reshape(-1, 3)
+
+
+def group_panel0(image, cam_params=None) -> np.ndarray:
+    """Panel 0 of the three-panel picture on the host: ``image`` as uint8 (floats in [0, 1] are scaled, floats beyond 10 taken
+    as 0 .. 255: renderer_cam.py:164-165) with, given ``cam_params`` = (vfov, pitch, roll, f_pix), the horizon line and caption
+    of :170-173."""
+    image = np.asarray(image)
+    if image.dtype != np.uint8:
+        image = np.clip(image * 255.0 if image.max() <= 10 else image, 0, 255).astype(np.uint8)
+    if cam_params is not None:
+        image, _ = show_horizon_line(image, cam_params[0], cam_params[1], cam_params[2], focal_length=cam_params[3], color=(0, 255, 0),
+                                     width=5, debug=True, text_size=30)
+    return np.ascontiguousarray(image)
+
+
+def render_image_group(image, camera_translation, vertices, camera_rotation, focal_length, camera_center, mesh_color='pinkish',
+                       faces=None, mesh_filename: Optional[str] = None, save_filename: Optional[str] = None, cam_params: Optional[Sequence] = None,
+                       device=None, engine=None):
+    """The three panels of ``render_image_group`` (renderer_cam.py:147-218) side by side, (H, 3W, 3) uint8 on the device:
+
+    0. ``image`` (H, W, 3; uint8, or floats in [0, 1] / [0, 255] as the reference accepts) with - given ``cam_params`` =
+       (vfov, pitch, roll, f_pix) - the horizon line and caption of ``show_horizon_line(..., width=5, debug=True, text_size=30)``;
+    1. the meshes drawn over panel 0;
+    2. the side view at 270 degrees with the ground plane.
+
+    ``vertices`` (M, V, 3) / ``camera_translation`` (M, 3) may hold all detections of a frame: they are drawn together, one
+    launch sequence per panel (one mesh (V, 3) / (3,) is the reference's call).  ``mesh_filename``: the meshes after the 180
+    degree turn as .obj (``NAME.obj``; ``NAME_<m>.obj`` from the second on) and the x-flipped translations as .npy
+    (renderer_cam.py:74,87-90).  ``save_filename``: the image through Pillow (the reference's cv2.imwrite of the RGB-swapped
+    array stores the same pixels)."""
+    from . import cam_utils
+    if isinstance(image, torch.Tensor):
+        device = device or (image.device if image.device.type == 'cuda' else None)
+        image = image.detach().cpu().numpy()
+    image = group_panel0(image, cam_params)
+    dev = torch.device(device or 'cuda')
+    eng = engine or cam_utils._engine(dev)
+    panel0 = torch.from_numpy(np.ascontiguousarray(image)).to(eng.device)
+    kw = dict(faces=faces, color=mesh_color, engine=eng, cull=_closed(faces))
+    overlay = render_overlay(panel0, vertices, camera_translation, camera_rotation, focal_length, camera_center, **kw)
+    side = render_overlay(panel0, vertices, camera_translation, camera_rotation, focal_length, camera_center, side_view=True, ground_plane=True, **kw)
+    out = torch.cat([panel0, overlay, side], dim=1)
+    if mesh_filename:
+        v = torch.as_tensor(vertices).detach().float().cpu().numpy().reshape(-1, int(torch.as_tensor(vertices).shape[-2]), 3)
+        t = torch.as_tensor(camera_translation).detach().float().cpu().numpy().reshape(-1, 3) * np.array([-1., 1., 1.], np.float32)
+        table = device_faces(faces, eng.device).cpu().numpy()
+        for m in range(v.shape[0]):
+            name = mesh_filename if m == 0 else mesh_filename.replace('.obj', f'_{m}.obj')
+            write_obj(name, v[m] * np.array([1., -1., -1.], np.float32), table)
+            np.save(name.replace('.obj', '.npy'), t[m])
+    if save_filename is not None:
+        from PIL import Image
+        os.makedirs(os.path.dirname(os.path.abspath(save_filename)), exist_ok=True)
+        Image.fromarray(out.cpu().numpy()).save(save_filename)
+    return out
+
+
+def _closed(faces) -> bool:
+    """Cull back faces?  Yes for a caller's table and for the SMPL file's (closed, outward-wound); no for the synthetic body
+    model's triangle soup, whose winding means nothing."""
+    if faces is not None:
+        return True
+    from . import assets
+    assets.faces()
+    return assets._STATE['smpl_path'] is not None

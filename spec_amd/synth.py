@@ -451,6 +451,32 @@ def smpl_model(seed: int = 1003, nv: int = C.NUM_SMPL_VERTS):
     return m
 
 
+_faces_memo = {}
+
+
+def smpl_faces(v_template: np.ndarray, nf: int = 13776) -> np.ndarray:
+    """A deterministic (nf, 3) int32 triangle table for a synthetic body model - SMPL's face count over vertices that form
+    no surface: vertex i with its two nearest neighbours in the template, then with its second and third nearest, in vertex
+    order until ``nf`` triangles exist (every vertex is used, the triangles are small and local; winding is arbitrary, so
+    draw such a model with culling off)."""
+    v = np.asarray(v_template, np.float64)
+    nv = v.shape[0]
+    key = (hash(v.tobytes()), nf)
+    if key in _faces_memo:
+        return _faces_memo[key]
+    k = min(3, nv - 1)
+    nn = np.empty((nv, k), np.int64)
+    for a in range(0, nv, 1024):                       # blocks: the distance matrix of 6890 points need not exist at once
+        d = ((v[a:a + 1024, None, :] - v[None, :, :]) ** 2).sum(-1)
+        d[np.arange(d.shape[0]), np.arange(a, a + d.shape[0])] = np.inf
+        near = np.argpartition(d, k - 1, axis=1)[:, :k]
+        nn[a:a + 1024] = np.take_along_axis(near, np.argsort(np.take_along_axis(d, near, 1), axis=1, kind='stable'), 1)
+    i = np.arange(nv)
+    rounds = [np.stack([i, nn[:, r % k], nn[:, (r + 1) % k]], 1) for r in range(-(-nf // nv))]
+    _faces_memo[key] = np.ascontiguousarray(np.concatenate(rounds)[:nf].astype(np.int32))
+    return _faces_memo[key]
+
+
 def h36m_regressor(seed: int = 1003, nv: int = C.NUM_SMPL_VERTS) -> np.ndarray:
     """A synthetic 17-row joint regressor standing in for ``data/J_regressor_h36m.npy``
     (used by the evaluation metrics, spec/trainer.py:96-99,272-279): rows sum to 1."""

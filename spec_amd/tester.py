@@ -6,8 +6,11 @@ disk (``<out>/camcalib/<image name>.pkl``, ``<out>/spec_results/<stem>.pkl``).
 Differences by design: ``run_camcalib`` runs CamCalib in this process on the GPU instead of spawning
 ``python scripts/camcalib_demo.py`` (tester.py:86-88) - the drop-in ``scripts/camcalib_demo.py`` wraps the same function; the
 crops of ``run_on_image_folder`` are cut on the device (``specmi_crop_normalize``); the person detector (multi-person-tracker /
-YOLOv3, tester.py:73-84) and the OpenGL renderer (:165-200) are outside the path: ``run_detector`` reads boxes from
-``args.detections`` (joblib: list or ``{image name: (n,4) [cx, cy, w, h]}``) and rendering is skipped with a notice."""
+YOLOv3, tester.py:73-84) is outside the path: ``run_detector`` reads boxes from ``args.detections`` (joblib: list or
+``{image name: (n,4) [cx, cy, w, h]}``).  The three-panel pictures (:165-201) are drawn by this project's own rasteriser on the
+device (``spec_amd/render.py``; same geometry and file names, its own declared shading - not pyrender's look) when ``args.no_render``
+is present and false; a frame's detections are drawn together, one launch sequence per panel, and that picture is written under
+each detection's name."""
 from __future__ import annotations
 
 import os
@@ -143,6 +146,34 @@ class SPECTester:
         R[:k], K[:k] = cam_utils.cam_params_from_angles(per_crop([r['pitch'].item() for r in recs]), per_crop([r['roll'].item() for r in recs]),
                                                         per_crop([float(r['f_pix']) for r in recs]), w, h, device=self.device)
 
+    def _render_frame(self, img_fname, rgb, vertices, cam_t, output_path, output_img_folder):
+        """``spec/tester.py:165-201`` for one frame: ``vertices`` (n, V, 3) / ``cam_t`` (n, 3) as the step left them on the device.
+        The render rotation is ``batch_euler2matrix([-pitch, 0, roll])`` = Rx(-pitch) Rz(roll) (:169-171), the focal length the
+        frame's f_pix, the centre (W // 2, H // 2) (:175).  -> the files written."""
+        import joblib
+        from PIL import Image
+        from . import render
+        rec = joblib.load(io_formats.camcalib_result_path(output_path, img_fname))
+        pitch, roll, vfov, f_pix = rec['pitch'].item(), rec['roll'].item(), rec['vfov'].item(), float(rec['f_pix'])
+        cp, sp, cr, sr = np.cos(-pitch), np.sin(-pitch), np.cos(roll), np.sin(roll)
+        rot = np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]]) @ np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]])
+        h, w = rgb.shape[:2]
+        group = render.render_image_group(rgb, cam_t, vertices, rot.astype(np.float32), (f_pix, f_pix), (w // 2, h // 2),
+                                          cam_params=np.array([vfov, pitch, roll, f_pix]), device=self.device)
+        picture = Image.fromarray(group.cpu().numpy())
+        stem, ext = os.path.splitext(os.path.basename(img_fname))
+        os.makedirs(output_img_folder, exist_ok=True)
+        written = []
+        for i in range(vertices.shape[0]):
+            written.append(os.path.join(output_img_folder, f'{stem}_{i:06d}{ext}'))
+            picture.save(written[-1])
+            if getattr(self.args, 'save_obj', False):
+                mesh_folder = os.path.join(output_path, 'meshes', os.path.basename(img_fname).split('.')[0])
+                os.makedirs(mesh_folder, exist_ok=True)
+                render.write_obj(os.path.join(mesh_folder, f'{i:06d}.obj'), vertices[i].cpu().numpy() * np.array([1., -1., -1.], np.float32),
+                                 assets.faces())
+        return written
+
     def run_camcalib(self, image_folder, output_folder):
         return run_camcalib_folder(image_folder, f'{output_folder}/camcalib', ckpt=getattr(self.args, 'camcalib_ckpt', None) or CAMCALIB_CKPT,
                                    model=self._camcalib, device=self.device)
@@ -193,6 +224,10 @@ class SPECTester:
         held = []                     # ragged route: (RGB array, detections) of the frames waiting for this flush
         pending, k, n_done = [], 0, 0
         save = not getattr(self.args, 'no_save', False)
+        render = not getattr(self.args, 'no_render', True)            # absent = no pictures, as before there were any
+        if render and output_img_folder is None:
+            raise ValueError('no_render is false: output_img_folder must name the folder the pictures go to')
+        shown = {}                    # rendering: the decoded frames of this flush by file name
         if save:
             os.makedirs(os.path.join(output_path, 'spec_results'), exist_ok=True)
 
@@ -205,6 +240,10 @@ class SPECTester:
                 held.clear()
             output = self.model(buf['inp_images'][:k], cam_rotmat=R[:k], cam_intrinsics=K[:k], bbox_scale=buf['bbox_scale'][:k],
                                 bbox_center=buf['bbox_center'][:k], img_w=img_w[:k], img_h=img_h[:k])
+            if render:
+                for img_fname, k0, n in pending:
+                    self._render_frame(img_fname, shown.pop(img_fname), output['smpl_vertices'][k0:k0 + n], output['pred_cam_t'][k0:k0 + n],
+                                       output_path, output_img_folder)
             output = {key: v.cpu().numpy() for key, v in output.items()}          # ONE device->host hand-over per batch
             if save:
                 import joblib
@@ -248,11 +287,11 @@ class SPECTester:
                     R[k:k + n] = cam_rotmat
                     K[k:k + n] = cam_intrinsics
                 pending.append((img_fname, k, n))
+                if render:
+                    shown[img_fname] = rgb
                 k += n
                 if per_frame:
                     flush()
-                if not getattr(self.args, 'no_render', True) and n_done == 0:
-                    _log('rendering (pyrender / OpenGL, spec/tester.py:165-200) is outside the hot path: skipped')
                 n_done += 1
             flush()
         return n_done
