@@ -585,6 +585,60 @@ int specmi_regress_joints(specmi_handle* h, const float* vertices, int B, int V,
  * -> out (B,N,3), out[b,n] = R[b] points[b,n]. */
 int specmi_rotate_points(specmi_handle* h, const float* R, const float* points, int B, int N, float* out, void* stream);
 
+/* ---- SPEC's loss modules, forward value ---------------------------------------------------------- */
+
+/* HMRLoss.forward (spec/losses.py:59-141; mode = SPECMI_HMR_LOSS) and HMRCamLoss.forward (:171-271; mode = SPECMI_HMR_CAM_LOSS)
+ * as an evaluation quantity: the value only, no gradient.  All pointers are device pointers, fp32 unless stated.
+ *   prediction (the dict of HMR.forward): pred_pose (B,24,3,3), pred_shape (B,10), pred_cam (B,3), joints3d (B,49,3) =
+ *     smpl_joints3d, joints2d (B,49,2) = smpl_joints2d, vertices (B,V,3) = smpl_vertices;
+ *   ground truth (the batch of spec/dataset/cam_dataset.py): pose (B,72) axis-angle, betas (B,10), pose_conf (B,24), pose_3d
+ *     (B,24,4) = xyz + confidence, keypoints (B,49,3) = xy + confidence - gt['keypoints'] (crop-normalised) in mode 0,
+ *     gt['keypoints_orig'] (pixels) in mode 1 -, gt_vertices (B,V,3) or NULL, has_smpl / has_pose_3d (B) int32 (non-zero =
+ *     annotated); mode 1 only: orig_shape (B,2) = (H, W) of the full image, scale (B) = the bbox scale;
+ *   the eight weights are the constructor arguments of both classes (:27-36, :145-154); w_smpl_part belongs to the part
+ *     segmentation branch, whose criterion the reference never defines (:131, :259), and is not read.
+ * The terms, as the reference computes them:
+ *   smpl_losses (:412-432): criterion = nn.MSELoss() (mean).  Over the Nv images with has_smpl, loss_regr_pose =
+ *     mean(pose_conf over Nv x 24) * MSE(pred_pose, batch_rodrigues(pose)) over Nv x 24 x 3 x 3 - a PRODUCT OF TWO MEANS
+ *     (:427 multiplies the confidences by an already reduced scalar), not a confidence-weighted mean; loss_regr_betas = MSE over
+ *     Nv x 10; both 0 when Nv = 0.  batch_rodrigues is pare.utils.geometry's, i.e. SPIN's form: angle = |theta + 1e-8| (the
+ *     epsilon added to every component), axis = theta / angle, quaternion (cos(angle / 2), sin(angle / 2) * axis) divided by its
+ *     norm, quaternion -> matrix.  It is NOT the smplx Rodrigues that specmi_smpl_native applies to an axis-angle pose.
+ *   projected_keypoint_loss (:274-296): conf = keypoints[..., 2] times w_openpose for joints 0-24 and w_gt for joints 25-48;
+ *     element = conf * (joints2d - keypoints_xy)^2.  Mode 0: mean over B x 49 x 2.  Mode 1: both sides are first mapped to
+ *     2 * (xy / (W, H)) - 1 (:188-195; `orig_shape.rot90().T` turns (H, W) into (W, H)), each element is then multiplied by
+ *     (W, H) / (scale * 200) on its axis (:222-223), then the mean.  The prediction is only read (the reference overwrites
+ *     pred['smpl_joints2d'] in place at :191).
+ *   keypoint_3d_loss (:326-348): joints3d[:, 25:] against pose_3d over the Np images with has_pose_3d, each side minus its own
+ *     pelvis = (joint 2 + joint 3) / 2; mean over Np x 24 x 3 of conf * squared error; 0 when Np = 0.
+ *   shape_loss (:375-387): nn.L1Loss() = mean |vertices - gt_vertices| over Nv x V x 3; 0 when Nv = 0 or gt_vertices is NULL.
+ *   loss_cam (:119, :247) = mean over B of exp(-10 * pred_cam[:, 0])^2.
+ *   weights (:114-118): shape * w_shape; keypoints and keypoints_3d * w_keypoint; regr_pose * w_pose; regr_betas * w_beta;
+ *     total = w_loss * (keypoints + keypoints_3d + regr_pose + regr_betas + shape + cam), added in that order (:135-137).
+ * Outputs:
+ *   terms (6,B), required: the UNNORMALISED per-image sums, computed for every image whatever its masks say.  Rows: 0 keypoints
+ *     (49 x 2 elements, mode 1 already rescaled), 1 keypoints_3d (24 x 3), 2 and 3 the pose term's two factors - 2 the squared
+ *     error of the 24 x 9 matrix elements, 3 the sum of the 24 pose confidences -, 4 betas (10), 5 vertices (V x 3; 0 without
+ *     gt_vertices).  loss_cam is a function of one float per image and has no row.
+ *   counts (2 int32, may be NULL): Nv, Np.
+ *   means (7, may be NULL): loss_keypoints, loss_keypoints_3d, loss_regr_pose, loss_regr_betas, loss_shape, loss_cam (weighted,
+ *     the reference's loss_dict order), then total_loss.
+ * One launch reduces every image in a workgroup of its own (the vertices as 16-byte vectors counted from the image's first float,
+ * wavefront shuffles, then LDS, no atomics), one small launch folds the B rows in an order that depends on B alone.  A per-image
+ * value never depends on the other rows; the same inputs give the same bits in every run and at every batch position.  Nothing is
+ * allocated: the call may be captured into a graph.  Works on a handle of any model kind, committed or not.
+ * Refused (SPECMI_ERR_ARG), launching nothing, the message naming the argument: B <= 0, V <= 0 (or V * 3 past 31 bits), a mode
+ * outside {0, 1}, a NULL required pointer (gt_vertices may be NULL only when w_shape == 0; counts and means are optional),
+ * mode 1 without orig_shape or scale. */
+#define SPECMI_HMR_LOSS 0
+#define SPECMI_HMR_CAM_LOSS 1
+int specmi_hmr_loss(specmi_handle* h, int mode, const float* pred_pose, const float* pred_shape, const float* pred_cam,
+                    const float* joints3d, const float* joints2d, const float* vertices, const float* pose, const float* betas,
+                    const float* pose_conf, const float* pose_3d, const float* keypoints, const float* gt_vertices,
+                    const int32_t* has_smpl, const int32_t* has_pose_3d, const float* orig_shape, const float* scale, int B, int V,
+                    float w_shape, float w_keypoint, float w_pose, float w_smpl_part, float w_beta, float w_openpose, float w_gt,
+                    float w_loss, float* terms, int32_t* counts, float* means, void* stream);
+
 /* Which execution plan a trunk forward of (B, 3, H, W) takes under the handle's current options ("plan" and its thresholds):
  * *mode = 0 throughput, 1 latency, 2 single; pair != 0: as specmi_trunk_forward_pair decides (the FIRST handle's options).  Callers
  * that describe or log what ran ask here instead of re-deriving the rule (bench.py, SpecPipeline). */

@@ -12,6 +12,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only pano_views         # the panorama view extractor -> profiles/pano_views_aux.json
     python scripts/bench_aux.py --only ragged_crops       # crops from frames of different sizes, per-frame route against the ragged one -> profiles/ragged_crops_aux.json
     python scripts/bench_aux.py --only render             # mesh overlay + side view, 8 meshes on a 1080p frame, both raster launch shapes -> profiles/render_aux.json
+    python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
     python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
 import argparse
@@ -352,9 +353,26 @@ def render_section(eng, a):
                               'vertices_faces': round((v.size * 4 * 3 + v.shape[0] * f.size * 4) / 1e6, 3)}}
 
 
+def hmr_loss_section(eng, a, add):
+    """``specmi_hmr_loss`` in HMRCamLoss mode with the per-vertex L1 term on: 2 * B * 6890 * 3 floats per call, at the batch of the
+    evaluation config (64) and at ``--batch``."""
+    rng = np.random.default_rng(0)
+    f = lambda *shape: torch.from_numpy(rng.standard_normal(shape).astype(np.float32)).to(eng.device)
+    for B in sorted({64, a.batch}):
+        pred = {'pred_pose': f(B, 24, 3, 3), 'pred_shape': f(B, 10), 'pred_cam': f(B, 3).abs() + 0.5, 'smpl_joints3d': f(B, 49, 3),
+                'smpl_joints2d': f(B, 49, 2) * 100, 'smpl_vertices': f(B, 6890, 3)}
+        gt = {'pose': f(B, 72) * 0.3, 'betas': f(B, 10), 'pose_conf': torch.ones(B, 24, device=eng.device), 'pose_3d': f(B, 24, 4),
+              'keypoints_orig': f(B, 49, 3).abs() * 100, 'vertices': f(B, 6890, 3), 'has_smpl': torch.ones(B, dtype=torch.int32, device=eng.device),
+              'has_pose_3d': torch.ones(B, dtype=torch.int32, device=eng.device), 'orig_shape': torch.full((B, 2), 480., device=eng.device),
+              'scale': torch.ones(B, device=eng.device)}
+        out = eng.hmr_loss(1, pred, gt, [1., 5., 1., 1., 0.001, 0., 1., 60.])
+        add('Engine.hmr_loss (HMRCamLoss, shape_loss_weight 1)', f'{B} images, 6890 vertices: {2 * B * 6890 * 3 * 4 / 1e6:.1f} MB of vertices',
+            timed(eng, lambda: eng.hmr_loss(1, pred, gt, [1., 5., 1., 1., 0.001, 0., 1., 60.], out=out), a.iters), ('images_per_s', B))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render'], default=None, help='run one section only')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -382,6 +400,11 @@ def main():
             if per_unit:
                 row[per_unit[0]] = round(per_unit[1] / (ms * 1e-3), 1)
             table.append(row)
+
+    if a.only == 'hmr_loss':
+        from spec_amd import _lib
+        hmr_loss_section(eng, a, add)
+        return finish(a, table, {'source_hash': _lib.source_hash()})
 
     if a.only == 'camcalib_eval':
         from spec_amd import _lib
@@ -470,6 +493,7 @@ def main():
     add('cam_utils bins (arg-max + soft-argmax)', f'{3 * B} rows x 256 bins',
         timed(eng, lambda: eng.camcalib_bins(logits, argmax=True, soft=True), a.iters), ('rows_per_s', 3 * B))
 
+    hmr_loss_section(eng, a, add)
     cmp_ = camcalib_eval_section(eng, a, add, g)
     finish(a, table, {'pad_batch_vs_per_frame_composition': cmp_})
 

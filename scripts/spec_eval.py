@@ -75,6 +75,8 @@ def main():
     ap.add_argument('--batch_size', type=int, default=64)
     ap.add_argument('--log_dir', type=str, default='logs/eval')
     ap.add_argument('--dataset_name', type=str, default='spec-syn')
+    ap.add_argument('--loss', action='store_true', help="also report the mean of HMRCamLoss's loss dict (the training objective of "
+                                                        'spec/losses.py, forward value only) over each dataset; off by default')
     ap.add_argument('--report', type=str, default=None, metavar='eval.json',
                     help='write the scores and the delta against the reference README table (README.md:155-159) as JSON; the exit '
                          'code is 3 when |delta W-MPJPE| > 0.1 mm on a dataset the table lists (use on the real assets)')
@@ -97,7 +99,7 @@ def main():
         ckpt = 'data/spec/checkpoints/spec_checkpoint.ckpt'          # scripts/spec_demo.py:31
     if not os.path.isdir(os.path.join(root, 'data')):
         sys.exit(f'{os.path.join(root, "data")} not found: download the reference data (README.md:127-147) or use --standin DIR')
-    results = evaluation.run_evaluation(hp, data_root=root, ckpt=ckpt, limit=args.limit)
+    results = evaluation.run_evaluation(hp, data_root=root, ckpt=ckpt, limit=args.limit, loss=args.loss)
     if args.report:
         import json
         rep = {'config': cfg, 'checkpoint': ckpt or hp['TRAINING']['PRETRAINED_LIT'], 'data_root': os.path.abspath(root),
@@ -107,6 +109,8 @@ def main():
         for name, res in results.items():
             m, ref = res['mean'], evaluation.README_TABLE.get(name)
             entry = {'mean': {k: float(v) for k, v in m.items()}, 'readme': None, 'delta_mm': res.get('readme_delta_mm'), 'within_target': None}
+            if 'loss' in res:
+                entry['loss'] = res['loss']
             if ref:
                 entry['readme'] = {'wmpjpe': ref[0], 'pampjpe': ref[1], 'wpve': ref[2]}
                 entry['within_target'] = abs(res['readme_delta_mm']['wmpjpe']) <= 0.1

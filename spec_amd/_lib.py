@@ -33,6 +33,10 @@ OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_MISSING = 0, 1, 2, 3, 4
 PRECISION_FP32, PRECISION_FP16 = 0, 1       # SPECMI_PRECISION_* (include/specmi.h)
 MODEL_CAMCALIB, MODEL_HMR, MODEL_SMPL = 0, 1, 2
 RENDER_SIDE_VIEW, RENDER_GROUND_PLANE, RENDER_CULL, RENDER_THREAD_PER_TRIANGLE = 1, 2, 4, 8     # SPECMI_RENDER_* (include/specmi.h)
+HMR_LOSS, HMR_CAM_LOSS = 0, 1                 # SPECMI_HMR_LOSS / SPECMI_HMR_CAM_LOSS (include/specmi.h)
+# the ground-truth tensors of specmi_hmr_loss in the order of its prototype, per-image shapes (None = (V, 3)); int32 where named has_*
+HMR_LOSS_GT = (('pose', (72,)), ('betas', (10,)), ('pose_conf', (24,)), ('pose_3d', (24, 4)), ('keypoints', (49, 3)), ('vertices', None),
+               ('has_smpl', ()), ('has_pose_3d', ()), ('orig_shape', (2,)), ('scale', ()))
 LOSS_TYPES = {'ce': 0, 'kl': 1, 'softargmax_l2': 2, 'softargmax_biased_l2': 3}     # SPECMI_LOSS_* (include/specmi.h)
 
 c_float_p = C.POINTER(C.c_float)
@@ -170,6 +174,9 @@ PROTOTYPES = {
                                      C.c_void_p, C.c_void_p]),
     'specmi_regress_joints': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                         C.c_void_p]),
+    # (h, mode, 6 prediction tensors, 6 ground-truth tensors, has_smpl, has_pose_3d, orig_shape, scale, B, V, 8 weights, terms, counts, means, stream)
+    'specmi_hmr_loss': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 16 + [C.c_int, C.c_int] + [C.c_float] * 8 +
+                        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'specmi_rotate_points': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'specmi_trunk_plan': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     'specmi_sync_status': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),

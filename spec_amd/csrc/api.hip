@@ -1783,6 +1783,41 @@ int specmi_regress_joints(specmi_handle* h, const float* vertices, int B, int V,
     return SPECMI_OK;
 }
 
+int specmi_hmr_loss(specmi_handle* h, int mode, const float* pred_pose, const float* pred_shape, const float* pred_cam,
+                    const float* joints3d, const float* joints2d, const float* vertices, const float* pose, const float* betas,
+                    const float* pose_conf, const float* pose_3d, const float* keypoints, const float* gt_vertices,
+                    const int32_t* has_smpl, const int32_t* has_pose_3d, const float* orig_shape, const float* scale, int B, int V,
+                    float w_shape, float w_keypoint, float w_pose, float w_smpl_part, float w_beta, float w_openpose, float w_gt,
+                    float w_loss, float* terms, int32_t* counts, float* means, void* stream) {
+    ENTER(h);
+    (void)w_smpl_part;   // the part-segmentation branch: its criterion is never defined in the reference (spec/losses.py:131,259)
+    if (B <= 0) return fail(h, SPECMI_ERR_ARG, "hmr_loss: B = %d must be positive", B);
+    if (V <= 0 || V > 0x7fffffff / 3) return fail(h, SPECMI_ERR_ARG, "hmr_loss: V = %d must be positive with V * 3 below 2^31", V);
+    if (mode != SPECMI_HMR_LOSS && mode != SPECMI_HMR_CAM_LOSS)
+        return fail(h, SPECMI_ERR_ARG, "hmr_loss: mode = %d is not defined (0 = HMRLoss, 1 = HMRCamLoss)", mode);
+    const struct { const void* p; const char* name; } required[] = {
+        {pred_pose, "pred_pose"}, {pred_shape, "pred_shape"}, {pred_cam, "pred_cam"}, {joints3d, "joints3d"}, {joints2d, "joints2d"},
+        {vertices, "vertices"}, {pose, "pose"}, {betas, "betas"}, {pose_conf, "pose_conf"}, {pose_3d, "pose_3d"},
+        {keypoints, "keypoints"}, {has_smpl, "has_smpl"}, {has_pose_3d, "has_pose_3d"}, {terms, "terms"}};
+    for (const auto& r : required)
+        if (!r.p) return fail(h, SPECMI_ERR_ARG, "hmr_loss: %s is NULL", r.name);
+    if (!gt_vertices && w_shape != 0.f)
+        return fail(h, SPECMI_ERR_ARG, "hmr_loss: gt_vertices is NULL but shape_loss_weight = %g (NULL is accepted only with weight 0)", (double)w_shape);
+    if (mode == SPECMI_HMR_CAM_LOSS && !orig_shape) return fail(h, SPECMI_ERR_ARG, "hmr_loss: orig_shape is NULL (HMRCamLoss needs it)");
+    if (mode == SPECMI_HMR_CAM_LOSS && !scale) return fail(h, SPECMI_ERR_ARG, "hmr_loss: scale is NULL (HMRCamLoss needs it)");
+    HmrLossArgs a;
+    a.mode = mode; a.B = B; a.V = V;
+    a.pred_pose = pred_pose; a.pred_shape = pred_shape; a.pred_cam = pred_cam; a.joints3d = joints3d; a.joints2d = joints2d;
+    a.vertices = vertices; a.pose = pose; a.betas = betas; a.pose_conf = pose_conf; a.pose_3d = pose_3d; a.keypoints = keypoints;
+    a.gt_vertices = gt_vertices; a.has_smpl = has_smpl; a.has_pose_3d = has_pose_3d; a.orig_shape = orig_shape; a.scale = scale;
+    a.w_shape = w_shape; a.w_keypoint = w_keypoint; a.w_pose = w_pose; a.w_beta = w_beta; a.w_openpose = w_openpose; a.w_gt = w_gt;
+    a.w_loss = w_loss;
+    a.terms = terms; a.counts = counts; a.means = means;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "loss.hmr"};
+    LAUNCHCHK(h, launch_hmr_loss(a, ctx), "hmr_loss");
+    return SPECMI_OK;
+}
+
 int specmi_rotate_points(specmi_handle* h, const float* R, const float* points, int B, int N, float* out, void* stream) {
     ENTER(h);
     if (!R || !points || !out || B <= 0 || N <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");

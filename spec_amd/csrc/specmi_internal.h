@@ -374,6 +374,22 @@ int launch_regress_joints(const float* verts, int B, int V, const float* Jr, int
 int launch_rotate_points(const float* R, const float* x, int B, int N, float* out, const LaunchCtx& ctx);
 
 // ----------------------------------------------------------------------------------------
+// SPEC's loss modules, forward value  (loss.hip)
+// ----------------------------------------------------------------------------------------
+// HMRLoss (mode 0) / HMRCamLoss (mode 1) of spec/losses.py; shapes, rows of `terms` and the order of `means`: include/specmi.h,
+// specmi_hmr_loss.  gt_vertices, orig_shape and scale may be null where the header says so; counts and means may be null.
+struct HmrLossArgs {
+    int mode, B, V;
+    const float *pred_pose, *pred_shape, *pred_cam, *joints3d, *joints2d, *vertices;
+    const float *pose, *betas, *pose_conf, *pose_3d, *keypoints, *gt_vertices;
+    const int *has_smpl, *has_pose_3d;
+    const float *orig_shape, *scale;
+    float w_shape, w_keypoint, w_pose, w_beta, w_openpose, w_gt, w_loss;
+    float* terms; int* counts; float* means;
+};
+int launch_hmr_loss(const HmrLossArgs& a, const LaunchCtx& ctx);
+
+// ----------------------------------------------------------------------------------------
 // crop + normalise  (preprocess.hip)
 // ----------------------------------------------------------------------------------------
 // Every producer: f16 = false -> `out` is the fp32 NCHW image; f16 = true -> `out` is NHWC8 fp16 (include/specmi.h), 16-byte aligned

@@ -46,6 +46,18 @@ def _record_shapes(num_verts: int):
     return {k: shp for k, _, shp in record_layout(num_verts)[0]}
 
 
+# specmi_hmr_loss (include/specmi.h), stated once: the tensors in the order of the C prototype with their per-image shapes
+# (None = (num_verts, 3)), the constructor weights in the reference's order (spec/losses.py:27-36) and the keys of its loss_dict.
+HMR_LOSS_INPUTS = {     # the prediction side is six entries of the packed record; the ground-truth side is stated beside the prototype
+    'pred': tuple((k, dict(PACKED_KEYS)[k]) for k in ('pred_pose', 'pred_shape', 'pred_cam', 'smpl_joints3d', 'smpl_joints2d', 'smpl_vertices')),
+    'gt': _lib.HMR_LOSS_GT,
+}
+HMR_LOSS_WEIGHTS = ('shape_loss_weight', 'keypoint_loss_weight', 'pose_loss_weight', 'smpl_part_loss_weight', 'beta_loss_weight',
+                    'openpose_train_weight', 'gt_train_weight', 'loss_weight')
+HMR_LOSS_KEYS = ('loss/loss_keypoints', 'loss/loss_keypoints_3d', 'loss/loss_regr_pose', 'loss/loss_regr_betas', 'loss/loss_shape',
+                 'loss/loss_cam', 'loss/total_loss')
+
+
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -432,6 +444,46 @@ class Engine:
                 self.h, _ptr(lv), _ptr(lp), _ptr(lr), B, nb, _lib.LOSS_TYPES[loss_type], _ptr(tg[0]), _ptr(tg[1]), _ptr(tg[2]),
                 _ptr(gt[0]), _ptr(gt[1]), _ptr(gt[2]), float(weights[0]), float(weights[1]), float(weights[2]), _ptr(res['loss_term']),
                 _ptr(res['argmax']), _ptr(res['soft']), _ptr(res['angle']), _ptr(res['err']), _ptr(res['means']), self._stream()))
+        return res
+
+    def hmr_loss(self, mode, pred, gt, weights, out=None):
+        """``specmi_hmr_loss``: the forward value of the reference's HMRLoss (``mode`` 0) / HMRCamLoss (``mode`` 1).  ``pred``
+        and ``gt`` map the names of ``HMR_LOSS_INPUTS`` to tensors or arrays ((B, ...) each; gt['vertices'] may be None when the
+        shape weight is 0; 'orig_shape' as (H, W) and 'scale' are read in mode 1 only), ``weights`` the eight constructor
+        arguments in ``HMR_LOSS_WEIGHTS`` order.  -> dict(terms (6, B), counts (2,) int32 = Nv, Np, means (7,) in
+        ``HMR_LOSS_KEYS`` order), device tensors; ``out`` supplies them (a captured graph replays into the same three)."""
+        if mode not in (_lib.HMR_LOSS, _lib.HMR_CAM_LOSS):
+            raise ValueError(f'mode must be 0 (HMRLoss) or 1 (HMRCamLoss), got {mode!r}')
+        if len(weights) != len(HMR_LOSS_WEIGHTS):
+            raise ValueError(f'weights: {len(HMR_LOSS_WEIGHTS)} values in the order {HMR_LOSS_WEIGHTS}')
+        verts = _dev_f32(pred['smpl_vertices'], self.device)
+        if verts.dim() != 3 or verts.shape[2] != 3 or min(verts.shape[:2]) < 1:
+            raise ValueError(f'smpl_vertices must be (B, V, 3) with B, V >= 1, got {tuple(verts.shape)}')
+        B, V = int(verts.shape[0]), int(verts.shape[1])
+        args = [verts if k == 'smpl_vertices' else _dev_f32(pred[k], self.device, (B,) + shp) for k, shp in HMR_LOSS_INPUTS['pred']]
+        for k, shp in HMR_LOSS_INPUTS['gt']:
+            shp = (B,) + ((V, 3) if shp is None else shp)
+            if k in ('has_smpl', 'has_pose_3d'):      # .bool() of the reference: non-zero = annotated
+                m = gt[k] if isinstance(gt[k], torch.Tensor) else torch.as_tensor(np.asarray(gt[k]))
+                m = (m.to(self.device) != 0).to(torch.int32).contiguous()
+                if tuple(m.shape) != shp:
+                    raise ValueError(f'{k}: expected shape {shp}, got {tuple(m.shape)}')
+                args.append(m)
+            elif k == 'vertices':
+                v = gt.get('vertices')
+                if v is None and float(weights[0]) != 0.0:
+                    raise ValueError("gt['vertices'] is needed when shape_loss_weight != 0 (spec_amd.losses.gt_vertices makes them)")
+                args.append(_dev_f32(v, self.device, shp))
+            elif k in ('orig_shape', 'scale'):
+                args.append(_dev_f32(gt[k], self.device, shp) if mode == _lib.HMR_CAM_LOSS else None)
+            else:
+                args.append(_dev_f32(gt['keypoints_orig' if (k == 'keypoints' and mode == _lib.HMR_CAM_LOSS) else k], self.device, shp))
+        res = out if out is not None else {'terms': self._empty(6, B), 'counts': self._empty(2, dtype=torch.int32), 'means': self._empty(len(HMR_LOSS_KEYS))}
+        for k, shp, dt in (('terms', (6, B), torch.float32), ('counts', (2,), torch.int32), ('means', (len(HMR_LOSS_KEYS),), torch.float32)):
+            if tuple(res[k].shape) != shp or res[k].dtype != dt or not res[k].is_contiguous() or res[k].device != self.device:
+                raise ValueError(f'out[{k!r}] must be a contiguous {shp} {dt} tensor on the engine device')
+        _lib.check(self.h, self.lib.specmi_hmr_loss(self.h, int(mode), *(_ptr(t) for t in args), B, V, *(float(w) for w in weights),
+                                                    _ptr(res['terms']), _ptr(res['counts']), _ptr(res['means']), self._stream()))
         return res
 
     def resize_normalize_ragged(self, slab, offsets, geom, out=None, dtype=torch.float32):

@@ -103,6 +103,29 @@ class EvalDataset:
     def __len__(self):
         return self.n
 
+    def loss_gt(self, idx, shapes, device) -> Dict[str, torch.Tensor]:
+        """The ground-truth half of ``HMRCamLoss.forward`` for the samples ``idx`` (``shapes``: their (H, W)), without
+        ``vertices``.  Fields the annotation file lacks are filled as the reference dataset fills them
+        (spec/dataset/cam_dataset.py:93-116,148-157,353-359,386-413,480-486): ``pose_0yaw_inverseyz`` before ``pose``; ``has_smpl``
+        = 1 when the file has pose and shape but no such key, 0 (with zero pose and betas) when it has neither; ``pose_conf`` = 1;
+        ``pose_3d`` = ``S`` with ``has_pose_3d`` = 1, else zeros with 0; ``part`` / ``openpose`` keypoints, zeros when missing."""
+        d, n = self.data, len(idx)
+        f = lambda a, dt=torch.float32: torch.as_tensor(np.ascontiguousarray(a)).to(device=device, dtype=dt)
+        pose_key = 'pose_0yaw_inverseyz' if 'pose_0yaw_inverseyz' in d else 'pose'
+        if pose_key in d and 'shape' in d:
+            has_smpl = np.asarray(d['has_smpl'][idx]) if 'has_smpl' in d else np.ones(n)
+            keep = (has_smpl != 0)[:, None]
+            pose, betas = np.where(keep, d[pose_key][idx], 0.0), np.where(keep, d['shape'][idx], 0.0)
+        else:
+            has_smpl, pose, betas = np.zeros(n), np.zeros((n, 72)), np.zeros((n, 10))
+        kp = np.concatenate([d['openpose'][idx] if 'openpose' in d else np.zeros((n, 25, 3)),
+                             d['part'][idx] if 'part' in d else np.zeros((n, 24, 3))], axis=1)
+        return {'pose': f(pose), 'betas': f(betas), 'pose_conf': torch.ones(n, 24, device=device),
+                'pose_3d': f(d['S'][idx]) if 'S' in d else torch.zeros(n, 24, 4, device=device),
+                'keypoints_orig': f(kp), 'has_smpl': f(has_smpl != 0, torch.int32),
+                'has_pose_3d': torch.full((n,), int('S' in d), device=device, dtype=torch.int32),
+                'scale': f(d['scale'][idx]), 'orig_shape': shapes if isinstance(shapes, torch.Tensor) else f(shapes)}
+
     def batch(self, idx, device, img_res=224, use_gt_cam=False, dtype=torch.float32) -> Dict[str, torch.Tensor]:
         """``dtype``: what the crops are stored as (``spec_amd.preprocess``: fp32 (n,3,S,S), or NHWC8 fp16 for an fp16 model)."""
         d = self.data
@@ -138,10 +161,24 @@ class EvalDataset:
                 'imgname': paths}
 
 
+def loss_module(hparams: dict):
+    """``HMRCamLoss`` as ``SPECTrainer.__init__`` builds it (spec/trainer.py:57-66): the ``HMR.*_WEIGHT`` keys of the config
+    where it has them, the constructor's defaults (= the defaults of spec/config.py:155-163) elsewhere."""
+    from .losses import HMRCamLoss
+    hm = hparams.get('HMR') or {}
+    names = {'shape_loss_weight': 'SHAPE_LOSS_WEIGHT', 'keypoint_loss_weight': 'KEYPOINT_LOSS_WEIGHT', 'pose_loss_weight': 'POSE_LOSS_WEIGHT',
+             'beta_loss_weight': 'BETA_LOSS_WEIGHT', 'openpose_train_weight': 'OPENPOSE_TRAIN_WEIGHT', 'gt_train_weight': 'GT_TRAIN_WEIGHT',
+             'loss_weight': 'LOSS_WEIGHT', 'smpl_part_loss_weight': 'SMPL_PART_LOSS_WEIGHT'}
+    return HMRCamLoss(**{k: hm[v] for k, v in names.items() if v in hm})
+
+
 @torch.no_grad()
 def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = None, log=print, limit: Optional[int] = None,
-                   device='cuda') -> Dict[str, dict]:
-    """Test + compute_error for every dataset of ``DATASET.VAL_DS``; returns {dataset: compute_error result}."""
+                   device='cuda', loss: bool = False) -> Dict[str, dict]:
+    """Test + compute_error for every dataset of ``DATASET.VAL_DS``; returns {dataset: compute_error result}.  ``loss``: every
+    batch also goes through ``HMRCamLoss`` (the objective the checkpoint was trained under, spec/trainer.py:141-168, with the
+    ground-truth vertices of the body model); the mean of each key over the run's images (a batch's dict weighted by its size) is
+    logged after the error lines and returned under ``'loss'``.  Off by default: the log and the files are then unchanged."""
     from .modules import HMR
     dev = torch.device(device)
     if hparams.get('METHOD') != 'hmr_cam':
@@ -173,12 +210,18 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         ds = EvalDataset(name, data_root)
         n = len(ds) if limit is None else min(limit, len(ds))
         dump = io_formats.EvalDump()
+        loss_fn, loss_sum = (loss_module(hparams), None) if loss else (None, None)
         for b0 in range(0, n, bs):
             idx = np.arange(b0, min(n, b0 + bs))
             b = ds.batch(idx, dev, hparams['DATASET']['IMG_RES'], bool(hparams['TESTING']['USE_GT_CAM']), dtype=flow_image_dtype(hm))
             # positional call of spec/trainer.py:139
             pred = hm(b['img'], b['cam_rotmat'], b['cam_int'], b['scale'], b['center'], b['img_w'], b['img_h'])
             dump.add(pred, imgnames=b['imgname'], dataset_name=name)
+            if loss_fn is not None:
+                gt = ds.loss_gt(idx, torch.stack([b['img_h'], b['img_w']], 1), dev)
+                gt['vertices'] = body.native(gt['pose'], gt['betas'], vertices=True, joints24=False)[0]      # spec/trainer.py:149-155,166
+                means = torch.stack(list(loss_fn(pred, gt)[1].values())).double() * len(idx)
+                loss_sum = means if loss_sum is None else loss_sum + means
         path = dump.write(log_dir, name)
         log(f'wrote {path}')
         if n != len(ds):                            # a truncated run scores the truncated annotations
@@ -202,6 +245,11 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
                 f'(target |delta W-MPJPE| <= 0.1 mm: {"met" if abs(d[0]) <= 0.1 else "NOT met"})')
             res['readme_delta_mm'] = {'wmpjpe': d[0], 'pampjpe': d[1], 'wpve': d[2]}
         res['precision'] = precision
+        if loss_fn is not None:
+            from .engine import HMR_LOSS_KEYS
+            res['loss'] = dict(zip(HMR_LOSS_KEYS, (loss_sum / n).tolist()))
+            for k, v in res['loss'].items():
+                log(f'{k}: {v:.6g}')
         results[name] = res
     return results
 

@@ -1,0 +1,116 @@
+"""The forward value of the reference's two loss modules on the device (``spec/losses.py``: ``HMRLoss`` :26-141,
+``HMRCamLoss`` :144-271) - the objective a checkpoint was trained under, as an evaluation quantity.  No gradient: training
+(backward, optimiser, datasets, augmentation) is out of scope.
+
+Everything numeric runs in ``specmi_hmr_loss`` (spec_amd/csrc/loss.hip; the quirks of the reference it restates are listed at
+its declaration in include/specmi.h): one launch reduces every image, one folds the batch.
+
+Stated deviations from the reference:
+
+* ``pred['smpl_joints2d']`` is NOT overwritten in place (``HMRCamLoss`` normalises it in place at :191; here ``pred`` is only read).
+* ``estimate_var=True`` raises ``NotImplementedError``: the reference's branch cannot run - ``smpl_losses_uncertainty`` (:390-397)
+  is called with ``gt_pose_conf`` in the position of its ``criterion`` parameter (:79-87) - and the uncertainty criterion it names is an
+  un-vendored pare class.
+* a ``pred_segm_rgb`` key in ``pred`` raises ``NotImplementedError``: ``self.criterion_part`` (:131, :259) is never defined in
+  the reference.
+"""
+from __future__ import annotations
+
+import threading
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .cam_utils import _engine
+from .engine import HMR_LOSS_KEYS, HMR_LOSS_WEIGHTS
+
+_tls = threading.local()
+
+
+@torch.no_grad()
+def gt_vertices(pose, betas, body_model=None):
+    """What ``SPECTrainer.training_step`` puts in ``gt['vertices']`` (spec/trainer.py:149-155,166): the vertices of
+    ``self.smpl(betas=gt_betas, body_pose=gt_pose[:, 3:], global_orient=gt_pose[:, :3])`` for (B, 72) axis-angle poses, through
+    ``specmi_smpl_native(pose_is_axis_angle=1)``.  ``body_model``: a ``spec_amd.metrics.BodyModel`` (default: one per thread
+    and device on the assets of ``spec_amd.assets``)."""
+    if body_model is None:
+        from . import assets
+        from .metrics import BodyModel
+        dev = pose.device if isinstance(pose, torch.Tensor) and pose.device.type == 'cuda' else torch.device('cuda', torch.cuda.current_device())
+        cache = getattr(_tls, 'bodies', None)
+        if cache is None:
+            cache = _tls.bodies = {}
+        model = assets.smpl_model()
+        if dev not in cache or cache[dev][0] is not model:      # the entry holds the asset dict it was built from: `is` cannot alias
+            cache[dev] = (model, BodyModel(model, device=dev))
+        body_model = cache[dev][1]
+    return body_model.native(pose, betas, vertices=True, joints24=False)[0]
+
+
+class _LossBase(nn.Module):
+    _mode = None
+
+    def _set_weights(self, kw):
+        for name in HMR_LOSS_WEIGHTS:
+            setattr(self, name, kw[name])
+
+    @torch.no_grad()
+    def forward(self, pred, gt):
+        """-> (loss, loss_dict): the seven keys of the reference in its order, 0-dim device tensors; ``loss`` is
+        ``loss_dict['loss/total_loss']``.  ``gt['vertices']`` is used when present (``gt_vertices`` makes it) and may be
+        missing while ``shape_loss_weight`` is 0."""
+        if 'pred_segm_rgb' in pred:
+            raise NotImplementedError("'pred_segm_rgb': the part-segmentation term calls self.criterion_part, which the reference never "
+                                      'defines (spec/losses.py:131,259)')
+        v = pred['smpl_vertices']
+        if not isinstance(v, torch.Tensor) or v.device.type != 'cuda':
+            raise RuntimeError('spec_amd.losses needs device tensors (no CPU path)')
+        res = _engine(v.device).hmr_loss(self._mode, pred, gt, [getattr(self, n) for n in HMR_LOSS_WEIGHTS])
+        loss_dict = dict(zip(HMR_LOSS_KEYS, res['means'].unbind(0)))
+        return loss_dict['loss/total_loss'], loss_dict
+
+
+class HMRLoss(_LossBase):
+    """spec/losses.py:26-141; ``gt['keypoints']`` is the crop-normalised annotation."""
+    _mode = _lib.HMR_LOSS
+
+    def __init__(
+            self,
+            shape_loss_weight=0,
+            keypoint_loss_weight=5.,
+            pose_loss_weight=1.,
+            smpl_part_loss_weight=1.,
+            beta_loss_weight=0.001,
+            openpose_train_weight=0.,
+            gt_train_weight=1.,
+            loss_weight=60.,
+            estimate_var=False,
+            uncertainty_loss='MultivariateGaussianNegativeLogLikelihood',
+    ):
+        super().__init__()
+        if estimate_var:
+            raise NotImplementedError(
+                'estimate_var=True: the branch cannot run in the reference - smpl_losses_uncertainty receives gt_pose_conf in its '
+                f'criterion slot (spec/losses.py:79-87,390-397) - and its criterion {uncertainty_loss!r} is an un-vendored pare class')
+        self.estimate_var = estimate_var
+        self._set_weights(locals())
+
+
+class HMRCamLoss(_LossBase):
+    """spec/losses.py:144-271; reads ``gt['keypoints_orig']`` (pixels), ``gt['orig_shape']`` (H, W) and ``gt['scale']``."""
+    _mode = _lib.HMR_CAM_LOSS
+
+    def __init__(
+            self,
+            shape_loss_weight=0,
+            keypoint_loss_weight=5.,
+            pose_loss_weight=1.,
+            smpl_part_loss_weight=1.,
+            beta_loss_weight=0.001,
+            openpose_train_weight=0.,
+            gt_train_weight=1.,
+            loss_weight=60.,
+    ):
+        super().__init__()
+        self._set_weights(locals())
