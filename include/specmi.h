@@ -560,6 +560,47 @@ int specmi_render_meshes(specmi_handle* h, const float* vertices, int M, int V, 
                          const float* rgb, int flags, uint8_t* out_rgb_hwc, int32_t* id_map, float* depth, void* screen,
                          void* stream);
 
+/* MANY VIEWS IN ONE CALL: the pictures of a flush of frames of DIFFERENT sizes - replaces two specmi_render_meshes calls, one
+ * upload, one concatenation and one download per frame (the loop of spec/tester.py:165-201).  A VIEW is what one
+ * specmi_render_meshes call draws: one camera, one output rectangle, a contiguous range of the call's meshes.  DEVICE pointers:
+ * vertices (Mtot,V,3) fp32, cam_t (Mtot,3) fp32, faces (F,3) int32 - one face table and one V for the whole call.  HOST: rgb, 3
+ * floats in [0, 1] (clamped).  The frames lie in one uint8 device slab of in_slab_bytes (the slab and offsets convention of
+ * specmi_crop_normalize_ragged: what spec_amd.preprocess.pack_frames builds is valid input; in_slab may be NULL when no view
+ * names a frame), the outputs go into one uint8 device slab of out_slab_bytes; the two must not overlap.
+ * THE VIEW RECORD, three HOST arrays with one row per view:
+ *   view_geom    (nviews x 5 int32):  H, W, mesh0, count, flags (SPECMI_RENDER_* above)
+ *   view_offsets (nviews x 4 int64):  in_offset (-1 = no frame, legal only with SIDE_VIEW), in_pitch, out_offset, out_pitch -
+ *                                     byte offsets into the two slabs and bytes from one row of the view to the next (>= 3 W),
+ *                                     so that a view can be written straight into its column of a three-panel picture
+ *   view_cams    (nviews x 13 float): R (3,3) row-major, fx, fy, cx, cy
+ * View v draws meshes mesh0 .. mesh0 + count - 1; the ranges of different views may overlap (a frame's overlay and side view
+ * name the same meshes).  count == 0 is legal: such a view copies its frame rectangle (black in side view) - how panel 0 of a
+ * picture is written; GROUND_PLANE with count == 0 is refused.  THREAD_PER_TRIANGLE names the call's one raster launch: it is
+ * set on every view or on none.
+ * Optional outputs (DEVICE, NULL for none): id_map (int32) and depth (fp32) with the views back to back, view v at the sum of
+ * H * W over the views before it; screen with the (view, mesh of the view) pairs back to back in view order, V x 3 words each.
+ * CONTRACT: every view equals, bit for bit, what specmi_render_meshes writes when called with that view's arguments on a
+ * count >= 1 range - every byte of its output rectangle, every element of its id_map, depth and screen part.  Ids are m F + f
+ * with m counted from the view's mesh0; the ground plane lies through the lowest vertex of the view's own meshes and is
+ * anchored to the view's first mesh.  Bytes of the output slab outside every view's rectangle are not touched.
+ * One launch per stage - vertex, raster, resolve - and two memsets, whatever nviews is (spec_amd/csrc/render.hip).
+ * Refused (SPECMI_ERR_ARG), launching nothing: a null required pointer; nviews <= 0 or > 65535; V or F below 1; a mesh range
+ * outside [0, Mtot]; count * F or 3 * count * V of a view, or the same products of the counts summed over the views, of 2^31 or
+ * more; 2^31 pixels or more in all; H or W outside [1, 32768]; a pitch below 3 W; a view rectangle that leaves its slab; a slab
+ * of 4 GiB or more; overlapping slabs; two views whose output rectangles share a byte; an unknown flag; GROUND_PLANE without
+ * SIDE_VIEW or with count == 0; in_offset < 0 without SIDE_VIEW; THREAD_PER_TRIANGLE on some views only; a focal length that
+ * is not positive and finite; a centre, colour or R entry that is not finite.
+ * The view records live in one device table owned by the handle, under the rule of the ragged calls above: a call whose
+ * records differ from the previous call's rewrites the table and therefore first SYNCHRONISES THE WHOLE DEVICE, and cannot be
+ * made while a stream is being captured (SPECMI_ERR_STATE; the stream is asked first, so the capture stays valid and nothing is
+ * enqueued); a call that repeats the previous records does neither and can be captured.  The
+ * workspace is specmi_render_meshes' (one per handle, growth synchronises the device): 8 bytes of depth key per pixel of
+ * every view with count >= 1, and 24 bytes of snapped vertex and normal sum per vertex of every (view, mesh) pair. */
+int specmi_render_views(specmi_handle* h, const float* vertices, int Mtot, int V, const int32_t* faces, int F, const float* cam_t,
+                        const float* rgb, const uint8_t* in_slab, size_t in_slab_bytes, uint8_t* out_slab, size_t out_slab_bytes,
+                        const int32_t* view_geom, const int64_t* view_offsets, const float* view_cams, int nviews,
+                        int32_t* id_map, float* depth, void* screen, void* stream);
+
 /* ---- evaluation metrics on the path's outputs ---------------------------------- */
 
 /* eval_single (spec/utils/compute_error.py:52-86, spec/trainer.py:272-316): joints =

@@ -12,6 +12,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only pano_views         # the panorama view extractor -> profiles/pano_views_aux.json
     python scripts/bench_aux.py --only ragged_crops       # crops from frames of different sizes, per-frame route against the ragged one -> profiles/ragged_crops_aux.json
     python scripts/bench_aux.py --only render             # mesh overlay + side view, 8 meshes on a 1080p frame, both raster launch shapes -> profiles/render_aux.json
+    python scripts/bench_aux.py --only render_batch       # the pictures of a 32-frame flush, per-frame loop against the batched call -> profiles/render_batch_aux.json
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
     python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
@@ -353,6 +354,109 @@ def render_section(eng, a):
                               'vertices_faces': round((v.size * 4 * 3 + v.shape[0] * f.size * 4) / 1e6, 3)}}
 
 
+def render_batch_section(eng, a):
+    """The pictures of a 32-frame flush, (a) the per-frame loop - per frame two ``render_meshes`` calls and a concatenation; from
+    host frames ``render_image_group`` with its upload and download - against (b) the batched route - one ``render_views`` call per
+    chunk of ``plan_views``; from host frames ``render_image_groups`` -, alternated in this process in 3 rounds.  Device-resident
+    inputs: HIP events around the whole sequence.  Host frames to host pictures: wall clock, the copies included."""
+    import time
+    from spec_amd import _lib, render
+    from spec_amd.preprocess import pack_frames
+    v8, f, t8, _, _, _ = render_workload()
+    dev = eng.device
+    faces = torch.from_numpy(f).to(dev)
+    rng = np.random.default_rng(0)
+    rgb = render._rgb('pinkish')
+    side = _lib.RENDER_CULL | _lib.RENDER_SIDE_VIEW | _lib.RENDER_GROUND_PLANE
+    mixed = [(480, 640), (1080, 1920), (720, 1280), (600, 800), (1080, 1440), (768, 1024), (900, 1600), (1920, 1080)]      # (H, W)
+    shapes = {'A_32x1080p_8_meshes': ([(1080, 1920)] * 32, [8] * 32),
+              'B_32_mixed_sizes_1_to_8_meshes': ([mixed[i % len(mixed)] for i in range(32)], [int(c) for c in rng.integers(1, 9, 32)])}
+    reps = max(3, a.iters // 4)
+    out = {}
+    for name, (sizes, counts) in shapes.items():
+        F = len(sizes)
+        first = np.concatenate([[0], np.cumsum(counts)]).tolist()
+        host = [rng.integers(0, 256, (H, W, 3), dtype=np.uint8) for H, W in sizes]
+        verts = torch.from_numpy(np.concatenate([v8[:c] for c in counts])).to(dev)
+        cam_t = torch.from_numpy(np.concatenate([t8[:c] for c in counts])).to(dev)
+        Rs, R_dev = [np.eye(3, dtype=np.float32)] * F, torch.eye(3, device=dev)
+        focals, centers = [(1200. * H / 1080, 1200. * H / 1080) for H, _ in sizes], [(W / 2, H / 2) for H, W in sizes]
+        frames = [torch.from_numpy(fr).to(dev) for fr in host]
+        chunks = render.plan_views(sizes, counts)
+        for ch in chunks:
+            ch['in_slab'] = pack_frames([host[k] for k in ch['frames']], dev)[0]
+            ch['out_slab'] = torch.empty(ch['out_bytes'], device=dev, dtype=torch.uint8)
+            ch['cams'] = render.view_cams(ch['view_frame'], Rs, focals, centers)
+
+        def loop_dev(keep=False):
+            pics = []
+            for k in range(F):
+                m = slice(first[k], first[k + 1])
+                o = eng.render_meshes(verts[m], faces, cam_t[m], R_dev, focals[k], centers[k], frame=frames[k], rgb=rgb, flags=_lib.RENDER_CULL)
+                s = eng.render_meshes(verts[m], faces, cam_t[m], R_dev, focals[k], centers[k], frame=frames[k], rgb=rgb, flags=side)
+                pic = torch.cat([frames[k], o, s], dim=1)
+                if keep:
+                    pics.append(pic.cpu())
+            return pics
+
+        def batched_dev(keep=False):
+            pics = []
+            for ch in chunks:
+                eng.render_views(verts, faces, cam_t, ch['geom'], ch['offsets'], ch['cams'], ch['in_slab'], ch['out_slab'], rgb=rgb)
+                if keep:
+                    slab = ch['out_slab'].cpu()
+                    pics += [slab[o:o + 9 * sizes[k][0] * sizes[k][1]].reshape(sizes[k][0], 3 * sizes[k][1], 3) for (k, _), o in zip(ch['pictures'], ch['picture_offsets'])]
+            return pics
+
+        def loop_host():
+            return [render.render_image_group(host[k], cam_t[first[k]:first[k + 1]], verts[first[k]:first[k + 1]], Rs[k], focals[k], centers[k],
+                                              faces=faces, engine=eng).cpu().numpy() for k in range(F)]
+
+        def batched_host():
+            return render.render_image_groups(host, verts, cam_t, counts, Rs, focals, centers, faces=faces, engine=eng)
+
+        pa, pb = loop_dev(True), batched_dev(True)
+        same = len(pa) == len(pb) == F and all(torch.equal(x, y) for x, y in zip(pa, pb))
+        same = same and all(np.array_equal(x, y) for x, y in zip(loop_host(), batched_host()))
+        del pa, pb
+
+        def by_events(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize(); e0.record(); fn(); e1.record(); torch.cuda.synchronize()
+            return e0.elapsed_time(e1)
+
+        def by_wall(fn):
+            torch.cuda.synchronize(); t0 = time.perf_counter(); fn(); torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3
+
+        def compare(route_a, route_b, clock):
+            rounds = {'per_frame': [], 'batched': []}
+            for _ in range(3):                                          # alternated: both see the same clocks and the same neighbours
+                ms = {'per_frame': [], 'batched': []}
+                for _ in range(reps):
+                    for key, fn in (('per_frame', route_a), ('batched', route_b)):
+                        ms[key].append(clock(fn))
+                for key, v in ms.items():
+                    rounds[key].append(float(np.median(v)))
+            med = {k: float(np.median(v)) for k, v in rounds.items()}
+            spread = max(rounds['per_frame']) - min(rounds['per_frame'])
+            return {'ms_round_medians': {k: [round(x, 3) for x in v] for k, v in rounds.items()}, 'ms_median': {k: round(v, 3) for k, v in med.items()},
+                    'per_frame_spread_between_rounds_ms': round(spread, 3), 'ratio_per_frame_over_batched': round(med['per_frame'] / med['batched'], 2),
+                    'batched_not_slower_beyond_the_spread': bool(med['batched'] <= med['per_frame'] + spread)}
+        px = sum(H * W for H, W in sizes)
+        row = {'workload': f'{F} frames, {px / 1e6:.1f} Mpx in all, {sum(counts)} meshes of {v8.shape[1]} vertices / {f.shape[0]} faces; '
+                           f'{len(chunks)} chunks at the default pixel budget', 'bit_identical': bool(same),
+               'calls': {'per_frame': {'render_meshes': 2 * F, 'cat': F, 'uploads': F, 'downloads': F},
+                         'batched': {'render_views': len(chunks), 'uploads': len(chunks), 'downloads': len(chunks)}},
+               'device_resident_hip_events': compare(loop_dev, batched_dev, by_events),
+               'host_frames_to_host_pictures_wall': compare(loop_host, batched_host, by_wall)}
+        out[name] = row
+        print(json.dumps(row, indent=1))
+        del frames, chunks, verts, cam_t
+        torch.cuda.empty_cache()
+    return out
+
+
 def hmr_loss_section(eng, a, add):
     """``specmi_hmr_loss`` in HMRCamLoss mode with the per-vertex L1 term on: 2 * B * 6890 * 3 floats per call, at the batch of the
     evaluation config (64) and at ``--batch``."""
@@ -372,7 +476,7 @@ def hmr_loss_section(eng, a, add):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch'], default=None, help='run one section only')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -428,6 +532,15 @@ def main():
             json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'per-launch HIP events (library profiler)', 'render': row,
                        'source_hash': _lib.source_hash()}, f, indent=1)
         print(json.dumps(row))
+        return
+
+    if a.only == 'render_batch':
+        from spec_amd import _lib
+        rows = render_batch_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'iters': a.iters, 'timing': 'device_resident: HIP events around the whole sequence; host_frames_to_host_pictures: wall clock '
+                       'with the copies; 3 alternated rounds each', 'render_batch': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     if a.only == 'ragged_crops':

@@ -115,6 +115,8 @@ if __name__ == '__main__':
     parser.add_argument('--display', action='store_true')
     parser.add_argument('--smooth', action='store_true')
     parser.add_argument('--no_render', action='store_true', help='write no pictures (frame with horizon line | mesh overlay | side view, drawn by the device rasteriser)')
+    parser.add_argument('--render_each', action='store_true', help="one picture per detection showing that detection alone, as the reference "
+                        "draws it (default: a frame's detections drawn together, the picture written under each detection's name)")
     parser.add_argument('--no_save', action='store_true', help='disable final save of output results.')
     parser.add_argument('--save_obj', action='store_true')
     parser.add_argument('--sideview', action='store_true')

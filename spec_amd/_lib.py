@@ -165,6 +165,11 @@ PROTOTYPES = {
     'specmi_render_meshes': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, c_float_p, C.c_int,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (h, vertices, Mtot, V, faces, F, cam_t, rgb, in_slab, in_bytes, out_slab, out_bytes, view_geom, view_offsets, view_cams, nviews,
+    #  id_map, depth, screen, stream)
+    'specmi_render_views': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_float_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p, C.c_size_t, c_int32_p, c_int64_p, c_float_p, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
     'specmi_camcalib_eval': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1,6 +1,7 @@
 // api.hip - host side of libspecmi.so: the C ABI of include/specmi.h, parameter staging, workspace management and the launch
 // sequences of the two networks.  Weight packing / BatchNorm folding / the composed regressor live in commit.hip, the option table
 // in options.hip, device code in conv_igemm.hip / conv_wsplit.hip / conv_wino.hip / stem.hip / head.hip / smpl.hip / ...
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <climits>
@@ -803,6 +804,7 @@ int specmi_destroy(specmi_handle* h) {
     if (h->pano_tab) (void)hipFree(h->pano_tab);
     if (h->crop_tab) (void)hipFree(h->crop_tab);
     if (h->render_ws) (void)hipFree(h->render_ws);
+    if (h->views_tab) (void)hipFree(h->views_tab);
     hrnet_free(h->hrnet);
     delete h;
     return SPECMI_OK;
@@ -1605,9 +1607,147 @@ int specmi_render_meshes(specmi_handle* h, const float* vertices, int M, int V, 
     a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
     a.M = M; a.V = V; a.F = F; a.H = H; a.W = W; a.side = side; a.ground = ground; a.cull = (flags & SPECMI_RENDER_CULL) ? 1 : 0;
     a.keys = (unsigned long long*)(ws + off[0]); a.sws = (int*)(ws + off[1]); a.normals = (int*)(ws + off[2]); a.lowest = (int*)(ws + off[3]);
+    a.in_pitch = a.out_pitch = 3u * (unsigned)W;
     a.out = out; a.id_map = id_map; a.depth = depth; a.screen = (int*)screen;
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, side ? "render.side_view" : "render.overlay"};
     LAUNCHCHK(h, launch_render(a, (flags & SPECMI_RENDER_THREAD_PER_TRIANGLE) != 0, ctx), "render_meshes");
+    return SPECMI_OK;
+}
+
+// do the output rectangles of two views share a byte?  a rectangle = H rows of 3 W bytes, `pitch` bytes apart, from `off`
+struct ByteRect { long long off, pitch, row; int H; long long end() const { return off + (H - 1) * pitch + row; } };
+static bool rects_overlap(ByteRect a, ByteRect b) {
+    if (a.off > b.off) std::swap(a, b);
+    if (b.off >= a.end()) return false;
+    if (a.pitch == b.pitch) {       // the columns of one picture: b starts c bytes into row q of a
+        const long long q = (b.off - a.off) / a.pitch, c = (b.off - a.off) % a.pitch;
+        return (q < a.H && c < a.row) || (q + 1 < a.H && c + b.row > a.pitch);
+    }
+    for (int r = 0; r < b.H; ++r) {      // row r of b against the rows of a it reaches
+        const long long s0 = b.off + r * b.pitch - a.off, e0 = s0 + b.row - 1;     // first and last byte, counted from a's first
+        if (s0 >= a.end() - a.off) break;
+        const long long k1 = s0 / a.pitch, k2 = std::min<long long>(e0 / a.pitch, a.H - 1);
+        if (k2 - k1 >= 2) return true;                                              // a whole row of a lies inside
+        for (long long k = k1; k <= k2; ++k)
+            if (std::max(s0, k * a.pitch) <= std::min(e0, k * a.pitch + a.row - 1)) return true;
+    }
+    return false;
+}
+
+int specmi_render_views(specmi_handle* h, const float* vertices, int Mtot, int V, const int32_t* faces, int F, const float* cam_t,
+                        const float* rgb, const uint8_t* in_slab, size_t in_slab_bytes, uint8_t* out_slab, size_t out_slab_bytes,
+                        const int32_t* view_geom, const int64_t* view_offsets, const float* view_cams, int nviews, int32_t* id_map,
+                        float* depth, void* screen, void* stream) {
+    ENTER(h);
+    if (!vertices || !faces || !cam_t || !rgb || !out_slab || !view_geom || !view_offsets || !view_cams)
+        return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (nviews <= 0 || nviews > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 views per call, got %d", nviews);
+    if (Mtot < 0 || V < 1 || F < 1) return fail(h, SPECMI_ERR_ARG, "%d meshes of %d vertices and %d faces", Mtot, V, F);
+    if (in_slab_bytes >= 4294967296.0 || out_slab_bytes >= 4294967296.0)
+        return fail(h, SPECMI_ERR_ARG, "slabs of %zu / %zu bytes are beyond the kernels' 32-bit offsets", in_slab_bytes, out_slab_bytes);
+    if (in_slab && (const uint8_t*)out_slab < in_slab + in_slab_bytes && in_slab < (const uint8_t*)out_slab + out_slab_bytes)
+        return fail(h, SPECMI_ERR_ARG, "the frame slab and the output slab overlap");
+    RenderViewsArgs b{};
+    for (int k = 0; k < 3; ++k) {
+        if (!std::isfinite(rgb[k])) return fail(h, SPECMI_ERR_ARG, "base colour component %d is not finite", k);
+        b.rgb[k] = std::fmin(std::fmax(rgb[k], 0.f), 1.f);
+    }
+    const int known = SPECMI_RENDER_SIDE_VIEW | SPECMI_RENDER_GROUND_PLANE | SPECMI_RENDER_CULL | SPECMI_RENDER_THREAD_PER_TRIANGLE;
+    // [nviews records | px_prefix (nviews + 1) | pair_view (npairs)]
+    std::vector<int> tab((size_t)nviews * kRenderViewRec + nviews + 1, 0);
+    std::vector<ByteRect> rects((size_t)nviews);
+    long long px = 0, keys = 0, pairs = 0;
+    bool any_ground = false;
+    const bool thread_per_triangle = (view_geom[4] & SPECMI_RENDER_THREAD_PER_TRIANGLE) != 0;
+    for (int v = 0; v < nviews; ++v) {
+        const int H = view_geom[5 * v], W = view_geom[5 * v + 1], mesh0 = view_geom[5 * v + 2], count = view_geom[5 * v + 3], flags = view_geom[5 * v + 4];
+        const int64_t in_off = view_offsets[4 * v], in_pitch = view_offsets[4 * v + 1], out_off = view_offsets[4 * v + 2], out_pitch = view_offsets[4 * v + 3];
+        const float* cam = view_cams + 13 * (size_t)v;
+        const bool side = flags & SPECMI_RENDER_SIDE_VIEW, ground = flags & SPECMI_RENDER_GROUND_PLANE;
+        if (flags & ~known) return fail(h, SPECMI_ERR_ARG, "view %d: unknown render flag in 0x%x", v, flags);
+        if (ground && !side) return fail(h, SPECMI_ERR_ARG, "view %d: the ground plane belongs to the side view", v);
+        if (((flags & SPECMI_RENDER_THREAD_PER_TRIANGLE) != 0) != thread_per_triangle)
+            return fail(h, SPECMI_ERR_ARG, "view %d: THREAD_PER_TRIANGLE names the call's one raster launch: set it on every view or on none", v);
+        if (H < 1 || W < 1 || H > 32768 || W > 32768) return fail(h, SPECMI_ERR_ARG, "view %d: a %d x %d frame (1 .. 32768 per side)", v, H, W);
+        if (count < 0 || mesh0 < 0 || (long long)mesh0 + count > Mtot)
+            return fail(h, SPECMI_ERR_ARG, "view %d: meshes %d .. %lld leave the call's %d", v, mesh0, (long long)mesh0 + count, Mtot);
+        if ((double)count * F >= 2147483648.0 || (double)count * V * 3 >= 2147483648.0)
+            return fail(h, SPECMI_ERR_ARG, "view %d: %d meshes of %d vertices and %d faces are beyond 31-bit ids", v, count, V, F);
+        if (ground && count == 0) return fail(h, SPECMI_ERR_ARG, "view %d: a ground plane needs a mesh to lie under", v);
+        if (in_off < 0 && !side) return fail(h, SPECMI_ERR_ARG, "view %d: an overlay needs the frame it is drawn over (in_offset %lld)", v, (long long)in_off);
+        if (in_off >= 0 && !in_slab) return fail(h, SPECMI_ERR_ARG, "view %d: names a frame, but the frame slab is a null pointer", v);
+        if (out_pitch < 3LL * W || (in_off >= 0 && in_pitch < 3LL * W))
+            return fail(h, SPECMI_ERR_ARG, "view %d: pitches of %lld / %lld bytes for rows of %d", v, (long long)in_pitch, (long long)out_pitch, 3 * W);
+        if (out_off < 0 || (double)out_off + (double)(H - 1) * (double)out_pitch + 3.0 * W > (double)out_slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "view %d: its output rectangle leaves the slab of %zu bytes", v, out_slab_bytes);
+        if (in_off >= 0 && (double)in_off + (double)(H - 1) * (double)in_pitch + 3.0 * W > (double)in_slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "view %d: its frame leaves the slab of %zu bytes", v, in_slab_bytes);
+        if (!(cam[9] > 0.f) || !(cam[10] > 0.f) || !std::isfinite(cam[9]) || !std::isfinite(cam[10]) || !std::isfinite(cam[11]) || !std::isfinite(cam[12]))
+            return fail(h, SPECMI_ERR_ARG, "view %d: focal length (%g, %g) (> 0, finite) / centre (%g, %g) (finite)", v, (double)cam[9], (double)cam[10],
+                        (double)cam[11], (double)cam[12]);
+        for (int k = 0; k < 9; ++k)
+            if (!std::isfinite(cam[k])) return fail(h, SPECMI_ERR_ARG, "view %d: R entry %d is not finite", v, k);
+        RenderView r{};
+        std::memcpy(r.R, cam, 13 * sizeof(float));
+        r.H = H; r.W = W; r.mesh0 = mesh0; r.count = count; r.side = side; r.ground = ground; r.cull = (flags & SPECMI_RENDER_CULL) ? 1 : 0;
+        r.pair0 = (int)pairs; r.px0 = (int)px; r.key0 = count ? (int)keys : -1;
+        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal views give equal records
+        r.in_off = in_off >= 0 ? (unsigned)in_off : 0u; r.in_pitch = (in_off >= 0 && H > 1) ? (unsigned)in_pitch : 3u * W;
+        r.out_off = (unsigned)out_off; r.out_pitch = H > 1 ? (unsigned)out_pitch : 3u * W;
+        std::memcpy(tab.data() + (size_t)v * kRenderViewRec, &r, sizeof(r));
+        tab[(size_t)nviews * kRenderViewRec + v] = (int)px;
+        rects[v] = ByteRect{out_off, (long long)r.out_pitch, 3LL * W, H};
+        px += (long long)H * W;
+        if (count) keys += (long long)H * W;
+        pairs += count;
+        any_ground |= ground;
+        if (px >= 2147483648LL) return fail(h, SPECMI_ERR_ARG, "the views hold 2^31 pixels or more");
+        if ((double)pairs * F >= 2147483648.0 || (double)pairs * V * 3 >= 2147483648.0)
+            return fail(h, SPECMI_ERR_ARG, "the views name %lld meshes of %d vertices and %d faces in all: beyond 31-bit indices", pairs, V, F);
+        tab.insert(tab.end(), (size_t)count, v);
+    }
+    tab[(size_t)nviews * kRenderViewRec + nviews] = (int)px;
+    {   // no two output rectangles share a byte: sorted by first byte, a view is compared with those that start before it ends
+        std::vector<int> order((size_t)nviews);
+        for (int v = 0; v < nviews; ++v) order[v] = v;
+        std::sort(order.begin(), order.end(), [&](int x, int y) { return rects[x].off < rects[y].off; });
+        for (int i = 0; i < nviews; ++i)
+            for (int j = i + 1; j < nviews && rects[order[j]].off < rects[order[i]].end(); ++j)
+                if (rects_overlap(rects[order[i]], rects[order[j]]))
+                    return fail(h, SPECMI_ERR_ARG, "the output rectangles of views %d and %d overlap", order[i], order[j]);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    size_t off[4];
+    const size_t need = render_views_ws_layout(keys, pairs, V, nviews, off);
+    const bool regrown = tab.size() * 4 > h->views_tab_bytes;
+    if (need > h->render_ws_bytes || regrown || tab != h->views_host) {
+        // both need a whole-device synchronise, which would invalidate a capture under way on this stream: ask first and leave it valid
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone)
+            return fail(h, SPECMI_ERR_STATE, "new view records or a larger render workspace are not possible while the stream is being captured: "
+                        "run one eager call with these views first (nothing was enqueued)");
+    }
+    int rc;
+    if ((rc = grow_ragged(h, &h->render_ws, &h->render_ws_bytes, need, "the render workspace"))) return rc;
+    if ((rc = grow_ragged(h, (void**)&h->views_tab, &h->views_tab_bytes, tab.size() * 4, "the render view table"))) return rc;
+    if (regrown || tab != h->views_host) {
+        // views enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
+        if (!regrown && (rc = sync_for_growth(h, "the render view table"))) return rc;
+        h->views_host.swap(tab);
+        HIPCHK(h, hipMemcpyAsync(h->views_tab, h->views_host.data(), h->views_host.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    char* ws = (char*)h->render_ws;
+    b.vertices = vertices; b.faces = faces; b.cam_t = cam_t;
+    b.views = (const RenderView*)h->views_tab;
+    b.px_prefix = h->views_tab + (size_t)nviews * kRenderViewRec;
+    b.pair_view = b.px_prefix + nviews + 1;
+    b.in_slab = in_slab; b.out_slab = out_slab;
+    b.V = V; b.F = F; b.nviews = nviews; b.npairs = (int)pairs; b.total_px = (int)px;
+    b.keys = (unsigned long long*)(ws + off[0]); b.sws = (int*)(ws + off[1]); b.normals = (int*)(ws + off[2]); b.lowest = (int*)(ws + off[3]);
+    b.id_map = id_map; b.depth = depth; b.screen = (int*)screen;
+    LaunchCtx ctx{s, &h->prof, "render.views"};
+    LAUNCHCHK(h, launch_render_views(b, keys, any_ground, thread_per_triangle, ctx), "render_views");
     return SPECMI_OK;
 }
 

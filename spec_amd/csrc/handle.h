@@ -172,9 +172,13 @@ struct specmi_handle {
     CropFrame* crop_tab = nullptr;
     size_t crop_tab_bytes = 0;
     std::vector<CropFrame> crop_host;   // host image of crop_tab as last uploaded
-    // mesh rasteriser (specmi_render_meshes): depth keys, snapped vertices, normal sums; grows like ragged_tmp
+    // mesh rasteriser (specmi_render_meshes, specmi_render_views): depth keys, snapped vertices, normal sums; grows like ragged_tmp
     void* render_ws = nullptr;
     size_t render_ws_bytes = 0;
+    // specmi_render_views: the view records, pixel prefix and pair table, same growth and upload rules as ragged_tab
+    int* views_tab = nullptr;
+    size_t views_tab_bytes = 0;
+    std::vector<int> views_host;        // host image of views_tab as last uploaded
     SkWs sk;                            // split-K partial tiles + arrival counters (ensure_sk; never allocated under graph capture:
                                         // the warm-up call of a shape sizes it)
     std::vector<void*> sk_retired;      // outgrown split-K buffers, kept until destroy (captured graphs may still name them)

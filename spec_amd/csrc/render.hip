@@ -49,6 +49,21 @@
 // zfar) and nearer than the mesh.  Per pixel, fp32 in this order: g = ((j + 0.5 - cx) / fx, -((i + 0.5 - cy) / fy), -1),
 // d = R g (row k: (R[k][0] g.x + R[k][1] g.y) + R[k][2] g.z), s = y_plane / d.y, hit = o_0 + s d with o_0 = R t'_0,
 // tile parity = (floor(hit.x / 0.5) + floor(hit.z / 0.5)) & 1.
+//
+// MANY VIEWS IN ONE CALL (specmi_render_views).  A view is what one specmi_render_meshes call
+// draws - one camera, one output rectangle, a contiguous range of the call's meshes - and every view is drawn by the SAME device
+// functions (vertex_one, raster_one, resolve_one) from a RenderArgs put together out of its record, so the contract above holds
+// per view, bit for bit.  One launch per stage whatever the number of views: the vertex stage over all (pair, vertex), the raster
+// stage over all (pair, triangle), a pair being a (view, mesh of that view) enumerated on the host; the resolve stage over all
+// views' pixels.  One memset covers every key plane, one the per-view lowest-vertex words.  A view without meshes has no key plane
+// and no pairs: its resolve copies the frame (black in side view).
+// Normal sums are computed once per PAIR, not once per mesh: a mesh named by an overlay and a side view is summed twice, into
+// two copies, by the raster launch that visits both pairs anyway - integer sums, the same bits, and no pass that would have to
+// find the distinct meshes first.
+// Pixel -> view: the views' pixels are numbered back to back and a resolve thread finds its view in the prefix table
+// (px_prefix): a bisection for the wavefront's first pixel (uniform, about log2(nviews) scalar loads) and a walk forward for
+// the lanes behind a boundary.  No thread is idle for views of unequal size - the only waste is the last workgroup's tail, under
+// 256 threads per call, where a 2-D grid (view x tiles of the largest view) would idle (max - mean) / max of its workgroups.
 #include <climits>
 
 #include "specmi_internal.h"
@@ -78,34 +93,42 @@ __device__ __forceinline__ float cam_origin(const float* R, const float* t, int 
     return (R[3 * k] * -t[0] + R[3 * k + 1] * t[1]) + R[3 * k + 2] * t[2];
 }
 
+// vertex i = m V + v of the call `a` -> its height for the lowest-vertex search as an ordered int (INT_MAX without the ground plane)
+__device__ __forceinline__ int vertex_one(const RenderArgs& a, int i) {
+    const int m = i / a.V;
+    const float* v = a.vertices + (size_t)i * 3;
+    const float* t = a.cam_t + (size_t)m * 3;
+    const float* R = a.R;
+    float px = v[0], py = -v[1], pz = -v[2];
+    if (a.side) { const float x = px; px = -pz; pz = x; }
+    const float qx = (R[0] * px + R[3] * py) + R[6] * pz;
+    const float qy = (R[1] * px + R[4] * py) + R[7] * pz;
+    const float qz = (R[2] * px + R[5] * py) + R[8] * pz;
+    const float X = qx + t[0], Y = t[1] - qy, Z = t[2] - qz;
+    const float xs = (a.fx * X) / Z + a.cx, ys = (a.fy * Y) / Z + a.cy;
+    const bool keep = Z > kZNear && fabsf(xs) < kScreenLimit && fabsf(ys) < kScreenLimit;     // false for a NaN
+    int* s = a.sws + (size_t)i * 3;
+    s[0] = keep ? (int)rintf(xs * 256.f) : kDropped;
+    s[1] = keep ? (int)rintf(ys * 256.f) : kDropped;
+    s[2] = __float_as_int(Z);
+    if (a.screen) { int* u = a.screen + (size_t)i * 3; u[0] = s[0]; u[1] = s[1]; u[2] = s[2]; }
+    int* n = a.normals + (size_t)i * 3;
+    n[0] = 0; n[1] = 0; n[2] = 0;
+    return a.ground ? float_ordered(py - cam_origin(R, t, 1)) : INT_MAX;
+}
+
+__device__ __forceinline__ int wave_min(int low) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) low = min(low, __shfl_xor(low, o));
+    return low;
+}
+
 __global__ void __launch_bounds__(256) render_vertex_kernel(RenderArgs a) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     int low = INT_MAX;
-    if (i < a.M * a.V) {
-        const int m = i / a.V;
-        const float* v = a.vertices + (size_t)i * 3;
-        const float* t = a.cam_t + (size_t)m * 3;
-        const float* R = a.R;
-        float px = v[0], py = -v[1], pz = -v[2];
-        if (a.side) { const float x = px; px = -pz; pz = x; }
-        const float qx = (R[0] * px + R[3] * py) + R[6] * pz;
-        const float qy = (R[1] * px + R[4] * py) + R[7] * pz;
-        const float qz = (R[2] * px + R[5] * py) + R[8] * pz;
-        const float X = qx + t[0], Y = t[1] - qy, Z = t[2] - qz;
-        const float xs = (a.fx * X) / Z + a.cx, ys = (a.fy * Y) / Z + a.cy;
-        const bool keep = Z > kZNear && fabsf(xs) < kScreenLimit && fabsf(ys) < kScreenLimit;     // false for a NaN
-        int* s = a.sws + (size_t)i * 3;
-        s[0] = keep ? (int)rintf(xs * 256.f) : kDropped;
-        s[1] = keep ? (int)rintf(ys * 256.f) : kDropped;
-        s[2] = __float_as_int(Z);
-        if (a.screen) { int* u = a.screen + (size_t)i * 3; u[0] = s[0]; u[1] = s[1]; u[2] = s[2]; }
-        int* n = a.normals + (size_t)i * 3;
-        n[0] = 0; n[1] = 0; n[2] = 0;
-        if (a.ground) low = float_ordered(py - cam_origin(R, t, 1));
-    }
+    if (i < a.M * a.V) low = vertex_one(a, i);
     if (a.ground) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) low = min(low, __shfl_xor(low, o));
+        low = wave_min(low);
         if ((threadIdx.x & 63) == 0 && low != INT_MAX) atomicMin(a.lowest, low);
     }
 }
@@ -156,15 +179,10 @@ __device__ __forceinline__ float depth_at(const ScreenTri& t, const long long E[
     return 1.f / s;
 }
 
+// Triangle f of mesh m of the call `a`, as lane `lane` of the BW x BW lanes that share it sees it.
 // BW = 8: one wavefront per triangle, lanes striding the bounding box in 8 x 8 blocks; BW = 1: one thread per triangle
 template <int BW>
-__global__ void __launch_bounds__(256) render_raster_kernel(RenderArgs a) {
-    constexpr int L = BW * BW;
-    const long long gt = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long tri = gt / L;
-    const int lane = (int)(gt % L);
-    if (tri >= (long long)a.M * a.F) return;
-    const int m = (int)(tri / a.F), f = (int)(tri % a.F);
+__device__ __forceinline__ void raster_one(const RenderArgs& a, int m, int f, int lane) {
     int idx[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -211,11 +229,19 @@ __global__ void __launch_bounds__(256) render_raster_kernel(RenderArgs a) {
     }
 }
 
-__global__ void __launch_bounds__(256) render_resolve_kernel(RenderArgs a) {
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= a.H * a.W) return;
+template <int BW>
+__global__ void __launch_bounds__(256) render_raster_kernel(RenderArgs a) {
+    constexpr int L = BW * BW;
+    const long long gt = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long tri = gt / L;
+    if (tri >= (long long)a.M * a.F) return;
+    raster_one<BW>(a, (int)(tri / a.F), (int)(tri % a.F), (int)(gt % L));
+}
+
+// pixel p = i W + j of the call `a`
+__device__ __forceinline__ void resolve_one(const RenderArgs& a, int p) {
     const int i = p / a.W, j = p % a.W;
-    const unsigned long long key = a.keys[p];
+    const unsigned long long key = a.keys ? a.keys[p] : ~0ull;      // no key plane: a view without meshes
     const bool hit = key != ~0ull;
     int id = hit ? (int)(unsigned)(key & 0xffffffffull) : -1;
     float z = hit ? __uint_as_float((unsigned)(key >> 32)) : 0.f;
@@ -264,12 +290,18 @@ __global__ void __launch_bounds__(256) render_resolve_kernel(RenderArgs a) {
         for (int k = 0; k < 3; ++k) c[k] = (unsigned char)(int)rintf((255.f * a.rgb[k]) * shade);
     } else {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) c[k] = a.side ? (unsigned char)0 : a.frame[(size_t)p * 3 + k];
+        for (int k = 0; k < 3; ++k) c[k] = a.side ? (unsigned char)0 : a.frame[(size_t)i * a.in_pitch + j * 3 + k];
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) a.out[(size_t)p * 3 + k] = c[k];
+    for (int k = 0; k < 3; ++k) a.out[(size_t)i * a.out_pitch + j * 3 + k] = c[k];
     if (a.id_map) a.id_map[p] = id;
     if (a.depth) a.depth[p] = z;
+}
+
+__global__ void __launch_bounds__(256) render_resolve_kernel(RenderArgs a) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= a.H * a.W) return;
+    resolve_one(a, p);
 }
 
 size_t render_ws_layout(int M, int V, int H, int W, size_t off[4]) {
@@ -300,6 +332,108 @@ int launch_render(const RenderArgs& a, bool thread_per_triangle, const LaunchCtx
     {   // per pixel: the key, the frame byte triple in, the byte triple out (+ id and depth)
         ProfScope ps(ctx, "render_resolve", 0.0, px * (8 + (a.side ? 0 : 3) + 3 + (a.id_map ? 4 : 0) + (a.depth ? 4 : 0)));
         hipLaunchKernelGGL(render_resolve_kernel, dim3((unsigned)((a.H * a.W + 255) / 256)), dim3(256), 0, ctx.stream, a);
+    }
+    return (int)hipGetLastError();
+}
+
+// ---- many views in one call (specmi_render_views) --------------------------------------------------------------------------
+// The RenderArgs of view `view`, put together from its record: the device functions above then see one specmi_render_meshes call
+__device__ __forceinline__ RenderArgs view_args(const RenderViewsArgs& b, int view) {
+    const RenderView& r = b.views[view];
+    const size_t pv = (size_t)r.pair0 * b.V * 3;
+    RenderArgs a;
+    a.vertices = b.vertices + (size_t)r.mesh0 * b.V * 3;
+    a.faces = b.faces;
+    a.cam_t = b.cam_t + (size_t)r.mesh0 * 3;
+    a.R = r.R;
+    a.frame = b.in_slab + r.in_off;
+    a.fx = r.fx; a.fy = r.fy; a.cx = r.cx; a.cy = r.cy;
+    a.rgb[0] = b.rgb[0]; a.rgb[1] = b.rgb[1]; a.rgb[2] = b.rgb[2];
+    a.M = r.count; a.V = b.V; a.F = b.F; a.H = r.H; a.W = r.W; a.side = r.side; a.ground = r.ground; a.cull = r.cull;
+    a.in_pitch = r.in_pitch; a.out_pitch = r.out_pitch;
+    a.keys = r.key0 >= 0 ? b.keys + r.key0 : nullptr;
+    a.sws = b.sws + pv;
+    a.normals = b.normals + pv;
+    a.lowest = b.lowest + view;
+    a.out = b.out_slab + r.out_off;
+    a.id_map = b.id_map ? b.id_map + r.px0 : nullptr;
+    a.depth = b.depth ? b.depth + r.px0 : nullptr;
+    a.screen = b.screen ? b.screen + pv : nullptr;
+    return a;
+}
+
+__global__ void __launch_bounds__(256) render_views_vertex_kernel(RenderViewsArgs b) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int low = INT_MAX, view = -1;
+    if (i < b.npairs * b.V) {
+        view = b.pair_view[i / b.V];
+        low = vertex_one(view_args(b, view), i - b.views[view].pair0 * b.V);
+    }
+    // the lowest vertex of each view: one atomic per wavefront where the whole wavefront serves one view, one per lane where it
+    // straddles two pairs (min is order-free: the same word either way)
+    const int first = __shfl(view, 0);
+    if (__all(view == first)) {
+        low = wave_min(low);
+        if ((threadIdx.x & 63) == 0 && low != INT_MAX) atomicMin(b.lowest + first, low);
+    } else if (low != INT_MAX) {
+        atomicMin(b.lowest + view, low);
+    }
+}
+
+template <int BW>
+__global__ void __launch_bounds__(256) render_views_raster_kernel(RenderViewsArgs b) {
+    constexpr int L = BW * BW;
+    const long long gt = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long tri = gt / L;
+    if (tri >= (long long)b.npairs * b.F) return;
+    const int pair = (int)(tri / b.F);
+    const int view = b.pair_view[pair];
+    raster_one<BW>(view_args(b, view), pair - b.views[view].pair0, (int)(tri % b.F), (int)(gt % L));
+}
+
+__global__ void __launch_bounds__(256) render_views_resolve_kernel(RenderViewsArgs b) {
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= b.total_px) return;
+    // px_prefix[v] <= p < px_prefix[v + 1]: bisect for the wavefront's first pixel (uniform), then walk to the lane's own view
+    const int p0 = __builtin_amdgcn_readfirstlane(p);
+    int lo = 0, hi = b.nviews;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (b.px_prefix[mid] <= p0) lo = mid; else hi = mid;
+    }
+    int view = lo;
+    while (p >= b.px_prefix[view + 1]) ++view;
+    resolve_one(view_args(b, view), p - b.px_prefix[view]);
+}
+
+size_t render_views_ws_layout(long long keys, long long pairs, int V, int nviews, size_t off[4]) {
+    const auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    off[0] = 0;                                                   // keys: 8 bytes per pixel of every view that has meshes
+    off[1] = off[0] + up((size_t)keys * 8);                       // snapped vertices per (view, mesh) pair
+    off[2] = off[1] + up((size_t)pairs * V * 12);                 // normal sums per pair
+    off[3] = off[2] + up((size_t)pairs * V * 12);                 // the lowest y of every view
+    return off[3] + up((size_t)nviews * 4);
+}
+
+int launch_render_views(const RenderViewsArgs& b, long long keys, bool any_ground, bool thread_per_triangle, const LaunchCtx& ctx) {
+    const double px = (double)b.total_px, mv = (double)b.npairs * b.V, mf = (double)b.npairs * b.F;
+    hipError_t e;
+    if (keys && (e = hipMemsetAsync(b.keys, 0xFF, (size_t)keys * 8, ctx.stream)) != hipSuccess) return (int)e;
+    if (any_ground && (e = hipMemsetAsync(b.lowest, 0x7F, (size_t)b.nviews * 4, ctx.stream)) != hipSuccess) return (int)e;
+    if (b.npairs) {
+        {
+            ProfScope ps(ctx, "render_views_vertex", 0.0, mv * (12 + 12 + 12 + (b.screen ? 12 : 0)));
+            hipLaunchKernelGGL(render_views_vertex_kernel, dim3((unsigned)((b.npairs * b.V + 255) / 256)), dim3(256), 0, ctx.stream, b);
+        }
+        ProfScope ps(ctx, thread_per_triangle ? "render_views_raster_thread" : "render_views_raster_wave", 0.0, mf * (12 + 36 + 36 + 36) + (double)keys * 8);
+        const long long threads = (long long)b.npairs * b.F * (thread_per_triangle ? 1 : 64);
+        const unsigned blocks = (unsigned)((threads + 255) / 256);
+        if (thread_per_triangle) hipLaunchKernelGGL(render_views_raster_kernel<1>, dim3(blocks), dim3(256), 0, ctx.stream, b);
+        else hipLaunchKernelGGL(render_views_raster_kernel<8>, dim3(blocks), dim3(256), 0, ctx.stream, b);
+    }
+    {
+        ProfScope ps(ctx, "render_views_resolve", 0.0, (double)keys * 8 + px * (3 + 3 + (b.id_map ? 4 : 0) + (b.depth ? 4 : 0)));
+        hipLaunchKernelGGL(render_views_resolve_kernel, dim3((unsigned)((b.total_px + 255) / 256)), dim3(256), 0, ctx.stream, b);
     }
     return (int)hipGetLastError();
 }

@@ -454,14 +454,15 @@ struct RenderArgs {
     const int* faces;           // (F, 3)
     const float* cam_t;         // (M, 3)
     const float* R;             // (3, 3)
-    const unsigned char* frame; // (H, W, 3); unused in side view
+    const unsigned char* frame; // H rows of W x 3 bytes, in_pitch bytes apart; unused in side view
     float fx, fy, cx, cy, rgb[3];
     int M, V, F, H, W, side, ground, cull;
-    unsigned long long* keys;   // (H, W): float_bits(z) << 32 | id, all ones = nothing drawn
+    unsigned in_pitch, out_pitch;   // bytes from one row of frame / out to the next (3 W: dense)
+    unsigned long long* keys;   // (H, W): float_bits(z) << 32 | id, all ones = nothing drawn; null = nothing drawn anywhere
     int* sws;                   // (M, V, 3): snapped x, y and the bits of z
     int* normals;               // (M, V, 3): fixed-point sums of the incident face normals
     int* lowest;                // the lowest y of the scene as an ordered int (ground plane)
-    unsigned char* out;         // (H, W, 3)
+    unsigned char* out;         // H rows of W x 3 bytes, out_pitch bytes apart
     int* id_map;                // (H, W) or null
     float* depth;               // (H, W) or null
     int* screen;                // (M, V, 3) or null: the caller's copy of sws
@@ -469,5 +470,39 @@ struct RenderArgs {
 // byte offsets of keys, sws, normals, lowest in the workspace -> its size
 size_t render_ws_layout(int M, int V, int H, int W, size_t off[4]);
 int launch_render(const RenderArgs& a, bool thread_per_triangle, const LaunchCtx& ctx);
+
+// One view of a specmi_render_views call as the device reads it (28 ints).  pair0 = the view's first (view, mesh) pair, which
+// numbers its snapped vertices, normal sums and `screen` part; px0 = its first pixel in id_map / depth; key0 = its first key
+// (-1: count == 0, no key plane); offsets and pitches in bytes (slabs stay below 4 GiB)
+struct RenderView {
+    float R[9], fx, fy, cx, cy;
+    int H, W, mesh0, count, side, ground, cull, pair0, px0, key0;
+    unsigned in_off, in_pitch, out_off, out_pitch;
+    int pad_;
+};
+constexpr int kRenderViewRec = sizeof(RenderView) / 4;
+// One specmi_render_views call as the three kernels read it.  views, px_prefix (nviews + 1) and pair_view (npairs: the view of
+// each pair) are the three parts of the handle's view table; keys / sws / normals / lowest the four of its render workspace
+// (render_views_ws_layout); id_map, depth, screen the caller's optional outputs
+struct RenderViewsArgs {
+    const float* vertices;      // (Mtot, V, 3)
+    const int* faces;           // (F, 3)
+    const float* cam_t;         // (Mtot, 3)
+    const RenderView* views;
+    const int* px_prefix;
+    const int* pair_view;
+    const unsigned char* in_slab;
+    unsigned char* out_slab;
+    float rgb[3];
+    int V, F, nviews, npairs, total_px;
+    unsigned long long* keys;
+    int *sws, *normals, *lowest;
+    int* id_map;
+    float* depth;
+    int* screen;
+};
+// byte offsets of keys, sws, normals, lowest in the workspace -> its size
+size_t render_views_ws_layout(long long keys, long long pairs, int V, int nviews, size_t off[4]);
+int launch_render_views(const RenderViewsArgs& b, long long keys, bool any_ground, bool thread_per_triangle, const LaunchCtx& ctx);
 
 }  // namespace specmi

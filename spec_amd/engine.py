@@ -114,6 +114,99 @@ def flow_ragged_crops(ragged_crops=None) -> bool:
     return RAGGED_CROPS_DEFAULT if ragged_crops is None else bool(ragged_crops)
 
 
+# Which route the demo flow (SPECTester.run_on_image_folder) takes for its pictures: False = one render_image_group per frame -
+# an upload, two specmi_render_meshes calls, a concatenation and a download each (route (a)), True = one render_image_groups per
+# flush: one slab up, one specmi_render_views call and one slab down per chunk (route (b)).  Same bytes either
+# way; the default follows F16_CROPS_DEFAULT's rule: (b) where it is not slower than (a) beyond (a)'s own spread between rounds -
+# and from host frames to host pictures it is 2.2 - 2.6 x slower (profiles/render_batch_aux.json: on the device it is 1.2 - 1.3 x
+# faster, but the packing pass and the large pageable copies outweigh that).
+RENDER_BATCH_DEFAULT = False
+# The view pixels one specmi_render_views call of render_image_groups may hold (the flush is split into chunks under it): 64 Mpx
+# bound the depth keys at 512 MB.  A default, not a measurement.
+RENDER_PIXEL_BUDGET = 64 << 20
+
+
+def flow_render_batch(render_batch=None) -> bool:
+    """``render_batch`` (the flow's private switch) decides, None = the default."""
+    return RENDER_BATCH_DEFAULT if render_batch is None else bool(render_batch)
+
+
+def _rects_overlap(a, b) -> bool:
+    """Do two byte rectangles (first byte, pitch, row bytes, rows) share a byte?  (rects_overlap of spec_amd/csrc/api.hip)"""
+    if a[0] > b[0]:
+        a, b = b, a
+    (ao, ap, ar, ah), (bo, bp, br, bh) = a, b
+    if bo >= ao + (ah - 1) * ap + ar:
+        return False
+    if ap == bp:
+        q, c = divmod(bo - ao, ap)
+        return (q < ah and c < ar) or (q + 1 < ah and c + br > ap)
+    s0 = bo - ao + bp * np.arange(bh, dtype=np.int64)             # row r of b, counted from a's first byte
+    e0 = s0 + br - 1
+    k1, k2 = s0 // ap, np.minimum(e0 // ap, ah - 1)
+    hit = lambda k: (k >= k1) & (k <= k2) & (np.maximum(s0, k * ap) <= np.minimum(e0, k * ap + ar - 1))
+    return bool(((k2 - k1 >= 2) | hit(k1) | hit(k2)).any())
+
+
+def check_render_views(Mtot, V, F, geom, offsets, cams, in_bytes, out_bytes, rgb):
+    """Every refusal of ``specmi_render_views`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom``
+    (n, 5) [H, W, mesh0, count, flags], ``offsets`` (n, 4) [in_offset, in_pitch, out_offset, out_pitch], ``cams`` (n, 13)
+    [R, fx, fy, cx, cy], the sizes of the two slabs (``in_bytes`` None: no frame slab) and ``rgb``.  -> the arrays as the
+    library reads them (int32, int64, float32, float32).  Needs no device."""
+    geom = np.ascontiguousarray(geom, dtype=np.int64)
+    offsets, cams = np.ascontiguousarray(offsets, dtype=np.int64), np.ascontiguousarray(cams, dtype=np.float32)
+    n = geom.shape[0] if geom.ndim == 2 else -1
+    if geom.ndim != 2 or geom.shape[1] != 5 or tuple(offsets.shape) != (n, 4) or tuple(cams.shape) != (n, 13):
+        raise ValueError('views: geom (n, 5), offsets (n, 4) and cams (n, 13) with one row per view')
+    if not 1 <= n <= 65535:
+        raise ValueError(f'1 to 65535 views per call, got {n}')
+    if Mtot < 0 or V < 1 or F < 1:
+        raise ValueError(f'{Mtot} meshes of {V} vertices and {F} faces')
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32).reshape(-1)
+    if rgb.shape[0] != 3 or not np.isfinite(rgb).all():
+        raise ValueError('rgb: three finite floats in [0, 1]')
+    if out_bytes >= 1 << 32 or (in_bytes or 0) >= 1 << 32:
+        raise ValueError('a slab of 4 GiB or more is beyond the kernels\' 32-bit offsets')
+    H, W, mesh0, count, flags = geom.T
+    in_off, in_pitch, out_off, out_pitch = offsets.T
+    side, ground = (flags & _lib.RENDER_SIDE_VIEW) != 0, (flags & _lib.RENDER_GROUND_PLANE) != 0
+    if (flags & ~15).any() or (ground & ~side).any():
+        raise ValueError('flags: RENDER_SIDE_VIEW | RENDER_GROUND_PLANE (side view only) | RENDER_CULL | RENDER_THREAD_PER_TRIANGLE')
+    if len(set((flags & _lib.RENDER_THREAD_PER_TRIANGLE).tolist())) != 1:
+        raise ValueError('RENDER_THREAD_PER_TRIANGLE names the one raster launch of the call: on every view or on none')
+    if ((H < 1) | (H > 32768) | (W < 1) | (W > 32768)).any():
+        raise ValueError('a view of 1 .. 32768 pixels per side')
+    if ((count < 0) | (mesh0 < 0) | (mesh0 + count > Mtot)).any():
+        raise ValueError(f'a mesh range leaves the call\'s {Mtot} meshes')
+    if max(int(count.max()), int(count.sum())) * max(F, 3 * V) >= 1 << 31 or int((H * W).sum()) >= 1 << 31:
+        raise ValueError('the views are beyond 31-bit indices (count * F, 3 * count * V, pixels)')
+    if (ground & (count == 0)).any():
+        raise ValueError('a ground plane needs a mesh to lie under (count == 0)')
+    framed = in_off >= 0
+    if (~framed & ~side).any():
+        raise ValueError('an overlay needs the frame it is drawn over (in_offset < 0 is for side views)')
+    if framed.any() and in_bytes is None:
+        raise ValueError('a view names a frame, but there is no frame slab')
+    if (out_pitch < 3 * W).any() or (framed & (in_pitch < 3 * W)).any():
+        raise ValueError('a pitch below 3 * W bytes')
+    if (out_off < 0).any() or (out_off + (H - 1) * out_pitch + 3 * W > out_bytes).any():
+        raise ValueError(f'an output rectangle leaves the slab of {out_bytes} bytes')
+    if (framed & (in_off + (H - 1) * in_pitch + 3 * W > (in_bytes or 0))).any():
+        raise ValueError(f'a frame leaves the slab of {in_bytes} bytes')
+    if not (np.isfinite(cams).all() and (cams[:, 9:11] > 0).all()):
+        raise ValueError('focal lengths must be positive and finite, the centre and R finite')
+    rects = [(int(o), int(p) if h > 1 else 3 * int(w), 3 * int(w), int(h)) for o, p, w, h in zip(out_off, out_pitch, W, H)]
+    order = sorted(range(n), key=lambda v: rects[v][0])
+    for i, a in enumerate(order):
+        end = rects[a][0] + (rects[a][3] - 1) * rects[a][1] + rects[a][2]
+        for b in order[i + 1:]:
+            if rects[b][0] >= end:
+                break
+            if _rects_overlap(rects[a], rects[b]):
+                raise ValueError(f'the output rectangles of views {a} and {b} overlap')
+    return geom.astype(np.int32), offsets, cams, rgb
+
+
 def out_dtype(dtype):
     """The ``dtype=`` keyword of the producers: torch.float32 -> the (n,3,H,W) fp32 image, torch.float16 -> NHWC8 fp16."""
     if dtype not in (torch.float32, torch.float16):
@@ -580,6 +673,49 @@ class Engine:
         if not maps:
             return out
         return {'image': out, 'id_map': id_map, 'depth': depth, 'screen_xy': screen[..., :2], 'screen_z': screen[..., 2].contiguous().view(torch.float32)}
+
+    def render_views(self, vertices, faces, cam_t, geom, offsets, cams, in_slab, out_slab, rgb=(1., 1., 1.), maps=False):
+        """``specmi_render_views``: many views - each what one ``render_meshes`` call draws - in one call.  ``vertices``
+        (Mtot, V, 3) / ``cam_t`` (Mtot, 3) fp32 and ``faces`` (F, 3) int32 on the engine device; the view record as three host
+        arrays, one row per view: ``geom`` (n, 5) [H, W, mesh0, count, flags], ``offsets`` (n, 4) [in_offset (-1: none), in_pitch,
+        out_offset, out_pitch] in bytes, ``cams`` (n, 13) [R row-major, fx, fy, cx, cy] (``render.plan_views`` lays them out);
+        ``in_slab`` (1-D uint8, what ``pack_frames`` builds; None when no view names a frame) and ``out_slab`` (1-D uint8), both
+        on the engine device and not overlapping.  Writes the views into ``out_slab`` and returns it; with ``maps`` a dict that
+        also holds ``id_map`` int32 and ``depth`` fp32 (the views' H * W back to back), ``screen_xy`` (P, V, 2) int32 and
+        ``screen_z`` (P, V) fp32 (P = the (view, mesh) pairs in view order).  Everything is checked here, before the library is
+        called (``check_render_views``)."""
+        d = self.device
+        for name, x, dt in (('vertices', vertices, torch.float32), ('cam_t', cam_t, torch.float32), ('faces', faces, torch.int32)):
+            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != dt or not x.is_contiguous():
+                raise ValueError(f'{name} must be a contiguous {dt} tensor on the engine device')
+        if vertices.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[1] < 1:
+            raise ValueError('vertices must be (Mtot, V, 3) with V >= 1')
+        Mtot, V = int(vertices.shape[0]), int(vertices.shape[1])
+        if tuple(cam_t.shape) != (Mtot, 3):
+            raise ValueError('cam_t must be (Mtot, 3)')
+        if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+            raise ValueError('faces must be (F, 3) with F >= 1')
+        for name, x in (('in_slab', in_slab), ('out_slab', out_slab)):
+            if x is None and name == 'in_slab':
+                continue
+            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
+                raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
+        if in_slab is not None and in_slab.data_ptr() < out_slab.data_ptr() + out_slab.numel() and out_slab.data_ptr() < in_slab.data_ptr() + in_slab.numel():
+            raise ValueError('in_slab and out_slab overlap')
+        geom, offsets, cams, rgb = check_render_views(Mtot, V, int(faces.shape[0]), geom, offsets, cams,
+                                                      None if in_slab is None else in_slab.numel(), out_slab.numel(), rgb)
+        n, px, pairs = geom.shape[0], int((geom[:, 0].astype(np.int64) * geom[:, 1]).sum()), int(geom[:, 3].sum())
+        id_map = torch.empty(px, device=d, dtype=torch.int32) if maps else None
+        depth = torch.empty(px, device=d, dtype=torch.float32) if maps else None
+        screen = torch.empty(pairs, V, 3, device=d, dtype=torch.int32) if maps else None
+        _lib.check(self.h, self.lib.specmi_render_views(
+            self.h, _ptr(vertices), Mtot, V, _ptr(faces), int(faces.shape[0]), _ptr(cam_t), rgb.ctypes.data_as(_lib.c_float_p),
+            _ptr(in_slab), 0 if in_slab is None else in_slab.numel(), _ptr(out_slab), out_slab.numel(),
+            geom.ctypes.data_as(_lib.c_int32_p), offsets.ctypes.data_as(_lib.c_int64_p), cams.ctypes.data_as(_lib.c_float_p), n,
+            _ptr(id_map), _ptr(depth), _ptr(screen), self._stream()))
+        if not maps:
+            return out_slab
+        return {'slab': out_slab, 'id_map': id_map, 'depth': depth, 'screen_xy': screen[..., :2], 'screen_z': screen[..., 2].contiguous().view(torch.float32)}
 
     def _cam_args(self, B, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h):
         d = self.device

@@ -170,6 +170,110 @@ def render_image_group(image, camera_translation, vertices, camera_rotation, foc
     return out
 
 
+def plan_views(sizes, counts, each=False, pixel_budget=None, gap=0, cull=True):
+    """The view records and slab layouts of the three-panel pictures of many frames, for ``Engine.render_views``: pure host
+    code.  ``sizes`` [(H, W)] and ``counts`` (detections per frame, >= 1) describe a flush whose meshes lie frame after frame in
+    one (sum counts, V, 3) array.  One (H, 3W, 3) picture per frame holding all its detections - ``each``: one per detection,
+    holding that detection alone, in frame then detection order.  A picture is three views of pitch 9 W, panel k at byte column
+    3 W k: a ``count == 0`` view that copies panel 0, the overlay, and the side view with its ground plane, all reading the
+    picture's frame.  The pictures are split into CHUNKS, one ``render_views`` call each, so that a chunk's view pixels
+    (3 H W per picture) stay under ``pixel_budget`` (None = ``engine.RENDER_PIXEL_BUDGET``); a picture is never split and a
+    chunk holds at least one.  A chunk's frame slab holds the frames its pictures name, each once, back to back in frame order
+    (``pack_frames`` of those frames); its output slab holds its pictures back to back, ``gap`` bytes apart.
+    -> a list of chunks, each a dict: ``frames`` (the frame indices of its frame slab), ``in_bytes``, ``pictures``
+    [(frame, detection or None)], ``picture_offsets`` (byte offset of each picture in the output slab), ``out_bytes``,
+    ``geom`` (n, 5) int32 [H, W, mesh0, count, flags], ``offsets`` (n, 4) int64 [in_offset, in_pitch, out_offset, out_pitch],
+    ``view_frame`` (n,) the frame whose camera view v takes."""
+    from .engine import RENDER_PIXEL_BUDGET
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    counts = [int(c) for c in counts]
+    if not sizes or len(sizes) != len(counts):
+        raise ValueError('one (H, W) and one detection count per frame (at least one frame)')
+    if min(counts) < 1 or min(min(s) for s in sizes) < 1:
+        raise ValueError('every frame has at least one detection and at least one pixel per side')
+    budget = RENDER_PIXEL_BUDGET if pixel_budget is None else int(pixel_budget)
+    first = np.concatenate([[0], np.cumsum(counts)])
+    pictures = [(f, i) for f, c in enumerate(counts) for i in range(c)] if each else [(f, None) for f in range(len(counts))]
+    c = _lib.RENDER_CULL if cull else 0
+    chunks, cur, px = [], [], 0
+    for pic in pictures:
+        need = 3 * sizes[pic[0]][0] * sizes[pic[0]][1]
+        if cur and px + need > budget:
+            chunks.append(cur)
+            cur, px = [], 0
+        cur.append(pic)
+        px += need
+    chunks.append(cur)
+    out = []
+    for pics in chunks:
+        frames = sorted({f for f, _ in pics})
+        in_off, off = {}, 0
+        for f in frames:
+            in_off[f] = off
+            off += sizes[f][0] * sizes[f][1] * 3
+        geom, offsets, view_frame, pic_off, o = [], [], [], [], 0
+        for f, i in pics:
+            H, W = sizes[f]
+            mesh0, count = (int(first[f]), counts[f]) if i is None else (int(first[f]) + i, 1)
+            pic_off.append(o)
+            for k, (m0, cnt, flags) in enumerate(((0, 0, 0), (mesh0, count, c), (mesh0, count, c | _lib.RENDER_SIDE_VIEW | _lib.RENDER_GROUND_PLANE))):
+                geom.append((H, W, m0, cnt, flags))
+                offsets.append((in_off[f], 3 * W, o + 3 * W * k, 9 * W))
+                view_frame.append(f)
+            o += 9 * H * W + gap
+        out.append(dict(frames=frames, in_bytes=off, pictures=pics, picture_offsets=pic_off, out_bytes=o - gap,
+                        geom=np.asarray(geom, np.int32), offsets=np.asarray(offsets, np.int64), view_frame=np.asarray(view_frame, np.int64)))
+    return out
+
+
+def view_cams(view_frame, rotations, focals, centers) -> np.ndarray:
+    """The (n, 13) float32 camera rows [R row-major, fx, fy, cx, cy] of ``Engine.render_views`` for views that take the camera
+    of frame ``view_frame[v]``: ``rotations`` (F, 3, 3), ``focals`` (F, 2) = (fx, fy), ``centers`` (F, 2) = (cx, cy)."""
+    R = np.asarray(rotations, np.float32).reshape(-1, 9)
+    cam = np.concatenate([R, np.asarray(focals, np.float64).reshape(-1, 2).astype(np.float32),
+                          np.asarray(centers, np.float64).reshape(-1, 2).astype(np.float32)], axis=1)
+    return np.ascontiguousarray(cam[np.asarray(view_frame, np.int64)])
+
+
+def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, centers, cam_params=None, each=False, mesh_color='pinkish',
+                        faces=None, pixel_budget=None, device=None, engine=None, return_slabs=False):
+    """``render_image_group`` for the frames of a flush in one call per chunk (``specmi_render_views``): ``frames`` a list of
+    (H, W, 3) host images of any sizes, ``vertices`` (sum counts, V, 3) / ``cam_t`` (sum counts, 3) the detections frame after
+    frame (device tensors stay on the device), ``counts`` the detections per frame, ``rotations`` (F, 3, 3), ``focals`` (F, 2),
+    ``centers`` (F, 2) and ``cam_params`` (a list of (vfov, pitch, roll, f_pix) or None per frame) the frames' cameras.
+    Panel 0 is made per frame on the host (``group_panel0``: Pillow's horizon line); per chunk of ``plan_views`` the panels go
+    up in ONE slab, ONE ``render_views`` call draws every panel of every picture in place, and ONE slab comes down.
+    -> the list of (H, 3W, 3) uint8 host arrays, one per frame - ``each``: one per detection, that detection alone -, equal byte
+    for byte to ``render_image_group`` on the same frame and meshes.  ``return_slabs``: also [(device slab, picture offsets,
+    [(H, 3W)])] per chunk."""
+    from . import cam_utils
+    from .preprocess import pack_frames
+    frames = list(frames)
+    cam_params = [None] * len(frames) if cam_params is None else list(cam_params)
+    if not (len(frames) == len(counts) == len(cam_params)):
+        raise ValueError('one detection count (and one cam_params entry) per frame')
+    panel0 = [group_panel0(im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else im, cp) for im, cp in zip(frames, cam_params)]
+    dev = torch.device(device or (vertices.device if isinstance(vertices, torch.Tensor) and vertices.device.type == 'cuda' else 'cuda'))
+    eng = engine or cam_utils._engine(dev)
+    as_f32 = lambda x: torch.as_tensor(x).to(device=eng.device, dtype=torch.float32).contiguous()
+    vertices, cam_t = as_f32(vertices), as_f32(cam_t).reshape(-1, 3)
+    if vertices.dim() != 3 or vertices.shape[0] != sum(int(c) for c in counts):
+        raise ValueError('vertices must be (sum of counts, V, 3)')
+    table, rgb = device_faces(faces, eng.device), _rgb(mesh_color)
+    sizes = [p.shape[:2] for p in panel0]
+    pictures, slabs = [], []
+    for ch in plan_views(sizes, counts, each=each, pixel_budget=pixel_budget, cull=_closed(faces)):
+        in_slab, _, _ = pack_frames([panel0[f] for f in ch['frames']], eng.device)
+        out_slab = torch.empty(ch['out_bytes'], device=eng.device, dtype=torch.uint8)
+        eng.render_views(vertices, table, cam_t, ch['geom'], ch['offsets'], view_cams(ch['view_frame'], rotations, focals, centers),
+                         in_slab, out_slab, rgb=rgb)
+        host = out_slab.cpu().numpy()
+        shapes = [(sizes[f][0], 3 * sizes[f][1]) for f, _ in ch['pictures']]
+        pictures += [host[o:o + h * w3 * 3].reshape(h, w3, 3) for o, (h, w3) in zip(ch['picture_offsets'], shapes)]
+        slabs.append((out_slab, ch['picture_offsets'], shapes))
+    return (pictures, slabs) if return_slabs else pictures
+
+
 def _closed(faces) -> bool:
     """Cull back faces?  Yes for a caller's table and for the SMPL file's (closed, outward-wound); no for the synthetic body
     model's triangle soup, whose winding means nothing."""

@@ -10,7 +10,7 @@ YOLOv3, tester.py:73-84) is outside the path: ``run_detector`` reads boxes from 
 ``{image name: (n,4) [cx, cy, w, h]}``).  The three-panel pictures (:165-201) are drawn by this project's own rasteriser on the
 device (``spec_amd/render.py``; same geometry and file names, its own declared shading - not pyrender's look) when ``args.no_render``
 is present and false; a frame's detections are drawn together, one launch sequence per panel, and that picture is written under
-each detection's name."""
+each detection's name.  ``args.render_each`` writes the reference's pictures instead: file ``{stem}_{i:06d}`` shows detection i alone."""
 from __future__ import annotations
 
 import os
@@ -20,10 +20,10 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
-from . import assets, cam_utils, io_formats
+from . import assets, cam_utils, io_formats, render
 from .checkpoint import load_pretrained_model, read_checkpoint
 from .modules import HMR, CameraRegressorNetwork
-from .engine import flow_image_dtype, flow_ragged_crops, image_tensor
+from .engine import flow_image_dtype, flow_ragged_crops, flow_render_batch, image_tensor
 from .preprocess import camcalib_transform, crop_detections, crop_detections_ragged, pack_frames
 
 CAMCALIB_CKPT = 'data/camcalib/checkpoints/camcalib_sa_biased_l2.ckpt'     # scripts/camcalib_demo.py:39
@@ -101,6 +101,7 @@ class SPECTester:
         self._camcalib = getattr(args, 'camcalib_model', None)
         self._fp32_crops = None       # False: NHWC8 fp16 crops for a model at fp16; True: fp32 crops + in-trunk conversion (same bits)
         self._ragged_crops = None     # True: a flush's frames in one slab, one upload, one ragged crop launch; False: one of each per frame (same bits)
+        self._render_batch = None     # True: a flush's pictures in one render_image_groups call; False: one render_image_group per frame (same bytes)
 
     def _build_model(self):
         c = self.model_cfg
@@ -146,32 +147,56 @@ class SPECTester:
         R[:k], K[:k] = cam_utils.cam_params_from_angles(per_crop([r['pitch'].item() for r in recs]), per_crop([r['roll'].item() for r in recs]),
                                                         per_crop([float(r['f_pix']) for r in recs]), w, h, device=self.device)
 
-    def _render_frame(self, img_fname, rgb, vertices, cam_t, output_path, output_img_folder):
-        """``spec/tester.py:165-201`` for one frame: ``vertices`` (n, V, 3) / ``cam_t`` (n, 3) as the step left them on the device.
-        The render rotation is ``batch_euler2matrix([-pitch, 0, roll])`` = Rx(-pitch) Rz(roll) (:169-171), the focal length the
-        frame's f_pix, the centre (W // 2, H // 2) (:175).  -> the files written."""
+    def _frame_camera(self, img_fname, shape, output_path):
+        """What the pictures of one frame are drawn with (``spec/tester.py:169-175``): the render rotation
+        ``batch_euler2matrix([-pitch, 0, roll])`` = Rx(-pitch) Rz(roll), the frame's f_pix twice, the centre (W // 2, H // 2) and
+        the horizon line's (vfov, pitch, roll, f_pix)."""
         import joblib
-        from PIL import Image
-        from . import render
         rec = joblib.load(io_formats.camcalib_result_path(output_path, img_fname))
         pitch, roll, vfov, f_pix = rec['pitch'].item(), rec['roll'].item(), rec['vfov'].item(), float(rec['f_pix'])
         cp, sp, cr, sr = np.cos(-pitch), np.sin(-pitch), np.cos(roll), np.sin(roll)
         rot = np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]]) @ np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]])
-        h, w = rgb.shape[:2]
-        group = render.render_image_group(rgb, cam_t, vertices, rot.astype(np.float32), (f_pix, f_pix), (w // 2, h // 2),
-                                          cam_params=np.array([vfov, pitch, roll, f_pix]), device=self.device)
-        picture = Image.fromarray(group.cpu().numpy())
+        h, w = shape[:2]
+        return rot.astype(np.float32), (f_pix, f_pix), (w // 2, h // 2), np.array([vfov, pitch, roll, f_pix])
+
+    def _write_pictures(self, img_fname, pictures, vertices, output_path, output_img_folder):
+        """The files of one frame: ``pictures[i]`` (a PIL image) under detection i's name, and with ``args.save_obj`` its mesh."""
         stem, ext = os.path.splitext(os.path.basename(img_fname))
         os.makedirs(output_img_folder, exist_ok=True)
         written = []
         for i in range(vertices.shape[0]):
             written.append(os.path.join(output_img_folder, f'{stem}_{i:06d}{ext}'))
-            picture.save(written[-1])
+            pictures[i].save(written[-1])
             if getattr(self.args, 'save_obj', False):
                 mesh_folder = os.path.join(output_path, 'meshes', os.path.basename(img_fname).split('.')[0])
                 os.makedirs(mesh_folder, exist_ok=True)
                 render.write_obj(os.path.join(mesh_folder, f'{i:06d}.obj'), vertices[i].cpu().numpy() * np.array([1., -1., -1.], np.float32),
                                  assets.faces())
+        return written
+
+    def _render_frame(self, img_fname, rgb, vertices, cam_t, output_path, output_img_folder):
+        """``spec/tester.py:165-201`` for one frame: ``vertices`` (n, V, 3) / ``cam_t`` (n, 3) as the step left them on the device.
+        The render rotation is ``batch_euler2matrix([-pitch, 0, roll])`` = Rx(-pitch) Rz(roll) (:169-171), the focal length the
+        frame's f_pix, the centre (W // 2, H // 2) (:175).  -> the files written."""
+        from PIL import Image
+        rot, focal, center, cam_params = self._frame_camera(img_fname, rgb.shape, output_path)
+        group = render.render_image_group(rgb, cam_t, vertices, rot, focal, center, cam_params=cam_params, device=self.device)
+        return self._write_pictures(img_fname, [Image.fromarray(group.cpu().numpy())] * vertices.shape[0], vertices, output_path, output_img_folder)
+
+    def _render_flush(self, pending, frames, vertices, cam_t, output_path, output_img_folder, each):
+        """``_render_frame`` for every frame of a flush in one ``render_image_groups`` call: ``pending`` [(image, first crop,
+        crops)] and ``frames`` (the RGB arrays) in the same order, ``vertices`` / ``cam_t`` the flush's detections on the device.
+        Same file names, same bytes; ``each``: file i of a frame shows detection i alone (spec/tester.py:181-201)."""
+        from PIL import Image
+        cams = [self._frame_camera(f, rgb.shape, output_path) for (f, _, _), rgb in zip(pending, frames)]
+        counts = [n for _, _, n in pending]
+        groups = render.render_image_groups(frames, vertices, cam_t, counts, [c[0] for c in cams], [c[1] for c in cams], [c[2] for c in cams],
+                                            cam_params=[c[3] for c in cams], each=each, device=self.device)
+        written, g = [], 0
+        for img_fname, k0, n in pending:
+            pictures = [Image.fromarray(p) for p in groups[g:g + n]] if each else [Image.fromarray(groups[g])] * n
+            g += n if each else 1
+            written += self._write_pictures(img_fname, pictures, vertices[k0:k0 + n], output_path, output_img_folder)
         return written
 
     def run_camcalib(self, image_folder, output_folder):
@@ -195,7 +220,12 @@ class SPECTester:
         ``self._ragged_crops`` (None = ``engine.RAGGED_CROPS_DEFAULT``): the decoded frames of one flush are held on the host -
         at most ``frame_batch`` of them, on top of the decode window -, packed into one slab, uploaded once and cut by ONE
         ``crop_detections_ragged`` call; ``img_h``, ``img_w`` and the angles behind ``R`` / ``K`` are gathered on the host and go
-        up once per flush.  Same crops, same files, bit for bit."""
+        up once per flush.  Same crops, same files, bit for bit.
+        ``self._render_batch`` (None = ``engine.RENDER_BATCH_DEFAULT``), with ``args.no_render`` false: the pictures of one flush
+        are drawn by ONE ``render.render_image_groups`` call - one slab up, one ``specmi_render_views`` call, one slab down per
+        chunk - instead of one ``render_image_group`` per frame.  Same file names, same bytes.  ``args.render_each`` (implies the
+        batched route): file ``{stem}_{i:06d}`` shows detection i alone, as the reference draws it, instead of the frame's
+        detections together."""
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         image_file_names = list_images(image_folder)
@@ -225,6 +255,8 @@ class SPECTester:
         pending, k, n_done = [], 0, 0
         save = not getattr(self.args, 'no_save', False)
         render = not getattr(self.args, 'no_render', True)            # absent = no pictures, as before there were any
+        render_each = bool(getattr(self.args, 'render_each', False))
+        render_batch = render_each or flow_render_batch(self._render_batch)     # the per-detection pictures come from the batched call only
         if render and output_img_folder is None:
             raise ValueError('no_render is false: output_img_folder must name the folder the pictures go to')
         shown = {}                    # rendering: the decoded frames of this flush by file name
@@ -240,7 +272,10 @@ class SPECTester:
                 held.clear()
             output = self.model(buf['inp_images'][:k], cam_rotmat=R[:k], cam_intrinsics=K[:k], bbox_scale=buf['bbox_scale'][:k],
                                 bbox_center=buf['bbox_center'][:k], img_w=img_w[:k], img_h=img_h[:k])
-            if render:
+            if render and render_batch:
+                self._render_flush(pending, [shown.pop(f) for f, _, _ in pending], output['smpl_vertices'][:k], output['pred_cam_t'][:k],
+                                   output_path, output_img_folder, render_each)
+            elif render:
                 for img_fname, k0, n in pending:
                     self._render_frame(img_fname, shown.pop(img_fname), output['smpl_vertices'][k0:k0 + n], output['pred_cam_t'][k0:k0 + n],
                                        output_path, output_img_folder)
