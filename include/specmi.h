@@ -601,6 +601,50 @@ int specmi_render_views(specmi_handle* h, const float* vertices, int Mtot, int V
                         const int32_t* view_geom, const int64_t* view_offsets, const float* view_cams, int nviews,
                         int32_t* id_map, float* depth, void* screen, void* stream);
 
+/* How specmi_draw_skeletons paints.  NULL for the style means these defaults. */
+typedef struct specmi_draw_style {
+    int32_t radius;          /* of a joint's disc in pixels, 0 .. 64; default 4 */
+    int32_t thickness;       /* of a bone in pixels, 1 .. 64; default 2 */
+    float conf_thr;          /* D == 3: a keypoint is visible when conf > conf_thr (fp32); finite; default 0.3f */
+    uint8_t joint_rgb[3];    /* default 0, 255, 0 */
+    uint8_t bone_rgb[2][3];  /* bone b takes bone_rgb[b & 1]; defaults 0, 0, 255 (even) and 255, 0, 0 (odd) */
+} specmi_draw_style;
+
+/* 2D KEYPOINT SKELETONS painted in place into the uint8 frames of a slab, all frames of a flush in ONE launch: replaces
+ * pare.utils.vis_utils.draw_skeleton (cv2.circle / cv2.line on a host image) as render_image_group calls it before the mesh
+ * is laid over the frame (spec/utils/renderer_cam.py:159,167-168; spec/trainer.py:219,418), and the device-to-host copy of the
+ * keypoints and host-to-device copy of the frame around it.  pare and cv2 are not vendored: coverage, bone table and colours
+ * are THIS PROJECT'S OWN CONTRACT, exact and bit-reproducible; cv2's look is not claimed.  Works on a handle of any model kind,
+ * committed or not.
+ * DEVICE pointers: kp (Mtot, J, D) fp32 with D = 2 (x, y) or 3 (x, y, confidence), in pixels of the detection's frame;
+ * slab, uint8, of slab_bytes - the slab and offsets convention of specmi_render_views: what spec_amd.preprocess.pack_frames
+ * builds is valid, and so is the panel-0 column of a three-panel picture (pitch 9 W).  HOST: bones (NB x 2 int32 joint
+ * indices; may be NULL when NB == 0), style, and the FRAME RECORD, two arrays with one row per frame:
+ *   frame_geom    (nframes x 4 int32):  H, W, det0, count - the frame holds detections det0 .. det0 + count - 1 of kp;
+ *                                       count == 0 is legal and leaves the frame untouched
+ *   frame_offsets (nframes x 2 int64):  byte offset of the frame's first pixel in the slab, bytes from one row to the next
+ *                                       (pitch >= 3 W)
+ * THE CONTRACT in brief (stated in full at the head of spec_amd/csrc/draw.hip, restated in NumPy in tests/draw_ref.py):
+ * a keypoint is visible when x and y are finite, D == 2 or conf > conf_thr, and (int)x, (int)y (truncation) lie in
+ * [-16383, 16383]; nothing is clipped, a primitive with an invisible keypoint is not drawn.  Per frame, painter's order: for
+ * each detection in turn the J discs in joint order, then the NB bones in table order; later overwrites earlier.  Pixel
+ * (px, py) sits at its integer coordinate (no + 0.5).  A disc covers it iff (px - xi)^2 + (py - yi)^2 <= r^2; a bone iff its
+ * distance to the closed segment is at most t / 2, decided exactly in 64-bit integers (sides up to 8192 keep every term below
+ * 2^63).  Colours are uint8 RGB overwrite: no blending, no antialiasing.  Uncovered pixels, row padding and slab bytes outside
+ * every frame rectangle are not touched; no pixel is read; the result does not depend on scheduling.
+ * Refused (SPECMI_ERR_ARG), launching nothing: a null required pointer; nframes outside [1, 65535]; J < 1; D not 2 or 3;
+ * Mtot < 0; NB < 0, or NB > 0 with bones NULL; a bone index outside [0, J); Mtot * (J + NB) or Mtot * J * D of 2^31 or more;
+ * radius outside [0, 64]; thickness outside [1, 64]; a non-finite conf_thr; H or W outside [1, 8192]; a detection range outside
+ * [0, Mtot]; a pitch below 3 W; a frame rectangle that leaves the slab; two frames that share a byte.
+ * The frame records and the bone table live in one device table owned by the handle, under the rule of the ragged calls above:
+ * a call whose records or bones differ from the previous call's rewrites the table and therefore first SYNCHRONISES THE WHOLE
+ * DEVICE, and cannot be made while a stream is being captured (SPECMI_ERR_STATE; the stream is asked first, so the capture
+ * stays valid and nothing is enqueued); a call that repeats them does neither and can be captured.  The style and the pointers
+ * are not part of the table. */
+int specmi_draw_skeletons(specmi_handle* h, const float* kp, int Mtot, int J, int D, const int32_t* bones, int NB,
+                          const specmi_draw_style* style, uint8_t* slab, size_t slab_bytes, const int32_t* frame_geom,
+                          const int64_t* frame_offsets, int nframes, void* stream);
+
 /* ---- evaluation metrics on the path's outputs ---------------------------------- */
 
 /* eval_single (spec/utils/compute_error.py:52-86, spec/trainer.py:272-316): joints =

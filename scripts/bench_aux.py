@@ -13,6 +13,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only ragged_crops       # crops from frames of different sizes, per-frame route against the ragged one -> profiles/ragged_crops_aux.json
     python scripts/bench_aux.py --only render             # mesh overlay + side view, 8 meshes on a 1080p frame, both raster launch shapes -> profiles/render_aux.json
     python scripts/bench_aux.py --only render_batch       # the pictures of a 32-frame flush, per-frame loop against the batched call -> profiles/render_batch_aux.json
+    python scripts/bench_aux.py --only draw               # the 2D skeletons of a 1080p frame and of a 64-frame flush, next to render_views for the same flush -> profiles/draw_skeletons_aux.json
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
     python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
@@ -457,6 +458,99 @@ def render_batch_section(eng, a):
     return out
 
 
+def draw_section(eng, a):
+    """``specmi_draw_skeletons`` (49 joints and the 25 bones of ``constants.SKELETON_SPIN`` per detection, D = 2, keypoints spread
+    over the frame as a person's are: a cluster of about a third of the frame's height around a random centre) on (1) one
+    1080 x 1920 frame with 8 detections and (2) a 64-frame flush of mixed sizes with 1 to 8 detections each, next to
+    ``specmi_render_views`` for the pictures of the same flush, in this process.  HIP events around ``reps`` back-to-back calls
+    after a warm-up of the same calls, 3 alternated rounds; the drawing repeats its records, so no call rewrites the table."""
+    from spec_amd import render
+    from spec_amd.preprocess import pack_frames
+    v8, f, t8, _, _, _ = render_workload()
+    dev = eng.device
+    rng = np.random.default_rng(0)
+    faces = torch.from_numpy(f).to(dev)
+    rgb = render._rgb('pinkish')
+    mixed = [(480, 640), (1080, 1920), (720, 1280), (600, 800), (1080, 1440), (768, 1024), (900, 1600), (1920, 1080)]      # (H, W)
+    reps = max(5, a.iters)
+
+    def keypoints(sizes, counts):
+        out = []
+        for (H, W), c in zip(sizes, counts):
+            centre = np.stack([rng.uniform(0.1 * W, 0.9 * W, c), rng.uniform(0.2 * H, 0.8 * H, c)], 1)[:, None, :]
+            out.append(centre + rng.normal(0.0, 1.0, (c, 49, 2)) * np.array([0.06 * H, 0.17 * H]))
+        return torch.from_numpy(np.concatenate(out).astype(np.float32)).to(dev)
+
+    def events(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(); e0.record()
+        for _ in range(n):
+            fn()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    def rounds(fns):
+        for fn in fns.values():
+            for _ in range(3):
+                fn()
+        ms = {k: [] for k in fns}
+        for _ in range(3):
+            for k, fn in fns.items():
+                ms[k].append(events(fn, reps))
+        return {k: {'ms_per_call_rounds': [round(x, 4) for x in v], 'ms_per_call_median': round(float(np.median(v)), 4)} for k, v in ms.items()}
+
+    out = {}
+    # (1) one 1080p frame
+    sizes, counts = [(1080, 1920)], [8]
+    kp = keypoints(sizes, counts)
+    slab = pack_frames([rng.integers(0, 256, (1080, 1920, 3), dtype=np.uint8)], dev)[0]
+    geom, offsets = [[1080, 1920, 0, 8]], [[0, 3 * 1920]]
+    before = slab.clone()
+    eng.draw_skeletons(kp, slab, geom, offsets)
+    out['one_1080p_frame_8_detections'] = dict(rounds({'draw_skeletons': lambda: eng.draw_skeletons(kp, slab, geom, offsets)}),
+                                               workload='one 1080 x 1920 frame, 8 detections x (49 joints + 25 bones)',
+                                               pixels_painted=int((slab != before).reshape(-1, 3).any(dim=1).sum()))
+    # (2) a 64-frame flush, and render_views for its pictures
+    sizes = [mixed[i % len(mixed)] for i in range(64)]
+    counts = [int(c) for c in rng.integers(1, 9, 64)]
+    kp = keypoints(sizes, counts)
+    host = [rng.integers(0, 256, (H, W, 3), dtype=np.uint8) for H, W in sizes]
+    verts = torch.from_numpy(np.concatenate([v8[:c] for c in counts])).to(dev)
+    cam_t = torch.from_numpy(np.concatenate([t8[:c] for c in counts])).to(dev)
+    Rs = [np.eye(3, dtype=np.float32)] * 64
+    focals, centers = [(1200. * H / 1080, 1200. * H / 1080) for H, _ in sizes], [(W / 2, H / 2) for H, W in sizes]
+    chunks = render.plan_views(sizes, counts)
+    painted = 0
+    for ch in chunks:
+        ch['in_slab'] = pack_frames([host[k] for k in ch['frames']], dev)[0]
+        ch['out_slab'] = torch.empty(ch['out_bytes'], device=dev, dtype=torch.uint8)
+        ch['cams'] = render.view_cams(ch['view_frame'], Rs, focals, centers)
+        hw = np.asarray([sizes[k] for k in ch['frames']], np.int64)
+        ch['draw_geom'], ch['draw_offsets'] = np.concatenate([hw, ch['frame_dets']], axis=1), np.stack([ch['frame_offsets'], 3 * hw[:, 1]], axis=1)
+        before = ch['in_slab'].clone()
+        eng.draw_skeletons(kp, ch['in_slab'], ch['draw_geom'], ch['draw_offsets'])
+        painted += int((ch['in_slab'] != before).reshape(-1, 3).any(dim=1).sum())
+    del host
+
+    def draw_flush():
+        for ch in chunks:
+            eng.draw_skeletons(kp, ch['in_slab'], ch['draw_geom'], ch['draw_offsets'])
+
+    def views_flush():
+        for ch in chunks:
+            eng.render_views(verts, faces, cam_t, ch['geom'], ch['offsets'], ch['cams'], ch['in_slab'], ch['out_slab'], rgb=rgb)
+
+    # with several chunks both calls rewrite their record tables between chunks (a device synchronise each): timed as the flows pay it
+    row = rounds({'draw_skeletons': draw_flush, 'render_views': views_flush})
+    d, r = row['draw_skeletons']['ms_per_call_median'], row['render_views']['ms_per_call_median']
+    out['flush_64_mixed_frames'] = dict(row, workload=f'64 frames of 8 sizes, {sum(H * W for H, W in sizes) / 1e6:.1f} Mpx in all, {sum(counts)} detections x '
+                                        f'(49 joints + 25 bones); render_views: the same detections as meshes of {v8.shape[1]} vertices / {f.shape[0]} faces; '
+                                        f'{len(chunks)} chunks at the default pixel budget, one call of each per chunk',
+                                        pixels_painted=painted, draw_over_render_views=round(d / r, 4))
+    print(json.dumps(out, indent=1))
+    return out
+
+
 def hmr_loss_section(eng, a, add):
     """``specmi_hmr_loss`` in HMRCamLoss mode with the per-vertex L1 term on: 2 * B * 6890 * 3 floats per call, at the batch of the
     evaluation config (64) and at ``--batch``."""
@@ -476,7 +570,7 @@ def hmr_loss_section(eng, a, add):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw'], default=None, help='run one section only')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -541,6 +635,15 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'iters': a.iters, 'timing': 'device_resident: HIP events around the whole sequence; host_frames_to_host_pictures: wall clock '
                        'with the copies; 3 alternated rounds each', 'render_batch': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'draw':
+        from spec_amd import _lib
+        rows = draw_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the same calls; 3 alternated rounds',
+                       'draw': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     if a.only == 'ragged_crops':

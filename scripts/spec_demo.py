@@ -91,7 +91,7 @@ def main(args):
         tmp.cleanup()
 
 
-if __name__ == '__main__':
+def build_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--cfg', type=str, help='config file that defines model hyperparams', default=CFG)
     parser.add_argument('--ckpt', type=str, help='checkpoint path', default=CKPT)
@@ -120,5 +120,10 @@ if __name__ == '__main__':
     parser.add_argument('--no_save', action='store_true', help='disable final save of output results.')
     parser.add_argument('--save_obj', action='store_true')
     parser.add_argument('--sideview', action='store_true')
+    parser.add_argument('--draw_keypoints', action='store_true', help='draw 2d keypoints on rendered image')
     parser.add_argument('--synthetic', type=int, default=0, help='run on N random frames with random weights')
-    main(parser.parse_args())
+    return parser
+
+
+if __name__ == '__main__':
+    main(build_parser().parse_args())

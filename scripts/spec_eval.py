@@ -77,6 +77,9 @@ def main():
     ap.add_argument('--dataset_name', type=str, default='spec-syn')
     ap.add_argument('--loss', action='store_true', help="also report the mean of HMRCamLoss's loss dict (the training objective of "
                                                         'spec/losses.py, forward value only) over each dataset; off by default')
+    ap.add_argument('--save-images', action='store_true', help='one three-panel picture (full image with the 2D keypoints and horizon line | mesh '
+                    'overlay | side view) of the first image of every TESTING.SAVE_FREQ-th batch under LOG_DIR/output_images: sets '
+                    'TESTING.SAVE_IMAGES and TRAINING.SAVE_IMAGES (the reference writes the files only with both)')
     ap.add_argument('--report', type=str, default=None, metavar='eval.json',
                     help='write the scores and the delta against the reference README table (README.md:155-159) as JSON; the exit '
                          'code is 3 when |delta W-MPJPE| > 0.1 mm on a dataset the table lists (use on the real assets)')
@@ -94,6 +97,8 @@ def main():
     if cfg is None and os.path.exists(os.path.join(root, 'data/spec/checkpoints/spec_config.yaml')):
         cfg = os.path.join(root, 'data/spec/checkpoints/spec_config.yaml')
     hp = evaluation.load_config(cfg, args.opts)
+    if args.save_images:
+        hp['TESTING']['SAVE_IMAGES'] = hp['TRAINING']['SAVE_IMAGES'] = True
     ckpt = args.ckpt
     if ckpt is None and hp['TRAINING']['PRETRAINED_LIT'] is None:
         ckpt = 'data/spec/checkpoints/spec_checkpoint.ckpt'          # scripts/spec_demo.py:31

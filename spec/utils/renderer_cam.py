@@ -1,6 +1,7 @@
 """Import-path shim: ``from spec.utils.renderer_cam import render_image_group`` (spec/tester.py:33, spec/trainer.py:41 of the
 reference) resolves to this build's device rasteriser (spec_amd/render.py): the reference's geometry and file names, its own
-declared shading - not pyrender's look.  ``RendererCam`` (the training-time TensorBoard grid) is not provided."""
+declared shading - not pyrender's look.  ``render_image_group`` takes the reference's full argument list (``alpha`` is accepted
+and ignored, ``keypoints_2d`` is drawn on the device by this project's own drawing contract).  ``RendererCam`` (the training-time TensorBoard grid) is not provided."""
 import numpy as np
 
 from spec_amd.render import render_image_group  # noqa: F401

@@ -33,6 +33,7 @@ OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_MISSING = 0, 1, 2, 3, 4
 PRECISION_FP32, PRECISION_FP16 = 0, 1       # SPECMI_PRECISION_* (include/specmi.h)
 MODEL_CAMCALIB, MODEL_HMR, MODEL_SMPL = 0, 1, 2
 RENDER_SIDE_VIEW, RENDER_GROUND_PLANE, RENDER_CULL, RENDER_THREAD_PER_TRIANGLE = 1, 2, 4, 8     # SPECMI_RENDER_* (include/specmi.h)
+DRAW_MAX_SIDE, DRAW_MAX_COORD, DRAW_MAX_RADIUS, DRAW_MAX_THICKNESS = 8192, 16383, 64, 64      # the limits of specmi_draw_skeletons (include/specmi.h)
 HMR_LOSS, HMR_CAM_LOSS = 0, 1                 # SPECMI_HMR_LOSS / SPECMI_HMR_CAM_LOSS (include/specmi.h)
 # the ground-truth tensors of specmi_hmr_loss in the order of its prototype, per-image shapes (None = (V, 3)); int32 where named has_*
 HMR_LOSS_GT = (('pose', (72,)), ('betas', (10,)), ('pose_conf', (24,)), ('pose_3d', (24, 4)), ('keypoints', (49, 3)), ('vertices', None),
@@ -54,6 +55,16 @@ class HmrOutputs(C.Structure):
 class ProfEntry(C.Structure):
     _fields_ = [('kernel', C.c_char * 48), ('label', C.c_char * 48), ('ms', C.c_double),
                 ('flops', C.c_double), ('bytes', C.c_double), ('launches', C.c_int)]
+
+
+class DrawStyle(C.Structure):
+    """``specmi_draw_style`` (include/specmi.h); the defaults are the header's."""
+    _fields_ = [('radius', C.c_int32), ('thickness', C.c_int32), ('conf_thr', C.c_float), ('joint_rgb', C.c_uint8 * 3),
+                ('bone_rgb', (C.c_uint8 * 3) * 2)]
+
+    def __init__(self, radius=4, thickness=2, conf_thr=0.3, joint_rgb=(0, 255, 0), bone_rgb=((0, 0, 255), (255, 0, 0))):
+        super().__init__(int(radius), int(thickness), float(conf_thr), (C.c_uint8 * 3)(*joint_rgb),
+                         ((C.c_uint8 * 3) * 2)(*[(C.c_uint8 * 3)(*c) for c in bone_rgb]))
 
 
 class SpecmiError(RuntimeError):
@@ -170,6 +181,9 @@ PROTOTYPES = {
     'specmi_render_views': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, c_float_p, C.c_void_p,
                                       C.c_size_t, C.c_void_p, C.c_size_t, c_int32_p, c_int64_p, c_float_p, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    # (h, kp, Mtot, J, D, bones, NB, style, slab, slab_bytes, frame_geom, frame_offsets, nframes, stream)
+    'specmi_draw_skeletons': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_int32_p, C.c_int, C.POINTER(DrawStyle), C.c_void_p,
+                                        C.c_size_t, c_int32_p, c_int64_p, C.c_int, C.c_void_p]),
     'specmi_camcalib_eval': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

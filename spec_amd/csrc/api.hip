@@ -805,6 +805,7 @@ int specmi_destroy(specmi_handle* h) {
     if (h->crop_tab) (void)hipFree(h->crop_tab);
     if (h->render_ws) (void)hipFree(h->render_ws);
     if (h->views_tab) (void)hipFree(h->views_tab);
+    if (h->draw_tab) (void)hipFree(h->draw_tab);
     hrnet_free(h->hrnet);
     delete h;
     return SPECMI_OK;
@@ -1748,6 +1749,89 @@ int specmi_render_views(specmi_handle* h, const float* vertices, int Mtot, int V
     b.id_map = id_map; b.depth = depth; b.screen = (int*)screen;
     LaunchCtx ctx{s, &h->prof, "render.views"};
     LAUNCHCHK(h, launch_render_views(b, keys, any_ground, thread_per_triangle, ctx), "render_views");
+    return SPECMI_OK;
+}
+
+int specmi_draw_skeletons(specmi_handle* h, const float* kp, int Mtot, int J, int D, const int32_t* bones, int NB,
+                          const specmi_draw_style* style, uint8_t* slab, size_t slab_bytes, const int32_t* frame_geom,
+                          const int64_t* frame_offsets, int nframes, void* stream) {
+    ENTER(h);
+    if (!kp || !slab || !frame_geom || !frame_offsets) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (nframes <= 0 || nframes > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 frames per call, got %d", nframes);
+    if (J < 1 || (D != 2 && D != 3) || Mtot < 0) return fail(h, SPECMI_ERR_ARG, "%d detections of %d keypoints of %d floats (J >= 1, D = 2 or 3)", Mtot, J, D);
+    if (NB < 0 || (NB > 0 && !bones)) return fail(h, SPECMI_ERR_ARG, "%d bones%s", NB, NB > 0 ? ", but the bone table is a null pointer" : "");
+    if ((double)Mtot * ((double)J + NB) >= 2147483648.0 || (double)Mtot * J * D >= 2147483648.0 || (double)J + NB >= 2147483648.0)
+        return fail(h, SPECMI_ERR_ARG, "%d detections of %d keypoints and %d bones are beyond 31-bit indices", Mtot, J, NB);
+    for (int b = 0; b < 2 * NB; ++b)
+        if (bones[b] < 0 || bones[b] >= J) return fail(h, SPECMI_ERR_ARG, "bone %d names joint %d of %d", b / 2, bones[b], J);
+    const specmi_draw_style def{4, 2, 0.3f, {0, 255, 0}, {{0, 0, 255}, {255, 0, 0}}};
+    const specmi_draw_style& st = style ? *style : def;
+    if (st.radius < 0 || st.radius > kDrawMaxRadius || st.thickness < 1 || st.thickness > kDrawMaxThickness)
+        return fail(h, SPECMI_ERR_ARG, "radius %d (0 .. %d) / thickness %d (1 .. %d)", st.radius, kDrawMaxRadius, st.thickness, kDrawMaxThickness);
+    if (!std::isfinite(st.conf_thr)) return fail(h, SPECMI_ERR_ARG, "the confidence threshold is not finite");
+    // [nframes records | bones (NB x 2)]
+    std::vector<int> tab((size_t)nframes * kDrawFrameRec, 0);
+    std::vector<ByteRect> rects((size_t)nframes);
+    long long tiles = 0;
+    double kp_bytes = 0.0, px = 0.0;
+    for (int f = 0; f < nframes; ++f) {
+        const int H = frame_geom[4 * f], W = frame_geom[4 * f + 1], det0 = frame_geom[4 * f + 2], count = frame_geom[4 * f + 3];
+        const int64_t off = frame_offsets[2 * f], pitch = frame_offsets[2 * f + 1];
+        if (H < 1 || W < 1 || H > kDrawMaxSide || W > kDrawMaxSide)
+            return fail(h, SPECMI_ERR_ARG, "frame %d: %d x %d pixels (1 .. %d per side: the exact 64-bit coverage test)", f, H, W, kDrawMaxSide);
+        if (count < 0 || det0 < 0 || (long long)det0 + count > Mtot)
+            return fail(h, SPECMI_ERR_ARG, "frame %d: detections %d .. %lld leave the call's %d", f, det0, (long long)det0 + count, Mtot);
+        if (pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "frame %d: a pitch of %lld bytes for rows of %d", f, (long long)pitch, 3 * W);
+        if (off < 0 || (double)off + (double)(H - 1) * (double)pitch + 3.0 * W > (double)slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "frame %d: its rectangle leaves the slab of %zu bytes", f, slab_bytes);
+        DrawFrame r{};
+        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal frames give equal records
+        r.off = off; r.pitch = H > 1 ? pitch : 3LL * W; r.H = H; r.W = W; r.det0 = det0; r.count = count; r.tile0 = (int)tiles;
+        const int n = draw_frame_tiles(H, W, &r.tiles_x);
+        if (count) {
+            tiles += n;
+            kp_bytes += (double)n * count * ((double)J + 2.0 * NB) * D * 4;
+            px += (double)H * W;
+        }
+        if (tiles >= 2147483648LL) return fail(h, SPECMI_ERR_ARG, "the frames hold 2^31 tiles of 32 x 32 pixels or more");
+        std::memcpy(tab.data() + (size_t)f * kDrawFrameRec, &r, sizeof(r));
+        rects[f] = ByteRect{off, r.pitch, 3LL * W, H};
+    }
+    {   // no two frames share a byte: sorted by first byte, a frame is compared with those that start before it ends
+        std::vector<int> order((size_t)nframes);
+        for (int f = 0; f < nframes; ++f) order[f] = f;
+        std::sort(order.begin(), order.end(), [&](int x, int y) { return rects[x].off < rects[y].off; });
+        for (int i = 0; i < nframes; ++i)
+            for (int j = i + 1; j < nframes && rects[order[j]].off < rects[order[i]].end(); ++j)
+                if (rects_overlap(rects[order[i]], rects[order[j]]))
+                    return fail(h, SPECMI_ERR_ARG, "frames %d and %d share a byte", order[i], order[j]);
+    }
+    tab.insert(tab.end(), bones, bones + 2 * (size_t)NB);
+    hipStream_t s = (hipStream_t)stream;
+    const bool regrown = tab.size() * 4 > h->draw_tab_bytes;
+    if (regrown || tab != h->draw_host) {
+        // rewriting the table needs a whole-device synchronise, which would invalidate a capture under way on this stream: ask first
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone)
+            return fail(h, SPECMI_ERR_STATE, "new frame records or bones are not possible while the stream is being captured: "
+                        "run one eager call with these records first (nothing was enqueued)");
+    }
+    int rc;
+    if ((rc = grow_ragged(h, (void**)&h->draw_tab, &h->draw_tab_bytes, tab.size() * 4, "the skeleton frame table"))) return rc;
+    if (regrown || tab != h->draw_host) {
+        // a drawing enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
+        if (!regrown && (rc = sync_for_growth(h, "the skeleton frame table"))) return rc;
+        h->draw_host.swap(tab);
+        HIPCHK(h, hipMemcpyAsync(h->draw_tab, h->draw_host.data(), h->draw_host.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    DrawArgs a{};
+    a.kp = kp; a.frames = (const DrawFrame*)h->draw_tab; a.bones = h->draw_tab + (size_t)nframes * kDrawFrameRec; a.slab = slab;
+    a.nframes = nframes; a.J = J; a.D = D; a.NB = NB; a.radius = st.radius; a.thickness = st.thickness; a.thr = st.conf_thr;
+    const auto pack = [](const uint8_t* c) { return (unsigned)c[0] | (unsigned)c[1] << 8 | (unsigned)c[2] << 16; };
+    a.rgb[0] = pack(st.joint_rgb); a.rgb[1] = pack(st.bone_rgb[0]); a.rgb[2] = pack(st.bone_rgb[1]);
+    LaunchCtx ctx{s, &h->prof, "render.skeletons"};
+    LAUNCHCHK(h, launch_draw_skeletons(a, (int)tiles, kp_bytes, px, ctx), "draw_skeletons");
     return SPECMI_OK;
 }
 

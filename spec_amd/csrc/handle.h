@@ -179,6 +179,10 @@ struct specmi_handle {
     int* views_tab = nullptr;
     size_t views_tab_bytes = 0;
     std::vector<int> views_host;        // host image of views_tab as last uploaded
+    // specmi_draw_skeletons: the frame records and the bone table, same growth and upload rules as ragged_tab
+    int* draw_tab = nullptr;
+    size_t draw_tab_bytes = 0;
+    std::vector<int> draw_host;         // host image of draw_tab as last uploaded
     SkWs sk;                            // split-K partial tiles + arrival counters (ensure_sk; never allocated under graph capture:
                                         // the warm-up call of a shape sizes it)
     std::vector<void*> sk_retired;      // outgrown split-K buffers, kept until destroy (captured graphs may still name them)

@@ -505,4 +505,28 @@ struct RenderViewsArgs {
 size_t render_views_ws_layout(long long keys, long long pairs, int V, int nviews, size_t off[4]);
 int launch_render_views(const RenderViewsArgs& b, long long keys, bool any_ground, bool thread_per_triangle, const LaunchCtx& ctx);
 
+// ----------------------------------------------------------------------------------------
+// 2D keypoint skeletons  (draw.hip)
+// ----------------------------------------------------------------------------------------
+constexpr int kDrawMaxSide = 8192, kDrawMaxCoord = 16383, kDrawMaxRadius = 64, kDrawMaxThickness = 64;
+// One frame of a specmi_draw_skeletons call as the device reads it (10 ints): byte offset of its first pixel in the slab and
+// bytes from one row to the next, its size, its detections det0 .. det0 + count - 1, its first tile among the call's tiles
+// (a frame with count == 0 has none) and its tiles per row
+struct DrawFrame { long long off, pitch; int H, W, det0, count, tile0, tiles_x; };
+constexpr int kDrawFrameRec = sizeof(DrawFrame) / 4;
+// One specmi_draw_skeletons call as the kernel reads it.  frames (nframes records) and bones (NB x 2) are the two parts of the
+// handle's draw table; rgb = joints, even bones, odd bones as r | g << 8 | b << 16
+struct DrawArgs {
+    const float* kp;            // (Mtot, J, D)
+    const DrawFrame* frames;
+    const int* bones;
+    unsigned char* slab;
+    int nframes, J, D, NB, radius, thickness;
+    float thr;
+    unsigned rgb[3];
+};
+// the tiles a frame of this size takes -> and its tiles per row
+int draw_frame_tiles(int H, int W, int* tiles_x);
+int launch_draw_skeletons(const DrawArgs& a, int total_tiles, double kp_bytes, double px, const LaunchCtx& ctx);
+
 }  // namespace specmi

@@ -207,6 +207,54 @@ def check_render_views(Mtot, V, F, geom, offsets, cams, in_bytes, out_bytes, rgb
     return geom.astype(np.int32), offsets, cams, rgb
 
 
+def check_draw_skeletons(Mtot, J, D, bones, geom, offsets, slab_bytes, style=None):
+    """Every refusal of ``specmi_draw_skeletons`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``bones``
+    (NB, 2) joint indices (None or empty: no bones), ``geom`` (n, 4) [H, W, det0, count], ``offsets`` (n, 2) [byte offset, pitch],
+    the size of the slab and the ``_lib.DrawStyle`` (None: the defaults).  -> the arrays as the library reads them (int32, int32,
+    int64) and the style.  Needs no device."""
+    geom, offsets = np.ascontiguousarray(geom, dtype=np.int64), np.ascontiguousarray(offsets, dtype=np.int64)
+    bones = np.zeros((0, 2), np.int64) if bones is None else np.ascontiguousarray(bones, dtype=np.int64).reshape(-1, 2)
+    n = geom.shape[0] if geom.ndim == 2 else -1
+    if geom.ndim != 2 or geom.shape[1] != 4 or tuple(offsets.shape) != (n, 2):
+        raise ValueError('frames: geom (n, 4) and offsets (n, 2) with one row per frame')
+    if not 1 <= n <= 65535:
+        raise ValueError(f'1 to 65535 frames per call, got {n}')
+    if J < 1 or D not in (2, 3) or Mtot < 0:
+        raise ValueError(f'{Mtot} detections of {J} keypoints of {D} floats (J >= 1, D = 2 or 3)')
+    NB = bones.shape[0]
+    if NB and ((bones < 0) | (bones >= J)).any():
+        raise ValueError(f'a bone names a joint outside [0, {J})')
+    if Mtot * (J + NB) >= 1 << 31 or Mtot * J * D >= 1 << 31:
+        raise ValueError('the keypoints are beyond 31-bit indices')
+    style = _lib.DrawStyle() if style is None else style
+    if not (0 <= style.radius <= _lib.DRAW_MAX_RADIUS and 1 <= style.thickness <= _lib.DRAW_MAX_THICKNESS):
+        raise ValueError(f'radius 0 .. {_lib.DRAW_MAX_RADIUS}, thickness 1 .. {_lib.DRAW_MAX_THICKNESS}')
+    if not np.isfinite(style.conf_thr):
+        raise ValueError('the confidence threshold must be finite')
+    H, W, det0, count = geom.T
+    off, pitch = offsets.T
+    if ((H < 1) | (H > _lib.DRAW_MAX_SIDE) | (W < 1) | (W > _lib.DRAW_MAX_SIDE)).any():
+        raise ValueError(f'a frame of 1 .. {_lib.DRAW_MAX_SIDE} pixels per side')
+    if ((count < 0) | (det0 < 0) | (det0 + count > Mtot)).any():
+        raise ValueError(f'a detection range leaves the call\'s {Mtot} detections')
+    if (pitch < 3 * W).any():
+        raise ValueError('a pitch below 3 * W bytes')
+    if (off < 0).any() or (off + (H - 1) * pitch + 3 * W > slab_bytes).any():
+        raise ValueError(f'a frame rectangle leaves the slab of {slab_bytes} bytes')
+    if int((-(-H // 32) * -(-W // 32))[count > 0].sum()) >= 1 << 31:
+        raise ValueError('the frames hold 2^31 tiles of 32 x 32 pixels or more')
+    rects = [(int(o), int(p) if h > 1 else 3 * int(w), 3 * int(w), int(h)) for o, p, w, h in zip(off, pitch, W, H)]
+    order = sorted(range(n), key=lambda f: rects[f][0])
+    for i, a in enumerate(order):
+        end = rects[a][0] + (rects[a][3] - 1) * rects[a][1] + rects[a][2]
+        for b in order[i + 1:]:
+            if rects[b][0] >= end:
+                break
+            if _rects_overlap(rects[a], rects[b]):
+                raise ValueError(f'frames {a} and {b} share a byte')
+    return bones.astype(np.int32), geom.astype(np.int32), offsets, style
+
+
 def out_dtype(dtype):
     """The ``dtype=`` keyword of the producers: torch.float32 -> the (n,3,H,W) fp32 image, torch.float16 -> NHWC8 fp16."""
     if dtype not in (torch.float32, torch.float16):
@@ -716,6 +764,30 @@ class Engine:
         if not maps:
             return out_slab
         return {'slab': out_slab, 'id_map': id_map, 'depth': depth, 'screen_xy': screen[..., :2], 'screen_z': screen[..., 2].contiguous().view(torch.float32)}
+
+    def draw_skeletons(self, kp, slab, geom, offsets, bones=None, style=None):
+        """``specmi_draw_skeletons``: the 2D skeletons of ``kp`` (Mtot, J, D) fp32 on the engine device - D = 2 (x, y) or 3
+        (x, y, confidence), in pixels of the detection's frame - painted in place into the frames of ``slab`` (1-D uint8 on the
+        engine device; what ``pack_frames`` builds, or the panel-0 columns of pictures).  The frame record as two host arrays, one
+        row per frame: ``geom`` (n, 4) [H, W, det0, count] and ``offsets`` (n, 2) [byte offset, pitch]; ``bones`` (NB, 2) joint
+        indices (None = ``constants.SKELETON_SPIN``, which needs J = 49; an empty table draws joints only), ``style`` a
+        ``_lib.DrawStyle`` (None = radius 4, thickness 2, threshold 0.3, green joints, blue / red bones).  Returns ``slab``.
+        Everything is checked here, before the library is called (``check_draw_skeletons``)."""
+        d = self.device
+        if not isinstance(kp, torch.Tensor) or kp.device != d or kp.dtype != torch.float32 or not kp.is_contiguous() or kp.dim() != 3:
+            raise ValueError('kp must be a contiguous (Mtot, J, D) float32 tensor on the engine device')
+        if not isinstance(slab, torch.Tensor) or slab.device != d or slab.dtype != torch.uint8 or slab.dim() != 1 or not slab.is_contiguous():
+            raise ValueError('slab must be a contiguous 1-D uint8 tensor on the engine device')
+        if bones is None:
+            from .constants import SKELETON_SPIN
+            bones = SKELETON_SPIN
+        Mtot, J, D = (int(x) for x in kp.shape)
+        bones, geom, offsets, style = check_draw_skeletons(Mtot, J, D, bones, geom, offsets, slab.numel(), style)
+        _lib.check(self.h, self.lib.specmi_draw_skeletons(
+            self.h, _ptr(kp), Mtot, J, D, bones.ctypes.data_as(_lib.c_int32_p) if bones.shape[0] else None, int(bones.shape[0]), C.byref(style),
+            _ptr(slab), slab.numel(), geom.ctypes.data_as(_lib.c_int32_p), offsets.ctypes.data_as(_lib.c_int64_p), int(geom.shape[0]),
+            self._stream()))
+        return slab
 
     def _cam_args(self, B, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h):
         d = self.device

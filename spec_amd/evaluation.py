@@ -41,8 +41,8 @@ README_TABLE = {'spec-mtp': (124.3, 71.8, 147.1), 'spec-syn': (74.9, 54.5, 90.5)
 DEFAULTS = {   # the hparams of spec/config.py the evaluation reads
     'LOG_DIR': 'logs/experiments', 'METHOD': 'hmr_cam',
     'DATASET': {'BATCH_SIZE': 64, 'VAL_DS': 'spec-syn_spec-mtp_3dpw-test-cam', 'IMG_RES': 224},
-    'TRAINING': {'PRETRAINED_LIT': None, 'USE_AMP': False},
-    'TESTING': {'USE_GT_CAM': False, 'SAVE_RESULTS': True},
+    'TRAINING': {'PRETRAINED_LIT': None, 'USE_AMP': False, 'SAVE_IMAGES': False},
+    'TESTING': {'USE_GT_CAM': False, 'SAVE_RESULTS': True, 'SAVE_IMAGES': False, 'SAVE_FREQ': 1},
     'HMR': {'BACKBONE': 'resnet50', 'USE_CAM_FEATS': False},
 }
 
@@ -118,8 +118,7 @@ class EvalDataset:
             pose, betas = np.where(keep, d[pose_key][idx], 0.0), np.where(keep, d['shape'][idx], 0.0)
         else:
             has_smpl, pose, betas = np.zeros(n), np.zeros((n, 72)), np.zeros((n, 10))
-        kp = np.concatenate([d['openpose'][idx] if 'openpose' in d else np.zeros((n, 25, 3)),
-                             d['part'][idx] if 'part' in d else np.zeros((n, 24, 3))], axis=1)
+        kp = keypoints_orig(d, idx)
         return {'pose': f(pose), 'betas': f(betas), 'pose_conf': torch.ones(n, 24, device=device),
                 'pose_3d': f(d['S'][idx]) if 'S' in d else torch.zeros(n, 24, 4, device=device),
                 'keypoints_orig': f(kp), 'has_smpl': f(has_smpl != 0, torch.int32),
@@ -161,6 +160,37 @@ class EvalDataset:
                 'imgname': paths}
 
 
+def keypoints_orig(data: dict, idx) -> np.ndarray:
+    """``keypoints_orig`` of the samples ``idx`` (spec/dataset/cam_dataset.py:148-157,386-413): the 25 ``openpose`` and the 24
+    ``part`` keypoints (x, y, confidence) in full-image pixels, zeros where the annotation file lacks them -> (n, 49, 3)."""
+    n = len(idx)
+    return np.concatenate([data['openpose'][idx] if 'openpose' in data else np.zeros((n, 25, 3)),
+                           data['part'][idx] if 'part' in data else np.zeros((n, 24, 3))], axis=1)
+
+
+def save_batch_picture(ds: 'EvalDataset', idx, pred, save_dir: str, dataloader_nb: int, batch_nb: int, device) -> str:
+    """``SPECTrainer.validation_summaries`` (spec/trainer.py:366-423) for one batch: ONE picture, of the batch's first image
+    (``max_save_img = 1``) - the full image with the ground-truth 2D skeleton ``keypoints_orig`` (drawn on the device), the
+    horizon line of the dataset's CamCalib prediction, the predicted mesh over it and the side view.  The render rotation is
+    ``batch_euler2matrix([-pitch, 0, roll])`` = Rx(-pitch) Rz(roll), the focal length f_pix twice, the centre (W // 2, H // 2),
+    all from the ``camcalib_*`` fields (what the dataset hands out as ``pred_cam_*``, whichever camera the model was given).
+    -> the file written: ``save_dir/{epoch 0:04d}_{dataloader:02d}_{batch:05d}_{image 0:02d}_{basename}``."""
+    from . import render
+    d, i = ds.data, int(idx[0])
+    imgname = os.path.join(ds.img_dir, str(ds.imgname[i]))
+    image = read_image_rgb(imgname)
+    pitch, roll, vfov, f_pix = (float(d[k][i]) for k in ('camcalib_pitch', 'camcalib_roll', 'camcalib_vfov', 'camcalib_f_pix'))
+    cp, sp, cr, sr = np.cos(-pitch), np.sin(-pitch), np.cos(roll), np.sin(roll)
+    rot = (np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]]) @ np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]])).astype(np.float32)
+    h, w = image.shape[:2]
+    os.makedirs(save_dir, exist_ok=True)
+    save_filename = os.path.join(save_dir, f'{0:04d}_{dataloader_nb:02d}_{batch_nb:05d}_{0:02d}_{os.path.basename(imgname)}')
+    render.render_image_group(image, pred['pred_cam_t'][0], pred['smpl_vertices'][0], rot, (f_pix, f_pix), (w // 2, h // 2),
+                              save_filename=save_filename, keypoints_2d=keypoints_orig(d, idx[:1])[0],
+                              cam_params=np.array([vfov, pitch, roll, f_pix]), device=device)
+    return save_filename
+
+
 def loss_module(hparams: dict):
     """``HMRCamLoss`` as ``SPECTrainer.__init__`` builds it (spec/trainer.py:57-66): the ``HMR.*_WEIGHT`` keys of the config
     where it has them, the constructor's defaults (= the defaults of spec/config.py:155-163) elsewhere."""
@@ -178,15 +208,23 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     """Test + compute_error for every dataset of ``DATASET.VAL_DS``; returns {dataset: compute_error result}.  ``loss``: every
     batch also goes through ``HMRCamLoss`` (the objective the checkpoint was trained under, spec/trainer.py:141-168, with the
     ground-truth vertices of the body model); the mean of each key over the run's images (a batch's dict weighted by its size) is
-    logged after the error lines and returned under ``'loss'``.  Off by default: the log and the files are then unchanged."""
+    logged after the error lines and returned under ``'loss'``.  Off by default: the log and the files are then unchanged.
+    ``TESTING.SAVE_IMAGES`` with ``TESTING.SAVE_FREQ`` (spec/trainer.py:355-357): every SAVE_FREQ-th batch one picture of the
+    batch's first image (``save_batch_picture``) goes to ``LOG_DIR/output_images`` - written only when ``TRAINING.SAVE_IMAGES``
+    is set too, the reference's quirk (:402), kept.  Error lines and result files do not change."""
     from .modules import HMR
     dev = torch.device(device)
     if hparams.get('METHOD') != 'hmr_cam':
         raise ValueError(f"METHOD {hparams.get('METHOD')!r} is undefined (spec/trainer.py:47-69 builds HMR for 'hmr_cam' only)")
+    testing, training = hparams.get('TESTING') or {}, hparams.get('TRAINING') or {}
+    save_images = bool(testing.get('SAVE_IMAGES', False)) and bool(training.get('SAVE_IMAGES', False))
+    save_freq = max(1, int(testing.get('SAVE_FREQ', 1)))
     cwd = os.getcwd()
     os.chdir(data_root)                     # the reference's asset paths are relative to the repo root
     try:
         assets.load_assets()
+        if save_images:
+            assets.faces()                  # the pictures' face table is read from the model file on first use: while its path resolves
         hm = HMR(backbone=hparams['HMR']['BACKBONE'], img_res=hparams['DATASET']['IMG_RES'], pretrained=None,
                  use_cam_feats=bool(hparams['HMR']['USE_CAM_FEATS']), use_cam=True)
         ckpt = ckpt or hparams['TRAINING']['PRETRAINED_LIT']
@@ -206,7 +244,7 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     bs = int(hparams['DATASET']['BATCH_SIZE'])
     log_dir = hparams['LOG_DIR'] if os.path.isabs(hparams['LOG_DIR']) else os.path.join(data_root, hparams['LOG_DIR'])
     results = {}
-    for name in str(hparams['DATASET']['VAL_DS']).split('_'):
+    for dataloader_nb, name in enumerate(str(hparams['DATASET']['VAL_DS']).split('_')):
         ds = EvalDataset(name, data_root)
         n = len(ds) if limit is None else min(limit, len(ds))
         dump = io_formats.EvalDump()
@@ -217,6 +255,8 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
             # positional call of spec/trainer.py:139
             pred = hm(b['img'], b['cam_rotmat'], b['cam_int'], b['scale'], b['center'], b['img_w'], b['img_h'])
             dump.add(pred, imgnames=b['imgname'], dataset_name=name)
+            if save_images and (b0 // bs) % save_freq == 0:
+                log(f"wrote {save_batch_picture(ds, idx, pred, os.path.join(log_dir, 'output_images'), dataloader_nb, b0 // bs, dev)}")
             if loss_fn is not None:
                 gt = ds.loss_gt(idx, torch.stack([b['img_h'], b['img_w']], 1), dev)
                 gt['vertices'] = body.native(gt['pose'], gt['betas'], vertices=True, joints24=False)[0]      # spec/trainer.py:149-155,166
@@ -258,11 +298,14 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
 # stand-in ``data/`` tree in the REAL container formats (tests / dry runs; the licensed files cannot ship)
 # ------------------------------------------------------------------------------------------------------------
 def write_standin_data_tree(root: str, n_images: int = 6, seed: int = 7, dataset: str = 'spec-syn',
-                            hmr_seed: int = 1002, smpl_seed: int = 1003) -> dict:
+                            hmr_seed: int = 1002, smpl_seed: int = 1003, keypoints: bool = False) -> dict:
     """Writes under ``root`` everything run_evaluation reads, with synthetic numbers but the real formats: a Lightning
     ``.ckpt`` (``model.``-prefixed keys, trainer-level ``smpl.*`` / ``J_regressor`` keys that must be ignored, a pickled
     foreign hyper-parameter class), an SMPL ``.pkl`` with chumpy-pickled and scipy-sparse members, the ``.npy`` / ``.npz``
-    side files, the yacs-style YAML, annotations and PNG frames.  Returns the ground truth it used."""
+    side files, the yacs-style YAML, annotations and PNG frames.  ``keypoints``: the annotations also hold ``openpose``
+    (n, 25, 3) and ``part`` (n, 24, 3) 2D keypoints (x, y in pixels of the frame - some beyond it -, confidences on both sides
+    of 0.3 and exact zeros), drawn from a generator of their own: everything else in the tree is unchanged by the switch.
+    Returns the ground truth it used."""
     import pickle
     import scipy.sparse as sp
     import yaml
@@ -388,5 +431,12 @@ def write_standin_data_tree(root: str, n_images: int = 6, seed: int = 7, dataset
         ann['pose_cam'] = (rng.standard_normal((n_images, 72)) * 0.25).astype(np.float64)
         import joblib
         joblib.dump(torch.from_numpy(Rgt), j(f'data/camcalib/{dataset}_cam_rotmat.pkl'))
+    if keypoints:
+        krng = np.random.default_rng(seed + 1000003)
+        for key, nj in (('openpose', 25), ('part', 24)):
+            kp = np.concatenate([krng.uniform(-20, W + 20, (n_images, nj, 1)), krng.uniform(-20, H + 20, (n_images, nj, 1)),
+                                 krng.uniform(0.0, 1.0, (n_images, nj, 1))], axis=2)
+            kp[:, ::5, 2] = 0.0                                      # unannotated joints
+            ann[key] = kp
     np.savez(j(DATASET_FILES[dataset]), **ann)
     return {'annotations': ann, 'smpl_model': model, 'hmr_state': hs, 'camcalib_state': cs, 'frame_hw': (H, W)}

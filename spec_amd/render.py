@@ -8,7 +8,14 @@ bit (tests/render_ref.py).  The look is NOT pyrender's: shading is ``rgb * min(1
 ground plane is an analytic two-grey checker of 0.5 m tiles (the reference's ``get_checkerboard_plane`` lives in the un-vendored
 ``pare``), the colour table below is a stand-in for ``pare``'s ``get_colors`` and there is no alpha blending.  Triangles that
 reach behind the near plane (z <= 0.05) are dropped, not clipped.  The horizon line and its caption are drawn on the host with
-Pillow exactly as ``camcalib/vis_utils.py:63-110`` does."""
+Pillow exactly as ``camcalib/vis_utils.py:63-110`` does.
+
+The 2D keypoint skeleton (``render_image_group(keypoints_2d=...)``, ``draw_skeleton``) is painted on the device by
+``specmi_draw_skeletons`` (spec_amd/csrc/draw.hip).  ``pare.utils.vis_utils.draw_skeleton``, ``kp_utils.get_spin_skeleton`` and
+``cv2`` are not vendored: which pixels a joint's disc and a bone cover, the bone table (``constants.SKELETON_SPIN``) and the
+colours (green joints, bones alternately blue and red) are this project's own contract, exact and reproducible bit for bit
+(tests/draw_ref.py) - cv2's look is not claimed.  The skeleton is drawn OVER the finished panel 0, where the reference draws it
+before the horizon line and caption: the two differ only where a bone or joint crosses the line or the caption strip."""
 from __future__ import annotations
 
 import os
@@ -128,13 +135,57 @@ def group_panel0(image, cam_params=None) -> np.ndarray:
     return np.ascontiguousarray(image)
 
 
+def _keypoints(kp, device, unnormalize=False, res=224) -> torch.Tensor:
+    """``kp`` (J, D) or (M, J, D), D = 2 or 3, as a contiguous (M, J, D) fp32 tensor on ``device`` (a device tensor stays there);
+    ``unnormalize``: x and y from [-1, 1] to pixels by ``(kp + 1) * res / 2``."""
+    kp = torch.as_tensor(kp).detach().to(device=device, dtype=torch.float32)
+    if kp.dim() == 2:
+        kp = kp[None]
+    if kp.dim() != 3 or kp.shape[2] not in (2, 3):
+        raise ValueError('keypoints must be (J, D) or (M, J, D) with D = 2 (x, y) or 3 (x, y, confidence)')
+    if unnormalize:
+        kp = kp.clone()
+        kp[..., :2] = (kp[..., :2] + 1.0) * float(res) / 2.0
+    return kp.contiguous()
+
+
+def draw_skeleton(image, kp_2d, dataset='spin', unnormalize=True, thickness=2, res=224, engine=None):
+    """``pare.utils.vis_utils.draw_skeleton`` as ``render_image_group`` calls it (renderer_cam.py:168), on the device
+    (``specmi_draw_skeletons``): the skeletons ``kp_2d`` (J, D) - or (M, J, D), drawn one after the other - over ``image``.
+    ``image``: an (H, W, 3) uint8 device tensor is drawn into and returned; a host array (uint8, or floats as ``group_panel0``
+    takes them) is uploaded and a uint8 host array returned.  ``dataset``: 'spin' only (``constants.SKELETON_SPIN``, J = 49).
+    ``unnormalize``: the keypoints are in [-1, 1] of a ``res`` x ``res`` crop and become pixels by ``(kp + 1) * res / 2``.
+    Joints are discs of radius 4, bones have ``thickness``; D = 3: a keypoint with confidence <= 0.3 is not drawn.  Coverage,
+    bone table and colours are this project's own (module docstring)."""
+    from . import cam_utils
+    if dataset != 'spin':
+        raise ValueError(f"dataset {dataset!r}: only the 'spin' skeleton (constants.SKELETON_SPIN) is defined")
+    on_device = isinstance(image, torch.Tensor) and image.device.type == 'cuda'
+    if on_device:
+        if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3 or not image.is_contiguous():
+            raise ValueError('a device image must be a contiguous (H, W, 3) uint8 tensor (it is drawn into)')
+        eng = engine or cam_utils._engine(image.device)
+        frame = image
+    else:
+        eng = engine or cam_utils._engine(torch.device('cuda'))
+        frame = torch.from_numpy(group_panel0(image.detach().numpy() if isinstance(image, torch.Tensor) else image)).to(eng.device)
+    kp = _keypoints(kp_2d, eng.device, unnormalize, res)
+    H, W = int(frame.shape[0]), int(frame.shape[1])
+    eng.draw_skeletons(kp, frame.view(-1), [[H, W, 0, kp.shape[0]]], [[0, 3 * W]], style=_lib.DrawStyle(thickness=thickness))
+    return frame if on_device else frame.cpu().numpy()
+
+
 def render_image_group(image, camera_translation, vertices, camera_rotation, focal_length, camera_center, mesh_color='pinkish',
-                       faces=None, mesh_filename: Optional[str] = None, save_filename: Optional[str] = None, cam_params: Optional[Sequence] = None,
-                       device=None, engine=None):
+                       alpha=1.0, faces=None, mesh_filename: Optional[str] = None, save_filename: Optional[str] = None, keypoints_2d=None,
+                       cam_params: Optional[Sequence] = None, device=None, engine=None):
     """The three panels of ``render_image_group`` (renderer_cam.py:147-218) side by side, (H, 3W, 3) uint8 on the device:
 
     0. ``image`` (H, W, 3; uint8, or floats in [0, 1] / [0, 255] as the reference accepts) with - given ``cam_params`` =
-       (vfov, pitch, roll, f_pix) - the horizon line and caption of ``show_horizon_line(..., width=5, debug=True, text_size=30)``;
+       (vfov, pitch, roll, f_pix) - the horizon line and caption of ``show_horizon_line(..., width=5, debug=True, text_size=30)``
+       and - given ``keypoints_2d`` (J, D), or (M, J, D) for the M meshes, in pixels of ``image`` - the 2D skeletons
+       (``draw_skeleton(..., unnormalize=False)``, on the device), so that they show in panels 0 and 1.  Stated deviation: the
+       reference draws the skeleton BEFORE the line and caption (renderer_cam.py:167-173); here it is drawn over the finished
+       panel, which differs only where a bone or joint crosses the line or the caption strip;
     1. the meshes drawn over panel 0;
     2. the side view at 270 degrees with the ground plane.
 
@@ -142,7 +193,7 @@ def render_image_group(image, camera_translation, vertices, camera_rotation, foc
     launch sequence per panel (one mesh (V, 3) / (3,) is the reference's call).  ``mesh_filename``: the meshes after the 180
     degree turn as .obj (``NAME.obj``; ``NAME_<m>.obj`` from the second on) and the x-flipped translations as .npy
     (renderer_cam.py:74,87-90).  ``save_filename``: the image through Pillow (the reference's cv2.imwrite of the RGB-swapped
-    array stores the same pixels)."""
+    array stores the same pixels).  ``alpha`` is accepted and ignored: the reference's material is ``alphaMode='OPAQUE'``."""
     from . import cam_utils
     if isinstance(image, torch.Tensor):
         device = device or (image.device if image.device.type == 'cuda' else None)
@@ -151,6 +202,8 @@ def render_image_group(image, camera_translation, vertices, camera_rotation, foc
     dev = torch.device(device or 'cuda')
     eng = engine or cam_utils._engine(dev)
     panel0 = torch.from_numpy(np.ascontiguousarray(image)).to(eng.device)
+    if keypoints_2d is not None:
+        draw_skeleton(panel0, keypoints_2d, unnormalize=False, engine=eng)
     kw = dict(faces=faces, color=mesh_color, engine=eng, cull=_closed(faces))
     overlay = render_overlay(panel0, vertices, camera_translation, camera_rotation, focal_length, camera_center, **kw)
     side = render_overlay(panel0, vertices, camera_translation, camera_rotation, focal_length, camera_center, side_view=True, ground_plane=True, **kw)
@@ -170,7 +223,7 @@ def render_image_group(image, camera_translation, vertices, camera_rotation, foc
     return out
 
 
-def plan_views(sizes, counts, each=False, pixel_budget=None, gap=0, cull=True):
+def plan_views(sizes, counts, each=False, pixel_budget=None, gap=0, cull=True, frame_per_picture=False):
     """The view records and slab layouts of the three-panel pictures of many frames, for ``Engine.render_views``: pure host
     code.  ``sizes`` [(H, W)] and ``counts`` (detections per frame, >= 1) describe a flush whose meshes lie frame after frame in
     one (sum counts, V, 3) array.  One (H, 3W, 3) picture per frame holding all its detections - ``each``: one per detection,
@@ -180,7 +233,10 @@ def plan_views(sizes, counts, each=False, pixel_budget=None, gap=0, cull=True):
     (3 H W per picture) stay under ``pixel_budget`` (None = ``engine.RENDER_PIXEL_BUDGET``); a picture is never split and a
     chunk holds at least one.  A chunk's frame slab holds the frames its pictures name, each once, back to back in frame order
     (``pack_frames`` of those frames); its output slab holds its pictures back to back, ``gap`` bytes apart.
-    -> a list of chunks, each a dict: ``frames`` (the frame indices of its frame slab), ``in_bytes``, ``pictures``
+    ``frame_per_picture``: the frame slab holds one copy of the frame PER PICTURE instead, in picture order - what ``each``
+    needs when something is drawn into the frames per detection (the 2D skeletons).
+    -> a list of chunks, each a dict: ``frames`` (the frame indices of its frame slab), ``frame_dets`` (one [first detection,
+    count] per slab frame: the detections of the pictures that read it), ``in_bytes``, ``pictures``
     [(frame, detection or None)], ``picture_offsets`` (byte offset of each picture in the output slab), ``out_bytes``,
     ``geom`` (n, 5) int32 [H, W, mesh0, count, flags], ``offsets`` (n, 4) int64 [in_offset, in_pitch, out_offset, out_pitch],
     ``view_frame`` (n,) the frame whose camera view v takes."""
@@ -206,22 +262,28 @@ def plan_views(sizes, counts, each=False, pixel_budget=None, gap=0, cull=True):
     chunks.append(cur)
     out = []
     for pics in chunks:
-        frames = sorted({f for f, _ in pics})
-        in_off, off = {}, 0
+        dets_of = lambda f, i: (int(first[f]), counts[f]) if i is None else (int(first[f]) + i, 1)
+        if frame_per_picture:
+            frames, frame_dets, slot = [f for f, _ in pics], [dets_of(f, i) for f, i in pics], list(range(len(pics)))
+        else:
+            frames = sorted({f for f, _ in pics})
+            frame_dets, slot = [dets_of(f, None) for f in frames], [frames.index(f) for f, _ in pics]
+        in_off, off = [], 0
         for f in frames:
-            in_off[f] = off
+            in_off.append(off)
             off += sizes[f][0] * sizes[f][1] * 3
         geom, offsets, view_frame, pic_off, o = [], [], [], [], 0
-        for f, i in pics:
+        for (f, i), sl in zip(pics, slot):
             H, W = sizes[f]
-            mesh0, count = (int(first[f]), counts[f]) if i is None else (int(first[f]) + i, 1)
+            mesh0, count = dets_of(f, i)
             pic_off.append(o)
             for k, (m0, cnt, flags) in enumerate(((0, 0, 0), (mesh0, count, c), (mesh0, count, c | _lib.RENDER_SIDE_VIEW | _lib.RENDER_GROUND_PLANE))):
                 geom.append((H, W, m0, cnt, flags))
-                offsets.append((in_off[f], 3 * W, o + 3 * W * k, 9 * W))
+                offsets.append((in_off[sl], 3 * W, o + 3 * W * k, 9 * W))
                 view_frame.append(f)
             o += 9 * H * W + gap
-        out.append(dict(frames=frames, in_bytes=off, pictures=pics, picture_offsets=pic_off, out_bytes=o - gap,
+        out.append(dict(frames=frames, frame_dets=np.asarray(frame_dets, np.int64).reshape(-1, 2), frame_offsets=np.asarray(in_off, np.int64),
+                        in_bytes=off, pictures=pics, picture_offsets=pic_off, out_bytes=o - gap,
                         geom=np.asarray(geom, np.int32), offsets=np.asarray(offsets, np.int64), view_frame=np.asarray(view_frame, np.int64)))
     return out
 
@@ -236,7 +298,7 @@ def view_cams(view_frame, rotations, focals, centers) -> np.ndarray:
 
 
 def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, centers, cam_params=None, each=False, mesh_color='pinkish',
-                        faces=None, pixel_budget=None, device=None, engine=None, return_slabs=False):
+                        faces=None, pixel_budget=None, device=None, engine=None, return_slabs=False, keypoints_2d=None):
     """``render_image_group`` for the frames of a flush in one call per chunk (``specmi_render_views``): ``frames`` a list of
     (H, W, 3) host images of any sizes, ``vertices`` (sum counts, V, 3) / ``cam_t`` (sum counts, 3) the detections frame after
     frame (device tensors stay on the device), ``counts`` the detections per frame, ``rotations`` (F, 3, 3), ``focals`` (F, 2),
@@ -245,7 +307,10 @@ def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, cent
     up in ONE slab, ONE ``render_views`` call draws every panel of every picture in place, and ONE slab comes down.
     -> the list of (H, 3W, 3) uint8 host arrays, one per frame - ``each``: one per detection, that detection alone -, equal byte
     for byte to ``render_image_group`` on the same frame and meshes.  ``return_slabs``: also [(device slab, picture offsets,
-    [(H, 3W)])] per chunk."""
+    [(H, 3W)])] per chunk.  ``keypoints_2d`` (sum counts, J, D), the detections' 2D keypoints in pixels of their frames (a device
+    tensor stays on the device): drawn into each chunk's frame slab by ONE ``draw_skeletons`` call before the chunk's
+    ``render_views`` call, as ``render_image_group(keypoints_2d=...)`` draws them per frame - the same bytes; with ``each`` the
+    slab holds one copy of a frame per picture and each picture shows its own detection's skeleton alone."""
     from . import cam_utils
     from .preprocess import pack_frames
     frames = list(frames)
@@ -261,9 +326,17 @@ def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, cent
         raise ValueError('vertices must be (sum of counts, V, 3)')
     table, rgb = device_faces(faces, eng.device), _rgb(mesh_color)
     sizes = [p.shape[:2] for p in panel0]
+    if keypoints_2d is not None:
+        keypoints_2d = _keypoints(keypoints_2d, eng.device)
+        if keypoints_2d.shape[0] != vertices.shape[0]:
+            raise ValueError('keypoints_2d must be (sum of counts, J, D)')
     pictures, slabs = [], []
-    for ch in plan_views(sizes, counts, each=each, pixel_budget=pixel_budget, cull=_closed(faces)):
+    for ch in plan_views(sizes, counts, each=each, pixel_budget=pixel_budget, cull=_closed(faces), frame_per_picture=each and keypoints_2d is not None):
         in_slab, _, _ = pack_frames([panel0[f] for f in ch['frames']], eng.device)
+        if keypoints_2d is not None:
+            hw = np.asarray([sizes[f] for f in ch['frames']], np.int64).reshape(-1, 2)
+            eng.draw_skeletons(keypoints_2d, in_slab, np.concatenate([hw, ch['frame_dets']], axis=1),
+                               np.stack([ch['frame_offsets'], 3 * hw[:, 1]], axis=1))
         out_slab = torch.empty(ch['out_bytes'], device=eng.device, dtype=torch.uint8)
         eng.render_views(vertices, table, cam_t, ch['geom'], ch['offsets'], view_cams(ch['view_frame'], rotations, focals, centers),
                          in_slab, out_slab, rgb=rgb)

@@ -174,24 +174,26 @@ class SPECTester:
                                  assets.faces())
         return written
 
-    def _render_frame(self, img_fname, rgb, vertices, cam_t, output_path, output_img_folder):
+    def _render_frame(self, img_fname, rgb, vertices, cam_t, output_path, output_img_folder, keypoints=None):
         """``spec/tester.py:165-201`` for one frame: ``vertices`` (n, V, 3) / ``cam_t`` (n, 3) as the step left them on the device.
         The render rotation is ``batch_euler2matrix([-pitch, 0, roll])`` = Rx(-pitch) Rz(roll) (:169-171), the focal length the
-        frame's f_pix, the centre (W // 2, H // 2) (:175).  -> the files written."""
+        frame's f_pix, the centre (W // 2, H // 2) (:175).  ``keypoints`` (n, 49, 2): the detections' 2D skeletons, drawn on the device
+        (``args.draw_keypoints``).  -> the files written."""
         from PIL import Image
         rot, focal, center, cam_params = self._frame_camera(img_fname, rgb.shape, output_path)
-        group = render.render_image_group(rgb, cam_t, vertices, rot, focal, center, cam_params=cam_params, device=self.device)
+        group = render.render_image_group(rgb, cam_t, vertices, rot, focal, center, cam_params=cam_params, device=self.device, keypoints_2d=keypoints)
         return self._write_pictures(img_fname, [Image.fromarray(group.cpu().numpy())] * vertices.shape[0], vertices, output_path, output_img_folder)
 
-    def _render_flush(self, pending, frames, vertices, cam_t, output_path, output_img_folder, each):
+    def _render_flush(self, pending, frames, vertices, cam_t, output_path, output_img_folder, each, keypoints=None):
         """``_render_frame`` for every frame of a flush in one ``render_image_groups`` call: ``pending`` [(image, first crop,
         crops)] and ``frames`` (the RGB arrays) in the same order, ``vertices`` / ``cam_t`` the flush's detections on the device.
-        Same file names, same bytes; ``each``: file i of a frame shows detection i alone (spec/tester.py:181-201)."""
+        Same file names, same bytes; ``each``: file i of a frame shows detection i alone (spec/tester.py:181-201) - with
+        ``keypoints`` (the flush's (k, 49, 2) 2D joints) its own skeleton alone."""
         from PIL import Image
         cams = [self._frame_camera(f, rgb.shape, output_path) for (f, _, _), rgb in zip(pending, frames)]
         counts = [n for _, _, n in pending]
         groups = render.render_image_groups(frames, vertices, cam_t, counts, [c[0] for c in cams], [c[1] for c in cams], [c[2] for c in cams],
-                                            cam_params=[c[3] for c in cams], each=each, device=self.device)
+                                            cam_params=[c[3] for c in cams], each=each, device=self.device, keypoints_2d=keypoints)
         written, g = [], 0
         for img_fname, k0, n in pending:
             pictures = [Image.fromarray(p) for p in groups[g:g + n]] if each else [Image.fromarray(groups[g])] * n
@@ -225,7 +227,10 @@ class SPECTester:
         are drawn by ONE ``render.render_image_groups`` call - one slab up, one ``specmi_render_views`` call, one slab down per
         chunk - instead of one ``render_image_group`` per frame.  Same file names, same bytes.  ``args.render_each`` (implies the
         batched route): file ``{stem}_{i:06d}`` shows detection i alone, as the reference draws it, instead of the frame's
-        detections together."""
+        detections together.  ``args.draw_keypoints``: the predicted ``smpl_joints2d`` of each frame's detections are drawn onto
+        the frame as 2D skeletons before the mesh is laid over it (``render.draw_skeleton``: on the device, this project's own
+        drawing contract), on both routes; with ``render_each`` each picture shows its own detection's skeleton alone.  Off by
+        default: the pictures are then unchanged."""
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         image_file_names = list_images(image_folder)
@@ -256,6 +261,7 @@ class SPECTester:
         save = not getattr(self.args, 'no_save', False)
         render = not getattr(self.args, 'no_render', True)            # absent = no pictures, as before there were any
         render_each = bool(getattr(self.args, 'render_each', False))
+        draw_kp = bool(getattr(self.args, 'draw_keypoints', False))
         render_batch = render_each or flow_render_batch(self._render_batch)     # the per-detection pictures come from the batched call only
         if render and output_img_folder is None:
             raise ValueError('no_render is false: output_img_folder must name the folder the pictures go to')
@@ -272,13 +278,14 @@ class SPECTester:
                 held.clear()
             output = self.model(buf['inp_images'][:k], cam_rotmat=R[:k], cam_intrinsics=K[:k], bbox_scale=buf['bbox_scale'][:k],
                                 bbox_center=buf['bbox_center'][:k], img_w=img_w[:k], img_h=img_h[:k])
+            joints2d = output['smpl_joints2d'][:k].contiguous() if render and draw_kp else None      # (k, 49, 2), full-image pixels
             if render and render_batch:
                 self._render_flush(pending, [shown.pop(f) for f, _, _ in pending], output['smpl_vertices'][:k], output['pred_cam_t'][:k],
-                                   output_path, output_img_folder, render_each)
+                                   output_path, output_img_folder, render_each, keypoints=joints2d)
             elif render:
                 for img_fname, k0, n in pending:
                     self._render_frame(img_fname, shown.pop(img_fname), output['smpl_vertices'][k0:k0 + n], output['pred_cam_t'][k0:k0 + n],
-                                       output_path, output_img_folder)
+                                       output_path, output_img_folder, keypoints=None if joints2d is None else joints2d[k0:k0 + n])
             output = {key: v.cpu().numpy() for key, v in output.items()}          # ONE device->host hand-over per batch
             if save:
                 import joblib
