@@ -645,6 +645,46 @@ int specmi_draw_skeletons(specmi_handle* h, const float* kp, int Mtot, int J, in
                           const specmi_draw_style* style, uint8_t* slab, size_t slab_bytes, const int32_t* frame_geom,
                           const int64_t* frame_offsets, int nframes, void* stream);
 
+/* BASELINE JPEG FILES encoded on the device, all pictures of a flush in one fixed sequence of launches: replaces the download
+ * of the raw pictures and the host encoder behind every picture the flows write (cv2.imwrite / PIL's save in
+ * spec/utils/renderer_cam.py:213-216, spec/tester.py:188-201, camcalib/datagen/generateCalibrationDataset.py:131-132) - the
+ * encoded bytes come down instead, and the host only writes files.  Works on a handle of any model kind, committed or not.
+ * DEVICE pointers: in_slab, uint8 RGB, of in_slab_bytes - the slab and offsets convention of specmi_render_views: its output
+ * slab (three-panel pictures at pitch 9 W) is valid input, and so is what spec_amd.preprocess.pack_frames builds; out_slab,
+ * uint8, of out_slab_bytes, which must not overlap in_slab; sizes (n int64).  HOST: THE PICTURE RECORD, two arrays with one
+ * row per picture:
+ *   pic_geom    (n x 2 int32):  H, W
+ *   pic_offsets (n x 4 int64):  in_offset (byte offset of the picture's first pixel in in_slab), in_pitch (bytes from one row
+ *                               to the next, >= 3 W), out_offset (where its file begins in out_slab), out_capacity (bytes it
+ *                               may take there)
+ * and ONE quality (1 .. 100) for the call.
+ * THE CONTRACT (stated in full at the head of spec_amd/csrc/jpeg.hip, restated in NumPy in tests/jpeg_ref.py): picture i's file
+ * is, byte for byte, what PIL.Image.fromarray(a).save(f, format='JPEG', quality=q, optimize=False, progressive=False) writes on
+ * a libjpeg-turbo build of Pillow - baseline sequential, 4:2:0, the Annex-K Huffman tables, no restart markers; quality 75 is a
+ * plain .save(path).  sizes[i] ALWAYS receives the file's true length.  A picture whose length exceeds its capacity has nothing
+ * written at or beyond out_offset + out_capacity and is otherwise unspecified; the call still returns SPECMI_OK: the caller reads
+ * sizes and encodes that picture again with enough room.  Bytes of out_slab outside [out_offset, out_offset + sizes[i]) of the
+ * pictures that fit are not touched.  The result does not depend on scheduling.
+ * One memset and seven launches, whatever n and the picture sizes are.
+ * Refused (SPECMI_ERR_ARG), launching nothing: a null pointer; n outside [1, 65535]; quality outside [1, 100]; H or W outside
+ * [1, 32768]; a pitch below 3 W; a picture rectangle that leaves in_slab; a capacity below the header's 623 bytes; an output
+ * range that leaves out_slab; overlapping slabs; two output ranges that share a byte; more than 2^24 blocks of 16 x 16 pixels in
+ * all.
+ * The picture records and the quality's tables (header, divisors, Huffman codes, built on the host) live in one device table
+ * owned by the handle, under the rule of the ragged calls above: a call whose records or quality differ from the previous
+ * call's rewrites the table and therefore first SYNCHRONISES THE WHOLE DEVICE, and cannot be made while a stream is being
+ * captured (SPECMI_ERR_STATE; the stream is asked first, so the capture stays valid and nothing is enqueued); a call that
+ * repeats them does neither and can be captured.  The workspace is one per handle (growth synchronises the device): 7.9 bytes
+ * per pixel of the pictures rounded up to whole 16 x 16 blocks - 768 bytes of coefficients, 1248 of unstuffed scan (its worst
+ * case) and 4 of bit count per block - plus 12 bytes per chunk of 256 blocks or 4096 scan bytes and 8 per picture. */
+int specmi_jpeg_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_bytes, uint8_t* out_slab, size_t out_slab_bytes,
+                       const int32_t* pic_geom, const int64_t* pic_offsets, int n, int quality, int64_t* sizes, void* stream);
+
+/* The 623 header bytes of such a file - SOI, APP0 (JFIF 1.01), two DQT, SOF0, four DHT, SOS - for a quality and a size, into
+ * `out` (HOST, of `capacity` >= 623 bytes).  Host only: needs no handle and no device.  SPECMI_ERR_ARG for a null pointer, a
+ * quality outside [1, 100], H or W outside [1, 32768] or a capacity below 623. */
+int specmi_jpeg_header(int quality, int H, int W, uint8_t* out, size_t capacity);
+
 /* ---- evaluation metrics on the path's outputs ---------------------------------- */
 
 /* eval_single (spec/utils/compute_error.py:52-86, spec/trainer.py:272-316): joints =

@@ -14,6 +14,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only render             # mesh overlay + side view, 8 meshes on a 1080p frame, both raster launch shapes -> profiles/render_aux.json
     python scripts/bench_aux.py --only render_batch       # the pictures of a 32-frame flush, per-frame loop against the batched call -> profiles/render_batch_aux.json
     python scripts/bench_aux.py --only draw               # the 2D skeletons of a 1080p frame and of a 64-frame flush, next to render_views for the same flush -> profiles/draw_skeletons_aux.json
+    python scripts/bench_aux.py --only jpeg_encode        # pictures to JPEG files: device encode + download of the bytes against raw download + Pillow -> profiles/jpeg_encode_aux.json
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
     python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
@@ -551,6 +552,105 @@ def draw_section(eng, a):
     return out
 
 
+def jpeg_section(eng, a):
+    """Pictures on the device to JPEG files on the host, two routes alternated in this process (wall clock with the copies, 3
+    rounds): DEVICE = ``Engine.jpeg_encode`` (``specmi_jpeg_encode``, then the sizes and the files' bytes come down), HOST = the raw
+    pictures come down and Pillow encodes each.  Workloads: (1) eight 1080 x 5760 three-panel pictures as ``render_image_groups``
+    draws them from seeded 1080p frames (smooth fields with noise, two meshes each), quality 75 - the demo's files; (2) twelve
+    600 x 800 views of the same kind of content, quality 95 - ``write_tree``'s files.  Per kernel (library profiler, HIP events):
+    its time next to the bytes the stage must move, computed here from the shapes and the files' lengths."""
+    import io
+    import time
+    from PIL import Image
+    from spec_amd import _lib, render
+    dev = eng.device
+    v8, f, t8, _, _, _ = render_workload()
+    rng = np.random.default_rng(0)
+
+    def frame(H, W):
+        yy, xx = np.mgrid[0:H, 0:W]
+        ph = rng.uniform(0, 6.28, (3, 4))
+        img = np.stack([127 + 60 * np.sin(xx / 97.0 + p[0]) * np.cos(yy / 71.0 + p[1]) + 40 * np.sin((xx + yy) / 23.0 + p[2]) + 20 * np.cos(yy / 9.0 + p[3])
+                        for p in ph], -1)
+        return np.clip(img + rng.normal(0, 6, img.shape), 0, 255).astype(np.uint8)
+
+    def workload(name):
+        if name == 'demo_pictures':
+            F, (H, W), q = 8, (1080, 1920), 75
+            frames = [frame(H, W) for _ in range(F)]
+            verts = torch.from_numpy(np.concatenate([v8[:2]] * F)).to(dev)
+            cam_t = torch.from_numpy(np.concatenate([t8[2:4]] * F)).to(dev)
+            _, slabs = render.render_image_groups(frames, verts, cam_t, [2] * F, [np.eye(3, dtype=np.float32)] * F, [(1200., 1200.)] * F, [(W / 2, H / 2)] * F,
+                                                  faces=torch.from_numpy(f).to(dev), engine=eng, return_slabs=True)
+            assert len(slabs) == 1
+            slab, offs, shapes = slabs[0]
+            return slab, [tuple(sh) for sh in shapes], [(int(o), 3 * sh[1]) for o, sh in zip(offs, shapes)], q
+        pics = [frame(600, 800) for _ in range(12)]
+        return torch.from_numpy(np.concatenate([p_.reshape(-1) for p_ in pics])).to(dev), [(600, 800)] * 12, [(k * 600 * 800 * 3, 2400) for k in range(12)], 95
+
+    def wall(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, r
+
+    out = {}
+    for name in ('demo_pictures', 'tree_views'):
+        slab, geom, offsets, q = workload(name)
+        n, px = len(geom), sum(h * w for h, w in geom)
+
+        def device_route():
+            return eng.jpeg_encode(slab, geom, offsets, q)
+
+        def host_route():
+            raw = slab.cpu().numpy()
+            files = []
+            for (h, w), (o, pitch) in zip(geom, offsets):
+                b = io.BytesIO()
+                Image.fromarray(raw[o:o + h * pitch].reshape(h, w, 3)).save(b, format='JPEG', quality=q, optimize=False, progressive=False)
+                files.append(b.getvalue())
+            return files
+
+        fd, fh = device_route(), host_route()
+        same = fd == fh
+        rounds = {'device': [], 'host': []}
+        reps = max(2, min(a.iters, 5))
+        for _ in range(3):                                              # alternated: both see the same clocks and the same neighbours
+            ms = {'device': [], 'host': []}
+            for _ in range(reps):
+                ms['device'].append(wall(device_route)[0])
+                ms['host'].append(wall(host_route)[0])
+            for k, v in ms.items():
+                rounds[k].append(float(np.median(v)) / n)
+        med = {k: float(np.median(v)) for k, v in rounds.items()}
+        spread = max(rounds['host']) - min(rounds['host'])
+        file_bytes = sum(len(x) for x in fd)
+        mcus = sum(-(-h // 16) * -(-w // 16) for h, w in geom)
+        scan = file_bytes - n * 625                                      # stuffed scan bytes: an upper bound of the unstuffed ones
+        must = {'jpeg_zero': mcus * 1248, 'jpeg_dct': 3 * px + mcus * 768, 'jpeg_count': mcus * 768 + mcus * 4, 'jpeg_scan_bits': (mcus // 256 + n) * 12,
+                'jpeg_write': mcus * 768 + mcus * 4 + scan, 'jpeg_ffcount': scan, 'jpeg_scan_ff': (mcus * 1248 // 4096 + n) * 12, 'jpeg_pack': 2 * scan + n * 625}
+        kern = {}
+        cap = [3 * h * w + 1024 for h, w in geom]
+        oo = np.concatenate([[0], np.cumsum(cap)])
+        ws_out = torch.empty(int(oo[-1]), device=dev, dtype=torch.uint8)
+        full = [(o, p_, int(x), c) for (o, p_), x, c in zip(offsets, oo[:-1], cap)]
+        total_ms = 0.0
+        for k, (ms_, _, _, nl) in timed(eng, lambda: eng.jpeg_encode_into(slab, ws_out, geom, full, q), a.iters).items():
+            kern[k] = {'ms_per_launch': round(ms_, 4), 'must_move_MB': round(must.get(k, 0) / 1e6, 3),
+                       'frac_of_hbm_peak': round(must.get(k, 0) / (ms_ * 1e-3) / HBM_PEAK, 4), 'launches_per_call': nl}
+            total_ms += ms_ * nl
+        row = {'workload': f'{n} pictures of {geom[0][0]} x {geom[0][1]}, quality {q}, {px / 1e6:.1f} Mpx in all', 'byte_identical': bool(same),
+               'ms_per_picture_rounds': {k: [round(x, 3) for x in v] for k, v in rounds.items()}, 'ms_per_picture_median': {k: round(v, 3) for k, v in med.items()},
+               'host_spread_between_rounds_ms': round(spread, 3), 'ratio_host_over_device': round(med['host'] / med['device'], 2),
+               'device_not_slower_beyond_the_spread': bool(med['device'] <= med['host'] + spread),
+               'bytes_moved_device_to_host': {'device_route': file_bytes + 8 * n, 'host_route': int(slab.numel())},
+               'kernels': kern, 'kernels_ms_per_call': round(total_ms, 4), 'kernels_ms_per_picture': round(total_ms / n, 4),
+               'kernels_frac_of_hbm_peak': round(sum(must.values()) / (total_ms * 1e-3) / HBM_PEAK, 4)}
+        out[name] = row
+        print(json.dumps(row, indent=1))
+        del slab, ws_out
+        torch.cuda.empty_cache()
+    return out
+
+
 def hmr_loss_section(eng, a, add):
     """``specmi_hmr_loss`` in HMRCamLoss mode with the per-vertex L1 term on: 2 * B * 6890 * 3 floats per call, at the batch of the
     evaluation config (64) and at ``--batch``."""
@@ -570,7 +670,7 @@ def hmr_loss_section(eng, a, add):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode'], default=None, help='run one section only')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -644,6 +744,15 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the same calls; 3 alternated rounds',
                        'draw': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'jpeg_encode':
+        from spec_amd import _lib
+        rows = jpeg_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'routes: wall clock with the copies, 3 alternated rounds, ms per '
+                       'picture; kernels: per-launch HIP events (library profiler)', 'jpeg_encode': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     if a.only == 'ragged_crops':

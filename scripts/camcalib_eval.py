@@ -40,6 +40,8 @@ def main():
     ap.add_argument('--views-per-pano', type=int, default=12)
     ap.add_argument('--seed', type=int, default=0, help='seed of the camera sampler (--panoramas)')
     ap.add_argument('--write-tree', type=str, default=None, metavar='OUT', help='with --panoramas: also write the views as a pano_scalenet tree')
+    ap.add_argument('--device-jpeg', action='store_true', help="with --write-tree: encode a panorama's views on the device in one call and "
+                    "download only the files' bytes (the same bytes as Pillow's; default: engine.JPEG_DEVICE_DEFAULT)")
     args = ap.parse_args()
     import torch
     torch.set_grad_enabled(False)
@@ -57,7 +59,8 @@ def main():
         from spec_amd import panorama
         dataset = panorama.PanoViewDataset(panorama.list_panoramas(args.panoramas), args.views_per_pano, args.seed)
         if args.write_tree:
-            panorama.write_tree(dataset, args.write_tree, while_evaluating=True)     # every view is generated once
+            panorama.write_tree(dataset, args.write_tree, while_evaluating=True,      # every view is generated once
+                                jpeg_device=True if args.device_jpeg else None)
     res = ce.run_evaluation(hp, data_root=root, ckpt=args.ckpt, dataset=dataset)
     if args.report:
         rep = {k: (v.tolist() if hasattr(v, 'tolist') else v) for k, v in res.items() if k != 'logits'}

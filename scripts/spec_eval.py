@@ -80,11 +80,16 @@ def main():
     ap.add_argument('--save-images', action='store_true', help='one three-panel picture (full image with the 2D keypoints and horizon line | mesh '
                     'overlay | side view) of the first image of every TESTING.SAVE_FREQ-th batch under LOG_DIR/output_images: sets '
                     'TESTING.SAVE_IMAGES and TRAINING.SAVE_IMAGES (the reference writes the files only with both)')
+    ap.add_argument('--device-jpeg', action='store_true', help='with --save-images: encode .jpg / .jpeg pictures on the device and download '
+                    "only the files' bytes (the same bytes as Pillow's; default: engine.JPEG_DEVICE_DEFAULT)")
     ap.add_argument('--report', type=str, default=None, metavar='eval.json',
                     help='write the scores and the delta against the reference README table (README.md:155-159) as JSON; the exit '
                          'code is 3 when |delta W-MPJPE| > 0.1 mm on a dataset the table lists (use on the real assets)')
     args = ap.parse_args()
     torch.set_grad_enabled(False)
+    if args.device_jpeg:
+        from spec_amd import engine
+        engine.JPEG_DEVICE_DEFAULT = True
     if args.synthetic:
         return synthetic(args)
     from spec_amd import evaluation

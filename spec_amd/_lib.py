@@ -34,6 +34,7 @@ PRECISION_FP32, PRECISION_FP16 = 0, 1       # SPECMI_PRECISION_* (include/specmi
 MODEL_CAMCALIB, MODEL_HMR, MODEL_SMPL = 0, 1, 2
 RENDER_SIDE_VIEW, RENDER_GROUND_PLANE, RENDER_CULL, RENDER_THREAD_PER_TRIANGLE = 1, 2, 4, 8     # SPECMI_RENDER_* (include/specmi.h)
 DRAW_MAX_SIDE, DRAW_MAX_COORD, DRAW_MAX_RADIUS, DRAW_MAX_THICKNESS = 8192, 16383, 64, 64      # the limits of specmi_draw_skeletons (include/specmi.h)
+JPEG_HEADER_BYTES = 623                       # what specmi_jpeg_header writes; the least capacity of specmi_jpeg_encode (include/specmi.h)
 HMR_LOSS, HMR_CAM_LOSS = 0, 1                 # SPECMI_HMR_LOSS / SPECMI_HMR_CAM_LOSS (include/specmi.h)
 # the ground-truth tensors of specmi_hmr_loss in the order of its prototype, per-image shapes (None = (V, 3)); int32 where named has_*
 HMR_LOSS_GT = (('pose', (72,)), ('betas', (10,)), ('pose_conf', (24,)), ('pose_3d', (24, 4)), ('keypoints', (49, 3)), ('vertices', None),
@@ -184,6 +185,10 @@ PROTOTYPES = {
     # (h, kp, Mtot, J, D, bones, NB, style, slab, slab_bytes, frame_geom, frame_offsets, nframes, stream)
     'specmi_draw_skeletons': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_int32_p, C.c_int, C.POINTER(DrawStyle), C.c_void_p,
                                         C.c_size_t, c_int32_p, c_int64_p, C.c_int, C.c_void_p]),
+    # (h, in_slab, in_bytes, out_slab, out_bytes, pic_geom, pic_offsets, n, quality, sizes, stream)
+    'specmi_jpeg_encode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_int32_p, c_int64_p, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p]),
+    'specmi_jpeg_header': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     'specmi_camcalib_eval': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -806,6 +806,8 @@ int specmi_destroy(specmi_handle* h) {
     if (h->render_ws) (void)hipFree(h->render_ws);
     if (h->views_tab) (void)hipFree(h->views_tab);
     if (h->draw_tab) (void)hipFree(h->draw_tab);
+    if (h->jpeg_tab) (void)hipFree(h->jpeg_tab);
+    if (h->jpeg_ws) (void)hipFree(h->jpeg_ws);
     hrnet_free(h->hrnet);
     delete h;
     return SPECMI_OK;
@@ -1832,6 +1834,83 @@ int specmi_draw_skeletons(specmi_handle* h, const float* kp, int Mtot, int J, in
     a.rgb[0] = pack(st.joint_rgb); a.rgb[1] = pack(st.bone_rgb[0]); a.rgb[2] = pack(st.bone_rgb[1]);
     LaunchCtx ctx{s, &h->prof, "render.skeletons"};
     LAUNCHCHK(h, launch_draw_skeletons(a, (int)tiles, kp_bytes, px, ctx), "draw_skeletons");
+    return SPECMI_OK;
+}
+
+int specmi_jpeg_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_bytes, uint8_t* out_slab, size_t out_slab_bytes,
+                       const int32_t* pic_geom, const int64_t* pic_offsets, int n, int quality, int64_t* sizes, void* stream) {
+    ENTER(h);
+    if (!in_slab || !out_slab || !pic_geom || !pic_offsets || !sizes) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (n <= 0 || n > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 pictures per call, got %d", n);
+    if (quality < 1 || quality > 100) return fail(h, SPECMI_ERR_ARG, "quality %d (1 .. 100)", quality);
+    if ((const uint8_t*)out_slab < in_slab + in_slab_bytes && in_slab < (const uint8_t*)out_slab + out_slab_bytes)
+        return fail(h, SPECMI_ERR_ARG, "the picture slab and the output slab overlap");
+    // [n records | JpegTables]
+    std::vector<int> tab((size_t)n * kJpegPicRec + sizeof(JpegTables) / 4, 0);
+    std::vector<std::pair<long long, long long>> outs((size_t)n);       // first byte, capacity
+    long long mcus = 0, mchunks = 0, bchunks = 0;
+    double px = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const int H = pic_geom[2 * i], W = pic_geom[2 * i + 1];
+        const int64_t in_off = pic_offsets[4 * i], in_pitch = pic_offsets[4 * i + 1], out_off = pic_offsets[4 * i + 2], cap = pic_offsets[4 * i + 3];
+        if (H < 1 || W < 1 || H > 32768 || W > 32768) return fail(h, SPECMI_ERR_ARG, "picture %d: %d x %d pixels (1 .. 32768 per side)", i, H, W);
+        if (in_pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "picture %d: a pitch of %lld bytes for rows of %d", i, (long long)in_pitch, 3 * W);
+        if (in_off < 0 || (double)in_off + (double)(H - 1) * (double)in_pitch + 3.0 * W > (double)in_slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "picture %d: its rectangle leaves the slab of %zu bytes", i, in_slab_bytes);
+        if (cap < kJpegHeaderBytes) return fail(h, SPECMI_ERR_ARG, "picture %d: a capacity of %lld bytes is below the header's %d", i, (long long)cap, kJpegHeaderBytes);
+        if (out_off < 0 || (double)out_off + (double)cap > (double)out_slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "picture %d: its output leaves the slab of %zu bytes", i, out_slab_bytes);
+        JpegPic r{};
+        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal pictures give equal records
+        r.in_off = in_off; r.in_pitch = H > 1 ? in_pitch : 3LL * W; r.out_off = out_off; r.cap = cap;
+        r.H = H; r.W = W; r.mx = (W + 15) / 16; r.my = (H + 15) / 16;
+        r.mcu0 = (int)mcus; r.mchunk0 = (int)mchunks; r.bchunk0 = (int)bchunks;
+        const long long m = (long long)r.mx * r.my;
+        mcus += m;
+        mchunks += (m + kJpegMcuChunk - 1) / kJpegMcuChunk;
+        bchunks += (m * kJpegMcuBytes + kJpegByteChunk - 1) / kJpegByteChunk;
+        px += (double)H * W;
+        if (mcus > kJpegMaxMcus) return fail(h, SPECMI_ERR_ARG, "the pictures hold more than 2^24 blocks of 16 x 16 pixels");
+        std::memcpy(tab.data() + (size_t)i * kJpegPicRec, &r, sizeof(r));
+        outs[i] = {out_off, cap};
+    }
+    std::sort(outs.begin(), outs.end());
+    for (int i = 0; i + 1 < n; ++i)
+        if (outs[i].first + outs[i].second > outs[i + 1].first) return fail(h, SPECMI_ERR_ARG, "two outputs share a byte (at offset %lld)", outs[i + 1].first);
+    JpegTables tables;
+    jpeg_build_tables(quality, &tables);
+    std::memcpy(tab.data() + (size_t)n * kJpegPicRec, &tables, sizeof(tables));
+    hipStream_t s = (hipStream_t)stream;
+    size_t off[8];
+    const size_t need = jpeg_ws_layout(n, mcus, mchunks, bchunks, off);
+    const bool regrown = tab.size() * 4 > h->jpeg_tab_bytes;
+    if (need > h->jpeg_ws_bytes || regrown || tab != h->jpeg_host) {
+        // both need a whole-device synchronise, which would invalidate a capture under way on this stream: ask first and leave it valid
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone)
+            return fail(h, SPECMI_ERR_STATE, "new picture records, another quality or a larger encoder workspace are not possible while the stream "
+                        "is being captured: run one eager call with these records first (nothing was enqueued)");
+    }
+    int rc;
+    if ((rc = grow_ragged(h, &h->jpeg_ws, &h->jpeg_ws_bytes, need, "the JPEG workspace"))) return rc;
+    if ((rc = grow_ragged(h, (void**)&h->jpeg_tab, &h->jpeg_tab_bytes, tab.size() * 4, "the JPEG picture table"))) return rc;
+    if (regrown || tab != h->jpeg_host) {
+        // an encode enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
+        if (!regrown && (rc = sync_for_growth(h, "the JPEG picture table"))) return rc;
+        h->jpeg_host.swap(tab);
+        HIPCHK(h, hipMemcpyAsync(h->jpeg_tab, h->jpeg_host.data(), h->jpeg_host.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    char* ws = (char*)h->jpeg_ws;
+    JpegArgs a{};
+    a.in = in_slab; a.out = out_slab; a.sizes = (long long*)sizes;
+    a.pics = (const JpegPic*)h->jpeg_tab; a.tabs = (const JpegTables*)(h->jpeg_tab + (size_t)n * kJpegPicRec);
+    a.coef = (short*)(ws + off[0]); a.mcu_bits = (unsigned*)(ws + off[1]); a.mchunk_sum = (unsigned*)(ws + off[2]);
+    a.mchunk_base = (unsigned long long*)(ws + off[3]); a.pic_bits = (unsigned long long*)(ws + off[4]); a.bitbuf = (unsigned*)(ws + off[5]);
+    a.bchunk_ff = (unsigned*)(ws + off[6]); a.bchunk_base = (unsigned long long*)(ws + off[7]);
+    a.n = n; a.mcus = (int)mcus; a.mchunks = (int)mchunks; a.bchunks = (int)bchunks;
+    LaunchCtx ctx{s, &h->prof, "jpeg.encode"};
+    LAUNCHCHK(h, launch_jpeg_encode(a, px * 3, ctx), "jpeg_encode");
     return SPECMI_OK;
 }
 

@@ -183,6 +183,13 @@ struct specmi_handle {
     int* draw_tab = nullptr;
     size_t draw_tab_bytes = 0;
     std::vector<int> draw_host;         // host image of draw_tab as last uploaded
+    // specmi_jpeg_encode: the picture records and the quality's tables, same growth and upload rules as ragged_tab; coefficients,
+    // bit counts, the unstuffed scans and the chunk sums (jpeg_ws_layout), grows like ragged_tmp
+    int* jpeg_tab = nullptr;
+    size_t jpeg_tab_bytes = 0;
+    std::vector<int> jpeg_host;         // host image of jpeg_tab as last uploaded
+    void* jpeg_ws = nullptr;
+    size_t jpeg_ws_bytes = 0;
     SkWs sk;                            // split-K partial tiles + arrival counters (ensure_sk; never allocated under graph capture:
                                         // the warm-up call of a shape sizes it)
     std::vector<void*> sk_retired;      // outgrown split-K buffers, kept until destroy (captured graphs may still name them)

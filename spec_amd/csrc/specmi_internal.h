@@ -529,4 +529,48 @@ struct DrawArgs {
 int draw_frame_tiles(int H, int W, int* tiles_x);
 int launch_draw_skeletons(const DrawArgs& a, int total_tiles, double kp_bytes, double px, const LaunchCtx& ctx);
 
+// ----------------------------------------------------------------------------------------
+// baseline JPEG encoder  (jpeg.hip)
+// ----------------------------------------------------------------------------------------
+constexpr int kJpegHeaderBytes = 623;
+constexpr int kJpegMcuBytes = 1248;       // an MCU codes into at most 6 * (22 + 63 * 26) = 9960 bits = 1245 bytes; 1248 = 16 * 78
+constexpr int kJpegMcuChunk = 256;        // MCUs per workgroup of the counting and writing kernels
+constexpr int kJpegByteChunk = 4096;      // unstuffed scan bytes per workgroup of the stuffing kernels (16 per thread)
+constexpr long long kJpegMaxMcus = 1 << 24;
+// One picture of a specmi_jpeg_encode call as the device reads it (16 ints): the four byte fields of its record, its size, its
+// MCU grid, and where its MCUs, MCU chunks and byte chunks begin among the call's
+struct JpegPic { long long in_off, in_pitch, out_off, cap; int H, W, mx, my, mcu0, mchunk0, bchunk0, pad; };
+constexpr int kJpegPicRec = sizeof(JpegPic) / 4;
+// What a quality decides, built on the host (jpeg_build_tables): the divisors 8 Q in natural order (table 0 luma, 1 chroma), the
+// Annex-K codes and lengths by symbol, and the header with H = W = 0
+struct JpegTables {
+    unsigned short div[2][64];
+    unsigned short dc_code[2][12];
+    unsigned char dc_len[2][12];
+    unsigned short ac_code[2][256];
+    unsigned char ac_len[2][256];
+    unsigned char header[624];
+};
+static_assert(sizeof(JpegTables) % 4 == 0, "the tables follow the picture records in a table of ints");
+struct JpegArgs {
+    const unsigned char* in;
+    unsigned char* out;
+    const JpegPic* pics;
+    const JpegTables* tabs;
+    long long* sizes;                     // (n): every picture's true encoded length
+    short* coef;                          // (mcus, 6, 64) quantised coefficients in zigzag order
+    unsigned* mcu_bits;                   // (mcus)
+    unsigned* mchunk_sum;                 // (mchunks) bits of a chunk's MCUs
+    unsigned long long* mchunk_base;      // (mchunks) bits of the picture's chunks before it
+    unsigned long long* pic_bits;         // (n)
+    unsigned* bitbuf;                     // (mcus * kJpegMcuBytes / 4) the unstuffed scans as big-endian words, zeroed per call
+    unsigned* bchunk_ff;                  // (bchunks) 0xFF bytes of a byte chunk
+    unsigned long long* bchunk_base;      // (bchunks) 0xFF bytes of the picture's chunks before it
+    int n, mcus, mchunks, bchunks;
+};
+void jpeg_build_tables(int quality, JpegTables* t);
+// byte offsets of coef, mcu_bits, mchunk_sum, mchunk_base, pic_bits, bitbuf, bchunk_ff, bchunk_base in the workspace -> its size
+size_t jpeg_ws_layout(int n, long long mcus, long long mchunks, long long bchunks, size_t off[8]);
+int launch_jpeg_encode(const JpegArgs& a, double in_bytes, const LaunchCtx& ctx);
+
 }  // namespace specmi

@@ -203,16 +203,23 @@ class PanoViewDataset:
         return self.device_view(i).cpu().numpy()
 
 
-def write_tree(ds: PanoViewDataset, out_root: str, image_format: str = 'JPEG', log=print, while_evaluating: bool = False) -> str:
+def write_tree(ds: PanoViewDataset, out_root: str, image_format: str = 'JPEG', log=print, while_evaluating: bool = False,
+               jpeg_device=None) -> str:
     """The dataset as a 'pano_scalenet' tree under ``out_root`` (a data root: the tree is
     ``out_root/data/dataset_folders/pano_scalenet``): ``images/NAME.jpg`` as the reference saves it (quality 95, not optimised,
     not progressive; generateCalibrationDataset.py:131-132), ``images/NAME.json`` with the reference's fields (:149-158) and
     ``val_images.pkl``.  ``image_format`` is what Pillow encodes INTO the ``.jpg`` name (a lossless format takes the JPEG
     round trip out of a comparison; loaders go by content).  ``while_evaluating``: write ``val_images.pkl`` now and a
-    panorama's views when the dataset extracts them, so that an evaluation that follows generates every view once."""
+    panorama's views when the dataset extracts them, so that an evaluation that follows generates every view once.
+    ``jpeg_device`` (None = ``engine.JPEG_DEVICE_DEFAULT``) with ``image_format='JPEG'``: all views of a panorama are encoded in
+    ONE ``Engine.jpeg_encode`` call at quality 95 from the device slab they share, and only the files' bytes come down - the
+    same bytes.  Views that do not lie in a device slab (an extractor on the host) are encoded by Pillow as before."""
     import joblib
     from PIL import Image
+    from . import cam_utils
     from .camcalib_eval import DATASET_FOLDERS
+    from .engine import flow_jpeg_device
+    on_device = image_format == 'JPEG' and flow_jpeg_device(jpeg_device)
     folder = os.path.join(out_root, DATASET_FOLDERS['pano_scalenet'])
     os.makedirs(os.path.join(folder, 'images'), exist_ok=True)
     opts = {'quality': 95, 'optimize': False, 'progressive': False} if image_format == 'JPEG' else {}
@@ -222,10 +229,18 @@ def write_tree(ds: PanoViewDataset, out_root: str, image_format: str = 'JPEG', l
         if p in written:
             return
         written.add(p)
+        files, slab = None, getattr(views, 'slab', None)
+        if on_device and slab is not None and slab.device.type == 'cuda':
+            eng = ds.engine or cam_utils._engine(slab.device)
+            files = eng.jpeg_encode(views.slab, list(views.sizes), [(int(o), 3 * w) for o, (_, w) in zip(views.offsets, views.sizes)], opts['quality'])
         for k, v in enumerate(views):
             i = p * ds.views_per_pano + k
             path = os.path.join(folder, 'images', ds.imgname(i))
-            Image.fromarray(v.cpu().numpy()).save(path, format=image_format, **opts)
+            if files is not None:
+                with open(path, 'wb') as f:
+                    f.write(files[k])
+            else:
+                Image.fromarray(v.cpu().numpy()).save(path, format=image_format, **opts)
             with open(path.replace('.jpg', '.json'), 'w') as f:
                 json.dump(ds.json_fields(i, path), f)
         if len(written) == len(ds.pano_files):

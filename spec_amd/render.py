@@ -177,7 +177,7 @@ def draw_skeleton(image, kp_2d, dataset='spin', unnormalize=True, thickness=2, r
 
 def render_image_group(image, camera_translation, vertices, camera_rotation, focal_length, camera_center, mesh_color='pinkish',
                        alpha=1.0, faces=None, mesh_filename: Optional[str] = None, save_filename: Optional[str] = None, keypoints_2d=None,
-                       cam_params: Optional[Sequence] = None, device=None, engine=None):
+                       cam_params: Optional[Sequence] = None, device=None, engine=None, jpeg_device=None):
     """The three panels of ``render_image_group`` (renderer_cam.py:147-218) side by side, (H, 3W, 3) uint8 on the device:
 
     0. ``image`` (H, W, 3; uint8, or floats in [0, 1] / [0, 255] as the reference accepts) with - given ``cam_params`` =
@@ -193,7 +193,9 @@ def render_image_group(image, camera_translation, vertices, camera_rotation, foc
     launch sequence per panel (one mesh (V, 3) / (3,) is the reference's call).  ``mesh_filename``: the meshes after the 180
     degree turn as .obj (``NAME.obj``; ``NAME_<m>.obj`` from the second on) and the x-flipped translations as .npy
     (renderer_cam.py:74,87-90).  ``save_filename``: the image through Pillow (the reference's cv2.imwrite of the RGB-swapped
-    array stores the same pixels).  ``alpha`` is accepted and ignored: the reference's material is ``alphaMode='OPAQUE'``."""
+    array stores the same pixels); with ``jpeg_device`` (None = ``engine.JPEG_DEVICE_DEFAULT``) a ``.jpg`` / ``.jpeg`` name is
+    encoded on the device (``save_picture``: the same bytes, and only they come down).  ``alpha`` is accepted and ignored: the
+    reference's material is ``alphaMode='OPAQUE'``."""
     from . import cam_utils
     if isinstance(image, torch.Tensor):
         device = device or (image.device if image.device.type == 'cuda' else None)
@@ -217,10 +219,31 @@ def render_image_group(image, camera_translation, vertices, camera_rotation, foc
             write_obj(name, v[m] * np.array([1., -1., -1.], np.float32), table)
             np.save(name.replace('.obj', '.npy'), t[m])
     if save_filename is not None:
-        from PIL import Image
         os.makedirs(os.path.dirname(os.path.abspath(save_filename)), exist_ok=True)
-        Image.fromarray(out.cpu().numpy()).save(save_filename)
+        save_picture(save_filename, out, engine=eng, jpeg_device=jpeg_device)
     return out
+
+
+def save_picture(path: str, picture, engine=None, jpeg_device=None) -> str:
+    """``picture`` - an (H, W, 3) uint8 device tensor, or the ``bytes`` of a file encoded already - written to ``path``.  A
+    tensor goes through Pillow as before (``Image.fromarray(...).save(path)``) unless ``jpeg_device`` (None =
+    ``engine.JPEG_DEVICE_DEFAULT``) is on, the name is ``.jpg`` / ``.jpeg`` and the tensor lies on the device: then ``Engine.jpeg_encode`` encodes it where it
+    lies at Pillow's default quality 75 - byte for byte Pillow's file - and only those bytes come down."""
+    from . import cam_utils
+    from .engine import flow_jpeg_device, is_jpeg_name
+    if isinstance(picture, (bytes, bytearray)):
+        data = picture
+    elif flow_jpeg_device(jpeg_device) and is_jpeg_name(path) and picture.device.type == 'cuda':
+        eng = engine or cam_utils._engine(picture.device)
+        H, W = int(picture.shape[0]), int(picture.shape[1])
+        data = eng.jpeg_encode(picture.contiguous().view(-1), [[H, W]], [[0, 3 * W]], 75)[0]
+    else:
+        from PIL import Image
+        Image.fromarray(picture.cpu().numpy()).save(path)
+        return path
+    with open(path, 'wb') as f:
+        f.write(data)
+    return path
 
 
 def plan_views(sizes, counts, each=False, pixel_budget=None, gap=0, cull=True, frame_per_picture=False):
@@ -298,7 +321,8 @@ def view_cams(view_frame, rotations, focals, centers) -> np.ndarray:
 
 
 def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, centers, cam_params=None, each=False, mesh_color='pinkish',
-                        faces=None, pixel_budget=None, device=None, engine=None, return_slabs=False, keypoints_2d=None):
+                        faces=None, pixel_budget=None, device=None, engine=None, return_slabs=False, keypoints_2d=None, encode=None,
+                        quality=75):
     """``render_image_group`` for the frames of a flush in one call per chunk (``specmi_render_views``): ``frames`` a list of
     (H, W, 3) host images of any sizes, ``vertices`` (sum counts, V, 3) / ``cam_t`` (sum counts, 3) the detections frame after
     frame (device tensors stay on the device), ``counts`` the detections per frame, ``rotations`` (F, 3, 3), ``focals`` (F, 2),
@@ -310,13 +334,20 @@ def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, cent
     [(H, 3W)])] per chunk.  ``keypoints_2d`` (sum counts, J, D), the detections' 2D keypoints in pixels of their frames (a device
     tensor stays on the device): drawn into each chunk's frame slab by ONE ``draw_skeletons`` call before the chunk's
     ``render_views`` call, as ``render_image_group(keypoints_2d=...)`` draws them per frame - the same bytes; with ``each`` the
-    slab holds one copy of a frame per picture and each picture shows its own detection's skeleton alone."""
+    slab holds one copy of a frame per picture and each picture shows its own detection's skeleton alone.
+    ``encode``: None, 'jpeg', or one of the two per frame.  A picture of a 'jpeg' frame comes back as the ``bytes`` of its JPEG
+    file at ``quality`` instead of an array - encoded from the output slab where it lies by ONE ``Engine.jpeg_encode`` call per
+    chunk, byte for byte what ``Image.fromarray(array).save(f, format='JPEG', quality=quality)`` writes; the raw slab does not
+    come down (only the pictures of frames that are not encoded do, one by one)."""
     from . import cam_utils
     from .preprocess import pack_frames
     frames = list(frames)
     cam_params = [None] * len(frames) if cam_params is None else list(cam_params)
     if not (len(frames) == len(counts) == len(cam_params)):
         raise ValueError('one detection count (and one cam_params entry) per frame')
+    encode = [encode] * len(frames) if encode is None or isinstance(encode, str) else list(encode)
+    if len(encode) != len(frames) or any(e not in (None, 'jpeg') for e in encode):
+        raise ValueError("encode: None, 'jpeg', or one of the two per frame")
     panel0 = [group_panel0(im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else im, cp) for im, cp in zip(frames, cam_params)]
     dev = torch.device(device or (vertices.device if isinstance(vertices, torch.Tensor) and vertices.device.type == 'cuda' else 'cuda'))
     eng = engine or cam_utils._engine(dev)
@@ -340,9 +371,16 @@ def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, cent
         out_slab = torch.empty(ch['out_bytes'], device=eng.device, dtype=torch.uint8)
         eng.render_views(vertices, table, cam_t, ch['geom'], ch['offsets'], view_cams(ch['view_frame'], rotations, focals, centers),
                          in_slab, out_slab, rgb=rgb)
-        host = out_slab.cpu().numpy()
         shapes = [(sizes[f][0], 3 * sizes[f][1]) for f, _ in ch['pictures']]
-        pictures += [host[o:o + h * w3 * 3].reshape(h, w3, 3) for o, (h, w3) in zip(ch['picture_offsets'], shapes)]
+        coded = [k for k, (f, _) in enumerate(ch['pictures']) if encode[f] == 'jpeg']
+        if not coded:
+            host = out_slab.cpu().numpy()
+            pictures += [host[o:o + h * w3 * 3].reshape(h, w3, 3) for o, (h, w3) in zip(ch['picture_offsets'], shapes)]
+        else:
+            files = eng.jpeg_encode(out_slab, [shapes[k] for k in coded], [(ch['picture_offsets'][k], 3 * shapes[k][1]) for k in coded], quality)
+            got = dict(zip(coded, files))
+            for k, (o, (h, w3)) in enumerate(zip(ch['picture_offsets'], shapes)):
+                pictures.append(got[k] if k in got else out_slab[o:o + h * w3 * 3].cpu().numpy().reshape(h, w3, 3))
         slabs.append((out_slab, ch['picture_offsets'], shapes))
     return (pictures, slabs) if return_slabs else pictures
 

@@ -23,7 +23,7 @@ import torch
 from . import assets, cam_utils, io_formats, render
 from .checkpoint import load_pretrained_model, read_checkpoint
 from .modules import HMR, CameraRegressorNetwork
-from .engine import flow_image_dtype, flow_ragged_crops, flow_render_batch, image_tensor
+from .engine import flow_image_dtype, flow_jpeg_device, flow_ragged_crops, flow_render_batch, image_tensor, is_jpeg_name
 from .preprocess import camcalib_transform, crop_detections, crop_detections_ragged, pack_frames
 
 CAMCALIB_CKPT = 'data/camcalib/checkpoints/camcalib_sa_biased_l2.ckpt'     # scripts/camcalib_demo.py:39
@@ -102,6 +102,7 @@ class SPECTester:
         self._fp32_crops = None       # False: NHWC8 fp16 crops for a model at fp16; True: fp32 crops + in-trunk conversion (same bits)
         self._ragged_crops = None     # True: a flush's frames in one slab, one upload, one ragged crop launch; False: one of each per frame (same bits)
         self._render_batch = None     # True: a flush's pictures in one render_image_groups call; False: one render_image_group per frame (same bytes)
+        self._jpeg_device = None      # True: .jpg / .jpeg pictures are encoded on the device and only the files' bytes come down (same bytes)
 
     def _build_model(self):
         c = self.model_cfg
@@ -160,13 +161,18 @@ class SPECTester:
         return rot.astype(np.float32), (f_pix, f_pix), (w // 2, h // 2), np.array([vfov, pitch, roll, f_pix])
 
     def _write_pictures(self, img_fname, pictures, vertices, output_path, output_img_folder):
-        """The files of one frame: ``pictures[i]`` (a PIL image) under detection i's name, and with ``args.save_obj`` its mesh."""
+        """The files of one frame: ``pictures[i]`` (a PIL image, or the ``bytes`` of a file encoded on the device) under detection
+        i's name, and with ``args.save_obj`` its mesh."""
         stem, ext = os.path.splitext(os.path.basename(img_fname))
         os.makedirs(output_img_folder, exist_ok=True)
         written = []
         for i in range(vertices.shape[0]):
             written.append(os.path.join(output_img_folder, f'{stem}_{i:06d}{ext}'))
-            pictures[i].save(written[-1])
+            if isinstance(pictures[i], bytes):
+                with open(written[-1], 'wb') as f:
+                    f.write(pictures[i])
+            else:
+                pictures[i].save(written[-1])
             if getattr(self.args, 'save_obj', False):
                 mesh_folder = os.path.join(output_path, 'meshes', os.path.basename(img_fname).split('.')[0])
                 os.makedirs(mesh_folder, exist_ok=True)
@@ -182,21 +188,30 @@ class SPECTester:
         from PIL import Image
         rot, focal, center, cam_params = self._frame_camera(img_fname, rgb.shape, output_path)
         group = render.render_image_group(rgb, cam_t, vertices, rot, focal, center, cam_params=cam_params, device=self.device, keypoints_2d=keypoints)
-        return self._write_pictures(img_fname, [Image.fromarray(group.cpu().numpy())] * vertices.shape[0], vertices, output_path, output_img_folder)
+        if flow_jpeg_device(self._jpeg_device) and is_jpeg_name(img_fname):       # encoded once, written once per detection
+            H, W3 = int(group.shape[0]), int(group.shape[1])
+            picture = cam_utils._engine(group.device).jpeg_encode(group.view(-1), [[H, W3]], [[0, 3 * W3]], 75)[0]
+        else:
+            picture = Image.fromarray(group.cpu().numpy())
+        return self._write_pictures(img_fname, [picture] * vertices.shape[0], vertices, output_path, output_img_folder)
 
     def _render_flush(self, pending, frames, vertices, cam_t, output_path, output_img_folder, each, keypoints=None):
         """``_render_frame`` for every frame of a flush in one ``render_image_groups`` call: ``pending`` [(image, first crop,
         crops)] and ``frames`` (the RGB arrays) in the same order, ``vertices`` / ``cam_t`` the flush's detections on the device.
         Same file names, same bytes; ``each``: file i of a frame shows detection i alone (spec/tester.py:181-201) - with
-        ``keypoints`` (the flush's (k, 49, 2) 2D joints) its own skeleton alone."""
+        ``keypoints`` (the flush's (k, 49, 2) 2D joints) its own skeleton alone.  With ``self._jpeg_device`` the pictures of
+        ``.jpg`` / ``.jpeg`` frames come back from that call as the bytes of their files (``encode='jpeg'``, Pillow's default
+        quality 75); a frame's shared picture is encoded once and written once per detection."""
         from PIL import Image
+        encode = [('jpeg' if is_jpeg_name(f) else None) for f, _, _ in pending] if flow_jpeg_device(self._jpeg_device) else None
+        as_picture = lambda p: p if isinstance(p, bytes) else Image.fromarray(p)
         cams = [self._frame_camera(f, rgb.shape, output_path) for (f, _, _), rgb in zip(pending, frames)]
         counts = [n for _, _, n in pending]
         groups = render.render_image_groups(frames, vertices, cam_t, counts, [c[0] for c in cams], [c[1] for c in cams], [c[2] for c in cams],
-                                            cam_params=[c[3] for c in cams], each=each, device=self.device, keypoints_2d=keypoints)
+                                            cam_params=[c[3] for c in cams], each=each, device=self.device, keypoints_2d=keypoints, encode=encode)
         written, g = [], 0
         for img_fname, k0, n in pending:
-            pictures = [Image.fromarray(p) for p in groups[g:g + n]] if each else [Image.fromarray(groups[g])] * n
+            pictures = [as_picture(p) for p in groups[g:g + n]] if each else [as_picture(groups[g])] * n
             g += n if each else 1
             written += self._write_pictures(img_fname, pictures, vertices[k0:k0 + n], output_path, output_img_folder)
         return written
@@ -230,7 +245,10 @@ class SPECTester:
         detections together.  ``args.draw_keypoints``: the predicted ``smpl_joints2d`` of each frame's detections are drawn onto
         the frame as 2D skeletons before the mesh is laid over it (``render.draw_skeleton``: on the device, this project's own
         drawing contract), on both routes; with ``render_each`` each picture shows its own detection's skeleton alone.  Off by
-        default: the pictures are then unchanged."""
+        default: the pictures are then unchanged.
+        ``self._jpeg_device`` (None = ``engine.JPEG_DEVICE_DEFAULT``): the pictures of ``.jpg`` / ``.jpeg`` frames are encoded on
+        the device (``specmi_jpeg_encode``, Pillow's default quality 75) and only the files' bytes come down, on both routes; a
+        ``.png`` frame keeps the host route.  Same files, byte for byte."""
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         image_file_names = list_images(image_folder)
