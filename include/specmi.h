@@ -691,18 +691,23 @@ int specmi_jpeg_header(int quality, int H, int W, uint8_t* out, size_t capacity)
  * J_regressor (J,V) @ vertices for prediction and ground truth, pelvis (joint 0) alignment,
  * selection of `nsel` joints (`joint_sel` device int32, NULL = the first nsel), then per image
  * MPJPE, PA-MPJPE (similarity Procrustes) and pelvis-aligned V2V, all in millimetres.  All
- * pointers are device pointers; any output may be NULL.  J, nsel <= 32. */
+ * pointers are device pointers; any output may be NULL.  J and nsel in [1,32] (SPECMI_ERR_ARG otherwise; the joints are held
+ * on chip); every entry of joint_sel must lie in [0,J) - it is device memory and is not checked - and may repeat; with
+ * joint_sel NULL, nsel <= J (SPECMI_ERR_ARG otherwise).  A selection without variance (one joint, coincident joints) has no
+ * similarity fit: PA-MPJPE is NaN there, as in the reference (0 / 0), and MPJPE stays finite. */
 int specmi_eval_mesh(specmi_handle* h, const float* pred_vertices, const float* gt_vertices, int B,
                      int V, const float* J_regressor, int J, const int32_t* joint_sel, int nsel,
                      float* mpjpe_mm, float* pampjpe_mm, float* v2v_mm, void* stream);
 
 /* eval_j_24 (spec/utils/compute_error.py:33-49): pelvis-aligned MPJPE / PA-MPJPE (mm) of two
- * (B,J,3) joint sets. */
+ * (B,J,3) joint sets.  J in [1,32] (SPECMI_ERR_ARG otherwise); any output may be NULL.  The pelvis is subtracted in fp32 as the
+ * reference does, everything after it runs in fp64; PA-MPJPE of a pose without variance is NaN, as in the reference. */
 int specmi_eval_joints(specmi_handle* h, const float* pred_joints, const float* gt_joints, int B,
                        int J, float* mpjpe_mm, float* pampjpe_mm, void* stream);
 
 /* pred_joints = einsum('bik,ji->bjk', vertices, J_regressor) (spec/utils/compute_error.py:184,187): vertices (B,V,3),
- * J_regressor (J,V) device -> joints (B,J,3). */
+ * J_regressor (J,V) device -> joints (B,J,3).  Any J >= 1: unlike the two calls above nothing per joint is held on chip, so
+ * there is no cap of 32 (the joints run in chunks of 8, one workgroup per image and chunk). */
 int specmi_regress_joints(specmi_handle* h, const float* vertices, int B, int V, const float* J_regressor, int J,
                           float* joints, void* stream);
 

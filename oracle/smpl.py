@@ -123,8 +123,9 @@ class SMPLOracle(nn.Module):
         return vertices, joints[:, self.joint_map, :]
 
 
-def smpl_forward_f64(model, betas, rot_mats):
-    """NumPy float64 reference of the same forward: returns verts (B,V,3), joints49 (B,49,3)."""
+def smpl_forward_f64(model, betas, rot_mats, joints24=False):
+    """NumPy float64 reference of the same forward: returns verts (B,V,3), joints49 (B,49,3) and, with ``joints24``, the 24 posed
+    kinematic-chain joints (B,24,3) (``smplx.SMPL(...).joints[:, :24]``) as a third value."""
     f = lambda a: np.asarray(a, dtype=np.float64)
     vt, sdirs, pdirs = f(model['v_template']), f(model['shapedirs']), f(model['posedirs'])
     Jr, W, Jx = f(model['J_regressor']), f(model['lbs_weights']), f(model['J_regressor_extra'])
@@ -151,4 +152,5 @@ def smpl_forward_f64(model, betas, rot_mats):
     extra_v = verts[:, np.asarray(model['extra_vertex_ids']).astype(np.int64)]
     extra_r = np.einsum('bik,ji->bjk', verts, Jx)
     joints = np.concatenate([posed, extra_v, extra_r], axis=1)
-    return verts, joints[:, np.asarray(model['joint_map']).astype(np.int64)]
+    j49 = joints[:, np.asarray(model['joint_map']).astype(np.int64)]
+    return (verts, j49, posed) if joints24 else (verts, j49)

@@ -2062,6 +2062,7 @@ int specmi_eval_mesh(specmi_handle* h, const float* pred, const float* gt, int B
     ENTER(h);
     if (!pred || !gt || !Jr || B <= 0 || V <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
     if (J < 1 || J > 32 || nsel < 1 || nsel > 32) return fail(h, SPECMI_ERR_ARG, "J and nsel must be in [1,32]");
+    if (!sel && nsel > J) return fail(h, SPECMI_ERR_ARG, "eval_mesh: joint_sel is NULL (the first nsel joints) but nsel = %d exceeds J = %d", nsel, J);
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, "eval.mesh"};
     LAUNCHCHK(h, launch_eval_mesh(pred, gt, B, V, Jr, J, sel, nsel, mpjpe, pampjpe, v2v, ctx), "eval_mesh");
     return SPECMI_OK;

@@ -341,6 +341,46 @@ def test_smpl_lbs_joints_projection(hmr_engine, B):
     assert np.abs(out['smpl_joints3d'].cpu().numpy() - j64).max() < 5e-6
 
 
+_SMPL_TILES = {}
+
+
+def _smpl_tiles_ref():
+    """65 poses (three 32-image skinning tiles, the last with one image) and their float64 mesh, once per process."""
+    if not _SMPL_TILES:
+        from oracle.smpl import smpl_forward_f64
+        R, betas, cam = _rand_pose(65, 4242)
+        _SMPL_TILES.update(R=R, betas=betas, cam=cam, ref=smpl_forward_f64(smpl_model(), betas.numpy(), R.numpy(), joints24=True))
+    return _SMPL_TILES
+
+
+@pytest.mark.parametrize('split', [0, 1])
+@pytest.mark.parametrize('B', [32, 33, 65])
+def test_smpl_beyond_one_image_tile_vs_float64(hmr_engine, B, split):
+    """``smpl`` and ``smpl_native`` past the first 32-image tile, under both skinning variants, against float64 and PER IMAGE: the worst
+    image within the file's 5e-6, and no image of a later tile worse than twice the worst image of tile 0 - a tile-indexing fault
+    (``b / IT``, ``frag_slot(., b % IT)``, ``tile * FEAT_TILE``, shared by both variants) is a step between tiles long before it
+    moves the maximum norm."""
+    d = _smpl_tiles_ref()
+    R, betas, cam = d['R'][:B].contiguous(), d['betas'][:B].contiguous(), d['cam'][:B].contiguous()
+    v64, j49, j24 = (a[:B] for a in d['ref'])
+    K = torch.zeros(B, 3, 3)
+    K[:, 0, 0] = K[:, 1, 1] = 500.0
+    try:
+        hmr_engine.set_option('smpl_skin_split', split)
+        out = hmr_engine.smpl(R.to(DEV), betas.to(DEV), cam.to(DEV), torch.eye(3).expand(B, 3, 3).contiguous().to(DEV), K.to(DEV),
+                              torch.ones(B).to(DEV), torch.zeros(B, 2).to(DEV), torch.ones(B).to(DEV), torch.ones(B).to(DEV))
+        got = {'smpl.vertices': (out['smpl_vertices'].cpu().numpy(), v64), 'smpl.joints3d': (out['smpl_joints3d'].cpu().numpy(), j49)}
+        v, j = hmr_engine.smpl_native(R.to(DEV), betas.to(DEV))
+        got.update({'native.vertices': (v.cpu().numpy(), v64), 'native.joints24': (j.cpu().numpy(), j24)})
+    finally:
+        hmr_engine.set_option('smpl_skin_split', -1)
+    for name, (a, ref) in got.items():
+        err = np.abs(a.astype(np.float64) - ref).reshape(B, -1).max(1)          # per image
+        assert err.max() < 5e-6, (name, int(err.argmax()), err.max())
+        if B > 32:
+            assert err[32:].max() <= 2 * err[:32].max(), (name, 32 + int(err[32:].argmax()), err[32:].max(), err[:32].max())
+
+
 def test_smpl_index_paths_bit_exact(hmr_engine):
     """Vertex-picked joints are copies of vertices and joint_map duplicates are identical: exact."""
     from spec_amd import constants as C
