@@ -645,6 +645,61 @@ int specmi_draw_skeletons(specmi_handle* h, const float* kp, int Mtot, int J, in
                           const specmi_draw_style* style, uint8_t* slab, size_t slab_bytes, const int32_t* frame_geom,
                           const int64_t* frame_offsets, int nframes, void* stream);
 
+/* HORIZON LINES AND CAPTIONS drawn in place into the uint8 frames of a slab, all frames of a flush in ONE launch: replaces
+ * show_horizon_line (camcalib/vis_utils.py:63-110: a black caption strip, ImageDraw.text, ImageDraw.line on a host image) as
+ * render_image_group calls it for panel 0 (spec/utils/renderer_cam.py:170-173) and as CamCalib's save_images calls it twice per
+ * validation picture (camcalib/trainer.py:118-169), and the copies of the frame to the host and back around it.  The contract
+ * is PILLOW'S, byte for byte (stated in full at the head of spec_amd/csrc/marks.hip, restated in NumPy in tests/marks_ref.py
+ * and pinned there against the installed Pillow).  Works on a handle of any model kind, committed or not.
+ * DEVICE pointers: slab, uint8 RGB, of slab_bytes - the slab and offsets convention of specmi_draw_skeletons: what
+ * spec_amd.preprocess.pack_frames builds, or the panel-0 column of a three-panel picture (pitch 9 W); masks, uint8, of
+ * mask_bytes: the coverage masks the mask blends name (may be NULL when no mark is a mask blend).  HOST: the FRAME RECORD,
+ *   frame_geom    (nframes x 4 int32):  H, W, mark0, count - the frame takes marks mark0 .. mark0 + count - 1 in that order;
+ *                                       count == 0 is legal and leaves the frame untouched
+ *   frame_offsets (nframes x 2 int64):  byte offset of the frame's first pixel in the slab, bytes from one row to the next
+ * and THE MARK RECORD, marks (nmarks x 8 int64): kind, colour as r | g << 8 | b << 16, and six parameters p0 .. p5:
+ *   SPECMI_MARK_STRIP: p0 = y0, p1 = y1 - rows [y0, y1) n [0, H) are set to the colour
+ *   SPECMI_MARK_MASK:  p0 = x, p1 = y, p2 = mw, p3 = mh, p4 = byte offset in masks - the mw x mh mask with its top-left corner
+ *                      at (x, y), clipped to the frame, blended with the colour as Pillow's ImagingFill2 does for a mode L mask:
+ *                      per channel, where the mask byte m != 0, t = in * (255 - m) + ink * m + 128, out = ((t >> 8) + t) >> 8;
+ *                      a pixel under m == 0 is not written
+ *   SPECMI_MARK_LINE:  p0 .. p3 = x0, y0, x1, y1, p4 = width - Pillow's ImagingDrawWideLine, overwriting: the quadrilateral's
+ *                      edges come from hypot and Pillow's two rounding macros in double on the host; a row is covered from
+ *                      RU(min xx) to RD(max xx) over its edges' xx = (float)(y - ey0) * edx + (float)ex0, a separately rounded
+ *                      fp32 multiply and add
+ * Unused parameters are ignored.  A pixel's final value is decided by walking its frame's marks in order: no atomics, nothing
+ * depends on scheduling.  Pixels that no mark covers, row padding and slab bytes outside every frame rectangle are never
+ * written.  Work follows the area the marks can reach (tiles of 64 x 16 pixels listed on the host), not the frames' sizes.
+ * Refused (SPECMI_ERR_ARG), launching nothing: a null required pointer (marks with nmarks > 0, masks with a mask blend);
+ * nframes outside [1, 65535]; nmarks < 0; H or W outside [1, 8192]; a pitch below 3 W; a frame rectangle that leaves the slab;
+ * two frames that share a byte; a mark range outside [0, nmarks]; an unknown kind; a colour outside 24 bits; a width outside
+ * [2, 64] (width 1 is Pillow's Bresenham line: not drawn here); a line end point outside [-100000, 100000] - the range pinned
+ * against Pillow; mw or mh outside [1, 8192]; a mask position outside [-16383, 16383]; a mask that leaves the mask buffer; marks that reach 2^30
+ * tiles or more.
+ * The frame records, the marks and the tile list live in one device table owned by the handle, under the rule of the ragged
+ * calls above: a call whose records differ from the previous call's rewrites the table and therefore first SYNCHRONISES THE
+ * WHOLE DEVICE, and cannot be made while a stream is being captured (SPECMI_ERR_STATE; the stream is asked first, so the
+ * capture stays valid and nothing is enqueued); a call that repeats them does neither and can be captured.  The contents of
+ * the mask buffer and the pointers are not part of the table. */
+#define SPECMI_MARK_STRIP 0
+#define SPECMI_MARK_MASK 1
+#define SPECMI_MARK_LINE 2
+int specmi_draw_marks(specmi_handle* h, uint8_t* slab, size_t slab_bytes, const int32_t* frame_geom, const int64_t* frame_offsets,
+                      int nframes, const int64_t* marks, int nmarks, const uint8_t* masks, size_t mask_bytes, void* stream);
+
+/* ONE IMAGE OF A NORMALISED BATCH AS A uint8 FRAME: image `index` of x (B, 3, Hp, Wp) fp32 NCHW on the device, cut to its top-left
+ * H x W, written as HWC uint8 at byte `offset` and `pitch` of a slab - the base of CamCalib's validation pictures
+ * (camcalib/trainer.py:118-133: pare's denormalize_images, * 255, astype('uint8'), the crop to the image's own resized size).
+ * Per channel v = (x * std_c + mean_c) * 255, every operation rounded separately in fp32; NaN gives 0, v is clamped to
+ * [0, 255] - the reference's astype('uint8') is undefined outside it: this project's stated deviation - and truncated.
+ * mean3 / std3: three HOST floats each, NULL = ImageNet's (0.485, 0.456, 0.406) / (0.229, 0.224, 0.225); pare is not vendored,
+ * its denormalize_images is restated with these constants and parity with it is not pinned.
+ * Refused (SPECMI_ERR_ARG): a null x or slab; B < 1; Hp or Wp outside [1, 32768]; index outside [0, B); H outside [1, Hp] or W
+ * outside [1, Wp]; a pitch below 3 W; a rectangle that leaves the slab; a non-finite mean or std.  Works on a handle of any
+ * model kind, committed or not; one launch, nothing synchronised. */
+int specmi_denormalize_u8(specmi_handle* h, const float* x, int B, int Hp, int Wp, int index, int H, int W, const float* mean3,
+                          const float* std3, uint8_t* slab, size_t slab_bytes, int64_t offset, int64_t pitch, void* stream);
+
 /* BASELINE JPEG FILES encoded on the device, all pictures of a flush in one fixed sequence of launches: replaces the download
  * of the raw pictures and the host encoder behind every picture the flows write (cv2.imwrite / PIL's save in
  * spec/utils/renderer_cam.py:213-216, spec/tester.py:188-201, camcalib/datagen/generateCalibrationDataset.py:131-132) - the

@@ -15,6 +15,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only render_batch       # the pictures of a 32-frame flush, per-frame loop against the batched call -> profiles/render_batch_aux.json
     python scripts/bench_aux.py --only draw               # the 2D skeletons of a 1080p frame and of a 64-frame flush, next to render_views for the same flush -> profiles/draw_skeletons_aux.json
     python scripts/bench_aux.py --only jpeg_encode        # pictures to JPEG files: device encode + download of the bytes against raw download + Pillow -> profiles/jpeg_encode_aux.json
+    python scripts/bench_aux.py --only horizon_panel      # panel 0 of eight 1080p frames: Pillow on the host against specmi_draw_marks -> profiles/horizon_panel_aux.json
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
     python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
@@ -651,6 +652,56 @@ def jpeg_section(eng, a):
     return out
 
 
+def horizon_panel_section(eng, a):
+    """Panel 0 of a flush of eight 1080 x 1920 frames with the demo's marks (green line of width 5, caption strip of 30 rows), from
+    host frames to a finished slab on the device, two routes alternated in this process (wall clock with the copies, 3 rounds):
+    HOST = ``render.group_panel0`` on each frame (Pillow) + ``pack_frames``; DEVICE = ``pack_frames`` of the raw frames +
+    ``render.show_horizon_lines`` (one mask upload, one ``specmi_draw_marks`` call).  The launch itself by the library's profiler."""
+    import time
+    from spec_amd import render
+    from spec_amd.preprocess import pack_frames
+    F, H, W = 8, 1080, 1920
+    rng = np.random.default_rng(0)
+    frames = [rng.integers(0, 256, (H, W, 3), dtype=np.uint8) for _ in range(F)]
+    cams = [(float(rng.uniform(0.8, 1.4)), float(rng.uniform(-0.3, 0.3)), float(rng.uniform(-0.2, 0.2)), float(rng.uniform(800, 1500))) for _ in range(F)]
+    sizes, horizons = [(H, W)] * F, [render._panel0_horizon(c) for c in cams]
+    offs = np.arange(F, dtype=np.int64) * H * W * 3
+
+    def host_route():
+        return pack_frames([render.group_panel0(f, c) for f, c in zip(frames, cams)], eng.device)[0]
+
+    def device_route():
+        slab = pack_frames(frames, eng.device)[0]
+        render.show_horizon_lines(slab, sizes, offs, horizons, engine=eng)
+        return slab
+
+    def wall(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, r
+
+    same = bool(torch.equal(host_route(), device_route()))
+    rounds = {'host': [], 'device': []}
+    reps = max(2, min(a.iters, 5))
+    for _ in range(3):                                                  # alternated: both see the same clocks and the same neighbours
+        ms = {'host': [], 'device': []}
+        for _ in range(reps):
+            ms['host'].append(wall(host_route)[0])
+            ms['device'].append(wall(device_route)[0])
+        for k, v in ms.items():
+            rounds[k].append(float(np.median(v)))
+    med = {k: float(np.median(v)) for k, v in rounds.items()}
+    spread = max(max(v) - min(v) for v in rounds.values())
+    slab = pack_frames(frames, eng.device)[0]
+    kern = {k: {'ms_per_launch': round(ms_, 5), 'launches_per_call': nl}
+            for k, (ms_, _, _, nl) in timed(eng, lambda: render.show_horizon_lines(slab, sizes, offs, horizons, engine=eng), a.iters).items()}
+    row = {'workload': f'{F} frames of {H} x {W}, one horizon each: line of width 5, caption strip of 30 rows', 'byte_identical': same,
+           'ms_per_flush_rounds': {k: [round(x, 3) for x in v] for k, v in rounds.items()}, 'ms_per_flush_median': {k: round(v, 3) for k, v in med.items()},
+           'spread_between_rounds_ms': round(spread, 3), 'ratio_host_over_device': round(med['host'] / med['device'], 2),
+           'device_faster_beyond_the_spread': bool(med['device'] + spread < med['host']), 'kernels': kern}
+    print(json.dumps(row, indent=1))
+    return row
+
+
 def hmr_loss_section(eng, a, add):
     """``specmi_hmr_loss`` in HMRCamLoss mode with the per-vertex L1 term on: 2 * B * 6890 * 3 floats per call, at the batch of the
     evaluation config (64) and at ``--batch``."""
@@ -670,7 +721,7 @@ def hmr_loss_section(eng, a, add):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'horizon_panel'], default=None, help='run one section only')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -753,6 +804,15 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'routes: wall clock with the copies, 3 alternated rounds, ms per '
                        'picture; kernels: per-launch HIP events (library profiler)', 'jpeg_encode': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'horizon_panel':
+        from spec_amd import _lib
+        row = horizon_panel_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'iters': a.iters, 'timing': 'routes: wall clock from host frames to the finished slab on the device, 3 alternated rounds, ms per '
+                       'flush; kernels: per-launch HIP events (library profiler)', 'horizon_panel': row, 'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     if a.only == 'ragged_crops':

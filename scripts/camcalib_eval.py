@@ -13,6 +13,11 @@ the reference logs at epoch end: val loss, vfov / pitch / roll mean absolute err
 ``val_images.pkl``, a Lightning-layout checkpoint, the YAML config) and evaluates that: a dry run of the whole flow, the
 numbers are meaningless.  ``--report FILE`` writes the result (without the logits) as JSON.
 
+``--save-images`` / ``--no-save-images`` (default: ``TRAINING.SAVE_IMAGES`` of the config): the reference's validation pictures
+(camcalib/trainer.py:118-169) - the network input of the first image of every fourth batch with the ground-truth horizon (blue,
+caption at the bottom) and the predicted one (red, caption at the top), ``result_0000000_{batch:05d}.jpg`` under ``--image-dir``
+(default ``LOG_DIR/val_output_images``), denormalised, drawn and encoded on the device.
+
 ``--panoramas DIR`` evaluates on views generated from the equirectangular panoramas under DIR instead of a stored validation
 set - the reference's dataset generator (camcalib/datagen/generateCalibrationDataset.py) on the GPU: ``--views-per-pano``
 cameras per panorama drawn from its distribution with ``--seed``, cut out on the device and fed to the network without
@@ -42,6 +47,10 @@ def main():
     ap.add_argument('--write-tree', type=str, default=None, metavar='OUT', help='with --panoramas: also write the views as a pano_scalenet tree')
     ap.add_argument('--device-jpeg', action='store_true', help="with --write-tree: encode a panorama's views on the device in one call and "
                     "download only the files' bytes (the same bytes as Pillow's; default: engine.JPEG_DEVICE_DEFAULT)")
+    ap.add_argument('--save-images', dest='save_images', action='store_true', default=None,
+                    help='write the validation pictures (default: TRAINING.SAVE_IMAGES of the config)')
+    ap.add_argument('--no-save-images', dest='save_images', action='store_false')
+    ap.add_argument('--image-dir', type=str, default=None, help='where the validation pictures go (default: LOG_DIR/val_output_images)')
     args = ap.parse_args()
     import torch
     torch.set_grad_enabled(False)
@@ -61,7 +70,8 @@ def main():
         if args.write_tree:
             panorama.write_tree(dataset, args.write_tree, while_evaluating=True,      # every view is generated once
                                 jpeg_device=True if args.device_jpeg else None)
-    res = ce.run_evaluation(hp, data_root=root, ckpt=args.ckpt, dataset=dataset)
+    res = ce.run_evaluation(hp, data_root=root, ckpt=args.ckpt, dataset=dataset, save_images=args.save_images, image_dir=args.image_dir,
+                            jpeg_device=True if args.device_jpeg else None)
     if args.report:
         rep = {k: (v.tolist() if hasattr(v, 'tolist') else v) for k, v in res.items() if k != 'logits'}
         with open(args.report, 'w') as f:

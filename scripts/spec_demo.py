@@ -76,6 +76,7 @@ def main(args):
     total_time = time.time()
     tester = SPECTester(args)
     tester._jpeg_device = True if args.device_jpeg else None
+    tester._panel0_device = True if args.device_panel0 else None
     print(f'Number of input frames {num_frames}')
     tester.run_camcalib(args.image_folder, output_path)                       # CamCalib
     detections = tester.run_detector(args.image_folder) if args.detections else default_boxes(args.image_folder)
@@ -124,6 +125,8 @@ def build_parser():
     parser.add_argument('--draw_keypoints', action='store_true', help='draw 2d keypoints on rendered image')
     parser.add_argument('--device_jpeg', action='store_true', help='encode the pictures of .jpg / .jpeg frames on the device and download only '
                         "the files' bytes (the same bytes as Pillow's; default: engine.JPEG_DEVICE_DEFAULT)")
+    parser.add_argument('--device_panel0', action='store_true', help='draw the horizon line and caption of panel 0 on the device instead of '
+                        "with Pillow on the host (the same bytes; default: engine.PANEL0_DEVICE_DEFAULT)")
     parser.add_argument('--synthetic', type=int, default=0, help='run on N random frames with random weights')
     return parser
 

@@ -82,6 +82,8 @@ def main():
                     'TESTING.SAVE_IMAGES and TRAINING.SAVE_IMAGES (the reference writes the files only with both)')
     ap.add_argument('--device-jpeg', action='store_true', help='with --save-images: encode .jpg / .jpeg pictures on the device and download '
                     "only the files' bytes (the same bytes as Pillow's; default: engine.JPEG_DEVICE_DEFAULT)")
+    ap.add_argument('--device-panel0', action='store_true', help='with --save-images: draw the horizon line and caption of panel 0 on the '
+                    "device instead of with Pillow on the host (the same bytes; default: engine.PANEL0_DEVICE_DEFAULT)")
     ap.add_argument('--report', type=str, default=None, metavar='eval.json',
                     help='write the scores and the delta against the reference README table (README.md:155-159) as JSON; the exit '
                          'code is 3 when |delta W-MPJPE| > 0.1 mm on a dataset the table lists (use on the real assets)')
@@ -90,6 +92,9 @@ def main():
     if args.device_jpeg:
         from spec_amd import engine
         engine.JPEG_DEVICE_DEFAULT = True
+    if args.device_panel0:
+        from spec_amd import engine
+        engine.PANEL0_DEVICE_DEFAULT = True
     if args.synthetic:
         return synthetic(args)
     from spec_amd import evaluation

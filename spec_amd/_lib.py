@@ -34,6 +34,9 @@ PRECISION_FP32, PRECISION_FP16 = 0, 1       # SPECMI_PRECISION_* (include/specmi
 MODEL_CAMCALIB, MODEL_HMR, MODEL_SMPL = 0, 1, 2
 RENDER_SIDE_VIEW, RENDER_GROUND_PLANE, RENDER_CULL, RENDER_THREAD_PER_TRIANGLE = 1, 2, 4, 8     # SPECMI_RENDER_* (include/specmi.h)
 DRAW_MAX_SIDE, DRAW_MAX_COORD, DRAW_MAX_RADIUS, DRAW_MAX_THICKNESS = 8192, 16383, 64, 64      # the limits of specmi_draw_skeletons (include/specmi.h)
+MARK_STRIP, MARK_MASK, MARK_LINE, MARK_REC = 0, 1, 2, 8         # SPECMI_MARK_* and the int64 per mark record (include/specmi.h)
+# the limits of specmi_draw_marks: frame side, line width, line end point, mask side, mask position (include/specmi.h)
+MARK_MAX_SIDE, MARK_MIN_WIDTH, MARK_MAX_WIDTH, MARK_MAX_COORD, MARK_MAX_MASK_SIDE, MARK_MAX_MASK_POS = 8192, 2, 64, 100000, 8192, 16383
 JPEG_HEADER_BYTES = 623                       # what specmi_jpeg_header writes; the least capacity of specmi_jpeg_encode (include/specmi.h)
 HMR_LOSS, HMR_CAM_LOSS = 0, 1                 # SPECMI_HMR_LOSS / SPECMI_HMR_CAM_LOSS (include/specmi.h)
 # the ground-truth tensors of specmi_hmr_loss in the order of its prototype, per-image shapes (None = (V, 3)); int32 where named has_*
@@ -185,6 +188,12 @@ PROTOTYPES = {
     # (h, kp, Mtot, J, D, bones, NB, style, slab, slab_bytes, frame_geom, frame_offsets, nframes, stream)
     'specmi_draw_skeletons': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, c_int32_p, C.c_int, C.POINTER(DrawStyle), C.c_void_p,
                                         C.c_size_t, c_int32_p, c_int64_p, C.c_int, C.c_void_p]),
+    # (h, slab, slab_bytes, frame_geom, frame_offsets, nframes, marks, nmarks, masks, mask_bytes, stream)
+    'specmi_draw_marks': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_int32_p, c_int64_p, C.c_int, c_int64_p, C.c_int, C.c_void_p,
+                                    C.c_size_t, C.c_void_p]),
+    # (h, x, B, Hp, Wp, index, H, W, mean3, std3, slab, slab_bytes, offset, pitch, stream)
+    'specmi_denormalize_u8': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
+                                        C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p]),
     # (h, in_slab, in_bytes, out_slab, out_bytes, pic_geom, pic_offsets, n, quality, sizes, stream)
     'specmi_jpeg_encode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_int32_p, c_int64_p, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p]),

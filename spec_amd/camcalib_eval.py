@@ -191,9 +191,51 @@ def build_model(hparams: dict, ckpt: Optional[str], data_root: str = '.', device
     return model.to(torch.device(device)).eval().commit(torch.device(device), freeze=True)
 
 
+def validation_horizons(size_hw, gt, pred) -> list:
+    """The two horizons of a validation picture in the order ``save_images`` draws them (camcalib/trainer.py:155-161): ground
+    truth - blue, width 3, caption strip at the bottom - then prediction - red, width 3, strip at the top -, both with
+    ``debug=True``, ``text_size=16`` and ``f_pix = H / 2 / tan(vfov / 2)``; ``gt`` / ``pred`` = (vfov, pitch, roll) as NumPy scalars
+    of the run's own dtypes.  -> what ``render.plan_horizon_marks`` / ``show_horizon_lines`` take for one frame."""
+    H = int(size_hw[0])
+    one = lambda a, colour, GT: dict(vfov=a[0], pitch=a[1], roll=a[2], focal_length=H / 2. / np.tan(a[0] / 2.), debug=True, color=colour, width=3,
+                                     GT=GT, text_size=16)
+    return [one(gt, (0, 0, 255), True), one(pred, (255, 0, 0), False)]
+
+
+def save_validation_picture(eng, images: torch.Tensor, size_hw, gt, pred, path: str, jpeg_device=None, index: int = 0) -> str:
+    """One picture of ``save_images`` (camcalib/trainer.py:118-169) made where the batch lies: image ``index`` of the padded
+    network input ``images`` - (n, 3, H, W) fp32, or the fp16 trunk's (n, H, W, 8), of which the one image is converted with
+    ``.float()`` - denormalised to uint8 and cut to its own resized size ``size_hw`` (``Engine.denormalize_u8``: ImageNet's
+    constants as pare's un-vendored ``denormalize_images``, parity unpinned; values beyond [0, 255] are clamped where the
+    reference's ``astype('uint8')`` is undefined), the two horizons of ``validation_horizons`` drawn by ONE ``draw_marks`` call
+    (``render.show_horizon_lines``), and the file written through ``render.save_picture`` - a ``.jpg`` on the device when the
+    JPEG route is on.  A horizon the device route cannot reproduce (``horizon_marks`` -> None) is drawn on the host."""
+    from . import render
+    H, W = int(size_hw[0]), int(size_hw[1])
+    if images.dtype == torch.float16:
+        x = images[index, :, :, :3].permute(2, 0, 1).float().contiguous()[None]
+        index = 0
+    else:
+        x = images.contiguous()
+    frame = eng.denormalize_u8(x, index, H, W)
+    horizons = validation_horizons((H, W), gt, pred)
+    if render.plan_horizon_marks([(H, W)], [horizons]) is not None:
+        render.show_horizon_lines(frame, [(H, W)], [0], [horizons], engine=eng)
+        picture = frame.view(H, W, 3)
+    else:
+        img = frame.cpu().numpy().reshape(H, W, 3)
+        for hz in horizons:
+            kw = dict(hz)
+            img, _ = render.show_horizon_line(img, kw.pop('vfov'), kw.pop('pitch'), kw.pop('roll'), **kw)
+        picture = torch.from_numpy(img).to(eng.device)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    return render.save_picture(path, picture, engine=eng, jpeg_device=jpeg_device)
+
+
 @torch.no_grad()
 def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = None, log=print, device='cuda', model=None,
-                   sub_batch: Optional[int] = None, dataset=None, _fp32_images: Optional[bool] = None) -> dict:
+                   sub_batch: Optional[int] = None, dataset=None, _fp32_images: Optional[bool] = None, save_images: Optional[bool] = None,
+                   image_dir: Optional[str] = None, jpeg_device=None) -> dict:
     """CamCalib's test epoch over ``DATASET.VAL_DS`` - or over ``dataset``, an object with ``PanoValDataset``'s interface such as
     ``spec_amd.panorama.PanoViewDataset``, whose ``device_batch`` hands frames over without a host round trip: consecutive batches of ``DATASET.BATCH_SIZE`` frames in file order, each
     padded to ITS OWN largest height and width, forwarded, scored.  Returns the four epoch figures the reference logs
@@ -207,8 +249,19 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     the host with the kernel's arg-max indices and the accuracies are float64, as in the reference.
 
     ``_fp32_images=False``: a model at precision 'fp16' is fed NHWC8 fp16 batches (``pad_batch(dtype=torch.float16)``); True: the
-    fp32 batch + in-trunk conversion (same bits); None = ``engine.F16_CROPS_DEFAULT``."""
+    fp32 batch + in-trunk conversion (same bits); None = ``engine.F16_CROPS_DEFAULT``.
+
+    ``save_images`` (None = ``TRAINING.SAVE_IMAGES`` of the config, which every config of the reference sets): the validation
+    pictures of ``save_images`` (camcalib/trainer.py:94-95,118-169) - for the first image of every fourth batch the network input
+    with the ground-truth and the predicted horizon, ``result_{step 0:07d}_{batch:05d}.jpg`` under ``image_dir`` (None =
+    ``LOG_DIR/val_output_images``), made on the device (``save_validation_picture``); the files are listed under ``'pictures'``."""
     dev = torch.device(device)
+    if save_images is None:
+        save_images = bool((hparams.get('TRAINING') or {}).get('SAVE_IMAGES', False))
+    if save_images and image_dir is None:
+        log_dir = hparams['LOG_DIR'] if os.path.isabs(hparams['LOG_DIR']) else os.path.join(data_root, hparams['LOG_DIR'])
+        image_dir = os.path.join(log_dir, 'val_output_images')
+    pictures = []
     m = hparams['MODEL']
     loss_type = m['LOSS_TYPE']
     if loss_type not in LOSS_TYPES:
@@ -253,6 +306,13 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         per['logits'].append(torch.stack(logits, 0).cpu().numpy())
         per['pred'].append(pred); per['err'].append(err); per['gt'].append(gt)
         per['img_sizes'] += [resize_size(w, h, min_res, max_res) for h, w in sizes_hw]
+        batch_nb = b0 // bs
+        if save_images and batch_nb % 4 == 0:
+            # the labels as the reference's batch holds them: fp32 tensors (float64 for 'pano''s vfov); the predictions as decoded
+            g0 = (gt[0][0] if ds.name == 'pano' else gt32[0][0], gt32[1][0], gt32[2][0])
+            pictures.append(save_validation_picture(eng, images, per['img_sizes'][b0], g0, tuple(pred[k][0] for k in range(3)),
+                                                    os.path.join(image_dir, f'result_{0:07d}_{batch_nb:05d}.jpg'), jpeg_device=jpeg_device))
+            log(f'wrote {pictures[-1]}')
     if eng.sync_status() != 0:
         raise RuntimeError('a split-K arrival counter was left non-zero')
     res = epoch_end(outputs)
@@ -262,7 +322,7 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     log(f"[EPOCH 0] roll acc: {res['roll_acc']}")
     cat = lambda k: np.concatenate(per[k], axis=1)
     res.update(batches=outputs, loss_type=loss_type, imgname=[ds.imgname(i) for i in range(len(ds))], logits=cat('logits'),
-               img_sizes=per['img_sizes'])
+               img_sizes=per['img_sizes'], pictures=pictures)
     for k, name in enumerate(('vfov', 'pitch', 'roll')):
         res['pred_' + name], res['err_' + name], res['gt_' + name] = cat('pred')[k], cat('err')[k], cat('gt')[k]
     return res

@@ -806,6 +806,7 @@ int specmi_destroy(specmi_handle* h) {
     if (h->render_ws) (void)hipFree(h->render_ws);
     if (h->views_tab) (void)hipFree(h->views_tab);
     if (h->draw_tab) (void)hipFree(h->draw_tab);
+    if (h->marks_tab) (void)hipFree(h->marks_tab);
     if (h->jpeg_tab) (void)hipFree(h->jpeg_tab);
     if (h->jpeg_ws) (void)hipFree(h->jpeg_ws);
     hrnet_free(h->hrnet);
@@ -1834,6 +1835,179 @@ int specmi_draw_skeletons(specmi_handle* h, const float* kp, int Mtot, int J, in
     a.rgb[0] = pack(st.joint_rgb); a.rgb[1] = pack(st.bone_rgb[0]); a.rgb[2] = pack(st.bone_rgb[1]);
     LaunchCtx ctx{s, &h->prof, "render.skeletons"};
     LAUNCHCHK(h, launch_draw_skeletons(a, (int)tiles, kp_bytes, px, ctx), "draw_skeletons");
+    return SPECMI_OK;
+}
+
+// Pillow's ROUND_UP / ROUND_DOWN in double (Draw.c), as ImagingDrawWideLine applies them to the half width and the offsets
+static int marks_ru(double f) { return (int)(f >= 0.0 ? std::floor(f + 0.5) : -std::floor(std::fabs(f) + 0.5)); }
+static int marks_rd(double f) { return (int)(f >= 0.0 ? std::ceil(f - 0.5) : -std::ceil(std::fabs(f) - 0.5)); }
+
+// The four edges of Pillow's wide line (the contract at the head of marks.hip); the zero-length line is four horizontal edges
+// on its one pixel
+static void marks_line_edges(int x0, int y0, int x1, int y1, int width, MarkEdge e[4]) {
+    const int dx = x1 - x0, dy = y1 - y0;
+    int v[4][2] = {{x0, y0}, {x0, y0}, {x0, y0}, {x0, y0}};
+    if (dx != 0 || dy != 0) {
+        const double big = std::hypot((double)dx, (double)dy), small = (width - 1) / 2.0;
+        const double rmax = marks_ru(small) / big, rmin = marks_rd(small) / big;
+        const int dxmin = marks_rd(rmin * dy), dxmax = marks_rd(rmax * dy), dymin = marks_ru(rmin * dx), dymax = marks_ru(rmax * dx);
+        v[0][0] = x0 - dxmin; v[0][1] = y0 + dymax; v[1][0] = x1 - dxmin; v[1][1] = y1 + dymax;
+        v[2][0] = x1 + dxmax; v[2][1] = y1 - dymin; v[3][0] = x0 + dxmax; v[3][1] = y0 - dymin;
+    }
+    for (int i = 0; i < 4; ++i) {
+        const int ax = v[i][0], ay = v[i][1], bx = v[(i + 1) & 3][0], by = v[(i + 1) & 3][1];
+        MarkEdge& k = e[i];
+        k.xmin = std::min(ax, bx); k.xmax = std::max(ax, bx); k.ymin = std::min(ay, by); k.ymax = std::max(ay, by);
+        k.x0 = ax; k.y0 = ay; k.horiz = ay == by;
+        k.dx = k.horiz ? 0.f : (float)(bx - ax) / (float)(by - ay);
+    }
+}
+
+int specmi_draw_marks(specmi_handle* h, uint8_t* slab, size_t slab_bytes, const int32_t* frame_geom, const int64_t* frame_offsets,
+                      int nframes, const int64_t* marks, int nmarks, const uint8_t* masks, size_t mask_bytes, void* stream) {
+    ENTER(h);
+    if (!slab || !frame_geom || !frame_offsets || (nmarks > 0 && !marks)) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (nframes <= 0 || nframes > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 frames per call, got %d", nframes);
+    if (nmarks < 0) return fail(h, SPECMI_ERR_ARG, "%d marks", nmarks);
+    // the marks first: [nframes frame records | nmarks mark records | tiles]
+    const size_t marks_at = (size_t)nframes * kMarkFrameRec, tiles_at = marks_at + (size_t)nmarks * kMarkDevRec;
+    std::vector<int> tab(tiles_at, 0);
+    for (int m = 0; m < nmarks; ++m) {
+        const int64_t* r = marks + (size_t)m * kMarkRec;
+        MarkDev d{};
+        if (r[0] != kMarkStrip && r[0] != kMarkMask && r[0] != kMarkLine) return fail(h, SPECMI_ERR_ARG, "mark %d: unknown kind %lld", m, (long long)r[0]);
+        if (r[1] < 0 || r[1] > 0xffffff) return fail(h, SPECMI_ERR_ARG, "mark %d: colour %lld is not r | g << 8 | b << 16", m, (long long)r[1]);
+        d.kind = (int)r[0]; d.rgb = (unsigned)r[1];
+        if (d.kind == kMarkStrip) {
+            d.a = (int)std::min<int64_t>(std::max<int64_t>(r[2], 0), kMarkMaxSide);       // the kernel writes rows below H only
+            d.b = (int)std::min<int64_t>(std::max<int64_t>(r[3], 0), kMarkMaxSide);
+        } else if (d.kind == kMarkMask) {
+            if (!masks) return fail(h, SPECMI_ERR_ARG, "mark %d is a mask blend, but the mask buffer is a null pointer", m);
+            if (r[4] < 1 || r[4] > kMarkMaxMaskSide || r[5] < 1 || r[5] > kMarkMaxMaskSide)
+                return fail(h, SPECMI_ERR_ARG, "mark %d: a mask of %lld x %lld (1 .. %d per side)", m, (long long)r[4], (long long)r[5], kMarkMaxMaskSide);
+            if (r[2] < -kMarkMaxMaskPos || r[2] > kMarkMaxMaskPos || r[3] < -kMarkMaxMaskPos || r[3] > kMarkMaxMaskPos)
+                return fail(h, SPECMI_ERR_ARG, "mark %d: mask position (%lld, %lld) outside [-%d, %d]", m, (long long)r[2], (long long)r[3], kMarkMaxMaskPos, kMarkMaxMaskPos);
+            if (r[6] < 0 || (uint64_t)r[6] > mask_bytes || (uint64_t)(r[4] * r[5]) > mask_bytes - (uint64_t)r[6])
+                return fail(h, SPECMI_ERR_ARG, "mark %d: its mask leaves the mask buffer of %zu bytes", m, mask_bytes);
+            d.a = (int)r[2]; d.b = (int)r[3]; d.c = (int)r[4]; d.d = (int)r[5]; d.off = r[6];
+        } else {
+            for (int k = 2; k < 6; ++k)
+                if (r[k] < -kMarkMaxCoord || r[k] > kMarkMaxCoord)
+                    return fail(h, SPECMI_ERR_ARG, "mark %d: line end point %lld outside [-%d, %d]", m, (long long)r[k], kMarkMaxCoord, kMarkMaxCoord);
+            if (r[6] < kMarkMinWidth || r[6] > kMarkMaxWidth) return fail(h, SPECMI_ERR_ARG, "mark %d: line width %lld (%d .. %d)", m, (long long)r[6], kMarkMinWidth, kMarkMaxWidth);
+            marks_line_edges((int)r[2], (int)r[3], (int)r[4], (int)r[5], (int)r[6], d.e);
+        }
+        std::memcpy(tab.data() + marks_at + (size_t)m * kMarkDevRec, &d, sizeof(d));
+    }
+    std::vector<ByteRect> rects((size_t)nframes);
+    std::vector<unsigned char> hit;
+    long long ntiles = 0;
+    for (int f = 0; f < nframes; ++f) {
+        const int H = frame_geom[4 * f], W = frame_geom[4 * f + 1], mark0 = frame_geom[4 * f + 2], count = frame_geom[4 * f + 3];
+        const int64_t off = frame_offsets[2 * f], pitch = frame_offsets[2 * f + 1];
+        if (H < 1 || W < 1 || H > kMarkMaxSide || W > kMarkMaxSide) return fail(h, SPECMI_ERR_ARG, "frame %d: %d x %d pixels (1 .. %d per side)", f, H, W, kMarkMaxSide);
+        if (count < 0 || mark0 < 0 || (long long)mark0 + count > nmarks)
+            return fail(h, SPECMI_ERR_ARG, "frame %d: marks %d .. %lld leave the call's %d", f, mark0, (long long)mark0 + count, nmarks);
+        if (pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "frame %d: a pitch of %lld bytes for rows of %d", f, (long long)pitch, 3 * W);
+        if (off < 0 || (double)off + (double)(H - 1) * (double)pitch + 3.0 * W > (double)slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "frame %d: its rectangle leaves the slab of %zu bytes", f, slab_bytes);
+        MarkFrame r{};
+        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal frames give equal records
+        r.off = off; r.pitch = H > 1 ? pitch : 3LL * W; r.H = H; r.W = W; r.mark0 = mark0; r.count = count;
+        std::memcpy(tab.data() + (size_t)f * kMarkFrameRec, &r, sizeof(r));
+        rects[f] = ByteRect{off, r.pitch, 3LL * W, H};
+        if (!count) continue;
+        // the tiles some mark of this frame can reach: a superset is harmless (a tile's threads write only covered pixels)
+        const int tx_n = (W + kMarkTileW - 1) / kMarkTileW, ty_n = (H + kMarkTileH - 1) / kMarkTileH;
+        hit.assign((size_t)tx_n * ty_n, 0);
+        const auto span = [&](int y, int xa, int xb) {          // row y, columns xa .. xb: clipped here
+            xa = std::max(xa, 0); xb = std::min(xb, W - 1);
+            if (y < 0 || y >= H || xa > xb) return;
+            std::memset(hit.data() + (size_t)(y / kMarkTileH) * tx_n + xa / kMarkTileW, 1, (size_t)(xb / kMarkTileW - xa / kMarkTileW + 1));
+        };
+        for (int m = mark0; m < mark0 + count; ++m) {
+            MarkDev d;
+            std::memcpy(&d, tab.data() + marks_at + (size_t)m * kMarkDevRec, sizeof(d));
+            if (d.kind == kMarkStrip) {
+                for (int y = d.a; y < std::min(d.b, H); y = (y / kMarkTileH + 1) * kMarkTileH) span(y, 0, W - 1);
+            } else if (d.kind == kMarkMask) {
+                for (int y = std::max(d.b, 0); y < std::min(d.b + d.d, H); y = (y / kMarkTileH + 1) * kMarkTileH) span(y, d.a, d.a + d.c - 1);
+            } else {
+                int ylo = H, yhi = -1;
+                for (int i = 0; i < 4; ++i) {
+                    if (d.e[i].horiz) span(d.e[i].ymin, d.e[i].xmin, d.e[i].xmax);
+                    else { ylo = std::min(ylo, d.e[i].ymin); yhi = std::max(yhi, d.e[i].ymax); }
+                }
+                for (int y = std::max(ylo, 0); y <= std::min(yhi, H - 1); ++y) {
+                    int xa, xb;
+                    mark_line_span(d.e, y, xa, xb);
+                    if (xa <= xb) span(y, xa - 1, xb + 1);
+                }
+            }
+        }
+        for (int t = 0; t < tx_n * ty_n; ++t)
+            if (hit[t]) {
+                tab.push_back(f);
+                tab.push_back((t / tx_n) << 16 | (t % tx_n));
+                ++ntiles;
+            }
+        if (ntiles >= (1LL << 30)) return fail(h, SPECMI_ERR_ARG, "the marks reach 2^30 tiles of %d x %d pixels or more", kMarkTileW, kMarkTileH);
+    }
+    {   // no two frames share a byte: sorted by first byte, a frame is compared with those that start before it ends
+        std::vector<int> order((size_t)nframes);
+        for (int f = 0; f < nframes; ++f) order[f] = f;
+        std::sort(order.begin(), order.end(), [&](int x, int y) { return rects[x].off < rects[y].off; });
+        for (int i = 0; i < nframes; ++i)
+            for (int j = i + 1; j < nframes && rects[order[j]].off < rects[order[i]].end(); ++j)
+                if (rects_overlap(rects[order[i]], rects[order[j]]))
+                    return fail(h, SPECMI_ERR_ARG, "frames %d and %d share a byte", order[i], order[j]);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const bool regrown = tab.size() * 4 > h->marks_tab_bytes;
+    if (regrown || tab != h->marks_host) {
+        // rewriting the table needs a whole-device synchronise, which would invalidate a capture under way on this stream: ask first
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone)
+            return fail(h, SPECMI_ERR_STATE, "new frame or mark records are not possible while the stream is being captured: "
+                        "run one eager call with these records first (nothing was enqueued)");
+    }
+    int rc;
+    if ((rc = grow_ragged(h, (void**)&h->marks_tab, &h->marks_tab_bytes, tab.size() * 4, "the marks table"))) return rc;
+    if (regrown || tab != h->marks_host) {
+        // a drawing enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
+        if (!regrown && (rc = sync_for_growth(h, "the marks table"))) return rc;
+        h->marks_host.swap(tab);
+        HIPCHK(h, hipMemcpyAsync(h->marks_tab, h->marks_host.data(), h->marks_host.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    MarksArgs a{};
+    a.frames = (const MarkFrame*)h->marks_tab; a.marks = (const MarkDev*)(h->marks_tab + marks_at); a.tiles = h->marks_tab + tiles_at;
+    a.masks = masks; a.slab = slab; a.ntiles = (int)ntiles;
+    LaunchCtx ctx{s, &h->prof, "render.marks"};
+    LAUNCHCHK(h, launch_draw_marks(a, (double)ntiles * kMarkTileW * kMarkTileH, ctx), "draw_marks");
+    return SPECMI_OK;
+}
+
+int specmi_denormalize_u8(specmi_handle* h, const float* x, int B, int Hp, int Wp, int index, int H, int W, const float* mean3,
+                          const float* std3, uint8_t* slab, size_t slab_bytes, int64_t offset, int64_t pitch, void* stream) {
+    ENTER(h);
+    if (!x || !slab) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (B < 1 || Hp < 1 || Wp < 1 || Hp > 32768 || Wp > 32768) return fail(h, SPECMI_ERR_ARG, "a batch of %d images of %d x %d (1 .. 32768 per side)", B, Hp, Wp);
+    if (index < 0 || index >= B) return fail(h, SPECMI_ERR_ARG, "image %d of %d", index, B);
+    if (H < 1 || H > Hp || W < 1 || W > Wp) return fail(h, SPECMI_ERR_ARG, "a frame of %d x %d out of an image of %d x %d", H, W, Hp, Wp);
+    if (pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "a pitch of %lld bytes for rows of %d", (long long)pitch, 3 * W);
+    if (offset < 0 || (double)offset + (double)(H - 1) * (double)pitch + 3.0 * W > (double)slab_bytes)
+        return fail(h, SPECMI_ERR_ARG, "the frame's rectangle leaves the slab of %zu bytes", slab_bytes);
+    static const float kMean[3] = {0.485f, 0.456f, 0.406f}, kStd[3] = {0.229f, 0.224f, 0.225f};     // ImageNet's, as pare's denormalize_images
+    DenormArgs a{};
+    a.plane = (long long)Hp * Wp;
+    a.x = x + (size_t)index * 3 * (size_t)a.plane; a.out = slab + offset; a.pitch = pitch; a.h = H; a.w = W; a.Wp = Wp;
+    for (int c = 0; c < 3; ++c) {
+        a.mean[c] = mean3 ? mean3[c] : kMean[c]; a.std[c] = std3 ? std3[c] : kStd[c];
+        if (!std::isfinite(a.mean[c]) || !std::isfinite(a.std[c])) return fail(h, SPECMI_ERR_ARG, "mean and std must be finite");
+    }
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "render.denormalize"};
+    LAUNCHCHK(h, launch_denormalize_u8(a, ctx), "denormalize_u8");
     return SPECMI_OK;
 }
 

@@ -183,6 +183,10 @@ struct specmi_handle {
     int* draw_tab = nullptr;
     size_t draw_tab_bytes = 0;
     std::vector<int> draw_host;         // host image of draw_tab as last uploaded
+    // specmi_draw_marks: the frame records, the marks and the tile list, same growth and upload rules as ragged_tab
+    int* marks_tab = nullptr;
+    size_t marks_tab_bytes = 0;
+    std::vector<int> marks_host;        // host image of marks_tab as last uploaded
     // specmi_jpeg_encode: the picture records and the quality's tables, same growth and upload rules as ragged_tab; coefficients,
     // bit counts, the unstuffed scans and the chunk sums (jpeg_ws_layout), grows like ragged_tmp
     int* jpeg_tab = nullptr;

@@ -530,6 +530,70 @@ int draw_frame_tiles(int H, int W, int* tiles_x);
 int launch_draw_skeletons(const DrawArgs& a, int total_tiles, double kp_bytes, double px, const LaunchCtx& ctx);
 
 // ----------------------------------------------------------------------------------------
+// horizon lines and captions: strips, mask blends, Pillow's wide line; denormalised frames  (marks.hip)
+// ----------------------------------------------------------------------------------------
+// THE MARK RECORD of specmi_draw_marks as the caller writes it (include/specmi.h states the same): kMarkRec int64 per mark,
+//   [kind, r | g << 8 | b << 16, p0 .. p5] with  strip: p0 = y0, p1 = y1 (rows [y0, y1));
+//   mask blend: p0 = x, p1 = y, p2 = mw, p3 = mh, p4 = byte offset of the mask in the mask buffer;
+//   wide line: p0 .. p3 = x0, y0, x1, y1, p4 = width.  Unused parameters are ignored.
+constexpr int kMarkStrip = 0, kMarkMask = 1, kMarkLine = 2, kMarkRec = 8;
+constexpr int kMarkMaxSide = 8192, kMarkMinWidth = 2, kMarkMaxWidth = 64, kMarkMaxCoord = 100000, kMarkMaxMaskSide = 8192, kMarkMaxMaskPos = 16383;
+constexpr int kMarkTileW = 64, kMarkTileH = 16;       // one 256-thread workgroup: a wavefront per row, four rows per thread
+// One edge of a wide line's quadrilateral as Pillow's add_edge keeps it; dx = (float)(x1 - x0) / (float)(y1 - y0), 0 when horiz
+struct MarkEdge { int ymin, ymax, x0, y0; float dx; int xmin, xmax, horiz; };
+// One mark as the device reads it (40 ints).  strip: a = y0, b = y1; mask: a = x, b = y, c = mw, d = mh, off; line: e[4]
+struct MarkDev { int kind; unsigned rgb; int a, b, c, d; long long off; MarkEdge e[4]; };
+constexpr int kMarkDevRec = sizeof(MarkDev) / 4;
+// One frame (8 ints): byte offset of its first pixel, bytes from row to row, size, its marks mark0 .. mark0 + count - 1
+struct MarkFrame { long long off, pitch; int H, W, mark0, count; };
+constexpr int kMarkFrameRec = sizeof(MarkFrame) / 4;
+// One call as the kernel reads it.  frames, marks and tiles are the three parts of the handle's marks table; a tile is two ints:
+// its frame, and tile row << 16 | tile column
+struct MarksArgs {
+    const MarkFrame* frames;
+    const MarkDev* marks;
+    const int* tiles;
+    const unsigned char* masks;
+    unsigned char* slab;
+    int ntiles;
+};
+// Pillow's ROUND_UP / ROUND_DOWN on an fp32 value: the + 0.5F is an fp32 addition.  |f| stays far below 2^31 here
+__host__ __device__ inline int mark_ru(float f) { return (int)(f >= 0.f ? floorf(f + 0.5f) : -floorf(fabsf(f) + 0.5f)); }
+__host__ __device__ inline int mark_rd(float f) { return (int)(f >= 0.f ? ceilf(f - 0.5f) : -ceilf(fabsf(f) - 0.5f)); }
+// where edge e crosses row y: a separately rounded fp32 multiply and add, as Pillow's x86 build evaluates it - never an FMA.
+// The pragma is what keeps the two apart on host and device alike: HIP's __fmul_rn / __fadd_rn are a plain * and + to the
+// compiler, which contracts them under the build's default -ffp-contract=fast
+__host__ __device__ inline float mark_edge_x(const MarkEdge& e, int y) {
+#pragma clang fp contract(off)
+    const float p = (float)(y - e.y0) * e.dx;
+    return p + (float)e.x0;
+}
+// the span [xa, xb] (unclipped; xa > xb: none) that the non-horizontal edges of a line give row y: RU(min xx) .. RD(max xx)
+// over the edges with ymin <= y <= ymax.  One function for the kernel and for the host's tile list
+__host__ __device__ inline void mark_line_span(const MarkEdge* e, int y, int& xa, int& xb) {
+    float lo = 3.0e38f, hi = -3.0e38f;
+    bool any = false;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (!e[i].horiz && y >= e[i].ymin && y <= e[i].ymax) {
+            const float xx = mark_edge_x(e[i], y);
+            lo = fminf(lo, xx); hi = fmaxf(hi, xx);
+            any = true;
+        }
+    xa = any ? mark_ru(lo) : 1;
+    xb = any ? mark_rd(hi) : 0;
+}
+int launch_draw_marks(const MarksArgs& a, double px, const LaunchCtx& ctx);
+struct DenormArgs {
+    const float* x;             // image `index` of (B, 3, Hp, Wp): already offset to it
+    unsigned char* out;         // the frame's first pixel
+    long long pitch, plane;     // bytes per output row; Hp * Wp
+    int h, w, Wp;
+    float mean[3], std[3];
+};
+int launch_denormalize_u8(const DenormArgs& a, const LaunchCtx& ctx);
+
+// ----------------------------------------------------------------------------------------
 // baseline JPEG encoder  (jpeg.hip)
 // ----------------------------------------------------------------------------------------
 constexpr int kJpegHeaderBytes = 623;

@@ -255,6 +255,77 @@ def check_draw_skeletons(Mtot, J, D, bones, geom, offsets, slab_bytes, style=Non
     return bones.astype(np.int32), geom.astype(np.int32), offsets, style
 
 
+def check_draw_marks(geom, offsets, marks, slab_bytes, mask_bytes=0):
+    """Every refusal of ``specmi_draw_marks`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom`` (n, 4)
+    [H, W, mark0, count], ``offsets`` (n, 2) [byte offset, pitch], ``marks`` (nmarks, 8) [kind, r | g << 8 | b << 16, p0 .. p5]
+    (strip: y0, y1; mask blend: x, y, mw, mh, byte offset in the mask buffer; wide line: x0, y0, x1, y1, width) and the sizes of
+    the slab and of the mask buffer.  -> the arrays as the library reads them (int32, int64, int64).  Needs no device."""
+    geom, offsets = np.ascontiguousarray(geom, dtype=np.int64), np.ascontiguousarray(offsets, dtype=np.int64)
+    marks = np.ascontiguousarray(marks, dtype=np.int64)
+    if marks.size == 0:
+        marks = marks.reshape(0, _lib.MARK_REC)
+    n = geom.shape[0] if geom.ndim == 2 else -1
+    if geom.ndim != 2 or geom.shape[1] != 4 or tuple(offsets.shape) != (n, 2):
+        raise ValueError('frames: geom (n, 4) and offsets (n, 2) with one row per frame')
+    if marks.ndim != 2 or marks.shape[1] != _lib.MARK_REC:
+        raise ValueError(f'marks: (nmarks, {_lib.MARK_REC}) [kind, colour, p0 .. p5]')
+    if not 1 <= n <= 65535:
+        raise ValueError(f'1 to 65535 frames per call, got {n}')
+    nmarks = marks.shape[0]
+    if nmarks >= 1 << 31:
+        raise ValueError('2^31 marks or more')
+    H, W, mark0, count = geom.T
+    off, pitch = offsets.T
+    if ((H < 1) | (H > _lib.MARK_MAX_SIDE) | (W < 1) | (W > _lib.MARK_MAX_SIDE)).any():
+        raise ValueError(f'a frame of 1 .. {_lib.MARK_MAX_SIDE} pixels per side')
+    if ((count < 0) | (mark0 < 0) | (mark0 + count > nmarks)).any():
+        raise ValueError(f'a mark range leaves the call\'s {nmarks} marks')
+    if (pitch < 3 * W).any():
+        raise ValueError('a pitch below 3 * W bytes')
+    if (off < 0).any() or (off + (H - 1) * pitch + 3 * W > slab_bytes).any():
+        raise ValueError(f'a frame rectangle leaves the slab of {slab_bytes} bytes')
+    kind, rgb = marks[:, 0], marks[:, 1]
+    if (~np.isin(kind, (_lib.MARK_STRIP, _lib.MARK_MASK, _lib.MARK_LINE))).any():
+        raise ValueError('an unknown mark kind (MARK_STRIP, MARK_MASK, MARK_LINE)')
+    if ((rgb < 0) | (rgb > 0xffffff)).any():
+        raise ValueError('a colour is r | g << 8 | b << 16')
+    ln, mk = marks[kind == _lib.MARK_LINE], marks[kind == _lib.MARK_MASK]
+    if ((ln[:, 6] < _lib.MARK_MIN_WIDTH) | (ln[:, 6] > _lib.MARK_MAX_WIDTH)).any():
+        raise ValueError(f'a line width outside {_lib.MARK_MIN_WIDTH} .. {_lib.MARK_MAX_WIDTH}')
+    if (np.abs(ln[:, 2:6]) > _lib.MARK_MAX_COORD).any():
+        raise ValueError(f'a line end point outside [-{_lib.MARK_MAX_COORD}, {_lib.MARK_MAX_COORD}]')
+    if ((mk[:, 4:6] < 1) | (mk[:, 4:6] > _lib.MARK_MAX_MASK_SIDE)).any():
+        raise ValueError(f'a mask of 1 .. {_lib.MARK_MAX_MASK_SIDE} bytes per side')
+    if (np.abs(mk[:, 2:4]) > _lib.MARK_MAX_MASK_POS).any():
+        raise ValueError(f'a mask position outside [-{_lib.MARK_MAX_MASK_POS}, {_lib.MARK_MAX_MASK_POS}]')
+    if ((mk[:, 6] < 0) | (mk[:, 6] + mk[:, 4] * mk[:, 5] > mask_bytes)).any():
+        raise ValueError(f'a mask leaves the mask buffer of {mask_bytes} bytes')
+    rects = [(int(o), int(p) if h > 1 else 3 * int(w), 3 * int(w), int(h)) for o, p, w, h in zip(off, pitch, W, H)]
+    order = sorted(range(n), key=lambda f: rects[f][0])
+    for i, a in enumerate(order):
+        end = rects[a][0] + (rects[a][3] - 1) * rects[a][1] + rects[a][2]
+        for b in order[i + 1:]:
+            if rects[b][0] >= end:
+                break
+            if _rects_overlap(rects[a], rects[b]):
+                raise ValueError(f'frames {a} and {b} share a byte')
+    return geom.astype(np.int32), offsets, marks
+
+
+# Which route panel 0 of the pictures takes (render_image_group, render_image_groups, SPECTester, evaluation.save_batch_picture):
+# False = render.group_panel0 draws the horizon line and caption per frame on the host with Pillow - a download of a device
+# frame, a Pillow raster and an upload each (route (a)), True = uint8 frames go up raw and ONE specmi_draw_marks call per flush
+# draws them in the slab (route (b), DESIGN.md 7 f-13).  Same bytes either way; the default is (b) only where it is faster than (a)
+# beyond the spread between repeats of the same run - and for eight 1080 x 1920 frames, host frames to the finished slab, it is
+# 4.7 x faster (7.8 against 36.8 ms per flush, spread 0.4; the launch itself takes 10 us: profiles/horizon_panel_aux.json).
+PANEL0_DEVICE_DEFAULT = True
+
+
+def flow_panel0_device(panel0_device=None) -> bool:
+    """``panel0_device`` (the flow's private switch) decides, None = the default."""
+    return PANEL0_DEVICE_DEFAULT if panel0_device is None else bool(panel0_device)
+
+
 # Which route the pictures the flows write as .jpg / .jpeg take (SPECTester._write_pictures, render_image_group(save_filename=),
 # panorama.write_tree, evaluation.save_batch_picture): False = the raw picture comes down and Pillow encodes it on the host (route
 # (a)), True = specmi_jpeg_encode encodes it where it lies and only the file's bytes come down (route (b), DESIGN.md 7 f-12).
@@ -848,6 +919,52 @@ class Engine:
             self.h, _ptr(kp), Mtot, J, D, bones.ctypes.data_as(_lib.c_int32_p) if bones.shape[0] else None, int(bones.shape[0]), C.byref(style),
             _ptr(slab), slab.numel(), geom.ctypes.data_as(_lib.c_int32_p), offsets.ctypes.data_as(_lib.c_int64_p), int(geom.shape[0]),
             self._stream()))
+        return slab
+
+    def draw_marks(self, slab, geom, offsets, marks, masks=None):
+        """``specmi_draw_marks``: strips, mask blends and Pillow's wide lines drawn in place into the frames of ``slab`` (1-D
+        uint8 on the engine device; what ``pack_frames`` builds, or the panel-0 columns of pictures), every frame of the call in
+        one launch.  Host arrays: ``geom`` (n, 4) [H, W, mark0, count], ``offsets`` (n, 2) [byte offset, pitch] and ``marks``
+        (nmarks, 8) int64 [kind, r | g << 8 | b << 16, p0 .. p5] (``check_draw_marks``; ``render.horizon_marks`` builds the marks
+        of a horizon line).  ``masks``: the 1-D uint8 device buffer the mask blends index (None: no mask blend).  Returns
+        ``slab``.  Everything the host arrays decide is checked here, before the library is called."""
+        d = self.device
+        if not isinstance(slab, torch.Tensor) or slab.device != d or slab.dtype != torch.uint8 or slab.dim() != 1 or not slab.is_contiguous():
+            raise ValueError('slab must be a contiguous 1-D uint8 tensor on the engine device')
+        if masks is not None and (not isinstance(masks, torch.Tensor) or masks.device != d or masks.dtype != torch.uint8 or masks.dim() != 1
+                                  or not masks.is_contiguous()):
+            raise ValueError('masks must be a contiguous 1-D uint8 tensor on the engine device')
+        geom, offsets, marks = check_draw_marks(geom, offsets, marks, slab.numel(), 0 if masks is None else masks.numel())
+        _lib.check(self.h, self.lib.specmi_draw_marks(
+            self.h, _ptr(slab), slab.numel(), geom.ctypes.data_as(_lib.c_int32_p), offsets.ctypes.data_as(_lib.c_int64_p), int(geom.shape[0]),
+            marks.ctypes.data_as(_lib.c_int64_p) if marks.shape[0] else None, int(marks.shape[0]), _ptr(masks),
+            0 if masks is None else masks.numel(), self._stream()))
+        return slab
+
+    def denormalize_u8(self, x, index, H, W, slab=None, offset=0, pitch=None, mean=None, std=None):
+        """``specmi_denormalize_u8``: image ``index`` of ``x`` (B, 3, Hp, Wp) fp32 on the engine device, cut to its top-left
+        ``H`` x ``W``, as an HWC uint8 frame at byte ``offset`` / ``pitch`` (None = 3 W) of ``slab`` (1-D uint8; None: a new
+        slab of that one frame).  v = (x * std + mean) * 255 in fp32, NaN -> 0, clamped to [0, 255], truncated; ``mean`` /
+        ``std`` None = ImageNet's.  Returns ``slab``."""
+        d = self.device
+        if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3 or not x.is_contiguous():
+            raise ValueError('x must be a contiguous (B, 3, Hp, Wp) float32 tensor on the engine device')
+        H, W, index, offset = int(H), int(W), int(index), int(offset)
+        pitch = 3 * W if pitch is None else int(pitch)
+        B, _, Hp, Wp = (int(v) for v in x.shape)
+        if not (0 <= index < B and 1 <= H <= Hp and 1 <= W <= Wp and pitch >= 3 * W and offset >= 0):
+            raise ValueError(f'image {index} of {B}, {H} x {W} of {Hp} x {Wp}, pitch {pitch}, offset {offset}')
+        if slab is None:
+            slab = torch.empty(offset + (H - 1) * pitch + 3 * W, device=d, dtype=torch.uint8)
+        elif not isinstance(slab, torch.Tensor) or slab.device != d or slab.dtype != torch.uint8 or slab.dim() != 1 or not slab.is_contiguous():
+            raise ValueError('slab must be a contiguous 1-D uint8 tensor on the engine device')
+        if offset + (H - 1) * pitch + 3 * W > slab.numel():
+            raise ValueError(f'the frame leaves the slab of {slab.numel()} bytes')
+        f3 = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(3)
+        mean, std = f3(mean), f3(std)
+        as_p = lambda v: None if v is None else v.ctypes.data_as(_lib.c_float_p)
+        _lib.check(self.h, self.lib.specmi_denormalize_u8(self.h, _ptr(x), B, Hp, Wp, index, H, W, as_p(mean), as_p(std), _ptr(slab),
+                                                           slab.numel(), offset, pitch, self._stream()))
         return slab
 
     def jpeg_encode_into(self, slab, out_slab, geom, offsets, quality=75, sizes=None):

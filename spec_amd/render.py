@@ -7,8 +7,9 @@ pose and pyrender's intrinsics) is the reference's, and coverage and visibility 
 bit (tests/render_ref.py).  The look is NOT pyrender's: shading is ``rgb * min(1, 0.3 + 0.7 max(0, n.l))``, the side view's
 ground plane is an analytic two-grey checker of 0.5 m tiles (the reference's ``get_checkerboard_plane`` lives in the un-vendored
 ``pare``), the colour table below is a stand-in for ``pare``'s ``get_colors`` and there is no alpha blending.  Triangles that
-reach behind the near plane (z <= 0.05) are dropped, not clipped.  The horizon line and its caption are drawn on the host with
-Pillow exactly as ``camcalib/vis_utils.py:63-110`` does.
+reach behind the near plane (z <= 0.05) are dropped, not clipped.  The horizon line and its caption are drawn exactly as
+``camcalib/vis_utils.py:63-110`` does: on the host with Pillow (``show_horizon_line``), or - the ``panel0_device`` route - on the
+device by ``specmi_draw_marks`` (spec_amd/csrc/marks.hip; ``horizon_marks``, ``show_horizon_lines``), byte for byte the same.
 
 The 2D keypoint skeleton (``render_image_group(keypoints_2d=...)``, ``draw_skeleton``) is painted on the device by
 ``specmi_draw_skeletons`` (spec_amd/csrc/draw.hip).  ``pare.utils.vis_utils.draw_skeleton``, ``kp_utils.get_spin_skeleton`` and
@@ -100,6 +101,130 @@ def show_horizon_line(image, vfov, pitch, roll, focal_length=-1, color=(0, 255, 
     return np.array(im), ctr / h
 
 
+_caption_cache = {}
+
+
+def caption_mask(text):
+    """The coverage mask Pillow's ``ImageDraw.text`` blends for ``text`` on an RGB image in its default font - whatever font and
+    layout engine the installation has: ``getmask2(text, 'L', anchor='la')``.  -> ((mh, mw) uint8 array, (x, y) offset of its
+    corner from the text position); cached by text."""
+    hit = _caption_cache.get(text)
+    if hit is None:
+        from PIL import Image, ImageDraw
+        font = ImageDraw.Draw(Image.new('RGB', (1, 1))).getfont()
+        core, offset = font.getmask2(text, 'L', anchor='la')
+        mw, mh = core.size
+        mask = np.frombuffer(bytes(Image.Image()._new(core).tobytes()), np.uint8).reshape(mh, mw) if mw and mh else np.zeros((0, 0), np.uint8)
+        if len(_caption_cache) >= 4096:
+            _caption_cache.clear()
+        hit = _caption_cache[text] = (mask, (int(offset[0]), int(offset[1])))
+    return hit
+
+
+def _pack_rgb(c) -> int:
+    return int(c[0]) | int(c[1]) << 8 | int(c[2]) << 16
+
+
+def horizon_marks(H, W, vfov, pitch, roll, focal_length=-1, color=(0, 255, 0), width=5, debug=False, GT=False, text_size=16, dtype=np.uint8):
+    """One ``show_horizon_line`` call on an (H, W, 3) image as marks for ``Engine.draw_marks``: -> (marks (k, 8) int64 - the
+    caption strip, the caption's mask blend (its mask at byte 0 of a mask buffer: the caller adds where it packs it), the wide
+    line, in the reference's order -, the caption's (mask (mh, mw) uint8, offset) or None without ``debug``, ``ctr / h``).  The
+    float64 arithmetic is the reference's (vis_utils.py:86-88: ``np.tan``, then C truncation of the end points), the caption its
+    format, the mask the installed Pillow's (``caption_mask``).  -> None where the device route cannot reproduce the host: a
+    non-finite end point or one beyond +-100000 (``_lib.MARK_MAX_COORD``), ``width`` < 2 (Pillow's Bresenham line) or > 64,
+    ``text_size`` > H (the reference's negative slice wraps) or < 0, a colour that is not three integers in 0 .. 255, a frame
+    beyond 8192 pixels per side, or an image ``dtype`` other than uint8 (the reference converts a float image first)."""
+    h, w = int(H), int(W)
+    if np.dtype(dtype) != np.uint8 or not (1 <= h <= _lib.MARK_MAX_SIDE and 1 <= w <= _lib.MARK_MAX_SIDE):
+        return None
+    try:
+        rgb = tuple(int(c) for c in color)
+        if isinstance(color, str) or len(rgb) != 3 or any(c != k or not 0 <= c <= 255 for c, k in zip(rgb, color)):
+            return None
+    except (TypeError, ValueError):
+        return None
+    if not (isinstance(width, (int, np.integer)) and _lib.MARK_MIN_WIDTH <= width <= _lib.MARK_MAX_WIDTH):
+        return None
+    if debug and not (isinstance(text_size, (int, np.integer)) and 0 <= text_size <= h):
+        return None
+    with np.errstate(all='ignore'):
+        ctr = h * (0.5 - 0.5 * np.tan(pitch) / np.tan(vfov / 2))
+        left, right = ctr - w * np.tan(roll) / 2, ctr + w * np.tan(roll) / 2
+    if not (np.isfinite(left) and np.isfinite(right)) or max(abs(float(left)), abs(float(right))) >= _lib.MARK_MAX_COORD + 1:
+        return None
+    marks, caption = [], None
+    if debug:
+        top = h - text_size if GT else 0
+        marks.append([_lib.MARK_STRIP, 0, top, top + text_size, 0, 0, 0, 0])
+        text = ('GT: ' if GT else '') + 'vfov:{0:.1f}, pitch:{1:.1f}, roll:{2:.1f}, f_pix:{3:.1f}'.format(
+            np.degrees(vfov), np.degrees(pitch), np.degrees(roll), focal_length)
+        caption = caption_mask(text)
+        mask, (ox, oy) = caption
+        if mask.size:
+            if max(mask.shape) > _lib.MARK_MAX_MASK_SIDE:
+                return None
+            marks.append([_lib.MARK_MASK, 0xffffff, ox, top + oy, mask.shape[1], mask.shape[0], 0, 0])
+    marks.append([_lib.MARK_LINE, _pack_rgb(rgb), 0, int(left), w, int(right), int(width), 0])     # int(): C's truncation
+    return np.asarray(marks, np.int64).reshape(-1, _lib.MARK_REC), caption, ctr / h
+
+
+def plan_horizon_marks(sizes, params, dtypes=None):
+    """The host side of ``show_horizon_lines``: ``sizes`` [(H, W)] and ``params``, per frame None or a list of horizons, each a
+    dict of ``horizon_marks``' arguments (``vfov``, ``pitch``, ``roll`` and any of its keywords) or a (vfov, pitch, roll) tuple -
+    drawn in order, e.g. ground truth, then prediction.  -> (geom columns [mark0, count] (n, 2) int64, marks (nmarks, 8) int64,
+    the packed mask buffer (1-D uint8 host array: every distinct caption once), [[ctr / h per horizon] per frame]) - or None
+    where ``horizon_marks`` gives None for some horizon."""
+    ranges, rows, bufs, fracs, at, used = [], [], [], [], {}, 0
+    for k, ((H, W), hs) in enumerate(zip(sizes, params)):
+        first, fr = sum(r.shape[0] for r in rows), []
+        for hz in hs or ():
+            kw = dict(hz) if isinstance(hz, dict) else dict(zip(('vfov', 'pitch', 'roll'), hz))
+            got = horizon_marks(H, W, dtype=np.uint8 if dtypes is None else dtypes[k], **kw)
+            if got is None:
+                return None
+            marks, caption, frac = got
+            marks = marks.copy()
+            blend = marks[:, 0] == _lib.MARK_MASK
+            if blend.any():
+                key = id(caption[0])
+                if key not in at:
+                    at[key] = used
+                    bufs.append(caption[0].reshape(-1))
+                    used += caption[0].size
+                marks[blend, 6] = at[key]
+            rows.append(marks)
+            fr.append(frac)
+        ranges.append((first, sum(r.shape[0] for r in rows) - first))
+        fracs.append(fr)
+    marks = np.concatenate(rows) if rows else np.zeros((0, _lib.MARK_REC), np.int64)
+    masks = np.concatenate(bufs) if bufs else np.zeros(0, np.uint8)
+    return np.asarray(ranges, np.int64).reshape(-1, 2), marks, masks, fracs
+
+
+def show_horizon_lines(slab, sizes, offsets, params, engine=None):
+    """``show_horizon_line`` for the frames of a flush on the device: ``slab`` a 1-D uint8 device tensor holding the (H, W, 3)
+    frames ``sizes`` at ``offsets`` - (n,) byte offsets of packed frames (``pack_frames``) or (n, 2) [byte offset, pitch] -,
+    ``params`` as ``plan_horizon_marks`` takes them (a frame may carry several horizons, drawn in order).  All captions' masks
+    go up in ONE buffer and ONE ``Engine.draw_marks`` call draws every frame in place: byte for byte what the host function
+    makes.  -> [[ctr / h per horizon] per frame].  Raises ``ValueError`` for a horizon the device route cannot reproduce
+    (``horizon_marks`` -> None): callers keep the host route for such a frame."""
+    from . import cam_utils
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    plan = plan_horizon_marks(sizes, params)
+    if plan is None:
+        raise ValueError('a horizon that the device route cannot reproduce (render.horizon_marks gives None): keep the host route for it')
+    ranges, marks, masks, fracs = plan
+    if not marks.shape[0]:
+        return fracs
+    eng = engine or cam_utils._engine(slab.device)
+    offsets = np.asarray(offsets, np.int64)
+    if offsets.ndim == 1:
+        offsets = np.stack([offsets, 3 * np.asarray([w for _, w in sizes], np.int64)], axis=1)
+    geom = np.concatenate([np.asarray(sizes, np.int64).reshape(-1, 2), ranges], axis=1)
+    eng.draw_marks(slab, geom, offsets, marks, torch.from_numpy(masks).to(eng.device) if masks.size else None)
+    return fracs
+
+
 def write_obj(path: str, vertices, faces) -> str:
     """A Wavefront .obj with ``v`` and 1-based ``f`` records (17 significant digits are not needed: ``%.9g`` round-trips fp32)."""
     v, f = np.asarray(vertices, np.float32).reshape(-1, 3), np.asarray(faces, np.int64).reshape(-1, 3)
@@ -133,6 +258,43 @@ def group_panel0(image, cam_params=None) -> np.ndarray:
         image, _ = show_horizon_line(image, cam_params[0], cam_params[1], cam_params[2], focal_length=cam_params[3], color=(0, 255, 0),
                                      width=5, debug=True, text_size=30)
     return np.ascontiguousarray(image)
+
+
+def _panel0_horizon(cp):
+    """The horizon of ``group_panel0`` for ``cam_params`` = (vfov, pitch, roll, f_pix) as ``plan_horizon_marks`` takes it."""
+    return None if cp is None else [dict(vfov=cp[0], pitch=cp[1], roll=cp[2], focal_length=cp[3], color=(0, 255, 0), width=5, debug=True, text_size=30)]
+
+
+def _panel0_raw(image, cam_params):
+    """Can panel 0 of ``image`` be finished on the device?  -> the raw frame - a contiguous (H, W, 3) uint8 host array, or a
+    uint8 device tensor as it is - when it is uint8 and ``horizon_marks`` can reproduce its horizon; None: ``group_panel0``."""
+    if isinstance(image, torch.Tensor):
+        if image.dtype != torch.uint8 or image.dim() != 3 or image.shape[2] != 3:
+            return None
+        raw = image.detach() if image.device.type == 'cuda' else np.ascontiguousarray(image.detach().numpy())
+    else:
+        raw = np.asarray(image)
+        if raw.dtype != np.uint8 or raw.ndim != 3 or raw.shape[2] != 3:
+            return None
+        raw = np.ascontiguousarray(raw)
+    if plan_horizon_marks([raw.shape[:2]], [_panel0_horizon(cam_params)]) is None:
+        return None
+    return raw
+
+
+def _pack_raw(frames, device):
+    """``pack_frames`` for frames of which some lie on the device already: host frames go up, device frames are copied where
+    they lie.  -> the 1-D uint8 slab on ``device``."""
+    from .preprocess import pack_frames
+    if all(isinstance(f, np.ndarray) for f in frames):
+        return pack_frames(frames, device)[0]
+    slab = torch.empty(sum(int(f.shape[0]) * int(f.shape[1]) * 3 for f in frames), device=device, dtype=torch.uint8)
+    at = 0
+    for f in frames:
+        n = int(f.shape[0]) * int(f.shape[1]) * 3
+        slab[at:at + n].copy_((torch.from_numpy(f) if isinstance(f, np.ndarray) else f).reshape(-1))
+        at += n
+    return slab
 
 
 def _keypoints(kp, device, unnormalize=False, res=224) -> torch.Tensor:
@@ -177,7 +339,7 @@ def draw_skeleton(image, kp_2d, dataset='spin', unnormalize=True, thickness=2, r
 
 def render_image_group(image, camera_translation, vertices, camera_rotation, focal_length, camera_center, mesh_color='pinkish',
                        alpha=1.0, faces=None, mesh_filename: Optional[str] = None, save_filename: Optional[str] = None, keypoints_2d=None,
-                       cam_params: Optional[Sequence] = None, device=None, engine=None, jpeg_device=None):
+                       cam_params: Optional[Sequence] = None, device=None, engine=None, jpeg_device=None, panel0_device=None):
     """The three panels of ``render_image_group`` (renderer_cam.py:147-218) side by side, (H, 3W, 3) uint8 on the device:
 
     0. ``image`` (H, W, 3; uint8, or floats in [0, 1] / [0, 255] as the reference accepts) with - given ``cam_params`` =
@@ -195,15 +357,25 @@ def render_image_group(image, camera_translation, vertices, camera_rotation, foc
     (renderer_cam.py:74,87-90).  ``save_filename``: the image through Pillow (the reference's cv2.imwrite of the RGB-swapped
     array stores the same pixels); with ``jpeg_device`` (None = ``engine.JPEG_DEVICE_DEFAULT``) a ``.jpg`` / ``.jpeg`` name is
     encoded on the device (``save_picture``: the same bytes, and only they come down).  ``alpha`` is accepted and ignored: the
-    reference's material is ``alphaMode='OPAQUE'``."""
+    reference's material is ``alphaMode='OPAQUE'``.  ``panel0_device`` (None = ``engine.PANEL0_DEVICE_DEFAULT``): a uint8
+    ``image`` goes up raw - a device tensor does not come down at all - and the line and caption are drawn where it lies
+    (``show_horizon_lines``), before the skeleton and the meshes as on the host: the same bytes.  A float image, or a horizon
+    that ``horizon_marks`` cannot reproduce, keeps the host route."""
     from . import cam_utils
+    from .engine import flow_panel0_device
     if isinstance(image, torch.Tensor):
         device = device or (image.device if image.device.type == 'cuda' else None)
-        image = image.detach().cpu().numpy()
-    image = group_panel0(image, cam_params)
     dev = torch.device(device or 'cuda')
     eng = engine or cam_utils._engine(dev)
-    panel0 = torch.from_numpy(np.ascontiguousarray(image)).to(eng.device)
+    raw = _panel0_raw(image, cam_params) if flow_panel0_device(panel0_device) else None
+    if raw is not None:
+        panel0 = (torch.from_numpy(raw) if isinstance(raw, np.ndarray) else raw).to(eng.device, copy=True).contiguous()
+        if cam_params is not None:
+            H, W = int(panel0.shape[0]), int(panel0.shape[1])
+            show_horizon_lines(panel0.view(-1), [(H, W)], [0], [_panel0_horizon(cam_params)], engine=eng)
+    else:
+        image = group_panel0(image.detach().cpu().numpy() if isinstance(image, torch.Tensor) else image, cam_params)
+        panel0 = torch.from_numpy(np.ascontiguousarray(image)).to(eng.device)
     if keypoints_2d is not None:
         draw_skeleton(panel0, keypoints_2d, unnormalize=False, engine=eng)
     kw = dict(faces=faces, color=mesh_color, engine=eng, cull=_closed(faces))
@@ -322,12 +494,12 @@ def view_cams(view_frame, rotations, focals, centers) -> np.ndarray:
 
 def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, centers, cam_params=None, each=False, mesh_color='pinkish',
                         faces=None, pixel_budget=None, device=None, engine=None, return_slabs=False, keypoints_2d=None, encode=None,
-                        quality=75):
+                        quality=75, panel0_device=None):
     """``render_image_group`` for the frames of a flush in one call per chunk (``specmi_render_views``): ``frames`` a list of
     (H, W, 3) host images of any sizes, ``vertices`` (sum counts, V, 3) / ``cam_t`` (sum counts, 3) the detections frame after
     frame (device tensors stay on the device), ``counts`` the detections per frame, ``rotations`` (F, 3, 3), ``focals`` (F, 2),
     ``centers`` (F, 2) and ``cam_params`` (a list of (vfov, pitch, roll, f_pix) or None per frame) the frames' cameras.
-    Panel 0 is made per frame on the host (``group_panel0``: Pillow's horizon line); per chunk of ``plan_views`` the panels go
+    Panel 0 is made per frame on the host (``group_panel0``: Pillow's horizon line) or, with ``panel0_device``, in the slab; per chunk of ``plan_views`` the panels go
     up in ONE slab, ONE ``render_views`` call draws every panel of every picture in place, and ONE slab comes down.
     -> the list of (H, 3W, 3) uint8 host arrays, one per frame - ``each``: one per detection, that detection alone -, equal byte
     for byte to ``render_image_group`` on the same frame and meshes.  ``return_slabs``: also [(device slab, picture offsets,
@@ -338,9 +510,13 @@ def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, cent
     ``encode``: None, 'jpeg', or one of the two per frame.  A picture of a 'jpeg' frame comes back as the ``bytes`` of its JPEG
     file at ``quality`` instead of an array - encoded from the output slab where it lies by ONE ``Engine.jpeg_encode`` call per
     chunk, byte for byte what ``Image.fromarray(array).save(f, format='JPEG', quality=quality)`` writes; the raw slab does not
-    come down (only the pictures of frames that are not encoded do, one by one)."""
+    come down (only the pictures of frames that are not encoded do, one by one).
+    ``panel0_device`` (None = ``engine.PANEL0_DEVICE_DEFAULT``): uint8 frames go into the chunk's slab raw - a frame given as a
+    device tensor does not come down at all - and ONE ``draw_marks`` call per chunk (``show_horizon_lines``) draws their lines
+    and captions there, before the skeletons: the same bytes.  A float frame, or one whose horizon ``horizon_marks`` cannot
+    reproduce, keeps ``group_panel0``."""
     from . import cam_utils
-    from .preprocess import pack_frames
+    from .engine import flow_panel0_device
     frames = list(frames)
     cam_params = [None] * len(frames) if cam_params is None else list(cam_params)
     if not (len(frames) == len(counts) == len(cam_params)):
@@ -348,7 +524,9 @@ def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, cent
     encode = [encode] * len(frames) if encode is None or isinstance(encode, str) else list(encode)
     if len(encode) != len(frames) or any(e not in (None, 'jpeg') for e in encode):
         raise ValueError("encode: None, 'jpeg', or one of the two per frame")
-    panel0 = [group_panel0(im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else im, cp) for im, cp in zip(frames, cam_params)]
+    raw = [_panel0_raw(im, cp) for im, cp in zip(frames, cam_params)] if flow_panel0_device(panel0_device) else [None] * len(frames)
+    panel0 = [r if r is not None else group_panel0(im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else im, cp)
+              for r, im, cp in zip(raw, frames, cam_params)]
     dev = torch.device(device or (vertices.device if isinstance(vertices, torch.Tensor) and vertices.device.type == 'cuda' else 'cuda'))
     eng = engine or cam_utils._engine(dev)
     as_f32 = lambda x: torch.as_tensor(x).to(device=eng.device, dtype=torch.float32).contiguous()
@@ -356,14 +534,17 @@ def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, cent
     if vertices.dim() != 3 or vertices.shape[0] != sum(int(c) for c in counts):
         raise ValueError('vertices must be (sum of counts, V, 3)')
     table, rgb = device_faces(faces, eng.device), _rgb(mesh_color)
-    sizes = [p.shape[:2] for p in panel0]
+    sizes = [(int(p.shape[0]), int(p.shape[1])) for p in panel0]
     if keypoints_2d is not None:
         keypoints_2d = _keypoints(keypoints_2d, eng.device)
         if keypoints_2d.shape[0] != vertices.shape[0]:
             raise ValueError('keypoints_2d must be (sum of counts, J, D)')
     pictures, slabs = [], []
     for ch in plan_views(sizes, counts, each=each, pixel_budget=pixel_budget, cull=_closed(faces), frame_per_picture=each and keypoints_2d is not None):
-        in_slab, _, _ = pack_frames([panel0[f] for f in ch['frames']], eng.device)
+        in_slab = _pack_raw([panel0[f] for f in ch['frames']], eng.device)
+        if any(raw[f] is not None and cam_params[f] is not None for f in ch['frames']):
+            show_horizon_lines(in_slab, [sizes[f] for f in ch['frames']], ch['frame_offsets'],
+                               [_panel0_horizon(cam_params[f]) if raw[f] is not None else None for f in ch['frames']], engine=eng)
         if keypoints_2d is not None:
             hw = np.asarray([sizes[f] for f in ch['frames']], np.int64).reshape(-1, 2)
             eng.draw_skeletons(keypoints_2d, in_slab, np.concatenate([hw, ch['frame_dets']], axis=1),

@@ -103,6 +103,7 @@ class SPECTester:
         self._ragged_crops = None     # True: a flush's frames in one slab, one upload, one ragged crop launch; False: one of each per frame (same bits)
         self._render_batch = None     # True: a flush's pictures in one render_image_groups call; False: one render_image_group per frame (same bytes)
         self._jpeg_device = None      # True: .jpg / .jpeg pictures are encoded on the device and only the files' bytes come down (same bytes)
+        self._panel0_device = None    # True: the horizon line and caption of panel 0 are drawn on the device, uint8 frames go up raw (same bytes)
 
     def _build_model(self):
         c = self.model_cfg
@@ -187,7 +188,8 @@ class SPECTester:
         (``args.draw_keypoints``).  -> the files written."""
         from PIL import Image
         rot, focal, center, cam_params = self._frame_camera(img_fname, rgb.shape, output_path)
-        group = render.render_image_group(rgb, cam_t, vertices, rot, focal, center, cam_params=cam_params, device=self.device, keypoints_2d=keypoints)
+        group = render.render_image_group(rgb, cam_t, vertices, rot, focal, center, cam_params=cam_params, device=self.device, keypoints_2d=keypoints,
+                                          panel0_device=self._panel0_device)
         if flow_jpeg_device(self._jpeg_device) and is_jpeg_name(img_fname):       # encoded once, written once per detection
             H, W3 = int(group.shape[0]), int(group.shape[1])
             picture = cam_utils._engine(group.device).jpeg_encode(group.view(-1), [[H, W3]], [[0, 3 * W3]], 75)[0]
@@ -208,7 +210,8 @@ class SPECTester:
         cams = [self._frame_camera(f, rgb.shape, output_path) for (f, _, _), rgb in zip(pending, frames)]
         counts = [n for _, _, n in pending]
         groups = render.render_image_groups(frames, vertices, cam_t, counts, [c[0] for c in cams], [c[1] for c in cams], [c[2] for c in cams],
-                                            cam_params=[c[3] for c in cams], each=each, device=self.device, keypoints_2d=keypoints, encode=encode)
+                                            cam_params=[c[3] for c in cams], each=each, device=self.device, keypoints_2d=keypoints, encode=encode,
+                                            panel0_device=self._panel0_device)
         written, g = [], 0
         for img_fname, k0, n in pending:
             pictures = [as_picture(p) for p in groups[g:g + n]] if each else [as_picture(groups[g])] * n
@@ -248,7 +251,9 @@ class SPECTester:
         default: the pictures are then unchanged.
         ``self._jpeg_device`` (None = ``engine.JPEG_DEVICE_DEFAULT``): the pictures of ``.jpg`` / ``.jpeg`` frames are encoded on
         the device (``specmi_jpeg_encode``, Pillow's default quality 75) and only the files' bytes come down, on both routes; a
-        ``.png`` frame keeps the host route.  Same files, byte for byte."""
+        ``.png`` frame keeps the host route.  Same files, byte for byte.
+        ``self._panel0_device`` (None = ``engine.PANEL0_DEVICE_DEFAULT``): the horizon line and caption of panel 0 are drawn on
+        the device (``specmi_draw_marks``) instead of with Pillow on the host, on both routes.  Same files, byte for byte."""
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         image_file_names = list_images(image_folder)
