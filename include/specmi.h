@@ -370,6 +370,26 @@ int specmi_conv2d(specmi_handle* h, const float* x, int B, int H, int W, int Cin
                   int Cout, int KH, int KW, int stride, int pad, const float* residual,
                   int relu, float* out, void* stream);
 
+/* specmi_conv2d with everything the trunks' own launches vary: specmi_conv2d(...) is this call with ldx = Cin, ldo = Cout and
+ * no x2, bit for bit.  x is read as (B,H,W) pixels of ldx >= Cin floats of which the first Cin are the channels (the rest are
+ * never read); out, and residual if given, as (B,OH,OW) pixels of ldo >= Cout floats of which the first Cout are written
+ * (read); nothing else in those rows is touched.  x, out and residual are plain pointers: a channel offset into a wider map
+ * (HRNet's concat slices) is the caller's pointer arithmetic.  Optional second A source, the bottleneck's conv3 with its
+ * downsample folded in: x2 (B,H2,W2) pixels of ldx2 >= Cin2 floats, read at (oy*stride2, ox*stride2) and concatenated after x
+ * along K; w is then (Cout, Cin+Cin2, 1, 1) and the layer 1x1 / stride 1 / pad 0, (OH-1)*stride2 < H2, (OW-1)*stride2 < W2.
+ * Refused with SPECMI_ERR_ARG, nothing launched and the handle usable: ldx < Cin, ldo < Cout, an x2 on any other layer, and
+ * whatever the kernel that the options select cannot take - the direct kernels need Cin % 32 == 0 (Cin2 too), ldx % 4 == 0
+ * (ldx2 too) and 16-byte aligned x (x2); Winograd (3x3 / stride 1 / pad 1, Cin % 16 == 0, Cout % 64 == 0 or Cout % 32 == 0 and
+ * Cout > 64) needs an even ldx, x aligned to 8 bytes (16 and ldx % 4 == 0 when Cin % 32 == 0) and 16-byte aligned rows of
+ * out / residual (ldo % 4 == 0).  On the direct kernels out and residual need no more than 4-byte alignment and any ldo: rows
+ * that are not 16-byte aligned take the scalar epilogue.  The 7x7 stem takes dense tensors only.  Synchronises the stream.
+ * Used by the per-layer exactness tests. */
+int specmi_conv2d_strided(specmi_handle* h, const float* x, int B, int H, int W, int Cin, int ldx,
+                          const float* w_oihw_host, const float* scale_host, const float* shift_host,
+                          int Cout, int KH, int KW, int stride, int pad, const float* residual,
+                          int relu, float* out, int ldo, const float* x2, int H2, int W2, int Cin2, int ldx2,
+                          int stride2, void* stream);
+
 /* One fused layer of the fp16 trunk (conv_f16.hip), as specmi_conv2d is for the fp32 one.  x (B,H,W,Cp) fp16 NHWC device,
  * Cp = Cin rounded up to a multiple of 8 (channels past Cin zero); w (Cout,Cin,KH,KW) OIHW fp32 HOST and scale / shift (Cout)
  * fp32 HOST are folded exactly as specmi_commit folds them: weights fp16_rne(w * scale) from the fp64 product (SPECMI_ERR_ARG

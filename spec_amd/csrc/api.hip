@@ -1244,13 +1244,34 @@ int specmi_hmr_uncertainty(specmi_handle* h, int B, float* pred_pose_var, float*
 int specmi_conv2d(specmi_handle* h, const float* x, int B, int H, int W, int Cin, const float* w_host,
                   const float* scale_host, const float* shift_host, int Cout, int KH, int KW, int stride, int pad,
                   const float* residual, int relu, float* out, void* stream) {
+    return specmi_conv2d_strided(h, x, B, H, W, Cin, Cin, w_host, scale_host, shift_host, Cout, KH, KW, stride, pad, residual, relu,
+                                 out, Cout, nullptr, 0, 0, 0, 0, 1, stream);
+}
+
+// The layer as the trunks launch it: channel strides on both sides (HRNet's padded maps and concat slices) and the second A
+// source of a bottleneck's conv3 with the downsample folded in.  specmi_conv2d is this with ldx = Cin, ldo = Cout, no x2.
+int specmi_conv2d_strided(specmi_handle* h, const float* x, int B, int H, int W, int Cin, int ldx, const float* w_host,
+                          const float* scale_host, const float* shift_host, int Cout, int KH, int KW, int stride, int pad,
+                          const float* residual, int relu, float* out, int ldo, const float* x2, int H2, int W2, int Cin2, int ldx2,
+                          int stride2, void* stream) {
     ENTER(h);
-    if (!x || !w_host || !scale_host || !shift_host || !out || B <= 0 || KH != KW)
+    if (!x || !w_host || !scale_host || !shift_host || !out || B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH != KW || KH < 1 ||
+        stride < 1 || pad < 0)
         return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if (ldx < Cin || ldo < Cout) return fail(h, SPECMI_ERR_ARG, "ldx (%d) < Cin (%d) or ldo (%d) < Cout (%d)", ldx, Cin, ldo, Cout);
+    if (conv_out(H, KH, stride, pad) < 1 || conv_out(W, KW, stride, pad) < 1) return fail(h, SPECMI_ERR_ARG, "empty output");
+    if (x2) {
+        if (KH != 1 || pad != 0 || stride != 1) return fail(h, SPECMI_ERR_ARG, "a second A source needs a 1x1 / stride 1 / pad 0 layer");
+        if (Cin2 <= 0 || ldx2 < Cin2 || stride2 < 1 || (H - 1) * (long)stride2 >= H2 || (W - 1) * (long)stride2 >= W2)
+            return fail(h, SPECMI_ERR_ARG, "second A source: Cin2 %d, ldx2 %d, stride2 %d, %dx%d does not cover the %dx%d outputs", Cin2, ldx2,
+                        stride2, H2, W2, H, W);
+    } else Cin2 = 0;
     hipStream_t s = (hipStream_t)stream;
     std::vector<void*> tmp;
     std::vector<float> packed, sc, sh;
     const bool stem = (Cin == 3 && KH == 7 && Cout == 64 && stride == 2 && pad == 3);
+    if (stem && (ldx != Cin || ldo != Cout)) return fail(h, SPECMI_ERR_ARG, "the 7x7 stem reads a dense NCHW image and writes dense rows");
+    const int Kc = Cin + Cin2;          // input channels of w: with x2 the 1x1 weights of both sources, concatenated along K
     int rc = SPECMI_OK;
     float *dw = nullptr, *dsc = nullptr, *dsh = nullptr;
     const int Npad = round_up(Cout, 64);
@@ -1260,19 +1281,22 @@ int specmi_conv2d(specmi_handle* h, const float* x, int B, int H, int W, int Cin
     // option "winograd": 1 (default) = F(2x2,3x3) where the shape allows it, 0 = always the direct implicit GEMM
     const bool wino = !stem && opt(h, OPT_winograd) && KH == 3 && stride == 1 && pad == 1 && Cin % 16 == 0 &&
                       (Cout % 64 == 0 || (Cout % 32 == 0 && Cout > 64));
+    // (the Winograd kernel stores 16 bytes per lane: its rows of out / residual are 16-byte aligned in every trunk)
+    if (wino && (ldo % 4 || (reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(residual) & 15)))
+        return fail(h, SPECMI_ERR_ARG, "Winograd: out / residual rows must be 16-byte aligned (ldo %d)", ldo);
     const int terms = opt(h, OPT_conv_precision);
-    const bool split = !stem && (terms == 3 || terms == 6) && Cin % 16 == 0 && Cout % 4 == 0;
+    const bool split = !stem && (terms == 3 || terms == 6) && Cin % 16 == 0 && Cin2 % 16 == 0 && Cout % 4 == 0;
     std::vector<unsigned short> pieces;
     void* dsplit = nullptr;
     if (split) {
-        pack_bf16_split_weights_oihw(w_host, Cout, Cin, KH, KW, Npad, pieces);
+        pack_bf16_split_weights_oihw(w_host, Cout, Kc, KH, KW, Npad, pieces);
         if ((rc = dev_upload(h, pieces.data(), pieces.size() * 2, &dsplit, tmp))) { free_pool(tmp); return rc; }
     }
     if (stem) pack_stem_weights(w_host, packed);
     else if (wino) pack_wino_weights(w_host, Cout, Cin, packed);
     else {
-        if (Cin % 32) { free_pool(tmp); return fail(h, SPECMI_ERR_ARG, "Cin must be a multiple of 32 (got %d)", Cin); }
-        pack_gemm_weights(w_host, Cout, Cin, KH, KW, Cin * KH * KW, Npad, packed);
+        if (Cin % 32 || Cin2 % 32) { free_pool(tmp); return fail(h, SPECMI_ERR_ARG, "Cin (and Cin2) must be multiples of 32 (got %d, %d)", Cin, Cin2); }
+        pack_gemm_weights(w_host, Cout, Kc, KH, KW, Kc * KH * KW, Npad, packed);
     }
     if ((rc = dev_upload(h, packed.data(), packed.size() * 4, (void**)&dw, tmp)) ||
         (rc = dev_upload(h, sc.data(), sc.size() * 4, (void**)&dsc, tmp)) ||
@@ -1288,8 +1312,9 @@ int specmi_conv2d(specmi_handle* h, const float* x, int B, int H, int W, int Cin
     } else {
         ConvArgs a;
         a.x = x; a.w = dw; a.scale = dsc; a.shift = dsh; a.res = residual; a.out = out;
-        a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldx = Cin; a.OH = OH; a.OW = OW; a.Cout = Cout; a.Npad = Npad;
-        a.ldo = Cout; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.relu = relu;
+        a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.ldx = ldx; a.OH = OH; a.OW = OW; a.Cout = Cout; a.Npad = Npad;
+        a.ldo = ldo; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.relu = relu;
+        if (x2) { a.x2 = x2; a.H2 = H2; a.W2 = W2; a.ldx2 = ldx2; a.Cin2 = Cin2; a.stride2 = stride2; }
         a.force_variant = opt(h, OPT_force_conv_variant);
         a.wino_variant = opt(h, OPT_force_wino_variant);
         // option "conv2d_sk" (tests): > 1 = that many leaves, -1 = the latency plan's own rule, 0 = the throughput kernel;
@@ -1321,6 +1346,8 @@ int specmi_conv2d(specmi_handle* h, const float* x, int B, int H, int W, int Cin
     }
     hipError_t se = hipStreamSynchronize(s);
     free_pool(tmp);
+    // what conv_igemm_check / conv_wino_supported (and the launchers' alignment and size rules) refuse: nothing was launched
+    if (lrc == (int)hipErrorInvalidValue) return fail(h, SPECMI_ERR_ARG, "conv2d: shape, stride or alignment not supported");
     if (lrc) return fail(h, SPECMI_ERR_HIP, "conv2d launch failed: %s", hipGetErrorString((hipError_t)lrc));
     if (se != hipSuccess) return fail(h, SPECMI_ERR_HIP, "conv2d failed: %s", hipGetErrorString(se));
     return SPECMI_OK;

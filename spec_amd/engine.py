@@ -1123,24 +1123,64 @@ class Engine:
                                                        self._stream()))
         return v, j
 
-    def conv2d(self, x, w_oihw, scale, shift, stride, pad, residual=None, relu=True, nchw_input=False):
-        """Single fused layer (tests).  x NHWC device tensor (NCHW for the 7x7 stem)."""
-        x = _dev_f32(x, self.device)
-        w = np.ascontiguousarray(np.asarray(w_oihw, dtype=np.float32))
+    @staticmethod
+    def _pixel_rows(t):
+        """A (B,H,W,C) NHWC tensor or channel-sliced view of one -> its pixel stride ld (unit stride along C, one stride
+        ld >= C from pixel to pixel, pixels dense in B, H, W), or None if it is laid out otherwise."""
+        _, H, W, Cc = t.shape
+        ld = t.stride(2) if W > 1 else t.stride(1) // W if H > 1 else t.stride(0) // (H * W) if t.shape[0] > 1 else Cc
+        want = (H * W * ld, W * ld, ld, 1)
+        return ld if ld >= Cc and all(n == 1 or st == wt for n, st, wt in zip(t.shape, t.stride(), want)) else None
+
+    def conv2d(self, x, w_oihw, scale, shift, stride, pad, residual=None, relu=True, nchw_input=False, out=None,
+               x2=None, w2_oihw=None, stride2=1):
+        """Single fused layer (tests).  x NHWC device tensor (NCHW for the 7x7 stem).  x, x2 and out may be channel-sliced views
+        of wider NHWC maps (unit channel stride, pixel stride ld >= C: specmi_conv2d_strided's ldx / ldx2 / ldo); a residual is
+        read with out's pixel stride.  out: where the result goes (only its (pixel, channel < Cout) floats are written); by
+        default a dense new tensor.  x2 / w2_oihw / stride2: the second A source of a 1x1 layer (B,H2,W2,Cin2) and its 1x1
+        weights (Cout,Cin2,1,1), concatenated after w along K."""
+        def rows(t):      # (tensor, pixel stride): a view that fits is passed as it is, anything else as a dense copy
+            if isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 4:
+                t = t.to(self.device)         # (a tensor already there is returned as it is, strides included)
+                ld = self._pixel_rows(t)
+                if ld is not None:
+                    return t, ld
+            t = _dev_f32(t, self.device)
+            return t, t.shape[-1]
+        w = np.asarray(w_oihw, dtype=np.float32)
         sc = np.ascontiguousarray(np.asarray(scale, dtype=np.float32))
         sh = np.ascontiguousarray(np.asarray(shift, dtype=np.float32))
         cout, cin, kh, kw = w.shape
         if nchw_input:
+            x = _dev_f32(x, self.device)
             B, _, H, W = x.shape
+            ldx = cin
         else:
+            x, ldx = rows(x)
             B, H, W, _ = x.shape
+        cin2 = H2 = W2 = ldx2 = 0
+        if x2 is not None:
+            x2, ldx2 = rows(x2)
+            _, H2, W2, cin2 = x2.shape
+            w = np.concatenate([w, np.asarray(w2_oihw, dtype=np.float32)], axis=1)
+        w = np.ascontiguousarray(w)
         oh, ow = (H + 2 * pad - kh) // stride + 1, (W + 2 * pad - kw) // stride + 1
-        out = torch.empty(B, oh, ow, cout, device=self.device, dtype=torch.float32)
-        res = _dev_f32(residual, self.device, (B, oh, ow, cout))
-        _lib.check(self.h, self.lib.specmi_conv2d(
-            self.h, _ptr(x), B, H, W, cin, w.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
-            sh.ctypes.data_as(C.c_void_p), cout, kh, kw, stride, pad, _ptr(res), int(relu), _ptr(out),
-            self._stream()))
+        if out is None:
+            out = torch.empty(B, oh, ow, cout, device=self.device, dtype=torch.float32)
+        elif tuple(out.shape) != (B, oh, ow, cout) or out.dtype != torch.float32 or not out.is_cuda:
+            raise ValueError(f'out must be a float32 cuda tensor of shape {(B, oh, ow, cout)}')
+        ldo = self._pixel_rows(out)
+        if ldo is None:
+            raise ValueError(f'out: unit channel stride and one pixel stride >= Cout expected, got strides {tuple(out.stride())}')
+        res, ldr = (None, ldo) if residual is None else rows(residual)
+        if res is not None and tuple(res.shape) != (B, oh, ow, cout):
+            raise ValueError(f'expected shape {(B, oh, ow, cout)}, got {tuple(res.shape)}')
+        if ldr != ldo:
+            raise ValueError(f'the residual is read with the pixel stride of out ({ldo}), got {ldr}')
+        _lib.check(self.h, self.lib.specmi_conv2d_strided(
+            self.h, _ptr(x), B, H, W, cin, ldx, w.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.c_void_p),
+            sh.ctypes.data_as(C.c_void_p), cout, kh, kw, stride, pad, _ptr(res), int(relu), _ptr(out), ldo,
+            _ptr(x2), H2, W2, cin2, ldx2, int(stride2), self._stream()))
         return out
 
     def conv2d_f16(self, x, w_oihw, scale, shift, stride, pad, residual=None, relu=True, out_f32=False,
