@@ -780,6 +780,29 @@ int specmi_eval_mesh(specmi_handle* h, const float* pred_vertices, const float* 
 int specmi_eval_joints(specmi_handle* h, const float* pred_joints, const float* gt_joints, int B,
                        int J, float* mpjpe_mm, float* pampjpe_mm, void* stream);
 
+/* What SPECTrainer.validation_step scores per batch (spec/trainer.py:272-344), in one launch, PER JOINT and in METRES - the unit
+ * of the per-joint arrays in evaluation_results_<ds>.pkl (:338-344); callers multiply by 1000 where they print.  Per image:
+ *   jp = J_regressor @ pred_vertices, jg = J_regressor @ gt_vertices, fp32, the summation of specmi_eval_mesh;
+ *   selected joints p_i = jp[sel[i]] - jp[0], g_i = jg[sel[i]] - jg[0] (fp32 subtraction; joint_sel NULL = the first nsel joints)
+ *     -> err_sel, pa_err_sel (B,nsel);
+ *   given joints pred_joints, gt_joints (B,Jk,3), joint 0 subtracted from each set in fp32 (:282-283; a no-op on a set whose
+ *     joint 0 is already the origin, as the dataset's joints_24 is) -> err_k, pa_err_k (B,Jk);
+ *   err[b,i] = |p_i - g_i|; pa_err[b,i] = |s R (p_i - mean p) + mean g - g_i| with (s, R) the least-squares similarity fit of the
+ *     whole set (reconstruction_error(..., reduction=None)[1]; Horn's quaternion solution in fp64, as in the two calls above).
+ *     Everything after the pelvis subtraction runs in fp64 with one rounding to fp32.  A set without variance has no fit: every
+ *     pa_err of it is NaN, as in the reference (0 / 0); its err stays finite;
+ *   v2v[b] = mean_v |gt_v - pred_v| on the meshes as given - compute_error_verts (:312-315), NOT the pelvis-aligned V2V of
+ *     specmi_eval_mesh.
+ * All pointers are device pointers and any output may be NULL.  pred_joints and gt_joints are NULL together; then Jk is not read
+ * and err_k / pa_err_k must be NULL.  SPECMI_ERR_ARG (nothing is launched or written): B < 1 or V < 1; J, nsel or (with joints)
+ * Jk outside [1,32]; joint_sel NULL with nsel > J; exactly one of the joint sets NULL; a joint output without the joint sets.
+ * The entries of joint_sel lie in [0,J) and may repeat (device memory, not checked).  One workgroup per image: an image's outputs
+ * do not depend on B or on the other images. */
+int specmi_eval_step(specmi_handle* h, const float* pred_vertices, const float* gt_vertices, int B, int V,
+                     const float* J_regressor, int J, const int32_t* joint_sel, int nsel,
+                     const float* pred_joints, const float* gt_joints, int Jk,
+                     float* err_sel, float* pa_err_sel, float* err_k, float* pa_err_k, float* v2v, void* stream);
+
 /* pred_joints = einsum('bik,ji->bjk', vertices, J_regressor) (spec/utils/compute_error.py:184,187): vertices (B,V,3),
  * J_regressor (J,V) device -> joints (B,J,3).  Any J >= 1: unlike the two calls above nothing per joint is held on chip, so
  * there is no cap of 32 (the joints run in chunks of 8, one workgroup per image and chunk). */

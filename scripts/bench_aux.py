@@ -17,6 +17,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only jpeg_encode        # pictures to JPEG files: device encode + download of the bytes against raw download + Pillow -> profiles/jpeg_encode_aux.json
     python scripts/bench_aux.py --only horizon_panel      # panel 0 of eight 1080p frames: Pillow on the host against specmi_draw_marks -> profiles/horizon_panel_aux.json
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
+    python scripts/bench_aux.py --only eval_step          # the validation step's one launch against eval_mesh + eval_joints (means only) -> profiles/eval_step_aux.json
     python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
 import argparse
@@ -719,9 +720,66 @@ def hmr_loss_section(eng, a, add):
             timed(eng, lambda: eng.hmr_loss(1, pred, gt, [1., 5., 1., 1., 0.001, 0., 1., 60.], out=out), a.iters), ('images_per_s', B))
 
 
+def eval_step_section(eng, a):
+    """``specmi_eval_step`` (per-joint errors of both joint sets + the unaligned V2V, one launch) against the two launches it sits
+    next to, ``specmi_eval_mesh`` + ``specmi_eval_joints`` (per-image means only), at the evaluation config's batch: B = 64,
+    V = 6890, J = 17, nsel = 14, Jk = 24.  HIP events around ``iters`` back-to-back calls after a warm-up of the same calls, the
+    two alternated in this process, 3 rounds.  The bytes a call must move: both meshes and the regressor once, the joint sets,
+    the outputs."""
+    from spec_amd import constants, metrics
+    dev = eng.device
+    rng = np.random.default_rng(0)
+    B, V, J, Jk = 64, 6890, 17, 24
+    f = lambda *shape, std=0.3: torch.from_numpy((rng.standard_normal(shape) * std).astype(np.float32)).to(dev)
+    gv, gj = f(B, V, 3), f(B, Jk, 3)
+    pv, pj = gv + f(B, V, 3, std=0.03), gj + f(B, Jk, 3, std=0.03)
+    Jr = torch.from_numpy(rng.random((J, V)).astype(np.float32)).to(dev)
+    Jr /= Jr.sum(1, keepdim=True)
+    sel = list(constants.H36M_TO_J14)
+
+    def pair():
+        metrics.eval_single(pv, gv, Jr, joint_sel=sel)
+        metrics.eval_j_24(pj, gj)
+
+    def step():
+        eng.eval_step(pv, gv, Jr, joint_sel=sel, pred_joints=pj, gt_joints=gj)
+
+    def ms_per_call(fn):
+        for _ in range(5):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+    rounds = {'pair': [], 'eval_step': []}
+    for _ in range(3):                                              # alternated: both see the same clocks and the same neighbours
+        rounds['pair'].append(ms_per_call(pair))
+        rounds['eval_step'].append(ms_per_call(step))
+    med = {k: float(np.median(v)) for k, v in rounds.items()}
+    spread = {k: max(v) - min(v) for k, v in rounds.items()}
+    by = {'eval_step': 4.0 * (B * V * 6 + J * V + B * Jk * 6 + B * (2 * len(sel) + 2 * Jk + 1)),
+          'pair': 4.0 * (B * V * 6 + J * V + B * Jk * 6 + B * 5)}
+    kern = {k: {'ms_per_launch': round(v[0], 5), 'algorithmic_MB': round(v[1] / 1e6, 3)}
+            for fn in (pair, step) for k, v in timed(eng, fn, a.iters).items()}
+    row = {'workload': f'B = {B}, V = {V}, J = {J}, nsel = {len(sel)}, Jk = {Jk}; the pair returns 5 per-image means in millimetres, eval_step '
+                       f'{2 * len(sel) + 2 * Jk} per-joint errors per image in metres and the unaligned V2V',
+           'launches': {'pair': 2, 'eval_step': 1}, 'ms_round_values': {k: [round(x, 5) for x in v] for k, v in rounds.items()},
+           'ms_median': {k: round(v, 5) for k, v in med.items()}, 'spread_between_rounds_ms': {k: round(v, 5) for k, v in spread.items()},
+           'must_move_MB': {k: round(v / 1e6, 3) for k, v in by.items()},
+           'frac_of_hbm_peak': {k: round(by[k] / (med[k] * 1e-3) / HBM_PEAK, 4) for k in med},
+           'ratio_pair_over_eval_step': round(med['pair'] / med['eval_step'], 3),
+           'eval_step_slower_beyond_the_pairs_spread': bool(med['eval_step'] > med['pair'] + spread['pair']),
+           'kernels_by_the_library_profiler': kern}
+    print(json.dumps(row, indent=1))
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'horizon_panel'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'horizon_panel'], default=None, help='run one section only')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -749,6 +807,16 @@ def main():
             if per_unit:
                 row[per_unit[0]] = round(per_unit[1] / (ms * 1e-3), 1)
             table.append(row)
+
+    if a.only == 'eval_step':
+        from spec_amd import _lib
+        row = eval_step_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the '
+                       'same calls; 3 alternated rounds; kernels: per-launch HIP events (library profiler)', 'eval_step': row,
+                       'source_hash': _lib.source_hash()}, f, indent=1)
+        return
 
     if a.only == 'hmr_loss':
         from spec_amd import _lib

@@ -8,6 +8,9 @@ the Lightning checkpoint + SMPL pickle + annotations, runs every image through t
 ``DATASET.BATCH_SIZE`` with the dataset's precomputed CamCalib camera (or the GT camera with TESTING.USE_GT_CAM
 True), writes ``evaluation_results_<ds>.pkl`` in the reference's format, scores it on the device like
 ``spec/utils/compute_error.py`` and prints W-MPJPE / PA-MPJPE / W-PVE beside the README table (README.md:155-159).
+Every batch is also scored on the device as the reference's ``validation_step`` scores it, against the dataset's own ground
+truth: the per-joint arrays ``mpjpe``, ``pampjpe``, ``mpjpe_24``, ``pampjpe_24`` of the pkl, the five ``<ds> MPJPE: ...`` lines and
+``val_accuracy_results_<ds>.json`` (``--no-step-metrics`` leaves them out).
 
 ``--standin DIR`` first writes a small synthetic ``data/`` tree in the REAL container formats under DIR and evaluates
 that (a dry run of the whole flow; the numbers are meaningless).  ``--synthetic N`` is the quick in-memory variant.
@@ -77,6 +80,8 @@ def main():
     ap.add_argument('--dataset_name', type=str, default='spec-syn')
     ap.add_argument('--loss', action='store_true', help="also report the mean of HMRCamLoss's loss dict (the training objective of "
                                                         'spec/losses.py, forward value only) over each dataset; off by default')
+    ap.add_argument('--no-step-metrics', action='store_true', help="do not score the batches as the reference's validation step does "
+                    '(the per-joint arrays of the pkl, the five "<ds> MPJPE: ..." lines, val_accuracy_results_<ds>.json)')
     ap.add_argument('--save-images', action='store_true', help='one three-panel picture (full image with the 2D keypoints and horizon line | mesh '
                     'overlay | side view) of the first image of every TESTING.SAVE_FREQ-th batch under LOG_DIR/output_images: sets '
                     'TESTING.SAVE_IMAGES and TRAINING.SAVE_IMAGES (the reference writes the files only with both)')
@@ -114,7 +119,7 @@ def main():
         ckpt = 'data/spec/checkpoints/spec_checkpoint.ckpt'          # scripts/spec_demo.py:31
     if not os.path.isdir(os.path.join(root, 'data')):
         sys.exit(f'{os.path.join(root, "data")} not found: download the reference data (README.md:127-147) or use --standin DIR')
-    results = evaluation.run_evaluation(hp, data_root=root, ckpt=ckpt, limit=args.limit, loss=args.loss)
+    results = evaluation.run_evaluation(hp, data_root=root, ckpt=ckpt, limit=args.limit, loss=args.loss, step_metrics=not args.no_step_metrics)
     if args.report:
         import json
         rep = {'config': cfg, 'checkpoint': ckpt or hp['TRAINING']['PRETRAINED_LIT'], 'data_root': os.path.abspath(root),
@@ -126,6 +131,8 @@ def main():
             entry = {'mean': {k: float(v) for k, v in m.items()}, 'readme': None, 'delta_mm': res.get('readme_delta_mm'), 'within_target': None}
             if 'loss' in res:
                 entry['loss'] = res['loss']
+            if 'step' in res:
+                entry['step'] = res['step']['acc']
             if ref:
                 entry['readme'] = {'wmpjpe': ref[0], 'pampjpe': ref[1], 'wpve': ref[2]}
                 entry['within_target'] = abs(res['readme_delta_mm']['wmpjpe']) <= 0.1

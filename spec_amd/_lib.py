@@ -209,6 +209,9 @@ PROTOTYPES = {
                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'specmi_eval_joints': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    # (h, pred_vertices, gt_vertices, B, V, J_regressor, J, joint_sel, nsel, pred_joints, gt_joints, Jk, err_sel, pa_err_sel, err_k, pa_err_k, v2v, stream)
+    'specmi_eval_step': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6),
     'specmi_regress_joints': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                         C.c_void_p]),
     # (h, mode, 6 prediction tensors, 6 ground-truth tensors, has_smpl, has_pose_3d, orig_shape, scale, B, V, 8 weights, terms, counts, means, stream)

@@ -2279,6 +2279,21 @@ int specmi_eval_joints(specmi_handle* h, const float* pred, const float* gt, int
     return SPECMI_OK;
 }
 
+int specmi_eval_step(specmi_handle* h, const float* pred, const float* gt, int B, int V, const float* Jr, int J, const int32_t* sel,
+                     int nsel, const float* pj, const float* gj, int Jk, float* err_sel, float* pa_err_sel, float* err_k,
+                     float* pa_err_k, float* v2v, void* stream) {
+    ENTER(h);
+    if (!pred || !gt || !Jr || B <= 0 || V <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if (J < 1 || J > 32 || nsel < 1 || nsel > 32) return fail(h, SPECMI_ERR_ARG, "J and nsel must be in [1,32]");
+    if (!sel && nsel > J) return fail(h, SPECMI_ERR_ARG, "eval_step: joint_sel is NULL (the first nsel joints) but nsel = %d exceeds J = %d", nsel, J);
+    if (!pj != !gj) return fail(h, SPECMI_ERR_ARG, "eval_step: pred_joints and gt_joints are given together or not at all");
+    if (!pj && (err_k || pa_err_k)) return fail(h, SPECMI_ERR_ARG, "eval_step: err_k / pa_err_k asked for without pred_joints and gt_joints");
+    if (pj && (Jk < 1 || Jk > 32)) return fail(h, SPECMI_ERR_ARG, "Jk must be in [1,32]");
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "eval.step"};
+    LAUNCHCHK(h, launch_eval_step(pred, gt, B, V, Jr, J, sel, nsel, pj, gj, Jk, err_sel, pa_err_sel, err_k, pa_err_k, v2v, ctx), "eval_step");
+    return SPECMI_OK;
+}
+
 int specmi_regress_joints(specmi_handle* h, const float* vertices, int B, int V, const float* Jr, int J, float* joints,
                           void* stream) {
     ENTER(h);

@@ -239,6 +239,145 @@ __global__ void __launch_bounds__(64) eval_joints_kernel(const float* __restrict
     if (pampjpe) pampjpe[b0 + t] = pa;
 }
 
+// ---- the validation step's scores (spec/trainer.py:272-344): per-joint errors in metres, unaligned V2V ------------------------
+//
+// Similarity fit of N pelvis-aligned joints p onto g (coordinate c of joint i at p[i * 3 + c]), the arithmetic of joint_errors
+// above: fit[0..2] = mean of p, fit[3..5] = mean of g, fit[6..14] = scale * R row-major.  Zero variance of p gives 0 / 0 = NaN
+// in every entry of scale * R, as in the reference.
+__device__ void similarity_fit(const float* p, const float* g, int N, double* fit) {
+    double mu1[3] = {0, 0, 0}, mu2[3] = {0, 0, 0};
+    for (int i = 0; i < N; ++i)
+        for (int c = 0; c < 3; ++c) { mu1[c] += p[i * 3 + c]; mu2[c] += g[i * 3 + c]; }
+    for (int c = 0; c < 3; ++c) { mu1[c] /= N; mu2[c] /= N; }
+    double S[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, var1 = 0;
+    for (int i = 0; i < N; ++i) {
+        double x1[3], x2[3];
+        for (int c = 0; c < 3; ++c) { x1[c] = p[i * 3 + c] - mu1[c]; x2[c] = g[i * 3 + c] - mu2[c]; var1 += x1[c] * x1[c]; }
+        for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) S[a][b] += x1[a] * x2[b];
+    }
+    double Nm[4][4] = {
+        {S[0][0] + S[1][1] + S[2][2], S[1][2] - S[2][1], S[2][0] - S[0][2], S[0][1] - S[1][0]},
+        {S[1][2] - S[2][1], S[0][0] - S[1][1] - S[2][2], S[0][1] + S[1][0], S[2][0] + S[0][2]},
+        {S[2][0] - S[0][2], S[0][1] + S[1][0], -S[0][0] + S[1][1] - S[2][2], S[1][2] + S[2][1]},
+        {S[0][1] - S[1][0], S[2][0] + S[0][2], S[1][2] + S[2][1], -S[0][0] - S[1][1] + S[2][2]}};
+    double q[4], lam;
+    sym4_max_eig(Nm, q, &lam);
+    const double w = q[0], x = q[1], y = q[2], z = q[3], scale = lam / var1;
+    const double R[9] = {w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y),
+                         2 * (x * y + w * z), w * w - x * x + y * y - z * z, 2 * (y * z - w * x),
+                         2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z};
+    for (int c = 0; c < 3; ++c) { fit[c] = mu1[c]; fit[3 + c] = mu2[c]; }
+    for (int k = 0; k < 9; ++k) fit[6 + k] = scale * R[k];
+}
+
+// |p_i - g_i| and |s R (p_i - mu_p) + mu_g - g_i| of one joint, fp64 with one rounding to fp32 each
+__device__ __forceinline__ void joint_error(const float* p, const float* g, const double* fit, float* err, float* pa_err) {
+    if (err) {
+        double d = 0;
+        for (int a = 0; a < 3; ++a) {
+            const double df = (double)p[a] - (double)g[a];
+            d += df * df;
+        }
+        *err = (float)sqrt(d);
+    }
+    if (pa_err) {
+        double d = 0;
+        for (int a = 0; a < 3; ++a) {
+            double v = 0;
+            for (int b = 0; b < 3; ++b) v += fit[6 + a * 3 + b] * (p[b] - fit[b]);
+            const double df = v + fit[3 + a] - g[a];
+            d += df * df;
+        }
+        *pa_err = (float)sqrt(d);
+    }
+}
+
+// One workgroup per image.  The regression loop is eval_mesh_kernel's (the same summation order, so the same joints); the first
+// chunk of joints also accumulates the unaligned V2V from the vertices it already holds, so no pass reads the meshes for V2V
+// alone.  Then wave 0 solves the Procrustes problem of the selected regressed joints and wave 1 that of the given joints (lane 0
+// each, side by side), and one lane per joint writes that joint's two errors.
+__global__ void __launch_bounds__(256) eval_step_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int V,
+                                                         const float* __restrict__ Jr, int J, const int* __restrict__ sel, int nsel,
+                                                         const float* __restrict__ pj, const float* __restrict__ gj, int Jk,
+                                                         float* __restrict__ err_sel, float* __restrict__ pa_err_sel,
+                                                         float* __restrict__ err_k, float* __restrict__ pa_err_k,
+                                                         float* __restrict__ v2v) {
+    __shared__ float red[4];
+    __shared__ float jp[kMaxJ][3], jg[kMaxJ][3];
+    __shared__ float sp[2][kMaxJ * 3], sg[2][kMaxJ * 3];   // [0] the selected regressed joints, [1] the given joints, pelvis-aligned
+    __shared__ float part[4 * kJC * 6], sums[kJC * 6];
+    __shared__ double fit[2][15];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const float* pv = pred + (size_t)b * V * 3;
+    const float* gv = gt + (size_t)b * V * 3;
+    float acc = 0.f;
+    for (int j0 = 0; j0 < J; j0 += kJC) {
+        float a[kJC * 6];
+#pragma unroll
+        for (int i = 0; i < kJC * 6; ++i) a[i] = 0.f;
+        const float* wr[kJC];   // rows past J alias row J - 1 (unconditional loads); their sums are never stored
+#pragma unroll
+        for (int jj = 0; jj < kJC; ++jj) wr[jj] = Jr + (size_t)min(j0 + jj, J - 1) * V;
+        const bool first = j0 == 0;
+#pragma unroll 3
+        for (int v = t; v < V; v += 256) {
+            const float x[6] = {pv[v * 3 + 0], pv[v * 3 + 1], pv[v * 3 + 2], gv[v * 3 + 0], gv[v * 3 + 1], gv[v * 3 + 2]};
+#pragma unroll
+            for (int jj = 0; jj < kJC; ++jj) {
+                const float w = wr[jj][v];
+#pragma unroll
+                for (int c = 0; c < 6; ++c) a[jj * 6 + c] = fmaf(w, x[c], a[jj * 6 + c]);
+            }
+            if (first) {
+                const float dx = x[3] - x[0], dy = x[4] - x[1], dz = x[5] - x[2];
+                acc += sqrtf(dx * dx + dy * dy + dz * dz);
+            }
+        }
+        block_sum_many_256<kJC * 6>(a, part, sums);
+        if (t < kJC * 6 && j0 + t / 6 < J) {
+            const int jj = t / 6, c = t % 6;
+            if (c < 3) jp[j0 + jj][c] = sums[t]; else jg[j0 + jj][c - 3] = sums[t];
+        }
+    }
+    const float vs = block_sum_256(acc, red);   // its barriers also publish jp / jg
+    if (t == 0 && v2v) v2v[b] = vs / (float)V;
+    if (t < nsel * 3) {
+        const int i = t / 3, c = t % 3, j = sel ? sel[i] : i;
+        sp[0][t] = jp[j][c] - jp[0][c];
+        sg[0][t] = jg[j][c] - jg[0][c];
+    }
+    if (pj && t < Jk * 3) {
+        const size_t base = (size_t)b * Jk * 3;
+        sp[1][t] = pj[base + t] - pj[base + t % 3];
+        sg[1][t] = gj[base + t] - gj[base + t % 3];
+    }
+    __syncthreads();
+    const int w = t >> 6, lane = t & 63;
+    const int N = w == 0 ? nsel : (w == 1 && pj) ? Jk : 0;
+    float* const err = w == 0 ? err_sel : err_k;
+    float* const pa_err = w == 0 ? pa_err_sel : pa_err_k;
+    const int q = w & 1;                        // waves 2 and 3 have N = 0 and touch nothing
+    if (lane == 0 && N && pa_err) similarity_fit(sp[q], sg[q], N, fit[q]);
+    __syncthreads();
+    if (lane < N) {
+        const size_t o = (size_t)b * N + lane;
+        joint_error(sp[q] + lane * 3, sg[q] + lane * 3, fit[q], err ? err + o : nullptr, pa_err ? pa_err + o : nullptr);
+    }
+}
+
+int launch_eval_step(const float* pred, const float* gt, int B, int V, const float* Jr, int J, const int* sel, int nsel,
+                     const float* pj, const float* gj, int Jk, float* err_sel, float* pa_err_sel, float* err_k, float* pa_err_k,
+                     float* v2v, const LaunchCtx& ctx) {
+    if (J > kMaxJ || nsel > kMaxJ || nsel < 1 || J < 1 || (pj && (Jk > kMaxJ || Jk < 1))) return (int)hipErrorInvalidValue;
+    const double nk = pj ? Jk : 0;
+    // algorithmic HBM bytes: both meshes once + the regressor once (re-reads per joint chunk come through L2) + the joint sets + the outputs
+    ProfScope ps(ctx, "eval_step_metrics", 2.0 * B * (double)V * 6 * J,
+                 4.0 * ((double)B * V * 6 + (double)J * V + B * (6.0 * nk + 2.0 * nsel + 2.0 * nk + 1.0)));
+    hipLaunchKernelGGL(eval_step_kernel, dim3(B), dim3(256), 0, ctx.stream, pred, gt, V, Jr, J, sel, nsel, pj, gj, Jk, err_sel, pa_err_sel,
+                       err_k, pa_err_k, v2v);
+    return (int)hipGetLastError();
+}
+
 // joints (B,J,3) = J_regressor (J,V) @ vertices (B,V,3)  (torch.einsum('bik,ji->bjk'), compute_error.py:184,187;
 // torch.matmul(J_regressor_batch, vertices), :53,58): one workgroup per (image, chunk of kRC joints); the vertices are
 // read once per chunk and every load of the loop is independent

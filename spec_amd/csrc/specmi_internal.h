@@ -370,6 +370,9 @@ int launch_eval_mesh(const float* pred, const float* gt, int B, int V, const flo
                      float* mpjpe, float* pampjpe, float* v2v, const LaunchCtx& ctx);
 int launch_eval_joints(const float* pred, const float* gt, int B, int J, float* mpjpe, float* pampjpe,
                        const LaunchCtx& ctx);
+int launch_eval_step(const float* pred, const float* gt, int B, int V, const float* Jr, int J, const int* sel, int nsel,
+                     const float* pj, const float* gj, int Jk, float* err_sel, float* pa_err_sel, float* err_k, float* pa_err_k,
+                     float* v2v, const LaunchCtx& ctx);
 int launch_regress_joints(const float* verts, int B, int V, const float* Jr, int J, float* out, const LaunchCtx& ctx);
 int launch_rotate_points(const float* R, const float* x, int B, int N, float* out, const LaunchCtx& ctx);
 

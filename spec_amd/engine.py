@@ -387,6 +387,40 @@ def check_jpeg_encode(geom, offsets, in_bytes, out_bytes, quality, in_ptr=None, 
     return geom.astype(np.int32), offsets
 
 
+EVAL_STEP_OUTPUTS = ('err_sel', 'pa_err_sel', 'err_k', 'pa_err_k', 'v2v')
+EVAL_STEP_MAX_JOINTS = 32      # kMaxJ of spec_amd/csrc/eval.hip: the joints are held on chip
+
+
+def check_eval_step(B, V, J, nsel, joint_sel=None, Jk=0, pred_joints=False, gt_joints=False, joint_outputs=False):
+    """Every refusal of ``specmi_eval_step`` (include/specmi.h) as ``ValueError``, and one more that only the host can make: an
+    entry of ``joint_sel`` outside [0, J) (the library reads the selection from device memory and does not check it).
+    ``joint_sel``: the selection on the host, or None for the first ``nsel`` joints; ``pred_joints`` / ``gt_joints``: is that
+    joint set given; ``joint_outputs``: are ``err_k`` / ``pa_err_k`` asked for.  -> the selection as an int32 array, or None.
+    Needs no device."""
+    M = EVAL_STEP_MAX_JOINTS
+    if B < 1 or V < 1:
+        raise ValueError(f'{B} images of {V} vertices: at least one of each')
+    if not (1 <= J <= M and 1 <= nsel <= M):
+        raise ValueError(f'J = {J} and nsel = {nsel} must be in [1,{M}]')
+    if joint_sel is None:
+        if nsel > J:
+            raise ValueError(f'joint_sel is None (the first nsel joints) but nsel = {nsel} exceeds J = {J}')
+    else:
+        joint_sel = np.ascontiguousarray(joint_sel, dtype=np.int64).reshape(-1)
+        if joint_sel.shape[0] != nsel:
+            raise ValueError(f'joint_sel holds {joint_sel.shape[0]} joints, nsel = {nsel}')
+        if ((joint_sel < 0) | (joint_sel >= J)).any():
+            raise ValueError(f'joint_sel names a joint outside [0,{J})')
+        joint_sel = joint_sel.astype(np.int32)
+    if bool(pred_joints) != bool(gt_joints):
+        raise ValueError('pred_joints and gt_joints are given together or not at all')
+    if joint_outputs and not pred_joints:
+        raise ValueError('err_k / pa_err_k asked for without pred_joints and gt_joints')
+    if pred_joints and not 1 <= Jk <= M:
+        raise ValueError(f'Jk = {Jk} must be in [1,{M}]')
+    return joint_sel
+
+
 def out_dtype(dtype):
     """The ``dtype=`` keyword of the producers: torch.float32 -> the (n,3,H,W) fp32 image, torch.float16 -> NHWC8 fp16."""
     if dtype not in (torch.float32, torch.float16):
@@ -757,6 +791,43 @@ class Engine:
                 raise ValueError(f'out[{k!r}] must be a contiguous {shp} {dt} tensor on the engine device')
         _lib.check(self.h, self.lib.specmi_hmr_loss(self.h, int(mode), *(_ptr(t) for t in args), B, V, *(float(w) for w in weights),
                                                     _ptr(res['terms']), _ptr(res['counts']), _ptr(res['means']), self._stream()))
+        return res
+
+    def eval_step(self, pred_vertices, gt_vertices, J_regressor, joint_sel=None, nsel=None, pred_joints=None, gt_joints=None,
+                  outputs=None):
+        """``specmi_eval_step``: what the reference's validation step scores for a batch, per joint and in METRES, in one launch.
+        ``pred_vertices`` / ``gt_vertices`` (B, V, 3), ``J_regressor`` (J, V), ``joint_sel`` a host sequence of joint indices (None:
+        the first ``nsel`` joints, ``nsel`` None: all J), ``pred_joints`` / ``gt_joints`` (B, Jk, 3) or both None.  ``outputs``: the
+        names of ``EVAL_STEP_OUTPUTS`` to compute (None: all the inputs allow).  -> {name: device tensor}: err_sel, pa_err_sel
+        (B, nsel), err_k, pa_err_k (B, Jk), v2v (B,)."""
+        pv = _dev_f32(pred_vertices, self.device)
+        if pv.dim() != 3 or pv.shape[2] != 3:
+            raise ValueError(f'pred_vertices must be (B, V, 3), got {tuple(pv.shape)}')
+        B, V = int(pv.shape[0]), int(pv.shape[1])
+        gv = _dev_f32(gt_vertices, self.device, (B, V, 3))
+        Jr = _dev_f32(J_regressor, self.device)
+        if Jr.dim() != 2 or Jr.shape[1] != V:
+            raise ValueError(f'J_regressor must be (J, {V}), got {tuple(Jr.shape)}')
+        J = int(Jr.shape[0])
+        if joint_sel is not None:
+            joint_sel = [int(j) for j in joint_sel]
+            nsel = len(joint_sel) if nsel is None else nsel
+        nsel = J if nsel is None else int(nsel)
+        pj = _dev_f32(pred_joints, self.device)
+        if pj is not None and (pj.dim() != 3 or pj.shape[0] != B or pj.shape[2] != 3):
+            raise ValueError(f'pred_joints must be ({B}, Jk, 3), got {tuple(pj.shape)}')
+        Jk = int(pj.shape[1]) if pj is not None else 0
+        names = tuple(k for k in EVAL_STEP_OUTPUTS if pred_joints is not None or k not in ('err_k', 'pa_err_k')) if outputs is None else tuple(outputs)
+        if set(names) - set(EVAL_STEP_OUTPUTS):
+            raise ValueError(f'outputs: names of {EVAL_STEP_OUTPUTS}, got {names}')
+        sel = check_eval_step(B, V, J, nsel, joint_sel, Jk, pred_joints is not None, gt_joints is not None,
+                              'err_k' in names or 'pa_err_k' in names)
+        gj = _dev_f32(gt_joints, self.device, (B, Jk, 3))
+        sel_t = None if sel is None else torch.from_numpy(sel).to(self.device)
+        shapes = {'err_sel': (B, nsel), 'pa_err_sel': (B, nsel), 'err_k': (B, Jk), 'pa_err_k': (B, Jk), 'v2v': (B,)}
+        res = {k: self._empty(*shapes[k]) for k in names}
+        _lib.check(self.h, self.lib.specmi_eval_step(self.h, _ptr(pv), _ptr(gv), B, V, _ptr(Jr), J, _ptr(sel_t), nsel, _ptr(pj), _ptr(gj), Jk,
+                                                     *(_ptr(res.get(k)) for k in EVAL_STEP_OUTPUTS), self._stream()))
         return res
 
     def resize_normalize_ragged(self, slab, offsets, geom, out=None, dtype=torch.float32):

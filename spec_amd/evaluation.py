@@ -125,6 +125,21 @@ class EvalDataset:
                 'has_pose_3d': torch.full((n,), int('S' in d), device=device, dtype=torch.int32),
                 'scale': f(d['scale'][idx]), 'orig_shape': shapes if isinstance(shapes, torch.Tensor) else f(shapes)}
 
+    def eval_gt(self, idx, device, body) -> Dict[str, torch.Tensor]:
+        """What the reference dataset adds to an evaluation item for the validation step (spec/dataset/cam_dataset.py:415-478), for
+        the samples ``idx``, from ONE call of the body model ``body`` (``metrics.BodyModel``): ``vertices`` (n, V, 3) and
+        ``joints_24`` (n, 24, 3), the kinematic-chain joints with the pelvis (joint 0) subtracted (:476-477).  The pose key follows
+        ``loss_gt``'s rule: ``pose_0yaw_inverseyz`` before ``pose``.  (``pose_3d`` of :443-447 is the H36M regression of these
+        vertices; ``metrics.validation_errors`` regresses it on the device.  ``DATASET.USE_GENDER`` concerns 3dpw / 3dpw-all
+        only, which this class does not read.)"""
+        d = self.data
+        pose_key = 'pose_0yaw_inverseyz' if 'pose_0yaw_inverseyz' in d else 'pose'
+        if pose_key not in d or 'shape' not in d:
+            raise KeyError(f'{self.name}: the annotations hold no SMPL ground truth (pose and shape), the validation step needs it')
+        f = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(device=device, dtype=torch.float32)
+        vertices, joints = body.native(f(d[pose_key][idx]), f(d['shape'][idx]))
+        return {'vertices': vertices, 'joints_24': joints - joints[:, :1]}
+
     def batch(self, idx, device, img_res=224, use_gt_cam=False, dtype=torch.float32) -> Dict[str, torch.Tensor]:
         """``dtype``: what the crops are stored as (``spec_amd.preprocess``: fp32 (n,3,S,S), or NHWC8 fp16 for an fp16 model)."""
         d = self.data
@@ -203,10 +218,46 @@ def loss_module(hparams: dict):
     return HMRCamLoss(**{k: hm[v] for k, v in names.items() if v in hm})
 
 
+STEP_KEYS = ('mpjpe', 'pampjpe', 'mpjpe_24', 'pampjpe_24')     # the per-joint arrays of evaluation_results_<ds>.pkl (spec/trainer.py:341-344)
+
+
+def step_accuracy(per_joint: Dict[str, np.ndarray], v2v) -> dict:
+    """``acc`` of ``validation_epoch_end`` (spec/trainer.py:494-512) from the per-joint arrays (n, joints) in metres and the
+    per-image ``v2v`` (n,): 1000 x the mean over the images of each image's mean over its joints, taken in float64."""
+    img = lambda a: np.asarray(a, np.float64).mean(axis=-1)
+    acc = {f'val_{k}': float(1000 * img(per_joint[k]).mean()) for k in STEP_KEYS}
+    acc['val_v2v'] = float(1000 * np.asarray(v2v, np.float64).mean())
+    return acc
+
+
+def step_lines(ds_name: str, acc: dict) -> List[str]:
+    """The five lines of ``validation_epoch_end`` in their multi-dataset form (spec/trainer.py:500-504), whatever the number of
+    datasets: the dataset's name in front keeps them apart from ``compute_error``'s own ``MPJPE:`` lines."""
+    return [f'{ds_name} MPJPE: ' + str(acc['val_mpjpe']), f'{ds_name} PA-MPJPE: ' + str(acc['val_pampjpe']),
+            f'{ds_name} MPJPE (24j): ' + str(acc['val_mpjpe_24']), f'{ds_name} PA-MPJPE (24j): ' + str(acc['val_pampjpe_24']),
+            f'{ds_name} V2V: ' + str(acc['val_v2v'])]
+
+
+def write_val_accuracy(log_dir: str, ds_name: str, acc: dict) -> str:
+    """``val_save_best_results`` (spec/trainer.py:655-662) of a test run: ``val_accuracy_results_<ds>.json`` holding
+    ``[[global_step, acc, epoch]]`` with step and epoch 0."""
+    import json
+    path = os.path.join(log_dir, f'val_accuracy_results_{ds_name}.json')
+    os.makedirs(log_dir, exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump([[0, acc, 0]], f, indent=4)
+    return path
+
+
 @torch.no_grad()
 def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = None, log=print, limit: Optional[int] = None,
-                   device='cuda', loss: bool = False) -> Dict[str, dict]:
-    """Test + compute_error for every dataset of ``DATASET.VAL_DS``; returns {dataset: compute_error result}.  ``loss``: every
+                   device='cuda', loss: bool = False, step_metrics: bool = True) -> Dict[str, dict]:
+    """Test + compute_error for every dataset of ``DATASET.VAL_DS``; returns {dataset: compute_error result}.
+    ``step_metrics``: every batch is also scored as ``SPECTrainer.validation_step`` scores it (spec/trainer.py:272-344) - against
+    the dataset's own ground truth (``EvalDataset.eval_gt``), per joint, in one launch (``metrics.validation_errors``); the four
+    per-joint arrays go into ``evaluation_results_<ds>.pkl``, and per dataset the five lines of ``validation_epoch_end``
+    (``step_lines``) are logged, ``val_accuracy_results_<ds>.json`` is written and the result carries ``'step'`` = {'acc', 'per_sample'}.
+    Off: the log, the pkl and the folder are what they were without it.  ``loss``: every
     batch also goes through ``HMRCamLoss`` (the objective the checkpoint was trained under, spec/trainer.py:141-168, with the
     ground-truth vertices of the body model); the mean of each key over the run's images (a batch's dict weighted by its size) is
     logged after the error lines and returned under ``'loss'``.  Off by default: the log and the files are then unchanged.
@@ -242,6 +293,7 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     hm.set_precision(precision)           # (no engine yet: recorded, packed by the commit below)
     hm.to(dev).eval().commit(dev, freeze=True)
     body = metrics.BodyModel(assets.smpl_model(), device=dev)
+    Jh36m_dev = torch.as_tensor(np.asarray(Jh36m), dtype=torch.float32).to(dev)
     bs = int(hparams['DATASET']['BATCH_SIZE'])
     log_dir = hparams['LOG_DIR'] if os.path.isabs(hparams['LOG_DIR']) else os.path.join(data_root, hparams['LOG_DIR'])
     results = {}
@@ -250,12 +302,21 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         n = len(ds) if limit is None else min(limit, len(ds))
         dump = io_formats.EvalDump()
         loss_fn, loss_sum = (loss_module(hparams), None) if loss else (None, None)
+        step_v2v = []
         for b0 in range(0, n, bs):
             idx = np.arange(b0, min(n, b0 + bs))
             b = ds.batch(idx, dev, hparams['DATASET']['IMG_RES'], bool(hparams['TESTING']['USE_GT_CAM']), dtype=flow_image_dtype(hm))
             # positional call of spec/trainer.py:139
             pred = hm(b['img'], b['cam_rotmat'], b['cam_int'], b['scale'], b['center'], b['img_w'], b['img_h'])
-            dump.add(pred, imgnames=b['imgname'], dataset_name=name)
+            if step_metrics:
+                gt = ds.eval_gt(idx, dev, body)
+                pred_joints_24 = body.native(pred['pred_pose'], pred['pred_shape'], vertices=False)[1]              # spec/trainer.py:249-254
+                e = metrics.validation_errors(pred['smpl_vertices'], gt['vertices'], Jh36m_dev, pred_joints_24, gt['joints_24'])
+                dump.add(pred, imgnames=b['imgname'], dataset_name=name, mpjpe=e['err_sel'][:, :14], pampjpe=e['pa_err_sel'][:, :14],
+                         mpjpe_24=e['err_k'], pampjpe_24=e['pa_err_k'])                                              # :341-344
+                step_v2v.append(e['v2v'].cpu().numpy())
+            else:
+                dump.add(pred, imgnames=b['imgname'], dataset_name=name)
             if save_images and (b0 // bs) % save_freq == 0:
                 log(f"wrote {save_batch_picture(ds, idx, pred, os.path.join(log_dir, 'output_images'), dataloader_nb, b0 // bs, dev)}")
             if loss_fn is not None:
@@ -263,6 +324,14 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
                 gt['vertices'] = body.native(gt['pose'], gt['betas'], vertices=True, joints24=False)[0]      # spec/trainer.py:149-155,166
                 means = torch.stack(list(loss_fn(pred, gt)[1].values())).double() * len(idx)
                 loss_sum = means if loss_sum is None else loss_sum + means
+        step = None
+        if step_metrics:
+            per = {k: np.concatenate(dump.errors[k]) for k in STEP_KEYS}
+            per['v2v'] = np.concatenate(step_v2v)
+            step = {'acc': step_accuracy(per, per['v2v']), 'per_sample': per}
+            for line in step_lines(name, step['acc']):
+                log(line)
+            log(f"wrote {write_val_accuracy(log_dir, name, step['acc'])}")
         path = dump.write(log_dir, name)
         log(f'wrote {path}')
         if n != len(ds):                            # a truncated run scores the truncated annotations
@@ -286,6 +355,8 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
                 f'(target |delta W-MPJPE| <= 0.1 mm: {"met" if abs(d[0]) <= 0.1 else "NOT met"})')
             res['readme_delta_mm'] = {'wmpjpe': d[0], 'pampjpe': d[1], 'wpve': d[2]}
         res['precision'] = precision
+        if step is not None:
+            res['step'] = step
         if loss_fn is not None:
             from .engine import HMR_LOSS_KEYS
             res['loss'] = dict(zip(HMR_LOSS_KEYS, (loss_sum / n).tolist()))

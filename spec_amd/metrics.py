@@ -51,6 +51,24 @@ def eval_j_24(pred_joints, gt_joints):
 
 
 @torch.no_grad()
+def validation_errors(pred_vertices, gt_vertices, J_regressor, pred_joints=None, gt_joints=None, joint_sel=constants.H36M_TO_J14):
+    """What ``SPECTrainer.validation_step`` scores for a batch (spec/trainer.py:272-344) in one launch (``specmi_eval_step``) ->
+    dict of device tensors, per joint and in METRES (the unit of the per-joint arrays of ``evaluation_results_<ds>.pkl``):
+    ``err_sel`` / ``pa_err_sel`` (B, len(joint_sel)) of the joints ``J_regressor`` (J,V) regresses from both meshes, pelvis =
+    regressed joint 0 (the reference's ``error_per_joint`` / ``r_error_per_joint``, whose ground truth is the dataset's
+    ``pose_3d``, cam_dataset.py:443-447); ``err_k`` / ``pa_err_k`` (B, Jk) of the given joint sets, e.g. the 24 kinematic-chain
+    joints (absent without them); ``v2v`` (B,), ``compute_error_verts`` on the meshes as they are - NOT pelvis-aligned like
+    ``eval_single``'s.  A set without variance has NaN in every ``pa_err``."""
+    if pred_vertices.device.type != 'cuda':
+        raise RuntimeError('spec_amd.metrics needs device tensors (no CPU path)')
+    if (pred_joints is None) != (gt_joints is None):
+        raise ValueError('pred_joints and gt_joints are given together or not at all')
+    Jr = J_regressor[0] if J_regressor.dim() == 3 else J_regressor
+    return _engine(pred_vertices.device).eval_step(pred_vertices, gt_vertices, Jr, joint_sel=joint_sel, pred_joints=pred_joints,
+                                                   gt_joints=gt_joints)
+
+
+@torch.no_grad()
 def regress_joints(vertices, J_regressor):
     """``torch.einsum('bik,ji->bjk', vertices, J_regressor)`` (compute_error.py:184,187) on the device."""
     eng = _engine(vertices.device)
