@@ -417,6 +417,29 @@ int specmi_maxpool3x3s2_f16(specmi_handle* h, const void* x, int B, int H, int W
 int specmi_to_nhwc_f16(specmi_handle* h, const float* x, int B, int C, int H, int W, void* out,
                        void* stream);
 
+/* The three kernels of the HRNet trunks (hrnet.hip) on their own, through the launchers the trunk itself calls (parity tests).
+ * They work on any handle; no HRNet needs to be committed.  All pointers are device pointers, float tensors 16-byte aligned.
+ * Bad arguments (NULL, sizes <= 0, C % 4, a pixel stride that is not a multiple of 4 or below C, H or W not divisible by
+ * 2^sh[k], n outside 1..4) return SPECMI_ERR_ARG with a message and launch nothing. */
+
+/* The trunk's first layer: 3x3 / stride 2 / pad 1 convolution of the 3-channel NCHW image (B,3,H,W), then
+ * ReLU(acc * scale[cout] + shift[cout]), stored NHWC as (B,OH,OW,64) with OH = (H-1)/2+1, OW = (W-1)/2+1.  w holds 27 x 64
+ * floats in the kernel's own layout, index ((c*3+ky)*3+kx)*64 + cout; scale and shift hold 64 floats.  Any H, W >= 1. */
+int specmi_hr_stem3x3(specmi_handle* h, const float* images_nchw, int B, int H, int W, const float* w, const float* scale,
+                      const float* shift, float* out_nhwc, void* stream);
+
+/* The exchange-unit sum: out = [ReLU](((t0 + t1) + t2) + t3) over the first n terms, added in fp32 in exactly that order.
+ * Term k is (B, H >> sh[k], W >> sh[k], C) NHWC in pixels of ld[k] floats and is read nearest-upsampled by 2^sh[k]; out is
+ * (B,H,W,C) in pixels of ldo floats (ldo > C: a channel slice of a wider map; floats outside the slice are not touched).
+ * With n = 1, relu = 0 it is the strided copy into the concat head's slice.  Entries k >= n of the arrays are ignored. */
+int specmi_hr_fuse_sum(specmi_handle* h, const float* const terms[4], const int ld[4], const int sh[4], int n, int B, int H, int W,
+                       int C, int relu, float* out, int ldo, void* stream);
+
+/* F.interpolate(mode='bilinear', align_corners=True) on NHWC: x (B,H,W,C) in pixels of ld floats -> out (B,OH,OW,C) in pixels
+ * of ldo floats.  The source coordinate of output o is o * (in - 1) / (out - 1) along each axis, 0 where out == 1. */
+int specmi_hr_resize_ac(specmi_handle* h, const float* x, int B, int H, int W, int C, int ld, float* out, int OH, int OW, int ldo,
+                        void* stream);
+
 /* ---- crop + normalise in front of the path ------------------------------------ */
 
 /* The detection loop of spec/tester.py:116-128: for each bbox (cx, cy, w, h) [device, (n,4)]

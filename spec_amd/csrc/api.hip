@@ -1441,6 +1441,53 @@ int specmi_avgpool(specmi_handle* h, const float* x, int B, int HW, int C, float
     return SPECMI_OK;
 }
 
+// ---- HRNet's own kernels on their own (hrnet.hip): the launchers hrnet_forward calls, behind argument checks -------------------
+static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+int specmi_hr_stem3x3(specmi_handle* h, const float* images_nchw, int B, int H, int W, const float* w, const float* scale,
+                      const float* shift, float* out_nhwc, void* stream) {
+    ENTER(h);
+    if (!images_nchw || !w || !scale || !shift || !out_nhwc) return fail(h, SPECMI_ERR_ARG, "hr_stem3x3: NULL pointer");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(h, SPECMI_ERR_ARG, "hr_stem3x3: B, H and W must be positive, got %d, %d, %d", B, H, W);
+    if (misaligned16(out_nhwc)) return fail(h, SPECMI_ERR_ARG, "hr_stem3x3: out is not 16-byte aligned");
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "hr_stem3x3"};
+    return hr_launch_stem3x3(h, images_nchw, B, H, W, w, scale, shift, out_nhwc, ctx);
+}
+
+int specmi_hr_fuse_sum(specmi_handle* h, const float* const terms[4], const int ld[4], const int sh[4], int n, int B, int H, int W,
+                       int C, int relu, float* out, int ldo, void* stream) {
+    ENTER(h);
+    if (!terms || !ld || !sh || !out) return fail(h, SPECMI_ERR_ARG, "hr_fuse_sum: NULL pointer");
+    if (n < 1 || n > 4) return fail(h, SPECMI_ERR_ARG, "hr_fuse_sum: n must be 1..4, got %d", n);
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(h, SPECMI_ERR_ARG, "hr_fuse_sum: B, H, W and C must be positive, got %d, %d, %d, %d", B, H, W, C);
+    if (C % 4) return fail(h, SPECMI_ERR_ARG, "hr_fuse_sum: C must be a multiple of 4, got %d", C);
+    if (ldo % 4 || ldo < C) return fail(h, SPECMI_ERR_ARG, "hr_fuse_sum: ldo must be a multiple of 4 and >= C, got %d (C = %d)", ldo, C);
+    if (misaligned16(out)) return fail(h, SPECMI_ERR_ARG, "hr_fuse_sum: out is not 16-byte aligned");
+    for (int k = 0; k < n; ++k) {
+        if (!terms[k]) return fail(h, SPECMI_ERR_ARG, "hr_fuse_sum: term %d is NULL", k);
+        if (misaligned16(terms[k])) return fail(h, SPECMI_ERR_ARG, "hr_fuse_sum: term %d is not 16-byte aligned", k);
+        if (ld[k] % 4 || ld[k] < C) return fail(h, SPECMI_ERR_ARG, "hr_fuse_sum: ld[%d] must be a multiple of 4 and >= C, got %d (C = %d)", k, ld[k], C);
+        if (sh[k] < 0 || sh[k] > 30 || (H >> sh[k]) << sh[k] != H || (W >> sh[k]) << sh[k] != W)
+            return fail(h, SPECMI_ERR_ARG, "hr_fuse_sum: %dx%d is not divisible by 2^sh[%d] (sh = %d)", H, W, k, sh[k]);
+    }
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "hr_fuse_sum"};
+    return hr_launch_fuse_sum(h, terms, ld, sh, n, B, H, W, C, relu ? 1 : 0, out, ldo, ctx);
+}
+
+int specmi_hr_resize_ac(specmi_handle* h, const float* x, int B, int H, int W, int C, int ld, float* out, int OH, int OW, int ldo,
+                        void* stream) {
+    ENTER(h);
+    if (!x || !out) return fail(h, SPECMI_ERR_ARG, "hr_resize_ac: NULL pointer");
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || OH <= 0 || OW <= 0)
+        return fail(h, SPECMI_ERR_ARG, "hr_resize_ac: B, H, W, C, OH and OW must be positive, got %d, %d, %d, %d, %d, %d", B, H, W, C, OH, OW);
+    if (C % 4) return fail(h, SPECMI_ERR_ARG, "hr_resize_ac: C must be a multiple of 4, got %d", C);
+    if (ld % 4 || ld < C) return fail(h, SPECMI_ERR_ARG, "hr_resize_ac: ld must be a multiple of 4 and >= C, got %d (C = %d)", ld, C);
+    if (ldo % 4 || ldo < C) return fail(h, SPECMI_ERR_ARG, "hr_resize_ac: ldo must be a multiple of 4 and >= C, got %d (C = %d)", ldo, C);
+    if (misaligned16(x) || misaligned16(out)) return fail(h, SPECMI_ERR_ARG, "hr_resize_ac: x or out is not 16-byte aligned");
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "hr_resize_ac"};
+    return hr_launch_resize_ac(h, x, B, H, W, C, ld, out, OH, OW, ldo, ctx);
+}
+
 // every *_f16 producer: the output is NHWC8 fp16 (include/specmi.h), one 16-byte vector per pixel
 #define NEED_ALIGNED16(h, p) \
     if (reinterpret_cast<uintptr_t>(p) & 15) return fail(h, SPECMI_ERR_ARG, "the NHWC8 fp16 output is not 16-byte aligned");

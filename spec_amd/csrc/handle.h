@@ -247,3 +247,11 @@ int hrnet_commit(specmi_handle* h, const std::string& prefix, int width, int use
 // images NCHW -> (B, H/32, W/32, feat_ch) NHWC in feat_out
 const float* hrnet_feat_ws(specmi_handle* h);   // the internal (B, fh, fw, feat_ch) buffer used when feat_out == NULL
 int hrnet_forward(specmi_handle* h, const float* images, int B, int H, int W, float* feat_out, int* fh, int* fw, hipStream_t s);
+// the launchers of HRNet's own kernels, shared by hrnet_forward and the kernel-level entries (specmi_hr_*): they return a
+// specmi status and leave the message on the handle.  The callers guarantee C % 4 == 0, ld % 4 == 0 and 16-byte aligned pointers.
+int hr_launch_stem3x3(specmi_handle* h, const float* images, int B, int H, int W, const float* w, const float* scale,
+                      const float* shift, float* out, const LaunchCtx& ctx);
+int hr_launch_fuse_sum(specmi_handle* h, const float* const* terms, const int* ld, const int* sh, int nt, int B, int H, int W, int C,
+                       int relu, float* out, int ldo, const LaunchCtx& ctx);
+int hr_launch_resize_ac(specmi_handle* h, const float* x, int B, int H, int W, int C, int ld, float* out, int OH, int OW, int ldo,
+                        const LaunchCtx& ctx);

@@ -1314,6 +1314,78 @@ class Engine:
         _lib.check(self.h, self.lib.specmi_avgpool(self.h, _ptr(x), B, H * W, Cc, _ptr(out), self._stream()))
         return out
 
+    # ---- HRNet's own kernels on their own (tests): the launchers the trunk calls ---------------
+    def _nhwc_rows(self, t):
+        """-> (fp32 device tensor, pixel stride): a (B,H,W,C) view with unit channel stride and one pixel stride ld >= C is
+        passed as it is (a channel slice of a wider map), anything else as a dense copy."""
+        if isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 4 and t.device == self.device:
+            ld = self._pixel_rows(t)
+            if ld is not None:
+                return t, ld
+        t = _dev_f32(t, self.device)
+        if t.dim() != 4:
+            raise ValueError(f'expected a (B,H,W,C) tensor, got shape {tuple(t.shape)}')
+        return t, t.shape[-1]
+
+    def _nhwc_out(self, out, shape):
+        """The output of a kernel-level call: ``out`` (a float32 device view of ``shape`` in pixel rows) or a dense new tensor."""
+        if out is None:
+            return self._empty(*shape), shape[-1]
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == self.device and tuple(out.shape) == tuple(shape)):
+            raise ValueError(f'out must be a float32 tensor of shape {tuple(shape)} on {self.device}')
+        ldo = self._pixel_rows(out)
+        if ldo is None:
+            raise ValueError(f'out: unit channel stride and one pixel stride >= C expected, got strides {tuple(out.stride())}')
+        return out, ldo
+
+    def hr_stem3x3(self, images, w_oihw, scale, shift, out=None):
+        """HRNet's first layer on its own (specmi_hr_stem3x3): images (B,3,H,W) fp32 NCHW, w (64,3,3,3) OIHW, scale / shift (64)
+        -> ReLU(conv3x3 / stride 2 / pad 1 * scale + shift) as (B,OH,OW,64) NHWC.  out: a dense tensor of that shape to write into."""
+        x = _dev_f32(images, self.device)
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f'images must be (B,3,H,W), got {tuple(x.shape)}')
+        w = np.asarray(w_oihw, dtype=np.float32)
+        if w.shape != (64, 3, 3, 3):
+            raise ValueError(f'w must be (64,3,3,3), got {w.shape}')
+        wk = _dev_f32(np.ascontiguousarray(w.reshape(64, 27).T), self.device)       # [(c*3+ky)*3+kx][cout]
+        sc, sh = _dev_f32(scale, self.device, (64,)), _dev_f32(shift, self.device, (64,))
+        B, _, H, W = x.shape
+        out, ldo = self._nhwc_out(out, (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64))
+        if ldo != 64:
+            raise ValueError('the stem writes a dense (B,OH,OW,64) map')
+        _lib.check(self.h, self.lib.specmi_hr_stem3x3(self.h, _ptr(x), B, H, W, _ptr(wk), _ptr(sc), _ptr(sh), _ptr(out), self._stream()))
+        return out
+
+    def hr_fuse_sum(self, terms, sh, relu=True, out=None):
+        """HRNet's exchange-unit sum on its own (specmi_hr_fuse_sum): out = [ReLU](((t0 + t1) + t2) + t3) in that order, term k
+        (B, H >> sh[k], W >> sh[k], C) NHWC read nearest-upsampled by 2^sh[k].  Terms and out may be channel-sliced views of
+        wider maps (each with its own pixel stride); one term, relu=False: the strided copy into the concat head's slice."""
+        n = len(terms)
+        if not 1 <= n <= 4 or len(sh) != n:
+            raise ValueError('one to four terms, one shift each')
+        rows = [self._nhwc_rows(t) for t in terms]
+        B, h0, w0, Cc = rows[0][0].shape
+        H, W = h0 << sh[0], w0 << sh[0]
+        for (t, _), s in zip(rows, sh):
+            if s < 0 or tuple(t.shape) != (B, H >> s, W >> s, Cc) or (H >> s) << s != H or (W >> s) << s != W:
+                raise ValueError(f'term of shape {tuple(t.shape)} with shift {s} does not make a {(B, H, W, Cc)} map')
+        out, ldo = self._nhwc_out(out, (B, H, W, Cc))
+        ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t, _ in rows], *([None] * (4 - n)))
+        lds = (C.c_int * 4)(*[ld for _, ld in rows], *([0] * (4 - n)))
+        shs = (C.c_int * 4)(*[int(s) for s in sh], *([0] * (4 - n)))
+        _lib.check(self.h, self.lib.specmi_hr_fuse_sum(self.h, ptrs, lds, shs, n, B, H, W, Cc, int(bool(relu)), _ptr(out), ldo, self._stream()))
+        return out
+
+    def hr_resize_ac(self, x, size, out=None):
+        """HRNet's 'interp' head resize on its own (specmi_hr_resize_ac): F.interpolate(bilinear, align_corners=True) of x
+        (B,H,W,C) NHWC to size = (OH, OW).  x and out may be channel-sliced views of wider maps."""
+        x, ld = self._nhwc_rows(x)
+        B, H, W, Cc = x.shape
+        OH, OW = int(size[0]), int(size[1])
+        out, ldo = self._nhwc_out(out, (B, OH, OW, Cc))
+        _lib.check(self.h, self.lib.specmi_hr_resize_ac(self.h, _ptr(x), B, H, W, Cc, ld, _ptr(out), OH, OW, ldo, self._stream()))
+        return out
+
     # ---- profiling -------------------------------------------------------------------------
     def profile(self, on: bool):
         _lib.check(self.h, self.lib.specmi_profile_enable(self.h, int(on)))
