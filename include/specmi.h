@@ -417,6 +417,21 @@ int specmi_maxpool3x3s2_f16(specmi_handle* h, const void* x, int B, int H, int W
 int specmi_to_nhwc_f16(specmi_handle* h, const float* x, int B, int C, int H, int W, void* out,
                        void* stream);
 
+/* One Linear layer of the heads on caller-supplied parameters, through the code the heads run (parity tests): nheads (1..3)
+ * layers of one shape, head i with HOST weights w_host[i] (N,K) row-major and bias_host[i] (N), packed and uploaded exactly as
+ * specmi_commit packs a Linear layer (K zero padded to Kp = K rounded up to 32) into temporaries that are freed before the
+ * call returns.  x[i]: B device rows of ldx floats of which the first Kp are READ (columns K..Kp meet zero weights; they must be
+ * readable, their values do not matter as long as they are finite); out[i][b*ldo + n] = w[n] . x[b] + bias[n]
+ * (+ residual[i][b*ldo + n]) for n < N; nothing else of out is written.  residual may be NULL (no head has one) and
+ * residual[i] may equal out[i].  path 0: the small-batch GEMV kernel, all heads in one launch (an image's sum has a fixed
+ * order whatever B is); path 1: the matrix-core GEMM in row blocks of 1024 (option "fc_splitk" applies), one head.  Refused
+ * with SPECMI_ERR_ARG and a message, nothing launched: nheads outside 1..3, N, K or B < 1, ldx < Kp, ldx % 4 != 0, ldo < N, an
+ * x[i] that is not 16-byte aligned, an out / residual that is not 4-byte aligned, path 1 with more than one head.
+ * Synchronises the stream. */
+int specmi_fc_forward(specmi_handle* h, int nheads, const float* const* w_host, const float* const* bias_host, int N, int K,
+                      const float* const* x, int ldx, const float* const* residual, float* const* out, int ldo, int B, int path,
+                      void* stream);
+
 /* The three kernels of the HRNet trunks (hrnet.hip) on their own, through the launchers the trunk itself calls (parity tests).
  * They work on any handle; no HRNet needs to be committed.  All pointers are device pointers, float tensors 16-byte aligned.
  * Bad arguments (NULL, sizes <= 0, C % 4, a pixel stride that is not a multiple of 4 or below C, H or W not divisible by

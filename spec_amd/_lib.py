@@ -140,6 +140,10 @@ PROTOTYPES = {
                                      C.c_void_p, C.c_void_p]),
     'specmi_avgpool': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                  C.c_void_p]),
+    # (h, nheads, w_host[3], bias_host[3], N, K, x[3], ldx, residual[3], out[3], ldo, B, path, stream)
+    'specmi_fc_forward': (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int,
+                                    C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.c_int,
+                                    C.c_int, C.c_void_p]),
     'specmi_hr_stem3x3': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
     'specmi_hr_fuse_sum': (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int,

@@ -1441,8 +1441,53 @@ int specmi_avgpool(specmi_handle* h, const float* x, int B, int HW, int C, float
     return SPECMI_OK;
 }
 
-// ---- HRNet's own kernels on their own (hrnet.hip): the launchers hrnet_forward calls, behind argument checks -------------------
 static bool misaligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+
+// One Linear layer (or up to three of one shape in one GEMV launch) on caller-supplied parameters, through the code the heads run:
+// upload_fc (what commit_fc uploads) into temporaries, then launch_fc_gemv (path 0) or run_fc (path 1)
+int specmi_fc_forward(specmi_handle* h, int nheads, const float* const* w_host, const float* const* bias_host, int N, int K,
+                      const float* const* x, int ldx, const float* const* residual, float* const* out, int ldo, int B, int path,
+                      void* stream) {
+    ENTER(h);
+    if (!w_host || !bias_host || !x || !out) return fail(h, SPECMI_ERR_ARG, "fc_forward: NULL pointer");
+    if (nheads < 1 || nheads > 3) return fail(h, SPECMI_ERR_ARG, "fc_forward: nheads must be 1..3, got %d", nheads);
+    if (N <= 0 || K <= 0 || B <= 0) return fail(h, SPECMI_ERR_ARG, "fc_forward: N, K and B must be positive, got %d, %d, %d", N, K, B);
+    if (path != 0 && path != 1) return fail(h, SPECMI_ERR_ARG, "fc_forward: path must be 0 (GEMV) or 1 (matrix cores), got %d", path);
+    if (path == 1 && nheads != 1) return fail(h, SPECMI_ERR_ARG, "fc_forward: the matrix-core path takes one head, got %d", nheads);
+    const int Kp = round_up(K, 32);
+    if (ldx < Kp) return fail(h, SPECMI_ERR_ARG, "fc_forward: ldx (%d) < K rounded up to 32 (%d): the kernels read the padded row", ldx, Kp);
+    if (ldx % 4) return fail(h, SPECMI_ERR_ARG, "fc_forward: ldx must be a multiple of 4, got %d", ldx);
+    if (ldo < N) return fail(h, SPECMI_ERR_ARG, "fc_forward: ldo (%d) < N (%d)", ldo, N);
+    for (int i = 0; i < nheads; ++i) {
+        if (!w_host[i] || !bias_host[i] || !x[i] || !out[i]) return fail(h, SPECMI_ERR_ARG, "fc_forward: head %d has a NULL pointer", i);
+        if (misaligned16(x[i])) return fail(h, SPECMI_ERR_ARG, "fc_forward: x of head %d is not 16-byte aligned", i);
+        if ((reinterpret_cast<uintptr_t>(out[i]) & 3) || (residual && (reinterpret_cast<uintptr_t>(residual[i]) & 3)))
+            return fail(h, SPECMI_ERR_ARG, "fc_forward: out / residual of head %d is not 4-byte aligned", i);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    std::vector<void*> tmp;
+    FcW fc[3];
+    int rc = SPECMI_OK;
+    for (int i = 0; i < nheads && !rc; ++i) rc = upload_fc(h, w_host[i], bias_host[i], N, K, fc[i], tmp);
+    int lrc = 0;
+    if (!rc && path == 0) {
+        FcGemv hd[3];
+        for (int i = 0; i < nheads; ++i) hd[i] = FcGemv{x[i], fc[i].w_rm, fc[i].shift, residual ? residual[i] : nullptr, out[i]};
+        LaunchCtx ctx{s, &h->prof, "fc_forward"};
+        lrc = launch_fc_gemv(hd, nheads, N, Kp, ldx, ldo, B, ctx);
+    } else if (!rc) {
+        rc = run_fc(h, fc[0], x[0], ldx, B, residual ? residual[0] : nullptr, out[0], ldo, s, "fc_forward");
+    }
+    hipError_t se = hipStreamSynchronize(s);
+    free_pool(tmp);
+    if (rc) return rc;
+    if (lrc == (int)hipErrorInvalidValue) return fail(h, SPECMI_ERR_ARG, "fc_forward: shape, stride or alignment not supported");
+    if (lrc) return fail(h, SPECMI_ERR_HIP, "fc_forward launch failed: %s", hipGetErrorString((hipError_t)lrc));
+    if (se != hipSuccess) return fail(h, SPECMI_ERR_HIP, "fc_forward failed: %s", hipGetErrorString(se));
+    return SPECMI_OK;
+}
+
+// ---- HRNet's own kernels on their own (hrnet.hip): the launchers hrnet_forward calls, behind argument checks -------------------
 
 int specmi_hr_stem3x3(specmi_handle* h, const float* images_nchw, int B, int H, int W, const float* w, const float* scale,
                       const float* shift, float* out_nhwc, void* stream) {

@@ -191,21 +191,34 @@ int commit_fused_ds(specmi_handle* h, const std::string& prefix, Bneck& b) {
 
 // One or several Linear layers stacked along the output dimension
 // (nout, nin) -> (nout, Kp) row-major with zero padding: the operand of the small-batch GEMV kernel (head.hip)
-static int upload_row_major(specmi_handle* h, const float* w, int nout, int nin, FcW& fc) {
+static int upload_row_major(specmi_handle* h, const float* w, int nout, int nin, FcW& fc, std::vector<void*>& pool) {
     std::vector<float> rm((size_t)nout * fc.Kp, 0.f);
     for (int n = 0; n < nout; ++n) std::memcpy(rm.data() + (size_t)n * fc.Kp, w + (size_t)n * nin, (size_t)nin * 4);
-    return dev_upload(h, rm.data(), rm.size() * 4, (void**)&fc.w_rm, h->param_allocs);
+    return dev_upload(h, rm.data(), rm.size() * 4, (void**)&fc.w_rm, pool);
+}
+
+// (ntot, nin) row-major weights + (ntot) bias -> both device forms of the layer, allocated from `pool`: the packed matrix-core
+// operand [Kp/4][Npad][4] with scale 1 / shift = bias (Npad entries, zero padded) and the GEMV kernel's zero-padded rows
+int upload_fc(specmi_handle* h, const float* w, const float* b, int ntot, int nin, FcW& fc, std::vector<void*>& pool) {
+    fc.nin = nin;
+    fc.nout = ntot;
+    fc.Kp = round_up(nin, 32);
+    fc.Npad = round_up(ntot, 64);
+    std::vector<float> bias(fc.Npad, 0.f), ones(fc.Npad, 1.f), packed;
+    std::memcpy(bias.data(), b, (size_t)ntot * 4);
+    pack_gemm_weights(w, ntot, nin, 1, 1, fc.Kp, fc.Npad, packed);
+    int rc;
+    if ((rc = dev_upload(h, packed.data(), packed.size() * 4, (void**)&fc.w, pool))) return rc;
+    if ((rc = dev_upload(h, ones.data(), ones.size() * 4, (void**)&fc.scale, pool))) return rc;
+    if ((rc = dev_upload(h, bias.data(), bias.size() * 4, (void**)&fc.shift, pool))) return rc;
+    return upload_row_major(h, w, ntot, nin, fc, pool);
 }
 
 int commit_fc(specmi_handle* h, const std::vector<std::string>& names, const std::vector<int>& nouts, int nin,
                      FcW& fc) {
     int ntot = 0;
     for (int n : nouts) ntot += n;
-    fc.nin = nin;
-    fc.nout = ntot;
-    fc.Kp = round_up(nin, 32);
-    fc.Npad = round_up(ntot, 64);
-    std::vector<float> wcat((size_t)ntot * nin), bias(fc.Npad, 0.f), ones(fc.Npad, 1.f);
+    std::vector<float> wcat((size_t)ntot * nin), bias(ntot);
     int row = 0, rc;
     for (size_t i = 0; i < names.size(); ++i) {
         const HostTensor *w, *b;
@@ -215,12 +228,7 @@ int commit_fc(specmi_handle* h, const std::vector<std::string>& names, const std
         std::memcpy(bias.data() + row, b->f.data(), (size_t)nouts[i] * 4);
         row += nouts[i];
     }
-    std::vector<float> packed;
-    pack_gemm_weights(wcat.data(), ntot, nin, 1, 1, fc.Kp, fc.Npad, packed);
-    if ((rc = dev_upload(h, packed.data(), packed.size() * 4, (void**)&fc.w, h->param_allocs))) return rc;
-    if ((rc = dev_upload(h, ones.data(), ones.size() * 4, (void**)&fc.scale, h->param_allocs))) return rc;
-    if ((rc = dev_upload(h, bias.data(), bias.size() * 4, (void**)&fc.shift, h->param_allocs))) return rc;
-    return upload_row_major(h, wcat.data(), ntot, nin, fc);
+    return upload_fc(h, wcat.data(), bias.data(), ntot, nin, fc, h->param_allocs);
 }
 
 // HMRHead in eval mode is an affine map: there is no activation between fc1, fc2 and the decoders and dropout is
@@ -365,7 +373,7 @@ int commit_head_collapsed(specmi_handle* h, int F, int ucf) {
     if ((rc = dev_upload(h, packed.data(), packed.size() * 4, (void**)&fc.w, h->param_allocs))) return rc;
     if ((rc = dev_upload(h, ones.data(), ones.size() * 4, (void**)&fc.scale, h->param_allocs))) return rc;
     if ((rc = dev_upload(h, bias.data(), bias.size() * 4, (void**)&fc.shift, h->param_allocs))) return rc;
-    if ((rc = upload_row_major(h, wcat.data(), NO, nin, fc))) return rc;
+    if ((rc = upload_row_major(h, wcat.data(), NO, nin, fc, h->param_allocs))) return rc;
     h->has_head_c = true;
     return SPECMI_OK;
 }

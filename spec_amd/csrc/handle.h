@@ -236,6 +236,8 @@ int commit_conv(specmi_handle* h, const std::string& prefix, ConvW& c);
 void pack_gemm_weights(const float* w, int cout, int cin, int kh, int kw, int Kp, int Npad, std::vector<float>& out);
 int commit_fused_ds(specmi_handle* h, const std::string& prefix, Bneck& b);
 int commit_fc(specmi_handle* h, const std::vector<std::string>& names, const std::vector<int>& nouts, int nin, FcW& fc);
+// what commit_fc uploads for its stacked (ntot, nin) weights and (ntot) bias, allocated from `pool` (specmi_fc_forward: a temporary one)
+int upload_fc(specmi_handle* h, const float* w, const float* b, int ntot, int nin, FcW& fc, std::vector<void*>& pool);
 int commit_head_collapsed(specmi_handle* h, int F, int ucf);
 void build_resnet(specmi_handle* h, int depth);
 int commit_smpl(specmi_handle* h);

@@ -74,7 +74,7 @@ int launch_head_final(const float* state, long ld_state, float* pred_pose, float
 // (optionally activated) extra decoder outputs of the LAST iteration
 __device__ __forceinline__ float uncertainty_act(float x, int act) {
     switch (act) {
-        case 1: return fmaxf(x, 0.f);                                  // F.relu
+        case 1: return x < 0.f ? 0.f : x;                              // F.relu: a NaN stays a NaN (fmaxf(NaN, 0) is 0)
         case 2: return x > 20.f ? x : log1pf(expf(x));                 // F.softplus (beta 1, threshold 20)
         case 3: return 1.f / (1.f + expf(-x));                         // F.sigmoid
         case 4: return tanhf(x);                                       // F.tanh
@@ -234,11 +234,14 @@ int launch_fc_gemv(const FcGemv* heads, int nheads, int N, int Kp, int ldx, int 
 }
 
 // soft_idx_to_angle of head 0 / 1 / 2 = vfov / pitch / roll (camcalib/cam_utils.py:94-107,128-133): (max - min) is a python double
-// rounded to fp32 when it meets the tensor
+// rounded to fp32 when it meets the tensor.  The product and the sum are rounded separately, as torch's two tensor operations are
+// (the pragma: under the build's -ffp-contract=fast they became one fused multiply-add, up to 3 ulp away at angles near 0)
 __device__ __forceinline__ float soft_idx_to_angle(float s, int head) {
+#pragma clang fp contract(off)
     const float span = head == 0 ? (float)(2.1 - 0.2617) : (float)(0.6 - (-0.6));
     const float lo = head == 0 ? (float)0.2617 : (float)-0.6;
-    return span * ((s + 1.0f) / 2.0f) + lo;
+    const float p = span * ((s + 1.0f) / 2.0f);
+    return p + lo;
 }
 
 // soft-argmax decode of image b: waves 0..2 = vfov / pitch / roll (a fourth wave idles), `ang` = 3 floats of LDS

@@ -1314,6 +1314,34 @@ class Engine:
         _lib.check(self.h, self.lib.specmi_avgpool(self.h, _ptr(x), B, H * W, Cc, _ptr(out), self._stream()))
         return out
 
+    def fc_forward(self, w, bias, x, out, B, residual=None, path=0, ldx=None, ldo=None):
+        """One Linear layer of the heads on its own (specmi_fc_forward, tests).  One head: w (N,K), bias (N), x, out; up to three
+        heads of one shape: lists of those.  x: fp32 device tensors holding B rows of ldx floats (default: the tensor's row stride),
+        out (and residual, which may be out itself): device tensors of 4-byte words holding B rows of ldo words - only
+        out[b*ldo + n], n < N, is written.  path 0 = the small-batch GEMV kernel, 1 = the matrix-core GEMM (one head)."""
+        many = isinstance(w, (list, tuple))
+        ws, bs, xs, outs = (list(v) if many else [v] for v in (w, bias, x, out))
+        rs = None if residual is None else (list(residual) if many else [residual])
+        n = len(ws)
+        if not 1 <= n <= 3 or len(bs) != n or len(xs) != n or len(outs) != n or (rs is not None and len(rs) != n):
+            raise ValueError('one to three heads, each with its weights, bias, x and out')
+        ws = [np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in ws]
+        bs = [np.ascontiguousarray(np.asarray(a, dtype=np.float32)) for a in bs]
+        N, K = ws[0].shape
+        if any(a.shape != (N, K) for a in ws) or any(a.shape != (N,) for a in bs):
+            raise ValueError(f'every head needs (N, K) = {(N, K)} weights and an (N,) bias')
+        for a in xs + outs + (rs or []):
+            if not (isinstance(a, torch.Tensor) and a.device == self.device and a.element_size() == 4):
+                raise ValueError(f'x, out and residual must be tensors of 4-byte words on {self.device}')
+        ldx = int(xs[0].stride(0) if ldx is None else ldx)
+        ldo = int(outs[0].stride(0) if ldo is None else ldo)
+        arr = lambda ptrs: (C.c_void_p * 3)(*ptrs, *([None] * (3 - n)))
+        _lib.check(self.h, self.lib.specmi_fc_forward(
+            self.h, n, arr([a.ctypes.data for a in ws]), arr([a.ctypes.data for a in bs]), N, K, arr([a.data_ptr() for a in xs]), ldx,
+            None if rs is None else arr([a.data_ptr() for a in rs]), arr([a.data_ptr() for a in outs]), ldo, int(B), int(path),
+            self._stream()))
+        return out
+
     # ---- HRNet's own kernels on their own (tests): the launchers the trunk calls ---------------
     def _nhwc_rows(self, t):
         """-> (fp32 device tensor, pixel stride): a (B,H,W,C) view with unit channel stride and one pixel stride ld >= C is

@@ -95,3 +95,39 @@ def test_python_front_end_raises_with_the_library_message():
     sc, ce, iw, ih = [t(a).to(DEV) for a in synth.bbox_inputs(2, 2)]
     with pytest.raises(ValueError):                  # wrong side-input shape
         hm(x, torch.eye(3, device=DEV)[None].repeat(3, 1, 1), torch.eye(3, device=DEV)[None].repeat(2, 1, 1), sc, ce, iw, ih)
+
+
+def test_fc_forward_refusals():
+    """specmi_fc_forward refuses what launch_fc_gemv / run_fc cannot take - with SPECMI_ERR_ARG, a message, nothing written - and the
+    handle then runs the same layer."""
+    from spec_amd.engine import Engine
+    eng = Engine('camcalib', torch.device(DEV))
+    lib, h = eng.lib, eng.h
+    N, K, B, ldx, ldo = 5, 40, 2, 64, 8                    # K rounded up to 32 is 64
+    w, b = np.ones((N, K), np.float32), np.arange(N, dtype=np.float32)
+    x = torch.ones(B * ldx + 8, device=DEV)
+    out = torch.full((B * ldo + 8,), 0x5A5AA5A5, dtype=torch.int32, device=DEV)
+    arr = lambda *v: (C.c_void_p * 3)(*v)
+
+    def call(nheads=1, N=N, K=K, B=B, ldx=ldx, ldo=ldo, path=0, xoff=0, ooff=0, res=False, wp=None):
+        wp = arr(*[w.ctypes.data] * 3) if wp is None else wp
+        o = arr(*[out.data_ptr() + ooff] * 3)
+        return lib.specmi_fc_forward(h, nheads, wp, arr(*[b.ctypes.data] * 3), N, K, arr(*[x.data_ptr() + xoff] * 3), ldx, o if res else None,
+                                     o, ldo, B, path, None)
+
+    for kwargs, word in ((dict(nheads=0), 'nheads'), (dict(nheads=4), 'nheads'), (dict(N=0), 'positive'), (dict(K=0), 'positive'),
+                         (dict(B=0), 'positive'), (dict(path=2), 'path'), (dict(ldx=60), 'ldx (60) <'), (dict(ldx=66), 'multiple of 4'),
+                         (dict(ldo=4), 'ldo (4) < N (5)'), (dict(xoff=4), '16-byte'), (dict(ooff=2), '4-byte'), (dict(ooff=2, res=True), '4-byte'),
+                         (dict(path=1, nheads=2), 'one head'), (dict(path=1, ldx=60), 'ldx (60) <'), (dict(path=1, xoff=8), '16-byte'),
+                         (dict(wp=arr(None, None, None)), 'NULL')):
+        assert call(**kwargs) == _lib.ERR_ARG and word in _err(lib, h), (kwargs, _err(lib, h))
+    assert lib.specmi_fc_forward(h, 1, None, None, N, K, None, ldx, None, None, ldo, B, 0, None) == _lib.ERR_ARG and 'NULL' in _err(lib, h)
+    torch.cuda.synchronize()
+    assert bool((out == 0x5A5AA5A5).all())
+    for path in (0, 1):
+        assert call(path=path) == _lib.OK, _err(lib, h)
+        got = out.cpu().numpy()
+        assert np.array_equal(got[:B * ldo].reshape(B, ldo)[:, :N].copy().view(np.float32), np.tile(K + b, (B, 1)))
+        assert np.all(got[:B * ldo].reshape(B, ldo)[:, N:] == 0x5A5AA5A5) and np.all(got[B * ldo:] == 0x5A5AA5A5)
+        out.fill_(0x5A5AA5A5)
+    eng.close()
