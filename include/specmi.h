@@ -798,6 +798,75 @@ int specmi_jpeg_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_
  * quality outside [1, 100], H or W outside [1, 32768] or a capacity below 623. */
 int specmi_jpeg_header(int quality, int H, int W, uint8_t* out, size_t capacity);
 
+/* BASELINE JPEG FILES decoded on the device, all files of a call together: the read side of specmi_jpeg_encode.  Replaces the
+ * host decode (PIL's Image.open(path).convert('RGB')) and the upload of the raw frames in front of every flow that reads .jpg
+ * frames - the files' bytes go up instead, 10 to 20 times fewer.
+ * THE CONTRACT (stated in full at the head of spec_amd/csrc/jpeg_dec.hip, restated in NumPy in tests/jpeg_dec_ref.py): for a
+ * SUPPORTED file the (H, W, 3) uint8 RGB picture equals np.array(Image.open(f).convert('RGB')) on a libjpeg-turbo build of
+ * Pillow, element for element: libjpeg's islow IDCT, fancy 4:2:0 upsampling and 16-bit fixed-point colour conversion.
+ *
+ * specmi_jpeg_probe: host only, needs no handle and no device.  Parses the markers of `file` (HOST, `bytes` long) and says
+ * whether specmi_jpeg_decode takes it: *reason receives SPECMI_JPEG_SUPPORTED or why not, *H and *W the picture's size and
+ * *sampling 420 or 444 (all three 0 when not supported).  SUPPORTED is: one SOF0 with 8-bit samples; three
+ * components, YCbCr; sampling 2x2,1x1,1x1 or 1x1,1x1,1x1; one interleaved scan (Ss 0, Se 63, Ah/Al 0); 8-bit quantisation
+ * tables; Huffman tables from the file's own DHT segments, ids 0 and 1; no DRI with a non-zero interval; H and W in [1, 32768];
+ * no Adobe APP14 segment and not the component ids 'R','G','B' without JFIF; EOI as the last two bytes.  The reasons:
+ *   NOT_JPEG (no SOI, bytes that are no marker)   TRUNCATED (the header or the EOI is cut off)   PROGRESSIVE (SOF2)
+ *   SOF (any other frame type, a second frame)    PRECISION (12-bit samples, 16-bit tables)      COMPONENTS (greyscale, CMYK)
+ *   SAMPLING (4:2:2, 4:4:0, ...)   RESTART   SCAN (not one interleaved sequential scan)   COLOURSPACE (Adobe, RGB ids)
+ *   TABLES (a table is missing, malformed or has an id above 1)   SIZE   TRAILING (bytes behind the EOI)
+ * The probe reads the markers up to the first SOS and the file's last two bytes; it does NOT look inside the scan.  A file with
+ * a second scan, or any other marker between the first SOS and the final EOI, therefore counts as supported here; specmi_jpeg_decode
+ * launches it, finds the marker (status bit 128) and the caller decodes it on the host like a damaged file.
+ * Returns SPECMI_ERR_ARG for a null pointer, else SPECMI_OK.
+ *
+ * specmi_jpeg_decode.  DEVICE pointers: in_slab, the files' bytes, of in_slab_bytes; out_slab, uint8 RGB, of out_slab_bytes,
+ * which must not overlap in_slab - the slab and offsets convention of the ragged calls, what spec_amd.preprocess.pack_frames
+ * builds; status (n int32); coef (optional, NULL in the flows: receives the coefficient workspace after the dc stage -
+ * (blocks, 64) int16, natural order within a block, MCU order between blocks, file after file - of coef_bytes >= 128 bytes per
+ * block; it lets a test name the stage that is wrong).  HOST: files_host, the SAME bytes as in_slab (the probe reads the
+ * markers from them; the scan is read on the device only; that the two agree is the caller's contract and is not checked - a
+ * difference cannot take a read or a write out of bounds, it only gives a status or pixels that belong to no file); THE FILE RECORD, two arrays with one row per file:
+ *   file_ranges (n x 2 int64):  offset of the file's first byte in in_slab and files_host, length
+ *   out_offsets (n x 2 int64):  offset of the picture's first pixel in out_slab, pitch (bytes from one row to the next, >= 3 W)
+ * and passes (optional): receives how often the sync stage was launched.
+ * status[i] is 0 when file i's scan satisfied T.81 F.2.2 completely; else a set of bits - 1 an invalid code, 2 a zigzag index
+ * beyond 63, 4 a DC category above 11 or an AC size above 10, 8 |coefficient x quantiser| above 32767, 16 the scan ended early,
+ * 32 bits left over, 64 a block count that is not the file's, 128 a marker inside the scan - and the picture's rectangle is then
+ * unspecified: the caller decodes that file on the host, so that the device never has to agree with libjpeg on a damaged file.
+ * Bytes of out_slab outside the rectangles (H rows of 3 W bytes) are not touched.  A file's pixels do not depend on the other
+ * files of the call, on its place in the slabs or on scheduling.
+ * Every read of a file is confined to its byte range, every write to its rectangle or its share of the workspace; no kernel
+ * waits for another workgroup.  The call SYNCHRONISES THE STREAM once per pass of the sync stage but the last (one word is read
+ * back; at most as many passes as the largest file has groups of 256 x 128 scan bytes), and is therefore refused while the
+ * stream is being captured (SPECMI_ERR_STATE; the stream is asked first, so the capture stays valid and nothing is enqueued).
+ * Refused (SPECMI_ERR_ARG), launching nothing: a null pointer (coef and passes excepted); n outside [1, 65535]; a file range
+ * that leaves in_slab; a file the probe refuses; a pitch below 3 W; a rectangle that leaves out_slab; overlapping slabs; two
+ * rectangles that share a byte; a coef_bytes too small; more than 2^24 MCUs in all.
+ * The file records (with quantisers and Huffman tables) live in one device table owned by the handle, under the rule of the
+ * ragged calls above: a call whose records differ from the previous call's rewrites the table and first SYNCHRONISES THE
+ * WHOLE DEVICE.  The workspace is one per handle (growth synchronises the device): per MCU of 16 x 16 pixels 768 bytes of
+ * coefficients and 384 of planes - 4.5 bytes per pixel of the pictures rounded up to whole MCUs (9 at 4:4:4) - plus 16 bytes
+ * per 128 scan bytes and 8 per group. */
+#define SPECMI_JPEG_SUPPORTED 0
+#define SPECMI_JPEG_NOT_JPEG 1
+#define SPECMI_JPEG_TRUNCATED 2
+#define SPECMI_JPEG_PROGRESSIVE 3
+#define SPECMI_JPEG_SOF 4
+#define SPECMI_JPEG_PRECISION 5
+#define SPECMI_JPEG_COMPONENTS 6
+#define SPECMI_JPEG_SAMPLING 7
+#define SPECMI_JPEG_RESTART 8
+#define SPECMI_JPEG_SCAN 9
+#define SPECMI_JPEG_COLOURSPACE 10
+#define SPECMI_JPEG_TABLES 11
+#define SPECMI_JPEG_SIZE 12
+#define SPECMI_JPEG_TRAILING 13
+int specmi_jpeg_probe(const uint8_t* file, size_t bytes, int32_t* reason, int32_t* H, int32_t* W, int32_t* sampling);
+int specmi_jpeg_decode(specmi_handle* h, const uint8_t* files_host, const uint8_t* in_slab, size_t in_slab_bytes, const int64_t* file_ranges,
+                       uint8_t* out_slab, size_t out_slab_bytes, const int64_t* out_offsets, int n, int32_t* status, int16_t* coef,
+                       size_t coef_bytes, int32_t* passes, void* stream);
+
 /* ---- evaluation metrics on the path's outputs ---------------------------------- */
 
 /* eval_single (spec/utils/compute_error.py:52-86, spec/trainer.py:272-316): joints =

@@ -15,6 +15,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only render_batch       # the pictures of a 32-frame flush, per-frame loop against the batched call -> profiles/render_batch_aux.json
     python scripts/bench_aux.py --only draw               # the 2D skeletons of a 1080p frame and of a 64-frame flush, next to render_views for the same flush -> profiles/draw_skeletons_aux.json
     python scripts/bench_aux.py --only jpeg_encode        # pictures to JPEG files: device encode + download of the bytes against raw download + Pillow -> profiles/jpeg_encode_aux.json
+    python scripts/bench_aux.py --only jpeg_decode        # 64 1080p .jpg frames to the frame slab: 16 Pillow threads + upload against bytes up + device decode -> profiles/jpeg_decode_aux.json
     python scripts/bench_aux.py --only horizon_panel      # panel 0 of eight 1080p frames: Pillow on the host against specmi_draw_marks -> profiles/horizon_panel_aux.json
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
     python scripts/bench_aux.py --only eval_step          # the validation step's one launch against eval_mesh + eval_joints (means only) -> profiles/eval_step_aux.json
@@ -777,9 +778,64 @@ def eval_step_section(eng, a):
     return row
 
 
+def jpeg_decode_section(eng, a):
+    """64 frames of 1080p, natural-like content (low-frequency structure plus mild noise), at quality 75 and 95, from files on disk to
+    the frame slab on the device: 16 Pillow threads + pack + one upload against read bytes + one upload + one specmi_jpeg_decode
+    (preprocess.decode_frames).  Wall clock, 3 alternated rounds after one warm-up of each; the slabs are compared."""
+    import tempfile
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    from spec_amd import preprocess
+    dev = eng.device
+    rng = np.random.default_rng(0)
+    yy, xx = np.mgrid[0:1080, 0:1920]
+    noise = [rng.normal(0, 5, (1080, 1920, 3)) for _ in range(4)]
+    rows, imgs = {}, []
+    for i in range(64):
+        base = np.stack([128 + 80 * np.sin(yy / (60.0 + 7 * c + i) + i) * np.cos(xx / (90.0 + 11 * c) + 0.3 * i) + 30 * np.sin((xx + yy) / (17.0 + i % 5))
+                         for c in range(3)], axis=2)
+        imgs.append(np.clip(base + noise[i % 4], 0, 255).astype(np.uint8))
+    with tempfile.TemporaryDirectory() as tmp:
+        for q in (75, 95):
+            paths = [os.path.join(tmp, f'q{q}_{i:02d}.jpg') for i in range(64)]
+            for path, img in zip(paths, imgs):
+                Image.fromarray(img).save(path, quality=q)
+
+            def host_route():
+                with ThreadPoolExecutor(max_workers=16) as ex:
+                    frames = list(ex.map(preprocess._host_rgb, paths))
+                out = preprocess.pack_frames(frames, dev)
+                torch.cuda.synchronize()
+                return out
+
+            def device_route():
+                out = preprocess.decode_frames(paths, dev, True)
+                torch.cuda.synchronize()
+                return out
+
+            want, got = host_route(), device_route()          # warm-up, and the comparison
+            same = bool(torch.equal(want[0], got[0])) and want[2] == got[2]
+            ms = {'host': [], 'device': []}
+            for _ in range(3):
+                for name, fn in (('host', host_route), ('device', device_route)):
+                    t0 = time.perf_counter()
+                    fn()
+                    ms[name].append((time.perf_counter() - t0) * 1e3)
+            spread = max(ms['host']) - min(ms['host'])
+            rows[f'q{q}'] = {'frames': 64, 'size': [1080, 1920], 'file_MB': round(sum(os.path.getsize(p) for p in paths) / 1e6, 2),
+                             'host_16_threads_ms': [round(v, 1) for v in ms['host']], 'device_ms': [round(v, 1) for v in ms['device']],
+                             'host_spread_ms': round(spread, 1), 'passes': eng.jpeg_decode_passes, 'identical_slabs': same,
+                             'device_ahead_beyond_host_spread': bool(min(ms['host']) - max(ms['device']) > spread)}
+    rows['default_on_rule'] = 'engine.JPEG_DECODE_DEVICE_DEFAULT becomes True only when device_ahead_beyond_host_spread holds at both qualities'
+    rows['rule_met'] = bool(rows['q75']['device_ahead_beyond_host_spread'] and rows['q95']['device_ahead_beyond_host_spread'])
+    print(json.dumps(rows, indent=1))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'horizon_panel'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'jpeg_decode', 'horizon_panel'], default=None, help='run one section only')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -872,6 +928,15 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'routes: wall clock with the copies, 3 alternated rounds, ms per '
                        'picture; kernels: per-launch HIP events (library profiler)', 'jpeg_encode': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'jpeg_decode':
+        from spec_amd import _lib
+        rows = jpeg_decode_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'timing': 'wall clock from the files on disk to the frame slab on the device, one warm-up then 3 alternated rounds, ms per '
+                       '64-frame batch', 'jpeg_decode': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     if a.only == 'horizon_panel':

@@ -47,6 +47,10 @@ def main():
     ap.add_argument('--write-tree', type=str, default=None, metavar='OUT', help='with --panoramas: also write the views as a pano_scalenet tree')
     ap.add_argument('--device-jpeg', action='store_true', help="with --write-tree: encode a panorama's views on the device in one call and "
                     "download only the files' bytes (the same bytes as Pillow's; default: engine.JPEG_DEVICE_DEFAULT)")
+    ap.add_argument('--device-decode', dest='device_decode', action='store_true', default=None,
+                    help="send the frames' .jpg files up as bytes and decode them on the device instead of with Pillow on the host (the same "
+                    "pixels; default: engine.JPEG_DECODE_DEVICE_DEFAULT)")
+    ap.add_argument('--host-decode', dest='device_decode', action='store_false', help='decode every frame with Pillow on the host')
     ap.add_argument('--save-images', dest='save_images', action='store_true', default=None,
                     help='write the validation pictures (default: TRAINING.SAVE_IMAGES of the config)')
     ap.add_argument('--no-save-images', dest='save_images', action='store_false')
@@ -71,7 +75,7 @@ def main():
             panorama.write_tree(dataset, args.write_tree, while_evaluating=True,      # every view is generated once
                                 jpeg_device=True if args.device_jpeg else None)
     res = ce.run_evaluation(hp, data_root=root, ckpt=args.ckpt, dataset=dataset, save_images=args.save_images, image_dir=args.image_dir,
-                            jpeg_device=True if args.device_jpeg else None)
+                            jpeg_device=True if args.device_jpeg else None, jpeg_decode_device=args.device_decode)
     if args.report:
         rep = {k: (v.tolist() if hasattr(v, 'tolist') else v) for k, v in res.items() if k != 'logits'}
         with open(args.report, 'w') as f:

@@ -87,6 +87,12 @@ def main():
                     'TESTING.SAVE_IMAGES and TRAINING.SAVE_IMAGES (the reference writes the files only with both)')
     ap.add_argument('--device-jpeg', action='store_true', help='with --save-images: encode .jpg / .jpeg pictures on the device and download '
                     "only the files' bytes (the same bytes as Pillow's; default: engine.JPEG_DEVICE_DEFAULT)")
+    ap.add_argument('--ragged-crops', action='store_true', help="a batch's images in one slab, one upload and one crop launch instead of one of "
+                    'each per sample (the same crops; default: engine.RAGGED_CROPS_DEFAULT).  The device decode below is part of this route only')
+    ap.add_argument('--device-decode', dest='device_decode', action='store_true', default=None,
+                    help="with --ragged-crops: send a batch's .jpg files up as bytes and decode them on the device instead of with Pillow on "
+                    "the host (the same pixels; default: engine.JPEG_DECODE_DEVICE_DEFAULT)")
+    ap.add_argument('--host-decode', dest='device_decode', action='store_false', help='with --ragged-crops: decode every frame with Pillow on the host')
     ap.add_argument('--device-panel0', action='store_true', help='with --save-images: draw the horizon line and caption of panel 0 on the '
                     "device instead of with Pillow on the host (the same bytes; default: engine.PANEL0_DEVICE_DEFAULT)")
     ap.add_argument('--report', type=str, default=None, metavar='eval.json',
@@ -100,6 +106,12 @@ def main():
     if args.device_panel0:
         from spec_amd import engine
         engine.PANEL0_DEVICE_DEFAULT = True
+    if args.ragged_crops:
+        from spec_amd import engine
+        engine.RAGGED_CROPS_DEFAULT = True
+    if args.device_decode is not None:
+        from spec_amd import engine
+        engine.JPEG_DECODE_DEVICE_DEFAULT = args.device_decode
     if args.synthetic:
         return synthetic(args)
     from spec_amd import evaluation

@@ -38,6 +38,9 @@ MARK_STRIP, MARK_MASK, MARK_LINE, MARK_REC = 0, 1, 2, 8         # SPECMI_MARK_* 
 # the limits of specmi_draw_marks: frame side, line width, line end point, mask side, mask position (include/specmi.h)
 MARK_MAX_SIDE, MARK_MIN_WIDTH, MARK_MAX_WIDTH, MARK_MAX_COORD, MARK_MAX_MASK_SIDE, MARK_MAX_MASK_POS = 8192, 2, 64, 100000, 8192, 16383
 JPEG_HEADER_BYTES = 623                       # what specmi_jpeg_header writes; the least capacity of specmi_jpeg_encode (include/specmi.h)
+# SPECMI_JPEG_* (include/specmi.h): what specmi_jpeg_probe answers, by value
+JPEG_REASONS = ('supported', 'not_jpeg', 'truncated', 'progressive', 'sof', 'precision', 'components', 'sampling', 'restart', 'scan',
+                'colourspace', 'tables', 'size', 'trailing')
 HMR_LOSS, HMR_CAM_LOSS = 0, 1                 # SPECMI_HMR_LOSS / SPECMI_HMR_CAM_LOSS (include/specmi.h)
 # the ground-truth tensors of specmi_hmr_loss in the order of its prototype, per-image shapes (None = (V, 3)); int32 where named has_*
 HMR_LOSS_GT = (('pose', (72,)), ('betas', (10,)), ('pose_conf', (24,)), ('pose_3d', (24, 4)), ('keypoints', (49, 3)), ('vertices', None),
@@ -212,6 +215,11 @@ PROTOTYPES = {
     'specmi_jpeg_encode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_int32_p, c_int64_p, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p]),
     'specmi_jpeg_header': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    # (file, bytes, reason, H, W, sampling)
+    'specmi_jpeg_probe': (C.c_int, [C.c_void_p, C.c_size_t, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
+    # (h, files_host, in_slab, in_bytes, file_ranges, out_slab, out_bytes, out_offsets, n, status, coef, coef_bytes, passes, stream)
+    'specmi_jpeg_decode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, C.c_void_p, C.c_size_t, c_int64_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_size_t, c_int32_p, C.c_void_p]),
     'specmi_camcalib_eval': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

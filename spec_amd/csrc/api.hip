@@ -809,6 +809,8 @@ int specmi_destroy(specmi_handle* h) {
     if (h->marks_tab) (void)hipFree(h->marks_tab);
     if (h->jpeg_tab) (void)hipFree(h->jpeg_tab);
     if (h->jpeg_ws) (void)hipFree(h->jpeg_ws);
+    if (h->jdec_tab) (void)hipFree(h->jdec_tab);
+    if (h->jdec_ws) (void)hipFree(h->jdec_ws);
     hrnet_free(h->hrnet);
     delete h;
     return SPECMI_OK;
@@ -2204,6 +2206,105 @@ int specmi_jpeg_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_
     a.n = n; a.mcus = (int)mcus; a.mchunks = (int)mchunks; a.bchunks = (int)bchunks;
     LaunchCtx ctx{s, &h->prof, "jpeg.encode"};
     LAUNCHCHK(h, launch_jpeg_encode(a, px * 3, ctx), "jpeg_encode");
+    return SPECMI_OK;
+}
+
+int specmi_jpeg_probe(const uint8_t* file, size_t bytes, int32_t* reason, int32_t* H, int32_t* W, int32_t* sampling) {
+    if (!file || !reason || !H || !W || !sampling) return SPECMI_ERR_ARG;
+    JdecFile f;
+    *reason = jpeg_probe(file, bytes, &f);
+    *H = f.H; *W = f.W;
+    *sampling = *reason != JDEC_SUPPORTED ? 0 : (f.s420 ? 420 : 444);
+    return SPECMI_OK;
+}
+
+int specmi_jpeg_decode(specmi_handle* h, const uint8_t* files_host, const uint8_t* in_slab, size_t in_slab_bytes, const int64_t* file_ranges,
+                       uint8_t* out_slab, size_t out_slab_bytes, const int64_t* out_offsets, int n, int32_t* status, int16_t* coef,
+                       size_t coef_bytes, int32_t* passes, void* stream) {
+    ENTER(h);
+    if (!files_host || !in_slab || !file_ranges || !out_slab || !out_offsets || !status) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (n <= 0 || n > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 files per call, got %d", n);
+    if ((const uint8_t*)out_slab < in_slab + in_slab_bytes && in_slab < (const uint8_t*)out_slab + out_slab_bytes)
+        return fail(h, SPECMI_ERR_ARG, "the file slab and the output slab overlap");
+    std::vector<int> tab((size_t)n * (sizeof(JdecFile) / 4), 0);
+    std::vector<ByteRect> rects((size_t)n);
+    long long mcus = 0, blocks = 0, plane_bytes = 0, lanes = 0, groups = 0, bchunks = 0, pchunks = 0, max_groups = 1;
+    double px = 0.0, in_bytes = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t off = file_ranges[2 * i], len = file_ranges[2 * i + 1], out_off = out_offsets[2 * i], pitch = out_offsets[2 * i + 1];
+        if (off < 0 || len < 0 || (double)off + (double)len > (double)in_slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "file %d: its bytes leave the slab of %zu bytes", i, in_slab_bytes);
+        JdecFile f;
+        const int reason = jpeg_probe(files_host + off, (size_t)len, &f);
+        if (reason != JDEC_SUPPORTED) return fail(h, SPECMI_ERR_ARG, "file %d is not a supported baseline JPEG file (specmi_jpeg_probe: reason %d)", i, reason);
+        if (pitch < 3LL * f.W) return fail(h, SPECMI_ERR_ARG, "file %d: a pitch of %lld bytes for rows of %d", i, (long long)pitch, 3 * f.W);
+        if (out_off < 0 || (double)out_off + (double)(f.H - 1) * (double)pitch + 3.0 * f.W > (double)out_slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "file %d: its rectangle leaves the slab of %zu bytes", i, out_slab_bytes);
+        const long long m = (long long)f.mx * f.my;
+        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal files give equal records
+        f.scan_off += off; f.out_off = out_off; f.pitch = f.H > 1 ? pitch : 3LL * f.W;
+        f.block0 = blocks; f.plane0 = plane_bytes;
+        f.nblocks = (int)(m * f.bpm);
+        const long long nsub = std::max<long long>(1, (f.scan_len + kJdecSubBytes - 1) / kJdecSubBytes);
+        const long long g = (nsub + kJdecGroup - 1) / kJdecGroup;
+        mcus += m;
+        if (mcus > kJdecMaxMcus || lanes + g * kJdecGroup > (1LL << 30))
+            return fail(h, SPECMI_ERR_ARG, "the files hold more than 2^24 MCUs or 2^37 scan bytes");
+        f.nsub = (int)nsub; f.lane0 = (int)lanes; f.group0 = (int)groups; f.bchunk0 = (int)bchunks; f.pchunk0 = (int)pchunks;
+        blocks += m * f.bpm;
+        plane_bytes += m * (f.s420 ? 384 : 192);
+        lanes += g * kJdecGroup;
+        groups += g;
+        max_groups = std::max(max_groups, g);
+        bchunks += (m * f.bpm + 255) / 256;
+        pchunks += ((long long)f.H * f.W + 255) / 256;
+        px += (double)f.H * f.W;
+        in_bytes += (double)f.scan_len;
+        std::memcpy(tab.data() + (size_t)i * (sizeof(JdecFile) / 4), &f, sizeof(f));
+        rects[i] = ByteRect{out_off, f.pitch, 3LL * f.W, f.H};
+    }
+    {   // no two rectangles share a byte: sorted by first byte, one is compared with those that start before it ends
+        std::vector<int> order((size_t)n);
+        for (int i = 0; i < n; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](int x, int y) { return rects[x].off < rects[y].off; });
+        for (int i = 0; i < n; ++i)
+            for (int j = i + 1; j < n && rects[order[j]].off < rects[order[i]].end(); ++j)
+                if (rects_overlap(rects[order[i]], rects[order[j]]))
+                    return fail(h, SPECMI_ERR_ARG, "the output rectangles of files %d and %d share a byte", order[i], order[j]);
+    }
+    if (coef && coef_bytes < (size_t)blocks * 128)
+        return fail(h, SPECMI_ERR_ARG, "the coefficient output holds %zu bytes, these files have %lld", coef_bytes, blocks * 128);
+    hipStream_t s = (hipStream_t)stream;
+    {   // the passes are counted on the host and the table is rewritten: neither is possible under capture; ask first and leave it valid
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone)
+            return fail(h, SPECMI_ERR_STATE, "specmi_jpeg_decode is not possible while the stream is being captured (nothing was enqueued)");
+    }
+    size_t woff[8];
+    const size_t need = jdec_ws_layout(blocks, plane_bytes, lanes, groups, woff);
+    const bool regrown = tab.size() * 4 > h->jdec_tab_bytes;
+    int rc;
+    if ((rc = grow_ragged(h, &h->jdec_ws, &h->jdec_ws_bytes, need, "the JPEG decoder workspace"))) return rc;
+    if ((rc = grow_ragged(h, (void**)&h->jdec_tab, &h->jdec_tab_bytes, tab.size() * 4, "the JPEG file table"))) return rc;
+    if (regrown || tab != h->jdec_host) {
+        // a decode enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
+        if (!regrown && (rc = sync_for_growth(h, "the JPEG file table"))) return rc;
+        h->jdec_host.swap(tab);
+        HIPCHK(h, hipMemcpyAsync(h->jdec_tab, h->jdec_host.data(), h->jdec_host.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    char* ws = (char*)h->jdec_ws;
+    JdecArgs a{};
+    a.in = in_slab; a.out = out_slab; a.files = (const JdecFile*)h->jdec_tab; a.status = status;
+    a.coef = (short*)(ws + woff[0]); a.planes = (unsigned char*)(ws + woff[1]); a.entry = (unsigned*)(ws + woff[2]);
+    a.exits = (unsigned*)(ws + woff[3]); a.count = (int*)(ws + woff[4]); a.first = (int*)(ws + woff[5]); a.gexit = (unsigned*)(ws + woff[6]);
+    a.changed = (unsigned*)(ws + woff[7]);
+    a.n = n; a.groups = (int)groups; a.bchunks = (int)bchunks; a.pchunks = (int)pchunks;
+    LaunchCtx ctx{s, &h->prof, "jpeg.decode"};
+    int npass = 0;
+    LAUNCHCHK(h, launch_jpeg_decode(a, blocks, lanes, (int)max_groups, in_bytes, px * 3, &npass, ctx), "jpeg_decode");
+    if (passes) *passes = npass;
+    if (coef) HIPCHK(h, hipMemcpyAsync(coef, a.coef, (size_t)blocks * 128, hipMemcpyDeviceToDevice, s));
     return SPECMI_OK;
 }
 

@@ -194,6 +194,13 @@ struct specmi_handle {
     std::vector<int> jpeg_host;         // host image of jpeg_tab as last uploaded
     void* jpeg_ws = nullptr;
     size_t jpeg_ws_bytes = 0;
+    // specmi_jpeg_decode: the file records with their tables, same growth and upload rules as ragged_tab; coefficients, planes and
+    // the lanes' states (jdec_ws_layout), grows like ragged_tmp
+    int* jdec_tab = nullptr;
+    size_t jdec_tab_bytes = 0;
+    std::vector<int> jdec_host;         // host image of jdec_tab as last uploaded
+    void* jdec_ws = nullptr;
+    size_t jdec_ws_bytes = 0;
     SkWs sk;                            // split-K partial tiles + arrival counters (ensure_sk; never allocated under graph capture:
                                         // the warm-up call of a shape sizes it)
     std::vector<void*> sk_retired;      // outgrown split-K buffers, kept until destroy (captured graphs may still name them)

@@ -640,4 +640,56 @@ void jpeg_build_tables(int quality, JpegTables* t);
 size_t jpeg_ws_layout(int n, long long mcus, long long mchunks, long long bchunks, size_t off[8]);
 int launch_jpeg_encode(const JpegArgs& a, double in_bytes, const LaunchCtx& ctx);
 
+// ----------------------------------------------------------------------------------------
+// baseline JPEG decoder  (jpeg_dec.hip)
+// ----------------------------------------------------------------------------------------
+constexpr int kJdecSubBytes = 128;        // a subsequence: 1024 scan bits = 128 bytes of the file, one lane
+constexpr int kJdecGroup = 256;           // subsequences per workgroup of the sync and write kernels
+constexpr long long kJdecMaxMcus = 1 << 24;
+// One Huffman table as the lanes read it: by the next 8 bits `length << 8 | symbol` (0: the code is longer), and for the
+// lengths 9 .. 16 the largest code (-1: none) and what added to a code gives its place in vals
+struct JdecHuff {
+    unsigned short lut[256];
+    int maxcode[18], valoff[18];
+    unsigned char vals[256];
+};
+// One file of a specmi_jpeg_decode call as the device reads it.  Table slots: dc[0..1], ac[0..1]; q per component, natural order
+struct JdecFile {
+    long long scan_off, scan_len;         // the scan's first byte in the input slab and its length (the EOI excluded)
+    long long out_off, pitch;
+    long long block0, plane0;             // the file's first block in the coefficient workspace, first byte in the plane workspace
+    int H, W, mx, my;
+    int s420, bpm, nblocks, nsub;         // 4:2:0 or 4:4:4; blocks per MCU (6 or 3); blocks; subsequences
+    int lane0, group0, bchunk0, pchunk0;  // where its lanes (a multiple of kJdecGroup), groups, 256-block and 256-pixel chunks begin
+    unsigned char tdc[4], tac[4];         // table slot per component
+    unsigned short q[3][64];
+    JdecHuff huff[4];
+};
+static_assert(sizeof(JdecFile) % 8 == 0, "records follow each other in a table of ints");
+struct JdecArgs {
+    const unsigned char* in;
+    unsigned char* out;
+    const JdecFile* files;
+    int* status;                          // (n) one word per file, zeroed per call, bits joined with atomicOr
+    short* coef;                          // (blocks, 64) quantised coefficients in natural order, zeroed per call
+    unsigned char* planes;                // per file Y, Cb, Cr in whole MCUs
+    unsigned* entry;                      // (lanes) the entry state a lane last decoded from
+    unsigned* exits;                      // (lanes) its exit state
+    int* count;                           // (lanes) blocks it completed
+    int* first;                           // (lanes) blocks of its file completed before it
+    unsigned* gexit;                      // (2, groups) every group's last exit as the previous pass left it / as this pass leaves it
+    unsigned* changed;                    // one word per call: did the pass change a lane
+    int n, groups, bchunks, pchunks;
+};
+enum { JDEC_SUPPORTED = 0, JDEC_NOT_JPEG, JDEC_TRUNCATED, JDEC_PROGRESSIVE, JDEC_SOF, JDEC_PRECISION, JDEC_COMPONENTS, JDEC_SAMPLING,
+       JDEC_RESTART, JDEC_SCAN, JDEC_COLOURSPACE, JDEC_TABLES, JDEC_SIZE, JDEC_TRAILING };
+// rule 1 on the host: -> a JDEC_ reason; on JDEC_SUPPORTED f holds H, W, s420, the scan's range within the file (scan_off,
+// scan_len), the quantisers, the tables and their selectors
+int jpeg_probe(const unsigned char* d, size_t n, JdecFile* f);
+// byte offsets of coef, planes, entry, [exits, count, first, gexit, changed] in the workspace -> its size
+size_t jdec_ws_layout(long long blocks, long long plane_bytes, long long lanes, long long groups, size_t off[8]);
+// the whole sequence; max_groups: the groups of the file that has most; -> passes run
+int launch_jpeg_decode(const JdecArgs& a, long long blocks, long long lanes, int max_groups, double in_bytes, double out_bytes, int* passes,
+                       const LaunchCtx& ctx);
+
 }  // namespace specmi

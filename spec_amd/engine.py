@@ -387,6 +387,74 @@ def check_jpeg_encode(geom, offsets, in_bytes, out_bytes, quality, in_ptr=None, 
     return geom.astype(np.int32), offsets
 
 
+# Which route the .jpg / .jpeg frames the flows READ take (preprocess.decode_frames): False = Pillow decodes every file on the host
+# and the raw frames go up (today's path, bit for bit), True = the files' bytes go up and specmi_jpeg_decode decodes the supported
+# ones where they land.  Same pixels either way on a libjpeg-turbo Pillow.  The rule: True only when
+# scripts/bench_aux.py --only jpeg_decode shows the device route ahead of 16 host threads at both qualities by more than the host
+# route's own spread between rounds - and it is, on 64 frames of 1080p: 7.1 - 9.5 against 155.2 - 213.2 ms at quality 75 (spread
+# 58.0), 31.9 - 37.3 against 162.1 - 185.7 ms at quality 95 (spread 23.6), identical slabs (profiles/jpeg_decode_aux.json).
+JPEG_DECODE_DEVICE_DEFAULT = True
+
+
+def flow_jpeg_decode_device(jpeg_decode_device=None) -> bool:
+    """``jpeg_decode_device`` (the flow's private switch) decides, None = the default."""
+    return JPEG_DECODE_DEVICE_DEFAULT if jpeg_decode_device is None else bool(jpeg_decode_device)
+
+
+def jpeg_probe(data):
+    """``specmi_jpeg_probe`` on a file's ``bytes`` -> (reason, H, W, sampling): reason is a name of ``_lib.JPEG_REASONS``
+    ('supported' or why ``specmi_jpeg_decode`` refuses the file), sampling 420 or 444.  Host only: needs no device."""
+    data = bytes(data)
+    out = (C.c_int32 * 4)()
+    p = [C.cast(C.byref(out, 4 * i), _lib.c_int32_p) for i in range(4)]
+    rc = _lib.load().specmi_jpeg_probe(data, len(data), *p)
+    if rc != _lib.OK:
+        raise ValueError('specmi_jpeg_probe refused its arguments')
+    return _lib.JPEG_REASONS[out[0]], int(out[1]), int(out[2]), int(out[3])
+
+
+def check_jpeg_decode(ranges, geom, outs, in_bytes, out_bytes, in_ptr=None, out_ptr=None):
+    """Every refusal of ``specmi_jpeg_decode`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``ranges`` (n, 2)
+    [offset, length] of the files in the input slab, ``geom`` (n, 3) [H, W, sampling (420 or 444)] as the probe gave them, ``outs`` (n, 2) [offset, pitch]
+    of the pictures in the output slab, the sizes of the two slabs and - where known - their addresses (None for either: a
+    missing slab).  -> ranges and outs as the library reads them (int64).  Needs no device."""
+    ranges, geom, outs = (np.ascontiguousarray(x, dtype=np.int64) for x in (ranges, geom, outs))
+    n = ranges.shape[0] if ranges.ndim == 2 else -1
+    if ranges.ndim != 2 or ranges.shape[1] != 2 or tuple(geom.shape) != (n, 3) or tuple(outs.shape) != (n, 2):
+        raise ValueError('files: ranges (n, 2), geom (n, 3) and outs (n, 2) with one row per file')
+    if not 1 <= n <= 65535:
+        raise ValueError(f'1 to 65535 files per call, got {n}')
+    if in_bytes is None or out_bytes is None or in_ptr == 0 or out_ptr == 0:
+        raise ValueError('the file slab or the output slab is missing (a null pointer)')
+    if in_ptr is not None and out_ptr is not None and out_ptr < in_ptr + in_bytes and in_ptr < out_ptr + out_bytes:
+        raise ValueError('the file slab and the output slab overlap')
+    off, length = ranges.T
+    H, W, sampling = geom.T
+    out_off, pitch = outs.T
+    if (off < 0).any() or (length < 0).any() or (off + length > in_bytes).any():
+        raise ValueError(f'a file leaves the slab of {in_bytes} bytes')
+    if ((H < 1) | (H > 32768) | (W < 1) | (W > 32768)).any() or not np.isin(sampling, (420, 444)).all():
+        raise ValueError('a picture of 1 .. 32768 pixels per side, sampled 420 or 444 (a file the probe refuses?)')
+    if (pitch < 3 * W).any():
+        raise ValueError('a pitch below 3 * W bytes')
+    if (out_off < 0).any() or (out_off + (H - 1) * pitch + 3 * W > out_bytes).any():
+        raise ValueError(f'a picture rectangle leaves the slab of {out_bytes} bytes')
+    mcu = np.where(sampling == 420, 16, 8)
+    if int((-(-H // mcu) * -(-W // mcu)).sum()) > 1 << 24:
+        raise ValueError('the files hold more than 2^24 MCUs')
+    end = out_off + (H - 1) * pitch + 3 * W
+    order = np.argsort(out_off, kind='stable')
+    for k, i in enumerate(order):                                # rectangles with gaps: a byte test per pair that may meet
+        for j in order[k + 1:]:
+            if out_off[j] >= end[i]:
+                break
+            rows_i = out_off[i] + pitch[i] * np.arange(H[i])
+            rows_j = out_off[j] + pitch[j] * np.arange(H[j])
+            if ((rows_i[:, None] < rows_j[None, :] + 3 * W[j]) & (rows_j[None, :] < rows_i[:, None] + 3 * W[i])).any():
+                raise ValueError('two picture rectangles share a byte')
+    return ranges, outs
+
+
 EVAL_STEP_OUTPUTS = ('err_sel', 'pa_err_sel', 'err_k', 'pa_err_k', 'v2v')
 EVAL_STEP_MAX_JOINTS = 32      # kMaxJ of spec_amd/csrc/eval.hip: the joints are held on chip
 
@@ -1088,6 +1156,60 @@ class Engine:
             cap[todo] = sizes
             todo = todo[~fits]
         return files
+
+    def jpeg_decode_into(self, host, slab, ranges, geom, out_slab, outs, status=None, coef=None):
+        """``specmi_jpeg_decode``: the files at ``ranges`` (n, 2) [offset, length] of ``slab`` (1-D uint8 on the engine device)
+        and of ``host`` (the same bytes on the host: a 1-D uint8 array; only the sizes are compared, that the bytes agree is the caller's
+        contract), of ``geom`` (n, 3) [H, W, sampling] as ``jpeg_probe``
+        gave them, decoded into the rectangles ``outs`` (n, 2) [offset, pitch] of ``out_slab`` (1-D uint8, same device, not
+        overlapping).  -> (``status`` (n,) int32 on the device, given or new: 0 where the file's pixels are Pillow's; passes of
+        the sync stage).  ``coef``: an int16 device tensor that receives the coefficients.  Synchronises the stream between
+        passes; everything the arrays decide is checked before the library is called (``check_jpeg_decode``)."""
+        d = self.device
+        for name, x in (('slab', slab), ('out_slab', out_slab)):
+            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
+                raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
+        host = np.ascontiguousarray(host, dtype=np.uint8).reshape(-1)
+        if host.size != slab.numel():
+            raise ValueError('host and slab hold the same bytes: their sizes differ')
+        ranges, outs = check_jpeg_decode(ranges, geom, outs, slab.numel(), out_slab.numel(), slab.data_ptr(), out_slab.data_ptr())
+        n = int(ranges.shape[0])
+        if status is None:
+            status = torch.empty(n, device=d, dtype=torch.int32)
+        elif not isinstance(status, torch.Tensor) or status.device != d or status.dtype != torch.int32 or tuple(status.shape) != (n,) or not status.is_contiguous():
+            raise ValueError('status must be a contiguous (n,) int32 tensor on the engine device')
+        if coef is not None and (not isinstance(coef, torch.Tensor) or coef.device != d or coef.dtype != torch.int16 or not coef.is_contiguous()):
+            raise ValueError('coef must be a contiguous int16 tensor on the engine device')
+        passes = C.c_int32(0)
+        _lib.check(self.h, self.lib.specmi_jpeg_decode(
+            self.h, host.ctypes.data_as(C.c_void_p), _ptr(slab), slab.numel(), ranges.ctypes.data_as(_lib.c_int64_p), _ptr(out_slab),
+            out_slab.numel(), outs.ctypes.data_as(_lib.c_int64_p), n, _ptr(status), _ptr(coef), 0 if coef is None else 2 * coef.numel(),
+            C.byref(passes), self._stream()))
+        self.jpeg_decode_passes = int(passes.value)           # of the last call: what scripts/bench_aux.py records
+        return status, self.jpeg_decode_passes
+
+    def jpeg_decode(self, files):
+        """``files``: a list of ``bytes``, every one a file ``jpeg_probe`` calls supported -> (slab, offsets, sizes, status): the
+        pictures back to back in one 1-D uint8 device slab with their (n,) int64 byte offsets and [(H, W)] - the triple
+        ``preprocess.pack_frames`` builds from Pillow's decodes of the same files, bit for bit where ``status`` (n,) int32 on the
+        device is 0 (include/specmi.h states the contract).  One upload of the files' bytes, one ``specmi_jpeg_decode``."""
+        files = [bytes(f) for f in files]
+        if not files:
+            raise ValueError('at least one file')
+        probes = [jpeg_probe(f) for f in files]
+        for i, p in enumerate(probes):
+            if p[0] != 'supported':
+                raise ValueError(f'file {i} is not a supported baseline JPEG file ({p[0]})')
+        length = np.array([len(f) for f in files], np.int64)
+        ranges = np.stack([np.concatenate([[0], np.cumsum(length)[:-1]]), length], axis=1)
+        host = np.frombuffer(b''.join(files), np.uint8)
+        geom = np.array([p[1:] for p in probes], np.int64)
+        size = 3 * geom[:, 0] * geom[:, 1]
+        offsets = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64)
+        slab = torch.from_numpy(host.copy()).to(self.device)
+        out_slab = torch.empty(int(size.sum()), device=self.device, dtype=torch.uint8)
+        status, _ = self.jpeg_decode_into(host, slab, ranges, geom, out_slab, np.stack([offsets, 3 * geom[:, 1]], axis=1))
+        return out_slab, offsets, [(int(h), int(w)) for h, w, _ in geom], status
 
     def _cam_args(self, B, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h):
         d = self.device

@@ -28,7 +28,7 @@ from . import assets, io_formats, metrics
 from .cam_utils import cam_params_from_angles
 from .checkpoint import load_pretrained_model, read_checkpoint
 from .engine import flow_image_dtype, flow_ragged_crops
-from .preprocess import dataset_crops, dataset_crops_ragged, pack_frames
+from .preprocess import dataset_crops, dataset_crops_ragged, decode_frames, pack_frames
 
 # spec/config.py:34-56
 DATASET_FOLDERS = {'spec-mtp': 'data/dataset_folders/spec-mtp', 'spec-syn': 'data/dataset_folders/spec-syn',
@@ -98,6 +98,7 @@ class EvalDataset:
         self.data = dict(np.load(dataset_file or os.path.join(data_root, DATASET_FILES[name])))
         self.imgname = self.data['imgname']
         self.n = len(self.imgname)
+        self._jpeg_decode_device = None     # True: the batch's .jpg files go up as bytes and are decoded on the device (preprocess.decode_frames; same bits); None = engine.JPEG_DECODE_DEVICE_DEFAULT
         self._ragged_crops = None     # True: one slab, one upload, one ragged crop launch per batch; False: one of each per sample (same bits)
 
     def __len__(self):
@@ -145,7 +146,7 @@ class EvalDataset:
         d = self.data
         paths = [os.path.join(self.img_dir, str(self.imgname[i])) for i in idx]
         if flow_ragged_crops(self._ragged_crops):     # the batch's images in one slab, one upload, one launch into the batch tensor
-            slab, offsets, shapes = pack_frames([read_image_rgb(p) for p in paths], device)
+            slab, offsets, shapes = decode_frames(paths, device, self._jpeg_decode_device)     # off: pack_frames of read_image_rgb's decodes
             img = dataset_crops_ragged(slab, offsets, shapes, np.arange(len(paths), dtype=np.int32), d['center'][idx], d['scale'][idx],
                                        img_res, dtype=dtype)                                                    # cam_dataset.py:367-377
         else:

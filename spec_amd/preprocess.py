@@ -134,6 +134,70 @@ def pack_frames(frames, device=None):
     return slab, np.asarray(offsets, dtype=np.int64), sizes
 
 
+def _host_rgb(item):
+    """A frame on the host route: a path or a file's ``bytes`` -> Pillow's (H,W,3) uint8 RGB, what ``tester._read_rgb`` and
+    ``evaluation.read_image_rgb`` return; an array passes."""
+    import io
+    import numpy as np
+    from PIL import Image
+    if isinstance(item, np.ndarray):
+        return item
+    with Image.open(io.BytesIO(item) if isinstance(item, (bytes, bytearray)) else item) as im:
+        return np.array(im.convert('RGB'))
+
+
+def decode_frames(paths, device, jpeg_decode_device=None):
+    """The frames of a batch from their files -> the triple ``pack_frames([Pillow's decode of each], device)`` returns, bit for
+    bit.  ``paths``: per frame a path, a file's ``bytes`` already read, or a decoded (H,W,3) uint8 array.  ``jpeg_decode_device``
+    (None = ``engine.JPEG_DECODE_DEVICE_DEFAULT``): False is exactly that host path; True sends the baseline .jpg / .jpeg files
+    ``engine.jpeg_probe`` calls supported up as BYTES in one copy and decodes them in one ``specmi_jpeg_decode`` into their
+    places of the slab.  Every other frame - a .png, a file the probe refuses, a file whose status came back non-zero, an array -
+    is decoded by Pillow as before and uploaded into its place of the same slab (a damaged file raises there what it raises
+    today)."""
+    import numpy as np
+    from .engine import flow_jpeg_decode_device, is_jpeg_name, jpeg_probe
+    items = list(paths)
+    if not items:
+        raise ValueError('at least one frame')
+    if not flow_jpeg_decode_device(jpeg_decode_device):
+        return pack_frames([_host_rgb(p) for p in items], device)
+    dev = torch.device(device)
+    eng = _engine(dev)
+    files, sizes, host = {}, [None] * len(items), {}
+    for i, p in enumerate(items):
+        if isinstance(p, (bytes, bytearray)) or (not isinstance(p, np.ndarray) and is_jpeg_name(p)):
+            if not isinstance(p, (bytes, bytearray)):
+                with open(p, 'rb') as f:
+                    p = f.read()
+            probe = jpeg_probe(p)
+            if probe[0] == 'supported':
+                files[i], sizes[i] = (bytes(p), probe), (probe[1], probe[2])
+                continue
+        host[i] = _host_rgb(p)
+        if host[i].dtype != np.uint8 or host[i].ndim != 3 or host[i].shape[2] != 3:
+            raise ValueError('frames must be (H,W,3) uint8 RGB')
+        sizes[i] = (int(host[i].shape[0]), int(host[i].shape[1]))
+    nbytes = np.array([3 * h * w for h, w in sizes], np.int64)
+    offsets = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
+    slab = torch.empty(int(nbytes.sum()), device=eng.device, dtype=torch.uint8)
+    if files:
+        order = sorted(files)
+        length = np.array([len(files[i][0]) for i in order], np.int64)
+        ranges = np.stack([np.concatenate([[0], np.cumsum(length)[:-1]]), length], axis=1)
+        blob = np.frombuffer(b''.join(files[i][0] for i in order), np.uint8)
+        geom = np.array([files[i][1][1:] for i in order], np.int64)
+        status, _ = eng.jpeg_decode_into(blob, torch.from_numpy(blob.copy()).to(eng.device), ranges, geom, slab,
+                                         np.stack([offsets[order], 3 * geom[:, 1]], axis=1))
+        for i, st in zip(order, status.cpu().tolist()):
+            if st:                                            # a scan that does not satisfy T.81: the host route decides
+                host[i] = _host_rgb(files[i][0])
+                if tuple(host[i].shape) != sizes[i] + (3,):
+                    raise ValueError('a damaged file decodes to another size on the host')
+    for i, fr in host.items():
+        slab[int(offsets[i]):int(offsets[i] + nbytes[i])].copy_(torch.from_numpy(np.ascontiguousarray(fr)).reshape(-1))
+    return slab, offsets, [(int(h), int(w)) for h, w in sizes]
+
+
 def _ragged_args(name, slab, offsets, sizes, frame_index, n):
     """The frame side of the ragged crop ``name``, checked in this order: the host tables (one offset and one (H, W) per
     frame), ``frame_index`` against the number of frames while it is still on the host - ``crop_detections_batch``'s check -,
