@@ -798,6 +798,48 @@ int specmi_jpeg_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_
  * quality outside [1, 100], H or W outside [1, 32768] or a capacity below 623. */
 int specmi_jpeg_header(int quality, int H, int W, uint8_t* out, size_t capacity);
 
+/* PNG FILES encoded on the device, all pictures of a flush in one fixed sequence of launches: the same service as
+ * specmi_jpeg_encode for the pictures of .png frames (spec/tester.py:95 accepts them and :188-201 keeps the frame's extension;
+ * camcalib/pano_preprocessing.py:354 writes a tree of them) - the file's bytes come down instead of the raw picture, and zlib
+ * does not run on a host thread.  Every convention is specmi_jpeg_encode's: the slabs (DEVICE; in_slab uint8 RGB, the output
+ * slab of specmi_render_views and what spec_amd.preprocess.pack_frames builds are valid input; out_slab must not overlap it),
+ * THE PICTURE RECORD (HOST) pic_geom (n x 2 int32: H, W) and pic_offsets (n x 4 int64: in_offset, in_pitch, out_offset,
+ * out_capacity), sizes (n int64, DEVICE); a handle of any model kind, committed or not.  There is no quality: PNG is lossless.
+ * THE CONTRACT (stated in full at the head of spec_amd/csrc/png.hip, restated in NumPy and plain Python in tests/png_ref.py):
+ * picture i's file is a valid PNG file - signature, IHDR (8 bit, colour type 2, no interlace), ONE IDAT holding one zlib stream
+ * (78 01, deflate, the Adler-32 of the filtered stream), IEND, every CRC-32 correct and computed on the device like the Adler-32 -
+ * that decodes to exactly the picture.  Its bytes are NOT zlib's or Pillow's (only the first 33 are); they are fixed by the
+ * stated rules and depend on that picture alone, not on its neighbours in the call, on grouping or on scheduling: per row the
+ * filter 0 .. 4 with the smallest sum of absolute signed bytes; the filtered stream cut into segments of 32768 bytes, each coded
+ * on its own as one dynamic-Huffman block of literals and matches at distances 1 and 3 followed by an empty stored block, or as
+ * one stored block where that is not shorter.  No file is longer than specmi_png_bound.
+ * sizes[i] ALWAYS receives the file's true length.  A picture whose length exceeds its capacity has nothing written at or beyond
+ * out_offset + out_capacity and is otherwise unspecified; the call still returns SPECMI_OK: the caller reads sizes and encodes
+ * that picture again with enough room - never needed where the capacity is specmi_png_bound.  Bytes of out_slab outside
+ * [out_offset, out_offset + sizes[i]) of the pictures that fit are not touched.
+ * One memset and five launches, whatever n and the picture sizes are.
+ * Refused (SPECMI_ERR_ARG), launching nothing: a null pointer; n outside [1, 65535]; H or W outside [1, 32768]; a pitch below
+ * 3 W; a picture rectangle that leaves in_slab; a capacity below the fixed overhead of 63 bytes (signature, the chunks' frames,
+ * zlib's header and checksum); an output range that leaves out_slab; overlapping slabs; two output ranges that share a byte; a
+ * picture whose zlib stream with every segment stored does not fit one IDAT chunk (2^31 bytes or more); more than 2^23 segments
+ * in all (256 GiB of filtered stream: a launch has a workgroup per segment).  The number of rows is not limited beyond n x H.
+ * The picture records live in a device table owned by the handle, under the rule of specmi_jpeg_encode: a call whose records
+ * differ from the previous call's rewrites the table and therefore first SYNCHRONISES THE WHOLE DEVICE, and cannot be made while
+ * a stream is being captured (SPECMI_ERR_STATE; the stream is asked first, so the capture stays valid and nothing is enqueued);
+ * a call that repeats them does neither and can be captured.  The workspace is one per handle (growth synchronises the device):
+ * the filtered streams, H (1 + 3 W) bytes per picture rounded up to 256, and 32824 bytes per segment. */
+int specmi_png_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_bytes, uint8_t* out_slab, size_t out_slab_bytes,
+                      const int32_t* pic_geom, const int64_t* pic_offsets, int n, int64_t* sizes, void* stream);
+
+/* The length no file of specmi_png_encode for an (H, W) picture exceeds, into *bytes: 63 + L + 5 ceil(L / 32768) with
+ * L = H (1 + 3 W) - signature, chunks, the zlib wrapper, and every segment stored.  Host only: needs no handle and no device.
+ * SPECMI_ERR_ARG for a null pointer or H or W outside [1, 32768]. */
+int specmi_png_bound(int H, int W, int64_t* bytes);
+
+/* The 33 bytes such a file begins with - the signature and IHDR with its CRC - into `out` (HOST, of `capacity` >= 33 bytes).
+ * Host only.  SPECMI_ERR_ARG for a null pointer, H or W outside [1, 32768] or a capacity below 33. */
+int specmi_png_header(int H, int W, uint8_t* out, size_t capacity);
+
 /* BASELINE JPEG FILES decoded on the device, all files of a call together: the read side of specmi_jpeg_encode.  Replaces the
  * host decode (PIL's Image.open(path).convert('RGB')) and the upload of the raw frames in front of every flow that reads .jpg
  * frames - the files' bytes go up instead, 10 to 20 times fewer.

@@ -15,6 +15,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only render_batch       # the pictures of a 32-frame flush, per-frame loop against the batched call -> profiles/render_batch_aux.json
     python scripts/bench_aux.py --only draw               # the 2D skeletons of a 1080p frame and of a 64-frame flush, next to render_views for the same flush -> profiles/draw_skeletons_aux.json
     python scripts/bench_aux.py --only jpeg_encode        # pictures to JPEG files: device encode + download of the bytes against raw download + Pillow -> profiles/jpeg_encode_aux.json
+    python scripts/bench_aux.py --only png_encode         # pictures to PNG files: device encode + download of the bytes against raw download + Pillow -> profiles/png_encode_aux.json
     python scripts/bench_aux.py --only jpeg_decode        # 64 1080p .jpg frames to the frame slab: 16 Pillow threads + upload against bytes up + device decode -> profiles/jpeg_decode_aux.json
     python scripts/bench_aux.py --only horizon_panel      # panel 0 of eight 1080p frames: Pillow on the host against specmi_draw_marks -> profiles/horizon_panel_aux.json
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
@@ -555,6 +556,31 @@ def draw_section(eng, a):
     return out
 
 
+def picture_frame(rng, H, W):
+    """A seeded frame: smooth fields with noise."""
+    yy, xx = np.mgrid[0:H, 0:W]
+    ph = rng.uniform(0, 6.28, (3, 4))
+    img = np.stack([127 + 60 * np.sin(xx / 97.0 + p[0]) * np.cos(yy / 71.0 + p[1]) + 40 * np.sin((xx + yy) / 23.0 + p[2]) + 20 * np.cos(yy / 9.0 + p[3])
+                    for p in ph], -1)
+    return np.clip(img + rng.normal(0, 6, img.shape), 0, 255).astype(np.uint8)
+
+
+def demo_pictures(eng, rng, v8, f, t8):
+    """Eight 1080 x 5760 three-panel pictures as ``render_image_groups`` draws them from seeded 1080p frames, two meshes each, where
+    ``render_views`` left them -> (device slab, geom, offsets (n, 2))."""
+    from spec_amd import render
+    dev = eng.device
+    F, (H, W) = 8, (1080, 1920)
+    frames = [picture_frame(rng, H, W) for _ in range(F)]
+    verts = torch.from_numpy(np.concatenate([v8[:2]] * F)).to(dev)
+    cam_t = torch.from_numpy(np.concatenate([t8[2:4]] * F)).to(dev)
+    _, slabs = render.render_image_groups(frames, verts, cam_t, [2] * F, [np.eye(3, dtype=np.float32)] * F, [(1200., 1200.)] * F, [(W / 2, H / 2)] * F,
+                                          faces=torch.from_numpy(f).to(dev), engine=eng, return_slabs=True)
+    assert len(slabs) == 1
+    slab, offs, shapes = slabs[0]
+    return slab, [tuple(sh) for sh in shapes], [(int(o), 3 * sh[1]) for o, sh in zip(offs, shapes)]
+
+
 def jpeg_section(eng, a):
     """Pictures on the device to JPEG files on the host, two routes alternated in this process (wall clock with the copies, 3
     rounds): DEVICE = ``Engine.jpeg_encode`` (``specmi_jpeg_encode``, then the sizes and the files' bytes come down), HOST = the raw
@@ -570,24 +596,11 @@ def jpeg_section(eng, a):
     v8, f, t8, _, _, _ = render_workload()
     rng = np.random.default_rng(0)
 
-    def frame(H, W):
-        yy, xx = np.mgrid[0:H, 0:W]
-        ph = rng.uniform(0, 6.28, (3, 4))
-        img = np.stack([127 + 60 * np.sin(xx / 97.0 + p[0]) * np.cos(yy / 71.0 + p[1]) + 40 * np.sin((xx + yy) / 23.0 + p[2]) + 20 * np.cos(yy / 9.0 + p[3])
-                        for p in ph], -1)
-        return np.clip(img + rng.normal(0, 6, img.shape), 0, 255).astype(np.uint8)
+    frame = lambda H, W: picture_frame(rng, H, W)
 
     def workload(name):
         if name == 'demo_pictures':
-            F, (H, W), q = 8, (1080, 1920), 75
-            frames = [frame(H, W) for _ in range(F)]
-            verts = torch.from_numpy(np.concatenate([v8[:2]] * F)).to(dev)
-            cam_t = torch.from_numpy(np.concatenate([t8[2:4]] * F)).to(dev)
-            _, slabs = render.render_image_groups(frames, verts, cam_t, [2] * F, [np.eye(3, dtype=np.float32)] * F, [(1200., 1200.)] * F, [(W / 2, H / 2)] * F,
-                                                  faces=torch.from_numpy(f).to(dev), engine=eng, return_slabs=True)
-            assert len(slabs) == 1
-            slab, offs, shapes = slabs[0]
-            return slab, [tuple(sh) for sh in shapes], [(int(o), 3 * sh[1]) for o, sh in zip(offs, shapes)], q
+            return demo_pictures(eng, rng, v8, f, t8) + (75,)
         pics = [frame(600, 800) for _ in range(12)]
         return torch.from_numpy(np.concatenate([p_.reshape(-1) for p_ in pics])).to(dev), [(600, 800)] * 12, [(k * 600 * 800 * 3, 2400) for k in range(12)], 95
 
@@ -652,6 +665,74 @@ def jpeg_section(eng, a):
         del slab, ws_out
         torch.cuda.empty_cache()
     return out
+
+
+def png_section(eng, a):
+    """Pictures on the device to PNG files on the host, two routes alternated in this process (wall clock with the copies, 3
+    rounds): DEVICE = ``Engine.png_encode`` (``specmi_png_encode``, then the sizes and the files' bytes come down), HOST = the raw
+    pictures come down and Pillow saves each as the flows do (``Image.fromarray(a).save(f, format='PNG')``: zlib on one thread at
+    Pillow's default level).  Workload: the eight 1080 x 5760 three-panel pictures of ``--only jpeg_encode``.  The files' sizes
+    next to Pillow's at compress_level 1 and 6; per kernel (library profiler, HIP events) its time."""
+    import io
+    import time
+    from PIL import Image
+    from spec_amd.engine import png_bound
+    dev = eng.device
+    v8, f, t8, _, _, _ = render_workload()
+    slab, geom, offsets = demo_pictures(eng, np.random.default_rng(0), v8, f, t8)
+    n, px = len(geom), sum(h * w for h, w in geom)
+
+    def wall(fn):
+        torch.cuda.synchronize(); t0 = time.perf_counter(); r = fn(); torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, r
+
+    def device_route():
+        return eng.png_encode(slab, geom, offsets)
+
+    def host_route(**kw):
+        raw = slab.cpu().numpy()
+        files = []
+        for (h, w), (o, pitch) in zip(geom, offsets):
+            b = io.BytesIO()
+            Image.fromarray(raw[o:o + h * pitch].reshape(h, w, 3)).save(b, format='PNG', **kw)
+            files.append(b.getvalue())
+        return files
+
+    fd, fh = device_route(), host_route()
+    raw = slab.cpu().numpy()
+    lossless = all(np.array_equal(np.array(Image.open(io.BytesIO(x)).convert('RGB')), raw[o:o + h * pitch].reshape(h, w, 3))
+                   for x, (h, w), (o, pitch) in zip(fd, geom, offsets))
+    level1 = host_route(compress_level=1)
+    rounds = {'device': [], 'host': []}
+    reps = max(2, min(a.iters, 5))
+    for _ in range(3):                                              # alternated: both see the same clocks and the same neighbours
+        ms = {'device': [], 'host': []}
+        for _ in range(reps):
+            ms['device'].append(wall(device_route)[0])
+            ms['host'].append(wall(host_route)[0])
+        for k, v in ms.items():
+            rounds[k].append(float(np.median(v)) / n)
+    med = {k: float(np.median(v)) for k, v in rounds.items()}
+    spread = max(rounds['host']) - min(rounds['host'])
+    cap = [png_bound(h, w) for h, w in geom]
+    oo = np.concatenate([[0], np.cumsum(cap)])
+    ws_out = torch.empty(int(oo[-1]), device=dev, dtype=torch.uint8)
+    full = [(o, p_, int(x), c) for (o, p_), x, c in zip(offsets, oo[:-1], cap)]
+    kern, total_ms = {}, 0.0
+    for k, (ms_, _, _, nl) in timed(eng, lambda: eng.png_encode_into(slab, ws_out, geom, full), a.iters).items():
+        kern[k] = {'ms_per_launch': round(ms_, 4), 'launches_per_call': nl}
+        total_ms += ms_ * nl
+    size = lambda files: sum(len(x) for x in files)
+    row = {'workload': f'{n} pictures of {geom[0][0]} x {geom[0][1]}, {px / 1e6:.1f} Mpx in all', 'decodes_to_the_pictures': bool(lossless),
+           'ms_per_picture_rounds': {k: [round(x, 3) for x in v] for k, v in rounds.items()}, 'ms_per_picture_median': {k: round(v, 3) for k, v in med.items()},
+           'host_spread_between_rounds_ms': round(spread, 3), 'ratio_host_over_device': round(med['host'] / med['device'], 2),
+           'file_bytes': {'device': size(fd), 'pillow_compress_level_6': size(fh), 'pillow_compress_level_1': size(level1), 'raw': 3 * px},
+           'fraction_of_raw': {'device': round(size(fd) / (3 * px), 4), 'pillow_compress_level_6': round(size(fh) / (3 * px), 4),
+                               'pillow_compress_level_1': round(size(level1) / (3 * px), 4)},
+           'bytes_moved_device_to_host': {'device_route': size(fd) + 8 * n, 'host_route': int(slab.numel())},
+           'kernels': kern, 'kernels_ms_per_call': round(total_ms, 4), 'kernels_ms_per_picture': round(total_ms / n, 4)}
+    print(json.dumps(row, indent=1))
+    return {'demo_pictures': row}
 
 
 def horizon_panel_section(eng, a):
@@ -835,7 +916,7 @@ def jpeg_decode_section(eng, a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'jpeg_decode', 'horizon_panel'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'horizon_panel'], default=None, help='run one section only')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -928,6 +1009,15 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'routes: wall clock with the copies, 3 alternated rounds, ms per '
                        'picture; kernels: per-launch HIP events (library profiler)', 'jpeg_encode': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'png_encode':
+        from spec_amd import _lib
+        rows = png_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'iters': a.iters, 'timing': 'routes: wall clock with the copies, 3 alternated rounds, ms per picture; kernels: per-launch HIP '
+                       'events (library profiler)', 'png_encode': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     if a.only == 'jpeg_decode':

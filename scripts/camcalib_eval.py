@@ -47,6 +47,11 @@ def main():
     ap.add_argument('--write-tree', type=str, default=None, metavar='OUT', help='with --panoramas: also write the views as a pano_scalenet tree')
     ap.add_argument('--device-jpeg', action='store_true', help="with --write-tree: encode a panorama's views on the device in one call and "
                     "download only the files' bytes (the same bytes as Pillow's; default: engine.JPEG_DEVICE_DEFAULT)")
+    ap.add_argument('--tree-format', choices=['JPEG', 'PNG'], default='JPEG', help="with --write-tree: what is encoded into the tree's image files "
+                    "(write_tree's image_format; PNG takes the JPEG round trip out of a comparison between the tree and the evaluation)")
+    ap.add_argument('--device-png', action='store_true', help="with --write-tree --tree-format PNG: encode a panorama's views on the device in one "
+                    "call and download only the files' bytes (they decode to the same views; the bytes are not Pillow's; default: "
+                    "engine.PNG_DEVICE_DEFAULT, off)")
     ap.add_argument('--device-decode', dest='device_decode', action='store_true', default=None,
                     help="send the frames' .jpg files up as bytes and decode them on the device instead of with Pillow on the host (the same "
                     "pixels; default: engine.JPEG_DECODE_DEVICE_DEFAULT)")
@@ -73,7 +78,8 @@ def main():
         dataset = panorama.PanoViewDataset(panorama.list_panoramas(args.panoramas), args.views_per_pano, args.seed)
         if args.write_tree:
             panorama.write_tree(dataset, args.write_tree, while_evaluating=True,      # every view is generated once
-                                jpeg_device=True if args.device_jpeg else None)
+                                image_format=args.tree_format, jpeg_device=True if args.device_jpeg else None,
+                                png_device=True if args.device_png else None)
     res = ce.run_evaluation(hp, data_root=root, ckpt=args.ckpt, dataset=dataset, save_images=args.save_images, image_dir=args.image_dir,
                             jpeg_device=True if args.device_jpeg else None, jpeg_decode_device=args.device_decode)
     if args.report:

@@ -76,6 +76,7 @@ def main(args):
     total_time = time.time()
     tester = SPECTester(args)
     tester._jpeg_device = True if args.device_jpeg else None
+    tester._png_device = True if args.device_png else None
     tester._jpeg_decode_device = args.device_decode
     tester._ragged_crops = True if args.ragged_crops else None
     tester._panel0_device = True if args.device_panel0 else None
@@ -127,6 +128,8 @@ def build_parser():
     parser.add_argument('--draw_keypoints', action='store_true', help='draw 2d keypoints on rendered image')
     parser.add_argument('--device_jpeg', action='store_true', help='encode the pictures of .jpg / .jpeg frames on the device and download only '
                         "the files' bytes (the same bytes as Pillow's; default: engine.JPEG_DEVICE_DEFAULT)")
+    parser.add_argument('--device_png', action='store_true', help='encode the pictures of .png frames on the device and download only the files\' '
+                        "bytes (they decode to the same pictures; the bytes are not Pillow's; default: engine.PNG_DEVICE_DEFAULT, off)")
     parser.add_argument('--ragged_crops', action='store_true', help="a flush's frames in one slab, one upload and one crop launch instead of one of each "
                         'per frame (the same crops; default: engine.RAGGED_CROPS_DEFAULT).  The device decode below is part of this route only')
     parser.add_argument('--device_decode', dest='device_decode', action='store_true', default=None,

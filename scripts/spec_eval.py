@@ -87,6 +87,8 @@ def main():
                     'TESTING.SAVE_IMAGES and TRAINING.SAVE_IMAGES (the reference writes the files only with both)')
     ap.add_argument('--device-jpeg', action='store_true', help='with --save-images: encode .jpg / .jpeg pictures on the device and download '
                     "only the files' bytes (the same bytes as Pillow's; default: engine.JPEG_DEVICE_DEFAULT)")
+    ap.add_argument('--device-png', action='store_true', help='with --save-images: encode .png pictures on the device and download only the '
+                    "files' bytes (they decode to the same pictures; the bytes are not Pillow's; default: engine.PNG_DEVICE_DEFAULT, off)")
     ap.add_argument('--ragged-crops', action='store_true', help="a batch's images in one slab, one upload and one crop launch instead of one of "
                     'each per sample (the same crops; default: engine.RAGGED_CROPS_DEFAULT).  The device decode below is part of this route only')
     ap.add_argument('--device-decode', dest='device_decode', action='store_true', default=None,
@@ -103,6 +105,9 @@ def main():
     if args.device_jpeg:
         from spec_amd import engine
         engine.JPEG_DEVICE_DEFAULT = True
+    if args.device_png:
+        from spec_amd import engine
+        engine.PNG_DEVICE_DEFAULT = True
     if args.device_panel0:
         from spec_amd import engine
         engine.PANEL0_DEVICE_DEFAULT = True

@@ -38,6 +38,7 @@ MARK_STRIP, MARK_MASK, MARK_LINE, MARK_REC = 0, 1, 2, 8         # SPECMI_MARK_* 
 # the limits of specmi_draw_marks: frame side, line width, line end point, mask side, mask position (include/specmi.h)
 MARK_MAX_SIDE, MARK_MIN_WIDTH, MARK_MAX_WIDTH, MARK_MAX_COORD, MARK_MAX_MASK_SIDE, MARK_MAX_MASK_POS = 8192, 2, 64, 100000, 8192, 16383
 JPEG_HEADER_BYTES = 623                       # what specmi_jpeg_header writes; the least capacity of specmi_jpeg_encode (include/specmi.h)
+PNG_OVERHEAD_BYTES, PNG_HEADER_BYTES = 63, 33   # the least capacity of specmi_png_encode; what specmi_png_header writes (include/specmi.h)
 # SPECMI_JPEG_* (include/specmi.h): what specmi_jpeg_probe answers, by value
 JPEG_REASONS = ('supported', 'not_jpeg', 'truncated', 'progressive', 'sof', 'precision', 'components', 'sampling', 'restart', 'scan',
                 'colourspace', 'tables', 'size', 'trailing')
@@ -215,6 +216,11 @@ PROTOTYPES = {
     'specmi_jpeg_encode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_int32_p, c_int64_p, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p]),
     'specmi_jpeg_header': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+    # (h, in_slab, in_bytes, out_slab, out_bytes, pic_geom, pic_offsets, n, sizes, stream)
+    'specmi_png_encode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_int32_p, c_int64_p, C.c_int, C.c_void_p,
+                                    C.c_void_p]),
+    'specmi_png_bound': (C.c_int, [C.c_int, C.c_int, c_int64_p]),
+    'specmi_png_header': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     # (file, bytes, reason, H, W, sampling)
     'specmi_jpeg_probe': (C.c_int, [C.c_void_p, C.c_size_t, c_int32_p, c_int32_p, c_int32_p, c_int32_p]),
     # (h, files_host, in_slab, in_bytes, file_ranges, out_slab, out_bytes, out_offsets, n, status, coef, coef_bytes, passes, stream)

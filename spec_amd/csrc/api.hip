@@ -809,6 +809,8 @@ int specmi_destroy(specmi_handle* h) {
     if (h->marks_tab) (void)hipFree(h->marks_tab);
     if (h->jpeg_tab) (void)hipFree(h->jpeg_tab);
     if (h->jpeg_ws) (void)hipFree(h->jpeg_ws);
+    if (h->png_tab) (void)hipFree(h->png_tab);
+    if (h->png_ws) (void)hipFree(h->png_ws);
     if (h->jdec_tab) (void)hipFree(h->jdec_tab);
     if (h->jdec_ws) (void)hipFree(h->jdec_ws);
     hrnet_free(h->hrnet);
@@ -2206,6 +2208,77 @@ int specmi_jpeg_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_
     a.n = n; a.mcus = (int)mcus; a.mchunks = (int)mchunks; a.bchunks = (int)bchunks;
     LaunchCtx ctx{s, &h->prof, "jpeg.encode"};
     LAUNCHCHK(h, launch_jpeg_encode(a, px * 3, ctx), "jpeg_encode");
+    return SPECMI_OK;
+}
+
+int specmi_png_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_bytes, uint8_t* out_slab, size_t out_slab_bytes,
+                      const int32_t* pic_geom, const int64_t* pic_offsets, int n, int64_t* sizes, void* stream) {
+    ENTER(h);
+    if (!in_slab || !out_slab || !pic_geom || !pic_offsets || !sizes) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (n <= 0 || n > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 pictures per call, got %d", n);
+    if ((const uint8_t*)out_slab < in_slab + in_slab_bytes && in_slab < (const uint8_t*)out_slab + out_slab_bytes)
+        return fail(h, SPECMI_ERR_ARG, "the picture slab and the output slab overlap");
+    std::vector<int> tab((size_t)n * kPngPicRec, 0);
+    std::vector<std::pair<long long, long long>> outs((size_t)n);       // first byte, capacity
+    long long rows = 0, segs = 0, filt = 0;
+    double px = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const int H = pic_geom[2 * i], W = pic_geom[2 * i + 1];
+        const int64_t in_off = pic_offsets[4 * i], in_pitch = pic_offsets[4 * i + 1], out_off = pic_offsets[4 * i + 2], cap = pic_offsets[4 * i + 3];
+        if (H < 1 || W < 1 || H > 32768 || W > 32768) return fail(h, SPECMI_ERR_ARG, "picture %d: %d x %d pixels (1 .. 32768 per side)", i, H, W);
+        if (in_pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "picture %d: a pitch of %lld bytes for rows of %d", i, (long long)in_pitch, 3 * W);
+        if (in_off < 0 || (double)in_off + (double)(H - 1) * (double)in_pitch + 3.0 * W > (double)in_slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "picture %d: its rectangle leaves the slab of %zu bytes", i, in_slab_bytes);
+        if (cap < kPngOverhead) return fail(h, SPECMI_ERR_ARG, "picture %d: a capacity of %lld bytes is below the fixed overhead of %d", i, (long long)cap, kPngOverhead);
+        if (out_off < 0 || (double)out_off + (double)cap > (double)out_slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "picture %d: its output leaves the slab of %zu bytes", i, out_slab_bytes);
+        // IDAT's length field: the zlib stream with every segment stored is the bound minus what stands around it
+        if (png_bound(H, W) - (kPngOverhead - 6) >= (1LL << 31))
+            return fail(h, SPECMI_ERR_ARG, "picture %d: the zlib stream of %d x %d pixels may not fit one IDAT chunk (2^31 bytes)", i, H, W);
+        PngPic r{};
+        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal pictures give equal records
+        r.in_off = in_off; r.in_pitch = H > 1 ? in_pitch : 3LL * W; r.out_off = out_off; r.cap = cap;
+        r.H = H; r.W = W; r.stream = (long long)H * (1 + 3LL * W); r.filt_off = filt;
+        r.row0 = (int)rows; r.seg0 = (int)segs; r.nseg = (int)((r.stream + kPngSegment - 1) / kPngSegment);
+        rows += H; segs += r.nseg; filt += (r.stream + 255) & ~255LL;
+        px += (double)H * W;
+        if (segs > kPngMaxSegments) return fail(h, SPECMI_ERR_ARG, "the pictures' filtered streams hold more than 2^23 segments of 32768 bytes");
+        std::memcpy(tab.data() + (size_t)i * kPngPicRec, &r, sizeof(r));
+        outs[i] = {out_off, cap};
+    }
+    std::sort(outs.begin(), outs.end());
+    for (int i = 0; i + 1 < n; ++i)
+        if (outs[i].first + outs[i].second > outs[i + 1].first) return fail(h, SPECMI_ERR_ARG, "two outputs share a byte (at offset %lld)", outs[i + 1].first);
+    hipStream_t s = (hipStream_t)stream;
+    size_t off[7];
+    const size_t need = png_ws_layout(n, filt, segs, off);
+    const bool regrown = tab.size() * 4 > h->png_tab_bytes;
+    if (need > h->png_ws_bytes || regrown || tab != h->png_host) {
+        // both need a whole-device synchronise, which would invalidate a capture under way on this stream: ask first and leave it valid
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone)
+            return fail(h, SPECMI_ERR_STATE, "new picture records or a larger encoder workspace are not possible while the stream "
+                        "is being captured: run one eager call with these records first (nothing was enqueued)");
+    }
+    int rc;
+    if ((rc = grow_ragged(h, &h->png_ws, &h->png_ws_bytes, need, "the PNG workspace"))) return rc;
+    if ((rc = grow_ragged(h, (void**)&h->png_tab, &h->png_tab_bytes, tab.size() * 4, "the PNG picture table"))) return rc;
+    if (regrown || tab != h->png_host) {
+        // an encode enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
+        if (!regrown && (rc = sync_for_growth(h, "the PNG picture table"))) return rc;
+        h->png_host.swap(tab);
+        HIPCHK(h, hipMemcpyAsync(h->png_tab, h->png_host.data(), h->png_host.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    char* ws = (char*)h->png_ws;
+    PngArgs a{};
+    a.in = in_slab; a.out = out_slab; a.sizes = (long long*)sizes; a.pics = (const PngPic*)h->png_tab;
+    a.filt = (unsigned char*)(ws + off[0]); a.segbuf = (unsigned*)(ws + off[1]); a.seg_bytes = (unsigned*)(ws + off[2]);
+    a.seg_sum = (unsigned*)(ws + off[3]); a.seg_base = (unsigned long long*)(ws + off[4]); a.seg_crc = (unsigned*)(ws + off[5]);
+    a.pic_adler = (unsigned*)(ws + off[6]);
+    a.n = n; a.rows = (int)rows; a.segs = (int)segs;
+    LaunchCtx ctx{s, &h->prof, "png.encode"};
+    LAUNCHCHK(h, launch_png_encode(a, px * 3, ctx), "png_encode");
     return SPECMI_OK;
 }
 

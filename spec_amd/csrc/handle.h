@@ -194,6 +194,13 @@ struct specmi_handle {
     std::vector<int> jpeg_host;         // host image of jpeg_tab as last uploaded
     void* jpeg_ws = nullptr;
     size_t jpeg_ws_bytes = 0;
+    // specmi_png_encode: the picture records, same growth and upload rules as ragged_tab; the filtered streams, the segments'
+    // blocks and their sums (png_ws_layout), grows like ragged_tmp
+    int* png_tab = nullptr;
+    size_t png_tab_bytes = 0;
+    std::vector<int> png_host;          // host image of png_tab as last uploaded
+    void* png_ws = nullptr;
+    size_t png_ws_bytes = 0;
     // specmi_jpeg_decode: the file records with their tables, same growth and upload rules as ragged_tab; coefficients, planes and
     // the lanes' states (jdec_ws_layout), grows like ragged_tmp
     int* jdec_tab = nullptr;

@@ -641,6 +641,39 @@ size_t jpeg_ws_layout(int n, long long mcus, long long mchunks, long long bchunk
 int launch_jpeg_encode(const JpegArgs& a, double in_bytes, const LaunchCtx& ctx);
 
 // ----------------------------------------------------------------------------------------
+// PNG encoder  (png.hip)
+// ----------------------------------------------------------------------------------------
+constexpr int kPngSegment = 32768;                 // bytes of the filtered stream one workgroup codes on its own
+constexpr int kPngSegStride = kPngSegment + 32;    // room of a segment's blocks in the workspace: a stored block takes 5 + 32768 bytes
+constexpr int kPngOverhead = 63;                   // signature 8, IHDR 25, IDAT's length, type and CRC 12, zlib's header 2 and Adler-32 4, IEND 12
+constexpr int kPngHeaderBytes = 33;                // signature + IHDR
+constexpr long long kPngMaxSegments = 1 << 23;    // a workgroup of 256 per segment: HIP refuses a launch of 2^32 threads or more
+constexpr unsigned kPngFilterGrid = 1u << 20;     // workgroups of the filter kernel at most; each takes every 2^20th row
+// One picture of a specmi_png_encode call as the device reads it (18 ints): the four byte fields of its record, where its filtered
+// stream lies in the workspace and how long it is, its size, and where its rows and segments begin among the call's
+struct PngPic { long long in_off, in_pitch, out_off, cap, filt_off, stream; int H, W, row0, seg0, nseg, pad; };
+constexpr int kPngPicRec = sizeof(PngPic) / 4;
+struct PngArgs {
+    const unsigned char* in;
+    unsigned char* out;
+    const PngPic* pics;
+    long long* sizes;                     // (n): every picture's true encoded length
+    unsigned char* filt;                  // the filtered streams, each picture's from a multiple of 256
+    unsigned* segbuf;                     // (segs * kPngSegStride / 4) every segment's deflate blocks, zeroed per call
+    unsigned* seg_bytes;                  // (segs) bytes of a segment's blocks
+    unsigned* seg_sum;                    // (segs, 2) Adler-32 partials: the sum of the bytes, the sum of (n - i) byte[i] mod 65521
+    unsigned long long* seg_base;         // (segs) bytes of the picture's segments before it
+    unsigned* seg_crc;                    // (segs) the segment's blocks' share of IDAT's CRC
+    unsigned* pic_adler;                  // (n)
+    int n, rows, segs;
+};
+long long png_bound(int H, int W);
+void png_header(int H, int W, unsigned char* out);
+// byte offsets of filt, segbuf, seg_bytes, seg_sum, seg_base, seg_crc, pic_adler in the workspace -> its size
+size_t png_ws_layout(int n, long long filt_bytes, long long segs, size_t off[7]);
+int launch_png_encode(const PngArgs& a, double in_bytes, const LaunchCtx& ctx);
+
+// ----------------------------------------------------------------------------------------
 // baseline JPEG decoder  (jpeg_dec.hip)
 // ----------------------------------------------------------------------------------------
 constexpr int kJdecSubBytes = 128;        // a subsequence: 1024 scan bits = 128 bytes of the file, one lane

@@ -387,6 +387,71 @@ def check_jpeg_encode(geom, offsets, in_bytes, out_bytes, quality, in_ptr=None, 
     return geom.astype(np.int32), offsets
 
 
+# Which route the pictures the flows write as .png take (the same flows as JPEG_DEVICE_DEFAULT's): False = the raw picture comes
+# down and Pillow (zlib, one host thread) encodes it, True = specmi_png_encode encodes it where it lies and only the file's bytes
+# come down.  Unlike the JPEG route the BYTES differ from the host route's - the file decodes to the same
+# picture, but it is this library's deflate, not zlib's (include/specmi.h states the contract) - so the route is opt-in: off by
+# default whatever scripts/bench_aux.py --only png_encode measures (6.3 against 336 ms per 1080 x 5760 picture, files of 0.43 of raw
+# against Pillow's 0.23: profiles/png_encode_aux.json).
+PNG_DEVICE_DEFAULT = False
+
+
+def flow_png_device(png_device=None) -> bool:
+    """``png_device`` (the flow's private switch) decides, None = the default."""
+    return PNG_DEVICE_DEFAULT if png_device is None else bool(png_device)
+
+
+def is_png_name(path) -> bool:
+    """Does Pillow write ``path`` as a PNG (by its extension)?"""
+    return str(path).lower().endswith('.png')
+
+
+def png_bound(H, W) -> int:
+    """``specmi_png_bound``: the length no file of ``Engine.png_encode`` for an (H, W) picture exceeds.  Host only."""
+    out = np.zeros(1, np.int64)
+    if _lib.load().specmi_png_bound(int(H), int(W), out.ctypes.data_as(_lib.c_int64_p)) != _lib.OK:
+        raise ValueError(f'a picture of {H} x {W}: 1 .. 32768 pixels per side')
+    return int(out[0])
+
+
+def check_png_encode(geom, offsets, in_bytes, out_bytes, in_ptr=None, out_ptr=None):
+    """Every refusal of ``specmi_png_encode`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom`` (n, 2)
+    [H, W], ``offsets`` (n, 4) [in_offset, in_pitch, out_offset, out_capacity], the sizes of the two slabs and - where known - the
+    slabs' addresses (None for either: a missing slab).  -> the arrays as the library reads them (int32, int64).  Needs no device."""
+    geom, offsets = np.ascontiguousarray(geom, dtype=np.int64), np.ascontiguousarray(offsets, dtype=np.int64)
+    n = geom.shape[0] if geom.ndim == 2 else -1
+    if geom.ndim != 2 or geom.shape[1] != 2 or tuple(offsets.shape) != (n, 4):
+        raise ValueError('pictures: geom (n, 2) and offsets (n, 4) with one row per picture')
+    if not 1 <= n <= 65535:
+        raise ValueError(f'1 to 65535 pictures per call, got {n}')
+    if in_bytes is None or out_bytes is None or in_ptr == 0 or out_ptr == 0:
+        raise ValueError('the picture slab or the output slab is missing (a null pointer)')
+    if in_ptr is not None and out_ptr is not None and out_ptr < in_ptr + in_bytes and in_ptr < out_ptr + out_bytes:
+        raise ValueError('the picture slab and the output slab overlap')
+    H, W = geom.T
+    in_off, in_pitch, out_off, cap = offsets.T
+    if ((H < 1) | (H > 32768) | (W < 1) | (W > 32768)).any():
+        raise ValueError('a picture of 1 .. 32768 pixels per side')
+    if (in_pitch < 3 * W).any():
+        raise ValueError('a pitch below 3 * W bytes')
+    if (in_off < 0).any() or (in_off + (H - 1) * in_pitch + 3 * W > in_bytes).any():
+        raise ValueError(f'a picture rectangle leaves the slab of {in_bytes} bytes')
+    if (cap < _lib.PNG_OVERHEAD_BYTES).any():
+        raise ValueError(f'a capacity below the fixed overhead of {_lib.PNG_OVERHEAD_BYTES} bytes')
+    if (out_off < 0).any() or (out_off + cap > out_bytes).any():
+        raise ValueError(f'an output leaves the slab of {out_bytes} bytes')
+    stream = H * (1 + 3 * W)
+    segments = -(-stream // 32768)
+    if (6 + stream + 5 * segments >= 1 << 31).any():
+        raise ValueError('a picture whose zlib stream may not fit one IDAT chunk (2^31 bytes)')
+    if int(segments.sum()) > 1 << 23:
+        raise ValueError('the pictures\' filtered streams hold more than 2^23 segments of 32768 bytes')
+    order = np.argsort(out_off, kind='stable')
+    if ((out_off + cap)[order][:-1] > out_off[order][1:]).any():
+        raise ValueError('two outputs share a byte')
+    return geom.astype(np.int32), offsets
+
+
 # Which route the .jpg / .jpeg frames the flows READ take (preprocess.decode_frames): False = Pillow decodes every file on the host
 # and the raw frames go up (today's path, bit for bit), True = the files' bytes go up and specmi_jpeg_decode decodes the supported
 # ones where they land (DESIGN.md 7 f-15).  Same pixels either way on a libjpeg-turbo Pillow.  The rule: True only when
@@ -1156,6 +1221,47 @@ class Engine:
             cap[todo] = sizes
             todo = todo[~fits]
         return files
+
+    def png_encode_into(self, slab, out_slab, geom, offsets, sizes=None):
+        """``specmi_png_encode``: the pictures ``geom`` (n, 2) [H, W] at ``offsets`` (n, 4) [in_offset, in_pitch, out_offset,
+        out_capacity] of ``slab`` (1-D uint8 on the engine device, as ``jpeg_encode_into`` takes it) encoded as PNG files into
+        ``out_slab`` (1-D uint8, same device, not overlapping).  -> ``sizes`` (n,) int64 on the device (given or new): every
+        file's true length, also of a picture that did not fit its capacity (nothing is written beyond it; with
+        ``png_bound(H, W)`` of room every picture fits).  Nothing is synchronised or downloaded here; a repeat of the previous
+        records can be captured in a graph.  Everything is checked before the library is called (``check_png_encode``)."""
+        d = self.device
+        for name, x in (('slab', slab), ('out_slab', out_slab)):
+            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
+                raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
+        geom, offsets = check_png_encode(geom, offsets, slab.numel(), out_slab.numel(), slab.data_ptr(), out_slab.data_ptr())
+        n = int(geom.shape[0])
+        if sizes is None:
+            sizes = torch.empty(n, device=d, dtype=torch.int64)
+        elif not isinstance(sizes, torch.Tensor) or sizes.device != d or sizes.dtype != torch.int64 or tuple(sizes.shape) != (n,) or not sizes.is_contiguous():
+            raise ValueError('sizes must be a contiguous (n,) int64 tensor on the engine device')
+        _lib.check(self.h, self.lib.specmi_png_encode(
+            self.h, _ptr(slab), slab.numel(), _ptr(out_slab), out_slab.numel(), geom.ctypes.data_as(_lib.c_int32_p),
+            offsets.ctypes.data_as(_lib.c_int64_p), n, _ptr(sizes), self._stream()))
+        return sizes
+
+    def png_encode(self, slab, geom, offsets) -> List[bytes]:
+        """The pictures ``geom`` (n, 2) [H, W] at ``offsets`` (n, 2) [in_offset, in_pitch] of ``slab`` as PNG files that decode
+        to exactly the pictures (include/specmi.h states the contract; the bytes are not Pillow's): one ``png_encode_into`` call
+        into a private slab with ``png_bound(H, W)`` bytes per picture - every file fits, so there is no second call - a
+        download of the sizes, then of the used bytes only.  -> the files as a list of ``bytes``."""
+        geom = np.ascontiguousarray(geom, dtype=np.int64).reshape(-1, 2)
+        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+        if tuple(offsets.shape) != (geom.shape[0], 2):
+            raise ValueError('offsets (n, 2): in_offset and in_pitch per picture')
+        cap = np.array([png_bound(h, w) for h, w in geom], np.int64)
+        out_off = np.concatenate([[0], np.cumsum(cap)])
+        out_slab = torch.empty(int(out_off[-1]), device=self.device, dtype=torch.uint8)
+        sizes = self.png_encode_into(slab, out_slab, geom, np.concatenate([offsets, out_off[:-1, None], cap[:, None]], axis=1)).cpu().numpy()
+        if (sizes > cap).any():
+            raise RuntimeError('specmi_png_encode reports a file beyond specmi_png_bound')
+        host = torch.cat([out_slab[int(o):int(o + s)] for o, s in zip(out_off[:-1], sizes)]).cpu().numpy().tobytes()
+        ends = np.cumsum(sizes)
+        return [host[int(e - s):int(e)] for e, s in zip(ends, sizes)]
 
     def jpeg_decode_into(self, host, slab, ranges, geom, out_slab, outs, status=None, coef=None):
         """``specmi_jpeg_decode``: the files at ``ranges`` (n, 2) [offset, length] of ``slab`` (1-D uint8 on the engine device)

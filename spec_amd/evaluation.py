@@ -184,14 +184,16 @@ def keypoints_orig(data: dict, idx) -> np.ndarray:
                            data['part'][idx] if 'part' in data else np.zeros((n, 24, 3))], axis=1)
 
 
-def save_batch_picture(ds: 'EvalDataset', idx, pred, save_dir: str, dataloader_nb: int, batch_nb: int, device, panel0_device=None) -> str:
+def save_batch_picture(ds: 'EvalDataset', idx, pred, save_dir: str, dataloader_nb: int, batch_nb: int, device, panel0_device=None,
+                       png_device=None) -> str:
     """``SPECTrainer.validation_summaries`` (spec/trainer.py:366-423) for one batch: ONE picture, of the batch's first image
     (``max_save_img = 1``) - the full image with the ground-truth 2D skeleton ``keypoints_orig`` (drawn on the device), the
     horizon line of the dataset's CamCalib prediction, the predicted mesh over it and the side view.  The render rotation is
     ``batch_euler2matrix([-pitch, 0, roll])`` = Rx(-pitch) Rz(roll), the focal length f_pix twice, the centre (W // 2, H // 2),
     all from the ``camcalib_*`` fields (what the dataset hands out as ``pred_cam_*``, whichever camera the model was given).
     ``panel0_device`` (None = ``engine.PANEL0_DEVICE_DEFAULT``): the line and caption are drawn on the device (the same bytes).
-    -> the file written: ``save_dir/{epoch 0:04d}_{dataloader:02d}_{batch:05d}_{image 0:02d}_{basename}``."""
+    ``png_device`` (None = ``engine.PNG_DEVICE_DEFAULT``, off): the picture of a ``.png`` image is encoded on the device (the same
+    picture, other bytes than Pillow's).  -> the file written: ``save_dir/{epoch 0:04d}_{dataloader:02d}_{batch:05d}_{image 0:02d}_{basename}``."""
     from . import render
     d, i = ds.data, int(idx[0])
     imgname = os.path.join(ds.img_dir, str(ds.imgname[i]))
@@ -204,7 +206,7 @@ def save_batch_picture(ds: 'EvalDataset', idx, pred, save_dir: str, dataloader_n
     save_filename = os.path.join(save_dir, f'{0:04d}_{dataloader_nb:02d}_{batch_nb:05d}_{0:02d}_{os.path.basename(imgname)}')
     render.render_image_group(image, pred['pred_cam_t'][0], pred['smpl_vertices'][0], rot, (f_pix, f_pix), (w // 2, h // 2),
                               save_filename=save_filename, keypoints_2d=keypoints_orig(d, idx[:1])[0],
-                              cam_params=np.array([vfov, pitch, roll, f_pix]), device=device, panel0_device=panel0_device)
+                              cam_params=np.array([vfov, pitch, roll, f_pix]), device=device, panel0_device=panel0_device, png_device=png_device)
     return save_filename
 
 

@@ -204,7 +204,7 @@ class PanoViewDataset:
 
 
 def write_tree(ds: PanoViewDataset, out_root: str, image_format: str = 'JPEG', log=print, while_evaluating: bool = False,
-               jpeg_device=None) -> str:
+               jpeg_device=None, png_device=None) -> str:
     """The dataset as a 'pano_scalenet' tree under ``out_root`` (a data root: the tree is
     ``out_root/data/dataset_folders/pano_scalenet``): ``images/NAME.jpg`` as the reference saves it (quality 95, not optimised,
     not progressive; generateCalibrationDataset.py:131-132), ``images/NAME.json`` with the reference's fields (:149-158) and
@@ -213,13 +213,15 @@ def write_tree(ds: PanoViewDataset, out_root: str, image_format: str = 'JPEG', l
     panorama's views when the dataset extracts them, so that an evaluation that follows generates every view once.
     ``jpeg_device`` (None = ``engine.JPEG_DEVICE_DEFAULT``) with ``image_format='JPEG'``: all views of a panorama are encoded in
     ONE ``Engine.jpeg_encode`` call at quality 95 from the device slab they share, and only the files' bytes come down - the
-    same bytes.  Views that do not lie in a device slab (an extractor on the host) are encoded by Pillow as before."""
+    same bytes.  ``png_device`` (None = ``engine.PNG_DEVICE_DEFAULT``, off) with ``image_format='PNG'``: ONE
+    ``Engine.png_encode`` call per panorama instead - files that decode to the same views, with bytes of their own.  Views that do
+    not lie in a device slab (an extractor on the host) are encoded by Pillow as before."""
     import joblib
     from PIL import Image
     from . import cam_utils
     from .camcalib_eval import DATASET_FOLDERS
-    from .engine import flow_jpeg_device
-    on_device = image_format == 'JPEG' and flow_jpeg_device(jpeg_device)
+    from .engine import flow_jpeg_device, flow_png_device
+    on_device = (image_format == 'JPEG' and flow_jpeg_device(jpeg_device)) or (image_format == 'PNG' and flow_png_device(png_device))
     folder = os.path.join(out_root, DATASET_FOLDERS['pano_scalenet'])
     os.makedirs(os.path.join(folder, 'images'), exist_ok=True)
     opts = {'quality': 95, 'optimize': False, 'progressive': False} if image_format == 'JPEG' else {}
@@ -232,7 +234,8 @@ def write_tree(ds: PanoViewDataset, out_root: str, image_format: str = 'JPEG', l
         files, slab = None, getattr(views, 'slab', None)
         if on_device and slab is not None and slab.device.type == 'cuda':
             eng = ds.engine or cam_utils._engine(slab.device)
-            files = eng.jpeg_encode(views.slab, list(views.sizes), [(int(o), 3 * w) for o, (_, w) in zip(views.offsets, views.sizes)], opts['quality'])
+            where = [(int(o), 3 * w) for o, (_, w) in zip(views.offsets, views.sizes)]
+            files = eng.jpeg_encode(views.slab, list(views.sizes), where, opts['quality']) if image_format == 'JPEG' else eng.png_encode(views.slab, list(views.sizes), where)
         for k, v in enumerate(views):
             i = p * ds.views_per_pano + k
             path = os.path.join(folder, 'images', ds.imgname(i))

@@ -339,7 +339,7 @@ def draw_skeleton(image, kp_2d, dataset='spin', unnormalize=True, thickness=2, r
 
 def render_image_group(image, camera_translation, vertices, camera_rotation, focal_length, camera_center, mesh_color='pinkish',
                        alpha=1.0, faces=None, mesh_filename: Optional[str] = None, save_filename: Optional[str] = None, keypoints_2d=None,
-                       cam_params: Optional[Sequence] = None, device=None, engine=None, jpeg_device=None, panel0_device=None):
+                       cam_params: Optional[Sequence] = None, device=None, engine=None, jpeg_device=None, panel0_device=None, png_device=None):
     """The three panels of ``render_image_group`` (renderer_cam.py:147-218) side by side, (H, 3W, 3) uint8 on the device:
 
     0. ``image`` (H, W, 3; uint8, or floats in [0, 1] / [0, 255] as the reference accepts) with - given ``cam_params`` =
@@ -356,7 +356,8 @@ def render_image_group(image, camera_translation, vertices, camera_rotation, foc
     degree turn as .obj (``NAME.obj``; ``NAME_<m>.obj`` from the second on) and the x-flipped translations as .npy
     (renderer_cam.py:74,87-90).  ``save_filename``: the image through Pillow (the reference's cv2.imwrite of the RGB-swapped
     array stores the same pixels); with ``jpeg_device`` (None = ``engine.JPEG_DEVICE_DEFAULT``) a ``.jpg`` / ``.jpeg`` name is
-    encoded on the device (``save_picture``: the same bytes, and only they come down).  ``alpha`` is accepted and ignored: the
+    encoded on the device (``save_picture``: the same bytes, and only they come down), with ``png_device`` (None =
+    ``engine.PNG_DEVICE_DEFAULT``, off) a ``.png`` name (the same picture, other bytes).  ``alpha`` is accepted and ignored: the
     reference's material is ``alphaMode='OPAQUE'``.  ``panel0_device`` (None = ``engine.PANEL0_DEVICE_DEFAULT``): a uint8
     ``image`` goes up raw - a device tensor does not come down at all - and the line and caption are drawn where it lies
     (``show_horizon_lines``), before the skeleton and the meshes as on the host: the same bytes.  A float image, or a horizon
@@ -392,19 +393,25 @@ def render_image_group(image, camera_translation, vertices, camera_rotation, foc
             np.save(name.replace('.obj', '.npy'), t[m])
     if save_filename is not None:
         os.makedirs(os.path.dirname(os.path.abspath(save_filename)), exist_ok=True)
-        save_picture(save_filename, out, engine=eng, jpeg_device=jpeg_device)
+        save_picture(save_filename, out, engine=eng, jpeg_device=jpeg_device, png_device=png_device)
     return out
 
 
-def save_picture(path: str, picture, engine=None, jpeg_device=None) -> str:
+def save_picture(path: str, picture, engine=None, jpeg_device=None, png_device=None) -> str:
     """``picture`` - an (H, W, 3) uint8 device tensor, or the ``bytes`` of a file encoded already - written to ``path``.  A
     tensor goes through Pillow as before (``Image.fromarray(...).save(path)``) unless ``jpeg_device`` (None =
     ``engine.JPEG_DEVICE_DEFAULT``) is on, the name is ``.jpg`` / ``.jpeg`` and the tensor lies on the device: then ``Engine.jpeg_encode`` encodes it where it
-    lies at Pillow's default quality 75 - byte for byte Pillow's file - and only those bytes come down."""
+    lies at Pillow's default quality 75 - byte for byte Pillow's file - and only those bytes come down.  Likewise with
+    ``png_device`` (None = ``engine.PNG_DEVICE_DEFAULT``, off) and a ``.png`` name: ``Engine.png_encode`` writes a file that
+    decodes to the same picture, with bytes of its own (include/specmi.h)."""
     from . import cam_utils
-    from .engine import flow_jpeg_device, is_jpeg_name
+    from .engine import flow_jpeg_device, flow_png_device, is_jpeg_name, is_png_name
     if isinstance(picture, (bytes, bytearray)):
         data = picture
+    elif flow_png_device(png_device) and is_png_name(path) and picture.device.type == 'cuda':
+        eng = engine or cam_utils._engine(picture.device)
+        H, W = int(picture.shape[0]), int(picture.shape[1])
+        data = eng.png_encode(picture.contiguous().view(-1), [[H, W]], [[0, 3 * W]])[0]
     elif flow_jpeg_device(jpeg_device) and is_jpeg_name(path) and picture.device.type == 'cuda':
         eng = engine or cam_utils._engine(picture.device)
         H, W = int(picture.shape[0]), int(picture.shape[1])
@@ -507,7 +514,8 @@ def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, cent
     tensor stays on the device): drawn into each chunk's frame slab by ONE ``draw_skeletons`` call before the chunk's
     ``render_views`` call, as ``render_image_group(keypoints_2d=...)`` draws them per frame - the same bytes; with ``each`` the
     slab holds one copy of a frame per picture and each picture shows its own detection's skeleton alone.
-    ``encode``: None, 'jpeg', or one of the two per frame.  A picture of a 'jpeg' frame comes back as the ``bytes`` of its JPEG
+    ``encode``: None, 'jpeg', 'png', or one of them per frame.  A picture of a 'png' frame comes back as the ``bytes`` of its PNG
+    file (``Engine.png_encode``, ONE call per chunk: it decodes to the array, its bytes are not Pillow's).  A picture of a 'jpeg' frame comes back as the ``bytes`` of its JPEG
     file at ``quality`` instead of an array - encoded from the output slab where it lies by ONE ``Engine.jpeg_encode`` call per
     chunk, byte for byte what ``Image.fromarray(array).save(f, format='JPEG', quality=quality)`` writes; the raw slab does not
     come down (only the pictures of frames that are not encoded do, one by one).
@@ -522,8 +530,8 @@ def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, cent
     if not (len(frames) == len(counts) == len(cam_params)):
         raise ValueError('one detection count (and one cam_params entry) per frame')
     encode = [encode] * len(frames) if encode is None or isinstance(encode, str) else list(encode)
-    if len(encode) != len(frames) or any(e not in (None, 'jpeg') for e in encode):
-        raise ValueError("encode: None, 'jpeg', or one of the two per frame")
+    if len(encode) != len(frames) or any(e not in (None, 'jpeg', 'png') for e in encode):
+        raise ValueError("encode: None, 'jpeg', 'png', or one of them per frame")
     raw = [_panel0_raw(im, cp) for im, cp in zip(frames, cam_params)] if flow_panel0_device(panel0_device) else [None] * len(frames)
     panel0 = [r if r is not None else group_panel0(im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else im, cp)
               for r, im, cp in zip(raw, frames, cam_params)]
@@ -554,12 +562,15 @@ def render_image_groups(frames, vertices, cam_t, counts, rotations, focals, cent
                          in_slab, out_slab, rgb=rgb)
         shapes = [(sizes[f][0], 3 * sizes[f][1]) for f, _ in ch['pictures']]
         coded = [k for k, (f, _) in enumerate(ch['pictures']) if encode[f] == 'jpeg']
-        if not coded:
+        as_png = [k for k, (f, _) in enumerate(ch['pictures']) if encode[f] == 'png']
+        if not coded and not as_png:
             host = out_slab.cpu().numpy()
             pictures += [host[o:o + h * w3 * 3].reshape(h, w3, 3) for o, (h, w3) in zip(ch['picture_offsets'], shapes)]
         else:
-            files = eng.jpeg_encode(out_slab, [shapes[k] for k in coded], [(ch['picture_offsets'][k], 3 * shapes[k][1]) for k in coded], quality)
-            got = dict(zip(coded, files))
+            where = lambda ks: ([shapes[k] for k in ks], [(ch['picture_offsets'][k], 3 * shapes[k][1]) for k in ks])
+            got = dict(zip(coded, eng.jpeg_encode(out_slab, *where(coded), quality))) if coded else {}
+            if as_png:
+                got.update(zip(as_png, eng.png_encode(out_slab, *where(as_png))))
             for k, (o, (h, w3)) in enumerate(zip(ch['picture_offsets'], shapes)):
                 pictures.append(got[k] if k in got else out_slab[o:o + h * w3 * 3].cpu().numpy().reshape(h, w3, 3))
         slabs.append((out_slab, ch['picture_offsets'], shapes))

@@ -23,7 +23,8 @@ import torch
 from . import assets, cam_utils, io_formats, render
 from .checkpoint import load_pretrained_model, read_checkpoint
 from .modules import HMR, CameraRegressorNetwork
-from .engine import flow_image_dtype, flow_jpeg_decode_device, flow_jpeg_device, flow_ragged_crops, flow_render_batch, image_tensor, is_jpeg_name, jpeg_probe
+from .engine import (flow_image_dtype, flow_jpeg_decode_device, flow_jpeg_device, flow_png_device, flow_ragged_crops, flow_render_batch, image_tensor,
+                     is_jpeg_name, is_png_name, jpeg_probe)
 from .preprocess import camcalib_transform, crop_detections, crop_detections_ragged, decode_frames, pack_frames
 
 CAMCALIB_CKPT = 'data/camcalib/checkpoints/camcalib_sa_biased_l2.ckpt'     # scripts/camcalib_demo.py:39
@@ -114,6 +115,7 @@ class SPECTester:
         self._ragged_crops = None     # True: a flush's frames in one slab, one upload, one ragged crop launch; False: one of each per frame (same bits)
         self._render_batch = None     # True: a flush's pictures in one render_image_groups call; False: one render_image_group per frame (same bytes)
         self._jpeg_device = None      # True: .jpg / .jpeg pictures are encoded on the device and only the files' bytes come down (same bytes)
+        self._png_device = None       # True: .png pictures are encoded on the device and only the files' bytes come down (the same picture, other bytes than Pillow's); None = engine.PNG_DEVICE_DEFAULT (off)
         self._panel0_device = None    # True: the horizon line and caption of panel 0 are drawn on the device, uint8 frames go up raw (same bytes)
 
     def _build_model(self):
@@ -205,6 +207,9 @@ class SPECTester:
         if flow_jpeg_device(self._jpeg_device) and is_jpeg_name(img_fname):       # encoded once, written once per detection
             H, W3 = int(group.shape[0]), int(group.shape[1])
             picture = cam_utils._engine(group.device).jpeg_encode(group.view(-1), [[H, W3]], [[0, 3 * W3]], 75)[0]
+        elif flow_png_device(self._png_device) and is_png_name(img_fname):
+            H, W3 = int(group.shape[0]), int(group.shape[1])
+            picture = cam_utils._engine(group.device).png_encode(group.view(-1), [[H, W3]], [[0, 3 * W3]])[0]
         else:
             picture = Image.fromarray(group.cpu().numpy())
         return self._write_pictures(img_fname, [picture] * vertices.shape[0], vertices, output_path, output_img_folder)
@@ -215,9 +220,11 @@ class SPECTester:
         Same file names, same bytes; ``each``: file i of a frame shows detection i alone (spec/tester.py:181-201) - with
         ``keypoints`` (the flush's (k, 49, 2) 2D joints) its own skeleton alone.  With ``self._jpeg_device`` the pictures of
         ``.jpg`` / ``.jpeg`` frames come back from that call as the bytes of their files (``encode='jpeg'``, Pillow's default
-        quality 75); a frame's shared picture is encoded once and written once per detection."""
+        quality 75), with ``self._png_device`` those of ``.png`` frames (``encode='png'``); a frame's shared picture is encoded once
+        and written once per detection."""
         from PIL import Image
-        encode = [('jpeg' if is_jpeg_name(f) else None) for f, _, _ in pending] if flow_jpeg_device(self._jpeg_device) else None
+        on_jpeg, on_png = flow_jpeg_device(self._jpeg_device), flow_png_device(self._png_device)
+        encode = [('jpeg' if on_jpeg and is_jpeg_name(f) else 'png' if on_png and is_png_name(f) else None) for f, _, _ in pending]
         as_picture = lambda p: p if isinstance(p, bytes) else Image.fromarray(p)
         cams = [self._frame_camera(f, rgb.shape, output_path) for (f, _, _), rgb in zip(pending, frames)]
         counts = [n for _, _, n in pending]
