@@ -909,6 +909,72 @@ int specmi_jpeg_decode(specmi_handle* h, const uint8_t* files_host, const uint8_
                        uint8_t* out_slab, size_t out_slab_bytes, const int64_t* out_offsets, int n, int32_t* status, int16_t* coef,
                        size_t coef_bytes, int32_t* passes, void* stream);
 
+/* PNG FILES decoded on the device, all files of a call together: the read side of specmi_png_encode.  Replaces the host decode
+ * (PIL's Image.open(path).convert('RGB'), of which zlib's inflate is about half) and the upload of the raw frames in front of
+ * every flow that reads .png frames (spec/tester.py:95, camcalib/pano_dataset.py:117).
+ * THE CONTRACT (stated in full at the head of spec_amd/csrc/png_dec.hip, restated in NumPy in tests/png_dec_ref.py): for a SUPPORTED
+ * file the (H, W, 3) uint8 RGB picture equals np.array(Image.open(f).convert('RGB')), element for element.
+ *
+ * specmi_png_probe: host only, needs no handle and no device.  Walks the chunks of `file` (HOST, `bytes` long) and says whether
+ * specmi_png_decode takes it: *reason receives SPECMI_PNG_SUPPORTED or why not, *H, *W and *colour_type the picture (all 0 when
+ * not supported), *nranges how many IDAT chunks the file has, and idat_ranges (max_ranges x 2 int64; may be NULL with
+ * max_ranges 0) the first max_ranges of their payloads as [offset in the file, length].  A zlib stream is cut across IDAT chunks
+ * wherever the writer liked: the caller joins the payloads, so that the device sees the stream contiguous.  SUPPORTED is: the 8
+ * signature bytes; IHDR first; at least one IDAT, all IDATs consecutive; IEND last and nothing behind it; every chunk's CRC-32
+ * correct; bit depth 8; colour type 0, 2, 4 or 6 (grey is replicated, alpha dropped, tRNS / gAMA / sRGB ignored, as
+ * convert('RGB') does); compression 0, filter 0, interlace 0; H and W in [1, 32768]; no acTL; no unknown critical chunk.  The reasons:
+ *   NOT_PNG (the signature)   TRUNCATED (a chunk or IEND is cut off)   CRC   DEPTH (16-bit, sub-byte)   PALETTE   INTERLACED
+ *   ANIMATED (acTL)   CHUNK (order, a second IHDR, an unknown critical chunk, an unknown colour type or method, no IDAT)   SIZE
+ *   TRAILING (bytes behind IEND)
+ * Returns SPECMI_ERR_ARG for a null pointer or a negative max_ranges, else SPECMI_OK.
+ *
+ * specmi_png_decode.  DEVICE pointers: in_slab, of in_slab_bytes, which holds every file's zlib stream CONTIGUOUS (the IDAT
+ * payloads joined); out_slab, uint8 RGB, of out_slab_bytes, which must not overlap in_slab - the slab and offsets convention of
+ * the ragged calls; status (n int32); raw (optional, NULL in the flows: receives the inflated, still filtered streams, file i's
+ * H (1 + W bpp) bytes beginning at the sum of the streams before it, each rounded up to 256; of raw_bytes; it lets a test name
+ * the stage that is wrong).  HOST, one row per file:
+ *   stream_ranges (n x 2 int64):  offset of the zlib stream in in_slab, length (8 at least)
+ *   geom          (n x 3 int32):  H, W, colour type, as the probe gave them
+ *   out_offsets   (n x 2 int64):  offset of the picture's first pixel in out_slab, pitch (bytes from one row to the next, >= 3 W)
+ * status[i] is 0 when file i's stream satisfied RFC 1950 / 1951 completely, inflated to exactly H (1 + W bpp) bytes with the
+ * right Adler-32 and every filter byte in 0 .. 4; else a set of bits - 1 a bad zlib header, 2 block type 3, 4 a stored block whose
+ * LEN and NLEN disagree, 8 code lengths that over-subscribe or are incomplete, 16 a repeat code without a previous length or past
+ * the end, 32 no end-of-block code, 64 an invalid code, 128 length symbol 286 / 287 or distance symbol 30 / 31, 256 a distance
+ * beyond the output so far or the window, 512 the stream ended early, 1024 output longer or shorter than expected, 2048 bytes
+ * between the final block and the Adler word, 4096 an Adler-32 mismatch, 8192 a filter byte above 4 - and the picture's
+ * rectangle is then unspecified: the caller decodes that file on the host, which raises what it raises today.
+ * Bytes of out_slab outside the rectangles (H rows of 3 W bytes) are not touched.  A file's pixels do not depend on the other
+ * files of the call, on its place in the slabs or on scheduling.  Every read of a file is confined to its stream's range, every
+ * write to its rectangle or its share of the workspace; no kernel waits for another workgroup and every loop has a bound known
+ * from the records.  Nothing is read back: the call may be captured once its records and workspace exist.
+ * Refused (SPECMI_ERR_ARG), launching nothing: a null pointer (raw excepted); n outside [1, 65535]; a stream range that leaves
+ * in_slab; a stream shorter than 8 bytes; H or W outside [1, 32768]; a colour type other than 0, 2, 4, 6; a pitch below 3 W; a
+ * rectangle that leaves out_slab; overlapping slabs; two rectangles that share a byte; a raw_bytes too small; more than 2^31
+ * inflated bytes in all.
+ * The file records live in one device table owned by the handle, under the rule of the ragged calls above: a call whose records
+ * differ from the previous call's rewrites the table and first SYNCHRONISES THE WHOLE DEVICE; new records or a larger workspace
+ * are refused while the stream is being captured (SPECMI_ERR_STATE; asked first, nothing enqueued).  The workspace is one per
+ * handle: per file its inflated stream rounded up to 256 bytes, 512 KiB of match records (SPECMI_PNG_LANES x SPECMI_PNG_SUB_BITS
+ * / 2 of 8 bytes), and 8 bytes per 32 KiB of the inflated stream. */
+#define SPECMI_PNG_SUPPORTED 0
+#define SPECMI_PNG_NOT_PNG 1
+#define SPECMI_PNG_TRUNCATED 2
+#define SPECMI_PNG_CRC 3
+#define SPECMI_PNG_DEPTH 4
+#define SPECMI_PNG_PALETTE 5
+#define SPECMI_PNG_INTERLACED 6
+#define SPECMI_PNG_ANIMATED 7
+#define SPECMI_PNG_CHUNK 8
+#define SPECMI_PNG_SIZE 9
+#define SPECMI_PNG_TRAILING 10
+#define SPECMI_PNG_LANES 256      /* lanes of the inflate workgroup: subsequences of a window */
+#define SPECMI_PNG_SUB_BITS 512   /* bits of the zlib stream per subsequence */
+int specmi_png_probe(const uint8_t* file, size_t bytes, int32_t* reason, int32_t* H, int32_t* W, int32_t* colour_type, int64_t* idat_ranges,
+                     int max_ranges, int32_t* nranges);
+int specmi_png_decode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_bytes, const int64_t* stream_ranges, const int32_t* geom,
+                      uint8_t* out_slab, size_t out_slab_bytes, const int64_t* out_offsets, int n, int32_t* status, uint8_t* raw,
+                      size_t raw_bytes, void* stream);
+
 /* ---- evaluation metrics on the path's outputs ---------------------------------- */
 
 /* eval_single (spec/utils/compute_error.py:52-86, spec/trainer.py:272-316): joints =

@@ -16,6 +16,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only draw               # the 2D skeletons of a 1080p frame and of a 64-frame flush, next to render_views for the same flush -> profiles/draw_skeletons_aux.json
     python scripts/bench_aux.py --only jpeg_encode        # pictures to JPEG files: device encode + download of the bytes against raw download + Pillow -> profiles/jpeg_encode_aux.json
     python scripts/bench_aux.py --only png_encode         # pictures to PNG files: device encode + download of the bytes against raw download + Pillow -> profiles/png_encode_aux.json
+    python scripts/bench_aux.py --only png_decode         # 64 1080p .png frames and 8 three-panel pictures to the frame slab: 16 Pillow threads + upload against streams up + device decode -> profiles/png_decode_aux.json
     python scripts/bench_aux.py --only jpeg_decode        # 64 1080p .jpg frames to the frame slab: 16 Pillow threads + upload against bytes up + device decode -> profiles/jpeg_decode_aux.json
     python scripts/bench_aux.py --only horizon_panel      # panel 0 of eight 1080p frames: Pillow on the host against specmi_draw_marks -> profiles/horizon_panel_aux.json
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
@@ -914,9 +915,79 @@ def jpeg_decode_section(eng, a):
     return rows
 
 
+def png_decode_section(eng, a):
+    """PNG files on disk to the frame slab on the device, two content classes: the 64 synthetic 1080p frames of ``--only jpeg_decode``
+    saved at Pillow's default level, and the eight 1080 x 5760 three-panel pictures of ``--only jpeg_encode`` (flat areas with long
+    matches).  HOST = 16 Pillow threads + pack + one upload, DEVICE = read bytes + one upload + one specmi_png_decode
+    (preprocess.decode_frames).  Wall clock, 3 alternated rounds after one warm-up of each; the slabs are compared.  For information:
+    the same with the first 1 and 8 files, and the three stages' times from HIP events (library profiler)."""
+    import tempfile
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image
+    from spec_amd import preprocess
+    dev = eng.device
+    rng = np.random.default_rng(0)
+    yy, xx = np.mgrid[0:1080, 0:1920]
+    noise = [rng.normal(0, 5, (1080, 1920, 3)) for _ in range(4)]
+    frames = []
+    for i in range(64):
+        base = np.stack([128 + 80 * np.sin(yy / (60.0 + 7 * c + i) + i) * np.cos(xx / (90.0 + 11 * c) + 0.3 * i) + 30 * np.sin((xx + yy) / (17.0 + i % 5))
+                         for c in range(3)], axis=2)
+        frames.append(np.clip(base + noise[i % 4], 0, 255).astype(np.uint8))
+    v8, f, t8, _, _, _ = render_workload()
+    slab, geom, offsets = demo_pictures(eng, np.random.default_rng(0), v8, f, t8)
+    raw = slab.cpu().numpy()
+    panels = [raw[o:o + h * pitch].reshape(h, w, 3) for (h, w), (o, pitch) in zip(geom, offsets)]
+    del slab
+    rows = {}
+    with tempfile.TemporaryDirectory() as tmp:
+        for cls, imgs in (('frames_1080p', frames), ('three_panel', panels)):
+            paths = [os.path.join(tmp, f'{cls}_{i:02d}.png') for i in range(len(imgs))]
+            for path, img in zip(paths, imgs):
+                Image.fromarray(img).save(path)
+            for n in sorted({1, 8, len(paths)}):
+                sub = paths[:n]
+
+                def host_route():
+                    with ThreadPoolExecutor(max_workers=16) as ex:
+                        fr = list(ex.map(preprocess._host_rgb, sub))
+                    out = preprocess.pack_frames(fr, dev)
+                    torch.cuda.synchronize()
+                    return out
+
+                def device_route():
+                    out = preprocess.decode_frames(sub, dev, False, True)
+                    torch.cuda.synchronize()
+                    return out
+
+                want, got = host_route(), device_route()          # warm-up, and the comparison
+                same = bool(torch.equal(want[0], got[0])) and want[2] == got[2]
+                ms = {'host': [], 'device': []}
+                for _ in range(3):
+                    for name, fn in (('host', host_route), ('device', device_route)):
+                        t0 = time.perf_counter()
+                        fn()
+                        ms[name].append((time.perf_counter() - t0) * 1e3)
+                spread = max(ms['host']) - min(ms['host'])
+                row = {'files': n, 'size': list(imgs[0].shape[:2]), 'file_MB': round(sum(os.path.getsize(p) for p in sub) / 1e6, 2),
+                       'host_16_threads_ms': [round(v, 1) for v in ms['host']], 'device_ms': [round(v, 1) for v in ms['device']],
+                       'host_spread_ms': round(spread, 1), 'identical_slabs': same,
+                       'device_ahead_beyond_host_spread': bool(min(ms['host']) - max(ms['device']) > spread)}
+                if n == len(paths):
+                    row['stage_ms'] = {k: round(v[0], 3) for k, v in timed(eng, device_route, 1).items() if k.startswith('pdec_')}
+                rows[f'{cls}_{n}'] = row
+    full = [rows[f'frames_1080p_{len(frames)}'], rows[f'three_panel_{len(panels)}']]
+    rows['default_on_rule'] = ('engine.PNG_DECODE_DEVICE_DEFAULT becomes True only when device_ahead_beyond_host_spread holds for the whole batch of '
+                               'both content classes')
+    rows['rule_met'] = bool(all(r['device_ahead_beyond_host_spread'] and r['identical_slabs'] for r in full))
+    print(json.dumps(rows, indent=1))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'horizon_panel'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel'], default=None, help='run one section only')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -1027,6 +1098,15 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'timing': 'wall clock from the files on disk to the frame slab on the device, one warm-up then 3 alternated rounds, ms per '
                        '64-frame batch', 'jpeg_decode': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'png_decode':
+        from spec_amd import _lib
+        rows = png_decode_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'timing': 'wall clock from the files on disk to the frame slab on the device, one warm-up then 3 alternated rounds, ms per '
+                       'batch; stage_ms: per-launch HIP events (library profiler)', 'png_decode': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     if a.only == 'horizon_panel':

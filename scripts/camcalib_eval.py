@@ -53,8 +53,8 @@ def main():
                     "call and download only the files' bytes (they decode to the same views; the bytes are not Pillow's; default: "
                     "engine.PNG_DEVICE_DEFAULT, off)")
     ap.add_argument('--device-decode', dest='device_decode', action='store_true', default=None,
-                    help="send the frames' .jpg files up as bytes and decode them on the device instead of with Pillow on the host (the same "
-                    "pixels; default: engine.JPEG_DECODE_DEVICE_DEFAULT)")
+                    help="send the frames' .jpg and .png files up as bytes and decode them on the device instead of with Pillow on the host (the same "
+                    "pixels; defaults: engine.JPEG_DECODE_DEVICE_DEFAULT, engine.PNG_DECODE_DEVICE_DEFAULT)")
     ap.add_argument('--host-decode', dest='device_decode', action='store_false', help='decode every frame with Pillow on the host')
     ap.add_argument('--save-images', dest='save_images', action='store_true', default=None,
                     help='write the validation pictures (default: TRAINING.SAVE_IMAGES of the config)')
@@ -81,7 +81,8 @@ def main():
                                 image_format=args.tree_format, jpeg_device=True if args.device_jpeg else None,
                                 png_device=True if args.device_png else None)
     res = ce.run_evaluation(hp, data_root=root, ckpt=args.ckpt, dataset=dataset, save_images=args.save_images, image_dir=args.image_dir,
-                            jpeg_device=True if args.device_jpeg else None, jpeg_decode_device=args.device_decode)
+                            jpeg_device=True if args.device_jpeg else None, jpeg_decode_device=args.device_decode,
+                            png_decode_device=args.device_decode)
     if args.report:
         rep = {k: (v.tolist() if hasattr(v, 'tolist') else v) for k, v in res.items() if k != 'logits'}
         with open(args.report, 'w') as f:

@@ -77,7 +77,7 @@ def main(args):
     tester = SPECTester(args)
     tester._jpeg_device = True if args.device_jpeg else None
     tester._png_device = True if args.device_png else None
-    tester._jpeg_decode_device = args.device_decode
+    tester._jpeg_decode_device = tester._png_decode_device = args.device_decode
     tester._ragged_crops = True if args.ragged_crops else None
     tester._panel0_device = True if args.device_panel0 else None
     print(f'Number of input frames {num_frames}')
@@ -133,8 +133,8 @@ def build_parser():
     parser.add_argument('--ragged_crops', action='store_true', help="a flush's frames in one slab, one upload and one crop launch instead of one of each "
                         'per frame (the same crops; default: engine.RAGGED_CROPS_DEFAULT).  The device decode below is part of this route only')
     parser.add_argument('--device_decode', dest='device_decode', action='store_true', default=None,
-                        help="with --ragged_crops and --no_render: send the frames' .jpg files up as bytes and decode them on the device instead of "
-                        "on --decode_threads host threads (the same pixels; default: engine.JPEG_DECODE_DEVICE_DEFAULT)")
+                        help="with --ragged_crops and --no_render: send the frames' .jpg and .png files up as bytes and decode them on the device instead of "
+                        "on --decode_threads host threads (the same pixels; defaults: engine.JPEG_DECODE_DEVICE_DEFAULT, engine.PNG_DECODE_DEVICE_DEFAULT)")
     parser.add_argument('--host_decode', dest='device_decode', action='store_false', help='decode every frame with Pillow on --decode_threads host threads')
     parser.add_argument('--device_panel0', action='store_true', help='draw the horizon line and caption of panel 0 on the device instead of '
                         "with Pillow on the host (the same bytes; default: engine.PANEL0_DEVICE_DEFAULT)")

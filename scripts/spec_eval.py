@@ -92,8 +92,8 @@ def main():
     ap.add_argument('--ragged-crops', action='store_true', help="a batch's images in one slab, one upload and one crop launch instead of one of "
                     'each per sample (the same crops; default: engine.RAGGED_CROPS_DEFAULT).  The device decode below is part of this route only')
     ap.add_argument('--device-decode', dest='device_decode', action='store_true', default=None,
-                    help="with --ragged-crops: send a batch's .jpg files up as bytes and decode them on the device instead of with Pillow on "
-                    "the host (the same pixels; default: engine.JPEG_DECODE_DEVICE_DEFAULT)")
+                    help="with --ragged-crops: send a batch's .jpg and .png files up as bytes and decode them on the device instead of with Pillow on "
+                    "the host (the same pixels; defaults: engine.JPEG_DECODE_DEVICE_DEFAULT, engine.PNG_DECODE_DEVICE_DEFAULT)")
     ap.add_argument('--host-decode', dest='device_decode', action='store_false', help='with --ragged-crops: decode every frame with Pillow on the host')
     ap.add_argument('--device-panel0', action='store_true', help='with --save-images: draw the horizon line and caption of panel 0 on the '
                     "device instead of with Pillow on the host (the same bytes; default: engine.PANEL0_DEVICE_DEFAULT)")
@@ -116,7 +116,7 @@ def main():
         engine.RAGGED_CROPS_DEFAULT = True
     if args.device_decode is not None:
         from spec_amd import engine
-        engine.JPEG_DECODE_DEVICE_DEFAULT = args.device_decode
+        engine.JPEG_DECODE_DEVICE_DEFAULT = engine.PNG_DECODE_DEVICE_DEFAULT = args.device_decode
     if args.synthetic:
         return synthetic(args)
     from spec_amd import evaluation

@@ -42,6 +42,14 @@ PNG_OVERHEAD_BYTES, PNG_HEADER_BYTES = 63, 33   # the least capacity of specmi_p
 # SPECMI_JPEG_* (include/specmi.h): what specmi_jpeg_probe answers, by value
 JPEG_REASONS = ('supported', 'not_jpeg', 'truncated', 'progressive', 'sof', 'precision', 'components', 'sampling', 'restart', 'scan',
                 'colourspace', 'tables', 'size', 'trailing')
+# SPECMI_PNG_* (include/specmi.h): what specmi_png_probe answers, by value
+PNG_REASONS = ('supported', 'not_png', 'truncated', 'crc', 'depth', 'palette', 'interlaced', 'animated', 'chunk', 'size', 'trailing')
+# the inflate stage of specmi_png_decode: lanes of a workgroup = subsequences of a window, bits of the zlib stream per subsequence
+# (SPECMI_PNG_LANES, SPECMI_PNG_SUB_BITS); tests size their streams from them
+PNG_DECODE_LANES, PNG_DECODE_SUB_BITS = 256, 512
+# the status bits of specmi_png_decode (include/specmi.h), by bit number
+PNG_STATUS_BITS = ('zlib', 'btype', 'stored', 'lens', 'repeat', 'noeob', 'code', 'symbol', 'far', 'early', 'length', 'leftover', 'adler',
+                   'filter')
 HMR_LOSS, HMR_CAM_LOSS = 0, 1                 # SPECMI_HMR_LOSS / SPECMI_HMR_CAM_LOSS (include/specmi.h)
 # the ground-truth tensors of specmi_hmr_loss in the order of its prototype, per-image shapes (None = (V, 3)); int32 where named has_*
 HMR_LOSS_GT = (('pose', (72,)), ('betas', (10,)), ('pose_conf', (24,)), ('pose_3d', (24, 4)), ('keypoints', (49, 3)), ('vertices', None),
@@ -226,6 +234,11 @@ PROTOTYPES = {
     # (h, files_host, in_slab, in_bytes, file_ranges, out_slab, out_bytes, out_offsets, n, status, coef, coef_bytes, passes, stream)
     'specmi_jpeg_decode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, C.c_void_p, C.c_size_t, c_int64_p, C.c_int,
                                      C.c_void_p, C.c_void_p, C.c_size_t, c_int32_p, C.c_void_p]),
+    # (file, bytes, reason, H, W, colour_type, idat_ranges, max_ranges, nranges)
+    'specmi_png_probe': (C.c_int, [C.c_void_p, C.c_size_t, c_int32_p, c_int32_p, c_int32_p, c_int32_p, c_int64_p, C.c_int, c_int32_p]),
+    # (h, in_slab, in_bytes, stream_ranges, geom, out_slab, out_bytes, out_offsets, n, status, raw, raw_bytes, stream)
+    'specmi_png_decode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, c_int64_p, c_int32_p, C.c_void_p, C.c_size_t, c_int64_p, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'specmi_camcalib_eval': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -29,7 +29,7 @@ import torch
 
 from . import cam_utils, evaluation
 from .checkpoint import load_pretrained_model, read_checkpoint
-from .engine import flow_image_dtype, flow_jpeg_decode_device
+from .engine import flow_image_dtype, flow_jpeg_decode_device, flow_png_decode_device
 from .preprocess import decode_frames
 
 # camcalib/config.py:36-87 (the keys the test step reads)
@@ -236,7 +236,7 @@ def save_validation_picture(eng, images: torch.Tensor, size_hw, gt, pred, path: 
 @torch.no_grad()
 def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = None, log=print, device='cuda', model=None,
                    sub_batch: Optional[int] = None, dataset=None, _fp32_images: Optional[bool] = None, save_images: Optional[bool] = None,
-                   image_dir: Optional[str] = None, jpeg_device=None, jpeg_decode_device=None) -> dict:
+                   image_dir: Optional[str] = None, jpeg_device=None, jpeg_decode_device=None, png_decode_device=None) -> dict:
     """CamCalib's test epoch over ``DATASET.VAL_DS`` - or over ``dataset``, an object with ``PanoValDataset``'s interface such as
     ``spec_amd.panorama.PanoViewDataset``, whose ``device_batch`` hands frames over without a host round trip: consecutive batches of ``DATASET.BATCH_SIZE`` frames in file order, each
     padded to ITS OWN largest height and width, forwarded, scored.  Returns the four epoch figures the reference logs
@@ -254,6 +254,8 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
 
     ``jpeg_decode_device`` (None = ``engine.JPEG_DECODE_DEVICE_DEFAULT``): where the frames come from files (``ds.imgname``), the
     files' bytes go up and ``preprocess.decode_frames`` decodes them on the device instead of Pillow on the host (same bits).
+    ``png_decode_device`` (None = ``engine.PNG_DECODE_DEVICE_DEFAULT``): the same for .png files, which is what the ``pano`` tree
+    holds (camcalib/pano_dataset.py:117).
 
     ``save_images`` (None = ``TRAINING.SAVE_IMAGES`` of the config, which every config of the reference sets): the validation
     pictures of ``save_images`` (camcalib/trainer.py:94-95,118-169) - for the first image of every fourth batch the network input
@@ -284,9 +286,10 @@ def run_evaluation(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     for b0 in range(0, len(ds), bs):
         idx = range(b0, min(len(ds), b0 + bs))
         on_device = hasattr(ds, 'device_batch')
-        if not on_device and hasattr(ds, 'imgname') and flow_jpeg_decode_device(jpeg_decode_device):
+        jdec, pdec = flow_jpeg_decode_device(jpeg_decode_device), flow_png_decode_device(png_decode_device)
+        if not on_device and hasattr(ds, 'imgname') and (jdec or pdec):
             # the frames come from files: their bytes go up and are decoded where they land (preprocess.decode_frames; same bits)
-            frames, on_device = decode_frames([ds.imgname(i) for i in idx], dev, True), True
+            frames, on_device = decode_frames([ds.imgname(i) for i in idx], dev, jdec, pdec), True
         else:
             frames = ds.device_batch(idx) if on_device else [ds.frame(i) for i in idx]
         sizes_hw = frames[2] if on_device else [f.shape[:2] for f in frames]

@@ -813,6 +813,8 @@ int specmi_destroy(specmi_handle* h) {
     if (h->png_ws) (void)hipFree(h->png_ws);
     if (h->jdec_tab) (void)hipFree(h->jdec_tab);
     if (h->jdec_ws) (void)hipFree(h->jdec_ws);
+    if (h->pdec_tab) (void)hipFree(h->pdec_tab);
+    if (h->pdec_ws) (void)hipFree(h->pdec_ws);
     hrnet_free(h->hrnet);
     delete h;
     return SPECMI_OK;
@@ -2378,6 +2380,97 @@ int specmi_jpeg_decode(specmi_handle* h, const uint8_t* files_host, const uint8_
     LAUNCHCHK(h, launch_jpeg_decode(a, blocks, lanes, (int)max_groups, in_bytes, px * 3, &npass, ctx), "jpeg_decode");
     if (passes) *passes = npass;
     if (coef) HIPCHK(h, hipMemcpyAsync(coef, a.coef, (size_t)blocks * 128, hipMemcpyDeviceToDevice, s));
+    return SPECMI_OK;
+}
+
+int specmi_png_probe(const uint8_t* file, size_t bytes, int32_t* reason, int32_t* H, int32_t* W, int32_t* colour_type, int64_t* idat_ranges,
+                     int max_ranges, int32_t* nranges) {
+    if (!file || !reason || !H || !W || !colour_type || !nranges || max_ranges < 0 || (max_ranges > 0 && !idat_ranges)) return SPECMI_ERR_ARG;
+    int hh, ww, ct, nr;
+    static_assert(sizeof(long long) == sizeof(int64_t), "the ranges are written as long long");
+    *reason = png_probe(file, bytes, &hh, &ww, &ct, (long long*)idat_ranges, max_ranges, &nr);
+    *H = hh; *W = ww; *colour_type = ct; *nranges = nr;
+    return SPECMI_OK;
+}
+
+int specmi_png_decode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_bytes, const int64_t* stream_ranges, const int32_t* geom,
+                      uint8_t* out_slab, size_t out_slab_bytes, const int64_t* out_offsets, int n, int32_t* status, uint8_t* raw,
+                      size_t raw_bytes, void* stream) {
+    ENTER(h);
+    if (!in_slab || !stream_ranges || !geom || !out_slab || !out_offsets || !status) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (n <= 0 || n > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 files per call, got %d", n);
+    if ((const uint8_t*)out_slab < in_slab + in_slab_bytes && in_slab < (const uint8_t*)out_slab + out_slab_bytes)
+        return fail(h, SPECMI_ERR_ARG, "the stream slab and the output slab overlap");
+    std::vector<int> tab((size_t)n * (sizeof(PdecFile) / 4), 0);
+    std::vector<ByteRect> rects((size_t)n);
+    long long raw_total = 0, chunks = 0;
+    double px = 0.0, in_bytes = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t off = stream_ranges[2 * i], len = stream_ranges[2 * i + 1], out_off = out_offsets[2 * i], pitch = out_offsets[2 * i + 1];
+        const int H = geom[3 * i], W = geom[3 * i + 1], ct = geom[3 * i + 2];
+        if (off < 0 || len < 0 || (double)off + (double)len > (double)in_slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "file %d: its stream leaves the slab of %zu bytes", i, in_slab_bytes);
+        if (len < 8) return fail(h, SPECMI_ERR_ARG, "file %d: a zlib stream of %lld bytes (8 at least: header, a block, Adler-32)", i, (long long)len);
+        if (H < 1 || H > 32768 || W < 1 || W > 32768) return fail(h, SPECMI_ERR_ARG, "file %d: %d x %d pixels (1 .. 32768 per side)", i, H, W);
+        if (ct != 0 && ct != 2 && ct != 4 && ct != 6) return fail(h, SPECMI_ERR_ARG, "file %d: colour type %d (0, 2, 4 or 6)", i, ct);
+        if (pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "file %d: a pitch of %lld bytes for rows of %d", i, (long long)pitch, 3 * W);
+        if (out_off < 0 || (double)out_off + (double)(H - 1) * (double)pitch + 3.0 * W > (double)out_slab_bytes)
+            return fail(h, SPECMI_ERR_ARG, "file %d: its rectangle leaves the slab of %zu bytes", i, out_slab_bytes);
+        PdecFile f{};
+        f.stream_off = off; f.stream_len = len; f.out_off = out_off;
+        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal files give equal records
+        f.pitch = H > 1 ? pitch : 3LL * W;
+        f.H = H; f.W = W; f.bpp = ct == 0 ? 1 : ct == 2 ? 3 : ct == 4 ? 2 : 4; f.nch = (ct & 2) ? 3 : 1;
+        f.raw_off = raw_total; f.raw_len = (long long)H * (1 + (long long)W * f.bpp);
+        f.chunk0 = (int)chunks; f.nchunk = (int)((f.raw_len + kPdecAdlerChunk - 1) / kPdecAdlerChunk);
+        raw_total += (f.raw_len + 255) & ~255LL;
+        chunks += f.nchunk;
+        if (raw_total > kPdecMaxRaw) return fail(h, SPECMI_ERR_ARG, "the files' inflated streams hold more than 2^31 bytes");
+        px += (double)H * W;
+        in_bytes += (double)len;
+        std::memcpy(tab.data() + (size_t)i * (sizeof(PdecFile) / 4), &f, sizeof(f));
+        rects[i] = ByteRect{out_off, f.pitch, 3LL * W, H};
+    }
+    {   // no two rectangles share a byte: sorted by first byte, one is compared with those that start before it ends
+        std::vector<int> order((size_t)n);
+        for (int i = 0; i < n; ++i) order[i] = i;
+        std::sort(order.begin(), order.end(), [&](int x, int y) { return rects[x].off < rects[y].off; });
+        for (int i = 0; i < n; ++i)
+            for (int j = i + 1; j < n && rects[order[j]].off < rects[order[i]].end(); ++j)
+                if (rects_overlap(rects[order[i]], rects[order[j]]))
+                    return fail(h, SPECMI_ERR_ARG, "the output rectangles of files %d and %d share a byte", order[i], order[j]);
+    }
+    if (raw && raw_bytes < (size_t)raw_total)
+        return fail(h, SPECMI_ERR_ARG, "the raw output holds %zu bytes, these files' inflated streams take %lld", raw_bytes, raw_total);
+    hipStream_t s = (hipStream_t)stream;
+    size_t woff[3];
+    const size_t need = pdec_ws_layout(n, raw_total, chunks, woff);
+    const bool regrown = tab.size() * 4 > h->pdec_tab_bytes;
+    if (need > h->pdec_ws_bytes || regrown || tab != h->pdec_host) {
+        // both need a whole-device synchronise, which would invalidate a capture under way on this stream: ask first and leave it valid
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs != hipStreamCaptureStatusNone)
+            return fail(h, SPECMI_ERR_STATE, "new file records or a larger decoder workspace are not possible while the stream "
+                        "is being captured: run one eager call with these records first (nothing was enqueued)");
+    }
+    int rc;
+    if ((rc = grow_ragged(h, &h->pdec_ws, &h->pdec_ws_bytes, need, "the PNG decoder workspace"))) return rc;
+    if ((rc = grow_ragged(h, (void**)&h->pdec_tab, &h->pdec_tab_bytes, tab.size() * 4, "the PNG file table"))) return rc;
+    if (regrown || tab != h->pdec_host) {
+        // a decode enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
+        if (!regrown && (rc = sync_for_growth(h, "the PNG file table"))) return rc;
+        h->pdec_host.swap(tab);
+        HIPCHK(h, hipMemcpyAsync(h->pdec_tab, h->pdec_host.data(), h->pdec_host.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    char* ws = (char*)h->pdec_ws;
+    PdecArgs a{};
+    a.in = in_slab; a.out = out_slab; a.files = (const PdecFile*)h->pdec_tab; a.status = status;
+    a.raw = (unsigned char*)(ws + woff[0]); a.rec = (uint2*)(ws + woff[1]); a.sums = (uint2*)(ws + woff[2]);
+    a.n = n; a.chunks = (int)chunks;
+    LaunchCtx ctx{s, &h->prof, "png.decode"};
+    LAUNCHCHK(h, launch_png_decode(a, in_bytes, (double)raw_total, px * 3, ctx), "png_decode");
+    if (raw) HIPCHK(h, hipMemcpyAsync(raw, a.raw, (size_t)raw_total, hipMemcpyDeviceToDevice, s));
     return SPECMI_OK;
 }
 

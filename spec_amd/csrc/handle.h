@@ -208,6 +208,13 @@ struct specmi_handle {
     std::vector<int> jdec_host;         // host image of jdec_tab as last uploaded
     void* jdec_ws = nullptr;
     size_t jdec_ws_bytes = 0;
+    // specmi_png_decode: the file records, same growth and upload rules as ragged_tab; the inflated streams, the match records
+    // and the Adler sums (pdec_ws_layout), grows like ragged_tmp
+    int* pdec_tab = nullptr;
+    size_t pdec_tab_bytes = 0;
+    std::vector<int> pdec_host;         // host image of pdec_tab as last uploaded
+    void* pdec_ws = nullptr;
+    size_t pdec_ws_bytes = 0;
     SkWs sk;                            // split-K partial tiles + arrival counters (ensure_sk; never allocated under graph capture:
                                         // the warm-up call of a shape sizes it)
     std::vector<void*> sk_retired;      // outgrown split-K buffers, kept until destroy (captured graphs may still name them)

@@ -725,4 +725,40 @@ size_t jdec_ws_layout(long long blocks, long long plane_bytes, long long lanes, 
 int launch_jpeg_decode(const JdecArgs& a, long long blocks, long long lanes, int max_groups, double in_bytes, double out_bytes, int* passes,
                        const LaunchCtx& ctx);
 
+// ----------------------------------------------------------------------------------------
+// PNG decoder  (png_dec.hip)
+// ----------------------------------------------------------------------------------------
+constexpr int kPdecLanes = 256;           // lanes of the inflate workgroup = subsequences per window
+constexpr int kPdecSubBits = 512;         // a subsequence: 512 bits of the zlib stream, one lane
+constexpr int kPdecMaxRec = kPdecLanes * kPdecSubBits / 2;     // match records of one window at most: a match takes 2 bits or more
+constexpr int kPdecAdlerChunk = 32768;    // inflated bytes per workgroup of the Adler-32 stage
+constexpr long long kPdecMaxRaw = 1ll << 31;      // inflated bytes of one call at most (a record's destination is 32 bits)
+// One file of a specmi_png_decode call as the device reads it
+struct PdecFile {
+    long long stream_off, stream_len;     // the zlib stream in the input slab
+    long long out_off, pitch;
+    long long raw_off, raw_len;           // the inflated stream in the workspace (a multiple of 256) and its length H (1 + W bpp)
+    int H, W, bpp, nch;                   // bytes per pixel in the file (1, 3, 2, 4); channels the picture keeps (1 or 3)
+    int chunk0, nchunk;                   // its Adler chunks among the call's
+};
+static_assert(sizeof(PdecFile) % 8 == 0, "records follow each other in a table of ints");
+struct PdecArgs {
+    const unsigned char* in;
+    unsigned char* out;
+    const PdecFile* files;
+    int* status;                          // (n) one word per file, zeroed per call, bits joined with atomicOr
+    unsigned char* raw;                   // the inflated streams
+    uint2* rec;                           // (n, kPdecMaxRec) the current window's matches: destination - window's first byte, length | distance << 9
+    uint2* sums;                          // (chunks) Adler-32 partials
+    int n, chunks;
+};
+enum { PDEC_SUPPORTED = 0, PDEC_NOT_PNG, PDEC_TRUNCATED, PDEC_CRC, PDEC_DEPTH, PDEC_PALETTE, PDEC_INTERLACED, PDEC_ANIMATED, PDEC_CHUNK,
+       PDEC_SIZE, PDEC_TRAILING };
+// rule 1 on the host: -> a PDEC_ reason; on PDEC_SUPPORTED H, W, the colour type and the IDAT payload ranges [offset, length] (the
+// first max_ranges of them; *nranges: how many the file has)
+int png_probe(const unsigned char* d, size_t n, int* H, int* W, int* ctype, long long* ranges, int max_ranges, int* nranges);
+// byte offsets of raw, rec, sums in the workspace -> its size
+size_t pdec_ws_layout(int n, long long raw_bytes, long long chunks, size_t off[3]);
+int launch_png_decode(const PdecArgs& a, double in_bytes, double raw_bytes, double out_bytes, const LaunchCtx& ctx);
+
 }  // namespace specmi

@@ -520,6 +520,104 @@ def check_jpeg_decode(ranges, geom, outs, in_bytes, out_bytes, in_ptr=None, out_
     return ranges, outs
 
 
+# Which route the .png frames the flows READ take (preprocess.decode_frames): False = Pillow decodes every file on the host and the
+# raw frames go up (today's path, bit for bit), True = the files' zlib streams go up and specmi_png_decode inflates and unfilters
+# the supported ones where they land.  Same pixels either way.  The rule is the JPEG rule: True only when
+# scripts/bench_aux.py --only png_decode shows the device route ahead of 16 host threads in both content classes by more than the
+# host route's own spread between rounds.  It is not in both (profiles/png_decode_aux.json, MI355X): 64 frames of 1080p 215.0 - 222.5 against
+# 232.6 - 250.4 ms (spread 17.8), eight 1080 x 5760 three-panel pictures 476.6 - 480.1 against 134.0 - 142.1 ms (spread
+# 8.1), identical slabs.  The inflate stage loses it: 73 of the 112 ms the kernels take on the frames, 370 of 464 on the
+# pictures, where one wavefront resolves chains of dependent matches one at a time.  So the route is opt-in.
+PNG_DECODE_DEVICE_DEFAULT = False
+
+
+def flow_png_decode_device(png_decode_device=None) -> bool:
+    """``png_decode_device`` (the flow's private switch) decides, None = the default."""
+    return PNG_DECODE_DEVICE_DEFAULT if png_decode_device is None else bool(png_decode_device)
+
+
+def png_probe(data):
+    """``specmi_png_probe`` on a file's ``bytes`` -> (reason, H, W, colour_type, ranges): reason is a name of ``_lib.PNG_REASONS``
+    ('supported' or why ``specmi_png_decode`` refuses the file); ranges (k, 2) int64 [offset, length] of the IDAT payloads, which
+    joined are the file's zlib stream.  Host only: needs no device."""
+    data = bytes(data)
+    out = (C.c_int32 * 5)()
+    p = [C.cast(C.byref(out, 4 * i), _lib.c_int32_p) for i in range(5)]
+    ranges = np.zeros((64, 2), np.int64)
+    for _ in range(2):
+        rc = _lib.load().specmi_png_probe(data, len(data), p[0], p[1], p[2], p[3], ranges.ctypes.data_as(_lib.c_int64_p), ranges.shape[0], p[4])
+        if rc != _lib.OK:
+            raise ValueError('specmi_png_probe refused its arguments')
+        if out[4] <= ranges.shape[0]:
+            break
+        ranges = np.zeros((int(out[4]), 2), np.int64)
+    return _lib.PNG_REASONS[out[0]], int(out[1]), int(out[2]), int(out[3]), ranges[:int(out[4])].copy()
+
+
+def png_stream(data, ranges) -> bytes:
+    """The zlib stream of a file: its IDAT payloads (``png_probe``'s ranges) joined."""
+    return b''.join(bytes(data[int(o):int(o + n)]) for o, n in ranges)
+
+
+def png_takes_device(probe) -> bool:
+    """Does a file with this ``png_probe`` answer go to the device?  Supported, and not beyond ``Image.MAX_IMAGE_PIXELS``: such a
+    file takes the host route, so that Pillow's bomb warning or error stays what it is."""
+    from PIL import Image
+    limit = Image.MAX_IMAGE_PIXELS
+    return probe[0] == 'supported' and (limit is None or probe[1] * probe[2] <= limit)
+
+
+PNG_BPP = {0: 1, 2: 3, 4: 2, 6: 4}      # bytes per pixel of the colour types specmi_png_decode takes
+
+
+def check_png_decode(ranges, geom, outs, in_bytes, out_bytes, in_ptr=None, out_ptr=None, raw_bytes=None):
+    """Every refusal of ``specmi_png_decode`` (include/specmi.h) as ``ValueError``: ``ranges`` (n, 2) [offset, length] of the zlib
+    streams in the input slab, ``geom`` (n, 3) [H, W, colour type] as the probe gave them, ``outs`` (n, 2) [offset, pitch] of the
+    pictures in the output slab, the sizes of the two slabs and - where known - their addresses (None for either: a missing
+    slab); ``raw_bytes``: the size of the optional raw output.  -> (ranges int64, geom int32, outs int64, the bytes ``raw``
+    needs).  Needs no device."""
+    ranges, geom, outs = (np.ascontiguousarray(x, dtype=np.int64) for x in (ranges, geom, outs))
+    n = ranges.shape[0] if ranges.ndim == 2 else -1
+    if ranges.ndim != 2 or ranges.shape[1] != 2 or tuple(geom.shape) != (n, 3) or tuple(outs.shape) != (n, 2):
+        raise ValueError('files: ranges (n, 2), geom (n, 3) and outs (n, 2) with one row per file')
+    if not 1 <= n <= 65535:
+        raise ValueError(f'1 to 65535 files per call, got {n}')
+    if in_bytes is None or out_bytes is None or in_ptr == 0 or out_ptr == 0:
+        raise ValueError('the stream slab or the output slab is missing (a null pointer)')
+    if in_ptr is not None and out_ptr is not None and out_ptr < in_ptr + in_bytes and in_ptr < out_ptr + out_bytes:
+        raise ValueError('the stream slab and the output slab overlap')
+    off, length = ranges.T
+    H, W, ctype = geom.T
+    out_off, pitch = outs.T
+    if (off < 0).any() or (length < 0).any() or (off + length > in_bytes).any():
+        raise ValueError(f'a stream leaves the slab of {in_bytes} bytes')
+    if (length < 8).any():
+        raise ValueError('a zlib stream shorter than 8 bytes')
+    if ((H < 1) | (H > 32768) | (W < 1) | (W > 32768)).any() or not np.isin(ctype, tuple(PNG_BPP)).all():
+        raise ValueError('a picture of 1 .. 32768 pixels per side, colour type 0, 2, 4 or 6 (a file the probe refuses?)')
+    if (pitch < 3 * W).any():
+        raise ValueError('a pitch below 3 * W bytes')
+    if (out_off < 0).any() or (out_off + (H - 1) * pitch + 3 * W > out_bytes).any():
+        raise ValueError(f'a picture rectangle leaves the slab of {out_bytes} bytes')
+    bpp = np.array([PNG_BPP[int(c)] for c in ctype], np.int64)
+    need = int(((H * (1 + W * bpp) + 255) // 256 * 256).sum())
+    if need > 1 << 31:
+        raise ValueError('the files\' inflated streams hold more than 2^31 bytes')
+    if raw_bytes is not None and raw_bytes < need:
+        raise ValueError(f'the raw output holds {raw_bytes} bytes, these files\' inflated streams take {need}')
+    end = out_off + (H - 1) * pitch + 3 * W
+    order = np.argsort(out_off, kind='stable')
+    for k, i in enumerate(order):                                # rectangles with gaps: a byte test per pair that may meet
+        for j in order[k + 1:]:
+            if out_off[j] >= end[i]:
+                break
+            rows_i = out_off[i] + pitch[i] * np.arange(H[i])
+            rows_j = out_off[j] + pitch[j] * np.arange(H[j])
+            if ((rows_i[:, None] < rows_j[None, :] + 3 * W[j]) & (rows_j[None, :] < rows_i[:, None] + 3 * W[i])).any():
+                raise ValueError('two picture rectangles share a byte')
+    return ranges, geom.astype(np.int32), outs, need
+
+
 EVAL_STEP_OUTPUTS = ('err_sel', 'pa_err_sel', 'err_k', 'pa_err_k', 'v2v')
 EVAL_STEP_MAX_JOINTS = 32      # kMaxJ of spec_amd/csrc/eval.hip: the joints are held on chip
 
@@ -1315,6 +1413,55 @@ class Engine:
         slab = torch.from_numpy(host.copy()).to(self.device)
         out_slab = torch.empty(int(size.sum()), device=self.device, dtype=torch.uint8)
         status, _ = self.jpeg_decode_into(host, slab, ranges, geom, out_slab, np.stack([offsets, 3 * geom[:, 1]], axis=1))
+        return out_slab, offsets, [(int(h), int(w)) for h, w, _ in geom], status
+
+    def png_decode_into(self, slab, ranges, geom, out_slab, outs, status=None, raw=None):
+        """``specmi_png_decode``: the zlib streams at ``ranges`` (n, 2) [offset, length] of ``slab`` (1-D uint8 on the engine
+        device; every file's IDAT payloads joined, ``png_stream``), of ``geom`` (n, 3) [H, W, colour type] as ``png_probe`` gave
+        them, inflated and unfiltered into the rectangles ``outs`` (n, 2) [offset, pitch] of ``out_slab`` (1-D uint8, same device,
+        not overlapping).  -> ``status`` (n,) int32 on the device, given or new: 0 where the file's pixels are Pillow's.  ``raw``:
+        a uint8 device tensor that receives the inflated streams, each from a multiple of 256.  Everything the arrays decide is
+        checked before the library is called (``check_png_decode``)."""
+        d = self.device
+        for name, x in (('slab', slab), ('out_slab', out_slab)):
+            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
+                raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
+        if raw is not None and (not isinstance(raw, torch.Tensor) or raw.device != d or raw.dtype != torch.uint8 or not raw.is_contiguous()):
+            raise ValueError('raw must be a contiguous uint8 tensor on the engine device')
+        ranges, geom, outs, _ = check_png_decode(ranges, geom, outs, slab.numel(), out_slab.numel(), slab.data_ptr(), out_slab.data_ptr(),
+                                                 None if raw is None else raw.numel())
+        n = int(ranges.shape[0])
+        if status is None:
+            status = torch.empty(n, device=d, dtype=torch.int32)
+        elif not isinstance(status, torch.Tensor) or status.device != d or status.dtype != torch.int32 or tuple(status.shape) != (n,) or not status.is_contiguous():
+            raise ValueError('status must be a contiguous (n,) int32 tensor on the engine device')
+        _lib.check(self.h, self.lib.specmi_png_decode(
+            self.h, _ptr(slab), slab.numel(), ranges.ctypes.data_as(_lib.c_int64_p), geom.ctypes.data_as(_lib.c_int32_p), _ptr(out_slab),
+            out_slab.numel(), outs.ctypes.data_as(_lib.c_int64_p), n, _ptr(status), _ptr(raw), 0 if raw is None else raw.numel(),
+            self._stream()))
+        return status
+
+    def png_decode(self, files):
+        """``files``: a list of ``bytes``, every one a file ``png_probe`` calls supported -> (slab, offsets, sizes, status): the
+        pictures back to back in one 1-D uint8 device slab with their (n,) int64 byte offsets and [(H, W)] - the triple
+        ``preprocess.pack_frames`` builds from Pillow's decodes of the same files, bit for bit where ``status`` (n,) int32 on the
+        device is 0 (include/specmi.h states the contract).  One upload of the files' zlib streams, one ``specmi_png_decode``."""
+        files = [bytes(f) for f in files]
+        if not files:
+            raise ValueError('at least one file')
+        probes = [png_probe(f) for f in files]
+        for i, p in enumerate(probes):
+            if p[0] != 'supported':
+                raise ValueError(f'file {i} is not a supported PNG file ({p[0]})')
+        streams = [png_stream(f, p[4]) for f, p in zip(files, probes)]
+        length = np.array([len(s) for s in streams], np.int64)
+        ranges = np.stack([np.concatenate([[0], np.cumsum(length)[:-1]]), length], axis=1)
+        geom = np.array([p[1:4] for p in probes], np.int64)
+        size = 3 * geom[:, 0] * geom[:, 1]
+        offsets = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64)
+        slab = torch.from_numpy(np.frombuffer(b''.join(streams), np.uint8).copy()).to(self.device)
+        out_slab = torch.empty(int(size.sum()), device=self.device, dtype=torch.uint8)
+        status = self.png_decode_into(slab, ranges, geom, out_slab, np.stack([offsets, 3 * geom[:, 1]], axis=1))
         return out_slab, offsets, [(int(h), int(w)) for h, w, _ in geom], status
 
     def _cam_args(self, B, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h):

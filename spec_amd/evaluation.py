@@ -99,6 +99,7 @@ class EvalDataset:
         self.imgname = self.data['imgname']
         self.n = len(self.imgname)
         self._jpeg_decode_device = None     # True: the batch's .jpg files go up as bytes and are decoded on the device (preprocess.decode_frames; same bits); None = engine.JPEG_DECODE_DEVICE_DEFAULT
+        self._png_decode_device = None      # the same for the batch's .png files (specmi_png_decode; same bits); None = engine.PNG_DECODE_DEVICE_DEFAULT
         self._ragged_crops = None     # True: one slab, one upload, one ragged crop launch per batch; False: one of each per sample (same bits)
 
     def __len__(self):
@@ -146,7 +147,7 @@ class EvalDataset:
         d = self.data
         paths = [os.path.join(self.img_dir, str(self.imgname[i])) for i in idx]
         if flow_ragged_crops(self._ragged_crops):     # the batch's images in one slab, one upload, one launch into the batch tensor
-            slab, offsets, shapes = decode_frames(paths, device, self._jpeg_decode_device)     # off: pack_frames of read_image_rgb's decodes
+            slab, offsets, shapes = decode_frames(paths, device, self._jpeg_decode_device, self._png_decode_device)     # off: pack_frames of read_image_rgb's decodes
             img = dataset_crops_ragged(slab, offsets, shapes, np.arange(len(paths), dtype=np.int32), d['center'][idx], d['scale'][idx],
                                        img_res, dtype=dtype)                                                    # cam_dataset.py:367-377
         else:

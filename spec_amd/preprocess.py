@@ -146,33 +146,61 @@ def _host_rgb(item):
         return np.array(im.convert('RGB'))
 
 
-def decode_frames(paths, device, jpeg_decode_device=None):
+def decode_frames(paths, device, jpeg_decode_device=None, png_decode_device=None):
     """The frames of a batch from their files -> the triple ``pack_frames([Pillow's decode of each], device)`` returns, bit for
     bit.  ``paths``: per frame a path, a file's ``bytes`` already read, or a decoded (H,W,3) uint8 array.  ``jpeg_decode_device``
     (None = ``engine.JPEG_DECODE_DEVICE_DEFAULT``): False is exactly that host path; True sends the baseline .jpg / .jpeg files
     ``engine.jpeg_probe`` calls supported up as BYTES in one copy and decodes them in one ``specmi_jpeg_decode`` into their
-    places of the slab.  Every other frame - a .png, a file the probe refuses, a file whose status came back non-zero, an array -
-    is decoded by Pillow as before and uploaded into its place of the same slab (a damaged file raises there what it raises
-    today)."""
+    places of the slab.  ``png_decode_device`` (None = ``engine.PNG_DECODE_DEVICE_DEFAULT``) does the same for the .png files
+    ``engine.png_probe`` calls supported: their zlib streams go up and one ``specmi_png_decode`` writes them into their places of
+    the same slab.  Every other frame - a file its probe refuses, a file whose status came back non-zero, an array - is decoded
+    by Pillow as before and uploaded into its place of the same slab (a damaged file raises there what it raises today)."""
     import numpy as np
-    from .engine import flow_jpeg_decode_device, is_jpeg_name, jpeg_probe
+    from .engine import (flow_jpeg_decode_device, flow_png_decode_device, is_jpeg_name, is_png_name, jpeg_probe, png_probe, png_stream,
+                         png_takes_device)
     items = list(paths)
     if not items:
         raise ValueError('at least one frame')
-    if not flow_jpeg_decode_device(jpeg_decode_device):
+    jpeg_on, png_on = flow_jpeg_decode_device(jpeg_decode_device), flow_png_decode_device(png_decode_device)
+    if not jpeg_on and not png_on:
         return pack_frames([_host_rgb(p) for p in items], device)
     dev = torch.device(device)
     eng = _engine(dev)
-    files, sizes, host = {}, [None] * len(items), {}
-    for i, p in enumerate(items):
-        if isinstance(p, (bytes, bytearray)) or (not isinstance(p, np.ndarray) and is_jpeg_name(p)):
-            if not isinstance(p, (bytes, bytearray)):
+    files, pngs, sizes, host = {}, {}, [None] * len(items), {}
+
+    def classify(p):
+        """-> ('png', file, probe, zlib stream) | ('jpeg', file, probe) | ('host', item): reads the file; a PNG's CRC walk and the
+        join of its IDAT payloads are done here, so that a batch's files share the host's threads as the host route's decodes do"""
+        is_bytes = isinstance(p, (bytes, bytearray))
+        named = not is_bytes and not isinstance(p, np.ndarray)
+        if is_bytes or (named and ((jpeg_on and is_jpeg_name(p)) or (png_on and is_png_name(p)))):
+            if not is_bytes:
                 with open(p, 'rb') as f:
                     p = f.read()
-            probe = jpeg_probe(p)
-            if probe[0] == 'supported':
-                files[i], sizes[i] = (bytes(p), probe), (probe[1], probe[2])
-                continue
+            if png_on and p[:4] == b'\x89PNG':
+                probe = png_probe(p)
+                if png_takes_device(probe):
+                    return 'png', bytes(p), probe, png_stream(p, probe[4])
+            elif jpeg_on:
+                probe = jpeg_probe(p)
+                if probe[0] == 'supported':
+                    return 'jpeg', bytes(p), probe
+        return 'host', p
+
+    if png_on and len(items) > 1:
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=min(16, len(items))) as ex:
+            kinds = list(ex.map(classify, items))
+    else:
+        kinds = [classify(p) for p in items]
+    for i, k in enumerate(kinds):
+        if k[0] == 'png':
+            pngs[i], sizes[i] = k[1:], (k[2][1], k[2][2])
+            continue
+        if k[0] == 'jpeg':
+            files[i], sizes[i] = k[1:], (k[2][1], k[2][2])
+            continue
+        p = k[1]
         host[i] = _host_rgb(p)
         if host[i].dtype != np.uint8 or host[i].ndim != 3 or host[i].shape[2] != 3:
             raise ValueError('frames must be (H,W,3) uint8 RGB')
@@ -193,6 +221,25 @@ def decode_frames(paths, device, jpeg_decode_device=None):
                 host[i] = _host_rgb(files[i][0])
                 if tuple(host[i].shape) != sizes[i] + (3,):
                     raise ValueError('a damaged file decodes to another size on the host')
+    if pngs:
+        order = sorted(pngs)
+        streams = [pngs[i][2] for i in order]
+        short = [i for i, s in zip(order, streams) if len(s) < 8]             # no zlib stream at all: the host route decides
+        order, streams = [i for i in order if i not in short], [s for s in streams if len(s) >= 8]
+        for i in short:
+            host[i] = _host_rgb(pngs[i][0])
+        if order:
+            length = np.array([len(s) for s in streams], np.int64)
+            ranges = np.stack([np.concatenate([[0], np.cumsum(length)[:-1]]), length], axis=1)
+            geom = np.array([pngs[i][1][1:4] for i in order], np.int64)
+            blob = torch.from_numpy(np.frombuffer(bytearray().join(streams), np.uint8)).to(eng.device)
+            status = eng.png_decode_into(blob, ranges, geom, slab, np.stack([offsets[order], 3 * geom[:, 1]], axis=1))
+            for i, st in zip(order, status.cpu().tolist()):
+                if st:                                            # a stream that does not satisfy RFC 1950 / 1951: the host route decides
+                    host[i] = _host_rgb(pngs[i][0])
+    for i, fr in host.items():
+        if tuple(fr.shape) != tuple(sizes[i]) + (3,):
+            raise ValueError('a damaged file decodes to another size on the host')
     for i, fr in host.items():
         slab[int(offsets[i]):int(offsets[i] + nbytes[i])].copy_(torch.from_numpy(np.ascontiguousarray(fr)).reshape(-1))
     return slab, offsets, [(int(h), int(w)) for h, w in sizes]

@@ -24,7 +24,7 @@ from . import assets, cam_utils, io_formats, render
 from .checkpoint import load_pretrained_model, read_checkpoint
 from .modules import HMR, CameraRegressorNetwork
 from .engine import (flow_image_dtype, flow_jpeg_decode_device, flow_jpeg_device, flow_png_device, flow_ragged_crops, flow_render_batch, image_tensor,
-                     is_jpeg_name, is_png_name, jpeg_probe)
+                     is_jpeg_name, is_png_name, jpeg_probe, flow_png_decode_device, png_probe, png_takes_device)
 from .preprocess import camcalib_transform, crop_detections, crop_detections_ragged, decode_frames, pack_frames
 
 CAMCALIB_CKPT = 'data/camcalib/checkpoints/camcalib_sa_biased_l2.ckpt'     # scripts/camcalib_demo.py:39
@@ -54,14 +54,17 @@ def _read_rgb(path):
         return np.array(im.convert('RGB'))
 
 
-def _read_frame(path):
-    """A decode-ahead thread's work with the device decode on: the bytes of a .jpg / .jpeg file ``specmi_jpeg_decode`` takes
-    (``engine.jpeg_probe``); every other frame - a .png, a progressive or greyscale file - is decoded here, on the thread, as before."""
-    if not is_jpeg_name(path):
+def _read_frame(path, jpeg=True, png=False):
+    """A decode-ahead thread's work with a device decode on: the bytes of a .jpg / .jpeg file ``specmi_jpeg_decode`` takes
+    (``engine.jpeg_probe``; ``jpeg``) or of a .png file ``specmi_png_decode`` takes (``engine.png_probe``; ``png``); every other
+    frame - a progressive or greyscale JPEG, a palette PNG - is decoded here, on the thread, as before."""
+    if not ((jpeg and is_jpeg_name(path)) or (png and is_png_name(path))):
         return _read_rgb(path)
     with open(path, 'rb') as f:
         data = f.read()
-    return data if jpeg_probe(data)[0] == 'supported' else _read_rgb(path)
+    if data[:4] == b'\x89PNG':
+        return data if png and png_takes_device(png_probe(data)) else _read_rgb(path)
+    return data if jpeg and jpeg_probe(data)[0] == 'supported' else _read_rgb(path)
 
 
 def list_images(image_folder):
@@ -112,6 +115,7 @@ class SPECTester:
         self._camcalib = getattr(args, 'camcalib_model', None)
         self._fp32_crops = None       # False: NHWC8 fp16 crops for a model at fp16; True: fp32 crops + in-trunk conversion (same bits)
         self._jpeg_decode_device = None     # True: on the ragged route without pictures the frames' files go up as bytes and are decoded on the device (preprocess.decode_frames; same bits); None = engine.JPEG_DECODE_DEVICE_DEFAULT
+        self._png_decode_device = None      # the same for the frames' .png files (specmi_png_decode; same bits); None = engine.PNG_DECODE_DEVICE_DEFAULT
         self._ragged_crops = None     # True: a flush's frames in one slab, one upload, one ragged crop launch; False: one of each per frame (same bits)
         self._render_batch = None     # True: a flush's pictures in one render_image_groups call; False: one render_image_group per frame (same bytes)
         self._jpeg_device = None      # True: .jpg / .jpeg pictures are encoded on the device and only the files' bytes come down (same bytes)
@@ -151,7 +155,8 @@ class SPECTester:
         bytes instead of RGB arrays: ``decode_frames`` takes either and gives the same slab."""
         import joblib
         k = pending[-1][1] + pending[-1][2]
-        slab, offsets, sizes = decode_frames([rgb for rgb, _ in held], self.device, any(isinstance(rgb, bytes) for rgb, _ in held))
+        slab, offsets, sizes = decode_frames([rgb for rgb, _ in held], self.device, any(isinstance(rgb, bytes) for rgb, _ in held),
+                                             any(isinstance(rgb, bytes) and rgb[:4] == b'\x89PNG' for rgb, _ in held))
         counts = [n for _, _, n in pending]
         crop_detections_ragged(slab, offsets, sizes, np.repeat(np.arange(len(held), dtype=np.int32), counts),
                                np.concatenate([dets for _, dets in held]), scale=1.0, crop_size=res, dtype=crop_dtype,
@@ -340,7 +345,8 @@ class SPECTester:
         nthreads = int(getattr(self.args, 'decode_threads', 4) or 1)
         # pictures are drawn on the decoded host frame (shown): with them the host decode stays; without, the threads only read the
         # bytes of the files the device decodes
-        read = _read_frame if ragged and not render and flow_jpeg_decode_device(self._jpeg_decode_device) else _read_rgb
+        jdec, pdec = flow_jpeg_decode_device(self._jpeg_decode_device), flow_png_decode_device(self._png_decode_device)
+        read = (lambda path: _read_frame(path, jdec, pdec)) if ragged and not render and (jdec or pdec) else _read_rgb
 
         def decoded(ex):
             """(todo entry, RGB array) in order, at most 2 x nthreads frames decoded ahead of the consumer"""
