@@ -352,6 +352,39 @@ int specmi_smpl_forward(specmi_handle* h, const float* rotmat, const float* beta
                         float* vertices, float* joints3d, float* joints2d, float* cam_t,
                         void* stream);
 
+/* The vector-Jacobian product of specmi_smpl_forward, for both head modes (the handle's "use_cam": SMPLCamHead with the six
+ * camera arguments, else SMPLHead weak perspective with normalize_joints2d) - what torch.autograd computes through
+ * rot-matrix LBS + 49 joints + convert_pare_to_full_img_cam / convert_weak_perspective_to_perspective + perspective_projection.
+ *   inputs: the forward's own - rotmat (B,24,3,3), betas (B,10), cam (B,3) and, with use_cam, cam_rotmat (B,3,3),
+ *     cam_intrinsics (B,3,3), bbox_scale (B), bbox_center (B,2), img_w (B), img_h (B) (not read otherwise, may be NULL);
+ *   upstream gradients, dense fp32: g_vertices (B,V,3), g_joints3d (B,49,3), g_joints2d (B,49,2), g_cam_t (B,3).  Any of them
+ *     may be NULL and counts as zero - the result is the same bits as with an all-zero tensor - but not all four;
+ *   outputs, dense fp32: g_rotmat (B,24,3,3), g_betas (B,10), g_cam (B,3).  Any may be NULL (not wanted), not all three; with
+ *     only g_cam wanted the two contractions over the vertices are not launched.  The camera arguments get no gradient.
+ * Stateless: the call recomputes the forward from its arguments into the handle's scratch and reads nothing an earlier call
+ * left there.  Works on SPECMI_MODEL_SMPL and SPECMI_MODEL_HMR handles.  Its workspace (the vertex gradient (B,V,3) and
+ * ceil(V / 64) partial slabs of 640 x 32 floats per 32 images) grows on first use of a batch size; after one eager call of a
+ * shape nothing is allocated and the call can be captured into a graph.
+ * Deterministic: no float atomics; the sums over the vertices are folded in an order fixed by V alone (chunks of 64 vertices,
+ * in order), joint_map entries that repeat add in joint order, so every run gives the same bits and an image's gradients do
+ * not depend on the batch it is in.
+ * Refusals (SPECMI_ERR_ARG, nothing launched): B <= 0; rotmat / betas / cam NULL; all upstream gradients NULL; all outputs
+ * NULL; use_cam and one of the six camera arguments NULL. */
+int specmi_smpl_backward(specmi_handle* h, const float* rotmat, const float* betas, const float* cam, int B,
+                         const float* cam_rotmat, const float* cam_intrinsics, const float* bbox_scale,
+                         const float* bbox_center, const float* img_w, const float* img_h,
+                         const float* g_vertices, const float* g_joints3d, const float* g_joints2d, const float* g_cam_t,
+                         float* g_rotmat, float* g_betas, float* g_cam, void* stream);
+
+/* The head's rot6d -> rotation matrix on its own (pare.utils.geometry.rot6d_to_rotmat; the regressor runs the same function
+ * inside its last kernel, same bits): x6d (N,6) -> rotmat (N,3,3).  Any handle.  Refuses NULL pointers and N <= 0. */
+int specmi_rot6d_forward(specmi_handle* h, const float* x6d, int N, float* rotmat, void* stream);
+
+/* The backward of the head's rot6d -> rotation matrix (Gram-Schmidt with columns b1, b2, b3; x6d viewed (N,3,2), element
+ * [i, c] = row i of column c; F.normalize's eps = 1e-12 kept: below it the divisor is a constant): x6d (N,6), g_rotmat
+ * (N,3,3) -> g_x6d (N,6).  One lane per rotation; any handle.  Refuses NULL pointers and N <= 0 (SPECMI_ERR_ARG). */
+int specmi_rot6d_backward(specmi_handle* h, const float* x6d, const float* g_rotmat, int N, float* g_x6d, void* stream);
+
 /* The body model WITHOUT the 49-joint wrapper - smplx.SMPL.forward as the evaluation code calls it (`smpl_native` /
  * `body_model` / `body_model_orig`, spec/trainer.py:71-86,249-254, spec/utils/compute_error.py:118-160): `pose` is
  * (B,24,3,3) rotation matrices (pose2rot=False) or, with pose_is_axis_angle != 0, (B,72) axis-angle vectors
@@ -1031,7 +1064,7 @@ int specmi_rotate_points(specmi_handle* h, const float* R, const float* points, 
 /* ---- SPEC's loss modules, forward value ---------------------------------------------------------- */
 
 /* HMRLoss.forward (spec/losses.py:59-141; mode = SPECMI_HMR_LOSS) and HMRCamLoss.forward (:171-271; mode = SPECMI_HMR_CAM_LOSS)
- * as an evaluation quantity: the value only, no gradient.  All pointers are device pointers, fp32 unless stated.
+ * as an evaluation quantity: the value only (its gradient: specmi_hmr_loss_backward below).  All pointers are device pointers, fp32 unless stated.
  *   prediction (the dict of HMR.forward): pred_pose (B,24,3,3), pred_shape (B,10), pred_cam (B,3), joints3d (B,49,3) =
  *     smpl_joints3d, joints2d (B,49,2) = smpl_joints2d, vertices (B,V,3) = smpl_vertices;
  *   ground truth (the batch of spec/dataset/cam_dataset.py): pose (B,72) axis-angle, betas (B,10), pose_conf (B,24), pose_3d
@@ -1081,6 +1114,31 @@ int specmi_hmr_loss(specmi_handle* h, int mode, const float* pred_pose, const fl
                     const int32_t* has_smpl, const int32_t* has_pose_3d, const float* orig_shape, const float* scale, int B, int V,
                     float w_shape, float w_keypoint, float w_pose, float w_smpl_part, float w_beta, float w_openpose, float w_gt,
                     float w_loss, float* terms, int32_t* counts, float* means, void* stream);
+
+/* The gradient of specmi_hmr_loss's seven means with respect to the six prediction tensors - what torch.autograd computes through
+ * the reference's HMRLoss / HMRCamLoss.  The ground truth is never differentiated.
+ *   inputs: mode, every tensor, B, V and the eight weights exactly as given to specmi_hmr_loss, plus what that call produced:
+ *     terms (6, B) and counts (2 int32), both required - the pose term is a product of two batch means, so its gradient needs the
+ *     batch sum of pose_conf (row 3 of terms over the images with has_smpl) and Nv;
+ *   g_means (7): the upstream gradient of means.  The effective coefficient of term k (0 .. 5) is g_means[k] + w_loss *
+ *     g_means[6], so any entry of the reference's loss_dict may be backpropagated, not only the total;
+ *   outputs, dense fp32, each written in full: g_pred_pose (B,24,3,3), g_pred_shape (B,10), g_pred_cam (B,3) (columns 1 and 2 are
+ *     0), g_joints3d (B,49,3) (non-zero only for joints 25 .. 48; joints 27 and 28 - 2 and 3 of those 24 - also carry what the
+ *     pelvis takes back from the other 22), g_joints2d (B,49,2) (mode 1: through the normalisation to [-1, 1] and the
+ *     (W, H) / (scale * 200) rescale), g_vertices (B,V,3) (the slope of |x|: -k, 0 at exactly 0, +k; written as 16-byte chunks
+ *     counted from the image's first float, as the forward reads them).  Any output may be NULL, not all six.
+ * An image masked out of a term gets exactly +0 there; Nv = 0 / Np = 0 give zeros, never NaN; a zero confidence gives 0;
+ * gt_vertices NULL (w_shape == 0) gives g_vertices = 0.
+ * One launch, one workgroup per image, no atomics, nothing allocated (capturable); any handle, committed or not.
+ * Refused (SPECMI_ERR_ARG), launching nothing: what specmi_hmr_loss refuses; terms, counts or g_means NULL; every output NULL. */
+int specmi_hmr_loss_backward(specmi_handle* h, int mode, const float* pred_pose, const float* pred_shape, const float* pred_cam,
+                             const float* joints3d, const float* joints2d, const float* vertices, const float* pose, const float* betas,
+                             const float* pose_conf, const float* pose_3d, const float* keypoints, const float* gt_vertices,
+                             const int32_t* has_smpl, const int32_t* has_pose_3d, const float* orig_shape, const float* scale, int B, int V,
+                             float w_shape, float w_keypoint, float w_pose, float w_smpl_part, float w_beta, float w_openpose, float w_gt,
+                             float w_loss, const float* terms, const int32_t* counts, const float* g_means, float* g_pred_pose,
+                             float* g_pred_shape, float* g_pred_cam, float* g_joints3d, float* g_joints2d, float* g_vertices,
+                             void* stream);
 
 /* Which execution plan a trunk forward of (B, 3, H, W) takes under the handle's current options ("plan" and its thresholds):
  * *mode = 0 throughput, 1 latency, 2 single; pair != 0: as specmi_trunk_forward_pair decides (the FIRST handle's options).  Callers

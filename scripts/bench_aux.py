@@ -21,6 +21,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only horizon_panel      # panel 0 of eight 1080p frames: Pillow on the host against specmi_draw_marks -> profiles/horizon_panel_aux.json
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
     python scripts/bench_aux.py --only eval_step          # the validation step's one launch against eval_mesh + eval_joints (means only) -> profiles/eval_step_aux.json
+    python scripts/bench_aux.py --smpl-backward           # the SMPL head's forward, its backward and the loss backward at B = 256, V = 6890, next to torch autograd over the oracle chain on the same device -> profiles/smpl_backward_aux.json
     python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
 import argparse
@@ -985,9 +986,88 @@ def png_decode_section(eng, a):
     return rows
 
 
+def smpl_backward_section(a):
+    """``specmi_smpl_forward``, ``specmi_smpl_backward`` and ``specmi_hmr_loss_backward`` at B = ``--batch`` (256), V = 6890
+    (SMPLCamHead mode), and torch's own autograd (forward + backward) over the oracle chain - oracle/smpl.py, oracle/geometry.py,
+    fp32 - moved to the same device.  HIP events around ``iters`` back-to-back calls after a warm-up of the same calls, the four
+    alternated in this process, 3 rounds; then the backward's kernels by the library profiler."""
+    from oracle.geometry import convert_pare_to_full_img_cam
+    from oracle.smpl import SMPLOracle
+    from spec_amd import assets, differentiable
+    from spec_amd.cam_utils import _engine
+    dev = torch.device('cuda', 0)
+    B, V = a.batch, 6890
+    model = assets.smpl_model()
+    eng, leng = differentiable._smpl_engine(dev, model, True, 224, 5000.), _engine(dev)
+    rng = np.random.default_rng(0)
+    f = lambda *shape, std=1.0: torch.from_numpy((rng.standard_normal(shape) * std).astype(np.float32)).to(dev)
+    rot = torch.linalg.qr(f(B, 24, 3, 3))[0].contiguous()
+    betas, cam = f(B, 10, std=0.8), torch.cat([0.6 + 0.5 * torch.rand(B, 1, device=dev), f(B, 2, std=0.1)], 1)
+    K = torch.zeros(B, 3, 3, device=dev)
+    K[:, 0, 0] = K[:, 1, 1] = 1000.
+    K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = 960., 540., 1.
+    camera = (torch.eye(3, device=dev).repeat(B, 1, 1), K, 0.8 + torch.rand(B, device=dev), torch.tensor([[960., 540.]], device=dev).repeat(B, 1),
+              torch.full((B,), 1920., device=dev), torch.full((B,), 1080., device=dev))
+    ups = dict(g_vertices=f(B, V, 3, std=0.01), g_joints3d=f(B, 49, 3, std=0.1), g_joints2d=f(B, 49, 2, std=0.001), g_cam_t=f(B, 3, std=0.1))
+    pred = {'pred_pose': rot, 'pred_shape': betas, 'pred_cam': cam, 'smpl_joints3d': f(B, 49, 3), 'smpl_joints2d': f(B, 49, 2) * 100,
+            'smpl_vertices': f(B, V, 3)}
+    gt = {'pose': f(B, 72) * 0.3, 'betas': f(B, 10), 'pose_conf': torch.ones(B, 24, device=dev), 'pose_3d': f(B, 24, 4),
+          'keypoints_orig': f(B, 49, 3).abs() * 100, 'vertices': f(B, V, 3), 'has_smpl': torch.ones(B, dtype=torch.int32, device=dev),
+          'has_pose_3d': torch.ones(B, dtype=torch.int32, device=dev), 'orig_shape': torch.full((B, 2), 480., device=dev),
+          'scale': torch.ones(B, device=dev)}
+    wl = [1., 5., 1., 1., 0.001, 0., 1., 60.]
+    res = leng.hmr_loss(1, pred, gt, wl)
+    gm = torch.tensor([0., 0, 0, 0, 0, 0, 1], device=dev)
+    oracle = SMPLOracle(model).to(dev)
+
+    def torch_autograd():
+        with torch.enable_grad():
+            leaves = [t.detach().requires_grad_(True) for t in (rot, betas, cam)]
+            verts, j3d = oracle(leaves[1], leaves[0])
+            cam_t = convert_pare_to_full_img_cam(pare_cam=leaves[2], bbox_height=camera[2] * 200., bbox_center=camera[3], img_w=camera[4],
+                                                 img_h=camera[5], focal_length=K[:, 0, 0], crop_res=224)
+            pts = torch.einsum('bij,bkj->bki', camera[0], j3d) + cam_t.unsqueeze(1)
+            j2d = torch.einsum('bij,bkj->bki', K, pts / pts[:, :, -1:])[:, :, :-1]
+            obj = (verts * ups['g_vertices']).sum() + (j3d * ups['g_joints3d']).sum() + (j2d * ups['g_joints2d']).sum() + (cam_t * ups['g_cam_t']).sum()
+            torch.autograd.grad(obj, leaves)
+
+    calls = {'smpl_forward': lambda: eng.smpl(rot, betas, cam, *camera),
+             'smpl_backward': lambda: eng.smpl_backward(rot, betas, cam, *camera, **ups),
+             'hmr_loss_backward': lambda: leng.hmr_loss_backward(1, pred, gt, wl, res, gm),
+             'torch_autograd_forward_and_backward': torch_autograd}
+
+    def ms_per_call(fn):
+        for _ in range(5):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+    rounds = {k: [] for k in calls}
+    for _ in range(3):                                              # alternated: all see the same clocks and the same neighbours
+        for k, fn in calls.items():
+            rounds[k].append(ms_per_call(fn))
+    med = {k: float(np.median(v)) for k, v in rounds.items()}
+    kern = {k: {'ms_per_launch': round(v[0], 5), 'TFLOPs': round(v[2] / (v[0] * 1e-3) / 1e12, 2) if v[2] else None}
+            for k, v in timed(eng, calls['smpl_backward'], a.iters).items()}
+    row = {'workload': f'B = {B}, V = {V}, SMPLCamHead mode; smpl_backward recomputes the forward (its three kernels are part of its time); '
+                       'hmr_loss_backward: HMRCamLoss, shape_loss_weight 1, all six gradients',
+           'ms_round_values': {k: [round(x, 5) for x in v] for k, v in rounds.items()}, 'ms_median': {k: round(v, 5) for k, v in med.items()},
+           'spread_between_rounds_ms': {k: round(max(v) - min(v), 5) for k, v in rounds.items()},
+           'backward_over_forward': round(med['smpl_backward'] / med['smpl_forward'], 3),
+           'torch_autograd_over_forward_plus_backward': round(med['torch_autograd_forward_and_backward'] / (med['smpl_forward'] + med['smpl_backward']), 3),
+           'smpl_backward_kernels_by_the_library_profiler': kern}
+    print(json.dumps(row, indent=1))
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'smpl_backward'], default=None, help='run one section only')
+    ap.add_argument('--smpl-backward', dest='only', action='store_const', const='smpl_backward', help='the same as --only smpl_backward')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -1004,6 +1084,15 @@ def main():
     g = torch.Generator().manual_seed(0)
     B = a.batch
     table = []
+
+    if a.only == 'smpl_backward':
+        from spec_amd import _lib
+        row = smpl_backward_section(a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the same calls; 3 alternated rounds; '
+                       'kernels: per-launch HIP events (library profiler)', 'smpl_backward': row, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
 
     def add(name, workload, res, per_unit=None):
         for k, (ms, by, fl, n) in res.items():

@@ -131,6 +131,11 @@ PROTOTYPES = {
                                       C.c_void_p]),
     'specmi_smpl_native': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p]),
+    # (h, rotmat, betas, cam, B, 6 camera arguments, 4 upstream gradients, g_rotmat, g_betas, g_cam, stream)
+    'specmi_smpl_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p] * 4 +
+                             [C.c_void_p] * 3 + [C.c_void_p]),
+    'specmi_rot6d_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'specmi_rot6d_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'specmi_conv2d': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
@@ -254,6 +259,9 @@ PROTOTYPES = {
     # (h, mode, 6 prediction tensors, 6 ground-truth tensors, has_smpl, has_pose_3d, orig_shape, scale, B, V, 8 weights, terms, counts, means, stream)
     'specmi_hmr_loss': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 16 + [C.c_int, C.c_int] + [C.c_float] * 8 +
                         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (h, mode, the 16 tensors of specmi_hmr_loss, B, V, 8 weights, terms, counts, g_means, 6 gradients, stream)
+    'specmi_hmr_loss_backward': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 16 + [C.c_int, C.c_int] + [C.c_float] * 8 +
+                                 [C.c_void_p] * 3 + [C.c_void_p] * 6 + [C.c_void_p]),
     'specmi_rotate_points': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     'specmi_trunk_plan': (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     'specmi_sync_status': (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),

@@ -798,6 +798,7 @@ int specmi_destroy(specmi_handle* h) {
     if (h->sk.cnt) (void)hipFree(h->sk.cnt);
     free_pool(h->sk_retired);
     free_pool(h->ws_retired);
+    if (h->smpl_bwd_ws) (void)hipFree(h->smpl_bwd_ws);
     if (h->resize_tab) (void)hipFree(h->resize_tab);
     if (h->ragged_tab) (void)hipFree(h->ragged_tab);
     if (h->ragged_tmp) (void)hipFree(h->ragged_tmp);
@@ -2694,6 +2695,102 @@ int specmi_hmr_loss(specmi_handle* h, int mode, const float* pred_pose, const fl
     a.terms = terms; a.counts = counts; a.means = means;
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, "loss.hmr"};
     LAUNCHCHK(h, launch_hmr_loss(a, ctx), "hmr_loss");
+    return SPECMI_OK;
+}
+
+int specmi_hmr_loss_backward(specmi_handle* h, int mode, const float* pred_pose, const float* pred_shape, const float* pred_cam,
+                             const float* joints3d, const float* joints2d, const float* vertices, const float* pose, const float* betas,
+                             const float* pose_conf, const float* pose_3d, const float* keypoints, const float* gt_vertices,
+                             const int32_t* has_smpl, const int32_t* has_pose_3d, const float* orig_shape, const float* scale, int B, int V,
+                             float w_shape, float w_keypoint, float w_pose, float w_smpl_part, float w_beta, float w_openpose, float w_gt,
+                             float w_loss, const float* terms, const int32_t* counts, const float* g_means, float* g_pred_pose,
+                             float* g_pred_shape, float* g_pred_cam, float* g_joints3d, float* g_joints2d, float* g_vertices,
+                             void* stream) {
+    ENTER(h);
+    (void)w_smpl_part;
+    if (B <= 0) return fail(h, SPECMI_ERR_ARG, "hmr_loss_backward: B = %d must be positive", B);
+    if (V <= 0 || V > 0x7fffffff / 3) return fail(h, SPECMI_ERR_ARG, "hmr_loss_backward: V = %d must be positive with V * 3 below 2^31", V);
+    if (mode != SPECMI_HMR_LOSS && mode != SPECMI_HMR_CAM_LOSS)
+        return fail(h, SPECMI_ERR_ARG, "hmr_loss_backward: mode = %d is not defined (0 = HMRLoss, 1 = HMRCamLoss)", mode);
+    const struct { const void* p; const char* name; } required[] = {
+        {pred_pose, "pred_pose"}, {pred_shape, "pred_shape"}, {pred_cam, "pred_cam"}, {joints3d, "joints3d"}, {joints2d, "joints2d"},
+        {vertices, "vertices"}, {pose, "pose"}, {betas, "betas"}, {pose_conf, "pose_conf"}, {pose_3d, "pose_3d"},
+        {keypoints, "keypoints"}, {has_smpl, "has_smpl"}, {has_pose_3d, "has_pose_3d"}, {terms, "terms"}, {counts, "counts"},
+        {g_means, "g_means"}};
+    for (const auto& r : required)
+        if (!r.p) return fail(h, SPECMI_ERR_ARG, "hmr_loss_backward: %s is NULL", r.name);
+    if (!gt_vertices && w_shape != 0.f)
+        return fail(h, SPECMI_ERR_ARG, "hmr_loss_backward: gt_vertices is NULL but shape_loss_weight = %g (NULL is accepted only with weight 0)", (double)w_shape);
+    if (mode == SPECMI_HMR_CAM_LOSS && (!orig_shape || !scale))
+        return fail(h, SPECMI_ERR_ARG, "hmr_loss_backward: orig_shape or scale is NULL (HMRCamLoss needs both)");
+    if (!g_pred_pose && !g_pred_shape && !g_pred_cam && !g_joints3d && !g_joints2d && !g_vertices)
+        return fail(h, SPECMI_ERR_ARG, "hmr_loss_backward: every output is NULL");
+    HmrLossArgs a;
+    a.mode = mode; a.B = B; a.V = V;
+    a.pred_pose = pred_pose; a.pred_shape = pred_shape; a.pred_cam = pred_cam; a.joints3d = joints3d; a.joints2d = joints2d;
+    a.vertices = vertices; a.pose = pose; a.betas = betas; a.pose_conf = pose_conf; a.pose_3d = pose_3d; a.keypoints = keypoints;
+    a.gt_vertices = gt_vertices; a.has_smpl = has_smpl; a.has_pose_3d = has_pose_3d; a.orig_shape = orig_shape; a.scale = scale;
+    a.w_shape = w_shape; a.w_keypoint = w_keypoint; a.w_pose = w_pose; a.w_beta = w_beta; a.w_openpose = w_openpose; a.w_gt = w_gt;
+    a.w_loss = w_loss;
+    a.terms = const_cast<float*>(terms); a.counts = const_cast<int*>(counts); a.means = nullptr;      // (read only by the backward)
+    HmrLossGrads g{g_means, g_pred_pose, g_pred_shape, g_pred_cam, g_joints3d, g_joints2d, g_vertices};
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "loss.hmr_backward"};
+    LAUNCHCHK(h, launch_hmr_loss_backward(a, g, ctx), "hmr_loss_backward");
+    return SPECMI_OK;
+}
+
+int specmi_smpl_backward(specmi_handle* h, const float* rotmat, const float* betas, const float* cam, int B, const float* R,
+                         const float* K, const float* bbox_scale, const float* bbox_center, const float* img_w, const float* img_h,
+                         const float* g_vertices, const float* g_joints3d, const float* g_joints2d, const float* g_cam_t,
+                         float* g_rotmat, float* g_betas, float* g_cam, void* stream) {
+    ENTER(h); NEED_COMMIT(h);
+    if (h->kind != SPECMI_MODEL_HMR && h->kind != SPECMI_MODEL_SMPL) return fail(h, SPECMI_ERR_STATE, "handle has no body model");
+    if (B <= 0) return fail(h, SPECMI_ERR_ARG, "smpl_backward: B = %d must be positive", B);
+    if (!rotmat || !betas || !cam) return fail(h, SPECMI_ERR_ARG, "smpl_backward: rotmat, betas and cam are required");
+    if (!g_vertices && !g_joints3d && !g_joints2d && !g_cam_t)
+        return fail(h, SPECMI_ERR_ARG, "smpl_backward: every upstream gradient is NULL");
+    if (!g_rotmat && !g_betas && !g_cam) return fail(h, SPECMI_ERR_ARG, "smpl_backward: every output is NULL");
+    const int use_cam = opt(h, OPT_use_cam);
+    if (use_cam && (!R || !K || !bbox_scale || !bbox_center || !img_w || !img_h))
+        return fail(h, SPECMI_ERR_ARG, "use_cam needs cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h");
+    int rc;
+    if ((rc = ensure_ws(h, B, 32, 32))) return rc;
+    if ((rc = grow_ragged(h, (void**)&h->smpl_bwd_ws, &h->smpl_bwd_ws_bytes, smpl_bwd_ws_floats(h->smpl.V, B) * 4,
+                          "the SMPL backward workspace")))
+        return rc;
+    SmplBwdArgs a;
+    SmplArgs& f = a.fwd;
+    f.rotmat = rotmat; f.betas = betas; f.cam = cam; f.cam_rotmat = R; f.cam_intrinsics = K;
+    f.bbox_scale = bbox_scale; f.bbox_center = bbox_center; f.img_w = img_w; f.img_h = img_h;
+    f.vertices = h->verts_ws; f.joints3d = f.joints2d = f.cam_t = nullptr;
+    f.pose_feat = h->pf_ws; f.A = h->A_ws; f.posed_j = h->pj_ws;
+    f.B = B;
+    f.mode = use_cam ? 0 : 1;
+    f.focal_length = h->focal_length;
+    f.img_res = (float)opt(h, OPT_img_res);
+    f.normalize_joints2d = use_cam ? 0 : 1;
+    f.skin_split = opt(h, OPT_smpl_skin_split);
+    a.g_vertices = g_vertices; a.g_joints3d = g_joints3d; a.g_joints2d = g_joints2d; a.g_cam_t = g_cam_t;
+    a.g_rotmat = g_rotmat; a.g_betas = g_betas; a.g_cam = g_cam;
+    a.ws = h->smpl_bwd_ws;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "smpl.backward"};
+    LAUNCHCHK(h, launch_smpl_backward(h->smpl, a, ctx), "smpl_backward");
+    return SPECMI_OK;
+}
+
+int specmi_rot6d_forward(specmi_handle* h, const float* x6d, int N, float* rotmat, void* stream) {
+    ENTER(h);
+    if (!x6d || !rotmat || N <= 0) return fail(h, SPECMI_ERR_ARG, "rot6d_forward: x6d, rotmat and N > 0 are required");
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "smpl.rot6d_forward"};
+    LAUNCHCHK(h, launch_rot6d_forward(x6d, rotmat, N, ctx), "rot6d_forward");
+    return SPECMI_OK;
+}
+
+int specmi_rot6d_backward(specmi_handle* h, const float* x6d, const float* g_rotmat, int N, float* g_x6d, void* stream) {
+    ENTER(h);
+    if (!x6d || !g_rotmat || !g_x6d || N <= 0) return fail(h, SPECMI_ERR_ARG, "rot6d_backward: x6d, g_rotmat, g_x6d and N > 0 are required");
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "smpl.rot6d_backward"};
+    LAUNCHCHK(h, launch_rot6d_backward(x6d, g_rotmat, g_x6d, N, ctx), "rot6d_backward");
     return SPECMI_OK;
 }
 

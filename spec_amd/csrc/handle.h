@@ -153,6 +153,9 @@ struct specmi_handle {
     float *rot_ws = nullptr, *betas_ws = nullptr, *cam_ws = nullptr, *verts_ws = nullptr;
     float *pf_ws = nullptr, *A_ws = nullptr, *pj_ws = nullptr;
     int ws_B = 0;
+    // specmi_smpl_backward's own workspace (smpl_bwd_ws_floats(V, B)); grows like ragged_tmp, an outgrown buffer joins ws_retired
+    float* smpl_bwd_ws = nullptr;
+    size_t smpl_bwd_ws_bytes = 0;
     int* resize_tab = nullptr;          // device copy of the Pillow coefficient tables of the last resize geometry
     size_t resize_tab_ints = 0;
     std::vector<int> resize_host;       // host image of the same (kept alive for the async copy)

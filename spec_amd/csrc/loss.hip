@@ -1,4 +1,5 @@
-// loss.hip - the forward value of SPEC's two loss modules on the device (include/specmi.h: specmi_hmr_loss).
+// loss.hip - SPEC's two loss modules on the device: the forward value (include/specmi.h: specmi_hmr_loss) and, at the end of the
+// file, its gradient with respect to the prediction (specmi_hmr_loss_backward: hmr_loss_bwd_kernel, one launch).
 //
 // Replaces spec/losses.py of the reference: HMRLoss.forward (:59-141, mode 0) and HMRCamLoss.forward (:171-271, mode 1) with the
 // helpers they call - projected_keypoint_loss (:274-296), keypoint_3d_loss (:326-348), shape_loss (:375-387), smpl_losses
@@ -184,7 +185,131 @@ __global__ void __launch_bounds__(448) hmr_loss_fold_kernel(const HmrLossArgs a)
     a.means[6] = (((((kp + kp3) + pose) + betas) + shape) + cam) * a.w_loss;
 }
 
+// The gradient of the seven means with respect to the six prediction tensors, one launch, elementwise outputs (no reduction
+// across images other than the three batch scalars every workgroup folds for itself out of `terms`, in hmr_loss_fold_kernel's
+// order).  coef[k] = g_means[k] + w_loss * g_means[6]: total_loss = w_loss * sum of the six.  What autograd does to the
+// reference: a masked-out image gets +0, an empty mask zeros, |x| at 0 has slope 0, the ground truth is a constant.
+__global__ void __launch_bounds__(256) hmr_loss_bwd_kernel(const HmrLossArgs a, const HmrLossGrads g) {
+    __shared__ float s_conf;      // sum of pose_conf over the images with has_smpl (row 3 of terms)
+    __shared__ float s_pel[3];    // sum over the 24 joints of 2 conf d: what the pelvis (joints 2 and 3) takes back
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int Nv = a.counts[0], Np = a.counts[1];
+    const bool hs = a.has_smpl[b] != 0, hp = a.has_pose_3d[b] != 0;
+    float coef[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) coef[k] = g.g_means[k] + a.w_loss * g.g_means[6];
+    if (t < 64) {
+        float acc = 0.f;
+        for (int i = t; i < a.B; i += 64) acc += a.has_smpl[i] != 0 ? a.terms[(size_t)3 * a.B + i] : 0.f;
+        acc = wave_sum64(acc);
+        if (t == 0) s_conf = acc;
+    } else if (t < 128) {
+        // keypoint_3d_loss: d_j = (p_j - pelvis_p) - (g_j - pelvis_g), pelvis = (joint 2 + joint 3) / 2
+        const int j = t - 64;
+        const float* gg = a.pose_3d + (size_t)b * 24 * 4;
+        const float* p = a.joints3d + ((size_t)b * 49 + 25) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float v = 0.f;
+            if (j < 24) {
+                const float gp = (gg[2 * 4 + c] + gg[3 * 4 + c]) / 2.f, pp = (p[2 * 3 + c] + p[3 * 3 + c]) / 2.f;
+                v = 2.f * gg[j * 4 + 3] * ((p[j * 3 + c] - pp) - (gg[j * 4 + c] - gp));
+            }
+            v = wave_sum64(v);
+            if (j == 0) s_pel[c] = v;
+        }
+    }
+    __syncthreads();
+    const float fB = (float)a.B, fNv = (float)Nv, fNp = (float)Np;
+
+    if (g.g_joints2d && t < 49) {
+        const float* kp = a.keypoints + ((size_t)b * 49 + t) * 3;
+        const float* pj = a.joints2d + ((size_t)b * 49 + t) * 2;
+        const float conf = kp[2] * (t < 25 ? a.w_openpose : a.w_gt);
+        const float k0 = coef[0] * a.w_keypoint / (fB * 98.f);
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            float v;
+            if (a.mode == 1) {   // e = conf d^2 (size / (scale 200)), d = 2 pj / size - 1 - (2 kp / size - 1)
+                const float size = a.orig_shape[(size_t)b * 2 + (1 - c)];
+                const float d = (2.f * (pj[c] / size) - 1.f) - (2.f * (kp[c] / size) - 1.f);
+                v = k0 * (size / (a.scale[b] * 200.f)) * (conf * (2.f * d)) * (2.f / size);
+            } else {
+                v = k0 * (conf * (2.f * (pj[c] - kp[c])));
+            }
+            g.g_joints2d[((size_t)b * 49 + t) * 2 + c] = v;
+        }
+    }
+    if (g.g_joints3d && t < 147) {
+        const int jt = t / 3, c = t - jt * 3, j = jt - 25;
+        float v = 0.f;
+        if (j >= 0 && hp && Np > 0) {
+            const float* gg = a.pose_3d + (size_t)b * 24 * 4;
+            const float* p = a.joints3d + ((size_t)b * 49 + 25) * 3;
+            const float gp = (gg[2 * 4 + c] + gg[3 * 4 + c]) / 2.f, pp = (p[2 * 3 + c] + p[3 * 3 + c]) / 2.f;
+            float e = 2.f * gg[j * 4 + 3] * ((p[j * 3 + c] - pp) - (gg[j * 4 + c] - gp));
+            if (j == 2 || j == 3) e -= 0.5f * s_pel[c];
+            v = coef[1] * a.w_keypoint / (fNp * 72.f) * e;
+        }
+        g.g_joints3d[(size_t)b * 147 + t] = v;
+    }
+    if (g.g_pred_pose && t < 216) {
+        float v = 0.f;
+        if (hs && Nv > 0) {
+            const int j = t / 9;
+            const float* th = a.pose + (size_t)b * 72 + j * 3;
+            const float d = a.pred_pose[(size_t)b * 216 + t] - spin_rodrigues_element(th[0], th[1], th[2], t - j * 9);
+            v = coef[2] * a.w_pose * (s_conf / (fNv * 24.f)) * (2.f * d) / (fNv * 216.f);
+        }
+        g.g_pred_pose[(size_t)b * 216 + t] = v;
+    }
+    if (g.g_pred_shape && t < 10) {
+        float v = 0.f;
+        if (hs && Nv > 0) v = coef[3] * a.w_beta * (2.f * (a.pred_shape[(size_t)b * 10 + t] - a.betas[(size_t)b * 10 + t])) / (fNv * 10.f);
+        g.g_pred_shape[(size_t)b * 10 + t] = v;
+    }
+    if (g.g_pred_cam && t < 3) {
+        float v = 0.f;
+        if (t == 0) { const float e = expf(-a.pred_cam[(size_t)b * 3] * 10.f); v = coef[5] * (-20.f * (e * e)) / fB; }
+        g.g_pred_cam[(size_t)b * 3 + t] = v;
+    }
+    if (g.g_vertices) {   // 16-byte chunks counted from the image's first float, as the forward reads them
+        const int n = a.V * 3, nchunk = n >> 2;
+        float* const ov = g.g_vertices + (size_t)b * n;
+        F4* const o4 = reinterpret_cast<F4*>(ov);
+        const bool on = hs && Nv > 0 && a.gt_vertices;
+        const float k4 = on ? coef[4] * a.w_shape / (float)((double)Nv * a.V * 3.0) : 0.f;
+        if (!on) {
+            const F4 z = {0.f, 0.f, 0.f, 0.f};
+            for (int k = t; k < nchunk; k += 256) o4[k] = z;
+            const int tail = (nchunk << 2) + t;
+            if (t < 3 && tail < n) ov[tail] = 0.f;
+            return;
+        }
+        const float* pv = a.vertices + (size_t)b * n;
+        const float* gv = a.gt_vertices + (size_t)b * n;
+        const F4* p4 = reinterpret_cast<const F4*>(pv);
+        const F4* g4 = reinterpret_cast<const F4*>(gv);
+        auto slope = [k4](float d) { return d > 0.f ? k4 : d < 0.f ? -k4 : 0.f; };
+#pragma unroll 4
+        for (int k = t; k < nchunk; k += 256) {
+            const F4 p = p4[k], q = g4[k];
+            const F4 o = {slope(p.x - q.x), slope(p.y - q.y), slope(p.z - q.z), slope(p.w - q.w)};
+            o4[k] = o;
+        }
+        const int tail = (nchunk << 2) + t;
+        if (t < 3 && tail < n) ov[tail] = slope(pv[tail] - gv[tail]);
+    }
+}
+
 }  // namespace
+
+int launch_hmr_loss_backward(const HmrLossArgs& a, const HmrLossGrads& g, const LaunchCtx& ctx) {
+    const double per_image = 216 * 2 + 10 * 2 + 3 * 2 + 49 * 5 + 49 * 5 + 72 + 24 * 4 + (g.g_vertices ? (a.gt_vertices ? 9.0 : 3.0) * a.V : 0.0);
+    ProfScope ps(ctx, "hmr_loss_bwd", 0.0, 4.0 * a.B * (per_image + a.B));
+    hipLaunchKernelGGL(hmr_loss_bwd_kernel, dim3(a.B), dim3(256), 0, ctx.stream, a, g);
+    return (int)hipGetLastError();
+}
 
 int launch_hmr_loss(const HmrLossArgs& a, const LaunchCtx& ctx) {
     {

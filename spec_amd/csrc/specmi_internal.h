@@ -363,6 +363,23 @@ int launch_smpl_native(const SmplDev& m, const SmplArgs& a, float* joints24, con
 // axis-angle (n,3) -> rotation matrices (n,3,3), smplx batch_rodrigues
 int launch_rodrigues(const float* aa, float* rot, int n, const LaunchCtx& ctx);
 
+// The vector-Jacobian product of launch_smpl (smpl_bwd.hip).  fwd: the forward's inputs, mode and its scratch (pose_feat, A,
+// posed_j, vertices = a (B,V,3) scratch mesh); the forward is recomputed into them, its outputs are not read from the caller.
+// Upstream gradients dense ((B,V,3), (B,49,3), (B,49,2), (B,3)), any may be null = zero; outputs (B,24,3,3), (B,10), (B,3), any
+// may be null.  ws: smpl_bwd_ws_floats(V, B) floats.
+struct SmplBwdArgs {
+    SmplArgs fwd;
+    const float *g_vertices, *g_joints3d, *g_joints2d, *g_cam_t;
+    float *g_rotmat, *g_betas, *g_cam;
+    float* ws;
+};
+size_t smpl_bwd_ws_floats(int V, int B);
+int launch_smpl_backward(const SmplDev& m, const SmplBwdArgs& a, const LaunchCtx& ctx);
+// rot6d_joint on its own: x6d (n,6) -> rotmat (n,3,3)
+int launch_rot6d_forward(const float* x6d, float* rotmat, int n, const LaunchCtx& ctx);
+// the backward of rot6d_joint: x6d (n,6), g_rotmat (n,3,3) -> g_x6d (n,6)
+int launch_rot6d_backward(const float* x6d, const float* g_rotmat, float* g_x6d, int n, const LaunchCtx& ctx);
+
 // ----------------------------------------------------------------------------------------
 // evaluation metrics  (eval.hip)
 // ----------------------------------------------------------------------------------------
@@ -391,6 +408,13 @@ struct HmrLossArgs {
     float* terms; int* counts; float* means;
 };
 int launch_hmr_loss(const HmrLossArgs& a, const LaunchCtx& ctx);
+// The gradient of the seven means (include/specmi.h: specmi_hmr_loss_backward): a = the forward's arguments with the `terms` and
+// `counts` it produced (read here; means is not); g_means (7) upstream; any output may be null.
+struct HmrLossGrads {
+    const float* g_means;
+    float *g_pred_pose, *g_pred_shape, *g_pred_cam, *g_joints3d, *g_joints2d, *g_vertices;
+};
+int launch_hmr_loss_backward(const HmrLossArgs& a, const HmrLossGrads& g, const LaunchCtx& ctx);
 
 // ----------------------------------------------------------------------------------------
 // crop + normalise  (preprocess.hip)

@@ -652,6 +652,44 @@ def check_eval_step(B, V, J, nsel, joint_sel=None, Jk=0, pred_joints=False, gt_j
     return joint_sel
 
 
+def check_hmr_loss_backward(B, V, terms_shape, counts_shape, want):
+    """Every refusal of ``specmi_hmr_loss_backward`` (include/specmi.h) that is not already one of ``specmi_hmr_loss``, as
+    ``ValueError``: ``terms`` / ``counts`` must be what the forward of the same batch produced, one output at least is wanted."""
+    if B < 1 or V < 1:
+        raise ValueError(f'{B} images of {V} vertices: at least one of each')
+    if tuple(terms_shape) != (6, B) or tuple(counts_shape) != (2,):
+        raise ValueError(f'terms must be (6, {B}) and counts (2,) as hmr_loss returned them, got {tuple(terms_shape)} and {tuple(counts_shape)}')
+    if len(want) != 6 or not any(want):
+        raise ValueError('want names the six prediction tensors (pred_pose, pred_shape, pred_cam, smpl_joints3d, smpl_joints2d, '
+                         'smpl_vertices) and asks for one at least')
+
+
+def check_smpl_backward(B, upstream, outputs, use_cam=False, camera=()):
+    """Every refusal of ``specmi_smpl_backward`` (include/specmi.h) as ``ValueError``.  ``upstream``: which of g_vertices,
+    g_joints3d, g_joints2d, g_cam_t are given (four truth values); ``outputs``: which of g_rotmat, g_betas, g_cam are wanted
+    (three); ``camera``: which of the six camera arguments are given (read with ``use_cam`` only).  Needs no device."""
+    if B < 1:
+        raise ValueError(f'B = {B}: at least one image')
+    if len(upstream) != 4 or len(outputs) != 3:
+        raise ValueError('upstream names four gradients (vertices, joints3d, joints2d, cam_t), outputs three (rotmat, betas, cam)')
+    if not any(upstream):
+        raise ValueError('every upstream gradient is None (at least one of g_vertices, g_joints3d, g_joints2d, g_cam_t)')
+    if not any(outputs):
+        raise ValueError('no output is wanted (at least one of rotmat, betas, cam)')
+    if use_cam and not (len(camera) == 6 and all(camera)):
+        raise ValueError('use_cam needs cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h')
+
+
+def check_rot6d_backward(x_shape, g_shape):
+    """The shapes ``specmi_rot6d_backward`` takes: x6d (N, 6) or rows of 24 such rotations, g_rotmat with 9 numbers per rotation; -> N."""
+    n = math.prod(x_shape)
+    if n == 0 or n % 6 or x_shape[-1] % 6:
+        raise ValueError(f'x6d must hold whole 6D rotations along its last axis, got shape {tuple(x_shape)}')
+    if math.prod(g_shape) != n // 6 * 9:
+        raise ValueError(f'g_rotmat of shape {tuple(g_shape)} does not hold {n // 6} 3x3 matrices')
+    return n // 6
+
+
 def out_dtype(dtype):
     """The ``dtype=`` keyword of the producers: torch.float32 -> the (n,3,H,W) fp32 image, torch.float16 -> NHWC8 fp16."""
     if dtype not in (torch.float32, torch.float16):
@@ -984,12 +1022,8 @@ class Engine:
                 _ptr(res['argmax']), _ptr(res['soft']), _ptr(res['angle']), _ptr(res['err']), _ptr(res['means']), self._stream()))
         return res
 
-    def hmr_loss(self, mode, pred, gt, weights, out=None):
-        """``specmi_hmr_loss``: the forward value of the reference's HMRLoss (``mode`` 0) / HMRCamLoss (``mode`` 1).  ``pred``
-        and ``gt`` map the names of ``HMR_LOSS_INPUTS`` to tensors or arrays ((B, ...) each; gt['vertices'] may be None when the
-        shape weight is 0; 'orig_shape' as (H, W) and 'scale' are read in mode 1 only), ``weights`` the eight constructor
-        arguments in ``HMR_LOSS_WEIGHTS`` order.  -> dict(terms (6, B), counts (2,) int32 = Nv, Np, means (7,) in
-        ``HMR_LOSS_KEYS`` order), device tensors; ``out`` supplies them (a captured graph replays into the same three)."""
+    def _hmr_loss_args(self, mode, pred, gt, weights):
+        """The 16 tensors of ``specmi_hmr_loss`` / ``specmi_hmr_loss_backward`` in the prototype's order, checked -> (args, B, V)."""
         if mode not in (_lib.HMR_LOSS, _lib.HMR_CAM_LOSS):
             raise ValueError(f'mode must be 0 (HMRLoss) or 1 (HMRCamLoss), got {mode!r}')
         if len(weights) != len(HMR_LOSS_WEIGHTS):
@@ -1016,6 +1050,15 @@ class Engine:
                 args.append(_dev_f32(gt[k], self.device, shp) if mode == _lib.HMR_CAM_LOSS else None)
             else:
                 args.append(_dev_f32(gt['keypoints_orig' if (k == 'keypoints' and mode == _lib.HMR_CAM_LOSS) else k], self.device, shp))
+        return args, B, V
+
+    def hmr_loss(self, mode, pred, gt, weights, out=None):
+        """``specmi_hmr_loss``: the forward value of the reference's HMRLoss (``mode`` 0) / HMRCamLoss (``mode`` 1).  ``pred``
+        and ``gt`` map the names of ``HMR_LOSS_INPUTS`` to tensors or arrays ((B, ...) each; gt['vertices'] may be None when the
+        shape weight is 0; 'orig_shape' as (H, W) and 'scale' are read in mode 1 only), ``weights`` the eight constructor
+        arguments in ``HMR_LOSS_WEIGHTS`` order.  -> dict(terms (6, B), counts (2,) int32 = Nv, Np, means (7,) in
+        ``HMR_LOSS_KEYS`` order), device tensors; ``out`` supplies them (a captured graph replays into the same three)."""
+        args, B, V = self._hmr_loss_args(mode, pred, gt, weights)
         res = out if out is not None else {'terms': self._empty(6, B), 'counts': self._empty(2, dtype=torch.int32), 'means': self._empty(len(HMR_LOSS_KEYS))}
         for k, shp, dt in (('terms', (6, B), torch.float32), ('counts', (2,), torch.int32), ('means', (len(HMR_LOSS_KEYS),), torch.float32)):
             if tuple(res[k].shape) != shp or res[k].dtype != dt or not res[k].is_contiguous() or res[k].device != self.device:
@@ -1023,6 +1066,23 @@ class Engine:
         _lib.check(self.h, self.lib.specmi_hmr_loss(self.h, int(mode), *(_ptr(t) for t in args), B, V, *(float(w) for w in weights),
                                                     _ptr(res['terms']), _ptr(res['counts']), _ptr(res['means']), self._stream()))
         return res
+
+    def hmr_loss_backward(self, mode, pred, gt, weights, res, g_means, want=(True,) * 6):
+        """``specmi_hmr_loss_backward``: the gradient of the seven means of ``hmr_loss`` with respect to the six prediction tensors.
+        ``pred``, ``gt``, ``weights`` as given to ``hmr_loss``, ``res`` what it returned (``terms`` and ``counts`` are read),
+        ``g_means`` (7) the upstream gradient; -> {key of ``pred``: gradient, or None where ``want`` (in the order of
+        ``HMR_LOSS_INPUTS['pred']``) says not wanted}."""
+        args, B, V = self._hmr_loss_args(mode, pred, gt, weights)
+        check_hmr_loss_backward(B, V, tuple(res['terms'].shape), tuple(res['counts'].shape), want)
+        for k, dt in (('terms', torch.float32), ('counts', torch.int32)):
+            if res[k].dtype != dt or not res[k].is_contiguous() or res[k].device != self.device:
+                raise ValueError(f'res[{k!r}] must be the contiguous {dt} tensor hmr_loss returned, on the engine device')
+        gm = _dev_f32(g_means, self.device, (len(HMR_LOSS_KEYS),))
+        out = [torch.empty_like(a) if w else None for a, w in zip(args[:6], want)]
+        _lib.check(self.h, self.lib.specmi_hmr_loss_backward(
+            self.h, int(mode), *(_ptr(t) for t in args), B, V, *(float(w) for w in weights), _ptr(res['terms']), _ptr(res['counts']),
+            _ptr(gm), *(_ptr(o) for o in out), self._stream()))
+        return {k: o for (k, _), o in zip(HMR_LOSS_INPUTS['pred'], out)}
 
     def eval_step(self, pred_vertices, gt_vertices, J_regressor, joint_sel=None, nsel=None, pred_joints=None, gt_joints=None,
                   outputs=None):
@@ -1551,6 +1611,44 @@ class Engine:
             self.h, _ptr(rot), _ptr(be), _ptr(cm), B, _ptr(R), _ptr(K), _ptr(sc), _ptr(ce), _ptr(iw),
             _ptr(ih), _ptr(out['smpl_vertices']), _ptr(out['smpl_joints3d']), _ptr(out['smpl_joints2d']),
             _ptr(out['pred_cam_t']), self._stream()))
+        return out
+
+    def smpl_backward(self, rotmat, betas, cam, cam_rotmat=None, cam_intrinsics=None, bbox_scale=None, bbox_center=None,
+                      img_w=None, img_h=None, g_vertices=None, g_joints3d=None, g_joints2d=None, g_cam_t=None,
+                      want=(True, True, True)):
+        """``specmi_smpl_backward``: the vector-Jacobian product of ``smpl`` at its own inputs.  Upstream gradients that are None
+        count as zero; -> (g_rotmat (B,24,3,3), g_betas (B,10), g_cam (B,3)), None where ``want`` says not wanted."""
+        rot = _dev_f32(rotmat, self.device)
+        B = rot.shape[0]
+        rot = rot.reshape(B, *_ROTMATS).contiguous()
+        be = _dev_f32(betas, self.device, (B, 10))
+        cm = _dev_f32(cam, self.device, (B, 3))
+        camera = self._cam_args(B, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h)
+        shapes = _record_shapes(self.num_verts)
+        up = tuple(_dev_f32(g, self.device, (B, *shapes[k])) for g, k in
+                   ((g_vertices, 'smpl_vertices'), (g_joints3d, 'smpl_joints3d'), (g_joints2d, 'smpl_joints2d'), (g_cam_t, 'pred_cam_t')))
+        check_smpl_backward(B, [g is not None for g in up], want, self.get_option('use_cam'), [c is not None for c in camera])
+        out = [self._empty(B, *shp) if w else None for w, shp in zip(want, (_ROTMATS, (10,), (3,)))]
+        _lib.check(self.h, self.lib.specmi_smpl_backward(
+            self.h, _ptr(rot), _ptr(be), _ptr(cm), B, *(_ptr(c) for c in camera), *(_ptr(g) for g in up),
+            *(_ptr(o) for o in out), self._stream()))
+        return tuple(out)
+
+    def rot6d_to_rotmat(self, x6d):
+        """``specmi_rot6d_forward``: (N,6), or the head's pose rows of 24 rotations -> (N,3,3) rotation matrices (its Gram-Schmidt)."""
+        x = _dev_f32(x6d, self.device)
+        n = check_rot6d_backward(tuple(x.shape), (math.prod(x.shape) // 6 * 9,))
+        out = self._empty(n, 3, 3)
+        _lib.check(self.h, self.lib.specmi_rot6d_forward(self.h, _ptr(x), n, _ptr(out), self._stream()))
+        return out
+
+    def rot6d_backward(self, x6d, g_rotmat):
+        """``specmi_rot6d_backward``: x6d as ``rot6d_to_rotmat`` takes it, g_rotmat (N,3,3) or (B,24,3,3) -> the gradient of x6d, in its shape."""
+        x = _dev_f32(x6d, self.device)
+        g = _dev_f32(g_rotmat, self.device)
+        n = check_rot6d_backward(tuple(x.shape), tuple(g.shape))
+        out = torch.empty_like(x)
+        _lib.check(self.h, self.lib.specmi_rot6d_backward(self.h, _ptr(x), _ptr(g), n, _ptr(out), self._stream()))
         return out
 
     def smpl_native(self, pose, betas, vertices=True, joints24=True):

@@ -1,6 +1,10 @@
 """The forward value of the reference's two loss modules on the device (``spec/losses.py``: ``HMRLoss`` :26-141,
-``HMRCamLoss`` :144-271) - the objective a checkpoint was trained under, as an evaluation quantity.  No gradient: training
-(backward, optimiser, datasets, augmentation) is out of scope.
+``HMRCamLoss`` :144-271) - the objective a checkpoint was trained under, as an evaluation quantity and, since the tail of the
+training step has a backward, as something to descend: when grad is enabled and a tensor of ``pred`` requires grad, every entry
+of ``loss_dict`` carries a ``grad_fn`` whose backward is ``specmi_hmr_loss_backward`` (first derivatives only; the ground truth
+is a constant).  ``loss.backward()`` then reaches whatever produced ``pred`` - the heads of ``spec_amd.differentiable``, say.
+With no tensor requiring grad nothing changes: the same launch, the same bits, no ``grad_fn``.  The trunk, the head's Linears,
+optimisers, datasets and augmentation stay out of scope.
 
 Everything numeric runs in ``specmi_hmr_loss`` (spec_amd/csrc/loss.hip; the quirks of the reference it restates are listed at
 its declaration in include/specmi.h): one launch reduces every image, one folds the batch.
@@ -21,9 +25,13 @@ import threading
 import torch
 import torch.nn as nn
 
+from torch.autograd.function import once_differentiable
+
 from . import _lib
 from .cam_utils import _engine
-from .engine import HMR_LOSS_KEYS, HMR_LOSS_WEIGHTS
+from .engine import HMR_LOSS_INPUTS, HMR_LOSS_KEYS, HMR_LOSS_WEIGHTS
+
+_PRED_KEYS = tuple(k for k, _ in HMR_LOSS_INPUTS['pred'])
 
 _tls = threading.local()
 
@@ -48,6 +56,24 @@ def gt_vertices(pose, betas, body_model=None):
     return body_model.native(pose, betas, vertices=True, joints24=False)[0]
 
 
+class _HmrLossFn(torch.autograd.Function):
+    """means (7) = Engine.hmr_loss of the six prediction tensors; backward = Engine.hmr_loss_backward."""
+
+    @staticmethod
+    def forward(ctx, eng, mode, gt, weights, *pred_tensors):
+        pred = {k: v.detach() if isinstance(v, torch.Tensor) else v for k, v in zip(_PRED_KEYS, pred_tensors)}
+        res = eng.hmr_loss(mode, pred, gt, weights)
+        ctx.eng, ctx.mode, ctx.gt, ctx.weights, ctx.pred, ctx.res = eng, mode, gt, weights, pred, res
+        return res['means']
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_means):
+        want = tuple(ctx.needs_input_grad[4:])
+        g = ctx.eng.hmr_loss_backward(ctx.mode, ctx.pred, ctx.gt, ctx.weights, ctx.res, g_means, want)
+        return (None, None, None, None) + tuple(None if g[k] is None else g[k].reshape(ctx.pred[k].shape) for k in _PRED_KEYS)
+
+
 class _LossBase(nn.Module):
     _mode = None
 
@@ -55,19 +81,23 @@ class _LossBase(nn.Module):
         for name in HMR_LOSS_WEIGHTS:
             setattr(self, name, kw[name])
 
-    @torch.no_grad()
     def forward(self, pred, gt):
         """-> (loss, loss_dict): the seven keys of the reference in its order, 0-dim device tensors; ``loss`` is
         ``loss_dict['loss/total_loss']``.  ``gt['vertices']`` is used when present (``gt_vertices`` makes it) and may be
-        missing while ``shape_loss_weight`` is 0."""
+        missing while ``shape_loss_weight`` is 0.  Differentiable in the six tensors of ``pred`` (module docstring)."""
         if 'pred_segm_rgb' in pred:
             raise NotImplementedError("'pred_segm_rgb': the part-segmentation term calls self.criterion_part, which the reference never "
                                       'defines (spec/losses.py:131,259)')
         v = pred['smpl_vertices']
         if not isinstance(v, torch.Tensor) or v.device.type != 'cuda':
             raise RuntimeError('spec_amd.losses needs device tensors (no CPU path)')
-        res = _engine(v.device).hmr_loss(self._mode, pred, gt, [getattr(self, n) for n in HMR_LOSS_WEIGHTS])
-        loss_dict = dict(zip(HMR_LOSS_KEYS, res['means'].unbind(0)))
+        weights = [getattr(self, n) for n in HMR_LOSS_WEIGHTS]
+        if torch.is_grad_enabled() and any(isinstance(pred[k], torch.Tensor) and pred[k].requires_grad for k in _PRED_KEYS):
+            means = _HmrLossFn.apply(_engine(v.device), self._mode, gt, weights, *(pred[k] for k in _PRED_KEYS))
+        else:
+            with torch.no_grad():
+                means = _engine(v.device).hmr_loss(self._mode, pred, gt, weights)['means']
+        loss_dict = dict(zip(HMR_LOSS_KEYS, means.unbind(0)))
         return loss_dict['loss/total_loss'], loss_dict
 
 
