@@ -798,24 +798,9 @@ int specmi_destroy(specmi_handle* h) {
     if (h->sk.cnt) (void)hipFree(h->sk.cnt);
     free_pool(h->sk_retired);
     free_pool(h->ws_retired);
-    if (h->smpl_bwd_ws) (void)hipFree(h->smpl_bwd_ws);
     if (h->resize_tab) (void)hipFree(h->resize_tab);
-    if (h->ragged_tab) (void)hipFree(h->ragged_tab);
-    if (h->ragged_tmp) (void)hipFree(h->ragged_tmp);
-    if (h->pano_tab) (void)hipFree(h->pano_tab);
-    if (h->crop_tab) (void)hipFree(h->crop_tab);
-    if (h->render_ws) (void)hipFree(h->render_ws);
-    if (h->views_tab) (void)hipFree(h->views_tab);
-    if (h->draw_tab) (void)hipFree(h->draw_tab);
-    if (h->marks_tab) (void)hipFree(h->marks_tab);
-    if (h->jpeg_tab) (void)hipFree(h->jpeg_tab);
-    if (h->jpeg_ws) (void)hipFree(h->jpeg_ws);
-    if (h->png_tab) (void)hipFree(h->png_tab);
-    if (h->png_ws) (void)hipFree(h->png_ws);
-    if (h->jdec_tab) (void)hipFree(h->jdec_tab);
-    if (h->jdec_ws) (void)hipFree(h->jdec_ws);
-    if (h->pdec_tab) (void)hipFree(h->pdec_tab);
-    if (h->pdec_ws) (void)hipFree(h->pdec_ws);
+    for (DevTable& t : h->tab) (void)hipFree(t.dev.p);       // hipFree(nullptr) is a no-op
+    for (DevBuf& b : h->buf) (void)hipFree(b.p);
     hrnet_free(h->hrnet);
     delete h;
     return SPECMI_OK;
@@ -1588,16 +1573,117 @@ int specmi_resize_normalize_f16(specmi_handle* h, const uint8_t* frame, int H, i
     return resize_normalize(h, frame, H, W, OH, OW, out_nhwc8, true, raw, stream);
 }
 
-// a device buffer of the ragged resize that must hold `need` bytes: kept, or replaced by one at least 1.5x the old size while the
-// outgrown one joins ws_retired (the rule of ensure_ws: work enqueued earlier may still name it)
-static int grow_ragged(specmi_handle* h, void** buf, size_t* have, size_t need, const char* what) {
-    if (need <= *have) return SPECMI_OK;
+// a device buffer of a ragged entry point that must hold `need` bytes: kept, or replaced by one at least 1.5x the old size while the
+// outgrown one joins ws_retired (the rule of ensure_ws: work enqueued earlier may still name it).  A failed allocation leaves it empty.
+static int grow_ragged(specmi_handle* h, DevBuf& b, size_t need, const char* what) {
+    if (need <= b.bytes) return SPECMI_OK;
     if (int rc0 = sync_for_growth(h, what)) return rc0;
-    if (*have && need < *have + *have / 2) need = *have + *have / 2;
-    if (*buf) h->ws_retired.push_back(*buf);
-    *buf = nullptr; *have = 0;
-    HIPCHK(h, hipMalloc(buf, need));
-    *have = need;
+    if (b.bytes && need < b.bytes + b.bytes / 2) need = b.bytes + b.bytes / 2;
+    if (b.p) h->ws_retired.push_back(b.p);
+    b = DevBuf{};
+    HIPCHK(h, hipMalloc(&b.p, need));
+    b.bytes = need;
+    return SPECMI_OK;
+}
+
+// is a capture under way on the stream?  (a failed query counts as no, and leaves no sticky error behind)
+static bool stream_is_capturing(hipStream_t s) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+// The rewrite rule of every DevTable (handle.h), for the records a call has just built - handed over: a rewrite swaps them with the
+// host image instead of copying them (the tile list of specmi_draw_marks is large); `ws` with `ws_need`: the workspace the same
+// call needs, which grows first.  `what` / `ws_what` name the two in messages.
+//   ask_first = the nouns of the refusal ("new frame records or bones"): growing either buffer or rewriting the table synchronises
+// the whole device, which would invalidate a capture under way on the stream.  Such a table asks the stream first and refuses with
+// SPECMI_ERR_STATE before anything is enqueued or synchronised, so the capture stays valid.
+//   ask_first = nullptr: the three older tables (ragged, pano, crop) do not ask: under capture they reach sync_for_growth and
+// report that the capture is invalid now.  Making them ask first is a change of behaviour that belongs to another pull request.
+// On return the records are in t.dev.p (read it after the call, not before: growing replaces it).
+static int publish_table(specmi_handle* h, DevTable& t, std::vector<int>& rec, const char* what, const char* ask_first, hipStream_t s,
+                         DevBuf* ws = nullptr, size_t ws_need = 0, const char* ws_what = nullptr) {
+    const size_t len = rec.size() * sizeof(int);
+    const bool regrown = len > t.dev.bytes;
+    const bool rewrite = regrown || rec != t.host;
+    if (ask_first && (rewrite || (ws && ws_need > ws->bytes)) && stream_is_capturing(s))
+        return fail(h, SPECMI_ERR_STATE, "%s are not possible while the stream is being captured: run one eager call with these records "
+                    "first (nothing was enqueued)", ask_first);
+    int rc;
+    if (ws && (rc = grow_ragged(h, *ws, ws_need, ws_what))) return rc;
+    if ((rc = grow_ragged(h, t.dev, len, what))) return rc;
+    if (!rewrite) return SPECMI_OK;
+    // a call enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize has the same rule); growing
+    // the table has just waited for the whole device
+    if (!regrown && (rc = sync_for_growth(h, what))) return rc;
+    t.host.swap(rec);
+    HIPCHK(h, hipMemcpyAsync(t.dev.p, t.host.data(), len, hipMemcpyHostToDevice, s));
+    return SPECMI_OK;
+}
+
+// ---- byte rectangles: what the ragged entry points check about the places their records name in a slab ------------------------------
+// a rectangle = H rows of `row` (3 W) bytes, `pitch` bytes apart, from byte `off` of its slab
+struct ByteRect { long long off, pitch, row; int H; long long end() const { return off + (H - 1) * pitch + row; } };
+
+// does the rectangle of H rows of 3 W bytes lie inside a slab of slab_bytes?  In double: no offset or pitch overflows it
+static bool rect_in_slab(long long off, long long pitch, int H, int W, size_t slab_bytes) {
+    return off >= 0 && (double)off + (double)(H - 1) * (double)pitch + 3.0 * W <= (double)slab_bytes;
+}
+
+// a single row has no next row: its pitch is not read, and is stored as 3 W so that equal rectangles give equal records
+static long long stored_pitch(long long pitch, int H, int W) { return H > 1 ? pitch : 3LL * W; }
+
+// do two buffers share a byte?
+static bool slabs_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    return (const uint8_t*)b < (const uint8_t*)a + a_bytes && (const uint8_t*)a < (const uint8_t*)b + b_bytes;
+}
+
+static bool rects_overlap(ByteRect a, ByteRect b) {
+    if (a.off > b.off) std::swap(a, b);
+    if (b.off >= a.end()) return false;
+    if (a.pitch == b.pitch) {       // the columns of one picture: b starts c bytes into row q of a
+        const long long q = (b.off - a.off) / a.pitch, c = (b.off - a.off) % a.pitch;
+        return (q < a.H && c < a.row) || (q + 1 < a.H && c + b.row > a.pitch);
+    }
+    for (int r = 0; r < b.H; ++r) {      // row r of b against the rows of a it reaches
+        const long long s0 = b.off + r * b.pitch - a.off, e0 = s0 + b.row - 1;     // first and last byte, counted from a's first
+        if (s0 >= a.end() - a.off) break;
+        const long long k1 = s0 / a.pitch, k2 = std::min<long long>(e0 / a.pitch, a.H - 1);
+        if (k2 - k1 >= 2) return true;                                              // a whole row of a lies inside
+        for (long long k = k1; k <= k2; ++k)
+            if (std::max(s0, k * a.pitch) <= std::min(e0, k * a.pitch + a.row - 1)) return true;
+    }
+    return false;
+}
+
+// the first two rectangles that share a byte -> true and their indices: sorted by first byte, a rectangle is compared with those
+// that start before it ends
+static bool first_overlap(const std::vector<ByteRect>& rects, int* a, int* b) {
+    const int n = (int)rects.size();
+    std::vector<int> order((size_t)n);
+    for (int i = 0; i < n; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](int x, int y) { return rects[x].off < rects[y].off; });
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 1; j < n && rects[order[j]].off < rects[order[i]].end(); ++j)
+            if (rects_overlap(rects[order[i]], rects[order[j]])) { *a = order[i]; *b = order[j]; return true; }
+    return false;
+}
+
+// the same for gapless ranges (first byte, bytes), which it sorts -> true and the first byte of the later of two that meet
+static bool first_shared_byte(std::vector<std::pair<long long, long long>>& ranges, long long* at) {
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 0; i + 1 < ranges.size(); ++i)
+        if (ranges[i].first + ranges[i].second > ranges[i + 1].first) { *at = ranges[i + 1].first; return true; }
+    return false;
+}
+// ---- end of byte rectangles -------------------------------------------------------------------------------------------------------
+
+// the two refusals of record i's pitched rectangle in its slab; `noun` = what the call's records are ("frame", "picture", "file")
+static int check_rect(specmi_handle* h, const char* noun, int i, long long off, long long pitch, int H, int W, size_t slab_bytes) {
+    if (pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "%s %d: a pitch of %lld bytes for rows of %d", noun, i, pitch, 3 * W);
+    if (!rect_in_slab(off, pitch, H, W, slab_bytes))
+        return fail(h, SPECMI_ERR_ARG, "%s %d: its rectangle leaves the slab of %zu bytes", noun, i, slab_bytes);
     return SPECMI_OK;
 }
 
@@ -1618,7 +1704,7 @@ static int resize_normalize_ragged(specmi_handle* h, const uint8_t* frames, size
         const int H = geom[4 * f], W = geom[4 * f + 1], OH = geom[4 * f + 2], OW = geom[4 * f + 3];
         if (H <= 0 || W <= 0 || OH <= 0 || OW <= 0 || OH > Hmax || OW > Wmax)
             return fail(h, SPECMI_ERR_ARG, "frame %d: size %d x %d -> %d x %d does not fit the %d x %d batch", f, H, W, OH, OW, Hmax, Wmax);
-        if (offsets[f] < 0 || (double)offsets[f] + (double)H * W * 3 > (double)slab_bytes)
+        if (!rect_in_slab(offsets[f], 3LL * W, H, W, slab_bytes))
             return fail(h, SPECMI_ERR_ARG, "frame %d: %d x %d x 3 bytes at offset %lld leave the slab of %zu bytes", f, H, W, (long long)offsets[f], slab_bytes);
         RaggedFrame fr{};
         fr.src_off = (unsigned)offsets[f]; fr.H = H; fr.W = W; fr.OH = OH; fr.OW = OW;
@@ -1640,19 +1726,12 @@ static int resize_normalize_ragged(specmi_handle* h, const uint8_t* frames, size
         }
         std::memcpy(tab.data() + (size_t)f * kRaggedRec, &fr, sizeof(fr));
     }
-    int rc;
-    if ((rc = grow_ragged(h, (void**)&h->ragged_tmp, &h->ragged_tmp_bytes, tmp_bytes, "the ragged-resize row workspace"))) return rc;
-    const bool regrown = tab.size() * 4 > h->ragged_tab_bytes;
-    if ((rc = grow_ragged(h, (void**)&h->ragged_tab, &h->ragged_tab_bytes, tab.size() * 4, "the ragged-resize tables"))) return rc;
-    if (regrown || tab != h->ragged_host) {
-        // a batch enqueued earlier on ANY stream may still read the old tables (specmi_resize_normalize has the same rule)
-        if (!regrown && (rc = sync_for_growth(h, "the ragged-resize tables"))) return rc;
-        h->ragged_host.swap(tab);
-        HIPCHK(h, hipMemcpyAsync(h->ragged_tab, h->ragged_host.data(), h->ragged_host.size() * 4, hipMemcpyHostToDevice, s));
-    }
+    DevBuf& tmp = h->buf[BUF_ragged_tmp];
+    DevTable& T = h->tab[TAB_ragged];
+    if (int rc = publish_table(h, T, tab, "the ragged-resize tables", nullptr, s, &tmp, tmp_bytes, "the ragged-resize row workspace")) return rc;
     LaunchCtx ctx{s, &h->prof, "preprocess.resize_ragged"};
-    LAUNCHCHK(h, launch_resize_normalize_ragged(frames, h->ragged_tab, h->ragged_tmp, n, max_hpass, Hmax, Wmax, (double)slab_bytes, (double)tmp_bytes,
-                                                out, ctx, f16),
+    LAUNCHCHK(h, launch_resize_normalize_ragged(frames, (const int*)T.dev.p, (unsigned char*)tmp.p, n, max_hpass, Hmax, Wmax, (double)slab_bytes,
+                                                (double)tmp_bytes, out, ctx, f16),
               "resize_normalize_ragged");
     return SPECMI_OK;
 }
@@ -1675,7 +1754,9 @@ int specmi_pano_extract_views(specmi_handle* h, const uint8_t* pano, int PH, int
     if (n > 65535) return fail(h, SPECMI_ERR_ARG, "at most 65535 views per call (grid dimension), got %d", n);
     if (PH < 1 || PW < 1) return fail(h, SPECMI_ERR_ARG, "a %d x %d panorama", PH, PW);
     hipStream_t s = (hipStream_t)stream;
-    std::vector<PanoView> tab((size_t)n);
+    static_assert(sizeof(PanoView) % sizeof(int) == 0, "the view records are kept as ints");
+    constexpr size_t kRec = sizeof(PanoView) / sizeof(int);
+    std::vector<int> tab((size_t)n * kRec, 0);
     int max_tiles = 0;
     double out_bytes = 0.0;
     for (int f = 0; f < n; ++f) {
@@ -1687,24 +1768,19 @@ int specmi_pano_extract_views(specmi_handle* h, const uint8_t* pano, int PH, int
             return fail(h, SPECMI_ERR_ARG, "view %d: vfov %g degrees (0 < vfov < 180) / ratio %g (> 0)", f, v[3], v[4]);
         if (H < 1 || W < 1) return fail(h, SPECMI_ERR_ARG, "view %d: size %d x %d", f, H, W);
         if ((double)H * W >= 2147483648.0 / 3) return fail(h, SPECMI_ERR_ARG, "view %d: %d x %d pixels are beyond 31-bit offsets", f, H, W);
-        if (offsets[f] < 0 || (double)offsets[f] + (double)H * W * 3 > (double)slab_bytes)
+        if (!rect_in_slab(offsets[f], 3LL * W, H, W, slab_bytes))
             return fail(h, SPECMI_ERR_ARG, "view %d: %d x %d x 3 bytes at offset %lld leave the slab of %zu bytes", f, H, W, (long long)offsets[f], slab_bytes);
-        if (!make_pano_view(v, H, W, (long long)offsets[f], tab[f]))
+        PanoView r{};
+        if (!make_pano_view(v, H, W, (long long)offsets[f], r))
             return fail(h, SPECMI_ERR_ARG, "view %d: a height of %d at ratio %g gives a width of round(h * ratio), not %d", f, H, v[4], W);
+        std::memcpy(tab.data() + (size_t)f * kRec, &r, sizeof(r));
         max_tiles = std::max(max_tiles, pano_view_tiles(H, W));
         out_bytes += (double)H * W * 3;
     }
-    int rc;
-    const bool regrown = tab.size() * sizeof(PanoView) > h->pano_tab_bytes;
-    if ((rc = grow_ragged(h, (void**)&h->pano_tab, &h->pano_tab_bytes, tab.size() * sizeof(PanoView), "the panorama view table"))) return rc;
-    if (regrown || tab.size() != h->pano_host.size() || std::memcmp(tab.data(), h->pano_host.data(), tab.size() * sizeof(PanoView))) {
-        // an extraction enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
-        if (!regrown && (rc = sync_for_growth(h, "the panorama view table"))) return rc;
-        h->pano_host.swap(tab);
-        HIPCHK(h, hipMemcpyAsync(h->pano_tab, h->pano_host.data(), h->pano_host.size() * sizeof(PanoView), hipMemcpyHostToDevice, s));
-    }
+    DevTable& T = h->tab[TAB_pano];
+    if (int rc = publish_table(h, T, tab, "the panorama view table", nullptr, s)) return rc;
     LaunchCtx ctx{s, &h->prof, "preprocess.pano_views"};
-    LAUNCHCHK(h, launch_pano_extract(pano, PH, PW, h->pano_tab, n, max_tiles, out_bytes, out_slab, ctx), "pano_extract_views");
+    LAUNCHCHK(h, launch_pano_extract(pano, PH, PW, (const PanoView*)T.dev.p, n, max_tiles, out_bytes, out_slab, ctx), "pano_extract_views");
     return SPECMI_OK;
 }
 
@@ -1731,8 +1807,8 @@ int specmi_render_meshes(specmi_handle* h, const float* vertices, int M, int V, 
     }
     size_t off[4];
     const size_t need = render_ws_layout(M, V, H, W, off);
-    if (int rc = grow_ragged(h, &h->render_ws, &h->render_ws_bytes, need, "the render workspace")) return rc;
-    char* ws = (char*)h->render_ws;
+    if (int rc = grow_ragged(h, h->buf[BUF_render], need, "the render workspace")) return rc;
+    char* ws = (char*)h->buf[BUF_render].p;
     a.vertices = vertices; a.faces = faces; a.cam_t = cam_t; a.R = R; a.frame = frame;
     a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy;
     a.M = M; a.V = V; a.F = F; a.H = H; a.W = W; a.side = side; a.ground = ground; a.cull = (flags & SPECMI_RENDER_CULL) ? 1 : 0;
@@ -1742,26 +1818,6 @@ int specmi_render_meshes(specmi_handle* h, const float* vertices, int M, int V, 
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, side ? "render.side_view" : "render.overlay"};
     LAUNCHCHK(h, launch_render(a, (flags & SPECMI_RENDER_THREAD_PER_TRIANGLE) != 0, ctx), "render_meshes");
     return SPECMI_OK;
-}
-
-// do the output rectangles of two views share a byte?  a rectangle = H rows of 3 W bytes, `pitch` bytes apart, from `off`
-struct ByteRect { long long off, pitch, row; int H; long long end() const { return off + (H - 1) * pitch + row; } };
-static bool rects_overlap(ByteRect a, ByteRect b) {
-    if (a.off > b.off) std::swap(a, b);
-    if (b.off >= a.end()) return false;
-    if (a.pitch == b.pitch) {       // the columns of one picture: b starts c bytes into row q of a
-        const long long q = (b.off - a.off) / a.pitch, c = (b.off - a.off) % a.pitch;
-        return (q < a.H && c < a.row) || (q + 1 < a.H && c + b.row > a.pitch);
-    }
-    for (int r = 0; r < b.H; ++r) {      // row r of b against the rows of a it reaches
-        const long long s0 = b.off + r * b.pitch - a.off, e0 = s0 + b.row - 1;     // first and last byte, counted from a's first
-        if (s0 >= a.end() - a.off) break;
-        const long long k1 = s0 / a.pitch, k2 = std::min<long long>(e0 / a.pitch, a.H - 1);
-        if (k2 - k1 >= 2) return true;                                              // a whole row of a lies inside
-        for (long long k = k1; k <= k2; ++k)
-            if (std::max(s0, k * a.pitch) <= std::min(e0, k * a.pitch + a.row - 1)) return true;
-    }
-    return false;
 }
 
 int specmi_render_views(specmi_handle* h, const float* vertices, int Mtot, int V, const int32_t* faces, int F, const float* cam_t,
@@ -1775,7 +1831,7 @@ int specmi_render_views(specmi_handle* h, const float* vertices, int Mtot, int V
     if (Mtot < 0 || V < 1 || F < 1) return fail(h, SPECMI_ERR_ARG, "%d meshes of %d vertices and %d faces", Mtot, V, F);
     if (in_slab_bytes >= 4294967296.0 || out_slab_bytes >= 4294967296.0)
         return fail(h, SPECMI_ERR_ARG, "slabs of %zu / %zu bytes are beyond the kernels' 32-bit offsets", in_slab_bytes, out_slab_bytes);
-    if (in_slab && (const uint8_t*)out_slab < in_slab + in_slab_bytes && in_slab < (const uint8_t*)out_slab + out_slab_bytes)
+    if (in_slab && slabs_overlap(in_slab, in_slab_bytes, out_slab, out_slab_bytes))
         return fail(h, SPECMI_ERR_ARG, "the frame slab and the output slab overlap");
     RenderViewsArgs b{};
     for (int k = 0; k < 3; ++k) {
@@ -1808,9 +1864,9 @@ int specmi_render_views(specmi_handle* h, const float* vertices, int Mtot, int V
         if (in_off >= 0 && !in_slab) return fail(h, SPECMI_ERR_ARG, "view %d: names a frame, but the frame slab is a null pointer", v);
         if (out_pitch < 3LL * W || (in_off >= 0 && in_pitch < 3LL * W))
             return fail(h, SPECMI_ERR_ARG, "view %d: pitches of %lld / %lld bytes for rows of %d", v, (long long)in_pitch, (long long)out_pitch, 3 * W);
-        if (out_off < 0 || (double)out_off + (double)(H - 1) * (double)out_pitch + 3.0 * W > (double)out_slab_bytes)
+        if (!rect_in_slab(out_off, out_pitch, H, W, out_slab_bytes))
             return fail(h, SPECMI_ERR_ARG, "view %d: its output rectangle leaves the slab of %zu bytes", v, out_slab_bytes);
-        if (in_off >= 0 && (double)in_off + (double)(H - 1) * (double)in_pitch + 3.0 * W > (double)in_slab_bytes)
+        if (in_off >= 0 && !rect_in_slab(in_off, in_pitch, H, W, in_slab_bytes))
             return fail(h, SPECMI_ERR_ARG, "view %d: its frame leaves the slab of %zu bytes", v, in_slab_bytes);
         if (!(cam[9] > 0.f) || !(cam[10] > 0.f) || !std::isfinite(cam[9]) || !std::isfinite(cam[10]) || !std::isfinite(cam[11]) || !std::isfinite(cam[12]))
             return fail(h, SPECMI_ERR_ARG, "view %d: focal length (%g, %g) (> 0, finite) / centre (%g, %g) (finite)", v, (double)cam[9], (double)cam[10],
@@ -1821,9 +1877,8 @@ int specmi_render_views(specmi_handle* h, const float* vertices, int Mtot, int V
         std::memcpy(r.R, cam, 13 * sizeof(float));
         r.H = H; r.W = W; r.mesh0 = mesh0; r.count = count; r.side = side; r.ground = ground; r.cull = (flags & SPECMI_RENDER_CULL) ? 1 : 0;
         r.pair0 = (int)pairs; r.px0 = (int)px; r.key0 = count ? (int)keys : -1;
-        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal views give equal records
-        r.in_off = in_off >= 0 ? (unsigned)in_off : 0u; r.in_pitch = (in_off >= 0 && H > 1) ? (unsigned)in_pitch : 3u * W;
-        r.out_off = (unsigned)out_off; r.out_pitch = H > 1 ? (unsigned)out_pitch : 3u * W;
+        r.in_off = in_off >= 0 ? (unsigned)in_off : 0u; r.in_pitch = in_off >= 0 ? (unsigned)stored_pitch(in_pitch, H, W) : 3u * W;
+        r.out_off = (unsigned)out_off; r.out_pitch = (unsigned)stored_pitch(out_pitch, H, W);
         std::memcpy(tab.data() + (size_t)v * kRenderViewRec, &r, sizeof(r));
         tab[(size_t)nviews * kRenderViewRec + v] = (int)px;
         rects[v] = ByteRect{out_off, (long long)r.out_pitch, 3LL * W, H};
@@ -1837,40 +1892,20 @@ int specmi_render_views(specmi_handle* h, const float* vertices, int Mtot, int V
         tab.insert(tab.end(), (size_t)count, v);
     }
     tab[(size_t)nviews * kRenderViewRec + nviews] = (int)px;
-    {   // no two output rectangles share a byte: sorted by first byte, a view is compared with those that start before it ends
-        std::vector<int> order((size_t)nviews);
-        for (int v = 0; v < nviews; ++v) order[v] = v;
-        std::sort(order.begin(), order.end(), [&](int x, int y) { return rects[x].off < rects[y].off; });
-        for (int i = 0; i < nviews; ++i)
-            for (int j = i + 1; j < nviews && rects[order[j]].off < rects[order[i]].end(); ++j)
-                if (rects_overlap(rects[order[i]], rects[order[j]]))
-                    return fail(h, SPECMI_ERR_ARG, "the output rectangles of views %d and %d overlap", order[i], order[j]);
-    }
+    int ra, rb;
+    if (first_overlap(rects, &ra, &rb)) return fail(h, SPECMI_ERR_ARG, "the output rectangles of views %d and %d overlap", ra, rb);
     hipStream_t s = (hipStream_t)stream;
     size_t off[4];
     const size_t need = render_views_ws_layout(keys, pairs, V, nviews, off);
-    const bool regrown = tab.size() * 4 > h->views_tab_bytes;
-    if (need > h->render_ws_bytes || regrown || tab != h->views_host) {
-        // both need a whole-device synchronise, which would invalidate a capture under way on this stream: ask first and leave it valid
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-        else if (cs != hipStreamCaptureStatusNone)
-            return fail(h, SPECMI_ERR_STATE, "new view records or a larger render workspace are not possible while the stream is being captured: "
-                        "run one eager call with these views first (nothing was enqueued)");
-    }
-    int rc;
-    if ((rc = grow_ragged(h, &h->render_ws, &h->render_ws_bytes, need, "the render workspace"))) return rc;
-    if ((rc = grow_ragged(h, (void**)&h->views_tab, &h->views_tab_bytes, tab.size() * 4, "the render view table"))) return rc;
-    if (regrown || tab != h->views_host) {
-        // views enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
-        if (!regrown && (rc = sync_for_growth(h, "the render view table"))) return rc;
-        h->views_host.swap(tab);
-        HIPCHK(h, hipMemcpyAsync(h->views_tab, h->views_host.data(), h->views_host.size() * 4, hipMemcpyHostToDevice, s));
-    }
-    char* ws = (char*)h->render_ws;
+    DevTable& T = h->tab[TAB_views];
+    if (int rc = publish_table(h, T, tab, "the render view table", "new view records or a larger render workspace", s, &h->buf[BUF_render], need,
+                               "the render workspace"))
+        return rc;
+    char* ws = (char*)h->buf[BUF_render].p;
+    const int* dtab = (const int*)T.dev.p;
     b.vertices = vertices; b.faces = faces; b.cam_t = cam_t;
-    b.views = (const RenderView*)h->views_tab;
-    b.px_prefix = h->views_tab + (size_t)nviews * kRenderViewRec;
+    b.views = (const RenderView*)dtab;
+    b.px_prefix = dtab + (size_t)nviews * kRenderViewRec;
     b.pair_view = b.px_prefix + nviews + 1;
     b.in_slab = in_slab; b.out_slab = out_slab;
     b.V = V; b.F = F; b.nviews = nviews; b.npairs = (int)pairs; b.total_px = (int)px;
@@ -1910,12 +1945,9 @@ int specmi_draw_skeletons(specmi_handle* h, const float* kp, int Mtot, int J, in
             return fail(h, SPECMI_ERR_ARG, "frame %d: %d x %d pixels (1 .. %d per side: the exact 64-bit coverage test)", f, H, W, kDrawMaxSide);
         if (count < 0 || det0 < 0 || (long long)det0 + count > Mtot)
             return fail(h, SPECMI_ERR_ARG, "frame %d: detections %d .. %lld leave the call's %d", f, det0, (long long)det0 + count, Mtot);
-        if (pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "frame %d: a pitch of %lld bytes for rows of %d", f, (long long)pitch, 3 * W);
-        if (off < 0 || (double)off + (double)(H - 1) * (double)pitch + 3.0 * W > (double)slab_bytes)
-            return fail(h, SPECMI_ERR_ARG, "frame %d: its rectangle leaves the slab of %zu bytes", f, slab_bytes);
+        if (int rc = check_rect(h, "frame", f, off, pitch, H, W, slab_bytes)) return rc;
         DrawFrame r{};
-        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal frames give equal records
-        r.off = off; r.pitch = H > 1 ? pitch : 3LL * W; r.H = H; r.W = W; r.det0 = det0; r.count = count; r.tile0 = (int)tiles;
+        r.off = off; r.pitch = stored_pitch(pitch, H, W); r.H = H; r.W = W; r.det0 = det0; r.count = count; r.tile0 = (int)tiles;
         const int n = draw_frame_tiles(H, W, &r.tiles_x);
         if (count) {
             tiles += n;
@@ -1926,36 +1958,15 @@ int specmi_draw_skeletons(specmi_handle* h, const float* kp, int Mtot, int J, in
         std::memcpy(tab.data() + (size_t)f * kDrawFrameRec, &r, sizeof(r));
         rects[f] = ByteRect{off, r.pitch, 3LL * W, H};
     }
-    {   // no two frames share a byte: sorted by first byte, a frame is compared with those that start before it ends
-        std::vector<int> order((size_t)nframes);
-        for (int f = 0; f < nframes; ++f) order[f] = f;
-        std::sort(order.begin(), order.end(), [&](int x, int y) { return rects[x].off < rects[y].off; });
-        for (int i = 0; i < nframes; ++i)
-            for (int j = i + 1; j < nframes && rects[order[j]].off < rects[order[i]].end(); ++j)
-                if (rects_overlap(rects[order[i]], rects[order[j]]))
-                    return fail(h, SPECMI_ERR_ARG, "frames %d and %d share a byte", order[i], order[j]);
-    }
+    int ra, rb;
+    if (first_overlap(rects, &ra, &rb)) return fail(h, SPECMI_ERR_ARG, "frames %d and %d share a byte", ra, rb);
     tab.insert(tab.end(), bones, bones + 2 * (size_t)NB);
     hipStream_t s = (hipStream_t)stream;
-    const bool regrown = tab.size() * 4 > h->draw_tab_bytes;
-    if (regrown || tab != h->draw_host) {
-        // rewriting the table needs a whole-device synchronise, which would invalidate a capture under way on this stream: ask first
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-        else if (cs != hipStreamCaptureStatusNone)
-            return fail(h, SPECMI_ERR_STATE, "new frame records or bones are not possible while the stream is being captured: "
-                        "run one eager call with these records first (nothing was enqueued)");
-    }
-    int rc;
-    if ((rc = grow_ragged(h, (void**)&h->draw_tab, &h->draw_tab_bytes, tab.size() * 4, "the skeleton frame table"))) return rc;
-    if (regrown || tab != h->draw_host) {
-        // a drawing enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
-        if (!regrown && (rc = sync_for_growth(h, "the skeleton frame table"))) return rc;
-        h->draw_host.swap(tab);
-        HIPCHK(h, hipMemcpyAsync(h->draw_tab, h->draw_host.data(), h->draw_host.size() * 4, hipMemcpyHostToDevice, s));
-    }
+    DevTable& T = h->tab[TAB_draw];
+    if (int rc = publish_table(h, T, tab, "the skeleton frame table", "new frame records or bones", s)) return rc;
+    const int* dtab = (const int*)T.dev.p;
     DrawArgs a{};
-    a.kp = kp; a.frames = (const DrawFrame*)h->draw_tab; a.bones = h->draw_tab + (size_t)nframes * kDrawFrameRec; a.slab = slab;
+    a.kp = kp; a.frames = (const DrawFrame*)dtab; a.bones = dtab + (size_t)nframes * kDrawFrameRec; a.slab = slab;
     a.nframes = nframes; a.J = J; a.D = D; a.NB = NB; a.radius = st.radius; a.thickness = st.thickness; a.thr = st.conf_thr;
     const auto pack = [](const uint8_t* c) { return (unsigned)c[0] | (unsigned)c[1] << 8 | (unsigned)c[2] << 16; };
     a.rgb[0] = pack(st.joint_rgb); a.rgb[1] = pack(st.bone_rgb[0]); a.rgb[2] = pack(st.bone_rgb[1]);
@@ -2034,12 +2045,9 @@ int specmi_draw_marks(specmi_handle* h, uint8_t* slab, size_t slab_bytes, const 
         if (H < 1 || W < 1 || H > kMarkMaxSide || W > kMarkMaxSide) return fail(h, SPECMI_ERR_ARG, "frame %d: %d x %d pixels (1 .. %d per side)", f, H, W, kMarkMaxSide);
         if (count < 0 || mark0 < 0 || (long long)mark0 + count > nmarks)
             return fail(h, SPECMI_ERR_ARG, "frame %d: marks %d .. %lld leave the call's %d", f, mark0, (long long)mark0 + count, nmarks);
-        if (pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "frame %d: a pitch of %lld bytes for rows of %d", f, (long long)pitch, 3 * W);
-        if (off < 0 || (double)off + (double)(H - 1) * (double)pitch + 3.0 * W > (double)slab_bytes)
-            return fail(h, SPECMI_ERR_ARG, "frame %d: its rectangle leaves the slab of %zu bytes", f, slab_bytes);
+        if (int rc = check_rect(h, "frame", f, off, pitch, H, W, slab_bytes)) return rc;
         MarkFrame r{};
-        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal frames give equal records
-        r.off = off; r.pitch = H > 1 ? pitch : 3LL * W; r.H = H; r.W = W; r.mark0 = mark0; r.count = count;
+        r.off = off; r.pitch = stored_pitch(pitch, H, W); r.H = H; r.W = W; r.mark0 = mark0; r.count = count;
         std::memcpy(tab.data() + (size_t)f * kMarkFrameRec, &r, sizeof(r));
         rects[f] = ByteRect{off, r.pitch, 3LL * W, H};
         if (!count) continue;
@@ -2079,35 +2087,14 @@ int specmi_draw_marks(specmi_handle* h, uint8_t* slab, size_t slab_bytes, const 
             }
         if (ntiles >= (1LL << 30)) return fail(h, SPECMI_ERR_ARG, "the marks reach 2^30 tiles of %d x %d pixels or more", kMarkTileW, kMarkTileH);
     }
-    {   // no two frames share a byte: sorted by first byte, a frame is compared with those that start before it ends
-        std::vector<int> order((size_t)nframes);
-        for (int f = 0; f < nframes; ++f) order[f] = f;
-        std::sort(order.begin(), order.end(), [&](int x, int y) { return rects[x].off < rects[y].off; });
-        for (int i = 0; i < nframes; ++i)
-            for (int j = i + 1; j < nframes && rects[order[j]].off < rects[order[i]].end(); ++j)
-                if (rects_overlap(rects[order[i]], rects[order[j]]))
-                    return fail(h, SPECMI_ERR_ARG, "frames %d and %d share a byte", order[i], order[j]);
-    }
+    int ra, rb;
+    if (first_overlap(rects, &ra, &rb)) return fail(h, SPECMI_ERR_ARG, "frames %d and %d share a byte", ra, rb);
     hipStream_t s = (hipStream_t)stream;
-    const bool regrown = tab.size() * 4 > h->marks_tab_bytes;
-    if (regrown || tab != h->marks_host) {
-        // rewriting the table needs a whole-device synchronise, which would invalidate a capture under way on this stream: ask first
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-        else if (cs != hipStreamCaptureStatusNone)
-            return fail(h, SPECMI_ERR_STATE, "new frame or mark records are not possible while the stream is being captured: "
-                        "run one eager call with these records first (nothing was enqueued)");
-    }
-    int rc;
-    if ((rc = grow_ragged(h, (void**)&h->marks_tab, &h->marks_tab_bytes, tab.size() * 4, "the marks table"))) return rc;
-    if (regrown || tab != h->marks_host) {
-        // a drawing enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
-        if (!regrown && (rc = sync_for_growth(h, "the marks table"))) return rc;
-        h->marks_host.swap(tab);
-        HIPCHK(h, hipMemcpyAsync(h->marks_tab, h->marks_host.data(), h->marks_host.size() * 4, hipMemcpyHostToDevice, s));
-    }
+    DevTable& T = h->tab[TAB_marks];
+    if (int rc = publish_table(h, T, tab, "the marks table", "new frame or mark records", s)) return rc;
+    const int* dtab = (const int*)T.dev.p;
     MarksArgs a{};
-    a.frames = (const MarkFrame*)h->marks_tab; a.marks = (const MarkDev*)(h->marks_tab + marks_at); a.tiles = h->marks_tab + tiles_at;
+    a.frames = (const MarkFrame*)dtab; a.marks = (const MarkDev*)(dtab + marks_at); a.tiles = dtab + tiles_at;
     a.masks = masks; a.slab = slab; a.ntiles = (int)ntiles;
     LaunchCtx ctx{s, &h->prof, "render.marks"};
     LAUNCHCHK(h, launch_draw_marks(a, (double)ntiles * kMarkTileW * kMarkTileH, ctx), "draw_marks");
@@ -2122,7 +2109,7 @@ int specmi_denormalize_u8(specmi_handle* h, const float* x, int B, int Hp, int W
     if (index < 0 || index >= B) return fail(h, SPECMI_ERR_ARG, "image %d of %d", index, B);
     if (H < 1 || H > Hp || W < 1 || W > Wp) return fail(h, SPECMI_ERR_ARG, "a frame of %d x %d out of an image of %d x %d", H, W, Hp, Wp);
     if (pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "a pitch of %lld bytes for rows of %d", (long long)pitch, 3 * W);
-    if (offset < 0 || (double)offset + (double)(H - 1) * (double)pitch + 3.0 * W > (double)slab_bytes)
+    if (!rect_in_slab(offset, pitch, H, W, slab_bytes))
         return fail(h, SPECMI_ERR_ARG, "the frame's rectangle leaves the slab of %zu bytes", slab_bytes);
     static const float kMean[3] = {0.485f, 0.456f, 0.406f}, kStd[3] = {0.229f, 0.224f, 0.225f};     // ImageNet's, as pare's denormalize_images
     DenormArgs a{};
@@ -2137,32 +2124,55 @@ int specmi_denormalize_u8(specmi_handle* h, const float* x, int B, int Hp, int W
     return SPECMI_OK;
 }
 
+// ---- what specmi_jpeg_encode and specmi_png_encode check alike, each part where both check it ------------------------------------
+struct EncodePic { int H, W; long long in_off, in_pitch, out_off, cap; };      // in_pitch as the records store it
+
+static int encode_call_checks(specmi_handle* h, const uint8_t* in_slab, const uint8_t* out_slab, const int32_t* pic_geom,
+                              const int64_t* pic_offsets, int n, const int64_t* sizes) {
+    if (!in_slab || !out_slab || !pic_geom || !pic_offsets || !sizes) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (n <= 0 || n > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 pictures per call, got %d", n);
+    return SPECMI_OK;
+}
+
+// picture i: its geometry, its rectangle in the picture slab and its room in the output slab, min_cap bytes (`min_cap_what`) at least
+static int encode_pic_checks(specmi_handle* h, int i, const int32_t* pic_geom, const int64_t* pic_offsets, size_t in_slab_bytes,
+                             size_t out_slab_bytes, int min_cap, const char* min_cap_what, EncodePic* p) {
+    const int H = pic_geom[2 * i], W = pic_geom[2 * i + 1];
+    const long long in_off = pic_offsets[4 * i], in_pitch = pic_offsets[4 * i + 1], out_off = pic_offsets[4 * i + 2], cap = pic_offsets[4 * i + 3];
+    if (H < 1 || W < 1 || H > 32768 || W > 32768) return fail(h, SPECMI_ERR_ARG, "picture %d: %d x %d pixels (1 .. 32768 per side)", i, H, W);
+    if (int rc = check_rect(h, "picture", i, in_off, in_pitch, H, W, in_slab_bytes)) return rc;
+    if (cap < min_cap) return fail(h, SPECMI_ERR_ARG, "picture %d: a capacity of %lld bytes is below %s %d", i, cap, min_cap_what, min_cap);
+    if (out_off < 0 || (double)out_off + (double)cap > (double)out_slab_bytes)
+        return fail(h, SPECMI_ERR_ARG, "picture %d: its output leaves the slab of %zu bytes", i, out_slab_bytes);
+    *p = EncodePic{H, W, in_off, stored_pitch(in_pitch, H, W), out_off, cap};
+    return SPECMI_OK;
+}
+
+// after the pictures: no two outputs (first byte, capacity) share a byte
+static int encode_outputs_disjoint(specmi_handle* h, std::vector<std::pair<long long, long long>>& outs) {
+    long long at;
+    if (first_shared_byte(outs, &at)) return fail(h, SPECMI_ERR_ARG, "two outputs share a byte (at offset %lld)", at);
+    return SPECMI_OK;
+}
+
 int specmi_jpeg_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_bytes, uint8_t* out_slab, size_t out_slab_bytes,
                        const int32_t* pic_geom, const int64_t* pic_offsets, int n, int quality, int64_t* sizes, void* stream) {
     ENTER(h);
-    if (!in_slab || !out_slab || !pic_geom || !pic_offsets || !sizes) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
-    if (n <= 0 || n > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 pictures per call, got %d", n);
+    int rc;
+    if ((rc = encode_call_checks(h, in_slab, out_slab, pic_geom, pic_offsets, n, sizes))) return rc;
     if (quality < 1 || quality > 100) return fail(h, SPECMI_ERR_ARG, "quality %d (1 .. 100)", quality);
-    if ((const uint8_t*)out_slab < in_slab + in_slab_bytes && in_slab < (const uint8_t*)out_slab + out_slab_bytes)
-        return fail(h, SPECMI_ERR_ARG, "the picture slab and the output slab overlap");
+    if (slabs_overlap(in_slab, in_slab_bytes, out_slab, out_slab_bytes)) return fail(h, SPECMI_ERR_ARG, "the picture slab and the output slab overlap");
     // [n records | JpegTables]
     std::vector<int> tab((size_t)n * kJpegPicRec + sizeof(JpegTables) / 4, 0);
     std::vector<std::pair<long long, long long>> outs((size_t)n);       // first byte, capacity
     long long mcus = 0, mchunks = 0, bchunks = 0;
     double px = 0.0;
     for (int i = 0; i < n; ++i) {
-        const int H = pic_geom[2 * i], W = pic_geom[2 * i + 1];
-        const int64_t in_off = pic_offsets[4 * i], in_pitch = pic_offsets[4 * i + 1], out_off = pic_offsets[4 * i + 2], cap = pic_offsets[4 * i + 3];
-        if (H < 1 || W < 1 || H > 32768 || W > 32768) return fail(h, SPECMI_ERR_ARG, "picture %d: %d x %d pixels (1 .. 32768 per side)", i, H, W);
-        if (in_pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "picture %d: a pitch of %lld bytes for rows of %d", i, (long long)in_pitch, 3 * W);
-        if (in_off < 0 || (double)in_off + (double)(H - 1) * (double)in_pitch + 3.0 * W > (double)in_slab_bytes)
-            return fail(h, SPECMI_ERR_ARG, "picture %d: its rectangle leaves the slab of %zu bytes", i, in_slab_bytes);
-        if (cap < kJpegHeaderBytes) return fail(h, SPECMI_ERR_ARG, "picture %d: a capacity of %lld bytes is below the header's %d", i, (long long)cap, kJpegHeaderBytes);
-        if (out_off < 0 || (double)out_off + (double)cap > (double)out_slab_bytes)
-            return fail(h, SPECMI_ERR_ARG, "picture %d: its output leaves the slab of %zu bytes", i, out_slab_bytes);
+        EncodePic p;
+        if ((rc = encode_pic_checks(h, i, pic_geom, pic_offsets, in_slab_bytes, out_slab_bytes, kJpegHeaderBytes, "the header's", &p))) return rc;
+        const int H = p.H, W = p.W;
         JpegPic r{};
-        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal pictures give equal records
-        r.in_off = in_off; r.in_pitch = H > 1 ? in_pitch : 3LL * W; r.out_off = out_off; r.cap = cap;
+        r.in_off = p.in_off; r.in_pitch = p.in_pitch; r.out_off = p.out_off; r.cap = p.cap;
         r.H = H; r.W = W; r.mx = (W + 15) / 16; r.my = (H + 15) / 16;
         r.mcu0 = (int)mcus; r.mchunk0 = (int)mchunks; r.bchunk0 = (int)bchunks;
         const long long m = (long long)r.mx * r.my;
@@ -2172,39 +2182,24 @@ int specmi_jpeg_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_
         px += (double)H * W;
         if (mcus > kJpegMaxMcus) return fail(h, SPECMI_ERR_ARG, "the pictures hold more than 2^24 blocks of 16 x 16 pixels");
         std::memcpy(tab.data() + (size_t)i * kJpegPicRec, &r, sizeof(r));
-        outs[i] = {out_off, cap};
+        outs[i] = {p.out_off, p.cap};
     }
-    std::sort(outs.begin(), outs.end());
-    for (int i = 0; i + 1 < n; ++i)
-        if (outs[i].first + outs[i].second > outs[i + 1].first) return fail(h, SPECMI_ERR_ARG, "two outputs share a byte (at offset %lld)", outs[i + 1].first);
+    if ((rc = encode_outputs_disjoint(h, outs))) return rc;
     JpegTables tables;
     jpeg_build_tables(quality, &tables);
     std::memcpy(tab.data() + (size_t)n * kJpegPicRec, &tables, sizeof(tables));
     hipStream_t s = (hipStream_t)stream;
     size_t off[8];
     const size_t need = jpeg_ws_layout(n, mcus, mchunks, bchunks, off);
-    const bool regrown = tab.size() * 4 > h->jpeg_tab_bytes;
-    if (need > h->jpeg_ws_bytes || regrown || tab != h->jpeg_host) {
-        // both need a whole-device synchronise, which would invalidate a capture under way on this stream: ask first and leave it valid
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-        else if (cs != hipStreamCaptureStatusNone)
-            return fail(h, SPECMI_ERR_STATE, "new picture records, another quality or a larger encoder workspace are not possible while the stream "
-                        "is being captured: run one eager call with these records first (nothing was enqueued)");
-    }
-    int rc;
-    if ((rc = grow_ragged(h, &h->jpeg_ws, &h->jpeg_ws_bytes, need, "the JPEG workspace"))) return rc;
-    if ((rc = grow_ragged(h, (void**)&h->jpeg_tab, &h->jpeg_tab_bytes, tab.size() * 4, "the JPEG picture table"))) return rc;
-    if (regrown || tab != h->jpeg_host) {
-        // an encode enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
-        if (!regrown && (rc = sync_for_growth(h, "the JPEG picture table"))) return rc;
-        h->jpeg_host.swap(tab);
-        HIPCHK(h, hipMemcpyAsync(h->jpeg_tab, h->jpeg_host.data(), h->jpeg_host.size() * 4, hipMemcpyHostToDevice, s));
-    }
-    char* ws = (char*)h->jpeg_ws;
+    DevTable& T = h->tab[TAB_jpeg];
+    if ((rc = publish_table(h, T, tab, "the JPEG picture table", "new picture records, another quality or a larger encoder workspace", s,
+                            &h->buf[BUF_jpeg], need, "the JPEG workspace")))
+        return rc;
+    char* ws = (char*)h->buf[BUF_jpeg].p;
+    const int* dtab = (const int*)T.dev.p;
     JpegArgs a{};
     a.in = in_slab; a.out = out_slab; a.sizes = (long long*)sizes;
-    a.pics = (const JpegPic*)h->jpeg_tab; a.tabs = (const JpegTables*)(h->jpeg_tab + (size_t)n * kJpegPicRec);
+    a.pics = (const JpegPic*)dtab; a.tabs = (const JpegTables*)(dtab + (size_t)n * kJpegPicRec);
     a.coef = (short*)(ws + off[0]); a.mcu_bits = (unsigned*)(ws + off[1]); a.mchunk_sum = (unsigned*)(ws + off[2]);
     a.mchunk_base = (unsigned long long*)(ws + off[3]); a.pic_bits = (unsigned long long*)(ws + off[4]); a.bitbuf = (unsigned*)(ws + off[5]);
     a.bchunk_ff = (unsigned*)(ws + off[6]); a.bchunk_base = (unsigned long long*)(ws + off[7]);
@@ -2217,65 +2212,41 @@ int specmi_jpeg_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_
 int specmi_png_encode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_bytes, uint8_t* out_slab, size_t out_slab_bytes,
                       const int32_t* pic_geom, const int64_t* pic_offsets, int n, int64_t* sizes, void* stream) {
     ENTER(h);
-    if (!in_slab || !out_slab || !pic_geom || !pic_offsets || !sizes) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
-    if (n <= 0 || n > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 pictures per call, got %d", n);
-    if ((const uint8_t*)out_slab < in_slab + in_slab_bytes && in_slab < (const uint8_t*)out_slab + out_slab_bytes)
-        return fail(h, SPECMI_ERR_ARG, "the picture slab and the output slab overlap");
+    int rc;
+    if ((rc = encode_call_checks(h, in_slab, out_slab, pic_geom, pic_offsets, n, sizes))) return rc;
+    if (slabs_overlap(in_slab, in_slab_bytes, out_slab, out_slab_bytes)) return fail(h, SPECMI_ERR_ARG, "the picture slab and the output slab overlap");
     std::vector<int> tab((size_t)n * kPngPicRec, 0);
     std::vector<std::pair<long long, long long>> outs((size_t)n);       // first byte, capacity
     long long rows = 0, segs = 0, filt = 0;
     double px = 0.0;
     for (int i = 0; i < n; ++i) {
-        const int H = pic_geom[2 * i], W = pic_geom[2 * i + 1];
-        const int64_t in_off = pic_offsets[4 * i], in_pitch = pic_offsets[4 * i + 1], out_off = pic_offsets[4 * i + 2], cap = pic_offsets[4 * i + 3];
-        if (H < 1 || W < 1 || H > 32768 || W > 32768) return fail(h, SPECMI_ERR_ARG, "picture %d: %d x %d pixels (1 .. 32768 per side)", i, H, W);
-        if (in_pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "picture %d: a pitch of %lld bytes for rows of %d", i, (long long)in_pitch, 3 * W);
-        if (in_off < 0 || (double)in_off + (double)(H - 1) * (double)in_pitch + 3.0 * W > (double)in_slab_bytes)
-            return fail(h, SPECMI_ERR_ARG, "picture %d: its rectangle leaves the slab of %zu bytes", i, in_slab_bytes);
-        if (cap < kPngOverhead) return fail(h, SPECMI_ERR_ARG, "picture %d: a capacity of %lld bytes is below the fixed overhead of %d", i, (long long)cap, kPngOverhead);
-        if (out_off < 0 || (double)out_off + (double)cap > (double)out_slab_bytes)
-            return fail(h, SPECMI_ERR_ARG, "picture %d: its output leaves the slab of %zu bytes", i, out_slab_bytes);
+        EncodePic p;
+        if ((rc = encode_pic_checks(h, i, pic_geom, pic_offsets, in_slab_bytes, out_slab_bytes, kPngOverhead, "the fixed overhead of", &p))) return rc;
+        const int H = p.H, W = p.W;
         // IDAT's length field: the zlib stream with every segment stored is the bound minus what stands around it
         if (png_bound(H, W) - (kPngOverhead - 6) >= (1LL << 31))
             return fail(h, SPECMI_ERR_ARG, "picture %d: the zlib stream of %d x %d pixels may not fit one IDAT chunk (2^31 bytes)", i, H, W);
         PngPic r{};
-        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal pictures give equal records
-        r.in_off = in_off; r.in_pitch = H > 1 ? in_pitch : 3LL * W; r.out_off = out_off; r.cap = cap;
+        r.in_off = p.in_off; r.in_pitch = p.in_pitch; r.out_off = p.out_off; r.cap = p.cap;
         r.H = H; r.W = W; r.stream = (long long)H * (1 + 3LL * W); r.filt_off = filt;
         r.row0 = (int)rows; r.seg0 = (int)segs; r.nseg = (int)((r.stream + kPngSegment - 1) / kPngSegment);
         rows += H; segs += r.nseg; filt += (r.stream + 255) & ~255LL;
         px += (double)H * W;
         if (segs > kPngMaxSegments) return fail(h, SPECMI_ERR_ARG, "the pictures' filtered streams hold more than 2^23 segments of 32768 bytes");
         std::memcpy(tab.data() + (size_t)i * kPngPicRec, &r, sizeof(r));
-        outs[i] = {out_off, cap};
+        outs[i] = {p.out_off, p.cap};
     }
-    std::sort(outs.begin(), outs.end());
-    for (int i = 0; i + 1 < n; ++i)
-        if (outs[i].first + outs[i].second > outs[i + 1].first) return fail(h, SPECMI_ERR_ARG, "two outputs share a byte (at offset %lld)", outs[i + 1].first);
+    if ((rc = encode_outputs_disjoint(h, outs))) return rc;
     hipStream_t s = (hipStream_t)stream;
     size_t off[7];
     const size_t need = png_ws_layout(n, filt, segs, off);
-    const bool regrown = tab.size() * 4 > h->png_tab_bytes;
-    if (need > h->png_ws_bytes || regrown || tab != h->png_host) {
-        // both need a whole-device synchronise, which would invalidate a capture under way on this stream: ask first and leave it valid
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-        else if (cs != hipStreamCaptureStatusNone)
-            return fail(h, SPECMI_ERR_STATE, "new picture records or a larger encoder workspace are not possible while the stream "
-                        "is being captured: run one eager call with these records first (nothing was enqueued)");
-    }
-    int rc;
-    if ((rc = grow_ragged(h, &h->png_ws, &h->png_ws_bytes, need, "the PNG workspace"))) return rc;
-    if ((rc = grow_ragged(h, (void**)&h->png_tab, &h->png_tab_bytes, tab.size() * 4, "the PNG picture table"))) return rc;
-    if (regrown || tab != h->png_host) {
-        // an encode enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
-        if (!regrown && (rc = sync_for_growth(h, "the PNG picture table"))) return rc;
-        h->png_host.swap(tab);
-        HIPCHK(h, hipMemcpyAsync(h->png_tab, h->png_host.data(), h->png_host.size() * 4, hipMemcpyHostToDevice, s));
-    }
-    char* ws = (char*)h->png_ws;
+    DevTable& T = h->tab[TAB_png];
+    if ((rc = publish_table(h, T, tab, "the PNG picture table", "new picture records or a larger encoder workspace", s, &h->buf[BUF_png], need,
+                            "the PNG workspace")))
+        return rc;
+    char* ws = (char*)h->buf[BUF_png].p;
     PngArgs a{};
-    a.in = in_slab; a.out = out_slab; a.sizes = (long long*)sizes; a.pics = (const PngPic*)h->png_tab;
+    a.in = in_slab; a.out = out_slab; a.sizes = (long long*)sizes; a.pics = (const PngPic*)T.dev.p;
     a.filt = (unsigned char*)(ws + off[0]); a.segbuf = (unsigned*)(ws + off[1]); a.seg_bytes = (unsigned*)(ws + off[2]);
     a.seg_sum = (unsigned*)(ws + off[3]); a.seg_base = (unsigned long long*)(ws + off[4]); a.seg_crc = (unsigned*)(ws + off[5]);
     a.pic_adler = (unsigned*)(ws + off[6]);
@@ -2300,8 +2271,7 @@ int specmi_jpeg_decode(specmi_handle* h, const uint8_t* files_host, const uint8_
     ENTER(h);
     if (!files_host || !in_slab || !file_ranges || !out_slab || !out_offsets || !status) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
     if (n <= 0 || n > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 files per call, got %d", n);
-    if ((const uint8_t*)out_slab < in_slab + in_slab_bytes && in_slab < (const uint8_t*)out_slab + out_slab_bytes)
-        return fail(h, SPECMI_ERR_ARG, "the file slab and the output slab overlap");
+    if (slabs_overlap(in_slab, in_slab_bytes, out_slab, out_slab_bytes)) return fail(h, SPECMI_ERR_ARG, "the file slab and the output slab overlap");
     std::vector<int> tab((size_t)n * (sizeof(JdecFile) / 4), 0);
     std::vector<ByteRect> rects((size_t)n);
     long long mcus = 0, blocks = 0, plane_bytes = 0, lanes = 0, groups = 0, bchunks = 0, pchunks = 0, max_groups = 1;
@@ -2313,12 +2283,9 @@ int specmi_jpeg_decode(specmi_handle* h, const uint8_t* files_host, const uint8_
         JdecFile f;
         const int reason = jpeg_probe(files_host + off, (size_t)len, &f);
         if (reason != JDEC_SUPPORTED) return fail(h, SPECMI_ERR_ARG, "file %d is not a supported baseline JPEG file (specmi_jpeg_probe: reason %d)", i, reason);
-        if (pitch < 3LL * f.W) return fail(h, SPECMI_ERR_ARG, "file %d: a pitch of %lld bytes for rows of %d", i, (long long)pitch, 3 * f.W);
-        if (out_off < 0 || (double)out_off + (double)(f.H - 1) * (double)pitch + 3.0 * f.W > (double)out_slab_bytes)
-            return fail(h, SPECMI_ERR_ARG, "file %d: its rectangle leaves the slab of %zu bytes", i, out_slab_bytes);
+        if (int rc = check_rect(h, "file", i, out_off, pitch, f.H, f.W, out_slab_bytes)) return rc;
         const long long m = (long long)f.mx * f.my;
-        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal files give equal records
-        f.scan_off += off; f.out_off = out_off; f.pitch = f.H > 1 ? pitch : 3LL * f.W;
+        f.scan_off += off; f.out_off = out_off; f.pitch = stored_pitch(pitch, f.H, f.W);
         f.block0 = blocks; f.plane0 = plane_bytes;
         f.nblocks = (int)(m * f.bpm);
         const long long nsub = std::max<long long>(1, (f.scan_len + kJdecSubBytes - 1) / kJdecSubBytes);
@@ -2339,39 +2306,22 @@ int specmi_jpeg_decode(specmi_handle* h, const uint8_t* files_host, const uint8_
         std::memcpy(tab.data() + (size_t)i * (sizeof(JdecFile) / 4), &f, sizeof(f));
         rects[i] = ByteRect{out_off, f.pitch, 3LL * f.W, f.H};
     }
-    {   // no two rectangles share a byte: sorted by first byte, one is compared with those that start before it ends
-        std::vector<int> order((size_t)n);
-        for (int i = 0; i < n; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](int x, int y) { return rects[x].off < rects[y].off; });
-        for (int i = 0; i < n; ++i)
-            for (int j = i + 1; j < n && rects[order[j]].off < rects[order[i]].end(); ++j)
-                if (rects_overlap(rects[order[i]], rects[order[j]]))
-                    return fail(h, SPECMI_ERR_ARG, "the output rectangles of files %d and %d share a byte", order[i], order[j]);
-    }
+    int ra, rb;
+    if (first_overlap(rects, &ra, &rb)) return fail(h, SPECMI_ERR_ARG, "the output rectangles of files %d and %d share a byte", ra, rb);
     if (coef && coef_bytes < (size_t)blocks * 128)
         return fail(h, SPECMI_ERR_ARG, "the coefficient output holds %zu bytes, these files have %lld", coef_bytes, blocks * 128);
     hipStream_t s = (hipStream_t)stream;
-    {   // the passes are counted on the host and the table is rewritten: neither is possible under capture; ask first and leave it valid
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-        else if (cs != hipStreamCaptureStatusNone)
-            return fail(h, SPECMI_ERR_STATE, "specmi_jpeg_decode is not possible while the stream is being captured (nothing was enqueued)");
-    }
+    // the passes are counted on the host, so EVERY call is refused under capture, repeated records or not: asked here, ahead of the
+    // table's own rule, which then has nothing left to ask
+    if (stream_is_capturing(s))
+        return fail(h, SPECMI_ERR_STATE, "specmi_jpeg_decode is not possible while the stream is being captured (nothing was enqueued)");
     size_t woff[8];
     const size_t need = jdec_ws_layout(blocks, plane_bytes, lanes, groups, woff);
-    const bool regrown = tab.size() * 4 > h->jdec_tab_bytes;
-    int rc;
-    if ((rc = grow_ragged(h, &h->jdec_ws, &h->jdec_ws_bytes, need, "the JPEG decoder workspace"))) return rc;
-    if ((rc = grow_ragged(h, (void**)&h->jdec_tab, &h->jdec_tab_bytes, tab.size() * 4, "the JPEG file table"))) return rc;
-    if (regrown || tab != h->jdec_host) {
-        // a decode enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
-        if (!regrown && (rc = sync_for_growth(h, "the JPEG file table"))) return rc;
-        h->jdec_host.swap(tab);
-        HIPCHK(h, hipMemcpyAsync(h->jdec_tab, h->jdec_host.data(), h->jdec_host.size() * 4, hipMemcpyHostToDevice, s));
-    }
-    char* ws = (char*)h->jdec_ws;
+    DevTable& T = h->tab[TAB_jdec];
+    if (int rc = publish_table(h, T, tab, "the JPEG file table", nullptr, s, &h->buf[BUF_jdec], need, "the JPEG decoder workspace")) return rc;
+    char* ws = (char*)h->buf[BUF_jdec].p;
     JdecArgs a{};
-    a.in = in_slab; a.out = out_slab; a.files = (const JdecFile*)h->jdec_tab; a.status = status;
+    a.in = in_slab; a.out = out_slab; a.files = (const JdecFile*)T.dev.p; a.status = status;
     a.coef = (short*)(ws + woff[0]); a.planes = (unsigned char*)(ws + woff[1]); a.entry = (unsigned*)(ws + woff[2]);
     a.exits = (unsigned*)(ws + woff[3]); a.count = (int*)(ws + woff[4]); a.first = (int*)(ws + woff[5]); a.gexit = (unsigned*)(ws + woff[6]);
     a.changed = (unsigned*)(ws + woff[7]);
@@ -2400,8 +2350,7 @@ int specmi_png_decode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_b
     ENTER(h);
     if (!in_slab || !stream_ranges || !geom || !out_slab || !out_offsets || !status) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
     if (n <= 0 || n > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 files per call, got %d", n);
-    if ((const uint8_t*)out_slab < in_slab + in_slab_bytes && in_slab < (const uint8_t*)out_slab + out_slab_bytes)
-        return fail(h, SPECMI_ERR_ARG, "the stream slab and the output slab overlap");
+    if (slabs_overlap(in_slab, in_slab_bytes, out_slab, out_slab_bytes)) return fail(h, SPECMI_ERR_ARG, "the stream slab and the output slab overlap");
     std::vector<int> tab((size_t)n * (sizeof(PdecFile) / 4), 0);
     std::vector<ByteRect> rects((size_t)n);
     long long raw_total = 0, chunks = 0;
@@ -2414,13 +2363,9 @@ int specmi_png_decode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_b
         if (len < 8) return fail(h, SPECMI_ERR_ARG, "file %d: a zlib stream of %lld bytes (8 at least: header, a block, Adler-32)", i, (long long)len);
         if (H < 1 || H > 32768 || W < 1 || W > 32768) return fail(h, SPECMI_ERR_ARG, "file %d: %d x %d pixels (1 .. 32768 per side)", i, H, W);
         if (ct != 0 && ct != 2 && ct != 4 && ct != 6) return fail(h, SPECMI_ERR_ARG, "file %d: colour type %d (0, 2, 4 or 6)", i, ct);
-        if (pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "file %d: a pitch of %lld bytes for rows of %d", i, (long long)pitch, 3 * W);
-        if (out_off < 0 || (double)out_off + (double)(H - 1) * (double)pitch + 3.0 * W > (double)out_slab_bytes)
-            return fail(h, SPECMI_ERR_ARG, "file %d: its rectangle leaves the slab of %zu bytes", i, out_slab_bytes);
+        if (int rc = check_rect(h, "file", i, out_off, pitch, H, W, out_slab_bytes)) return rc;
         PdecFile f{};
-        f.stream_off = off; f.stream_len = len; f.out_off = out_off;
-        // a single row has no next row: its pitch is not read, and is stored as 3 W so that equal files give equal records
-        f.pitch = H > 1 ? pitch : 3LL * W;
+        f.stream_off = off; f.stream_len = len; f.out_off = out_off; f.pitch = stored_pitch(pitch, H, W);
         f.H = H; f.W = W; f.bpp = ct == 0 ? 1 : ct == 2 ? 3 : ct == 4 ? 2 : 4; f.nch = (ct & 2) ? 3 : 1;
         f.raw_off = raw_total; f.raw_len = (long long)H * (1 + (long long)W * f.bpp);
         f.chunk0 = (int)chunks; f.nchunk = (int)((f.raw_len + kPdecAdlerChunk - 1) / kPdecAdlerChunk);
@@ -2432,41 +2377,20 @@ int specmi_png_decode(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_b
         std::memcpy(tab.data() + (size_t)i * (sizeof(PdecFile) / 4), &f, sizeof(f));
         rects[i] = ByteRect{out_off, f.pitch, 3LL * W, H};
     }
-    {   // no two rectangles share a byte: sorted by first byte, one is compared with those that start before it ends
-        std::vector<int> order((size_t)n);
-        for (int i = 0; i < n; ++i) order[i] = i;
-        std::sort(order.begin(), order.end(), [&](int x, int y) { return rects[x].off < rects[y].off; });
-        for (int i = 0; i < n; ++i)
-            for (int j = i + 1; j < n && rects[order[j]].off < rects[order[i]].end(); ++j)
-                if (rects_overlap(rects[order[i]], rects[order[j]]))
-                    return fail(h, SPECMI_ERR_ARG, "the output rectangles of files %d and %d share a byte", order[i], order[j]);
-    }
+    int ra, rb;
+    if (first_overlap(rects, &ra, &rb)) return fail(h, SPECMI_ERR_ARG, "the output rectangles of files %d and %d share a byte", ra, rb);
     if (raw && raw_bytes < (size_t)raw_total)
         return fail(h, SPECMI_ERR_ARG, "the raw output holds %zu bytes, these files' inflated streams take %lld", raw_bytes, raw_total);
     hipStream_t s = (hipStream_t)stream;
     size_t woff[3];
     const size_t need = pdec_ws_layout(n, raw_total, chunks, woff);
-    const bool regrown = tab.size() * 4 > h->pdec_tab_bytes;
-    if (need > h->pdec_ws_bytes || regrown || tab != h->pdec_host) {
-        // both need a whole-device synchronise, which would invalidate a capture under way on this stream: ask first and leave it valid
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) != hipSuccess) (void)hipGetLastError();
-        else if (cs != hipStreamCaptureStatusNone)
-            return fail(h, SPECMI_ERR_STATE, "new file records or a larger decoder workspace are not possible while the stream "
-                        "is being captured: run one eager call with these records first (nothing was enqueued)");
-    }
-    int rc;
-    if ((rc = grow_ragged(h, &h->pdec_ws, &h->pdec_ws_bytes, need, "the PNG decoder workspace"))) return rc;
-    if ((rc = grow_ragged(h, (void**)&h->pdec_tab, &h->pdec_tab_bytes, tab.size() * 4, "the PNG file table"))) return rc;
-    if (regrown || tab != h->pdec_host) {
-        // a decode enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
-        if (!regrown && (rc = sync_for_growth(h, "the PNG file table"))) return rc;
-        h->pdec_host.swap(tab);
-        HIPCHK(h, hipMemcpyAsync(h->pdec_tab, h->pdec_host.data(), h->pdec_host.size() * 4, hipMemcpyHostToDevice, s));
-    }
-    char* ws = (char*)h->pdec_ws;
+    DevTable& T = h->tab[TAB_pdec];
+    if (int rc = publish_table(h, T, tab, "the PNG file table", "new file records or a larger decoder workspace", s, &h->buf[BUF_pdec], need,
+                               "the PNG decoder workspace"))
+        return rc;
+    char* ws = (char*)h->buf[BUF_pdec].p;
     PdecArgs a{};
-    a.in = in_slab; a.out = out_slab; a.files = (const PdecFile*)h->pdec_tab; a.status = status;
+    a.in = in_slab; a.out = out_slab; a.files = (const PdecFile*)T.dev.p; a.status = status;
     a.raw = (unsigned char*)(ws + woff[0]); a.rec = (uint2*)(ws + woff[1]); a.sums = (uint2*)(ws + woff[2]);
     a.n = n; a.chunks = (int)chunks;
     LaunchCtx ctx{s, &h->prof, "png.decode"};
@@ -2546,24 +2470,18 @@ static int crop_ragged_table(specmi_handle* h, const uint8_t* frames, size_t sla
     if (crop_size < 1) return fail(h, SPECMI_ERR_ARG, "a crop size of %d", crop_size);
     if (f16) NEED_ALIGNED16(h, out);
     if (slab_bytes >= 4294967296.0) return fail(h, SPECMI_ERR_ARG, "a frame slab of %zu bytes is beyond the kernels' 32-bit offsets", slab_bytes);
-    std::vector<CropFrame> tab((size_t)nframes);
+    static_assert(sizeof(CropFrame) % sizeof(int) == 0, "the frame records are kept as ints");
+    constexpr size_t kRec = sizeof(CropFrame) / sizeof(int);
+    std::vector<int> tab((size_t)nframes * kRec, 0);
     for (int f = 0; f < nframes; ++f) {
         const int H = geom[2 * f], W = geom[2 * f + 1];
         if (H < 1 || W < 1 || H >= (1 << 24) || W >= (1 << 24)) return fail(h, SPECMI_ERR_ARG, "frame %d: size %d x %d (1 <= side < 2^24)", f, H, W);
-        if (offsets[f] < 0 || (double)offsets[f] + (double)H * W * 3 > (double)slab_bytes)
+        if (!rect_in_slab(offsets[f], 3LL * W, H, W, slab_bytes))
             return fail(h, SPECMI_ERR_ARG, "frame %d: %d x %d x 3 bytes at offset %lld leave the slab of %zu bytes", f, H, W, (long long)offsets[f], slab_bytes);
-        tab[f] = CropFrame{(unsigned)offsets[f], H, W, 0};
+        const CropFrame r{(unsigned)offsets[f], H, W, 0};
+        std::memcpy(tab.data() + (size_t)f * kRec, &r, sizeof(r));
     }
-    int rc;
-    const bool regrown = tab.size() * sizeof(CropFrame) > h->crop_tab_bytes;
-    if ((rc = grow_ragged(h, (void**)&h->crop_tab, &h->crop_tab_bytes, tab.size() * sizeof(CropFrame), "the ragged-crop frame table"))) return rc;
-    if (regrown || tab.size() != h->crop_host.size() || std::memcmp(tab.data(), h->crop_host.data(), tab.size() * sizeof(CropFrame))) {
-        // crops enqueued earlier on ANY stream may still read the old records (specmi_resize_normalize_ragged has the same rule)
-        if (!regrown && (rc = sync_for_growth(h, "the ragged-crop frame table"))) return rc;
-        h->crop_host.swap(tab);
-        HIPCHK(h, hipMemcpyAsync(h->crop_tab, h->crop_host.data(), h->crop_host.size() * sizeof(CropFrame), hipMemcpyHostToDevice, s));
-    }
-    return SPECMI_OK;
+    return publish_table(h, h->tab[TAB_crop], tab, "the ragged-crop frame table", nullptr, s);
 }
 
 static int crop_normalize_ragged(specmi_handle* h, const uint8_t* frames, size_t slab_bytes, const int64_t* offsets, const int32_t* geom,
@@ -2574,7 +2492,7 @@ static int crop_normalize_ragged(specmi_handle* h, const uint8_t* frames, size_t
     hipStream_t s = (hipStream_t)stream;
     if (int rc = crop_ragged_table(h, frames, slab_bytes, offsets, geom, nframes, frame_index, bboxes, n, crop_size, out, f16, s)) return rc;
     LaunchCtx ctx{s, &h->prof, "preprocess.crop_ragged"};
-    LAUNCHCHK(h, launch_crop_normalize_ragged(frames, h->crop_tab, nframes, (double)slab_bytes, frame_index, bboxes, n, scale, crop_size, out,
+    LAUNCHCHK(h, launch_crop_normalize_ragged(frames, (const CropFrame*)h->tab[TAB_crop].dev.p, nframes, (double)slab_bytes, frame_index, bboxes, n, scale, crop_size, out,
                                               raw, bbox_scale, bbox_center, ctx, f16),
               "crop_normalize_ragged");
     return SPECMI_OK;
@@ -2601,7 +2519,7 @@ static int crop_resize_normalize_ragged(specmi_handle* h, const uint8_t* frames,
     hipStream_t s = (hipStream_t)stream;
     if (int rc = crop_ragged_table(h, frames, slab_bytes, offsets, geom, nframes, frame_index, boxes, n, crop_size, out, f16, s)) return rc;
     LaunchCtx ctx{s, &h->prof, "preprocess.dataset_crop_ragged"};
-    LAUNCHCHK(h, launch_crop_resize_normalize_ragged(frames, h->crop_tab, nframes, (double)slab_bytes, frame_index, boxes, n, crop_size, out, ctx, f16),
+    LAUNCHCHK(h, launch_crop_resize_normalize_ragged(frames, (const CropFrame*)h->tab[TAB_crop].dev.p, nframes, (double)slab_bytes, frame_index, boxes, n, crop_size, out, ctx, f16),
               "crop_resize_normalize_ragged");
     return SPECMI_OK;
 }
@@ -2755,9 +2673,7 @@ int specmi_smpl_backward(specmi_handle* h, const float* rotmat, const float* bet
         return fail(h, SPECMI_ERR_ARG, "use_cam needs cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h");
     int rc;
     if ((rc = ensure_ws(h, B, 32, 32))) return rc;
-    if ((rc = grow_ragged(h, (void**)&h->smpl_bwd_ws, &h->smpl_bwd_ws_bytes, smpl_bwd_ws_floats(h->smpl.V, B) * 4,
-                          "the SMPL backward workspace")))
-        return rc;
+    if ((rc = grow_ragged(h, h->buf[BUF_smpl_bwd], smpl_bwd_ws_floats(h->smpl.V, B) * 4, "the SMPL backward workspace"))) return rc;
     SmplBwdArgs a;
     SmplArgs& f = a.fwd;
     f.rotmat = rotmat; f.betas = betas; f.cam = cam; f.cam_rotmat = R; f.cam_intrinsics = K;
@@ -2772,7 +2688,7 @@ int specmi_smpl_backward(specmi_handle* h, const float* rotmat, const float* bet
     f.skin_split = opt(h, OPT_smpl_skin_split);
     a.g_vertices = g_vertices; a.g_joints3d = g_joints3d; a.g_joints2d = g_joints2d; a.g_cam_t = g_cam_t;
     a.g_rotmat = g_rotmat; a.g_betas = g_betas; a.g_cam = g_cam;
-    a.ws = h->smpl_bwd_ws;
+    a.ws = (float*)h->buf[BUF_smpl_bwd].p;
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, "smpl.backward"};
     LAUNCHCHK(h, launch_smpl_backward(h->smpl, a, ctx), "smpl_backward");
     return SPECMI_OK;

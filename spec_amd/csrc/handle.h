@@ -109,6 +109,49 @@ struct HrNet;
 enum Opt { SPECMI_OPTIONS(SPECMI_OPT) OPT_COUNT };
 #undef SPECMI_OPT
 
+// A device buffer grown on demand (grow_ragged, api.hip): kept while it is large enough, else replaced by one at least 1.5x its
+// size.  The outgrown one joins ws_retired and is freed at specmi_destroy only: work enqueued earlier, or a captured graph, may
+// still name it.
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+};
+
+// The per-call records of a ragged entry point on the device, with their host image.  The rule, stated once (publish_table,
+// api.hip): a call builds its records on the host and compares them with `host`.  Equal bytes are neither copied nor waited
+// for, which is what makes a repeated call capturable.  Other bytes, or a table that has to grow (as a DevBuf grows),
+// synchronise the WHOLE device first - a call enqueued earlier on any stream may still read the old records - then become
+// `host`, which stays alive until the next rewrite, and are copied on the caller's stream.
+struct DevTable {
+    DevBuf dev;
+    std::vector<int> host;              // the records of dev as last uploaded (every record type is a whole number of ints)
+};
+
+enum Tab {
+    TAB_ragged,     // specmi_resize_normalize_ragged: the per-frame records (RaggedFrame) + their Pillow coefficient tables
+    TAB_pano,       // specmi_pano_extract_views: the per-view records (PanoView)
+    TAB_crop,       // specmi_crop_normalize_ragged, specmi_crop_resize_normalize_ragged: the per-frame records (CropFrame)
+    TAB_views,      // specmi_render_views: the view records, pixel prefix and pair table
+    TAB_draw,       // specmi_draw_skeletons: the frame records and the bone table
+    TAB_marks,      // specmi_draw_marks: the frame records, the marks and the tile list
+    TAB_jpeg,       // specmi_jpeg_encode: the picture records and the quality's tables
+    TAB_png,        // specmi_png_encode: the picture records
+    TAB_jdec,       // specmi_jpeg_decode: the file records with their tables
+    TAB_pdec,       // specmi_png_decode: the file records
+    TAB_COUNT
+};
+
+enum Buf {
+    BUF_ragged_tmp, // specmi_resize_normalize_ragged: the uint8 rows between the two passes
+    BUF_render,     // mesh rasteriser (specmi_render_meshes, specmi_render_views): depth keys, snapped vertices, normal sums
+    BUF_jpeg,       // specmi_jpeg_encode: coefficients, bit counts, the unstuffed scans and the chunk sums (jpeg_ws_layout)
+    BUF_png,        // specmi_png_encode: the filtered streams, the segments' blocks and their sums (png_ws_layout)
+    BUF_jdec,       // specmi_jpeg_decode: coefficients, planes and the lanes' states (jdec_ws_layout)
+    BUF_pdec,       // specmi_png_decode: the inflated streams, the match records and the Adler sums (pdec_ws_layout)
+    BUF_smpl_bwd,   // specmi_smpl_backward: smpl_bwd_ws_floats(V, B) floats
+    BUF_COUNT
+};
+
 struct specmi_handle {
     specmi_handle();                // options.hip: every option at its default
     int device = 0;
@@ -153,71 +196,14 @@ struct specmi_handle {
     float *rot_ws = nullptr, *betas_ws = nullptr, *cam_ws = nullptr, *verts_ws = nullptr;
     float *pf_ws = nullptr, *A_ws = nullptr, *pj_ws = nullptr;
     int ws_B = 0;
-    // specmi_smpl_backward's own workspace (smpl_bwd_ws_floats(V, B)); grows like ragged_tmp, an outgrown buffer joins ws_retired
-    float* smpl_bwd_ws = nullptr;
-    size_t smpl_bwd_ws_bytes = 0;
+    // specmi_resize_normalize's own table: keyed by the geometry, not by its bytes, and freed when outgrown (resize_normalize, api.hip)
     int* resize_tab = nullptr;          // device copy of the Pillow coefficient tables of the last resize geometry
     size_t resize_tab_ints = 0;
     std::vector<int> resize_host;       // host image of the same (kept alive for the async copy)
     int resize_geom[4] = {0, 0, 0, 0};  // H, W, OH, OW the tables were built for
-    // ragged batch resize (specmi_resize_normalize_ragged): per-frame records + coefficient tables, and the uint8 rows between
-    // the two passes.  Both grow geometrically; an outgrown buffer joins ws_retired
-    int* ragged_tab = nullptr;
-    size_t ragged_tab_bytes = 0;
-    unsigned char* ragged_tmp = nullptr;
-    size_t ragged_tmp_bytes = 0;
-    std::vector<int> ragged_host;       // host image of ragged_tab as last uploaded
-    // panorama views (specmi_pano_extract_views): the per-view records, same growth and upload rules as ragged_tab
-    PanoView* pano_tab = nullptr;
-    size_t pano_tab_bytes = 0;
-    std::vector<PanoView> pano_host;    // host image of pano_tab as last uploaded
-    // ragged crops (specmi_crop_normalize_ragged, specmi_crop_resize_normalize_ragged): the per-frame records, same rules again
-    CropFrame* crop_tab = nullptr;
-    size_t crop_tab_bytes = 0;
-    std::vector<CropFrame> crop_host;   // host image of crop_tab as last uploaded
-    // mesh rasteriser (specmi_render_meshes, specmi_render_views): depth keys, snapped vertices, normal sums; grows like ragged_tmp
-    void* render_ws = nullptr;
-    size_t render_ws_bytes = 0;
-    // specmi_render_views: the view records, pixel prefix and pair table, same growth and upload rules as ragged_tab
-    int* views_tab = nullptr;
-    size_t views_tab_bytes = 0;
-    std::vector<int> views_host;        // host image of views_tab as last uploaded
-    // specmi_draw_skeletons: the frame records and the bone table, same growth and upload rules as ragged_tab
-    int* draw_tab = nullptr;
-    size_t draw_tab_bytes = 0;
-    std::vector<int> draw_host;         // host image of draw_tab as last uploaded
-    // specmi_draw_marks: the frame records, the marks and the tile list, same growth and upload rules as ragged_tab
-    int* marks_tab = nullptr;
-    size_t marks_tab_bytes = 0;
-    std::vector<int> marks_host;        // host image of marks_tab as last uploaded
-    // specmi_jpeg_encode: the picture records and the quality's tables, same growth and upload rules as ragged_tab; coefficients,
-    // bit counts, the unstuffed scans and the chunk sums (jpeg_ws_layout), grows like ragged_tmp
-    int* jpeg_tab = nullptr;
-    size_t jpeg_tab_bytes = 0;
-    std::vector<int> jpeg_host;         // host image of jpeg_tab as last uploaded
-    void* jpeg_ws = nullptr;
-    size_t jpeg_ws_bytes = 0;
-    // specmi_png_encode: the picture records, same growth and upload rules as ragged_tab; the filtered streams, the segments'
-    // blocks and their sums (png_ws_layout), grows like ragged_tmp
-    int* png_tab = nullptr;
-    size_t png_tab_bytes = 0;
-    std::vector<int> png_host;          // host image of png_tab as last uploaded
-    void* png_ws = nullptr;
-    size_t png_ws_bytes = 0;
-    // specmi_jpeg_decode: the file records with their tables, same growth and upload rules as ragged_tab; coefficients, planes and
-    // the lanes' states (jdec_ws_layout), grows like ragged_tmp
-    int* jdec_tab = nullptr;
-    size_t jdec_tab_bytes = 0;
-    std::vector<int> jdec_host;         // host image of jdec_tab as last uploaded
-    void* jdec_ws = nullptr;
-    size_t jdec_ws_bytes = 0;
-    // specmi_png_decode: the file records, same growth and upload rules as ragged_tab; the inflated streams, the match records
-    // and the Adler sums (pdec_ws_layout), grows like ragged_tmp
-    int* pdec_tab = nullptr;
-    size_t pdec_tab_bytes = 0;
-    std::vector<int> pdec_host;         // host image of pdec_tab as last uploaded
-    void* pdec_ws = nullptr;
-    size_t pdec_ws_bytes = 0;
+    // the ragged entry points' record tables and workspaces: what each holds stands at its name in enum Tab / enum Buf
+    DevTable tab[TAB_COUNT];
+    DevBuf buf[BUF_COUNT];
     SkWs sk;                            // split-K partial tiles + arrival counters (ensure_sk; never allocated under graph capture:
                                         // the warm-up call of a shape sizes it)
     std::vector<void*> sk_retired;      // outgrown split-K buffers, kept until destroy (captured graphs may still name them)

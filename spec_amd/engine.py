@@ -148,6 +148,26 @@ def _rects_overlap(a, b) -> bool:
     return bool(((k2 - k1 >= 2) | hit(k1) | hit(k2)).any())
 
 
+def _byte_rects(off, pitch, W, H):
+    """The (first byte, pitch, row bytes, rows) of n pitched rectangles of H rows of 3 W bytes; a single row has no next row, so
+    its pitch counts as 3 W (stored_pitch of spec_amd/csrc/api.hip)."""
+    return [(int(o), int(p) if h > 1 else 3 * int(w), 3 * int(w), int(h)) for o, p, w, h in zip(off, pitch, W, H)]
+
+
+def _first_overlap(rects):
+    """The first two rectangles that share a byte, as (a, b) indices into ``rects``, or None: sorted by first byte, a rectangle
+    is compared with those that start before it ends (first_overlap of spec_amd/csrc/api.hip)."""
+    order = sorted(range(len(rects)), key=lambda v: rects[v][0])
+    for i, a in enumerate(order):
+        end = rects[a][0] + (rects[a][3] - 1) * rects[a][1] + rects[a][2]
+        for b in order[i + 1:]:
+            if rects[b][0] >= end:
+                break
+            if _rects_overlap(rects[a], rects[b]):
+                return a, b
+    return None
+
+
 def check_render_views(Mtot, V, F, geom, offsets, cams, in_bytes, out_bytes, rgb):
     """Every refusal of ``specmi_render_views`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom``
     (n, 5) [H, W, mesh0, count, flags], ``offsets`` (n, 4) [in_offset, in_pitch, out_offset, out_pitch], ``cams`` (n, 13)
@@ -195,15 +215,9 @@ def check_render_views(Mtot, V, F, geom, offsets, cams, in_bytes, out_bytes, rgb
         raise ValueError(f'a frame leaves the slab of {in_bytes} bytes')
     if not (np.isfinite(cams).all() and (cams[:, 9:11] > 0).all()):
         raise ValueError('focal lengths must be positive and finite, the centre and R finite')
-    rects = [(int(o), int(p) if h > 1 else 3 * int(w), 3 * int(w), int(h)) for o, p, w, h in zip(out_off, out_pitch, W, H)]
-    order = sorted(range(n), key=lambda v: rects[v][0])
-    for i, a in enumerate(order):
-        end = rects[a][0] + (rects[a][3] - 1) * rects[a][1] + rects[a][2]
-        for b in order[i + 1:]:
-            if rects[b][0] >= end:
-                break
-            if _rects_overlap(rects[a], rects[b]):
-                raise ValueError(f'the output rectangles of views {a} and {b} overlap')
+    pair = _first_overlap(_byte_rects(out_off, out_pitch, W, H))
+    if pair:
+        raise ValueError(f'the output rectangles of views {pair[0]} and {pair[1]} overlap')
     return geom.astype(np.int32), offsets, cams, rgb
 
 
@@ -243,15 +257,9 @@ def check_draw_skeletons(Mtot, J, D, bones, geom, offsets, slab_bytes, style=Non
         raise ValueError(f'a frame rectangle leaves the slab of {slab_bytes} bytes')
     if int((-(-H // 32) * -(-W // 32))[count > 0].sum()) >= 1 << 31:
         raise ValueError('the frames hold 2^31 tiles of 32 x 32 pixels or more')
-    rects = [(int(o), int(p) if h > 1 else 3 * int(w), 3 * int(w), int(h)) for o, p, w, h in zip(off, pitch, W, H)]
-    order = sorted(range(n), key=lambda f: rects[f][0])
-    for i, a in enumerate(order):
-        end = rects[a][0] + (rects[a][3] - 1) * rects[a][1] + rects[a][2]
-        for b in order[i + 1:]:
-            if rects[b][0] >= end:
-                break
-            if _rects_overlap(rects[a], rects[b]):
-                raise ValueError(f'frames {a} and {b} share a byte')
+    pair = _first_overlap(_byte_rects(off, pitch, W, H))
+    if pair:
+        raise ValueError(f'frames {pair[0]} and {pair[1]} share a byte')
     return bones.astype(np.int32), geom.astype(np.int32), offsets, style
 
 
@@ -300,15 +308,9 @@ def check_draw_marks(geom, offsets, marks, slab_bytes, mask_bytes=0):
         raise ValueError(f'a mask position outside [-{_lib.MARK_MAX_MASK_POS}, {_lib.MARK_MAX_MASK_POS}]')
     if ((mk[:, 6] < 0) | (mk[:, 6] + mk[:, 4] * mk[:, 5] > mask_bytes)).any():
         raise ValueError(f'a mask leaves the mask buffer of {mask_bytes} bytes')
-    rects = [(int(o), int(p) if h > 1 else 3 * int(w), 3 * int(w), int(h)) for o, p, w, h in zip(off, pitch, W, H)]
-    order = sorted(range(n), key=lambda f: rects[f][0])
-    for i, a in enumerate(order):
-        end = rects[a][0] + (rects[a][3] - 1) * rects[a][1] + rects[a][2]
-        for b in order[i + 1:]:
-            if rects[b][0] >= end:
-                break
-            if _rects_overlap(rects[a], rects[b]):
-                raise ValueError(f'frames {a} and {b} share a byte')
+    pair = _first_overlap(_byte_rects(off, pitch, W, H))
+    if pair:
+        raise ValueError(f'frames {pair[0]} and {pair[1]} share a byte')
     return geom.astype(np.int32), offsets, marks
 
 
@@ -350,19 +352,21 @@ def jpeg_capacity(H, W) -> int:
     return 3 * int(H) * int(W) + 1024
 
 
-def check_jpeg_encode(geom, offsets, in_bytes, out_bytes, quality, in_ptr=None, out_ptr=None):
-    """Every refusal of ``specmi_jpeg_encode`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom`` (n, 2)
-    [H, W], ``offsets`` (n, 4) [in_offset, in_pitch, out_offset, out_capacity], the sizes of the two slabs, the quality and -
-    where known - the slabs' addresses (None for either: a missing slab).  -> the arrays as the library reads them (int32,
-    int64).  Needs no device."""
+def _encode_pictures(geom, offsets):
+    """What ``check_jpeg_encode`` and ``check_png_encode`` refuse alike, each part where both refuse it: the arrays' shapes and
+    the number of pictures -> geom, offsets (int64)."""
     geom, offsets = np.ascontiguousarray(geom, dtype=np.int64), np.ascontiguousarray(offsets, dtype=np.int64)
     n = geom.shape[0] if geom.ndim == 2 else -1
     if geom.ndim != 2 or geom.shape[1] != 2 or tuple(offsets.shape) != (n, 4):
         raise ValueError('pictures: geom (n, 2) and offsets (n, 4) with one row per picture')
     if not 1 <= n <= 65535:
         raise ValueError(f'1 to 65535 pictures per call, got {n}')
-    if not (isinstance(quality, (int, np.integer)) and 1 <= quality <= 100):
-        raise ValueError(f'quality {quality!r}: an integer in 1 .. 100')
+    return geom, offsets
+
+
+def _encode_places(geom, offsets, in_bytes, out_bytes, in_ptr, out_ptr, min_cap, min_cap_what):
+    """The same for the two slabs and every picture's geometry, rectangle in the picture slab and room in the output slab,
+    ``min_cap`` bytes (``min_cap_what``) at least -> H, W, out_off, cap."""
     if in_bytes is None or out_bytes is None or in_ptr == 0 or out_ptr == 0:
         raise ValueError('the picture slab or the output slab is missing (a null pointer)')
     if in_ptr is not None and out_ptr is not None and out_ptr < in_ptr + in_bytes and in_ptr < out_ptr + out_bytes:
@@ -375,15 +379,32 @@ def check_jpeg_encode(geom, offsets, in_bytes, out_bytes, quality, in_ptr=None, 
         raise ValueError('a pitch below 3 * W bytes')
     if (in_off < 0).any() or (in_off + (H - 1) * in_pitch + 3 * W > in_bytes).any():
         raise ValueError(f'a picture rectangle leaves the slab of {in_bytes} bytes')
-    if (cap < _lib.JPEG_HEADER_BYTES).any():
-        raise ValueError(f'a capacity below the header\'s {_lib.JPEG_HEADER_BYTES} bytes')
+    if (cap < min_cap).any():
+        raise ValueError(f'a capacity below {min_cap_what} {min_cap} bytes')
     if (out_off < 0).any() or (out_off + cap > out_bytes).any():
         raise ValueError(f'an output leaves the slab of {out_bytes} bytes')
-    if int((-(-H // 16) * -(-W // 16)).sum()) > 1 << 24:
-        raise ValueError('the pictures hold more than 2^24 blocks of 16 x 16 pixels')
+    return H, W, out_off, cap
+
+
+def _encode_outputs_disjoint(out_off, cap):
+    """The same after the pictures: no two outputs share a byte."""
     order = np.argsort(out_off, kind='stable')
     if ((out_off + cap)[order][:-1] > out_off[order][1:]).any():
         raise ValueError('two outputs share a byte')
+
+
+def check_jpeg_encode(geom, offsets, in_bytes, out_bytes, quality, in_ptr=None, out_ptr=None):
+    """Every refusal of ``specmi_jpeg_encode`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom`` (n, 2)
+    [H, W], ``offsets`` (n, 4) [in_offset, in_pitch, out_offset, out_capacity], the sizes of the two slabs, the quality and -
+    where known - the slabs' addresses (None for either: a missing slab).  -> the arrays as the library reads them (int32,
+    int64).  Needs no device."""
+    geom, offsets = _encode_pictures(geom, offsets)
+    if not (isinstance(quality, (int, np.integer)) and 1 <= quality <= 100):
+        raise ValueError(f'quality {quality!r}: an integer in 1 .. 100')
+    H, W, out_off, cap = _encode_places(geom, offsets, in_bytes, out_bytes, in_ptr, out_ptr, _lib.JPEG_HEADER_BYTES, 'the header\'s')
+    if int((-(-H // 16) * -(-W // 16)).sum()) > 1 << 24:
+        raise ValueError('the pictures hold more than 2^24 blocks of 16 x 16 pixels')
+    _encode_outputs_disjoint(out_off, cap)
     return geom.astype(np.int32), offsets
 
 
@@ -418,37 +439,15 @@ def check_png_encode(geom, offsets, in_bytes, out_bytes, in_ptr=None, out_ptr=No
     """Every refusal of ``specmi_png_encode`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom`` (n, 2)
     [H, W], ``offsets`` (n, 4) [in_offset, in_pitch, out_offset, out_capacity], the sizes of the two slabs and - where known - the
     slabs' addresses (None for either: a missing slab).  -> the arrays as the library reads them (int32, int64).  Needs no device."""
-    geom, offsets = np.ascontiguousarray(geom, dtype=np.int64), np.ascontiguousarray(offsets, dtype=np.int64)
-    n = geom.shape[0] if geom.ndim == 2 else -1
-    if geom.ndim != 2 or geom.shape[1] != 2 or tuple(offsets.shape) != (n, 4):
-        raise ValueError('pictures: geom (n, 2) and offsets (n, 4) with one row per picture')
-    if not 1 <= n <= 65535:
-        raise ValueError(f'1 to 65535 pictures per call, got {n}')
-    if in_bytes is None or out_bytes is None or in_ptr == 0 or out_ptr == 0:
-        raise ValueError('the picture slab or the output slab is missing (a null pointer)')
-    if in_ptr is not None and out_ptr is not None and out_ptr < in_ptr + in_bytes and in_ptr < out_ptr + out_bytes:
-        raise ValueError('the picture slab and the output slab overlap')
-    H, W = geom.T
-    in_off, in_pitch, out_off, cap = offsets.T
-    if ((H < 1) | (H > 32768) | (W < 1) | (W > 32768)).any():
-        raise ValueError('a picture of 1 .. 32768 pixels per side')
-    if (in_pitch < 3 * W).any():
-        raise ValueError('a pitch below 3 * W bytes')
-    if (in_off < 0).any() or (in_off + (H - 1) * in_pitch + 3 * W > in_bytes).any():
-        raise ValueError(f'a picture rectangle leaves the slab of {in_bytes} bytes')
-    if (cap < _lib.PNG_OVERHEAD_BYTES).any():
-        raise ValueError(f'a capacity below the fixed overhead of {_lib.PNG_OVERHEAD_BYTES} bytes')
-    if (out_off < 0).any() or (out_off + cap > out_bytes).any():
-        raise ValueError(f'an output leaves the slab of {out_bytes} bytes')
+    geom, offsets = _encode_pictures(geom, offsets)
+    H, W, out_off, cap = _encode_places(geom, offsets, in_bytes, out_bytes, in_ptr, out_ptr, _lib.PNG_OVERHEAD_BYTES, 'the fixed overhead of')
     stream = H * (1 + 3 * W)
     segments = -(-stream // 32768)
     if (6 + stream + 5 * segments >= 1 << 31).any():
         raise ValueError('a picture whose zlib stream may not fit one IDAT chunk (2^31 bytes)')
     if int(segments.sum()) > 1 << 23:
         raise ValueError('the pictures\' filtered streams hold more than 2^23 segments of 32768 bytes')
-    order = np.argsort(out_off, kind='stable')
-    if ((out_off + cap)[order][:-1] > out_off[order][1:]).any():
-        raise ValueError('two outputs share a byte')
+    _encode_outputs_disjoint(out_off, cap)
     return geom.astype(np.int32), offsets
 
 
@@ -507,16 +506,8 @@ def check_jpeg_decode(ranges, geom, outs, in_bytes, out_bytes, in_ptr=None, out_
     mcu = np.where(sampling == 420, 16, 8)
     if int((-(-H // mcu) * -(-W // mcu)).sum()) > 1 << 24:
         raise ValueError('the files hold more than 2^24 MCUs')
-    end = out_off + (H - 1) * pitch + 3 * W
-    order = np.argsort(out_off, kind='stable')
-    for k, i in enumerate(order):                                # rectangles with gaps: a byte test per pair that may meet
-        for j in order[k + 1:]:
-            if out_off[j] >= end[i]:
-                break
-            rows_i = out_off[i] + pitch[i] * np.arange(H[i])
-            rows_j = out_off[j] + pitch[j] * np.arange(H[j])
-            if ((rows_i[:, None] < rows_j[None, :] + 3 * W[j]) & (rows_j[None, :] < rows_i[:, None] + 3 * W[i])).any():
-                raise ValueError('two picture rectangles share a byte')
+    if _first_overlap(_byte_rects(out_off, pitch, W, H)):
+        raise ValueError('two picture rectangles share a byte')
     return ranges, outs
 
 
@@ -605,16 +596,8 @@ def check_png_decode(ranges, geom, outs, in_bytes, out_bytes, in_ptr=None, out_p
         raise ValueError('the files\' inflated streams hold more than 2^31 bytes')
     if raw_bytes is not None and raw_bytes < need:
         raise ValueError(f'the raw output holds {raw_bytes} bytes, these files\' inflated streams take {need}')
-    end = out_off + (H - 1) * pitch + 3 * W
-    order = np.argsort(out_off, kind='stable')
-    for k, i in enumerate(order):                                # rectangles with gaps: a byte test per pair that may meet
-        for j in order[k + 1:]:
-            if out_off[j] >= end[i]:
-                break
-            rows_i = out_off[i] + pitch[i] * np.arange(H[i])
-            rows_j = out_off[j] + pitch[j] * np.arange(H[j])
-            if ((rows_i[:, None] < rows_j[None, :] + 3 * W[j]) & (rows_j[None, :] < rows_i[:, None] + 3 * W[i])).any():
-                raise ValueError('two picture rectangles share a byte')
+    if _first_overlap(_byte_rects(out_off, pitch, W, H)):
+        raise ValueError('two picture rectangles share a byte')
     return ranges, geom.astype(np.int32), outs, need
 
 

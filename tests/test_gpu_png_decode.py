@@ -178,6 +178,51 @@ def test_camcalib_evaluation_is_the_same_with_the_switch(tmp_path):
         assert host[k] == dev[k]
 
 
+def test_a_repeated_call_replays_from_a_graph(eng):
+    """The table's rule under capture (as tests/test_gpu_png.py pins it for the encoder): other records are refused with
+    ERR_STATE and leave the capture valid, the previous call's records are captured, and the replay writes the eager call's bytes."""
+    import io
+    from PIL import Image
+    rng = np.random.default_rng(11)
+    files = []
+    for H, W in ((8, 8), (5, 3)):
+        f = io.BytesIO()
+        Image.fromarray(rng.integers(0, 256, (H, W, 3), dtype=np.uint8)).save(f, format='PNG')
+        files.append(f.getvalue())
+    probes = [engine.png_probe(f) for f in files]
+    assert [p[:4] for p in probes] == [('supported', 8, 8, 2), ('supported', 5, 3, 2)]
+    streams = [engine.png_stream(f, p[4]) for f, p in zip(files, probes)]
+    slab = torch.from_numpy(np.frombuffer(b''.join(streams), np.uint8).copy()).to(DEV)
+    ranges = [(0, len(streams[0])), (len(streams[0]), len(streams[1]))]
+    geom, outs = [p[1:4] for p in probes], [(0, 24), (192, 9)]
+    out = torch.full((192 + 45,), SENTINEL, device=DEV, dtype=torch.uint8)
+    status = torch.ones(2, device=DEV, dtype=torch.int32)
+    eng.png_decode_into(slab, ranges, geom, out, outs, status=status)             # also the warm-up call of the capture below
+    want = out.clone()
+    assert not status.any().item()
+    assert want.cpu().numpy().tobytes() == b''.join(ref.pillow_pixels(f).tobytes() for f in files)
+    out.fill_(SENTINEL), status.fill_(1)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    g, err = torch.cuda.CUDAGraph(), None
+    with torch.cuda.graph(g, stream=s):
+        try:      # other records are another table: refused, and the capture goes on
+            eng.png_decode_into(slab, ranges[:1], geom[:1], out, outs[:1], status=status[:1])
+        except _lib.SpecmiError as e:
+            err = e
+        eng.png_decode_into(slab, ranges, geom, out, outs, status=status)         # the previous call's records: captured
+    assert err is not None and err.code == _lib.ERR_STATE, err
+    torch.cuda.synchronize()
+    assert (out == SENTINEL).all().item() and status.all().item()                 # capturing ran nothing
+    for _ in range(2):
+        g.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, want) and not status.any().item()
+        out.fill_(SENTINEL)
+    other, st, _, _, _ = _decode(eng, files[::-1])                                # the handle is usable afterwards, with other records
+    assert not st.any() and all(np.array_equal(px, ref.pillow_pixels(f)) for px, f in zip(other, files[::-1]))
+
+
 def _call(eng, **change):
     """specmi_png_decode on two good files with one argument changed -> the return code; the output slab must stay untouched."""
     files = [dict(_files())[k] for k in ('pillow-7x1-ct2-smooth-l6', 'pillow-1x7-ct6-noise-l6')]

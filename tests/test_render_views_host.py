@@ -161,3 +161,24 @@ def test_check_render_views_refuses(name):
     REFUSALS[name](a)
     with pytest.raises(ValueError):
         engine.check_render_views(**a)
+
+
+def test_first_overlap_against_every_byte():
+    """``engine._first_overlap`` reports a pair exactly when two rectangles share a byte, and then a pair that does: against the
+    bytes of every rectangle written out, on seeded sets of small rectangles of mixed pitches, one-row ones among them."""
+    rng = np.random.default_rng(5)
+    met = 0
+    for _ in range(400):
+        rects = []
+        for _ in range(int(rng.integers(2, 7))):
+            H, row = int(rng.integers(1, 5)), int(rng.integers(1, 7))
+            pitch = int(rng.integers(row, 13)) if H > 1 else row        # a single row's pitch counts as its row (engine._byte_rects)
+            rects.append((int(rng.integers(0, 120)), pitch, row, H))
+        held = [{o + y * p + x for y in range(h) for x in range(r)} for o, p, r, h in rects]
+        shared = any(held[a] & held[b] for a in range(len(rects)) for b in range(a))
+        pair = engine._first_overlap(rects)
+        assert (pair is not None) == shared, rects
+        if pair:
+            assert pair[0] != pair[1] and held[pair[0]] & held[pair[1]], (rects, pair)
+            met += 1
+    assert 50 <= met <= 350         # both answers are exercised, each by 50 of the 400 sets at least
