@@ -2111,12 +2111,13 @@ int specmi_denormalize_u8(specmi_handle* h, const float* x, int B, int Hp, int W
     if (pitch < 3LL * W) return fail(h, SPECMI_ERR_ARG, "a pitch of %lld bytes for rows of %d", (long long)pitch, 3 * W);
     if (!rect_in_slab(offset, pitch, H, W, slab_bytes))
         return fail(h, SPECMI_ERR_ARG, "the frame's rectangle leaves the slab of %zu bytes", slab_bytes);
-    static const float kMean[3] = {0.485f, 0.456f, 0.406f}, kStd[3] = {0.229f, 0.224f, 0.225f};     // ImageNet's, as pare's denormalize_images
     DenormArgs a{};
     a.plane = (long long)Hp * Wp;
     a.x = x + (size_t)index * 3 * (size_t)a.plane; a.out = slab + offset; a.pitch = pitch; a.h = H; a.w = W; a.Wp = Wp;
     for (int c = 0; c < 3; ++c) {
-        a.mean[c] = mean3 ? mean3[c] : kMean[c]; a.std[c] = std3 ? std3[c] : kStd[c];
+        imagenet_mean_std(c, a.mean[c], a.std[c]);                       // the defaults, as pare's denormalize_images
+        if (mean3) a.mean[c] = mean3[c];
+        if (std3) a.std[c] = std3[c];
         if (!std::isfinite(a.mean[c]) || !std::isfinite(a.std[c])) return fail(h, SPECMI_ERR_ARG, "mean and std must be finite");
     }
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, "render.denormalize"};

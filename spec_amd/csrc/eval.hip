@@ -19,8 +19,7 @@
 namespace specmi {
 
 __device__ __forceinline__ float block_sum_256(float v, float* red) {   // blockDim.x == 256
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = wave_sum64(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -32,12 +31,7 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {   // block
 template <int N>
 __device__ __forceinline__ void block_sum_many_256(float (&a)[N], float* part, float* dst) {
 #pragma unroll
-    for (int i = 0; i < N; ++i) {
-        float v = a[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        a[i] = v;
-    }
+    for (int i = 0; i < N; ++i) a[i] = wave_sum64(a[i]);
     __syncthreads();   // part may still be read from the previous call
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll

@@ -105,11 +105,6 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // R = batch_euler2matrix([pitch, 0, roll]) through the quaternion route and K with K[2,2] = 0
 // (spec/utils/cam_params.py:37-46)
@@ -198,12 +193,7 @@ __global__ void __launch_bounds__(256) fc_gemv_kernel(const GemvArgs a) {
         __builtin_amdgcn_sched_group_barrier(0x002, GKU * NB * 8, 0);
     }
 #pragma unroll
-    for (int b = 0; b < NB; ++b) {
-        float v = acc[b];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-        acc[b] = v;
-    }
+    for (int b = 0; b < NB; ++b) acc[b] = wave_sum64(acc[b]);
     if (lane < nb) {
         float v = 0.f;
 #pragma unroll
@@ -261,12 +251,12 @@ __device__ __forceinline__ void camcalib_decode_image(const DecodeArgs& a, int b
             const float e = expf(row[i] - mx);
             se += e;
         }
-        se = wave_sum(se);
+        se = wave_sum64(se);
         for (int i = lane; i < a.nbins; i += 64) {
             const float pr = expf(row[i] - mx) / se;  // softmax, then expectation of the index
             sp += pr * (float)i;
         }
-        sp = wave_sum(sp);
+        sp = wave_sum64(sp);
         if (lane == 0) {
             const float s = sp / (float)(a.nbins - 1) * 2.0f - 1.0f;                  // softargmax1d normalisation
             ang[wave] = soft_idx_to_angle(s, wave);
@@ -327,9 +317,9 @@ __device__ __forceinline__ float wave_softargmax_row(const float* __restrict__ r
     float sp = 0.f;
     se = 0.f;
     for (int i = lane; i < nbins; i += 64) se += expf(r[i] - mx);
-    se = wave_sum(se);
+    se = wave_sum64(se);
     for (int i = lane; i < nbins; i += 64) sp += expf(r[i] - mx) / se * (float)i;
-    sp = wave_sum(sp);
+    sp = wave_sum64(sp);
     return sp / (float)(nbins - 1) * 2.0f - 1.0f;
 }
 
@@ -397,7 +387,7 @@ __global__ void __launch_bounds__(384) camcalib_eval_mean_kernel(const CamEvalAr
     const float* v = (wave < 3 ? a.loss_term : a.err) + (size_t)head * a.B;
     float acc = 0.f;
     for (int i = lane; i < a.B; i += 64) acc += v[i];
-    acc = wave_sum(acc) / (float)a.B;
+    acc = wave_sum64(acc) / (float)a.B;
     if (lane == 0) {
         if (wave < 3) a.means[1 + head] = head_loss[head] = a.weight[head] * acc;
         else a.means[4 + head] = acc * (float)(180.0 / 3.14159265358979323846);     // Tensor.rad2deg

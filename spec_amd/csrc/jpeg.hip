@@ -160,18 +160,6 @@ constexpr int kJpegSofSize = 2 + 18 + 2 * 69 + 5;      // where H (2 bytes, big-
 // ---- device half ------------------------------------------------------------------------------------------------------------------
 namespace {
 
-__device__ __forceinline__ JpegPic find_pic(const JpegPic* pics, int n, int chunk, int JpegPic::*first, int* index) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pics[mid].*first <= chunk) lo = mid; else hi = mid;
-    }
-    *index = lo;
-    return pics[lo];
-}
-
-constexpr int fix16(double x) { return (int)(x * 65536.0 + 0.5); }
-
 __device__ __forceinline__ int luma(const unsigned char* px) {
     return (fix16(.299) * px[0] + fix16(.587) * px[1] + fix16(.114) * px[2] + 32768) >> 16;
 }
@@ -228,8 +216,8 @@ __device__ __forceinline__ int quantise(int c, int qv) {
 
 __global__ void __launch_bounds__(256) jpeg_dct_kernel(JpegArgs a) {
     const int chunk = blockIdx.x / 6, b = blockIdx.x % 6;      // the whole workgroup works on one kind of block
-    int pi;
-    const JpegPic p = find_pic(a.pics, a.n, chunk, &JpegPic::mchunk0, &pi);
+    const int pi = last_at_or_before(a.pics, a.n, chunk, &JpegPic::mchunk0);
+    const JpegPic p = a.pics[pi];
     const int m = (chunk - p.mchunk0) * kJpegMcuChunk + (int)threadIdx.x;
     if (m >= p.mx * p.my) return;
     const int mcy = m / p.mx, mcx = m - mcy * p.mx;
@@ -384,30 +372,12 @@ template <bool WRITE> __device__ __forceinline__ int code_mcu(const short* coef,
     return bits;
 }
 
-// exclusive scan of one value per thread over the 256 threads of a workgroup -> and the total
-template <typename T> __device__ __forceinline__ T block_scan(T v, T* lds, T* total) {
-    const int tid = threadIdx.x;
-    lds[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int d = 1; d < 256; d <<= 1) {
-        const T add = tid >= d ? lds[tid - d] : T(0);
-        __syncthreads();
-        lds[tid] += add;
-        __syncthreads();
-    }
-    const T incl = lds[tid];
-    *total = lds[255];
-    __syncthreads();                     // the caller may use lds again
-    return incl - v;
-}
-
 __global__ void __launch_bounds__(256) jpeg_count_kernel(JpegArgs a) {
     __shared__ JpegCodes s;
     __shared__ unsigned scan[256];
     load_codes(s, a.tabs);
-    int pi;
-    const JpegPic p = find_pic(a.pics, a.n, blockIdx.x, &JpegPic::mchunk0, &pi);
+    const int pi = last_at_or_before(a.pics, a.n, blockIdx.x, &JpegPic::mchunk0);
+    const JpegPic p = a.pics[pi];
     const int m = ((int)blockIdx.x - p.mchunk0) * kJpegMcuChunk + (int)threadIdx.x;
     unsigned bits = 0;
     if (m < p.mx * p.my) {
@@ -447,8 +417,8 @@ __global__ void __launch_bounds__(256) jpeg_write_kernel(JpegArgs a) {
     __shared__ JpegCodes s;
     __shared__ unsigned scan[256];
     load_codes(s, a.tabs);
-    int pi;
-    const JpegPic p = find_pic(a.pics, a.n, blockIdx.x, &JpegPic::mchunk0, &pi);
+    const int pi = last_at_or_before(a.pics, a.n, blockIdx.x, &JpegPic::mchunk0);
+    const JpegPic p = a.pics[pi];
     const int m = ((int)blockIdx.x - p.mchunk0) * kJpegMcuChunk + (int)threadIdx.x;
     const bool live = m < p.mx * p.my;
     unsigned total;
@@ -479,8 +449,8 @@ __device__ __forceinline__ int scan_bytes16(const unsigned* buf, long long i0, l
 
 template <bool PACK> __global__ void __launch_bounds__(256) jpeg_stuff_kernel(JpegArgs a) {
     __shared__ unsigned scan[256];
-    int pi;
-    const JpegPic p = find_pic(a.pics, a.n, blockIdx.x, &JpegPic::bchunk0, &pi);
+    const int pi = last_at_or_before(a.pics, a.n, blockIdx.x, &JpegPic::bchunk0);
+    const JpegPic p = a.pics[pi];
     const int j = (int)blockIdx.x - p.bchunk0;
     const unsigned long long bits = a.pic_bits[pi];
     const long long nbytes = (long long)((bits + 7) >> 3);

@@ -193,15 +193,6 @@ namespace {
 
 constexpr unsigned kInvalid = 0u, kNever = 0xFFFFFFFFu, kStart = 1u << 31;      // a state: valid << 31 | zigzag << 16 | block << 8 | overflow
 
-__device__ __forceinline__ const JdecFile* find_file(const JdecFile* files, int n, int chunk, int JdecFile::*first) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (files[mid].*first <= chunk) lo = mid; else hi = mid;
-    }
-    return files + lo;
-}
-
 // the file's tables in LDS
 struct JdecLds {
     JdecHuff huff[4];
@@ -315,7 +306,7 @@ __device__ __forceinline__ unsigned decode_lane(const JdecFile* f, const unsigne
 __global__ void __launch_bounds__(kJdecGroup) jdec_sync_kernel(JdecArgs a, int pass) {
     __shared__ JdecLds s;
     __shared__ unsigned sexit[kJdecGroup];
-    const JdecFile* f = find_file(a.files, a.n, blockIdx.x, &JdecFile::group0);
+    const JdecFile* f = a.files + last_at_or_before(a.files, a.n, blockIdx.x, &JdecFile::group0);
     load_tables(s, f);
     const int tid = threadIdx.x, g = (int)blockIdx.x - f->group0, lane = g * kJdecGroup + tid;
     const bool live = lane < f->nsub;
@@ -373,7 +364,7 @@ __global__ void __launch_bounds__(256) jdec_scan_kernel(JdecArgs a) {
 
 __global__ void __launch_bounds__(kJdecGroup) jdec_write_kernel(JdecArgs a) {
     __shared__ JdecLds s;
-    const JdecFile* f = find_file(a.files, a.n, blockIdx.x, &JdecFile::group0);
+    const JdecFile* f = a.files + last_at_or_before(a.files, a.n, blockIdx.x, &JdecFile::group0);
     load_tables(s, f);
     const int lane = ((int)blockIdx.x - f->group0) * kJdecGroup + (int)threadIdx.x;
     if (lane >= f->nsub) return;
@@ -460,7 +451,7 @@ __device__ __forceinline__ void plane_geom(const JdecFile* f, int* pw, int* cw, 
 }
 
 __global__ void __launch_bounds__(256) jdec_idct_kernel(JdecArgs a) {
-    const JdecFile* f = find_file(a.files, a.n, blockIdx.x, &JdecFile::bchunk0);
+    const JdecFile* f = a.files + last_at_or_before(a.files, a.n, blockIdx.x, &JdecFile::bchunk0);
     const int B = ((int)blockIdx.x - f->bchunk0) * 256 + (int)threadIdx.x;
     if (B >= f->nblocks) return;
     const int m = B / f->bpm, b = B - m * f->bpm;
@@ -509,8 +500,6 @@ __global__ void __launch_bounds__(256) jdec_idct_kernel(JdecArgs a) {
     }
 }
 
-constexpr int fix16(double x) { return (int)(x * 65536.0 + 0.5); }
-
 // rules 4, 5 and 5b: the chroma sample of pixel (y, x) from the plane p of row length cw
 __device__ __forceinline__ int fancy(const unsigned char* p, int cw, int Hc, int Wc, int y, int x) {
     const int r = y >> 1, c = x >> 1;
@@ -528,7 +517,7 @@ __device__ __forceinline__ int fancy(const unsigned char* p, int cw, int Hc, int
 }
 
 __global__ void __launch_bounds__(256) jdec_colour_kernel(JdecArgs a) {
-    const JdecFile* f = find_file(a.files, a.n, blockIdx.x, &JdecFile::pchunk0);
+    const JdecFile* f = a.files + last_at_or_before(a.files, a.n, blockIdx.x, &JdecFile::pchunk0);
     const long long i = (long long)((int)blockIdx.x - f->pchunk0) * 256 + threadIdx.x;
     const int H = f->H, W = f->W;
     if (i >= (long long)H * W) return;

@@ -32,17 +32,6 @@ namespace {
 
 struct __attribute__((packed, aligned(4))) F4 { float x, y, z, w; };   // 16 bytes from a 4-byte aligned address: one global_load_dwordx4
 
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_sum64(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // element e (0 .. 8, row-major) of pare's batch_rodrigues(theta) - SPIN's form, fp32 like the reference
 __device__ __forceinline__ float spin_rodrigues_element(float tx, float ty, float tz, int e) {
     const float ex = tx + 1e-8f, ey = ty + 1e-8f, ez = tz + 1e-8f;

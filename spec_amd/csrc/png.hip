@@ -105,16 +105,6 @@ __host__ __device__ inline void header33(int H, int W, unsigned char* o) {
 }
 
 // ---- device half ------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ PngPic find_pic(const PngPic* pics, int n, int index, int PngPic::*first, int* which) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pics[mid].*first <= index) lo = mid; else hi = mid;
-    }
-    *which = lo;
-    return pics[lo];
-}
-
 __device__ __forceinline__ int paeth(int a, int b, int c) {
     const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
     return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
@@ -128,8 +118,7 @@ __device__ __forceinline__ void filtered(const unsigned char* cur, const unsigne
 
 // one row of the call, by the whole workgroup; `sums` is its five counters in LDS
 __device__ __forceinline__ void filter_row(const PngArgs& a, int row, int* sums) {
-    int pi;
-    const PngPic p = find_pic(a.pics, a.n, row, &PngPic::row0, &pi);
+    const PngPic p = a.pics[last_at_or_before(a.pics, a.n, row, &PngPic::row0)];
     const int y = row - p.row0, n = 3 * p.W;
     const unsigned char* cur = a.in + p.in_off + (long long)y * p.in_pitch;
     const unsigned char* up = y ? cur - p.in_pitch : nullptr;
@@ -162,24 +151,6 @@ __device__ __forceinline__ void filter_row(const PngArgs& a, int row, int* sums)
 __global__ void __launch_bounds__(256) png_filter_kernel(PngArgs a) {
     __shared__ int sums[5];
     for (long long row = blockIdx.x; row < a.rows; row += gridDim.x) filter_row(a, (int)row, sums);
-}
-
-// exclusive scan of one value per thread over the 256 threads of a workgroup -> and the total
-template <typename T> __device__ __forceinline__ T block_scan(T v, T* lds, T* total) {
-    const int tid = threadIdx.x;
-    lds[tid] = v;
-    __syncthreads();
-#pragma unroll
-    for (int d = 1; d < 256; d <<= 1) {
-        const T add = tid >= d ? lds[tid - d] : T(0);
-        __syncthreads();
-        lds[tid] += add;
-        __syncthreads();
-    }
-    const T incl = lds[tid];
-    *total = lds[255];
-    __syncthreads();                     // the caller may use lds again
-    return incl - v;
 }
 
 // `len` bits of v into a zeroed little-endian bit stream at bit `at` (len <= 32)
@@ -267,8 +238,8 @@ template <bool EXIT> __device__ __forceinline__ void match_pass(PngSeg& s, int l
 __global__ void __launch_bounds__(256) png_segment_kernel(PngArgs a) {
     __shared__ PngSeg s;
     const int tid = threadIdx.x;
-    int pi;
-    const PngPic p = find_pic(a.pics, a.n, blockIdx.x, &PngPic::seg0, &pi);
+    const int pi = last_at_or_before(a.pics, a.n, blockIdx.x, &PngPic::seg0);
+    const PngPic p = a.pics[pi];
     const int k = (int)blockIdx.x - p.seg0;
     const int n = (int)min((long long)kPngSegment, p.stream - (long long)k * kPngSegment);
     const bool last = k == p.nseg - 1;
@@ -496,8 +467,8 @@ __global__ void __launch_bounds__(256) png_pack_kernel(PngArgs a) {
     __shared__ unsigned table[256];
     __shared__ unsigned share;
     const int tid = threadIdx.x;
-    int pi;
-    const PngPic p = find_pic(a.pics, a.n, blockIdx.x, &PngPic::seg0, &pi);
+    const int pi = last_at_or_before(a.pics, a.n, blockIdx.x, &PngPic::seg0);
+    const PngPic p = a.pics[pi];
     {
         unsigned c = (unsigned)tid;
         for (int k = 0; k < 8; ++k) c = (c & 1u) ? (c >> 1) ^ kCrcPoly : c >> 1;

@@ -536,19 +536,10 @@ __global__ void __launch_bounds__(kPdecLanes) pdec_inflate_kernel(PdecArgs a) {
     if (tid == 0 && st) atomicOr(a.status + blockIdx.x, st);
 }
 
-__device__ __forceinline__ const PdecFile* find_file(const PdecFile* files, int n, int chunk) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (files[mid].chunk0 <= chunk) lo = mid; else hi = mid;
-    }
-    return files + lo;
-}
-
 // a workgroup per chunk of kPdecAdlerChunk inflated bytes: the sum of the bytes and the sum of (n - i) byte[i], both mod 65521
 __global__ void __launch_bounds__(256) pdec_adler_kernel(PdecArgs a) {
     __shared__ unsigned long long l1[256], l2[256];
-    const PdecFile* f = find_file(a.files, a.n, blockIdx.x);
+    const PdecFile* f = a.files + last_at_or_before(a.files, a.n, blockIdx.x, &PdecFile::chunk0);
     const long long at = (long long)((int)blockIdx.x - f->chunk0) * kPdecAdlerChunk;
     const int n = (int)min((long long)kPdecAdlerChunk, f->raw_len - at), tid = threadIdx.x;
     const unsigned char* raw = a.raw + f->raw_off + at;

@@ -18,7 +18,8 @@
 
 namespace specmi {
 
-// Work mapping shared by the two crop kernels: a workgroup covers 256 * kPX consecutive output pixels of one crop as
+// Work mapping of both crops, in their kernels for one frame size and for ragged slabs alike (crop_normalize_pixels and
+// crop_resize_pixels state it): a workgroup covers kNB batches of 256 * kPX consecutive output pixels of one crop, each as
 // kPX chunks of 256; lane t handles pixel chunk * 256 + t of each chunk.  Neighbouring lanes therefore read neighbouring
 // source pixels (a wave's gather touches 2-5 cache lines, not the 10-20 a "4 consecutive pixels per lane" mapping does:
 // the L1 tag rate, not HBM, bounds a gather) and write 256 contiguous bytes per colour plane.  All taps of the kPX
@@ -96,44 +97,57 @@ constexpr int kTabX = 2048;                    // crops up to 2048 x 2048 use th
 constexpr int kNB = 2;                        // batches of kPX pixels per lane: a workgroup covers 256 * kPX * kNB pixels
 constexpr int kTabY = 256 * kPX * kNB + 2;     // rows a workgroup's pixels can touch (S = 1)
 
-// ToTensor + Normalize of a uint8 value takes two IEEE divisions; the 3 x 256 possible results are tabulated in LDS
+// ToTensor + ImageNet Normalize of a uint8 value of colour plane c: two IEEE divisions and a subtraction
+__device__ __forceinline__ float to_tensor_normalize(int v, int c) { return normalize_unit((float)v / 255.0f, c); }
+
+// what the four crop launchers share: the grid (x: workgroups of a crop, y: crops) and the refusal of a frame that the
+// 24-bit multiplies and 32-bit byte offsets of load_tap_pair cannot address
+static dim3 crop_grid(int S, int n) { return dim3((S * S + 256 * kPX * kNB - 1) / (256 * kPX * kNB), n); }
+static bool crop_frame_too_large(int H, int W) { return H >= (1 << 24) || W >= (1 << 24) || (double)H * W * 3 >= 4294967296.0; }
+// WIDE's condition: by the host for a launch on one frame size, per crop (wave-uniform) in the ragged kernels
+__host__ __device__ __forceinline__ bool crop_wide(int H, int W) { return W >= 2 && (size_t)H * W * 3 >= 8; }
+
+// Each crop is stated once, as a prologue (what a workgroup prepares) and a per-pixel path (crop_*_pixels); its kernel for
+// frames of one size and its ragged kernel differ only in where (frame, H, W) come from.
+//
+// Demo crop.  ToTensor + Normalize of a uint8 value takes two IEEE divisions; the 3 x 256 possible results are tabulated in LDS
 // once per workgroup with exactly those divisions.  The separable source coordinates (fp64 -> 1/1024 px fixed point) are
 // tabulated too: S columns + the few rows of this workgroup instead of 4 fp64->int64 conversions per pixel.  The
 // per-pixel path is integer arithmetic + three LDS reads + two 8-byte loads.
-template <bool WIDE, bool TABLE, bool F16>
-__global__ void __launch_bounds__(256) crop_normalize_kernel(const unsigned char* __restrict__ frame, int H, int W,
-                                                              const float* __restrict__ bboxes, float scale, int S,
-                                                              void* __restrict__ out_, unsigned char* __restrict__ raw,
-                                                              float* __restrict__ bbox_scale,
-                                                              float* __restrict__ bbox_center,
-                                                              const int* __restrict__ frame_of, size_t frame_stride, int nframes) {
-    __shared__ float lut[3][256];
-    __shared__ int2 tabx[TABLE ? kTabX : 1], taby[TABLE ? kTabY : 1];
+//
+// The prologue of crop d = blockIdx.y: the table of normalised values, the box (recorded as bbox_scale / bbox_center by the
+// crop's first workgroup), its inverse affine and the coordinate tables; ends with the barrier that publishes the tables
+template <bool TABLE>
+__device__ __forceinline__ CropAffine crop_normalize_prologue(int H, int W, const float* __restrict__ bboxes, float scale, int S,
+                                                              float* __restrict__ bbox_scale, float* __restrict__ bbox_center,
+                                                              float (&lut)[3][256], int2* tabx, int2* taby) {
     const int d = blockIdx.y, t = threadIdx.x;
-    float* __restrict__ out = static_cast<float*>(out_);
-    // batched: crop d is cut from frame frame_of[d] of a slab of equal-sized frames.  The index comes from caller memory the host
-    // side cannot check without a synchronisation: a stale / negative / too large value is clamped into the slab (a wrong crop,
-    // never an out-of-bounds read); spec_amd.preprocess.crop_detections_batch rejects it while the index is still on the host
-    if (frame_of) frame += (size_t)min((unsigned)max(frame_of[d], 0), (unsigned)(nframes - 1)) * frame_stride;
-    {
-        const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
 #pragma unroll
-        for (int c = 0; c < 3; ++c) lut[c][t] = ((float)t / 255.0f - mean[c]) / stdv[c];
-    }
+    for (int c = 0; c < 3; ++c) lut[c][t] = to_tensor_normalize(t, c);
     const float cx = bboxes[d * 4 + 0], cy = bboxes[d * 4 + 1], bw = bboxes[d * 4 + 2], bh = bboxes[d * 4 + 3];
     if (blockIdx.x == 0 && t == 0) {
         if (bbox_scale) bbox_scale[d] = bw / 200.0f;
         if (bbox_center) { bbox_center[d * 2 + 0] = cx; bbox_center[d * 2 + 1] = cy; }
     }
     const CropAffine A(cx, cy, bw, bh, scale, S);
-    const int npix = S * S, pix0 = blockIdx.x * (256 * kPX * kNB);
-    const int yfirst = pix0 / S;
     if (TABLE) {
-        const int ylast = min(pix0 + 256 * kPX * kNB - 1, npix - 1) / S;
+        const int npix = S * S, pix0 = blockIdx.x * (256 * kPX * kNB);
+        const int yfirst = pix0 / S, ylast = min(pix0 + 256 * kPX * kNB - 1, npix - 1) / S;
         for (int i = t; i < S; i += 256) tabx[i] = A.col(i, W);
         for (int i = t; i <= ylast - yfirst; i += 256) taby[i] = A.row(yfirst + i, H);
     }
     __syncthreads();
+    return A;
+}
+
+template <bool WIDE, bool TABLE, bool F16>
+__device__ __forceinline__ void crop_normalize_pixels(const unsigned char* __restrict__ frame, int H, int W, const CropAffine& A, int S,
+                                                      const float (&lut)[3][256], const int2* tabx, const int2* taby,
+                                                      void* __restrict__ out_, unsigned char* __restrict__ raw) {
+    float* __restrict__ out = static_cast<float*>(out_);
+    const int d = blockIdx.y, t = threadIdx.x;
+    const int npix = S * S, pix0 = blockIdx.x * (256 * kPX * kNB);
+    const int yfirst = pix0 / S;
     const size_t total = (size_t)H * W * 3;
 #pragma unroll 1
     for (int kb = 0; kb < kNB; ++kb) {
@@ -180,6 +194,23 @@ __global__ void __launch_bounds__(256) crop_normalize_kernel(const unsigned char
 }
 
 template <bool WIDE, bool TABLE, bool F16>
+__global__ void __launch_bounds__(256) crop_normalize_kernel(const unsigned char* __restrict__ frame, int H, int W,
+                                                              const float* __restrict__ bboxes, float scale, int S,
+                                                              void* __restrict__ out, unsigned char* __restrict__ raw,
+                                                              float* __restrict__ bbox_scale,
+                                                              float* __restrict__ bbox_center,
+                                                              const int* __restrict__ frame_of, size_t frame_stride, int nframes) {
+    __shared__ float lut[3][256];
+    __shared__ int2 tabx[TABLE ? kTabX : 1], taby[TABLE ? kTabY : 1];
+    // batched: crop d is cut from frame frame_of[d] of a slab of equal-sized frames.  The index comes from caller memory the host
+    // side cannot check without a synchronisation: a stale / negative / too large value is clamped into the slab (a wrong crop,
+    // never an out-of-bounds read); spec_amd.preprocess.crop_detections_batch rejects it while the index is still on the host
+    if (frame_of) frame += (size_t)min((unsigned)max(frame_of[blockIdx.y], 0), (unsigned)(nframes - 1)) * frame_stride;
+    const CropAffine A = crop_normalize_prologue<TABLE>(H, W, bboxes, scale, S, bbox_scale, bbox_center, lut, tabx, taby);
+    crop_normalize_pixels<WIDE, TABLE, F16>(frame, H, W, A, S, lut, tabx, taby, out, raw);
+}
+
+template <bool WIDE, bool TABLE, bool F16>
 static void crop_normalize_go(dim3 grid, hipStream_t st, const unsigned char* frame, int H, int W, const float* bboxes, float scale,
                               int S, void* out, unsigned char* raw, float* bbox_scale, float* bbox_center, const int* frame_of,
                               size_t frame_stride, int nframes) {
@@ -193,15 +224,14 @@ int launch_crop_normalize(const unsigned char* frame, int H, int W, const float*
     // algorithmic HBM bytes: every frame once + every output once (the 4 taps x 3 channels of a pixel come through L2)
     ProfScope ps(ctx, f16 ? "crop_normalize_f16" : "crop_normalize", 0.0,
                  (double)H * W * 3 * (frame_of ? nframes : 1) + (double)n * S * S * ((f16 ? 16.0 : 12.0) + (raw ? 3.0 : 0.0)));
-    if (H >= (1 << 24) || W >= (1 << 24) || (double)H * W * 3 >= 4294967296.0) return (int)hipErrorInvalidValue;   // 32-bit offsets
-    const dim3 grid((S * S + 256 * kPX * kNB - 1) / (256 * kPX * kNB), n);
-    const bool wide = W >= 2 && (size_t)H * W * 3 >= 8, table = S <= kTabX;
+    if (crop_frame_too_large(H, W)) return (int)hipErrorInvalidValue;
+    const bool wide = crop_wide(H, W), table = S <= kTabX;
     auto go = f16 ? (wide ? (table ? crop_normalize_go<true, true, true> : crop_normalize_go<true, false, true>)
                           : (table ? crop_normalize_go<false, true, true> : crop_normalize_go<false, false, true>))
                   : (wide ? (table ? crop_normalize_go<true, true, false> : crop_normalize_go<true, false, false>)
                           : (table ? crop_normalize_go<false, true, false> : crop_normalize_go<false, false, false>));
     if (frame_of && nframes < 1) return (int)hipErrorInvalidValue;
-    go(grid, ctx.stream, frame, H, W, bboxes, scale, S, out, raw, bbox_scale, bbox_center, frame_of, (size_t)H * W * 3, nframes);
+    go(crop_grid(S, n), ctx.stream, frame, H, W, bboxes, scale, S, out, raw, bbox_scale, bbox_center, frame_of, (size_t)H * W * 3, nframes);
     return (int)hipGetLastError();
 }
 
@@ -221,39 +251,51 @@ __device__ __forceinline__ void resize_coord(int i, double scale, int n, int& s0
     if (s0 >= n - 1) { f = 0.f; s0 = n - 1; }
 }
 
-template <bool WIDE, bool TABLE, bool F16>
-__global__ void __launch_bounds__(256) crop_resize_normalize_kernel(const unsigned char* __restrict__ frame, int H, int W,
-                                                                     const int* __restrict__ boxes, int S,
-                                                                     void* __restrict__ out_) {
+struct ResizeBox { int ulx, uly, bw, bh; double scale_x, scale_y; };
+
+// crop d = blockIdx.y: the box, cv::resize's scales and the coordinate tables (the coordinates are separable: S columns + this
+// workgroup's few rows, once); crop_resize_pixels begins with the barrier that publishes them, so that the frame record a ragged
+// kernel reads in between is in flight meanwhile.  An empty box (br <= ul) is all zeros to the reference: the workgroup writes
+// its pixels' Normalize(0) here and the caller returns on `false` - a decision per crop, so the whole workgroup takes it
+template <bool TABLE, bool F16>
+__device__ __forceinline__ bool crop_resize_prologue(const int* __restrict__ boxes, int S, void* __restrict__ out_, ResizeBox& b,
+                                                     int* txs, int* tys, float* txf, float* tyf) {
     float* __restrict__ out = static_cast<float*>(out_);
-    __shared__ int txs[TABLE ? kTabX : 1], tys[TABLE ? kTabY : 1];
-    __shared__ float txf[TABLE ? kTabX : 1], tyf[TABLE ? kTabY : 1];
     const int d = blockIdx.y, t = threadIdx.x;
-    const int npix = S * S, pix0 = blockIdx.x * (256 * kPX * kNB);     // same mapping as crop_normalize_kernel
-    const int ulx = boxes[d * 4 + 0], uly = boxes[d * 4 + 1], brx = boxes[d * 4 + 2], bry = boxes[d * 4 + 3];
-    const int bw = brx - ulx, bh = bry - uly;
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    if (bw <= 0 || bh <= 0) {
+    const int npix = S * S, pix0 = blockIdx.x * (256 * kPX * kNB);     // same mapping as the demo crop
+    b.ulx = boxes[d * 4 + 0]; b.uly = boxes[d * 4 + 1];
+    b.bw = boxes[d * 4 + 2] - b.ulx; b.bh = boxes[d * 4 + 3] - b.uly;
+    if (b.bw <= 0 || b.bh <= 0) {
         for (int i = pix0 + t; i < min(pix0 + 256 * kPX * kNB, npix); i += 256) {
             float r[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                r[c] = (0.0f - mean[c]) / stdv[c];
+                r[c] = normalize_unit(0.0f, c);
                 if (!F16) out[(size_t)(d * 3 + c) * npix + i] = r[c];
             }
             if (F16) store_nhwc8(out_, (size_t)d * npix + i, r);
         }
-        return;
+        return false;
     }
     // cv::resize INTER_LINEAR: fx = (float)((dx + 0.5) * scale - 0.5), sx = floor(fx), fx -= sx, clamped to the box
-    const double scale_x = (double)bw / (double)S, scale_y = (double)bh / (double)S;
-    const int yfirst = pix0 / S;
-    if (TABLE) {       // the coordinates are separable: S columns + this workgroup's few rows, once
-        const int ylast = min(pix0 + 256 * kPX * kNB - 1, npix - 1) / S;
-        for (int i = t; i < S; i += 256) resize_coord(i, scale_x, bw, txs[i], txf[i]);
-        for (int i = t; i <= ylast - yfirst; i += 256) resize_coord(yfirst + i, scale_y, bh, tys[i], tyf[i]);
-        __syncthreads();
+    b.scale_x = (double)b.bw / (double)S; b.scale_y = (double)b.bh / (double)S;
+    if (TABLE) {
+        const int yfirst = pix0 / S, ylast = min(pix0 + 256 * kPX * kNB - 1, npix - 1) / S;
+        for (int i = t; i < S; i += 256) resize_coord(i, b.scale_x, b.bw, txs[i], txf[i]);
+        for (int i = t; i <= ylast - yfirst; i += 256) resize_coord(yfirst + i, b.scale_y, b.bh, tys[i], tyf[i]);
     }
+    return true;
+}
+
+template <bool WIDE, bool TABLE, bool F16>
+__device__ __forceinline__ void crop_resize_pixels(const unsigned char* __restrict__ frame, int H, int W, const ResizeBox& b, int S,
+                                                   const int* txs, const int* tys, const float* txf, const float* tyf,
+                                                   void* __restrict__ out_) {
+    if (TABLE) __syncthreads();     // the tables of crop_resize_prologue
+    float* __restrict__ out = static_cast<float*>(out_);
+    const int d = blockIdx.y, t = threadIdx.x;
+    const int npix = S * S, pix0 = blockIdx.x * (256 * kPX * kNB);
+    const int yfirst = pix0 / S;
     const size_t total = (size_t)H * W * 3;
 #pragma unroll 1
     for (int kb = 0; kb < kNB; ++kb) {
@@ -270,11 +312,11 @@ __global__ void __launch_bounds__(256) crop_resize_normalize_kernel(const unsign
             int sx, sy;
             float fx, fy;
             if (TABLE) { sx = txs[dx]; fx = txf[dx]; sy = tys[dy - yfirst]; fy = tyf[dy - yfirst]; }
-            else { resize_coord(dx, scale_x, bw, sx, fx); resize_coord(dy, scale_y, bh, sy, fy); }
-            const int sx1 = sx + 1 < bw ? sx + 1 : sx, sy1 = sy + 1 < bh ? sy + 1 : sy;
+            else { resize_coord(dx, b.scale_x, b.bw, sx, fx); resize_coord(dy, b.scale_y, b.bh, sy, fy); }
+            const int sx1 = sx + 1 < b.bw ? sx + 1 : sx, sy1 = sy + 1 < b.bh ? sy + 1 : sy;
             cf[k][0] = fx; cf[k][1] = fy;
             // box pixel -> frame pixel (zero where the box leaves the frame)
-            const int iy0 = uly + sy, iy1 = uly + sy1, ix0 = ulx + sx, ix1 = ulx + sx1;
+            const int iy0 = b.uly + sy, iy1 = b.uly + sy1, ix0 = b.ulx + sx, ix1 = b.ulx + sx1;
             const bool vy0 = (unsigned)iy0 < (unsigned)H, vy1 = (unsigned)iy1 < (unsigned)H;
             const bool vx0 = (unsigned)ix0 < (unsigned)W, vx1 = (unsigned)ix1 < (unsigned)W;
             in[k][0] = vy0 && vx0; in[k][1] = vy0 && vx1; in[k][2] = vy1 && vx0; in[k][3] = vy1 && vx1;
@@ -298,14 +340,24 @@ __global__ void __launch_bounds__(256) crop_resize_normalize_kernel(const unsign
                     const double r1 = __dadd_rn(__dmul_rn(p10, a0), __dmul_rn(p11, a1));
                     double v = __dadd_rn(__dmul_rn(r0, b0), __dmul_rn(r1, b1));             // vertical pass
                     v = fmin(255.0, fmax(0.0, v));                                          // rgb_processing: pn = 1, clip
-                    const float tt = (float)v / 255.0f;                                     // astype('float32') / 255.0
-                    r[c] = (tt - mean[c]) / stdv[c];
+                    r[c] = normalize_unit((float)v / 255.0f, c);                            // astype('float32') / 255.0, Normalize
                     if (!F16) out[(size_t)(d * 3 + c) * npix + idx] = r[c];
                 }
                 if (F16) store_nhwc8(out_, (size_t)d * npix + idx, r);
             }
         }
     }
+}
+
+template <bool WIDE, bool TABLE, bool F16>
+__global__ void __launch_bounds__(256) crop_resize_normalize_kernel(const unsigned char* __restrict__ frame, int H, int W,
+                                                                     const int* __restrict__ boxes, int S,
+                                                                     void* __restrict__ out) {
+    __shared__ int txs[TABLE ? kTabX : 1], tys[TABLE ? kTabY : 1];
+    __shared__ float txf[TABLE ? kTabX : 1], tyf[TABLE ? kTabY : 1];
+    ResizeBox b;
+    if (!crop_resize_prologue<TABLE, F16>(boxes, S, out, b, txs, tys, txf, tyf)) return;
+    crop_resize_pixels<WIDE, TABLE, F16>(frame, H, W, b, S, txs, tys, txf, tyf, out);
 }
 
 template <bool WIDE, bool TABLE, bool F16>
@@ -317,14 +369,13 @@ int launch_crop_resize_normalize(const unsigned char* frame, int H, int W, const
                                  const LaunchCtx& ctx, bool f16) {
     ProfScope ps(ctx, f16 ? "crop_resize_normalize_f16" : "crop_resize_normalize", 0.0,
                  (double)H * W * 3 + (double)n * S * S * (f16 ? 16.0 : 12.0));
-    if (H >= (1 << 24) || W >= (1 << 24) || (double)H * W * 3 >= 4294967296.0) return (int)hipErrorInvalidValue;   // 32-bit offsets
-    const dim3 grid((S * S + 256 * kPX * kNB - 1) / (256 * kPX * kNB), n);
-    const bool wide = W >= 2 && (size_t)H * W * 3 >= 8, table = S <= kTabX;
+    if (crop_frame_too_large(H, W)) return (int)hipErrorInvalidValue;
+    const bool wide = crop_wide(H, W), table = S <= kTabX;
     auto go = f16 ? (wide ? (table ? crop_resize_go<true, true, true> : crop_resize_go<true, false, true>)
                           : (table ? crop_resize_go<false, true, true> : crop_resize_go<false, false, true>))
                   : (wide ? (table ? crop_resize_go<true, true, false> : crop_resize_go<true, false, false>)
                           : (table ? crop_resize_go<false, true, false> : crop_resize_go<false, false, false>));
-    go(grid, ctx.stream, frame, H, W, boxes, S, out);
+    go(crop_grid(S, n), ctx.stream, frame, H, W, boxes, S, out);
     return (int)hipGetLastError();
 }
 
@@ -332,63 +383,14 @@ int launch_crop_resize_normalize(const unsigned char* frame, int H, int W, const
 // The two crops from frames of DIFFERENT sizes in one launch (the per-sample loop of EvalDataset.batch, the per-frame loop of
 // SPECTester.run_on_image_folder): the frames lie in one uint8 slab, crop d (blockIdx.y) reads frame_of[d] - clamped into
 // [0, nframes) like the equal-size batch - and from that its frame's record (CropFrame: byte offset, H, W) out of a device
-// table, then runs the per-pixel path of the kernels above on frames + offset with that H and W: the same device functions in
-// the same order, hence the same bits.  Same work mapping, tables and stores.  WIDE is decided per crop (a slab mixes a 1 x 1
-// frame with a 1080p one); a workgroup serves one crop, so the branch is wave-uniform and each side keeps its taps back to
-// back.  The 8-byte tap load clamps against its own frame's `total`, so it never leaves the frame, hence never the slab;
-// frames start at any byte offset (the load is an unaligned memcpy).
+// table, then calls the crop's prologue and per-pixel path - the functions the kernels above call, so there is one statement of
+// the arithmetic, the work mapping, the tables and the stores - on frames + offset with that H and W.  WIDE is decided per crop
+// (a slab mixes a 1 x 1 frame with a 1080p one); a workgroup serves one crop, so the branch is wave-uniform and each side
+// keeps its taps back to back.  The 8-byte tap load clamps against its own frame's `total`, so it never leaves the frame,
+// hence never the slab; frames start at any byte offset (the load is an unaligned memcpy).
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ CropFrame ragged_frame(const CropFrame* __restrict__ tab, const int* __restrict__ frame_of, int d, int nframes) {
     return tab[min((unsigned)max(frame_of[d], 0), (unsigned)(nframes - 1))];
-}
-
-template <bool WIDE, bool TABLE, bool F16>
-__device__ __forceinline__ void crop_normalize_pixels(const unsigned char* __restrict__ frame, int H, int W, const CropAffine& A, int S,
-                                                      int d, int pix0, int yfirst, const float (&lut)[3][256], const int2* tabx,
-                                                      const int2* taby, void* __restrict__ out_, unsigned char* __restrict__ raw) {
-    float* __restrict__ out = static_cast<float*>(out_);
-    const int t = threadIdx.x, npix = S * S;
-    const size_t total = (size_t)H * W * 3;
-#pragma unroll 1
-    for (int kb = 0; kb < kNB; ++kb) {
-        const int idx0 = pix0 + kb * (256 * kPX) + t;
-        if (idx0 - t >= npix) break;
-        int tap[kPX][4][3], wgt[kPX][4];
-#pragma unroll
-        for (int k = 0; k < kPX; ++k) {
-            const int idx = min(idx0 + k * 256, npix - 1);
-            const int y = idx / S, x = idx - y * S;
-            const int2 cxf = TABLE ? tabx[x] : A.col(x, W), cyf = TABLE ? taby[y - yfirst] : A.row(y, H);
-            const int sx = cxf.x, fx = cxf.y, sy = cyf.x, fy = cyf.y;
-            const bool y0 = sy >= 0 && sy < H, y1 = sy + 1 >= 0 && sy + 1 < H;
-            const bool x0 = sx >= 0 && sx < W, x1 = sx + 1 >= 0 && sx + 1 < W;
-            wgt[k][0] = (y0 && x0) ? __mul24(32 - fx, 32 - fy) * 32 : 0;
-            wgt[k][1] = (y0 && x1) ? __mul24(fx, 32 - fy) * 32 : 0;
-            wgt[k][2] = (y1 && x0) ? __mul24(32 - fx, fy) * 32 : 0;
-            wgt[k][3] = (y1 && x1) ? __mul24(fx, fy) * 32 : 0;
-            const int cy0 = min(max(sy, 0), H - 1), cy1 = min(max(sy + 1, 0), H - 1);
-            const int cx0 = min(max(sx, 0), W - 1), cx1 = min(max(sx + 1, 0), W - 1);
-            load_tap_pair<WIDE>(frame, total, W, cy0, cx0, cx1, tap[k][0], tap[k][1]);
-            load_tap_pair<WIDE>(frame, total, W, cy1, cx0, cx1, tap[k][2], tap[k][3]);
-        }
-#pragma unroll
-        for (int k = 0; k < kPX; ++k) {
-            const int idx = idx0 + k * 256;
-            if (idx < npix) {
-                float r[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    int v = (__mul24(tap[k][0][c], wgt[k][0]) + __mul24(tap[k][1][c], wgt[k][1]) + __mul24(tap[k][2][c], wgt[k][2]) +
-                             __mul24(tap[k][3][c], wgt[k][3]) + (1 << 14)) >> 15;
-                    v = v < 0 ? 0 : (v > 255 ? 255 : v);
-                    if (raw) raw[((size_t)d * npix + idx) * 3 + c] = (unsigned char)v;
-                    r[c] = lut[c][v];
-                    if (!F16) out[(size_t)(d * 3 + c) * npix + idx] = r[c];
-                }
-                if (F16) store_nhwc8(out_, (size_t)d * npix + idx, r);
-            }
-        }
-    }
 }
 
 template <bool TABLE, bool F16>
@@ -396,37 +398,14 @@ __global__ void __launch_bounds__(256) crop_normalize_ragged_kernel(const unsign
                                                                      const CropFrame* __restrict__ tab, int nframes,
                                                                      const int* __restrict__ frame_of,
                                                                      const float* __restrict__ bboxes, float scale, int S,
-                                                                     void* __restrict__ out_, unsigned char* __restrict__ raw,
+                                                                     void* __restrict__ out, unsigned char* __restrict__ raw,
                                                                      float* __restrict__ bbox_scale, float* __restrict__ bbox_center) {
     __shared__ float lut[3][256];
     __shared__ int2 tabx[TABLE ? kTabX : 1], taby[TABLE ? kTabY : 1];
-    const int d = blockIdx.y, t = threadIdx.x;
-    const CropFrame fr = ragged_frame(tab, frame_of, d, nframes);
-    const unsigned char* __restrict__ frame = frames + fr.off;
-    const int H = fr.H, W = fr.W;
-    {
-        const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) lut[c][t] = ((float)t / 255.0f - mean[c]) / stdv[c];
-    }
-    const float cx = bboxes[d * 4 + 0], cy = bboxes[d * 4 + 1], bw = bboxes[d * 4 + 2], bh = bboxes[d * 4 + 3];
-    if (blockIdx.x == 0 && t == 0) {
-        if (bbox_scale) bbox_scale[d] = bw / 200.0f;
-        if (bbox_center) { bbox_center[d * 2 + 0] = cx; bbox_center[d * 2 + 1] = cy; }
-    }
-    const CropAffine A(cx, cy, bw, bh, scale, S);
-    const int npix = S * S, pix0 = blockIdx.x * (256 * kPX * kNB);
-    const int yfirst = pix0 / S;
-    if (TABLE) {
-        const int ylast = min(pix0 + 256 * kPX * kNB - 1, npix - 1) / S;
-        for (int i = t; i < S; i += 256) tabx[i] = A.col(i, W);
-        for (int i = t; i <= ylast - yfirst; i += 256) taby[i] = A.row(yfirst + i, H);
-    }
-    __syncthreads();
-    if (W >= 2 && (size_t)H * W * 3 >= 8)      // launch_crop_normalize's WIDE rule, per crop
-        crop_normalize_pixels<true, TABLE, F16>(frame, H, W, A, S, d, pix0, yfirst, lut, tabx, taby, out_, raw);
-    else
-        crop_normalize_pixels<false, TABLE, F16>(frame, H, W, A, S, d, pix0, yfirst, lut, tabx, taby, out_, raw);
+    const CropFrame fr = ragged_frame(tab, frame_of, blockIdx.y, nframes);
+    const CropAffine A = crop_normalize_prologue<TABLE>(fr.H, fr.W, bboxes, scale, S, bbox_scale, bbox_center, lut, tabx, taby);
+    if (crop_wide(fr.H, fr.W)) crop_normalize_pixels<true, TABLE, F16>(frames + fr.off, fr.H, fr.W, A, S, lut, tabx, taby, out, raw);
+    else crop_normalize_pixels<false, TABLE, F16>(frames + fr.off, fr.H, fr.W, A, S, lut, tabx, taby, out, raw);
 }
 
 int launch_crop_normalize_ragged(const unsigned char* frames, const CropFrame* tab, int nframes, double slab_bytes, const int* frame_of,
@@ -435,122 +414,36 @@ int launch_crop_normalize_ragged(const unsigned char* frames, const CropFrame* t
     // algorithmic HBM bytes: the slab once + every output once
     ProfScope ps(ctx, f16 ? "crop_normalize_ragged_f16" : "crop_normalize_ragged", 0.0,
                  slab_bytes + (double)n * S * S * ((f16 ? 16.0 : 12.0) + (raw ? 3.0 : 0.0)));
-    const dim3 grid((S * S + 256 * kPX * kNB - 1) / (256 * kPX * kNB), n);
     const bool table = S <= kTabX;
     auto k = f16 ? (table ? crop_normalize_ragged_kernel<true, true> : crop_normalize_ragged_kernel<false, true>)
                  : (table ? crop_normalize_ragged_kernel<true, false> : crop_normalize_ragged_kernel<false, false>);
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, ctx.stream, frames, tab, nframes, frame_of, bboxes, scale, S, out, raw, bbox_scale, bbox_center);
+    hipLaunchKernelGGL(k, crop_grid(S, n), dim3(256), 0, ctx.stream, frames, tab, nframes, frame_of, bboxes, scale, S, out, raw, bbox_scale,
+                       bbox_center);
     return (int)hipGetLastError();
-}
-
-template <bool WIDE, bool TABLE, bool F16>
-__device__ __forceinline__ void crop_resize_pixels(const unsigned char* __restrict__ frame, int H, int W, int ulx, int uly, int bw, int bh,
-                                                   double scale_x, double scale_y, int S, int d, int pix0, int yfirst, const int* txs,
-                                                   const int* tys, const float* txf, const float* tyf, void* __restrict__ out_) {
-    float* __restrict__ out = static_cast<float*>(out_);
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    const int t = threadIdx.x, npix = S * S;
-    const size_t total = (size_t)H * W * 3;
-#pragma unroll 1
-    for (int kb = 0; kb < kNB; ++kb) {
-        const int idx0 = pix0 + kb * (256 * kPX) + t;
-        if (idx0 - t >= npix) break;
-        int tap[kPX][4][3];
-        bool in[kPX][4];
-        float cf[kPX][2];
-#pragma unroll
-        for (int k = 0; k < kPX; ++k) {
-            const int idx = min(idx0 + k * 256, npix - 1);
-            const int dy = idx / S, dx = idx - dy * S;
-            int sx, sy;
-            float fx, fy;
-            if (TABLE) { sx = txs[dx]; fx = txf[dx]; sy = tys[dy - yfirst]; fy = tyf[dy - yfirst]; }
-            else { resize_coord(dx, scale_x, bw, sx, fx); resize_coord(dy, scale_y, bh, sy, fy); }
-            const int sx1 = sx + 1 < bw ? sx + 1 : sx, sy1 = sy + 1 < bh ? sy + 1 : sy;
-            cf[k][0] = fx; cf[k][1] = fy;
-            const int iy0 = uly + sy, iy1 = uly + sy1, ix0 = ulx + sx, ix1 = ulx + sx1;
-            const bool vy0 = (unsigned)iy0 < (unsigned)H, vy1 = (unsigned)iy1 < (unsigned)H;
-            const bool vx0 = (unsigned)ix0 < (unsigned)W, vx1 = (unsigned)ix1 < (unsigned)W;
-            in[k][0] = vy0 && vx0; in[k][1] = vy0 && vx1; in[k][2] = vy1 && vx0; in[k][3] = vy1 && vx1;
-            const int cx0 = min(max(ix0, 0), W - 1), cx1 = min(max(ix1, 0), W - 1);
-            load_tap_pair<WIDE>(frame, total, W, min(max(iy0, 0), H - 1), cx0, cx1, tap[k][0], tap[k][1]);
-            load_tap_pair<WIDE>(frame, total, W, min(max(iy1, 0), H - 1), cx0, cx1, tap[k][2], tap[k][3]);
-        }
-#pragma unroll
-        for (int k = 0; k < kPX; ++k) {
-            const int idx = idx0 + k * 256;
-            if (idx < npix) {
-                const double a0 = (double)(1.f - cf[k][0]), a1 = (double)cf[k][0], b0 = (double)(1.f - cf[k][1]), b1 = (double)cf[k][1];
-                float r[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double p00 = in[k][0] ? (double)tap[k][0][c] : 0.0, p01 = in[k][1] ? (double)tap[k][1][c] : 0.0;
-                    const double p10 = in[k][2] ? (double)tap[k][2][c] : 0.0, p11 = in[k][3] ? (double)tap[k][3][c] : 0.0;
-                    const double r0 = __dadd_rn(__dmul_rn(p00, a0), __dmul_rn(p01, a1));     // no fma contraction, as above
-                    const double r1 = __dadd_rn(__dmul_rn(p10, a0), __dmul_rn(p11, a1));
-                    double v = __dadd_rn(__dmul_rn(r0, b0), __dmul_rn(r1, b1));
-                    v = fmin(255.0, fmax(0.0, v));
-                    const float tt = (float)v / 255.0f;
-                    r[c] = (tt - mean[c]) / stdv[c];
-                    if (!F16) out[(size_t)(d * 3 + c) * npix + idx] = r[c];
-                }
-                if (F16) store_nhwc8(out_, (size_t)d * npix + idx, r);
-            }
-        }
-    }
 }
 
 template <bool TABLE, bool F16>
 __global__ void __launch_bounds__(256) crop_resize_normalize_ragged_kernel(const unsigned char* __restrict__ frames,
                                                                             const CropFrame* __restrict__ tab, int nframes,
                                                                             const int* __restrict__ frame_of,
-                                                                            const int* __restrict__ boxes, int S, void* __restrict__ out_) {
-    float* __restrict__ out = static_cast<float*>(out_);
+                                                                            const int* __restrict__ boxes, int S, void* __restrict__ out) {
     __shared__ int txs[TABLE ? kTabX : 1], tys[TABLE ? kTabY : 1];
     __shared__ float txf[TABLE ? kTabX : 1], tyf[TABLE ? kTabY : 1];
-    const int d = blockIdx.y, t = threadIdx.x;
-    const int npix = S * S, pix0 = blockIdx.x * (256 * kPX * kNB);
-    const int ulx = boxes[d * 4 + 0], uly = boxes[d * 4 + 1], brx = boxes[d * 4 + 2], bry = boxes[d * 4 + 3];
-    const int bw = brx - ulx, bh = bry - uly;
-    if (bw <= 0 || bh <= 0) {
-        const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-        for (int i = pix0 + t; i < min(pix0 + 256 * kPX * kNB, npix); i += 256) {
-            float r[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                r[c] = (0.0f - mean[c]) / stdv[c];
-                if (!F16) out[(size_t)(d * 3 + c) * npix + i] = r[c];
-            }
-            if (F16) store_nhwc8(out_, (size_t)d * npix + i, r);
-        }
-        return;
-    }
-    const CropFrame fr = ragged_frame(tab, frame_of, d, nframes);
-    const unsigned char* __restrict__ frame = frames + fr.off;
-    const int H = fr.H, W = fr.W;
-    const double scale_x = (double)bw / (double)S, scale_y = (double)bh / (double)S;
-    const int yfirst = pix0 / S;
-    if (TABLE) {
-        const int ylast = min(pix0 + 256 * kPX * kNB - 1, npix - 1) / S;
-        for (int i = t; i < S; i += 256) resize_coord(i, scale_x, bw, txs[i], txf[i]);
-        for (int i = t; i <= ylast - yfirst; i += 256) resize_coord(yfirst + i, scale_y, bh, tys[i], tyf[i]);
-        __syncthreads();
-    }
-    if (W >= 2 && (size_t)H * W * 3 >= 8)      // launch_crop_resize_normalize's WIDE rule, per crop
-        crop_resize_pixels<true, TABLE, F16>(frame, H, W, ulx, uly, bw, bh, scale_x, scale_y, S, d, pix0, yfirst, txs, tys, txf, tyf, out_);
-    else
-        crop_resize_pixels<false, TABLE, F16>(frame, H, W, ulx, uly, bw, bh, scale_x, scale_y, S, d, pix0, yfirst, txs, tys, txf, tyf, out_);
+    ResizeBox b;
+    if (!crop_resize_prologue<TABLE, F16>(boxes, S, out, b, txs, tys, txf, tyf)) return;     // an empty box reads no frame: before the frame table
+    const CropFrame fr = ragged_frame(tab, frame_of, blockIdx.y, nframes);
+    if (crop_wide(fr.H, fr.W)) crop_resize_pixels<true, TABLE, F16>(frames + fr.off, fr.H, fr.W, b, S, txs, tys, txf, tyf, out);
+    else crop_resize_pixels<false, TABLE, F16>(frames + fr.off, fr.H, fr.W, b, S, txs, tys, txf, tyf, out);
 }
 
 int launch_crop_resize_normalize_ragged(const unsigned char* frames, const CropFrame* tab, int nframes, double slab_bytes,
                                         const int* frame_of, const int* boxes, int n, int S, void* out, const LaunchCtx& ctx, bool f16) {
     ProfScope ps(ctx, f16 ? "crop_resize_normalize_ragged_f16" : "crop_resize_normalize_ragged", 0.0,
                  slab_bytes + (double)n * S * S * (f16 ? 16.0 : 12.0));
-    const dim3 grid((S * S + 256 * kPX * kNB - 1) / (256 * kPX * kNB), n);
     const bool table = S <= kTabX;
     auto k = f16 ? (table ? crop_resize_normalize_ragged_kernel<true, true> : crop_resize_normalize_ragged_kernel<false, true>)
                  : (table ? crop_resize_normalize_ragged_kernel<true, false> : crop_resize_normalize_ragged_kernel<false, false>);
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, ctx.stream, frames, tab, nframes, frame_of, boxes, S, out);
+    hipLaunchKernelGGL(k, crop_grid(S, n), dim3(256), 0, ctx.stream, frames, tab, nframes, frame_of, boxes, S, out);
     return (int)hipGetLastError();
 }
 
@@ -615,11 +508,6 @@ __device__ __forceinline__ void pil_hpass(const unsigned char* __restrict__ row,
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) v[c] = pil_clip8(h[c]);                 // the uint8 image between the two passes
-}
-// ToTensor + ImageNet Normalize of a uint8 value of colour plane c
-__device__ __forceinline__ float to_tensor_normalize(int v, int c) {
-    const float mean[3] = {0.485f, 0.456f, 0.406f}, stdv[3] = {0.229f, 0.224f, 0.225f};
-    return ((float)v / 255.0f - mean[c]) / stdv[c];
 }
 
 template <bool F16>

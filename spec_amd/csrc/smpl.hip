@@ -32,14 +32,6 @@ constexpr int SKIN_LD = 98;                // floats per image row of the output
 constexpr int SKIN_SPLIT_MAX_TILES = 2;    // image tiles up to which the skin kernel runs three waves per vertex group (measured: DESIGN.md section 4)
 constexpr int A_TILE = 12 * 3 * 64 * 4;    // floats of one image tile of transforms [entry][quad][lane][4] (288 per image)
 
-// a0 b0 + a1 b1 + a2 b2 with the roundings written out (one product, two fused steps): the two instantiations of the pose kernel
-// must agree to the bit, and left to itself the compiler contracts the same source differently in each (-ffp-contract=fast
-// with aggressive FMA fusion picks by context)
-__device__ __forceinline__ float dot3(float a0, float b0, float a1, float b1, float a2, float b2) {
-#pragma clang fp contract(off)
-    return fmaf(a2, b2, fmaf(a1, b1, a0 * b0));
-}
-
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -278,12 +270,6 @@ __global__ void __launch_bounds__(SPLIT ? 192 : 256) smpl_skin_kernel(const floa
     }
 }
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 struct JointArgs {
     const float* verts; const float* posed_j; const float* J_extra; const int* extra_ids; const int* joint_map;
     const float* cam; const float* R; const float* K; const float* bbox_scale; const float* bbox_center;
@@ -348,7 +334,7 @@ __global__ void __launch_bounds__(JT) smpl_joints_kernel(const JointArgs a) {
     for (int e = 0; e < 9; ++e)
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float s = wsum(acc[e][c]);
+            const float s = wave_sum64(acc[e][c]);
             if ((t & 63) == 0) red[t >> 6][e * 3 + c] = s;
         }
     if (t < 72) J54[t / 3][t % 3] = pre;

@@ -37,17 +37,6 @@ constexpr int PART_ROWS = 256 + 12 * 32;   // rows of a partial slab: 256 featur
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float dot3(float a0, float b0, float a1, float b1, float a2, float b2) {
-#pragma clang fp contract(off)
-    return fmaf(a2, b2, fmaf(a1, b1, a0 * b0));
-}
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 struct JointBwdArgs {
     const float *j3d, *camt;                       // forward values (recomputed by this call)
     const float *cam, *R, *K, *bbox_scale, *bbox_center, *img_w, *img_h;
@@ -463,7 +452,7 @@ __global__ void __launch_bounds__(64) smpl_chain_bwd_kernel(const float* __restr
         for (int l = 0; l < 10; ++l) {
             float s = 0.f;
             if (act) s = dot3(Jd[(jj * 3 + 0) * 10 + l], gJ[0], Jd[(jj * 3 + 1) * 10 + l], gJ[1], Jd[(jj * 3 + 2) * 10 + l], gJ[2]);
-            s = wsum(s);
+            s = wave_sum64(s);
             if (j == 0) g_betas[(size_t)b * 10 + l] = s + gfeat[(size_t)b * 224 + 207 + l];
         }
     }

@@ -74,6 +74,64 @@ inline int set_dyn_lds_once(DevOnce& once, const void* fn, int bytes) {
 }
 
 // ----------------------------------------------------------------------------------------
+// small helpers that several kernel files use: each is stated here once
+// ----------------------------------------------------------------------------------------
+// the sum of v over the 64 lanes of a wave, on every lane; the order of the additions is part of every result built on it
+template <typename T> __device__ __forceinline__ T wave_sum64(T v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+// a0 b0 + a1 b1 + a2 b2 with the roundings written out (one product, two fused steps): SMPL's pose kernel (both instantiations)
+// and its backward must agree to the bit, and left to itself the compiler contracts the same source differently in each
+// (-ffp-contract=fast with aggressive FMA fusion picks by context)
+__device__ __forceinline__ float dot3(float a0, float b0, float a1, float b1, float a2, float b2) {
+#pragma clang fp contract(off)
+    return fmaf(a2, b2, fmaf(a1, b1, a0 * b0));
+}
+// exclusive scan of one value per thread over the 256 threads of a workgroup -> and the total
+template <typename T> __device__ __forceinline__ T block_scan(T v, T* lds, T* total) {
+    const int tid = threadIdx.x;
+    lds[tid] = v;
+    __syncthreads();
+#pragma unroll
+    for (int d = 1; d < 256; d <<= 1) {
+        const T add = tid >= d ? lds[tid - d] : T(0);
+        __syncthreads();
+        lds[tid] += add;
+        __syncthreads();
+    }
+    const T incl = lds[tid];
+    *total = lds[255];
+    __syncthreads();                     // the caller may use lds again
+    return incl - v;
+}
+// index of the last of n records, sorted by their member `first`, whose `first` is <= key (0 when none is): the picture or file
+// that a chunk, row or segment of a whole call belongs to
+template <typename T> __host__ __device__ __forceinline__ int last_at_or_before(const T* recs, int n, int key, int T::*first) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (recs[mid].*first <= key) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// libjpeg's FIX(x) at 16 fractional bits, for the colour conversions of the JPEG encoder and decoder
+constexpr int fix16(double x) { return (int)(x * 65536.0 + 0.5); }
+// ImageNet's mean / std of colour plane c, as torchvision's Normalize and pare's denormalize_images take them (a function:
+// device code cannot index a host array with a channel that is not a constant)
+__host__ __device__ __forceinline__ void imagenet_mean_std(int c, float& mean, float& stdv) {
+    const float m[3] = {0.485f, 0.456f, 0.406f}, s[3] = {0.229f, 0.224f, 0.225f};
+    mean = m[c]; stdv = s[c];
+}
+// Normalize of a ToTensor value x01 = u8 / 255 of colour plane c: a subtraction and a division, each rounded (no reciprocal)
+__host__ __device__ __forceinline__ float normalize_unit(float x01, int c) {
+    float mean, stdv;
+    imagenet_mean_std(c, mean, stdv);
+    return (x01 - mean) / stdv;
+}
+
+// ----------------------------------------------------------------------------------------
 // implicit-GEMM convolution / linear layer on fp32 MFMA  (conv_igemm.hip)
 // ----------------------------------------------------------------------------------------
 struct ConvArgs {
