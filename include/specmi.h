@@ -385,6 +385,56 @@ int specmi_rot6d_forward(specmi_handle* h, const float* x6d, int N, float* rotma
  * (N,3,3) -> g_x6d (N,6).  One lane per rotation; any handle.  Refuses NULL pointers and N <= 0 (SPECMI_ERR_ARG). */
 int specmi_rot6d_backward(specmi_handle* h, const float* x6d, const float* g_rotmat, int N, float* g_x6d, void* stream);
 
+/* pare's HMRHead regressor for training (spec/models/hmr.py:57-64,94-98; STABLE): the iterative loop itself, on parameters
+ * that an optimiser rewrites every step, with dropout, a tape, and its vector-Jacobian product.  H = 1024, S = 157 (144 rot6d |
+ * 10 betas | 3 cam), C = 7 with use_cam_feats else 0, Kin = F + S + C:
+ *     for t in 0 .. n_iter-1:   xc_t = [xf | state_t | cam_feats]
+ *                               a1_t = drop1(xc_t fc1^T + b1),  a2_t = drop2(a1_t fc2^T + b2)        (no activation)
+ *                               state_{t+1} = state_t + [decpose | decshape | deccam](a2_t)
+ * Dropout: a = h * (m ? s : 0) with s = (float)(1 / (1 - p)); `masks` is uint8 (2 n_iter, B, 1024), ordered (t, layer), non-zero
+ * = kept, drawn by the caller.  masks NULL is eval mode: no multiply, p is not read.
+ * The ten parameters are DEVICE pointers to the tensors of the module's state_dict, in their shapes and row-major layout: fc1
+ * (1024, Kin) / (1024), fc2 (1024, 1024) / (1024), decpose (144, 1024) / (144), decshape (10, 1024) / (10), deccam (3, 1024) / (3).
+ * They are read in place at every call - nothing is packed, uploaded or committed, and nothing of the handle's committed model
+ * is read: both calls work on a handle of any kind, committed or not.
+ *
+ * specmi_hmr_head_tape_floats: the size of the tape in floats, n_iter B (157 + 2 x 1024) - the states state_0 .. state_{n-1} and
+ *   the activations a1_t, a2_t, each stacked in (t, b) row order.  A pure function: no handle, no GPU call.  Refuses (returns
+ *   SPECMI_ERR_ARG) the shapes the two calls refuse and floats NULL.
+ * specmi_hmr_head_train_forward: xf (B, F), rows ld_xf floats apart; cam_feats (B, 7) dense = [rotmat_to_rot6d(cam_rotmat) |
+ *   vfov], NULL with C = 0; init_state (B, 157) dense; -> state (B, 157) dense = state_n, and the tape.  The tape is the
+ *   caller's buffer and the only thing the backward needs of the forward: the handle keeps nothing between the two calls.
+ * specmi_hmr_head_backward: the forward's params, xf, cam_feats, masks, p and shapes, its tape, and g_state (B, 157) dense, the
+ *   gradient of state_n; -> g_xf (B, F) dense and the ten parameter gradients in the parameters' shapes.  g_xf, grads and every
+ *   member of grads may be NULL (not wanted), but not all of them.  With only g_xf wanted no weight-gradient product is launched,
+ *   with g_xf NULL its product is not; a wanted output has the same bits whatever else is wanted.  init_state and cam_feats get
+ *   no gradient.
+ * Every product runs on the exact-fp32 matrix instruction (v_mfma_f32_32x32x2_f32), tails in every dimension handled in the
+ * kernel.  Deterministic: no float atomics, the order of every sum is fixed by the shapes, two runs give the same bits; row b
+ * of state and of g_xf has the same bits whatever batch it is in; the parameter gradients are sums over the n_iter B stacked rows
+ * in (t, b) order and depend on B alone.
+ * Workspace: B x 1024 floats for the forward, n_iter B (157 + 2 x 1024) + B x 1024 for the backward, in the handle; it grows on
+ * the first call of a shape, afterwards nothing is allocated and the calls can be captured into a graph.
+ * Refusals (SPECMI_ERR_ARG with a message, nothing launched, no output written): B < 1 or B > 2^20; F < 1 or F > 2^20; C not 0
+ * or 7; n_iter outside 1 .. 3; masks given and p outside [0, 1); params, one of its ten pointers, xf, init_state, state, tape
+ * resp. g_state NULL; cam_feats NULL with C = 7; a float pointer that is not 4-byte aligned; ld_xf < F; every output NULL. */
+typedef struct specmi_hmr_head_params {
+    const float *fc1_weight, *fc1_bias, *fc2_weight, *fc2_bias, *decpose_weight, *decpose_bias, *decshape_weight, *decshape_bias,
+        *deccam_weight, *deccam_bias;
+} specmi_hmr_head_params;
+typedef struct specmi_hmr_head_grads {
+    float *fc1_weight, *fc1_bias, *fc2_weight, *fc2_bias, *decpose_weight, *decpose_bias, *decshape_weight, *decshape_bias,
+        *deccam_weight, *deccam_bias;
+} specmi_hmr_head_grads;
+int specmi_hmr_head_tape_floats(int B, int F, int C, int n_iter, int64_t* floats);
+int specmi_hmr_head_train_forward(specmi_handle* h, const specmi_hmr_head_params* params, const float* xf, int64_t ld_xf,
+                                  const float* cam_feats, const float* init_state, const uint8_t* masks, float p, int B, int F,
+                                  int C, int n_iter, float* state, float* tape, void* stream);
+int specmi_hmr_head_backward(specmi_handle* h, const specmi_hmr_head_params* params, const float* xf, int64_t ld_xf,
+                             const float* cam_feats, const uint8_t* masks, float p, int B, int F, int C, int n_iter,
+                             const float* tape, const float* g_state, float* g_xf, const specmi_hmr_head_grads* grads,
+                             void* stream);
+
 /* The body model WITHOUT the 49-joint wrapper - smplx.SMPL.forward as the evaluation code calls it (`smpl_native` /
  * `body_model` / `body_model_orig`, spec/trainer.py:71-86,249-254, spec/utils/compute_error.py:118-160): `pose` is
  * (B,24,3,3) rotation matrices (pose2rot=False) or, with pose_is_axis_angle != 0, (B,72) axis-angle vectors

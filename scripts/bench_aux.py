@@ -21,6 +21,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only horizon_panel      # panel 0 of eight 1080p frames: Pillow on the host against specmi_draw_marks -> profiles/horizon_panel_aux.json
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
     python scripts/bench_aux.py --only eval_step          # the validation step's one launch against eval_mesh + eval_joints (means only) -> profiles/eval_step_aux.json
+    python scripts/bench_aux.py --head-train --out profiles/head_train_aux.json     # the trainable HMRHead's forward + backward at F = 2048, B = 64 and 256, next to torch autograd over the plain nn.Module on the same device
     python scripts/bench_aux.py --smpl-backward           # the SMPL head's forward, its backward and the loss backward at B = 256, V = 6890, next to torch autograd over the oracle chain on the same device -> profiles/smpl_backward_aux.json
     python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
@@ -1064,10 +1065,75 @@ def smpl_backward_section(a):
     return row
 
 
+def head_train_section(a):
+    """The trainable HMRHead (``specmi_hmr_head_train_forward`` + ``specmi_hmr_head_backward`` with the draw of the dropout masks:
+    one training step's forward and backward of the regressor, all eleven gradients) at F = 2048, use_cam_feats, p = 0.5, three
+    iterations, B = 64 and B = 256, next to torch's own autograd over the same head as a plain nn.Module (oracle/heads.py in train
+    mode, fp32, rocBLAS / hipBLASLt) on the same device and the same parameters.  HIP events around ``iters`` back-to-back calls
+    after a warm-up, the two alternated in this process, 3 rounds; then the library's kernels by its profiler."""
+    from oracle.heads import HMRHead as PlainHead
+    from spec_amd.cam_utils import _engine
+    dev = torch.device('cuda', 0)
+    eng = _engine(dev)
+    F, n_iter, p = 2048, 3, 0.5
+    out = {}
+    for B in (64, 256):
+        torch.manual_seed(B)
+        plain = PlainHead(F, smpl_mean_params={'pose': np.tile([1., 0, 0, 1, 0, 0], 24), 'shape': np.zeros(10), 'cam': np.array([0.9, 0, 0])},
+                          use_cam_feats=True).to(dev).train()
+        params = {k: v.detach() for k, v in plain.named_parameters()}
+        xf = torch.rand(B, F, device=dev) * 1.5
+        init = torch.cat([plain.init_pose, plain.init_shape, plain.init_cam], 1).expand(B, -1).contiguous()
+        rot = torch.linalg.qr(torch.randn(B, 3, 3, device=dev))[0].contiguous()
+        vfov = 0.6 + 0.8 * torch.rand(B, device=dev)
+        cam_feats = torch.cat([rot[:, :, :2].reshape(B, 6), vfov[:, None]], 1)
+        g_state = torch.randn(B, 157, device=dev)
+
+        def library():
+            masks = torch.rand(2 * n_iter, B, 1024, device=dev) >= p
+            _, tape = eng.hmr_head_train_forward(params, xf, init, cam_feats, masks, p, n_iter)
+            eng.hmr_head_backward(params, xf, tape, g_state, cam_feats, masks, p, n_iter)
+
+        def torch_autograd():
+            with torch.enable_grad():
+                feats = xf[:, :, None, None].detach().requires_grad_(True)
+                o = plain(feats, cam_rotmat=rot, cam_vfov=vfov, n_iter=n_iter)
+                state = torch.cat([o['pred_pose_6d'], o['pred_shape'], o['pred_cam']], 1)
+                torch.autograd.grad((state * g_state).sum(), [feats] + list(plain.parameters()))
+
+        def ms_per_call(fn):
+            for _ in range(5):
+                fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / a.iters
+        calls = {'library_forward_and_backward': library, 'torch_autograd_forward_and_backward': torch_autograd}
+        rounds = {k: [] for k in calls}
+        for _ in range(3):                                          # alternated: both see the same clocks and the same neighbours
+            for k, fn in calls.items():
+                rounds[k].append(ms_per_call(fn))
+        med = {k: float(np.median(v)) for k, v in rounds.items()}
+        kern = {k: {'launches_per_call': v[3], 'ms_per_launch': round(v[0], 5), 'ms_per_call': round(v[0] * v[3], 5),
+                    'TFLOPs': round(v[2] / (v[0] * 1e-3) / 1e12, 2) if v[2] else None} for k, v in timed(eng, library, a.iters).items()}
+        out[f'B{B}'] = {'workload': f'B = {B}, F = {F}, use_cam_feats, p = {p}, n_iter = {n_iter}; the library call includes the draw of the masks, '
+                                    'torch draws its own inside nn.Dropout; both return g_xf and the ten parameter gradients',
+                        'ms_round_values': {k: [round(x, 5) for x in v] for k, v in rounds.items()}, 'ms_median': {k: round(v, 5) for k, v in med.items()},
+                        'spread_between_rounds_ms': {k: round(max(v) - min(v), 5) for k, v in rounds.items()},
+                        'library_over_torch_autograd': round(med['library_forward_and_backward'] / med['torch_autograd_forward_and_backward'], 3),
+                        'library_kernels_by_the_library_profiler': kern}
+    print(json.dumps(out, indent=1))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'smpl_backward'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'smpl_backward', 'head_train'], default=None, help='run one section only')
     ap.add_argument('--smpl-backward', dest='only', action='store_const', const='smpl_backward', help='the same as --only smpl_backward')
+    ap.add_argument('--head-train', dest='only', action='store_const', const='head_train', help='the same as --only head_train')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -1092,6 +1158,15 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the same calls; 3 alternated rounds; '
                        'kernels: per-launch HIP events (library profiler)', 'smpl_backward': row, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'head_train':
+        from spec_amd import _lib
+        row = head_train_section(a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the same calls; 3 alternated rounds; '
+                       'kernels: per-launch HIP events (library profiler)', 'head_train': row, 'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     def add(name, workload, res, per_unit=None):

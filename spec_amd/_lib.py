@@ -68,6 +68,15 @@ class HmrOutputs(C.Structure):
         'pred_shape', 'pred_pose_6d')]
 
 
+HMR_HEAD_PARAMS = ('fc1.weight', 'fc1.bias', 'fc2.weight', 'fc2.bias', 'decpose.weight', 'decpose.bias', 'decshape.weight',
+                   'decshape.bias', 'deccam.weight', 'deccam.bias')     # the members of the two structs below, in order
+
+
+class HmrHeadParams(C.Structure):
+    """``specmi_hmr_head_params`` and ``specmi_hmr_head_grads`` (include/specmi.h): ten device pointers under the state_dict names."""
+    _fields_ = [(n.replace('.', '_'), C.c_void_p) for n in HMR_HEAD_PARAMS]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [('kernel', C.c_char * 48), ('label', C.c_char * 48), ('ms', C.c_double),
                 ('flops', C.c_double), ('bytes', C.c_double), ('launches', C.c_int)]
@@ -136,6 +145,14 @@ PROTOTYPES = {
                              [C.c_void_p] * 3 + [C.c_void_p]),
     'specmi_rot6d_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     'specmi_rot6d_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    'specmi_hmr_head_tape_floats': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_int64_p]),
+    # (h, params, xf, ld_xf, cam_feats, init_state, masks, p, B, F, C, n_iter, state, tape, stream)
+    'specmi_hmr_head_train_forward': (C.c_int, [C.c_void_p, C.POINTER(HmrHeadParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (h, params, xf, ld_xf, cam_feats, masks, p, B, F, C, n_iter, tape, g_state, g_xf, grads, stream)
+    'specmi_hmr_head_backward': (C.c_int, [C.c_void_p, C.POINTER(HmrHeadParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HmrHeadParams),
+                                           C.c_void_p]),
     'specmi_conv2d': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -2711,6 +2711,87 @@ int specmi_rot6d_backward(specmi_handle* h, const float* x6d, const float* g_rot
     return SPECMI_OK;
 }
 
+// the refusals the two HMRHead training calls and the tape size share; nullptr = accepted, else the message
+static const char* head_train_shape_refusal(int B, int F, int C, int n_iter) {
+    if (B < 1 || B > (1 << 20)) return "B must be in [1, 2^20]";
+    if (F < 1 || F > (1 << 20)) return "F must be in [1, 2^20]";
+    if (C != 0 && C != 7) return "C must be 0 or 7 (use_cam_feats)";
+    if (n_iter < 1 || n_iter > 3) return "n_iter must be in 1 .. 3";
+    return nullptr;
+}
+
+int specmi_hmr_head_tape_floats(int B, int F, int C, int n_iter, int64_t* floats) {
+    if (!floats || head_train_shape_refusal(B, F, C, n_iter)) return SPECMI_ERR_ARG;
+    *floats = (int64_t)head_tape_floats(B, n_iter);
+    return SPECMI_OK;
+}
+
+// the argument checks of both calls, and the kernels' argument block; `second` = init_state resp. g_state
+static int head_train_args(specmi_handle* h, const char* who, const specmi_hmr_head_params* params, const float* xf, int64_t ld_xf,
+                           const float* cam_feats, const uint8_t* masks, float p, int B, int F, int C, int n_iter, const void* tape,
+                           const void* second, const char* second_name, HeadTrainArgs& a) {
+    if (const char* why = head_train_shape_refusal(B, F, C, n_iter))
+        return fail(h, SPECMI_ERR_ARG, "%s: %s (B = %d, F = %d, C = %d, n_iter = %d)", who, why, B, F, C, n_iter);
+    if (masks && !(p >= 0.f && p < 1.f)) return fail(h, SPECMI_ERR_ARG, "%s: p = %g must be in [0, 1) when masks are given", who, (double)p);
+    if (!params) return fail(h, SPECMI_ERR_ARG, "%s: params is NULL", who);
+    const struct { const void* p; const char* name; } required[] = {
+        {params->fc1_weight, "fc1.weight"}, {params->fc1_bias, "fc1.bias"}, {params->fc2_weight, "fc2.weight"}, {params->fc2_bias, "fc2.bias"},
+        {params->decpose_weight, "decpose.weight"}, {params->decpose_bias, "decpose.bias"}, {params->decshape_weight, "decshape.weight"},
+        {params->decshape_bias, "decshape.bias"}, {params->deccam_weight, "deccam.weight"}, {params->deccam_bias, "deccam.bias"},
+        {xf, "xf"}, {tape, "tape"}, {second, second_name}, {C ? cam_feats : xf, "cam_feats"}};      // (cam_feats is read with C = 7 only)
+    for (const auto& r : required) {
+        if (!r.p) return fail(h, SPECMI_ERR_ARG, "%s: %s is NULL", who, r.name);
+        if (reinterpret_cast<uintptr_t>(r.p) & 3) return fail(h, SPECMI_ERR_ARG, "%s: %s is not 4-byte aligned", who, r.name);
+    }
+    if (ld_xf < F) return fail(h, SPECMI_ERR_ARG, "%s: ld_xf = %lld is below the row length F = %d", who, (long long)ld_xf, F);
+    a.p = HeadTrainParams{params->fc1_weight, params->fc1_bias, params->fc2_weight, params->fc2_bias, params->decpose_weight,
+                          params->decpose_bias, params->decshape_weight, params->decshape_bias, params->deccam_weight, params->deccam_bias};
+    a.xf = xf; a.ld_xf = (long)ld_xf; a.cam_feats = C ? cam_feats : nullptr; a.masks = masks;
+    a.scale = masks ? (float)(1.0 / (1.0 - (double)p)) : 1.f;
+    a.B = B; a.F = F; a.C = C; a.n_iter = n_iter;
+    return SPECMI_OK;
+}
+
+int specmi_hmr_head_train_forward(specmi_handle* h, const specmi_hmr_head_params* params, const float* xf, int64_t ld_xf,
+                                  const float* cam_feats, const float* init_state, const uint8_t* masks, float p, int B, int F, int C,
+                                  int n_iter, float* state, float* tape, void* stream) {
+    ENTER(h);
+    HeadTrainArgs a;
+    if (int rc = head_train_args(h, "hmr_head_train_forward", params, xf, ld_xf, cam_feats, masks, p, B, F, C, n_iter, tape, init_state,
+                                 "init_state", a))
+        return rc;
+    if (!state) return fail(h, SPECMI_ERR_ARG, "hmr_head_train_forward: every output is NULL (state is required)");
+    if (reinterpret_cast<uintptr_t>(state) & 3) return fail(h, SPECMI_ERR_ARG, "hmr_head_train_forward: state is not 4-byte aligned");
+    if (int rc = grow_ragged(h, h->buf[BUF_head_train], head_train_fwd_ws_floats(B) * 4, "the HMRHead training workspace")) return rc;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "head.train_forward"};
+    LAUNCHCHK(h, launch_head_train_forward(a, init_state, state, tape, (float*)h->buf[BUF_head_train].p, ctx), "hmr_head_train_forward");
+    return SPECMI_OK;
+}
+
+int specmi_hmr_head_backward(specmi_handle* h, const specmi_hmr_head_params* params, const float* xf, int64_t ld_xf,
+                             const float* cam_feats, const uint8_t* masks, float p, int B, int F, int C, int n_iter, const float* tape,
+                             const float* g_state, float* g_xf, const specmi_hmr_head_grads* grads, void* stream) {
+    ENTER(h);
+    HeadTrainArgs a;
+    if (int rc = head_train_args(h, "hmr_head_backward", params, xf, ld_xf, cam_feats, masks, p, B, F, C, n_iter, tape, g_state, "g_state", a))
+        return rc;
+    HeadTrainGrads g{};
+    if (grads)
+        g = HeadTrainGrads{grads->fc1_weight, grads->fc1_bias, grads->fc2_weight, grads->fc2_bias, grads->decpose_weight,
+                           grads->decpose_bias, grads->decshape_weight, grads->decshape_bias, grads->deccam_weight, grads->deccam_bias};
+    float* const outs[] = {g_xf, g.fc1_w, g.fc1_b, g.fc2_w, g.fc2_b, g.decpose_w, g.decpose_b, g.decshape_w, g.decshape_b, g.deccam_w, g.deccam_b};
+    bool any = false;
+    for (float* o : outs) {
+        any = any || o;
+        if (reinterpret_cast<uintptr_t>(o) & 3) return fail(h, SPECMI_ERR_ARG, "hmr_head_backward: an output is not 4-byte aligned");
+    }
+    if (!any) return fail(h, SPECMI_ERR_ARG, "hmr_head_backward: every output is NULL");
+    if (int rc = grow_ragged(h, h->buf[BUF_head_train], head_train_bwd_ws_floats(B, n_iter) * 4, "the HMRHead training workspace")) return rc;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "head.backward"};
+    LAUNCHCHK(h, launch_head_backward(a, tape, g_state, g_xf, g, (float*)h->buf[BUF_head_train].p, ctx), "hmr_head_backward");
+    return SPECMI_OK;
+}
+
 int specmi_rotate_points(specmi_handle* h, const float* R, const float* points, int B, int N, float* out, void* stream) {
     ENTER(h);
     if (!R || !points || !out || B <= 0 || N <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");

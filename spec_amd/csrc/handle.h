@@ -149,6 +149,7 @@ enum Buf {
     BUF_jdec,       // specmi_jpeg_decode: coefficients, planes and the lanes' states (jdec_ws_layout)
     BUF_pdec,       // specmi_png_decode: the inflated streams, the match records and the Adler sums (pdec_ws_layout)
     BUF_smpl_bwd,   // specmi_smpl_backward: smpl_bwd_ws_floats(V, B) floats
+    BUF_head_train, // specmi_hmr_head_train_forward / specmi_hmr_head_backward: head_train_fwd_ws_floats / head_train_bwd_ws_floats floats
     BUF_COUNT
 };
 

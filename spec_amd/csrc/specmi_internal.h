@@ -438,6 +438,26 @@ int launch_rot6d_forward(const float* x6d, float* rotmat, int n, const LaunchCtx
 // the backward of rot6d_joint: x6d (n,6), g_rotmat (n,3,3) -> g_x6d (n,6)
 int launch_rot6d_backward(const float* x6d, const float* g_rotmat, float* g_x6d, int n, const LaunchCtx& ctx);
 
+// pare's HMRHead regressor for training (head_bwd.hip): the ten parameters where torch keeps them ((N, K) row-major weights),
+// xf (B, F) rows ld_xf apart, cam_feats (B, 7) with C = 7 else unused, masks uint8 (2 n_iter, B, 1024) or null (eval: scale is
+// not read).  The tape is head_tape_floats(B, n_iter) floats; ws is head_train_fwd_ws_floats(B) resp.
+// head_train_bwd_ws_floats(B, n_iter) floats.  g_xf and the members of HeadTrainGrads may be null (not wanted).
+struct HeadTrainParams { const float *fc1_w, *fc1_b, *fc2_w, *fc2_b, *decpose_w, *decpose_b, *decshape_w, *decshape_b, *deccam_w, *deccam_b; };
+struct HeadTrainGrads { float *fc1_w, *fc1_b, *fc2_w, *fc2_b, *decpose_w, *decpose_b, *decshape_w, *decshape_b, *deccam_w, *deccam_b; };
+struct HeadTrainArgs {
+    HeadTrainParams p;
+    const float* xf; long ld_xf;
+    const float* cam_feats;
+    const uint8_t* masks; float scale;
+    int B, F, C, n_iter;
+};
+size_t head_tape_floats(int B, int n_iter);
+size_t head_train_fwd_ws_floats(int B);
+size_t head_train_bwd_ws_floats(int B, int n_iter);
+int launch_head_train_forward(const HeadTrainArgs& a, const float* init_state, float* state, float* tape, float* ws, const LaunchCtx& ctx);
+int launch_head_backward(const HeadTrainArgs& a, const float* tape, const float* g_state, float* g_xf, const HeadTrainGrads& g, float* ws,
+                         const LaunchCtx& ctx);
+
 // ----------------------------------------------------------------------------------------
 // evaluation metrics  (eval.hip)
 // ----------------------------------------------------------------------------------------

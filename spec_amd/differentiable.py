@@ -6,6 +6,12 @@ spec_amd/csrc/smpl_bwd.hip).  No trained parameters and no BatchNorm live here: 
 camera-aware test-time refinement needs - optimise pose / shape / camera of a detection against 2D keypoints under the
 CamCalib camera - and where a trunk backward would start, from the gradient of the head's state vector.
 
+Upstream of that state vector sits :class:`HMRHead`, pare's iterative regressor with its five trained Linears, as it runs in
+training: dropout on in ``.train()``, the loop and its backward on the library's exact-fp32 matrix-core kernels
+(``specmi_hmr_head_train_forward`` / ``specmi_hmr_head_backward``; spec_amd/csrc/head_bwd.hip), which read the Parameters where
+torch keeps them - an optimiser steps them as they are.  Its gradient with respect to the pooled feature is where a trunk
+backward would start.
+
 First derivatives only (``once_differentiable``).  The camera arguments (``cam_rotmat``, ``cam_intrinsics``, the box, the image
 size) get no gradient.  With no input requiring grad the heads return exactly what ``Engine.smpl`` returns.
 """
@@ -17,8 +23,10 @@ import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
+from . import _lib
 from .cam_utils import _engine
 from .engine import Engine
+from .modules import HMRHeadParams
 
 _tls = threading.local()
 _KEYS = ('smpl_vertices', 'smpl_joints3d', 'smpl_joints2d', 'pred_cam_t')
@@ -132,3 +140,100 @@ class SMPLHead(nn.Module):
             raise NotImplementedError('SMPLHead is built as the reference calls it (spec/models/hmr.py:119: normalize_joints2d=True)')
         eng = _smpl_engine(_device_of(rotmat), self.model, False, self.img_res, self.focal_length)
         return _run(eng, (None,) * 6, rotmat, shape, cam)
+
+
+class _Regressor(torch.autograd.Function):
+    """(xf, the ten parameters in the order of ``_lib.HMR_HEAD_PARAMS``) -> state_n (B, 157); ``fixed`` = (init_state, cam_feats,
+    masks, p, n_iter), which get no gradient."""
+
+    @staticmethod
+    def forward(ctx, eng, fixed, xf, *params):
+        init_state, cam_feats, masks, p, n_iter = fixed
+        ps = [t.detach() for t in params]
+        state, tape = eng.hmr_head_train_forward(dict(zip(_lib.HMR_HEAD_PARAMS, ps)), xf.detach(), init_state, cam_feats, masks, p, n_iter)
+        ctx.eng, ctx.fixed = eng, fixed
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xf.detach(), tape, *ps)     # (an optimiser step between forward and backward is caught by autograd's version check)
+        return state
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_state):
+        if g_state is None:
+            return (None,) * (3 + len(_lib.HMR_HEAD_PARAMS))
+        xf, tape, *ps = ctx.saved_tensors
+        _, cam_feats, masks, p, n_iter = ctx.fixed
+        names = [n for n, need in zip(_lib.HMR_HEAD_PARAMS, ctx.needs_input_grad[3:]) if need]
+        g_xf, grads = ctx.eng.hmr_head_backward(dict(zip(_lib.HMR_HEAD_PARAMS, ps)), xf, tape, g_state, cam_feats, masks, p, n_iter,
+                                                want_xf=ctx.needs_input_grad[2], want_params=names)
+        return (None, None, g_xf) + tuple(grads.get(n) for n in _lib.HMR_HEAD_PARAMS)
+
+
+class HMRHead(HMRHeadParams):
+    """pare's ``HMRHead`` as spec/models/hmr.py:57-64 builds it and :94-98 calls it, trainable: the Parameters and buffers of
+    ``modules.HMRHeadParams`` (pare's state_dict names and shapes), ``forward`` with pare's signature and output dict.  In
+    ``.train()`` the two ``nn.Dropout(p)`` are on: their keep-masks are ``torch.rand((2 n_iter, B, 1024), generator=self.generator)
+    >= p``, ordered (iteration, layer), unless ``dropout_masks`` passes them; in ``.eval()`` they are the identity (masks passed
+    are not read).  ``features``: (B, F, h, w), or (B, h, w, F) with ``channels_last=True`` (what ``Engine.trunk`` returns), or
+    (B, F) already pooled; it and the ten Parameters get gradients, ``init_*`` and the camera inputs do not.  When grad is
+    disabled or nothing requires grad no tape is kept."""
+
+    def __init__(self, num_input_features=2048, use_cam_feats=False, mean_params=None, p=0.5, estimate_var=False):
+        if estimate_var:
+            raise NotImplementedError('estimate_var: the variance outputs and their losses are not built for training (DESIGN.md section 6)')
+        if not 0.0 <= p < 1.0:
+            raise ValueError(f'p = {p} must be in [0, 1)')
+        super().__init__(num_input_features, use_cam_feats, mean_params)
+        self.num_input_features = int(num_input_features)
+        self.use_cam_feats = bool(use_cam_feats)
+        self.p = float(p)
+        self.generator = None       # a torch.Generator on the features' device; None = torch's default generator
+
+    @classmethod
+    def from_hmr(cls, hmr, p=0.5):
+        """A head that SHARES the Parameter objects and buffers of ``hmr.head`` (a ``spec_amd.modules.HMR``): an optimiser step on
+        this head's parameters is a step on the model's, and the model's next eval-mode call sees the bumped tensor versions and
+        commits them again by itself."""
+        if hmr.estimate_var:
+            raise NotImplementedError('estimate_var: the variance outputs and their losses are not built for training (DESIGN.md section 6)')
+        src = hmr.head
+        C = 7 if hmr.use_cam_feats else 0
+        mp = {'pose': src.init_pose.detach().cpu().numpy(), 'shape': src.init_shape.detach().cpu().numpy(), 'cam': src.init_cam.detach().cpu().numpy()}
+        head = cls(src.fc1.in_features - 157 - C, bool(hmr.use_cam_feats), mp, p)
+        for name in ('fc1', 'fc2', 'decpose', 'decshape', 'deccam'):
+            setattr(head, name, getattr(src, name))
+        for name in ('init_pose', 'init_shape', 'init_cam'):
+            head._buffers[name] = src._buffers[name]
+        return head
+
+    def forward(self, features, init_pose=None, init_shape=None, init_cam=None, cam_rotmat=None, cam_vfov=None, n_iter=3, *,
+                channels_last=False, dropout_masks=None):
+        dev = _device_of(features)
+        if features.dim() == 4:
+            xf = features.mean(dim=(1, 2) if channels_last else (2, 3))       # the average pool, inside autograd
+        elif features.dim() == 2:
+            xf = features
+        else:
+            raise ValueError(f'features must be (B, F, h, w), (B, h, w, F) with channels_last, or (B, F), got {tuple(features.shape)}')
+        B = xf.shape[0]
+        with torch.no_grad():
+            init = [t if t is not None else getattr(self, k).expand(B, -1) for t, k in
+                    ((init_pose, 'init_pose'), (init_shape, 'init_shape'), (init_cam, 'init_cam'))]
+            init_state = torch.cat([t.to(dev, torch.float32) for t in init], 1)
+            cam_feats = None
+            if self.use_cam_feats:
+                if cam_rotmat is None or cam_vfov is None:
+                    raise ValueError('a head built with use_cam_feats needs cam_rotmat and cam_vfov')
+                cam_feats = torch.cat([cam_rotmat.reshape(-1, 3, 3)[:, :, :2].reshape(B, 6), cam_vfov.reshape(B, 1)], 1).to(dev, torch.float32)
+            masks = None
+            if self.training:
+                masks = dropout_masks if dropout_masks is not None else \
+                    torch.rand(2 * n_iter, B, 1024, device=dev, generator=self.generator) >= self.p
+        params = tuple(getattr(getattr(self, n.split('.')[0]), n.split('.')[1]) for n in _lib.HMR_HEAD_PARAMS)
+        eng = _engine(dev)
+        if torch.is_grad_enabled() and (xf.requires_grad or any(t.requires_grad for t in params)):
+            state = _Regressor.apply(eng, (init_state, cam_feats, masks, self.p, n_iter), xf, *params)
+        else:
+            state, _ = eng.hmr_head_train_forward(dict(zip(_lib.HMR_HEAD_PARAMS, params)), xf, init_state, cam_feats, masks, self.p, n_iter)
+        pose6d, shape, cam = state[:, :144], state[:, 144:154], state[:, 154:]
+        return {'pred_pose': rot6d_to_rotmat(pose6d).view(B, 24, 3, 3), 'pred_cam': cam, 'pred_shape': shape, 'pred_pose_6d': pose6d}

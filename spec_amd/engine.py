@@ -673,6 +673,59 @@ def check_rot6d_backward(x_shape, g_shape):
     return n // 6
 
 
+# pare's HMRHead: the width of fc1 / fc2, the rows of its three decoders = the widths of the record's pred_pose_6d | pred_shape | pred_cam,
+# and the state vector they update
+HMR_HEAD_HIDDEN = 1024
+HMR_HEAD_DECODERS = {n: dict(PACKED_KEYS)[k][0] for n, k in (('decpose', 'pred_pose_6d'), ('decshape', 'pred_shape'), ('deccam', 'pred_cam'))}
+HMR_HEAD_STATE = sum(HMR_HEAD_DECODERS.values())
+
+
+def hmr_head_param_shapes(F, C):
+    """name -> shape of the ten parameters of pare's HMRHead (``_lib.HMR_HEAD_PARAMS``) for F pooled features and C in (0, 7)."""
+    H, rows = HMR_HEAD_HIDDEN, dict(HMR_HEAD_DECODERS, fc1=HMR_HEAD_HIDDEN, fc2=HMR_HEAD_HIDDEN)
+    return {n: ((rows[n.split('.')[0]], F + HMR_HEAD_STATE + C if n == 'fc1.weight' else H) if n.endswith('weight') else
+                (rows[n.split('.')[0]],)) for n in _lib.HMR_HEAD_PARAMS}
+
+
+def hmr_head_tape_floats(B, n_iter):
+    """What ``specmi_hmr_head_tape_floats`` answers, on the host."""
+    return n_iter * B * (HMR_HEAD_STATE + 2 * HMR_HEAD_HIDDEN)
+
+
+def check_hmr_head_train(B, F, C, n_iter, p=0.5, masks=False, param_shapes=None, cam_feats=None, ld_xf=None, outputs=None,
+                         addresses=()):
+    """Every refusal of ``specmi_hmr_head_train_forward`` / ``specmi_hmr_head_backward`` (include/specmi.h) as ``ValueError``,
+    and the parameters' shapes, which the library cannot see.  ``masks``: are masks given; ``param_shapes``: name -> shape of the
+    ten parameters (a missing or None entry is a NULL pointer), None = not checked; ``cam_feats``: is it given (None = as C
+    says); ``ld_xf``: the row stride of xf (None = F); ``outputs``: which of g_xf and the ten parameter gradients are wanted
+    (None = the forward, whose one output is required); ``addresses``: of the float tensors.  -> Kin.  Needs no device."""
+    if not 1 <= B <= 1 << 20:
+        raise ValueError(f'B = {B} must be in [1, 2^20]')
+    if not 1 <= F <= 1 << 20:
+        raise ValueError(f'F = {F} must be in [1, 2^20]')
+    if C not in (0, 7):
+        raise ValueError(f'C = {C} must be 0 or 7 (use_cam_feats)')
+    if not 1 <= n_iter <= 3:
+        raise ValueError(f'n_iter = {n_iter} must be in 1 .. 3')
+    if masks and not 0.0 <= p < 1.0:
+        raise ValueError(f'p = {p} must be in [0, 1) when masks are given')
+    if param_shapes is not None:
+        for name, shape in hmr_head_param_shapes(F, C).items():
+            if param_shapes.get(name) is None:
+                raise ValueError(f'{name} is missing')
+            if tuple(param_shapes[name]) != shape:
+                raise ValueError(f'{name} must be {shape} for F = {F}, C = {C}, got {tuple(param_shapes[name])}')
+    if C == 7 and cam_feats is not None and not cam_feats:
+        raise ValueError('cam_feats is required with C = 7')
+    if any(a % 4 for a in addresses):
+        raise ValueError('a float tensor is not 4-byte aligned')
+    if ld_xf is not None and ld_xf < F:
+        raise ValueError(f'the row stride of xf, {ld_xf}, is below the row length F = {F}')
+    if outputs is not None and not any(outputs):
+        raise ValueError('no output is wanted (g_xf or one parameter gradient at least)')
+    return F + HMR_HEAD_STATE + C
+
+
 def out_dtype(dtype):
     """The ``dtype=`` keyword of the producers: torch.float32 -> the (n,3,H,W) fp32 image, torch.float16 -> NHWC8 fp16."""
     if dtype not in (torch.float32, torch.float16):
@@ -1633,6 +1686,82 @@ class Engine:
         out = torch.empty_like(x)
         _lib.check(self.h, self.lib.specmi_rot6d_backward(self.h, _ptr(x), _ptr(g), n, _ptr(out), self._stream()))
         return out
+
+    def _hmr_head_args(self, params, xf, cam_feats, masks, p, n_iter, outputs, others):
+        """The arguments the two HMRHead training calls share, checked: -> (params struct, xf, ld_xf, cam_feats, masks, B, F, C).
+        ``params``: the ten tensors under their state_dict names, read where they lie - fp32, contiguous, on this device."""
+        ps = {n: params[n].detach() if params.get(n) is not None else None for n in _lib.HMR_HEAD_PARAMS}
+        for n, t in ps.items():
+            if t is not None and (t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError(f'{n} must be a contiguous fp32 tensor on {self.device} (the library reads it in place)')
+        x = xf.detach() if isinstance(xf, torch.Tensor) else xf
+        if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.device == self.device and x.dtype == torch.float32 and
+                (x.stride(1) == 1 or x.shape[1] == 1)):
+            x = _dev_f32(x, self.device)
+        if x.dim() != 2:
+            raise ValueError(f'xf must be (B, F), got {tuple(x.shape)}')
+        B, F = x.shape
+        ld = x.stride(0) if B > 1 else F
+        cf = _dev_f32(cam_feats, self.device, (B, 7))
+        C_ = 7 if cf is not None else 0
+        if masks is not None:
+            if masks.dtype == torch.bool:
+                masks = masks.view(torch.uint8)
+            if masks.dtype != torch.uint8 or tuple(masks.shape) != (2 * n_iter, B, HMR_HEAD_HIDDEN) or masks.device != self.device:
+                raise ValueError(f'masks must be uint8 or bool ({2 * n_iter}, {B}, {HMR_HEAD_HIDDEN}) on {self.device}')
+            masks = masks.contiguous()
+        fc1 = ps['fc1.weight']
+        if fc1 is not None and fc1.dim() == 2 and fc1.shape[1] == F + HMR_HEAD_STATE + 7 and cf is None:
+            raise ValueError('cam_feats is required with C = 7')
+        check_hmr_head_train(B, F, C_, n_iter, p, masks is not None, {n: None if t is None else t.shape for n, t in ps.items()},
+                             ld_xf=ld, outputs=outputs,
+                             addresses=[t.data_ptr() for t in (*ps.values(), x, cf, *others) if t is not None])
+        st = _lib.HmrHeadParams(*(t.data_ptr() for t in ps.values()))
+        return st, x, ld, cf, masks, B, F, C_
+
+    def hmr_head_train_forward(self, params, xf, init_state, cam_feats=None, masks=None, p=0.5, n_iter=3, tape=None):
+        """``specmi_hmr_head_train_forward``: pare's HMRHead loop on ``params`` (the ten tensors under their state_dict names, read
+        in place), xf (B, F) pooled features, init_state (B, 157), cam_feats (B, 7) when the head was built with use_cam_feats,
+        masks uint8 / bool (2 n_iter, B, 1024) or None = eval mode.  -> (state_n (B, 157), the tape ``hmr_head_backward`` needs;
+        ``tape=`` takes a caller's flat fp32 buffer of at least ``hmr_head_tape_floats(B, n_iter)`` floats)."""
+        init = _dev_f32(init_state, self.device)
+        st, x, ld, cf, masks, B, F, C_ = self._hmr_head_args(params, xf, cam_feats, masks, p, n_iter, None, (init,))
+        if tuple(init.shape) != (B, HMR_HEAD_STATE):
+            raise ValueError(f'init_state must be ({B}, {HMR_HEAD_STATE}), got {tuple(init.shape)}')
+        need = hmr_head_tape_floats(B, n_iter)
+        if tape is None:
+            tape = self._empty(need)
+        elif tape.device != self.device or tape.dtype != torch.float32 or not tape.is_contiguous() or tape.numel() < need:
+            raise ValueError(f'tape must be a contiguous fp32 tensor of at least {need} floats on {self.device}')
+        state = self._empty(B, HMR_HEAD_STATE)
+        _lib.check(self.h, self.lib.specmi_hmr_head_train_forward(
+            self.h, C.byref(st), _ptr(x), ld, _ptr(cf), _ptr(init), _ptr(masks), float(p), B, F, C_, int(n_iter), _ptr(state),
+            _ptr(tape), self._stream()))
+        return state, tape
+
+    def hmr_head_backward(self, params, xf, tape, g_state, cam_feats=None, masks=None, p=0.5, n_iter=3, want_xf=True,
+                          want_params=True):
+        """``specmi_hmr_head_backward``: the forward's arguments and its tape, g_state (B, 157) -> (g_xf (B, F) or None, {name:
+        gradient} of the wanted parameters).  ``want_params``: True (all ten), False, or the names wanted."""
+        g = _dev_f32(g_state, self.device)
+        names = _lib.HMR_HEAD_PARAMS if want_params is True else tuple(want_params or ())
+        if set(names) - set(_lib.HMR_HEAD_PARAMS):
+            raise ValueError(f'want_params names {sorted(set(names) - set(_lib.HMR_HEAD_PARAMS))}: not parameters of the head')
+        outputs = [bool(want_xf)] + [n in names for n in _lib.HMR_HEAD_PARAMS]
+        st, x, ld, cf, masks, B, F, C_ = self._hmr_head_args(params, xf, cam_feats, masks, p, n_iter, outputs, (g, tape))
+        if tuple(g.shape) != (B, HMR_HEAD_STATE):
+            raise ValueError(f'g_state must be ({B}, {HMR_HEAD_STATE}), got {tuple(g.shape)}')
+        need = hmr_head_tape_floats(B, n_iter)
+        if tape.device != self.device or tape.dtype != torch.float32 or not tape.is_contiguous() or tape.numel() < need:
+            raise ValueError(f'tape must be the contiguous fp32 tensor of at least {need} floats the forward wrote')
+        g_xf = self._empty(B, F) if want_xf else None
+        shapes = hmr_head_param_shapes(F, C_)
+        grads = {n: self._empty(*shapes[n]) for n in _lib.HMR_HEAD_PARAMS if n in names}
+        gs = _lib.HmrHeadParams(*(grads[n].data_ptr() if n in grads else None for n in _lib.HMR_HEAD_PARAMS))
+        _lib.check(self.h, self.lib.specmi_hmr_head_backward(
+            self.h, C.byref(st), _ptr(x), ld, _ptr(cf), _ptr(masks), float(p), B, F, C_, int(n_iter), _ptr(tape), _ptr(g), _ptr(g_xf),
+            C.byref(gs) if grads else None, self._stream()))
+        return g_xf, grads
 
     def smpl_native(self, pose, betas, vertices=True, joints24=True):
         """smplx-style body model call: ``pose`` (B,24,3,3) rotation matrices or (B,72) axis-angle; returns
