@@ -2,8 +2,8 @@
 
 The integer parts - snapping, edge functions, the top-left rule, culling, the 64-bit depth key - are exact.  The fp32 parts are
 written with ``np.float32`` operands in the kernel's order of operations (the kernel is compiled without contraction and HIP's
-fp32 division is correctly rounded), and ``vertex_stage`` also runs in float64, which is what the GPU test measures its bounds
-against.  Test meshes (octahedron, icosphere) live here as well."""
+fp32 division and square root are correctly rounded), and ``vertex_stage`` and ``resolve`` also run in float64, which is what the
+GPU tests measure their bounds against.  Test meshes (octahedron, icosphere) and the shading scene live here as well."""
 import numpy as np
 
 ZNEAR, ZFAR, LIMIT, DROPPED = 0.05, 100.0, 2.0 ** 20, -2 ** 31
@@ -114,17 +114,88 @@ def rasterize(sx, sy, z, faces, H, W, cull=True):
 
 # ---- normals and shading --------------------------------------------------------------------------------------------------
 def normal_sums(vertices, faces):
-    """(M,V,3) fp32, (F,3) -> (M,V,3) int64 sums of the quantised face normals (what the kernel holds in int32)."""
+    """(M,V,3) fp32, (F,3) -> (M,V,3) int64 holding the kernel's int32 sums of the quantised face normals.  Every face whose
+    three indices lie in [0, V) contributes, drawn or not; any other face contributes nothing.  The quantisation is the kernel's
+    ``(int)fminf(fmaxf(rintf(n * 2^28), -2^30), 2^30)``: fmaxf returns its other operand for a NaN, so a NaN component becomes
+    -2^30 (+-Inf clamp to +-2^30).  The sums wrap as int32."""
     f = np.float32
     v, faces = np.asarray(vertices, f), np.asarray(faces, np.int64)
+    faces = faces[((faces >= 0) & (faces < v.shape[1])).all(axis=1)]
     out = np.zeros(v.shape, np.int64)
     for m in range(v.shape[0]):
-        a, b = v[m][faces[:, 1]] - v[m][faces[:, 0]], v[m][faces[:, 2]] - v[m][faces[:, 0]]
-        n = np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], 1)
-        q = np.clip(np.rint(n * f(NORMAL_SCALE)), -NORMAL_CLAMP, NORMAL_CLAMP).astype(np.int64)
+        with np.errstate(all='ignore'):
+            a, b = v[m][faces[:, 1]] - v[m][faces[:, 0]], v[m][faces[:, 2]] - v[m][faces[:, 0]]
+            n = np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2], a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], 1)
+            s = np.rint(n * f(NORMAL_SCALE))
+        q = np.where(np.isnan(s), -NORMAL_CLAMP, np.clip(np.where(np.isnan(s), 0, s), -NORMAL_CLAMP, NORMAL_CLAMP)).astype(np.int64)
         for k in range(3):
             np.add.at(out[m], faces[:, k], q)
-    return out
+    return (out + 2 ** 31) % 2 ** 32 - 2 ** 31
+
+
+RESOLVE_VARIANTS = (None, 'weights_rotated', 'no_perspective', 'axes_exchanged')
+
+
+def resolve(sx, sy, z, vertices, faces, id_map, rgb, side=False, dtype=np.float32, variant=None):
+    """The resolve stage at the covered pixels of ``id_map`` (H, W; id = m F + f, negative: not a mesh pixel), from the snapped
+    (M,V) coordinates and fp32 depths the raster stage saw -> (value (H,W,3) in ``dtype`` = 255 rgb shade before rounding, NaN
+    where uncovered; byte (H,W,3) uint8, 0 where uncovered).  The kernel's order of operations:
+      w_k = (float)E_k / (float)A,  zz = 1 / ((w0 / z0 + w1 / z1) + w2 / z2),
+      len_k = sqrt((x x + y y) + u u) of vertex k's int32 normal sum q_k = (x, y, u) converted to float,
+      b_k = ((w_k / z_k) zz) / len_k  (0 where len_k == 0),  n = ((0 + b_0 q_0) + b_1 q_1) + b_2 q_2,
+      n.l = (side ? n.x : -n.z) / sqrt((n.x n.x + n.y n.y) + n.z n.z)  (0 for a zero n),
+      value = (255 rgb) min(1, 0.3 + 0.7 max(0, n.l)),  byte = rint(value).
+    ``dtype`` np.float32 restates the kernel bit for bit; np.float64 is the same chain from the same inputs (the fp32 depths and
+    rgb, the integer edge functions and normal sums) with every constant, conversion and operation in float64.
+    ``variant`` reruns the chain with one deliberate mistake (the host tests show that the scenes tell them apart):
+    'weights_rotated' pairs w_{k+1} with vertex k, 'no_perspective' takes b_k = w_k / len_k, 'axes_exchanged' reads n.x in the
+    overlay and -n.z in side view."""
+    assert variant in RESOLVE_VARIANTS
+    f = dtype
+    sx, sy, faces = np.asarray(sx, np.int64), np.asarray(sy, np.int64), np.asarray(faces, np.int64)
+    z, id_map = np.asarray(z, np.float32), np.asarray(id_map, np.int64)
+    F = faces.shape[0]
+    sums = normal_sums(vertices, faces)
+    ii, jj = np.nonzero(id_map >= 0)
+    m, idx = id_map[ii, jj] // F, faces[id_map[ii, jj] % F]                     # (n), (n, 3)
+    x, y, zv = sx[m[:, None], idx], sy[m[:, None], idx], z[m[:, None], idx].astype(f)
+    q = sums[m[:, None], idx].astype(f)                                          # (n, 3 vertices, 3 components)
+    X, Y = 256 * jj + 128, 256 * ii + 128
+    A = _orient(x[:, 0], y[:, 0], x[:, 1], y[:, 1], x[:, 2], y[:, 2])
+    sgn = np.where(A < 0, -1, 1)
+    E = [sgn * _orient(x[:, (k + 1) % 3], y[:, (k + 1) % 3], x[:, (k + 2) % 3], y[:, (k + 2) % 3], X, Y) for k in range(3)]
+    w = [E[k].astype(f) / (A * sgn).astype(f) for k in range(3)]
+    zz = f(1) / ((w[0] / zv[:, 0] + w[1] / zv[:, 1]) + w[2] / zv[:, 2])
+    n = [np.zeros(ii.shape, f) for _ in range(3)]
+    with np.errstate(all='ignore'):
+        for k in range(3):
+            wk = w[(k + 1) % 3] if variant == 'weights_rotated' else w[k]
+            length = np.sqrt((q[:, k, 0] * q[:, k, 0] + q[:, k, 1] * q[:, k, 1]) + q[:, k, 2] * q[:, k, 2])
+            b = wk / length if variant == 'no_perspective' else ((wk / zv[:, k]) * zz) / length
+            b = np.where(length > 0, b, f(0))
+            for c in range(3):
+                n[c] = n[c] + b * q[:, k, c]
+        length = np.sqrt((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2])
+        along = n[0] if bool(side) != (variant == 'axes_exchanged') else -n[2]
+        ndl = np.where(length > 0, along / length, f(0))
+    shade_ = np.minimum(f(1), f(0.3) + f(0.7) * np.maximum(f(0), ndl))
+    value = np.full(id_map.shape + (3,), np.nan, f)
+    value[ii, jj] = (f(255) * np.asarray(rgb, np.float32).astype(f))[None, :] * shade_[:, None]
+    byte = np.zeros(id_map.shape + (3,), np.uint8)
+    byte[ii, jj] = np.rint(value[ii, jj]).astype(np.uint8)
+    return value, byte
+
+
+def half_integer_margin(v32, v64):
+    """The fp32 and float64 ``resolve`` values of one picture -> (gap = max |fp32 - float64| in bytes, delta = 4 gap - the
+    factor for the GPU's own rounding of the same operations, as Z_BOUND in tests/test_gpu_render.py -, the (H,W,3) mask of
+    covered pixel-channels whose float64 value lies within delta of a half-integer, the covered mask): where the first mask is
+    False the rounded byte cannot depend on fp32 rounding."""
+    covered = ~np.isnan(v64)
+    gap = float(np.abs(v32.astype(np.float64) - v64)[covered].max())
+    with np.errstate(invalid='ignore'):
+        near = covered & (np.abs(v64 - np.floor(v64) - 0.5) <= 4.0 * gap)
+    return gap, 4.0 * gap, near, covered
 
 
 def shade(ndl):
@@ -156,6 +227,23 @@ def checker(i, j, R, cam_t0, fx, fy, cx, cy, y_plane):
 
 
 # ---- test meshes ----------------------------------------------------------------------------------------------------------
+def rot(pitch, roll):
+    """Rx(pitch) Rz(roll), fp32"""
+    cp, sp, cr, sr = np.cos(pitch), np.sin(pitch), np.cos(roll), np.sin(roll)
+    return (np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]]) @ np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]])).astype(np.float32)
+
+
+def shading_scene(meshes=1):
+    """The scene the smooth shading is pinned on: a spun icosahedron (12 vertices, 20 faces) that fills about 260 pixels of a
+    33 x 47 frame with 7 faces, so the interpolated normal varies strongly inside every face.  ``meshes`` = 2 adds a second,
+    differently spun and smaller one beside and partly in front of it (the per-mesh offset of the normal sums)."""
+    v, f = icosphere(0, 1.0)
+    spin = [rot(0.4, 0.7).astype(np.float64), 0.6 * rot(-0.9, 0.3).astype(np.float64)][:meshes]
+    t = [[0.1, -0.05, 3.0], [-0.55, 0.3, 2.2]][:meshes]
+    return dict(v=np.ascontiguousarray(np.stack([v.astype(np.float64) @ s.T for s in spin]), np.float32), f=f, t=np.asarray(t, np.float32),
+                R=rot(0.1, -0.05), cam=(30., 30., 23.5, 16.5), size=(33, 47), rgb=(0.8, 0.5, 0.6))
+
+
 def octahedron(radius=1.0):
     """6 vertices, 8 outward-wound faces"""
     v = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], np.float64) * radius

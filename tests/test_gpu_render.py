@@ -18,9 +18,7 @@ torch.set_grad_enabled(False)
 DEV = 'cuda:0'
 
 
-def _rot(pitch, roll):
-    cp, sp, cr, sr = np.cos(pitch), np.sin(pitch), np.cos(roll), np.sin(roll)
-    return (np.array([[1, 0, 0], [0, cp, -sp], [0, sp, cp]]) @ np.array([[cr, -sr, 0], [sr, cr, 0], [0, 0, 1]])).astype(np.float32)
+_rot = RR.rot          # shared with tests/test_render_host.py and tests/test_gpu_render_edges.py
 
 
 def _scenes():

@@ -1,6 +1,7 @@
 """Host side of the demo's pictures (spec_amd/render.py, specmi_render_meshes): the C ABI surface, the refusals made before any
-launch, the top-left rule of the CPU restatement (tests/render_ref.py), panel 0 against the reference's own show_horizon_line
-and the .obj writer.  No GPU."""
+launch, the top-left rule of the CPU restatement (tests/render_ref.py), what its normal sums and its resolve stage state and the
+conditions tests/test_gpu_render_edges.py relies on for its shading bounds, panel 0 against the reference's own
+show_horizon_line and the .obj writer.  No GPU."""
 import ctypes as C
 import os
 import re
@@ -116,6 +117,63 @@ def test_quad_split_either_way_covers_the_same_pixels():
     assert np.array_equal(n1, n2) and n1.max() == 1
     assert n1[1, 1] == 1 and n1[1, 8] == 0 and n1[6, 1] == 0          # the top-left corner pixel is in, right and bottom edges out
     assert n1.sum() == 7 * 5
+
+
+def test_normal_sums_nan_wrap_and_foreign_indices():
+    """What ``normal_sums`` states beyond the plain sum: a non-finite face normal, the int32 wrap, faces that name no vertex."""
+    v = np.array([[[0, 0, 0], [1, 0, 0], [0, 1, 0], [0, 0, 1]]], np.float32)
+    f = np.array([[0, 1, 2]], np.int32)
+    one = RR.normal_sums(v, f)
+    assert np.array_equal(one[0, :3], [[0, 0, 2 ** 28]] * 3) and not one[0, 3].any()
+    # faces naming -1, V or INT32_MIN contribute nothing, to no vertex
+    assert np.array_equal(RR.normal_sums(v, np.array([[0, 1, 2], [0, 1, -1], [4, 1, 2], [0, -2 ** 31, 2]], np.int64)), one)
+    # a NaN anywhere in a face makes each NaN component -2^30 at ALL three of its vertices; +-Inf clamps to +-2^30
+    w = v.copy()
+    w[0, 2] = np.nan
+    assert np.array_equal(RR.normal_sums(w, f)[0, :3], [[-2 ** 30] * 3] * 3)
+    w[0, 2] = [0, np.inf, 0]
+    assert np.array_equal(RR.normal_sums(w, f)[0, 0], [-2 ** 30, 0, 2 ** 30])          # (0 0 - 0 inf, 0 0 - 1 0, 1 inf - 0 0) = (NaN, 0, inf)
+    # the sums wrap as int32: three faces of 2 * 4 m^2 each clamp to 2^30 per face and add up to 3 * 2^30 = -2^30 (mod 2^32)
+    big = np.array([[[0, 0, 0], [2, 0, 0], [0, 2, 0]]], np.float32)
+    assert np.array_equal(RR.normal_sums(big, np.array([[0, 1, 2]] * 3, np.int32))[0, 0], [0, 0, -2 ** 30])
+
+
+def _host_pictures(meshes, side):
+    """The shading scene through the restatement alone: ids from ``rasterize``, then ``resolve`` in fp32 and in float64."""
+    d = RR.shading_scene(meshes)
+    xs, ys, z, keep = RR.vertex_stage(d['v'], d['t'], d['R'], *d['cam'], side=side)
+    assert keep.all()
+    sx, sy = RR.snap(xs, ys, keep)
+    ids = RR.rasterize(sx, sy, z, d['f'], *d['size'])[0]
+    run = lambda dtype, variant=None: RR.resolve(sx, sy, z, d['v'], d['f'], ids, d['rgb'], side, dtype, variant)
+    return d, ids, run
+
+
+@pytest.mark.parametrize('meshes', [1, 2])
+@pytest.mark.parametrize('side', [False, True])
+def test_shading_scene_margin_cap_and_discrimination(meshes, side):
+    """The conditions tests/test_gpu_render_edges.py relies on, for the restatement alone.  (a) The scene: about 260 pixels,
+    at least 7 faces, dozens of distinct bytes per channel (with M = 2 both meshes show).  (b) delta = 4 x max |fp32 - float64|
+    of ``resolve``, computed here from the inputs: at most 1 % of the covered pixel-channels lie within delta of a half-integer,
+    so the byte is decided by the float64 value at 99 % of them at least.  (c) Each deliberate mistake of ``resolve`` moves
+    EVERY channel's byte by 2 or more at more than a quarter of the covered pixels - a +-1 byte test could not hide it."""
+    d, ids, run = _host_pictures(meshes, side)
+    cov = ids >= 0
+    (v32, b32), (v64, b64) = run(np.float32), run(np.float64)
+    assert 200 < cov.sum() < 1000 and len(np.unique(ids[cov])) >= 7 and min(len(np.unique(b64[cov][:, c])) for c in range(3)) >= 50
+    assert meshes == 1 or all(((ids[cov] // 20) == m).sum() > 50 for m in range(2))
+    gap, delta, near, covered = RR.half_integer_margin(v32, v64)
+    assert np.array_equal(covered, np.repeat(cov[..., None], 3, 2))
+    share = near.sum() / covered.sum()
+    print(f'M={meshes} side={side}: {cov.sum()} px, {len(np.unique(ids[cov]))} faces, |fp32 - float64| {gap:.3e} byte, delta {delta:.3e}, '
+          f'near a half-integer {near.sum()} of {covered.sum()} ({share:.4f}), fp32 bytes != float64 bytes {(b32 != b64).sum()}')
+    assert 0 < gap < 1e-3                   # fp32 rounding of a chain of some 60 operations on values up to 255; 0 would mean one chain ran twice
+    assert share <= 0.01
+    assert np.array_equal(b32[~near], b64[~near]) and (np.abs(b32.astype(np.int64) - b64) <= 1).all()
+    for variant in RR.RESOLVE_VARIANTS[1:]:
+        moved = (np.abs(run(np.float32, variant)[1].astype(np.int64) - b32)[cov].min(axis=1) >= 2).mean()
+        print(f'   {variant}: every channel off by 2 or more at {moved:.3f} of the covered pixels')
+        assert moved > 0.25, variant
 
 
 def test_panel0_equals_the_reference_show_horizon_line():
