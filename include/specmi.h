@@ -150,7 +150,8 @@ const char* specmi_version(void);
  *     group / the whole K per workgroup), "conv2d_sk" (specmi_conv2d only: 0 = throughput kernel, -1 = the latency plan's rule,
  *     n > 1 = n leaves), "conv2d_wsplit" (specmi_conv2d only: 0 | 2 | 3), "smpl_skin_split" (-1 = by batch, 0 / 1 = never / always),
  *     "trunk_subbatch" (0) / "trunk_subbatch_layers" (2), "fc_splitk" (1), "fc_gemv" (1), "head_fuse" (3; bit 0: the regressor's state
- *     init rides in the pooling launch, bit 1: head_final's work is done by the SMPL pose kernel);
+ *     init rides in the pooling launch, bit 1: head_final's work is done by the SMPL pose kernel), "camcalib_head_group" (1; 0 = the
+ *     CamCalib training heads' independent products as three single launches instead of one grouped launch: same bits);
  *   plan thresholds: "single_max_batch" (2), "latency_max_batch" (10), "latency_max_batch_single" (16), "latency_target_wgs" (256),
  *     "latency_min_chunks" (4), "latency_wino_min_tiles" (128), "latency_fill_wgs" (240) / "latency_fill_wgs_large" (400),
  *     "latency_unit_model" (0; 1 = pick the unit by a round model with "latency_unit_slots" 256: measured equal or worse);
@@ -434,6 +435,68 @@ int specmi_hmr_head_backward(specmi_handle* h, const specmi_hmr_head_params* par
                              const float* cam_feats, const uint8_t* masks, float p, int B, int F, int C, int n_iter,
                              const float* tape, const float* g_state, float* g_xf, const specmi_hmr_head_grads* grads,
                              void* stream);
+
+/* CameraRegressorLoss for training (camcalib/loss.py:24-125; STABLE): the loss part of specmi_camcalib_eval without decode and
+ * angle errors - it needs no ground-truth angles - and its gradient with respect to the three logit tensors.
+ * specmi_camcalib_loss: three (B, nbins) logit tensors, loss_type, the three target tensors ((B,) int32 bin index for SPECMI_LOSS_CE /
+ *   _KL, (B,) fp32 soft index for the soft-argmax losses) and weights as specmi_camcalib_eval takes them -> loss_term (3, B)
+ *   (unweighted, heads vfov, pitch, roll) and means (4) = [loss, vfov_loss, pitch_loss, roll_loss].  Both carry the bits
+ *   specmi_camcalib_eval writes on the same inputs: the per-row arithmetic is one device function both kernels call.
+ * specmi_camcalib_loss_backward: the same inputs and g_means (4, device), the upstream gradients of loss, vfov_loss, pitch_loss and
+ *   roll_loss -> g_vfov, g_pitch, g_roll, each (B, nbins) dense.  With p = softmax(x), E = sum_i i p_i, s = 2 E / (nbins - 1) - 1
+ *   and c_k = w_k (g_means[0] + g_means[1 + k]) / B:  ce / kl: c_k (p_i - [i == t]);  softargmax_l2: c_k (-2 (t - s))
+ *   (2 / (nbins - 1)) p_i (i - E);  softargmax_biased_l2: the vfov head divides -2 (t - s) by ((t - s)^2 + 1)^2 wherever s > t is
+ *   false, pitch and roll use the plain form.  i - E is formed relative to the arg-max bin, so that a nearly one-hot row keeps its
+ *   leading digits.  One launch, one wave per row; a row never depends on another row; no atomics: two runs give the same bits.
+ *   The targets are constants (no gradient); first derivatives only.
+ * Refusals (SPECMI_ERR_ARG with a message, nothing launched, no output written): a NULL pointer; B < 1 or B > 2^20; nbins < 2 or
+ * nbins > 2^16; an unknown loss_type. */
+int specmi_camcalib_loss(specmi_handle* h, const float* logits_vfov, const float* logits_pitch, const float* logits_roll, int B,
+                         int nbins, int loss_type, const void* target_vfov, const void* target_pitch, const void* target_roll,
+                         float weight_vfov, float weight_pitch, float weight_roll, float* loss_term, float* means, void* stream);
+int specmi_camcalib_loss_backward(specmi_handle* h, const float* logits_vfov, const float* logits_pitch, const float* logits_roll,
+                                  int B, int nbins, int loss_type, const void* target_vfov, const void* target_pitch,
+                                  const void* target_roll, float weight_vfov, float weight_pitch, float weight_roll,
+                                  const float* g_means, float* g_vfov, float* g_pitch, float* g_roll, void* stream);
+
+/* CamCalib's three FC heads for training (camcalib/model.py:59-70; STABLE): fc_vfov / fc_pitch / fc_roll on the pooled feature
+ * xf (B, F), each one Linear or a chain of L = 2 or 3 Linears with NO activation between them, widths F -> Hc -> .. -> nbins
+ * (Hc = num_fc_channels; not read with L = 1, pass 1).  params->weight[k][l] / bias[k][l] (head k = vfov, pitch, roll; layer
+ * l < L; the rest is not read) are DEVICE pointers to torch's own row-major (out, in) / (out) tensors, read in place at every
+ * call - nothing is packed, uploaded or committed, and nothing of the handle's committed model is read.
+ * specmi_camcalib_head_tape_floats: 3 (L - 1) B Hc, the intermediate activations as (3, L - 1, B, Hc); 0 for L = 1.  A pure
+ *   function: no handle, no GPU call.  Refuses (returns SPECMI_ERR_ARG) the shapes the two calls refuse and floats NULL.
+ * specmi_camcalib_head_train_forward: xf rows ld_xf floats apart -> logits (3, B, nbins) dense and the tape, the caller's buffer
+ *   (may be NULL with L = 1) and the only state between the two calls.
+ * specmi_camcalib_head_backward: the forward's arguments, its tape and g_logits (3, B, nbins) dense -> g_xf (B, F) dense and the
+ *   parameter gradients in the parameters' shapes.  g_xf, grads and every member of grads may be NULL (not wanted), but not all
+ *   of them; a wanted output has the same bits whatever else is wanted; with only g_xf wanted no weight-gradient product runs.
+ *   Per head G_L = g_logits, G_{l-1} = G_l W_l, dW_l = G_l^T A_{l-1}, db_l = the column sums of G_l (eight interleaved row
+ *   slices in row order, then the slices in order); g_xf = the sum over the heads of G_1 W_1, added in the order vfov, pitch, roll.
+ * Every product runs on the exact-fp32 matrix instruction with tails in every dimension handled in the kernel; each step whose
+ * three heads are independent - a forward layer, a data gradient above layer 1, a weight gradient - is ONE grouped launch, and a
+ * head's numbers do not depend on the grouping.  Deterministic: no float atomics; row b of the logits and of g_xf has the same
+ * bits in any batch; the parameter gradients depend on B alone; head k's outputs have the same bits whatever the other two
+ * heads' parameters hold.
+ * Workspace: 3 (L - 1) B Hc floats for the backward, in the handle; it grows on the first call of a shape, afterwards nothing is
+ * allocated and the calls can be captured into a graph.
+ * Refusals (SPECMI_ERR_ARG with a message, nothing launched, no output written): L outside 1 .. 3; B, F, Hc or nbins < 1 or
+ * > 2^20; params, a weight or bias of a layer below L, xf, logits resp. g_logits NULL; tape NULL with L > 1; a float pointer that
+ * is not 4-byte aligned; ld_xf < F; every output NULL. */
+typedef struct specmi_camcalib_head_params {
+    const float* weight[3][3];
+    const float* bias[3][3];
+} specmi_camcalib_head_params;
+typedef struct specmi_camcalib_head_grads {
+    float* weight[3][3];
+    float* bias[3][3];
+} specmi_camcalib_head_grads;
+int specmi_camcalib_head_tape_floats(int B, int F, int L, int Hc, int nbins, int64_t* floats);
+int specmi_camcalib_head_train_forward(specmi_handle* h, const specmi_camcalib_head_params* params, const float* xf, int64_t ld_xf,
+                                       int B, int F, int L, int Hc, int nbins, float* tape, float* logits, void* stream);
+int specmi_camcalib_head_backward(specmi_handle* h, const specmi_camcalib_head_params* params, const float* xf, int64_t ld_xf,
+                                  int B, int F, int L, int Hc, int nbins, const float* tape, const float* g_logits, float* g_xf,
+                                  const specmi_camcalib_head_grads* grads, void* stream);
 
 /* The body model WITHOUT the 49-joint wrapper - smplx.SMPL.forward as the evaluation code calls it (`smpl_native` /
  * `body_model` / `body_model_orig`, spec/trainer.py:71-86,249-254, spec/utils/compute_error.py:118-160): `pose` is

@@ -22,6 +22,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
     python scripts/bench_aux.py --only eval_step          # the validation step's one launch against eval_mesh + eval_joints (means only) -> profiles/eval_step_aux.json
     python scripts/bench_aux.py --head-train --out profiles/head_train_aux.json     # the trainable HMRHead's forward + backward at F = 2048, B = 64 and 256, next to torch autograd over the plain nn.Module on the same device
+    python scripts/bench_aux.py --camcalib-train --out profiles/camcalib_train_aux.json     # CamCalib's three FC heads + CameraRegressorLoss, forward + backward with all gradients, at F = 2048, L = 1 and 3, B = 16 and 64: grouped against single launches, next to torch autograd
     python scripts/bench_aux.py --smpl-backward           # the SMPL head's forward, its backward and the loss backward at B = 256, V = 6890, next to torch autograd over the oracle chain on the same device -> profiles/smpl_backward_aux.json
     python scripts/bench_aux.py --only pano_views_host --reference DIR     # the reference's extractImage on this host's CPU, same views (no GPU)
 """
@@ -1129,11 +1130,106 @@ def head_train_section(a):
     return out
 
 
+def camcalib_train_section(a):
+    """CamCalib's differentiable tail (``specmi_camcalib_head_train_forward`` -> ``specmi_camcalib_loss`` ->
+    ``specmi_camcalib_loss_backward`` -> ``specmi_camcalib_head_backward``, g_xf and all 6 L parameter gradients) at F = 2048,
+    nbins = 256, L = 1 and L = 3 x 1024, B = 16 and 64, 'softargmax_biased_l2': the grouped launches (one per step for the three
+    heads, the default) against three single launches per step (option "camcalib_head_group" = 0, same bits), next to torch's own
+    autograd over the same heads as plain ``nn.Linear``s and the restated loss (fp32, rocBLAS / hipBLASLt) on the same device and
+    the same parameters.  HIP events around ``iters`` back-to-back calls after a warm-up, the three alternated in this process,
+    3 rounds; then the library's kernels by its profiler."""
+    from spec_amd.cam_utils import _engine
+    from spec_amd.engine import camcalib_head_param_names
+    dev = torch.device('cuda', 0)
+    eng = _engine(dev)
+    F, nbins, Hc, lt, weights = 2048, 256, 1024, 'softargmax_biased_l2', (1.0, 1.0, 1.0)
+    eng.set_option('experimental', 1)           # "camcalib_head_group" is on the experimental list
+    g_means = torch.tensor([1.0, 0.0, 0.0, 0.0], device=dev)
+    idx = torch.arange(nbins, device=dev, dtype=torch.float32)
+    out = {}
+    for L in (1, 3):
+        for B in (16, 64):
+            torch.manual_seed(100 * L + B)
+            widths = [F] + [Hc] * (L - 1) + [nbins]
+            plain = torch.nn.ModuleDict({h: (torch.nn.Linear(F, nbins) if L == 1 else
+                                             torch.nn.Sequential(*(torch.nn.Linear(i, o) for i, o in zip(widths[:-1], widths[1:]))))
+                                         for h in ('fc_vfov', 'fc_pitch', 'fc_roll')}).to(dev)
+            names = camcalib_head_param_names(L)
+            named = dict(plain.named_parameters())
+            params = {n: named[n].detach() for n in names}
+            xf = torch.rand(B, F, device=dev) * 1.5
+            targets = [torch.rand(B, device=dev) * 2 - 1 for _ in range(3)]
+
+            def library():
+                logits, tape = eng.camcalib_head_train_forward(params, xf, L)
+                eng.camcalib_loss(logits, targets, lt, weights)
+                g = eng.camcalib_loss_backward(logits, targets, lt, weights, g_means)
+                eng.camcalib_head_backward(params, xf, L, tape, torch.stack(g))
+
+            def single(fn):                                             # the option is set around the timed loop, not inside it
+                def run(*args):
+                    eng.set_option('camcalib_head_group', 0)
+                    try:
+                        return fn(*args)
+                    finally:
+                        eng.set_option('camcalib_head_group', 1)
+                return run
+
+            def torch_autograd():
+                with torch.enable_grad():
+                    x = xf.detach().requires_grad_(True)
+                    total = 0.0
+                    for k, h in enumerate(('fc_vfov', 'fc_pitch', 'fc_roll')):
+                        p = torch.softmax(plain[h](x), -1)
+                        s = 2 * (p * idx).sum(-1) / (nbins - 1) - 1
+                        l2 = (targets[k] - s) ** 2
+                        total = total + weights[k] * (torch.where(s > targets[k], l2, l2 / (l2 + 1)) if k == 0 else l2).mean()
+                    torch.autograd.grad(total, [x] + list(plain.parameters()))
+
+            def ms_per_call(fn):
+                for _ in range(5):
+                    fn()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.iters):
+                    fn()
+                e1.record()
+                torch.cuda.synchronize()
+                return e0.elapsed_time(e1) / a.iters
+            calls = {'library_grouped': lambda: ms_per_call(library), 'library_single_launches': single(lambda: ms_per_call(library)),
+                     'torch_autograd': lambda: ms_per_call(torch_autograd)}
+            rounds = {k: [] for k in calls}
+            for _ in range(3):                                          # alternated: all see the same clocks and the same neighbours
+                for k, fn in calls.items():
+                    rounds[k].append(fn())
+            med = {k: float(np.median(v)) for k, v in rounds.items()}
+
+            def kernels(fn):
+                return {k: {'launches_per_call': v[3], 'ms_per_launch': round(v[0], 5), 'ms_per_call': round(v[0] * v[3], 5),
+                            'TFLOPs': round(v[2] / (v[0] * 1e-3) / 1e12, 2) if v[2] else None} for k, v in timed(eng, fn, a.iters).items()}
+            kg, ks = kernels(library), single(kernels)(library)
+            out[f'L{L}_B{B}'] = {'workload': f'B = {B}, F = {F}, L = {L}' + (f' x {Hc}' if L > 1 else '') + f', nbins = {nbins}, {lt}; head forward, loss, loss '
+                                 'backward, head backward with g_xf and every parameter gradient',
+                                 'ms_round_values': {k: [round(x, 5) for x in v] for k, v in rounds.items()},
+                                 'ms_median': {k: round(v, 5) for k, v in med.items()},
+                                 'spread_between_rounds_ms': {k: round(max(v) - min(v), 5) for k, v in rounds.items()},
+                                 'grouped_over_single': round(med['library_grouped'] / med['library_single_launches'], 3),
+                                 'library_over_torch_autograd': round(med['library_grouped'] / med['torch_autograd'], 3),
+                                 'device_ms_per_call_by_the_library_profiler': {'grouped': round(sum(v['ms_per_call'] for v in kg.values()), 5),
+                                                                               'single_launches': round(sum(v['ms_per_call'] for v in ks.values()), 5)},
+                                 'launches_per_call': {'grouped': sum(v['launches_per_call'] for v in kg.values()),
+                                                       'single_launches': sum(v['launches_per_call'] for v in ks.values())},
+                                 'grouped_kernels_by_the_library_profiler': kg, 'single_kernels_by_the_library_profiler': ks}
+    print(json.dumps(out, indent=1))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'smpl_backward', 'head_train'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'smpl_backward', 'head_train', 'camcalib_train'], default=None, help='run one section only')
     ap.add_argument('--smpl-backward', dest='only', action='store_const', const='smpl_backward', help='the same as --only smpl_backward')
     ap.add_argument('--head-train', dest='only', action='store_const', const='head_train', help='the same as --only head_train')
+    ap.add_argument('--camcalib-train', dest='only', action='store_const', const='camcalib_train', help='the same as --only camcalib_train')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -1167,6 +1263,15 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the same calls; 3 alternated rounds; '
                        'kernels: per-launch HIP events (library profiler)', 'head_train': row, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'camcalib_train':
+        from spec_amd import _lib
+        row = camcalib_train_section(a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the same calls; 3 alternated rounds; '
+                       'kernels: per-launch HIP events (library profiler)', 'camcalib_train': row, 'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     def add(name, workload, res, per_unit=None):

@@ -77,6 +77,15 @@ class HmrHeadParams(C.Structure):
     _fields_ = [(n.replace('.', '_'), C.c_void_p) for n in HMR_HEAD_PARAMS]
 
 
+CAMCALIB_HEADS = ('fc_vfov', 'fc_pitch', 'fc_roll')     # the head index of the two structs below, in order
+CAMCALIB_HEAD_MAX_LAYERS = 3
+
+
+class CamcalibHeadParams(C.Structure):
+    """``specmi_camcalib_head_params`` and ``specmi_camcalib_head_grads`` (include/specmi.h): device pointers [head][layer]."""
+    _fields_ = [('weight', (C.c_void_p * 3) * 3), ('bias', (C.c_void_p * 3) * 3)]
+
+
 class ProfEntry(C.Structure):
     _fields_ = [('kernel', C.c_char * 48), ('label', C.c_char * 48), ('ms', C.c_double),
                 ('flops', C.c_double), ('bytes', C.c_double), ('launches', C.c_int)]
@@ -153,6 +162,17 @@ PROTOTYPES = {
     'specmi_hmr_head_backward': (C.c_int, [C.c_void_p, C.POINTER(HmrHeadParams), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_float,
                                            C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(HmrHeadParams),
                                            C.c_void_p]),
+    # (h, 3 logit tensors, B, nbins, loss_type, 3 targets, 3 weights, loss_term, means, stream)
+    'specmi_camcalib_loss': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_float] * 3 + [C.c_void_p] * 3),
+    # (h, 3 logit tensors, B, nbins, loss_type, 3 targets, 3 weights, g_means, 3 gradients, stream)
+    'specmi_camcalib_loss_backward': (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_float] * 3 + [C.c_void_p] * 5),
+    'specmi_camcalib_head_tape_floats': (C.c_int, [C.c_int] * 5 + [c_int64_p]),
+    # (h, params, xf, ld_xf, B, F, L, Hc, nbins, tape, logits, stream)
+    'specmi_camcalib_head_train_forward': (C.c_int, [C.c_void_p, C.POINTER(CamcalibHeadParams), C.c_void_p, C.c_int64] + [C.c_int] * 5 +
+                                           [C.c_void_p] * 3),
+    # (h, params, xf, ld_xf, B, F, L, Hc, nbins, tape, g_logits, g_xf, grads, stream)
+    'specmi_camcalib_head_backward': (C.c_int, [C.c_void_p, C.POINTER(CamcalibHeadParams), C.c_void_p, C.c_int64] + [C.c_int] * 5 +
+                                      [C.c_void_p] * 3 + [C.POINTER(CamcalibHeadParams), C.c_void_p]),
     'specmi_conv2d': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libspecmi.so')
-SOURCES = ['api.hip', 'commit.hip', 'options.hip', 'hrnet.hip', 'conv_igemm.hip', 'conv_wsplit.hip', 'conv_wino.hip', 'conv_bf16s.hip', 'conv_f16.hip', 'stem.hip', 'head.hip', 'smpl.hip', 'smpl_bwd.hip', 'head_bwd.hip', 'eval.hip', 'loss.hip', 'preprocess.hip', 'panorama.hip', 'render.hip', 'draw.hip', 'marks.hip', 'jpeg.hip', 'jpeg_dec.hip', 'png.hip', 'png_dec.hip']
+SOURCES = ['api.hip', 'commit.hip', 'options.hip', 'hrnet.hip', 'conv_igemm.hip', 'conv_wsplit.hip', 'conv_wino.hip', 'conv_bf16s.hip', 'conv_f16.hip', 'stem.hip', 'head.hip', 'smpl.hip', 'smpl_bwd.hip', 'head_bwd.hip', 'camcalib_bwd.hip', 'eval.hip', 'loss.hip', 'preprocess.hip', 'panorama.hip', 'render.hip', 'draw.hip', 'marks.hip', 'jpeg.hip', 'jpeg_dec.hip', 'png.hip', 'png_dec.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 
 
@@ -37,7 +37,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     objdir = os.path.join(LIBDIR, 'obj')
     os.makedirs(objdir, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, 'specmi_internal.h'), os.path.join(CSRC, 'handle.h'), os.path.join(CSRC, 'conv_igemm_tile.h'),
+    headers = [os.path.join(CSRC, 'specmi_internal.h'), os.path.join(CSRC, 'handle.h'), os.path.join(CSRC, 'conv_igemm_tile.h'), os.path.join(CSRC, 'camcalib_rows.h'),
                os.path.join(os.path.dirname(HERE), 'include', 'specmi.h')]
 
     def compile_one(src):

@@ -1,0 +1,118 @@
+"""Head-only fine-tuning of CamCalib on MI355X: the reference's ``training_step`` (camcalib/trainer.py:60-82 - network ->
+``CameraRegressorLoss`` -> ``loss.backward()`` -> ``torch.optim.Adam``, :201-205) on a FROZEN, committed trunk.  What is trained are
+the three FC heads (``fc_vfov`` / ``fc_pitch`` / ``fc_roll``) on the trunk's pooled features - what adapting the released
+checkpoint to one's own cameras needs, with labelled views such as ``spec_amd.panorama`` cuts out of panoramas.
+
+Per batch: ``DATASET.BATCH_SIZE`` frames in a seeded shuffle, resized and padded as the test step does (``camcalib_eval.pad_batch``),
+``Engine.trunk`` under ``no_grad`` -> ``differentiable.CameraRegressorHead`` (sharing the model's Parameters) ->
+``losses.CameraRegressorLoss(MODEL.LOSS_*)`` -> ``backward()`` -> ``torch.optim.Adam(lr=OPTIMIZER.LR, weight_decay=OPTIMIZER.WD)``.
+The targets come from ``camcalib_eval.encode_targets``.  The optimiser is torch's; forward, loss and both backwards run in the
+library (``specmi_camcalib_head_train_forward`` / ``_backward``, ``specmi_camcalib_loss`` / ``_backward``).
+
+Out of scope, as for the SPEC side: the backward of the trunk, BatchNorm in training mode, the
+reference's augmentation and its training datasets (the frames are those the tree's ``val_images.pkl`` lists, or a ``dataset``
+object with ``PanoValDataset``'s interface), second derivatives.
+"""
+from __future__ import annotations
+
+import copy
+import os
+from typing import List, Optional
+
+import numpy as np
+import torch
+
+from . import camcalib_eval as ce
+
+# camcalib/config.py:63-66,72 over the test step's defaults
+DEFAULTS = dict(copy.deepcopy(ce.DEFAULTS), OPTIMIZER={'TYPE': 'adam', 'LR': 0.001, 'WD': 0.0})
+TRAIN_KEYS = ('train/loss', 'train/vfov_loss', 'train/pitch_loss', 'train/roll_loss')
+
+
+def load_config(cfg_path: Optional[str], opts: Optional[List[str]] = None) -> dict:
+    """``camcalib_eval.load_config`` with the optimiser keys of camcalib/config.py among the defaults."""
+    from . import evaluation
+    return evaluation.load_config(cfg_path, opts, defaults=DEFAULTS)
+
+
+def trunk_features(model, images: torch.Tensor) -> torch.Tensor:
+    """The frozen trunk on one padded batch -> (n, fh, fw, C) NHWC features, whole images in sub-batches of
+    ``camcalib_eval.forward_limit`` (bit-identical under the pinned plan)."""
+    eng = model.engine(images.device)
+    n, _, H, W = images.shape
+    step = ce.forward_limit(H, W)
+    with torch.no_grad():
+        if step >= n:
+            return eng.trunk(images)
+        return torch.cat([eng.trunk(images[b0:b0 + step]) for b0 in range(0, n, step)])
+
+
+def write_checkpoint(model, path: str, epoch: int, global_step: int) -> str:
+    """The model's state_dict in the Lightning layout ``camcalib_eval.build_model`` reads (``model.``-prefixed keys)."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    torch.save({'epoch': int(epoch), 'global_step': int(global_step), 'pytorch-lightning_version': '1.1.8',
+                'state_dict': {'model.' + k: v.detach().cpu().clone() for k, v in model.state_dict().items()}}, path)
+    return path
+
+
+def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = None, epochs: int = 1, seed: int = 0, out: Optional[str] = None,
+                   dataset=None, model=None, log=print, device='cuda', evaluate: bool = True) -> dict:
+    """Head-only fine-tuning (module docstring) for ``epochs`` passes over the labelled frames.  Logs the four ``train/...`` means
+    per epoch, runs ``camcalib_eval.run_evaluation`` before and after (``evaluate``), and writes the Lightning-layout checkpoint
+    ``out`` (None: ``LOG_DIR/camcalib_finetuned.ckpt``).  -> dict(model, ckpt, epochs = the per-epoch means, before / after = the
+    evaluations' four epoch figures)."""
+    from .differentiable import CameraRegressorHead
+    from .losses import CameraRegressorLoss
+    dev = torch.device(device)
+    m = hparams['MODEL']
+    if m['LOSS_TYPE'] not in ce.LOSS_TYPES:
+        raise ValueError(f"{m['LOSS_TYPE']} is not defined..")
+    opt_cfg = dict(DEFAULTS['OPTIMIZER'], **(hparams.get('OPTIMIZER') or {}))
+    if str(opt_cfg['TYPE']).lower() != 'adam':
+        raise NotImplementedError(f"OPTIMIZER.TYPE {opt_cfg['TYPE']!r}: the reference's configure_optimizers builds Adam (camcalib/trainer.py:201-205)")
+    ds = dataset if dataset is not None else ce.PanoValDataset(ce.val_dataset_name(hparams), data_root)
+    if model is None:
+        model = ce.build_model(hparams, ckpt, data_root, dev)
+    else:
+        model.set_plan('throughput')
+    figures = ('val_loss', 'vfov_acc', 'pitch_acc', 'roll_acc')
+    run_eval = lambda: {k: v for k, v in ce.run_evaluation(hparams, data_root, model=model, dataset=dataset, log=log, device=dev,
+                                                          save_images=False).items() if k in figures}
+    before = run_eval() if evaluate else None
+    head = CameraRegressorHead.from_model(model)
+    crit = CameraRegressorLoss(float(m['LOSS_VFOV_WEIGHT']), float(m['LOSS_PITCH_WEIGHT']), float(m['LOSS_ROLL_WEIGHT']), m['LOSS_TYPE'])
+    optim = torch.optim.Adam(head.parameters(), lr=float(opt_cfg['LR']), weight_decay=float(opt_cfg['WD']))
+    bs, min_res, max_res = int(hparams['DATASET']['BATCH_SIZE']), int(hparams['DATASET']['MIN_RES']), hparams['DATASET']['MAX_RES']
+    rng = np.random.default_rng(seed)
+    eng = model.engine(dev)
+    log(f'Train dataset len: {len(ds)}')
+    history, step = [], 0
+    for epoch in range(int(epochs)):
+        order = rng.permutation(len(ds))
+        sums = torch.zeros(4, device=dev)
+        nb = 0
+        for b0 in range(0, len(ds), bs):
+            idx = [int(i) for i in order[b0:b0 + bs]]
+            frames = ds.device_batch(idx) if hasattr(ds, 'device_batch') else [ds.frame(i) for i in idx]
+            gt = np.asarray([ds.labels(i) for i in idx], dtype=np.float64).T
+            images = ce.pad_batch(frames, min_res, max_res, dev, eng)
+            feat = trunk_features(model, images)
+            with torch.enable_grad():
+                loss, loss_dict = crit(*head(feat, channels_last=True), *ce.encode_targets(*gt, m['LOSS_TYPE']))
+                optim.zero_grad(set_to_none=True)
+                loss.backward()
+            optim.step()
+            sums += torch.stack([loss_dict[k].detach() for k in ('loss', 'vfov_loss', 'pitch_loss', 'roll_loss')])
+            nb += 1
+            step += 1
+        means = (sums / max(nb, 1)).cpu().tolist()
+        history.append(dict(zip(TRAIN_KEYS, (float(v) for v in means))))
+        log(f'[EPOCH {epoch}] ' + ', '.join(f'{k}: {v:.6g}' for k, v in history[-1].items()))
+    model.commit(dev, freeze=True)            # the frozen model skips the per-forward check: commit the stepped heads now
+    after = run_eval() if evaluate else None
+    if out is None:
+        log_dir = hparams['LOG_DIR'] if os.path.isabs(hparams['LOG_DIR']) else os.path.join(data_root, hparams['LOG_DIR'])
+        out = os.path.join(log_dir, 'camcalib_finetuned.ckpt')
+    path = write_checkpoint(model, out, int(epochs), step)
+    log(f'checkpoint written to {path}')
+    return {'model': model, 'ckpt': path, 'epochs': history, 'before': before, 'after': after}

@@ -2792,6 +2792,136 @@ int specmi_hmr_head_backward(specmi_handle* h, const specmi_hmr_head_params* par
     return SPECMI_OK;
 }
 
+// the refusals the two CamCalib head training calls and the tape size share; nullptr = accepted, else the message
+static const char* cam_head_shape_refusal(int B, int F, int L, int Hc, int nbins) {
+    if (L < 1 || L > 3) return "L must be in 1 .. 3";
+    if (B < 1 || B > (1 << 20)) return "B must be in [1, 2^20]";
+    if (F < 1 || F > (1 << 20)) return "F must be in [1, 2^20]";
+    if (Hc < 1 || Hc > (1 << 20)) return "Hc must be in [1, 2^20]";
+    if (nbins < 1 || nbins > (1 << 20)) return "nbins must be in [1, 2^20]";
+    return nullptr;
+}
+
+int specmi_camcalib_head_tape_floats(int B, int F, int L, int Hc, int nbins, int64_t* floats) {
+    if (!floats || cam_head_shape_refusal(B, F, L, Hc, nbins)) return SPECMI_ERR_ARG;
+    *floats = (int64_t)cam_head_tape_floats(B, L, Hc);
+    return SPECMI_OK;
+}
+
+// the argument checks of both calls, and the kernels' argument block; `second` = logits resp. g_logits
+static int cam_head_args(specmi_handle* h, const char* who, const specmi_camcalib_head_params* params, const float* xf, int64_t ld_xf,
+                         int B, int F, int L, int Hc, int nbins, const void* tape, const void* second, const char* second_name,
+                         CamHeadArgs& a) {
+    if (const char* why = cam_head_shape_refusal(B, F, L, Hc, nbins))
+        return fail(h, SPECMI_ERR_ARG, "%s: %s (B = %d, F = %d, L = %d, Hc = %d, nbins = %d)", who, why, B, F, L, Hc, nbins);
+    if (!params) return fail(h, SPECMI_ERR_ARG, "%s: params is NULL", who);
+    static const char* const heads[3] = {"fc_vfov", "fc_pitch", "fc_roll"};
+    for (int k = 0; k < 3; ++k)
+        for (int l = 0; l < L; ++l) {
+            const void* const two[2] = {params->weight[k][l], params->bias[k][l]};
+            for (int i = 0; i < 2; ++i) {
+                if (!two[i]) return fail(h, SPECMI_ERR_ARG, "%s: %s layer %d %s is NULL", who, heads[k], l, i ? "bias" : "weight");
+                if (reinterpret_cast<uintptr_t>(two[i]) & 3)
+                    return fail(h, SPECMI_ERR_ARG, "%s: %s layer %d %s is not 4-byte aligned", who, heads[k], l, i ? "bias" : "weight");
+            }
+        }
+    const struct { const void* p; const char* name; } required[] = {{xf, "xf"}, {L > 1 ? tape : xf, "tape"}, {second, second_name}};
+    for (const auto& r : required) {
+        if (!r.p) return fail(h, SPECMI_ERR_ARG, "%s: %s is NULL", who, r.name);
+        if (reinterpret_cast<uintptr_t>(r.p) & 3) return fail(h, SPECMI_ERR_ARG, "%s: %s is not 4-byte aligned", who, r.name);
+    }
+    if (ld_xf < F) return fail(h, SPECMI_ERR_ARG, "%s: ld_xf = %lld is below the row length F = %d", who, (long long)ld_xf, F);
+    std::memset(&a, 0, sizeof(a));
+    for (int k = 0; k < 3; ++k)
+        for (int l = 0; l < L; ++l) { a.p.w[k][l] = params->weight[k][l]; a.p.b[k][l] = params->bias[k][l]; }
+    a.xf = xf; a.ld_xf = (long)ld_xf; a.B = B; a.F = F; a.L = L; a.Hc = Hc; a.nbins = nbins;
+    a.grouped = opt(h, OPT_camcalib_head_group) != 0;
+    return SPECMI_OK;
+}
+
+int specmi_camcalib_head_train_forward(specmi_handle* h, const specmi_camcalib_head_params* params, const float* xf, int64_t ld_xf,
+                                       int B, int F, int L, int Hc, int nbins, float* tape, float* logits, void* stream) {
+    ENTER(h);
+    CamHeadArgs a;
+    if (int rc = cam_head_args(h, "camcalib_head_train_forward", params, xf, ld_xf, B, F, L, Hc, nbins, tape, logits, "logits", a)) return rc;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "camcalib.head_train_forward"};
+    LAUNCHCHK(h, launch_cam_head_train_forward(a, tape, logits, ctx), "camcalib_head_train_forward");
+    return SPECMI_OK;
+}
+
+int specmi_camcalib_head_backward(specmi_handle* h, const specmi_camcalib_head_params* params, const float* xf, int64_t ld_xf, int B,
+                                  int F, int L, int Hc, int nbins, const float* tape, const float* g_logits, float* g_xf,
+                                  const specmi_camcalib_head_grads* grads, void* stream) {
+    ENTER(h);
+    CamHeadArgs a;
+    if (int rc = cam_head_args(h, "camcalib_head_backward", params, xf, ld_xf, B, F, L, Hc, nbins, tape, g_logits, "g_logits", a)) return rc;
+    CamHeadGrads g;
+    std::memset(&g, 0, sizeof(g));
+    bool any = g_xf != nullptr;
+    if (reinterpret_cast<uintptr_t>(g_xf) & 3) return fail(h, SPECMI_ERR_ARG, "camcalib_head_backward: an output is not 4-byte aligned");
+    if (grads)
+        for (int k = 0; k < 3; ++k)
+            for (int l = 0; l < L; ++l) {
+                g.w[k][l] = grads->weight[k][l]; g.b[k][l] = grads->bias[k][l];
+                any = any || g.w[k][l] || g.b[k][l];
+                if ((reinterpret_cast<uintptr_t>(g.w[k][l]) | reinterpret_cast<uintptr_t>(g.b[k][l])) & 3)
+                    return fail(h, SPECMI_ERR_ARG, "camcalib_head_backward: an output is not 4-byte aligned");
+            }
+    if (!any) return fail(h, SPECMI_ERR_ARG, "camcalib_head_backward: every output is NULL");
+    if (L > 1)
+        if (int rc = grow_ragged(h, h->buf[BUF_cam_head_train], cam_head_bwd_ws_floats(B, L, Hc) * 4, "the CamCalib head training workspace")) return rc;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "camcalib.head_backward"};
+    LAUNCHCHK(h, launch_cam_head_backward(a, tape, g_logits, g_xf, g, (float*)h->buf[BUF_cam_head_train].p, ctx), "camcalib_head_backward");
+    return SPECMI_OK;
+}
+
+// the argument checks of specmi_camcalib_loss and its backward, and the kernels' argument block
+static int cam_loss_args(specmi_handle* h, const char* who, const float* lv, const float* lp, const float* lr, int B, int nbins, int loss_type,
+                         const void* tv, const void* tp, const void* tr, float wv, float wp, float wr, CamLossArgs& a) {
+    if (B < 1 || B > (1 << 20)) return fail(h, SPECMI_ERR_ARG, "%s: B = %d must be in [1, 2^20]", who, B);
+    if (nbins < 2 || nbins > (1 << 16)) return fail(h, SPECMI_ERR_ARG, "%s: nbins = %d must be in [2, 2^16]", who, nbins);
+    if (loss_type < SPECMI_LOSS_CE || loss_type > SPECMI_LOSS_SOFTARGMAX_BIASED_L2)
+        return fail(h, SPECMI_ERR_ARG, "%s: loss_type %d is not defined (camcalib/loss.py:75-85: ce, kl, softargmax_l2, softargmax_biased_l2)", who, loss_type);
+    if (!lv || !lp || !lr) return fail(h, SPECMI_ERR_ARG, "%s: a logit tensor is NULL", who);
+    if (!tv || !tp || !tr) return fail(h, SPECMI_ERR_ARG, "%s: a target tensor is NULL", who);
+    a.logits[0] = lv; a.logits[1] = lp; a.logits[2] = lr;
+    a.target[0] = tv; a.target[1] = tp; a.target[2] = tr;
+    a.B = B; a.nbins = nbins; a.loss_type = loss_type;
+    a.weight[0] = wv; a.weight[1] = wp; a.weight[2] = wr;
+    a.loss_term = nullptr; a.means = nullptr;
+    return SPECMI_OK;
+}
+
+int specmi_camcalib_loss(specmi_handle* h, const float* lv, const float* lp, const float* lr, int B, int nbins, int loss_type,
+                         const void* target_vfov, const void* target_pitch, const void* target_roll, float w_vfov, float w_pitch,
+                         float w_roll, float* loss_term, float* means, void* stream) {
+    ENTER(h);
+    CamLossArgs a;
+    if (int rc = cam_loss_args(h, "camcalib_loss", lv, lp, lr, B, nbins, loss_type, target_vfov, target_pitch, target_roll, w_vfov, w_pitch, w_roll, a))
+        return rc;
+    if (!loss_term || !means) return fail(h, SPECMI_ERR_ARG, "camcalib_loss: loss_term or means is NULL");
+    a.loss_term = loss_term; a.means = means;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "camcalib.loss"};
+    LAUNCHCHK(h, launch_camcalib_loss(a, ctx), "camcalib_loss");
+    return SPECMI_OK;
+}
+
+int specmi_camcalib_loss_backward(specmi_handle* h, const float* lv, const float* lp, const float* lr, int B, int nbins, int loss_type,
+                                  const void* target_vfov, const void* target_pitch, const void* target_roll, float w_vfov, float w_pitch,
+                                  float w_roll, const float* g_means, float* g_vfov, float* g_pitch, float* g_roll, void* stream) {
+    ENTER(h);
+    CamLossArgs a;
+    if (int rc = cam_loss_args(h, "camcalib_loss_backward", lv, lp, lr, B, nbins, loss_type, target_vfov, target_pitch, target_roll, w_vfov,
+                               w_pitch, w_roll, a))
+        return rc;
+    if (!g_means) return fail(h, SPECMI_ERR_ARG, "camcalib_loss_backward: g_means is NULL");
+    if (!g_vfov || !g_pitch || !g_roll) return fail(h, SPECMI_ERR_ARG, "camcalib_loss_backward: a gradient output is NULL");
+    float* const g[3] = {g_vfov, g_pitch, g_roll};
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "camcalib.loss_backward"};
+    LAUNCHCHK(h, launch_camcalib_loss_backward(a, g_means, g, ctx), "camcalib_loss_backward");
+    return SPECMI_OK;
+}
+
 int specmi_rotate_points(specmi_handle* h, const float* R, const float* points, int B, int N, float* out, void* stream) {
     ENTER(h);
     if (!R || !points || !out || B <= 0 || N <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");

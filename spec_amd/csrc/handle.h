@@ -103,7 +103,8 @@ struct HrNet;
     SPECMI_OPT(wsplit_max_units_single, 500, false)                                                                       \
     SPECMI_OPT(wsplit_slots, 256, false)                                                                                  \
     SPECMI_OPT(conv2d_sk, 0, false)                                                                                       \
-    SPECMI_OPT(conv2d_wsplit, 0, false)
+    SPECMI_OPT(conv2d_wsplit, 0, false)                                                                                   \
+    SPECMI_OPT(camcalib_head_group, 1, false)
 
 #define SPECMI_OPT(name, def, stable) OPT_##name,
 enum Opt { SPECMI_OPTIONS(SPECMI_OPT) OPT_COUNT };
@@ -150,6 +151,7 @@ enum Buf {
     BUF_pdec,       // specmi_png_decode: the inflated streams, the match records and the Adler sums (pdec_ws_layout)
     BUF_smpl_bwd,   // specmi_smpl_backward: smpl_bwd_ws_floats(V, B) floats
     BUF_head_train, // specmi_hmr_head_train_forward / specmi_hmr_head_backward: head_train_fwd_ws_floats / head_train_bwd_ws_floats floats
+    BUF_cam_head_train, // specmi_camcalib_head_backward: cam_head_bwd_ws_floats floats
     BUF_COUNT
 };
 

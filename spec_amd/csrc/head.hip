@@ -13,6 +13,7 @@
 //     via the quaternion route and K with K[2,2] = 0 (spec/utils/cam_params.py:37-46).
 //     One wave per (image, head): 64-lane shuffle reductions, no LDS traffic for the softmax.
 #include "specmi_internal.h"
+#include "camcalib_rows.h"
 
 namespace specmi {
 
@@ -290,39 +291,7 @@ int launch_camcalib_decode(const float* lv, const float* lp, const float* lr, in
     return (int)hipGetLastError();
 }
 
-// The two per-row reductions camcalib/cam_utils.py applies to a (rows, nbins) logit tensor, one wave per row:
-//   idx[row]  = np.argmax(row)            (bins2vfov / bins2pitch / bins2roll / bins2horizon, cam_utils.py:66-91):
-//               FIRST index of the maximum, a NaN counts as the maximum (NumPy semantics) - index work, bit-exact;
-//   soft[row] = softargmax1d(row, normalize_keypoints=True) in [-1, 1] (get_softargmax, cam_utils.py:110-118).
-// np.argmax of a row by one wave -> index (every lane); mx = the largest non-NaN value (-inf for an all-NaN row)
-__device__ __forceinline__ int wave_argmax_row(const float* __restrict__ r, int nbins, int lane, float& mx) {
-    mx = -INFINITY;
-    int mi = 0x7fffffff, nan_i = 0x7fffffff;
-    for (int i = lane; i < nbins; i += 64) {
-        const float v = r[i];
-        if (v != v) nan_i = min(nan_i, i);
-        if (v > mx || (v == mx && i < mi)) { mx = v; mi = i; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float omx = __shfl_xor(mx, o, 64);
-        const int omi = __shfl_xor(mi, o, 64);
-        nan_i = min(nan_i, __shfl_xor(nan_i, o, 64));
-        if (omx > mx || (omx == mx && omi < mi)) { mx = omx; mi = omi; }
-    }
-    return nan_i != 0x7fffffff ? nan_i : (mi == 0x7fffffff ? 0 : mi);
-}
-// softargmax1d(normalize_keypoints=True) of a row by one wave, given its maximum -> [-1, 1] (every lane); se = sum exp(x - mx)
-__device__ __forceinline__ float wave_softargmax_row(const float* __restrict__ r, int nbins, int lane, float mx, float& se) {
-    float sp = 0.f;
-    se = 0.f;
-    for (int i = lane; i < nbins; i += 64) se += expf(r[i] - mx);
-    se = wave_sum64(se);
-    for (int i = lane; i < nbins; i += 64) sp += expf(r[i] - mx) / se * (float)i;
-    sp = wave_sum64(sp);
-    return sp / (float)(nbins - 1) * 2.0f - 1.0f;
-}
-
+// The two per-row reductions of camcalib/cam_utils.py (camcalib_rows.h: wave_argmax_row, wave_softargmax_row), one wave per row
 __global__ void __launch_bounds__(256) bins_reduce_kernel(const float* __restrict__ x, int rows, int nbins,
                                                            int* __restrict__ idx, float* __restrict__ soft) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -358,15 +327,7 @@ __global__ void __launch_bounds__(192) camcalib_eval_kernel(const CamEvalArgs a)
     const int mi = wave_argmax_row(r, a.nbins, lane, mx);
     const float s = wave_softargmax_row(r, a.nbins, lane, mx, se);
     if (lane != 0) return;
-    float term;
-    if (a.loss_type <= 1) {
-        const int t = min(max(static_cast<const int*>(a.target[head])[b], 0), a.nbins - 1);
-        term = logf(se) - (r[t] - mx);
-    } else {
-        const float t = static_cast<const float*>(a.target[head])[b];
-        const float d = t - s, l2 = d * d;
-        term = (a.loss_type == 3 && head == 0 && !(s > t)) ? l2 / (l2 + 1.0f) : l2;
-    }
+    const float term = camcalib_row_loss_term(r, a.nbins, a.loss_type, head, a.target[head], b, mx, se, s);
     const float ang = soft_idx_to_angle(s, head);
     const size_t o = (size_t)head * a.B + b;
     a.loss_term[o] = term;
@@ -385,9 +346,7 @@ __global__ void __launch_bounds__(384) camcalib_eval_mean_kernel(const CamEvalAr
     __shared__ float head_loss[3];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, head = wave % 3;
     const float* v = (wave < 3 ? a.loss_term : a.err) + (size_t)head * a.B;
-    float acc = 0.f;
-    for (int i = lane; i < a.B; i += 64) acc += v[i];
-    acc = wave_sum64(acc) / (float)a.B;
+    const float acc = wave_batch_mean(v, a.B, lane);
     if (lane == 0) {
         if (wave < 3) a.means[1 + head] = head_loss[head] = a.weight[head] * acc;
         else a.means[4 + head] = acc * (float)(180.0 / 3.14159265358979323846);     // Tensor.rad2deg

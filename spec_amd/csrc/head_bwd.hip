@@ -1,4 +1,5 @@
-// head_bwd.hip - pare's HMRHead regressor for training: its forward with dropout and a tape, and its backward (gfx950).
+// head_bwd.hip - pare's HMRHead regressor for training: its forward with dropout and a tape, and its backward (gfx950); at the end
+// of the file CamCalib's three FC heads for training on the same product, three heads per launch (head_gemm_group_kernel).
 //
 // The loop (oracle/heads.py:80-125; H = 1024, S = 157, Kin = F + S + C, C = 7 with use_cam_feats else 0):
 //     xc_t = [xf | state_t | c],  a1_t = drop1(fc1(xc_t)),  a2_t = drop2(fc2(a1_t)),  state_{t+1} = state_t + dec(a2_t)
@@ -53,7 +54,8 @@ struct GemmArgs {
     int M, N, K;
 };
 
-__global__ void __launch_bounds__(256) head_gemm_kernel(const GemmArgs a) {
+// the tile body, stated once for the single launch and the grouped one (blockIdx.z picks the argument block there)
+__device__ __forceinline__ void head_gemm_tile(const GemmArgs& a) {
     __shared__ float part[3][16][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, c = lane & 31;
     const int m0 = blockIdx.y * 32, n0 = blockIdx.x * 32;
@@ -107,6 +109,14 @@ __global__ void __launch_bounds__(256) head_gemm_kernel(const GemmArgs a) {
     }
 }
 
+__global__ void __launch_bounds__(256) head_gemm_kernel(const GemmArgs a) { head_gemm_tile(a); }
+
+// Up to three products of ONE shape (M, N, K) in one launch: the grid's z picks the argument block, everything else is
+// head_gemm_kernel's - the same split of k among the four waves, the same wave-order sum - so a product's bits do not depend on
+// whether, or with what, it was grouped
+struct GemmGroup { GemmArgs g[3]; };
+__global__ void __launch_bounds__(256) head_gemm_group_kernel(const GemmGroup a) { head_gemm_tile(a.g[blockIdx.z]); }
+
 // out[n] = sum over the R rows of G[r ld + n]; the n columns are cut into up to three outputs at end[0..2].  A workgroup owns 32
 // columns; slice j of 8 adds rows j, j + 8, ... in order and slice 0 adds the eight partial sums in slice order: fixed by R alone
 struct ColSumArgs { const float* G; long ld; int R, N; float* out[3]; int end[3]; };
@@ -137,14 +147,38 @@ __global__ void __launch_bounds__(256) head_sum_t_kernel(const float* __restrict
 struct Op { const float* p; long s0, s1; };                    // an operand and its two strides (row / column index of the product, k)
 struct Epi { const float* bias; const float* res; long ldr; const uint8_t* mask; };
 
-int gemm(const char* name, Op A, Op B, int M, int N, int K, Epi e, float scale, float* C, long ldc, const LaunchCtx& ctx) {
+GemmArgs gemm_args(Op A, Op B, int M, int N, int K, Epi e, float scale, float* C, long ldc) {
     GemmArgs g;
     g.A = A.p; g.sam = A.s0; g.sak = A.s1;
     g.Bm = B.p; g.sbn = B.s0; g.sbk = B.s1;
     g.bias = e.bias; g.res = e.res; g.ldr = e.ldr; g.mask = e.mask; g.ldm = H; g.scale = scale;
     g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+    return g;
+}
+
+int gemm(const char* name, Op A, Op B, int M, int N, int K, Epi e, float scale, float* C, long ldc, const LaunchCtx& ctx) {
+    const GemmArgs g = gemm_args(A, B, M, N, K, e, scale, C, ldc);
     ProfScope ps(ctx, name, 2.0 * M * N * K, 4.0 * ((double)M * K + (double)K * N + (double)M * N));
     hipLaunchKernelGGL(head_gemm_kernel, dim3((N + 31) / 32, (M + 31) / 32), dim3(256), 0, ctx.stream, g);
+    return (int)hipGetLastError();
+}
+
+// n (1 .. 3) products of one shape: one grouped launch, or - grouped == false, or n == 1 - n single ones; the same bits
+int gemm_group(const char* name, const GemmArgs* g, int n, bool grouped, const LaunchCtx& ctx) {
+    const int M = g[0].M, N = g[0].N, K = g[0].K;
+    const dim3 grid((N + 31) / 32, (M + 31) / 32, 1);
+    if (!grouped || n == 1) {
+        for (int i = 0; i < n; ++i) {
+            ProfScope ps(ctx, name, 2.0 * M * N * K, 4.0 * ((double)M * K + (double)K * N + (double)M * N));
+            hipLaunchKernelGGL(head_gemm_kernel, grid, dim3(256), 0, ctx.stream, g[i]);
+            if (const int rc = (int)hipGetLastError()) return rc;
+        }
+        return 0;
+    }
+    GemmGroup grp;
+    for (int i = 0; i < 3; ++i) grp.g[i] = g[i < n ? i : 0];
+    ProfScope ps(ctx, name, 2.0 * n * M * N * K, 4.0 * n * ((double)M * K + (double)K * N + (double)M * N));
+    hipLaunchKernelGGL(head_gemm_group_kernel, dim3(grid.x, grid.y, n), dim3(256), 0, ctx.stream, grp);
     return (int)hipGetLastError();
 }
 
@@ -254,6 +288,79 @@ int launch_head_backward(const HeadTrainArgs& a, const float* tape, const float*
     TRY(colsum(Gs, S, R, S, g.decpose_b, 144, g.decshape_b, 154, g.deccam_b, ctx));
     TRY(colsum(Gh2, H, R, H, g.fc2_b, H, nullptr, H, nullptr, ctx));
     TRY(colsum(Gh1, H, R, H, g.fc1_b, H, nullptr, H, nullptr, ctx));
+    return 0;
+}
+
+// ---- CamCalib's three FC heads for training (camcalib/model.py:59-70) --------------------------------------------------------
+// Head k (vfov, pitch, roll) is a chain of L = 1 .. 3 Linears with NO activation between them: A_0 = xf (B, F),
+// A_l = A_{l-1} W_l^T + b_l, widths F -> Hc -> .. -> nbins.  The tape keeps A_1 .. A_{L-1} as (3, L - 1, B, Hc); the backward's
+// workspace keeps the gradients of the same rows in the same layout.  G_L = g_logits, G_{l-1} = G_l W_l, dW_l = G_l^T A_{l-1},
+// db_l = the column sums of G_l; g_xf = the sum over the heads of G_1 W_1, added in the order vfov, pitch, roll onto one output.
+// Every step whose three heads are independent - each forward layer, each data gradient above layer 1, each weight gradient - is
+// one grouped launch (gemm_group).
+size_t cam_head_tape_floats(int B, int L, int Hc) { return (size_t)3 * (L - 1) * B * Hc; }
+size_t cam_head_bwd_ws_floats(int B, int L, int Hc) { return cam_head_tape_floats(B, L, Hc); }
+
+namespace {
+inline int cam_in(const CamHeadArgs& a, int l) { return l == 0 ? a.F : a.Hc; }
+inline int cam_out(const CamHeadArgs& a, int l) { return l == a.L - 1 ? a.nbins : a.Hc; }
+// row (head k, layer l) of the tape / of the gradient workspace: the OUTPUT of layer l, l < L - 1
+inline size_t cam_slot(const CamHeadArgs& a, int k, int l) { return ((size_t)k * (a.L - 1) + l) * a.B * a.Hc; }
+}  // namespace
+
+int launch_cam_head_train_forward(const CamHeadArgs& a, float* tape, float* logits, const LaunchCtx& ctx) {
+    const int B = a.B, L = a.L;
+    for (int l = 0; l < L; ++l) {
+        const int K = cam_in(a, l), N = cam_out(a, l);
+        GemmArgs g[3];
+        for (int k = 0; k < 3; ++k) {
+            const Op X = l == 0 ? Op{a.xf, a.ld_xf, 1} : Op{tape + cam_slot(a, k, l - 1), a.Hc, 1};
+            float* const Y = l == L - 1 ? logits + (size_t)k * B * a.nbins : tape + cam_slot(a, k, l);
+            g[k] = gemm_args(X, Op{a.p.w[k][l], K, 1}, B, N, K, Epi{a.p.b[k][l], nullptr, 0, nullptr}, 0.f, Y, N);
+        }
+        TRY(gemm_group("cam_head_fwd_gemm", g, 3, a.grouped, ctx));
+    }
+    return 0;
+}
+
+int launch_cam_head_backward(const CamHeadArgs& a, const float* tape, const float* g_logits, float* g_xf, const CamHeadGrads& gr,
+                             float* ws, const LaunchCtx& ctx) {
+    const int B = a.B, L = a.L;
+    // G(k, l) = the gradient of layer l's output, (B, cam_out(l)) dense
+    auto G = [&](int k, int l) -> const float* { return l == L - 1 ? g_logits + (size_t)k * B * a.nbins : ws + cam_slot(a, k, l); };
+    bool below[3] = {false, false, false};       // is a gradient below layer l wanted (layers l' < l, or g_xf)
+    {
+        bool any = g_xf != nullptr;
+        for (int l = 0; l < 3; ++l) {
+            below[l] = any;
+            for (int k = 0; k < 3; ++k) any = any || (l < L && (gr.w[k][l] || gr.b[k][l]));
+        }
+    }
+    for (int l = L - 1; l >= 1 && below[l]; --l) {
+        const int N = cam_in(a, l), K = cam_out(a, l);
+        GemmArgs g[3];
+        for (int k = 0; k < 3; ++k)
+            g[k] = gemm_args(Op{G(k, l), K, 1}, Op{a.p.w[k][l], 1, N}, B, N, K, NONE, 0.f, ws + cam_slot(a, k, l - 1), N);
+        TRY(gemm_group("cam_head_bwd_dgrad_gemm", g, 3, a.grouped, ctx));
+    }
+    if (g_xf) {
+        const int K = cam_out(a, 0);
+        for (int k = 0; k < 3; ++k)
+            TRY(gemm("cam_head_bwd_dgrad_gemm", Op{G(k, 0), K, 1}, Op{a.p.w[k][0], 1, a.F}, B, a.F, K,
+                     Epi{nullptr, k ? g_xf : nullptr, a.F, nullptr}, 0.f, g_xf, a.F, ctx));
+    }
+    for (int l = 0; l < L; ++l) {
+        const int M = cam_out(a, l), N = cam_in(a, l);
+        GemmArgs g[3];
+        int n = 0;
+        for (int k = 0; k < 3; ++k) {
+            if (!gr.w[k][l]) continue;
+            const Op X = l == 0 ? Op{a.xf, 1, a.ld_xf} : Op{tape + cam_slot(a, k, l - 1), 1, a.Hc};
+            g[n++] = gemm_args(Op{G(k, l), 1, M}, X, M, N, B, NONE, 0.f, gr.w[k][l], N);
+        }
+        if (n) TRY(gemm_group("cam_head_bwd_wgrad_gemm", g, n, a.grouped, ctx));
+        for (int k = 0; k < 3; ++k) TRY(colsum(G(k, l), M, B, M, gr.b[k][l], M, nullptr, M, nullptr, ctx));
+    }
     return 0;
 }
 

@@ -458,6 +458,36 @@ int launch_head_train_forward(const HeadTrainArgs& a, const float* init_state, f
 int launch_head_backward(const HeadTrainArgs& a, const float* tape, const float* g_state, float* g_xf, const HeadTrainGrads& g, float* ws,
                          const LaunchCtx& ctx);
 
+// CamCalib's three FC heads for training (head_bwd.hip): [head vfov / pitch / roll][layer 0 .. L-1] weights (out, in) row-major
+// and biases where torch keeps them; xf (B, F) rows ld_xf apart; widths F -> Hc -> .. -> nbins.  tape: cam_head_tape_floats
+// floats = the (3, L - 1, B, Hc) hidden rows; logits / g_logits (3, B, nbins) dense; ws: cam_head_bwd_ws_floats floats.  g_xf and
+// the members of CamHeadGrads may be null (not wanted).  grouped: the three heads' independent products as one launch each.
+struct CamHeadParams { const float* w[3][3]; const float* b[3][3]; };
+struct CamHeadGrads { float* w[3][3]; float* b[3][3]; };
+struct CamHeadArgs {
+    CamHeadParams p;
+    const float* xf; long ld_xf;
+    int B, F, L, Hc, nbins;
+    bool grouped;
+};
+size_t cam_head_tape_floats(int B, int L, int Hc);
+size_t cam_head_bwd_ws_floats(int B, int L, int Hc);
+int launch_cam_head_train_forward(const CamHeadArgs& a, float* tape, float* logits, const LaunchCtx& ctx);
+int launch_cam_head_backward(const CamHeadArgs& a, const float* tape, const float* g_logits, float* g_xf, const CamHeadGrads& g, float* ws,
+                             const LaunchCtx& ctx);
+
+// CameraRegressorLoss for training (camcalib_bwd.hip; include/specmi.h: specmi_camcalib_loss): the loss part of CamEvalArgs.
+// loss_term (3, B), means 4 floats; the backward writes three (B, nbins) gradients from g_means (4).
+struct CamLossArgs {
+    const float* logits[3];
+    const void* target[3];        // int32 bin index (loss_type 0 / 1) or fp32 soft index (2 / 3)
+    int B, nbins, loss_type;
+    float weight[3];
+    float* loss_term; float* means;
+};
+int launch_camcalib_loss(const CamLossArgs& a, const LaunchCtx& ctx);
+int launch_camcalib_loss_backward(const CamLossArgs& a, const float* g_means, float* const g_logits[3], const LaunchCtx& ctx);
+
 // ----------------------------------------------------------------------------------------
 // evaluation metrics  (eval.hip)
 // ----------------------------------------------------------------------------------------

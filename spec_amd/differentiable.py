@@ -12,6 +12,11 @@ training: dropout on in ``.train()``, the loop and its backward on the library's
 torch keeps them - an optimiser steps them as they are.  Its gradient with respect to the pooled feature is where a trunk
 backward would start.
 
+Beside it :class:`CameraRegressorHead`: CamCalib's three FC heads (``fc_vfov`` / ``fc_pitch`` / ``fc_roll``, one Linear or a chain of
+two or three with no activation between them) on the pooled feature, forward and backward on the same kernels
+(``specmi_camcalib_head_train_forward`` / ``specmi_camcalib_head_backward``) - with ``spec_amd.losses.CameraRegressorLoss`` the
+differentiable tail of the reference's CamCalib ``training_step`` on a frozen trunk.
+
 First derivatives only (``once_differentiable``).  The camera arguments (``cam_rotmat``, ``cam_intrinsics``, the box, the image
 size) get no gradient.  With no input requiring grad the heads return exactly what ``Engine.smpl`` returns.
 """
@@ -25,7 +30,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .cam_utils import _engine
-from .engine import Engine
+from .engine import Engine, camcalib_head_param_names
 from .modules import HMRHeadParams
 
 _tls = threading.local()
@@ -237,3 +242,81 @@ class HMRHead(HMRHeadParams):
             state, _ = eng.hmr_head_train_forward(dict(zip(_lib.HMR_HEAD_PARAMS, params)), xf, init_state, cam_feats, masks, self.p, n_iter)
         pose6d, shape, cam = state[:, :144], state[:, 144:154], state[:, 154:]
         return {'pred_pose': rot6d_to_rotmat(pose6d).view(B, 24, 3, 3), 'pred_cam': cam, 'pred_shape': shape, 'pred_pose_6d': pose6d}
+
+
+class _CamHeads(torch.autograd.Function):
+    """(xf, the 6 L parameters in the order of ``camcalib_head_param_names(L)``) -> logits (3, B, nbins)."""
+
+    @staticmethod
+    def forward(ctx, eng, L, xf, *params):
+        names = camcalib_head_param_names(L)
+        ps = [t.detach() for t in params]
+        logits, tape = eng.camcalib_head_train_forward(dict(zip(names, ps)), xf.detach(), L)
+        ctx.eng, ctx.L = eng, L
+        ctx.save_for_backward(xf.detach(), tape, *ps)     # (an optimiser step between forward and backward is caught by autograd's version check)
+        return logits
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_logits):
+        xf, tape, *ps = ctx.saved_tensors
+        names = camcalib_head_param_names(ctx.L)
+        want = [n for n, need in zip(names, ctx.needs_input_grad[3:]) if need]
+        g_xf, grads = ctx.eng.camcalib_head_backward(dict(zip(names, ps)), xf, ctx.L, tape, g_logits, want_xf=ctx.needs_input_grad[2],
+                                                     want_params=want)
+        return (None, None, g_xf) + tuple(grads.get(n) for n in names)
+
+
+class CameraRegressorHead(nn.Module):
+    """The three FC heads of ``CameraRegressorNetwork`` (camcalib/model.py:42-70), trainable: the reference's state_dict names
+    (``fc_vfov.weight``, or ``fc_vfov.0.weight`` .. for chains) and its initialisation (N(0, 0.01) weights and zero bias for one
+    Linear, ``nn.Linear``'s default for chains).  ``forward(features)`` -> [vfov, pitch, roll] logits, each (B, num_out_channels).
+    ``features``: (B, F, h, w), or (B, h, w, F) with ``channels_last=True`` (what ``Engine.trunk`` returns), or (B, F) already
+    pooled; it and the parameters get gradients.  When grad is disabled or nothing requires grad no tape is kept."""
+
+    def __init__(self, num_input_features=2048, num_fc_layers=1, num_fc_channels=1024, num_out_channels=256):
+        super().__init__()
+        if not 1 <= num_fc_layers <= _lib.CAMCALIB_HEAD_MAX_LAYERS:
+            raise NotImplementedError(f'num_fc_layers in 1 .. {_lib.CAMCALIB_HEAD_MAX_LAYERS} are built')
+        self.num_input_features, self.num_fc_layers = int(num_input_features), int(num_fc_layers)
+        self.num_fc_channels, self.num_out_channels = int(num_fc_channels), int(num_out_channels)
+        for name in _lib.CAMCALIB_HEADS:
+            if num_fc_layers == 1:
+                fc = nn.Linear(num_input_features, num_out_channels)
+                nn.init.normal_(fc.weight, mean=0, std=0.01)
+                nn.init.constant_(fc.bias, 0)
+            else:
+                widths = [num_input_features] + [num_fc_channels] * (num_fc_layers - 1) + [num_out_channels]
+                fc = nn.Sequential(*(nn.Linear(a, b) for a, b in zip(widths[:-1], widths[1:])))
+            setattr(self, name, fc)
+
+    @classmethod
+    def from_model(cls, net):
+        """A head that SHARES the ``fc_*`` modules of ``net`` (a ``spec_amd.modules.CameraRegressorNetwork``), and so its Parameter
+        objects: an optimiser step on this head's parameters is a step on the network's, and the network's next call sees the
+        bumped tensor versions and commits them again by itself."""
+        first = net.fc_vfov if net.num_fc_layers == 1 else net.fc_vfov[0]
+        head = cls(first.in_features, net.num_fc_layers, net.num_fc_channels, net.num_out_channels)
+        for name in _lib.CAMCALIB_HEADS:
+            setattr(head, name, getattr(net, name))
+        return head
+
+    def _params(self):
+        sd = dict(self.named_parameters())
+        return tuple(sd[n] for n in camcalib_head_param_names(self.num_fc_layers))
+
+    def forward(self, features, channels_last=False):
+        dev = _device_of(features)
+        if features.dim() == 4:
+            xf = features.mean(dim=(1, 2) if channels_last else (2, 3))       # the average pool, inside autograd
+        elif features.dim() == 2:
+            xf = features
+        else:
+            raise ValueError(f'features must be (B, F, h, w), (B, h, w, F) with channels_last, or (B, F), got {tuple(features.shape)}')
+        params, L = self._params(), self.num_fc_layers
+        eng = _engine(dev)
+        if torch.is_grad_enabled() and (xf.requires_grad or any(t.requires_grad for t in params)):
+            logits = _CamHeads.apply(eng, L, xf, *params)
+        else:
+            logits, _ = eng.camcalib_head_train_forward(dict(zip(camcalib_head_param_names(L), params)), xf, L)
+        return list(logits.unbind(0))

@@ -726,6 +726,71 @@ def check_hmr_head_train(B, F, C, n_iter, p=0.5, masks=False, param_shapes=None,
     return F + HMR_HEAD_STATE + C
 
 
+def camcalib_head_param_names(L):
+    """The state_dict names of CamCalib's three FC heads with L layers each (camcalib/model.py:59-70), ordered head, layer, weight
+    / bias: ``fc_vfov.weight`` for one Linear, ``fc_vfov.0.weight`` .. for an ``nn.Sequential`` chain."""
+    return tuple(f'{h}.{kind}' if L == 1 else f'{h}.{l}.{kind}' for h in _lib.CAMCALIB_HEADS for l in range(L) for kind in ('weight', 'bias'))
+
+
+def camcalib_head_param_shapes(F, L, Hc, nbins):
+    """name -> shape of the 6 L parameters of ``camcalib_head_param_names(L)``: widths F -> Hc -> .. -> nbins."""
+    out = {}
+    for h in _lib.CAMCALIB_HEADS:
+        for l in range(L):
+            nin, nout = (F if l == 0 else Hc), (nbins if l == L - 1 else Hc)
+            stem = h if L == 1 else f'{h}.{l}'
+            out[f'{stem}.weight'], out[f'{stem}.bias'] = (nout, nin), (nout,)
+    return out
+
+
+def camcalib_head_tape_floats(B, L, Hc):
+    """What ``specmi_camcalib_head_tape_floats`` answers, on the host."""
+    return 3 * (L - 1) * B * Hc
+
+
+def check_camcalib_head_train(B, F, L, Hc, nbins, param_shapes=None, ld_xf=None, outputs=None, addresses=()):
+    """Every refusal of ``specmi_camcalib_head_train_forward`` / ``specmi_camcalib_head_backward`` (include/specmi.h) as
+    ``ValueError``, and the parameters' shapes, which the library cannot see.  ``param_shapes``: name -> shape of the 6 L
+    parameters (a missing or None entry is a NULL pointer), None = not checked; ``ld_xf``: the row stride of xf (None = F);
+    ``outputs``: which of g_xf and the 6 L parameter gradients are wanted (None = the forward, whose one output is required);
+    ``addresses``: of the float tensors.  Needs no device."""
+    if not 1 <= L <= _lib.CAMCALIB_HEAD_MAX_LAYERS:
+        raise ValueError(f'L = {L} must be in 1 .. {_lib.CAMCALIB_HEAD_MAX_LAYERS}')
+    for name, v in (('B', B), ('F', F), ('Hc', Hc), ('nbins', nbins)):
+        if not 1 <= v <= 1 << 20:
+            raise ValueError(f'{name} = {v} must be in [1, 2^20]')
+    if param_shapes is not None:
+        for name, shape in camcalib_head_param_shapes(F, L, Hc, nbins).items():
+            if param_shapes.get(name) is None:
+                raise ValueError(f'{name} is missing')
+            if tuple(param_shapes[name]) != shape:
+                raise ValueError(f'{name} must be {shape} for F = {F}, L = {L}, Hc = {Hc}, nbins = {nbins}, got {tuple(param_shapes[name])}')
+    if any(a % 4 for a in addresses):
+        raise ValueError('a float tensor is not 4-byte aligned')
+    if ld_xf is not None and ld_xf < F:
+        raise ValueError(f'the row stride of xf, {ld_xf}, is below the row length F = {F}')
+    if outputs is not None and not any(outputs):
+        raise ValueError('no output is wanted (g_xf or one parameter gradient at least)')
+
+
+def check_camcalib_loss(B, nbins, loss_type, shapes=None, g_means_shape=None):
+    """Every refusal of ``specmi_camcalib_loss`` / ``specmi_camcalib_loss_backward`` (include/specmi.h) as ``ValueError``, with the
+    reference's text for an unknown ``loss_type`` (camcalib/loss.py:85).  ``shapes``: of the three logit and three target tensors
+    (None = not checked); ``g_means_shape``: of the backward's upstream gradient.  -> SPECMI_LOSS_*.  Needs no device."""
+    if loss_type not in _lib.LOSS_TYPES:
+        raise ValueError(f'{loss_type} is not defined..')
+    if not 1 <= B <= 1 << 20:
+        raise ValueError(f'B = {B} must be in [1, 2^20]')
+    if not 2 <= nbins <= 1 << 16:
+        raise ValueError(f'nbins = {nbins} must be in [2, 2^16]')
+    if shapes is not None:
+        if len(shapes) != 6 or any(tuple(s) != (B, nbins) for s in shapes[:3]) or any(tuple(s) != (B,) for s in shapes[3:]):
+            raise ValueError(f'three ({B}, {nbins}) logit tensors and three ({B},) targets, got {[tuple(s) for s in shapes]}')
+    if g_means_shape is not None and tuple(g_means_shape) != (4,):
+        raise ValueError(f'g_means must be (4,) = the gradients of loss, vfov_loss, pitch_loss, roll_loss, got {tuple(g_means_shape)}')
+    return _lib.LOSS_TYPES[loss_type]
+
+
 def out_dtype(dtype):
     """The ``dtype=`` keyword of the producers: torch.float32 -> the (n,3,H,W) fp32 image, torch.float16 -> NHWC8 fp16."""
     if dtype not in (torch.float32, torch.float16):
@@ -1760,6 +1825,118 @@ class Engine:
         gs = _lib.HmrHeadParams(*(grads[n].data_ptr() if n in grads else None for n in _lib.HMR_HEAD_PARAMS))
         _lib.check(self.h, self.lib.specmi_hmr_head_backward(
             self.h, C.byref(st), _ptr(x), ld, _ptr(cf), _ptr(masks), float(p), B, F, C_, int(n_iter), _ptr(tape), _ptr(g), _ptr(g_xf),
+            C.byref(gs) if grads else None, self._stream()))
+        return g_xf, grads
+
+    def _camcalib_loss_args(self, preds, targets, loss_type, weights):
+        """The arguments ``specmi_camcalib_loss`` and its backward share, checked -> (logits, targets, B, nbins, SPECMI_LOSS_*)."""
+        if loss_type not in _lib.LOSS_TYPES:
+            raise ValueError(f'{loss_type} is not defined..')
+        if len(preds) != 3 or len(targets) != 3 or len(weights) != 3:
+            raise ValueError('three logit tensors, three targets and three weights, in the order vfov, pitch, roll')
+        lg = [_dev_f32(t, self.device) for t in preds]
+        if lg[0].dim() != 2:
+            raise ValueError(f'the logit tensors must be (B, nbins), got {tuple(lg[0].shape)}')
+        B, nb = (int(v) for v in lg[0].shape)
+        tdt = torch.int32 if loss_type in ('ce', 'kl') else torch.float32
+        tg = [(t if isinstance(t, torch.Tensor) else torch.as_tensor(np.asarray(t))).to(device=self.device, dtype=tdt).contiguous() for t in targets]
+        lt = check_camcalib_loss(B, nb, loss_type, [t.shape for t in lg + tg])
+        return lg, tg, B, nb, lt
+
+    def camcalib_loss(self, preds, targets, loss_type, weights=(1.0, 1.0, 1.0)):
+        """``specmi_camcalib_loss``: CameraRegressorLoss on three (B, nbins) logit tensors (vfov, pitch, roll).  ``targets``: three
+        (B,) arrays - integer bin indices for 'ce' / 'kl', fp32 soft indices for the soft-argmax losses.  -> dict(loss_term (3, B),
+        means (4,) = loss, vfov_loss, pitch_loss, roll_loss), the bits of ``camcalib_eval`` on the same inputs."""
+        lg, tg, B, nb, lt = self._camcalib_loss_args(preds, targets, loss_type, weights)
+        res = {'loss_term': self._empty(3, B), 'means': self._empty(4)}
+        _lib.check(self.h, self.lib.specmi_camcalib_loss(
+            self.h, *(_ptr(t) for t in lg), B, nb, lt, *(_ptr(t) for t in tg), *(float(w) for w in weights), _ptr(res['loss_term']),
+            _ptr(res['means']), self._stream()))
+        return res
+
+    def camcalib_loss_backward(self, preds, targets, loss_type, weights, g_means):
+        """``specmi_camcalib_loss_backward``: the arguments of ``camcalib_loss`` and ``g_means`` (4,), the upstream gradients of
+        loss, vfov_loss, pitch_loss, roll_loss -> the three (B, nbins) gradients of the logits."""
+        lg, tg, B, nb, lt = self._camcalib_loss_args(preds, targets, loss_type, weights)
+        gm = _dev_f32(g_means, self.device)
+        check_camcalib_loss(B, nb, loss_type, g_means_shape=gm.shape)
+        out = [torch.empty_like(t) for t in lg]
+        _lib.check(self.h, self.lib.specmi_camcalib_loss_backward(
+            self.h, *(_ptr(t) for t in lg), B, nb, lt, *(_ptr(t) for t in tg), *(float(w) for w in weights), _ptr(gm),
+            *(_ptr(t) for t in out), self._stream()))
+        return out
+
+    def _camcalib_head_args(self, params, xf, L, outputs, others):
+        """The arguments the two CamCalib head training calls share, checked -> (params struct, xf, ld_xf, B, F, Hc, nbins).
+        ``params``: the 6 L tensors under their state_dict names, read where they lie - fp32, contiguous, on this device."""
+        if not 1 <= int(L) <= _lib.CAMCALIB_HEAD_MAX_LAYERS:
+            raise ValueError(f'L = {L} must be in 1 .. {_lib.CAMCALIB_HEAD_MAX_LAYERS}')
+        names = camcalib_head_param_names(L)
+        ps = {n: params[n].detach() if params.get(n) is not None else None for n in names}
+        for n, t in ps.items():
+            if t is not None and (t.device != self.device or t.dtype != torch.float32 or not t.is_contiguous()):
+                raise ValueError(f'{n} must be a contiguous fp32 tensor on {self.device} (the library reads it in place)')
+        x = xf.detach() if isinstance(xf, torch.Tensor) else xf
+        if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.device == self.device and x.dtype == torch.float32 and
+                (x.stride(1) == 1 or x.shape[1] == 1)):
+            x = _dev_f32(x, self.device)
+        if x.dim() != 2:
+            raise ValueError(f'xf must be (B, F), got {tuple(x.shape)}')
+        B, F = (int(v) for v in x.shape)
+        ld = x.stride(0) if B > 1 else F
+        first, last = ps[names[0]], ps[names[-2]]
+        if first is None or last is None or first.dim() != 2 or last.dim() != 2:
+            raise ValueError(f'{names[0]} and {names[-2]} must be 2-D weights')
+        Hc, nbins = (int(first.shape[0]) if L > 1 else 1), int(last.shape[0])
+        check_camcalib_head_train(B, F, L, Hc, nbins, {n: None if t is None else t.shape for n, t in ps.items()}, ld_xf=ld, outputs=outputs,
+                                  addresses=[t.data_ptr() for t in (*ps.values(), x, *others) if t is not None])
+        st = _lib.CamcalibHeadParams()
+        for i, n in enumerate(names):
+            k, l, kind = i // (2 * L), i // 2 % L, i % 2
+            (st.bias if kind else st.weight)[k][l] = ps[n].data_ptr()
+        return st, x, ld, B, F, Hc, nbins
+
+    def camcalib_head_train_forward(self, params, xf, L, tape=None):
+        """``specmi_camcalib_head_train_forward``: CamCalib's three FC heads on ``params`` (the 6 L tensors of
+        ``camcalib_head_param_names(L)``, read in place) and xf (B, F) pooled features -> (logits (3, B, nbins), the tape
+        ``camcalib_head_backward`` needs; ``tape=`` takes a caller's flat fp32 buffer of at least
+        ``camcalib_head_tape_floats(B, L, Hc)`` floats)."""
+        st, x, ld, B, F, Hc, nbins = self._camcalib_head_args(params, xf, L, None, ())
+        need = camcalib_head_tape_floats(B, L, Hc)
+        if tape is None:
+            tape = self._empty(need)
+        elif tape.device != self.device or tape.dtype != torch.float32 or not tape.is_contiguous() or tape.numel() < need:
+            raise ValueError(f'tape must be a contiguous fp32 tensor of at least {need} floats on {self.device}')
+        logits = self._empty(3, B, nbins)
+        _lib.check(self.h, self.lib.specmi_camcalib_head_train_forward(
+            self.h, C.byref(st), _ptr(x), ld, B, F, int(L), Hc, nbins, _ptr(tape) if need else None, _ptr(logits), self._stream()))
+        return logits, tape
+
+    def camcalib_head_backward(self, params, xf, L, tape, g_logits, want_xf=True, want_params=True):
+        """``specmi_camcalib_head_backward``: the forward's arguments and its tape, g_logits (3, B, nbins) -> (g_xf (B, F) or None,
+        {name: gradient} of the wanted parameters).  ``want_params``: True (all 6 L), False, or the names wanted."""
+        g = _dev_f32(g_logits, self.device)
+        all_names = camcalib_head_param_names(L)
+        names = all_names if want_params is True else tuple(want_params or ())
+        if set(names) - set(all_names):
+            raise ValueError(f'want_params names {sorted(set(names) - set(all_names))}: not parameters of the heads')
+        outputs = [bool(want_xf)] + [n in names for n in all_names]
+        st, x, ld, B, F, Hc, nbins = self._camcalib_head_args(params, xf, L, outputs, (g, tape))
+        if tuple(g.shape) != (3, B, nbins):
+            raise ValueError(f'g_logits must be (3, {B}, {nbins}), got {tuple(g.shape)}')
+        need = camcalib_head_tape_floats(B, L, Hc)
+        if tape is None or tape.device != self.device or tape.dtype != torch.float32 or not tape.is_contiguous() or tape.numel() < need:
+            raise ValueError(f'tape must be the contiguous fp32 tensor of at least {need} floats the forward wrote')
+        g_xf = self._empty(B, F) if want_xf else None
+        shapes = camcalib_head_param_shapes(F, L, Hc, nbins)
+        grads = {n: self._empty(*shapes[n]) for n in all_names if n in names}
+        gs = _lib.CamcalibHeadParams()
+        for i, n in enumerate(all_names):
+            if n in grads:
+                k, l, kind = i // (2 * L), i // 2 % L, i % 2
+                (gs.bias if kind else gs.weight)[k][l] = grads[n].data_ptr()
+        _lib.check(self.h, self.lib.specmi_camcalib_head_backward(
+            self.h, C.byref(st), _ptr(x), ld, B, F, int(L), Hc, nbins, _ptr(tape) if need else None, _ptr(g), _ptr(g_xf),
             C.byref(gs) if grads else None, self._stream()))
         return g_xf, grads
 

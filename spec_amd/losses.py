@@ -144,3 +144,85 @@ class HMRCamLoss(_LossBase):
     ):
         super().__init__()
         self._set_weights(locals())
+
+
+# ---- CamCalib: CameraRegressorLoss (camcalib/loss.py:24-125) --------------------------------------------------------------------
+CAMCALIB_LOSS_KEYS = ('loss', 'vfov_loss', 'pitch_loss', 'roll_loss')
+
+
+class _CamLossFn(torch.autograd.Function):
+    """means (4) = Engine.camcalib_loss of the three logit tensors; backward = Engine.camcalib_loss_backward."""
+
+    @staticmethod
+    def forward(ctx, eng, loss_type, targets, weights, pv, pp, pr):
+        preds = [t.detach() for t in (pv, pp, pr)]
+        ctx.eng, ctx.loss_type, ctx.targets, ctx.weights, ctx.preds = eng, loss_type, targets, weights, preds
+        return eng.camcalib_loss(preds, targets, loss_type, weights)['means']
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_means):
+        g = ctx.eng.camcalib_loss_backward(ctx.preds, ctx.targets, ctx.loss_type, ctx.weights, g_means)
+        return (None, None, None, None) + tuple(gi.reshape(p.shape) if need else None for gi, p, need in zip(g, ctx.preds, ctx.needs_input_grad[4:]))
+
+
+def _camcalib_means(preds, targets, loss_type, weights):
+    """The four means of CameraRegressorLoss on device logits; a graph only when grad is enabled and a pred requires grad."""
+    if loss_type not in _lib.LOSS_TYPES:
+        raise ValueError(f'{loss_type} is not defined..')
+    preds = [p.squeeze(-1) if isinstance(p, torch.Tensor) else p for p in preds]
+    v = preds[0]
+    if not isinstance(v, torch.Tensor) or v.device.type != 'cuda':
+        raise RuntimeError('spec_amd.losses needs device tensors (no CPU path)')
+    if torch.is_grad_enabled() and any(p.requires_grad for p in preds):
+        return _CamLossFn.apply(_engine(v.device), loss_type, tuple(targets), tuple(weights), *preds)
+    with torch.no_grad():
+        return _engine(v.device).camcalib_loss(preds, targets, loss_type, weights)['means']
+
+
+class CameraRegressorLoss(nn.Module):
+    """camcalib/loss.py:62-125: ``forward(pred_vfov, pred_pitch, pred_roll, gt_vfov, gt_pitch, gt_roll)`` -> (loss, loss_dict) with
+    the keys ``loss``, ``vfov_loss``, ``pitch_loss``, ``roll_loss`` (0-dim device tensors).  The targets are integer bin indices
+    (any integer dtype) for 'ce' / 'kl', fp32 soft indices in [-1, 1] for the soft-argmax losses.  When grad is enabled and a pred
+    requires grad every entry carries a ``grad_fn`` whose backward is ``specmi_camcalib_loss_backward`` (first derivatives only);
+    otherwise the values are ``Engine.camcalib_eval(...)['means'][:4]`` bit for bit, without a graph."""
+
+    def __init__(self, vfov_loss_weight=1.0, pitch_loss_weight=1.0, roll_loss_weight=1.0, loss_type='kl'):
+        super().__init__()
+        if loss_type not in _lib.LOSS_TYPES:
+            raise ValueError(f'{loss_type} is not defined..')
+        self.loss_type = loss_type
+        self.vfov_loss_weight = vfov_loss_weight
+        self.pitch_loss_weight = pitch_loss_weight
+        self.roll_loss_weight = roll_loss_weight
+
+    def forward(self, pred_vfov, pred_pitch, pred_roll, gt_vfov, gt_pitch, gt_roll):
+        means = _camcalib_means((pred_vfov, pred_pitch, pred_roll), (gt_vfov, gt_pitch, gt_roll), self.loss_type,
+                                (self.vfov_loss_weight, self.pitch_loss_weight, self.roll_loss_weight))
+        loss_dict = dict(zip(CAMCALIB_LOSS_KEYS, means.unbind(0)))
+        return loss_dict['loss'], loss_dict
+
+
+class _OneHead(nn.Module):
+    """A leaf criterion of camcalib/loss.py on ONE head: the row arithmetic of the vfov head (the only one 'biased_l2' differs
+    on), weight 1, the other two heads fed the same logits."""
+    _loss_type = None
+
+    def forward(self, pred, target):
+        return _camcalib_means((pred, pred.detach(), pred.detach()), (target, target, target), self._loss_type, (1.0, 1.0, 1.0))[1]
+
+
+class KLDivergence(_OneHead):
+    """camcalib/loss.py:24-30: ``F.kl_div(log_softmax(pred), one_hot(target), 'batchmean')`` of (N, nbins) logits."""
+    _loss_type = 'kl'
+
+
+class SoftargmaxClsLoss(_OneHead):
+    """camcalib/loss.py:33-59: pred (N, nbins), target (N,) in [-1, 1]; ``criterion`` 'l2' or 'biased_l2'."""
+
+    def __init__(self, criterion='l2'):
+        super().__init__()
+        if criterion not in ('l2', 'biased_l2'):
+            raise ValueError(f'{criterion} is not defined!')
+        self.criterion = criterion
+        self._loss_type = 'softargmax_l2' if criterion == 'l2' else 'softargmax_biased_l2'
