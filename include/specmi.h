@@ -904,6 +904,44 @@ int specmi_draw_marks(specmi_handle* h, uint8_t* slab, size_t slab_bytes, const 
 int specmi_denormalize_u8(specmi_handle* h, const float* x, int B, int Hp, int Wp, int index, int H, int W, const float* mean3,
                           const float* std3, uint8_t* slab, size_t slab_bytes, int64_t offset, int64_t pitch, void* stream);
 
+/* TORCHVISION'S ColorJitter on the uint8 RGB frames of a slab, every frame with its own order and factors, in at most TWO kernel
+ * launches per call: the one step by which CameraRegressorDataset(is_train=True) differs from the validation half
+ * (camcalib/pano_dataset.py:62-78), so that training frames stay where specmi_jpeg_decode / specmi_png_decode /
+ * specmi_pano_extract_views left them and specmi_resize_normalize_ragged reads them.  The contract is PILLOW'S, byte for byte
+ * (stated in full at the head of spec_amd/csrc/color_jitter.hip, restated in NumPy in tests/color_jitter_ref.py and pinned
+ * there against the installed Pillow).  Works on a handle of any model kind, committed or not.
+ * DEVICE pointers: in_slab / out_slab, uint8 RGB, of in_slab_bytes / out_slab_bytes.  HOST:
+ *   frame_geom    (nframes x 2 int32):  H, W
+ *   frame_offsets (nframes x 4 int64):  byte offset of the frame's first pixel and bytes from one row to the next, in in_slab,
+ *                                       then the same two in out_slab
+ *   records       (nframes x 8 int32):  THE JITTER RECORD - the ids of the operations in application order, -1 = none
+ *                                       (SPECMI_JITTER_BRIGHTNESS / _CONTRAST / _SATURATION / _HUE); the bit patterns of the fp32
+ *                                       factors of brightness, contrast and saturation (read even where the operation is
+ *                                       absent: write 1.0f); the hue shift k = trunc(hue * 255) mod 256
+ * Each operation works on the uint8 result of the one before it.  blend(d, v, a) = clamp-and-truncate of float(d) + a *
+ * float(v - d), product and sum rounded to fp32 separately.  Brightness: blend(0, v, f).  Saturation: blend(L, v, f) with
+ * L = (19595 r + 38470 g + 7471 b + 32768) >> 16.  Contrast: blend(m, v, f), m = int(S / (H W) + 0.5) in float64 with S the
+ * 64-bit integer sum of L over the frame as it stands when contrast is reached.  Hue: Pillow's RGB -> HSV, h + k mod 256,
+ * HSV -> RGB.  A stat launch sums L for the frames whose order holds contrast (integer atomics: nothing depends on scheduling; a
+ * memset node zeroes the sums in front of it), an apply launch writes every pixel once; without contrast anywhere the call
+ * is the apply launch alone.  In place - out_slab == in_slab and every frame's two rectangles the same - gives the bytes
+ * out of place gives.  Row padding and slab bytes outside every output rectangle are never written.
+ * Refused (SPECMI_ERR_ARG), launching nothing: a null pointer; nframes outside [1, 65535]; H or W outside [1, 8192]; a pitch
+ * below 3 W; a rectangle that leaves its slab; two frames that share an output byte; slabs that overlap without being in
+ * place as above; an id outside [-1, 3] or named twice; a factor that is negative or not finite; k outside [0, 255]; frames that
+ * hold 2^31 tiles of 256 x 16 pixels or more.
+ * The frame records live in a device table owned by the handle and the sums in a workspace next to it, under the rule of the
+ * ragged calls above: a call whose records differ from the previous call's rewrites the table and therefore first
+ * SYNCHRONISES THE WHOLE DEVICE, and cannot be made while a stream is being captured (SPECMI_ERR_STATE; the stream is asked
+ * first, so the capture stays valid and nothing is enqueued); a call that repeats them does neither and can be captured.  The
+ * pointers are not part of the table. */
+#define SPECMI_JITTER_BRIGHTNESS 0
+#define SPECMI_JITTER_CONTRAST 1
+#define SPECMI_JITTER_SATURATION 2
+#define SPECMI_JITTER_HUE 3
+int specmi_color_jitter(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_bytes, uint8_t* out_slab, size_t out_slab_bytes,
+                        const int32_t* frame_geom, const int64_t* frame_offsets, const int32_t* records, int nframes, void* stream);
+
 /* BASELINE JPEG FILES encoded on the device, all pictures of a flush in one fixed sequence of launches: replaces the download
  * of the raw pictures and the host encoder behind every picture the flows write (cv2.imwrite / PIL's save in
  * spec/utils/renderer_cam.py:213-216, spec/tester.py:188-201, camcalib/datagen/generateCalibrationDataset.py:131-132) - the

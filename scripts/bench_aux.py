@@ -18,6 +18,7 @@ section 3 states).  All of them are byte / gather work: none is reshaped into a 
     python scripts/bench_aux.py --only png_encode         # pictures to PNG files: device encode + download of the bytes against raw download + Pillow -> profiles/png_encode_aux.json
     python scripts/bench_aux.py --only png_decode         # 64 1080p .png frames and 8 three-panel pictures to the frame slab: 16 Pillow threads + upload against streams up + device decode -> profiles/png_decode_aux.json
     python scripts/bench_aux.py --only jpeg_decode        # 64 1080p .jpg frames to the frame slab: 16 Pillow threads + upload against bytes up + device decode -> profiles/jpeg_decode_aux.json
+    python scripts/bench_aux.py --only color_jitter       # ColorJitter on 64 1080p frames: the two launches next to a device-to-device copy; Pillow on 16 threads against the device call -> profiles/color_jitter_aux.json
     python scripts/bench_aux.py --only horizon_panel      # panel 0 of eight 1080p frames: Pillow on the host against specmi_draw_marks -> profiles/horizon_panel_aux.json
     python scripts/bench_aux.py --only hmr_loss           # the two launches of the loss forward (HMRCamLoss, per-vertex term on) -> profiles/hmr_loss_aux.json
     python scripts/bench_aux.py --only eval_step          # the validation step's one launch against eval_mesh + eval_joints (means only) -> profiles/eval_step_aux.json
@@ -863,6 +864,127 @@ def eval_step_section(eng, a):
     return row
 
 
+def natural_frames_1080p(n=64):
+    """``n`` synthetic frames of 1080 x 1920 with natural-like content: low-frequency structure plus mild noise"""
+    rng = np.random.default_rng(0)
+    yy, xx = np.mgrid[0:1080, 0:1920]
+    noise = [rng.normal(0, 5, (1080, 1920, 3)) for _ in range(4)]
+    imgs = []
+    for i in range(n):
+        base = np.stack([128 + 80 * np.sin(yy / (60.0 + 7 * c + i) + i) * np.cos(xx / (90.0 + 11 * c) + 0.3 * i) + 30 * np.sin((xx + yy) / (17.0 + i % 5))
+                         for c in range(3)], axis=2)
+        imgs.append(np.clip(base + noise[i % 4], 0, 255).astype(np.uint8))
+    return imgs
+
+
+def binding_statement(full_over_copy, no_hue_over_copy, hue_cost):
+    """What bounds the apply launch, from its time against the copy of the same bytes with and without the hue shift (1.25 x = beyond
+    what the rounds differ by)"""
+    if full_over_copy <= 1.25:
+        return 'HBM bandwidth bounds the apply launch: it takes what a copy of the same bytes takes'
+    if no_hue_over_copy <= 1.25:
+        return f'the hue arithmetic bounds the apply launch: without hue it takes what the copy takes, with it {full_over_copy} x'
+    return (f'arithmetic bounds the apply launch, not HBM: with hue taken out of every order it still takes {no_hue_over_copy} x the copy of the same '
+            f'bytes (the blends and the byte unpacking), and the hue shift multiplies that by {round(hue_cost, 2)}')
+
+
+def color_jitter_section(eng, a):
+    """``specmi_color_jitter`` on the 64 synthetic 1080p frames of ``--only jpeg_decode`` with the reference's four settings and a
+    seeded order per frame (``augment.ColorJitter.records``); the same with contrast removed (one launch) and with the hue shift
+    removed (what the hue arithmetic costs).  Per launch: HIP events of the library's profiler after a warm-up, next to a
+    device-to-device copy of the same slab timed by events in the same process, alternated over 3 rounds - the copy is the
+    yardstick.  Bytes are counted here: 3 N read by the stat launch, 3 N read + 3 N written by the apply launch and by the copy.
+    Host comparison, wall clock, 3 alternated rounds: Pillow's chain on 16 threads + ``pack_frames`` (one upload) against
+    ``pack_frames`` + the device call; the two slabs are compared."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    from PIL import Image, ImageEnhance
+    from spec_amd import augment
+    from spec_amd.preprocess import pack_frames
+    dev = eng.device
+    imgs = natural_frames_1080p()
+    slab, offsets, sizes = pack_frames(imgs, dev)
+    out = torch.empty_like(slab)
+    N = sum(H * W for H, W in sizes)
+    cj = augment.ColorJitter(**augment.CAMCALIB_TRAIN_JITTER)
+    full = cj.records(len(imgs), torch.Generator().manual_seed(0))
+
+    def without(recs, op):
+        r = recs.copy()
+        for row in r:
+            ids = [i for i in row[:4] if i >= 0 and i != op]
+            row[:4] = ids + [-1] * (4 - len(ids))
+        return r
+    workloads = {'full': full, 'no_contrast': without(full, 1), 'no_hue': without(full, 3)}
+    counted = {'color_jitter_stat': 3 * N, 'color_jitter_apply': 6 * N, 'copy': 6 * N}
+
+    def copy_ms(iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            out.copy_(slab)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+    rows = {}
+    for name, recs in workloads.items():
+        ms = {}
+        for _ in range(3):                                              # alternated: the launches and the copy see the same clocks
+            for k, (t, _, _, _) in timed(eng, lambda: eng.color_jitter(slab, offsets, sizes, recs, out=out), a.iters).items():
+                ms.setdefault(k, []).append(t)
+            ms.setdefault('copy', []).append(copy_ms(a.iters))
+        med = {k: float(np.median(v)) for k, v in ms.items()}
+        rows[name] = {'ms_rounds': {k: [round(x, 4) for x in v] for k, v in ms.items()}, 'ms_median': {k: round(v, 4) for k, v in med.items()},
+                      'counted_MB': {k: round(counted[k] / 1e6, 1) for k in med}, 'achieved_GBps': {k: round(counted[k] / (med[k] * 1e-3) / 1e9, 1) for k in med},
+                      'frac_of_hbm_peak': {k: round(counted[k] / (med[k] * 1e-3) / HBM_PEAK, 3) for k in med},
+                      'apply_over_copy': round(med['color_jitter_apply'] / med['copy'], 2)}
+    hue_cost = rows['full']['ms_median']['color_jitter_apply'] / rows['no_hue']['ms_median']['color_jitter_apply']
+    rows['binding_limit'] = {'apply_full_over_apply_no_hue': round(hue_cost, 2), 'apply_no_hue_over_copy': rows['no_hue']['apply_over_copy'],
+                             'apply_full_over_copy': rows['full']['apply_over_copy'],
+                             'statement': binding_statement(rows['full']['apply_over_copy'], rows['no_hue']['apply_over_copy'], hue_cost)}
+
+    def pil_chain(arg):
+        img, rec = Image.fromarray(arg[0]), arg[1]
+        f = rec[4:7].view(np.float32)
+        for op in rec[:4]:
+            if op == 0:
+                img = ImageEnhance.Brightness(img).enhance(float(f[0]))
+            elif op == 1:
+                img = ImageEnhance.Contrast(img).enhance(float(f[1]))
+            elif op == 2:
+                img = ImageEnhance.Color(img).enhance(float(f[2]))
+            elif op == 3:                                               # torchvision's adjust_hue
+                h, s_, v = img.convert('HSV').split()
+                h = Image.fromarray((np.asarray(h).astype(np.int32) + int(rec[7])).astype(np.uint8), 'L')
+                img = Image.merge('HSV', (h, s_, v)).convert('RGB')
+        return np.asarray(img)
+
+    def host_route():
+        with ThreadPoolExecutor(max_workers=16) as ex:
+            frames = list(ex.map(pil_chain, zip(imgs, full)))
+        res = pack_frames(frames, dev)[0]
+        torch.cuda.synchronize()
+        return res
+
+    def device_route():
+        s_, o_, z_ = pack_frames(imgs, dev)
+        res = eng.color_jitter(s_, o_, z_, full, out=s_)
+        torch.cuda.synchronize()
+        return res
+    same = bool(torch.equal(host_route(), device_route()))              # warm-up, and the comparison
+    wall = {'host': [], 'device': []}
+    for _ in range(3):
+        for name, fn in (('host', host_route), ('device', device_route)):
+            t0 = time.perf_counter()
+            fn()
+            wall[name].append((time.perf_counter() - t0) * 1e3)
+    rows['host_comparison'] = {'host_16_threads_ms': [round(v, 1) for v in wall['host']], 'device_ms': [round(v, 1) for v in wall['device']],
+                               'identical_slabs': same, 'ratio_host_over_device': round(float(np.median(wall['host']) / np.median(wall['device'])), 1)}
+    rows['workload'] = f'{len(imgs)} frames of 1080 x 1920 ({N * 3 / 1e6:.1f} MB), brightness / contrast / saturation 0.2, hue 0.1, a seeded order per frame'
+    print(json.dumps(rows, indent=1))
+    return rows
+
+
 def jpeg_decode_section(eng, a):
     """64 frames of 1080p, natural-like content (low-frequency structure plus mild noise), at quality 75 and 95, from files on disk to
     the frame slab on the device: 16 Pillow threads + pack + one upload against read bytes + one upload + one specmi_jpeg_decode
@@ -873,14 +995,7 @@ def jpeg_decode_section(eng, a):
     from PIL import Image
     from spec_amd import preprocess
     dev = eng.device
-    rng = np.random.default_rng(0)
-    yy, xx = np.mgrid[0:1080, 0:1920]
-    noise = [rng.normal(0, 5, (1080, 1920, 3)) for _ in range(4)]
-    rows, imgs = {}, []
-    for i in range(64):
-        base = np.stack([128 + 80 * np.sin(yy / (60.0 + 7 * c + i) + i) * np.cos(xx / (90.0 + 11 * c) + 0.3 * i) + 30 * np.sin((xx + yy) / (17.0 + i % 5))
-                         for c in range(3)], axis=2)
-        imgs.append(np.clip(base + noise[i % 4], 0, 255).astype(np.uint8))
+    rows, imgs = {}, natural_frames_1080p()
     with tempfile.TemporaryDirectory() as tmp:
         for q in (75, 95):
             paths = [os.path.join(tmp, f'q{q}_{i:02d}.jpg') for i in range(64)]
@@ -1226,7 +1341,7 @@ def camcalib_train_section(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'smpl_backward', 'head_train', 'camcalib_train'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'color_jitter', 'smpl_backward', 'head_train', 'camcalib_train'], default=None, help='run one section only')
     ap.add_argument('--smpl-backward', dest='only', action='store_const', const='smpl_backward', help='the same as --only smpl_backward')
     ap.add_argument('--head-train', dest='only', action='store_const', const='head_train', help='the same as --only head_train')
     ap.add_argument('--camcalib-train', dest='only', action='store_const', const='camcalib_train', help='the same as --only camcalib_train')
@@ -1376,6 +1491,17 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'timing': 'wall clock from the files on disk to the frame slab on the device, one warm-up then 3 alternated rounds, ms per '
                        'batch; stage_ms: per-launch HIP events (library profiler)', 'png_decode': rows, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'color_jitter':
+        from spec_amd import _lib
+        rows = color_jitter_section(eng, a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'launches: per-launch HIP events (library profiler) after a warm-up, the '
+                       'device-to-device copy of the same slab by events in the same process, 3 alternated rounds; routes: wall clock from host '
+                       'frames to the jittered slab on the device, 3 alternated rounds, ms per 64-frame batch', 'color_jitter': rows,
+                       'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     if a.only == 'horizon_panel':

@@ -2,11 +2,14 @@
 """Head-only fine-tuning of CamCalib in one command - the part of the reference's ``python scripts/camcalib_train.py --cfg FILE``
 (camcalib/trainer.py:60-82,201-205) that adapts a released checkpoint to other cameras:
 
-    python scripts/camcalib_finetune.py --cfg camcalib_config.yaml [--ckpt FILE] [--epochs 5] [--out FILE] [--opts OPTIMIZER.LR 0.0003 ...]
+    python scripts/camcalib_finetune.py --cfg camcalib_config.yaml [--ckpt FILE] [--epochs 5] [--out FILE] [--augment [--train-split]]
+                                        [--opts OPTIMIZER.LR 0.0003 ...]
 
 The trunk stays FROZEN and committed; only the three FC heads (fc_vfov / fc_pitch / fc_roll) are trained, on the trunk's pooled
 features, under ``CameraRegressorLoss(MODEL.LOSS_*)`` with ``torch.optim.Adam(lr=OPTIMIZER.LR)``.  No trunk backward, no BatchNorm
-in training mode, no augmentation.  The labelled frames are those of ``DATASET.VAL_DS`` under ``--data-root``
+in training mode.  ``--augment`` applies the reference's training ColorJitter (brightness, contrast, saturation 0.2, hue 0.1:
+camcalib/pano_dataset.py:65) to every frame on the device, in Pillow's bytes, seeded by ``--augment-seed``; ``--train-split``
+takes the frames ``train_images.pkl`` lists, as the reference's ``is_train=True`` half does.  The labelled frames are those of ``DATASET.VAL_DS`` under ``--data-root``
 (``data/dataset_folders/pano`` / ``pano_scalenet``: the frames ``val_images.pkl`` lists), batched ``DATASET.BATCH_SIZE`` at a time in
 a shuffle seeded by ``--seed``.  The test step runs before and after, the four ``train/...`` means are logged per epoch, and the
 result is a Lightning-layout checkpoint that ``scripts/camcalib_eval.py --ckpt`` (and the reference) loads.
@@ -38,6 +41,9 @@ def main():
     ap.add_argument('--panoramas', type=str, default=None, metavar='DIR', help='train on views generated from the panoramas in DIR')
     ap.add_argument('--views-per-pano', type=int, default=12)
     ap.add_argument('--seed', type=int, default=0, help='seed of the shuffle (and of the camera sampler with --panoramas)')
+    ap.add_argument('--augment', action='store_true', help="the reference's training ColorJitter on every frame, on the device")
+    ap.add_argument('--augment-seed', type=int, default=0, help='seed of the jitter parameters')
+    ap.add_argument('--train-split', action='store_true', help='train on the frames train_images.pkl lists (default: val_images.pkl)')
     ap.add_argument('--report', type=str, default=None, metavar='train.json')
     args = ap.parse_args()
     from spec_amd import camcalib_eval as ce
@@ -52,7 +58,8 @@ def main():
     if args.panoramas:
         from spec_amd import panorama
         dataset = panorama.PanoViewDataset(panorama.list_panoramas(args.panoramas), args.views_per_pano, args.seed)
-    res = ct.finetune_heads(hp, data_root=root, ckpt=args.ckpt, epochs=args.epochs, seed=args.seed, out=args.out, dataset=dataset)
+    res = ct.finetune_heads(hp, data_root=root, ckpt=args.ckpt, epochs=args.epochs, seed=args.seed, out=args.out, dataset=dataset,
+                            augment=args.augment, augment_seed=args.augment_seed, split='train' if args.train_split else 'val')
     if args.report:
         with open(args.report, 'w') as f:
             json.dump({k: res[k] for k in ('ckpt', 'epochs', 'before', 'after')}, f, indent=1)

@@ -37,6 +37,8 @@ DRAW_MAX_SIDE, DRAW_MAX_COORD, DRAW_MAX_RADIUS, DRAW_MAX_THICKNESS = 8192, 16383
 MARK_STRIP, MARK_MASK, MARK_LINE, MARK_REC = 0, 1, 2, 8         # SPECMI_MARK_* and the int64 per mark record (include/specmi.h)
 # the limits of specmi_draw_marks: frame side, line width, line end point, mask side, mask position (include/specmi.h)
 MARK_MAX_SIDE, MARK_MIN_WIDTH, MARK_MAX_WIDTH, MARK_MAX_COORD, MARK_MAX_MASK_SIDE, MARK_MAX_MASK_POS = 8192, 2, 64, 100000, 8192, 16383
+# SPECMI_JITTER_* (the operation ids of specmi_color_jitter), the int32 words of its record and its largest frame side (include/specmi.h)
+JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE, JITTER_REC, JITTER_MAX_SIDE = 0, 1, 2, 3, 8, 8192
 JPEG_HEADER_BYTES = 623                       # what specmi_jpeg_header writes; the least capacity of specmi_jpeg_encode (include/specmi.h)
 PNG_OVERHEAD_BYTES, PNG_HEADER_BYTES = 63, 33   # the least capacity of specmi_png_encode; what specmi_png_header writes (include/specmi.h)
 # SPECMI_JPEG_* (include/specmi.h): what specmi_jpeg_probe answers, by value
@@ -262,6 +264,9 @@ PROTOTYPES = {
     # (h, x, B, Hp, Wp, index, H, W, mean3, std3, slab, slab_bytes, offset, pitch, stream)
     'specmi_denormalize_u8': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
                                         C.c_void_p, C.c_size_t, C.c_int64, C.c_int64, C.c_void_p]),
+    # in slab + bytes, out slab + bytes, frame_geom (n x 2), frame_offsets (n x 4), records (n x 8), nframes, stream
+    'specmi_color_jitter': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_int32_p, c_int64_p, c_int32_p, C.c_int,
+                                      C.c_void_p]),
     # (h, in_slab, in_bytes, out_slab, out_bytes, pic_geom, pic_offsets, n, quality, sizes, stream)
     'specmi_jpeg_encode': (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, c_int32_p, c_int64_p, C.c_int, C.c_int,
                                      C.c_void_p, C.c_void_p]),

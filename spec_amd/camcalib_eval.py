@@ -99,17 +99,22 @@ def val_dataset_name(hparams: dict) -> str:
 class PanoValDataset:
     """The ``is_train=False`` half of ``CameraRegressorDataset`` (camcalib/pano_dataset.py:48-144): ``val_images.pkl`` lists
     the file names under ``images/``; labels come from ``images/NAME.json`` ('pano_scalenet': vfov in radians, the image is
-    ``NAME.jpg``) or ``annotations/NAME.json`` ('pano': vfov in degrees, the image is ``NAME.png``)."""
+    ``NAME.jpg``) or ``annotations/NAME.json`` ('pano': vfov in degrees, the image is ``NAME.png``).  ``split='train'`` lists the
+    ``is_train=True`` half's frames instead (``train_images.pkl``, :63), read the same way; the ColorJitter that half applies is
+    ``spec_amd.augment.ColorJitter``, applied by the training flow where the batch lies."""
 
-    def __init__(self, name: str, data_root: str = '.', folder: Optional[str] = None):
+    def __init__(self, name: str, data_root: str = '.', folder: Optional[str] = None, split: str = 'val'):
         import joblib
+        if split not in ('val', 'train'):
+            raise ValueError(f"split {split!r}: 'val' (val_images.pkl) or 'train' (train_images.pkl)")
         if name == 'pano_agora':
             raise NotImplementedError("'pano_agora' needs AGORA's own files and is not built")
         if name not in DATASET_FOLDERS:
             raise ValueError(f'{name} is not implemented.')
         self.name = name
         self.folder = folder or os.path.join(data_root, DATASET_FOLDERS[name])
-        self.image_filenames = [str(f) for f in joblib.load(os.path.join(self.folder, 'val_images.pkl'))]
+        self.split = split
+        self.image_filenames = [str(f) for f in joblib.load(os.path.join(self.folder, f'{split}_images.pkl'))]
 
     def __len__(self):
         return len(self.image_filenames)

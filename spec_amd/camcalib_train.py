@@ -9,9 +9,14 @@ Per batch: ``DATASET.BATCH_SIZE`` frames in a seeded shuffle, resized and padded
 The targets come from ``camcalib_eval.encode_targets``.  The optimiser is torch's; forward, loss and both backwards run in the
 library (``specmi_camcalib_head_train_forward`` / ``_backward``, ``specmi_camcalib_loss`` / ``_backward``).
 
-Out of scope, as for the SPEC side: the backward of the trunk, BatchNorm in training mode, the
-reference's augmentation and its training datasets (the frames are those the tree's ``val_images.pkl`` lists, or a ``dataset``
-object with ``PanoValDataset``'s interface), second derivatives.
+``augment=True`` adds the one step by which the reference's training dataset differs from its validation half
+(camcalib/pano_dataset.py:62-78): ``ColorJitter(brightness=0.2, contrast=0.2, saturation=0.2, hue=0.1)`` on every frame before
+the resize, applied to the batch's uint8 slab on the device in Pillow's bytes (``spec_amd.augment``, ``specmi_color_jitter``).
+``split='train'`` reads the frames ``train_images.pkl`` lists instead of ``val_images.pkl``'s.
+
+Out of scope, as for the SPEC side: the backward of the trunk, BatchNorm in training mode, 'pano_agora'
+(the frames are those the tree's ``val_images.pkl`` / ``train_images.pkl`` list, or a ``dataset`` object with
+``PanoValDataset``'s interface), second derivatives.
 """
 from __future__ import annotations
 
@@ -56,11 +61,15 @@ def write_checkpoint(model, path: str, epoch: int, global_step: int) -> str:
 
 
 def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = None, epochs: int = 1, seed: int = 0, out: Optional[str] = None,
-                   dataset=None, model=None, log=print, device='cuda', evaluate: bool = True) -> dict:
+                   dataset=None, model=None, log=print, device='cuda', evaluate: bool = True, augment: bool = False, augment_seed: int = 0,
+                   split: str = 'val') -> dict:
     """Head-only fine-tuning (module docstring) for ``epochs`` passes over the labelled frames.  Logs the four ``train/...`` means
     per epoch, runs ``camcalib_eval.run_evaluation`` before and after (``evaluate``), and writes the Lightning-layout checkpoint
     ``out`` (None: ``LOG_DIR/camcalib_finetuned.ckpt``).  -> dict(model, ckpt, epochs = the per-epoch means, before / after = the
-    evaluations' four epoch figures)."""
+    evaluations' four epoch figures).  ``augment``: every batch is packed into a uint8 device slab (or taken as
+    ``device_batch`` hands it over), jittered by ``augment.ColorJitter`` with the reference's four settings - the parameters drawn
+    frame by frame from a torch CPU generator seeded with ``augment_seed`` - and resized from there; False: exactly the flow
+    without it.  ``split``: which list of the tree the training frames come from (the evaluations keep reading 'val')."""
     from .differentiable import CameraRegressorHead
     from .losses import CameraRegressorLoss
     dev = torch.device(device)
@@ -70,7 +79,7 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     opt_cfg = dict(DEFAULTS['OPTIMIZER'], **(hparams.get('OPTIMIZER') or {}))
     if str(opt_cfg['TYPE']).lower() != 'adam':
         raise NotImplementedError(f"OPTIMIZER.TYPE {opt_cfg['TYPE']!r}: the reference's configure_optimizers builds Adam (camcalib/trainer.py:201-205)")
-    ds = dataset if dataset is not None else ce.PanoValDataset(ce.val_dataset_name(hparams), data_root)
+    ds = dataset if dataset is not None else ce.PanoValDataset(ce.val_dataset_name(hparams), data_root, split=split)
     if model is None:
         model = ce.build_model(hparams, ckpt, data_root, dev)
     else:
@@ -85,6 +94,11 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     bs, min_res, max_res = int(hparams['DATASET']['BATCH_SIZE']), int(hparams['DATASET']['MIN_RES']), hparams['DATASET']['MAX_RES']
     rng = np.random.default_rng(seed)
     eng = model.engine(dev)
+    jitter = jitter_rng = None
+    if augment:
+        from .augment import CAMCALIB_TRAIN_JITTER, ColorJitter
+        from .preprocess import pack_frames
+        jitter, jitter_rng = ColorJitter(**CAMCALIB_TRAIN_JITTER), torch.Generator().manual_seed(int(augment_seed))
     log(f'Train dataset len: {len(ds)}')
     history, step = [], 0
     for epoch in range(int(epochs)):
@@ -95,6 +109,8 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
             idx = [int(i) for i in order[b0:b0 + bs]]
             frames = ds.device_batch(idx) if hasattr(ds, 'device_batch') else [ds.frame(i) for i in idx]
             gt = np.asarray([ds.labels(i) for i in idx], dtype=np.float64).T
+            if jitter is not None:
+                frames = jitter(frames if isinstance(frames, tuple) else pack_frames(frames, dev), jitter_rng, engine=eng)
             images = ce.pad_batch(frames, min_res, max_res, dev, eng)
             feat = trunk_features(model, images)
             with torch.enable_grad():

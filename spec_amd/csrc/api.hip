@@ -2125,6 +2125,70 @@ int specmi_denormalize_u8(specmi_handle* h, const float* x, int B, int Hp, int W
     return SPECMI_OK;
 }
 
+int specmi_color_jitter(specmi_handle* h, const uint8_t* in_slab, size_t in_slab_bytes, uint8_t* out_slab, size_t out_slab_bytes,
+                        const int32_t* frame_geom, const int64_t* frame_offsets, const int32_t* records, int nframes, void* stream) {
+    ENTER(h);
+    if (!in_slab || !out_slab || !frame_geom || !frame_offsets || !records) return fail(h, SPECMI_ERR_ARG, "bad argument (null pointer)");
+    if (nframes <= 0 || nframes > 65535) return fail(h, SPECMI_ERR_ARG, "1 to 65535 frames per call, got %d", nframes);
+    // in place = the same slab and every frame on its own rectangle; any other shared byte is refused
+    const bool in_place = in_slab == out_slab;
+    if (!in_place && slabs_overlap(in_slab, in_slab_bytes, out_slab, out_slab_bytes))
+        return fail(h, SPECMI_ERR_ARG, "the two slabs overlap without being the same (in place: the same pointer and rectangles)");
+    static_assert(sizeof(JitterFrame) == kJitterFrameRec * sizeof(int) && sizeof(JitterRec) == 8 * sizeof(int), "the frame records are kept as ints");
+    std::vector<int> tab((size_t)nframes * kJitterFrameRec, 0);
+    std::vector<ByteRect> rects((size_t)nframes);
+    long long tiles = 0, stiles = 0;
+    double px = 0.0, stat_px = 0.0;
+    for (int f = 0; f < nframes; ++f) {
+        const int H = frame_geom[2 * f], W = frame_geom[2 * f + 1];
+        const int64_t* o = frame_offsets + 4 * (size_t)f;
+        if (H < 1 || W < 1 || H > kJitterMaxSide || W > kJitterMaxSide)
+            return fail(h, SPECMI_ERR_ARG, "frame %d: %d x %d pixels (1 .. %d per side)", f, H, W, kJitterMaxSide);
+        if (int rc = check_rect(h, "frame", f, o[0], o[1], H, W, in_slab_bytes)) return rc;
+        if (int rc = check_rect(h, "frame (output)", f, o[2], o[3], H, W, out_slab_bytes)) return rc;
+        JitterFrame r{};
+        r.in_off = o[0]; r.in_pitch = stored_pitch(o[1], H, W); r.out_off = o[2]; r.out_pitch = stored_pitch(o[3], H, W);
+        if (in_place && (r.in_off != r.out_off || r.in_pitch != r.out_pitch))
+            return fail(h, SPECMI_ERR_ARG, "frame %d: in place, but its output rectangle is not its input rectangle", f);
+        r.H = H; r.W = W; r.tile0 = (int)tiles; r.stile0 = (int)stiles; r.npre = -1;
+        const int32_t* q = records + 8 * (size_t)f;
+        unsigned seen = 0;
+        for (int i = 0; i < 4; ++i) {
+            if (q[i] < -1 || q[i] > 3) return fail(h, SPECMI_ERR_ARG, "frame %d: operation id %d outside [-1, 3]", f, q[i]);
+            if (q[i] < 0) continue;
+            if (seen & (1u << q[i])) return fail(h, SPECMI_ERR_ARG, "frame %d: operation %d is named twice", f, q[i]);
+            seen |= 1u << q[i];
+            if (q[i] == kJitterContrast) r.npre = r.nops;
+            r.rec.op[r.nops++] = q[i];
+        }
+        for (int i = r.nops; i < 4; ++i) r.rec.op[i] = -1;
+        std::memcpy(r.rec.f, q + 4, sizeof(r.rec.f));
+        for (int i = 0; i < 3; ++i)
+            if (!std::isfinite(r.rec.f[i]) || r.rec.f[i] < 0.f) return fail(h, SPECMI_ERR_ARG, "frame %d: factor %d is negative or not finite", f, i);
+        if (q[7] < 0 || q[7] > 255) return fail(h, SPECMI_ERR_ARG, "frame %d: hue shift %d outside [0, 255]", f, q[7]);
+        r.rec.k = q[7];
+        const int n = jitter_frame_tiles(H, W, &r.tiles_x);
+        tiles += n; px += (double)H * W;
+        if (r.npre >= 0) { stiles += n; stat_px += (double)H * W; }
+        if (tiles >= 2147483648LL) return fail(h, SPECMI_ERR_ARG, "the frames hold 2^31 tiles of %d x %d pixels or more", kJitterTileW, kJitterTileH);
+        std::memcpy(tab.data() + (size_t)f * kJitterFrameRec, &r, sizeof(r));
+        rects[f] = ByteRect{r.out_off, r.out_pitch, 3LL * W, H};
+    }
+    int ra, rb;
+    if (first_overlap(rects, &ra, &rb)) return fail(h, SPECMI_ERR_ARG, "frames %d and %d share an output byte", ra, rb);
+    hipStream_t s = (hipStream_t)stream;
+    DevTable& T = h->tab[TAB_jitter];
+    DevBuf& sums = h->buf[BUF_jitter];
+    if (int rc = publish_table(h, T, tab, "the jitter frame table", "new frame or jitter records", s, &sums, (size_t)nframes * sizeof(unsigned long long),
+                               "the jitter sums"))
+        return rc;
+    JitterArgs a{};
+    a.frames = (const JitterFrame*)T.dev.p; a.in = in_slab; a.out = out_slab; a.sums = (unsigned long long*)sums.p; a.nframes = nframes;
+    LaunchCtx ctx{s, &h->prof, "preprocess.color_jitter"};
+    LAUNCHCHK(h, launch_color_jitter(a, (int)stiles, (int)tiles, stat_px, px, ctx), "color_jitter");
+    return SPECMI_OK;
+}
+
 // ---- what specmi_jpeg_encode and specmi_png_encode check alike, each part where both check it ------------------------------------
 struct EncodePic { int H, W; long long in_off, in_pitch, out_off, cap; };      // in_pitch as the records store it
 

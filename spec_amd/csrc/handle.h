@@ -139,6 +139,7 @@ enum Tab {
     TAB_png,        // specmi_png_encode: the picture records
     TAB_jdec,       // specmi_jpeg_decode: the file records with their tables
     TAB_pdec,       // specmi_png_decode: the file records
+    TAB_jitter,     // specmi_color_jitter: the frame records with their jitter records
     TAB_COUNT
 };
 
@@ -152,6 +153,7 @@ enum Buf {
     BUF_smpl_bwd,   // specmi_smpl_backward: smpl_bwd_ws_floats(V, B) floats
     BUF_head_train, // specmi_hmr_head_train_forward / specmi_hmr_head_backward: head_train_fwd_ws_floats / head_train_bwd_ws_floats floats
     BUF_cam_head_train, // specmi_camcalib_head_backward: cam_head_bwd_ws_floats floats
+    BUF_jitter,     // specmi_color_jitter: one 64-bit sum of L per frame
     BUF_COUNT
 };
 

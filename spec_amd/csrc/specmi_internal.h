@@ -729,6 +729,35 @@ struct DenormArgs {
 int launch_denormalize_u8(const DenormArgs& a, const LaunchCtx& ctx);
 
 // ----------------------------------------------------------------------------------------
+// torchvision's ColorJitter on the frames of a slab, in Pillow's bytes  (color_jitter.hip)
+// ----------------------------------------------------------------------------------------
+constexpr int kJitterBrightness = 0, kJitterContrast = 1, kJitterSaturation = 2, kJitterHue = 3;
+constexpr int kJitterMaxSide = 8192;
+constexpr int kJitterTileW = 256, kJitterTileH = 16;  // one 256-thread workgroup: four pixels of a row per thread, four rows in turn
+// THE JITTER RECORD of specmi_color_jitter as the caller writes it (include/specmi.h states the same), eight int32 words: the
+// ids of the operations in application order (-1: none), the fp32 factors of brightness, contrast and saturation, the hue shift.
+// The device reads the same layout with the ids packed to the front
+struct JitterRec { int op[4]; float f[3]; int k; };
+constexpr int kJitterRec = sizeof(JitterRec) / 4;
+// One frame as the device reads it (24 ints): its rectangle in each slab (byte offset, pitch), its size, its first tile among the
+// apply launch's and among the stat launch's (a frame without contrast has none there), its tiles per row, how many
+// operations it has and how many of them come before contrast (-1: no contrast)
+struct JitterFrame { long long in_off, in_pitch, out_off, out_pitch; int H, W, tile0, stile0, tiles_x, nops, npre, pad_; JitterRec rec; };
+constexpr int kJitterFrameRec = sizeof(JitterFrame) / 4;
+// One call as the kernels read it: frames = the handle's jitter table, sums = one 64-bit sum of L per frame (its workspace)
+struct JitterArgs {
+    const JitterFrame* frames;
+    const unsigned char* in;
+    unsigned char* out;
+    unsigned long long* sums;
+    int nframes;
+};
+// the tiles a frame of this size takes -> and its tiles per row
+int jitter_frame_tiles(int H, int W, int* tiles_x);
+// stat_tiles == 0: no frame has contrast, one launch
+int launch_color_jitter(const JitterArgs& a, int stat_tiles, int tiles, double stat_px, double px, const LaunchCtx& ctx);
+
+// ----------------------------------------------------------------------------------------
 // baseline JPEG encoder  (jpeg.hip)
 // ----------------------------------------------------------------------------------------
 constexpr int kJpegHeaderBytes = 623;

@@ -314,6 +314,51 @@ def check_draw_marks(geom, offsets, marks, slab_bytes, mask_bytes=0):
     return geom.astype(np.int32), offsets, marks
 
 
+def check_color_jitter(geom, offsets, records, in_bytes, out_bytes, in_place):
+    """Every refusal of ``specmi_color_jitter`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom`` (n, 2)
+    [H, W], ``offsets`` (n, 4) [in_offset, in_pitch, out_offset, out_pitch], ``records`` (n, 8) int32 [four operation ids in
+    application order (-1: none), the bits of the fp32 factors of brightness, contrast and saturation, the hue shift k], the sizes
+    of the two slabs and whether they are the same slab.  -> the arrays as the library reads them (int32, int64, int32).  Needs no
+    device."""
+    geom, offsets = np.ascontiguousarray(geom, dtype=np.int64), np.ascontiguousarray(offsets, dtype=np.int64)
+    records = np.ascontiguousarray(records)
+    n = geom.shape[0] if geom.ndim == 2 else -1
+    if geom.ndim != 2 or geom.shape[1] != 2 or tuple(offsets.shape) != (n, 4):
+        raise ValueError('frames: geom (n, 2) and offsets (n, 4) with one row per frame')
+    if records.dtype != np.int32 or tuple(records.shape) != (n, _lib.JITTER_REC):
+        raise ValueError(f'records: (n, {_lib.JITTER_REC}) int32 [four ids, three fp32 factors as bits, k]')
+    if not 1 <= n <= 65535:
+        raise ValueError(f'1 to 65535 frames per call, got {n}')
+    H, W = geom.T
+    in_off, in_pitch, out_off, out_pitch = offsets.T
+    if ((H < 1) | (H > _lib.JITTER_MAX_SIDE) | (W < 1) | (W > _lib.JITTER_MAX_SIDE)).any():
+        raise ValueError(f'a frame of 1 .. {_lib.JITTER_MAX_SIDE} pixels per side')
+    if (in_pitch < 3 * W).any() or (out_pitch < 3 * W).any():
+        raise ValueError('a pitch below 3 * W bytes')
+    if (in_off < 0).any() or (in_off + (H - 1) * in_pitch + 3 * W > in_bytes).any():
+        raise ValueError(f'a frame rectangle leaves the slab of {in_bytes} bytes')
+    if (out_off < 0).any() or (out_off + (H - 1) * out_pitch + 3 * W > out_bytes).any():
+        raise ValueError(f'an output rectangle leaves the slab of {out_bytes} bytes')
+    if in_place and ((in_off != out_off) | ((in_pitch != out_pitch) & (H > 1))).any():
+        raise ValueError('in place, but an output rectangle is not its input rectangle')
+    ids = records[:, :4]
+    if ((ids < -1) | (ids > 3)).any():
+        raise ValueError('an operation id outside [-1, 3]')
+    if any((ids == op).sum(axis=1).max() > 1 for op in range(4)):
+        raise ValueError('an operation is named twice')
+    factors = records[:, 4:7].view(np.float32)
+    if not (np.isfinite(factors).all() and (factors >= 0).all()):
+        raise ValueError('a factor is negative or not finite')
+    if ((records[:, 7] < 0) | (records[:, 7] > 255)).any():
+        raise ValueError('a hue shift outside [0, 255]')
+    if int((-(-H // 16) * -(-W // 256)).sum()) >= 1 << 31:
+        raise ValueError('the frames hold 2^31 tiles of 256 x 16 pixels or more')
+    pair = _first_overlap(_byte_rects(out_off, out_pitch, W, H))
+    if pair:
+        raise ValueError(f'frames {pair[0]} and {pair[1]} share an output byte')
+    return geom.astype(np.int32), offsets, records
+
+
 # Which route panel 0 of the pictures takes (render_image_group, render_image_groups, SPECTester, evaluation.save_batch_picture):
 # False = render.group_panel0 draws the horizon line and caption per frame on the host with Pillow - a download of a device
 # frame, a Pillow raster and an upload each (route (a)), True = uint8 frames go up raw and ONE specmi_draw_marks call per flush
@@ -1403,6 +1448,39 @@ class Engine:
             marks.ctypes.data_as(_lib.c_int64_p) if marks.shape[0] else None, int(marks.shape[0]), _ptr(masks),
             0 if masks is None else masks.numel(), self._stream()))
         return slab
+
+    def color_jitter(self, slab, offsets, sizes, records, out=None, out_offsets=None):
+        """``specmi_color_jitter``: torchvision's ColorJitter, in Pillow's bytes, on the frames of ``slab`` (1-D uint8 on the engine
+        device: what ``pack_frames``, the decoders and ``pano_extract_views`` build).  Host arrays: ``offsets`` (n,) byte offsets
+        of dense frames or (n, 2) [byte offset, pitch], ``sizes`` (n, 2) [H, W], ``records`` (n, 8) int32 (``augment.ColorJitter
+        .records``).  ``out``: the slab the jittered frames go to - None: a new slab of the same size, ``slab`` itself: in place -
+        at ``out_offsets`` (None: the same rectangles).  Returns ``out``.  Everything the host arrays decide is checked here,
+        before the library is called (``check_color_jitter``)."""
+        d = self.device
+        if out is None:
+            out = torch.empty_like(slab) if isinstance(slab, torch.Tensor) else None
+        for name, x in (('slab', slab), ('out', out)):
+            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
+                raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
+        sizes = np.ascontiguousarray(sizes, dtype=np.int64).reshape(-1, 2)
+
+        def pitched(o):
+            o = np.ascontiguousarray(o, dtype=np.int64)
+            if o.ndim == 1 and o.shape[0] == sizes.shape[0]:
+                o = np.stack([o, 3 * sizes[:, 1]], axis=1)
+            if o.ndim != 2 or o.shape != (sizes.shape[0], 2):
+                raise ValueError('offsets: (n,) byte offsets of dense frames or (n, 2) [byte offset, pitch]')
+            return o
+        in_o = pitched(offsets)
+        both = np.concatenate([in_o, in_o if out_offsets is None else pitched(out_offsets)], axis=1)
+        in_place = out.data_ptr() == slab.data_ptr()
+        if not in_place and slab.data_ptr() < out.data_ptr() + out.numel() and out.data_ptr() < slab.data_ptr() + slab.numel():
+            raise ValueError('slab and out overlap without being the same slab')
+        geom, both, records = check_color_jitter(sizes, both, records, slab.numel(), out.numel(), in_place)
+        _lib.check(self.h, self.lib.specmi_color_jitter(
+            self.h, _ptr(slab), slab.numel(), _ptr(out), out.numel(), geom.ctypes.data_as(_lib.c_int32_p), both.ctypes.data_as(_lib.c_int64_p),
+            records.ctypes.data_as(_lib.c_int32_p), int(geom.shape[0]), self._stream()))
+        return out
 
     def denormalize_u8(self, x, index, H, W, slab=None, offset=0, pitch=None, mean=None, std=None):
         """``specmi_denormalize_u8``: image ``index`` of ``x`` (B, 3, Hp, Wp) fp32 on the engine device, cut to its top-left
