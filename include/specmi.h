@@ -498,6 +498,48 @@ int specmi_camcalib_head_backward(specmi_handle* h, const specmi_camcalib_head_p
                                   int B, int F, int L, int Hc, int nbins, const float* tape, const float* g_logits, float* g_xf,
                                   const specmi_camcalib_head_grads* grads, void* stream);
 
+/* One fused ResNet layer for training, with its gradients (spec_amd/csrc/conv_bwd.hip; STABLE): specmi_conv2d's layer
+ *     y = act(conv(x, W) * scale + shift [+ residual])
+ * x (B, H, W, Cin), y / residual / g_y / g_res (B, OH, OW, Cout), g_x / g_x_add (B, H, W, Cin): dense NHWC fp32 on the device.
+ * w_oihw_dev is torch's own (Cout, Cin, KH, KW) fp32 tensor ON THE DEVICE, read in place at every call, and scale_dev / shift_dev
+ * are (Cout) device vectors - the frozen BatchNorm as an affine map: nothing is packed on the host, uploaded or committed, nothing of
+ * the handle's committed model is read and the stream is not synchronised.  Both calls work on a handle of any kind, committed or
+ * not.  Layer shapes: KH = KW = 1 with pad 0 and KH = KW = 3 with pad 1, stride 1 or 2; OH = (H + 2 pad - KH) / stride + 1; any
+ * B, H, W, Cin, Cout >= 1, tails in every dimension are handled in the kernel and no access leaves a tensor.
+ * specmi_conv2d_train_forward: Y[p, o] = sum_k X[gather(p, k)] W[o, k], k = (ky, kx, ci); padding taps contribute exact zeros;
+ *   then v = Y * scale[o] + shift[o] (+ residual), and max(v, 0) with relu != 0.  residual may be NULL.
+ * specmi_conv2d_backward: the forward's x, w, scale, its output y (read only with relu != 0: may be NULL otherwise) and g_y ->
+ *     g_z = relu ? (y > 0 ? g_y : 0) : g_y        (torch's convention: an output that is exactly zero passes no gradient)
+ *     G = g_z * scale[o]
+ *     g_res = g_z                                                                        the gradient of the residual
+ *     g_x[q, ci] = sum_k G[scatter^-1(q, k)] W[k, ci] (+ g_x_add[q, ci]),  k = (ky, kx, o)
+ *     g_w[o, ci, ky, kx] = sum_p G[p, o] X[gather(p, ky, kx), ci],         p = the output pixels in (b, oy, ox) order
+ *   g_x, g_w (OIHW, dense) and g_res may be NULL (not wanted), but not all of them.  g_x_add may be NULL, and may be g_x itself
+ *   (a block's skip gradient summed in place: an element is read and written by the same lane); it is not read with g_x NULL.
+ * Every product runs on the exact-fp32 matrix instruction as an implicit GEMM.  Deterministic: no float atomics, the order of
+ * every sum is fixed by the layer's shape; two runs give the same bits; image b's y, g_x and g_res have the same bits in any
+ * batch; g_w depends on the shapes alone; a wanted output has the same bits whatever else is wanted; with g_w NULL no
+ * weight-gradient product is launched, with g_x NULL no data-gradient product.
+ * Workspace: Cout Cin KH KW floats for the forward (the weights transposed on the device at every call to [tap][ci][o], so that a
+ * column tile's lanes read contiguous bytes; counted in the call's time) and B OH OW Cout floats (G) for the backward, in the handle; it grows on the first call of a shape, afterwards nothing
+ * is allocated and the calls can be captured into a graph.
+ * Refusals (SPECMI_ERR_ARG with a message, nothing launched, no output written): x, w, scale, shift, y (forward) or g_y NULL; every
+ * output NULL; y NULL with relu (backward); a layer shape other than the four above; a dimension < 1; a tensor of the layer with
+ * 2^31 elements or more; a float pointer that is not 4-byte aligned. */
+int specmi_conv2d_train_forward(specmi_handle* h, const float* x, int B, int H, int W, int Cin, const float* w_oihw_dev,
+                                const float* scale_dev, const float* shift_dev, int Cout, int KH, int KW, int stride, int pad,
+                                const float* residual, int relu, float* y, void* stream);
+int specmi_conv2d_backward(specmi_handle* h, const float* x, int B, int H, int W, int Cin, const float* w_oihw_dev,
+                           const float* scale_dev, int Cout, int KH, int KW, int stride, int pad, const float* y, int relu,
+                           const float* g_y, const float* g_x_add, float* g_x, float* g_w, float* g_res, void* stream);
+
+/* The frozen part of a fine-tuning step (STABLE): the committed fp32 ResNet trunk's own op list up to the last op of
+ * layer{n_stages}, n_stages in 1 .. 4, whose block output goes NHWC to `out` ((B, h, w, C): stride 4, 8, 16, 32 and 256, 512,
+ * 1024, 2048 channels for a Bottleneck trunk).  The same kernels, plan and k order as specmi_trunk_forward: with n_stages = 4 `out`
+ * has specmi_trunk_forward's bits.  An HRNet trunk and the fp16 trunk are refused with SPECMI_ERR_STATE. */
+int specmi_trunk_forward_stages(specmi_handle* h, const float* images_nchw, int B, int H, int W, int n_stages, float* out,
+                                void* stream);
+
 /* The body model WITHOUT the 49-joint wrapper - smplx.SMPL.forward as the evaluation code calls it (`smpl_native` /
  * `body_model` / `body_model_orig`, spec/trainer.py:71-86,249-254, spec/utils/compute_error.py:118-160): `pose` is
  * (B,24,3,3) rotation matrices (pose2rot=False) or, with pose_is_axis_angle != 0, (B,72) axis-angle vectors

@@ -1339,12 +1339,115 @@ def camcalib_train_section(a):
     return out
 
 
+def conv_backward_section(a):
+    """The trainable ResNet layer (``specmi_conv2d_train_forward`` / ``specmi_conv2d_backward``, spec_amd/csrc/conv_bwd.hip) on every
+    distinct layer4 layer of ResNet-50 at CamCalib's fine-tuning shape (batch ``DATASET.BATCH_SIZE`` = 64, the stage-3 map of a
+    600 x 1000 frame, 38 x 63) and at SPEC's (B = 64, a 14 x 14 stage-3 map, 7 x 7 out): forward, data gradient and weight gradient,
+    each next to torch's own ``aten.convolution`` / ``aten.convolution_backward`` (MIOpen) on the same device tensors (NHWC memory,
+    OIHW weights), alternated in this process, 3 rounds of ``iters`` back-to-back calls after a warm-up; then the library's kernels by
+    its profiler; then the whole fine-tuning step with layer4 unfrozen against the head-only step."""
+    from spec_amd import camcalib_eval as ce
+    from spec_amd.cam_utils import _engine
+    dev = torch.device('cuda', 0)
+    eng = _engine(dev)
+    bs = int(ce.DEFAULTS['DATASET']['BATCH_SIZE'])
+    layers = [('0.conv1', 1024, 512, 1, 1, 0), ('0.conv2', 512, 512, 3, 2, 0), ('0.downsample', 1024, 2048, 1, 2, 0),
+              ('n.conv3', 512, 2048, 1, 1, 1), ('1.conv1', 2048, 512, 1, 1, 1), ('1.conv2', 512, 512, 3, 1, 1)]     # last: 1 = on the stage's output map
+    shapes = {'camcalib_b%d_38x63' % bs: (bs, 38, 63), 'spec_b64_14x14': (64, 14, 14)}
+
+    def ms_per_call(fn):
+        for _ in range(3):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+    out = {}
+    for sname, (B, h, w) in shapes.items():
+        for lname, cin, cout, k, stride, on_out in layers:
+            H, W = ((h + 1) // 2, (w + 1) // 2) if on_out else (h, w)
+            pad = k // 2
+            torch.manual_seed(cin + cout + k + stride)
+            x = torch.randn(B, H, W, cin, device=dev)
+            wt = torch.randn(cout, cin, k, k, device=dev) / float(np.sqrt(cin * k * k))
+            scale, shift = 0.5 + torch.rand(cout, device=dev), 0.3 * torch.randn(cout, device=dev)
+            relu = lname != '0.downsample'
+            y = eng.conv2d_train_forward(x, wt, scale, shift, stride, pad, None, relu)
+            g_y = torch.randn_like(y)
+            xn, gn = x.permute(0, 3, 1, 2), g_y.permute(0, 3, 1, 2)             # channels_last views of the same memory
+            conv = lambda: torch.ops.aten.convolution(xn, wt, None, [stride] * 2, [pad] * 2, [1, 1], False, [0, 0], 1)
+            bwd = lambda mask: (lambda: torch.ops.aten.convolution_backward(gn, xn, wt, None, [stride] * 2, [pad] * 2, [1, 1], False, [0, 0], 1, mask))
+            lib_bwd = lambda want: (lambda: eng.conv2d_backward(x, wt, scale, stride, pad, y, g_y, relu, None, want))
+            calls = {'forward': (lambda: eng.conv2d_train_forward(x, wt, scale, shift, stride, pad, None, relu), conv),
+                     'dgrad': (lib_bwd((True, False, False)), bwd([True, False, False])),
+                     'wgrad': (lib_bwd((False, True, False)), bwd([False, True, False]))}
+            rounds = {p: {'library': [], 'torch': []} for p in calls}
+            for _ in range(3):                                          # alternated: both see the same clocks and the same neighbours
+                for p, (mine, theirs) in calls.items():
+                    rounds[p]['library'].append(ms_per_call(mine))
+                    rounds[p]['torch'].append(ms_per_call(theirs))
+            kern = timed(eng, lambda: (calls['forward'][0](), eng.conv2d_backward(x, wt, scale, stride, pad, y, g_y, relu, None, (True, True, True))),
+                         a.iters)
+            row = {'workload': f'B = {B}, {H} x {W} x {cin} -> {cout}, {k}x{k} stride {stride}' + (', relu' if relu else ''),
+                   'kernels_by_the_library_profiler': {kk: {'ms_per_launch': round(v[0], 5), 'TFLOPs': round(v[2] / (v[0] * 1e-3) / 1e12, 2) if v[2] else None}
+                                                       for kk, v in kern.items()}}
+            for p in calls:
+                lib, tor = float(np.median(rounds[p]['library'])), float(np.median(rounds[p]['torch']))
+                row[p] = {'library_ms': round(lib, 5), 'torch_ms': round(tor, 5), 'library_over_torch': round(lib / tor, 3),
+                          'library_rounds_ms': [round(v, 5) for v in rounds[p]['library']], 'torch_rounds_ms': [round(v, 5) for v in rounds[p]['torch']]}
+            out[f'{sname}.layer4.{lname}'] = row
+            print(sname, lname, {p: (row[p]['library_ms'], row[p]['torch_ms']) for p in calls}, flush=True)
+            del x, wt, y, g_y, xn, gn
+    # the whole step: stages=3 under no_grad -> ResNetStage -> heads -> loss -> backward -> Adam, against the head-only step
+    from spec_amd import synth
+    from spec_amd.camcalib_train import trunk_features
+    from spec_amd.differentiable import CameraRegressorHead, ResNetStage
+    from spec_amd.losses import CameraRegressorLoss
+    from spec_amd.modules import CameraRegressorNetwork
+    net = CameraRegressorNetwork()
+    net.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in synth.camcalib_state(1001).items()}, strict=False)
+    net = net.to(dev).eval()
+    net.set_plan('throughput')
+    net.commit(dev, freeze=True)
+    images = torch.randn(bs, 3, 600, 1000, device=dev)
+    targets = [torch.randint(0, 256, (bs,), device=dev) for _ in range(3)]
+    head, stage, crit = CameraRegressorHead.from_model(net), ResNetStage.from_model(net, 'layer4'), CameraRegressorLoss(1.0, 1.0, 1.0, 'ce')
+    opts = {'head_only': torch.optim.Adam(head.parameters(), lr=1e-6), 'unfreeze_layer4': torch.optim.Adam(list(head.parameters()) + stage.conv_parameters(), lr=1e-6)}
+
+    def step(which):
+        def run():
+            feat = trunk_features(net, images, stages=3 if which == 'unfreeze_layer4' else None)
+            with torch.enable_grad():
+                if which == 'unfreeze_layer4':
+                    feat = stage(feat)
+                loss, _ = crit(*head(feat, channels_last=True), *targets)
+                opts[which].zero_grad(set_to_none=True)
+                loss.backward()
+            opts[which].step()
+        return run
+    rounds = {k: [] for k in opts}
+    for _ in range(3):
+        for k in opts:
+            rounds[k].append(ms_per_call(step(k)))
+    med = {k: float(np.median(v)) for k, v in rounds.items()}
+    out['whole_step'] = {'workload': f'ResNet-50 CamCalib, B = {bs} frames of 600 x 1000, ce loss, Adam: frozen trunk -> [layer4 with gradients] -> heads -> loss -> '
+                         'backward -> step', 'ms_round_values': {k: [round(x, 3) for x in v] for k, v in rounds.items()},
+                         'ms_median': {k: round(v, 3) for k, v in med.items()}, 'unfreeze_over_head_only': round(med['unfreeze_layer4'] / med['head_only'], 3)}
+    print(json.dumps(out['whole_step'], indent=1))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'color_jitter', 'smpl_backward', 'head_train', 'camcalib_train'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'color_jitter', 'smpl_backward', 'head_train', 'camcalib_train', 'conv_backward'], default=None, help='run one section only')
     ap.add_argument('--smpl-backward', dest='only', action='store_const', const='smpl_backward', help='the same as --only smpl_backward')
     ap.add_argument('--head-train', dest='only', action='store_const', const='head_train', help='the same as --only head_train')
     ap.add_argument('--camcalib-train', dest='only', action='store_const', const='camcalib_train', help='the same as --only camcalib_train')
+    ap.add_argument('--conv-backward', dest='only', action='store_const', const='conv_backward',
+                    help='the same as --only conv_backward (writes profiles/conv_backward_aux.json unless --out is given)')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -1387,6 +1490,18 @@ def main():
         with open(a.out, 'w') as f:
             json.dump({'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the same calls; 3 alternated rounds; '
                        'kernels: per-launch HIP events (library profiler)', 'camcalib_train': row, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'conv_backward':
+        from spec_amd import _lib
+        row = conv_backward_section(a)
+        path = a.out if a.out != ap.get_default('out') else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                                                         'conv_backward_aux.json')
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, 'w') as f:
+            json.dump({'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the same calls; library and torch '
+                       'alternated, 3 rounds, medians; kernels: per-launch HIP events (library profiler)', 'conv_backward': row,
+                       'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     def add(name, workload, res, per_unit=None):

@@ -44,6 +44,8 @@ def main():
     ap.add_argument('--augment', action='store_true', help="the reference's training ColorJitter on every frame, on the device")
     ap.add_argument('--augment-seed', type=int, default=0, help='seed of the jitter parameters')
     ap.add_argument('--train-split', action='store_true', help='train on the frames train_images.pkl lists (default: val_images.pkl)')
+    ap.add_argument('--unfreeze', nargs='*', default=[], choices=['layer4'], metavar='STAGE',
+                    help="also train the conv weights of this ResNet stage on frozen BatchNorm ('layer4' is the one built)")
     ap.add_argument('--report', type=str, default=None, metavar='train.json')
     args = ap.parse_args()
     from spec_amd import camcalib_eval as ce
@@ -59,7 +61,8 @@ def main():
         from spec_amd import panorama
         dataset = panorama.PanoViewDataset(panorama.list_panoramas(args.panoramas), args.views_per_pano, args.seed)
     res = ct.finetune_heads(hp, data_root=root, ckpt=args.ckpt, epochs=args.epochs, seed=args.seed, out=args.out, dataset=dataset,
-                            augment=args.augment, augment_seed=args.augment_seed, split='train' if args.train_split else 'val')
+                            augment=args.augment, augment_seed=args.augment_seed, split='train' if args.train_split else 'val',
+                            unfreeze=tuple(args.unfreeze))
     if args.report:
         with open(args.report, 'w') as f:
             json.dump({k: res[k] for k in ('ckpt', 'epochs', 'before', 'after')}, f, indent=1)

@@ -175,6 +175,14 @@ PROTOTYPES = {
     # (h, params, xf, ld_xf, B, F, L, Hc, nbins, tape, g_logits, g_xf, grads, stream)
     'specmi_camcalib_head_backward': (C.c_int, [C.c_void_p, C.POINTER(CamcalibHeadParams), C.c_void_p, C.c_int64] + [C.c_int] * 5 +
                                       [C.c_void_p] * 3 + [C.POINTER(CamcalibHeadParams), C.c_void_p]),
+    # (h, x, B, H, W, Cin, w, scale, shift, Cout, KH, KW, stride, pad, residual, relu, y, stream)
+    'specmi_conv2d_train_forward': (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3 + [C.c_int] * 5 +
+                                    [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    # (h, x, B, H, W, Cin, w, scale, Cout, KH, KW, stride, pad, y, relu, g_y, g_x_add, g_x, g_w, g_res, stream)
+    'specmi_conv2d_backward': (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] * 5 +
+                               [C.c_void_p, C.c_int] + [C.c_void_p] * 6),
+    # (h, images, B, H, W, n_stages, out, stream)
+    'specmi_trunk_forward_stages': (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     'specmi_conv2d': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                 C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -1,4 +1,4 @@
-"""Head-only fine-tuning of CamCalib on MI355X: the reference's ``training_step`` (camcalib/trainer.py:60-82 - network ->
+"""Fine-tuning of CamCalib on MI355X - the heads, or the heads and the last ResNet stage: the reference's ``training_step`` (camcalib/trainer.py:60-82 - network ->
 ``CameraRegressorLoss`` -> ``loss.backward()`` -> ``torch.optim.Adam``, :201-205) on a FROZEN, committed trunk.  What is trained are
 the three FC heads (``fc_vfov`` / ``fc_pitch`` / ``fc_roll``) on the trunk's pooled features - what adapting the released
 checkpoint to one's own cameras needs, with labelled views such as ``spec_amd.panorama`` cuts out of panoramas.
@@ -14,7 +14,14 @@ library (``specmi_camcalib_head_train_forward`` / ``_backward``, ``specmi_camcal
 the resize, applied to the batch's uint8 slab on the device in Pillow's bytes (``spec_amd.augment``, ``specmi_color_jitter``).
 ``split='train'`` reads the frames ``train_images.pkl`` lists instead of ``val_images.pkl``'s.
 
-Out of scope, as for the SPEC side: the backward of the trunk, BatchNorm in training mode, 'pano_agora'
+``unfreeze=('layer4',)`` trains the last ResNet stage with the heads, the usual recipe for adapting a released checkpoint: the
+frozen part is ``Engine.trunk(images, stages=3)`` under ``no_grad``, then ``differentiable.ResNetStage`` (layer4 on FROZEN BatchNorm
+statistics, sharing the model's conv weights; ``specmi_conv2d_train_forward`` / ``specmi_conv2d_backward``) -> the heads -> the loss
+-> ``backward()``, and Adam steps the head parameters and the stage's conv weights.  The written checkpoint holds the stepped trunk
+weights and the after-evaluation runs on the recommitted model.
+
+Out of scope, as for the SPEC side: the backward of the stem and of layers 1-3 (through a max-pool backward),
+BatchNorm in training mode (batch statistics; gamma / beta stay as they are), an fp16 backward, 'pano_agora'
 (the frames are those the tree's ``val_images.pkl`` / ``train_images.pkl`` list, or a ``dataset`` object with
 ``PanoValDataset``'s interface), second derivatives.
 """
@@ -40,16 +47,18 @@ def load_config(cfg_path: Optional[str], opts: Optional[List[str]] = None) -> di
     return evaluation.load_config(cfg_path, opts, defaults=DEFAULTS)
 
 
-def trunk_features(model, images: torch.Tensor) -> torch.Tensor:
+def trunk_features(model, images: torch.Tensor, stages: Optional[int] = None) -> torch.Tensor:
     """The frozen trunk on one padded batch -> (n, fh, fw, C) NHWC features, whole images in sub-batches of
-    ``camcalib_eval.forward_limit`` (bit-identical under the pinned plan)."""
+    ``camcalib_eval.forward_limit`` (bit-identical under the pinned plan).  ``stages``: the trunk cut after that stage
+    (``Engine.trunk``)."""
     eng = model.engine(images.device)
     n, _, H, W = images.shape
     step = ce.forward_limit(H, W)
+    kw = {} if stages is None else {'stages': stages}
     with torch.no_grad():
         if step >= n:
-            return eng.trunk(images)
-        return torch.cat([eng.trunk(images[b0:b0 + step]) for b0 in range(0, n, step)])
+            return eng.trunk(images, **kw)
+        return torch.cat([eng.trunk(images[b0:b0 + step], **kw) for b0 in range(0, n, step)])
 
 
 def write_checkpoint(model, path: str, epoch: int, global_step: int) -> str:
@@ -62,15 +71,21 @@ def write_checkpoint(model, path: str, epoch: int, global_step: int) -> str:
 
 def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = None, epochs: int = 1, seed: int = 0, out: Optional[str] = None,
                    dataset=None, model=None, log=print, device='cuda', evaluate: bool = True, augment: bool = False, augment_seed: int = 0,
-                   split: str = 'val') -> dict:
-    """Head-only fine-tuning (module docstring) for ``epochs`` passes over the labelled frames.  Logs the four ``train/...`` means
+                   split: str = 'val', unfreeze=()) -> dict:
+    """Fine-tuning (module docstring) for ``epochs`` passes over the labelled frames.  Logs the four ``train/...`` means
     per epoch, runs ``camcalib_eval.run_evaluation`` before and after (``evaluate``), and writes the Lightning-layout checkpoint
     ``out`` (None: ``LOG_DIR/camcalib_finetuned.ckpt``).  -> dict(model, ckpt, epochs = the per-epoch means, before / after = the
     evaluations' four epoch figures).  ``augment``: every batch is packed into a uint8 device slab (or taken as
     ``device_batch`` hands it over), jittered by ``augment.ColorJitter`` with the reference's four settings - the parameters drawn
     frame by frame from a torch CPU generator seeded with ``augment_seed`` - and resized from there; False: exactly the flow
-    without it.  ``split``: which list of the tree the training frames come from (the evaluations keep reading 'val')."""
-    from .differentiable import CameraRegressorHead
+    without it.  ``split``: which list of the tree the training frames come from (the evaluations keep reading 'val').
+    ``unfreeze``: ``()`` trains the heads alone; ``('layer4',)`` also the conv weights of the last ResNet stage on frozen BatchNorm
+    (the only other value built)."""
+    from .differentiable import CameraRegressorHead, ResNetStage
+    unfreeze = tuple(unfreeze)
+    if unfreeze not in ((), ('layer4',)):
+        raise NotImplementedError(f"unfreeze = {unfreeze!r}: () and ('layer4',) are built (DESIGN.md section 6: the stem and layers 1-3 need "
+                                  'a max-pool backward)')
     from .losses import CameraRegressorLoss
     dev = torch.device(device)
     m = hparams['MODEL']
@@ -90,7 +105,8 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     before = run_eval() if evaluate else None
     head = CameraRegressorHead.from_model(model)
     crit = CameraRegressorLoss(float(m['LOSS_VFOV_WEIGHT']), float(m['LOSS_PITCH_WEIGHT']), float(m['LOSS_ROLL_WEIGHT']), m['LOSS_TYPE'])
-    optim = torch.optim.Adam(head.parameters(), lr=float(opt_cfg['LR']), weight_decay=float(opt_cfg['WD']))
+    stage = ResNetStage.from_model(model, 'layer4') if unfreeze else None
+    optim = torch.optim.Adam(list(head.parameters()) + (stage.conv_parameters() if stage is not None else []), lr=float(opt_cfg['LR']), weight_decay=float(opt_cfg['WD']))
     bs, min_res, max_res = int(hparams['DATASET']['BATCH_SIZE']), int(hparams['DATASET']['MIN_RES']), hparams['DATASET']['MAX_RES']
     rng = np.random.default_rng(seed)
     eng = model.engine(dev)
@@ -112,8 +128,10 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
             if jitter is not None:
                 frames = jitter(frames if isinstance(frames, tuple) else pack_frames(frames, dev), jitter_rng, engine=eng)
             images = ce.pad_batch(frames, min_res, max_res, dev, eng)
-            feat = trunk_features(model, images)
+            feat = trunk_features(model, images, stages=3 if stage is not None else None)
             with torch.enable_grad():
+                if stage is not None:
+                    feat = stage(feat)
                 loss, loss_dict = crit(*head(feat, channels_last=True), *ce.encode_targets(*gt, m['LOSS_TYPE']))
                 optim.zero_grad(set_to_none=True)
                 loss.backward()
@@ -124,7 +142,7 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         means = (sums / max(nb, 1)).cpu().tolist()
         history.append(dict(zip(TRAIN_KEYS, (float(v) for v in means))))
         log(f'[EPOCH {epoch}] ' + ', '.join(f'{k}: {v:.6g}' for k, v in history[-1].items()))
-    model.commit(dev, freeze=True)            # the frozen model skips the per-forward check: commit the stepped heads now
+    model.commit(dev, freeze=True)            # the frozen model skips the per-forward check: commit the stepped weights now
     after = run_eval() if evaluate else None
     if out is None:
         log_dir = hparams['LOG_DIR'] if os.path.isabs(hparams['LOG_DIR']) else os.path.join(data_root, hparams['LOG_DIR'])

@@ -589,7 +589,7 @@ static int run_trunk_f16(specmi_handle* h, const float* images, const void* imag
 // resident in the 256 MiB Infinity Cache between layers); later stages see the whole batch.
 // images16 (NHWC8 fp16, include/specmi.h) in place of images: the fp16 ResNet trunk only; refused before anything is allocated or launched.
 static int run_trunk(specmi_handle* h, const float* images, int B, int H, int W, float* feat_out, const float** feat,
-                     int* fh, int* fw, hipStream_t s, const void* images16 = nullptr) {
+                     int* fh, int* fw, hipStream_t s, const void* images16 = nullptr, int n_stages = 4) {
     int rc;
     if (images16) {
         if (h->hrnet) return fail(h, SPECMI_ERR_STATE, "fp16 NHWC8 images feed the fp16 ResNet trunk: this handle has an HRNet trunk");
@@ -607,6 +607,14 @@ static int run_trunk(specmi_handle* h, const float* images, int B, int H, int W,
     if (h->committed_precision == SPECMI_PRECISION_FP16) return run_trunk_f16(h, images, images16, B, H, W, feat_out, feat, fh, fw, s);
     TrunkPlan P;
     plan_trunk(h, H, W, feat_out != nullptr, P);
+    if (n_stages < 4) {
+        // specmi_trunk_forward_stages: the same list cut after the last op of layer{n_stages}, which writes the caller's buffer
+        size_t n = 0;
+        while (n < P.ops.size() && P.stage_of[n] <= n_stages) ++n;
+        P.ops.resize(n); P.stage_of.resize(n);
+        P.ops.back().out_buf = -2;
+        P.final_buf = -2; P.fh = P.ops.back().OH; P.fw = P.ops.back().OW;
+    }
     const std::vector<TrunkOp>& ops = P.ops;
     const std::vector<int>& stage_of = P.stage_of;
     const int final_buf = P.final_buf, ch = P.fh, cw = P.fw;
@@ -940,6 +948,20 @@ static int trunk_forward(specmi_handle* h, const float* images, const void* imag
 
 int specmi_trunk_forward(specmi_handle* h, const float* images, int B, int H, int W, float* feat, void* stream) {
     return trunk_forward(h, images, nullptr, B, H, W, feat, stream);
+}
+
+int specmi_trunk_forward_stages(specmi_handle* h, const float* images, int B, int H, int W, int n_stages, float* out, void* stream) {
+    ENTER(h); NEED_COMMIT(h);
+    if (!images || !out || B <= 0) return fail(h, SPECMI_ERR_ARG, "bad argument");
+    if (n_stages < 1 || n_stages > 4) return fail(h, SPECMI_ERR_ARG, "trunk_forward_stages: n_stages = %d must be in 1 .. 4", n_stages);
+    if (h->hrnet) return fail(h, SPECMI_ERR_STATE, "trunk_forward_stages: the handle has an HRNet trunk, which has no layer1 .. layer4");
+    if (h->committed_precision == SPECMI_PRECISION_FP16)
+        return fail(h, SPECMI_ERR_STATE, "trunk_forward_stages: the fp16 trunk is not cut into stages (commit at fp32)");
+    if (h->blocks.empty()) return fail(h, SPECMI_ERR_STATE, "trunk_forward_stages: the handle has no ResNet trunk");
+    const float* f; int fh, fw;
+    const int rc = run_trunk(h, images, B, H, W, out, &f, &fh, &fw, (hipStream_t)stream, nullptr, n_stages);
+    if (rc) reset_sync_state(h, (hipStream_t)stream);
+    return rc;
 }
 
 int specmi_trunk_forward_f16in(specmi_handle* h, const void* images_nhwc8, int B, int H, int W, float* feat, void* stream) {
@@ -2936,6 +2958,65 @@ int specmi_camcalib_head_backward(specmi_handle* h, const specmi_camcalib_head_p
         if (int rc = grow_ragged(h, h->buf[BUF_cam_head_train], cam_head_bwd_ws_floats(B, L, Hc) * 4, "the CamCalib head training workspace")) return rc;
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, "camcalib.head_backward"};
     LAUNCHCHK(h, launch_cam_head_backward(a, tape, g_logits, g_xf, g, (float*)h->buf[BUF_cam_head_train].p, ctx), "camcalib_head_backward");
+    return SPECMI_OK;
+}
+
+// the argument checks specmi_conv2d_train_forward and specmi_conv2d_backward share, and the kernels' argument block
+static int conv_train_args(specmi_handle* h, const char* who, const float* x, int B, int H, int W, int Cin, const float* w, const float* scale,
+                           int Cout, int KH, int KW, int stride, int pad, ConvTrainArgs& t) {
+    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1)
+        return fail(h, SPECMI_ERR_ARG, "%s: every dimension must be >= 1 (B = %d, H = %d, W = %d, Cin = %d, Cout = %d)", who, B, H, W, Cin, Cout);
+    const bool k1 = KH == 1 && KW == 1 && pad == 0, k3 = KH == 3 && KW == 3 && pad == 1;
+    if (!(k1 || k3) || (stride != 1 && stride != 2))
+        return fail(h, SPECMI_ERR_ARG, "%s: the layers built are 1x1 pad 0 and 3x3 pad 1 at stride 1 or 2 (KH = %d, KW = %d, stride = %d, pad = %d)",
+                    who, KH, KW, stride, pad);
+    const int OH = conv_out(H, KH, stride, pad), OW = conv_out(W, KW, stride, pad);
+    const double lim = 2147483648.0;
+    if ((double)B * H * W * Cin >= lim || (double)B * OH * OW * Cout >= lim || (double)Cout * Cin * KH * KW >= lim || (double)B * H * W >= lim)
+        return fail(h, SPECMI_ERR_ARG, "%s: a tensor of this layer has 2^31 elements or more", who);
+    if (!x || !w || !scale) return fail(h, SPECMI_ERR_ARG, "%s: x, w or scale is NULL", who);
+    t = ConvTrainArgs{x, w, scale, nullptr, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad};
+    return SPECMI_OK;
+}
+
+static bool misaligned4(std::initializer_list<const void*> ps) {
+    for (const void* p : ps)
+        if (reinterpret_cast<uintptr_t>(p) & 3) return true;
+    return false;
+}
+
+int specmi_conv2d_train_forward(specmi_handle* h, const float* x, int B, int H, int W, int Cin, const float* w_oihw_dev, const float* scale_dev,
+                                const float* shift_dev, int Cout, int KH, int KW, int stride, int pad, const float* residual, int relu,
+                                float* y, void* stream) {
+    ENTER(h);
+    ConvTrainArgs t;
+    if (int rc = conv_train_args(h, "conv2d_train_forward", x, B, H, W, Cin, w_oihw_dev, scale_dev, Cout, KH, KW, stride, pad, t)) return rc;
+    if (!shift_dev || !y) return fail(h, SPECMI_ERR_ARG, "conv2d_train_forward: shift or y is NULL");
+    if (misaligned4({x, w_oihw_dev, scale_dev, shift_dev, residual, y}))
+        return fail(h, SPECMI_ERR_ARG, "conv2d_train_forward: a float pointer is not 4-byte aligned");
+    t.shift = shift_dev;
+    if (int rc = grow_ragged(h, h->buf[BUF_conv_fwd], conv_fwd_ws_floats(t) * 4, "the convolution training workspace")) return rc;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "conv.train_forward"};
+    LAUNCHCHK(h, launch_conv_train_forward(t, residual, relu != 0, y, (float*)h->buf[BUF_conv_fwd].p, ctx), "conv2d_train_forward");
+    return SPECMI_OK;
+}
+
+int specmi_conv2d_backward(specmi_handle* h, const float* x, int B, int H, int W, int Cin, const float* w_oihw_dev, const float* scale_dev,
+                           int Cout, int KH, int KW, int stride, int pad, const float* y, int relu, const float* g_y, const float* g_x_add,
+                           float* g_x, float* g_w, float* g_res, void* stream) {
+    ENTER(h);
+    ConvTrainArgs t;
+    if (int rc = conv_train_args(h, "conv2d_backward", x, B, H, W, Cin, w_oihw_dev, scale_dev, Cout, KH, KW, stride, pad, t)) return rc;
+    if (!g_y) return fail(h, SPECMI_ERR_ARG, "conv2d_backward: g_y is NULL");
+    if (relu && !y) return fail(h, SPECMI_ERR_ARG, "conv2d_backward: relu needs y (the mask is y > 0)");
+    if (!g_x && !g_w && !g_res) return fail(h, SPECMI_ERR_ARG, "conv2d_backward: every output is NULL");
+    if (misaligned4({x, w_oihw_dev, scale_dev, y, g_y, g_x_add, g_x, g_w, g_res}))
+        return fail(h, SPECMI_ERR_ARG, "conv2d_backward: a float pointer is not 4-byte aligned");
+    if (g_x || g_w)
+        if (int rc = grow_ragged(h, h->buf[BUF_conv_bwd], conv_bwd_ws_floats(t) * 4, "the convolution backward workspace")) return rc;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "conv.backward"};
+    LAUNCHCHK(h, launch_conv_backward(t, y, relu != 0, g_y, g_x ? g_x_add : nullptr, g_x, g_w, g_res, (float*)h->buf[BUF_conv_bwd].p, ctx),
+              "conv2d_backward");
     return SPECMI_OK;
 }
 

@@ -154,6 +154,8 @@ enum Buf {
     BUF_head_train, // specmi_hmr_head_train_forward / specmi_hmr_head_backward: head_train_fwd_ws_floats / head_train_bwd_ws_floats floats
     BUF_cam_head_train, // specmi_camcalib_head_backward: cam_head_bwd_ws_floats floats
     BUF_jitter,     // specmi_color_jitter: one 64-bit sum of L per frame
+    BUF_conv_bwd,   // specmi_conv2d_backward: conv_bwd_ws_floats floats (the gradient operand G)
+    BUF_conv_fwd,   // specmi_conv2d_train_forward: conv_fwd_ws_floats floats (the weights transposed for this call)
     BUF_COUNT
 };
 

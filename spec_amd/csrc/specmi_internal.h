@@ -488,6 +488,20 @@ struct CamLossArgs {
 int launch_camcalib_loss(const CamLossArgs& a, const LaunchCtx& ctx);
 int launch_camcalib_loss_backward(const CamLossArgs& a, const float* g_means, float* const g_logits[3], const LaunchCtx& ctx);
 
+// One fused ResNet layer for training (conv_bwd.hip; include/specmi.h: specmi_conv2d_train_forward): x (B, H, W, Cin) and
+// y / res / g_y / g_res (B, OH, OW, Cout) dense NHWC, w torch's OIHW tensor on the device, scale / shift (Cout) on the device.
+// The backward's ws is conv_bwd_ws_floats floats (G = g_z * scale); g_x, g_w and g_res may be null (not wanted), g_x_add may be
+// null or g_x itself.
+struct ConvTrainArgs {
+    const float* x; const float* w; const float* scale; const float* shift;
+    int B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad;
+};
+size_t conv_bwd_ws_floats(const ConvTrainArgs& t);
+size_t conv_fwd_ws_floats(const ConvTrainArgs& t);      // the forward's ws: the weights transposed to [tap][ci][o]
+int launch_conv_train_forward(const ConvTrainArgs& t, const float* residual, int relu, float* y, float* ws, const LaunchCtx& ctx);
+int launch_conv_backward(const ConvTrainArgs& t, const float* y, int relu, const float* g_y, const float* g_x_add, float* g_x, float* g_w,
+                         float* g_res, float* ws, const LaunchCtx& ctx);
+
 // ----------------------------------------------------------------------------------------
 // evaluation metrics  (eval.hip)
 // ----------------------------------------------------------------------------------------

@@ -17,6 +17,10 @@ two or three with no activation between them) on the pooled feature, forward and
 (``specmi_camcalib_head_train_forward`` / ``specmi_camcalib_head_backward``) - with ``spec_amd.losses.CameraRegressorLoss`` the
 differentiable tail of the reference's CamCalib ``training_step`` on a frozen trunk.
 
+Below the pooled feature :class:`ResNetStage`: one stage of a Bottleneck ResNet trunk on frozen BatchNorm, every block one
+``torch.autograd.Function`` over the trainable conv layer (``specmi_conv2d_train_forward`` / ``specmi_conv2d_backward``;
+spec_amd/csrc/conv_bwd.hip) - with ``Engine.trunk(images, stages=3)`` as the frozen part, layer4 of either network fine-tunes.
+
 First derivatives only (``once_differentiable``).  The camera arguments (``cam_rotmat``, ``cam_intrinsics``, the box, the image
 size) get no gradient.  With no input requiring grad the heads return exactly what ``Engine.smpl`` returns.
 """
@@ -320,3 +324,119 @@ class CameraRegressorHead(nn.Module):
         else:
             logits, _ = eng.camcalib_head_train_forward(dict(zip(camcalib_head_param_names(L), params)), xf, L)
         return list(logits.unbind(0))
+
+
+def _fold_bn(bn):
+    """Frozen BatchNorm as the affine map of ``commit.hip``'s ``fold_bn``, in its fp32 expression, from the running statistics on the
+    device: scale = gamma / sqrt(var + eps), shift = beta - mean * scale.  No gradient reaches gamma or beta."""
+    with torch.no_grad():
+        invstd = 1.0 / torch.sqrt(bn.running_var.float() + float(bn.eps))
+        scale = invstd * bn.weight.float()
+        return scale.contiguous(), (bn.bias.float() - bn.running_mean.float() * scale).contiguous()
+
+
+def _bottleneck_forward(eng, stride, folds, x, ws):
+    """conv1 -> conv2 -> [downsample, relu = 0] -> conv3 with the residual -> (y1, y2, out)."""
+    y1 = eng.conv2d_train_forward(x, ws[0], *folds[0], 1, 0)
+    y2 = eng.conv2d_train_forward(y1, ws[1], *folds[1], stride, 1)
+    idn = eng.conv2d_train_forward(x, ws[3], *folds[3], stride, 0, relu=False) if len(ws) == 4 else x
+    return y1, y2, eng.conv2d_train_forward(y2, ws[2], *folds[2], 1, 0, residual=idn)
+
+
+class _Bottleneck(torch.autograd.Function):
+    """(x NHWC, conv1 / conv2 / conv3 [/ downsample] weights) -> the block's output NHWC; ``folds`` = the (scale, shift) pairs of the
+    frozen BatchNorms in the same order, which get no gradient."""
+
+    @staticmethod
+    def forward(ctx, eng, stride, folds, x, *ws):
+        xd, wd = x.detach().float().contiguous(), [w.detach() for w in ws]
+        y1, y2, out = _bottleneck_forward(eng, stride, folds, xd, wd)
+        ctx.eng, ctx.stride, ctx.scales = eng, stride, [f[0] for f in folds]
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xd, y1, y2, out, *wd)       # (an optimiser step between forward and backward is caught by autograd's version check)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        x, y1, y2, out, *ws = ctx.saved_tensors
+        n = len(ws)
+        if g_out is None:
+            return (None,) * (4 + n)
+        eng, s, sc = ctx.eng, ctx.stride, ctx.scales
+        need_x, need_w = ctx.needs_input_grad[3], list(ctx.needs_input_grad[4:])
+        below1 = need_x or need_w[0]                      # is g_y1 needed, is g_y2
+        below2 = below1 or need_w[1]
+        has_ds = n == 4
+        g_w = [None] * n
+        want3 = (below2, need_w[2], need_x or (has_ds and need_w[3]))
+        if not any(want3):
+            return (None,) * (4 + n)
+        g_y2, g_w[2], g_res = eng.conv2d_backward(y2, ws[2], sc[2], 1, 0, out, g_out, True, want=want3)
+        skip = g_res
+        if has_ds and (need_x or need_w[3]):
+            skip, g_w[3], _ = eng.conv2d_backward(x, ws[3], sc[3], s, 0, None, g_res, False, want=(need_x, need_w[3], False))
+        g_x = None
+        if below2:
+            g_y1, g_w[1], _ = eng.conv2d_backward(y1, ws[1], sc[1], s, 1, y2, g_y2, True, want=(below1, need_w[1], False))
+            if below1:
+                # the skip (or downsample) gradient is summed in conv1's epilogue, in place where the buffer is this call's own
+                own = need_x and has_ds
+                g_x, g_w[0], _ = eng.conv2d_backward(x, ws[0], sc[0], 1, 0, y1, g_y1, True, g_x_add=skip if need_x else None,
+                                                     want=(need_x, need_w[0], False), g_x_out=skip if own else None)
+        return (None, None, None, g_x) + tuple(g_w)
+
+
+class ResNetStage(nn.Module):
+    """One stage (``layer1`` .. ``layer4``) of a torchvision-layout Bottleneck trunk (ResNet-50 / 101 / 152), trainable on FROZEN
+    BatchNorm: ``forward(x)`` takes (B, h, w, Cin) NHWC - what ``Engine.trunk(images, stages=n - 1)`` returns - and gives
+    (B, oh, ow, 4 planes) NHWC.  Every bottleneck is one ``torch.autograd.Function`` over the library's trainable layer
+    (``specmi_conv2d_train_forward`` / ``specmi_conv2d_backward``; spec_amd/csrc/conv_bwd.hip), which reads the conv weights where
+    torch keeps them - an optimiser steps them as they are.
+
+    BatchNorm is frozen whatever ``train()`` says: at every forward each BN is the affine map scale = gamma / sqrt(running_var + eps),
+    shift = beta - running_mean * scale, computed on the device; batch statistics are never built, the running statistics are not
+    updated, and gamma / beta get no gradient.  The trainable parameters are the conv weights (``conv_parameters()``).
+    First derivatives only."""
+
+    def __init__(self, blocks):
+        super().__init__()
+        self.blocks = blocks
+
+    @classmethod
+    def from_model(cls, net, name='layer4'):
+        """The stage ``name`` of ``net.backbone`` (a ``spec_amd.modules.CameraRegressorNetwork`` or ``HMR``), SHARING its block modules
+        and so their Parameter objects: an optimiser step on ``conv_parameters()`` is a step on the network's weights, and the
+        network's next call sees the bumped tensor versions and commits them again by itself."""
+        from .modules import ResNet50Params
+        if name not in ('layer1', 'layer2', 'layer3', 'layer4'):
+            raise ValueError(f'{name!r} is not a stage: layer1 .. layer4')
+        backbone = getattr(net, 'backbone', None)
+        if not isinstance(backbone, ResNet50Params):
+            raise NotImplementedError(f'ResNetStage is built for the Bottleneck trunks (ResNet-50 / 101 / 152), not for {type(backbone).__name__}')
+        return cls(getattr(backbone, name))
+
+    def conv_parameters(self):
+        """The conv weights, block by block in the order conv1, conv2, conv3[, downsample]: what an optimiser is given."""
+        out = []
+        for blk in self.blocks:
+            out += [blk.conv1.weight, blk.conv2.weight, blk.conv3.weight] + ([blk.downsample[0].weight] if hasattr(blk, 'downsample') else [])
+        return out
+
+    def forward(self, x):
+        dev = _device_of(x)
+        if x.dim() != 4:
+            raise ValueError(f'x must be (B, h, w, Cin) NHWC, got {tuple(x.shape)}')
+        eng = _engine(dev)
+        for blk in self.blocks:
+            ds = hasattr(blk, 'downsample')
+            ws = [blk.conv1.weight, blk.conv2.weight, blk.conv3.weight] + ([blk.downsample[0].weight] if ds else [])
+            folds = [_fold_bn(bn) for bn in [blk.bn1, blk.bn2, blk.bn3] + ([blk.downsample[1]] if ds else [])]
+            stride = blk.conv2.stride[0]
+            if x.shape[3] != blk.conv1.in_channels:
+                raise ValueError(f'the stage takes {blk.conv1.in_channels} channels, x has {x.shape[3]}')
+            if torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in ws)):
+                x = _Bottleneck.apply(eng, stride, folds, x, *ws)
+            else:
+                x = _bottleneck_forward(eng, stride, folds, x.detach().float().contiguous(), [w.detach() for w in ws])[2]
+        return x

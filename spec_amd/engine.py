@@ -1034,7 +1034,12 @@ class Engine:
         x = self._images(images)
         return x, x.shape[0], x.shape[2], x.shape[3], False
 
-    def trunk(self, images):
+    def trunk(self, images, stages=None):
+        """The trunk's feature map (B, fh, fw, C) NHWC.  ``stages`` = 1 .. 4: the committed fp32 ResNet trunk cut after
+        ``layer{stages}`` (``specmi_trunk_forward_stages`` - the frozen part of a fine-tuning step; 4 has this call's bits);
+        ``None``: the whole trunk."""
+        if stages is not None:
+            return self._trunk_stages(images, stages)
         x, B, H, W, f16 = self._images_in(images)
         feat = self._empty(B, *self._feat_shape(H, W), self.feat_channels)
         if B == 0:
@@ -1043,13 +1048,25 @@ class Engine:
         _lib.check(self.h, fn(self.h, _ptr(x), B, H, W, _ptr(feat), self._stream()))
         return feat
 
+    def _trunk_stages(self, images, stages):
+        if isinstance(stages, bool) or not isinstance(stages, int) or not 1 <= stages <= 4:
+            raise ValueError(f'stages must be None or an int in 1 .. 4, got {stages!r}')
+        x = self._images(images)
+        B, _, H, W = x.shape
+        out = self._empty(B, *self._feat_shape(H, W, stages), self.feat_channels >> (4 - stages))
+        if B == 0:
+            return out
+        _lib.check(self.h, self.lib.specmi_trunk_forward_stages(self.h, _ptr(x), B, H, W, stages, _ptr(out), self._stream()))
+        return out
+
     @staticmethod
-    def _feat_shape(H, W):
-        """(fh, fw) of the trunk's feature map: the 7x7 stride-2 stem, then the max-pool and three stride-2 stages (3x3, pad 1)."""
+    def _feat_shape(H, W, stages=4):
+        """(fh, fw) of the trunk's feature map: the 7x7 stride-2 stem, then the max-pool and three stride-2 stages (3x3, pad 1);
+        ``stages`` < 4: of the map after that stage."""
         def o(n, k, s, p):
             return (n + 2 * p - k) // s + 1
         fh, fw = o(H, 7, 2, 3), o(W, 7, 2, 3)
-        for _ in range(4):
+        for _ in range(stages):
             fh, fw = o(fh, 3, 2, 1), o(fw, 3, 2, 1)
         return fh, fw
 
@@ -2042,6 +2059,55 @@ class Engine:
         ld = t.stride(2) if W > 1 else t.stride(1) // W if H > 1 else t.stride(0) // (H * W) if t.shape[0] > 1 else Cc
         want = (H * W * ld, W * ld, ld, 1)
         return ld if ld >= Cc and all(n == 1 or st == wt for n, st, wt in zip(t.shape, t.stride(), want)) else None
+
+    def _conv_train_args(self, x, w, scale, stride, pad):
+        """The layer of the two training calls, checked -> (x, w, scale, B, H, W, Cin, Cout, k, OH, OW); the tensors are read in
+        place when they are dense fp32 on this device."""
+        x, w, scale = _dev_f32(x, self.device), _dev_f32(w, self.device), _dev_f32(scale, self.device)
+        if x.dim() != 4 or w.dim() != 4 or x.shape[3] != w.shape[1] or w.shape[2] != w.shape[3]:
+            raise ValueError(f'x must be (B, H, W, Cin) NHWC and w (Cout, Cin, k, k), got {tuple(x.shape)} and {tuple(w.shape)}')
+        B, H, W, Cin = x.shape
+        Cout, _, k, _ = w.shape
+        if (k, pad) not in ((1, 0), (3, 1)) or stride not in (1, 2):
+            raise ValueError(f'the layers built are 1x1 pad 0 and 3x3 pad 1 at stride 1 or 2, got k = {k}, pad = {pad}, stride = {stride}')
+        if tuple(scale.shape) != (Cout,):
+            raise ValueError(f'scale must be ({Cout},), got {tuple(scale.shape)}')
+        return x, w, scale, B, H, W, Cin, Cout, k, (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+    def conv2d_train_forward(self, x, w, scale, shift, stride, pad, residual=None, relu=True):
+        """``specmi_conv2d_train_forward``: y = act(conv(x, w) * scale + shift [+ residual]) with x (B, H, W, Cin) NHWC, w torch's
+        (Cout, Cin, k, k) tensor and scale / shift (Cout), all read on the device where they lie -> y (B, OH, OW, Cout) NHWC."""
+        x, w, scale, B, H, W, Cin, Cout, k, OH, OW = self._conv_train_args(x, w, scale, stride, pad)
+        shift = _dev_f32(shift, self.device, (Cout,))
+        res = _dev_f32(residual, self.device, (B, OH, OW, Cout))
+        y = self._empty(B, OH, OW, Cout)
+        if y.numel():
+            _lib.check(self.h, self.lib.specmi_conv2d_train_forward(self.h, _ptr(x), B, H, W, Cin, _ptr(w), _ptr(scale), _ptr(shift), Cout, k, k,
+                                                                    stride, pad, _ptr(res), int(bool(relu)), _ptr(y), self._stream()))
+        return y
+
+    def conv2d_backward(self, x, w, scale, stride, pad, y, g_y, relu=True, g_x_add=None, want=(True, True, False), g_x_out=None):
+        """``specmi_conv2d_backward``: the forward's x, w, scale, its output y (may be None without relu) and g_y -> (g_x, g_w, g_res),
+        None where ``want`` = (g_x, g_w, g_res) says so.  ``g_x_add`` (B, H, W, Cin) is added to g_x; ``g_x_out``: the tensor g_x is
+        written to (it may be ``g_x_add`` itself: the sum in place)."""
+        x, w, scale, B, H, W, Cin, Cout, k, OH, OW = self._conv_train_args(x, w, scale, stride, pad)
+        g = _dev_f32(g_y, self.device, (B, OH, OW, Cout))
+        yy = _dev_f32(y, self.device, (B, OH, OW, Cout))
+        if relu and yy is None:
+            raise ValueError('relu needs y (the mask is y > 0)')
+        if not any(want):
+            raise ValueError('no output is wanted')
+        add = _dev_f32(g_x_add, self.device, (B, H, W, Cin)) if want[0] else None
+        g_x = None
+        if want[0]:
+            g_x = g_x_out if g_x_out is not None else self._empty(B, H, W, Cin)
+            if tuple(g_x.shape) != (B, H, W, Cin) or g_x.dtype != torch.float32 or g_x.device != self.device or not g_x.is_contiguous():
+                raise ValueError(f'g_x_out must be a dense fp32 tensor of shape {(B, H, W, Cin)} on {self.device}')
+        g_w = torch.empty_like(w) if want[1] else None
+        g_res = self._empty(B, OH, OW, Cout) if want[2] else None
+        _lib.check(self.h, self.lib.specmi_conv2d_backward(self.h, _ptr(x), B, H, W, Cin, _ptr(w), _ptr(scale), Cout, k, k, stride, pad, _ptr(yy),
+                                                           int(bool(relu)), _ptr(g), _ptr(add), _ptr(g_x), _ptr(g_w), _ptr(g_res), self._stream()))
+        return g_x, g_w, g_res
 
     def conv2d(self, x, w_oihw, scale, shift, stride, pad, residual=None, relu=True, nchw_input=False, out=None,
                x2=None, w2_oihw=None, stride2=1):
