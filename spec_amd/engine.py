@@ -11,6 +11,9 @@ import numpy as np
 import torch
 
 from . import _lib
+# the host records of the picture operations - what the wrappers below refuse before any device call - live in spec_amd.records
+from .records import (PNG_BPP, check_color_jitter, check_draw_marks, check_draw_skeletons, check_jpeg_decode,  # noqa: F401
+                      check_jpeg_encode, check_png_decode, check_png_encode, check_render_views, jpeg_capacity, png_bound, starts)
 
 KIND = {'camcalib': _lib.MODEL_CAMCALIB, 'hmr': _lib.MODEL_HMR, 'smpl': _lib.MODEL_SMPL}
 
@@ -74,6 +77,55 @@ def _dev_f32(t, device, shape=None):
     return t
 
 
+def _u8_slab(name, x, device, optional=False):
+    """``x`` is a contiguous 1-D uint8 tensor on ``device`` (``optional``: or None), or ``ValueError``."""
+    if x is None and optional:
+        return
+    if not isinstance(x, torch.Tensor) or x.device != device or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
+        raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
+
+
+def _dev_tensor(name, x, dtype, device, optional=False):
+    """``x`` is a contiguous tensor of ``dtype`` and any shape on ``device`` (``optional``: or None), or ``ValueError``."""
+    if x is None and optional:
+        return
+    if not isinstance(x, torch.Tensor) or x.device != device or x.dtype != dtype or not x.is_contiguous():
+        raise ValueError(f'{name} must be a contiguous {dtype} tensor on the engine device')
+
+
+def _dev_vector(name, x, n, dtype, device):
+    """-> ``x``, a contiguous (n,) vector of ``dtype`` on ``device``, or a new one for None; anything else: ``ValueError``."""
+    if x is None:
+        return torch.empty(n, device=device, dtype=dtype)
+    if not isinstance(x, torch.Tensor) or x.device != device or x.dtype != dtype or tuple(x.shape) != (n,) or not x.is_contiguous():
+        raise ValueError(f'{name} must be a contiguous (n,) {dtype} tensor on the engine device')
+    return x
+
+
+def _mesh_inputs(vertices, faces, cam_t, device, min_meshes):
+    """The meshes of ``render_meshes`` and ``render_views``: ``vertices`` (M, V, 3) / ``cam_t`` (M, 3) fp32 and ``faces`` (F, 3)
+    int32 on ``device``, M >= ``min_meshes``, V >= 1, F >= 1 -> M, V, F."""
+    for name, x, dt in (('vertices', vertices, torch.float32), ('cam_t', cam_t, torch.float32), ('faces', faces, torch.int32)):
+        _dev_tensor(name, x, dt, device)
+    if vertices.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[0] < min_meshes or vertices.shape[1] < 1:
+        raise ValueError(f'vertices must be (M, V, 3) with M >= {min_meshes} and V >= 1')
+    M, V = int(vertices.shape[0]), int(vertices.shape[1])
+    if tuple(cam_t.shape) != (M, 3):
+        raise ValueError('cam_t must be (M, 3)')
+    if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError('faces must be (F, 3) with F >= 1')
+    return M, V, int(faces.shape[0])
+
+
+def _encode_rows(geom, offsets):
+    """The host arrays of ``jpeg_encode`` and ``png_encode`` -> geom (n, 2) [H, W], offsets (n, 2) [in_offset, in_pitch], int64."""
+    geom = np.ascontiguousarray(geom, dtype=np.int64).reshape(-1, 2)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if tuple(offsets.shape) != (geom.shape[0], 2):
+        raise ValueError('offsets (n, 2): in_offset and in_pitch per picture')
+    return geom, offsets
+
+
 def nhwc8_input(images, precision: str) -> bool:
     """Is ``images`` the fp16 entrance of the fp16 trunk - a ``torch.float16`` tensor in the NHWC8 layout (B, H, W, 8) of
     include/specmi.h?  Validation only, no device call: an fp16 tensor of another shape, or one handed to a model whose
@@ -131,234 +183,6 @@ def flow_render_batch(render_batch=None) -> bool:
     return RENDER_BATCH_DEFAULT if render_batch is None else bool(render_batch)
 
 
-def _rects_overlap(a, b) -> bool:
-    """Do two byte rectangles (first byte, pitch, row bytes, rows) share a byte?  (rects_overlap of spec_amd/csrc/api.hip)"""
-    if a[0] > b[0]:
-        a, b = b, a
-    (ao, ap, ar, ah), (bo, bp, br, bh) = a, b
-    if bo >= ao + (ah - 1) * ap + ar:
-        return False
-    if ap == bp:
-        q, c = divmod(bo - ao, ap)
-        return (q < ah and c < ar) or (q + 1 < ah and c + br > ap)
-    s0 = bo - ao + bp * np.arange(bh, dtype=np.int64)             # row r of b, counted from a's first byte
-    e0 = s0 + br - 1
-    k1, k2 = s0 // ap, np.minimum(e0 // ap, ah - 1)
-    hit = lambda k: (k >= k1) & (k <= k2) & (np.maximum(s0, k * ap) <= np.minimum(e0, k * ap + ar - 1))
-    return bool(((k2 - k1 >= 2) | hit(k1) | hit(k2)).any())
-
-
-def _byte_rects(off, pitch, W, H):
-    """The (first byte, pitch, row bytes, rows) of n pitched rectangles of H rows of 3 W bytes; a single row has no next row, so
-    its pitch counts as 3 W (stored_pitch of spec_amd/csrc/api.hip)."""
-    return [(int(o), int(p) if h > 1 else 3 * int(w), 3 * int(w), int(h)) for o, p, w, h in zip(off, pitch, W, H)]
-
-
-def _first_overlap(rects):
-    """The first two rectangles that share a byte, as (a, b) indices into ``rects``, or None: sorted by first byte, a rectangle
-    is compared with those that start before it ends (first_overlap of spec_amd/csrc/api.hip)."""
-    order = sorted(range(len(rects)), key=lambda v: rects[v][0])
-    for i, a in enumerate(order):
-        end = rects[a][0] + (rects[a][3] - 1) * rects[a][1] + rects[a][2]
-        for b in order[i + 1:]:
-            if rects[b][0] >= end:
-                break
-            if _rects_overlap(rects[a], rects[b]):
-                return a, b
-    return None
-
-
-def check_render_views(Mtot, V, F, geom, offsets, cams, in_bytes, out_bytes, rgb):
-    """Every refusal of ``specmi_render_views`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom``
-    (n, 5) [H, W, mesh0, count, flags], ``offsets`` (n, 4) [in_offset, in_pitch, out_offset, out_pitch], ``cams`` (n, 13)
-    [R, fx, fy, cx, cy], the sizes of the two slabs (``in_bytes`` None: no frame slab) and ``rgb``.  -> the arrays as the
-    library reads them (int32, int64, float32, float32).  Needs no device."""
-    geom = np.ascontiguousarray(geom, dtype=np.int64)
-    offsets, cams = np.ascontiguousarray(offsets, dtype=np.int64), np.ascontiguousarray(cams, dtype=np.float32)
-    n = geom.shape[0] if geom.ndim == 2 else -1
-    if geom.ndim != 2 or geom.shape[1] != 5 or tuple(offsets.shape) != (n, 4) or tuple(cams.shape) != (n, 13):
-        raise ValueError('views: geom (n, 5), offsets (n, 4) and cams (n, 13) with one row per view')
-    if not 1 <= n <= 65535:
-        raise ValueError(f'1 to 65535 views per call, got {n}')
-    if Mtot < 0 or V < 1 or F < 1:
-        raise ValueError(f'{Mtot} meshes of {V} vertices and {F} faces')
-    rgb = np.ascontiguousarray(rgb, dtype=np.float32).reshape(-1)
-    if rgb.shape[0] != 3 or not np.isfinite(rgb).all():
-        raise ValueError('rgb: three finite floats in [0, 1]')
-    if out_bytes >= 1 << 32 or (in_bytes or 0) >= 1 << 32:
-        raise ValueError('a slab of 4 GiB or more is beyond the kernels\' 32-bit offsets')
-    H, W, mesh0, count, flags = geom.T
-    in_off, in_pitch, out_off, out_pitch = offsets.T
-    side, ground = (flags & _lib.RENDER_SIDE_VIEW) != 0, (flags & _lib.RENDER_GROUND_PLANE) != 0
-    if (flags & ~15).any() or (ground & ~side).any():
-        raise ValueError('flags: RENDER_SIDE_VIEW | RENDER_GROUND_PLANE (side view only) | RENDER_CULL | RENDER_THREAD_PER_TRIANGLE')
-    if len(set((flags & _lib.RENDER_THREAD_PER_TRIANGLE).tolist())) != 1:
-        raise ValueError('RENDER_THREAD_PER_TRIANGLE names the one raster launch of the call: on every view or on none')
-    if ((H < 1) | (H > 32768) | (W < 1) | (W > 32768)).any():
-        raise ValueError('a view of 1 .. 32768 pixels per side')
-    if ((count < 0) | (mesh0 < 0) | (mesh0 + count > Mtot)).any():
-        raise ValueError(f'a mesh range leaves the call\'s {Mtot} meshes')
-    if max(int(count.max()), int(count.sum())) * max(F, 3 * V) >= 1 << 31 or int((H * W).sum()) >= 1 << 31:
-        raise ValueError('the views are beyond 31-bit indices (count * F, 3 * count * V, pixels)')
-    if (ground & (count == 0)).any():
-        raise ValueError('a ground plane needs a mesh to lie under (count == 0)')
-    framed = in_off >= 0
-    if (~framed & ~side).any():
-        raise ValueError('an overlay needs the frame it is drawn over (in_offset < 0 is for side views)')
-    if framed.any() and in_bytes is None:
-        raise ValueError('a view names a frame, but there is no frame slab')
-    if (out_pitch < 3 * W).any() or (framed & (in_pitch < 3 * W)).any():
-        raise ValueError('a pitch below 3 * W bytes')
-    if (out_off < 0).any() or (out_off + (H - 1) * out_pitch + 3 * W > out_bytes).any():
-        raise ValueError(f'an output rectangle leaves the slab of {out_bytes} bytes')
-    if (framed & (in_off + (H - 1) * in_pitch + 3 * W > (in_bytes or 0))).any():
-        raise ValueError(f'a frame leaves the slab of {in_bytes} bytes')
-    if not (np.isfinite(cams).all() and (cams[:, 9:11] > 0).all()):
-        raise ValueError('focal lengths must be positive and finite, the centre and R finite')
-    pair = _first_overlap(_byte_rects(out_off, out_pitch, W, H))
-    if pair:
-        raise ValueError(f'the output rectangles of views {pair[0]} and {pair[1]} overlap')
-    return geom.astype(np.int32), offsets, cams, rgb
-
-
-def check_draw_skeletons(Mtot, J, D, bones, geom, offsets, slab_bytes, style=None):
-    """Every refusal of ``specmi_draw_skeletons`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``bones``
-    (NB, 2) joint indices (None or empty: no bones), ``geom`` (n, 4) [H, W, det0, count], ``offsets`` (n, 2) [byte offset, pitch],
-    the size of the slab and the ``_lib.DrawStyle`` (None: the defaults).  -> the arrays as the library reads them (int32, int32,
-    int64) and the style.  Needs no device."""
-    geom, offsets = np.ascontiguousarray(geom, dtype=np.int64), np.ascontiguousarray(offsets, dtype=np.int64)
-    bones = np.zeros((0, 2), np.int64) if bones is None else np.ascontiguousarray(bones, dtype=np.int64).reshape(-1, 2)
-    n = geom.shape[0] if geom.ndim == 2 else -1
-    if geom.ndim != 2 or geom.shape[1] != 4 or tuple(offsets.shape) != (n, 2):
-        raise ValueError('frames: geom (n, 4) and offsets (n, 2) with one row per frame')
-    if not 1 <= n <= 65535:
-        raise ValueError(f'1 to 65535 frames per call, got {n}')
-    if J < 1 or D not in (2, 3) or Mtot < 0:
-        raise ValueError(f'{Mtot} detections of {J} keypoints of {D} floats (J >= 1, D = 2 or 3)')
-    NB = bones.shape[0]
-    if NB and ((bones < 0) | (bones >= J)).any():
-        raise ValueError(f'a bone names a joint outside [0, {J})')
-    if Mtot * (J + NB) >= 1 << 31 or Mtot * J * D >= 1 << 31:
-        raise ValueError('the keypoints are beyond 31-bit indices')
-    style = _lib.DrawStyle() if style is None else style
-    if not (0 <= style.radius <= _lib.DRAW_MAX_RADIUS and 1 <= style.thickness <= _lib.DRAW_MAX_THICKNESS):
-        raise ValueError(f'radius 0 .. {_lib.DRAW_MAX_RADIUS}, thickness 1 .. {_lib.DRAW_MAX_THICKNESS}')
-    if not np.isfinite(style.conf_thr):
-        raise ValueError('the confidence threshold must be finite')
-    H, W, det0, count = geom.T
-    off, pitch = offsets.T
-    if ((H < 1) | (H > _lib.DRAW_MAX_SIDE) | (W < 1) | (W > _lib.DRAW_MAX_SIDE)).any():
-        raise ValueError(f'a frame of 1 .. {_lib.DRAW_MAX_SIDE} pixels per side')
-    if ((count < 0) | (det0 < 0) | (det0 + count > Mtot)).any():
-        raise ValueError(f'a detection range leaves the call\'s {Mtot} detections')
-    if (pitch < 3 * W).any():
-        raise ValueError('a pitch below 3 * W bytes')
-    if (off < 0).any() or (off + (H - 1) * pitch + 3 * W > slab_bytes).any():
-        raise ValueError(f'a frame rectangle leaves the slab of {slab_bytes} bytes')
-    if int((-(-H // 32) * -(-W // 32))[count > 0].sum()) >= 1 << 31:
-        raise ValueError('the frames hold 2^31 tiles of 32 x 32 pixels or more')
-    pair = _first_overlap(_byte_rects(off, pitch, W, H))
-    if pair:
-        raise ValueError(f'frames {pair[0]} and {pair[1]} share a byte')
-    return bones.astype(np.int32), geom.astype(np.int32), offsets, style
-
-
-def check_draw_marks(geom, offsets, marks, slab_bytes, mask_bytes=0):
-    """Every refusal of ``specmi_draw_marks`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom`` (n, 4)
-    [H, W, mark0, count], ``offsets`` (n, 2) [byte offset, pitch], ``marks`` (nmarks, 8) [kind, r | g << 8 | b << 16, p0 .. p5]
-    (strip: y0, y1; mask blend: x, y, mw, mh, byte offset in the mask buffer; wide line: x0, y0, x1, y1, width) and the sizes of
-    the slab and of the mask buffer.  -> the arrays as the library reads them (int32, int64, int64).  Needs no device."""
-    geom, offsets = np.ascontiguousarray(geom, dtype=np.int64), np.ascontiguousarray(offsets, dtype=np.int64)
-    marks = np.ascontiguousarray(marks, dtype=np.int64)
-    if marks.size == 0:
-        marks = marks.reshape(0, _lib.MARK_REC)
-    n = geom.shape[0] if geom.ndim == 2 else -1
-    if geom.ndim != 2 or geom.shape[1] != 4 or tuple(offsets.shape) != (n, 2):
-        raise ValueError('frames: geom (n, 4) and offsets (n, 2) with one row per frame')
-    if marks.ndim != 2 or marks.shape[1] != _lib.MARK_REC:
-        raise ValueError(f'marks: (nmarks, {_lib.MARK_REC}) [kind, colour, p0 .. p5]')
-    if not 1 <= n <= 65535:
-        raise ValueError(f'1 to 65535 frames per call, got {n}')
-    nmarks = marks.shape[0]
-    if nmarks >= 1 << 31:
-        raise ValueError('2^31 marks or more')
-    H, W, mark0, count = geom.T
-    off, pitch = offsets.T
-    if ((H < 1) | (H > _lib.MARK_MAX_SIDE) | (W < 1) | (W > _lib.MARK_MAX_SIDE)).any():
-        raise ValueError(f'a frame of 1 .. {_lib.MARK_MAX_SIDE} pixels per side')
-    if ((count < 0) | (mark0 < 0) | (mark0 + count > nmarks)).any():
-        raise ValueError(f'a mark range leaves the call\'s {nmarks} marks')
-    if (pitch < 3 * W).any():
-        raise ValueError('a pitch below 3 * W bytes')
-    if (off < 0).any() or (off + (H - 1) * pitch + 3 * W > slab_bytes).any():
-        raise ValueError(f'a frame rectangle leaves the slab of {slab_bytes} bytes')
-    kind, rgb = marks[:, 0], marks[:, 1]
-    if (~np.isin(kind, (_lib.MARK_STRIP, _lib.MARK_MASK, _lib.MARK_LINE))).any():
-        raise ValueError('an unknown mark kind (MARK_STRIP, MARK_MASK, MARK_LINE)')
-    if ((rgb < 0) | (rgb > 0xffffff)).any():
-        raise ValueError('a colour is r | g << 8 | b << 16')
-    ln, mk = marks[kind == _lib.MARK_LINE], marks[kind == _lib.MARK_MASK]
-    if ((ln[:, 6] < _lib.MARK_MIN_WIDTH) | (ln[:, 6] > _lib.MARK_MAX_WIDTH)).any():
-        raise ValueError(f'a line width outside {_lib.MARK_MIN_WIDTH} .. {_lib.MARK_MAX_WIDTH}')
-    if (np.abs(ln[:, 2:6]) > _lib.MARK_MAX_COORD).any():
-        raise ValueError(f'a line end point outside [-{_lib.MARK_MAX_COORD}, {_lib.MARK_MAX_COORD}]')
-    if ((mk[:, 4:6] < 1) | (mk[:, 4:6] > _lib.MARK_MAX_MASK_SIDE)).any():
-        raise ValueError(f'a mask of 1 .. {_lib.MARK_MAX_MASK_SIDE} bytes per side')
-    if (np.abs(mk[:, 2:4]) > _lib.MARK_MAX_MASK_POS).any():
-        raise ValueError(f'a mask position outside [-{_lib.MARK_MAX_MASK_POS}, {_lib.MARK_MAX_MASK_POS}]')
-    if ((mk[:, 6] < 0) | (mk[:, 6] + mk[:, 4] * mk[:, 5] > mask_bytes)).any():
-        raise ValueError(f'a mask leaves the mask buffer of {mask_bytes} bytes')
-    pair = _first_overlap(_byte_rects(off, pitch, W, H))
-    if pair:
-        raise ValueError(f'frames {pair[0]} and {pair[1]} share a byte')
-    return geom.astype(np.int32), offsets, marks
-
-
-def check_color_jitter(geom, offsets, records, in_bytes, out_bytes, in_place):
-    """Every refusal of ``specmi_color_jitter`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom`` (n, 2)
-    [H, W], ``offsets`` (n, 4) [in_offset, in_pitch, out_offset, out_pitch], ``records`` (n, 8) int32 [four operation ids in
-    application order (-1: none), the bits of the fp32 factors of brightness, contrast and saturation, the hue shift k], the sizes
-    of the two slabs and whether they are the same slab.  -> the arrays as the library reads them (int32, int64, int32).  Needs no
-    device."""
-    geom, offsets = np.ascontiguousarray(geom, dtype=np.int64), np.ascontiguousarray(offsets, dtype=np.int64)
-    records = np.ascontiguousarray(records)
-    n = geom.shape[0] if geom.ndim == 2 else -1
-    if geom.ndim != 2 or geom.shape[1] != 2 or tuple(offsets.shape) != (n, 4):
-        raise ValueError('frames: geom (n, 2) and offsets (n, 4) with one row per frame')
-    if records.dtype != np.int32 or tuple(records.shape) != (n, _lib.JITTER_REC):
-        raise ValueError(f'records: (n, {_lib.JITTER_REC}) int32 [four ids, three fp32 factors as bits, k]')
-    if not 1 <= n <= 65535:
-        raise ValueError(f'1 to 65535 frames per call, got {n}')
-    H, W = geom.T
-    in_off, in_pitch, out_off, out_pitch = offsets.T
-    if ((H < 1) | (H > _lib.JITTER_MAX_SIDE) | (W < 1) | (W > _lib.JITTER_MAX_SIDE)).any():
-        raise ValueError(f'a frame of 1 .. {_lib.JITTER_MAX_SIDE} pixels per side')
-    if (in_pitch < 3 * W).any() or (out_pitch < 3 * W).any():
-        raise ValueError('a pitch below 3 * W bytes')
-    if (in_off < 0).any() or (in_off + (H - 1) * in_pitch + 3 * W > in_bytes).any():
-        raise ValueError(f'a frame rectangle leaves the slab of {in_bytes} bytes')
-    if (out_off < 0).any() or (out_off + (H - 1) * out_pitch + 3 * W > out_bytes).any():
-        raise ValueError(f'an output rectangle leaves the slab of {out_bytes} bytes')
-    if in_place and ((in_off != out_off) | ((in_pitch != out_pitch) & (H > 1))).any():
-        raise ValueError('in place, but an output rectangle is not its input rectangle')
-    ids = records[:, :4]
-    if ((ids < -1) | (ids > 3)).any():
-        raise ValueError('an operation id outside [-1, 3]')
-    if any((ids == op).sum(axis=1).max() > 1 for op in range(4)):
-        raise ValueError('an operation is named twice')
-    factors = records[:, 4:7].view(np.float32)
-    if not (np.isfinite(factors).all() and (factors >= 0).all()):
-        raise ValueError('a factor is negative or not finite')
-    if ((records[:, 7] < 0) | (records[:, 7] > 255)).any():
-        raise ValueError('a hue shift outside [0, 255]')
-    if int((-(-H // 16) * -(-W // 256)).sum()) >= 1 << 31:
-        raise ValueError('the frames hold 2^31 tiles of 256 x 16 pixels or more')
-    pair = _first_overlap(_byte_rects(out_off, out_pitch, W, H))
-    if pair:
-        raise ValueError(f'frames {pair[0]} and {pair[1]} share an output byte')
-    return geom.astype(np.int32), offsets, records
-
-
 # Which route panel 0 of the pictures takes (render_image_group, render_image_groups, SPECTester, evaluation.save_batch_picture):
 # False = render.group_panel0 draws the horizon line and caption per frame on the host with Pillow - a download of a device
 # frame, a Pillow raster and an upload each (route (a)), True = uint8 frames go up raw and ONE specmi_draw_marks call per flush
@@ -392,67 +216,6 @@ def is_jpeg_name(path) -> bool:
     return str(path).lower().endswith(('.jpg', '.jpeg'))
 
 
-def jpeg_capacity(H, W) -> int:
-    """The room ``Engine.jpeg_encode`` gives an (H, W) picture at first: its raw size and 1 KiB for the header."""
-    return 3 * int(H) * int(W) + 1024
-
-
-def _encode_pictures(geom, offsets):
-    """What ``check_jpeg_encode`` and ``check_png_encode`` refuse alike, each part where both refuse it: the arrays' shapes and
-    the number of pictures -> geom, offsets (int64)."""
-    geom, offsets = np.ascontiguousarray(geom, dtype=np.int64), np.ascontiguousarray(offsets, dtype=np.int64)
-    n = geom.shape[0] if geom.ndim == 2 else -1
-    if geom.ndim != 2 or geom.shape[1] != 2 or tuple(offsets.shape) != (n, 4):
-        raise ValueError('pictures: geom (n, 2) and offsets (n, 4) with one row per picture')
-    if not 1 <= n <= 65535:
-        raise ValueError(f'1 to 65535 pictures per call, got {n}')
-    return geom, offsets
-
-
-def _encode_places(geom, offsets, in_bytes, out_bytes, in_ptr, out_ptr, min_cap, min_cap_what):
-    """The same for the two slabs and every picture's geometry, rectangle in the picture slab and room in the output slab,
-    ``min_cap`` bytes (``min_cap_what``) at least -> H, W, out_off, cap."""
-    if in_bytes is None or out_bytes is None or in_ptr == 0 or out_ptr == 0:
-        raise ValueError('the picture slab or the output slab is missing (a null pointer)')
-    if in_ptr is not None and out_ptr is not None and out_ptr < in_ptr + in_bytes and in_ptr < out_ptr + out_bytes:
-        raise ValueError('the picture slab and the output slab overlap')
-    H, W = geom.T
-    in_off, in_pitch, out_off, cap = offsets.T
-    if ((H < 1) | (H > 32768) | (W < 1) | (W > 32768)).any():
-        raise ValueError('a picture of 1 .. 32768 pixels per side')
-    if (in_pitch < 3 * W).any():
-        raise ValueError('a pitch below 3 * W bytes')
-    if (in_off < 0).any() or (in_off + (H - 1) * in_pitch + 3 * W > in_bytes).any():
-        raise ValueError(f'a picture rectangle leaves the slab of {in_bytes} bytes')
-    if (cap < min_cap).any():
-        raise ValueError(f'a capacity below {min_cap_what} {min_cap} bytes')
-    if (out_off < 0).any() or (out_off + cap > out_bytes).any():
-        raise ValueError(f'an output leaves the slab of {out_bytes} bytes')
-    return H, W, out_off, cap
-
-
-def _encode_outputs_disjoint(out_off, cap):
-    """The same after the pictures: no two outputs share a byte."""
-    order = np.argsort(out_off, kind='stable')
-    if ((out_off + cap)[order][:-1] > out_off[order][1:]).any():
-        raise ValueError('two outputs share a byte')
-
-
-def check_jpeg_encode(geom, offsets, in_bytes, out_bytes, quality, in_ptr=None, out_ptr=None):
-    """Every refusal of ``specmi_jpeg_encode`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom`` (n, 2)
-    [H, W], ``offsets`` (n, 4) [in_offset, in_pitch, out_offset, out_capacity], the sizes of the two slabs, the quality and -
-    where known - the slabs' addresses (None for either: a missing slab).  -> the arrays as the library reads them (int32,
-    int64).  Needs no device."""
-    geom, offsets = _encode_pictures(geom, offsets)
-    if not (isinstance(quality, (int, np.integer)) and 1 <= quality <= 100):
-        raise ValueError(f'quality {quality!r}: an integer in 1 .. 100')
-    H, W, out_off, cap = _encode_places(geom, offsets, in_bytes, out_bytes, in_ptr, out_ptr, _lib.JPEG_HEADER_BYTES, 'the header\'s')
-    if int((-(-H // 16) * -(-W // 16)).sum()) > 1 << 24:
-        raise ValueError('the pictures hold more than 2^24 blocks of 16 x 16 pixels')
-    _encode_outputs_disjoint(out_off, cap)
-    return geom.astype(np.int32), offsets
-
-
 # Which route the pictures the flows write as .png take (the same flows as JPEG_DEVICE_DEFAULT's): False = the raw picture comes
 # down and Pillow (zlib, one host thread) encodes it, True = specmi_png_encode encodes it where it lies and only the file's bytes
 # come down (DESIGN.md 7 f-16).  Unlike the JPEG route the BYTES differ from the host route's - the file decodes to the same
@@ -470,30 +233,6 @@ def flow_png_device(png_device=None) -> bool:
 def is_png_name(path) -> bool:
     """Does Pillow write ``path`` as a PNG (by its extension)?"""
     return str(path).lower().endswith('.png')
-
-
-def png_bound(H, W) -> int:
-    """``specmi_png_bound``: the length no file of ``Engine.png_encode`` for an (H, W) picture exceeds.  Host only."""
-    out = np.zeros(1, np.int64)
-    if _lib.load().specmi_png_bound(int(H), int(W), out.ctypes.data_as(_lib.c_int64_p)) != _lib.OK:
-        raise ValueError(f'a picture of {H} x {W}: 1 .. 32768 pixels per side')
-    return int(out[0])
-
-
-def check_png_encode(geom, offsets, in_bytes, out_bytes, in_ptr=None, out_ptr=None):
-    """Every refusal of ``specmi_png_encode`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``geom`` (n, 2)
-    [H, W], ``offsets`` (n, 4) [in_offset, in_pitch, out_offset, out_capacity], the sizes of the two slabs and - where known - the
-    slabs' addresses (None for either: a missing slab).  -> the arrays as the library reads them (int32, int64).  Needs no device."""
-    geom, offsets = _encode_pictures(geom, offsets)
-    H, W, out_off, cap = _encode_places(geom, offsets, in_bytes, out_bytes, in_ptr, out_ptr, _lib.PNG_OVERHEAD_BYTES, 'the fixed overhead of')
-    stream = H * (1 + 3 * W)
-    segments = -(-stream // 32768)
-    if (6 + stream + 5 * segments >= 1 << 31).any():
-        raise ValueError('a picture whose zlib stream may not fit one IDAT chunk (2^31 bytes)')
-    if int(segments.sum()) > 1 << 23:
-        raise ValueError('the pictures\' filtered streams hold more than 2^23 segments of 32768 bytes')
-    _encode_outputs_disjoint(out_off, cap)
-    return geom.astype(np.int32), offsets
 
 
 # Which route the .jpg / .jpeg frames the flows READ take (preprocess.decode_frames): False = Pillow decodes every file on the host
@@ -520,40 +259,6 @@ def jpeg_probe(data):
     if rc != _lib.OK:
         raise ValueError('specmi_jpeg_probe refused its arguments')
     return _lib.JPEG_REASONS[out[0]], int(out[1]), int(out[2]), int(out[3])
-
-
-def check_jpeg_decode(ranges, geom, outs, in_bytes, out_bytes, in_ptr=None, out_ptr=None):
-    """Every refusal of ``specmi_jpeg_decode`` (include/specmi.h) that the host arrays decide, as ``ValueError``: ``ranges`` (n, 2)
-    [offset, length] of the files in the input slab, ``geom`` (n, 3) [H, W, sampling (420 or 444)] as the probe gave them, ``outs`` (n, 2) [offset, pitch]
-    of the pictures in the output slab, the sizes of the two slabs and - where known - their addresses (None for either: a
-    missing slab).  -> ranges and outs as the library reads them (int64).  Needs no device."""
-    ranges, geom, outs = (np.ascontiguousarray(x, dtype=np.int64) for x in (ranges, geom, outs))
-    n = ranges.shape[0] if ranges.ndim == 2 else -1
-    if ranges.ndim != 2 or ranges.shape[1] != 2 or tuple(geom.shape) != (n, 3) or tuple(outs.shape) != (n, 2):
-        raise ValueError('files: ranges (n, 2), geom (n, 3) and outs (n, 2) with one row per file')
-    if not 1 <= n <= 65535:
-        raise ValueError(f'1 to 65535 files per call, got {n}')
-    if in_bytes is None or out_bytes is None or in_ptr == 0 or out_ptr == 0:
-        raise ValueError('the file slab or the output slab is missing (a null pointer)')
-    if in_ptr is not None and out_ptr is not None and out_ptr < in_ptr + in_bytes and in_ptr < out_ptr + out_bytes:
-        raise ValueError('the file slab and the output slab overlap')
-    off, length = ranges.T
-    H, W, sampling = geom.T
-    out_off, pitch = outs.T
-    if (off < 0).any() or (length < 0).any() or (off + length > in_bytes).any():
-        raise ValueError(f'a file leaves the slab of {in_bytes} bytes')
-    if ((H < 1) | (H > 32768) | (W < 1) | (W > 32768)).any() or not np.isin(sampling, (420, 444)).all():
-        raise ValueError('a picture of 1 .. 32768 pixels per side, sampled 420 or 444 (a file the probe refuses?)')
-    if (pitch < 3 * W).any():
-        raise ValueError('a pitch below 3 * W bytes')
-    if (out_off < 0).any() or (out_off + (H - 1) * pitch + 3 * W > out_bytes).any():
-        raise ValueError(f'a picture rectangle leaves the slab of {out_bytes} bytes')
-    mcu = np.where(sampling == 420, 16, 8)
-    if int((-(-H // mcu) * -(-W // mcu)).sum()) > 1 << 24:
-        raise ValueError('the files hold more than 2^24 MCUs')
-    if _first_overlap(_byte_rects(out_off, pitch, W, H)):
-        raise ValueError('two picture rectangles share a byte')
-    return ranges, outs
 
 
 # Which route the .png frames the flows READ take (preprocess.decode_frames): False = Pillow decodes every file on the host and the
@@ -601,49 +306,6 @@ def png_takes_device(probe) -> bool:
     from PIL import Image
     limit = Image.MAX_IMAGE_PIXELS
     return probe[0] == 'supported' and (limit is None or probe[1] * probe[2] <= limit)
-
-
-PNG_BPP = {0: 1, 2: 3, 4: 2, 6: 4}      # bytes per pixel of the colour types specmi_png_decode takes
-
-
-def check_png_decode(ranges, geom, outs, in_bytes, out_bytes, in_ptr=None, out_ptr=None, raw_bytes=None):
-    """Every refusal of ``specmi_png_decode`` (include/specmi.h) as ``ValueError``: ``ranges`` (n, 2) [offset, length] of the zlib
-    streams in the input slab, ``geom`` (n, 3) [H, W, colour type] as the probe gave them, ``outs`` (n, 2) [offset, pitch] of the
-    pictures in the output slab, the sizes of the two slabs and - where known - their addresses (None for either: a missing
-    slab); ``raw_bytes``: the size of the optional raw output.  -> (ranges int64, geom int32, outs int64, the bytes ``raw``
-    needs).  Needs no device."""
-    ranges, geom, outs = (np.ascontiguousarray(x, dtype=np.int64) for x in (ranges, geom, outs))
-    n = ranges.shape[0] if ranges.ndim == 2 else -1
-    if ranges.ndim != 2 or ranges.shape[1] != 2 or tuple(geom.shape) != (n, 3) or tuple(outs.shape) != (n, 2):
-        raise ValueError('files: ranges (n, 2), geom (n, 3) and outs (n, 2) with one row per file')
-    if not 1 <= n <= 65535:
-        raise ValueError(f'1 to 65535 files per call, got {n}')
-    if in_bytes is None or out_bytes is None or in_ptr == 0 or out_ptr == 0:
-        raise ValueError('the stream slab or the output slab is missing (a null pointer)')
-    if in_ptr is not None and out_ptr is not None and out_ptr < in_ptr + in_bytes and in_ptr < out_ptr + out_bytes:
-        raise ValueError('the stream slab and the output slab overlap')
-    off, length = ranges.T
-    H, W, ctype = geom.T
-    out_off, pitch = outs.T
-    if (off < 0).any() or (length < 0).any() or (off + length > in_bytes).any():
-        raise ValueError(f'a stream leaves the slab of {in_bytes} bytes')
-    if (length < 8).any():
-        raise ValueError('a zlib stream shorter than 8 bytes')
-    if ((H < 1) | (H > 32768) | (W < 1) | (W > 32768)).any() or not np.isin(ctype, tuple(PNG_BPP)).all():
-        raise ValueError('a picture of 1 .. 32768 pixels per side, colour type 0, 2, 4 or 6 (a file the probe refuses?)')
-    if (pitch < 3 * W).any():
-        raise ValueError('a pitch below 3 * W bytes')
-    if (out_off < 0).any() or (out_off + (H - 1) * pitch + 3 * W > out_bytes).any():
-        raise ValueError(f'a picture rectangle leaves the slab of {out_bytes} bytes')
-    bpp = np.array([PNG_BPP[int(c)] for c in ctype], np.int64)
-    need = int(((H * (1 + W * bpp) + 255) // 256 * 256).sum())
-    if need > 1 << 31:
-        raise ValueError('the files\' inflated streams hold more than 2^31 bytes')
-    if raw_bytes is not None and raw_bytes < need:
-        raise ValueError(f'the raw output holds {raw_bytes} bytes, these files\' inflated streams take {need}')
-    if _first_overlap(_byte_rects(out_off, pitch, W, H)):
-        raise ValueError('two picture rectangles share a byte')
-    return ranges, geom.astype(np.int32), outs, need
 
 
 EVAL_STEP_OUTPUTS = ('err_sel', 'pa_err_sel', 'err_k', 'pa_err_k', 'v2v')
@@ -1319,7 +981,7 @@ class Engine:
             raise ValueError('one [H, W] row per view')
         nbytes = out_hw.astype(np.int64).prod(axis=1) * 3
         if offsets is None:
-            offsets = np.concatenate([[0], np.cumsum(nbytes)[:-1]]) if n else np.zeros(0)
+            offsets = starts(nbytes)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
         if offsets.shape[0] != n:
             raise ValueError('one offset per view')
@@ -1339,16 +1001,10 @@ class Engine:
         ``id_map`` (H, W) int32, ``depth`` (H, W) fp32, ``screen_xy`` (M, V, 2) int32 and ``screen_z`` (M, V) fp32.
         Everything is checked here, before the library is called."""
         d = self.device
-        for name, x, dt in (('vertices', vertices, torch.float32), ('cam_t', cam_t, torch.float32), ('R', R, torch.float32), ('faces', faces, torch.int32)):
-            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != dt or not x.is_contiguous():
-                raise ValueError(f'{name} must be a contiguous {dt} tensor on the engine device')
-        if vertices.dim() != 3 or vertices.shape[2] != 3 or min(vertices.shape[:2]) < 1:
-            raise ValueError('vertices must be (M, V, 3) with M, V >= 1')
-        M, V = int(vertices.shape[0]), int(vertices.shape[1])
-        if tuple(cam_t.shape) != (M, 3) or tuple(R.shape) != (3, 3):
-            raise ValueError('cam_t must be (M, 3) and R (3, 3)')
-        if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
-            raise ValueError('faces must be (F, 3) with F >= 1')
+        M, V, F = _mesh_inputs(vertices, faces, cam_t, d, 1)
+        _dev_tensor('R', R, torch.float32, d)
+        if tuple(R.shape) != (3, 3):
+            raise ValueError('R must be (3, 3)')
         side = bool(flags & _lib.RENDER_SIDE_VIEW)
         if flags & ~15 or (flags & _lib.RENDER_GROUND_PLANE and not side):
             raise ValueError('flags: RENDER_SIDE_VIEW | RENDER_GROUND_PLANE (side view only) | RENDER_CULL | RENDER_THREAD_PER_TRIANGLE')
@@ -1373,7 +1029,7 @@ class Engine:
         depth = torch.empty(H, W, device=d, dtype=torch.float32) if maps else None
         screen = torch.empty(M, V, 3, device=d, dtype=torch.int32) if maps else None
         _lib.check(self.h, self.lib.specmi_render_meshes(
-            self.h, _ptr(vertices), M, V, _ptr(faces), int(faces.shape[0]), _ptr(cam_t), _ptr(R), *cam, _ptr(frame), H, W,
+            self.h, _ptr(vertices), M, V, _ptr(faces), F, _ptr(cam_t), _ptr(R), *cam, _ptr(frame), H, W,
             rgb.ctypes.data_as(_lib.c_float_p), int(flags), _ptr(out), _ptr(id_map), _ptr(depth), _ptr(screen), self._stream()))
         if not maps:
             return out
@@ -1390,31 +1046,18 @@ class Engine:
         ``screen_z`` (P, V) fp32 (P = the (view, mesh) pairs in view order).  Everything is checked here, before the library is
         called (``check_render_views``)."""
         d = self.device
-        for name, x, dt in (('vertices', vertices, torch.float32), ('cam_t', cam_t, torch.float32), ('faces', faces, torch.int32)):
-            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != dt or not x.is_contiguous():
-                raise ValueError(f'{name} must be a contiguous {dt} tensor on the engine device')
-        if vertices.dim() != 3 or vertices.shape[2] != 3 or vertices.shape[1] < 1:
-            raise ValueError('vertices must be (Mtot, V, 3) with V >= 1')
-        Mtot, V = int(vertices.shape[0]), int(vertices.shape[1])
-        if tuple(cam_t.shape) != (Mtot, 3):
-            raise ValueError('cam_t must be (Mtot, 3)')
-        if faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
-            raise ValueError('faces must be (F, 3) with F >= 1')
-        for name, x in (('in_slab', in_slab), ('out_slab', out_slab)):
-            if x is None and name == 'in_slab':
-                continue
-            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
-                raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
+        Mtot, V, F = _mesh_inputs(vertices, faces, cam_t, d, 0)
+        _u8_slab('in_slab', in_slab, d, optional=True)
+        _u8_slab('out_slab', out_slab, d)
         if in_slab is not None and in_slab.data_ptr() < out_slab.data_ptr() + out_slab.numel() and out_slab.data_ptr() < in_slab.data_ptr() + in_slab.numel():
             raise ValueError('in_slab and out_slab overlap')
-        geom, offsets, cams, rgb = check_render_views(Mtot, V, int(faces.shape[0]), geom, offsets, cams,
-                                                      None if in_slab is None else in_slab.numel(), out_slab.numel(), rgb)
+        geom, offsets, cams, rgb = check_render_views(Mtot, V, F, geom, offsets, cams, None if in_slab is None else in_slab.numel(), out_slab.numel(), rgb)
         n, px, pairs = geom.shape[0], int((geom[:, 0].astype(np.int64) * geom[:, 1]).sum()), int(geom[:, 3].sum())
         id_map = torch.empty(px, device=d, dtype=torch.int32) if maps else None
         depth = torch.empty(px, device=d, dtype=torch.float32) if maps else None
         screen = torch.empty(pairs, V, 3, device=d, dtype=torch.int32) if maps else None
         _lib.check(self.h, self.lib.specmi_render_views(
-            self.h, _ptr(vertices), Mtot, V, _ptr(faces), int(faces.shape[0]), _ptr(cam_t), rgb.ctypes.data_as(_lib.c_float_p),
+            self.h, _ptr(vertices), Mtot, V, _ptr(faces), F, _ptr(cam_t), rgb.ctypes.data_as(_lib.c_float_p),
             _ptr(in_slab), 0 if in_slab is None else in_slab.numel(), _ptr(out_slab), out_slab.numel(),
             geom.ctypes.data_as(_lib.c_int32_p), offsets.ctypes.data_as(_lib.c_int64_p), cams.ctypes.data_as(_lib.c_float_p), n,
             _ptr(id_map), _ptr(depth), _ptr(screen), self._stream()))
@@ -1431,10 +1074,10 @@ class Engine:
         ``_lib.DrawStyle`` (None = radius 4, thickness 2, threshold 0.3, green joints, blue / red bones).  Returns ``slab``.
         Everything is checked here, before the library is called (``check_draw_skeletons``)."""
         d = self.device
-        if not isinstance(kp, torch.Tensor) or kp.device != d or kp.dtype != torch.float32 or not kp.is_contiguous() or kp.dim() != 3:
-            raise ValueError('kp must be a contiguous (Mtot, J, D) float32 tensor on the engine device')
-        if not isinstance(slab, torch.Tensor) or slab.device != d or slab.dtype != torch.uint8 or slab.dim() != 1 or not slab.is_contiguous():
-            raise ValueError('slab must be a contiguous 1-D uint8 tensor on the engine device')
+        _dev_tensor('kp', kp, torch.float32, d)
+        if kp.dim() != 3:
+            raise ValueError('kp must be (Mtot, J, D)')
+        _u8_slab('slab', slab, d)
         if bones is None:
             from .constants import SKELETON_SPIN
             bones = SKELETON_SPIN
@@ -1453,12 +1096,8 @@ class Engine:
         (nmarks, 8) int64 [kind, r | g << 8 | b << 16, p0 .. p5] (``check_draw_marks``; ``render.horizon_marks`` builds the marks
         of a horizon line).  ``masks``: the 1-D uint8 device buffer the mask blends index (None: no mask blend).  Returns
         ``slab``.  Everything the host arrays decide is checked here, before the library is called."""
-        d = self.device
-        if not isinstance(slab, torch.Tensor) or slab.device != d or slab.dtype != torch.uint8 or slab.dim() != 1 or not slab.is_contiguous():
-            raise ValueError('slab must be a contiguous 1-D uint8 tensor on the engine device')
-        if masks is not None and (not isinstance(masks, torch.Tensor) or masks.device != d or masks.dtype != torch.uint8 or masks.dim() != 1
-                                  or not masks.is_contiguous()):
-            raise ValueError('masks must be a contiguous 1-D uint8 tensor on the engine device')
+        _u8_slab('slab', slab, self.device)
+        _u8_slab('masks', masks, self.device, optional=True)
         geom, offsets, marks = check_draw_marks(geom, offsets, marks, slab.numel(), 0 if masks is None else masks.numel())
         _lib.check(self.h, self.lib.specmi_draw_marks(
             self.h, _ptr(slab), slab.numel(), geom.ctypes.data_as(_lib.c_int32_p), offsets.ctypes.data_as(_lib.c_int64_p), int(geom.shape[0]),
@@ -1473,12 +1112,10 @@ class Engine:
         .records``).  ``out``: the slab the jittered frames go to - None: a new slab of the same size, ``slab`` itself: in place -
         at ``out_offsets`` (None: the same rectangles).  Returns ``out``.  Everything the host arrays decide is checked here,
         before the library is called (``check_color_jitter``)."""
-        d = self.device
+        _u8_slab('slab', slab, self.device)
         if out is None:
-            out = torch.empty_like(slab) if isinstance(slab, torch.Tensor) else None
-        for name, x in (('slab', slab), ('out', out)):
-            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
-                raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
+            out = torch.empty_like(slab)
+        _u8_slab('out', out, self.device)
         sizes = np.ascontiguousarray(sizes, dtype=np.int64).reshape(-1, 2)
 
         def pitched(o):
@@ -1514,8 +1151,7 @@ class Engine:
             raise ValueError(f'image {index} of {B}, {H} x {W} of {Hp} x {Wp}, pitch {pitch}, offset {offset}')
         if slab is None:
             slab = torch.empty(offset + (H - 1) * pitch + 3 * W, device=d, dtype=torch.uint8)
-        elif not isinstance(slab, torch.Tensor) or slab.device != d or slab.dtype != torch.uint8 or slab.dim() != 1 or not slab.is_contiguous():
-            raise ValueError('slab must be a contiguous 1-D uint8 tensor on the engine device')
+        _u8_slab('slab', slab, d)
         if offset + (H - 1) * pitch + 3 * W > slab.numel():
             raise ValueError(f'the frame leaves the slab of {slab.numel()} bytes')
         f3 = lambda v: None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(3)
@@ -1532,16 +1168,11 @@ class Engine:
         -> ``sizes`` (n,) int64 on the device (given or new): every file's true length, also of a picture that did not fit its
         capacity (nothing is written beyond it).  Nothing is synchronised or downloaded here; a repeat of the previous records
         can be captured in a graph.  Everything is checked before the library is called (``check_jpeg_encode``)."""
-        d = self.device
-        for name, x in (('slab', slab), ('out_slab', out_slab)):
-            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
-                raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
+        _u8_slab('slab', slab, self.device)
+        _u8_slab('out_slab', out_slab, self.device)
         geom, offsets = check_jpeg_encode(geom, offsets, slab.numel(), out_slab.numel(), quality, slab.data_ptr(), out_slab.data_ptr())
         n = int(geom.shape[0])
-        if sizes is None:
-            sizes = torch.empty(n, device=d, dtype=torch.int64)
-        elif not isinstance(sizes, torch.Tensor) or sizes.device != d or sizes.dtype != torch.int64 or tuple(sizes.shape) != (n,) or not sizes.is_contiguous():
-            raise ValueError('sizes must be a contiguous (n,) int64 tensor on the engine device')
+        sizes = _dev_vector('sizes', sizes, n, torch.int64, self.device)
         _lib.check(self.h, self.lib.specmi_jpeg_encode(
             self.h, _ptr(slab), slab.numel(), _ptr(out_slab), out_slab.numel(), geom.ctypes.data_as(_lib.c_int32_p),
             offsets.ctypes.data_as(_lib.c_int64_p), n, int(quality), _ptr(sizes), self._stream()))
@@ -1553,28 +1184,32 @@ class Engine:
         contract): one ``jpeg_encode_into`` call into a private slab with ``jpeg_capacity(H, W)`` bytes per picture, a download
         of the sizes, then of the used bytes only; a picture that did not fit (noise at a high quality) is encoded again with
         the room its size asks for.  -> the files as a list of ``bytes``."""
-        geom = np.ascontiguousarray(geom, dtype=np.int64).reshape(-1, 2)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        if tuple(offsets.shape) != (geom.shape[0], 2):
-            raise ValueError('offsets (n, 2): in_offset and in_pitch per picture')
+        geom, offsets = _encode_rows(geom, offsets)
         files = [None] * geom.shape[0]
         todo, cap = np.arange(geom.shape[0]), np.array([jpeg_capacity(h, w) for h, w in geom], np.int64)
         while todo.size:
-            out_off = np.concatenate([[0], np.cumsum(cap[todo])])
-            out_slab = torch.empty(int(out_off[-1]), device=self.device, dtype=torch.uint8)
-            full = np.concatenate([offsets[todo], out_off[:-1, None], cap[todo, None]], axis=1)
-            sizes = self.jpeg_encode_into(slab, out_slab, geom[todo], full, quality).cpu().numpy()
+            sizes, got = self._encode_round(lambda *a: self.jpeg_encode_into(slab, *a, quality), geom[todo], offsets[todo], cap[todo])
+            for i, f in zip(todo, got):
+                files[i] = f
             fits = sizes <= cap[todo]
-            spans = [(int(o), int(o + s)) for o, s, ok in zip(out_off[:-1], sizes, fits) if ok]
-            if spans:
-                host = torch.cat([out_slab[a:b] for a, b in spans]).cpu().numpy().tobytes()
-                at = 0
-                for i, (a, b) in zip(todo[fits], spans):
-                    files[i] = host[at:at + b - a]
-                    at += b - a
             cap[todo] = sizes
             todo = todo[~fits]
         return files
+
+    def _encode_round(self, into, geom, offsets, cap):
+        """What ``jpeg_encode`` and ``png_encode`` share: one ``into(out_slab, geom, offsets (n, 4))`` call into a private slab
+        with ``cap`` bytes per picture, a download of the sizes, then - in one copy - of the used bytes of the files that fit
+        -> (sizes on the host, the files as ``bytes``: None where one did not fit)."""
+        out_off = starts(cap)
+        out_slab = torch.empty(int(cap.sum()), device=self.device, dtype=torch.uint8)
+        sizes = into(out_slab, geom, np.concatenate([offsets, out_off[:, None], cap[:, None]], axis=1)).cpu().numpy()
+        fits = sizes <= cap
+        files = [None] * len(cap)
+        if fits.any():
+            host = torch.cat([out_slab[int(o):int(o + s)] for o, s in zip(out_off[fits], sizes[fits])]).cpu().numpy().tobytes()
+            for i, a, s in zip(np.flatnonzero(fits), starts(sizes[fits]), sizes[fits]):
+                files[i] = host[int(a):int(a + s)]
+        return sizes, files
 
     def png_encode_into(self, slab, out_slab, geom, offsets, sizes=None):
         """``specmi_png_encode``: the pictures ``geom`` (n, 2) [H, W] at ``offsets`` (n, 4) [in_offset, in_pitch, out_offset,
@@ -1583,16 +1218,11 @@ class Engine:
         file's true length, also of a picture that did not fit its capacity (nothing is written beyond it; with
         ``png_bound(H, W)`` of room every picture fits).  Nothing is synchronised or downloaded here; a repeat of the previous
         records can be captured in a graph.  Everything is checked before the library is called (``check_png_encode``)."""
-        d = self.device
-        for name, x in (('slab', slab), ('out_slab', out_slab)):
-            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
-                raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
+        _u8_slab('slab', slab, self.device)
+        _u8_slab('out_slab', out_slab, self.device)
         geom, offsets = check_png_encode(geom, offsets, slab.numel(), out_slab.numel(), slab.data_ptr(), out_slab.data_ptr())
         n = int(geom.shape[0])
-        if sizes is None:
-            sizes = torch.empty(n, device=d, dtype=torch.int64)
-        elif not isinstance(sizes, torch.Tensor) or sizes.device != d or sizes.dtype != torch.int64 or tuple(sizes.shape) != (n,) or not sizes.is_contiguous():
-            raise ValueError('sizes must be a contiguous (n,) int64 tensor on the engine device')
+        sizes = _dev_vector('sizes', sizes, n, torch.int64, self.device)
         _lib.check(self.h, self.lib.specmi_png_encode(
             self.h, _ptr(slab), slab.numel(), _ptr(out_slab), out_slab.numel(), geom.ctypes.data_as(_lib.c_int32_p),
             offsets.ctypes.data_as(_lib.c_int64_p), n, _ptr(sizes), self._stream()))
@@ -1603,19 +1233,12 @@ class Engine:
         to exactly the pictures (include/specmi.h states the contract; the bytes are not Pillow's): one ``png_encode_into`` call
         into a private slab with ``png_bound(H, W)`` bytes per picture - every file fits, so there is no second call - a
         download of the sizes, then of the used bytes only.  -> the files as a list of ``bytes``."""
-        geom = np.ascontiguousarray(geom, dtype=np.int64).reshape(-1, 2)
-        offsets = np.ascontiguousarray(offsets, dtype=np.int64)
-        if tuple(offsets.shape) != (geom.shape[0], 2):
-            raise ValueError('offsets (n, 2): in_offset and in_pitch per picture')
+        geom, offsets = _encode_rows(geom, offsets)
         cap = np.array([png_bound(h, w) for h, w in geom], np.int64)
-        out_off = np.concatenate([[0], np.cumsum(cap)])
-        out_slab = torch.empty(int(out_off[-1]), device=self.device, dtype=torch.uint8)
-        sizes = self.png_encode_into(slab, out_slab, geom, np.concatenate([offsets, out_off[:-1, None], cap[:, None]], axis=1)).cpu().numpy()
+        sizes, files = self._encode_round(lambda *a: self.png_encode_into(slab, *a), geom, offsets, cap)
         if (sizes > cap).any():
             raise RuntimeError('specmi_png_encode reports a file beyond specmi_png_bound')
-        host = torch.cat([out_slab[int(o):int(o + s)] for o, s in zip(out_off[:-1], sizes)]).cpu().numpy().tobytes()
-        ends = np.cumsum(sizes)
-        return [host[int(e - s):int(e)] for e, s in zip(ends, sizes)]
+        return files
 
     def jpeg_decode_into(self, host, slab, ranges, geom, out_slab, outs, status=None, coef=None):
         """``specmi_jpeg_decode``: the files at ``ranges`` (n, 2) [offset, length] of ``slab`` (1-D uint8 on the engine device)
@@ -1625,21 +1248,15 @@ class Engine:
         overlapping).  -> (``status`` (n,) int32 on the device, given or new: 0 where the file's pixels are Pillow's; passes of
         the sync stage).  ``coef``: an int16 device tensor that receives the coefficients.  Synchronises the stream between
         passes; everything the arrays decide is checked before the library is called (``check_jpeg_decode``)."""
-        d = self.device
-        for name, x in (('slab', slab), ('out_slab', out_slab)):
-            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
-                raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
+        _u8_slab('slab', slab, self.device)
+        _u8_slab('out_slab', out_slab, self.device)
         host = np.ascontiguousarray(host, dtype=np.uint8).reshape(-1)
         if host.size != slab.numel():
             raise ValueError('host and slab hold the same bytes: their sizes differ')
         ranges, outs = check_jpeg_decode(ranges, geom, outs, slab.numel(), out_slab.numel(), slab.data_ptr(), out_slab.data_ptr())
         n = int(ranges.shape[0])
-        if status is None:
-            status = torch.empty(n, device=d, dtype=torch.int32)
-        elif not isinstance(status, torch.Tensor) or status.device != d or status.dtype != torch.int32 or tuple(status.shape) != (n,) or not status.is_contiguous():
-            raise ValueError('status must be a contiguous (n,) int32 tensor on the engine device')
-        if coef is not None and (not isinstance(coef, torch.Tensor) or coef.device != d or coef.dtype != torch.int16 or not coef.is_contiguous()):
-            raise ValueError('coef must be a contiguous int16 tensor on the engine device')
+        status = _dev_vector('status', status, n, torch.int32, self.device)
+        _dev_tensor('coef', coef, torch.int16, self.device, optional=True)
         passes = C.c_int32(0)
         _lib.check(self.h, self.lib.specmi_jpeg_decode(
             self.h, host.ctypes.data_as(C.c_void_p), _ptr(slab), slab.numel(), ranges.ctypes.data_as(_lib.c_int64_p), _ptr(out_slab),
@@ -1653,22 +1270,29 @@ class Engine:
         pictures back to back in one 1-D uint8 device slab with their (n,) int64 byte offsets and [(H, W)] - the triple
         ``preprocess.pack_frames`` builds from Pillow's decodes of the same files, bit for bit where ``status`` (n,) int32 on the
         device is 0 (include/specmi.h states the contract).  One upload of the files' bytes, one ``specmi_jpeg_decode``."""
+        return self._decode(files, jpeg_probe, lambda f, p: f, 'baseline JPEG', lambda host, *a: self.jpeg_decode_into(host, *a)[0])
+
+    def _decode(self, files, probe, payload, what, into):
+        """What ``jpeg_decode`` and ``png_decode`` share: every file probed (``probe``) and refused unless supported (a ``what``
+        file), its ``payload(file, probe answer)`` - what the device reads of it - back to back in one uploaded slab, dense
+        output rectangles, one ``into(host bytes, slab, ranges, geom, out_slab, outs)`` call -> (slab, offsets, sizes, status)."""
         files = [bytes(f) for f in files]
         if not files:
             raise ValueError('at least one file')
-        probes = [jpeg_probe(f) for f in files]
+        probes = [probe(f) for f in files]
         for i, p in enumerate(probes):
             if p[0] != 'supported':
-                raise ValueError(f'file {i} is not a supported baseline JPEG file ({p[0]})')
-        length = np.array([len(f) for f in files], np.int64)
-        ranges = np.stack([np.concatenate([[0], np.cumsum(length)[:-1]]), length], axis=1)
-        host = np.frombuffer(b''.join(files), np.uint8)
-        geom = np.array([p[1:] for p in probes], np.int64)
+                raise ValueError(f'file {i} is not a supported {what} file ({p[0]})')
+        payloads = [payload(f, p) for f, p in zip(files, probes)]
+        length = np.array([len(s) for s in payloads], np.int64)
+        ranges = np.stack([starts(length), length], axis=1)
+        host = np.frombuffer(b''.join(payloads), np.uint8)
+        geom = np.array([p[1:4] for p in probes], np.int64)
         size = 3 * geom[:, 0] * geom[:, 1]
-        offsets = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64)
+        offsets = starts(size)
         slab = torch.from_numpy(host.copy()).to(self.device)
         out_slab = torch.empty(int(size.sum()), device=self.device, dtype=torch.uint8)
-        status, _ = self.jpeg_decode_into(host, slab, ranges, geom, out_slab, np.stack([offsets, 3 * geom[:, 1]], axis=1))
+        status = into(host, slab, ranges, geom, out_slab, np.stack([offsets, 3 * geom[:, 1]], axis=1))
         return out_slab, offsets, [(int(h), int(w)) for h, w, _ in geom], status
 
     def png_decode_into(self, slab, ranges, geom, out_slab, outs, status=None, raw=None):
@@ -1678,19 +1302,13 @@ class Engine:
         not overlapping).  -> ``status`` (n,) int32 on the device, given or new: 0 where the file's pixels are Pillow's.  ``raw``:
         a uint8 device tensor that receives the inflated streams, each from a multiple of 256.  Everything the arrays decide is
         checked before the library is called (``check_png_decode``)."""
-        d = self.device
-        for name, x in (('slab', slab), ('out_slab', out_slab)):
-            if not isinstance(x, torch.Tensor) or x.device != d or x.dtype != torch.uint8 or x.dim() != 1 or not x.is_contiguous():
-                raise ValueError(f'{name} must be a contiguous 1-D uint8 tensor on the engine device')
-        if raw is not None and (not isinstance(raw, torch.Tensor) or raw.device != d or raw.dtype != torch.uint8 or not raw.is_contiguous()):
-            raise ValueError('raw must be a contiguous uint8 tensor on the engine device')
+        _u8_slab('slab', slab, self.device)
+        _u8_slab('out_slab', out_slab, self.device)
+        _dev_tensor('raw', raw, torch.uint8, self.device, optional=True)      # any shape: the streams land in its bytes
         ranges, geom, outs, _ = check_png_decode(ranges, geom, outs, slab.numel(), out_slab.numel(), slab.data_ptr(), out_slab.data_ptr(),
                                                  None if raw is None else raw.numel())
         n = int(ranges.shape[0])
-        if status is None:
-            status = torch.empty(n, device=d, dtype=torch.int32)
-        elif not isinstance(status, torch.Tensor) or status.device != d or status.dtype != torch.int32 or tuple(status.shape) != (n,) or not status.is_contiguous():
-            raise ValueError('status must be a contiguous (n,) int32 tensor on the engine device')
+        status = _dev_vector('status', status, n, torch.int32, self.device)
         _lib.check(self.h, self.lib.specmi_png_decode(
             self.h, _ptr(slab), slab.numel(), ranges.ctypes.data_as(_lib.c_int64_p), geom.ctypes.data_as(_lib.c_int32_p), _ptr(out_slab),
             out_slab.numel(), outs.ctypes.data_as(_lib.c_int64_p), n, _ptr(status), _ptr(raw), 0 if raw is None else raw.numel(),
@@ -1702,23 +1320,7 @@ class Engine:
         pictures back to back in one 1-D uint8 device slab with their (n,) int64 byte offsets and [(H, W)] - the triple
         ``preprocess.pack_frames`` builds from Pillow's decodes of the same files, bit for bit where ``status`` (n,) int32 on the
         device is 0 (include/specmi.h states the contract).  One upload of the files' zlib streams, one ``specmi_png_decode``."""
-        files = [bytes(f) for f in files]
-        if not files:
-            raise ValueError('at least one file')
-        probes = [png_probe(f) for f in files]
-        for i, p in enumerate(probes):
-            if p[0] != 'supported':
-                raise ValueError(f'file {i} is not a supported PNG file ({p[0]})')
-        streams = [png_stream(f, p[4]) for f, p in zip(files, probes)]
-        length = np.array([len(s) for s in streams], np.int64)
-        ranges = np.stack([np.concatenate([[0], np.cumsum(length)[:-1]]), length], axis=1)
-        geom = np.array([p[1:4] for p in probes], np.int64)
-        size = 3 * geom[:, 0] * geom[:, 1]
-        offsets = np.concatenate([[0], np.cumsum(size)[:-1]]).astype(np.int64)
-        slab = torch.from_numpy(np.frombuffer(b''.join(streams), np.uint8).copy()).to(self.device)
-        out_slab = torch.empty(int(size.sum()), device=self.device, dtype=torch.uint8)
-        status = self.png_decode_into(slab, ranges, geom, out_slab, np.stack([offsets, 3 * geom[:, 1]], axis=1))
-        return out_slab, offsets, [(int(h), int(w)) for h, w, _ in geom], status
+        return self._decode(files, png_probe, lambda f, p: png_stream(f, p[4]), 'PNG', lambda host, *a: self.png_decode_into(*a))
 
     def _cam_args(self, B, cam_rotmat, cam_intrinsics, bbox_scale, bbox_center, img_w, img_h):
         d = self.device

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from tests import render_ref as RR
-from tests.util import golden
+from tests.util import NoLibrary, golden
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = 'specmi_render_meshes'
@@ -40,23 +40,10 @@ def test_null_handle_is_refused():
     assert lib.specmi_render_meshes(None, None, 1, 1, None, 1, None, None, 1., 1., 0., 0., None, 1, 1, rgb, 0, None, None, None, None, None) == _lib.ERR_ARG
 
 
-class _NoLibrary:
-    """An engine whose library must not be reached: the wrapper refuses first."""
-    device = torch.device('cpu')
-    h = None
-
-    @property
-    def lib(self):
-        raise AssertionError('the library was called before the arguments were checked')
-
-    def _stream(self):
-        return None
-
-
 def test_wrapper_refuses_bad_arguments_before_any_library_call():
     from spec_amd import _lib, render
     from spec_amd.engine import Engine
-    eng = _NoLibrary()
+    eng = NoLibrary()
     call = lambda **kw: Engine.render_meshes(eng, **{**good, **kw})
     v, f = RR.octahedron()
     good = dict(vertices=torch.from_numpy(v)[None], faces=torch.from_numpy(f), cam_t=torch.tensor([[0., 0., 5.]]), R=torch.eye(3),

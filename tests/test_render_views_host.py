@@ -4,7 +4,7 @@ what include/specmi.h lists.  No GPU."""
 import numpy as np
 import pytest
 
-from spec_amd import _lib, engine, render
+from spec_amd import _lib, engine, records, render
 
 SIZES, COUNTS = [(33, 47), (64, 96), (40, 40)], [3, 2, 1]
 SIDE = _lib.RENDER_SIDE_VIEW | _lib.RENDER_GROUND_PLANE | _lib.RENDER_CULL
@@ -164,7 +164,7 @@ def test_check_render_views_refuses(name):
 
 
 def test_first_overlap_against_every_byte():
-    """``engine._first_overlap`` reports a pair exactly when two rectangles share a byte, and then a pair that does: against the
+    """``records.first_overlap`` reports a pair exactly when two rectangles share a byte, and then a pair that does: against the
     bytes of every rectangle written out, on seeded sets of small rectangles of mixed pitches, one-row ones among them."""
     rng = np.random.default_rng(5)
     met = 0
@@ -172,11 +172,11 @@ def test_first_overlap_against_every_byte():
         rects = []
         for _ in range(int(rng.integers(2, 7))):
             H, row = int(rng.integers(1, 5)), int(rng.integers(1, 7))
-            pitch = int(rng.integers(row, 13)) if H > 1 else row        # a single row's pitch counts as its row (engine._byte_rects)
+            pitch = int(rng.integers(row, 13)) if H > 1 else row        # a single row's pitch counts as its row (records.byte_rects)
             rects.append((int(rng.integers(0, 120)), pitch, row, H))
         held = [{o + y * p + x for y in range(h) for x in range(r)} for o, p, r, h in rects]
         shared = any(held[a] & held[b] for a in range(len(rects)) for b in range(a))
-        pair = engine._first_overlap(rects)
+        pair = records.first_overlap(rects)
         assert (pair is not None) == shared, rects
         if pair:
             assert pair[0] != pair[1] and held[pair[0]] & held[pair[1]], (rects, pair)

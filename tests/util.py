@@ -24,6 +24,19 @@ def rel_err(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
+class NoLibrary:
+    """An engine whose library must not be reached: the wrapper refuses first."""
+    device = torch.device('cpu')
+    h = None
+
+    @property
+    def lib(self):
+        raise AssertionError('the library was called before the arguments were checked')
+
+    def _stream(self):
+        return None
+
+
 _cache = {}
 
 
