@@ -533,6 +533,44 @@ int specmi_conv2d_backward(specmi_handle* h, const float* x, int B, int H, int W
                            const float* scale_dev, int Cout, int KH, int KW, int stride, int pad, const float* y, int relu,
                            const float* g_y, const float* g_x_add, float* g_x, float* g_w, float* g_res, void* stream);
 
+/* BatchNorm in training mode, with its gradients (spec_amd/csrc/bn_train.hip; STABLE): what nn.BatchNorm2d does in train() after a
+ * convolution of a bottleneck, with the block's residual and ReLU,
+ *     mean[c] = sum_m z[m, c] / M,  var[c] = sum_m (z[m, c] - mean[c])^2 / M (biased),  invstd = 1 / sqrt(var + eps)
+ *     y = (z - mean) invstd gamma + beta (+ residual), and max(., 0) with relu != 0
+ * z / y / residual / g_y / g_z / g_res are dense (M, C) fp32 with C contiguous - NHWC with M = B H W - and gamma / beta / mean /
+ * invstd / running_mean / running_var / g_gamma / g_beta are (C) vectors; all device pointers, read where torch keeps them.  Nothing
+ * of the handle's committed model is read and the stream is not synchronised; both calls work on a handle of any kind, committed
+ * or not.  Any M >= 2 and C >= 1 with M C < 2^31: tails in M and C are handled in the kernel and no access leaves a tensor.
+ * specmi_batchnorm_train_forward writes y and saves mean and invstd (C) for the backward.  residual may be NULL.  With
+ *   running_mean / running_var given (both or neither) they are updated in place by torch's rule with the factor `momentum`
+ *   (bn.momentum, or 1 / num_batches_tracked where that is None):
+ *     running_mean = (1 - f) running_mean + f mean,   running_var = (1 - f) running_var + f var M / (M - 1)
+ *   each evaluated in double from the fp32 values and rounded once, as invstd is: f = 0 leaves their bits, f = 1 replaces them.
+ *   The variance is never E[z^2] - E[z]^2: every chunk of rows is centred on its own mean and the chunks are merged by Chan's rule.
+ * specmi_batchnorm_backward: the forward's z, gamma, mean, invstd, its output y (read only with relu != 0: may be NULL otherwise)
+ *   and g_y ->
+ *     g = relu ? (y > 0 ? g_y : 0) : g_y          (the convention of specmi_conv2d_backward: an exact zero passes no gradient)
+ *     g_res = g,   g_beta[c] = sum_m g,   g_gamma[c] = sum_m g xhat,   xhat = (z - mean) invstd
+ *     g_z = gamma invstd (g - g_beta / M - xhat g_gamma / M)
+ *   g_z, g_gamma, g_beta and g_res may be NULL (not wanted), but not all of them; g_res may be g_y itself.
+ * Deterministic, the rule of specmi_smpl_backward: no float atomics; the M rows are cut into chunks of SPECMI_BN_ROWS_PER_CHUNK rows
+ * (chunk k = rows 64 k ..) and the chunks' partial results are combined in an order fixed by (M, C) alone, never by the device or
+ * by what else is wanted: two runs give the same bits and a wanted output has the same bits whatever else is wanted.  Unlike the
+ * convolution layer, image b's y and g_z DO depend on the other images of its batch - the statistics are the batch's.
+ * Workspace: (2 ceil(M / SPECMI_BN_ROWS_PER_CHUNK) + 2) C floats in the handle; it grows on the first call of a shape, afterwards
+ * nothing is allocated and the calls can be captured into a graph.
+ * Refusals (SPECMI_ERR_ARG with a message, nothing launched, nothing written): M < 2 (torch refuses one value per channel in
+ * training, so does this call); C < 1; M C >= 2^31; z, gamma, beta, y, mean, invstd (forward) or z, gamma, mean, invstd, g_y
+ * (backward) NULL; y NULL with relu (backward); every output NULL (backward); eps < 0; momentum outside [0, 1]; exactly one of
+ * running_mean / running_var; a float pointer that is not 4-byte aligned. */
+#define SPECMI_BN_ROWS_PER_CHUNK 64
+int specmi_batchnorm_train_forward(specmi_handle* h, const float* z, int M, int C, const float* gamma, const float* beta,
+                                   const float* residual, int relu, float eps, float momentum, float* running_mean,
+                                   float* running_var, float* y, float* mean, float* invstd, void* stream);
+int specmi_batchnorm_backward(specmi_handle* h, const float* z, int M, int C, const float* gamma, const float* mean,
+                              const float* invstd, const float* y, int relu, const float* g_y, float* g_z, float* g_gamma,
+                              float* g_beta, float* g_res, void* stream);
+
 /* The frozen part of a fine-tuning step (STABLE): the committed fp32 ResNet trunk's own op list up to the last op of
  * layer{n_stages}, n_stages in 1 .. 4, whose block output goes NHWC to `out` ((B, h, w, C): stride 4, 8, 16, 32 and 256, 512,
  * 1024, 2048 channels for a Bottleneck trunk).  The same kernels, plan and k order as specmi_trunk_forward: with n_stages = 4 `out`

@@ -1440,14 +1440,144 @@ def conv_backward_section(a):
     return out
 
 
+def bn_train_section(a):
+    """BatchNorm in training mode (``specmi_batchnorm_train_forward`` / ``specmi_batchnorm_backward``, spec_amd/csrc/bn_train.hip) at
+    every distinct BatchNorm shape of layer4 in the fine-tuning step - the output maps of the layers ``conv_backward_section`` times, at
+    CamCalib's shape (B = 64, the 38 x 63 stage-3 map) and SPEC's (B = 64, 14 x 14): the forward (statistics, running statistics,
+    apply, ReLU; the residual where the BatchNorm is bn3) and forward + backward, each next to torch's ``F.batch_norm`` (+ residual,
+    ReLU) with its autograd backward on the same device tensors (channels_last views), alternated in this process, 3 rounds of
+    ``iters`` back-to-back calls after a warm-up; the library's kernels by its profiler with the bytes they must move over their
+    time; then the whole fine-tuning step with layer4 unfrozen on batch statistics against the same step on frozen BatchNorm, and the
+    share of ``conv_bwd_prep_kernel`` - with the identity scale a plain copy of g_z - in it."""
+    import torch.nn.functional as F
+    from spec_amd import camcalib_eval as ce
+    from spec_amd.cam_utils import _engine
+    dev = torch.device('cuda', 0)
+    eng = _engine(dev)
+    bs = int(ce.DEFAULTS['DATASET']['BATCH_SIZE'])
+    # (name, map of the stage's input 0 / output 1, channels, residual)
+    bns = [('0.bn1', 0, 512, False), ('n.bn2', 1, 512, False), ('n.bn3', 1, 2048, True), ('0.downsample.1', 1, 2048, False)]
+    shapes = {'camcalib_b%d_38x63' % bs: (bs, 38, 63), 'spec_b64_14x14': (64, 14, 14)}
+
+    def ms_per_call(fn):
+        for _ in range(3):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(a.iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.iters
+    out = {}
+    for sname, (B, h, w) in shapes.items():
+        for lname, on_out, Cn, with_res in bns:
+            H, W = ((h + 1) // 2, (w + 1) // 2) if on_out else (h, w)
+            relu = lname != '0.downsample.1'
+            torch.manual_seed(H + W + Cn)
+            z = torch.randn(B, H, W, Cn, device=dev)
+            gamma, beta = 0.5 + torch.rand(Cn, device=dev), 0.3 * torch.randn(Cn, device=dev)
+            rm, rv = torch.zeros(Cn, device=dev), torch.ones(Cn, device=dev)
+            res = torch.randn_like(z) if with_res else None
+            g_y = torch.randn_like(z)
+            want = (True, True, True, with_res)
+
+            def lib_fwd():
+                return eng.batchnorm_train_forward(z, gamma, beta, 1e-5, res, relu, rm, rv, 0.1)
+
+            def lib_both():
+                y, mean, invstd = lib_fwd()
+                return eng.batchnorm_backward(z, gamma, mean, invstd, y if relu else None, g_y, relu, want)
+            zt, gt, bt = z.permute(0, 3, 1, 2).requires_grad_(True), gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+            rt = res.permute(0, 3, 1, 2).requires_grad_(True) if with_res else None
+            gn = g_y.permute(0, 3, 1, 2)
+
+            def torch_fwd():
+                with torch.enable_grad():
+                    y = F.batch_norm(zt, rm, rv, gt, bt, True, 0.1, 1e-5)
+                    y = y + rt if with_res else y
+                    return torch.relu(y) if relu else y
+
+            def torch_both():
+                torch.autograd.grad(torch_fwd(), [zt, gt, bt] + ([rt] if with_res else []), gn)
+            calls = {'forward': (lib_fwd, torch_fwd), 'forward_backward': (lib_both, torch_both)}
+            rounds = {p: {'library': [], 'torch': []} for p in calls}
+            for _ in range(3):                                          # alternated: both see the same clocks and the same neighbours
+                for p, (mine, theirs) in calls.items():
+                    rounds[p]['library'].append(ms_per_call(mine))
+                    rounds[p]['torch'].append(ms_per_call(theirs))
+            kern = timed(eng, lib_both, a.iters)
+            row = {'workload': f'(M, C) = ({B * H * W}, {Cn}): B = {B}, {H} x {W}' + (', relu' if relu else '') + (', residual' if with_res else ''),
+                   'kernels_by_the_library_profiler': {kk: {'ms_per_launch': round(v[0], 5), 'algorithmic_MB': round(v[1] / 1e6, 3),
+                                                            'achieved_GBps': round(v[1] / (v[0] * 1e-3) / 1e9, 1),
+                                                            'frac_of_hbm_peak': round(v[1] / (v[0] * 1e-3) / HBM_PEAK, 4)} for kk, v in kern.items()}}
+            for p in calls:
+                lib, tor = float(np.median(rounds[p]['library'])), float(np.median(rounds[p]['torch']))
+                names = [k for k in kern if k.startswith('bn_train')] + ([k for k in kern if k.startswith('bn_bwd')] if p == 'forward_backward' else [])
+                by = sum(kern[k][1] for k in names)
+                row[p] = {'library_ms': round(lib, 5), 'torch_ms': round(tor, 5), 'library_over_torch': round(lib / tor, 3),
+                          'algorithmic_MB': round(by / 1e6, 3), 'library_GBps_over_the_call': round(by / (lib * 1e-3) / 1e9, 1),
+                          'library_rounds_ms': [round(v, 5) for v in rounds[p]['library']], 'torch_rounds_ms': [round(v, 5) for v in rounds[p]['torch']]}
+            out[f'{sname}.layer4.{lname}'] = row
+            print(sname, lname, {p: (row[p]['library_ms'], row[p]['torch_ms']) for p in calls}, flush=True)
+            del z, res, g_y, zt, rt, gn
+    # the whole step: stages=3 under no_grad -> ResNetStage -> heads -> loss -> backward -> Adam, on batch statistics against frozen BatchNorm
+    from spec_amd import synth
+    from spec_amd.camcalib_train import trunk_features
+    from spec_amd.differentiable import CameraRegressorHead, ResNetStage
+    from spec_amd.losses import CameraRegressorLoss
+    from spec_amd.modules import CameraRegressorNetwork
+    net = CameraRegressorNetwork()
+    net.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in synth.camcalib_state(1001).items()}, strict=False)
+    net = net.to(dev).eval()
+    net.set_plan('throughput')
+    net.commit(dev, freeze=True)
+    images = torch.randn(bs, 3, 600, 1000, device=dev)
+    targets = [torch.randint(0, 256, (bs,), device=dev) for _ in range(3)]
+    head, crit = CameraRegressorHead.from_model(net), CameraRegressorLoss(1.0, 1.0, 1.0, 'ce')
+    stages = {'frozen': ResNetStage.from_model(net, 'layer4', 'frozen'), 'batch': ResNetStage.from_model(net, 'layer4', 'batch')}
+    opts = {'frozen': torch.optim.Adam(list(head.parameters()) + stages['frozen'].conv_parameters(), lr=1e-6),
+            'batch': torch.optim.Adam(list(head.parameters()) + stages['batch'].conv_parameters() + stages['batch'].bn_parameters(), lr=1e-6)}
+
+    def step(which):
+        def run():
+            net.backbone.layer4.train(which == 'batch')                 # the blocks alone; the stages share them
+            feat = trunk_features(net, images, stages=3)
+            with torch.enable_grad():
+                loss, _ = crit(*head(stages[which](feat), channels_last=True), *targets)
+                opts[which].zero_grad(set_to_none=True)
+                loss.backward()
+            opts[which].step()
+        return run
+    rounds = {k: [] for k in opts}
+    for _ in range(3):
+        for k in opts:
+            rounds[k].append(ms_per_call(step(k)))
+    med = {k: float(np.median(v)) for k, v in rounds.items()}
+    kern = timed(eng, step('batch'), a.iters)
+    net.backbone.layer4.eval()
+    per_step = {k: v[0] * v[3] for k, v in kern.items()}
+    out['whole_step'] = {'workload': f'ResNet-50 CamCalib, B = {bs} frames of 600 x 1000, ce loss, Adam: frozen trunk -> layer4 with gradients -> heads -> loss -> '
+                         'backward -> step; BatchNorm of layer4 frozen, or on batch statistics with gamma / beta trained',
+                         'ms_round_values': {k: [round(x, 3) for x in v] for k, v in rounds.items()}, 'ms_median': {k: round(v, 3) for k, v in med.items()},
+                         'batch_over_frozen': round(med['batch'] / med['frozen'], 3),
+                         'stage_kernels_ms_per_batch_step_by_the_library_profiler': {k: round(v, 4) for k, v in sorted(per_step.items())},
+                         'bn_kernels_share_of_the_batch_step': round(sum(v for k, v in per_step.items() if k.startswith('bn_')) / med['batch'], 4),
+                         'conv_bwd_prep_share_of_the_batch_step': round(per_step.get('conv_bwd_prep', 0.0) / med['batch'], 4)}
+    print(json.dumps(out['whole_step'], indent=1))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'color_jitter', 'smpl_backward', 'head_train', 'camcalib_train', 'conv_backward'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'color_jitter', 'smpl_backward', 'head_train', 'camcalib_train', 'conv_backward', 'bn_train'], default=None, help='run one section only')
     ap.add_argument('--smpl-backward', dest='only', action='store_const', const='smpl_backward', help='the same as --only smpl_backward')
     ap.add_argument('--head-train', dest='only', action='store_const', const='head_train', help='the same as --only head_train')
     ap.add_argument('--camcalib-train', dest='only', action='store_const', const='camcalib_train', help='the same as --only camcalib_train')
     ap.add_argument('--conv-backward', dest='only', action='store_const', const='conv_backward',
                     help='the same as --only conv_backward (writes profiles/conv_backward_aux.json unless --out is given)')
+    ap.add_argument('--bn-train', dest='only', action='store_const', const='bn_train',
+                    help='the same as --only bn_train (writes profiles/bn_train_aux.json unless --out is given)')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -1502,6 +1632,18 @@ def main():
             json.dump({'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the same calls; library and torch '
                        'alternated, 3 rounds, medians; kernels: per-launch HIP events (library profiler)', 'conv_backward': row,
                        'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'bn_train':
+        from spec_amd import _lib
+        row = bn_train_section(a)
+        path = a.out if a.out != ap.get_default('out') else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                                                         'bn_train_aux.json')
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, 'w') as f:
+            json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the '
+                       'same calls; library and torch alternated, 3 rounds, medians; kernels: per-launch HIP events (library profiler), bytes = what '
+                       'the kernel must move, computed from the shape', 'bn_train': row, 'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     def add(name, workload, res, per_unit=None):

@@ -3,11 +3,12 @@
 (camcalib/trainer.py:60-82,201-205) that adapts a released checkpoint to other cameras:
 
     python scripts/camcalib_finetune.py --cfg camcalib_config.yaml [--ckpt FILE] [--epochs 5] [--out FILE] [--augment [--train-split]]
-                                        [--opts OPTIMIZER.LR 0.0003 ...]
+                                        [--unfreeze layer4 [--bn batch]] [--opts OPTIMIZER.LR 0.0003 ...]
 
 The trunk stays FROZEN and committed; only the three FC heads (fc_vfov / fc_pitch / fc_roll) are trained, on the trunk's pooled
-features, under ``CameraRegressorLoss(MODEL.LOSS_*)`` with ``torch.optim.Adam(lr=OPTIMIZER.LR)``.  No trunk backward, no BatchNorm
-in training mode.  ``--augment`` applies the reference's training ColorJitter (brightness, contrast, saturation 0.2, hue 0.1:
+features, under ``CameraRegressorLoss(MODEL.LOSS_*)`` with ``torch.optim.Adam(lr=OPTIMIZER.LR)``.  ``--unfreeze layer4`` also trains
+the last ResNet stage, on frozen BatchNorm or with ``--bn batch`` on batch statistics with gamma / beta trained, as the reference's
+``training_step`` runs it; the stem and layers 1-3 stay frozen.  ``--augment`` applies the reference's training ColorJitter (brightness, contrast, saturation 0.2, hue 0.1:
 camcalib/pano_dataset.py:65) to every frame on the device, in Pillow's bytes, seeded by ``--augment-seed``; ``--train-split``
 takes the frames ``train_images.pkl`` lists, as the reference's ``is_train=True`` half does.  The labelled frames are those of ``DATASET.VAL_DS`` under ``--data-root``
 (``data/dataset_folders/pano`` / ``pano_scalenet``: the frames ``val_images.pkl`` lists), batched ``DATASET.BATCH_SIZE`` at a time in
@@ -46,8 +47,13 @@ def main():
     ap.add_argument('--train-split', action='store_true', help='train on the frames train_images.pkl lists (default: val_images.pkl)')
     ap.add_argument('--unfreeze', nargs='*', default=[], choices=['layer4'], metavar='STAGE',
                     help="also train the conv weights of this ResNet stage on frozen BatchNorm ('layer4' is the one built)")
+    ap.add_argument('--bn', choices=['frozen', 'batch'], default='frozen',
+                    help="BatchNorm of the unfrozen stage: 'frozen' = its running statistics, gamma / beta untouched; 'batch' = the "
+                         "reference's training mode: batch statistics, running statistics moved, gamma / beta trained (needs --unfreeze layer4)")
     ap.add_argument('--report', type=str, default=None, metavar='train.json')
     args = ap.parse_args()
+    if args.bn == 'batch' and not args.unfreeze:
+        ap.error("--bn batch trains the BatchNorms of an unfrozen stage: add --unfreeze layer4")
     from spec_amd import camcalib_eval as ce
     from spec_amd import camcalib_train as ct
     root, cfg = args.data_root, args.cfg
@@ -62,7 +68,7 @@ def main():
         dataset = panorama.PanoViewDataset(panorama.list_panoramas(args.panoramas), args.views_per_pano, args.seed)
     res = ct.finetune_heads(hp, data_root=root, ckpt=args.ckpt, epochs=args.epochs, seed=args.seed, out=args.out, dataset=dataset,
                             augment=args.augment, augment_seed=args.augment_seed, split='train' if args.train_split else 'val',
-                            unfreeze=tuple(args.unfreeze))
+                            unfreeze=tuple(args.unfreeze), bn=args.bn)
     if args.report:
         with open(args.report, 'w') as f:
             json.dump({k: res[k] for k in ('ckpt', 'epochs', 'before', 'after')}, f, indent=1)

@@ -56,6 +56,7 @@ HMR_LOSS, HMR_CAM_LOSS = 0, 1                 # SPECMI_HMR_LOSS / SPECMI_HMR_CAM
 # the ground-truth tensors of specmi_hmr_loss in the order of its prototype, per-image shapes (None = (V, 3)); int32 where named has_*
 HMR_LOSS_GT = (('pose', (72,)), ('betas', (10,)), ('pose_conf', (24,)), ('pose_3d', (24, 4)), ('keypoints', (49, 3)), ('vertices', None),
                ('has_smpl', ()), ('has_pose_3d', ()), ('orig_shape', (2,)), ('scale', ()))
+BN_ROWS_PER_CHUNK = 64                        # SPECMI_BN_ROWS_PER_CHUNK: the rows of a chunk of the BatchNorm reductions (include/specmi.h)
 LOSS_TYPES = {'ce': 0, 'kl': 1, 'softargmax_l2': 2, 'softargmax_biased_l2': 3}     # SPECMI_LOSS_* (include/specmi.h)
 
 c_float_p = C.POINTER(C.c_float)
@@ -181,6 +182,11 @@ PROTOTYPES = {
     # (h, x, B, H, W, Cin, w, scale, Cout, KH, KW, stride, pad, y, relu, g_y, g_x_add, g_x, g_w, g_res, stream)
     'specmi_conv2d_backward': (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_int] * 5 +
                                [C.c_void_p, C.c_int] + [C.c_void_p] * 6),
+    # (h, z, M, C, gamma, beta, residual, relu, eps, momentum, running_mean, running_var, y, mean, invstd, stream)
+    'specmi_batchnorm_train_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_float, C.c_float] +
+                                       [C.c_void_p] * 6),
+    # (h, z, M, C, gamma, mean, invstd, y, relu, g_y, g_z, g_gamma, g_beta, g_res, stream)
+    'specmi_batchnorm_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 6),
     # (h, images, B, H, W, n_stages, out, stream)
     'specmi_trunk_forward_stages': (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     'specmi_conv2d': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

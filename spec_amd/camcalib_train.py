@@ -20,8 +20,14 @@ statistics, sharing the model's conv weights; ``specmi_conv2d_train_forward`` / 
 -> ``backward()``, and Adam steps the head parameters and the stage's conv weights.  The written checkpoint holds the stepped trunk
 weights and the after-evaluation runs on the recommitted model.
 
-Out of scope, as for the SPEC side: the backward of the stem and of layers 1-3 (through a max-pool backward),
-BatchNorm in training mode (batch statistics; gamma / beta stay as they are), an fp16 backward, 'pano_agora'
+``bn='batch'`` (with ``unfreeze=('layer4',)``) is the reference's own semantics - its trainer is a Lightning module, the network is
+in ``train()`` during ``training_step``: the stage's blocks are put in ``train()`` for the epochs, every BatchNorm of layer4
+normalises with the statistics of the batch (``specmi_batchnorm_train_forward`` / ``specmi_batchnorm_backward``), its running
+statistics move and ``num_batches_tracked`` counts, and Adam steps gamma and beta too.  Afterwards the blocks go back to ``eval()``,
+the model is committed again - the folded trunk carries the trained running statistics - and the checkpoint holds them.
+
+Out of scope, as for the SPEC side: the backward of the stem and of layers 1-3 (through a max-pool backward,
+so their BatchNorms stay frozen), SyncBatchNorm across GPUs, an fp16 backward, 'pano_agora'
 (the frames are those the tree's ``val_images.pkl`` / ``train_images.pkl`` list, or a ``dataset`` object with
 ``PanoValDataset``'s interface), second derivatives.
 """
@@ -71,7 +77,7 @@ def write_checkpoint(model, path: str, epoch: int, global_step: int) -> str:
 
 def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = None, epochs: int = 1, seed: int = 0, out: Optional[str] = None,
                    dataset=None, model=None, log=print, device='cuda', evaluate: bool = True, augment: bool = False, augment_seed: int = 0,
-                   split: str = 'val', unfreeze=()) -> dict:
+                   split: str = 'val', unfreeze=(), bn: str = 'frozen') -> dict:
     """Fine-tuning (module docstring) for ``epochs`` passes over the labelled frames.  Logs the four ``train/...`` means
     per epoch, runs ``camcalib_eval.run_evaluation`` before and after (``evaluate``), and writes the Lightning-layout checkpoint
     ``out`` (None: ``LOG_DIR/camcalib_finetuned.ckpt``).  -> dict(model, ckpt, epochs = the per-epoch means, before / after = the
@@ -80,12 +86,18 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     frame by frame from a torch CPU generator seeded with ``augment_seed`` - and resized from there; False: exactly the flow
     without it.  ``split``: which list of the tree the training frames come from (the evaluations keep reading 'val').
     ``unfreeze``: ``()`` trains the heads alone; ``('layer4',)`` also the conv weights of the last ResNet stage on frozen BatchNorm
-    (the only other value built)."""
+    (the only other value built).  ``bn``: 'frozen' = the stage on its running statistics, gamma / beta untouched; 'batch' = the stage
+    in ``train()`` on batch statistics, gamma / beta trained, the running statistics moved (module docstring) - refused with
+    ``unfreeze=()``, where no BatchNorm is trained."""
     from .differentiable import CameraRegressorHead, ResNetStage
     unfreeze = tuple(unfreeze)
     if unfreeze not in ((), ('layer4',)):
         raise NotImplementedError(f"unfreeze = {unfreeze!r}: () and ('layer4',) are built (DESIGN.md section 6: the stem and layers 1-3 need "
                                   'a max-pool backward)')
+    if bn not in ('frozen', 'batch'):
+        raise ValueError(f"bn = {bn!r}: 'frozen' and 'batch' are built")
+    if bn == 'batch' and not unfreeze:
+        raise ValueError("bn = 'batch' trains the BatchNorms of an unfrozen stage: pass unfreeze=('layer4',)")
     from .losses import CameraRegressorLoss
     dev = torch.device(device)
     m = hparams['MODEL']
@@ -105,8 +117,9 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     before = run_eval() if evaluate else None
     head = CameraRegressorHead.from_model(model)
     crit = CameraRegressorLoss(float(m['LOSS_VFOV_WEIGHT']), float(m['LOSS_PITCH_WEIGHT']), float(m['LOSS_ROLL_WEIGHT']), m['LOSS_TYPE'])
-    stage = ResNetStage.from_model(model, 'layer4') if unfreeze else None
-    optim = torch.optim.Adam(list(head.parameters()) + (stage.conv_parameters() if stage is not None else []), lr=float(opt_cfg['LR']), weight_decay=float(opt_cfg['WD']))
+    stage = ResNetStage.from_model(model, 'layer4', bn) if unfreeze else None
+    trained = list(head.parameters()) + (stage.conv_parameters() if stage is not None else []) + (stage.bn_parameters() if bn == 'batch' else [])
+    optim = torch.optim.Adam(trained, lr=float(opt_cfg['LR']), weight_decay=float(opt_cfg['WD']))
     bs, min_res, max_res = int(hparams['DATASET']['BATCH_SIZE']), int(hparams['DATASET']['MIN_RES']), hparams['DATASET']['MAX_RES']
     rng = np.random.default_rng(seed)
     eng = model.engine(dev)
@@ -117,6 +130,8 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         jitter, jitter_rng = ColorJitter(**CAMCALIB_TRAIN_JITTER), torch.Generator().manual_seed(int(augment_seed))
     log(f'Train dataset len: {len(ds)}')
     history, step = [], 0
+    if bn == 'batch':
+        stage.blocks.train()                  # the blocks alone: the model itself has no training mode
     for epoch in range(int(epochs)):
         order = rng.permutation(len(ds))
         sums = torch.zeros(4, device=dev)
@@ -142,6 +157,8 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         means = (sums / max(nb, 1)).cpu().tolist()
         history.append(dict(zip(TRAIN_KEYS, (float(v) for v in means))))
         log(f'[EPOCH {epoch}] ' + ', '.join(f'{k}: {v:.6g}' for k, v in history[-1].items()))
+    if bn == 'batch':
+        stage.blocks.eval()
     model.commit(dev, freeze=True)            # the frozen model skips the per-forward check: commit the stepped weights now
     after = run_eval() if evaluate else None
     if out is None:

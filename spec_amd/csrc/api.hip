@@ -3020,6 +3020,55 @@ int specmi_conv2d_backward(specmi_handle* h, const float* x, int B, int H, int W
     return SPECMI_OK;
 }
 
+// the argument checks specmi_batchnorm_train_forward and specmi_batchnorm_backward share, and the kernels' argument block
+static int bn_args(specmi_handle* h, const char* who, const float* z, int M, int C, const float* gamma, int relu, BnArgs& a) {
+    if (M < 2) return fail(h, SPECMI_ERR_ARG, "%s: M = %d: batch statistics need more than one value per channel", who, M);
+    if (C < 1) return fail(h, SPECMI_ERR_ARG, "%s: C = %d must be >= 1", who, C);
+    if ((double)M * C >= 2147483648.0) return fail(h, SPECMI_ERR_ARG, "%s: the tensor has 2^31 elements or more (M = %d, C = %d)", who, M, C);
+    if (!z || !gamma) return fail(h, SPECMI_ERR_ARG, "%s: z or gamma is NULL", who);
+    a = BnArgs{z, gamma, M, C, relu != 0};
+    return SPECMI_OK;
+}
+
+int specmi_batchnorm_train_forward(specmi_handle* h, const float* z, int M, int C, const float* gamma, const float* beta, const float* residual,
+                                   int relu, float eps, float momentum, float* running_mean, float* running_var, float* y, float* mean,
+                                   float* invstd, void* stream) {
+    ENTER(h);
+    BnArgs a;
+    if (int rc = bn_args(h, "batchnorm_train_forward", z, M, C, gamma, relu, a)) return rc;
+    if (!beta || !y || !mean || !invstd) return fail(h, SPECMI_ERR_ARG, "batchnorm_train_forward: beta, y, mean or invstd is NULL");
+    if (!(eps >= 0.f)) return fail(h, SPECMI_ERR_ARG, "batchnorm_train_forward: eps = %g must be >= 0", (double)eps);
+    if (!(momentum >= 0.f && momentum <= 1.f))
+        return fail(h, SPECMI_ERR_ARG, "batchnorm_train_forward: the momentum factor %g must be in [0, 1]", (double)momentum);
+    if (!running_mean != !running_var)
+        return fail(h, SPECMI_ERR_ARG, "batchnorm_train_forward: running_mean and running_var are given together or not at all");
+    if (misaligned4({z, gamma, beta, residual, running_mean, running_var, y, mean, invstd}))
+        return fail(h, SPECMI_ERR_ARG, "batchnorm_train_forward: a float pointer is not 4-byte aligned");
+    if (int rc = grow_ragged(h, h->buf[BUF_bn_train], bn_ws_floats(M, C) * 4, "the BatchNorm training workspace")) return rc;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "bn.train_forward"};
+    LAUNCHCHK(h, launch_bn_train_forward(a, beta, residual, eps, momentum, running_mean, running_var, y, mean, invstd,
+                                         (float*)h->buf[BUF_bn_train].p, ctx), "batchnorm_train_forward");
+    return SPECMI_OK;
+}
+
+int specmi_batchnorm_backward(specmi_handle* h, const float* z, int M, int C, const float* gamma, const float* mean, const float* invstd,
+                              const float* y, int relu, const float* g_y, float* g_z, float* g_gamma, float* g_beta, float* g_res,
+                              void* stream) {
+    ENTER(h);
+    BnArgs a;
+    if (int rc = bn_args(h, "batchnorm_backward", z, M, C, gamma, relu, a)) return rc;
+    if (!mean || !invstd || !g_y) return fail(h, SPECMI_ERR_ARG, "batchnorm_backward: mean, invstd or g_y is NULL");
+    if (relu && !y) return fail(h, SPECMI_ERR_ARG, "batchnorm_backward: relu needs y (the mask is y > 0)");
+    if (!g_z && !g_gamma && !g_beta && !g_res) return fail(h, SPECMI_ERR_ARG, "batchnorm_backward: every output is NULL");
+    if (misaligned4({z, gamma, mean, invstd, y, g_y, g_z, g_gamma, g_beta, g_res}))
+        return fail(h, SPECMI_ERR_ARG, "batchnorm_backward: a float pointer is not 4-byte aligned");
+    if (int rc = grow_ragged(h, h->buf[BUF_bn_train], bn_ws_floats(M, C) * 4, "the BatchNorm training workspace")) return rc;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "bn.backward"};
+    LAUNCHCHK(h, launch_bn_backward(a, mean, invstd, y, g_y, g_z, g_gamma, g_beta, g_res, (float*)h->buf[BUF_bn_train].p, ctx),
+              "batchnorm_backward");
+    return SPECMI_OK;
+}
+
 // the argument checks of specmi_camcalib_loss and its backward, and the kernels' argument block
 static int cam_loss_args(specmi_handle* h, const char* who, const float* lv, const float* lp, const float* lr, int B, int nbins, int loss_type,
                          const void* tv, const void* tp, const void* tr, float wv, float wp, float wr, CamLossArgs& a) {

@@ -156,6 +156,7 @@ enum Buf {
     BUF_jitter,     // specmi_color_jitter: one 64-bit sum of L per frame
     BUF_conv_bwd,   // specmi_conv2d_backward: conv_bwd_ws_floats floats (the gradient operand G)
     BUF_conv_fwd,   // specmi_conv2d_train_forward: conv_fwd_ws_floats floats (the weights transposed for this call)
+    BUF_bn_train,   // specmi_batchnorm_train_forward / specmi_batchnorm_backward: bn_ws_floats floats (the chunk partials)
     BUF_COUNT
 };
 

@@ -502,6 +502,20 @@ int launch_conv_train_forward(const ConvTrainArgs& t, const float* residual, int
 int launch_conv_backward(const ConvTrainArgs& t, const float* y, int relu, const float* g_y, const float* g_x_add, float* g_x, float* g_w,
                          float* g_res, float* ws, const LaunchCtx& ctx);
 
+// BatchNorm in training mode with its backward (bn_train.hip; include/specmi.h: specmi_batchnorm_train_forward): z and
+// y / residual / g_y / g_z / g_res dense (M, C) fp32, C contiguous; gamma / beta / mean / invstd / the running statistics (C).  ws is
+// bn_ws_floats floats for both calls.  residual and the two running statistics may be null; in the backward g_z, g_gamma, g_beta
+// and g_res may be null (not wanted), y is read only with relu, g_res may be g_y itself.
+struct BnArgs {
+    const float* z; const float* gamma;
+    int M, C, relu;
+};
+size_t bn_ws_floats(int M, int C);
+int launch_bn_train_forward(const BnArgs& a, const float* beta, const float* residual, float eps, float f, float* running_mean,
+                            float* running_var, float* y, float* mean, float* invstd, float* ws, const LaunchCtx& ctx);
+int launch_bn_backward(const BnArgs& a, const float* mean, const float* invstd, const float* y, const float* g_y, float* g_z, float* g_gamma,
+                       float* g_beta, float* g_res, float* ws, const LaunchCtx& ctx);
+
 // ----------------------------------------------------------------------------------------
 // evaluation metrics  (eval.hip)
 // ----------------------------------------------------------------------------------------

@@ -17,9 +17,12 @@ two or three with no activation between them) on the pooled feature, forward and
 (``specmi_camcalib_head_train_forward`` / ``specmi_camcalib_head_backward``) - with ``spec_amd.losses.CameraRegressorLoss`` the
 differentiable tail of the reference's CamCalib ``training_step`` on a frozen trunk.
 
-Below the pooled feature :class:`ResNetStage`: one stage of a Bottleneck ResNet trunk on frozen BatchNorm, every block one
+Below the pooled feature :class:`ResNetStage`: one stage of a Bottleneck ResNet trunk, every block one
 ``torch.autograd.Function`` over the trainable conv layer (``specmi_conv2d_train_forward`` / ``specmi_conv2d_backward``;
 spec_amd/csrc/conv_bwd.hip) - with ``Engine.trunk(images, stages=3)`` as the frozen part, layer4 of either network fine-tunes.
+Its BatchNorm is frozen (``bn='frozen'``, the default) or, as in the reference's ``training_step``, runs on the statistics of the
+batch with its running statistics moving and gamma / beta trained (``bn='batch'``; ``specmi_batchnorm_train_forward`` /
+``specmi_batchnorm_backward``, spec_amd/csrc/bn_train.hip).
 
 First derivatives only (``once_differentiable``).  The camera arguments (``cam_rotmat``, ``cam_intrinsics``, the box, the image
 size) get no gradient.  With no input requiring grad the heads return exactly what ``Engine.smpl`` returns.
@@ -387,24 +390,153 @@ class _Bottleneck(torch.autograd.Function):
         return (None, None, None, g_x) + tuple(g_w)
 
 
+def _identity_affine(eng, n):
+    """The identity affine map of a layer with n output channels, (ones, zeros) on the engine's device, cached on the engine: with it
+    ``specmi_conv2d_train_forward`` is the plain product and ``specmi_conv2d_backward`` the product's own gradients."""
+    cache = eng.__dict__.setdefault('_identity_affine', {})
+    if n not in cache:
+        cache[n] = (torch.ones(n, device=eng.device), torch.zeros(n, device=eng.device))
+    return cache[n]
+
+
+def _block_bns(blk):
+    return [blk.bn1, blk.bn2, blk.bn3] + ([blk.downsample[1]] if hasattr(blk, 'downsample') else [])
+
+
+def _bn_step(bn):
+    """What ``nn.BatchNorm2d.forward`` does before it normalises in training mode: ``num_batches_tracked`` + 1 and the factor of the
+    running-statistics update -> (eps, factor, running_mean, running_var), the last two None for a module that tracks none."""
+    if bn.running_mean is None:
+        return float(bn.eps), 0.0, None, None
+    with torch.no_grad():
+        bn.num_batches_tracked.add_(1)
+    f = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else float(bn.momentum)
+    return float(bn.eps), f, bn.running_mean, bn.running_var
+
+
+def _conv_bn(eng, x, w, stride, pad, gamma, beta, step, residual=None, relu=True):
+    """One conv + training-mode BatchNorm [+ residual] [+ ReLU] -> (z, y, mean, invstd): the conv as a plain product, then
+    ``specmi_batchnorm_train_forward``, which also moves the running statistics of ``step`` (``_bn_step``) in place."""
+    eps, f, rm, rv = step
+    z = eng.conv2d_train_forward(x, w, *_identity_affine(eng, w.shape[0]), stride, pad, relu=False)
+    y, mean, invstd = eng.batchnorm_train_forward(z, gamma, beta, eps, residual, relu, rm, rv, f)
+    for t in (rm, rv):
+        if t is not None:
+            torch.autograd.graph.increment_version(t)         # written through its pointer: whoever watches the version sees it
+    return z, y, mean, invstd
+
+
+def _bottleneck_batch_forward(eng, stride, steps, x, ws, gammas, betas):
+    """The bottleneck on batch statistics -> (out, tape): tape = [(z, y, mean, invstd)] in the order conv1, conv2, conv3[, downsample]."""
+    t1 = _conv_bn(eng, x, ws[0], 1, 0, gammas[0], betas[0], steps[0])
+    t2 = _conv_bn(eng, t1[1], ws[1], stride, 1, gammas[1], betas[1], steps[1])
+    td = _conv_bn(eng, x, ws[3], stride, 0, gammas[3], betas[3], steps[3], relu=False) if len(ws) == 4 else None
+    t3 = _conv_bn(eng, t2[1], ws[2], 1, 0, gammas[2], betas[2], steps[2], residual=td[1] if td is not None else x)
+    return t3[1], [t1, t2, t3] + ([td] if td is not None else [])
+
+
+class _BottleneckBatch(torch.autograd.Function):
+    """``_Bottleneck`` on BATCH statistics: (x NHWC, the n conv weights, the n gammas, the n betas) -> the block's output NHWC, n = 3
+    or 4 in the order conv1, conv2, conv3[, downsample]; ``steps`` = ``_bn_step`` of the BatchNorms in the same order.  Saves z, mean
+    and invstd of every BatchNorm; the backward runs ``specmi_batchnorm_backward`` and then ``specmi_conv2d_backward`` on g_z with the
+    identity scale and no ReLU."""
+
+    @staticmethod
+    def forward(ctx, eng, stride, steps, x, *params):
+        n = len(params) // 3
+        xd, pd = x.detach().float().contiguous(), [p.detach() for p in params]
+        out, tape = _bottleneck_batch_forward(eng, stride, steps, xd, pd[:n], pd[n:2 * n], pd[2 * n:])
+        ctx.eng, ctx.stride, ctx.n = eng, stride, n
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(xd, *pd[:2 * n], *(t for rec in tape for t in rec))       # (an optimiser step in between is caught by autograd's version check)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        n = ctx.n
+        none = (None,) * (4 + 3 * n)
+        if g_out is None:
+            return none
+        x, *rest = ctx.saved_tensors
+        ws, gammas, tape = rest[:n], rest[n:2 * n], [rest[2 * n + 4 * i:2 * n + 4 * i + 4] for i in range(n)]
+        eng, s = ctx.eng, ctx.stride
+        need_x, need = ctx.needs_input_grad[3], list(ctx.needs_input_grad[4:])
+        need_w, need_g, need_b = need[:n], need[n:2 * n], need[2 * n:]
+        has_ds = n == 4
+        # what each launch has to hand down, from the block's input upwards
+        conv_any = [need_x or need_w[0]]                                   # conv i's backward is launched: BatchNorm i's g_z is wanted
+        bn_any = [conv_any[0] or need_g[0] or need_b[0]]                   # BatchNorm i's backward is launched: its g_y is wanted
+        for i in (1, 2):
+            conv_any.append(bn_any[i - 1] or need_w[i])
+            bn_any.append(conv_any[i] or need_g[i] or need_b[i])
+        if has_ds:
+            conv_any.append(need_x or need_w[3])
+            bn_any.append(conv_any[3] or need_g[3] or need_b[3])
+        want_res = bn_any[3] if has_ds else need_x
+        if not (bn_any[2] or want_res):
+            return none
+        g_w, g_g, g_b = [None] * n, [None] * n, [None] * n
+        ones = lambda i: _identity_affine(eng, ws[i].shape[0])[0]
+
+        def bn_bwd(i, g_y, relu, res=False):
+            z, y, mean, invstd = tape[i]
+            g_z, g_g[i], g_b[i], g_res = eng.batchnorm_backward(z, gammas[i], mean, invstd, y if relu else None, g_y, relu,
+                                                                want=(conv_any[i], need_g[i], need_b[i], res))
+            return g_z, g_res
+        g_z3, g_res = bn_bwd(2, g_out, True, want_res)
+        skip = g_res
+        if has_ds and bn_any[3]:
+            g_zd, _ = bn_bwd(3, g_res, False)
+            skip = None
+            if conv_any[3]:
+                skip, g_w[3], _ = eng.conv2d_backward(x, ws[3], ones(3), s, 0, None, g_zd, False, want=(need_x, need_w[3], False))
+        g_x = None
+        if conv_any[2]:
+            g_y2, g_w[2], _ = eng.conv2d_backward(tape[1][1], ws[2], ones(2), 1, 0, None, g_z3, False, want=(bn_any[1], need_w[2], False))
+            if bn_any[1]:
+                g_z2, _ = bn_bwd(1, g_y2, True)
+                if conv_any[1]:
+                    g_y1, g_w[1], _ = eng.conv2d_backward(tape[0][1], ws[1], ones(1), s, 1, None, g_z2, False, want=(bn_any[0], need_w[1], False))
+                    if bn_any[0]:
+                        g_z1, _ = bn_bwd(0, g_y1, True)
+                        if conv_any[0]:
+                            # the skip (or downsample) gradient is summed in conv1's epilogue, in place where the buffer is this call's own
+                            own = need_x and has_ds
+                            g_x, g_w[0], _ = eng.conv2d_backward(x, ws[0], ones(0), 1, 0, None, g_z1, False, g_x_add=skip if need_x else None,
+                                                                 want=(need_x, need_w[0], False), g_x_out=skip if own else None)
+        return (None, None, None, g_x) + tuple(g_w) + tuple(g_g) + tuple(g_b)
+
+
 class ResNetStage(nn.Module):
-    """One stage (``layer1`` .. ``layer4``) of a torchvision-layout Bottleneck trunk (ResNet-50 / 101 / 152), trainable on FROZEN
-    BatchNorm: ``forward(x)`` takes (B, h, w, Cin) NHWC - what ``Engine.trunk(images, stages=n - 1)`` returns - and gives
+    """One stage (``layer1`` .. ``layer4``) of a torchvision-layout Bottleneck trunk (ResNet-50 / 101 / 152), trainable:
+    ``forward(x)`` takes (B, h, w, Cin) NHWC - what ``Engine.trunk(images, stages=n - 1)`` returns - and gives
     (B, oh, ow, 4 planes) NHWC.  Every bottleneck is one ``torch.autograd.Function`` over the library's trainable layer
     (``specmi_conv2d_train_forward`` / ``specmi_conv2d_backward``; spec_amd/csrc/conv_bwd.hip), which reads the conv weights where
     torch keeps them - an optimiser steps them as they are.
 
-    BatchNorm is frozen whatever ``train()`` says: at every forward each BN is the affine map scale = gamma / sqrt(running_var + eps),
-    shift = beta - running_mean * scale, computed on the device; batch statistics are never built, the running statistics are not
-    updated, and gamma / beta get no gradient.  The trainable parameters are the conv weights (``conv_parameters()``).
+    ``bn='frozen'`` (the default): BatchNorm is frozen whatever ``train()`` says: at every forward each BN is the affine map
+    scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale, computed on the device; batch statistics are never
+    built, the running statistics are not updated, and gamma / beta get no gradient.  The trainable parameters are the conv weights
+    (``conv_parameters()``).
+
+    ``bn='batch'``: the reference's semantics (its trainers are Lightning modules: the whole network is in ``train()`` during
+    ``training_step``).  A block in ``train()`` mode normalises every conv's output with the statistics of the batch
+    (``specmi_batchnorm_train_forward`` / ``specmi_batchnorm_backward``; spec_amd/csrc/bn_train.hip), moves ``running_mean`` /
+    ``running_var`` in place by torch's rule, increments ``num_batches_tracked``, and gamma / beta (``bn_parameters()``) get gradients
+    beside the conv weights; an image's output then depends on the rest of its batch.  A block in ``eval()`` mode runs exactly the
+    frozen path, on the running statistics as they are by then.
     First derivatives only."""
 
-    def __init__(self, blocks):
+    def __init__(self, blocks, bn='frozen'):
         super().__init__()
+        if bn not in ('frozen', 'batch'):
+            raise ValueError(f"bn = {bn!r}: 'frozen' and 'batch' are built")
         self.blocks = blocks
+        self.bn = bn
 
     @classmethod
-    def from_model(cls, net, name='layer4'):
+    def from_model(cls, net, name='layer4', bn='frozen'):
         """The stage ``name`` of ``net.backbone`` (a ``spec_amd.modules.CameraRegressorNetwork`` or ``HMR``), SHARING its block modules
         and so their Parameter objects: an optimiser step on ``conv_parameters()`` is a step on the network's weights, and the
         network's next call sees the bumped tensor versions and commits them again by itself."""
@@ -414,7 +546,7 @@ class ResNetStage(nn.Module):
         backbone = getattr(net, 'backbone', None)
         if not isinstance(backbone, ResNet50Params):
             raise NotImplementedError(f'ResNetStage is built for the Bottleneck trunks (ResNet-50 / 101 / 152), not for {type(backbone).__name__}')
-        return cls(getattr(backbone, name))
+        return cls(getattr(backbone, name), bn)
 
     def conv_parameters(self):
         """The conv weights, block by block in the order conv1, conv2, conv3[, downsample]: what an optimiser is given."""
@@ -422,6 +554,11 @@ class ResNetStage(nn.Module):
         for blk in self.blocks:
             out += [blk.conv1.weight, blk.conv2.weight, blk.conv3.weight] + ([blk.downsample[0].weight] if hasattr(blk, 'downsample') else [])
         return out
+
+    def bn_parameters(self):
+        """gamma and beta of every BatchNorm, block by block in the order bn1, bn2, bn3[, downsample]: what an optimiser is given
+        beside ``conv_parameters()`` with ``bn='batch'``."""
+        return [p for blk in self.blocks for bn in _block_bns(blk) for p in (bn.weight, bn.bias)]
 
     def forward(self, x):
         dev = _device_of(x)
@@ -431,10 +568,21 @@ class ResNetStage(nn.Module):
         for blk in self.blocks:
             ds = hasattr(blk, 'downsample')
             ws = [blk.conv1.weight, blk.conv2.weight, blk.conv3.weight] + ([blk.downsample[0].weight] if ds else [])
-            folds = [_fold_bn(bn) for bn in [blk.bn1, blk.bn2, blk.bn3] + ([blk.downsample[1]] if ds else [])]
             stride = blk.conv2.stride[0]
             if x.shape[3] != blk.conv1.in_channels:
                 raise ValueError(f'the stage takes {blk.conv1.in_channels} channels, x has {x.shape[3]}')
+            if self.bn == 'batch' and blk.training:
+                bns = _block_bns(blk)
+                params = ws + [bn.weight for bn in bns] + [bn.bias for bn in bns]
+                steps = [_bn_step(bn) for bn in bns]
+                if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+                    x = _BottleneckBatch.apply(eng, stride, steps, x, *params)
+                else:
+                    n = len(ws)
+                    pd = [p.detach() for p in params]
+                    x = _bottleneck_batch_forward(eng, stride, steps, x.detach().float().contiguous(), pd[:n], pd[n:2 * n], pd[2 * n:])[0]
+                continue
+            folds = [_fold_bn(bn) for bn in _block_bns(blk)]
             if torch.is_grad_enabled() and (x.requires_grad or any(w.requires_grad for w in ws)):
                 x = _Bottleneck.apply(eng, stride, folds, x, *ws)
             else:

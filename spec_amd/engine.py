@@ -1711,6 +1711,61 @@ class Engine:
                                                            int(bool(relu)), _ptr(g), _ptr(add), _ptr(g_x), _ptr(g_w), _ptr(g_res), self._stream()))
         return g_x, g_w, g_res
 
+    def _bn_args(self, z, gamma):
+        """The tensor of the two BatchNorm calls, checked -> (z, gamma, M, C): z (..., C) with C contiguous, read in place when it is
+        dense fp32 on this device."""
+        z, gamma = _dev_f32(z, self.device), _dev_f32(gamma, self.device)
+        if z.dim() < 2 or z.shape[-1] < 1 or tuple(gamma.shape) != (z.shape[-1],):
+            raise ValueError(f'z must be (..., C) with C >= 1 and gamma (C,), got {tuple(z.shape)} and {tuple(gamma.shape)}')
+        C_ = z.shape[-1]
+        M = z.numel() // C_
+        if M < 2:
+            raise ValueError(f'batch statistics need more than one value per channel, got {M}')
+        return z, gamma, M, C_
+
+    def batchnorm_train_forward(self, z, gamma, beta, eps=1e-5, residual=None, relu=False, running_mean=None, running_var=None, momentum=0.1):
+        """``specmi_batchnorm_train_forward``: BatchNorm on the statistics of the batch, y = (z - mean) invstd gamma + beta [+ residual]
+        [max(., 0)], z (..., C) NHWC -> (y, mean (C), invstd (C)).  ``running_mean`` / ``running_var`` (both or neither; dense fp32
+        vectors on this device) are updated IN PLACE with the factor ``momentum``."""
+        z, gamma, M, C_ = self._bn_args(z, gamma)
+        beta = _dev_f32(beta, self.device, (C_,))
+        res = _dev_f32(residual, self.device, tuple(z.shape))
+        if (running_mean is None) != (running_var is None):
+            raise ValueError('running_mean and running_var are given together or not at all')
+        for name, t in (('running_mean', running_mean), ('running_var', running_var)):
+            _dev_tensor(name, t, torch.float32, self.device, optional=True)
+            if t is not None and tuple(t.shape) != (C_,):
+                raise ValueError(f'{name} must be ({C_},), got {tuple(t.shape)}')
+        y, mean, invstd = torch.empty_like(z), self._empty(C_), self._empty(C_)
+        _lib.check(self.h, self.lib.specmi_batchnorm_train_forward(self.h, _ptr(z), M, C_, _ptr(gamma), _ptr(beta), _ptr(res), int(bool(relu)),
+                                                                   float(eps), float(momentum), _ptr(running_mean), _ptr(running_var), _ptr(y),
+                                                                   _ptr(mean), _ptr(invstd), self._stream()))
+        return y, mean, invstd
+
+    def batchnorm_backward(self, z, gamma, mean, invstd, y, g_y, relu=False, want=(True, True, True, False), g_res_out=None):
+        """``specmi_batchnorm_backward``: the forward's z, gamma, mean, invstd, its output y (may be None without relu) and g_y ->
+        (g_z, g_gamma, g_beta, g_res), None where ``want`` says so.  ``g_res_out``: the tensor g_res is written to (it may be ``g_y``
+        itself)."""
+        z, gamma, M, C_ = self._bn_args(z, gamma)
+        mean, invstd = _dev_f32(mean, self.device, (C_,)), _dev_f32(invstd, self.device, (C_,))
+        g = _dev_f32(g_y, self.device, tuple(z.shape))
+        yy = _dev_f32(y, self.device, tuple(z.shape))
+        if relu and yy is None:
+            raise ValueError('relu needs y (the mask is y > 0)')
+        if not any(want):
+            raise ValueError('no output is wanted')
+        g_z = torch.empty_like(z) if want[0] else None
+        g_gamma = self._empty(C_) if want[1] else None
+        g_beta = self._empty(C_) if want[2] else None
+        g_res = None
+        if want[3]:
+            g_res = g_res_out if g_res_out is not None else torch.empty_like(z)
+            if g_res.shape != z.shape or g_res.dtype != torch.float32 or g_res.device != self.device or not g_res.is_contiguous():
+                raise ValueError(f'g_res_out must be a dense fp32 tensor of shape {tuple(z.shape)} on {self.device}')
+        _lib.check(self.h, self.lib.specmi_batchnorm_backward(self.h, _ptr(z), M, C_, _ptr(gamma), _ptr(mean), _ptr(invstd), _ptr(yy), int(bool(relu)),
+                                                              _ptr(g), _ptr(g_z), _ptr(g_gamma), _ptr(g_beta), _ptr(g_res), self._stream()))
+        return g_z, g_gamma, g_beta, g_res
+
     def conv2d(self, x, w_oihw, scale, shift, stride, pad, residual=None, relu=True, nchw_input=False, out=None,
                x2=None, w2_oihw=None, stride2=1):
         """Single fused layer (tests).  x NHWC device tensor (NCHW for the 7x7 stem).  x, x2 and out may be channel-sliced views
