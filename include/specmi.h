@@ -151,7 +151,9 @@ const char* specmi_version(void);
  *     n > 1 = n leaves), "conv2d_wsplit" (specmi_conv2d only: 0 | 2 | 3), "smpl_skin_split" (-1 = by batch, 0 / 1 = never / always),
  *     "trunk_subbatch" (0) / "trunk_subbatch_layers" (2), "fc_splitk" (1), "fc_gemv" (1), "head_fuse" (3; bit 0: the regressor's state
  *     init rides in the pooling launch, bit 1: head_final's work is done by the SMPL pose kernel), "camcalib_head_group" (1; 0 = the
- *     CamCalib training heads' independent products as three single launches instead of one grouped launch: same bits);
+ *     CamCalib training heads' independent products as three single launches instead of one grouped launch: same bits),
+ *     "conv_wgrad_splits" (0 = specmi_conv2d_wgrad_splits' rule; n >= 1: specmi_conv2d_backward cuts the weight gradient's contraction
+ *     into min(n, B OH) splits whatever the shape - other bits than the rule's; how profiles/trunk_train_aux.json measured the rule);
  *   plan thresholds: "single_max_batch" (2), "latency_max_batch" (10), "latency_max_batch_single" (16), "latency_target_wgs" (256),
  *     "latency_min_chunks" (4), "latency_wino_min_tiles" (128), "latency_fill_wgs" (240) / "latency_fill_wgs_large" (400),
  *     "latency_unit_model" (0; 1 = pick the unit by a round model with "latency_unit_slots" 256: measured equal or worse);
@@ -504,7 +506,8 @@ int specmi_camcalib_head_backward(specmi_handle* h, const specmi_camcalib_head_p
  * w_oihw_dev is torch's own (Cout, Cin, KH, KW) fp32 tensor ON THE DEVICE, read in place at every call, and scale_dev / shift_dev
  * are (Cout) device vectors - the frozen BatchNorm as an affine map: nothing is packed on the host, uploaded or committed, nothing of
  * the handle's committed model is read and the stream is not synchronised.  Both calls work on a handle of any kind, committed or
- * not.  Layer shapes: KH = KW = 1 with pad 0 and KH = KW = 3 with pad 1, stride 1 or 2; OH = (H + 2 pad - KH) / stride + 1; any
+ * not.  Layer shapes: KH = KW = 1 with pad 0 and KH = KW = 3 with pad 1, stride 1 or 2, and the stem's KH = KW = 7 with pad 3 at
+ * stride 2; OH = (H + 2 pad - KH) / stride + 1; any
  * B, H, W, Cin, Cout >= 1, tails in every dimension are handled in the kernel and no access leaves a tensor.
  * specmi_conv2d_train_forward: Y[p, o] = sum_k X[gather(p, k)] W[o, k], k = (ky, kx, ci); padding taps contribute exact zeros;
  *   then v = Y * scale[o] + shift[o] (+ residual), and max(v, 0) with relu != 0.  residual may be NULL.
@@ -521,17 +524,46 @@ int specmi_camcalib_head_backward(specmi_handle* h, const specmi_camcalib_head_p
  * batch; g_w depends on the shapes alone; a wanted output has the same bits whatever else is wanted; with g_w NULL no
  * weight-gradient product is launched, with g_x NULL no data-gradient product.
  * Workspace: Cout Cin KH KW floats for the forward (the weights transposed on the device at every call to [tap][ci][o], so that a
- * column tile's lanes read contiguous bytes; counted in the call's time) and B OH OW Cout floats (G) for the backward, in the handle; it grows on the first call of a shape, afterwards nothing
- * is allocated and the calls can be captured into a graph.
+ * column tile's lanes read contiguous bytes; counted in the call's time) and B OH OW Cout floats (G) for the backward, plus
+ * S Cout Cin KH KW floats where the weight gradient is split (below), in the handle; it grows on the first call of a shape,
+ * afterwards nothing is allocated and the calls can be captured into a graph.
+ * The weight gradient's contraction runs over the B OH output rows.  Where the product has few 32 x 32 tiles and many rows it is
+ * cut into S > 1 splits: workgroup (tile, s) sums q = B OH / S contiguous rows, one more where s < r = B OH % S, starting at row
+ * s q + min(s, r), into a partial product in the workspace, and a second kernel (profiler name conv_bwd_wgrad_reduce) adds the partials in the order s = 0 .. S - 1.  No atomics.
+ * S is a function of the layer's shape alone, never of the device: specmi_conv2d_wgrad_splits returns it (SPECMI_ERR_ARG for a
+ * NULL splits, a dimension < 1 or a layer shape that is not built).  S == 1 whenever the product has 256 tiles or more or
+ * B OH < 128; S == 1 is one launch writing g_w directly.
  * Refusals (SPECMI_ERR_ARG with a message, nothing launched, no output written): x, w, scale, shift, y (forward) or g_y NULL; every
- * output NULL; y NULL with relu (backward); a layer shape other than the four above; a dimension < 1; a tensor of the layer with
+ * output NULL; y NULL with relu (backward); a layer shape other than the five above; a dimension < 1; a tensor of the layer with
  * 2^31 elements or more; a float pointer that is not 4-byte aligned. */
+int specmi_conv2d_wgrad_splits(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int* splits);
 int specmi_conv2d_train_forward(specmi_handle* h, const float* x, int B, int H, int W, int Cin, const float* w_oihw_dev,
                                 const float* scale_dev, const float* shift_dev, int Cout, int KH, int KW, int stride, int pad,
                                 const float* residual, int relu, float* y, void* stream);
 int specmi_conv2d_backward(specmi_handle* h, const float* x, int B, int H, int W, int Cin, const float* w_oihw_dev,
                            const float* scale_dev, int Cout, int KH, int KW, int stride, int pad, const float* y, int relu,
                            const float* g_y, const float* g_x_add, float* g_x, float* g_w, float* g_res, void* stream);
+
+/* MaxPool2d(3, 2, 1) for training, with its gradient (spec_amd/csrc/pool_bwd.hip; STABLE).  x / g_x (B, H, W, C) and y / g_y
+ * (B, OH, OW, C), OH = (H - 1) / 2 + 1, are dense NHWC fp32 on the device; idx (B, OH, OW, C) is one uint8 per output element.
+ * Nothing of the handle's committed model is read, no workspace is used, nothing is allocated and the stream is not synchronised:
+ * both calls work on a handle of any kind and can be captured into a graph.
+ * specmi_maxpool3x3s2_train_forward: the in-range taps of a window are scanned in (ky, kx) ascending order and a tap replaces the
+ *   best so far when v > best || isnan(v) (torch's rule): among equal maxima the first tap wins, a padding tap never wins, a NaN
+ *   in the window gives NaN.  idx = ky * 3 + kx (0 .. 8) of the tap the scan ends on, y its value: without a NaN in the window
+ *   y has the bits of specmi_maxpool3x3s2.
+ * specmi_maxpool3x3s2_backward: g_x[b, iy, ix, c] = the sum of g_y over the at most 2 x 2 windows that contain the pixel and whose
+ *   idx names it, added in (oy, ox) ascending order in double and rounded once.  Every element of g_x is written exactly once;
+ *   pixels that never won get exact zeros.  idx values that name no tap of the window (> 8, or a padding tap) pass no gradient.
+ * A lane owns 4 channels as one 16-byte vector where C % 4 == 0, the float tensors are 16-byte aligned and idx 4-byte aligned;
+ * otherwise a scalar form gives the same bits.  Deterministic: no atomics, the bits are fixed by the shape, two runs give the
+ * same bits and image b's bits do not depend on its batch.
+ * Refusals (SPECMI_ERR_ARG with a message, nothing launched, nothing written): a NULL pointer; a dimension < 1; an input of 2^31
+ * elements or more; a float pointer that is not 4-byte aligned. */
+int specmi_maxpool3x3s2_train_forward(specmi_handle* h, const float* x, int B, int H, int W, int C, float* y, unsigned char* idx,
+                                      void* stream);
+int specmi_maxpool3x3s2_backward(specmi_handle* h, const float* g_y, const unsigned char* idx, int B, int H, int W, int C,
+                                 float* g_x, void* stream);
 
 /* BatchNorm in training mode, with its gradients (spec_amd/csrc/bn_train.hip; STABLE): what nn.BatchNorm2d does in train() after a
  * convolution of a bottleneck, with the block's residual and ReLU,

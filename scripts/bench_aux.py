@@ -1568,9 +1568,161 @@ def bn_train_section(a):
     return out
 
 
+def trunk_train_section(a):
+    """What the trainable trunk adds below layer4 (spec_amd/csrc/pool_bwd.hip, the 7x7 shape and the split weight gradient of
+    spec_amd/csrc/conv_bwd.hip) at CamCalib's fine-tuning shape, B = ``DATASET.BATCH_SIZE`` = 64 frames of 600 x 1000: the max-pool
+    forward + backward against ``aten.max_pool2d_with_indices`` and its backward on the same channels_last tensors, with the bytes
+    the kernels must move over their time; the stem's three products and one 1x1 and one 3x3 of each of layer1 - layer3 (forward and
+    weight gradient, with the rule's S) against ``aten.convolution`` / ``aten.convolution_backward``; library and torch alternated in
+    this process, 3 rounds of ``iters`` back-to-back calls after a warm-up, medians; the weight gradients of the stem, layer1 and
+    layer2 at every candidate S (the experimental option "conv_wgrad_splits" forces it; S = 1 is the unsplit launch), alternated
+    over 3 rounds; and the whole training step at SPEC's shape (B = 64, 224 x 224) too - with the heads alone, with layer4 and with
+    the whole trunk unfrozen, frozen and batch BatchNorm, each with ``torch.cuda.max_memory_allocated``."""
+    from spec_amd import camcalib_eval as ce
+    from spec_amd.cam_utils import _engine
+    dev = torch.device('cuda', 0)
+    eng = _engine(dev)
+    bs = int(ce.DEFAULTS['DATASET']['BATCH_SIZE'])
+
+    def ms_per_call(fn, iters):
+        for _ in range(2):
+            fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(iters):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters
+
+    def compare(calls, iters):
+        rounds = {p: {'library': [], 'torch': []} for p in calls}
+        for _ in range(3):                                              # alternated: both see the same clocks and the same neighbours
+            for p, (mine, theirs) in calls.items():
+                rounds[p]['library'].append(ms_per_call(mine, iters))
+                rounds[p]['torch'].append(ms_per_call(theirs, iters))
+        row = {}
+        for p in calls:
+            lib, tor = float(np.median(rounds[p]['library'])), float(np.median(rounds[p]['torch']))
+            row[p] = {'library_ms': round(lib, 5), 'torch_ms': round(tor, 5), 'library_over_torch': round(lib / tor, 3),
+                      'library_rounds_ms': [round(v, 5) for v in rounds[p]['library']], 'torch_rounds_ms': [round(v, 5) for v in rounds[p]['torch']]}
+        return row
+    out = {}
+    # the pool at the stem's output: B x 300 x 500 x 64 -> 150 x 250
+    torch.manual_seed(5)
+    x = torch.relu(torch.randn(bs, 300, 500, 64, device=dev))
+    y, idx = eng.maxpool_train_forward(x)
+    g_y = torch.randn_like(y)
+    xn, gn = x.permute(0, 3, 1, 2), g_y.permute(0, 3, 1, 2)                 # channels_last views of the same memory
+    ty, ti = torch.ops.aten.max_pool2d_with_indices(xn, [3, 3], [2, 2], [1, 1])
+    row = compare({'forward': (lambda: eng.maxpool_train_forward(x), lambda: torch.ops.aten.max_pool2d_with_indices(xn, [3, 3], [2, 2], [1, 1])),
+                   'backward': (lambda: eng.maxpool_backward(g_y, idx, 300, 500),
+                                lambda: torch.ops.aten.max_pool2d_with_indices_backward(gn, xn, [3, 3], [2, 2], [1, 1], [1, 1], False, ti))}, a.iters)
+    moved = {'forward': 4.0 * x.numel() + 5.0 * y.numel(), 'backward': 4.0 * x.numel() + 5.0 * y.numel()}
+    for p, by in moved.items():
+        row[p]['bytes_moved'] = by
+        row[p]['TBps'] = round(by / (row[p]['library_ms'] * 1e-3) / 1e12, 3)
+        row[p]['fraction_of_hbm_peak'] = round(row[p]['TBps'] * 1e12 / HBM_PEAK, 3)
+    row['workload'] = f'B = {bs}, 300 x 500 x 64 -> 150 x 250, post-ReLU input'
+    out['maxpool'] = row
+    print('maxpool', {p: (row[p]['library_ms'], row[p]['torch_ms']) for p in moved}, flush=True)
+    del x, y, idx, g_y, xn, gn, ty, ti
+    # the conv products: (name, H, W, Cin, Cout, k, stride, products)
+    fw = ('forward', 'wgrad')
+    layers = [(f'{sname}.{lname}', H0 // d, W0 // d, cin, cout, k, stride, products)
+              for sname, (H0, W0) in {'camcalib_b%d_600x1000' % bs: (600, 1000), 'spec_b64_224x224': (224, 224)}.items()
+              for lname, d, cin, cout, k, stride, products in [
+                  ('stem.conv1', 1, 3, 64, 7, 2, fw + ('dgrad',)), ('layer1.0.conv1', 4, 64, 64, 1, 1, fw), ('layer1.0.conv2', 4, 64, 64, 3, 1, fw),
+                  ('layer2.0.conv1', 4, 256, 128, 1, 1, fw), ('layer2.0.conv2', 4, 128, 128, 3, 2, fw),
+                  ('layer3.0.conv1', 8, 512, 256, 1, 1, fw), ('layer3.0.conv2', 8, 256, 256, 3, 2, fw)]]
+    for lname, H, W, cin, cout, k, stride, products in layers:
+        pad = k // 2
+        torch.manual_seed(cin + cout + k + stride)
+        x = torch.randn(bs, H, W, cin, device=dev)
+        wt = torch.randn(cout, cin, k, k, device=dev) / float(np.sqrt(cin * k * k))
+        scale, shift = 0.5 + torch.rand(cout, device=dev), 0.3 * torch.randn(cout, device=dev)
+        y = eng.conv2d_train_forward(x, wt, scale, shift, stride, pad, None, True)
+        g_y = torch.randn_like(y)
+        xn, gn = x.permute(0, 3, 1, 2), g_y.permute(0, 3, 1, 2)
+        bwd = lambda mask: (lambda: torch.ops.aten.convolution_backward(gn, xn, wt, None, [stride] * 2, [pad] * 2, [1, 1], False, [0, 0], 1, mask))
+        lib_bwd = lambda want: (lambda: eng.conv2d_backward(x, wt, scale, stride, pad, y, g_y, True, None, want))
+        calls = {'forward': (lambda: eng.conv2d_train_forward(x, wt, scale, shift, stride, pad, None, True),
+                             lambda: torch.ops.aten.convolution(xn, wt, None, [stride] * 2, [pad] * 2, [1, 1], False, [0, 0], 1)),
+                 'wgrad': (lib_bwd((False, True, False)), bwd([False, True, False])),
+                 'dgrad': (lib_bwd((True, False, False)), bwd([True, False, False]))}
+        row = compare({p: calls[p] for p in products}, max(1, a.iters // 4) if 'dgrad' in products else a.iters)
+        kern = timed(eng, calls['wgrad'][0], max(1, a.iters // 4))
+        row['wgrad_splits'] = eng.conv2d_wgrad_splits(bs, H, W, cin, cout, k, stride, pad)
+        if 'layer3' not in lname:
+            # the candidates: every S forced in turn (0 = the rule), wgrad product + reduce by HIP events around the call
+            cand = sorted({1, 4, 16, 32, 64, 128, 256, 512, 1024, row['wgrad_splits']})
+            eng.set_option('experimental', 1)
+            sweep = {S: [] for S in cand}
+            for _ in range(3):
+                for S in cand:
+                    eng.set_option('conv_wgrad_splits', S)
+                    sweep[S].append(ms_per_call(calls['wgrad'][0], max(2, a.iters // 2)))
+            eng.set_option('conv_wgrad_splits', 0)
+            prep = kern.get('conv_bwd_prep', (0.0,))[0]
+            row['wgrad_ms_by_forced_splits'] = {str(S): {'median_ms': round(float(np.median(v)), 5), 'rounds_ms': [round(x, 5) for x in v]} for S, v in sweep.items()}
+            row['wgrad_prep_ms_inside_every_figure'] = round(prep, 5)
+            best = min(cand, key=lambda S: float(np.median(sweep[S])))
+            row['wgrad_best_S'], row['wgrad_rule_over_best'] = best, round(float(np.median(sweep[row['wgrad_splits']])) / float(np.median(sweep[best])), 3)
+            row['wgrad_rule_over_unsplit'] = round(float(np.median(sweep[row['wgrad_splits']])) / float(np.median(sweep[1])), 4)
+            print(lname, 'forced S:', {S: round(float(np.median(v)), 3) for S, v in sweep.items()}, flush=True)
+        row['wgrad_kernels_by_the_library_profiler'] = {kk: round(v[0], 5) for kk, v in kern.items()}
+        row['workload'] = f'B = {bs}, {H} x {W} x {cin} -> {cout}, {k}x{k} stride {stride}, relu'
+        out[lname] = row
+        print(lname, 'S =', row['wgrad_splits'], {p: (row[p]['library_ms'], row[p]['torch_ms']) for p in products}, flush=True)
+        del x, wt, y, g_y, xn, gn
+    # the whole step: what lies below runs under no_grad, then the trainable part -> heads -> loss -> backward -> Adam
+    from spec_amd import synth
+    from spec_amd.camcalib_train import trunk_features
+    from spec_amd.differentiable import CameraRegressorHead, ResNetStage, ResNetTrunk
+    from spec_amd.losses import CameraRegressorLoss
+    from spec_amd.modules import CameraRegressorNetwork
+    net = CameraRegressorNetwork()
+    net.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in synth.camcalib_state(1001).items()}, strict=False)
+    net = net.to(dev).eval()
+    net.set_plan('throughput')
+    net.commit(dev, freeze=True)
+    head, crit = CameraRegressorHead.from_model(net), CameraRegressorLoss(1.0, 1.0, 1.0, 'ce')
+    for sname, (H, W) in {'camcalib_b%d_600x1000' % bs: (600, 1000), 'spec_b64_224x224': (224, 224)}.items():
+        images = torch.randn(bs, 3, H, W, device=dev)
+        targets = [torch.randint(0, 256, (bs,), device=dev) for _ in range(3)]
+        for what, bn in (('head_only', 'frozen'), ('layer4', 'frozen'), ('layer4', 'batch'), ('all', 'frozen'), ('all', 'batch')):
+            part = None if what == 'head_only' else ResNetStage.from_model(net, 'layer4', bn) if what == 'layer4' else ResNetTrunk.from_model(net, 'stem', bn)
+            mods = [] if part is None else [part.blocks] if what == 'layer4' else part.trained_modules()
+            params = list(head.parameters()) + ([] if part is None else part.conv_parameters() + (part.bn_parameters() if bn == 'batch' else []))
+            optim = torch.optim.Adam(params, lr=1e-6)
+            for m in mods:
+                m.train(bn == 'batch')
+
+            def step():
+                feat = None if what == 'all' else trunk_features(net, images, stages=3 if what == 'layer4' else None)
+                with torch.enable_grad():
+                    feat = part(images) if what == 'all' else part(feat) if part is not None else feat
+                    loss, _ = crit(*head(feat, channels_last=True), *targets)
+                    optim.zero_grad(set_to_none=True)
+                    loss.backward()
+                optim.step()
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            ms = ms_per_call(step, 2)
+            key = f'whole_step.{sname}.{what}.{bn}'
+            out[key] = {'ms_per_step': round(ms, 2), 'max_memory_allocated_GiB': round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
+                        'workload': f'ResNet-50, B = {bs} frames of {H} x {W}, ce, Adam; 2 warm-up steps, 2 timed'}
+            print(key, out[key]['ms_per_step'], 'ms,', out[key]['max_memory_allocated_GiB'], 'GiB', flush=True)
+            for m in mods:
+                m.eval()
+            del optim, part
+        del images
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'color_jitter', 'smpl_backward', 'head_train', 'camcalib_train', 'conv_backward', 'bn_train'], default=None, help='run one section only')
+    ap.add_argument('--only', choices=['eval_step', 'hmr_loss', 'camcalib_eval', 'pano_views', 'pano_views_host', 'ragged_crops', 'render', 'render_batch', 'draw', 'jpeg_encode', 'png_encode', 'jpeg_decode', 'png_decode', 'horizon_panel', 'color_jitter', 'smpl_backward', 'head_train', 'camcalib_train', 'conv_backward', 'bn_train', 'trunk_train'], default=None, help='run one section only')
     ap.add_argument('--smpl-backward', dest='only', action='store_const', const='smpl_backward', help='the same as --only smpl_backward')
     ap.add_argument('--head-train', dest='only', action='store_const', const='head_train', help='the same as --only head_train')
     ap.add_argument('--camcalib-train', dest='only', action='store_const', const='camcalib_train', help='the same as --only camcalib_train')
@@ -1578,6 +1730,8 @@ def main():
                     help='the same as --only conv_backward (writes profiles/conv_backward_aux.json unless --out is given)')
     ap.add_argument('--bn-train', dest='only', action='store_const', const='bn_train',
                     help='the same as --only bn_train (writes profiles/bn_train_aux.json unless --out is given)')
+    ap.add_argument('--trunk-train', dest='only', action='store_const', const='trunk_train',
+                    help='the same as --only trunk_train (writes profiles/trunk_train_aux.json unless --out is given)')
     ap.add_argument('--reference', default=None, help='the reference checkout (--only pano_views_host)')
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--batch', type=int, default=256)
@@ -1644,6 +1798,19 @@ def main():
             json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the '
                        'same calls; library and torch alternated, 3 rounds, medians; kernels: per-launch HIP events (library profiler), bytes = what '
                        'the kernel must move, computed from the shape', 'bn_train': row, 'source_hash': _lib.source_hash()}, f, indent=1)
+        return
+
+    if a.only == 'trunk_train':
+        from spec_amd import _lib
+        row = trunk_train_section(a)
+        path = a.out if a.out != ap.get_default('out') else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'profiles',
+                                                                         'trunk_train_aux.json')
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, 'w') as f:
+            json.dump({'hbm_peak_TBps': HBM_PEAK / 1e12, 'iters': a.iters, 'timing': 'HIP events around `iters` back-to-back calls after a warm-up of the '
+                       'same calls; library and torch alternated, 3 rounds, medians; the stem row, which includes the data gradient, runs iters / 4 calls',
+                       'wgrad_split_rule': 'the S that specmi_conv2d_wgrad_splits returns is wgrad_splits in every row; the candidates were forced through the '
+                       'experimental option conv_wgrad_splits', 'trunk_train': row, 'source_hash': _lib.source_hash()}, f, indent=1)
         return
 
     def add(name, workload, res, per_unit=None):

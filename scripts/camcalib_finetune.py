@@ -45,8 +45,9 @@ def main():
     ap.add_argument('--augment', action='store_true', help="the reference's training ColorJitter on every frame, on the device")
     ap.add_argument('--augment-seed', type=int, default=0, help='seed of the jitter parameters')
     ap.add_argument('--train-split', action='store_true', help='train on the frames train_images.pkl lists (default: val_images.pkl)')
-    ap.add_argument('--unfreeze', nargs='*', default=[], choices=['layer4'], metavar='STAGE',
-                    help="also train the conv weights of this ResNet stage on frozen BatchNorm ('layer4' is the one built)")
+    ap.add_argument('--unfreeze', nargs='*', default=[], choices=['stem', 'layer1', 'layer2', 'layer3', 'layer4', 'all'], metavar='PART',
+                    help="also train the conv weights of these parts of the ResNet trunk: a suffix of stem layer1 layer2 layer3 layer4 "
+                         "in any order ('layer4', 'layer3 layer4', ...), or 'all'")
     ap.add_argument('--bn', choices=['frozen', 'batch'], default='frozen',
                     help="BatchNorm of the unfrozen stage: 'frozen' = its running statistics, gamma / beta untouched; 'batch' = the "
                          "reference's training mode: batch statistics, running statistics moved, gamma / beta trained (needs --unfreeze layer4)")
@@ -68,7 +69,7 @@ def main():
         dataset = panorama.PanoViewDataset(panorama.list_panoramas(args.panoramas), args.views_per_pano, args.seed)
     res = ct.finetune_heads(hp, data_root=root, ckpt=args.ckpt, epochs=args.epochs, seed=args.seed, out=args.out, dataset=dataset,
                             augment=args.augment, augment_seed=args.augment_seed, split='train' if args.train_split else 'val',
-                            unfreeze=tuple(args.unfreeze), bn=args.bn)
+                            unfreeze='all' if 'all' in args.unfreeze else tuple(args.unfreeze), bn=args.bn)
     if args.report:
         with open(args.report, 'w') as f:
             json.dump({k: res[k] for k in ('ckpt', 'epochs', 'before', 'after')}, f, indent=1)

@@ -187,6 +187,12 @@ PROTOTYPES = {
                                        [C.c_void_p] * 6),
     # (h, z, M, C, gamma, mean, invstd, y, relu, g_y, g_z, g_gamma, g_beta, g_res, stream)
     'specmi_batchnorm_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 6),
+    # (B, H, W, Cin, Cout, KH, KW, stride, pad, splits)
+    'specmi_conv2d_wgrad_splits': (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_int)]),
+    # (h, x, B, H, W, C, y, idx, stream)
+    'specmi_maxpool3x3s2_train_forward': (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3),
+    # (h, g_y, idx, B, H, W, C, g_x, stream)
+    'specmi_maxpool3x3s2_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2),
     # (h, images, B, H, W, n_stages, out, stream)
     'specmi_trunk_forward_stages': (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     'specmi_conv2d': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIBDIR = os.path.join(HERE, 'lib')
 LIB = os.path.join(LIBDIR, 'libspecmi.so')
-SOURCES = ['api.hip', 'commit.hip', 'options.hip', 'hrnet.hip', 'conv_igemm.hip', 'conv_wsplit.hip', 'conv_wino.hip', 'conv_bf16s.hip', 'conv_f16.hip', 'stem.hip', 'head.hip', 'smpl.hip', 'smpl_bwd.hip', 'head_bwd.hip', 'conv_bwd.hip', 'bn_train.hip', 'camcalib_bwd.hip', 'eval.hip', 'loss.hip', 'preprocess.hip', 'panorama.hip', 'render.hip', 'draw.hip', 'marks.hip', 'color_jitter.hip', 'jpeg.hip', 'jpeg_dec.hip', 'png.hip', 'png_dec.hip']
+SOURCES = ['api.hip', 'commit.hip', 'options.hip', 'hrnet.hip', 'conv_igemm.hip', 'conv_wsplit.hip', 'conv_wino.hip', 'conv_bf16s.hip', 'conv_f16.hip', 'stem.hip', 'head.hip', 'smpl.hip', 'smpl_bwd.hip', 'head_bwd.hip', 'conv_bwd.hip', 'bn_train.hip', 'pool_bwd.hip', 'camcalib_bwd.hip', 'eval.hip', 'loss.hip', 'preprocess.hip', 'panorama.hip', 'render.hip', 'draw.hip', 'marks.hip', 'color_jitter.hip', 'jpeg.hip', 'jpeg_dec.hip', 'png.hip', 'png_dec.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 
 

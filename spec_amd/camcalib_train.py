@@ -26,8 +26,12 @@ normalises with the statistics of the batch (``specmi_batchnorm_train_forward`` 
 statistics move and ``num_batches_tracked`` counts, and Adam steps gamma and beta too.  Afterwards the blocks go back to ``eval()``,
 the model is committed again - the folded trunk carries the trained running statistics - and the checkpoint holds them.
 
-Out of scope, as for the SPEC side: the backward of the stem and of layers 1-3 (through a max-pool backward,
-so their BatchNorms stay frozen), SyncBatchNorm across GPUs, an fp16 backward, 'pano_agora'
+``unfreeze`` also takes the longer suffixes of the trunk, down to ``'all'`` = the stem and layers 1-4, the reference's own
+training mode (its trainer hands Adam every parameter): ``differentiable.ResNetTrunk`` runs what lies below the first trained part
+frozen, then the trainable stem (conv7x7/2 -> BatchNorm -> ReLU -> max-pool with its gradient, ``specmi_maxpool3x3s2_backward``)
+and stages; ``bn='batch'`` puts every unfrozen module in ``train()`` and hands Adam their gamma / beta.
+
+Out of scope, as for the SPEC side: BasicBlock trunks, SyncBatchNorm across GPUs, an fp16 backward, 'pano_agora'
 (the frames are those the tree's ``val_images.pkl`` / ``train_images.pkl`` list, or a ``dataset`` object with
 ``PanoValDataset``'s interface), second derivatives.
 """
@@ -75,6 +79,24 @@ def write_checkpoint(model, path: str, epoch: int, global_step: int) -> str:
     return path
 
 
+def normalise_unfreeze(unfreeze) -> tuple:
+    """``unfreeze`` as ``finetune_heads`` takes it -> () or a suffix of ('stem', 'layer1', 'layer2', 'layer3', 'layer4') in that
+    order: 'all' is the whole trunk, the names may come in any order; anything that is not such a suffix - ('layer3',) alone, a part
+    left out in the middle - is ``NotImplementedError``: a frozen part ABOVE a trained one is not built."""
+    from .differentiable import TRUNK_PARTS
+    if isinstance(unfreeze, str):
+        unfreeze = TRUNK_PARTS if unfreeze == 'all' else (unfreeze,)
+    names = tuple(unfreeze)
+    if not names:
+        return ()
+    if len(set(names)) == len(names) and set(names) <= set(TRUNK_PARTS):
+        suffix = TRUNK_PARTS[len(TRUNK_PARTS) - len(names):]
+        if set(names) == set(suffix):
+            return suffix
+    raise NotImplementedError(f"unfreeze = {unfreeze!r}: (), 'all' and the suffixes of {TRUNK_PARTS} are built - the trained part reaches "
+                              'from its first stage to layer4')
+
+
 def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = None, epochs: int = 1, seed: int = 0, out: Optional[str] = None,
                    dataset=None, model=None, log=print, device='cuda', evaluate: bool = True, augment: bool = False, augment_seed: int = 0,
                    split: str = 'val', unfreeze=(), bn: str = 'frozen') -> dict:
@@ -85,15 +107,13 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     ``device_batch`` hands it over), jittered by ``augment.ColorJitter`` with the reference's four settings - the parameters drawn
     frame by frame from a torch CPU generator seeded with ``augment_seed`` - and resized from there; False: exactly the flow
     without it.  ``split``: which list of the tree the training frames come from (the evaluations keep reading 'val').
-    ``unfreeze``: ``()`` trains the heads alone; ``('layer4',)`` also the conv weights of the last ResNet stage on frozen BatchNorm
-    (the only other value built).  ``bn``: 'frozen' = the stage on its running statistics, gamma / beta untouched; 'batch' = the stage
+    ``unfreeze``: ``()`` trains the heads alone; ``('layer4',)`` also the conv weights of the last ResNet stage on frozen BatchNorm;
+    the longer suffixes of the trunk - ('layer3', 'layer4') ... ('stem', 'layer1', 'layer2', 'layer3', 'layer4') = 'all', in any
+    order - train from that part upwards through ``differentiable.ResNetTrunk`` (``normalise_unfreeze``).  ``bn``: 'frozen' = the stage on its running statistics, gamma / beta untouched; 'batch' = the stage
     in ``train()`` on batch statistics, gamma / beta trained, the running statistics moved (module docstring) - refused with
     ``unfreeze=()``, where no BatchNorm is trained."""
-    from .differentiable import CameraRegressorHead, ResNetStage
-    unfreeze = tuple(unfreeze)
-    if unfreeze not in ((), ('layer4',)):
-        raise NotImplementedError(f"unfreeze = {unfreeze!r}: () and ('layer4',) are built (DESIGN.md section 6: the stem and layers 1-3 need "
-                                  'a max-pool backward)')
+    from .differentiable import CameraRegressorHead, ResNetStage, ResNetTrunk
+    unfreeze = normalise_unfreeze(unfreeze)
     if bn not in ('frozen', 'batch'):
         raise ValueError(f"bn = {bn!r}: 'frozen' and 'batch' are built")
     if bn == 'batch' and not unfreeze:
@@ -117,8 +137,15 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
     before = run_eval() if evaluate else None
     head = CameraRegressorHead.from_model(model)
     crit = CameraRegressorLoss(float(m['LOSS_VFOV_WEIGHT']), float(m['LOSS_PITCH_WEIGHT']), float(m['LOSS_ROLL_WEIGHT']), m['LOSS_TYPE'])
-    stage = ResNetStage.from_model(model, 'layer4', bn) if unfreeze else None
-    trained = list(head.parameters()) + (stage.conv_parameters() if stage is not None else []) + (stage.bn_parameters() if bn == 'batch' else [])
+    # ('layer4',) keeps the stage on the trunk cut after layer3; a longer suffix is a ResNetTrunk whose frozen part, if any, runs below it
+    stage = trunk = None
+    if unfreeze == ('layer4',):
+        stage = ResNetStage.from_model(model, 'layer4', bn)
+    elif unfreeze:
+        # what lies below layer2 .. layer4 runs in sub-batches, as the head-only flow; a frozen stem below layer1 takes the batch whole
+        trunk = ResNetTrunk.from_model(model, unfreeze[0], bn, cut_trunk=lambda images, k: trunk_features(model, images, stages=k))
+    part = stage if stage is not None else trunk
+    trained = list(head.parameters()) + (part.conv_parameters() if part is not None else []) + (part.bn_parameters() if bn == 'batch' else [])
     optim = torch.optim.Adam(trained, lr=float(opt_cfg['LR']), weight_decay=float(opt_cfg['WD']))
     bs, min_res, max_res = int(hparams['DATASET']['BATCH_SIZE']), int(hparams['DATASET']['MIN_RES']), hparams['DATASET']['MAX_RES']
     rng = np.random.default_rng(seed)
@@ -130,8 +157,9 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         jitter, jitter_rng = ColorJitter(**CAMCALIB_TRAIN_JITTER), torch.Generator().manual_seed(int(augment_seed))
     log(f'Train dataset len: {len(ds)}')
     history, step = [], 0
-    if bn == 'batch':
-        stage.blocks.train()                  # the blocks alone: the model itself has no training mode
+    train_mode = [] if bn != 'batch' else [stage.blocks] if stage is not None else trunk.trained_modules()
+    for mod in train_mode:
+        mod.train()                           # the unfrozen modules alone: the model itself has no training mode
     for epoch in range(int(epochs)):
         order = rng.permutation(len(ds))
         sums = torch.zeros(4, device=dev)
@@ -143,10 +171,12 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
             if jitter is not None:
                 frames = jitter(frames if isinstance(frames, tuple) else pack_frames(frames, dev), jitter_rng, engine=eng)
             images = ce.pad_batch(frames, min_res, max_res, dev, eng)
-            feat = trunk_features(model, images, stages=3 if stage is not None else None)
+            feat = None if trunk is not None else trunk_features(model, images, stages=3 if stage is not None else None)
             with torch.enable_grad():
                 if stage is not None:
                     feat = stage(feat)
+                elif trunk is not None:
+                    feat = trunk(images)
                 loss, loss_dict = crit(*head(feat, channels_last=True), *ce.encode_targets(*gt, m['LOSS_TYPE']))
                 optim.zero_grad(set_to_none=True)
                 loss.backward()
@@ -157,8 +187,8 @@ def finetune_heads(hparams: dict, data_root: str = '.', ckpt: Optional[str] = No
         means = (sums / max(nb, 1)).cpu().tolist()
         history.append(dict(zip(TRAIN_KEYS, (float(v) for v in means))))
         log(f'[EPOCH {epoch}] ' + ', '.join(f'{k}: {v:.6g}' for k, v in history[-1].items()))
-    if bn == 'batch':
-        stage.blocks.eval()
+    for mod in train_mode:
+        mod.eval()
     model.commit(dev, freeze=True)            # the frozen model skips the per-forward check: commit the stepped weights now
     after = run_eval() if evaluate else None
     if out is None:

@@ -2961,15 +2961,26 @@ int specmi_camcalib_head_backward(specmi_handle* h, const specmi_camcalib_head_p
     return SPECMI_OK;
 }
 
+// the five layer shapes of the trainable conv layer
+static bool conv_train_shape_ok(int KH, int KW, int stride, int pad) {
+    const bool k1 = KH == 1 && KW == 1 && pad == 0, k3 = KH == 3 && KW == 3 && pad == 1, k7 = KH == 7 && KW == 7 && pad == 3;
+    return ((k1 || k3) && (stride == 1 || stride == 2)) || (k7 && stride == 2);
+}
+
+int specmi_conv2d_wgrad_splits(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int* splits) {
+    if (!splits || B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1 || !conv_train_shape_ok(KH, KW, stride, pad)) return SPECMI_ERR_ARG;
+    *splits = conv_wgrad_splits(B, conv_out(H, KH, stride, pad), Cin, Cout, KH, KW);
+    return SPECMI_OK;
+}
+
 // the argument checks specmi_conv2d_train_forward and specmi_conv2d_backward share, and the kernels' argument block
 static int conv_train_args(specmi_handle* h, const char* who, const float* x, int B, int H, int W, int Cin, const float* w, const float* scale,
                            int Cout, int KH, int KW, int stride, int pad, ConvTrainArgs& t) {
     if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1)
         return fail(h, SPECMI_ERR_ARG, "%s: every dimension must be >= 1 (B = %d, H = %d, W = %d, Cin = %d, Cout = %d)", who, B, H, W, Cin, Cout);
-    const bool k1 = KH == 1 && KW == 1 && pad == 0, k3 = KH == 3 && KW == 3 && pad == 1;
-    if (!(k1 || k3) || (stride != 1 && stride != 2))
-        return fail(h, SPECMI_ERR_ARG, "%s: the layers built are 1x1 pad 0 and 3x3 pad 1 at stride 1 or 2 (KH = %d, KW = %d, stride = %d, pad = %d)",
-                    who, KH, KW, stride, pad);
+    if (!conv_train_shape_ok(KH, KW, stride, pad))
+        return fail(h, SPECMI_ERR_ARG, "%s: the layers built are 1x1 pad 0 and 3x3 pad 1 at stride 1 or 2 and 7x7 pad 3 at stride 2 (KH = %d, KW = %d, "
+                    "stride = %d, pad = %d)", who, KH, KW, stride, pad);
     const int OH = conv_out(H, KH, stride, pad), OW = conv_out(W, KW, stride, pad);
     const double lim = 2147483648.0;
     if ((double)B * H * W * Cin >= lim || (double)B * OH * OW * Cout >= lim || (double)Cout * Cin * KH * KW >= lim || (double)B * H * W >= lim)
@@ -3012,10 +3023,14 @@ int specmi_conv2d_backward(specmi_handle* h, const float* x, int B, int H, int W
     if (!g_x && !g_w && !g_res) return fail(h, SPECMI_ERR_ARG, "conv2d_backward: every output is NULL");
     if (misaligned4({x, w_oihw_dev, scale_dev, y, g_y, g_x_add, g_x, g_w, g_res}))
         return fail(h, SPECMI_ERR_ARG, "conv2d_backward: a float pointer is not 4-byte aligned");
+    // the splits of the weight gradient: the rule of the shape, or what the experimental option forces (measurements)
+    const int forced = opt(h, OPT_conv_wgrad_splits);
+    const long rows = (long)B * t.OH;
+    const int S = forced > 0 ? (int)std::min<long>({(long)forced, rows, 4096L}) : conv_wgrad_splits(B, t.OH, Cin, Cout, KH, KW);
     if (g_x || g_w)
-        if (int rc = grow_ragged(h, h->buf[BUF_conv_bwd], conv_bwd_ws_floats(t) * 4, "the convolution backward workspace")) return rc;
+        if (int rc = grow_ragged(h, h->buf[BUF_conv_bwd], conv_bwd_ws_floats(t, g_w ? S : 1) * 4, "the convolution backward workspace")) return rc;
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, "conv.backward"};
-    LAUNCHCHK(h, launch_conv_backward(t, y, relu != 0, g_y, g_x ? g_x_add : nullptr, g_x, g_w, g_res, (float*)h->buf[BUF_conv_bwd].p, ctx),
+    LAUNCHCHK(h, launch_conv_backward(t, y, relu != 0, g_y, g_x ? g_x_add : nullptr, g_x, g_w, g_res, (float*)h->buf[BUF_conv_bwd].p, S, ctx),
               "conv2d_backward");
     return SPECMI_OK;
 }
@@ -3066,6 +3081,37 @@ int specmi_batchnorm_backward(specmi_handle* h, const float* z, int M, int C, co
     LaunchCtx ctx{(hipStream_t)stream, &h->prof, "bn.backward"};
     LAUNCHCHK(h, launch_bn_backward(a, mean, invstd, y, g_y, g_z, g_gamma, g_beta, g_res, (float*)h->buf[BUF_bn_train].p, ctx),
               "batchnorm_backward");
+    return SPECMI_OK;
+}
+
+// the argument checks specmi_maxpool3x3s2_train_forward and specmi_maxpool3x3s2_backward share
+static int pool_train_args(specmi_handle* h, const char* who, int B, int H, int W, int C, std::initializer_list<const void*> f32,
+                           const void* idx) {
+    if (B < 1 || H < 1 || W < 1 || C < 1)
+        return fail(h, SPECMI_ERR_ARG, "%s: every dimension must be >= 1 (B = %d, H = %d, W = %d, C = %d)", who, B, H, W, C);
+    if ((double)B * H * W * C >= 2147483648.0) return fail(h, SPECMI_ERR_ARG, "%s: the input has 2^31 elements or more", who);
+    for (const void* p : f32)
+        if (!p) return fail(h, SPECMI_ERR_ARG, "%s: a tensor is NULL", who);
+    if (!idx) return fail(h, SPECMI_ERR_ARG, "%s: idx is NULL", who);
+    if (misaligned4(f32)) return fail(h, SPECMI_ERR_ARG, "%s: a float pointer is not 4-byte aligned", who);
+    return SPECMI_OK;
+}
+
+int specmi_maxpool3x3s2_train_forward(specmi_handle* h, const float* x, int B, int H, int W, int C, float* y, unsigned char* idx,
+                                      void* stream) {
+    ENTER(h);
+    if (int rc = pool_train_args(h, "maxpool3x3s2_train_forward", B, H, W, C, {x, y}, idx)) return rc;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "maxpool.train_forward"};
+    LAUNCHCHK(h, launch_maxpool_train_forward(x, B, H, W, C, y, idx, ctx), "maxpool3x3s2_train_forward");
+    return SPECMI_OK;
+}
+
+int specmi_maxpool3x3s2_backward(specmi_handle* h, const float* g_y, const unsigned char* idx, int B, int H, int W, int C, float* g_x,
+                                 void* stream) {
+    ENTER(h);
+    if (int rc = pool_train_args(h, "maxpool3x3s2_backward", B, H, W, C, {g_y, g_x}, idx)) return rc;
+    LaunchCtx ctx{(hipStream_t)stream, &h->prof, "maxpool.backward"};
+    LAUNCHCHK(h, launch_maxpool_backward(g_y, idx, B, H, W, C, g_x, ctx), "maxpool3x3s2_backward");
     return SPECMI_OK;
 }
 

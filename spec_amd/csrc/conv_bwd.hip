@@ -1,7 +1,8 @@
 // conv_bwd.hip - one fused ResNet layer for training: y = act(conv(x, W) * scale + shift [+ res]) with its three gradients
 // (gfx950).  x / y / res are dense NHWC fp32, W is torch's own OIHW fp32 tensor read where it lies at every call - the optimiser
 // rewrites it every step, nothing is packed, uploaded or committed (the rule of head_bwd.hip) - scale / shift are the frozen
-// BatchNorm as an affine map.  Layer shapes: 1x1 pad 0 and 3x3 pad 1, stride 1 or 2; any B, H, W, Cin, Cout >= 1.
+// BatchNorm as an affine map.  Layer shapes: 1x1 pad 0 and 3x3 pad 1, stride 1 or 2, and the stem's 7x7 pad 3 stride 2; any
+// B, H, W, Cin, Cout >= 1.
 //
 // Three products, implicit GEMMs with gathered addressing, on ONE kernel template (conv_gemm_kernel<MODE>): head_gemm_tile's
 // scheme - a workgroup owns a 32 x 32 tile of the product, its four waves take the k groups of 8 round robin on
@@ -17,6 +18,13 @@
 //                        pixel is in range
 //     weight gradient (2) g_W[o, (ci, ky, kx)] = sum G[p, o] X[gather(p, ky, kx), ci]  segment = output row (b, oy), inside it ox:
 //                        the output pixels in (b, oy, ox) order
+// The 7x7 stem's forward cuts its contraction otherwise (conv_gemm_kernel<0, true>): with Cin = 3 a tap segment would fill 3 of a
+// group's 8 slots, but in NHWC the (kx, ci) run of one kernel row is contiguous (21 floats), so there a segment is a kernel ROW
+// ky, nseg = KH and Kc = KW Cin, with the ix range checked per element; the transpose [tap][ci][o] already has that order.
+// A weight gradient with few tiles and many output rows (the stem: 10 tiles over B OH = 19200 rows at 64 frames of 600 x 1000)
+// is SPLIT (conv_gemm_kernel<2, true>): S = conv_wgrad_splits(shape) > 1, workgroup (tile, s) takes q = nseg / S contiguous segments
+// and one more where s < nseg % S, starting at s q + min(s, nseg % S), and writes its tile of partial s (S M N floats of workspace
+// behind G); conv_wgrad_reduce_kernel adds the partials in the order s = 0 .. S - 1.  S == 1 is the one launch described above.
 // The gradient operand G = g_z * scale[o], g_z = relu ? (y > 0 ? g_y : 0) : g_y, is written by one elementwise pre-pass
 // (conv_bwd_prep_kernel) into the handle's workspace, with g_res = g_z beside it when wanted: the data gradient reads every
 // element of G KH KW / stride^2 times and the weight gradient once per column tile, so forming it from three tensors inside the
@@ -47,9 +55,13 @@ struct ConvGemmArgs {
     int B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad;
     int M, N;                  // the product's extents
     int nseg, Kc;              // segments and the contraction length inside one
+    int S;                     // MODE 2: the splits of the segment list (gridDim.y); S > 1 writes partials, S == 1 writes C
+    float* part;               // MODE 2, S > 1: S partial products of M x N floats, split s at part + s M N
 };
 
-template <int MODE>
+// ALT selects the second form of a product, compiled apart so that the first form's code stays as it was: MODE 0 - a segment is a
+// kernel ROW ky with (kx, ci) inside it (the 7x7 stem); MODE 2 - the segment list is split over gridDim.y (S > 1)
+template <int MODE, bool ALT>
 __global__ void __launch_bounds__(256) conv_gemm_kernel(const ConvGemmArgs a) {
     __shared__ float part[3][16][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 5, c = lane & 31;
@@ -65,7 +77,14 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(const ConvGemmArgs a) {
     if (MODE == 0) { rx = m % a.OW; const int t = m / a.OW; ry = t % a.OH; rb = t / a.OH; }
     if (MODE == 1) { rx = m % a.W; const int t = m / a.W; ry = t % a.H; rb = t / a.H; }
     if (MODE == 2) { nkx = n % a.KW; const int t = n / a.KW; nky = t % a.KH; nci = t / a.KH; }
-    const int ng = (a.Kc + 7) / 8, T = a.nseg * ng;
+    // split s of S takes q = nseg / S contiguous segments, and one more where s < r = nseg % S: it starts at s q + min(s, r)
+    int seg_lo = 0, nseg = a.nseg;
+    if (MODE == 2 && ALT) {
+        const int s = (int)blockIdx.y, q = a.nseg / a.S, r = a.nseg - q * a.S;
+        seg_lo = s * q + min(s, r);
+        nseg = q + (s < r ? 1 : 0);
+    }
+    const int ng = (a.Kc + 7) / 8, T = nseg * ng;
     f32x16 acc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -75,12 +94,19 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(const ConvGemmArgs a) {
         for (int u = 0; u < KU; ++u) {
             const int t = t0 + 4 * u;
             const bool tok = t < T;
-            const int seg = tok ? t / ng : 0;
-            const int c0 = (tok ? t - seg * ng : 0) * 8 + 4 * h;
+            const int sl = tok ? t / ng : 0, seg = seg_lo + sl;
+            const int c0 = (tok ? t - sl * ng : 0) * 8 + 4 * h;
             const float* pa = nullptr; const float* pb = nullptr;
             long sa = 0, sb = 0;
             int bx0 = 0;                           // MODE 2: ix of element 0 of the segment; the elements step by the stride
-            if (MODE == 0) {
+            if (MODE == 0 && ALT) {
+                const int iy = ry * a.stride - a.pad + seg;
+                bx0 = rx * a.stride - a.pad;       // ix of kx = 0; element cj = (kx, ci) lies cj floats past it, in range or not
+                if (tok && mok && iy >= 0 && iy < a.H) pa = a.A + ((size_t)(rb * a.H + iy) * a.W) * a.Cin;
+                sa = 1;
+                if (tok && nok) pb = a.Bm + (size_t)seg * a.Kc * a.Cout + n;      // [ky][kx][ci][o] is the transpose's own order
+                sb = a.Cout;
+            } else if (MODE == 0) {
                 const int ky = seg / a.KW, kx = seg - ky * a.KW;
                 const int iy = ry * a.stride - a.pad + ky, ix = rx * a.stride - a.pad + kx;
                 if (tok && mok && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) pa = a.A + ((size_t)(rb * a.H + iy) * a.W + ix) * a.Cin;
@@ -115,6 +141,11 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(const ConvGemmArgs a) {
                     const int ix = cj * a.stride + bx0;
                     bok = bok && ix >= 0 && ix < a.W;
                     ob = bok ? (size_t)ix * sb : 0;
+                } else if (MODE == 0 && ALT) {
+                    const int ix = bx0 + cj / a.Cin;
+                    aok = aok && ix >= 0 && ix < a.W;
+                    oa = aok ? (size_t)((long)bx0 * a.Cin + cj) : 0;           // = ix Cin + ci >= 0
+                    ob = bok ? (size_t)cj * sb : 0;
                 } else {
                     ob = bok ? (size_t)cj * sb : 0;
                 }
@@ -140,6 +171,7 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(const ConvGemmArgs a) {
         for (int r = 0; r < 16; ++r) acc[r] += part[u][r][lane];
     if (!nok) return;
     const float sc = a.scale ? a.scale[n] : 1.f, sh = a.scale ? a.shift[n] : 0.f;
+    float* const C = (MODE == 2 && ALT) ? a.part + (size_t)blockIdx.y * a.M * a.N : a.C;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int mr = m0 + 4 * h + (r & 3) + 8 * (r >> 2);
@@ -148,7 +180,7 @@ __global__ void __launch_bounds__(256) conv_gemm_kernel(const ConvGemmArgs a) {
         if (a.scale) v = v * sc + sh;
         if (a.res) v += a.res[(size_t)mr * a.ldc + n];
         if (a.relu) v = v > 0.f ? v : 0.f;
-        a.C[(size_t)mr * a.ldc + n] = v;
+        C[(size_t)mr * a.ldc + n] = v;
     }
 }
 
@@ -181,22 +213,53 @@ ConvGemmArgs base_args(const ConvTrainArgs& t) {
     g.B = t.B; g.H = t.H; g.W = t.W; g.Cin = t.Cin; g.OH = t.OH; g.OW = t.OW; g.Cout = t.Cout;
     g.KH = t.KH; g.KW = t.KW; g.stride = t.stride; g.pad = t.pad;
     g.M = g.N = g.nseg = g.Kc = 0;
+    g.S = 1; g.part = nullptr;
     return g;
 }
 
-template <int MODE>
+template <int MODE, bool ALT = false>
 int launch_gemm(const char* name, const ConvGemmArgs& g, const LaunchCtx& ctx) {
     const double K = (double)g.nseg * g.Kc;
     ProfScope ps(ctx, name, 2.0 * g.M * g.N * K, 4.0 * ((double)g.M * K + K * g.N + (double)g.M * g.N));
     const long tiles = (long)((g.N + 31) / 32) * ((g.M + 31) / 32);
     if (tiles > 0x7fffffffL) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL(conv_gemm_kernel<MODE>, dim3((unsigned)tiles), dim3(256), 0, ctx.stream, g);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(conv_gemm_kernel<MODE, ALT>), dim3((unsigned)tiles, (unsigned)g.S), dim3(256), 0, ctx.stream, g);
     return (int)hipGetLastError();
+}
+
+// g_w[i] = part[0][i] + part[1][i] + ... + part[S - 1][i], added in that order
+__global__ void __launch_bounds__(256) conv_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ g_w, unsigned count, int S) {
+    const unsigned i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    float v = part[i];
+    for (int s = 1; s < S; ++s) v += part[(size_t)s * count + i];
+    g_w[i] = v;
 }
 
 }  // namespace
 
-size_t conv_bwd_ws_floats(const ConvTrainArgs& t) { return (size_t)t.B * t.OH * t.OW * t.Cout; }
+// The splits of the weight gradient's contraction, a function of the layer's shape alone (never of the device).  The product has
+// tiles = ceil(Cout / 32) ceil(Cin KH KW / 32) workgroups and nseg = B OH segments.  One launch (S = 1) where it fills the part
+// anyway (tiles >= WGRAD_FULL) or the contraction is short (nseg < WGRAD_MIN_NSEG); otherwise as many splits as leave each one
+// WGRAD_MIN_SEGS segments, at most WGRAD_MAX_SPLITS.  The two constants are measured (profiles/trunk_train_aux.json):
+// at 64 frames of 600 x 1000 the stem's, layer1's and layer2's weight gradients kept getting faster up to S = 256 - 512, whatever the
+// tile count (4 .. 144), and slower again at 1024, where layer2's 3x3 has fewer than 5 rows per split; 512 is the fastest or within
+// 5 % of it on all five.
+constexpr int WGRAD_FULL = 256, WGRAD_MIN_NSEG = 128, WGRAD_MIN_SEGS = 8, WGRAD_MAX_SPLITS = 512;
+
+int conv_wgrad_splits(int B, int OH, int Cin, int Cout, int KH, int KW) {
+    const long tiles = (long)((Cout + 31) / 32) * (((long)Cin * KH * KW + 31) / 32), nseg = (long)B * OH;
+    if (tiles >= WGRAD_FULL || nseg < WGRAD_MIN_NSEG) return 1;
+    const long s = std::min(nseg / WGRAD_MIN_SEGS, (long)WGRAD_MAX_SPLITS);
+    return (int)std::max(s, 1L);
+}
+
+static size_t conv_g_floats(const ConvTrainArgs& t) { return (size_t)t.B * t.OH * t.OW * t.Cout; }
+
+// G, and behind it the partial weight gradients of a product in S splits
+size_t conv_bwd_ws_floats(const ConvTrainArgs& t, int S) {
+    return conv_g_floats(t) + (S > 1 ? (size_t)S * t.Cout * t.Cin * t.KH * t.KW : 0);
+}
 size_t conv_fwd_ws_floats(const ConvTrainArgs& t) { return (size_t)t.Cout * t.Cin * t.KH * t.KW; }
 
 int launch_conv_train_forward(const ConvTrainArgs& t, const float* residual, int relu, float* y, float* ws, const LaunchCtx& ctx) {
@@ -210,12 +273,16 @@ int launch_conv_train_forward(const ConvTrainArgs& t, const float* residual, int
     g.A = t.x; g.Bm = ws; g.scale = t.scale; g.shift = t.shift; g.res = residual; g.relu = relu;
     g.C = y; g.ldc = t.Cout;
     g.M = t.B * t.OH * t.OW; g.N = t.Cout; g.nseg = t.KH * t.KW; g.Kc = t.Cin;
+    if (t.KH == 7) {
+        g.nseg = t.KH; g.Kc = t.KW * t.Cin;
+        return launch_gemm<0, true>("conv_train_fwd_gemm", g, ctx);
+    }
     return launch_gemm<0>("conv_train_fwd_gemm", g, ctx);
 }
 
 int launch_conv_backward(const ConvTrainArgs& t, const float* y, int relu, const float* g_y, const float* g_x_add, float* g_x, float* g_w,
-                         float* g_res, float* ws, const LaunchCtx& ctx) {
-    const size_t count = conv_bwd_ws_floats(t);
+                         float* g_res, float* ws, int S, const LaunchCtx& ctx) {
+    const size_t count = conv_g_floats(t);
     float* const G = (g_x || g_w) ? ws : nullptr;
     {
         ProfScope ps(ctx, "conv_bwd_prep", 2.0 * count, 4.0 * 4 * count);
@@ -233,7 +300,15 @@ int launch_conv_backward(const ConvTrainArgs& t, const float* y, int relu, const
         ConvGemmArgs g = base_args(t);
         g.A = G; g.Bm = t.x; g.C = g_w; g.ldc = (long)t.Cin * t.KH * t.KW;
         g.M = t.Cout; g.N = t.Cin * t.KH * t.KW; g.nseg = t.B * t.OH; g.Kc = t.OW;
-        if (const int rc = launch_gemm<2>("conv_bwd_wgrad_gemm", g, ctx)) return rc;
+        g.S = S;
+        g.part = ws + count;
+        if (const int rc = g.S > 1 ? launch_gemm<2, true>("conv_bwd_wgrad_gemm", g, ctx) : launch_gemm<2>("conv_bwd_wgrad_gemm", g, ctx)) return rc;
+        if (g.S > 1) {
+            const size_t n = (size_t)g.M * g.N;
+            ProfScope ps(ctx, "conv_bwd_wgrad_reduce", (double)(g.S - 1) * n, 4.0 * (g.S + 1) * n);
+            hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx.stream, g.part, g_w, (unsigned)n, g.S);
+            if (const int rc = (int)hipGetLastError()) return rc;
+        }
     }
     return 0;
 }

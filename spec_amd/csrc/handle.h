@@ -104,7 +104,8 @@ struct HrNet;
     SPECMI_OPT(wsplit_slots, 256, false)                                                                                  \
     SPECMI_OPT(conv2d_sk, 0, false)                                                                                       \
     SPECMI_OPT(conv2d_wsplit, 0, false)                                                                                   \
-    SPECMI_OPT(camcalib_head_group, 1, false)
+    SPECMI_OPT(camcalib_head_group, 1, false)                                                                             \
+    SPECMI_OPT(conv_wgrad_splits, 0, false)
 
 #define SPECMI_OPT(name, def, stable) OPT_##name,
 enum Opt { SPECMI_OPTIONS(SPECMI_OPT) OPT_COUNT };

@@ -496,11 +496,12 @@ struct ConvTrainArgs {
     const float* x; const float* w; const float* scale; const float* shift;
     int B, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad;
 };
-size_t conv_bwd_ws_floats(const ConvTrainArgs& t);
+int conv_wgrad_splits(int B, int OH, int Cin, int Cout, int KH, int KW);   // S of the weight gradient, from the shape alone
+size_t conv_bwd_ws_floats(const ConvTrainArgs& t, int S);   // G and, with S > 1 splits of the weight gradient, its S partial products
 size_t conv_fwd_ws_floats(const ConvTrainArgs& t);      // the forward's ws: the weights transposed to [tap][ci][o]
 int launch_conv_train_forward(const ConvTrainArgs& t, const float* residual, int relu, float* y, float* ws, const LaunchCtx& ctx);
 int launch_conv_backward(const ConvTrainArgs& t, const float* y, int relu, const float* g_y, const float* g_x_add, float* g_x, float* g_w,
-                         float* g_res, float* ws, const LaunchCtx& ctx);
+                         float* g_res, float* ws, int S, const LaunchCtx& ctx);    // S: 1 <= S <= B OH splits of the weight gradient
 
 // BatchNorm in training mode with its backward (bn_train.hip; include/specmi.h: specmi_batchnorm_train_forward): z and
 // y / residual / g_y / g_z / g_res dense (M, C) fp32, C contiguous; gamma / beta / mean / invstd / the running statistics (C).  ws is
@@ -515,6 +516,12 @@ int launch_bn_train_forward(const BnArgs& a, const float* beta, const float* res
                             float* running_var, float* y, float* mean, float* invstd, float* ws, const LaunchCtx& ctx);
 int launch_bn_backward(const BnArgs& a, const float* mean, const float* invstd, const float* y, const float* g_y, float* g_z, float* g_gamma,
                        float* g_beta, float* g_res, float* ws, const LaunchCtx& ctx);
+
+// MaxPool2d(3, 2, 1) for training (pool_bwd.hip; include/specmi.h: specmi_maxpool3x3s2_train_forward): x / g_x (B, H, W, C) and
+// y / g_y (B, OH, OW, C) dense NHWC fp32, idx (B, OH, OW, C) uint8 = the winning tap ky * 3 + kx.  Every dimension >= 1 and fewer
+// than 2^31 elements (hipErrorInvalidValue otherwise); the vector form is chosen from C and the pointers' alignment.
+int launch_maxpool_train_forward(const float* x, int B, int H, int W, int C, float* y, unsigned char* idx, const LaunchCtx& ctx);
+int launch_maxpool_backward(const float* g_y, const unsigned char* idx, int B, int H, int W, int C, float* g_x, const LaunchCtx& ctx);
 
 // ----------------------------------------------------------------------------------------
 // evaluation metrics  (eval.hip)

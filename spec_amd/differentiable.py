@@ -588,3 +588,171 @@ class ResNetStage(nn.Module):
             else:
                 x = _bottleneck_forward(eng, stride, folds, x.detach().float().contiguous(), [w.detach() for w in ws])[2]
         return x
+
+
+def _stem_frozen_forward(eng, fold, x, w):
+    """conv7x7/2 on the folded BatchNorm with ReLU, then the max-pool with its record -> (y, idx, out)."""
+    y = eng.conv2d_train_forward(x, w, *fold, 2, 3)
+    out, idx = eng.maxpool_train_forward(y)
+    return y, idx, out
+
+
+class _Stem(torch.autograd.Function):
+    """(x NHWC images, conv1's weight) -> the pooled stem output NHWC on a FROZEN BatchNorm (``fold`` = its scale / shift, which get no
+    gradient).  Saves x, y and idx; the backward runs the pool backward and then ``specmi_conv2d_backward`` wanting g_w alone: the
+    images get no gradient."""
+
+    @staticmethod
+    def forward(ctx, eng, fold, x, w):
+        wd = w.detach()
+        y, idx, out = _stem_frozen_forward(eng, fold, x, wd)
+        ctx.eng, ctx.scale = eng, fold[0]
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, y, idx, wd)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        if g_out is None or not ctx.needs_input_grad[3]:
+            return None, None, None, None
+        x, y, idx, w = ctx.saved_tensors
+        g_y = ctx.eng.maxpool_backward(g_out, idx, y.shape[1], y.shape[2])
+        return None, None, None, ctx.eng.conv2d_backward(x, w, ctx.scale, 2, 3, y, g_y, True, want=(False, True, False))[1]
+
+
+class _StemBatch(torch.autograd.Function):
+    """``_Stem`` on BATCH statistics: (x, conv1's weight, gamma, beta) -> the pooled output; ``step`` = ``_bn_step`` of bn1.  Saves x,
+    z, y, mean, invstd and idx; the backward runs the pool backward, ``specmi_batchnorm_backward`` with the ReLU mask, then
+    ``specmi_conv2d_backward`` on g_z with the identity scale."""
+
+    @staticmethod
+    def forward(ctx, eng, step, x, w, gamma, beta):
+        wd, gd = w.detach(), gamma.detach()
+        z, y, mean, invstd = _conv_bn(eng, x, wd, 2, 3, gd, beta.detach(), step)
+        out, idx = eng.maxpool_train_forward(y)
+        ctx.eng = eng
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(x, wd, gd, z, y, mean, invstd, idx)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        need_w, need_g, need_b = ctx.needs_input_grad[3:]
+        if g_out is None or not (need_w or need_g or need_b):
+            return (None,) * 6
+        x, w, gamma, z, y, mean, invstd, idx = ctx.saved_tensors
+        eng = ctx.eng
+        g_y = eng.maxpool_backward(g_out, idx, y.shape[1], y.shape[2])
+        g_z, g_gamma, g_beta, _ = eng.batchnorm_backward(z, gamma, mean, invstd, y, g_y, True, want=(need_w, need_g, need_b, False))
+        g_w = None
+        if need_w:
+            g_w = eng.conv2d_backward(x, w, _identity_affine(eng, w.shape[0])[0], 2, 3, None, g_z, False, want=(False, True, False))[1]
+        return None, None, None, g_w, g_gamma, g_beta
+
+
+class ResNetStem(nn.Module):
+    """The stem of a torchvision-layout ResNet, trainable: ``forward(images)`` takes (B, 3, H, W) NCHW fp32 images - as
+    ``camcalib_eval.pad_batch`` makes them; the permute to NHWC is torch's - and runs conv7x7/2 -> BatchNorm -> ReLU ->
+    MaxPool2d(3, 2, 1) as ONE ``torch.autograd.Function`` -> (B, oh, ow, 64) NHWC, what ``ResNetStage`` ('layer1') takes.  SHARES
+    ``conv1`` and ``bn1`` with the backbone they come from.  ``bn`` as in ``ResNetStage``: 'frozen' folds bn1 into scale / shift
+    whatever ``train()`` says; 'batch' with bn1 in ``train()`` normalises with the statistics of the batch, moves the running
+    statistics and ``num_batches_tracked`` and trains gamma / beta.  The images get no gradient.  First derivatives only."""
+
+    def __init__(self, conv1, bn1, bn='frozen'):
+        super().__init__()
+        if bn not in ('frozen', 'batch'):
+            raise ValueError(f"bn = {bn!r}: 'frozen' and 'batch' are built")
+        if tuple(conv1.kernel_size) != (7, 7) or tuple(conv1.stride) != (2, 2) or tuple(conv1.padding) != (3, 3) or conv1.bias is not None:
+            raise NotImplementedError('the stem built is conv 7x7, stride 2, padding 3 without bias')
+        self.conv1, self.bn1, self.bn = conv1, bn1, bn
+
+    def conv_parameters(self):
+        return [self.conv1.weight]
+
+    def bn_parameters(self):
+        return [self.bn1.weight, self.bn1.bias]
+
+    def forward(self, images):
+        dev = _device_of(images)
+        if images.dim() != 4 or images.shape[1] != self.conv1.in_channels:
+            raise ValueError(f'images must be (B, {self.conv1.in_channels}, H, W) NCHW, got {tuple(images.shape)}')
+        eng = _engine(dev)
+        x = images.detach().float().permute(0, 2, 3, 1).contiguous()
+        w, bn1 = self.conv1.weight, self.bn1
+        if self.bn == 'batch' and bn1.training:
+            step = _bn_step(bn1)
+            if torch.is_grad_enabled() and any(p.requires_grad for p in (w, bn1.weight, bn1.bias)):
+                return _StemBatch.apply(eng, step, x, w, bn1.weight, bn1.bias)
+            y = _conv_bn(eng, x, w.detach(), 2, 3, bn1.weight.detach(), bn1.bias.detach(), step)[1]
+            return eng.maxpool_train_forward(y)[0]
+        fold = _fold_bn(bn1)
+        if torch.is_grad_enabled() and w.requires_grad:
+            return _Stem.apply(eng, fold, x, w)
+        return _stem_frozen_forward(eng, fold, x, w.detach())[2]
+
+
+TRUNK_PARTS = ('stem', 'layer1', 'layer2', 'layer3', 'layer4')
+
+
+class ResNetTrunk(nn.Module):
+    """A Bottleneck trunk trainable from ``first`` upwards: ``forward(images)`` takes (B, 3, H, W) NCHW images and returns the NHWC
+    feature map of layer4.  What lies below ``first`` runs frozen and under ``no_grad`` (``below``: images -> NHWC map, None with a
+    trainable stem), then the trainable stem (``stem``, or None) and the ``ResNetStage``s in ``stages``."""
+
+    def __init__(self, stem, stages, below=None):
+        super().__init__()
+        if (stem is None) == (below is None):
+            raise ValueError('a trunk has a trainable stem or a frozen part below its first stage, not both and not neither')
+        self.stem = stem
+        self.stages = nn.ModuleList(stages)
+        self._below = below
+
+    @classmethod
+    def from_model(cls, net, first='layer4', bn='frozen', cut_trunk=None):
+        """The trunk of ``net`` (a ``spec_amd.modules.CameraRegressorNetwork`` or ``HMR`` on a Bottleneck ResNet) trainable from
+        ``first`` ('stem', 'layer1' .. 'layer4') upwards, SHARING the backbone's modules and Parameters as ``ResNetStage.from_model``
+        does.  Below ``first``: ``Engine.trunk(images, stages=k)`` of the committed network for 'layer2' and above; for 'layer1' the
+        stem's own frozen path (``ResNetStem`` on the folded bn1) without gradients.  ``cut_trunk``: a callable (images, k) -> the NHWC
+        map behind layer k that replaces ``Engine.trunk(images, stages=k)`` for 'layer2' and above, e.g. one that runs it in
+        sub-batches (``camcalib_train.trunk_features``); the frozen stem below 'layer1' always takes the batch whole."""
+        from .modules import ResNet50Params
+        if first not in TRUNK_PARTS:
+            raise ValueError(f'{first!r} is not a part of the trunk: {TRUNK_PARTS}')
+        backbone = getattr(net, 'backbone', None)
+        if not isinstance(backbone, ResNet50Params):
+            raise NotImplementedError(f'ResNetTrunk is built for the Bottleneck trunks (ResNet-50 / 101 / 152), not for {type(backbone).__name__}')
+        k = TRUNK_PARTS.index(first)
+        stem = below = None
+        if k == 0:
+            stem = ResNetStem(backbone.conv1, backbone.bn1, bn)
+        elif k == 1:
+            frozen = ResNetStem(backbone.conv1, backbone.bn1, 'frozen')
+            below = lambda images: frozen(images)
+        else:
+            cut = cut_trunk if cut_trunk is not None else (lambda images, n: net.engine(images.device).trunk(images, stages=n))
+            below = lambda images: cut(images, k - 1)
+        return cls(stem, [ResNetStage(getattr(backbone, n), bn) for n in TRUNK_PARTS[max(k, 1):]], below)
+
+    def conv_parameters(self):
+        """The conv weights of the trainable part, the stem's first: what an optimiser is given."""
+        return (self.stem.conv_parameters() if self.stem is not None else []) + [p for st in self.stages for p in st.conv_parameters()]
+
+    def bn_parameters(self):
+        """gamma and beta of the trainable part's BatchNorms (given to the optimiser with ``bn='batch'``)."""
+        return (self.stem.bn_parameters() if self.stem is not None else []) + [p for st in self.stages for p in st.bn_parameters()]
+
+    def trained_modules(self):
+        """The backbone modules of the trainable part: what ``bn='batch'`` puts in ``train()``."""
+        return ([self.stem.bn1] if self.stem is not None else []) + [st.blocks for st in self.stages]
+
+    def forward(self, images):
+        if self.stem is not None:
+            x = self.stem(images)
+        else:
+            with torch.no_grad():
+                x = self._below(images)
+        for st in self.stages:
+            x = st(x)
+        return x

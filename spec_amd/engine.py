@@ -1670,11 +1670,21 @@ class Engine:
             raise ValueError(f'x must be (B, H, W, Cin) NHWC and w (Cout, Cin, k, k), got {tuple(x.shape)} and {tuple(w.shape)}')
         B, H, W, Cin = x.shape
         Cout, _, k, _ = w.shape
-        if (k, pad) not in ((1, 0), (3, 1)) or stride not in (1, 2):
-            raise ValueError(f'the layers built are 1x1 pad 0 and 3x3 pad 1 at stride 1 or 2, got k = {k}, pad = {pad}, stride = {stride}')
+        if not (((k, pad) in ((1, 0), (3, 1)) and stride in (1, 2)) or (k, pad, stride) == (7, 3, 2)):
+            raise ValueError(f'the layers built are 1x1 pad 0 and 3x3 pad 1 at stride 1 or 2 and 7x7 pad 3 at stride 2, got k = {k}, pad = {pad}, '
+                             f'stride = {stride}')
         if tuple(scale.shape) != (Cout,):
             raise ValueError(f'scale must be ({Cout},), got {tuple(scale.shape)}')
         return x, w, scale, B, H, W, Cin, Cout, k, (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+
+    def conv2d_wgrad_splits(self, B, H, W, Cin, Cout, k, stride, pad):
+        """``specmi_conv2d_wgrad_splits``: the number of splits S of the weight gradient's contraction at this layer shape (1 = one
+        launch); a function of the shape alone."""
+        s = C.c_int(0)
+        if self.lib.specmi_conv2d_wgrad_splits(B, H, W, Cin, Cout, k, k, stride, pad, C.byref(s)) != 0:
+            raise ValueError(f'not a layer the trainable conv builds: B = {B}, H = {H}, W = {W}, Cin = {Cin}, Cout = {Cout}, k = {k}, '
+                             f'stride = {stride}, pad = {pad}')
+        return s.value
 
     def conv2d_train_forward(self, x, w, scale, shift, stride, pad, residual=None, relu=True):
         """``specmi_conv2d_train_forward``: y = act(conv(x, w) * scale + shift [+ residual]) with x (B, H, W, Cin) NHWC, w torch's
@@ -1851,6 +1861,33 @@ class Engine:
         out = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc, device=self.device, dtype=torch.float32)
         _lib.check(self.h, self.lib.specmi_maxpool3x3s2(self.h, _ptr(x), B, H, W, Cc, _ptr(out), self._stream()))
         return out
+
+    def maxpool_train_forward(self, x):
+        """``specmi_maxpool3x3s2_train_forward``: MaxPool2d(3, 2, 1) of x (B, H, W, C) NHWC fp32 -> (y (B, OH, OW, C), idx uint8 of y's
+        shape: the winning tap ky * 3 + kx, torch's tie and NaN rule)."""
+        x = _dev_f32(x, self.device)
+        if x.dim() != 4 or not x.numel():
+            raise ValueError(f'x must be (B, H, W, C) NHWC with every dimension >= 1, got {tuple(x.shape)}')
+        B, H, W, Cc = x.shape
+        y = self._empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cc)
+        idx = torch.empty(y.shape, device=self.device, dtype=torch.uint8)
+        _lib.check(self.h, self.lib.specmi_maxpool3x3s2_train_forward(self.h, _ptr(x), B, H, W, Cc, _ptr(y), _ptr(idx), self._stream()))
+        return y, idx
+
+    def maxpool_backward(self, g_y, idx, H, W):
+        """``specmi_maxpool3x3s2_backward``: g_y (B, OH, OW, C) and the forward's idx -> g_x (B, H, W, C), H and W the forward's input
+        extents ((H - 1) // 2 + 1 == OH); every element is written, pixels that never won are exactly zero."""
+        g = _dev_f32(g_y, self.device)
+        _dev_tensor('idx', idx, torch.uint8, self.device)
+        if g.dim() != 4 or not g.numel() or idx.shape != g.shape or not idx.is_contiguous():
+            raise ValueError(f'g_y must be (B, OH, OW, C) with every dimension >= 1 and idx a dense uint8 tensor of its shape, got '
+                             f'{tuple(g.shape)} and {tuple(idx.shape)}')
+        B, OH, OW, Cc = g.shape
+        if H < 1 or W < 1 or ((H - 1) // 2 + 1, (W - 1) // 2 + 1) != (OH, OW):
+            raise ValueError(f'an input of {H} x {W} pools to {(H - 1) // 2 + 1} x {(W - 1) // 2 + 1}, not to {OH} x {OW}')
+        g_x = self._empty(B, H, W, Cc)
+        _lib.check(self.h, self.lib.specmi_maxpool3x3s2_backward(self.h, _ptr(g), _ptr(idx), B, H, W, Cc, _ptr(g_x), self._stream()))
+        return g_x
 
     def maxpool_f16(self, x):
         """MaxPool2d(3, 2, 1) of the fp16 trunk (tests).  x (B,H,W,C) fp16 NHWC device tensor, C % 8 == 0."""
